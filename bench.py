@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the WHENet HIP path on MI355X -- prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype f16|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype f16|f32] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (uint8 crops resident in HBM -> yaw/pitch/roll,
 argmax, logits) over one batch of B synthetic crops per GPU.  Default workload:
@@ -16,14 +16,24 @@ GPU.  A forward is a chain of 46-51 dependent kernel launches (about half of a b
 launch latency), so a serving process keeps a few independent batches in flight; the library does
 that with engine option "inflight" (n engines behind one handle, round-robin, every forward in
 flight writes its own output buffers).  All K forwards complete inside the timed region (handle sync
-+ torch.cuda.synchronize() + barrier on both sides).  `serial_schedule` carries the same K steps
++ torch.cuda.synchronize() + barrier on both sides).  With --full, `serial_schedule` carries the same K steps
 run strictly one after the other (--inflight 1) for reference.
 
-Short timed regions: when the K timed steps take less than 200 ms (the driver runs --steps 20 --warmup 5: ~10 ms),
-the K-step region is repeated (each repeat again bracketed by sync + barrier) until ~0.3 s have been timed;
-`ms_per_step` / `value` are the MEDIAN repeat, every repeat is listed in `repeats_ms_per_step` (`steps` stays K).
+A plain run does only what the headline needs: set-up, W warmup steps, ONE timed region of exactly K steps, the
+outputs (--dump-outputs) and the JSON line with `metric`, `value` (crops/s), `unit`, `higher_is_better`, `dtype` and
+`ms_per_step` (timed region / K); `config.per_rank_crops_s` / `world_size` / `backend`: what each rank did on its
+own clock, the RCCL world.
 
-Extra objects on the line:
+--dump-outputs DIR: after the timed region, what the last timed step returned -- `ypr.npy` (yaw, pitch, roll [B,3]),
+`argmax.npy` (bin indices [B,3]) and `logits.npy` ([B,252]), float32, `rank<r>_` in front with --gpus N > 1.  Inputs are
+seeded (synthetic snapshot seed 1234, crops seed = rank), so two builds can be compared output for output.  Above 64 MB
+in all, a fixed seeded sample of rows is written, with their indices in `rows.npy`.
+
+--full: everything else, as listed below.  Short timed regions: with --full, when the K timed steps take less than
+200 ms, the K-step region is repeated (each repeat again bracketed by sync + barrier) until ~0.3 s have been timed;
+`ms_per_step` / `value` are then the MEDIAN repeat, every repeat is listed in `repeats_ms_per_step` (`steps` stays K).
+
+Extra objects on the line (--full only):
   sweep         the other north-star batch sizes in f16 -- 1, 8, 512 crops per step -- and the f32 parity configuration at batch
                 64 (`f32_b64`), ~0.1 s each: `value` (3 forwards in flight), `value_serial`, and the dominant kernel's roofline
                 fraction at that batch (for the crops per launch whenet_profile() reports)
@@ -43,7 +53,8 @@ Extra objects on the line:
   yolo_postprocess  §8f row 4: whenet_yolo_eval on one 416x416 detector output, per call, host to host
   serial_schedule the timed region with one forward at a time (also as top-level `value_serial` /
                 `ms_per_step_serial`)
-  config.per_rank_crops_s / world_size / backend   what each rank did on its own clock, the RCCL world
+  check         the batch's angles / argmax against the float64 oracle (and, at f16, the two parity-grade
+                configurations on the same crops); every in-flight slot must hold the same bits, N=1 only
 
 --strong: a fixed global batch (--global-batch, default 512) split over the ranks ("scaling": "strong");
 the default is weak scaling (the same --batch on every rank).
@@ -98,9 +109,36 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
     ap.add_argument("--dump-layers", default="", help="write the per-launch profile (JSON) to this path")
     ap.add_argument("--no-sweep", action="store_true", help="skip the batch 1 / 8 / 512 sweep")
-    ap.add_argument("--no-repeat", action="store_true", help="time the K steps once even if that is < 200 ms")
+    ap.add_argument("--no-repeat", action="store_true", help="with --full: time the K steps once even if that is < 200 ms")
     ap.add_argument("--check-crops", type=int, default=16, help="crops of the batch compared with the float64 oracle")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the serial schedule, repeats of short regions, per-kernel roofline, oracle check, latency, "
+                         "frame / PCIe / drop-in / YOLO legs, sweep and CPU baseline (a plain run: the headline alone)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays, prefix: str = "", limit: int = DUMP_LIMIT_BYTES):
+    """arrays: [(name, 2-D array)] with the same rows.  Writes DIR/<prefix><name>.npy as float32; when they exceed
+    `limit` bytes in all, a fixed seeded sample of rows (the same in every run), their indices in <prefix>rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    n = arrays[0][1].shape[0]
+    row_bytes = sum(a.shape[1] for _, a in arrays) * 4
+    rows = None
+    if n * row_bytes > limit:
+        keep = limit // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        np.save(os.path.join(dirname, f"{prefix}rows.npy"), rows.astype(np.float64))
+    for name, a in arrays:
+        a = np.asarray(a).astype(np.float32)
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), a if rows is None else a[rows])
 
 
 def relaunch(args) -> int:
@@ -736,13 +774,13 @@ def main():
         def step(i):
             y, a, l = outs[i % nslots]
             h.forward_device(d_crops.data_ptr(), B, y.data_ptr(), a.data_ptr(), l.data_ptr())
-        return timed_steps(step, h.sync, comm, args.steps, args.warmup, args.no_repeat)
+        return timed_steps(step, h.sync, comm, args.steps, args.warmup, args.no_repeat or not args.full)
 
     total_per_step = args.global_batch if args.strong else world * B      # crops all ranks process per step
 
     serial = None
     if M > 1:
-        if not args.no_serial:
+        if args.full and not args.no_serial:
             # the strictly serial schedule first (one forward at a time, 2 sub-batch lanes), for reference
             r1 = reduce_runs(timed(1), comm, B, total_per_step, args.steps)
             serial = {"value": r1["value"], "ms_per_step": r1["el"] / args.steps * 1e3, "in_flight": 1,
@@ -752,37 +790,44 @@ def main():
             h.set_option("lanes", args.lanes)
     res = reduce_runs(timed(M), comm, B, total_per_step, args.steps)
     el, els, value = res["el"], res["els"], res["value"]
+    if args.dump_outputs:
+        # what the caller of the timed path received from its last step (every timed step writes slot i % M)
+        y, a, l = outs[(args.steps - 1) % M]
+        dump_outputs(args.dump_outputs, [("ypr", y.cpu().numpy()), ("argmax", a.cpu().numpy()), ("logits", l.cpu().numpy())],
+                     prefix="" if world == 1 else f"rank{rank}_", limit=DUMP_LIMIT_BYTES // world)
 
-    # ---- per-kernel roofline (HIP events around every launch, same stream, eager) ----------
-    stats = h.profile(d_crops.data_ptr(), B, args.profile_iters)
-    if args.dump_layers and rank == 0:
-        with open(args.dump_layers, "w") as f:
-            json.dump({"batch": B, "dtype": args.dtype, "launches": stats}, f, indent=1)
-    # A launch's figure is the event-to-event time on the chain's stream.  Back-to-back launches pipeline, so for
-    # a real kernel that IS its duration as rocprofv3's hardware timestamps report it (profiles/: the
-    # kernel-trace averages agree within a few %); only for an EMPTY kernel is the ~2-9 us event/dispatch gap
-    # exposed.  The chain's last entry is such an empty kernel: reported as `boundary_us`, never subtracted.
-    crops_per_launch, chains = stats[0]["crops"], stats[0]["chains"]     # what whenet_profile() actually ran
-    stats, by_kernel, dom_name, dom, roofline, boundary_us = summarise_profile(stats)
-    for st in stats:
-        st["raw_us"] = st["avg_us"]
-    # HBM traffic of that kernel from the PMC counters (FETCH_SIZE / WRITE_SIZE, collected in separate
-    # rocprofv3 --pmc passes of this same command and committed under profiles/): per launch, bytes
-    traffic, traffic_source, pmc_extra = pmc_traffic(args.dtype, B, crops_per_launch, dom_name, dom["layer"])
-    roofline.update({"traffic": traffic, "traffic_source": traffic_source, "pmc": pmc_extra,
-                "traffic_over_alg_bytes": (traffic / roofline["alg_bytes_per_launch"]) if traffic else None,
-                "crops_per_launch": crops_per_launch, "chains_profiled": chains,
-                "method": "one hipEvent between consecutive launches on the chain's stream; one forward of the batch "
-                          "alone on the GPU (eager pass right after the timed region), as rocprofv3's kernel trace "
-                          "sees it; the timed region overlaps `forwards_in_flight` such chains",
-                "empty_kernel_event_to_event_us": boundary_us,
-                "chain_us_per_step": sum(st["raw_us"] for st in stats),
-                "by_kernel": {k: {"us": round(v["us"], 2), "launches": v["launches"],
-                                  "GBps": round(v["bytes"] / (v["us"] * 1e-6) / 1e9, 1),
-                                  "TFLOPs": round(v["flops"] / (v["us"] * 1e-6) / 1e12, 2),
-                                  "valu_frac": (round(v["swish"] / 64.0 * SWISH_CYCLES_PER_WAVE_VALUE / SIMDS /
-                                                      (SHADER_GHZ * 1e3) / v["us"], 3) if v["swish"] > 0 else None)}
-                              for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1]["us"])}})
+    roofline = None
+    if args.full:
+        # ---- per-kernel roofline (HIP events around every launch, same stream, eager) ----------
+        stats = h.profile(d_crops.data_ptr(), B, args.profile_iters)
+        if args.dump_layers and rank == 0:
+            with open(args.dump_layers, "w") as f:
+                json.dump({"batch": B, "dtype": args.dtype, "launches": stats}, f, indent=1)
+        # A launch's figure is the event-to-event time on the chain's stream.  Back-to-back launches pipeline, so for
+        # a real kernel that IS its duration as rocprofv3's hardware timestamps report it (profiles/: the
+        # kernel-trace averages agree within a few %); only for an EMPTY kernel is the ~2-9 us event/dispatch gap
+        # exposed.  The chain's last entry is such an empty kernel: reported as `boundary_us`, never subtracted.
+        crops_per_launch, chains = stats[0]["crops"], stats[0]["chains"]     # what whenet_profile() actually ran
+        stats, by_kernel, dom_name, dom, roofline, boundary_us = summarise_profile(stats)
+        for st in stats:
+            st["raw_us"] = st["avg_us"]
+        # HBM traffic of that kernel from the PMC counters (FETCH_SIZE / WRITE_SIZE, collected in separate
+        # rocprofv3 --pmc passes of this same command and committed under profiles/): per launch, bytes
+        traffic, traffic_source, pmc_extra = pmc_traffic(args.dtype, B, crops_per_launch, dom_name, dom["layer"])
+        roofline.update({"traffic": traffic, "traffic_source": traffic_source, "pmc": pmc_extra,
+                    "traffic_over_alg_bytes": (traffic / roofline["alg_bytes_per_launch"]) if traffic else None,
+                    "crops_per_launch": crops_per_launch, "chains_profiled": chains,
+                    "method": "one hipEvent between consecutive launches on the chain's stream; one forward of the batch "
+                              "alone on the GPU (eager pass right after the timed region), as rocprofv3's kernel trace "
+                              "sees it; the timed region overlaps `forwards_in_flight` such chains",
+                    "empty_kernel_event_to_event_us": boundary_us,
+                    "chain_us_per_step": sum(st["raw_us"] for st in stats),
+                    "by_kernel": {k: {"us": round(v["us"], 2), "launches": v["launches"],
+                                      "GBps": round(v["bytes"] / (v["us"] * 1e-6) / 1e9, 1),
+                                      "TFLOPs": round(v["flops"] / (v["us"] * 1e-6) / 1e12, 2),
+                                      "valu_frac": (round(v["swish"] / 64.0 * SWISH_CYCLES_PER_WAVE_VALUE / SIMDS /
+                                                          (SHADER_GHZ * 1e3) / v["us"], 3) if v["swish"] > 0 else None)}
+                                  for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1]["us"])}})
 
     out = {
         "metric": "head crops/sec (224x224)", "value": value, "unit": "crops/s", "n_gpus": world,
@@ -815,7 +860,6 @@ def main():
                                 f"{M} engines round-robin, own streams/arena/graphs, one chain each); ms_per_step = "
                                 "timed region / K, not the latency of one forward") if M > 1 else
                                "one forward at a time, up to 2 concurrent sub-batch chains inside it"},
-        "roofline": roofline,
         "serial_schedule": serial,
         "path_fraction": {"per_gpu_crops_s": value / world,
                           "vs_layer_granular_bound": value / world / PATH_BOUND_CROPS_S["layer_granular"],
@@ -823,7 +867,9 @@ def main():
                           "bounds_crops_s": PATH_BOUND_CROPS_S},
     }
 
-    if rank == 0 and world == 1:
+    if roofline is not None:
+        out["roofline"] = roofline
+    if args.full and rank == 0 and world == 1:
         # correctness spot check against the float64 oracle (outside every timed region)
         from oracle import whenet_oracle as O
         nchk = max(1, min(args.check_crops, B))
@@ -865,7 +911,7 @@ def main():
                 par[name] = {"max_abs_deg_vs_f64_oracle": float(e.max()), "mean_abs_deg": float(e.mean()), "argmax_flips": fl,
                              "meets_north_star_parity": bool(e.max() <= 1e-3 and fl == 0)}
             out["check"]["parity_configurations"] = par
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         # configs[1]: batch=1 fp32 latency
         h1 = _lib.Handle(blob, device=local_rank, dtype=_lib.F32)
         lat = []
@@ -899,7 +945,7 @@ def main():
         # the drop-in class on the reference's call shapes (B=1 wall latency; one 512-crop call), never `value`
         out["dropin"] = dropin_leg(blob, local_rank)
         out["yolo_postprocess"] = yolo_leg(h)
-    if rank == 0 and world == 1 and not distributed and not args.no_sweep and args.dtype == "f16" and B == 64 and not args.strong:
+    if args.full and rank == 0 and world == 1 and not distributed and not args.no_sweep and args.dtype == "f16" and B == 64 and not args.strong:
         out["sweep"] = sweep_leg(blob, local_rank, dev, args.lanes)
     if "sweep" in out:
         # the parity-grade figure as a first-class number: the faster of the two float32-storage configurations (both hold the
@@ -916,7 +962,7 @@ def main():
     elif out.get("value_serial") is not None:
         out["config"]["workload"] += (f"; value = {M} forwards of the batch in flight ({value:.0f} crops/s), value_serial = one forward at a "
                                       f"time ({out['value_serial']:.0f} crops/s)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     h.close()
     if rank == 0:

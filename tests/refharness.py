@@ -311,9 +311,11 @@ def reference(backbone_fn=None, load_weights=None, compute_dtype=np.float64, nms
     saved = {n: sys.modules.get(n) for n in set(names) | set(mods)}
     saved_path = list(sys.path)
     saved_state = dict(_STATE)
+    saved_bytecode = sys.dont_write_bytecode
     _STATE["load_weights"] = load_weights
     _STATE["compute_dtype"] = compute_dtype
     try:
+        sys.dont_write_bytecode = True          # the reference tree is read, never written (no __pycache__ next to it)
         for n in names:
             sys.modules.pop(n, None)
         sys.modules.update(mods)
@@ -332,6 +334,7 @@ def reference(backbone_fn=None, load_weights=None, compute_dtype=np.float64, nms
 
         yield types.SimpleNamespace(cv2=cv2, tf=mods["tensorflow"], load=load, dir=REF)
     finally:
+        sys.dont_write_bytecode = saved_bytecode
         sys.path[:] = saved_path
         for n, m in saved.items():
             if m is None:

@@ -116,6 +116,24 @@ def test_single_process_comm_is_a_no_op_group():
     assert r["per_rank_crops"] == [8] and r["value"] > 0
 
 
+def test_dump_outputs_writes_float32_and_a_fixed_sample_above_the_limit(tmp_path):
+    import numpy as np
+    bench = _bench()
+    ypr = np.arange(300, dtype=np.float32).reshape(100, 3)
+    am = np.arange(300, dtype=np.int32).reshape(100, 3) % 120
+    bench.dump_outputs(str(tmp_path / "all"), [("ypr", ypr), ("argmax", am)])
+    assert np.array_equal(np.load(tmp_path / "all" / "ypr.npy"), ypr)
+    a = np.load(tmp_path / "all" / "argmax.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, am) and not (tmp_path / "all" / "rows.npy").exists()
+    for k in ("s1", "s2"):                                  # 24 bytes per row + 8 for its index: 10 rows fit in 320
+        bench.dump_outputs(str(tmp_path / k), [("ypr", ypr), ("argmax", am)], prefix="rank0_", limit=320)
+    rows = np.load(tmp_path / "s1" / "rank0_rows.npy")
+    assert len(rows) == 10 and np.array_equal(rows, np.load(tmp_path / "s2" / "rank0_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "rank0_ypr.npy"), ypr[rows.astype(int)])
+    total = sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in os.listdir(tmp_path / "s1"))    # less the .npy headers
+    assert total <= 320
+
+
 def test_pmc_traffic_refuses_a_different_launch_geometry(tmp_path, monkeypatch):
     """roofline.traffic is only printed for a PMC set collected at the profiled launch's crops per launch."""
     import json

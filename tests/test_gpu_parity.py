@@ -983,7 +983,7 @@ def test_bench_distributed_path_one_rank():
     env = dict(os.environ, WHENET_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+    base = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
             "--no-latency", "--no-sweep", "--profile-iters", "2"]
     for extra, scaling, gb in (([], "weak", 64), (["--strong", "--global-batch", "512"], "strong", 512)):
         r = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=600)
@@ -993,3 +993,31 @@ def test_bench_distributed_path_one_rank():
         assert line["scaling"] == scaling and line["config"]["global_batch"] == gb
         assert len(line["config"]["per_rank_crops_s"]) == 1 and line["value"] > 0 and line["n_gpus"] == 1
         assert line["steps"] == 5 and line["warmup"] == 2 and "roofline" in line
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_outputs(tmp_path):
+    """A plain bench run: one region of exactly --steps timed steps, the headline keys, none of the --full legs, and
+    --dump-outputs writes what the last timed step returned (float32), equal to a forward of the same seeded crops."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["repeats"] == 1 and line["dtype"] == "f16"
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 64) < 1e-6 * 64
+    for k in ("roofline", "check", "sweep", "cpu_baseline", "latency_b1", "frame_pipeline"):
+        assert k not in line, k
+    got = {n: np.load(d / f"{n}.npy") for n in ("ypr", "argmax", "logits")}
+    assert {n: a.shape for n, a in got.items()} == {"ypr": (64, 3), "argmax": (64, 3), "logits": (64, 252)}
+    assert all(a.dtype == np.float32 for a in got.values())
+    crops = synth.noise_crops(64, seed=0)
+    with _lib.Handle(W.pack(W.synthetic(1234)), device=0, dtype=_lib.F16) as h:
+        y, am, lg = h.forward(crops)
+    assert np.abs(got["ypr"] - y).max() <= 1e-3 and np.abs(got["logits"] - lg).max() <= 1e-3
+    assert np.array_equal(got["argmax"], am.astype(np.float32))

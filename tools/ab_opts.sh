@@ -6,7 +6,7 @@ for round in 1 2; do
 for SET in "$@"; do
   OPTS=""
   if [ "$SET" != "-" ]; then for kv in $SET; do OPTS="$OPTS --opt $kv"; done; fi
-  python bench.py --dtype $DT --batch $B --no-cpu-baseline --no-latency --no-sweep $OPTS 2>/dev/null | python -c "
+  python bench.py --full --dtype $DT --batch $B --no-cpu-baseline --no-latency --no-sweep $OPTS 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$DT b$B [$SET] round $round: value %.0f  serial %.0f' % (d['value'], d.get('value_serial') or 0))"

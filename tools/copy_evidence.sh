@@ -1,6 +1,6 @@
 #!/bin/bash
-# gpurun_out/final (tools/final_round.sh on the GPU box) -> profiles/rNN; prints the numbers the docs quote
-R=$(cd "$(dirname "$0")/.." && pwd); RND=${RND:-r06}; F=$R/gpurun_out/final; P=$R/profiles/$RND
+# $OUT/final (tools/final_round.sh on the GPU box; default out/final) -> profiles/rNN; prints the numbers the docs quote
+R=$(cd "$(dirname "$0")/.." && pwd); RND=${RND:-r06}; F=${OUT:-$R/out}/final; P=$R/profiles/$RND
 cp $F/bench_default.json $F/bench_driver_args.json $F/bench_f16_b1.json $F/bench_f16_b8.json $F/bench_f16_b512.json $F/bench_f32_b64.json \
    $F/layers_default.json $F/layers_f32_b64.json $F/smoke.txt $F/diag.txt $F/f16_error_gpu.txt $F/rocprof_bench.json \
    $F/pmc_f16_b64_c64_by_kernel.txt $F/pmc_f16_b64_c32_by_kernel.txt $F/pmc_f32_b64_c64_by_kernel.txt $F/pmc_traffic_f16_b64.json $F/pmc_traffic_f32_b64.json $P/
@@ -22,8 +22,9 @@ import json,sys,collections
 P=sys.argv[1]
 def last(f): return json.loads(open(P+'/'+f).read().strip().splitlines()[-1])
 for f in ["bench_default.json","bench_driver_args.json","bench_f32_b64.json","bench_f16_b512.json","bench_f16_b8.json","bench_f16_b1.json","rocprof_bench.json"]:
-    d=last(f); r=d["roofline"]
-    print(f, "value %.0f serial %.0f ms %.4f / %.4f"%(d["value"],d.get("value_serial") or 0,d["ms_per_step"],d.get("ms_per_step_serial") or 0), "| dom", r["kernel"][:44], "us %.2f frac %.3f traffic %s"%(r["avg_launch_us"],r["frac"],r.get("traffic")))
+    d=last(f); r=d.get("roofline")      # a plain run (the driver's command line) carries no roofline
+    print(f, "value %.0f serial %.0f ms %.4f / %.4f"%(d["value"],d.get("value_serial") or 0,d["ms_per_step"],d.get("ms_per_step_serial") or 0),
+          *(("| dom", r["kernel"][:44], "us %.2f frac %.3f traffic %s"%(r["avg_launch_us"],r["frac"],r.get("traffic"))) if r else ()))
 d=last("bench_default.json")
 print("   sweep",{k:(round(v["value"]),round(v["value_serial"])) for k,v in d["sweep"].items() if isinstance(v,dict)})
 print("   latency",d["latency_b1"]); print("   cpu",d["cpu_baseline"]["value"],d["cpu_baseline"]["single_process"]["value"]); print("   pcie",d["pcie_inclusive"])

@@ -2,6 +2,8 @@
 # PMC counter passes (separate passes; rocprofv3 --pmc must not be combined with tracing other
 # than --kernel-trace).  Usage: bash tools/pmc_round.sh <dtype> <batch> [crops_per_launch]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-$R/out}              # where the counter passes and the launch list go
+mkdir -p $OUT
 DT=${1:-f16}; B=${2:-64}
 cd /tmp && export TMPDIR=/tmp
 # The counters are device-wide between a kernel's start and end: with several sub-batch chains (lanes) running side
@@ -14,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 # traffic JSON and bench.py only prints a traffic figure whose crops per launch equal the profiled launch's.
 LB=${3:-$B}
 # (--dump-layers: the chain's launch list of THIS command, which tools/pmc_summary.py uses to name every dispatch's layer)
-CMD="python $R/bench.py --dtype $DT --batch $LB --lanes 1 --inflight 1 --steps 2 --warmup 1 --no-cpu-baseline --no-latency --no-serial --no-sweep --no-repeat --profile-iters 1 --no-graph --opt concurrent=1 --dump-layers $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_layers.json $PMC_EXTRA"
+CMD="python $R/bench.py --full --dtype $DT --batch $LB --lanes 1 --inflight 1 --steps 2 --warmup 1 --no-cpu-baseline --no-latency --no-serial --no-sweep --no-repeat --profile-iters 1 --no-graph --opt concurrent=1 --dump-layers $OUT/pmc_${DT}_b${B}_c${LB}_layers.json $PMC_EXTRA"
 i=0
 for PMC in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT" \
            "FETCH_SIZE GRBM_GUI_ACTIVE" \
@@ -23,11 +25,11 @@ for PMC in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
            "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TA_BUSY_avr TCP_PENDING_STALL_CYCLES_sum" \
            "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_BUSY_CU_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  rm -rf $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_p$i
-  timeout 400 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_p$i -o p -- $CMD > $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_p$i.log 2>&1
+  rm -rf $OUT/pmc_${DT}_b${B}_c${LB}_p$i
+  timeout 400 rocprofv3 --kernel-trace --pmc $PMC --output-format csv -d $OUT/pmc_${DT}_b${B}_c${LB}_p$i -o p -- $CMD > $OUT/pmc_${DT}_b${B}_c${LB}_p$i.log 2>&1
   rc=$?
   # (exit 1 with a complete counter_collection.csv: the profiled command's own exit code -- see the log tail)
-  echo "pmc pass $i ($PMC) exit $rc; csv rows: $(cat $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_p$i/*counter_collection.csv 2>/dev/null | wc -l)"
-  tail -3 $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_p$i.log | cut -c1-300
+  echo "pmc pass $i ($PMC) exit $rc; csv rows: $(cat $OUT/pmc_${DT}_b${B}_c${LB}_p$i/*counter_collection.csv 2>/dev/null | wc -l)"
+  tail -3 $OUT/pmc_${DT}_b${B}_c${LB}_p$i.log | cut -c1-300
 done
-ls $R/gpurun_out/pmc_${DT}_b${B}_c${LB}_p1
+ls $OUT/pmc_${DT}_b${B}_c${LB}_p1
