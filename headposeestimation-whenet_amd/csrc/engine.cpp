@@ -1014,19 +1014,21 @@ hipGraphExec_t Engine::cached_graph(const GraphKey& key, hipStream_t s, F&& fn) 
     return exec;
 }
 
+// debug option "poison": every activation buffer holds NaN bit patterns when the forward starts, so a kernel that reads what no
+// kernel of THIS forward wrote shows up in the results (tests/test_gpu_parity.py)
+void Engine::poison_arena(int n, hipStream_t s) {
+    const size_t N = size_t(n), es = esz();
+    WHENET_HIP_CHECK(hipMemsetAsync(x0_, 0xff, N * X_ELEMS * es, s));
+    WHENET_HIP_CHECK(hipMemsetAsync(x1_, 0xff, N * X_ELEMS * es, s));
+    WHENET_HIP_CHECK(hipMemsetAsync(e_, 0xff, N * E_ELEMS * es, s));
+    WHENET_HIP_CHECK(hipMemsetAsync(d_, 0xff, N * D_ELEMS * es, s));
+    WHENET_HIP_CHECK(hipMemsetAsync(hc_, 0xff, N * HC_ELEMS * es, s));
+    WHENET_HIP_CHECK(hipMemsetAsync(partial_, 0xff, N * partial_per_crop_ * sizeof(float), s));
+    WHENET_HIP_CHECK(hipMemsetAsync(gate_, 0xff, N * 1152 * sizeof(float), s));
+}
+
 void Engine::run_forward(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want) {
-    if (poison_) {
-        // debug option "poison": every activation buffer holds NaN bit patterns when the forward starts, so a kernel
-        // that reads what no kernel of THIS forward wrote shows up in the results (tests/test_gpu_parity.py)
-        const size_t N = size_t(n), es = esz();
-        WHENET_HIP_CHECK(hipMemsetAsync(x0_, 0xff, N * X_ELEMS * es, s));
-        WHENET_HIP_CHECK(hipMemsetAsync(x1_, 0xff, N * X_ELEMS * es, s));
-        WHENET_HIP_CHECK(hipMemsetAsync(e_, 0xff, N * E_ELEMS * es, s));
-        WHENET_HIP_CHECK(hipMemsetAsync(d_, 0xff, N * D_ELEMS * es, s));
-        WHENET_HIP_CHECK(hipMemsetAsync(hc_, 0xff, N * HC_ELEMS * es, s));
-        WHENET_HIP_CHECK(hipMemsetAsync(partial_, 0xff, N * partial_per_crop_ * sizeof(float), s));
-        WHENET_HIP_CHECK(hipMemsetAsync(gate_, 0xff, N * 1152 * sizeof(float), s));
-    }
+    if (poison_) poison_arena(n, s);
     if (!use_graph_) {
         enqueue_lanes(d_in, n, d_ypr, d_amax, d_logits, s, want);
         return;
@@ -1158,6 +1160,10 @@ void Engine::forward_host_f32(const float* x, int n, float* ypr, int32_t* argmax
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&in_f32_), N * IN_BYTES * sizeof(float));
         if (e != hipSuccess) throw Error(WHENET_ENOMEM, std::string("float input buffer: ") + hipGetErrorString(e));
         in_f32_cap_ = n;
+    }
+    if (poison_) {
+        poison_arena(n, stream_);
+        WHENET_HIP_CHECK(hipMemsetAsync(in_f32_, 0xff, size_t(in_f32_cap_) * IN_BYTES * sizeof(float), stream_));
     }
     WHENET_HIP_CHECK(hipMemcpyAsync(in_f32_, x, N * IN_BYTES * sizeof(float), hipMemcpyHostToDevice, stream_));
     enqueue_forward(view(0), nullptr, n, o_ypr_, o_amax_, o_logits_, stream_, nullptr, in_f32_);

@@ -200,6 +200,7 @@ class Engine {
     int lanes_for(int n, int want) const;     // chains a forward of n crops runs as (want = 0: option "lanes")
     void enqueue_lanes(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want = 0);
     void run_forward(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want = 0);
+    void poison_arena(int n, hipStream_t s);        // option "poison": NaN bit patterns in every activation buffer of n crops
     void ensure_slot(Slot& s, int n);
     hipStream_t lane_stream(int i);     // created on first use
     using GraphKey = std::tuple<int, int, const void*, void*, void*, void*>;   // n, lane offset (-L: whole batch as L chains), buffers
@@ -223,7 +224,8 @@ class Engine {
                                 // squeeze-excite launch): 0 = never, 1 = on the blocks where that is faster, 2 = every fused-front block
     int front_impl_ = 1;        // option "front_impl": 0 = front.hip everywhere, 1 = per layer (f16: front2.hip where it is
                                 // the faster kernel), 2 = front2.hip everywhere (f16)
-    bool poison_ = false;       // debug option "poison": NaN-fill the activation arena before every forward
+    bool poison_ = false;       // debug option "poison": NaN-fill the activation arena before every forward (and forward_host_f32's
+                                // input staging buffer before its copy: the copy must cover every byte the forward reads)
     bool head_fuse_ = true;     // option "head_fuse": the head conv pools its own output (head7.hip, f16 and f32); 0 = round 3's two stages
     bool front7_ = true;        // option "front7": blocks 13-16 of an f16 handle run front7.hip (a group of crops per workgroup)
                                 // when front_impl = 1; 0 = the per-layer choice of round 3 (front.hip there)

@@ -26,6 +26,7 @@ What each function follows:
                      int(input_filters*0.25) | project 1x1 + BN | identity skip when
                      stride 1 and in==out; DropConnect is identity at inference);
                      head Conv1x1(1280) + BN + Swish.   
+  block()            one MBConvBlock of the above on any input of its shape (backbone() chains them)
   heads()            whenet.py:9-13  GlobalAveragePooling2D + Dense 120/66/66 (linear)
   softmax()          /root/reference/utils.py:7-11
   decode()           whenet.py:17-20, 28-33  expectation * 3 - 180 / - 99
@@ -123,6 +124,42 @@ def swish(x: np.ndarray) -> np.ndarray:
 BNHook = Optional[Callable[[str, np.ndarray], None]]
 
 
+def block(x: np.ndarray, w: Dict[str, np.ndarray], index: int, bn_hook: BNHook = None,
+          taps: Optional[Dict[str, np.ndarray]] = None) -> np.ndarray:
+    """MBConv block ``index`` (1..16) on an arbitrary input [N,H,W,Cin] of its shape: expand 1x1 + BN + Swish (blocks
+    2-16), depthwise kxk + BN + Swish, SEBlock, project 1x1 + BN, identity skip.  backbone() chains these; the per-block
+    tests call it on inputs of their own (scaled activations).  ``bn_hook`` / ``taps`` as in backbone()."""
+    b = G.mbconv_blocks()[index - 1]
+    p = f"b{b.number}"
+
+    def bn(t: np.ndarray, prefix: str) -> np.ndarray:
+        if bn_hook is not None:
+            bn_hook(prefix, t)
+        return batchnorm(t, w, prefix)
+
+    def tap(name: str, t: np.ndarray) -> None:
+        if taps is not None:
+            taps[name] = t
+
+    inp = x
+    if b.expands:
+        x = swish(bn(conv2d(x, w[f"{p}/expand/kernel"], 1), f"{p}/expand_bn"))
+        tap(f"{p}/expand", x)
+    x = swish(bn(depthwise(x, w[f"{p}/dw/kernel"], b.stride), f"{p}/dw_bn"))
+    tap(f"{p}/dw", x)
+    # SEBlock: mean over H,W (keepdims) -> conv1x1+bias -> swish -> conv1x1+bias -> sigmoid
+    sq = x.mean(axis=(1, 2), keepdims=True)
+    r = swish(sq @ w[f"{p}/se_reduce/kernel"][0, 0].astype(x.dtype) + w[f"{p}/se_reduce/bias"].astype(x.dtype))
+    g = sigmoid(r @ w[f"{p}/se_expand/kernel"][0, 0].astype(x.dtype) + w[f"{p}/se_expand/bias"].astype(x.dtype))
+    tap(f"{p}/gate", g)
+    x = x * g
+    x = bn(conv2d(x, w[f"{p}/project/kernel"], 1), f"{p}/project_bn")
+    if b.identity_skip:
+        x = x + inp
+    tap(f"{p}/out", x)
+    return x
+
+
 def backbone(x: np.ndarray, w: Dict[str, np.ndarray], bn_hook: BNHook = None,
              taps: Optional[Dict[str, np.ndarray]] = None) -> np.ndarray:
     """[N,224,224,3] normalised -> [N,7,7,1280].  ``bn_hook(prefix, bn_input)`` is called
@@ -133,32 +170,14 @@ def backbone(x: np.ndarray, w: Dict[str, np.ndarray], bn_hook: BNHook = None,
             bn_hook(prefix, t)
         return batchnorm(t, w, prefix)
 
-    def tap(name: str, t: np.ndarray) -> None:
-        if taps is not None:
-            taps[name] = t
-
     x = swish(bn(conv2d(x, w["stem/conv/kernel"], 2), "stem/bn"))
-    tap("stem", x)
+    if taps is not None:
+        taps["stem"] = x
     for b in G.mbconv_blocks():
-        p = f"b{b.number}"
-        inp = x
-        if b.expands:
-            x = swish(bn(conv2d(x, w[f"{p}/expand/kernel"], 1), f"{p}/expand_bn"))
-            tap(f"{p}/expand", x)
-        x = swish(bn(depthwise(x, w[f"{p}/dw/kernel"], b.stride), f"{p}/dw_bn"))
-        tap(f"{p}/dw", x)
-        # SEBlock: mean over H,W (keepdims) -> conv1x1+bias -> swish -> conv1x1+bias -> sigmoid
-        sq = x.mean(axis=(1, 2), keepdims=True)
-        r = swish(sq @ w[f"{p}/se_reduce/kernel"][0, 0].astype(x.dtype) + w[f"{p}/se_reduce/bias"].astype(x.dtype))
-        g = sigmoid(r @ w[f"{p}/se_expand/kernel"][0, 0].astype(x.dtype) + w[f"{p}/se_expand/bias"].astype(x.dtype))
-        tap(f"{p}/gate", g)
-        x = x * g
-        x = bn(conv2d(x, w[f"{p}/project/kernel"], 1), f"{p}/project_bn")
-        if b.identity_skip:
-            x = x + inp
-        tap(f"{p}/out", x)
+        x = block(x, w, b.number, bn_hook, taps)
     x = swish(bn(conv2d(x, w["head/conv/kernel"], 1), "head/bn"))
-    tap("head", x)
+    if taps is not None:
+        taps["head"] = x
     return x
 
 

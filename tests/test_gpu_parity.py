@@ -19,6 +19,8 @@ Tolerances (stated here, per dtype):
        margin is below the measured logit error (the synthetic heads are 3-bin-wide Gaussian bumps:
        neighbouring bins differ by <= 0.38, so f16 may legitimately pick the neighbour) and the
        picked bin is the oracle's runner-up; at most F16_ARGMAX_FLIPS of the 24 may flip.
+  f32s (WHENET_F32S, the drop-in class's default: float32 storage, 1x1 products as binary16 hi/lo pairs) is held to the
+       f32 bars everywhere in this file: the f32 branches of every dtype test, the same per-kernel tolerance.
 """
 import os
 
@@ -36,7 +38,8 @@ F16_DEG = 1.0              # every f16 angle of the small sets; round 3 had wide
 F16_DEG_TAIL = 1.5         # the maximum over the 512-crop set only (1536 draws of the noise's tail; p99.9 is bounded below it)
 F16_ARGMAX_FLIPS = 3
 MARGIN_F32 = 2e-3
-DTYPES = [("f32", _lib.F32), ("f16", _lib.F16)]
+DTYPES = [("f32", _lib.F32), ("f16", _lib.F16), ("f32s", _lib.F32S)]
+F32_NAMES = ("f32", "f32s")       # the dtypes held to the f32 bars
 
 
 @pytest.fixture(scope="module")
@@ -73,9 +76,9 @@ def rel_err(got, ref):
 
 
 def tol(h):
-    # f32: a few 1e-6 measured (tools/gpu_diag.py); f16: 2^-11 input/weight/output roundings
-    # through a k*k*C / K-deep sum, a few 1e-3 .. 1e-2 measured
-    return 2e-5 if h.name == "f32" else 1.5e-2
+    # f32: a few 1e-6 measured (tools/gpu_diag.py); f32s: the same bar (the hi/lo products drop only lo*lo, 2^-22 of each
+    # product); f16: 2^-11 input/weight/output roundings through a k*k*C / K-deep sum, a few 1e-3 .. 1e-2 measured
+    return 2e-5 if h.name in F32_NAMES else 1.5e-2
 
 
 def test_info(handle):
@@ -85,14 +88,20 @@ def test_info(handle):
     # stem, dw(b1), 15 front, 16 se, 16 project, head conv, heads = 51 with option se_fuse=0; by default the project
     # GEMMs of the blocks where it pays compute their squeeze-excite gate themselves (f16: blocks 4-6; f32: by the same
     # rule on front.hip's tile plans); 36 with se_fuse=2 (every block with a fused front kernel)
-    # f16 handles drop block 1's project launch (option fold12: folded into block 2's expand weights)
+    # f16 and f32s handles drop block 1's project launch (option fold12: folded into block 2's expand weights; f32s: front.hip's
+    # split form on block 2, engine.cpp fold12_active)
     assert i.macs_per_crop == spec.TOTAL_MACS and 35 <= i.n_kernels_per_forward <= 50
     # ... and the stem launch (option stem_fuse: computed inside block 1's depthwise kernel, stemdw.hip)
-    folded = 1 if handle.name == "f16" else 0
+    folded = 0 if handle.name == "f32" else 1
     stemdw = 1
     # round 6, option mb7 (off by default): blocks 13-16 of an f16 handle as one launch each instead of front + squeeze-excite + project
     mb = 4 if handle.name == "f16" else 0
+    # option se_fuse = 3: blocks 7-16 compute their gate inside the staged project GEMM -- f16 and f32s, never exact f32
+    mfma = 0 if handle.name == "f32" else 10
+    k1 = i.n_kernels_per_forward
     try:
+        handle.set_option("se_fuse", 3)
+        assert handle.info().n_kernels_per_forward == k1 - mfma
         handle.set_option("se_fuse", 0)
         assert handle.info().n_kernels_per_forward == 51 - folded - stemdw
         handle.set_option("mb7", 1)
@@ -143,7 +152,13 @@ def test_mbconv_block_kernels(handle, taps, index):
     expand+depthwise stage is checked in all its forms: front.hip (option front_impl=0: bitwise the two-launch
     schedule), and for f16 front2.hip (front_impl=2: depthwise taps as Toeplitz products on the matrix cores, f16
     tap weights -- another summation order, so within the kernel tolerance of the oracle) and the default per-layer
-    choice between the two."""
+    choice between the two.
+    f32s: front_impl=0 is front.hip's split form -- PwOps<float, true>::step on the same [hi | lo] weight images, k-steps in
+    the same order from a zero accumulator, the same epilogue as pw.hip's tile kernel -- so its depthwise output is BITWISE
+    the two-launch schedule's, as for f32, and so is the default (front_impl=1: front.hip on blocks 2-12 -- front2s_tuned.inc
+    prefers front2s.hip nowhere -- and front7.hip's split form on 13-16: the same products in the same order, the activations as
+    the A operand).  front_impl=2 is front2s.hip on blocks 2-12 (hi/lo expand with pixels as MFMA rows, Toeplitz taps: another
+    summation order): held to the tolerance."""
     b = spec.blocks()[index - 1]
     x = taps["stem"] if index == 1 else taps[f"b{index - 1}/out"]
     t = tol(handle)
@@ -159,7 +174,7 @@ def test_mbconv_block_kernels(handle, taps, index):
         assert rel_err(r0["expand"], taps[f"{p}/expand"]) < t, "expand"
         assert rel_err(r0["dw"], taps[f"{p}/dw"]) < 2 * t, "dw (unfused)"
         assert rel_err(r0["out"], taps[f"{p}/out"]) < 3 * t, "out (unfused)"
-    impls = (0, 2, 1) if (b.has_expand and handle.name == "f16") else (1,)
+    impls = (0, 2, 1) if (b.has_expand and handle.name in ("f16", "f32s")) else (1,)
     for impl in impls:
         handle.set_option("front_impl", impl)
         handle.set_option("se_fuse", 0)                    # (a squeeze-excite launch writes the gate: it can be checked)
@@ -174,10 +189,10 @@ def test_mbconv_block_kernels(handle, taps, index):
         assert np.array_equal(rf["out"], r["out"]) and np.array_equal(rf["dw"], r["dw"]), f"se_fuse changes bits (front_impl={impl})"
         assert not b.has_expand or np.isnan(rf["gate"]).all()          # (no launch wrote a gate)
         if b.has_expand:
-            if impl == 0 or handle.name == "f32":
+            if impl == 0 or handle.name == "f32" or (handle.name == "f32s" and impl == 1):
                 assert np.array_equal(r["dw"], r0["dw"]), "fused expand+depthwise differs from pw+dw"
             else:
-                # the same f16 expanded tensor, f16 instead of f32 tap weights: a rounding apart
+                # f16: the same f16 expanded tensor, f16 instead of f32 tap weights; f32s: other summation orders: a rounding apart
                 assert rel_err(r["dw"], r0["dw"]) < t, f"front2 vs pw+dw (front_impl={impl})"
             # the fused kernel also applies the SE reduce conv to its channel sums (another summation
             # order than se.hip's): same gate and block output within the kernel tolerance
@@ -192,9 +207,9 @@ def test_mbconv_block_kernels(handle, taps, index):
 def test_front7_group_kernel(blob, taps, golden, dt):
     """Round 4: blocks 13-16 (7 x 7 maps) run front7.hip -- a group of crops per workgroup (2 crops up to 16 crops per
     launch, 4 above), the chunk's expand weights staged once in LDS, the image-only tile.  Each block on the oracle's own
-    input: within the kernel tolerance of the oracle and of round 3's kernel (option front7=0) -- for f32 the depthwise
-    output is BITWISE round 3's (same fmaf chains in the same order; only the grouping of the squeeze-excite sums
-    differs); and the group size changes no bit: crops travel through launches of 1, 2, 3, 16, 17 and 21 crops (tail
+    input: within the kernel tolerance of the oracle and of round 3's kernel (option front7=0) -- for f32 and f32s the
+    depthwise output is BITWISE round 3's (same fmaf chains in the same order; f32s: the same three hi/lo products per 16-k
+    step in the same order, the activations as the A operand; only the grouping of the squeeze-excite sums differs); and the group size changes no bit: crops travel through launches of 1, 2, 3, 16, 17 and 21 crops (tail
     groups of both sizes) with identical results."""
     name, dtype = dt
     t = 1.5e-2 if name == "f16" else 2e-5
@@ -207,8 +222,8 @@ def test_front7_group_kernel(blob, taps, golden, dt):
             r3 = h.op_block(index, x)
             h.set_option("front7", 1)
             h.set_option("se_fuse", SE_FUSE_DEFAULT)
-            if name == "f32":
-                assert np.array_equal(r7["dw"], r3["dw"]), "f32 front7: depthwise output differs from front.hip's"
+            if name in F32_NAMES:
+                assert np.array_equal(r7["dw"], r3["dw"]), f"{name} front7: depthwise output differs from front.hip's"
                 assert not np.array_equal(r7["gate"], r3["gate"]), "front7 is not active"
             else:
                 assert not np.array_equal(r7["dw"], r3["dw"]), "front7 is not active"
@@ -267,7 +282,7 @@ def test_head_kernels(handle, taps):
     r = handle.op_head(taps["b16/out"].astype(np.float32))
     t = tol(handle)
     assert rel_err(r["feat"], taps["head"].mean(axis=(1, 2))) < 3 * t
-    assert np.abs(r["logits"] - taps["logits"]).max() < (2e-3 if handle.name == "f32" else 1.0)
+    assert np.abs(r["logits"] - taps["logits"]).max() < (2e-3 if handle.name in F32_NAMES else 1.0)
 
 
 def test_head_conv_fused_with_pooling(blob, taps, golden):
@@ -405,7 +420,7 @@ def test_end_to_end_golden(handle, golden):
     err = np.abs(ypr - exp["angles"]).max()
     print(f"\n[{handle.name}] max |angle - f64 oracle| = {err:.3e} deg; max |logit err| = "
           f"{np.abs(lg - exp['logits']).max():.3e}")
-    if handle.name == "f32":
+    if handle.name in F32_NAMES:
         assert err <= F32_DEG
         safe = exp["margins"] > MARGIN_F32
         assert safe.mean() > 0.9
@@ -440,7 +455,7 @@ def test_mfma_against_scalar_check_kernels(handle, golden):
         _, _, lg1 = handle.forward(crops)
     finally:
         handle.set_option("pw_impl", 0)
-    assert np.abs(lg0 - lg1).max() < (2e-3 if handle.name == "f32" else 0.5)
+    assert np.abs(lg0 - lg1).max() < (2e-3 if handle.name in F32_NAMES else 0.5)
 
 
 def test_batch_invariance_and_permutation(handle, golden):
@@ -518,7 +533,7 @@ def test_full_size_batch_properties(handle, weights):
     idx = [41, 50, 63]
     ref = O.forward(crops[idx], weights, np.float64)
     ang = np.stack([ref["yaw"], ref["pitch"], ref["roll"]], 1)
-    assert np.abs(ypr[idx] - ang).max() <= (F32_DEG if handle.name == "f32" else F16_DEG)
+    assert np.abs(ypr[idx] - ang).max() <= (F32_DEG if handle.name in F32_NAMES else F16_DEG)
     rev = crops[::-1].copy()
     _, _, lr = handle.forward(rev)
     assert np.array_equal(lr[::-1], lg)
@@ -596,8 +611,8 @@ def test_hip_path_against_huggingface_fixture(handle, weights, golden):
     ypr, am, lg = handle.forward(crops)
     y, p, r = O.decode(lg_hf)
     err = np.abs(ypr - np.stack([y, p, r], 1)).max()
-    assert err <= (F32_DEG if handle.name == "f32" else F16_DEG), err
-    if handle.name == "f32":
+    assert err <= (F32_DEG if handle.name in F32_NAMES else F16_DEG), err
+    if handle.name in F32_NAMES:
         assert np.abs(lg - lg_hf).max() < 2e-3
         assert np.array_equal(am, O.argmax_bins(lg_hf))
 
@@ -734,7 +749,8 @@ def _oracle_angles(crops, weights):
 def test_batch_512_bitwise_the_batch_64_path_and_against_the_oracle(handle, weights, schedule):
     """whenet.py:27 accepts any N.  512 crops (BASELINE.json configs[3]'s per-node batch; the project GEMMs take their
     NT = 2 / 3 tile instantiations here and nowhere below ~84 / 168 / 335 crops per launch) through the default
-    schedule (2 lanes), with 3 lanes, with 3 forwards in flight, and as one 512-crop chain: bitwise the same crops run as
+    schedule (2 lanes), with 3 lanes, with 3 forwards in flight, and as one 512-crop chain (lanes = 1 with the handle's fan-out into
+    128-crop forwards switched off: the only schedule here whose launches reach the NT = 3 tiles): bitwise the same crops run as
     8 x 64, and 9 crops spread over all lanes within tolerance of the float64 oracle."""
     crops = np.concatenate([synth.scene_crops(200, seed=41), synth.noise_crops(312, seed=42)])
     assert crops.shape[0] == 512
@@ -742,6 +758,7 @@ def test_batch_512_bitwise_the_batch_64_path_and_against_the_oracle(handle, weig
         handle.set_option("inflight", 3)
     if schedule == "lanes1":
         handle.set_option("lanes", 1)
+        handle.set_option("fanout_min", 0)
     if schedule == "lanes3":
         handle.set_option("lanes", 3)
     try:
@@ -753,6 +770,7 @@ def test_batch_512_bitwise_the_batch_64_path_and_against_the_oracle(handle, weig
     finally:
         handle.set_option("inflight", 1)
         handle.set_option("lanes", 2)
+        handle.set_option("fanout_min", 256)
     assert np.isfinite(lg).all()
     for lo in range(0, 512, 64):
         y, a, l = handle.forward(crops[lo:lo + 64])
@@ -760,8 +778,8 @@ def test_batch_512_bitwise_the_batch_64_path_and_against_the_oracle(handle, weig
     idx = [0, 63, 170, 171, 255, 256, 341, 342, 511]          # first / last crop of each of the 2 or 3 lanes and between
     ang, ref = _oracle_angles(crops[idx], weights)
     err = np.abs(ypr[idx] - ang).max()
-    assert err <= (F32_DEG if handle.name == "f32" else F16_DEG), err
-    if handle.name == "f32":
+    assert err <= (F32_DEG if handle.name in F32_NAMES else F16_DEG), err
+    if handle.name in F32_NAMES:
         assert np.abs(lg[idx] - ref["logits"]).max() < 2e-3
 
 
@@ -770,7 +788,7 @@ def test_batch_8_and_batch_1(handle, weights, golden):
     crops = np.concatenate([synth.scene_crops(5, seed=51), synth.noise_crops(3, seed=52)])
     ypr, am, lg = handle.forward(crops)
     ang, ref = _oracle_angles(crops, weights)
-    assert np.abs(ypr - ang).max() <= (F32_DEG if handle.name == "f32" else F16_DEG)
+    assert np.abs(ypr - ang).max() <= (F32_DEG if handle.name in F32_NAMES else F16_DEG)
     big = np.concatenate([golden["crops"], crops, golden["crops"][:3]])            # 19 crops
     yb, ab, lb = handle.forward(big)
     assert np.array_equal(lb[8:16], lg) and np.array_equal(yb[8:16], ypr) and np.array_equal(ab[8:16], am)
@@ -945,6 +963,45 @@ def test_no_kernel_reads_what_the_forward_did_not_write(handle):
             assert np.isfinite(dirty[2]).all() and all(np.array_equal(a, b) for a, b in zip(clean, dirty)), opts
             for k in opts:
                 handle.set_option(k, defaults[k])
+    finally:
+        handle.set_option("poison", 0)
+        for k, v in defaults.items():
+            handle.set_option(k, v)
+
+
+def test_no_kernel_reads_what_the_forward_did_not_write_at_512_crops(handle):
+    """The poison option where the buffers are big and shared: forwards of 512 crops as ONE chain (lanes = 1, fan-out off: the
+    project GEMMs' NT = 2 / 3 tiles and the XCD-grouped placement of >= 128 crops per launch), on three engines in turn (inflight =
+    3: every engine's arena), and through the default fan-out into 128-crop forwards -- with each dtype's own kernel options (f16
+    mb7 = 1; f32s front2s.hip on blocks 2-12; f16 / f32s se_fuse = 3; head_fuse = 0 for all).  Every result bitwise the clean run's
+    and finite.  The float32-input entry point (forward_f32, eager launches) poisons its input staging buffer too: the copy of
+    the caller's image must cover every byte the forward reads."""
+    crops = np.concatenate([synth.scene_crops(64, seed=91), synth.noise_crops(448, seed=92)])
+    defaults = {"lanes": 2, "inflight": 1, "fanout_min": 256, "head_fuse": 1, "mb7": 0, "se_fuse": SE_FUSE_DEFAULT, "front_impl": 1}
+    extra = [{"head_fuse": 0}]
+    if handle.name == "f16":
+        extra += [{"mb7": 1}, {"se_fuse": 3}]
+    if handle.name == "f32s":
+        extra += [{"front_impl": 2}, {"se_fuse": 3}]
+    legs = [{}] + [dict(sched, **o) for o in [{}] + extra for sched in ({"lanes": 1, "fanout_min": 0}, {"inflight": 3, "fanout_min": 0})]
+    try:
+        for opts in legs:
+            for k, v in opts.items():
+                handle.set_option(k, v)
+            handle.set_option("poison", 0)
+            clean = handle.forward(crops)
+            handle.set_option("poison", 1)
+            for _ in range(3 if opts.get("inflight") == 3 else 1):          # (round robin over the engines)
+                dirty = handle.forward(crops)
+                assert np.isfinite(dirty[2]).all() and all(np.array_equal(a, b) for a, b in zip(clean, dirty)), opts
+            for k in opts:
+                handle.set_option(k, defaults[k])
+        xf = O.normalise(crops[:160]).astype(np.float32)
+        handle.set_option("poison", 0)
+        clean = handle.forward_f32(xf)
+        handle.set_option("poison", 1)
+        dirty = handle.forward_f32(xf)
+        assert np.isfinite(dirty[2]).all() and all(np.array_equal(a, b) for a, b in zip(clean, dirty)), "forward_f32"
     finally:
         handle.set_option("poison", 0)
         for k, v in defaults.items():

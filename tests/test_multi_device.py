@@ -130,7 +130,7 @@ def test_min_shard_keeps_small_batches_on_one_device(fake):
 
 # ----------------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype", ["f32", "f16"])
+@pytest.mark.parametrize("dtype", ["f32", "f16", "f32s"])
 def test_gpu_two_handles_on_one_device_are_bitwise_one_handle(dtype):
     import whenet
     crops = np.concatenate([synth.scene_crops(200, seed=5), synth.noise_crops(77, seed=6)])       # 277: ragged, >= fan-out

@@ -27,6 +27,25 @@ def test_golden_regression(weights, golden):
     assert np.array_equal(r["argmax"], golden["expected"]["argmax"][:3])
 
 
+def test_block_is_the_backbone_s_arithmetic(weights, golden):
+    """backbone() chains block(): every tap of every block, recomputed by block() from the tap before it, is bit for bit the tap
+    backbone() recorded, and so is the feature map (the per-block tests feed block() inputs of their own: they must be checking the
+    arithmetic the end-to-end goldens check)."""
+    x = O.normalise(golden["crops"][:1]).astype(np.float64)
+    t = {}
+    feat = O.backbone(x, weights, taps=t)
+    cur = t["stem"]
+    for b in spec.blocks():
+        mine = {}
+        got = O.block(t["stem"] if b.index == 1 else t[f"b{b.index - 1}/out"], weights, b.index, taps=mine)
+        assert mine and all(np.array_equal(v, t[k]) for k, v in mine.items()), b.index
+        assert np.array_equal(got, t[f"b{b.index}/out"]), b.index
+        cur = O.block(cur, weights, b.index)
+    head = O.swish(O.batchnorm(O.conv2d(cur, weights["head/conv/kernel"], 1), weights, "head/bn"))
+    assert np.array_equal(head, feat)
+    np.testing.assert_allclose(O.heads(feat, weights), golden["expected"]["logits"][:1], rtol=0, atol=1e-9)
+
+
 def test_torch_restatement_agrees(weights, golden):
     """float32 torch (NCHW, oneDNN) vs float64 numpy: <= 1e-3 deg, the north-star bar."""
     crops = golden["crops"]
