@@ -313,7 +313,7 @@ int whenet_set_option(whenet_t* h, const char* key, long value) {
                 h->fanout_chunk = int(value);
             } else if (k == "fanout_stage") {
                 WHENET_REQUIRE(value >= -1 && value <= 3, WHENET_EINVAL,
-                               "fanout_stage must be -1 (calibrate 0 against 1), 0 (pinned staging), 1 (the runtime's pageable path) or 2 (registered, default)");
+                               "fanout_stage must be -1 (calibrate 0 against 1), 0 (pinned staging), 1 (the runtime's pageable path), 2 (registered, default) or 3 (probe: registered, a copy stream per engine)");
                 h->fanout_stage = int(value);
                 h->fanout_calib_calls = 0;
                 h->fanout_calib_rate[0] = h->fanout_calib_rate[1] = 0.0;

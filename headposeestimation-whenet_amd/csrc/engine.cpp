@@ -230,7 +230,7 @@ void Engine::set_option(const std::string& key, long value) {
         drop_graphs();
     } else if (key == "se_fuse") {
         WHENET_REQUIRE(value >= 0 && value <= 3, WHENET_EINVAL,
-                       "se_fuse must be 0 (never), 1 (where the prologue form pays), 2 (prologue form on every block) or 3 (1 + the matrix-core form on blocks 7-16, default)");
+                       "se_fuse must be 0 (never), 1 (where the prologue form pays, default), 2 (prologue form on every block) or 3 (1 + the matrix-core form on blocks 7-16)");
         se_fuse_ = int(value);
         sync();
         drop_graphs();
@@ -273,6 +273,12 @@ void Engine::set_option(const std::string& key, long value) {
         drop_graphs();
     } else if (key == "stem_fuse") {
         stem_fuse_ = value != 0;
+        sync();
+        drop_graphs();
+    } else if (key == "act_layout") {
+        WHENET_REQUIRE(value >= 0 && value <= 2, WHENET_EINVAL,
+                       "act_layout must be 0 (NHWC everywhere), 1 (16-channel blocks per layer, default) or 2 (16-channel blocks wherever supported)");
+        act_layout_ = int(value);
         sync();
         drop_graphs();
     } else if (key == "poison") {
@@ -506,19 +512,52 @@ bool Engine::stem_fuse_active() const {
            stemdw_supported(dtype_, b.dw.plan, b.spec.k, b.spec.s, b.spec.h_in, b.spec.cexp());
 }
 
+bool Engine::head_fused() const {
+    return head_fuse_ && pw_impl_ == 0 && split_heads_ && head7_supported(dtype_, head_.K, head_.N, 49) &&
+           partial_per_crop_ >= size_t(heads_split()) * N_LOGITS;
+}
+
+// The 7 x 7 tensors between the blocks of an f16 handle (outputs of the projects of blocks 12-16) are stored in the order the matrix
+// cores read them: [crop][C/16][HW][16] -- an MFMA operand of 32 pixels x 16 channels is then one or two runs
+// of whole cache lines instead of 16 bytes of each of 32 pixel rows.  Same bytes per crop as NHWC, pure addressing: the bits do not
+// change.  Blocked iff the producer (the split-K project epilogue, pw.hip) and EVERY consumer (the next block's front7.hip and,
+// through its skip, its split-K project; head7.hip behind block 16) know the layout.  front2.hip (the 14 x 14 blocks: measured, the
+// layout gains nothing there -- docs/experiments.md section 13), mb7.hip, front.hip and the unfused kernels do not: tensors they
+// touch stay NHWC, as do the boundaries of the single-stage entry points.
+bool Engine::act_blocked(int index) const {
+    if (act_layout_ == 0 || dtype_ != WHENET_F16 || pw_impl_ != 0 || single_stage_call_) return false;
+    if (index < 1 || index > int(blocks_.size())) return false;
+    const DevBlock& b = blocks_[size_t(index - 1)];
+    if (block_schedule(b).use_mb7 || b.project.K < 320 || b.spec.cout % 16 != 0) return false;     // producer: the split-K epilogue
+    if (index == int(blocks_.size())) {
+        if (!head_fused()) return false;
+    } else {
+        const DevBlock& c = blocks_[size_t(index)];
+        const BlockSchedule cs = block_schedule(c);
+        if (cs.use_mb7 || !cs.use_f7) return false;
+        if (c.spec.has_skip() && c.project.K < 320) return false;
+    }
+    // act_layout = 1, the per-layer table (one chain of 64 crops, blocked against the layer's own NHWC timing, profiles/r07): every
+    // tensor that CAN be blocked wins -- front7 -1.1 us of 17, head7 -3.0 us of 15.4, their producers' stores -0.1 .. -0.3 us
+    static constexpr bool WINS[17] = {false, false, false, false, false, false, false, false, false, false, false, false,
+                                      true, true, true, true, true};      // [block index]: outputs of blocks 12-16
+    return act_layout_ == 2 || (index <= 16 && WINS[index]);
+}
+
 void* Engine::enqueue_blocks(int first, int last, const View& v, void* cur, int n, hipStream_t s, LaunchRecorder* rec,
                              bool b1_dw_done) {
     const bool fold = fold12_active() && first <= 1 && last >= 2;
     for (int i = first; i <= last; ++i) {
         void* nxt = (cur == v.x0) ? v.x1 : v.x0;
-        enqueue_block(blocks_[size_t(i - 1)], v, cur, nxt, n, s, rec, fold && i <= 2 ? i : 0, b1_dw_done && i == 1);
+        enqueue_block(blocks_[size_t(i - 1)], v, cur, nxt, n, s, rec, fold && i <= 2 ? i : 0, b1_dw_done && i == 1,
+                      i > first && act_blocked(i - 1), i < last || last == int(blocks_.size()) ? act_blocked(i) : false);
         cur = nxt;
     }
     return cur;
 }
 
 void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, void* out, int n, hipStream_t s,
-                           LaunchRecorder* rec, int fold, bool dw_done) {
+                           LaunchRecorder* rec, int fold, bool dw_done, bool in_blocked, bool out_blocked) {
     Rec R{rec, s, repeat_};
     const BlockSpec& sp = b.spec;
     const std::string p = "b" + std::to_string(sp.index);
@@ -533,6 +572,8 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
     WHENET_REQUIRE(fold == 0 || (fold == 1 && !fused && sp.index == 1) ||
                        (fold == 2 && sp.index == 2 && (use_f2 || (split_ && fused && !bs.use_f2s && !bs.use_f7))), WHENET_EINVAL,
                    "fold12: block outside the folded pair");
+    WHENET_REQUIRE(!(in_blocked || out_blocked) || (dtype_ == WHENET_F16 && !bs.use_mb7 && (!in_blocked || bs.use_f7)),
+                   WHENET_EINVAL, "act_layout: a kernel of this block does not know the blocked layout");
     if (bs.use_mb7) {
         WHENET_REQUIRE(fold == 0, WHENET_EINVAL, "mb7: block outside the 7 x 7 stage");
         Mb7Args a{};
@@ -583,6 +624,7 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
         a.wsi = b.expand.wsi;
         a.n = n;
         a.xcd_grouped = xcd_grouped(2, n);
+        a.x_blocked = in_blocked;
         a.plan = front7_plan_for(dtype_, sp.cin, cexp, n);
         R(p + "/front", "front", kernel_name_front7(dtype_, sp.k, a.plan, a.split).c_str(), double(n) * (hw_in * sp.cin + hw_out * cexp) * es,
           2.0 * n * (double(hw_in) * sp.cin * cexp + double(hw_out) * sp.k * sp.k * cexp), [&] { launch_front7(a, s); });
@@ -803,6 +845,8 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
         set_split(a, b.project);
         a.HW = hw_out;
         a.act = ACT_NONE;
+        a.out_blocked = out_blocked;
+        a.res_blocked = in_blocked && sp.has_skip();
         R(p + "/project", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(),
           double(a.M) * (a.K + a.N + (sp.has_skip() ? a.N : 0)) * es, 2.0 * a.M * a.K * a.N,
           [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
@@ -839,8 +883,7 @@ void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, float* d
           [&] { launch_stem(a, dtype_, s); });
     }
     void* cur = enqueue_blocks(1, int(blocks_.size()), v, v.x0, n, s, rec, stemdw);
-    const bool fuse_head = head_fuse_ && pw_impl_ == 0 && split_heads_ && head7_supported(dtype_, head_.K, head_.N, 49) &&
-                           partial_per_crop_ >= size_t(heads_split()) * N_LOGITS;
+    const bool fuse_head = head_fused();
     if (fuse_head) {
         // head conv + GlobalAveragePooling2D as one kernel (head7.hip): v.hc receives the pooled features [n][1280] f32
         Head7Args a{};
@@ -857,6 +900,7 @@ void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, float* d
         a.wsi = head_.wsi;
         a.n = n;
         a.xcd_grouped = xcd_grouped(4, n);
+        a.x_blocked = act_blocked(int(blocks_.size()));
         R("head", "pw", kernel_name_head7(dtype_, n, a.split).c_str(), double(n) * (49.0 * a.K * es + a.N * 4.0), 2.0 * n * 49.0 * a.K * a.N,
           [&] { launch_head7(a, s); });
         HeadsArgs hargs{};

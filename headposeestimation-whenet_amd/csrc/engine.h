@@ -180,13 +180,19 @@ class Engine {
                          hipStream_t s, LaunchRecorder* rec, const float* d_in_f32 = nullptr);
     // fold: 0 = the block as it stands; 1 = block 1 without its project (its depthwise output goes to `out`);
     //       2 = block 2 fed by that output, block 1's project folded into its expand weights (fold12_active())
+    // in_blocked / out_blocked: the block's input / output tensor is in the blocked layout (act_blocked())
     void enqueue_block(const DevBlock& b, const View& v, const void* in, void* out, int n, hipStream_t s,
-                       LaunchRecorder* rec, int fold = 0, bool dw_done = false);
+                       LaunchRecorder* rec, int fold = 0, bool dw_done = false, bool in_blocked = false, bool out_blocked = false);
     // blocks first..last (1-based) as the forward pass runs them; returns the buffer (x0 / x1 of `v`) holding the result
     void* enqueue_blocks(int first, int last, const View& v, void* cur, int n, hipStream_t s, LaunchRecorder* rec,
                          bool b1_dw_done = false);
     bool stem_fuse_active() const;
     bool fold12_active() const;
+    bool head_fused() const;           // the head conv pools its own output (head7.hip)
+    // Layout of the OUTPUT of block `index` (1-based) in a whole forward: true = 16-channel blocks [crop][C/16][HW][16]
+    // (DESIGN.md section 2), false = NHWC.  A function of the layer and the options only, never of the batch.
+    bool act_blocked(int index) const;
+    int act_layout_ = 1;               // option "act_layout": 0 = NHWC everywhere, 1 = the per-layer table, 2 = blocked wherever supported
     struct BlockSchedule {     // which kernels a block runs under the current options
         bool fused = false, use_f2 = false, use_f2s = false, use_f7 = false, se_in_front = false, se_fused = false, se_mfma = false;
         bool use_mb7 = false;  // the whole block is one launch (mb7.hip): no front / squeeze-excite / project launches

@@ -57,6 +57,7 @@ struct F7Params {
     int off_w, off_stage, off_red, off_sum;
     float wsi;                         // WHENET_F32S: 2^-shift of the scaled split weights (wep is then the [hi | lo] image pair)
     int chunks, ngroups, xcd;          // launch geometry: a 1-D grid of chunks * ngroups workgroups (xcd_unit())
+    int xblk;                          // f16: x is [n][Cin/16][49][16] (the blocked layout, Front7Args::x_blocked)
 };
 
 // K: depthwise kernel size (3 | 5); KS: k-steps of the expand contraction (Cin / 16); G: crops per workgroup; CC: expanded
@@ -102,6 +103,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front7_kernel(const F7Params p) {
         }
     }
     // operand side: MFMA row lm = image row (lm >> 3) of the strip, pixel slot lm & 7 (slot 7 = pad: any valid address)
+    const bool xblk = p.xblk != 0;                             // (uniform)
     auto a_offset = [&](int strip) -> unsigned {
         int R = strip * 4 + (lm >> 3);
         R = R < nrow ? R : nrow - 1;
@@ -111,10 +113,21 @@ __global__ __launch_bounds__(NTHR) void whenet_front7_kernel(const F7Params p) {
         gc = gc < nlast ? gc : nlast;
         int px = lm & 7;
         px = px < 7 ? px : 6;
+        // blocked input: the crop's [KS][49] slices of 32 bytes -- the 28 pixels of a strip are 896 contiguous bytes per k-step
+        if (xblk) return unsigned(gc * 49 * Cin + (row * 7 + px) * 16 + g * 8) * 2u;
         return unsigned((gc * 49 + row * 7 + px) * Cin + g * 8) * 2u;
     };
     const unsigned char* xb = reinterpret_cast<const unsigned char*>(p.x);
     half8 a[KS];
+    auto load_rows = [&](unsigned off) {                       // this lane's KS operand fragments, straight from global memory
+        if (xblk) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xb + off + ks * (49 * 32));
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xb + off + ks * 32);
+        }
+    };
     // few strips (groups of 2 crops: 4 strips x NT tiles <= the waves): one (strip, tile) task per wave instead of one strip
     // per wave over all tiles -- at small launches the expand phase is the workgroup's critical path
     constexpr bool SPLIT = nstrip * NT <= NWAVE;
@@ -128,8 +141,11 @@ __global__ __launch_bounds__(NTHR) void whenet_front7_kernel(const F7Params p) {
     // DS operations of a wave execute in order, no barrier.  Pure data movement: the fragments, hence the bits, are the same.
     // (Groups of 4 crops: 7 strips on 8 waves, 7 x 4,032 B <= the tile region.  Smaller groups keep the direct loads.)
     constexpr bool STG = !SPLIT && nstrip <= NWAVE && nstrip * 4032 <= (G + 3) / 4 * NCB * ROWS * 64 * 16 && KS % 4 == 0;
+    // (a blocked input needs no such pass: its fragments ARE whole lines)
+    bool direct = true;
+    if constexpr (STG) direct = xblk;
     if (strip < nstrip) {
-        if constexpr (STG) {
+        if constexpr (STG) if (!direct) {
             constexpr int PX = 28, SEG = KS / 4;                 // pixels of a strip; 128-byte column groups of a pixel row
             constexpr int rowb = KS * 32;                        // bytes of a pixel row
             unsigned char* sa = E + wave * 4032;
@@ -159,11 +175,8 @@ __global__ __launch_bounds__(NTHR) void whenet_front7_kernel(const F7Params p) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) a[t * 4 + u] = *reinterpret_cast<const half8*>(sa + pf * 144 + u * 32 + g * 16);
             }
-        } else {
-            const unsigned off = a_offset(strip);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xb + off + ks * 32);
         }
+        if (direct) load_rows(a_offset(strip));
     }
     float bias_t[NT];
 #pragma unroll
@@ -211,9 +224,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front7_kernel(const F7Params p) {
             }
         }
         if (more) {                                            // (only plans with more strips than waves get here)
-            const unsigned off = a_offset(strip + NWAVE);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xb + off + ks * 32);
+            load_rows(a_offset(strip + NWAVE));
         }
     }
     STAMP(2);
@@ -709,6 +720,7 @@ void launch_f7(const Front7Args& a, hipStream_t stream) {
         attr.done[dev].store(true, std::memory_order_release);
     }
     p.chunks = pl.chunks;  p.ngroups = ceil_div(a.n, pl.G);  p.xcd = a.xcd_grouped ? 1 : 0;
+    p.xblk = a.x_blocked ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(unsigned(p.chunks) * unsigned(p.ngroups)), dim3(NTHR), pl.lds_bytes, stream, p);
     WHENET_HIP_CHECK(hipGetLastError());
 }
@@ -757,6 +769,7 @@ bool front7_supported(int k, int s, int H, int Cin) { return (k == 3 || k == 5) 
 void launch_front7(const Front7Args& a, hipStream_t stream) {
     WHENET_REQUIRE(front7_supported(a.k, 1, HW7, a.Cin) && a.w1t != nullptr && a.R >= 1 && a.R <= 64 && a.n >= 1, WHENET_EINVAL,
                    "front7: 7 x 7 maps, 3x3 / 5x5 stride-1 kernels, Cin = 192, squeeze-excite reduce conv in the kernel");
+    WHENET_REQUIRE(!a.x_blocked || a.dtype == WHENET_F16, WHENET_EINVAL, "front7: the blocked input layout exists for binary16 only");
     const int key = ((a.k * 10 + a.plan.G) * 1000 + a.plan.CC) * 1000 + a.plan.threads;
     if (a.dtype == WHENET_F32) {
         switch (key) {

@@ -32,7 +32,7 @@ constexpr int H7_K = 320, H7_KS = H7_K / 16, H7_HW = 49, H7_NC = 64, H7_NT = H7_
 template <int G, int NTHR>
 __global__ __launch_bounds__(NTHR) void whenet_head7_kernel(const half_t* __restrict__ x, const half_t* __restrict__ wep,
                                                             const float* __restrict__ bias, float* __restrict__ feat, int n,
-                                                            int NTILES, int N, int xcd) {
+                                                            int NTILES, int N, int xcd, int xblk) {
     constexpr int NWAVE = NTHR / 64;
     constexpr int nstrip = 2 * G;
     constexpr int KS = H7_KS, NT = H7_NT, NC = H7_NC;
@@ -75,9 +75,15 @@ __global__ __launch_bounds__(NTHR) void whenet_head7_kernel(const half_t* __rest
         gc = gc < nlast ? gc : nlast;
         int px = (strip & 1) * 32 + lm;
         px = px < H7_HW ? px : H7_HW - 1;                       // (idle rows: any valid address, masked out of the sum)
-        const unsigned char* xr = reinterpret_cast<const unsigned char*>(x) + (size_t(gc) * H7_HW + px) * (H7_K * 2) + g * 16;
+        if (xblk) {                                            // (uniform) x is [n][K/16][49][16]: a strip's k-step is one 1 KB run
+            const unsigned char* xr = reinterpret_cast<const unsigned char*>(x) + size_t(gc) * (H7_HW * H7_K * 2) + px * 32 + g * 16;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xr + ks * 32);
+            for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xr + ks * (H7_HW * 32));
+        } else {
+            const unsigned char* xr = reinterpret_cast<const unsigned char*>(x) + (size_t(gc) * H7_HW + px) * (H7_K * 2) + g * 16;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const half8*>(xr + ks * 32);
+        }
     }
     float bias_t[NT];
 #pragma unroll
@@ -271,7 +277,7 @@ void launch_h7(const Head7Args& a, hipStream_t stream) {
     constexpr int NTHR = 512;
     const size_t lds = size_t(H7_KS) * H7_NT * 1024 + size_t(2 * G) * 2 * H7_NC * 4;
     hipLaunchKernelGGL((whenet_head7_kernel<G, NTHR>), dim3(unsigned(a.N / H7_NC) * unsigned(ceil_div(a.n, G))), dim3(NTHR), lds, stream,
-                       static_cast<const half_t*>(a.x), static_cast<const half_t*>(a.wep), a.bias, a.feat, a.n, a.NTILES, a.N, a.xcd_grouped ? 1 : 0);
+                       static_cast<const half_t*>(a.x), static_cast<const half_t*>(a.wep), a.bias, a.feat, a.n, a.NTILES, a.N, a.xcd_grouped ? 1 : 0, a.x_blocked ? 1 : 0);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 
@@ -286,6 +292,7 @@ bool head7_supported(int dtype, int K, int N, int HW) {
 void launch_head7(const Head7Args& a, hipStream_t stream) {
     WHENET_REQUIRE(head7_supported(a.dtype, a.K, a.N, 49) && a.n >= 1 && a.x && a.wep && a.bias && a.feat, WHENET_EINVAL,
                    "head7: the 320 -> N (multiple of 64) head conv on 7 x 7 maps");
+    WHENET_REQUIRE(!a.x_blocked || a.dtype == WHENET_F16, WHENET_EINVAL, "head7: the blocked input layout exists for binary16 only");
     if (a.dtype == WHENET_F16) {
         if (a.n <= 16) launch_h7<2>(a, stream);
         else launch_h7<4>(a, stream);

@@ -113,6 +113,8 @@ struct PwArgs {
     int KSs = 0;                   // ceil(K / 16)
     float wsi = 1.0f;              // 2^-shift of the scaled weights
     bool staged = true;            // K >= 320: activation rows fetched coalesced and staged through LDS (whenet_pw_splitk_staged_kernel)
+    // f16 split-K kernels (K >= 320): `out` / `res` in the 16-channel blocked layout [crop][N/16][HW][16]
+    bool out_blocked = false, res_blocked = false;
 };
 void launch_pw(const PwArgs& a, int dtype, int impl, int num_cus, hipStream_t stream);
 
@@ -152,6 +154,7 @@ struct Head7Args {
     const void* weps = nullptr;    // [hi image | lo image]
     float wsi = 1.0f;
     bool xcd_grouped = false;      // the channel chunks of a crop group on one XCD (device_math.h xcd_unit)
+    bool x_blocked = false;        // f16: x is [n][K/16][49][16] (the blocked layout)
 };
 bool head7_supported(int dtype, int K, int N, int HW);
 void launch_head7(const Head7Args& a, hipStream_t stream);
@@ -331,6 +334,7 @@ struct Front7Args {
     const void* weps = nullptr;    // [hi image | lo image] of the expand weights
     float wsi = 1.0f;
     bool xcd_grouped = false;      // the channel chunks of a crop group on one XCD (device_math.h xcd_unit)
+    bool x_blocked = false;        // f16: x is [n][Cin/16][49][16] (the blocked layout)
 };
 void launch_front7(const Front7Args& a, hipStream_t stream);
 std::string kernel_name_front7(int dtype, int k, const Front7Plan& p, bool split = false);

@@ -45,7 +45,7 @@ namespace {
 template <typename T, int B2, bool RES, int ACT, bool SP>
 __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], float* s_red, int kpart, int lane, int mt, int nt0, int M,
                                                      int N, int NTILES, const float* __restrict__ bias, const T* __restrict__ res,
-                                                     T* __restrict__ out, float wsi) {
+                                                     T* __restrict__ out, float wsi, int HW, int lay) {
     using OT = T __attribute__((ext_vector_type(4)));
     constexpr int MB = B2, NT = B2;
     constexpr int NACC = MB * NT * 16, SL = NACC / 4;
@@ -55,6 +55,23 @@ __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], fl
     const int own_tile = f0 >> 4, own_mb = own_tile / NT, own_t = own_tile % NT;
     const int own_row = (mt * MB + own_mb) * 32 + (lane & 31);
     const bool own_valid = own_row < M && nt0 + own_t < NTILES;
+    // lay (PwArgs::out_blocked | res_blocked << 1): that operand is [crop][N/16][HW][16] instead of [row][N].  A lane's four
+    // channels stay one 8-byte piece; the 32 rows of a store then fall into 1 KB (8-10 cache lines) instead of 32 lines.
+    // Both forms are  base + (n0 >> 4) * s16 + (n0 & 15):  NHWC base = row * N, s16 = 16;  blocked base = crop * N * HW + pix * 16,
+    // s16 = HW * 16.
+    const size_t row_base = size_t(own_row) * N;
+    size_t blk_base = row_base;
+    if (lay != 0) {                                  // (uniform) row -> (crop, pixel): float estimate, made exact
+        int crop = int(float(own_row) * __builtin_amdgcn_rcpf(float(HW)));
+        int pix = own_row - crop * HW;
+        if (pix < 0) { --crop; pix += HW; }
+        if (pix >= HW) { ++crop; pix -= HW; }
+        blk_base = size_t(crop) * size_t(N) * HW + size_t(pix) * 16;
+    }
+    const bool out_blk = (lay & 1) != 0, res_blk = (lay & 2) != 0;
+    const size_t out_base = out_blk ? blk_base : row_base, res_base = res_blk ? blk_base : row_base;
+    const unsigned out_s16 = out_blk ? unsigned(HW) * 16u : 16u, res_s16 = res_blk ? unsigned(HW) * 16u : 16u;
+    auto elem_off = [&](size_t base, unsigned s16, int n0) -> size_t { return base + size_t(unsigned(n0 >> 4) * s16 + unsigned(n0 & 15)); };
     OT rv[SL / 4];
     float4v bv[SL / 4];
 #pragma unroll
@@ -63,7 +80,7 @@ __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], fl
         const int n0 = (nt0 + own_t) * 32 + 8 * qq + 4 * g;
         const bool ok = own_valid && n0 < N;
         bv[i4] = ok ? *reinterpret_cast<const float4v*>(bias + n0) : float4v{0.f, 0.f, 0.f, 0.f};
-        if constexpr (RES) rv[i4] = ok ? *reinterpret_cast<const OT*>(res + size_t(own_row) * N + n0) : OT{};
+        if constexpr (RES) rv[i4] = ok ? *reinterpret_cast<const OT*>(res + elem_off(res_base, res_s16, n0)) : OT{};
     }
     float own[SL];
 #pragma unroll
@@ -114,7 +131,7 @@ __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], fl
             if constexpr (RES) y += float(rv[i4][r]);
             o[r] = T(y);
         }
-        *reinterpret_cast<OT*>(out + size_t(own_row) * N + n0) = o;
+        *reinterpret_cast<OT*>(out + elem_off(out_base, out_s16, n0)) = o;
     }
     STAMP(4);
 }
@@ -142,7 +159,7 @@ template <typename T, int B2, int GM, bool RES, int ACT, bool SP = false>
 __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
     const T* __restrict__ A, const T* __restrict__ Wp, const float* __restrict__ bias, const T* __restrict__ gate,
     const T* __restrict__ res, T* __restrict__ out, int M, int K, int N, int KS, int NTILES, int HW, int MT, int NCH,
-    const SeFuse se, float wsi) {
+    const SeFuse se, float wsi, int lay) {
     constexpr bool GATE = GM != 0;
     using OPS = PwOps<T, SP>;
     constexpr int V = OPS::V;                       // k elements per lane and k-step (SP: 8 floats)
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
     }
     STAMP(2);
 
-    splitk_combine_store<T, B2, RES, ACT, SP>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi);
+    splitk_combine_store<T, B2, RES, ACT, SP>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi, HW, lay);
 }
 
 // Round 5: the same product with the activation rows fetched COALESCED and handed to the matrix cores through LDS.
@@ -287,7 +304,7 @@ template <typename T, int B2, int GM, bool RES, int ACT, bool SP = false>
 __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_kernel(
     const T* __restrict__ A, const T* __restrict__ Wp, const float* __restrict__ bias, const T* __restrict__ gate,
     const T* __restrict__ res, T* __restrict__ out, int M, int K, int N, int KS, int NTILES, int HW, int MT, int NCH,
-    const SeFuse se, float wsi) {
+    const SeFuse se, float wsi, int lay) {
     constexpr bool GATE = GM != 0;
     using OPS = PwOps<T, SP>;
     constexpr int V = OPS::V;
@@ -541,7 +558,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
         }
     }
     lds_barrier();                                          // every wave is done with its staging region: s_red may overwrite it
-    splitk_combine_store<T, B2, RES, ACT, SP>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi);
+    splitk_combine_store<T, B2, RES, ACT, SP>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi, HW, lay);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -870,18 +887,19 @@ PwChoice choose_pw(const PwArgs& a, int num_cus) {
 template <typename T, int B2, int GM, bool RES, int ACT, bool SP>
 void launch_splitk(const PwArgs& a, hipStream_t stream) {
     const int MT = ceil_div(a.M, 32 * B2), NCH = ceil_div(a.NTILES, B2);
+    const int lay = (a.out_blocked ? 1 : 0) | (a.res_blocked ? 2 : 0);
     if (GM == 3 || use_staged(a, IsF32<T>::value && !SP)) {
         hipLaunchKernelGGL((whenet_pw_splitk_staged_kernel<T, B2, GM, RES, ACT, SP>), dim3(8 * ceil_div(MT, 8) * NCH), dim3(256), 0,
                            stream, static_cast<const T*>(a.a), static_cast<const T*>(SP ? a.wps : a.wp), a.bias,
                            static_cast<const T*>(a.gate), static_cast<const T*>(a.res), static_cast<T*>(a.out), a.M, a.K,
-                           a.N, SP ? a.KSs : a.KS, a.NTILES, a.HW, MT, NCH, a.se, a.wsi);
+                           a.N, SP ? a.KSs : a.KS, a.NTILES, a.HW, MT, NCH, a.se, a.wsi, lay);
         return;
     }
     if constexpr (GM != 3)                  // (the matrix-core gate exists in the staged kernel only)
         hipLaunchKernelGGL((whenet_pw_splitk_kernel<T, B2, GM, RES, ACT, SP>), dim3(8 * ceil_div(MT, 8) * NCH), dim3(256), 0,
                            stream, static_cast<const T*>(a.a), static_cast<const T*>(SP ? a.wps : a.wp), a.bias,
                            static_cast<const T*>(a.gate), static_cast<const T*>(a.res), static_cast<T*>(a.out), a.M, a.K,
-                           a.N, SP ? a.KSs : a.KS, a.NTILES, a.HW, MT, NCH, a.se, a.wsi);
+                           a.N, SP ? a.KSs : a.KS, a.NTILES, a.HW, MT, NCH, a.se, a.wsi, lay);
 }
 
 template <typename T, int NT, int GM, bool RES, int ACT, bool SP>
@@ -961,6 +979,11 @@ void launch_pw(const PwArgs& a, int dtype, int impl, int num_cus, hipStream_t st
     WHENET_REQUIRE(a.se.rpart == nullptr || (a.se.RP % 4 == 0 && a.se.RP <= 48 && a.se.np >= 1 &&
                                              (a.K >= 320 || (a.K <= 256 && a.HW >= 196 && a.se.RP <= 12))),
                    WHENET_EINVAL, "pointwise: fused squeeze-excite outside its limits");
+    // the blocked layout exists in the binary16 split-K epilogue only (projects of blocks 7-16)
+    WHENET_REQUIRE(!(a.out_blocked || a.res_blocked) ||
+                       (dtype == WHENET_F16 && impl == 0 && a.K >= 320 && a.N % 16 == 0 && a.HW >= 1 && a.M % a.HW == 0 &&
+                        (!a.res_blocked || a.res != nullptr)),
+                   WHENET_EINVAL, "pointwise: blocked output / skip outside the binary16 split-K kernels (K >= 320, N % 16 == 0)");
     const bool split = a.split && impl == 0;          // (the scalar check kernel multiplies the f32 weights themselves)
     WHENET_REQUIRE(!a.split || (dtype == WHENET_F32 && a.wps != nullptr && a.KSs == ceil_div(a.K, 16)), WHENET_EINVAL,
                    "pointwise: the split-product form needs float32 storage and the split weight images");

@@ -38,7 +38,8 @@ extern "C" {
  * actually ran: with option "inflight" > 1 a forward is ONE chain of the whole batch).
  * 4 (round 5): dtype WHENET_F32S; whenet_normalise_table; options pw_staged, split_pw, fanout_min / _chunk / _stage / _depth,
  * host_pinned_max, host_lanes, se_fuse_tiny.  (Additions only: a version-3 caller runs unchanged.)
- * (round 6, still 4 -- options only: mb7, f2s_mask, se_fuse = 3, fanout_engines, fanout_stage = 2 | 3; the fan-out's default form is 2.) */
+ * (round 6, still 4 -- options only: mb7, f2s_mask, se_fuse = 3, fanout_engines, fanout_stage = 2 | 3; the fan-out's default form is 2.)
+ * (round 7, still 4 -- option act_layout.) */
 #define WHENET_ABI_VERSION 4
 #define WHENET_API __attribute__((visibility("default")))
 
@@ -191,6 +192,15 @@ WHENET_API int whenet_get_info(const whenet_t* h, whenet_info_t* out);
  *                  crops x 3 in flight, -4 % one forward at a time, +60 us at batch 1 -- the schedule must not depend on the batch, so it
  *                  is not the default.  Another rounding path of the same function: binary16 squeeze-excite kernels, other orders of
  *                  summation; bitwise independent of the batch like every other schedule),
+ *          "act_layout" (0..2, default 1, WHENET_F16 handles: how the tensors between the 7 x 7 blocks -- the outputs of the project
+ *                  convs of blocks 12-16, C = 192 / 320 -- lie in the activation arena.  0 = NHWC everywhere; 1 = the per-layer
+ *                  table: 16-channel blocks [crop][C/16][HW][16] where that is the faster form; 2 = 16-channel blocks wherever
+ *                  the producer and every consumer of a tensor know the layout (today the same tensors as 1).  In the blocked
+ *                  form the 32 pixels x 16 channels of one matrix-core operand are whole cache lines (1 KB in one or two runs)
+ *                  instead of 16 bytes of each of 32 pixel rows.  Pure addressing, the same bytes per crop: the results are
+ *                  bitwise the same for every value.  A function of the layer, never of the batch; tensors touched by "mb7",
+ *                  by "front7" = 0, by the 14 x 14 front kernels or by the unfused kernels stay NHWC, as do the inputs and
+ *                  outputs of the whenet_op_* entry points),
  *          "pw_impl" (0 = MFMA kernels, 1 = scalar-FMA check kernels, same results class) */
 WHENET_API int whenet_set_option(whenet_t* h, const char* key, long value);
 
