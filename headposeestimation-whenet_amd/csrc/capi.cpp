@@ -86,12 +86,15 @@ thread_local std::string g_create_error;
 struct HostRegistry {
     std::mutex mu;
     std::vector<std::pair<uintptr_t, uintptr_t>> held;
+    static std::pair<uintptr_t, uintptr_t> page_range(const void* p, size_t nbytes) {
+        const uintptr_t page = 4096, a = reinterpret_cast<uintptr_t>(p);
+        return {a & ~(page - 1), (a + nbytes + page - 1) & ~(page - 1)};
+    }
     bool acquire(const void* p, size_t nbytes, hipError_t* err) {
-        const uintptr_t page = 4096, lo = reinterpret_cast<uintptr_t>(p) & ~(page - 1),
-                        hi = (reinterpret_cast<uintptr_t>(p) + nbytes + page - 1) & ~(page - 1);
+        const auto range = page_range(p, nbytes);
         std::lock_guard<std::mutex> lock(mu);
         for (const auto& r : held)
-            if (lo < r.second && r.first < hi) {
+            if (range.first < r.second && r.first < range.second) {
                 *err = hipErrorUnknown;
                 return false;
             }
@@ -100,16 +103,15 @@ struct HostRegistry {
             (void)hipGetLastError();
             return false;
         }
-        held.emplace_back(lo, hi);
+        held.push_back(range);
         return true;
     }
     void release(const void* p, size_t nbytes) {
-        const uintptr_t page = 4096, lo = reinterpret_cast<uintptr_t>(p) & ~(page - 1),
-                        hi = (reinterpret_cast<uintptr_t>(p) + nbytes + page - 1) & ~(page - 1);
+        const auto range = page_range(p, nbytes);
         std::lock_guard<std::mutex> lock(mu);
         (void)hipHostUnregister(const_cast<void*>(p));
         for (size_t i = 0; i < held.size(); ++i)
-            if (held[i].first == lo && held[i].second == hi) {
+            if (held[i] == range) {
                 held.erase(held.begin() + long(i));
                 break;
             }
@@ -117,24 +119,33 @@ struct HostRegistry {
 };
 HostRegistry g_host_registry;
 
+// The exception in flight (call it inside a catch block) as the ABI's return code, its text in msg.
+int translate_exception(std::string& msg) {
+    try {
+        throw;
+    } catch (const whenet::Error& e) {
+        msg = e.what();
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        msg = "out of host memory";
+        return WHENET_ENOMEM;
+    } catch (const std::exception& e) {
+        msg = e.what();
+        return WHENET_EHIP;
+    } catch (...) {
+        msg = "unknown error";
+        return WHENET_EHIP;
+    }
+}
+
 template <typename F>
 int guarded(whenet_t* h, F&& fn) {
     if (h == nullptr || h->engine == nullptr) return WHENET_EINVAL;
     try {
         fn(*h->engine);
         return WHENET_OK;
-    } catch (const whenet::Error& e) {
-        h->engine->last_error = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        h->engine->last_error = "out of host memory";
-        return WHENET_ENOMEM;
-    } catch (const std::exception& e) {
-        h->engine->last_error = e.what();
-        return WHENET_EHIP;
     } catch (...) {
-        h->engine->last_error = "unknown error";
-        return WHENET_EHIP;
+        return translate_exception(h->engine->last_error);
     }
 }
 
@@ -150,18 +161,8 @@ int create_impl(const void* blob, size_t nbytes, int device_id, int dtype, whene
         h->dtype = dtype;
         *out = h;
         return WHENET_OK;
-    } catch (const whenet::Error& e) {
-        g_create_error = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        g_create_error = "out of host memory";
-        return WHENET_ENOMEM;
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        return WHENET_EHIP;
     } catch (...) {
-        g_create_error = "unknown error";
-        return WHENET_EHIP;
+        return translate_exception(g_create_error);
     }
 }
 
@@ -227,18 +228,8 @@ int whenet_create_postproc(int device_id, whenet_t** out) {
         h->device_id = device_id;
         *out = h;
         return WHENET_OK;
-    } catch (const whenet::Error& e) {
-        g_create_error = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        g_create_error = "out of host memory";
-        return WHENET_ENOMEM;
-    } catch (const std::exception& e) {
-        g_create_error = e.what();
-        return WHENET_EHIP;
     } catch (...) {
-        g_create_error = "unknown error";
-        return WHENET_EHIP;
+        return translate_exception(g_create_error);
     }
 }
 

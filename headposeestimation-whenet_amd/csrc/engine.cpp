@@ -15,9 +15,9 @@ using namespace detail;
 // construction / weights
 // ------------------------------------------------------------------------------------------
 void* Engine::upload_bytes(const void* p, size_t nbytes) {
-    void* d = nullptr;
-    WHENET_HIP_CHECK(hipMalloc(&d, nbytes ? nbytes : 16));
-    weight_allocs_.push_back(d);
+    weight_allocs_.emplace_back();
+    weight_allocs_.back().reset(nbytes);
+    void* d = weight_allocs_.back().as<void>();
     if (nbytes) WHENET_HIP_CHECK(hipMemcpy(d, p, nbytes, hipMemcpyHostToDevice));
     return d;
 }
@@ -141,6 +141,12 @@ Engine::Engine(const void* snapshot, size_t nbytes, int device_id, int dtype)
     d_dense_w_ = upload(m.dense_w);
     d_dense_b_ = upload(m.dense_b);
     WHENET_HIP_CHECK(hipDeviceSynchronize());
+
+    const size_t es = esz();
+    const size_t per_crop[A_COUNT] = {X_ELEMS * es, X_ELEMS * es, E_ELEMS * es, D_ELEMS * es, HC_ELEMS * es,
+                                      partial_per_crop_ * sizeof(float), GATE_ELEMS * sizeof(float), sizeof(unsigned), IN_BYTES,
+                                      3 * sizeof(float), 3 * sizeof(int32_t), N_LOGITS * sizeof(float)};
+    for (int i = 0; i < A_COUNT; ++i) arena_[i].per_crop = per_crop[i];
 }
 
 void Engine::open_device(int device_id) {
@@ -157,17 +163,14 @@ void Engine::open_device(int device_id) {
                    std::string("device is ") + prop_.gcnArchName + "; this library carries gfx950 code only");
     num_cus_ = prop_.multiProcessorCount;
 
-    WHENET_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    WHENET_HIP_CHECK(hipStreamCreateWithFlags(stream_.put(), hipStreamNonBlocking));
     // Only the main stream exists up front: the runtime places a new stream on its least-loaded
     // hardware queue (4 of them), so streams are created in the order concurrency needs them -- the
     // main streams of the engines of one handle, then sub-batch lanes / the copy stream on first use --
     // instead of nine per engine, most of them idle ballast that skews that placement.
-    WHENET_HIP_CHECK(hipEventCreateWithFlags(&fork_ev_, hipEventDisableTiming));
-    for (int i = 0; i < MAX_LANES - 1; ++i) {
-        hipEvent_t ev = nullptr;
-        WHENET_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        join_ev_.push_back(ev);
-    }
+    fork_ev_.create();
+    join_ev_.resize(MAX_LANES - 1);
+    for (Event& ev : join_ev_) ev.create();
 }
 
 // A handle without a network: what whenet_yolo_eval / whenet_op_crop_resize need (device, stream, scratch).
@@ -177,162 +180,100 @@ void Engine::require_model() const {
     WHENET_REQUIRE(has_model_, WHENET_EINVAL, "this handle was created without a network (whenet_create_postproc)");
 }
 
+// What has an order is done here: nothing is in flight and no graph refers to a buffer when the members go.  They free themselves
+// after this body, on the device it selected: buffers and events first, the streams last (engine.h declares them in that order).
 Engine::~Engine() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
-    for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
-    graphs_.clear();
-    auto free_slot_buffers = [](Slot& s) {
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_ypr) (void)hipHostFree(s.h_ypr);
-        if (s.h_amax) (void)hipHostFree(s.h_amax);
-        if (s.h_logits) (void)hipHostFree(s.h_logits);
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_ypr) (void)hipFree(s.d_ypr);
-        if (s.d_amax) (void)hipFree(s.d_amax);
-        if (s.d_logits) (void)hipFree(s.d_logits);
-        if (s.h_frame) (void)hipHostFree(s.h_frame);
-        if (s.d_frame) (void)hipFree(s.d_frame);
-        if (s.h_plan) (void)hipHostFree(s.h_plan);
-        if (s.d_plan) (void)hipFree(s.d_plan);
-        if (s.copied) (void)hipEventDestroy(s.copied);
-        if (s.done) (void)hipEventDestroy(s.done);
-    };
-    for (Slot& s : slots_) free_slot_buffers(s);
-    free_slot_buffers(host_slot_);
-    if (hout_ypr_) (void)hipHostFree(hout_ypr_);
-    if (hout_amax_) (void)hipHostFree(hout_amax_);
-    if (hout_logits_) (void)hipHostFree(hout_logits_);
-    void* arena[] = {x0_, x1_, e_, d_, hc_, partial_, gate_, hcount_, in_u8_, o_ypr_, o_amax_, o_logits_, in_f32_, yolo_scratch_};
-    for (void* p : arena)
-        if (p) (void)hipFree(p);
-    for (void* p : weight_allocs_) (void)hipFree(p);
-    for (hipStream_t st : lane_streams_) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    for (hipEvent_t ev : join_ev_) (void)hipEventDestroy(ev);
-    if (fork_ev_) (void)hipEventDestroy(fork_ev_);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
+    for (hipStream_t st : lane_streams_) (void)hipStreamSynchronize(st);
+    drop_graphs();
 }
 
 void Engine::set_option(const std::string& key, long value) {
     DeviceGuard guard(device_);
     if (key == "graph") {
         use_graph_ = value != 0;
+        return;
     } else if (key == "pw_impl") {
         WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "pw_impl must be 0 (MFMA) or 1 (check kernel)");
         pw_impl_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "fuse_front") {
         fuse_front_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "se_fuse") {
         WHENET_REQUIRE(value >= 0 && value <= 3, WHENET_EINVAL,
                        "se_fuse must be 0 (never), 1 (where the prologue form pays, default), 2 (prologue form on every block) or 3 (1 + the matrix-core form on blocks 7-16)");
         se_fuse_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "front_impl") {
         WHENET_REQUIRE(value >= 0 && value <= 2, WHENET_EINVAL,
                        "front_impl must be 0 (front.hip everywhere), 1 (per layer, default) or 2 (front2.hip / front2s.hip wherever they exist)");
         front_impl_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "f2s_mask") {
         // probes: bit i set = block i runs front2s.hip (f32s handles, front_impl = 1); -1 = the measured per-layer table
         WHENET_REQUIRE(value >= -1 && value < (1 << 17), WHENET_EINVAL, "f2s_mask must be -1 or a bit mask of blocks 2..12");
         f2s_mask_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "head_fuse") {
         head_fuse_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "concurrent") {
         xcd_always_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "xcd_map") {
         WHENET_REQUIRE(value >= 0 && value <= 7, WHENET_EINVAL, "xcd_map must be a bit mask 0..7 (1 = front / front2, 2 = front7, 4 = head7)");
         xcd_map_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "mb7") {
         mb7_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "front7") {
         front7_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "fold12") {
         fold12_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "stem_fuse") {
         stem_fuse_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "act_layout") {
         WHENET_REQUIRE(value >= 0 && value <= 2, WHENET_EINVAL,
                        "act_layout must be 0 (NHWC everywhere), 1 (16-channel blocks per layer, default) or 2 (16-channel blocks wherever supported)");
         act_layout_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "poison") {
         poison_ = value != 0;
+        return;
     } else if (key == "lanes" || key == "device_lanes") {
         // "lanes": every forward; "device_lanes" (set by the handle's "inflight" option): the asynchronous device-side
         // entry points only -- a blocking host forward keeps host_lanes_
         WHENET_REQUIRE(value >= 1 && value <= MAX_LANES, WHENET_EINVAL, "lanes must be 1..8");
         lanes_ = int(value);
         if (key == "lanes") host_lanes_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "split_heads") {
         split_heads_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "lane_graphs") {
         lane_graphs_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "pw_staged") {
         pw_staged_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "split_pw") {
         WHENET_REQUIRE(split_ || value == 0, WHENET_EINVAL, "split_pw: the handle was not created as WHENET_F32S");
         split_pw_ = value != 0;
-        sync();
-        drop_graphs();
     } else if (key == "host_pinned_max") {
         WHENET_REQUIRE(value >= 0 && value <= 4096, WHENET_EINVAL, "host_pinned_max must be 0..4096");
         sync();
         host_pinned_max_ = int(value);
+        return;
     } else if (key == "se_fuse_tiny") {
         WHENET_REQUIRE(value >= 0 && value <= 64, WHENET_EINVAL, "se_fuse_tiny must be 0..64");
         se_fuse_tiny_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "host_lanes") {
         WHENET_REQUIRE(value >= 1 && value <= MAX_LANES, WHENET_EINVAL, "host_lanes must be 1..8");
         host_lanes_ = int(value);
+        return;
     } else if (key == "min_lane_crops") {
         WHENET_REQUIRE(value >= 1, WHENET_EINVAL, "min_lane_crops must be >= 1");
         min_lane_crops_ = int(value);
-        sync();
-        drop_graphs();
     } else if (key == "repeat") {
         WHENET_REQUIRE(value >= 1 && value <= 16, WHENET_EINVAL, "repeat must be 1..16");
         repeat_ = int(value);
-        sync();
-        drop_graphs();
     } else {
         throw Error(WHENET_EINVAL, "unknown option '" + key + "'");
     }
+    // every key that did not return above changes what a forward enqueues: nothing in flight, no graph of the old schedule
+    // ("graph", "poison", "host_lanes" and "host_pinned_max" return early: they are read per call and no graph depends on them)
+    sync();
+    drop_graphs();
 }
 
 void Engine::get_info(whenet_info_t* out) const {
@@ -374,13 +315,7 @@ void Engine::drop_graphs() {
 }
 
 void Engine::release_arena() {
-    void** arena[] = {&x0_, &x1_, &e_, &d_, &hc_, reinterpret_cast<void**>(&partial_), reinterpret_cast<void**>(&gate_), reinterpret_cast<void**>(&hcount_),
-                      reinterpret_cast<void**>(&in_u8_), reinterpret_cast<void**>(&o_ypr_),
-                      reinterpret_cast<void**>(&o_amax_), reinterpret_cast<void**>(&o_logits_)};
-    for (void** p : arena) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
+    for (ArenaBuf& a : arena_) a.buf.release();
     cap_ = 0;
     arena_bytes_ = 0;
 }
@@ -391,35 +326,21 @@ void Engine::ensure_capacity(int n) {
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     drop_graphs();
     release_arena();
-    const size_t N = size_t(n), es = esz();
+    const size_t N = size_t(n);
     size_t total = 0;
-    auto alloc = [&](size_t bytes) {
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
+    for (ArenaBuf& a : arena_) {
+        const hipError_t e = a.buf.try_reset(N * a.per_crop);
         if (e != hipSuccess) {
             release_arena();
             throw Error(WHENET_ENOMEM, "activation arena for n=" + std::to_string(n) + ": " + hipGetErrorString(e));
         }
-        total += bytes;
-        return p;
-    };
-    x0_ = alloc(N * X_ELEMS * es);
-    x1_ = alloc(N * X_ELEMS * es);
-    e_ = alloc(N * E_ELEMS * es);
-    d_ = alloc(N * D_ELEMS * es);
-    hc_ = alloc(N * HC_ELEMS * es);
-    partial_ = static_cast<float*>(alloc(N * partial_per_crop_ * sizeof(float)));
-    gate_ = static_cast<float*>(alloc(N * 1152 * sizeof(float)));
-    hcount_ = static_cast<unsigned*>(alloc(N * sizeof(unsigned)));
+        total += a.buf.bytes();
+    }
     // (on the engine's OWN stream, and complete before any forward is enqueued: hipMemset runs on the null stream, which
     //  the engine's non-blocking streams do not wait for -- with other engines keeping the GPU busy it used to land in
     //  the middle of this engine's first heads kernel and leave the per-crop ticket counters off by one for good)
-    WHENET_HIP_CHECK(hipMemsetAsync(hcount_, 0, N * sizeof(unsigned), stream_));
+    WHENET_HIP_CHECK(hipMemsetAsync(arena_[A_HCOUNT].buf.as<void>(), 0, N * sizeof(unsigned), stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-    in_u8_ = static_cast<uint8_t*>(alloc(N * IN_BYTES));
-    o_ypr_ = static_cast<float*>(alloc(N * 3 * sizeof(float)));
-    o_amax_ = static_cast<int32_t*>(alloc(N * 3 * sizeof(int32_t)));
-    o_logits_ = static_cast<float*>(alloc(N * N_LOGITS * sizeof(float)));
     cap_ = n;
     arena_bytes_ = total;
 }
@@ -447,8 +368,8 @@ struct Rec {
             e.kernel = kernel;
             e.bytes = bytes;
             e.flops = flops;
-            WHENET_HIP_CHECK(hipEventCreate(&e.stop));
-            rec->entries.push_back(e);
+            e.stop.create(hipEventDefault);
+            rec->entries.push_back(std::move(e));
         }
         LaunchRecorder::Entry& e = rec->entries.at(rec->cursor++);
         fn();
@@ -558,24 +479,63 @@ void* Engine::enqueue_blocks(int first, int last, const View& v, void* cur, int 
 
 void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, void* out, int n, hipStream_t s,
                            LaunchRecorder* rec, int fold, bool dw_done, bool in_blocked, bool out_blocked) {
+    const BlockSpec& sp = b.spec;
+    const BlockSchedule bs = block_schedule(b, n);
+    // (checked before anything is enqueued: a violated invariant must not leave half a block in a stream capture)
+    WHENET_REQUIRE(fold == 0 || (fold == 1 && !bs.fused && sp.index == 1) ||
+                       (fold == 2 && sp.index == 2 && (bs.use_f2 || (split_ && bs.fused && !bs.use_f2s && !bs.use_f7))), WHENET_EINVAL,
+                   "fold12: block outside the folded pair");
+    WHENET_REQUIRE(!(in_blocked || out_blocked) || (dtype_ == WHENET_F16 && !bs.use_mb7 && (!in_blocked || bs.use_f7)),
+                   WHENET_EINVAL, "act_layout: a kernel of this block does not know the blocked layout");
+    WHENET_REQUIRE(!bs.use_mb7 || fold == 0, WHENET_EINVAL, "mb7: block outside the 7 x 7 stage");
+    if (bs.fused) enqueue_front(b, bs, v, in, out, n, s, rec, fold, in_blocked);
+    else enqueue_expand_dw(b, v, in, fold == 1 ? out : v.d, n, s, rec, dw_done);
+    if (bs.use_mb7) return;              // that one launch was the whole block
+    const SeFuse sef = enqueue_se(b, bs, v, n, s, rec, fold);
+    if (fold != 1) enqueue_project(b, sef, bs.se_fused, v, in, out, n, s, rec, in_blocked, out_blocked);
+}
+
+// The fields the four front kernels' argument structs share (kernels.h); the three tiled kinds add their geometry.
+template <typename A>
+void Engine::fill_front_common(A& a, const DevBlock& b, const View& v, const void* in, int n) const {
+    a.x = in;
+    a.be = b.expand.bias;
+    a.bd = b.dw.bias;
+    a.out = v.d;
+    a.rpart = v.partial;
+    a.w1t = b.se.w1t;                    // the SE reduce conv is applied by the front kernel to its channel sums
+    a.R = b.se.R;
+    a.k = b.spec.k;
+    a.Cin = b.spec.cin;
+    a.Cexp = b.spec.cexp();
+    a.NTe = b.expand.NTILES;
+    a.n = n;
+}
+
+namespace {
+template <typename A>
+void fill_front_tiled(A& a, const DevBlock& b) {
+    a.s = b.spec.s;
+    a.H = b.spec.h_in;
+    a.Ho = b.spec.h_out;
+    a.pad = b.spec.pad_before();
+    a.KSe = b.expand.KS;
+}
+}  // namespace
+
+void Engine::enqueue_front(const DevBlock& b, const BlockSchedule& bs, const View& v, const void* in, void* out, int n,
+                           hipStream_t s, LaunchRecorder* rec, int fold, bool in_blocked) {
     Rec R{rec, s, repeat_};
     const BlockSpec& sp = b.spec;
     const std::string p = "b" + std::to_string(sp.index);
     const double es = double(esz());
     const int hw_in = sp.h_in * sp.h_in, hw_out = sp.h_out * sp.h_out;
     const int cexp = sp.cexp();
-    const void* dw_in = in;
-    const BlockSchedule bs = block_schedule(b, n);
-    const bool fused = bs.fused, use_f2 = bs.use_f2, se_in_front = bs.se_in_front, se_fused = bs.se_fused;
-    const int se_ntiles = bs.se_ntiles, se_chunks = bs.se_chunks;
-    // (checked before anything is enqueued: a violated invariant must not leave half a block in a stream capture)
-    WHENET_REQUIRE(fold == 0 || (fold == 1 && !fused && sp.index == 1) ||
-                       (fold == 2 && sp.index == 2 && (use_f2 || (split_ && fused && !bs.use_f2s && !bs.use_f7))), WHENET_EINVAL,
-                   "fold12: block outside the folded pair");
-    WHENET_REQUIRE(!(in_blocked || out_blocked) || (dtype_ == WHENET_F16 && !bs.use_mb7 && (!in_blocked || bs.use_f7)),
-                   WHENET_EINVAL, "act_layout: a kernel of this block does not know the blocked layout");
+    // the stage's algorithmic traffic and work, for a contraction over cin input channels (fold12 changes it)
+    auto bytes = [&](int cin) { return double(n) * (hw_in * cin + hw_out * cexp) * es; };
+    auto flops = [&](int cin) { return 2.0 * n * (double(hw_in) * cin * cexp + double(hw_out) * sp.k * sp.k * cexp); };
+    const bool split = split_ && split_pw_ && b.expand.wps != nullptr;
     if (bs.use_mb7) {
-        WHENET_REQUIRE(fold == 0, WHENET_EINVAL, "mb7: block outside the 7 x 7 stage");
         Mb7Args a{};
         a.x = in;
         a.wep = b.expand.wp;
@@ -601,53 +561,26 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
           double(n) * (hw_in * sp.cin * (a.skip ? 2 : 1) + hw_out * sp.cout) * es,
           2.0 * n * (double(hw_in) * sp.cin * cexp + double(hw_out) * sp.k * sp.k * cexp + double(hw_out) * cexp * sp.cout),
           [&] { launch_mb7(a, s); });
-        return;
-    }
-    if (bs.use_f7) {
+    } else if (bs.use_f7) {
         Front7Args a{};
+        fill_front_common(a, b, v, in, n);
         a.dtype = dtype_;
-        a.x = in;
         a.wep = b.expand.wp;
-        a.be = b.expand.bias;
         a.wdt = dtype_ == WHENET_F16 ? static_cast<const void*>(b.dw.wt7) : static_cast<const void*>(b.dw.w);
-        a.bd = b.dw.bias;
-        a.out = v.d;
-        a.rpart = v.partial;
-        a.w1t = b.se.w1t;                    // the SE reduce conv is applied by the front kernel to its channel sums
-        a.R = b.se.R;
-        a.k = sp.k;
-        a.Cin = sp.cin;
-        a.Cexp = cexp;
-        a.NTe = b.expand.NTILES;
-        a.split = split_ && split_pw_ && b.expand.wps != nullptr;
+        a.split = split;
         a.weps = b.expand.wps;
         a.wsi = b.expand.wsi;
-        a.n = n;
         a.xcd_grouped = xcd_grouped(2, n);
         a.x_blocked = in_blocked;
         a.plan = front7_plan_for(dtype_, sp.cin, cexp, n);
-        R(p + "/front", "front", kernel_name_front7(dtype_, sp.k, a.plan, a.split).c_str(), double(n) * (hw_in * sp.cin + hw_out * cexp) * es,
-          2.0 * n * (double(hw_in) * sp.cin * cexp + double(hw_out) * sp.k * sp.k * cexp), [&] { launch_front7(a, s); });
-    } else if (use_f2) {
+        R(p + "/front", "front", kernel_name_front7(dtype_, sp.k, a.plan, a.split).c_str(), bytes(a.Cin), flops(a.Cin),
+          [&] { launch_front7(a, s); });
+    } else if (bs.use_f2) {
         Front2Args a{};
-        a.x = in;
+        fill_front_common(a, b, v, in, n);
+        fill_front_tiled(a, b);
         a.wep = b.expand.wp;
-        a.be = b.expand.bias;
         a.wdt = b.dw.wt;
-        a.bd = b.dw.bias;
-        a.out = v.d;
-        a.rpart = v.partial;
-        a.w1t = b.se.w1t;                    // the SE reduce conv is applied by the front kernel to its channel sums
-        a.R = b.se.R;
-        a.k = sp.k;
-        a.s = sp.s;
-        a.H = sp.h_in;
-        a.Ho = sp.h_out;
-        a.Cin = sp.cin;
-        a.Cexp = cexp;
-        a.pad = sp.pad_before();
-        a.KSe = b.expand.KS;
-        a.NTe = b.expand.NTILES;
         if (fold == 2) {                     // input = block 1's depthwise output, gated; weights = project1 x expand2
             a.wep = d_fold12_w32_;            // (f32: scaled by the gate, then rounded once -- front2.hip)
             a.be = fold12_pw_.bias;
@@ -656,62 +589,31 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
             a.NTe = fold12_pw_.NTILES;
             a.in_gate = static_cast<const float*>(v.gate);
         }
-        a.n = n;
         a.xcd_grouped = xcd_grouped(1, n);
         a.plan = b.f2plan;
         a.plan.threads = front2_threads(b.f2plan, n);
         R(p + "/front", "front", kernel_name_front2(sp.k, sp.s, a.KSe, a.plan.threads, a.plan.xs, a.in_gate != nullptr).c_str(),
-          double(n) * (hw_in * a.Cin + hw_out * cexp) * es,
-          2.0 * n * (double(hw_in) * a.Cin * cexp + double(hw_out) * sp.k * sp.k * cexp), [&] { launch_front2(a, s); });
+          bytes(a.Cin), flops(a.Cin), [&] { launch_front2(a, s); });
     } else if (bs.use_f2s) {
         Front2sArgs a{};
-        a.x = in;
+        fill_front_common(a, b, v, in, n);
+        fill_front_tiled(a, b);
         a.weps = b.expand.wps;
-        a.be = b.expand.bias;
         a.wdt = b.dw.wts;
-        a.bd = b.dw.bias;
-        a.out = v.d;
-        a.rpart = v.partial;
-        a.w1t = b.se.w1t;                    // the SE reduce conv is applied by the front kernel to its channel sums
-        a.R = b.se.R;
-        a.k = sp.k;
-        a.s = sp.s;
-        a.H = sp.h_in;
-        a.Ho = sp.h_out;
-        a.Cin = sp.cin;
-        a.Cexp = cexp;
-        a.pad = sp.pad_before();
         a.KSe = b.expand.KSs;
-        a.NTe = b.expand.NTILES;
         a.wsi = b.expand.wsi;
         a.wsi_d = b.dw.wts_wsi;
         a.tm = b.f2s_tm;
-        a.n = n;
         a.plan = b.f2splan;
-        R(p + "/front", "front", kernel_name_front2s(sp.k, sp.s, a.KSe, a.plan.threads, a.tm, false).c_str(),
-          double(n) * (hw_in * sp.cin + hw_out * cexp) * es,
-          2.0 * n * (double(hw_in) * sp.cin * cexp + double(hw_out) * sp.k * sp.k * cexp), [&] { launch_front2s(a, s); });
-    } else if (fused) {
+        R(p + "/front", "front", kernel_name_front2s(sp.k, sp.s, a.KSe, a.plan.threads, a.tm, false).c_str(), bytes(a.Cin),
+          flops(a.Cin), [&] { launch_front2s(a, s); });
+    } else {
         FrontArgs a{};
-        a.x = in;
+        fill_front_common(a, b, v, in, n);
+        fill_front_tiled(a, b);
         a.wep = b.expand.wp;
-        a.be = b.expand.bias;
         a.wd = b.dw.w;
-        a.bd = b.dw.bias;
-        a.out = v.d;
-        a.rpart = v.partial;
-        a.w1t = b.se.w1t;                    // the SE reduce conv is applied by the front kernel to its channel sums
-        a.R = b.se.R;
-        a.k = sp.k;
-        a.s = sp.s;
-        a.H = sp.h_in;
-        a.Ho = sp.h_out;
-        a.Cin = sp.cin;
-        a.Cexp = cexp;
-        a.pad = sp.pad_before();
-        a.KSe = b.expand.KS;
-        a.NTe = b.expand.NTILES;
-        a.split = split_ && split_pw_ && b.expand.wps != nullptr;
+        a.split = split;
         a.weps = b.expand.wps;
         a.KSes = b.expand.KSs;
         a.wsi = b.expand.wsi;
@@ -725,36 +627,34 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
             a.wsi = fold12_pw_.wsi;
             a.in_gate = static_cast<const float*>(v.gate);
         }
-        a.n = n;
         a.xcd_grouped = xcd_grouped(1, n);
         a.plan = b.fplan;
         a.plan.threads = front_threads(b.fplan, n);
-        R(p + "/front", "front", kernel_name_front(dtype_, sp.k, sp.s, a.plan.threads).c_str(), double(n) * (hw_in * a.Cin + hw_out * cexp) * es,
-          2.0 * n * (double(hw_in) * a.Cin * cexp + double(hw_out) * sp.k * sp.k * cexp),
+        R(p + "/front", "front", kernel_name_front(dtype_, sp.k, sp.s, a.plan.threads).c_str(), bytes(a.Cin), flops(a.Cin),
           [&] { launch_front(a, dtype_, s); });
-    } else if (sp.has_expand()) {
-        PwArgs a{};
-        a.a = in;
-        a.wp = b.expand.wp;
-        a.wdense = b.expand.wdense;
-        a.bias = b.expand.bias;
-        a.out = v.e;
-        a.M = n * hw_in;
-        a.K = b.expand.K;
-        a.N = b.expand.N;
-        a.KS = b.expand.KS;
-        a.NTILES = b.expand.NTILES;
-        set_split(a, b.expand);
-        a.HW = hw_in;
-        a.act = ACT_SWISH;
+    }
+}
+
+// The unfused pair: the expand conv (blocks that have one) into v.e, then the depthwise conv into dw_out.
+void Engine::enqueue_expand_dw(const DevBlock& b, const View& v, const void* in, void* dw_out, int n, hipStream_t s,
+                               LaunchRecorder* rec, bool dw_done) {
+    Rec R{rec, s, repeat_};
+    const BlockSpec& sp = b.spec;
+    const std::string p = "b" + std::to_string(sp.index);
+    const double es = double(esz());
+    const int hw_in = sp.h_in * sp.h_in, hw_out = sp.h_out * sp.h_out;
+    const int cexp = sp.cexp();
+    const void* dw_in = in;
+    if (sp.has_expand()) {
+        const PwArgs a = pw_args(b.expand, in, v.e, n * hw_in, hw_in, ACT_SWISH);
         R(p + "/expand", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(), double(a.M) * (a.K + a.N) * es,
           2.0 * a.M * a.K * a.N, [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
         dw_in = v.e;
     }
-    if (!fused && !dw_done) {
+    if (!dw_done) {
         DwArgs a{};
         a.in = dw_in;
-        a.out = fold == 1 ? out : v.d;
+        a.out = dw_out;
         a.w = b.dw.w;
         a.bias = b.dw.bias;
         a.partial = v.partial;
@@ -769,21 +669,28 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
         R(p + "/dw", "dw", kernel_name_dw(dtype_, sp.k, sp.s), double(n) * (hw_in + hw_out) * cexp * es,
           2.0 * n * hw_out * sp.k * sp.k * cexp, [&] { launch_dw(a, dtype_, s); });
     }
-    // Second half of the SEBlock.  Where it pays, the project GEMM's workgroups compute the gate of their own rows'
-    // crops from the front kernel's partial vectors in their prologue (se_device.h; no launch, the gate never reaches
-    // HBM); otherwise a stand-alone launch writes the gate.  Measured per block at 64 crops (tools/ab_layers.sh,
-    // se_fuse=2 against 0): every workgroup has to pull the WHOLE excite kernel (K x R floats) and all partial vectors
-    // of its crops, so the prologue costs +1 us for blocks 4-6 (<= 12 KB, <= 20 vectors: a 7-8 us launch saved), +7 /
-    // +12 us for blocks 3 / 2 (40 / 48 partial vectors: three dependent round trips), +4..9 us for the 14x14 blocks
-    // (38-75 KB: break-even) and +24 us for the 7x7 blocks (221 KB per workgroup at ~50 GB/s per CU).  The bits are
-    // the same either way.  Option se_fuse: 0 = never, 1 = where it pays (default), 2 = every fused-front block.
+}
+
+// Second half of the SEBlock.  Where it pays, the project GEMM's workgroups compute the gate of their own rows'
+// crops from the front kernel's partial vectors in their prologue (se_device.h; no launch, the gate never reaches
+// HBM); otherwise a stand-alone launch writes the gate.  Measured per block at 64 crops (tools/ab_layers.sh,
+// se_fuse=2 against 0): every workgroup has to pull the WHOLE excite kernel (K x R floats) and all partial vectors
+// of its crops, so the prologue costs +1 us for blocks 4-6 (<= 12 KB, <= 20 vectors: a 7-8 us launch saved), +7 /
+// +12 us for blocks 3 / 2 (40 / 48 partial vectors: three dependent round trips), +4..9 us for the 14x14 blocks
+// (38-75 KB: break-even) and +24 us for the 7x7 blocks (221 KB per workgroup at ~50 GB/s per CU).  The bits are
+// the same either way.  Option se_fuse: 0 = never, 1 = where it pays (default), 2 = every fused-front block.
+SeFuse Engine::enqueue_se(const DevBlock& b, const BlockSchedule& bs, const View& v, int n, hipStream_t s, LaunchRecorder* rec,
+                          int fold) {
+    Rec R{rec, s, repeat_};
+    const std::string p = "b" + std::to_string(b.spec.index);
+    const int hw_out = b.spec.h_out * b.spec.h_out;
     SeFuse sef{};
-    if (se_fused) {
+    if (bs.se_fused) {
         sef.rpart = v.partial;
         sef.b1 = b.se.b1;
         sef.w2c = b.se.w2c;
         sef.b2 = b.se.b2;
-        sef.np = se_ntiles * se_chunks;
+        sef.np = bs.se_ntiles * bs.se_chunks;
         sef.R = b.se.R;
         sef.RP = se_padded_r(b.se.R);
         sef.inv_hw = 1.0f / float(hw_out);
@@ -792,12 +699,12 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
             sef.KSr = b.se.KSr;
             sef.w2_wsi = b.se.w2_wsi;
         }
-    } else if (se_in_front) {
+    } else if (bs.se_in_front) {
         // the front kernel already applied se_reduce to its channel sums (v.partial holds the
         // (tiles x chunks) partial vectors of every crop): finish the SEBlock
         SeExciteArgs a{};
         a.rpart = v.partial;
-        a.np = se_ntiles * se_chunks;
+        a.np = bs.se_ntiles * bs.se_chunks;
         a.inv_hw = 1.0f / float(hw_out);
         a.b1 = b.se.b1;
         a.w2c = b.se.w2c;
@@ -813,7 +720,7 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
     } else {
         SeArgs a{};
         a.partial = v.partial;
-        a.ntiles = se_ntiles;
+        a.ntiles = bs.se_ntiles;
         a.inv_hw = 1.0f / float(hw_out);
         a.w1t = b.se.w1t;
         a.b1 = b.se.b1;
@@ -827,34 +734,67 @@ void Engine::enqueue_block(const DevBlock& b, const View& v, const void* in, voi
         R(p + "/se", "se", ("whenet_se_kernel<" + std::to_string(se_padded_r(a.R)) + ">").c_str(), double(n) * (a.ntiles + 1) * a.C * 4.0 + 2.0 * a.C * a.R * 4.0,
           4.0 * n * a.C * a.R, [&] { launch_se(a, s); });
     }
-    if (fold != 1) {
-        PwArgs a{};
-        a.a = v.d;
-        a.wp = b.project.wp;
-        a.wdense = b.project.wdense;
-        a.bias = b.project.bias;
-        a.gate = se_fused ? nullptr : v.gate;
-        a.se = sef;
-        a.res = sp.has_skip() ? in : nullptr;
-        a.out = out;
-        a.M = n * hw_out;
-        a.K = b.project.K;
-        a.N = b.project.N;
-        a.KS = b.project.KS;
-        a.NTILES = b.project.NTILES;
-        set_split(a, b.project);
-        a.HW = hw_out;
-        a.act = ACT_NONE;
-        a.out_blocked = out_blocked;
-        a.res_blocked = in_blocked && sp.has_skip();
-        R(p + "/project", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(),
-          double(a.M) * (a.K + a.N + (sp.has_skip() ? a.N : 0)) * es, 2.0 * a.M * a.K * a.N,
-          [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
-    }
+    return sef;
 }
 
-void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits,
-                             hipStream_t s, LaunchRecorder* rec, const float* d_in_f32) {
+void Engine::enqueue_project(const DevBlock& b, const SeFuse& sef, bool se_fused, const View& v, const void* in, void* out, int n,
+                             hipStream_t s, LaunchRecorder* rec, bool in_blocked, bool out_blocked) {
+    Rec R{rec, s, repeat_};
+    const BlockSpec& sp = b.spec;
+    const int hw_out = sp.h_out * sp.h_out;
+    PwArgs a = pw_args(b.project, v.d, out, n * hw_out, hw_out, ACT_NONE);
+    a.gate = se_fused ? nullptr : v.gate;
+    a.se = sef;
+    a.res = sp.has_skip() ? in : nullptr;
+    a.out_blocked = out_blocked;
+    a.res_blocked = in_blocked && sp.has_skip();
+    R("b" + std::to_string(sp.index) + "/project", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(),
+      double(a.M) * (a.K + a.N + (sp.has_skip() ? a.N : 0)) * double(esz()), 2.0 * a.M * a.K * a.N,
+      [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
+}
+
+Head7Args Engine::head7_args(const void* x, float* feat, int n) const {
+    Head7Args a{};
+    a.dtype = dtype_;
+    a.x = x;
+    a.wep = head_.wp;
+    a.bias = head_.bias;
+    a.feat = feat;
+    a.K = head_.K;
+    a.N = head_.N;
+    a.NTILES = head_.NTILES;
+    a.split = split_ && split_pw_ && head_.wps != nullptr;
+    a.weps = head_.wps;
+    a.wsi = head_.wsi;
+    a.n = n;
+    return a;
+}
+
+PwArgs Engine::pw_args(const DevPw& w, const void* a, void* out, int M, int HW, int act) const {
+    PwArgs r{};
+    r.a = a;
+    r.wp = w.wp;
+    r.wdense = w.wdense;
+    r.bias = w.bias;
+    r.out = out;
+    r.M = M;
+    r.K = w.K;
+    r.N = w.N;
+    r.KS = w.KS;
+    r.NTILES = w.NTILES;
+    r.HW = HW;
+    r.act = act;
+    // WHENET_F32S: 1x1 products as binary16 hi/lo pairs (option "split_pw" switches the pointwise kernels between the two forms)
+    r.staged = pw_staged_;
+    r.split = split_ && split_pw_ && w.wps != nullptr;
+    r.wps = w.wps;
+    r.KSs = w.KSs;
+    r.wsi = w.wsi;
+    return r;
+}
+
+void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, Results out, hipStream_t s, LaunchRecorder* rec,
+                             const float* d_in_f32) {
     Rec R{rec, s, repeat_};
     const double es = double(esz());
     const bool stemdw = stem_fuse_active() && d_in_f32 == nullptr;
@@ -883,83 +823,45 @@ void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, float* d
           [&] { launch_stem(a, dtype_, s); });
     }
     void* cur = enqueue_blocks(1, int(blocks_.size()), v, v.x0, n, s, rec, stemdw);
-    const bool fuse_head = head_fused();
-    if (fuse_head) {
+    HeadsArgs h{};
+    h.w = d_dense_w_;
+    h.b = d_dense_b_;
+    h.logits = out.logits;
+    h.ypr = out.ypr;
+    h.argmax = out.amax;
+    h.n = n;
+    if (head_fused()) {
         // head conv + GlobalAveragePooling2D as one kernel (head7.hip): v.hc receives the pooled features [n][1280] f32
-        Head7Args a{};
-        a.dtype = dtype_;
-        a.x = cur;
-        a.wep = head_.wp;
-        a.bias = head_.bias;
-        a.feat = reinterpret_cast<float*>(v.hc);
-        a.K = head_.K;
-        a.N = head_.N;
-        a.NTILES = head_.NTILES;
-        a.split = split_ && split_pw_ && head_.wps != nullptr;
-        a.weps = head_.wps;
-        a.wsi = head_.wsi;
-        a.n = n;
+        Head7Args a = head7_args(cur, reinterpret_cast<float*>(v.hc), n);
         a.xcd_grouped = xcd_grouped(4, n);
         a.x_blocked = act_blocked(int(blocks_.size()));
         R("head", "pw", kernel_name_head7(dtype_, n, a.split).c_str(), double(n) * (49.0 * a.K * es + a.N * 4.0), 2.0 * n * 49.0 * a.K * a.N,
           [&] { launch_head7(a, s); });
-        HeadsArgs hargs{};
-        hargs.feat_in = reinterpret_cast<const float*>(v.hc);
-        hargs.w = d_dense_w_;
-        hargs.b = d_dense_b_;
-        hargs.logits = d_logits;
-        hargs.ypr = d_ypr;
-        hargs.argmax = d_amax;
-        hargs.n = n;
+        h.feat_in = reinterpret_cast<const float*>(v.hc);
         R("heads", "heads", "whenet_heads_split_kernel<float, true>", double(n) * ((FEAT + N_LOGITS + 6) * 4.0) + double(FEAT) * N_LOGITS * 4.0,
-          2.0 * n * FEAT * N_LOGITS, [&] { launch_heads_split(hargs, v.partial, v.hcount, dtype_, s); });
+          2.0 * n * FEAT * N_LOGITS, [&] { launch_heads_split(h, v.partial, v.hcount, dtype_, s); });
         return;
     }
-    {
-        PwArgs a{};
-        a.a = cur;
-        a.wp = head_.wp;
-        a.wdense = head_.wdense;
-        a.bias = head_.bias;
-        a.out = v.hc;
-        a.M = n * 49;
-        a.K = head_.K;
-        a.N = head_.N;
-        a.KS = head_.KS;
-        a.NTILES = head_.NTILES;
-        set_split(a, head_);
-        a.HW = 49;
-        a.act = ACT_SWISH;
-        R("head", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(), double(a.M) * (a.K + a.N) * es,
-          2.0 * a.M * a.K * a.N, [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
-    }
-    {
-        HeadsArgs a{};
-        a.x = v.hc;
-        a.w = d_dense_w_;
-        a.b = d_dense_b_;
-        a.logits = d_logits;
-        a.ypr = d_ypr;
-        a.argmax = d_amax;
-        a.n = n;
-        // (v.partial is free here: the last squeeze-excite is long done)
-        const bool split = split_heads_ && partial_per_crop_ >= size_t(heads_split()) * N_LOGITS;
-        const std::string hname = std::string(split ? "whenet_heads_split_kernel<" : "whenet_heads_kernel<") +
-                                  (dtype_ == WHENET_F16 ? "_Float16" : "float") + (split ? ", false>" : ">");
-        R("heads", "heads", hname.c_str(),
-          double(n) * (HC_ELEMS * es + (N_LOGITS + 6) * 4.0) + double(FEAT) * N_LOGITS * 4.0, 2.0 * n * FEAT * N_LOGITS,
-          [&] {
-              if (split) launch_heads_split(a, v.partial, v.hcount, dtype_, s);
-              else launch_heads(a, dtype_, s);
-          });
-    }
+    const PwArgs a = head_pw_args(cur, v.hc, n);
+    R("head", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(), double(a.M) * (a.K + a.N) * es, 2.0 * a.M * a.K * a.N,
+      [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
+    h.x = v.hc;
+    // (v.partial is free here: the last squeeze-excite is long done)
+    const bool split = split_heads_ && partial_per_crop_ >= size_t(heads_split()) * N_LOGITS;
+    const std::string hname = std::string(split ? "whenet_heads_split_kernel<" : "whenet_heads_kernel<") +
+                              (dtype_ == WHENET_F16 ? "_Float16" : "float") + (split ? ", false>" : ">");
+    R("heads", "heads", hname.c_str(), double(n) * (HC_ELEMS * es + (N_LOGITS + 6) * 4.0) + double(FEAT) * N_LOGITS * 4.0,
+      2.0 * n * FEAT * N_LOGITS, [&] {
+          if (split) launch_heads_split(h, v.partial, v.hcount, dtype_, s);
+          else launch_heads(h, dtype_, s);
+      });
 }
 
 hipStream_t Engine::lane_stream(int i) {
     while (int(lane_streams_.size()) <= i) {
-        hipStream_t st = nullptr;
-        WHENET_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        lane_streams_.push_back(st);
+        Stream st;
+        WHENET_HIP_CHECK(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
+        lane_streams_.push_back(std::move(st));
     }
     return lane_streams_[size_t(i)];
 }
@@ -971,28 +873,28 @@ void Engine::release_aux_streams() {
     DeviceGuard guard(device_);
     sync();
     drop_graphs();
-    for (hipStream_t st : lane_streams_) (void)hipStreamDestroy(st);
     lane_streams_.clear();
-    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
-    copy_stream_ = nullptr;
+    copy_stream_.reset();
 }
 
 hipStream_t Engine::copy_stream() {
-    if (!copy_stream_) WHENET_HIP_CHECK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
+    if (!copy_stream_) WHENET_HIP_CHECK(hipStreamCreateWithFlags(copy_stream_.put(), hipStreamNonBlocking));
     return copy_stream_;
 }
 
 Engine::View Engine::view(int crop_off) const {
-    const size_t o = size_t(crop_off), es = esz();
+    auto at = [&](int i) { return arena_[i].buf.as<char>() + size_t(crop_off) * arena_[i].per_crop; };
     View v;
-    v.x0 = static_cast<char*>(x0_) + o * X_ELEMS * es;
-    v.x1 = static_cast<char*>(x1_) + o * X_ELEMS * es;
-    v.e = static_cast<char*>(e_) + o * E_ELEMS * es;
-    v.d = static_cast<char*>(d_) + o * D_ELEMS * es;
-    v.hc = static_cast<char*>(hc_) + o * HC_ELEMS * es;
-    v.partial = partial_ + o * partial_per_crop_;
-    v.hcount = hcount_ + o;
-    v.gate = gate_ + o * 1152;
+    v.x0 = at(A_X0);
+    v.x1 = at(A_X1);
+    v.e = at(A_E);
+    v.d = at(A_D);
+    v.hc = at(A_HC);
+    v.partial = reinterpret_cast<float*>(at(A_PARTIAL));
+    v.gate = reinterpret_cast<float*>(at(A_GATE));
+    v.hcount = reinterpret_cast<unsigned*>(at(A_HCOUNT));
+    v.in_u8 = reinterpret_cast<uint8_t*>(at(A_IN_U8));
+    v.out = {reinterpret_cast<float*>(at(A_YPR)), reinterpret_cast<int32_t*>(at(A_AMAX)), reinterpret_cast<float*>(at(A_LOGITS))};
     return v;
 }
 
@@ -1007,27 +909,32 @@ int Engine::lanes_for(int n, int want) const {
     return lanes;
 }
 
-void Engine::enqueue_lanes(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want) {
-    const int lanes = lanes_for(n, want);
-    if (lanes <= 1) {
-        enqueue_forward(view(0), d_in, n, d_ypr, d_amax, d_logits, s, nullptr);
-        return;
-    }
+template <typename F>
+void Engine::for_each_lane(int n, int lanes, hipStream_t s, F&& body) {
     WHENET_HIP_CHECK(hipEventRecord(fork_ev_, s));
     int off = 0;
     for (int i = 0; i < lanes; ++i) {
         const int cnt = n / lanes + (i < n % lanes ? 1 : 0);
         hipStream_t st = (i == 0) ? s : lane_stream(i - 1);
         if (i > 0) WHENET_HIP_CHECK(hipStreamWaitEvent(st, fork_ev_, 0));
-        enqueue_forward(view(off), d_in + size_t(off) * IN_BYTES, cnt, d_ypr + size_t(off) * 3,
-                        d_amax ? d_amax + size_t(off) * 3 : nullptr, d_logits ? d_logits + size_t(off) * N_LOGITS : nullptr,
-                        st, nullptr);
+        body(i, off, cnt, st);
         if (i > 0) {
             WHENET_HIP_CHECK(hipEventRecord(join_ev_[size_t(i - 1)], st));
             WHENET_HIP_CHECK(hipStreamWaitEvent(s, join_ev_[size_t(i - 1)], 0));
         }
         off += cnt;
     }
+}
+
+void Engine::enqueue_lanes(const uint8_t* d_in, int n, Results out, hipStream_t s, int want) {
+    const int lanes = lanes_for(n, want);
+    if (lanes <= 1) {
+        enqueue_forward(view(0), d_in, n, out, s, nullptr);
+        return;
+    }
+    for_each_lane(n, lanes, s, [&](int, int off, int cnt, hipStream_t st) {
+        enqueue_forward(view(off), d_in + size_t(off) * IN_BYTES, cnt, out.at(size_t(off)), st, nullptr);
+    });
 }
 
 // Capture fn's launches on stream s into an executable graph (cached under key) and return it.
@@ -1061,20 +968,14 @@ hipGraphExec_t Engine::cached_graph(const GraphKey& key, hipStream_t s, F&& fn) 
 // debug option "poison": every activation buffer holds NaN bit patterns when the forward starts, so a kernel that reads what no
 // kernel of THIS forward wrote shows up in the results (tests/test_gpu_parity.py)
 void Engine::poison_arena(int n, hipStream_t s) {
-    const size_t N = size_t(n), es = esz();
-    WHENET_HIP_CHECK(hipMemsetAsync(x0_, 0xff, N * X_ELEMS * es, s));
-    WHENET_HIP_CHECK(hipMemsetAsync(x1_, 0xff, N * X_ELEMS * es, s));
-    WHENET_HIP_CHECK(hipMemsetAsync(e_, 0xff, N * E_ELEMS * es, s));
-    WHENET_HIP_CHECK(hipMemsetAsync(d_, 0xff, N * D_ELEMS * es, s));
-    WHENET_HIP_CHECK(hipMemsetAsync(hc_, 0xff, N * HC_ELEMS * es, s));
-    WHENET_HIP_CHECK(hipMemsetAsync(partial_, 0xff, N * partial_per_crop_ * sizeof(float), s));
-    WHENET_HIP_CHECK(hipMemsetAsync(gate_, 0xff, N * 1152 * sizeof(float), s));
+    for (int i = 0; i < A_POISONED; ++i)
+        WHENET_HIP_CHECK(hipMemsetAsync(arena_[i].buf.as<void>(), 0xff, size_t(n) * arena_[i].per_crop, s));
 }
 
-void Engine::run_forward(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want) {
+void Engine::run_forward(const uint8_t* d_in, int n, Results out, hipStream_t s, int want) {
     if (poison_) poison_arena(n, s);
     if (!use_graph_) {
-        enqueue_lanes(d_in, n, d_ypr, d_amax, d_logits, s, want);
+        enqueue_lanes(d_in, n, out, s, want);
         return;
     }
     const int lanes = lanes_for(n, want);
@@ -1082,30 +983,18 @@ void Engine::run_forward(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_am
     if (lane_graphs_ && lanes > 1) {
         // One graph PER LANE, each launched on its own stream: the chains then run as independent queues.
         // (Branches of a single graph cost ~5 us per edge on this runtime, which eats the overlap.)
-        WHENET_HIP_CHECK(hipEventRecord(fork_ev_, s));
-        int off = 0;
-        for (int i = 0; i < lanes; ++i) {
-            const int cnt = n / lanes + (i < n % lanes ? 1 : 0);
-            hipStream_t st = (i == 0) ? s : lane_stream(i - 1);
+        // (The lane's wait on the fork event is enqueued before its graph is built: a capture enqueues nothing on the stream.)
+        for_each_lane(n, lanes, s, [&](int, int off, int cnt, hipStream_t st) {
             const uint8_t* in_i = d_in + size_t(off) * IN_BYTES;
-            float* ypr_i = d_ypr + size_t(off) * 3;
-            int32_t* am_i = d_amax ? d_amax + size_t(off) * 3 : nullptr;
-            float* lg_i = d_logits ? d_logits + size_t(off) * N_LOGITS : nullptr;
-            hipGraphExec_t g = cached_graph(GraphKey{cnt, off, in_i, ypr_i, am_i, lg_i}, st, [&] {
-                enqueue_forward(view(off), in_i, cnt, ypr_i, am_i, lg_i, st, nullptr);
-            });
-            if (i > 0) WHENET_HIP_CHECK(hipStreamWaitEvent(st, fork_ev_, 0));
+            const Results out_i = out.at(size_t(off));
+            hipGraphExec_t g = cached_graph(GraphKey{cnt, off, in_i, out_i.ypr, out_i.amax, out_i.logits}, st,
+                                            [&] { enqueue_forward(view(off), in_i, cnt, out_i, st, nullptr); });
             WHENET_HIP_CHECK(hipGraphLaunch(g, st));
-            if (i > 0) {
-                WHENET_HIP_CHECK(hipEventRecord(join_ev_[size_t(i - 1)], st));
-                WHENET_HIP_CHECK(hipStreamWaitEvent(s, join_ev_[size_t(i - 1)], 0));
-            }
-            off += cnt;
-        }
+        });
         return;
     }
-    hipGraphExec_t g = cached_graph(GraphKey{n, -lanes, d_in, d_ypr, d_amax, d_logits}, s,
-                                    [&] { enqueue_lanes(d_in, n, d_ypr, d_amax, d_logits, s, lanes); });
+    hipGraphExec_t g = cached_graph(GraphKey{n, -lanes, d_in, out.ypr, out.amax, out.logits}, s,
+                                    [&] { enqueue_lanes(d_in, n, out, s, lanes); });
     WHENET_HIP_CHECK(hipGraphLaunch(g, s));
 }
 
@@ -1119,7 +1008,7 @@ void Engine::forward_device(const uint8_t* d_crops, int n, float* d_ypr, int32_t
     WHENET_REQUIRE(d_crops != nullptr && d_ypr != nullptr, WHENET_EINVAL, "crops and ypr must not be NULL");
     WHENET_REQUIRE((reinterpret_cast<uintptr_t>(d_crops) & 3) == 0, WHENET_EINVAL, "crops must be 4-byte aligned");
     ensure_capacity(n);
-    run_forward(d_crops, n, d_ypr, d_argmax, d_logits, stream ? stream : stream_);
+    run_forward(d_crops, n, Results{d_ypr, d_argmax, d_logits}, stream ? stream : stream_);
 }
 
 void Engine::forward_host(const uint8_t* crops, int n, float* ypr, int32_t* argmax, float* logits) {
@@ -1128,6 +1017,7 @@ void Engine::forward_host(const uint8_t* crops, int n, float* ypr, int32_t* argm
     WHENET_REQUIRE(crops != nullptr && ypr != nullptr, WHENET_EINVAL, "crops and ypr must not be NULL");
     ensure_capacity(n);
     const size_t N = size_t(n);
+    const Results caller{ypr, argmax, logits};
     if (n <= host_pinned_max_) {
         // The reference's own call shape -- get_angle(uint8[1,224,224,3]) per head (demo.py:14, demo_video.py:27): latency.
         // Copies to and from PAGEABLE memory are synchronous inside the runtime (the three result copies each wait for the
@@ -1135,36 +1025,27 @@ void Engine::forward_host(const uint8_t* crops, int n, float* ypr, int32_t* argm
         // H2D -> graph -> 3 D2H, all asynchronous on ONE stream, one wait, memcpy out (round 5: 490 -> see DESIGN us at B=1 f32).
         Slot& sl = host_slot_;
         ensure_slot(sl, std::max(n, std::min(host_pinned_max_, 16)));
-        std::memcpy(sl.h_in, crops, N * IN_BYTES);
-        WHENET_HIP_CHECK(hipMemcpyAsync(sl.d_in, sl.h_in, N * IN_BYTES, hipMemcpyHostToDevice, stream_));
-        run_forward(sl.d_in, n, sl.d_ypr, sl.d_amax, sl.d_logits, stream_, host_lanes_);
-        WHENET_HIP_CHECK(hipMemcpyAsync(sl.h_ypr, sl.d_ypr, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-        if (argmax) WHENET_HIP_CHECK(hipMemcpyAsync(sl.h_amax, sl.d_amax, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-        if (logits)
-            WHENET_HIP_CHECK(hipMemcpyAsync(sl.h_logits, sl.d_logits, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        std::memcpy(sl.in.h.as<void>(), crops, N * IN_BYTES);
+        WHENET_HIP_CHECK(hipMemcpyAsync(sl.in.d.as<void>(), sl.in.h.as<void>(), N * IN_BYTES, hipMemcpyHostToDevice, stream_));
+        run_forward(sl.in.d.as<uint8_t>(), n, sl.dev(), stream_, host_lanes_);
+        copy_results_async(sl.host(), sl.dev(), n, stream_, argmax != nullptr, logits != nullptr);
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-        std::memcpy(ypr, sl.h_ypr, N * 3 * sizeof(float));
-        if (argmax) std::memcpy(argmax, sl.h_amax, N * 3 * sizeof(int32_t));
-        if (logits) std::memcpy(logits, sl.h_logits, N * N_LOGITS * sizeof(float));
+        copy_results_host(caller, sl.host(), n);
         return;
     }
     // (Measured, round 4: issuing the copy lane by lane in front of per-lane graphs, so that the first chain runs while the
     //  second lane's crops travel, changes nothing -- 68.5 k vs 69.6 k crops/s at 64 crops: the 9.6 MB copy from pageable
     //  memory is 0.18 ms of a 0.92 ms call, and two graphs on two streams lose what the overlap gains.)
     ensure_host_out(n);
-    WHENET_HIP_CHECK(hipMemcpyAsync(in_u8_, crops, N * IN_BYTES, hipMemcpyHostToDevice, stream_));
+    const View v = view(0);
+    WHENET_HIP_CHECK(hipMemcpyAsync(v.in_u8, crops, N * IN_BYTES, hipMemcpyHostToDevice, stream_));
     // a blocking call has the GPU to itself whatever "inflight" says: the forward runs as host_lanes_ chains
-    run_forward(in_u8_, n, o_ypr_, o_amax_, o_logits_, stream_, host_lanes_);
+    run_forward(v.in_u8, n, v.out, stream_, host_lanes_);
     // results: asynchronous copies into pinned memory, ONE wait (copies into the caller's pageable arrays each wait for the forward
     // and for each other inside the runtime)
-    WHENET_HIP_CHECK(hipMemcpyAsync(hout_ypr_, o_ypr_, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (argmax) WHENET_HIP_CHECK(hipMemcpyAsync(hout_amax_, o_amax_, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    if (logits)
-        WHENET_HIP_CHECK(hipMemcpyAsync(hout_logits_, o_logits_, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    copy_results_async(hout(), v.out, n, stream_, argmax != nullptr, logits != nullptr);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-    std::memcpy(ypr, hout_ypr_, N * 3 * sizeof(float));
-    if (argmax) std::memcpy(argmax, hout_amax_, N * 3 * sizeof(int32_t));
-    if (logits) std::memcpy(logits, hout_logits_, N * N_LOGITS * sizeof(float));
+    copy_results_host(caller, hout(), n);
 }
 
 void Engine::ensure_host_out(int n) {
@@ -1175,15 +1056,14 @@ void Engine::ensure_host_out(int n) {
     static std::mutex mu;
     std::lock_guard<std::mutex> lock(mu);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-    if (hout_ypr_) (void)hipHostFree(hout_ypr_);
-    if (hout_amax_) (void)hipHostFree(hout_amax_);
-    if (hout_logits_) (void)hipHostFree(hout_logits_);
-    hout_ypr_ = nullptr; hout_amax_ = nullptr; hout_logits_ = nullptr;
+    hout_ypr_.release();
+    hout_amax_.release();
+    hout_logits_.release();
     hout_cap_ = 0;
     const size_t N = size_t(std::max(n, 256));
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hout_ypr_), N * 3 * sizeof(float), hipHostMallocDefault));
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hout_amax_), N * 3 * sizeof(int32_t), hipHostMallocDefault));
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hout_logits_), N * N_LOGITS * sizeof(float), hipHostMallocDefault));
+    hout_ypr_.reset(N * 3 * sizeof(float));
+    hout_amax_.reset(N * 3 * sizeof(int32_t));
+    hout_logits_.reset(N * N_LOGITS * sizeof(float));
     hout_cap_ = int(N);
 }
 
@@ -1195,26 +1075,19 @@ void Engine::forward_host_f32(const float* x, int n, float* ypr, int32_t* argmax
     require_model();
     WHENET_REQUIRE(x != nullptr && ypr != nullptr, WHENET_EINVAL, "image and ypr must not be NULL");
     ensure_capacity(n);
-    const size_t N = size_t(n);
-    if (n > in_f32_cap_) {
+    const size_t nbytes = size_t(n) * IN_BYTES * sizeof(float);
+    if (nbytes > in_f32_.bytes()) {
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-        if (in_f32_) (void)hipFree(in_f32_);
-        in_f32_ = nullptr;
-        in_f32_cap_ = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&in_f32_), N * IN_BYTES * sizeof(float));
-        if (e != hipSuccess) throw Error(WHENET_ENOMEM, std::string("float input buffer: ") + hipGetErrorString(e));
-        in_f32_cap_ = n;
+        in_f32_.reset(nbytes, "float input buffer");
     }
     if (poison_) {
         poison_arena(n, stream_);
-        WHENET_HIP_CHECK(hipMemsetAsync(in_f32_, 0xff, size_t(in_f32_cap_) * IN_BYTES * sizeof(float), stream_));
+        WHENET_HIP_CHECK(hipMemsetAsync(in_f32_.as<void>(), 0xff, in_f32_.bytes(), stream_));
     }
-    WHENET_HIP_CHECK(hipMemcpyAsync(in_f32_, x, N * IN_BYTES * sizeof(float), hipMemcpyHostToDevice, stream_));
-    enqueue_forward(view(0), nullptr, n, o_ypr_, o_amax_, o_logits_, stream_, nullptr, in_f32_);
-    WHENET_HIP_CHECK(hipMemcpyAsync(ypr, o_ypr_, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (argmax) WHENET_HIP_CHECK(hipMemcpyAsync(argmax, o_amax_, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    if (logits)
-        WHENET_HIP_CHECK(hipMemcpyAsync(logits, o_logits_, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(in_f32_.as<void>(), x, nbytes, hipMemcpyHostToDevice, stream_));
+    const View v = view(0);
+    enqueue_forward(v, nullptr, n, v.out, stream_, nullptr, in_f32_.as<float>());
+    copy_results_async(Results{ypr, argmax, logits}, v.out, n, stream_, argmax != nullptr, logits != nullptr);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1232,30 +1105,17 @@ void Engine::sync() {
 
 void Engine::ensure_slot(Slot& s, int n) {
     if (!s.copied) {
-        WHENET_HIP_CHECK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-        WHENET_HIP_CHECK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        s.copied.create();
+        s.done.create();
     }
     if (n <= s.capacity) return;
-    if (s.h_in) (void)hipHostFree(s.h_in);
-    if (s.h_ypr) (void)hipHostFree(s.h_ypr);
-    if (s.h_amax) (void)hipHostFree(s.h_amax);
-    if (s.h_logits) (void)hipHostFree(s.h_logits);
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_ypr) (void)hipFree(s.d_ypr);
-    if (s.d_amax) (void)hipFree(s.d_amax);
-    if (s.d_logits) (void)hipFree(s.d_logits);
-    s.h_in = nullptr; s.h_ypr = nullptr; s.h_amax = nullptr; s.h_logits = nullptr;
-    s.d_in = nullptr; s.d_ypr = nullptr; s.d_amax = nullptr; s.d_logits = nullptr;
     s.capacity = 0;
     const size_t N = size_t(n);
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_in), N * IN_BYTES, hipHostMallocDefault));
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_ypr), N * 3 * sizeof(float), hipHostMallocDefault));
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_amax), N * 3 * sizeof(int32_t), hipHostMallocDefault));
-    WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_logits), N * N_LOGITS * sizeof(float), hipHostMallocDefault));
-    WHENET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_in), N * IN_BYTES));
-    WHENET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_ypr), N * 3 * sizeof(float)));
-    WHENET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_amax), N * 3 * sizeof(int32_t)));
-    WHENET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_logits), N * N_LOGITS * sizeof(float)));
+    const size_t bytes[4] = {N * IN_BYTES, N * 3 * sizeof(float), N * 3 * sizeof(int32_t), N * N_LOGITS * sizeof(float)};
+    StagedBuffer* const bufs[4] = {&s.in, &s.ypr, &s.amax, &s.logits};
+    for (StagedBuffer* b : bufs) b->h.release(), b->d.release();      // (all eight go before the first of the larger ones comes)
+    for (int i = 0; i < 4; ++i) bufs[i]->h.reset(bytes[i]);      // (the pinned four first, then the device four)
+    for (int i = 0; i < 4; ++i) bufs[i]->d.reset(bytes[i]);
     s.capacity = n;
 }
 
@@ -1270,19 +1130,27 @@ hipEvent_t Engine::copied_event(int ticket) const {
     throw Error(WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
 }
 
+Engine::Slot* Engine::free_slot() {
+    for (Slot& s : slots_)
+        if (!s.busy) return &s;
+    throw Error(WHENET_EINVAL, "too many submissions in flight (collect one first)");
+}
+
+int Engine::finish_submission(Slot& s, int n) {
+    WHENET_HIP_CHECK(hipEventRecord(s.done, stream_));
+    s.busy = true;
+    s.n = n;
+    s.ticket = next_ticket_++;
+    return s.ticket;
+}
+
 int Engine::submit(const uint8_t* crops, int n, int stage, int want_lanes, hipStream_t copy_on, hipEvent_t copy_after) {
     DeviceGuard guard(device_);
     require_model();
     WHENET_REQUIRE(crops != nullptr, WHENET_EINVAL, "crops must not be NULL");
-    Slot* slot = nullptr;
-    for (Slot& s : slots_)
-        if (!s.busy) {
-            slot = &s;
-            break;
-        }
-    WHENET_REQUIRE(slot != nullptr, WHENET_EINVAL, "too many submissions in flight (collect one first)");
+    Slot& slot = *free_slot();
     ensure_capacity(n);
-    ensure_slot(*slot, n);
+    ensure_slot(slot, n);
     const size_t N = size_t(n);
     // Through a pinned slot: a copy straight from the caller's pageable memory (hipMemcpyAsync stages it inside the runtime)
     // blocks the host until the DMA is done and serialises the submissions -- measured round 4: 67.8 k vs 90.4 k crops/s with
@@ -1291,23 +1159,18 @@ int Engine::submit(const uint8_t* crops, int n, int stage, int want_lanes, hipSt
     // host blocks for THIS chunk's DMA only, while the forwards of the chunks before it run.
     const hipStream_t cs = copy_on != nullptr ? copy_on : copy_stream();
     if (copy_after != nullptr) WHENET_HIP_CHECK(hipStreamWaitEvent(cs, copy_after, 0));
+    uint8_t* const d_in = slot.in.d.as<uint8_t>();
     if (stage == 1) {
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->d_in, crops, N * IN_BYTES, hipMemcpyHostToDevice, cs));
+        WHENET_HIP_CHECK(hipMemcpyAsync(d_in, crops, N * IN_BYTES, hipMemcpyHostToDevice, cs));
     } else {
-        std::memcpy(slot->h_in, crops, N * IN_BYTES);
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->d_in, slot->h_in, N * IN_BYTES, hipMemcpyHostToDevice, cs));
+        std::memcpy(slot.in.h.as<void>(), crops, N * IN_BYTES);
+        WHENET_HIP_CHECK(hipMemcpyAsync(d_in, slot.in.h.as<void>(), N * IN_BYTES, hipMemcpyHostToDevice, cs));
     }
-    WHENET_HIP_CHECK(hipEventRecord(slot->copied, cs));
-    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot->copied, 0));
-    run_forward(slot->d_in, n, slot->d_ypr, slot->d_amax, slot->d_logits, stream_, want_lanes);
-    WHENET_HIP_CHECK(hipMemcpyAsync(slot->h_ypr, slot->d_ypr, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    WHENET_HIP_CHECK(hipMemcpyAsync(slot->h_amax, slot->d_amax, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    WHENET_HIP_CHECK(hipMemcpyAsync(slot->h_logits, slot->d_logits, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    WHENET_HIP_CHECK(hipEventRecord(slot->done, stream_));
-    slot->busy = true;
-    slot->n = n;
-    slot->ticket = next_ticket_++;
-    return slot->ticket;
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, cs));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+    run_forward(d_in, n, slot.dev(), stream_, want_lanes);
+    copy_results_async(slot.host(), slot.dev(), n, stream_);
+    return finish_submission(slot, n);
 }
 
 // After a failed fan-out: wait for whatever was enqueued and hand every slot back.
@@ -1325,10 +1188,7 @@ void Engine::collect(int ticket, float* ypr, int32_t* argmax, float* logits) {
         if (s.busy && s.ticket == ticket) slot = &s;
     WHENET_REQUIRE(slot != nullptr, WHENET_EINVAL, "unknown or already collected ticket " + std::to_string(ticket));
     WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
-    const size_t N = size_t(slot->n);
-    if (ypr) std::memcpy(ypr, slot->h_ypr, N * 3 * sizeof(float));
-    if (argmax) std::memcpy(argmax, slot->h_amax, N * 3 * sizeof(int32_t));
-    if (logits) std::memcpy(logits, slot->h_logits, N * N_LOGITS * sizeof(float));
+    copy_results_host(Results{ypr, argmax, logits}, slot->host(), slot->n);
     slot->busy = false;
 }
 
@@ -1337,47 +1197,26 @@ int Engine::profile(const uint8_t* d_crops, int n, int iters, whenet_launch_stat
     require_model();
     WHENET_REQUIRE(d_crops != nullptr && iters >= 1, WHENET_EINVAL, "profile: bad arguments");
     ensure_capacity(n);
-    int lanes = lanes_;
-    while (lanes > 1 && n / lanes < min_lane_crops_) --lanes;
-    std::vector<LaunchRecorder> recs;
+    const int lanes = lanes_for(n, 0);
+    std::vector<LaunchRecorder> recs;      // (their events go with them)
     recs.resize(size_t(lanes));
-    struct Cleanup {
-        std::vector<LaunchRecorder>& r;
-        ~Cleanup() {
-            for (auto& lr : r) {
-                if (lr.start) (void)hipEventDestroy(lr.start);
-                for (auto& e : lr.entries)
-                    if (e.stop) (void)hipEventDestroy(e.stop);
-            }
-        }
-    } cleanup{recs};
-    for (auto& lr : recs) WHENET_HIP_CHECK(hipEventCreate(&lr.start));
+    for (auto& lr : recs) lr.start.create(hipEventDefault);
+    const Results out = view(0).out;
     // one untimed eager pass so that lazy code-object loading does not land in the numbers
-    enqueue_forward(view(0), d_crops, n, o_ypr_, o_amax_, o_logits_, stream_, nullptr);
+    enqueue_forward(view(0), d_crops, n, out, stream_, nullptr);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     for (int it = 0; it < iters; ++it) {
-        WHENET_HIP_CHECK(hipEventRecord(fork_ev_, stream_));
-        int off = 0;
-        for (int i = 0; i < lanes; ++i) {
-            const int cnt = n / lanes + (i < n % lanes ? 1 : 0);
-            hipStream_t st = (i == 0) ? stream_ : lane_stream(i - 1);
-            if (i > 0) WHENET_HIP_CHECK(hipStreamWaitEvent(st, fork_ev_, 0));
+        for_each_lane(n, lanes, stream_, [&](int i, int off, int cnt, hipStream_t st) {
             LaunchRecorder& lr = recs[size_t(i)];
             lr.cursor = 0;
             WHENET_HIP_CHECK(hipEventRecord(lr.start, st));
-            enqueue_forward(view(off), d_crops + size_t(off) * IN_BYTES, cnt, o_ypr_ + size_t(off) * 3,
-                            o_amax_ + size_t(off) * 3, o_logits_ + size_t(off) * N_LOGITS, st, &lr);
+            enqueue_forward(view(off), d_crops + size_t(off) * IN_BYTES, cnt, out.at(size_t(off)), st, &lr);
             {   // calibration entry: an empty kernel timed the same way = the boundary + event cost
                 Rec R{&lr, st, 1};
                 R("(boundary)", "calib", "whenet_empty_kernel", 0.0, 0.0, [&] { launch_empty(st); });
             }
             lr.first_pass = false;
-            if (i > 0) {
-                WHENET_HIP_CHECK(hipEventRecord(join_ev_[size_t(i - 1)], st));
-                WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, join_ev_[size_t(i - 1)], 0));
-            }
-            off += cnt;
-        }
+        });
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         for (auto& lr : recs) {
             hipEvent_t prev = lr.start;

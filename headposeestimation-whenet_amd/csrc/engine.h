@@ -15,6 +15,94 @@
 
 namespace whenet {
 
+// Move-only owners of what the engine takes from the runtime: each frees its resource in its destructor, on whichever device is
+// current.  ~Engine selects the engine's own first; when a constructor throws part-way they go with the caller's device current,
+// which hipFree / hipHostFree / hipEventDestroy / hipStreamDestroy accept (the handle carries its device).
+template <typename H, hipError_t (*Destroy)(H)>
+class Owned {
+  public:
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ~Owned() { reset(); }
+    void reset() {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    H* put() {             // for the hip...Create call that fills it
+        reset();
+        return &h_;
+    }
+    operator H() const { return h_; }
+
+  private:
+    H h_ = nullptr;
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    void create(unsigned flags = hipEventDisableTiming) { WHENET_HIP_CHECK(hipEventCreateWithFlags(put(), flags)); }
+};
+
+struct DeviceMem {
+    static constexpr const char* NAME = "hipMalloc";
+    static hipError_t alloc(void** p, size_t nbytes) { return hipMalloc(p, nbytes); }
+    static void release(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static constexpr const char* NAME = "hipHostMalloc";
+    static hipError_t alloc(void** p, size_t nbytes) { return hipHostMalloc(p, nbytes, hipHostMallocDefault); }
+    static void release(void* p) { (void)hipHostFree(p); }
+};
+template <typename Mem>
+class Buffer {
+  public:
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+    ~Buffer() { release(); }
+    size_t bytes() const { return bytes_; }
+    template <typename T> T* as() const { return static_cast<T*>(p_); }
+    void release() {
+        if (p_) Mem::release(p_);
+        p_ = nullptr, bytes_ = 0;
+    }
+    hipError_t try_reset(size_t nbytes) {          // free, then allocate (zero bytes allocates 16)
+        release();
+        const hipError_t e = Mem::alloc(&p_, nbytes ? nbytes : 16);
+        if (e == hipSuccess) bytes_ = nbytes;
+        else p_ = nullptr;
+        return e;
+    }
+    // what: the sites that report a failed allocation as out of memory under their own text; the others report the HIP call
+    void reset(size_t nbytes, const char* what = nullptr) {
+        const hipError_t e = try_reset(nbytes);
+        if (e == hipSuccess) return;
+        if (what) throw Error(WHENET_ENOMEM, std::string(what) + ": " + hipGetErrorString(e));
+        throw Error(WHENET_EHIP, std::string(Mem::NAME) + " of " + std::to_string(nbytes) + " bytes: " + hipGetErrorString(e));
+    }
+    void grow(size_t nbytes) {
+        if (nbytes > bytes_) reset(nbytes);
+    }
+
+  private:
+    void* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+using DeviceBuffer = Buffer<DeviceMem>;
+using PinnedBuffer = Buffer<PinnedMem>;
+struct StagedBuffer {      // a pinned host buffer and its device twin
+    PinnedBuffer h;
+    DeviceBuffer d;
+};
+
+// The three result arrays of a forward (argmax / logits may be nullptr where the caller does not want them).
+struct Results {
+    float* ypr;
+    int32_t* amax;
+    float* logits;
+    Results at(size_t crop) const {
+        return {ypr + crop * 3, amax ? amax + crop * 3 : nullptr, logits ? logits + crop * N_LOGITS : nullptr};
+    }
+};
+
 struct DevPw {
     int K = 0, N = 0, KS = 0, NTILES = 0;
     void* wp = nullptr;
@@ -68,11 +156,11 @@ struct LaunchRecorder {
     struct Entry {
         std::string layer, kind, kernel;
         double bytes = 0, flops = 0;
-        hipEvent_t stop = nullptr;      // recorded right after the launch; the previous entry's stop
+        Event stop;                      // recorded right after the launch; the previous entry's stop
         double total_ms = 0;             // (or the chain's start event) is this launch's start
     };
     std::vector<Entry> entries;
-    hipEvent_t start = nullptr;          // recorded on the chain's stream before its first launch
+    Event start;                         // recorded on the chain's stream before its first launch
     size_t cursor = 0;
     bool first_pass = true;
 };
@@ -137,30 +225,18 @@ class Engine {
     struct Slot {          // one in-flight submission of the pinned pipeline
         int capacity = 0, n = 0, ticket = -1;
         bool busy = false;
-        uint8_t* h_in = nullptr;
-        uint8_t* d_in = nullptr;
-        float *h_ypr = nullptr, *d_ypr = nullptr;
-        int32_t *h_amax = nullptr, *d_amax = nullptr;
-        float *h_logits = nullptr, *d_logits = nullptr;
-        hipEvent_t copied = nullptr, done = nullptr;
-        // frame submissions: the frame and the crop plans travel instead of the crops
-        size_t frame_cap = 0;
-        uint8_t *h_frame = nullptr, *d_frame = nullptr;
-        int plan_cap = 0;
-        int32_t *h_plan = nullptr, *d_plan = nullptr;
+        StagedBuffer in, ypr, amax, logits;
+        Event copied, done;
+        StagedBuffer frame, plan;        // frame submissions: the frame and the crop plans travel instead of the crops
+        Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
+        Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
 
     template <typename T> T* upload(const std::vector<T>& v);
     void* upload_bytes(const void* p, size_t nbytes);
     DevPw upload_pw(const HostPw& h);
-    // WHENET_F32S: 1x1 products as binary16 hi/lo pairs (option "split_pw" switches the pointwise kernels between the two forms)
-    void set_split(PwArgs& a, const DevPw& w) const {
-        a.staged = pw_staged_;
-        a.split = split_ && split_pw_ && w.wps != nullptr;
-        a.wps = w.wps;
-        a.KSs = w.KSs;
-        a.wsi = w.wsi;
-    }
+    // the arguments of a 1x1 conv with w's weights over M = n * HW rows: what every pointwise launch sets
+    PwArgs pw_args(const DevPw& w, const void* a, void* out, int M, int HW, int act) const;
     bool split_ = false;        // the handle was created as WHENET_F32S
     bool split_pw_ = true;      // option "split_pw"
     bool pw_staged_ = true;     // option "pw_staged": split-K GEMMs fetch their activation rows coalesced, through LDS
@@ -173,16 +249,32 @@ class Engine {
         void *x0, *x1, *e, *d, *hc;
         float *partial, *gate;
         unsigned* hcount;
+        uint8_t* in_u8;
+        Results out;
     };
     View view(int crop_off) const;
     // enqueue the kernels of one forward on `s` (eager); rec != nullptr -> event pairs
-    void enqueue_forward(const View& v, const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits,
-                         hipStream_t s, LaunchRecorder* rec, const float* d_in_f32 = nullptr);
+    void enqueue_forward(const View& v, const uint8_t* d_in, int n, Results out, hipStream_t s, LaunchRecorder* rec,
+                         const float* d_in_f32 = nullptr);
     // fold: 0 = the block as it stands; 1 = block 1 without its project (its depthwise output goes to `out`);
     //       2 = block 2 fed by that output, block 1's project folded into its expand weights (fold12_active())
     // in_blocked / out_blocked: the block's input / output tensor is in the blocked layout (act_blocked())
     void enqueue_block(const DevBlock& b, const View& v, const void* in, void* out, int n, hipStream_t s,
                        LaunchRecorder* rec, int fold = 0, bool dw_done = false, bool in_blocked = false, bool out_blocked = false);
+    struct BlockSchedule;
+    // its parts: the fused expand + depthwise stage (or the whole block: mb7.hip), the unfused pair, the rest of the SEBlock (returns
+    // what the project needs to compute the gate itself, if it does), the project
+    void enqueue_front(const DevBlock& b, const BlockSchedule& bs, const View& v, const void* in, void* out, int n, hipStream_t s,
+                       LaunchRecorder* rec, int fold, bool in_blocked);
+    void enqueue_expand_dw(const DevBlock& b, const View& v, const void* in, void* dw_out, int n, hipStream_t s, LaunchRecorder* rec,
+                           bool dw_done);
+    SeFuse enqueue_se(const DevBlock& b, const BlockSchedule& bs, const View& v, int n, hipStream_t s, LaunchRecorder* rec, int fold);
+    void enqueue_project(const DevBlock& b, const SeFuse& sef, bool se_fused, const View& v, const void* in, void* out, int n,
+                         hipStream_t s, LaunchRecorder* rec, bool in_blocked, bool out_blocked);
+    template <typename A> void fill_front_common(A& a, const DevBlock& b, const View& v, const void* in, int n) const;
+    // the head conv's arguments, fused with the pooling (head7.hip) and alone (pw.hip), for the forward and for op_head
+    Head7Args head7_args(const void* x, float* feat, int n) const;
+    PwArgs head_pw_args(const void* x, void* out, int n) const { return pw_args(head_, x, out, n * 49, 49, ACT_SWISH); }
     // blocks first..last (1-based) as the forward pass runs them; returns the buffer (x0 / x1 of `v`) holding the result
     void* enqueue_blocks(int first, int last, const View& v, void* cur, int n, hipStream_t s, LaunchRecorder* rec,
                          bool b1_dw_done = false);
@@ -204,8 +296,11 @@ class Engine {
     int f2s_mask_ = -1;                // option "f2s_mask" (probes)
     bool single_stage_call_ = false;   // op_block / op_block_range: the schedule must not depend on the test's batch size
     int lanes_for(int n, int want) const;     // chains a forward of n crops runs as (want = 0: option "lanes")
-    void enqueue_lanes(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want = 0);
-    void run_forward(const uint8_t* d_in, int n, float* d_ypr, int32_t* d_amax, float* d_logits, hipStream_t s, int want = 0);
+    // body(i, off, cnt, st): chain i of `lanes` takes crops [off, off + cnt) on stream st (chain 0: s itself), forked from and joined
+    // back into s with events
+    template <typename F> void for_each_lane(int n, int lanes, hipStream_t s, F&& body);
+    void enqueue_lanes(const uint8_t* d_in, int n, Results out, hipStream_t s, int want = 0);
+    void run_forward(const uint8_t* d_in, int n, Results out, hipStream_t s, int want = 0);
     void poison_arena(int n, hipStream_t s);        // option "poison": NaN bit patterns in every activation buffer of n crops
     void ensure_slot(Slot& s, int n);
     hipStream_t lane_stream(int i);     // created on first use
@@ -216,6 +311,7 @@ class Engine {
     hipStream_t copy_stream();          // created on first use
     void ensure_slot_frame(Slot& s, size_t frame_bytes, int k);
     Slot* free_slot();
+    int finish_submission(Slot& s, int n);      // record `done`, mark the slot busy, hand out its ticket
 
     void open_device(int device_id);
     void require_model() const;
@@ -255,16 +351,17 @@ class Engine {
     bool lane_graphs_ = false;  // one graph per lane on its own stream instead of one forked graph (option "lane_graphs")
     int min_lane_crops_ = 16;   // do not split below this many crops per chain
     int host_lanes_ = 2;        // chains of a BLOCKING host forward (it has the GPU to itself whatever "inflight" says)
-    std::vector<hipStream_t> lane_streams_;
-    std::vector<hipEvent_t> join_ev_;
-    hipEvent_t fork_ev_ = nullptr;
-    hipStream_t stream_ = nullptr, copy_stream_ = nullptr;
+    // (declaration order is destruction order reversed: every buffer and event below goes before these streams)
+    Stream stream_, copy_stream_;
+    std::vector<Stream> lane_streams_;
+    std::vector<Event> join_ev_;
+    Event fork_ev_;
     hipDeviceProp_t prop_{};
     int64_t params_backbone_ = 0, params_heads_ = 0;
     int n_tensors_ = 0;
 
     // weights
-    std::vector<void*> weight_allocs_;
+    std::vector<DeviceBuffer> weight_allocs_;
     float *d_lut_ = nullptr, *d_stem_w_ = nullptr, *d_stem_b_ = nullptr;
     StemDwTable* d_stemdw_tab_ = nullptr;   // stemdw.hip's packed LUT + stem weight fragments
     std::vector<DevBlock> blocks_;
@@ -276,18 +373,17 @@ class Engine {
     // activation arena (grown to the largest n seen)
     int cap_ = 0;
     size_t arena_bytes_ = 0;
-    void *x0_ = nullptr, *x1_ = nullptr, *e_ = nullptr, *d_ = nullptr, *hc_ = nullptr;
-    float *partial_ = nullptr, *gate_ = nullptr;
-    unsigned* hcount_ = nullptr;       // per-crop tickets of the split heads kernel (zero between launches)
-    uint8_t* in_u8_ = nullptr;
-    float* in_f32_ = nullptr;       // normalised float32 input of forward_host_f32 (grown on demand)
-    int in_f32_cap_ = 0;
-    float* o_ypr_ = nullptr;
-    int32_t* o_amax_ = nullptr;
-    float* o_logits_ = nullptr;
+    // ONE table of its buffers, in allocation order: sizes (ensure_capacity), per-crop offsets (view) and the NaN fill (poison_arena:
+    // the first A_POISONED entries) all come from it.  A_HCOUNT: per-crop tickets of the split heads kernel (zero between launches)
+    enum { A_X0, A_X1, A_E, A_D, A_HC, A_PARTIAL, A_GATE, A_HCOUNT, A_IN_U8, A_YPR, A_AMAX, A_LOGITS, A_COUNT, A_POISONED = A_HCOUNT };
+    struct ArenaBuf {
+        DeviceBuffer buf;
+        size_t per_crop = 0;       // bytes
+    };
+    ArenaBuf arena_[A_COUNT];
+    DeviceBuffer in_f32_;           // normalised float32 input of forward_host_f32 (grown on demand)
     size_t partial_per_crop_ = 0;
-    unsigned char* yolo_scratch_ = nullptr;      // device scratch of yolo_eval, grown on demand
-    size_t yolo_scratch_bytes_ = 0;
+    DeviceBuffer yolo_scratch_;     // device scratch of yolo_eval, grown on demand
     std::vector<int> yolo_counts_;               // host staging of the per-class detection counts
 
     std::map<GraphKey, hipGraphExec_t> graphs_;
@@ -296,10 +392,9 @@ class Engine {
     Slot host_slot_;                   // pinned staging of small BLOCKING host forwards (forward_host, n <= host_pinned_max_)
     // pinned landing zone of the RESULTS of larger blocking host forwards: three asynchronous D2H copies and one wait instead of three
     // synchronous copies into the caller's pageable arrays (round 6)
-    float* hout_ypr_ = nullptr;
-    int32_t* hout_amax_ = nullptr;
-    float* hout_logits_ = nullptr;
+    PinnedBuffer hout_ypr_, hout_amax_, hout_logits_;
     int hout_cap_ = 0;
+    Results hout() const { return {hout_ypr_.as<float>(), hout_amax_.as<int32_t>(), hout_logits_.as<float>()}; }
     void ensure_host_out(int n);
     int host_pinned_max_ = 8;      // measured round 5: pinned wins up to 8 crops (B=1 f32 420 vs 445 us), loses at 16-32
     int next_ticket_ = 0;

@@ -17,6 +17,7 @@ constexpr size_t X_ELEMS = size_t(112) * 112 * 32;    // largest block input/out
 constexpr size_t E_ELEMS = size_t(112) * 112 * 96;    // largest expanded tensor per crop (b2 expand)
 constexpr size_t D_ELEMS = size_t(56) * 56 * 144;     // largest depthwise output per crop (b3 dw)
 constexpr size_t HC_ELEMS = size_t(49) * FEAT;        // head conv output per crop
+constexpr size_t GATE_ELEMS = 1152;                   // widest squeeze-excite gate per crop (blocks 13-16)
 constexpr size_t IN_BYTES = size_t(IMG) * IMG * 3;
 constexpr int MAX_GRAPHS = 16;
 
@@ -25,17 +26,35 @@ struct DeviceGuard {
 };
 
 struct TempBufs {     // hipMalloc'd scratch of the single-stage entry points
-    std::vector<void*> ptrs;
+    std::vector<DeviceBuffer> bufs;
     void* get(size_t nbytes) {
-        void* p = nullptr;
-        WHENET_HIP_CHECK(hipMalloc(&p, nbytes ? nbytes : 16));
-        ptrs.push_back(p);
-        return p;
-    }
-    ~TempBufs() {
-        for (void* p : ptrs) (void)hipFree(p);
+        bufs.emplace_back();
+        bufs.back().reset(nbytes);
+        return bufs.back().as<void>();
     }
 };
+
+struct FlagGuard {    // sets a flag for a scope
+    bool& flag;
+    explicit FlagGuard(bool& f) : flag(f) { flag = true; }
+    ~FlagGuard() { flag = false; }
+};
+
+// The three result copies of n crops: device to host on a stream, and out of a pinned landing buffer into the caller's arrays
+// (those of them that are not nullptr).
+inline void copy_results_async(const Results& dst, const Results& src, int n, hipStream_t s, bool want_amax = true,
+                               bool want_logits = true) {
+    const size_t N = size_t(n);
+    WHENET_HIP_CHECK(hipMemcpyAsync(dst.ypr, src.ypr, N * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (want_amax) WHENET_HIP_CHECK(hipMemcpyAsync(dst.amax, src.amax, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (want_logits) WHENET_HIP_CHECK(hipMemcpyAsync(dst.logits, src.logits, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, s));
+}
+inline void copy_results_host(const Results& dst, const Results& src, int n) {
+    const size_t N = size_t(n);
+    if (dst.ypr) std::memcpy(dst.ypr, src.ypr, N * 3 * sizeof(float));
+    if (dst.amax) std::memcpy(dst.amax, src.amax, N * 3 * sizeof(int32_t));
+    if (dst.logits) std::memcpy(dst.logits, src.logits, N * N_LOGITS * sizeof(float));
+}
 
 inline void copy_name(char* dst, size_t cap, const std::string& s) {
     std::memset(dst, 0, cap);

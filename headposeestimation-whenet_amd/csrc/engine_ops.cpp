@@ -14,10 +14,11 @@ void Engine::op_stem(const uint8_t* crops, int n, float* out) {
     TempBufs tmp;
     const size_t N = size_t(n);
     float* d_out = static_cast<float*>(tmp.get(N * X_ELEMS * sizeof(float)));
-    WHENET_HIP_CHECK(hipMemcpyAsync(in_u8_, crops, N * IN_BYTES, hipMemcpyHostToDevice, stream_));
-    StemArgs a{in_u8_, x0_, d_stem_w_, d_stem_b_, d_lut_, n};
+    const View v = view(0);
+    WHENET_HIP_CHECK(hipMemcpyAsync(v.in_u8, crops, N * IN_BYTES, hipMemcpyHostToDevice, stream_));
+    StemArgs a{v.in_u8, v.x0, d_stem_w_, d_stem_b_, d_lut_, n};
     launch_stem(a, dtype_, stream_);
-    launch_act_to_f32(x0_, d_out, N * X_ELEMS, dtype_, stream_);
+    launch_act_to_f32(v.x0, d_out, N * X_ELEMS, dtype_, stream_);
     WHENET_HIP_CHECK(hipMemcpyAsync(out, d_out, N * X_ELEMS * sizeof(float), hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }
@@ -38,28 +39,25 @@ void Engine::op_block(int index, const float* in, int n, float* expand_out, floa
     TempBufs tmp;
     float* d_f32 = static_cast<float*>(tmp.get(std::max({in_elems, exp_elems, dw_elems, out_elems}) * sizeof(float)));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in, in_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_f32_to_act(d_f32, x0_, in_elems, dtype_, stream_);
-    WHENET_HIP_CHECK(hipMemsetAsync(gate_, 0xff, N * 1152 * sizeof(float), stream_));     // (NaN unless a launch writes it)
-    single_stage_call_ = true;
-    try {
-        enqueue_block(b, view(0), x0_, x1_, n, stream_, nullptr);
-    } catch (...) {
-        single_stage_call_ = false;
-        throw;
+    const View v = view(0);
+    launch_f32_to_act(d_f32, v.x0, in_elems, dtype_, stream_);
+    WHENET_HIP_CHECK(hipMemsetAsync(v.gate, 0xff, N * GATE_ELEMS * sizeof(float), stream_));     // (NaN unless a launch writes it)
+    {
+        FlagGuard single(single_stage_call_);
+        enqueue_block(b, v, v.x0, v.x1, n, stream_, nullptr);
     }
-    single_stage_call_ = false;
     auto fetch = [&](const void* src, size_t elems, float* dst) {
         if (!dst) return;
         launch_act_to_f32(src, d_f32, elems, dtype_, stream_);
         WHENET_HIP_CHECK(hipMemcpyAsync(dst, d_f32, elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     };
-    if (sp.has_expand()) fetch(e_, exp_elems, expand_out);
-    fetch(d_, dw_elems, dw_out);
+    if (sp.has_expand()) fetch(v.e, exp_elems, expand_out);
+    fetch(v.d, dw_elems, dw_out);
     if (gate) {
-        fetch(gate_, N * sp.cexp(), gate);         // (stored in the activation type: see se.hip)
+        fetch(v.gate, N * sp.cexp(), gate);         // (stored in the activation type: see se.hip)
     }
-    fetch(x1_, out_elems, out);
+    fetch(v.x1, out_elems, out);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -77,17 +75,13 @@ void Engine::op_block_range(int first, int last, const float* in, int n, float* 
     TempBufs tmp;
     float* d_f32 = static_cast<float*>(tmp.get(std::max(in_elems, out_elems) * sizeof(float)));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in, in_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_f32_to_act(d_f32, x0_, in_elems, dtype_, stream_);
     const View v = view(0);
-    single_stage_call_ = true;
+    launch_f32_to_act(d_f32, v.x0, in_elems, dtype_, stream_);
     const void* res = nullptr;
-    try {
+    {
+        FlagGuard single(single_stage_call_);
         res = enqueue_blocks(first, last, v, v.x0, n, stream_, nullptr);
-    } catch (...) {
-        single_stage_call_ = false;
-        throw;
     }
-    single_stage_call_ = false;
     launch_act_to_f32(res, d_f32, out_elems, dtype_, stream_);
     WHENET_HIP_CHECK(hipMemcpyAsync(out, d_f32, out_elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -104,55 +98,29 @@ void Engine::op_head(const float* in, int n, float* feat, float* logits, float* 
     float* d_f32 = static_cast<float*>(tmp.get(in_elems * sizeof(float)));
     float* d_feat = static_cast<float*>(tmp.get(N * FEAT * sizeof(float)));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in, in_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_f32_to_act(d_f32, x0_, in_elems, dtype_, stream_);
+    const View v = view(0);
+    launch_f32_to_act(d_f32, v.x0, in_elems, dtype_, stream_);
     const bool fuse_head = head_fuse_ && pw_impl_ == 0 && head7_supported(dtype_, head_.K, head_.N, 49);
     HeadsArgs h{};
     if (fuse_head) {          // the forward's form: head conv + pooling as one kernel (head7.hip), Dense heads on its features
-        Head7Args a{};
-        a.dtype = dtype_;
-        a.x = x0_;
-        a.wep = head_.wp;
-        a.bias = head_.bias;
-        a.feat = d_feat;
-        a.K = head_.K;
-        a.N = head_.N;
-        a.NTILES = head_.NTILES;
-        a.split = split_ && split_pw_ && head_.wps != nullptr;
-        a.weps = head_.wps;
-        a.wsi = head_.wsi;
-        a.n = n;
-        launch_head7(a, stream_);
+        launch_head7(head7_args(v.x0, d_feat, n), stream_);
         h.feat_in = d_feat;
     } else {
-        PwArgs a{};
-        a.a = x0_;
-        a.wp = head_.wp;
-        a.wdense = head_.wdense;
-        a.bias = head_.bias;
-        a.out = hc_;
-        a.M = n * 49;
-        a.K = head_.K;
-        a.N = head_.N;
-        a.KS = head_.KS;
-        a.NTILES = head_.NTILES;
-        set_split(a, head_);
-        a.HW = 49;
-        a.act = ACT_SWISH;
-        launch_pw(a, dtype_, pw_impl_, num_cus_, stream_);
-        h.x = hc_;
+        launch_pw(head_pw_args(v.x0, v.hc, n), dtype_, pw_impl_, num_cus_, stream_);
+        h.x = v.hc;
         h.feat = d_feat;
     }
     h.w = d_dense_w_;
     h.b = d_dense_b_;
-    h.logits = o_logits_;
-    h.ypr = o_ypr_;
-    h.argmax = o_amax_;
+    h.logits = v.out.logits;
+    h.ypr = v.out.ypr;
+    h.argmax = v.out.amax;
     h.n = n;
     launch_heads(h, dtype_, stream_);
     if (feat) WHENET_HIP_CHECK(hipMemcpyAsync(feat, d_feat, N * FEAT * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (logits) WHENET_HIP_CHECK(hipMemcpyAsync(logits, o_logits_, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (ypr) WHENET_HIP_CHECK(hipMemcpyAsync(ypr, o_ypr_, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (argmax) WHENET_HIP_CHECK(hipMemcpyAsync(argmax, o_amax_, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    if (logits) WHENET_HIP_CHECK(hipMemcpyAsync(logits, v.out.logits, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (ypr) WHENET_HIP_CHECK(hipMemcpyAsync(ypr, v.out.ypr, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (argmax) WHENET_HIP_CHECK(hipMemcpyAsync(argmax, v.out.amax, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -169,12 +137,12 @@ void Engine::op_decode(const float* logits, int n, float* ypr, int32_t* argmax) 
     h.logits_in = d_lg;
     h.w = d_dense_w_;
     h.b = d_dense_b_;
-    h.ypr = o_ypr_;
-    h.argmax = o_amax_;
+    const Results out = view(0).out;
+    h.ypr = out.ypr;
+    h.argmax = out.amax;
     h.n = n;
     launch_heads(h, WHENET_F32, stream_);
-    WHENET_HIP_CHECK(hipMemcpyAsync(ypr, o_ypr_, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    if (argmax) WHENET_HIP_CHECK(hipMemcpyAsync(argmax, o_amax_, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    copy_results_async(Results{ypr, argmax, nullptr}, out, n, stream_, argmax != nullptr, false);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

@@ -6,30 +6,12 @@ namespace whenet {
 
 using namespace detail;
 
-Engine::Slot* Engine::free_slot() {
-    for (Slot& s : slots_)
-        if (!s.busy) return &s;
-    throw Error(WHENET_EINVAL, "too many submissions in flight (collect one first)");
-}
-
 void Engine::ensure_slot_frame(Slot& s, size_t frame_bytes, int k) {
-    if (frame_bytes > s.frame_cap) {
-        if (s.h_frame) (void)hipHostFree(s.h_frame);
-        if (s.d_frame) (void)hipFree(s.d_frame);
-        s.h_frame = nullptr; s.d_frame = nullptr; s.frame_cap = 0;
-        WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_frame), frame_bytes, hipHostMallocDefault));
-        WHENET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_frame), frame_bytes));
-        s.frame_cap = frame_bytes;
-    }
-    if (k > s.plan_cap) {
-        if (s.h_plan) (void)hipHostFree(s.h_plan);
-        if (s.d_plan) (void)hipFree(s.d_plan);
-        s.h_plan = nullptr; s.d_plan = nullptr; s.plan_cap = 0;
-        const size_t bytes = size_t(k) * CROP_PLAN_INTS * sizeof(int32_t);
-        WHENET_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&s.h_plan), bytes, hipHostMallocDefault));
-        WHENET_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&s.d_plan), bytes));
-        s.plan_cap = k;
-    }
+    s.frame.h.grow(frame_bytes);
+    s.frame.d.grow(frame_bytes);
+    const size_t plan_bytes = size_t(k) * CROP_PLAN_INTS * sizeof(int32_t);
+    s.plan.h.grow(plan_bytes);
+    s.plan.d.grow(plan_bytes);
 }
 
 namespace {
@@ -50,33 +32,27 @@ int Engine::submit_frame(const uint8_t* frame, int fh, int fw, int swap_rb, cons
     WHENET_REQUIRE(frame != nullptr && fh > 0 && fw > 0 && k >= 0 && (k == 0 || rects != nullptr), WHENET_EINVAL,
                    "submit_frame: bad arguments");
     check_rects(fh, fw, rects, k);
-    Slot* slot = free_slot();
+    Slot& slot = *free_slot();
     if (k > 0) {
         ensure_capacity(k);
-        ensure_slot(*slot, k);
+        ensure_slot(slot, k);
         const size_t fbytes = size_t(fh) * fw * 3;
-        ensure_slot_frame(*slot, fbytes, k);
-        std::memcpy(slot->h_frame, frame, fbytes);
-        for (int i = 0; i < k; ++i) build_crop_plan(rects + 4 * i, slot->h_plan + size_t(i) * CROP_PLAN_INTS);
-        const size_t N = size_t(k);
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->d_frame, slot->h_frame, fbytes, hipMemcpyHostToDevice, copy_stream()));
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->d_plan, slot->h_plan, N * CROP_PLAN_INTS * sizeof(int32_t),
+        ensure_slot_frame(slot, fbytes, k);
+        int32_t* const h_plan = slot.plan.h.as<int32_t>();
+        std::memcpy(slot.frame.h.as<void>(), frame, fbytes);
+        for (int i = 0; i < k; ++i) build_crop_plan(rects + 4 * i, h_plan + size_t(i) * CROP_PLAN_INTS);
+        WHENET_HIP_CHECK(hipMemcpyAsync(slot.frame.d.as<void>(), slot.frame.h.as<void>(), fbytes, hipMemcpyHostToDevice, copy_stream()));
+        WHENET_HIP_CHECK(hipMemcpyAsync(slot.plan.d.as<void>(), h_plan, size_t(k) * CROP_PLAN_INTS * sizeof(int32_t),
                                         hipMemcpyHostToDevice, copy_stream()));
-        WHENET_HIP_CHECK(hipEventRecord(slot->copied, copy_stream()));
-        WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot->copied, 0));
-        launch_crop_resize(slot->d_frame, fw, swap_rb, slot->d_plan, k, slot->d_in, stream_);
-        run_forward(slot->d_in, k, slot->d_ypr, slot->d_amax, slot->d_logits, stream_);
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->h_ypr, slot->d_ypr, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->h_amax, slot->d_amax, N * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-        WHENET_HIP_CHECK(hipMemcpyAsync(slot->h_logits, slot->d_logits, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+        WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+        launch_crop_resize(slot.frame.d.as<uint8_t>(), fw, swap_rb, slot.plan.d.as<int32_t>(), k, slot.in.d.as<uint8_t>(), stream_);
+        run_forward(slot.in.d.as<uint8_t>(), k, slot.dev(), stream_);
+        copy_results_async(slot.host(), slot.dev(), k, stream_);
     } else {
-        ensure_slot(*slot, 1);
+        ensure_slot(slot, 1);
     }
-    WHENET_HIP_CHECK(hipEventRecord(slot->done, stream_));
-    slot->busy = true;
-    slot->n = k;
-    slot->ticket = next_ticket_++;
-    return slot->ticket;
+    return finish_submission(slot, k);
 }
 
 void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, const int32_t* rects, int k,
@@ -88,20 +64,15 @@ void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, c
     std::vector<int32_t> plan(size_t(k) * CROP_PLAN_INTS);
     for (int i = 0; i < k; ++i) build_crop_plan(rects + 4 * i, plan.data() + size_t(i) * CROP_PLAN_INTS);
     const size_t fbytes = size_t(fh) * fw * 3, obytes = size_t(k) * IN_BYTES;
-    uint8_t* d_frame = static_cast<uint8_t*>(dev_alloc(fbytes));
-    int32_t* d_plan = static_cast<int32_t*>(dev_alloc(plan.size() * sizeof(int32_t)));
-    uint8_t* d_out = static_cast<uint8_t*>(dev_alloc(obytes));
-    try {
-        WHENET_HIP_CHECK(hipMemcpy(d_frame, frame, fbytes, hipMemcpyHostToDevice));
-        WHENET_HIP_CHECK(hipMemcpy(d_plan, plan.data(), plan.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        launch_crop_resize(d_frame, fw, swap_rb, d_plan, k, d_out, stream_);
-        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-        WHENET_HIP_CHECK(hipMemcpy(crops_out, d_out, obytes, hipMemcpyDeviceToHost));
-    } catch (...) {
-        dev_free(d_frame); dev_free(d_plan); dev_free(d_out);
-        throw;
-    }
-    dev_free(d_frame); dev_free(d_plan); dev_free(d_out);
+    DeviceBuffer d_frame, d_plan, d_out;
+    d_frame.reset(fbytes, "hipMalloc");
+    d_plan.reset(plan.size() * sizeof(int32_t), "hipMalloc");
+    d_out.reset(obytes, "hipMalloc");
+    WHENET_HIP_CHECK(hipMemcpy(d_frame.as<void>(), frame, fbytes, hipMemcpyHostToDevice));
+    WHENET_HIP_CHECK(hipMemcpy(d_plan.as<void>(), plan.data(), plan.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    launch_crop_resize(d_frame.as<uint8_t>(), fw, swap_rb, d_plan.as<int32_t>(), k, d_out.as<uint8_t>(), stream_);
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+    WHENET_HIP_CHECK(hipMemcpy(crops_out, d_out.as<void>(), obytes, hipMemcpyDeviceToHost));
 }
 
 // yolo_eval (yolo_v3/model.py:193-232) on host feature maps: H2D, decode + NMS on the device, the selected boxes
@@ -183,16 +154,11 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
     const size_t o_os = cv.add(C * MB * sizeof(float));
     const size_t o_oi = cv.add(C * MB * sizeof(int));
     const size_t o_oc = cv.add(C * sizeof(int));
-    if (cv.used > yolo_scratch_bytes_) {
+    if (cv.used > yolo_scratch_.bytes()) {
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-        if (yolo_scratch_) (void)hipFree(yolo_scratch_);
-        yolo_scratch_ = nullptr;
-        yolo_scratch_bytes_ = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&yolo_scratch_), cv.used);
-        if (e != hipSuccess) throw Error(WHENET_ENOMEM, std::string("yolo_eval scratch: ") + hipGetErrorString(e));
-        yolo_scratch_bytes_ = cv.used;
+        yolo_scratch_.reset(cv.used, "yolo_eval scratch");
     }
-    unsigned char* base = yolo_scratch_;
+    unsigned char* base = yolo_scratch_.as<unsigned char>();
     for (int l = 0; l < num_layers; ++l) {
         float* d = reinterpret_cast<float*>(base + feat_off[l]);
         WHENET_HIP_CHECK(hipMemcpyAsync(d, feats[l], feat_bytes[l], hipMemcpyHostToDevice, stream_));
