@@ -509,6 +509,58 @@ int whenet_op_crop_resize(whenet_t* h, const uint8_t* frame, int frame_h, int fr
     });
 }
 
+int whenet_letterbox_plan(int in_h, int in_w, int out_h, int out_w, int32_t geom[4], int axis, int32_t* bounds, int32_t* coeffs,
+                          int cap, int* ksize) {
+    if (geom == nullptr || ksize == nullptr || (axis != 0 && axis != 1) || (bounds == nullptr) != (coeffs == nullptr)) return WHENET_EINVAL;
+    try {
+        const whenet::LetterboxPlan p = whenet::letterbox_plan_layout(in_h, in_w, out_h, out_w);
+        geom[0] = p.nw, geom[1] = p.nh, geom[2] = p.x0, geom[3] = p.y0;
+        const int in_size = axis == 0 ? in_w : in_h, out_size = axis == 0 ? p.nw : p.nh;
+        *ksize = axis == 0 ? p.ksx : p.ksy;
+        if (bounds == nullptr) return WHENET_OK;
+        if (cap < out_size * *ksize) return WHENET_EINVAL;
+        whenet::build_letterbox_axis(in_size, out_size, bounds, coeffs);
+        return WHENET_OK;
+    } catch (const whenet::Error& e) {
+        return e.code;
+    } catch (...) {
+        return WHENET_ENOMEM;
+    }
+}
+
+int whenet_op_letterbox(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, int out_h, int out_w,
+                        uint8_t* canvas_u8, float* image_f32) {
+    if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        e.op_letterbox(frame, frame_h, frame_w, channel_order == WHENET_BGR, out_h, out_w, canvas_u8, image_f32);
+    });
+}
+
+// the resident-frame form: the ticket of whenet_frame_begin carries its engine like every other ticket
+int whenet_frame_begin(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, int* ticket) {
+    if (ticket == nullptr || (channel_order != WHENET_RGB && channel_order != WHENET_BGR)) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        const size_t idx = h->next % size_t(h->inflight);
+        *ticket = h->take().frame_begin(frame, frame_h, frame_w, channel_order == WHENET_BGR) * MAX_INFLIGHT_ENGINES + int(idx);
+    });
+}
+
+int whenet_frame_letterbox(whenet_t* h, int ticket, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32) {
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        h->at(size_t(idx)).frame_letterbox(ticket / MAX_INFLIGHT_ENGINES, out_h, out_w, canvas_u8, image_f32);
+    });
+}
+
+int whenet_frame_heads(whenet_t* h, int ticket, const int32_t* rects, int k) {
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        h->at(size_t(idx)).frame_heads(ticket / MAX_INFLIGHT_ENGINES, rects, k);
+    });
+}
+
 int whenet_yolo_eval(whenet_t* h, const float* const* feats, const int* grid_h, const int* grid_w, int num_layers,
                      const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
                      float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,

@@ -202,6 +202,13 @@ class Engine {
     void op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, const int32_t* rects, int k,
                         uint8_t* crops_out);
     void collect(int ticket, float* ypr, int32_t* argmax, float* logits);
+    // the detector's letterbox (letterbox.hip) alone on a host frame, and the resident-frame form of submit_frame: the frame is
+    // uploaded when it arrives (the ticket is handed out and the slot held from then on), the detector input and the head crops
+    // are both cut from that one device copy; collect() returns the heads' results and frees the slot
+    void op_letterbox(const uint8_t* frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32);
+    int frame_begin(const uint8_t* frame, int fh, int fw, int swap_rb);
+    void frame_letterbox(int ticket, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32);
+    void frame_heads(int ticket, const int32_t* rects, int k);
     int profile(const uint8_t* d_crops, int n, int iters, whenet_launch_stat_t* stats, int cap);
 
     void op_stem(const uint8_t* crops, int n, float* out);
@@ -228,6 +235,8 @@ class Engine {
         StagedBuffer in, ypr, amax, logits;
         Event copied, done;
         StagedBuffer frame, plan;        // frame submissions: the frame and the crop plans travel instead of the crops
+        int frame_ticket = -1;           // resident frame: the ticket whose frame is held here and still waits for its heads
+        int fh = 0, fw = 0, swap_rb = 0; //   (tickets are never reused, so a stale value matches nothing)
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -311,6 +320,10 @@ class Engine {
     hipStream_t copy_stream();          // created on first use
     void ensure_slot_frame(Slot& s, size_t frame_bytes, int k);
     Slot* free_slot();
+    Slot& resident_slot(int ticket, const char* what);     // the held slot of a frame_begin ticket that has no heads yet
+    // frame on the device -> canvas in the caller's host arrays (either may be nullptr), through pinned memory with one wait
+    void run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                       float* image_f32);
     int finish_submission(Slot& s, int n);      // record `done`, mark the slot busy, hand out its ticket
 
     void open_device(int device_id);
@@ -385,6 +398,13 @@ class Engine {
     size_t partial_per_crop_ = 0;
     DeviceBuffer yolo_scratch_;     // device scratch of yolo_eval, grown on demand
     std::vector<int> yolo_counts_;               // host staging of the per-class detection counts
+    // letterbox scratch, grown on demand: the tables of the last geometry (kept: a video has one frame size), the horizontal
+    // pass's output, the /255 table, the outputs and their pinned landing zones, the frame of op_letterbox
+    LetterboxPlan lb_plan_{};
+    bool lb_plan_valid_ = false;
+    std::vector<int32_t> lb_tables_host_;
+    StagedBuffer lb_tables_, lb_u8_, lb_f32_;
+    DeviceBuffer lb_mid_, lb_lut_, lb_frame_;
 
     std::map<GraphKey, hipGraphExec_t> graphs_;
 

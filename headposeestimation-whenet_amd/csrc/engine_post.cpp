@@ -75,6 +75,118 @@ void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, c
     WHENET_HIP_CHECK(hipMemcpy(crops_out, d_out.as<void>(), obytes, hipMemcpyDeviceToHost));
 }
 
+// The detector's pre-processing (yolo_v3/utils.py:23-34 + yolo_postprocess.py:191-195) of a frame that is on the device.
+// The stream is idle on the letterbox scratch whenever this is entered: every call waits for its own results.
+void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                           float* image_f32) {
+    WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
+    if (!(lb_plan_valid_ && lb_plan_.ih == fh && lb_plan_.iw == fw && lb_plan_.oh == out_h && lb_plan_.ow == out_w)) {
+        lb_plan_valid_ = false;
+        const LetterboxPlan p = build_letterbox_plan(fh, fw, out_h, out_w, &lb_tables_host_);
+        const size_t tbytes = lb_tables_host_.size() * sizeof(int32_t);
+        lb_tables_.h.grow(tbytes);
+        lb_tables_.d.grow(tbytes);
+        std::memcpy(lb_tables_.h.as<void>(), lb_tables_host_.data(), tbytes);
+        WHENET_HIP_CHECK(hipMemcpyAsync(lb_tables_.d.as<void>(), lb_tables_.h.as<void>(), tbytes, hipMemcpyHostToDevice, stream_));
+        lb_plan_ = p;
+        lb_plan_valid_ = true;
+    }
+    if (lb_lut_.bytes() == 0) {
+        float lut[256];
+        letterbox_float_table(lut);
+        lb_lut_.reset(sizeof(lut));
+        WHENET_HIP_CHECK(hipMemcpy(lb_lut_.as<void>(), lut, sizeof(lut), hipMemcpyHostToDevice));
+    }
+    const LetterboxPlan& p = lb_plan_;
+    const size_t nout = size_t(out_h) * out_w * 3;
+    lb_mid_.grow(size_t(fh) * p.nw * 3);
+    if (canvas_u8) lb_u8_.h.grow(nout), lb_u8_.d.grow(nout);
+    if (image_f32) lb_f32_.h.grow(nout * sizeof(float)), lb_f32_.d.grow(nout * sizeof(float));
+    uint8_t* const d_u8 = canvas_u8 ? lb_u8_.d.as<uint8_t>() : nullptr;
+    float* const d_f32 = image_f32 ? lb_f32_.d.as<float>() : nullptr;
+    launch_letterbox(d_frame, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32,
+                     num_cus_, stream_);
+    if (canvas_u8) WHENET_HIP_CHECK(hipMemcpyAsync(lb_u8_.h.as<void>(), d_u8, nout, hipMemcpyDeviceToHost, stream_));
+    if (image_f32) WHENET_HIP_CHECK(hipMemcpyAsync(lb_f32_.h.as<void>(), d_f32, nout * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+    if (canvas_u8) std::memcpy(canvas_u8, lb_u8_.h.as<void>(), nout);
+    if (image_f32) std::memcpy(image_f32, lb_f32_.h.as<void>(), nout * sizeof(float));
+}
+
+void Engine::op_letterbox(const uint8_t* frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                          float* image_f32) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(frame != nullptr, WHENET_EINVAL, "op_letterbox: frame must not be NULL");
+    (void)letterbox_plan_layout(fh, fw, out_h, out_w);         // argument errors before anything is copied
+    const size_t fbytes = size_t(fh) * fw * 3;
+    lb_frame_.grow(fbytes);
+    WHENET_HIP_CHECK(hipMemcpyAsync(lb_frame_.as<void>(), frame, fbytes, hipMemcpyHostToDevice, stream_));
+    run_letterbox(lb_frame_.as<uint8_t>(), fh, fw, swap_rb, out_h, out_w, canvas_u8, image_f32);
+}
+
+// The resident-frame form of submit_frame.  frame_begin: pinned staging copy + asynchronous H2D into the slot's frame buffer; the
+// ticket is handed out here and the slot stays held.  (`done` is recorded at once with no heads: a collect that comes without
+// frame_heads returns no results and frees the slot.)
+int Engine::frame_begin(const uint8_t* frame, int fh, int fw, int swap_rb) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(frame != nullptr && fh > 0 && fw > 0, WHENET_EINVAL, "frame_begin: bad arguments");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const size_t fbytes = size_t(fh) * fw * 3;
+    slot.frame.h.grow(fbytes);
+    slot.frame.d.grow(fbytes);
+    std::memcpy(slot.frame.h.as<void>(), frame, fbytes);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.frame.d.as<void>(), slot.frame.h.as<void>(), fbytes, hipMemcpyHostToDevice, copy_stream()));
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = fh, slot.fw = fw, slot.swap_rb = swap_rb;
+    slot.frame_ticket = finish_submission(slot, 0);
+    return slot.frame_ticket;
+}
+
+Engine::Slot& Engine::resident_slot(int ticket, const char* what) {
+    for (Slot& s : slots_)
+        if (s.busy && s.ticket == ticket) {
+            WHENET_REQUIRE(s.frame_ticket == ticket, WHENET_EINVAL,
+                           std::string(what) + ": ticket " + std::to_string(ticket) +
+                               " holds no frame that waits for its heads (not from frame_begin, or its heads are already enqueued)");
+            return s;
+        }
+    throw Error(WHENET_EINVAL, std::string(what) + ": unknown or already collected ticket " + std::to_string(ticket));
+}
+
+void Engine::frame_letterbox(int ticket, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32) {
+    DeviceGuard guard(device_);
+    Slot& slot = resident_slot(ticket, "frame_letterbox");
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+    run_letterbox(slot.frame.d.as<uint8_t>(), slot.fh, slot.fw, slot.swap_rb, out_h, out_w, canvas_u8, image_f32);
+}
+
+// submit_frame from its crop plans on: nothing differs except that the frame is already on the device.
+void Engine::frame_heads(int ticket, const int32_t* rects, int k) {
+    DeviceGuard guard(device_);
+    Slot& slot = resident_slot(ticket, "frame_heads");
+    WHENET_REQUIRE(k >= 0 && (k == 0 || rects != nullptr), WHENET_EINVAL, "frame_heads: bad arguments");
+    check_rects(slot.fh, slot.fw, rects, k);
+    if (k > 0) {
+        require_model();
+        ensure_capacity(k);
+        ensure_slot(slot, k);
+        ensure_slot_frame(slot, size_t(slot.fh) * slot.fw * 3, k);
+        int32_t* const h_plan = slot.plan.h.as<int32_t>();
+        for (int i = 0; i < k; ++i) build_crop_plan(rects + 4 * i, h_plan + size_t(i) * CROP_PLAN_INTS);
+        WHENET_HIP_CHECK(hipMemcpyAsync(slot.plan.d.as<void>(), h_plan, size_t(k) * CROP_PLAN_INTS * sizeof(int32_t),
+                                        hipMemcpyHostToDevice, copy_stream()));
+        WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));      // (in order behind the frame's copy)
+        WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+        launch_crop_resize(slot.frame.d.as<uint8_t>(), slot.fw, slot.swap_rb, slot.plan.d.as<int32_t>(), k, slot.in.d.as<uint8_t>(), stream_);
+        run_forward(slot.in.d.as<uint8_t>(), k, slot.dev(), stream_);
+        copy_results_async(slot.host(), slot.dev(), k, stream_);
+    }
+    WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));
+    slot.n = k;
+    slot.frame_ticket = -1;
+}
+
 // yolo_eval (yolo_v3/model.py:193-232) on host feature maps: H2D, decode + NMS on the device, the selected boxes
 // back, concatenated class by class like the reference.  Returns the number of detections.
 int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* grid_w, int num_layers,

@@ -404,6 +404,28 @@ void build_crop_plan(const int32_t rect[4], int32_t* plan);
 void launch_crop_resize(const uint8_t* d_frame, int fw, int swap_rb, const int32_t* d_plan, int k, uint8_t* d_out,
                         hipStream_t stream);
 
+// ---- letterbox.hip ----------------------------------------------------------------------
+// The detector's pre-processing (yolo_v3/utils.py:23-34, yolo_postprocess.py:186-196): Pillow-exact BICUBIC resize at
+// unchanged aspect ratio, pasted centred on a grey canvas; uint8 and float32 (/255) outputs.
+constexpr int LETTERBOX_MAX_FRAME_SIDE = 8192;  // a frame row (3 bytes per pixel) is staged in LDS
+constexpr int LETTERBOX_MAX_BOX_SIDE = 4096;
+struct LetterboxPlan {                          // geometry + where each table lies in the int32 table block
+    int ih, iw, oh, ow;                         // frame and canvas
+    int nw, nh, x0, y0;                         // resized image and its paste offset
+    int ksx, ksy;                               // coefficient row stride per axis (Pillow's ksize)
+    int off_bx, off_cx, off_by, off_cy;         // bounds (xmin, n) x nw | coeffs [nw][ksx] | bounds x nh | coeffs [nh][ksy]
+    int table_ints;
+};
+int letterbox_axis_ksize(int in_size, int out_size);
+void build_letterbox_axis(int in_size, int out_size, int32_t* bounds, int32_t* coeffs);
+LetterboxPlan letterbox_plan_layout(int ih, int iw, int out_h, int out_w);      // throws WHENET_EINVAL (limits, nw / nh of zero)
+LetterboxPlan build_letterbox_plan(int ih, int iw, int out_h, int out_w, std::vector<int32_t>* tables);
+void letterbox_float_table(float lut[256]);
+// device pointers only: d_mid holds ih * nw * 3 bytes; either output may be nullptr
+void launch_letterbox(const uint8_t* d_frame, const LetterboxPlan& p, int swap_rb, const int32_t* d_tables,
+                      const float* d_lut, uint8_t* d_mid, uint8_t* d_canvas_u8, float* d_image_f32, int num_cus,
+                      hipStream_t stream);
+
 // ---- convert.hip ------------------------------------------------------------------------
 void launch_empty(hipStream_t stream);   // boundary calibration for whenet_profile()
 void launch_f32_to_act(const float* src, void* dst, size_t count, int dtype, hipStream_t stream);

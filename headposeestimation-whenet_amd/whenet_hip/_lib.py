@@ -10,7 +10,7 @@ from typing import Optional
 
 import numpy as np
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 F32, F16, F32S = 0, 1, 2          # include/whenet_hip.h WHENET_F32 / WHENET_F16 / WHENET_F32S
 OK, ENOENT, EIO, ENOMEM, ENODEV, EINVAL, EFORMAT, EHIP = 0, -2, -5, -12, -19, -22, -74, -1000
 MAX_INFLIGHT = 4
@@ -53,6 +53,12 @@ _PROTOS = {
     "whenet_normalise_table": (C.c_int, [_P]),
     "whenet_submit_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_crop_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "whenet_letterbox_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 4), C.c_int, _P, _P, C.c_int,
+                                        C.POINTER(C.c_int)]),
+    "whenet_op_letterbox": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_frame_begin": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "whenet_frame_letterbox": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_frame_heads": (C.c_int, [_P, C.c_int, _P, C.c_int]),
     "whenet_yolo_eval": (C.c_int, [_P, C.POINTER(_P), _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int), _P, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
@@ -137,6 +143,28 @@ def normalise_lut() -> np.ndarray:
     out = np.empty((3, 256), np.float32)
     raise_for(load().whenet_normalise_table(_ptr(out)), "whenet_normalise_table: bad arguments")
     return out
+
+
+def letterbox_plan(frame_h: int, frame_w: int, out_h: int, out_w: int):
+    """The letterbox geometry and resample tables as the kernels use them (yolo_v3/utils.py:25-33 + Pillow's
+    precompute_coeffs / normalize_coeffs_8bpc): ((nw, nh, x0, y0), [(ksize, bounds int32 [n,2], coeffs int32 [n,ksize]) for the
+    horizontal and the vertical axis]).  Pure host arithmetic inside the library (no GPU needed)."""
+    lib = load()
+    geom = (C.c_int32 * 4)()
+    axes = []
+    for axis in (0, 1):
+        ks = C.c_int(0)
+        args = (int(frame_h), int(frame_w), int(out_h), int(out_w), C.byref(geom), axis)
+        raise_for(lib.whenet_letterbox_plan(*args, None, None, 0, C.byref(ks)),
+                  f"whenet_letterbox_plan({frame_h}x{frame_w} -> {out_h}x{out_w}): frame sides 1..8192, output sides 1..4096, "
+                  "and the resized image needs at least one pixel per side")
+        n = geom[0] if axis == 0 else geom[1]
+        bounds = np.empty((n, 2), np.int32)
+        coeffs = np.empty((n, ks.value), np.int32)
+        raise_for(lib.whenet_letterbox_plan(*args, _ptr(bounds), _ptr(coeffs), coeffs.size, C.byref(ks)),
+                  "whenet_letterbox_plan: bad arguments")
+        axes.append((ks.value, bounds, coeffs))
+    return tuple(geom), axes
 
 
 class WhenetError(RuntimeError):
@@ -279,6 +307,41 @@ class Handle:
         self._check(self._lib.whenet_op_crop_resize(self._h, _ptr(frame), frame.shape[0], frame.shape[1],
                                                     BGR if bgr else RGB, _ptr(rects), rects.shape[0], _ptr(out)))
         return out
+
+    @staticmethod
+    def _letterbox_outputs(size, want_u8: bool, want_f32: bool):
+        oh, ow = int(size[0]), int(size[1])
+        if oh < 1 or ow < 1:
+            raise ValueError(f"letterbox: size must be (h, w) >= 1, got {size}")
+        u8 = np.empty((oh, ow, 3), np.uint8) if want_u8 else None
+        f32 = np.empty((oh, ow, 3), np.float32) if want_f32 else None
+        return oh, ow, u8, f32
+
+    def op_letterbox(self, frame: np.ndarray, size=(416, 416), bgr: bool = True, want_u8: bool = True, want_f32: bool = True):
+        """yolo_v3/utils.py:23-34 + yolo_postprocess.py:191-195 on the device: frame uint8 [H,W,3] -> (canvas uint8 [h,w,3],
+        image float32 [h,w,3] = canvas / 255); `size` = (h, w) as the reference's model_image_size.  An output not wanted is None."""
+        frame = _frame_u8(frame)
+        oh, ow, u8, f32 = self._letterbox_outputs(size, want_u8, want_f32)
+        self._check(self._lib.whenet_op_letterbox(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB,
+                                                  oh, ow, _ptr(u8), _ptr(f32)))
+        return u8, f32
+
+    def frame_begin(self, frame: np.ndarray, bgr: bool = True) -> int:
+        """Upload the frame once; the ticket is carried through frame_letterbox / frame_heads to collect."""
+        frame = _frame_u8(frame)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB,
+                                                 C.byref(t)))
+        return t.value
+
+    def frame_letterbox(self, ticket: int, size=(416, 416), want_u8: bool = True, want_f32: bool = True):
+        oh, ow, u8, f32 = self._letterbox_outputs(size, want_u8, want_f32)
+        self._check(self._lib.whenet_frame_letterbox(self._h, int(ticket), oh, ow, _ptr(u8), _ptr(f32)))
+        return u8, f32
+
+    def frame_heads(self, ticket: int, rects: np.ndarray) -> None:
+        rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        self._check(self._lib.whenet_frame_heads(self._h, int(ticket), _ptr(rects), rects.shape[0]))
 
     def yolo_eval(self, yolo_outputs, anchors, num_classes: int, image_shape, max_boxes: int = 20,
                   score_threshold: float = .6, iou_threshold: float = .5, debug: bool = False):

@@ -11,7 +11,11 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     bit-exact with OpenCV's generic fixed-point INTER_LINEAR as restated in the oracle);
   * the k heads go through the network as ONE batch;
   * `submit()` returns as soon as the work is enqueued, so the caller can run the detector on the
-    next frame while this one is on the GPU; `collect()` returns results in submission order.
+    next frame while this one is on the GPU; `collect()` returns results in submission order;
+  * a caller that also wants the DETECTOR's input from the GPU uses the resident form: `begin(frame)`
+    uploads the frame once, `detector_input()` returns the `image_data` of YOLO.detect
+    (yolo_postprocess.py:186-196: Pillow-BICUBIC letterbox and /255, `csrc/letterbox.hip`, bit-exact),
+    `heads(bboxes)` enqueues what `submit()` enqueues without copying the frame again.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -46,11 +50,14 @@ class FramePipeline:
         self._depth = depth
         self._bgr = bool(bgr)
         self._pending: Deque[Tuple[int, np.ndarray]] = deque()
+        self._begun = None         # (ticket, frame_h, frame_w) of the frame begun last, until its heads are enqueued
 
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
+        if self._begun is not None:            # a frame without heads: released as a frame with none
+            self.heads(np.zeros((0, 4), np.float32))
         while self._pending:
             self.collect()
 
@@ -68,6 +75,40 @@ class FramePipeline:
             raise ValueError(f"frame must be uint8 [H,W,3], got {frame.dtype} {frame.shape}")
         rects = _lib.frame_rects(frame.shape[0], frame.shape[1], bboxes)
         ticket = self._h.submit_frame(frame, rects, bgr=self._bgr)
+        self._pending.append((ticket, rects))
+
+    def begin(self, frame: np.ndarray) -> None:
+        """Resident form, step 1: upload the frame (it crosses PCIe once).  The frame holds one of the `depth`
+        places from here until its `collect()`; `heads()` must follow before the next `begin()` / `submit()`."""
+        if self._begun is not None:
+            raise ValueError("the frame begun last has no heads yet: heads() first")
+        if len(self._pending) >= self._depth:
+            raise ValueError(f"{self._depth} frames already in flight: collect() first")
+        frame = np.asarray(frame)
+        if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
+            raise ValueError(f"frame must be uint8 [H,W,3], got {frame.dtype} {frame.shape}")
+        ticket = self._h.frame_begin(frame, bgr=self._bgr)
+        self._begun = (ticket, frame.shape[0], frame.shape[1])
+
+    def detector_input(self, size=(416, 416), as_uint8: bool = False) -> np.ndarray:
+        """Resident form, step 2 (any number of times): float32 [1, h, w, 3], the `image_data` YOLO.detect feeds to
+        sess.run, cut from the frame begun last; `size` = (h, w) as `model_image_size`, multiples of 32."""
+        from .yolo import check_model_image_size
+        if self._begun is None:
+            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        check_model_image_size(size)
+        u8, f32 = self._h.frame_letterbox(self._begun[0], size, want_u8=as_uint8, want_f32=not as_uint8)
+        return u8 if as_uint8 else f32[None]
+
+    def heads(self, bboxes) -> None:
+        """Resident form, step 3: the detector's boxes of the frame begun last (an empty list is fine) -> margins,
+        crops, one batched forward, exactly as `submit()`; `collect()` returns them in order with the submitted frames."""
+        if self._begun is None:
+            raise ValueError("no frame begun: begin() first")
+        ticket, fh, fw = self._begun
+        rects = _lib.frame_rects(fh, fw, bboxes)
+        self._h.frame_heads(ticket, rects)
+        self._begun = None
         self._pending.append((ticket, rects))
 
     def collect(self):

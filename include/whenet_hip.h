@@ -39,8 +39,10 @@ extern "C" {
  * 4 (round 5): dtype WHENET_F32S; whenet_normalise_table; options pw_staged, split_pw, fanout_min / _chunk / _stage / _depth,
  * host_pinned_max, host_lanes, se_fuse_tiny.  (Additions only: a version-3 caller runs unchanged.)
  * (round 6, still 4 -- options only: mb7, f2s_mask, se_fuse = 3, fanout_engines, fanout_stage = 2 | 3; the fan-out's default form is 2.)
- * (round 7, still 4 -- option act_layout.) */
-#define WHENET_ABI_VERSION 4
+ * (round 7, still 4 -- option act_layout.)
+ * 5 (round 8): whenet_letterbox_plan, whenet_op_letterbox and the resident-frame form whenet_frame_begin / whenet_frame_letterbox /
+ * whenet_frame_heads.  (Additions only: a version-4 caller runs unchanged.) */
+#define WHENET_ABI_VERSION 5
 #define WHENET_API __attribute__((visibility("default")))
 
 /* return codes (negative errno-style) */
@@ -271,6 +273,41 @@ WHENET_API int whenet_submit_frame(whenet_t* h, const uint8_t* frame, int frame_
  * get_angle would have been handed */
 WHENET_API int whenet_op_crop_resize(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order,
                           const int32_t* rects, int k, uint8_t* crops);
+
+/* ---- the detector's PRE-processing on the device: replaces `letterbox_image` (yolo_v3/utils.py:23-34: Pillow BICUBIC resize at
+ * unchanged aspect ratio, pasted centred on a grey (128, 128, 128) canvas) and `np.array(boxed_image, 'float32') / 255.`
+ * (yolo_v3/yolo_postprocess.py:186-196), which YOLO.detect runs on the host for every frame.  Bit-exact with Pillow's 8-bit
+ * resample: its coefficient tables are computed on the host in double exactly as Pillow computes them, the kernels are int32
+ * arithmetic.  out_h / out_w are the reference's `model_image_size` (h, w); the reference asserts multiples of 32, this
+ * interface takes any size.  LIMITS: frame sides 1..8192, output sides 1..4096; a frame so thin that the resized image would
+ * have a side of zero pixels is WHENET_EINVAL (Pillow raises there).
+ *
+ * whenet_letterbox_plan: the geometry -- geom = {nw, nh, x0, y0}: size of the resized image and where it is pasted -- and the
+ * resample tables of one axis (0 = horizontal, in_w -> nw; 1 = vertical, in_h -> nh) as the kernels use them:
+ * bounds [n_out][2] = (first source pixel, number of taps), coeffs [n_out][*ksize] int32 with 22 fractional bits, zero beyond the
+ * taps.  `cap` = ints `coeffs` can hold (n_out * *ksize needed; `bounds` holds 2 * n_out).  bounds and coeffs may both be NULL:
+ * geom and *ksize alone.  Pure host arithmetic, no GPU needed. */
+WHENET_API int whenet_letterbox_plan(int in_h, int in_w, int out_h, int out_w, int32_t geom[4], int axis, int32_t* bounds,
+                          int32_t* coeffs, int cap, int* ksize);
+/* the stage alone (host pointers): frame uint8 [frame_h, frame_w, 3] -> canvas_u8 uint8 [out_h, out_w, 3] and / or image_f32
+ * float [out_h, out_w, 3] = canvas / 255 in float32, the `image_data` YOLO.detect feeds to sess.run (before its batch axis).
+ * Either output may be NULL.  Works on a whenet_create_postproc handle. */
+WHENET_API int whenet_op_letterbox(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, int out_h,
+                        int out_w, uint8_t* canvas_u8, float* image_f32);
+/* The RESIDENT-FRAME form of whenet_submit_frame for a caller that also wants the detector input: the frame crosses PCIe once,
+ * when it arrives, and the detector input and the head crops are both cut from that one device copy.
+ *   whenet_frame_begin      pinned staging copy + asynchronous H2D of the frame; hands out the ticket and HOLDS the submission
+ *                           slot from here on (order, WHENET_MAX_INFLIGHT and option "inflight" as for whenet_submit_frame)
+ *   whenet_frame_letterbox  the letterbox of the resident frame, results through pinned memory with one wait; any number of
+ *                           times (any sizes) before the heads are enqueued
+ *   whenet_frame_heads      crop plans -> crop / resize -> forward -> D2H enqueued exactly as whenet_submit_frame does, without
+ *                           copying the frame again; k = 0 is valid
+ *   whenet_collect          returns the k heads' results and frees the slot
+ * A ticket that never gets heads is released by whenet_frame_heads(h, ticket, NULL, 0) + whenet_collect.  An unknown ticket,
+ * heads enqueued twice and a letterbox after the heads are WHENET_EINVAL; the handle stays usable. */
+WHENET_API int whenet_frame_begin(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, int* ticket);
+WHENET_API int whenet_frame_letterbox(whenet_t* h, int ticket, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32);
+WHENET_API int whenet_frame_heads(whenet_t* h, int ticket, const int32_t* rects, int k);
 
 /* ---- the detector's post-processing on the device: replaces yolo_eval (yolo_v3/model.py:193-232 =
  * yolo_head :125-150, yolo_correct_boxes :153-178, yolo_boxes_and_scores :181-190, per-class
