@@ -274,6 +274,7 @@ int whenet_set_option(whenet_t* h, const char* key, long value) {
                 std::unique_ptr<whenet::Engine> r(
                     new whenet::Engine(h->snapshot.data(), h->snapshot.size(), h->device_id, h->dtype));
                 for (const auto& kv : h->options) r->set_option(kv.first, kv.second);
+                if (e.has_detector()) r->share_detector(e);
                 h->replicas.push_back(r.release());
             }
             h->inflight = int(value);
@@ -570,6 +571,103 @@ int whenet_yolo_eval(whenet_t* h, const float* const* feats, const int* grid_h, 
         *count = e.yolo_eval(feats, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_h, image_w,
                              score_threshold, iou_threshold, max_boxes, boxes, scores, classes, index, all_boxes,
                              all_scores);
+    });
+}
+
+// ---- the detector body (detector.cpp) ----
+namespace {
+int read_file(const char* path, std::vector<char>& blob, std::string& err) {
+    try {
+        std::ifstream f(path, std::ios::binary | std::ios::ate);
+        if (!f) {
+            err = std::string("cannot open snapshot '") + path + "'";
+            return WHENET_ENOENT;
+        }
+        const std::streamoff sz = f.tellg();
+        if (sz < 0 || !f.seekg(0) || uint64_t(sz) > (uint64_t(1) << 32)) {
+            err = std::string("snapshot '") + path + "' is not a readable regular file";
+            return WHENET_EIO;
+        }
+        blob.resize(size_t(sz));
+        if (sz > 0 && !f.read(blob.data(), std::streamsize(sz))) {
+            err = std::string("cannot read snapshot '") + path + "'";
+            return WHENET_EIO;
+        }
+        return WHENET_OK;
+    } catch (const std::bad_alloc&) {
+        err = "out of host memory";
+        return WHENET_ENOMEM;
+    } catch (...) {
+        err = std::string("cannot read snapshot '") + path + "'";
+        return WHENET_EIO;
+    }
+}
+}  // namespace
+
+int whenet_detector_load_from_memory(whenet_t* h, const void* snapshot, size_t nbytes) {
+    return guarded(h, [&](whenet::Engine& e) {
+        e.detector_load(snapshot, nbytes);
+        for (whenet::Engine* r : h->replicas) r->share_detector(e);
+    });
+}
+
+int whenet_detector_load(whenet_t* h, const char* snapshot_path) {
+    if (h == nullptr || h->engine == nullptr || snapshot_path == nullptr) return WHENET_EINVAL;
+    std::vector<char> blob;
+    const int rc = read_file(snapshot_path, blob, h->engine->last_error);
+    if (rc != WHENET_OK) return rc;
+    return whenet_detector_load_from_memory(h, blob.data(), blob.size());
+}
+
+int whenet_detector_spec(int kind, int anchors_per_scale, int num_classes, int index, int32_t out[12], int* count) {
+    if ((kind != 0 && kind != 1) || anchors_per_scale < 1 || num_classes < 1 || anchors_per_scale > 64 || num_classes > 4096) return WHENET_EINVAL;
+    try {
+        const std::vector<whenet::DetLayer> t = whenet::detector_table(kind, anchors_per_scale * (num_classes + 5));
+        if (count) *count = int(t.size());
+        if (out == nullptr) return count ? WHENET_OK : WHENET_EINVAL;
+        if (index < 0 || index >= int(t.size())) return WHENET_EINVAL;
+        const whenet::DetLayer& L = t[size_t(index)];
+        const int32_t v[12] = {L.op, L.k, L.stride, L.cin, L.cout, L.bn, L.leaky, L.src0, L.src1, L.skip, L.is_output, L.cin0};
+        std::memcpy(out, v, sizeof(v));
+        return WHENET_OK;
+    } catch (const whenet::Error& e) {
+        return e.code;
+    } catch (...) {
+        return WHENET_ENOMEM;
+    }
+}
+
+int whenet_op_dconv(whenet_t* h, const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel,
+                    const float* bias, int k, int stride, int cout, int leaky, const float* skip, int f32_out, float* out) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_dconv(in, n, H, W, cin, in2, cin2, kernel, bias, k, stride, cout, leaky, skip, f32_out, out); });
+}
+
+int whenet_op_dpool(whenet_t* h, const float* in, int n, int H, int W, int c, int stride, float* out) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_dpool(in, n, H, W, c, stride, out); });
+}
+
+int whenet_detector_forward(whenet_t* h, const float* image, int n, int H, int W, float* const* maps) {
+    return guarded(h, [&](whenet::Engine& e) { e.detector_forward(image, n, H, W, maps); });
+}
+
+int whenet_op_detect(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, int out_h, int out_w,
+                     const float* anchors, int num_anchors, float score_threshold, float iou_threshold, int max_boxes, float* boxes,
+                     float* scores, int32_t* classes, int* count) {
+    if (count == nullptr || (channel_order != WHENET_RGB && channel_order != WHENET_BGR)) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        *count = e.op_detect(frame, frame_h, frame_w, channel_order == WHENET_BGR, out_h, out_w, anchors, num_anchors, score_threshold,
+                             iou_threshold, max_boxes, boxes, scores, classes);
+    });
+}
+
+int whenet_frame_detect(whenet_t* h, int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold,
+                        float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int* count) {
+    if (count == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        *count = h->at(size_t(idx)).frame_detect(ticket / MAX_INFLIGHT_ENGINES, out_h, out_w, anchors, num_anchors, score_threshold,
+                                                 iou_threshold, max_boxes, boxes, scores, classes);
     });
 }
 

@@ -7,6 +7,7 @@
 #include <memory>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -167,6 +168,21 @@ struct LaunchRecorder {
 
 constexpr int MAX_LANES = 8;
 
+// One row of the detector body's layer table (detector.cpp): a convolution or a pool in the reference's layer-creation order; the
+// layers around it (zero padding, BatchNorm, LeakyReLU, Add, UpSampling2D + Concatenate) are properties of the row.
+enum { DET_CONV = 0, DET_POOL = 1 };
+struct DetLayer {
+    int op, k, stride, cin, cout, bn, leaky;
+    int src0;          // row whose output is read (-1: the image); with src1 it is the HALF-resolution tensor, upsampled by 2
+    int src1;          // row concatenated behind the upsampled src0 (channels cin0..), or -1
+    int skip;          // row added to the activated output (Add), or -1
+    int is_output;     // linear convolution with a bias, float32 map [gh][gw][A (5 + C)]
+    int cin0;          // channels of src0
+};
+std::vector<DetLayer> detector_table(int kind, int out_filters);      // kind 0 = yolo_body (75 rows), 1 = tiny_yolo_body (19 rows)
+struct Detector;
+struct DetPlan;
+
 class Engine {
   public:
     Engine(const void* snapshot, size_t nbytes, int device_id, int dtype);      // dtype: WHENET_F32 / F16 / F32S
@@ -220,6 +236,19 @@ class Engine {
     void op_block_range(int first, int last, const float* in, int n, float* out);
     void op_head(const float* in, int n, float* feat, float* logits, float* ypr, int32_t* argmax);
     void op_decode(const float* logits, int n, float* ypr, int32_t* argmax);
+    // the detector body (detector.cpp): attach its weights, the body alone on host images, YOLO.detect on a host frame and on a
+    // resident one (letterbox -> body -> yolo_eval on the device; return the number of detections), and single layers for the tests
+    void detector_load(const void* snapshot, size_t nbytes);
+    void share_detector(const Engine& from);
+    bool has_detector() const { return det_ != nullptr; }
+    void detector_forward(const float* image, int n, int H, int W, float* const* maps);
+    int op_detect(const uint8_t* frame, int fh, int fw, int swap_rb, int out_h, int out_w, const float* anchors, int num_anchors,
+                  float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes);
+    int frame_detect(int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold, float iou_threshold,
+                     int max_boxes, float* boxes, float* scores, int32_t* classes);
+    void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
+                  int stride, int cout, int leaky, const float* skip, int f32_out, float* out);
+    void op_dpool(const float* in, int n, int H, int W, int c, int stride, float* out);
 
     void* dev_alloc(size_t nbytes);
     void dev_free(void* p);
@@ -325,6 +354,18 @@ class Engine {
     void run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
                        float* image_f32);
     int finish_submission(Slot& s, int n);      // record `done`, mark the slot busy, hand out its ticket
+    // run_letterbox's launches alone: the device canvas (uint8, float32) of those asked for, valid until the next letterbox
+    std::pair<uint8_t*, float*> enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, bool want_u8,
+                                                  bool want_f32);
+    // yolo_eval on maps that are in host memory (uploaded first) or already on the device
+    int yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
+                       int num_anchors, int num_classes, float image_h, float image_w, float score_threshold, float iou_threshold,
+                       int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index, float* all_boxes, float* all_scores);
+    void require_detector() const;
+    DetPlan& detector_plan(int n, int H, int W);
+    void enqueue_detector(DetPlan& p, hipStream_t s);
+    int detect_device(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, const float* anchors, int num_anchors,
+                      float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes);
 
     void open_device(int device_id);
     void require_model() const;
@@ -418,6 +459,8 @@ class Engine {
     void ensure_host_out(int n);
     int host_pinned_max_ = 8;      // measured round 5: pinned wins up to 8 crops (B=1 f32 420 vs 445 us), loses at 16-32
     int next_ticket_ = 0;
+    std::shared_ptr<Detector> det_;    // (declared last: its buffers and graphs go first)
+    std::map<std::tuple<int, int, int>, std::shared_ptr<DetPlan>> det_plans_;      // by (n, H, W)
 };
 
 }  // namespace whenet

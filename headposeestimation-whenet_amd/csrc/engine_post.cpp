@@ -77,9 +77,8 @@ void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, c
 
 // The detector's pre-processing (yolo_v3/utils.py:23-34 + yolo_postprocess.py:191-195) of a frame that is on the device.
 // The stream is idle on the letterbox scratch whenever this is entered: every call waits for its own results.
-void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
-                           float* image_f32) {
-    WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
+std::pair<uint8_t*, float*> Engine::enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w,
+                                                      bool want_u8, bool want_f32) {
     if (!(lb_plan_valid_ && lb_plan_.ih == fh && lb_plan_.iw == fw && lb_plan_.oh == out_h && lb_plan_.ow == out_w)) {
         lb_plan_valid_ = false;
         const LetterboxPlan p = build_letterbox_plan(fh, fw, out_h, out_w, &lb_tables_host_);
@@ -100,12 +99,22 @@ void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, 
     const LetterboxPlan& p = lb_plan_;
     const size_t nout = size_t(out_h) * out_w * 3;
     lb_mid_.grow(size_t(fh) * p.nw * 3);
-    if (canvas_u8) lb_u8_.h.grow(nout), lb_u8_.d.grow(nout);
-    if (image_f32) lb_f32_.h.grow(nout * sizeof(float)), lb_f32_.d.grow(nout * sizeof(float));
-    uint8_t* const d_u8 = canvas_u8 ? lb_u8_.d.as<uint8_t>() : nullptr;
-    float* const d_f32 = image_f32 ? lb_f32_.d.as<float>() : nullptr;
+    if (want_u8) lb_u8_.h.grow(nout), lb_u8_.d.grow(nout);
+    if (want_f32) lb_f32_.h.grow(nout * sizeof(float)), lb_f32_.d.grow(nout * sizeof(float));
+    uint8_t* const d_u8 = want_u8 ? lb_u8_.d.as<uint8_t>() : nullptr;
+    float* const d_f32 = want_f32 ? lb_f32_.d.as<float>() : nullptr;
     launch_letterbox(d_frame, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32,
                      num_cus_, stream_);
+    return {d_u8, d_f32};
+}
+
+void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                           float* image_f32) {
+    WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
+    const size_t nout = size_t(out_h) * out_w * 3;
+    const auto dev = enqueue_letterbox(d_frame, fh, fw, swap_rb, out_h, out_w, canvas_u8 != nullptr, image_f32 != nullptr);
+    uint8_t* const d_u8 = dev.first;
+    float* const d_f32 = dev.second;
     if (canvas_u8) WHENET_HIP_CHECK(hipMemcpyAsync(lb_u8_.h.as<void>(), d_u8, nout, hipMemcpyDeviceToHost, stream_));
     if (image_f32) WHENET_HIP_CHECK(hipMemcpyAsync(lb_f32_.h.as<void>(), d_f32, nout * sizeof(float), hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -194,6 +203,15 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
                       float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
                       int32_t* classes, int32_t* index, float* all_boxes, float* all_scores) {
     DeviceGuard guard(device_);
+    return yolo_eval_maps(feats, false, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_h, image_w, score_threshold,
+                          iou_threshold, max_boxes, boxes, scores, classes, index, all_boxes, all_scores);
+}
+
+// on_device: the maps are where the detector body left them (detector.cpp); nothing is uploaded
+int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
+                           const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
+                           float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
+                           int32_t* classes, int32_t* index, float* all_boxes, float* all_scores) {
     WHENET_REQUIRE(feats && grid_h && grid_w && anchors && boxes && scores && classes, WHENET_EINVAL,
                    "yolo_eval: NULL argument");
     WHENET_REQUIRE((num_layers == 3 && num_anchors == 9) || (num_layers == 2 && num_anchors == 6), WHENET_EINVAL,
@@ -249,7 +267,7 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
             L.anchor[k][1] = anchors[2 * m + 1];
         }
         feat_bytes[l] = size_t(L.gh) * L.gw * per * sizeof(float);
-        feat_off[l] = cv.add(feat_bytes[l]);
+        if (!on_device) feat_off[l] = cv.add(feat_bytes[l]);
         N += L.gh * L.gw * 3;
     }
     a.N = N;
@@ -272,6 +290,10 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
     }
     unsigned char* base = yolo_scratch_.as<unsigned char>();
     for (int l = 0; l < num_layers; ++l) {
+        if (on_device) {
+            a.layer[l].feats = feats[l];
+            continue;
+        }
         float* d = reinterpret_cast<float*>(base + feat_off[l]);
         WHENET_HIP_CHECK(hipMemcpyAsync(d, feats[l], feat_bytes[l], hipMemcpyHostToDevice, stream_));
         a.layer[l].feats = d;

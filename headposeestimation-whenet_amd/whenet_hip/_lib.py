@@ -10,7 +10,7 @@ from typing import Optional
 
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 F32, F16, F32S = 0, 1, 2          # include/whenet_hip.h WHENET_F32 / WHENET_F16 / WHENET_F32S
 OK, ENOENT, EIO, ENOMEM, ENODEV, EINVAL, EFORMAT, EHIP = 0, -2, -5, -12, -19, -22, -74, -1000
 MAX_INFLIGHT = 4
@@ -61,6 +61,17 @@ _PROTOS = {
     "whenet_frame_heads": (C.c_int, [_P, C.c_int, _P, C.c_int]),
     "whenet_yolo_eval": (C.c_int, [_P, C.POINTER(_P), _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int), _P, _P]),
+    "whenet_detector_load": (C.c_int, [_P, C.c_char_p]),
+    "whenet_detector_load_from_memory": (C.c_int, [_P, _P, C.c_size_t]),
+    "whenet_detector_spec": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 12), C.POINTER(C.c_int)]),
+    "whenet_op_dconv": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  _P, C.c_int, _P]),
+    "whenet_op_dpool": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "whenet_detector_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "whenet_op_detect": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int,
+                                   _P, _P, _P, C.POINTER(C.c_int)]),
+    "whenet_frame_detect": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P,
+                                      C.POINTER(C.c_int)]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -383,6 +394,91 @@ class Handle:
         res = (boxes[:k].copy(), scores[:k].copy(), classes[:k].copy())
         return res + (index[:k].copy(), all_boxes, all_scores) if debug else res
 
+    # ---- the detector body (csrc/detector.cpp) --------------------------------------------------
+    def detector_load(self, snapshot) -> None:
+        """Attach a detector: packed snapshot bytes or a path (whenet_hip/detector_weights.py)."""
+        if isinstance(snapshot, (bytes, bytearray, memoryview)):
+            buf = (C.c_char * len(snapshot)).from_buffer_copy(bytes(snapshot))
+            self._check(self._lib.whenet_detector_load_from_memory(self._h, C.cast(buf, _P), len(snapshot)))
+        else:
+            self._check(self._lib.whenet_detector_load(self._h, os.fsencode(snapshot)))
+
+    def detector_forward(self, image: np.ndarray, kind: int, out_filters: int):
+        """yolo_model.predict(image_data): image float32 [n,H,W,3] -> list of maps [n,gh,gw,out_filters], coarsest first."""
+        x = np.ascontiguousarray(image, np.float32)
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError(f"detector_forward: image must be float32 [n,H,W,3], got {x.shape}")
+        n, H, W, _ = x.shape
+        if H % 32 or W % 32 or H < 32 or W < 32:
+            raise ValueError(f"Multiples of 32 required, got image size {(H, W)}")
+        maps = [np.empty((n, (H // 32) << l, (W // 32) << l, out_filters), np.float32) for l in range(2 if kind == 1 else 3)]
+        ptrs = (_P * len(maps))(*[_ptr(m) for m in maps])
+        self._check(self._lib.whenet_detector_forward(self._h, _ptr(x), n, H, W, ptrs))
+        return maps
+
+    @staticmethod
+    def _detect_outputs(anchors, num_classes: int, max_boxes: int):
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 2)
+        if max_boxes < 1:
+            raise ValueError("detect: max_boxes must be >= 1")
+        cap = int(num_classes) * int(max_boxes)
+        return anchors, np.empty((cap, 4), np.float32), np.empty(cap, np.float32), np.empty(cap, np.int32), C.c_int(0)
+
+    def op_detect(self, frame: np.ndarray, anchors, num_classes: int, size=(416, 416), score: float = .3, iou: float = .45,
+                  max_boxes: int = 20, bgr: bool = True):
+        """YOLO.detect (yolo_postprocess.py:180-205) of one host frame on the device: (boxes [k,4], scores [k], classes [k])."""
+        frame = _frame_u8(frame)
+        anchors, boxes, scores, classes, count = self._detect_outputs(anchors, num_classes, max_boxes)
+        self._check(self._lib.whenet_op_detect(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, int(size[0]),
+                                               int(size[1]), _ptr(anchors), anchors.shape[0], float(score), float(iou), int(max_boxes),
+                                               _ptr(boxes), _ptr(scores), _ptr(classes), C.byref(count)))
+        k = count.value
+        return boxes[:k].copy(), scores[:k].copy(), classes[:k].copy()
+
+    def frame_detect(self, ticket: int, anchors, num_classes: int, size=(416, 416), score: float = .3, iou: float = .45,
+                     max_boxes: int = 20):
+        """The same on the resident frame of `ticket` (frame_begin), before its heads."""
+        anchors, boxes, scores, classes, count = self._detect_outputs(anchors, num_classes, max_boxes)
+        self._check(self._lib.whenet_frame_detect(self._h, int(ticket), int(size[0]), int(size[1]), _ptr(anchors), anchors.shape[0],
+                                                  float(score), float(iou), int(max_boxes), _ptr(boxes), _ptr(scores), _ptr(classes),
+                                                  C.byref(count)))
+        k = count.value
+        return boxes[:k].copy(), scores[:k].copy(), classes[:k].copy()
+
+    def op_dconv(self, x: np.ndarray, kernel: np.ndarray, bias: np.ndarray, stride: int = 1, leaky: bool = True, x2=None, skip=None,
+                 f32_out: bool = False) -> np.ndarray:
+        """One convolution of the body on caller tensors: x [n,H,W,cin] (with x2 [n,2H,2W,cin2]: the half-resolution source of the
+        upsample + concatenate read), kernel HWIO, bias [cout] -> [n,Ho,Wo,cout] float32."""
+        x = np.ascontiguousarray(x, np.float32)
+        kernel = np.ascontiguousarray(kernel, np.float32)
+        bias = np.ascontiguousarray(bias, np.float32)
+        k, _, ctot, cout = kernel.shape
+        n, cin = x.shape[0], x.shape[3]
+        if x2 is not None:
+            x2 = np.ascontiguousarray(x2, np.float32)
+            H, W, cin2 = x2.shape[1], x2.shape[2], x2.shape[3]
+            assert x.shape[1:3] == (H // 2, W // 2) and x2.shape[0] == n, (x.shape, x2.shape)
+        else:
+            H, W, cin2 = x.shape[1], x.shape[2], 0
+        assert kernel.shape[0] == kernel.shape[1] and ctot == cin + cin2 and bias.shape == (cout,), (kernel.shape, cin, cin2, bias.shape)
+        Ho, Wo = ((H - 2) // 2 + 1, (W - 2) // 2 + 1) if stride == 2 else (H, W)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.float32)
+            assert skip.shape == (n, Ho, Wo, cout), skip.shape
+        out = np.empty((n, Ho, Wo, cout), np.float32)
+        self._check(self._lib.whenet_op_dconv(self._h, _ptr(x), n, H, W, cin, _ptr(x2), cin2, _ptr(kernel), _ptr(bias), k, int(stride),
+                                              cout, int(bool(leaky)), _ptr(skip), int(bool(f32_out)), _ptr(out)))
+        return out
+
+    def op_dpool(self, x: np.ndarray, stride: int) -> np.ndarray:
+        """MaxPooling2D(2, strides=stride, 'same') of the tiny body on x [n,H,W,c] -> float32."""
+        x = np.ascontiguousarray(x, np.float32)
+        n, H, W, c = x.shape
+        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if stride == 2 else (H, W)
+        out = np.empty((n, Ho, Wo, c), np.float32)
+        self._check(self._lib.whenet_op_dpool(self._h, _ptr(x), n, H, W, c, int(stride), _ptr(out)))
+        return out
+
     def collect(self, ticket: int, n: int, want_logits: bool = False):
         ypr = np.empty((n, 3), np.float32)
         am = np.empty((n, 3), np.int32)
@@ -505,3 +601,22 @@ def front_plan(dtype: int, index: int) -> dict:
         raise_for(rc, f"whenet_front_plan({dtype},{index})")
     keys = ("threads", "CC", "TH", "NSX", "tiles_x", "tiles_y", "chunks", "EH", "EW", "lds_bytes", "w_off", "C")
     return dict(zip(keys, out))
+
+
+DETECTOR_SPEC_KEYS = ("op", "k", "stride", "cin", "cout", "bn", "leaky", "src0", "src1", "skip", "is_output", "cin0")
+
+
+def detector_spec(kind: int, anchors_per_scale: int = 3, num_classes: int = 1):
+    """The detector body's layer table as the engine builds it (pure host logic, no GPU): a list of dicts, one per convolution
+    or pool in the reference's layer-creation order (kind 0 = yolo_body, 1 = tiny_yolo_body)."""
+    lib = load()
+    count = C.c_int(0)
+    raise_for(lib.whenet_detector_spec(int(kind), int(anchors_per_scale), int(num_classes), 0, None, C.byref(count)),
+              f"whenet_detector_spec(kind={kind}, anchors_per_scale={anchors_per_scale}, num_classes={num_classes}): kind 0 / 1, both counts >= 1")
+    rows = []
+    out = (C.c_int32 * 12)()
+    for i in range(count.value):
+        raise_for(lib.whenet_detector_spec(int(kind), int(anchors_per_scale), int(num_classes), i, C.byref(out), None),
+                  "whenet_detector_spec: bad arguments")
+        rows.append(dict(zip(DETECTOR_SPEC_KEYS, (int(v) for v in out))))
+    return rows

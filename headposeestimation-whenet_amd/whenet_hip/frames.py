@@ -15,7 +15,10 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
   * a caller that also wants the DETECTOR's input from the GPU uses the resident form: `begin(frame)`
     uploads the frame once, `detector_input()` returns the `image_data` of YOLO.detect
     (yolo_postprocess.py:186-196: Pillow-BICUBIC letterbox and /255, `csrc/letterbox.hip`, bit-exact),
-    `heads(bboxes)` enqueues what `submit()` enqueues without copying the frame again.
+    `heads(bboxes)` enqueues what `submit()` enqueues without copying the frame again;
+  * with a detector attached to the model's handle (`whenet_hip.detector.YOLO(handle=model, ...)`), `detect()` between
+    `begin` and `heads` runs YOLO.detect itself on that device copy -- letterbox, Darknet body, box selection -- and
+    returns the boxes: a frame goes in, head boxes and head poses come out, with one library.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -50,6 +53,7 @@ class FramePipeline:
         self._depth = depth
         self._bgr = bool(bgr)
         self._pending: Deque[Tuple[int, np.ndarray]] = deque()
+        self._detector = None
         self._begun = None         # (ticket, frame_h, frame_w) of the frame begun last, until its heads are enqueued
 
     def __enter__(self):
@@ -99,6 +103,27 @@ class FramePipeline:
         check_model_image_size(size)
         u8, f32 = self._h.frame_letterbox(self._begun[0], size, want_u8=as_uint8, want_f32=not as_uint8)
         return u8 if as_uint8 else f32[None]
+
+    def detect(self, size=(416, 416), score=.3, iou=.45, max_boxes=20, anchors=None, num_classes=1):
+        """Resident form, step 2 with a detector loaded on the model's handle: YOLO.detect (yolo_postprocess.py:180-205) of
+        the frame begun last, on the device -> (boxes [k,4] y_min, x_min, y_max, x_max, scores [k], classes [k]).  `anchors`
+        and `num_classes` default to those of the `whenet_hip.detector.YOLO` that loaded the detector on this handle (or the
+        one given to `attach_detector`)."""
+        from .yolo import check_model_image_size
+        if self._begun is None:
+            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        check_model_image_size(size)
+        if anchors is None:
+            det = self._detector if self._detector is not None else getattr(self._h, "detector", None)
+            if det is None:
+                raise ValueError("detect: no whenet_hip.detector.YOLO was built on this model's handle: pass anchors= and num_classes=")
+            anchors, num_classes = det.anchors, len(det.class_names)
+        return self._h.frame_detect(self._begun[0], anchors, num_classes, size, score, iou, max_boxes)
+
+    def attach_detector(self, yolo) -> None:
+        """Use this `whenet_hip.detector.YOLO`'s anchors and class count in `detect()` (the default is the one built last with
+        `handle=model`)."""
+        self._detector = yolo
 
     def heads(self, bboxes) -> None:
         """Resident form, step 3: the detector's boxes of the frame begun last (an empty list is fine) -> margins,

@@ -7,8 +7,8 @@ Pillow-BICUBIC `letterbox_image` of yolo_v3/utils.py:23-34 and the float32 `/ 25
 reference builds TensorFlow graph ops from symbolic tensors and runs them in `sess.run`
 (yolo_postprocess.py:102-104, 198-204), here the arguments are the numpy output maps of the detector
 (`sess.run(yolo_model.output)`) and the result is numpy: boxes [k,4] (y_min, x_min, y_max, x_max), scores
-[k], classes [k] -- what `YOLO.detect` returns (yolo_postprocess.py:205).  The detector itself stays where
-it is (its weights are absent from the reference); there is no CPU fallback.
+[k], classes [k] -- what `YOLO.detect` returns (yolo_postprocess.py:205).  The detector network between the two runs on
+the device as well (whenet_hip/detector.py: `YOLO`, csrc/dconv.hip); there is no CPU fallback.
 """
 from __future__ import annotations
 

@@ -42,7 +42,7 @@ extern "C" {
  * (round 7, still 4 -- option act_layout.)
  * 5 (round 8): whenet_letterbox_plan, whenet_op_letterbox and the resident-frame form whenet_frame_begin / whenet_frame_letterbox /
  * whenet_frame_heads.  (Additions only: a version-4 caller runs unchanged.) */
-#define WHENET_ABI_VERSION 5
+#define WHENET_ABI_VERSION 6
 #define WHENET_API __attribute__((visibility("default")))
 
 /* return codes (negative errno-style) */
@@ -328,6 +328,45 @@ WHENET_API int whenet_yolo_eval(whenet_t* h, const float* const* feats, const in
                      float image_w, float score_threshold, float iou_threshold, int max_boxes, float* boxes,
                      float* scores, int32_t* classes, int32_t* index, int* count, float* all_boxes,
                      float* all_scores);
+
+/* ---- the detector's network on the device (ABI 6): yolo_body / tiny_yolo_body (yolo_v3/model.py:20-122) between the letterbox
+ * and whenet_yolo_eval, so that YOLO.detect (yolo_postprocess.py:180-205) needs no TensorFlow.  binary16 storage, f32 accumulation.
+ *   whenet_detector_load[_from_memory]  attaches a detector to ANY handle (a model handle or a whenet_create_postproc one); replaces
+ *                  tiny_yolo_body / yolo_body + load_weights (yolo_postprocess.py:66-79).  A WHNPACK1 container holding
+ *                  dconvNNN/kernel (Keras HWIO), dbnNNN/{gamma,beta,moving_mean,moving_variance} and, for the output convolutions,
+ *                  dconvNNN/bias, numbered from 000 in the reference's layer-creation order (convolutions and BatchNorms counted
+ *                  apart).  75 kernels = yolo_body, 13 = tiny_yolo_body; A * (5 + C) is the output convolutions' Cout.  A missing
+ *                  or mis-shaped tensor is WHENET_EFORMAT with its name in whenet_last_error.
+ *   whenet_detector_spec  pure host logic, no GPU: kind 0 = yolo_body, 1 = tiny_yolo_body; row `index` (0-based; convolutions and
+ *                  pools in creation order) as {op (0 conv, 1 max-pool), k, stride, cin, cout, bn, leaky, src0, src1, skip,
+ *                  is_output, cin_of_src0}.  src0 / src1 / skip are rows (-1: the image / none): with src1 >= 0 the input is
+ *                  Concatenate()([UpSampling2D(2)(src0), src1]); skip is the Add() operand; a stride-2 convolution pads top and left
+ *                  only.  *count = rows (75 / 19).  `out` may be NULL to ask for the count alone.
+ *   whenet_op_dconv / whenet_op_dpool  one layer on caller tensors (host pointers, float32 in / out, converted on the device like
+ *                  whenet_op_*): exactly the kernels the body runs.  in [n,H,W,cin] -- with in2 [n,H,W,cin2] it is the
+ *                  HALF-resolution tensor [n,H/2,W/2,cin]; kernel HWIO [k,k,cin+cin2,cout]; bias [cout] (a folded BatchNorm's);
+ *                  skip [n,Ho,Wo,cout] or NULL; f32_out selects the output convolutions' float32 store (else one rounding to
+ *                  binary16).  cin = 3 runs the body's first-layer input stage.  Pool: 2x2 'same', stride 1 or 2.
+ *   whenet_detector_forward  the body alone = yolo_model.predict(image_data): image float32 [n,H,W,3] (H, W multiples of 32 in
+ *                  32..1024, n 1..16) -> maps[l] float32 [n][H/32 << l][W/32 << l][A*(5+C)], coarsest first (3 maps, tiny 2)
+ *   whenet_op_detect  YOLO.detect on a host frame: letterbox -> body -> yolo_eval without leaving the device; outputs as
+ *                  whenet_yolo_eval's (boxes [C*max_boxes][4], scores, classes; image shape = the frame's)
+ *   whenet_frame_detect  the same on a resident frame, between whenet_frame_begin and whenet_frame_heads
+ * A handle without a loaded detector answers forward / detect with WHENET_EINVAL and stays usable. */
+WHENET_API int whenet_detector_load(whenet_t* h, const char* snapshot_path);
+WHENET_API int whenet_detector_load_from_memory(whenet_t* h, const void* snapshot, size_t nbytes);
+WHENET_API int whenet_detector_spec(int kind, int anchors_per_scale, int num_classes, int index, int32_t out[12], int* count);
+WHENET_API int whenet_op_dconv(whenet_t* h, const float* in, int n, int H, int W, int cin, const float* in2, int cin2,
+                    const float* kernel, const float* bias, int k, int stride, int cout, int leaky, const float* skip,
+                    int f32_out, float* out);
+WHENET_API int whenet_op_dpool(whenet_t* h, const float* in, int n, int H, int W, int c, int stride, float* out);
+WHENET_API int whenet_detector_forward(whenet_t* h, const float* image, int n, int H, int W, float* const* maps);
+WHENET_API int whenet_op_detect(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, int out_h, int out_w,
+                     const float* anchors, int num_anchors, float score_threshold, float iou_threshold, int max_boxes,
+                     float* boxes, float* scores, int32_t* classes, int* count);
+WHENET_API int whenet_frame_detect(whenet_t* h, int ticket, int out_h, int out_w, const float* anchors, int num_anchors,
+                        float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
+                        int32_t* classes, int* count);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
