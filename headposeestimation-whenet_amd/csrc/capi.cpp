@@ -671,6 +671,44 @@ int whenet_frame_detect(whenet_t* h, int ticket, int out_h, int out_w, const flo
     });
 }
 
+int whenet_frame_detect_heads(whenet_t* h, int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold,
+                              float iou_threshold, int max_boxes) {
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        h->at(size_t(idx)).frame_detect_heads(ticket / MAX_INFLIGHT_ENGINES, out_h, out_w, anchors, num_anchors, score_threshold,
+                                              iou_threshold, max_boxes);
+    });
+}
+
+int whenet_collect_detect(whenet_t* h, int ticket, int capacity, int* count, float* boxes, float* scores, int32_t* classes, int32_t* rects,
+                          int32_t* valid, float* ypr, int32_t* argmax, float* logits) {
+    if (count == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        *count = h->at(size_t(idx)).collect_detect(ticket / MAX_INFLIGHT_ENGINES, capacity, boxes, scores, classes, rects, valid, ypr, argmax,
+                                                   logits);
+    });
+}
+
+int whenet_op_head_plan(whenet_t* h, int frame_h, int frame_w, const float* boxes, int k, int32_t* rects, int32_t* valid, int32_t* plans) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_head_plan(frame_h, frame_w, boxes, k, rects, valid, plans); });
+}
+
+static_assert(WHENET_CROP_PLAN_INTS == whenet::CROP_PLAN_INTS, "whenet_hip.h and kernels.h disagree on the crop plan size");
+int whenet_crop_plan(const int32_t rect[4], int32_t* plan) {
+    if (rect == nullptr || plan == nullptr) return WHENET_EINVAL;
+    try {
+        whenet::build_crop_plan(rect, plan);
+        return WHENET_OK;
+    } catch (const whenet::Error& e) {
+        return e.code;
+    } catch (...) {
+        return WHENET_ENOMEM;
+    }
+}
+
 int whenet_collect(whenet_t* h, int ticket, float* ypr, int32_t* argmax, float* logits) {
     return guarded(h, [&](whenet::Engine&) {
         const int idx = ticket % MAX_INFLIGHT_ENGINES;

@@ -418,6 +418,62 @@ int Engine::frame_detect(int ticket, int out_h, int out_w, const float* anchors,
                          iou_threshold, max_boxes, boxes, scores, classes);
 }
 
+// begin -> detect_heads -> collect: what frame_detect + frame_heads do in two steps with the host in between, as ONE enqueue-only
+// submission.  The boxes yolo.hip selected stay in yolo_scratch_; headplan.hip turns them into the detections, their windows and
+// their crop plans in the slot's buffers; the crop kernel and the forward run over the CAPACITY K = classes x max_boxes (rows
+// without a head are zero crops: a crop's result is bitwise independent of the batch and of its position, so head i equals
+// the two-step path's); everything comes back with the copies enqueued here.  The letterbox scratch, the plan's activations
+// and yolo_scratch_ are one per engine: the next frame's launches are behind this frame's on stream_.  Buffers are allocated
+// and graphs captured on the first call for a shape; after that nothing here waits for the device.
+void Engine::frame_detect_heads(int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold,
+                                float iou_threshold, int max_boxes) {
+    DeviceGuard guard(device_);
+    require_model();
+    require_detector();
+    Slot& slot = resident_slot(ticket, "frame_detect_heads");
+    (void)letterbox_plan_layout(slot.fh, slot.fw, out_h, out_w);
+    check_detector_input(1, out_h, out_w);
+    WHENET_REQUIRE(det_->out_filters % 3 == 0 && det_->out_filters / 3 > 5, WHENET_EINVAL,
+                   "detect: the loaded detector's outputs are not 3 anchors x (5 + classes) wide");
+    WHENET_REQUIRE(anchors != nullptr, WHENET_EINVAL, "detect: NULL argument");
+    const int num_classes = det_->out_filters / 3 - 5;
+    WHENET_REQUIRE(max_boxes >= 1 && max_boxes <= 64 && num_classes * max_boxes <= 64, WHENET_EINVAL,
+                   "frame_detect_heads: classes x max_boxes = " + std::to_string(num_classes) + " x " + std::to_string(max_boxes) +
+                       " must be 1..64 (every slot is a crop of the forward)");
+    const int cap = num_classes * max_boxes;              // (allocations first: nothing is enqueued yet if one of them fails)
+    ensure_capacity(cap);
+    ensure_slot(slot, cap);
+    ensure_slot_frame(slot, size_t(slot.fh) * slot.fw * 3, cap);
+    slot.det.h.grow(DetRows(cap).bytes());
+    slot.det.d.grow(DetRows(cap).bytes());
+    DetPlan& p = detector_plan(1, out_h, out_w);
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+    const uint8_t* d_canvas = enqueue_letterbox(slot.frame.d.as<uint8_t>(), slot.fh, slot.fw, slot.swap_rb, out_h, out_w, true, false).first;
+    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img16.as<half_t>(), size_t(out_h) * out_w, stream_);
+    WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
+    const float* feats[3] = {p.maps[0].as<float>(), p.maps[1].as<float>(), p.maps[2].as<float>()};
+    const YoloArgs y = enqueue_yolo_eval(feats, true, p.gh, p.gw, det_->num_maps, anchors, num_anchors, num_classes, float(slot.fh),
+                                         float(slot.fw), score_threshold, iou_threshold, max_boxes, false);
+    const int K = num_classes * y.max_boxes;              // (max_boxes is cut to the number of boxes the maps hold)
+    const DetRows rows(K);
+    void* const d_rows = slot.det.d.as<void>();
+    HeadPlanArgs a{};
+    a.in_boxes = y.out_boxes, a.in_scores = y.out_scores, a.in_count = y.out_count;
+    a.num_classes = num_classes, a.max_boxes = y.max_boxes, a.frame_h = slot.fh, a.frame_w = slot.fw;
+    a.boxes = rows.boxes(d_rows), a.scores = rows.scores(d_rows), a.classes = rows.classes(d_rows), a.count = rows.count(d_rows);
+    a.rects = rows.rects(d_rows), a.valid = rows.valid(d_rows), a.plans = slot.plan.d.as<int32_t>();
+    launch_head_plan(a, stream_);
+    launch_crop_resize_masked(slot.frame.d.as<uint8_t>(), slot.fw, slot.swap_rb, a.plans, K, a.valid, a.count, slot.in.d.as<uint8_t>(),
+                              stream_);
+    run_forward(slot.in.d.as<uint8_t>(), K, slot.dev(), stream_);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.det.h.as<void>(), d_rows, rows.bytes(), hipMemcpyDeviceToHost, stream_));
+    copy_results_async(slot.host(), slot.dev(), K, stream_);
+    WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));
+    slot.n = K;
+    slot.det_cap = K;
+    slot.frame_ticket = -1;
+}
+
 // ------------------------------------------------------------------------------------------
 // single layers on caller tensors (float32 in / out, converted on the device): exactly the kernels the body runs
 // ------------------------------------------------------------------------------------------

@@ -218,6 +218,10 @@ class Engine {
     void op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, const int32_t* rects, int k,
                         uint8_t* crops_out);
     void collect(int ticket, float* ypr, int32_t* argmax, float* logits);
+    // a frame_detect_heads ticket: one wait, then the detections (count rows of each array) and their heads' results; the rows of
+    // heads without a window inside the frame are NaN / -1 / NaN.  Returns the number of detections.
+    int collect_detect(int ticket, int capacity, float* boxes, float* scores, int32_t* classes, int32_t* rects, int32_t* valid, float* ypr,
+                       int32_t* argmax, float* logits);
     // the detector's letterbox (letterbox.hip) alone on a host frame, and the resident-frame form of submit_frame: the frame is
     // uploaded when it arrives (the ticket is handed out and the slot held from then on), the detector input and the head crops
     // are both cut from that one device copy; collect() returns the heads' results and frees the slot
@@ -246,6 +250,12 @@ class Engine {
                   float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes);
     int frame_detect(int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold, float iou_threshold,
                      int max_boxes, float* boxes, float* scores, int32_t* classes);
+    // ONE enqueue-only submission per resident frame: letterbox -> body -> yolo_eval -> head plans (headplan.hip) -> crops over the
+    // capacity C * max_boxes -> forward -> D2H of detections and results; nothing waits and nothing returns to the host in between
+    void frame_detect_heads(int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold,
+                            float iou_threshold, int max_boxes);
+    // the plan kernel alone on caller boxes (host pointers): rects [k,4], valid [k], plans [k][CROP_PLAN_INTS] (may be nullptr)
+    void op_head_plan(int fh, int fw, const float* boxes, int k, int32_t* rects, int32_t* valid, int32_t* plans);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
                   int stride, int cout, int leaky, const float* skip, int f32_out, float* out);
     void op_dpool(const float* in, int n, int H, int W, int c, int stride, float* out);
@@ -266,6 +276,8 @@ class Engine {
         StagedBuffer frame, plan;        // frame submissions: the frame and the crop plans travel instead of the crops
         int frame_ticket = -1;           // resident frame: the ticket whose frame is held here and still waits for its heads
         int fh = 0, fw = 0, swap_rb = 0; //   (tickets are never reused, so a stale value matches nothing)
+        StagedBuffer det;                // frame_detect_heads: count | boxes | scores | classes | rects | valid over det_cap rows
+        int det_cap = -1;                //   (DetRows); >= 0 marks a submission that collect_detect, not collect, returns
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -357,6 +369,11 @@ class Engine {
     // run_letterbox's launches alone: the device canvas (uint8, float32) of those asked for, valid until the next letterbox
     std::pair<uint8_t*, float*> enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, bool want_u8,
                                                   bool want_f32);
+    // the argument set-up of yolo_eval (scratch carved and grown, host maps uploaded) and its launches on stream_; no wait, no copy
+    // back: the selected boxes stay in yolo_scratch_ (out_boxes / out_scores / out_count of the returned arguments)
+    YoloArgs enqueue_yolo_eval(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
+                               const float* anchors, int num_anchors, int num_classes, float image_h, float image_w, float score_threshold,
+                               float iou_threshold, int max_boxes, bool want_all_scores);
     // yolo_eval on maps that are in host memory (uploaded first) or already on the device
     int yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
                        int num_anchors, int num_classes, float image_h, float image_w, float score_threshold, float iou_threshold,

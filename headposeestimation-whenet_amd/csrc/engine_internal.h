@@ -56,6 +56,20 @@ inline void copy_results_host(const Results& dst, const Results& src, int n) {
     if (dst.logits) std::memcpy(dst.logits, src.logits, N * N_LOGITS * sizeof(float));
 }
 
+// The detection block of a frame_detect_heads slot over a capacity of K rows, one allocation so that ONE copy brings it back:
+// count (int32, padded to 16 bytes) | boxes [K][4] f32 | scores [K] f32 | classes [K] i32 | rects [K][4] i32 | valid [K] i32
+struct DetRows {
+    size_t K;
+    explicit DetRows(int k) : K(size_t(k)) {}
+    size_t bytes() const { return 16 + K * 44; }
+    int32_t* count(void* base) const { return static_cast<int32_t*>(base); }
+    float* boxes(void* base) const { return reinterpret_cast<float*>(static_cast<char*>(base) + 16); }
+    float* scores(void* base) const { return boxes(base) + K * 4; }
+    int32_t* classes(void* base) const { return reinterpret_cast<int32_t*>(scores(base) + K); }
+    int32_t* rects(void* base) const { return classes(base) + K; }
+    int32_t* valid(void* base) const { return rects(base) + K * 4; }
+};
+
 inline void copy_name(char* dst, size_t cap, const std::string& s) {
     std::memset(dst, 0, cap);
     std::memcpy(dst, s.data(), std::min(cap - 1, s.size()));

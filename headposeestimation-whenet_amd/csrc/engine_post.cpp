@@ -1,5 +1,7 @@
 // Frame-level entry points around the hot path: one submission per video frame (crop + resize +
 // colour order on the device, then the forward), the crop/resize stage alone, and the YOLOv3 detector's post-processing.
+#include <limits>
+
 #include "engine_internal.h"
 
 namespace whenet {
@@ -76,11 +78,14 @@ void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, c
 }
 
 // The detector's pre-processing (yolo_v3/utils.py:23-34 + yolo_postprocess.py:191-195) of a frame that is on the device.
-// The stream is idle on the letterbox scratch whenever this is entered: every call waits for its own results.
+// The scratch is one per engine and safe because everything that touches it runs in order on stream_.  The callers that wait for
+// their own results leave the stream idle; frame_detect_heads does not, so the one host-side hazard -- re-staging the tables
+// through their single pinned buffer while an earlier copy out of it may still be queued -- waits for the stream, on that branch only.
 std::pair<uint8_t*, float*> Engine::enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w,
                                                       bool want_u8, bool want_f32) {
     if (!(lb_plan_valid_ && lb_plan_.ih == fh && lb_plan_.iw == fw && lb_plan_.oh == out_h && lb_plan_.ow == out_w)) {
         lb_plan_valid_ = false;
+        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         const LetterboxPlan p = build_letterbox_plan(fh, fw, out_h, out_w, &lb_tables_host_);
         const size_t tbytes = lb_tables_host_.size() * sizeof(int32_t);
         lb_tables_.h.grow(tbytes);
@@ -208,12 +213,10 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
 }
 
 // on_device: the maps are where the detector body left them (detector.cpp); nothing is uploaded
-int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
-                           const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
-                           float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
-                           int32_t* classes, int32_t* index, float* all_boxes, float* all_scores) {
-    WHENET_REQUIRE(feats && grid_h && grid_w && anchors && boxes && scores && classes, WHENET_EINVAL,
-                   "yolo_eval: NULL argument");
+YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
+                                   const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
+                                   float score_threshold, float iou_threshold, int max_boxes, bool want_all_scores) {
+    WHENET_REQUIRE(feats && grid_h && grid_w && anchors, WHENET_EINVAL, "yolo_eval: NULL argument");
     WHENET_REQUIRE((num_layers == 3 && num_anchors == 9) || (num_layers == 2 && num_anchors == 6), WHENET_EINVAL,
                    "yolo_eval: 3 maps with 9 anchors or 2 maps with 6 (model.py:203)");
     WHENET_REQUIRE(num_classes >= 1 && num_classes <= 1024 && image_h > 0 && image_w > 0, WHENET_EINVAL,
@@ -277,7 +280,7 @@ int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int*
     a.max_boxes = max_boxes;
     const size_t C = size_t(num_classes), MB = size_t(max_boxes);
     const size_t o_boxes = cv.add(size_t(N) * 4 * sizeof(float));
-    const size_t o_all = all_scores ? cv.add(size_t(N) * C * sizeof(float)) : 0;
+    const size_t o_all = want_all_scores ? cv.add(size_t(N) * C * sizeof(float)) : 0;
     const size_t o_counts = cv.add(C * sizeof(int));
     const size_t o_keys = cv.add(C * size_t(a.NP) * sizeof(unsigned long long));
     const size_t o_ob = cv.add(C * MB * 4 * sizeof(float));
@@ -299,7 +302,7 @@ int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int*
         a.layer[l].feats = d;
     }
     a.boxes = reinterpret_cast<float*>(base + o_boxes);
-    a.all_scores = all_scores ? reinterpret_cast<float*>(base + o_all) : nullptr;
+    a.all_scores = want_all_scores ? reinterpret_cast<float*>(base + o_all) : nullptr;
     a.counts = reinterpret_cast<int*>(base + o_counts);
     a.keys = reinterpret_cast<unsigned long long*>(base + o_keys);
     a.out_boxes = reinterpret_cast<float*>(base + o_ob);
@@ -307,6 +310,18 @@ int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int*
     a.out_index = reinterpret_cast<int*>(base + o_oi);
     a.out_count = reinterpret_cast<int*>(base + o_oc);
     launch_yolo_eval(a, stream_);
+    return a;
+}
+
+int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
+                           const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
+                           float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
+                           int32_t* classes, int32_t* index, float* all_boxes, float* all_scores) {
+    WHENET_REQUIRE(boxes && scores && classes, WHENET_EINVAL, "yolo_eval: NULL argument");
+    const YoloArgs a = enqueue_yolo_eval(feats, on_device, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_h, image_w,
+                                         score_threshold, iou_threshold, max_boxes, all_scores != nullptr);
+    const int N = a.N;
+    const size_t C = size_t(num_classes), MB = size_t(a.max_boxes);
     // The per-class counts first, then ONLY the selected rows, straight into the caller's arrays (model.py:227-229:
     // concatenated class by class).  Round 3 copied all C x max_boxes slots into temporaries: ~20 MB per frame for 80
     // classes x 10,647 boxes where the reference returns a handful of detections.
@@ -331,6 +346,68 @@ int Engine::yolo_eval_maps(const float* const* feats, bool on_device, const int*
     }
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     return out;
+}
+
+// What frame_detect_heads (detector.cpp) enqueued: one wait, then the detections and the results of their heads.
+int Engine::collect_detect(int ticket, int capacity, float* boxes, float* scores, int32_t* classes, int32_t* rects, int32_t* valid,
+                           float* ypr, int32_t* argmax, float* logits) {
+    DeviceGuard guard(device_);
+    Slot* slot = nullptr;
+    for (Slot& s : slots_)
+        if (s.busy && s.ticket == ticket) slot = &s;
+    WHENET_REQUIRE(slot != nullptr, WHENET_EINVAL, "unknown or already collected ticket " + std::to_string(ticket));
+    WHENET_REQUIRE(slot->det_cap >= 0, WHENET_EINVAL,
+                   "collect_detect: ticket " + std::to_string(ticket) + " was not submitted by frame_detect_heads");
+    WHENET_REQUIRE(boxes && scores && classes && rects && valid && ypr, WHENET_EINVAL, "collect_detect: NULL argument");
+    WHENET_REQUIRE(capacity >= slot->det_cap, WHENET_EINVAL,
+                   "collect_detect: capacity " + std::to_string(capacity) + " is below the submission's " + std::to_string(slot->det_cap) +
+                       " rows (classes x max_boxes)");
+    WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
+    const DetRows rows(slot->det_cap);
+    void* const base = slot->det.h.as<void>();
+    const int count = std::max(0, std::min(*rows.count(base), slot->det_cap));
+    const size_t n = size_t(count);
+    std::memcpy(boxes, rows.boxes(base), n * 4 * sizeof(float));
+    std::memcpy(scores, rows.scores(base), n * sizeof(float));
+    std::memcpy(classes, rows.classes(base), n * sizeof(int32_t));
+    std::memcpy(rects, rows.rects(base), n * 4 * sizeof(int32_t));
+    std::memcpy(valid, rows.valid(base), n * sizeof(int32_t));
+    copy_results_host(Results{ypr, argmax, logits}, slot->host(), count);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (size_t i = 0; i < n; ++i) {
+        if (valid[i]) continue;
+        std::fill(ypr + i * 3, ypr + i * 3 + 3, nan);
+        if (argmax) std::fill(argmax + i * 3, argmax + i * 3 + 3, -1);
+        if (logits) std::fill(logits + i * N_LOGITS, logits + (i + 1) * N_LOGITS, nan);
+    }
+    slot->busy = false;
+    slot->det_cap = -1;
+    return count;
+}
+
+void Engine::op_head_plan(int fh, int fw, const float* boxes, int k, int32_t* rects, int32_t* valid, int32_t* plans) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(boxes != nullptr && rects != nullptr && valid != nullptr && fh > 0 && fw > 0 && k >= 1 && k <= 2048, WHENET_EINVAL,
+                   "op_head_plan: NULL argument, an empty frame, or k outside 1..2048");
+    const DetRows rows(k);
+    const size_t in_bytes = size_t(k) * 4 * sizeof(float), plan_bytes = size_t(k) * CROP_PLAN_INTS * sizeof(int32_t);
+    TempBufs tmp;
+    float* const d_in = static_cast<float*>(tmp.get(in_bytes));
+    int* const d_k = static_cast<int*>(tmp.get(sizeof(int)));
+    void* const d_rows = tmp.get(rows.bytes());
+    int32_t* const d_plans = plans ? static_cast<int32_t*>(tmp.get(plan_bytes)) : nullptr;
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_in, boxes, in_bytes, hipMemcpyHostToDevice, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_k, &k, sizeof(int), hipMemcpyHostToDevice, stream_));
+    HeadPlanArgs a{};
+    a.in_boxes = d_in, a.in_scores = nullptr, a.in_count = d_k;
+    a.num_classes = 1, a.max_boxes = k, a.frame_h = fh, a.frame_w = fw;
+    a.boxes = rows.boxes(d_rows), a.scores = rows.scores(d_rows), a.classes = rows.classes(d_rows), a.count = rows.count(d_rows);
+    a.rects = rows.rects(d_rows), a.valid = rows.valid(d_rows), a.plans = d_plans;
+    launch_head_plan(a, stream_);
+    WHENET_HIP_CHECK(hipMemcpyAsync(rects, a.rects, size_t(k) * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(valid, a.valid, size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    if (plans) WHENET_HIP_CHECK(hipMemcpyAsync(plans, d_plans, plan_bytes, hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 }  // namespace whenet

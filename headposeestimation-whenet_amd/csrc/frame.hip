@@ -12,7 +12,8 @@
 // ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2; an exact 2x shrink is switched
 // to INTER_AREA (2x2 box mean).  The tables are integer data computed on the HOST with the same
 // float/double operations as OpenCV (build_crop_plan), so the kernel is pure integer arithmetic
-// and the result is bit-exact with the restatement in oracle/preprocess_oracle.py.
+// and the result is bit-exact with the restatement in oracle/preprocess_oracle.py.  (headplan.hip computes the same windows and
+// tables on the device, bit for bit, for the frames whose detections never leave it; the masked kernel below crops those.)
 #include <cmath>
 
 #include "kernels.h"
@@ -24,11 +25,9 @@ namespace {
 constexpr int OUT = IMG;                    // 224
 constexpr int COEF_SCALE = 1 << 11;         // INTER_RESIZE_COEF_SCALE
 
-__global__ __launch_bounds__(256) void whenet_crop_resize_kernel(const uint8_t* __restrict__ frame, int fw,
-                                                                 int swap_rb, const int32_t* __restrict__ plan,
-                                                                 uint8_t* __restrict__ out) {
-    const int dy = blockIdx.x, crop = blockIdx.y, dx = threadIdx.x;
-    if (dx >= OUT) return;
+// output pixel (dy, dx) of one crop
+__device__ __forceinline__ void crop_resize_pixel(const uint8_t* __restrict__ frame, int fw, int swap_rb,
+                                                  const int32_t* __restrict__ plan, uint8_t* __restrict__ out, int crop, int dy, int dx) {
     const int32_t* P = plan + size_t(crop) * CROP_PLAN_INTS;
     const int y0 = P[0], x0 = P[1], ch = P[2], cw = P[3], area2x = P[4], xmax = P[5];
     const int32_t* T = P + 8;               // xofs | a0 | a1 | yofs | b0 | b1, 224 ints each
@@ -60,6 +59,30 @@ __global__ __launch_bounds__(256) void whenet_crop_resize_kernel(const uint8_t* 
         o[c] = uint8_t(v);
     }
     (void)cw;
+}
+
+__global__ __launch_bounds__(256) void whenet_crop_resize_kernel(const uint8_t* __restrict__ frame, int fw,
+                                                                 int swap_rb, const int32_t* __restrict__ plan,
+                                                                 uint8_t* __restrict__ out) {
+    const int dy = blockIdx.x, crop = blockIdx.y, dx = threadIdx.x;
+    if (dx >= OUT) return;
+    crop_resize_pixel(frame, fw, swap_rb, plan, out, crop, dy, dx);
+}
+
+// the head count and the valid flags are on the device (headplan.hip): rows without a head are zero-filled, never read from
+__global__ __launch_bounds__(256) void whenet_crop_resize_masked_kernel(const uint8_t* __restrict__ frame, int fw, int swap_rb,
+                                                                        const int32_t* __restrict__ plan,
+                                                                        const int32_t* __restrict__ valid,
+                                                                        const int32_t* __restrict__ count,
+                                                                        uint8_t* __restrict__ out) {
+    const int dy = blockIdx.x, crop = blockIdx.y, dx = threadIdx.x;
+    if (dx >= OUT) return;
+    if (crop >= *count || valid[crop] == 0) {
+        uint8_t* o = out + ((size_t(crop) * OUT + dy) * OUT + dx) * 3;
+        o[0] = 0, o[1] = 0, o[2] = 0;
+        return;
+    }
+    crop_resize_pixel(frame, fw, swap_rb, plan, out, crop, dy, dx);
 }
 
 // saturate_cast<short>(float): cvRound (round half to even, the default FP rounding mode) + saturation
@@ -140,6 +163,14 @@ void launch_crop_resize(const uint8_t* d_frame, int fw, int swap_rb, const int32
     if (k <= 0) return;
     hipLaunchKernelGGL(whenet_crop_resize_kernel, dim3(OUT, k), dim3(256), 0, stream, d_frame, fw, swap_rb, d_plan,
                        d_out);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+void launch_crop_resize_masked(const uint8_t* d_frame, int fw, int swap_rb, const int32_t* d_plan, int k, const int32_t* d_valid,
+                               const int32_t* d_count, uint8_t* d_out, hipStream_t stream) {
+    if (k <= 0) return;
+    hipLaunchKernelGGL(whenet_crop_resize_masked_kernel, dim3(OUT, k), dim3(256), 0, stream, d_frame, fw, swap_rb, d_plan, d_valid,
+                       d_count, d_out);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

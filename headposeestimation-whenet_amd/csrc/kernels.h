@@ -403,6 +403,31 @@ void frame_box_rect(int frame_h, int frame_w, const float bbox[4], int32_t rect[
 void build_crop_plan(const int32_t rect[4], int32_t* plan);
 void launch_crop_resize(const uint8_t* d_frame, int fw, int swap_rb, const int32_t* d_plan, int k, uint8_t* d_out,
                         hipStream_t stream);
+// The same over a CAPACITY of k rows whose head count is on the device: row i is cropped iff i < *d_count and d_valid[i] != 0
+// (headplan.hip writes both); every other row is filled with zero bytes.  Valid rows: the arithmetic above, unchanged.
+void launch_crop_resize_masked(const uint8_t* d_frame, int fw, int swap_rb, const int32_t* d_plan, int k, const int32_t* d_valid,
+                               const int32_t* d_count, uint8_t* d_out, hipStream_t stream);
+
+// ---- headplan.hip -----------------------------------------------------------------------
+// The detector's selected boxes (yolo.hip's out_boxes / out_scores / out_count, left where launch_yolo_eval wrote them) ->
+// the detections concatenated class by class, their crop windows (frame_box_rect), which of them have a window inside the
+// frame (check_rects of engine_post.cpp) and the crop plan of each (build_crop_plan), bit for bit the host's.
+struct HeadPlanArgs {
+    const float* in_boxes;     // [C][max_boxes][4]
+    const float* in_scores;    // [C][max_boxes] or nullptr (scores come out as 0)
+    const int* in_count;       // [C]
+    int num_classes, max_boxes;
+    int frame_h, frame_w;
+    // outputs over the capacity K = C * max_boxes; rows from *count on: zeros, class -1, valid 0
+    float* boxes;              // [K][4]
+    float* scores;             // [K]
+    int32_t* classes;          // [K]
+    int32_t* count;            // [1]
+    int32_t* rects;            // [K][4] (y0, x0, y1, x1)
+    int32_t* valid;            // [K]
+    int32_t* plans;            // [K][CROP_PLAN_INTS] or nullptr; zeros where valid is 0
+};
+void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream);
 
 // ---- letterbox.hip ----------------------------------------------------------------------
 // The detector's pre-processing (yolo_v3/utils.py:23-34, yolo_postprocess.py:186-196): Pillow-exact BICUBIC resize at

@@ -72,6 +72,10 @@ _PROTOS = {
                                    _P, _P, _P, C.POINTER(C.c_int)]),
     "whenet_frame_detect": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P, _P,
                                       C.POINTER(C.c_int)]),
+    "whenet_frame_detect_heads": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "whenet_collect_detect": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "whenet_op_head_plan": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "whenet_crop_plan": (C.c_int, [_P, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -145,6 +149,19 @@ def frame_rects(frame_h: int, frame_w: int, bboxes) -> np.ndarray:
     out = np.empty((b.shape[0], 4), np.int32)
     code = load().whenet_frame_rects(int(frame_h), int(frame_w), _ptr(b), b.shape[0], _ptr(out))
     raise_for(code, "whenet_frame_rects: bad arguments")
+    return out
+
+
+CROP_PLAN_INTS = 8 + 6 * 224      # WHENET_CROP_PLAN_INTS
+
+
+def crop_plan(rect) -> np.ndarray:
+    """The crop plan of one window (y0, x0, y1, x1) as the library computes it for `frame_heads`: int32 [CROP_PLAN_INTS] =
+    {y0, x0, h, w, 2x-shrink flag, xmax, 0, 0} + xofs | a0 | a1 | yofs | b0 | b1 (224 each).  Pure host arithmetic inside the
+    library (no GPU needed); an empty window raises ValueError."""
+    r = np.ascontiguousarray(rect, np.int32).reshape(4)
+    out = np.empty(CROP_PLAN_INTS, np.int32)
+    raise_for(load().whenet_crop_plan(_ptr(r), _ptr(out)), f"whenet_crop_plan: empty crop window {r.tolist()}")
     return out
 
 
@@ -444,6 +461,39 @@ class Handle:
                                                   C.byref(count)))
         k = count.value
         return boxes[:k].copy(), scores[:k].copy(), classes[:k].copy()
+
+    def frame_detect_heads(self, ticket: int, anchors, num_classes: int, size=(416, 416), score: float = .3, iou: float = .45,
+                           max_boxes: int = 20) -> int:
+        """frame_detect + frame_heads of the resident frame of `ticket` as ONE enqueue-only submission: returns at once with the
+        capacity (rows) that `collect_detect` needs."""
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 2)
+        self._check(self._lib.whenet_frame_detect_heads(self._h, int(ticket), int(size[0]), int(size[1]), _ptr(anchors), anchors.shape[0],
+                                                        float(score), float(iou), int(max_boxes)))
+        return int(num_classes) * int(max_boxes)
+
+    def collect_detect(self, ticket: int, capacity: int, want_logits: bool = False):
+        """A `frame_detect_heads` ticket -> (boxes [k,4], scores [k], classes [k], rects [k,4], valid [k], ypr [k,3], argmax [k,3],
+        logits [k,252] or None) over all k detections; rows of heads without a window inside the frame: valid 0, NaN / -1 / NaN."""
+        cap = int(capacity)
+        boxes, scores, classes = np.empty((cap, 4), np.float32), np.empty(cap, np.float32), np.empty(cap, np.int32)
+        rects, valid = np.empty((cap, 4), np.int32), np.empty(cap, np.int32)
+        ypr, am = np.empty((cap, 3), np.float32), np.empty((cap, 3), np.int32)
+        lg = np.empty((cap, 252), np.float32) if want_logits else None
+        count = C.c_int(0)
+        self._check(self._lib.whenet_collect_detect(self._h, int(ticket), cap, C.byref(count), _ptr(boxes), _ptr(scores), _ptr(classes),
+                                                    _ptr(rects), _ptr(valid), _ptr(ypr), _ptr(am), _ptr(lg)))
+        k = count.value
+        return tuple(None if a is None else a[:k].copy() for a in (boxes, scores, classes, rects, valid, ypr, am, lg))
+
+    def op_head_plan(self, frame_h: int, frame_w: int, boxes, want_plans: bool = True):
+        """The window / crop plan kernel alone on caller boxes [k,4] (y_min, x_min, y_max, x_max), 1 <= k <= 2048:
+        (rects int32 [k,4], valid int32 [k], plans int32 [k, CROP_PLAN_INTS] or None)."""
+        b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
+        k = b.shape[0]
+        rects, valid = np.empty((k, 4), np.int32), np.empty(k, np.int32)
+        plans = np.empty((k, CROP_PLAN_INTS), np.int32) if want_plans else None
+        self._check(self._lib.whenet_op_head_plan(self._h, int(frame_h), int(frame_w), _ptr(b), k, _ptr(rects), _ptr(valid), _ptr(plans)))
+        return rects, valid, plans
 
     def op_dconv(self, x: np.ndarray, kernel: np.ndarray, bias: np.ndarray, stride: int = 1, leaky: bool = True, x2=None, skip=None,
                  f32_out: bool = False) -> np.ndarray:

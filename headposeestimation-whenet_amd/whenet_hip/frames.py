@@ -18,7 +18,10 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     `heads(bboxes)` enqueues what `submit()` enqueues without copying the frame again;
   * with a detector attached to the model's handle (`whenet_hip.detector.YOLO(handle=model, ...)`), `detect()` between
     `begin` and `heads` runs YOLO.detect itself on that device copy -- letterbox, Darknet body, box selection -- and
-    returns the boxes: a frame goes in, head boxes and head poses come out, with one library.
+    returns the boxes: a frame goes in, head boxes and head poses come out, with one library;
+  * `detect_heads()` takes the place of `detect()` + `heads()`: the boxes stay on the device, a kernel turns them into windows and
+    crop plans (`csrc/headplan.hip`), and the call returns as soon as everything is enqueued -- `begin; detect_heads; collect`
+    is one submission per frame, so with `depth` > 1 the next frame is begun and detected while this one is on the GPU.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -52,7 +55,7 @@ class FramePipeline:
         self._h.set_option("inflight", min(depth, 4))
         self._depth = depth
         self._bgr = bool(bgr)
-        self._pending: Deque[Tuple[int, np.ndarray]] = deque()
+        self._pending: Deque[Tuple[int, object, int]] = deque()      # (ticket, rects, 0) or, from detect_heads, (ticket, None, capacity)
         self._detector = None
         self._begun = None         # (ticket, frame_h, frame_w) of the frame begun last, until its heads are enqueued
 
@@ -79,7 +82,7 @@ class FramePipeline:
             raise ValueError(f"frame must be uint8 [H,W,3], got {frame.dtype} {frame.shape}")
         rects = _lib.frame_rects(frame.shape[0], frame.shape[1], bboxes)
         ticket = self._h.submit_frame(frame, rects, bgr=self._bgr)
-        self._pending.append((ticket, rects))
+        self._pending.append((ticket, rects, 0))
 
     def begin(self, frame: np.ndarray) -> None:
         """Resident form, step 1: upload the frame (it crosses PCIe once).  The frame holds one of the `depth`
@@ -113,12 +116,31 @@ class FramePipeline:
         if self._begun is None:
             raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
         check_model_image_size(size)
+        anchors, num_classes = self._anchors(anchors, num_classes)
+        return self._h.frame_detect(self._begun[0], anchors, num_classes, size, score, iou, max_boxes)
+
+    def _anchors(self, anchors, num_classes):
         if anchors is None:
             det = self._detector if self._detector is not None else getattr(self._h, "detector", None)
             if det is None:
                 raise ValueError("detect: no whenet_hip.detector.YOLO was built on this model's handle: pass anchors= and num_classes=")
             anchors, num_classes = det.anchors, len(det.class_names)
-        return self._h.frame_detect(self._begun[0], anchors, num_classes, size, score, iou, max_boxes)
+        return anchors, num_classes
+
+    def detect_heads(self, size=(416, 416), score=.3, iou=.45, max_boxes=20, anchors=None, num_classes=1) -> None:
+        """Resident form, steps 2 and 3 as ONE submission: `detect()` and `heads()` of the frame begun last without the host in
+        between.  Returns as soon as the work is enqueued; `collect()` returns the heads that have a window inside the frame,
+        `collect(detections=True)` the detector's boxes as well.  num_classes x max_boxes <= 64: every slot is a crop of the forward
+        (few heads in a large `max_boxes` pay for the padding; `detect()` + `heads()` run the forward at the head count)."""
+        from .yolo import check_model_image_size
+        if self._begun is None:
+            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        check_model_image_size(size)
+        anchors, num_classes = self._anchors(anchors, num_classes)
+        ticket = self._begun[0]
+        cap = self._h.frame_detect_heads(ticket, anchors, num_classes, size, score, iou, max_boxes)
+        self._begun = None
+        self._pending.append((ticket, None, cap))
 
     def attach_detector(self, yolo) -> None:
         """Use this `whenet_hip.detector.YOLO`'s anchors and class count in `detect()` (the default is the one built last with
@@ -134,13 +156,25 @@ class FramePipeline:
         rects = _lib.frame_rects(fh, fw, bboxes)
         self._h.frame_heads(ticket, rects)
         self._begun = None
-        self._pending.append((ticket, rects))
+        self._pending.append((ticket, rects, 0))
 
-    def collect(self):
-        """Oldest submitted frame -> (rects [k,4] int32, yaw, pitch, roll float32 (k,))."""
+    def collect(self, detections: bool = False):
+        """Oldest submitted frame -> (rects [k,4] int32, yaw, pitch, roll float32 (k,)).  A `detect_heads()` frame: the k heads
+        whose window lies inside the frame; with `detections=True` also (boxes [n,4], scores [n], classes [n], valid [n]) of ALL n
+        detections (valid 0: a window that is empty or leaves the frame -- `heads()` raises for such a box).  `detections=True` on
+        a frame submitted any other way raises ValueError and leaves it in flight."""
         if not self._pending:
             raise ValueError("nothing in flight")
-        ticket, rects = self._pending.popleft()
+        ticket, rects, cap = self._pending[0]
+        if rects is None:
+            boxes, scores, classes, rects, valid, ypr, _, _ = self._h.collect_detect(ticket, cap)
+            self._pending.popleft()
+            keep = valid != 0
+            res = (np.ascontiguousarray(rects[keep]), ypr[keep, 0].copy(), ypr[keep, 1].copy(), ypr[keep, 2].copy())
+            return res + (boxes, scores, classes, valid) if detections else res
+        if detections:
+            raise ValueError("collect(detections=True): the oldest frame in flight was not submitted by detect_heads()")
+        self._pending.popleft()
         k = rects.shape[0]
         ypr, _, _ = self._h.collect(ticket, k)
         return rects, ypr[:, 0].copy(), ypr[:, 1].copy(), ypr[:, 2].copy()

@@ -368,6 +368,39 @@ WHENET_API int whenet_frame_detect(whenet_t* h, int ticket, int out_h, int out_w
                         float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
                         int32_t* classes, int* count);
 
+/* ---- ONE submission per video frame: detect, crop and pose without the host in between.  whenet_frame_detect takes the boxes
+ * to the host (it waits for the detector), the caller turns them into windows and whenet_frame_heads uploads their crop plans;
+ * here the selected boxes stay on the device, a kernel computes the windows (whenet_frame_rects) and crop plans from them, and the
+ * heads are cropped and run over the CAPACITY classes x max_boxes (rows without a head are zero crops; a crop's result does not
+ * depend on the batch or on its position, so head i is bitwise what the two-step path returns for detection i).
+ *   whenet_frame_detect_heads  between whenet_frame_begin and the collect, in the place of whenet_frame_detect + whenet_frame_heads:
+ *                  letterbox -> body -> yolo_eval -> windows + crop plans -> crop / resize -> forward -> D2H, ENQUEUE-ONLY: it returns
+ *                  without waiting for the device (buffers are allocated and graphs captured on the first call for a shape).  Arguments
+ *                  as whenet_frame_detect; classes x max_boxes must be 1..64 (the head detector has one class, the reference's
+ *                  default max_boxes is 20).  Needs a network AND a detector on the handle.  The ticket then behaves like one whose
+ *                  heads are enqueued.
+ *   whenet_collect_detect  waits once and returns *count detections, class by class as whenet_yolo_eval orders them: boxes [count][4],
+ *                  scores, classes, rects [count][4] = (y0, x0, y1, x1) as whenet_frame_rects, valid [count] = 1 iff the window is
+ *                  non-empty and inside the frame (what whenet_frame_heads rejects with WHENET_EINVAL; the device cannot raise, so the
+ *                  head is skipped and reported), and the heads' results ypr [count][3], argmax [count][3], logits [count][252]
+ *                  (the last two may be NULL); rows of invalid heads are NaN / -1 / NaN.  `capacity` = rows the arrays hold, at least
+ *                  classes x max_boxes of the submission.  WHENET_EINVAL for a ticket that whenet_frame_detect_heads did not submit;
+ *                  whenet_collect answers such a ticket the same way.  Either error leaves the ticket collectable.
+ *   whenet_op_head_plan  the window / crop plan kernel alone on caller boxes [k][4] (host pointers, k 1..2048): rects [k][4], valid [k],
+ *                  plans [k][WHENET_CROP_PLAN_INTS] (may be NULL; zeros where valid is 0).  Works on a whenet_create_postproc handle.
+ *   whenet_crop_plan  the crop plan of one window as the host computes it for whenet_frame_heads: {y0, x0, h, w, 2x-shrink flag (set
+ *                  for a 448 x 448 window only: cv2.resize switches to INTER_AREA), xmax (first output column that reads a single
+ *                  sample), 0, 0} followed by six 224-entry tables xofs | a0 | a1 | yofs | b0 | b1 (OpenCV's INTER_LINEAR offsets and
+ *                  11-bit coefficients).  An empty window is WHENET_EINVAL.  Pure host arithmetic, no GPU needed. */
+#define WHENET_CROP_PLAN_INTS (8 + 6 * 224)
+WHENET_API int whenet_frame_detect_heads(whenet_t* h, int ticket, int out_h, int out_w, const float* anchors, int num_anchors,
+                              float score_threshold, float iou_threshold, int max_boxes);
+WHENET_API int whenet_collect_detect(whenet_t* h, int ticket, int capacity, int* count, float* boxes, float* scores, int32_t* classes,
+                          int32_t* rects, int32_t* valid, float* ypr, int32_t* argmax, float* logits);
+WHENET_API int whenet_op_head_plan(whenet_t* h, int frame_h, int frame_w, const float* boxes, int k, int32_t* rects, int32_t* valid,
+                        int32_t* plans);
+WHENET_API int whenet_crop_plan(const int32_t rect[4], int32_t* plan);
+
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
  * recorded on the chain's stream between consecutive kernel launches; a launch's time is
