@@ -696,6 +696,66 @@ int whenet_op_head_plan(whenet_t* h, int frame_h, int frame_w, const float* boxe
     return guarded(h, [&](whenet::Engine& e) { e.op_head_plan(frame_h, frame_w, boxes, k, rects, valid, plans); });
 }
 
+// ---- clips: F frames per submission (detector.cpp, engine_post.cpp) ----
+int whenet_clip_begin(whenet_t* h, const uint8_t* frames, int num_frames, int frame_h, int frame_w, int channel_order, int* ticket) {
+    if (ticket == nullptr || (channel_order != WHENET_RGB && channel_order != WHENET_BGR)) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        // (argument errors before an engine is taken: a refused clip must not shift the round-robin)
+        WHENET_REQUIRE(num_frames >= 1 && num_frames <= 16, WHENET_EINVAL,
+                       "clip_begin: " + std::to_string(num_frames) + " frames: a clip holds 1..16 (the detector's batch limit)");
+        (void)e;
+        const size_t idx = h->next % size_t(h->inflight);
+        *ticket = h->take().clip_begin(frames, num_frames, frame_h, frame_w, channel_order == WHENET_BGR) * MAX_INFLIGHT_ENGINES + int(idx);
+    });
+}
+
+int whenet_clip_detect_heads(whenet_t* h, int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold,
+                             float iou_threshold, int max_boxes, int max_heads, int* slots_per_frame) {
+    if (slots_per_frame == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        *slots_per_frame = h->at(size_t(idx)).clip_detect_heads(ticket / MAX_INFLIGHT_ENGINES, out_h, out_w, anchors, num_anchors,
+                                                                score_threshold, iou_threshold, max_boxes, max_heads);
+    });
+}
+
+int whenet_collect_clip(whenet_t* h, int ticket, int capacity, int* num_frames, int32_t* counts, float* boxes, float* scores,
+                        int32_t* classes, int32_t* rects, int32_t* valid, int32_t* row, float* ypr, int32_t* argmax, float* logits,
+                        int* rows_used, int* overflow) {
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "unknown ticket " + std::to_string(ticket));
+        h->at(size_t(idx)).collect_clip(ticket / MAX_INFLIGHT_ENGINES, capacity, num_frames, counts, boxes, scores, classes, rects, valid, row,
+                                        ypr, argmax, logits, rows_used, overflow);
+    });
+}
+
+int whenet_op_letterbox_batch(whenet_t* h, const uint8_t* frames, int num_frames, int frame_h, int frame_w, int channel_order, int out_h,
+                              int out_w, uint8_t* canvas_u8, float* image_f32) {
+    if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        e.op_letterbox_batch(frames, num_frames, frame_h, frame_w, channel_order == WHENET_BGR, out_h, out_w, canvas_u8, image_f32);
+    });
+}
+
+int whenet_yolo_eval_batch(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
+                           const float* anchors, int num_anchors, int num_classes, float image_h, float image_w, float score_threshold,
+                           float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,
+                           int32_t* counts) {
+    return guarded(h, [&](whenet::Engine& e) {
+        e.yolo_eval_batch(feats, num_images, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_h, image_w, score_threshold,
+                          iou_threshold, max_boxes, boxes, scores, classes, index, counts);
+    });
+}
+
+int whenet_op_head_compact(whenet_t* h, const int32_t* valid, const int32_t* count, int num_frames, int slots_per_frame, int max_heads,
+                           int32_t* row, int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow) {
+    return guarded(h, [&](whenet::Engine& e) {
+        e.op_head_compact(valid, count, num_frames, slots_per_frame, max_heads, row, slot_of_row, rows_used, overflow);
+    });
+}
+
 static_assert(WHENET_CROP_PLAN_INTS == whenet::CROP_PLAN_INTS, "whenet_hip.h and kernels.h disagree on the crop plan size");
 int whenet_crop_plan(const int32_t rect[4], int32_t* plan) {
     if (rect == nullptr || plan == nullptr) return WHENET_EINVAL;

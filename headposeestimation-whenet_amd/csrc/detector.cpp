@@ -474,6 +474,75 @@ void Engine::frame_detect_heads(int ticket, int out_h, int out_w, const float* a
     slot.frame_ticket = -1;
 }
 
+// clip_begin -> clip_detect_heads -> collect_clip: frame_detect_heads over the F frames of a clip (demo_video.py:49-63 with the
+// next frames in hand).  The letterbox, the selection and the head plans take the frame as a grid dimension, the body runs its
+// plan of n = F; the compaction kernel then numbers the slots that hold a head with a window in (frame, detection) order, the
+// gathering crop kernel fills forward row r from slot_of_row[r] and the forward runs over max_heads rows instead of the
+// capacity F x K.  Every stage is batch-invariant, so slot (f, i) holds the bytes frame_detect_heads returns for frame f alone.
+// Allocations and the graph capture come first; after the first call for a shape nothing here waits for the device.
+int Engine::clip_detect_heads(int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold,
+                              float iou_threshold, int max_boxes, int max_heads) {
+    DeviceGuard guard(device_);
+    require_model();
+    require_detector();
+    Slot& slot = resident_slot(ticket, "clip_detect_heads", HOLDS_CLIP);
+    const int F = slot.clip_f;
+    (void)letterbox_plan_layout(slot.fh, slot.fw, out_h, out_w);
+    check_detector_input(F, out_h, out_w);
+    WHENET_REQUIRE(det_->out_filters % 3 == 0 && det_->out_filters / 3 > 5, WHENET_EINVAL,
+                   "detect: the loaded detector's outputs are not 3 anchors x (5 + classes) wide");
+    WHENET_REQUIRE(anchors != nullptr, WHENET_EINVAL, "detect: NULL argument");
+    const int num_classes = det_->out_filters / 3 - 5;
+    int held = 0;                                         // boxes the maps hold: max_boxes is cut to it, as yolo_eval does
+    for (int m = 0; m < det_->num_maps; ++m) held += ((out_h / 32) << m) * ((out_w / 32) << m) * 3;
+    WHENET_REQUIRE(max_boxes >= 1, WHENET_EINVAL, "clip_detect_heads: max_boxes must be >= 1");
+    const long K_long = long(num_classes) * std::min(max_boxes, held);
+    WHENET_REQUIRE(K_long * F <= HEAD_COMPACT_MAX_SLOTS, WHENET_EINVAL,
+                   "clip_detect_heads: frames x classes x max_boxes = " + std::to_string(F) + " x " + std::to_string(num_classes) + " x " +
+                       std::to_string(std::min(max_boxes, held)) + " must be 1.." + std::to_string(HEAD_COMPACT_MAX_SLOTS));
+    const int K = int(K_long);
+    if (max_heads == 0) max_heads = std::min(F * K, 256);
+    WHENET_REQUIRE(max_heads >= 1 && max_heads <= 256, WHENET_EINVAL,
+                   "clip_detect_heads: max_heads = " + std::to_string(max_heads) + " must be 1..256 (the rows of the forward)");
+    const ClipRows rows(F, K, max_heads);
+    const size_t frame_bytes = size_t(slot.fh) * slot.fw * 3;
+    ensure_capacity(max_heads);                           // (allocations first: nothing is enqueued yet if one of them fails)
+    ensure_slot(slot, max_heads);
+    slot.plan.d.grow(rows.S * CROP_PLAN_INTS * sizeof(int32_t));
+    slot.det.h.grow(rows.bytes());
+    slot.det.d.grow(rows.bytes());
+    DetPlan& p = detector_plan(F, out_h, out_w);
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+    const uint8_t* d_frames = slot.frame.d.as<uint8_t>();
+    const uint8_t* d_canvas = enqueue_letterbox(d_frames, slot.fh, slot.fw, slot.swap_rb, out_h, out_w, true, false, F).first;
+    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img16.as<half_t>(), size_t(F) * out_h * out_w, stream_);
+    WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
+    const float* feats[3] = {p.maps[0].as<float>(), p.maps[1].as<float>(), p.maps[2].as<float>()};
+    const YoloArgs y = enqueue_yolo_eval(feats, true, p.gh, p.gw, det_->num_maps, anchors, num_anchors, num_classes, float(slot.fh),
+                                         float(slot.fw), score_threshold, iou_threshold, max_boxes, false, F);
+    WHENET_REQUIRE(num_classes * y.max_boxes == K, WHENET_EINVAL, "clip_detect_heads: the selection's capacity differs from the plan's");
+    void* const d_rows = slot.det.d.as<void>();
+    HeadPlanArgs a{};
+    a.in_boxes = y.out_boxes, a.in_scores = y.out_scores, a.in_count = y.out_count;
+    a.num_classes = num_classes, a.max_boxes = y.max_boxes, a.frame_h = slot.fh, a.frame_w = slot.fw, a.frames = F;
+    a.boxes = rows.boxes(d_rows), a.scores = rows.scores(d_rows), a.classes = rows.classes(d_rows), a.count = rows.count(d_rows);
+    a.rects = rows.rects(d_rows), a.valid = rows.valid(d_rows), a.plans = slot.plan.d.as<int32_t>();
+    launch_head_plan(a, stream_);
+    launch_head_compact(a.valid, a.count, F, K, max_heads, rows.row(d_rows), rows.slot_of_row(d_rows), rows.rows_used(d_rows),
+                        rows.overflow(d_rows), stream_);
+    launch_crop_resize_gather(d_frames, frame_bytes, slot.fw, slot.swap_rb, a.plans, K, rows.slot_of_row(d_rows), max_heads,
+                              slot.in.d.as<uint8_t>(), stream_);
+    run_forward(slot.in.d.as<uint8_t>(), max_heads, slot.dev(), stream_);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.det.h.as<void>(), d_rows, rows.bytes(), hipMemcpyDeviceToHost, stream_));
+    copy_results_async(slot.host(), slot.dev(), max_heads, stream_);
+    WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));
+    slot.n = max_heads;
+    slot.clip_cap = K;
+    slot.clip_heads = max_heads;
+    slot.frame_ticket = -1;
+    return K;
+}
+
 // ------------------------------------------------------------------------------------------
 // single layers on caller tensors (float32 in / out, converted on the device): exactly the kernels the body runs
 // ------------------------------------------------------------------------------------------

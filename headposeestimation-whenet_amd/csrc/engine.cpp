@@ -1141,6 +1141,7 @@ int Engine::finish_submission(Slot& s, int n) {
     s.busy = true;
     s.n = n;
     s.det_cap = -1;
+    s.clip_f = 0, s.clip_cap = -1;
     s.ticket = next_ticket_++;
     return s.ticket;
 }
@@ -1190,6 +1191,8 @@ void Engine::collect(int ticket, float* ypr, int32_t* argmax, float* logits) {
     WHENET_REQUIRE(slot != nullptr, WHENET_EINVAL, "unknown or already collected ticket " + std::to_string(ticket));
     WHENET_REQUIRE(slot->det_cap < 0, WHENET_EINVAL,
                    "collect: ticket " + std::to_string(ticket) + " was submitted by frame_detect_heads: collect_detect returns it");
+    WHENET_REQUIRE(slot->clip_cap < 0, WHENET_EINVAL,
+                   "collect: ticket " + std::to_string(ticket) + " was submitted by clip_detect_heads: collect_clip returns it");
     WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
     copy_results_host(Results{ypr, argmax, logits}, slot->host(), slot->n);
     slot->busy = false;

@@ -256,6 +256,24 @@ class Engine {
                             float iou_threshold, int max_boxes);
     // the plan kernel alone on caller boxes (host pointers): rects [k,4], valid [k], plans [k][CROP_PLAN_INTS] (may be nullptr)
     void op_head_plan(int fh, int fw, const float* boxes, int k, int32_t* rects, int32_t* valid, int32_t* plans);
+    // A CLIP: F frames of one size as one submission (detector.cpp).  clip_begin uploads [F][fh][fw][3] once and holds the slot;
+    // clip_detect_heads (enqueue-only; returns K = slots per frame) runs letterbox, body, selection and head plans over the F
+    // frames, numbers the heads that have a window (headplan.hip's compaction) and runs the forward over max_heads rows
+    // (0: min(F * K, 256)); collect_clip waits once and scatters: slot (f, i) gets the result of its row, or NaN / -1 / NaN.
+    int clip_begin(const uint8_t* frames, int nframes, int fh, int fw, int swap_rb);
+    int clip_detect_heads(int ticket, int out_h, int out_w, const float* anchors, int num_anchors, float score_threshold, float iou_threshold,
+                          int max_boxes, int max_heads);
+    void collect_clip(int ticket, int capacity, int* nframes, int32_t* counts, float* boxes, float* scores, int32_t* classes, int32_t* rects,
+                      int32_t* valid, int32_t* row, float* ypr, int32_t* argmax, float* logits, int* rows_used, int* overflow);
+    // single stages of a clip on host arrays, for the tests: the letterbox of F frames, the selection of F images (outputs
+    // [F][C * max_boxes]..., counts [F]) and the compaction kernel alone
+    void op_letterbox_batch(const uint8_t* frames, int nframes, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                            float* image_f32);
+    void yolo_eval_batch(const float* const* feats, int images, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
+                         int num_anchors, int num_classes, float image_h, float image_w, float score_threshold, float iou_threshold,
+                         int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* counts);
+    void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
+                         int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
                   int stride, int cout, int leaky, const float* skip, int f32_out, float* out);
     void op_dpool(const float* in, int n, int H, int W, int c, int stride, float* out);
@@ -278,6 +296,8 @@ class Engine {
         int fh = 0, fw = 0, swap_rb = 0; //   (tickets are never reused, so a stale value matches nothing)
         StagedBuffer det;                // frame_detect_heads: count | boxes | scores | classes | rects | valid over det_cap rows
         int det_cap = -1;                //   (DetRows); >= 0 marks a submission that collect_detect, not collect, returns
+        int clip_f = 0;                  // clip_begin: frames held in `frame` (0: a single frame); with clip_detect_heads `det` is a
+        int clip_cap = -1, clip_heads = 0;   // ClipRows(clip_f, clip_cap, clip_heads); clip_cap >= 0: collect_clip returns it
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -361,19 +381,22 @@ class Engine {
     hipStream_t copy_stream();          // created on first use
     void ensure_slot_frame(Slot& s, size_t frame_bytes, int k);
     Slot* free_slot();
-    Slot& resident_slot(int ticket, const char* what);     // the held slot of a frame_begin ticket that has no heads yet
+    // the held slot of a frame_begin (HOLDS_FRAME) or clip_begin (HOLDS_CLIP) ticket that has no heads yet
+    enum { HOLDS_FRAME = 0, HOLDS_CLIP = 1, HOLDS_EITHER = 2 };
+    Slot& resident_slot(int ticket, const char* what, int holds = HOLDS_FRAME);
     // frame on the device -> canvas in the caller's host arrays (either may be nullptr), through pinned memory with one wait
     void run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
-                       float* image_f32);
+                       float* image_f32, int frames = 1);
     int finish_submission(Slot& s, int n);      // record `done`, mark the slot busy, hand out its ticket
     // run_letterbox's launches alone: the device canvas (uint8, float32) of those asked for, valid until the next letterbox
+    // frames > 1: d_frame is a clip [frames][fh][fw][3], the canvases are [frames][out_h][out_w][3]
     std::pair<uint8_t*, float*> enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, bool want_u8,
-                                                  bool want_f32);
+                                                  bool want_f32, int frames = 1);
     // the argument set-up of yolo_eval (scratch carved and grown, host maps uploaded) and its launches on stream_; no wait, no copy
     // back: the selected boxes stay in yolo_scratch_ (out_boxes / out_scores / out_count of the returned arguments)
     YoloArgs enqueue_yolo_eval(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
                                const float* anchors, int num_anchors, int num_classes, float image_h, float image_w, float score_threshold,
-                               float iou_threshold, int max_boxes, bool want_all_scores);
+                               float iou_threshold, int max_boxes, bool want_all_scores, int images = 1);
     // yolo_eval on maps that are in host memory (uploaded first) or already on the device
     int yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
                        int num_anchors, int num_classes, float image_h, float image_w, float score_threshold, float iou_threshold,

@@ -70,6 +70,26 @@ struct DetRows {
     int32_t* valid(void* base) const { return rects(base) + K * 4; }
 };
 
+// The detection block of a clip_detect_heads slot: F frames x K slots (S = F * K <= 1024) and M forward rows, one allocation so
+// that ONE copy brings it back:
+// rows_used, overflow (int32, padded to 16 bytes) | count [16] i32 | boxes [S][4] f32 | scores [S] f32 | classes [S] i32 |
+// rects [S][4] i32 | valid [S] i32 | row [S] i32 | slot_of_row [M] i32
+struct ClipRows {
+    size_t S, M;
+    ClipRows(int frames, int k, int max_heads) : S(size_t(frames) * size_t(k)), M(size_t(max_heads)) {}
+    size_t bytes() const { return 80 + S * 48 + M * 4; }
+    int32_t* rows_used(void* base) const { return static_cast<int32_t*>(base); }
+    int32_t* overflow(void* base) const { return static_cast<int32_t*>(base) + 1; }
+    int32_t* count(void* base) const { return static_cast<int32_t*>(base) + 4; }
+    float* boxes(void* base) const { return reinterpret_cast<float*>(static_cast<char*>(base) + 80); }
+    float* scores(void* base) const { return boxes(base) + S * 4; }
+    int32_t* classes(void* base) const { return reinterpret_cast<int32_t*>(scores(base) + S); }
+    int32_t* rects(void* base) const { return classes(base) + S; }
+    int32_t* valid(void* base) const { return rects(base) + S * 4; }
+    int32_t* row(void* base) const { return valid(base) + S; }
+    int32_t* slot_of_row(void* base) const { return row(base) + S; }
+};
+
 inline void copy_name(char* dst, size_t cap, const std::string& s) {
     std::memset(dst, 0, cap);
     std::memcpy(dst, s.data(), std::min(cap - 1, s.size()));

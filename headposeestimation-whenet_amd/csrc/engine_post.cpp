@@ -82,7 +82,7 @@ void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, c
 // their own results leave the stream idle; frame_detect_heads does not, so the one host-side hazard -- re-staging the tables
 // through their single pinned buffer while an earlier copy out of it may still be queued -- waits for the stream, on that branch only.
 std::pair<uint8_t*, float*> Engine::enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w,
-                                                      bool want_u8, bool want_f32) {
+                                                      bool want_u8, bool want_f32, int frames) {
     if (!(lb_plan_valid_ && lb_plan_.ih == fh && lb_plan_.iw == fw && lb_plan_.oh == out_h && lb_plan_.ow == out_w)) {
         lb_plan_valid_ = false;
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -102,22 +102,26 @@ std::pair<uint8_t*, float*> Engine::enqueue_letterbox(const uint8_t* d_frame, in
         WHENET_HIP_CHECK(hipMemcpy(lb_lut_.as<void>(), lut, sizeof(lut), hipMemcpyHostToDevice));
     }
     const LetterboxPlan& p = lb_plan_;
-    const size_t nout = size_t(out_h) * out_w * 3;
-    lb_mid_.grow(size_t(fh) * p.nw * 3);
+    const size_t nout = size_t(frames) * out_h * out_w * 3;
+    lb_mid_.grow(size_t(frames) * fh * p.nw * 3);
     if (want_u8) lb_u8_.h.grow(nout), lb_u8_.d.grow(nout);
     if (want_f32) lb_f32_.h.grow(nout * sizeof(float)), lb_f32_.d.grow(nout * sizeof(float));
     uint8_t* const d_u8 = want_u8 ? lb_u8_.d.as<uint8_t>() : nullptr;
     float* const d_f32 = want_f32 ? lb_f32_.d.as<float>() : nullptr;
-    launch_letterbox(d_frame, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32,
-                     num_cus_, stream_);
+    if (frames == 1)
+        launch_letterbox(d_frame, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32,
+                         num_cus_, stream_);
+    else
+        launch_letterbox_batch(d_frame, frames, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8,
+                               d_f32, num_cus_, stream_);
     return {d_u8, d_f32};
 }
 
 void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
-                           float* image_f32) {
+                           float* image_f32, int frames) {
     WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
-    const size_t nout = size_t(out_h) * out_w * 3;
-    const auto dev = enqueue_letterbox(d_frame, fh, fw, swap_rb, out_h, out_w, canvas_u8 != nullptr, image_f32 != nullptr);
+    const size_t nout = size_t(frames) * out_h * out_w * 3;
+    const auto dev = enqueue_letterbox(d_frame, fh, fw, swap_rb, out_h, out_w, canvas_u8 != nullptr, image_f32 != nullptr, frames);
     uint8_t* const d_u8 = dev.first;
     float* const d_f32 = dev.second;
     if (canvas_u8) WHENET_HIP_CHECK(hipMemcpyAsync(lb_u8_.h.as<void>(), d_u8, nout, hipMemcpyDeviceToHost, stream_));
@@ -136,6 +140,17 @@ void Engine::op_letterbox(const uint8_t* frame, int fh, int fw, int swap_rb, int
     lb_frame_.grow(fbytes);
     WHENET_HIP_CHECK(hipMemcpyAsync(lb_frame_.as<void>(), frame, fbytes, hipMemcpyHostToDevice, stream_));
     run_letterbox(lb_frame_.as<uint8_t>(), fh, fw, swap_rb, out_h, out_w, canvas_u8, image_f32);
+}
+
+void Engine::op_letterbox_batch(const uint8_t* frames, int nframes, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                                float* image_f32) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(frames != nullptr && nframes >= 1 && nframes <= 16, WHENET_EINVAL, "op_letterbox_batch: NULL frames, or a frame count outside 1..16");
+    (void)letterbox_plan_layout(fh, fw, out_h, out_w);
+    const size_t bytes = size_t(nframes) * fh * fw * 3;
+    lb_frame_.grow(bytes);
+    WHENET_HIP_CHECK(hipMemcpyAsync(lb_frame_.as<void>(), frames, bytes, hipMemcpyHostToDevice, stream_));
+    run_letterbox(lb_frame_.as<uint8_t>(), fh, fw, swap_rb, out_h, out_w, canvas_u8, image_f32, nframes);
 }
 
 // The resident-frame form of submit_frame.  frame_begin: pinned staging copy + asynchronous H2D into the slot's frame buffer; the
@@ -157,12 +172,36 @@ int Engine::frame_begin(const uint8_t* frame, int fh, int fw, int swap_rb) {
     return slot.frame_ticket;
 }
 
-Engine::Slot& Engine::resident_slot(int ticket, const char* what) {
+// frame_begin for the F frames of a clip [F][fh][fw][3]: one pinned staging copy, one H2D; the slot's frame buffer holds them all
+int Engine::clip_begin(const uint8_t* frames, int nframes, int fh, int fw, int swap_rb) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(frames != nullptr && fh > 0 && fw > 0, WHENET_EINVAL, "clip_begin: bad arguments");
+    WHENET_REQUIRE(nframes >= 1 && nframes <= 16, WHENET_EINVAL,
+                   "clip_begin: " + std::to_string(nframes) + " frames: a clip holds 1..16 (the detector's batch limit)");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const size_t bytes = size_t(nframes) * fh * fw * 3;
+    slot.frame.h.grow(bytes);
+    slot.frame.d.grow(bytes);
+    std::memcpy(slot.frame.h.as<void>(), frames, bytes);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.frame.d.as<void>(), slot.frame.h.as<void>(), bytes, hipMemcpyHostToDevice, copy_stream()));
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = fh, slot.fw = fw, slot.swap_rb = swap_rb;
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = nframes;
+    return slot.frame_ticket;
+}
+
+Engine::Slot& Engine::resident_slot(int ticket, const char* what, int holds) {
     for (Slot& s : slots_)
         if (s.busy && s.ticket == ticket) {
             WHENET_REQUIRE(s.frame_ticket == ticket, WHENET_EINVAL,
                            std::string(what) + ": ticket " + std::to_string(ticket) +
                                " holds no frame that waits for its heads (not from frame_begin, or its heads are already enqueued)");
+            WHENET_REQUIRE(holds != HOLDS_FRAME || s.clip_f == 0, WHENET_EINVAL,
+                           std::string(what) + ": ticket " + std::to_string(ticket) + " holds a clip (clip_begin): clip_detect_heads enqueues it");
+            WHENET_REQUIRE(holds != HOLDS_CLIP || s.clip_f > 0, WHENET_EINVAL,
+                           std::string(what) + ": ticket " + std::to_string(ticket) + " holds a single frame (frame_begin), not a clip");
             return s;
         }
     throw Error(WHENET_EINVAL, std::string(what) + ": unknown or already collected ticket " + std::to_string(ticket));
@@ -178,7 +217,7 @@ void Engine::frame_letterbox(int ticket, int out_h, int out_w, uint8_t* canvas_u
 // submit_frame from its crop plans on: nothing differs except that the frame is already on the device.
 void Engine::frame_heads(int ticket, const int32_t* rects, int k) {
     DeviceGuard guard(device_);
-    Slot& slot = resident_slot(ticket, "frame_heads");
+    Slot& slot = resident_slot(ticket, "frame_heads", k == 0 ? HOLDS_EITHER : HOLDS_FRAME);      // (no heads: releases a clip as well)
     WHENET_REQUIRE(k >= 0 && (k == 0 || rects != nullptr), WHENET_EINVAL, "frame_heads: bad arguments");
     check_rects(slot.fh, slot.fw, rects, k);
     if (k > 0) {
@@ -215,8 +254,9 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
 // on_device: the maps are where the detector body left them (detector.cpp); nothing is uploaded
 YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
                                    const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
-                                   float score_threshold, float iou_threshold, int max_boxes, bool want_all_scores) {
+                                   float score_threshold, float iou_threshold, int max_boxes, bool want_all_scores, int images) {
     WHENET_REQUIRE(feats && grid_h && grid_w && anchors, WHENET_EINVAL, "yolo_eval: NULL argument");
+    WHENET_REQUIRE(images >= 1 && images <= 16, WHENET_EINVAL, "yolo_eval: 1..16 images");
     WHENET_REQUIRE((num_layers == 3 && num_anchors == 9) || (num_layers == 2 && num_anchors == 6), WHENET_EINVAL,
                    "yolo_eval: 3 maps with 9 anchors or 2 maps with 6 (model.py:203)");
     WHENET_REQUIRE(num_classes >= 1 && num_classes <= 1024 && image_h > 0 && image_w > 0, WHENET_EINVAL,
@@ -226,6 +266,7 @@ YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, co
     static const int ANCHOR_MASK3[3][3] = {{6, 7, 8}, {3, 4, 5}, {0, 1, 2}};
     static const int ANCHOR_MASK2[2][3] = {{3, 4, 5}, {1, 2, 3}};
     YoloArgs a{};
+    a.images = images;
     a.num_layers = num_layers;
     a.num_classes = num_classes;
     a.na = 3;
@@ -269,7 +310,7 @@ YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, co
             L.anchor[k][0] = anchors[2 * m];
             L.anchor[k][1] = anchors[2 * m + 1];
         }
-        feat_bytes[l] = size_t(L.gh) * L.gw * per * sizeof(float);
+        feat_bytes[l] = size_t(images) * L.gh * L.gw * per * sizeof(float);
         if (!on_device) feat_off[l] = cv.add(feat_bytes[l]);
         N += L.gh * L.gw * 3;
     }
@@ -278,15 +319,15 @@ YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, co
     while (a.NP < N) a.NP <<= 1;
     if (max_boxes > N) max_boxes = N;                       // (no more selections than boxes)
     a.max_boxes = max_boxes;
-    const size_t C = size_t(num_classes), MB = size_t(max_boxes);
-    const size_t o_boxes = cv.add(size_t(N) * 4 * sizeof(float));
-    const size_t o_all = want_all_scores ? cv.add(size_t(N) * C * sizeof(float)) : 0;
-    const size_t o_counts = cv.add(C * sizeof(int));
-    const size_t o_keys = cv.add(C * size_t(a.NP) * sizeof(unsigned long long));
-    const size_t o_ob = cv.add(C * MB * 4 * sizeof(float));
-    const size_t o_os = cv.add(C * MB * sizeof(float));
-    const size_t o_oi = cv.add(C * MB * sizeof(int));
-    const size_t o_oc = cv.add(C * sizeof(int));
+    const size_t C = size_t(num_classes), MB = size_t(max_boxes), F = size_t(images);      // (every array: [images][...])
+    const size_t o_boxes = cv.add(F * size_t(N) * 4 * sizeof(float));
+    const size_t o_all = want_all_scores ? cv.add(F * size_t(N) * C * sizeof(float)) : 0;
+    const size_t o_counts = cv.add(F * C * sizeof(int));
+    const size_t o_keys = cv.add(F * C * size_t(a.NP) * sizeof(unsigned long long));
+    const size_t o_ob = cv.add(F * C * MB * 4 * sizeof(float));
+    const size_t o_os = cv.add(F * C * MB * sizeof(float));
+    const size_t o_oi = cv.add(F * C * MB * sizeof(int));
+    const size_t o_oc = cv.add(F * C * sizeof(int));
     if (cv.used > yolo_scratch_.bytes()) {
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         yolo_scratch_.reset(cv.used, "yolo_eval scratch");
@@ -383,6 +424,116 @@ int Engine::collect_detect(int ticket, int capacity, float* boxes, float* scores
     slot->busy = false;
     slot->det_cap = -1;
     return count;
+}
+
+// yolo_eval over the images of a batch (host maps [images][gh][gw][A (5 + C)] per layer): one upload, the two launches with the
+// image as a grid dimension, the selected rows of every image back in one wait, concatenated class by class per image.
+void Engine::yolo_eval_batch(const float* const* feats, int images, const int* grid_h, const int* grid_w, int num_layers,
+                             const float* anchors, int num_anchors, int num_classes, float image_h, float image_w, float score_threshold,
+                             float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,
+                             int32_t* counts) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(boxes && scores && classes && counts, WHENET_EINVAL, "yolo_eval_batch: NULL argument");
+    const YoloArgs a = enqueue_yolo_eval(feats, false, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_h, image_w,
+                                         score_threshold, iou_threshold, max_boxes, false, images);
+    const size_t C = size_t(num_classes), MB = size_t(a.max_boxes), F = size_t(images), S = F * C * MB;
+    std::vector<float> ob(S * 4), os(S);
+    std::vector<int> oi(S), oc(F * C);
+    WHENET_HIP_CHECK(hipMemcpyAsync(ob.data(), a.out_boxes, S * 4 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(os.data(), a.out_scores, S * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(oi.data(), a.out_index, S * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(oc.data(), a.out_count, F * C * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+    for (size_t f = 0; f < F; ++f) {
+        size_t out = f * C * MB;                            // image f's rows of the caller's arrays
+        const size_t first = out;
+        for (size_t c = 0; c < C; ++c) {
+            const size_t src = (f * C + c) * MB, k = size_t(std::max(0, std::min(oc[f * C + c], int(MB))));
+            std::memcpy(boxes + out * 4, ob.data() + src * 4, k * 4 * sizeof(float));
+            std::memcpy(scores + out, os.data() + src, k * sizeof(float));
+            if (index) std::memcpy(index + out, oi.data() + src, k * sizeof(int));
+            for (size_t j = 0; j < k; ++j) classes[out + j] = int32_t(c);
+            out += k;
+        }
+        counts[f] = int32_t(out - first);
+    }
+}
+
+// What clip_detect_heads (detector.cpp) enqueued: one wait, then every frame's detections over its K slots and, scattered by `row`,
+// the results of the heads that got a forward row.
+void Engine::collect_clip(int ticket, int capacity, int* nframes, int32_t* counts, float* boxes, float* scores, int32_t* classes,
+                          int32_t* rects, int32_t* valid, int32_t* row, float* ypr, int32_t* argmax, float* logits, int* rows_used,
+                          int* overflow) {
+    DeviceGuard guard(device_);
+    Slot* slot = nullptr;
+    for (Slot& s : slots_)
+        if (s.busy && s.ticket == ticket) slot = &s;
+    WHENET_REQUIRE(slot != nullptr, WHENET_EINVAL, "unknown or already collected ticket " + std::to_string(ticket));
+    WHENET_REQUIRE(slot->clip_cap >= 0, WHENET_EINVAL,
+                   "collect_clip: ticket " + std::to_string(ticket) + " was not submitted by clip_detect_heads");
+    WHENET_REQUIRE(nframes && counts && boxes && scores && classes && rects && valid && row && ypr && rows_used && overflow, WHENET_EINVAL,
+                   "collect_clip: NULL argument");
+    const int F = slot->clip_f, K = slot->clip_cap, M = slot->clip_heads;
+    WHENET_REQUIRE(capacity >= F * K, WHENET_EINVAL,
+                   "collect_clip: capacity " + std::to_string(capacity) + " is below the submission's " + std::to_string(F * K) +
+                       " rows (frames x classes x max_boxes)");
+    WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
+    const ClipRows rows(F, K, M);
+    void* const base = slot->det.h.as<void>();
+    const size_t S = rows.S;
+    *nframes = F;
+    *rows_used = std::max(0, std::min(*rows.rows_used(base), M));
+    *overflow = std::max(0, *rows.overflow(base));
+    for (int f = 0; f < F; ++f) counts[f] = std::max(0, std::min(rows.count(base)[f], K));
+    std::memcpy(boxes, rows.boxes(base), S * 4 * sizeof(float));
+    std::memcpy(scores, rows.scores(base), S * sizeof(float));
+    std::memcpy(classes, rows.classes(base), S * sizeof(int32_t));
+    std::memcpy(rects, rows.rects(base), S * 4 * sizeof(int32_t));
+    std::memcpy(valid, rows.valid(base), S * sizeof(int32_t));
+    const Results res = slot->host();
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (size_t s = 0; s < S; ++s) {
+        const int r = rows.row(base)[s];
+        const bool has = r >= 0 && r < M;
+        row[s] = has ? r : -1;
+        if (has) {
+            std::memcpy(ypr + s * 3, res.ypr + size_t(r) * 3, 3 * sizeof(float));
+            if (argmax) std::memcpy(argmax + s * 3, res.amax + size_t(r) * 3, 3 * sizeof(int32_t));
+            if (logits) std::memcpy(logits + s * N_LOGITS, res.logits + size_t(r) * N_LOGITS, N_LOGITS * sizeof(float));
+        } else {
+            std::fill(ypr + s * 3, ypr + s * 3 + 3, nan);
+            if (argmax) std::fill(argmax + s * 3, argmax + s * 3 + 3, -1);
+            if (logits) std::fill(logits + s * N_LOGITS, logits + (s + 1) * N_LOGITS, nan);
+        }
+    }
+    slot->busy = false;
+    slot->clip_cap = -1;
+    slot->clip_f = 0;
+}
+
+void Engine::op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
+                             int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(valid && count && row && slot_of_row && rows_used && overflow, WHENET_EINVAL, "op_head_compact: NULL argument");
+    WHENET_REQUIRE(frames >= 1 && frames <= 1024 && slots_per_frame >= 1 && slots_per_frame <= 1024 &&
+                       frames * slots_per_frame <= HEAD_COMPACT_MAX_SLOTS && max_heads >= 1 && max_heads <= 256,
+                   WHENET_EINVAL, "op_head_compact: frames x slots must be 1..1024 and max_heads 1..256");
+    const size_t S = size_t(frames) * slots_per_frame;
+    TempBufs tmp;
+    int32_t* const d_valid = static_cast<int32_t*>(tmp.get(S * sizeof(int32_t)));
+    int32_t* const d_count = static_cast<int32_t*>(tmp.get(size_t(frames) * sizeof(int32_t)));
+    int32_t* const d_row = static_cast<int32_t*>(tmp.get(S * sizeof(int32_t)));
+    int32_t* const d_sor = static_cast<int32_t*>(tmp.get(size_t(max_heads) * sizeof(int32_t)));
+    int32_t* const d_two = static_cast<int32_t*>(tmp.get(2 * sizeof(int32_t)));
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_valid, valid, S * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_count, count, size_t(frames) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    launch_head_compact(d_valid, d_count, frames, slots_per_frame, max_heads, d_row, d_sor, d_two, d_two + 1, stream_);
+    int32_t two[2] = {0, 0};
+    WHENET_HIP_CHECK(hipMemcpyAsync(row, d_row, S * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot_of_row, d_sor, size_t(max_heads) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipMemcpyAsync(two, d_two, sizeof(two), hipMemcpyDeviceToHost, stream_));
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+    *rows_used = two[0], *overflow = two[1];
 }
 
 void Engine::op_head_plan(int fh, int fw, const float* boxes, int k, int32_t* rects, int32_t* valid, int32_t* plans) {

@@ -14,7 +14,9 @@
 // the per-class counts (at most 64 classes, uniform loads); lane 0 writes the row's box / score / class / window / valid
 // flag; lanes 0..223 each write one entry of the six 224-entry tables (xofs | a0 | a1 | yofs | b0 | b1); the first column
 // that reads a single sample (xmax) is an LDS atomic minimum.  A row beyond the detection count, or one whose window is
-// empty or leaves the frame, gets valid = 0 and a plan of zeros: the crop kernel skips it.
+// empty or leaves the frame, gets valid = 0 and a plan of zeros: the crop kernel skips it.  The frames of a clip (one size)
+// are the grid's second dimension; whenet_head_compact_kernel then numbers the clip's live heads so that the forward runs
+// over them alone.
 #include <climits>
 
 #include "kernels.h"
@@ -90,13 +92,16 @@ __device__ __forceinline__ bool axis_entry(int src, bool horizontal, int d, int3
 
 __global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
     __shared__ int s_xmax;
-    const int row = blockIdx.x, tid = threadIdx.x;
+    const int slot = blockIdx.x, tid = threadIdx.x;         // detection slot of its frame
+    const size_t f = blockIdx.y;                            // frame of a clip: inputs [F][C]..., outputs [F][K]..., count [F]
+    const size_t row = f * (size_t(a.num_classes) * a.max_boxes) + slot;
+    const int* in_count = a.in_count + f * a.num_classes;
     // class-by-class concatenation (yolo_v3/model.py:227-229): row -> (class, position in the class)
     int cls = -1, pos = 0, total = 0;
     for (int c = 0; c < a.num_classes; ++c) {
-        int n = a.in_count[c];
+        int n = in_count[c];
         n = n < 0 ? 0 : (n > a.max_boxes ? a.max_boxes : n);
-        if (cls < 0 && row < total + n) cls = c, pos = row - total;
+        if (cls < 0 && slot < total + n) cls = c, pos = slot - total;
         total += n;
     }
     if (tid == 0) s_xmax = OUT;
@@ -105,31 +110,31 @@ __global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
     int32_t rect[4] = {0, 0, 0, 0};
     bool ok = false;
     if (cls >= 0) {
-        const size_t src = size_t(cls) * a.max_boxes + pos;
+        const size_t src = (f * a.num_classes + size_t(cls)) * a.max_boxes + pos;
         const float* b = a.in_boxes + src * 4;
         const float b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
         box_rect(a.frame_h, a.frame_w, b0, b1, b2, b3, rect);
         ok = rect[0] >= 0 && rect[1] >= 0 && rect[2] <= a.frame_h && rect[3] <= a.frame_w && rect[0] < rect[2] && rect[1] < rect[3];
         if (tid == 0) {
-            float* ob = a.boxes + size_t(row) * 4;
+            float* ob = a.boxes + row * 4;
             ob[0] = b0, ob[1] = b1, ob[2] = b2, ob[3] = b3;
             a.scores[row] = a.in_scores ? a.in_scores[src] : 0.0f;
             a.classes[row] = cls;
         }
     } else if (tid == 0) {
-        float* ob = a.boxes + size_t(row) * 4;
+        float* ob = a.boxes + row * 4;
         ob[0] = ob[1] = ob[2] = ob[3] = 0.0f;
         a.scores[row] = 0.0f;
         a.classes[row] = -1;
     }
     if (tid == 0) {
-        int32_t* orc = a.rects + size_t(row) * 4;
+        int32_t* orc = a.rects + row * 4;
         orc[0] = rect[0], orc[1] = rect[1], orc[2] = rect[2], orc[3] = rect[3];
         a.valid[row] = ok ? 1 : 0;
-        if (row == 0) *a.count = total;
+        if (slot == 0) a.count[f] = total;
     }
     if (a.plans == nullptr) return;
-    int32_t* P = a.plans + size_t(row) * CROP_PLAN_INTS;
+    int32_t* P = a.plans + row * CROP_PLAN_INTS;
     if (!ok) {
         for (int i = tid; i < CROP_PLAN_INTS; i += 256) P[i] = 0;
         return;
@@ -149,11 +154,66 @@ __global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
     }
 }
 
+// Compaction of a clip's heads (kernels.h): lane s owns slot s.  A wave's ballot numbers its live slots, the 16 wave totals
+// go through LDS, every lane adds the totals of the waves before its own: an exclusive scan in slot order, the same on every
+// run.  Rows from rows_used on get slot -1; no two lanes write the same word.
+__global__ __launch_bounds__(HEAD_COMPACT_MAX_SLOTS) void whenet_head_compact_kernel(const int32_t* __restrict__ valid,
+                                                                                     const int32_t* __restrict__ count, int frames,
+                                                                                     int K, int max_heads, int32_t* __restrict__ row,
+                                                                                     int32_t* __restrict__ slot_of_row,
+                                                                                     int32_t* __restrict__ rows_used,
+                                                                                     int32_t* __restrict__ overflow) {
+    __shared__ int s_wave[HEAD_COMPACT_MAX_SLOTS / 64];
+    const int s = threadIdx.x, slots = frames * K;
+    bool live = false;
+    if (s < slots) {
+        const int f = s / K, i = s - f * K;
+        int n = count[f];
+        n = n < 0 ? 0 : (n > K ? K : n);
+        live = i < n && valid[s] != 0;
+    }
+    const unsigned long long ballot = __ballot(live);
+    const int lane = s & 63, wave = s >> 6;
+    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wave[wave] = __popcll(ballot);
+    __syncthreads();
+    int base = 0, total = 0;
+    for (int w = 0; w < HEAD_COMPACT_MAX_SLOTS / 64; ++w) {
+        const int n = s_wave[w];
+        if (w < wave) base += n;
+        total += n;
+    }
+    const int used = total < max_heads ? total : max_heads;
+    if (s < slots) {
+        const int r = base + before;
+        const bool placed = live && r < max_heads;
+        row[s] = placed ? r : -1;
+        if (placed) slot_of_row[r] = s;
+    }
+    for (int r = used + s; r < max_heads; r += HEAD_COMPACT_MAX_SLOTS) slot_of_row[r] = -1;
+    if (s == 0) {
+        *rows_used = used;
+        *overflow = total - used;
+    }
+}
+
 }  // namespace
 
 void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream) {
-    WHENET_REQUIRE(a.num_classes >= 1 && a.max_boxes >= 1 && a.frame_h > 0 && a.frame_w > 0, WHENET_EINVAL, "head_plan: bad sizes");
-    hipLaunchKernelGGL(whenet_head_plan_kernel, dim3(unsigned(a.num_classes) * unsigned(a.max_boxes)), dim3(256), 0, stream, a);
+    WHENET_REQUIRE(a.num_classes >= 1 && a.max_boxes >= 1 && a.frame_h > 0 && a.frame_w > 0 && a.frames >= 0 && a.frames <= 65535,
+                   WHENET_EINVAL, "head_plan: bad sizes");
+    hipLaunchKernelGGL(whenet_head_plan_kernel, dim3(unsigned(a.num_classes) * unsigned(a.max_boxes), a.frames > 1 ? unsigned(a.frames) : 1u),
+                       dim3(256), 0, stream, a);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+void launch_head_compact(const int32_t* d_valid, const int32_t* d_count, int frames, int slots_per_frame, int max_heads, int32_t* d_row,
+                         int32_t* d_slot_of_row, int32_t* d_rows_used, int32_t* d_overflow, hipStream_t stream) {
+    WHENET_REQUIRE(frames >= 1 && slots_per_frame >= 1 && size_t(frames) * size_t(slots_per_frame) <= size_t(HEAD_COMPACT_MAX_SLOTS) &&
+                       max_heads >= 1,
+                   WHENET_EINVAL, "head_compact: frames x slots must be 1.." + std::to_string(HEAD_COMPACT_MAX_SLOTS) + " and max_heads >= 1");
+    hipLaunchKernelGGL(whenet_head_compact_kernel, dim3(1), dim3(HEAD_COMPACT_MAX_SLOTS), 0, stream, d_valid, d_count, frames,
+                       slots_per_frame, max_heads, d_row, d_slot_of_row, d_rows_used, d_overflow);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

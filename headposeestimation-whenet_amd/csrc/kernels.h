@@ -370,7 +370,7 @@ std::string kernel_name_mb7(int k, int Cout, bool skip);
 // ---- yolo.hip ---------------------------------------------------------------------------
 // YOLOv3 post-processing (yolo_v3/model.py:125-232): decode + score threshold + per-class NMS.
 struct YoloLayer {
-    const float* feats;    // device [gh][gw][A*(5+C)]
+    const float* feats;    // device [gh][gw][A*(5+C)] (a batch: [images][gh][gw][A*(5+C)])
     int gh, gw;
     int first;             // index of this layer's first box in the concatenated list
     float anchor[3][2];    // (w, h) of the layer's anchors (anchor_mask applied)
@@ -383,6 +383,7 @@ struct YoloArgs {
     float off_y, off_x, scale_y, scale_x;  // letterbox correction (model.py:160-162), float32 as the graph computes it
     float score_thr, iou_thr;
     int max_boxes;
+    int images;                            // 0 / 1: one image; F: every array below has a leading [F] axis (grid dimension y)
     float* boxes;                          // [N][4] y_min, x_min, y_max, x_max
     float* all_scores;                     // [N][C] or nullptr (tests)
     int* counts;                           // [C]
@@ -407,6 +408,10 @@ void launch_crop_resize(const uint8_t* d_frame, int fw, int swap_rb, const int32
 // (headplan.hip writes both); every other row is filled with zero bytes.  Valid rows: the arithmetic above, unchanged.
 void launch_crop_resize_masked(const uint8_t* d_frame, int fw, int swap_rb, const int32_t* d_plan, int k, const int32_t* d_valid,
                                const int32_t* d_count, uint8_t* d_out, hipStream_t stream);
+// The gathering form over the frames of a clip [F][fh][fw][3]: output row r is the crop of slot s = d_slot_of_row[r] (headplan.hip's
+// compaction) with plan d_plan[s], cut from frame s / slots_per_frame; a row with s < 0 is filled with zero bytes.
+void launch_crop_resize_gather(const uint8_t* d_frames, size_t frame_bytes, int fw, int swap_rb, const int32_t* d_plan, int slots_per_frame,
+                               const int32_t* d_slot_of_row, int rows, uint8_t* d_out, hipStream_t stream);
 
 // ---- headplan.hip -----------------------------------------------------------------------
 // The detector's selected boxes (yolo.hip's out_boxes / out_scores / out_count, left where launch_yolo_eval wrote them) ->
@@ -418,6 +423,7 @@ struct HeadPlanArgs {
     const int* in_count;       // [C]
     int num_classes, max_boxes;
     int frame_h, frame_w;
+    int frames;                // 0 / 1: one frame; F: inputs [F][C]..., outputs [F][K]..., count [F] (grid dimension y), one frame size
     // outputs over the capacity K = C * max_boxes; rows from *count on: zeros, class -1, valid 0
     float* boxes;              // [K][4]
     float* scores;             // [K]
@@ -428,6 +434,12 @@ struct HeadPlanArgs {
     int32_t* plans;            // [K][CROP_PLAN_INTS] or nullptr; zeros where valid is 0
 };
 void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream);
+// Compaction of a clip's heads: slot s = f * K + i (s < F * K <= 1024) is LIVE iff valid[s] != 0 and i < count[f].  The r-th
+// live slot in slot order gets row[s] = r if r < max_heads; every other slot gets row -1.  slot_of_row [max_heads] is the
+// inverse (-1: an empty row), *rows_used = min(live, max_heads), *overflow = live - *rows_used.  One workgroup, no atomics.
+constexpr int HEAD_COMPACT_MAX_SLOTS = 1024;
+void launch_head_compact(const int32_t* d_valid, const int32_t* d_count, int frames, int slots_per_frame, int max_heads, int32_t* d_row,
+                         int32_t* d_slot_of_row, int32_t* d_rows_used, int32_t* d_overflow, hipStream_t stream);
 
 // ---- letterbox.hip ----------------------------------------------------------------------
 // The detector's pre-processing (yolo_v3/utils.py:23-34, yolo_postprocess.py:186-196): Pillow-exact BICUBIC resize at
@@ -450,6 +462,10 @@ void letterbox_float_table(float lut[256]);
 void launch_letterbox(const uint8_t* d_frame, const LetterboxPlan& p, int swap_rb, const int32_t* d_tables,
                       const float* d_lut, uint8_t* d_mid, uint8_t* d_canvas_u8, float* d_image_f32, int num_cus,
                       hipStream_t stream);
+// the frames of a clip [F][ih][iw][3] (p: ONE frame's plan) -> canvases [F][oh][ow][3]; d_mid holds F * ih * nw * 3 bytes
+void launch_letterbox_batch(const uint8_t* d_frames, int frames, const LetterboxPlan& p, int swap_rb, const int32_t* d_tables,
+                            const float* d_lut, uint8_t* d_mid, uint8_t* d_canvas_u8, float* d_image_f32, int num_cus,
+                            hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC binary16 activations: implicit-GEMM convolution on the f16

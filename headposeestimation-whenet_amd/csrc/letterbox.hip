@@ -79,13 +79,10 @@ __global__ __launch_bounds__(THREADS) void whenet_letterbox_h_kernel(const uint8
 
 // Vertical pass + paste + /255: mid [ih][nw][3] -> canvas [oh][ow][3] (uint8 and / or float32).  One thread per canvas
 // byte, adjacent threads on adjacent bytes of a row; it walks the n source rows of its output row.
-__global__ __launch_bounds__(THREADS) void whenet_letterbox_v_kernel(const uint8_t* __restrict__ mid, LetterboxPlan p,
-                                                                     const int32_t* __restrict__ tab,
-                                                                     const float* __restrict__ lut,
-                                                                     uint8_t* __restrict__ canvas_u8,
-                                                                     float* __restrict__ image_f32) {
-    const int oy = blockIdx.y;
-    const int ob = blockIdx.x * THREADS + threadIdx.x;
+// one canvas byte of the vertical pass: output row oy, byte ob of the row
+__device__ __forceinline__ void letterbox_v_byte(const uint8_t* __restrict__ mid, const LetterboxPlan& p, const int32_t* __restrict__ tab,
+                                                 const float* __restrict__ lut, uint8_t* __restrict__ canvas_u8,
+                                                 float* __restrict__ image_f32, int oy, int ob) {
     const int row_out = p.ow * 3;
     if (ob >= row_out) return;
     const int mid_row = p.nw * 3;
@@ -103,6 +100,27 @@ __global__ __launch_bounds__(THREADS) void whenet_letterbox_v_kernel(const uint8
     const size_t o = size_t(oy) * row_out + ob;
     if (canvas_u8) canvas_u8[o] = uint8_t(v);
     if (image_f32) image_f32[o] = lut[v];
+}
+
+__global__ __launch_bounds__(THREADS) void whenet_letterbox_v_kernel(const uint8_t* __restrict__ mid, LetterboxPlan p,
+                                                                     const int32_t* __restrict__ tab,
+                                                                     const float* __restrict__ lut,
+                                                                     uint8_t* __restrict__ canvas_u8,
+                                                                     float* __restrict__ image_f32) {
+    letterbox_v_byte(mid, p, tab, lut, canvas_u8, image_f32, blockIdx.y, blockIdx.x * THREADS + threadIdx.x);
+}
+
+// The same over the frames of a clip (grid z): frame f reads mid + f * ih * nw * 3 and writes canvas f of [F][oh][ow][3].
+// p is the plan of ONE frame; every frame shares its tables.
+__global__ __launch_bounds__(THREADS) void whenet_letterbox_v_batch_kernel(const uint8_t* __restrict__ mid, LetterboxPlan p,
+                                                                           const int32_t* __restrict__ tab,
+                                                                           const float* __restrict__ lut,
+                                                                           uint8_t* __restrict__ canvas_u8,
+                                                                           float* __restrict__ image_f32) {
+    const size_t f = blockIdx.z;
+    const size_t mid_stride = size_t(p.ih) * p.nw * 3, out_stride = size_t(p.oh) * p.ow * 3;
+    letterbox_v_byte(mid + f * mid_stride, p, tab, lut, canvas_u8 ? canvas_u8 + f * out_stride : nullptr,
+                     image_f32 ? image_f32 + f * out_stride : nullptr, blockIdx.y, blockIdx.x * THREADS + threadIdx.x);
 }
 
 // Resample.c bicubic_filter
@@ -208,6 +226,25 @@ void launch_letterbox(const uint8_t* d_frame, const LetterboxPlan& p, int swap_r
     WHENET_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(whenet_letterbox_v_kernel, dim3((p.ow * 3 + THREADS - 1) / THREADS, p.oh), dim3(THREADS), 0, stream,
                        d_mid, p, d_tables, d_lut, d_canvas_u8, d_image_f32);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+// F frames [F][ih][iw][3] of one geometry -> canvases [F][oh][ow][3].  The horizontal pass is row-independent: the clip is
+// F * ih rows of one buffer (a frame's first byte need not be 16-byte aligned; neither is a row's), so it is the kernel above
+// with the row count of the whole clip.  d_mid holds F * ih * nw * 3 bytes.
+void launch_letterbox_batch(const uint8_t* d_frames, int frames, const LetterboxPlan& p, int swap_rb, const int32_t* d_tables,
+                            const float* d_lut, uint8_t* d_mid, uint8_t* d_canvas_u8, float* d_image_f32, int num_cus,
+                            hipStream_t stream) {
+    WHENET_REQUIRE(frames >= 1 && frames <= 65535, WHENET_EINVAL, "letterbox: bad frame count");
+    if (d_canvas_u8 == nullptr && d_image_f32 == nullptr) return;
+    LetterboxPlan rows = p;
+    rows.ih = p.ih * frames;
+    const int rows_wg = rows.ih < num_cus * 8 ? rows.ih : num_cus * 8;
+    hipLaunchKernelGGL(whenet_letterbox_h_kernel, dim3(rows_wg), dim3(THREADS), 0, stream, d_frames, rows, swap_rb, d_tables,
+                       d_mid);
+    WHENET_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(whenet_letterbox_v_batch_kernel, dim3((p.ow * 3 + THREADS - 1) / THREADS, p.oh, frames), dim3(THREADS), 0,
+                       stream, d_mid, p, d_tables, d_lut, d_canvas_u8, d_image_f32);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

@@ -6,6 +6,8 @@
 // inside sess.run (yolo_postprocess.py:198-204) on the detector's 2 or 3 output maps.  SURVEY.md §8f row 4.
 //
 // Mapping (gfx950).  The work is small (10,647 boxes for a 416x416 input) and branchy, so it is two launches:
+// A batch of images (a clip's frames) is the grid's second dimension of both launches: image f's maps, boxes, counters, keys
+// and outputs lie f strides behind image 0's, the arithmetic and the key order are those of one image.
 //   1. whenet_yolo_decode_kernel: one lane per box (layer, y, x, anchor), coalesced over the map.  It writes the
 //      corrected box (y_min, x_min, y_max, x_max in image pixels) to a dense [N][4] array and, for every class
 //      whose score = confidence * class probability passes the threshold, appends a 64-bit key
@@ -29,13 +31,14 @@ __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + ex
 __global__ __launch_bounds__(256) void whenet_yolo_decode_kernel(YoloArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.N) return;
+    const size_t img = blockIdx.y;                              // image of a batch: every array below is [images][...]
     int l = 0;
     while (l + 1 < a.num_layers && i >= a.layer[l + 1].first) ++l;
     const YoloLayer& L = a.layer[l];
     const int j = i - L.first;                                  // ((y * gw + x) * A + anchor)
     const int an = j % a.na, cell = j / a.na;
     const int y = cell / L.gw, x = cell - y * L.gw;
-    const float* t = L.feats + size_t(j) * (5 + a.num_classes);
+    const float* t = L.feats + (img * L.gh * L.gw * a.na + size_t(j)) * (5 + a.num_classes);
 
     // yolo_head (model.py:141-145)
     const float bx = __fdiv_rn(__fadd_rn(sigmoid_ref(t[0]), float(x)), float(L.gw));
@@ -52,14 +55,15 @@ __global__ __launch_bounds__(256) void whenet_yolo_decode_kernel(YoloArgs a) {
     box.y = __fmul_rn(__fsub_rn(cx, hx), a.image_w);
     box.z = __fmul_rn(__fadd_rn(cy, hy), a.image_h);
     box.w = __fmul_rn(__fadd_rn(cx, hx), a.image_w);
-    reinterpret_cast<float4*>(a.boxes)[i] = box;
+    reinterpret_cast<float4*>(a.boxes)[img * a.N + i] = box;
     // yolo_boxes_and_scores (model.py:188) + the mask of yolo_eval (model.py:212)
     for (int c = 0; c < a.num_classes; ++c) {
         const float score = __fmul_rn(conf, sigmoid_ref(t[5 + c]));
-        if (a.all_scores) a.all_scores[size_t(i) * a.num_classes + c] = score;
+        if (a.all_scores) a.all_scores[(img * a.N + i) * a.num_classes + c] = score;
         if (score >= a.score_thr) {
-            const int slot = atomicAdd(&a.counts[c], 1);
-            a.keys[size_t(c) * a.NP + slot] =
+            const size_t ic = img * a.num_classes + c;
+            const int slot = atomicAdd(&a.counts[ic], 1);
+            a.keys[ic * a.NP + slot] =
                 (static_cast<unsigned long long>(__float_as_uint(score)) << 32) | (0xffffffffu - unsigned(i));
         }
     }
@@ -85,13 +89,13 @@ constexpr int NMS_MAX_SELECT = 256;
 __global__ __launch_bounds__(NMS_THREADS) void whenet_yolo_nms_kernel(YoloArgs a) {
     __shared__ unsigned long long s_keys[NMS_LDS_KEYS];
     __shared__ float4 s_sel[NMS_MAX_SELECT];
-    const int c = blockIdx.x;
+    const size_t c = size_t(blockIdx.y) * a.num_classes + blockIdx.x;      // (image, class): every array below is [images][C]...
     const int tid = threadIdx.x;
     int n = a.counts[c];
     if (n > a.N) n = a.N;
     int P = 1;
     while (P < n) P <<= 1;
-    unsigned long long* gk = a.keys + size_t(c) * a.NP;
+    unsigned long long* gk = a.keys + c * a.NP;
     const bool in_lds = P <= NMS_LDS_KEYS;
     unsigned long long* k = in_lds ? s_keys : gk;           // (generic pointer: LDS or global)
     if (in_lds) {
@@ -118,10 +122,10 @@ __global__ __launch_bounds__(NMS_THREADS) void whenet_yolo_nms_kernel(YoloArgs a
     }
     if (tid >= 64) return;
     // greedy selection by wave 0
-    const float4* boxes = reinterpret_cast<const float4*>(a.boxes);
-    float* ob = a.out_boxes + size_t(c) * a.max_boxes * 4;
-    float* os = a.out_scores + size_t(c) * a.max_boxes;
-    int* oi = a.out_index + size_t(c) * a.max_boxes;
+    const float4* boxes = reinterpret_cast<const float4*>(a.boxes) + size_t(blockIdx.y) * a.N;
+    float* ob = a.out_boxes + c * a.max_boxes * 4;
+    float* os = a.out_scores + c * a.max_boxes;
+    int* oi = a.out_index + c * a.max_boxes;
     int nsel = 0;
     for (int i = 0; i < n && nsel < a.max_boxes; ++i) {
         const unsigned long long key = k[i];
@@ -167,9 +171,10 @@ int yolo_max_select() { return NMS_MAX_SELECT; }
 void launch_yolo_eval(const YoloArgs& a, hipStream_t stream) {
     WHENET_REQUIRE(a.N > 0 && a.num_classes > 0 && a.max_boxes > 0 && a.max_boxes <= a.N, WHENET_EINVAL,
                    "yolo_eval: bad sizes (max_boxes must be 1..number of boxes)");
-    WHENET_HIP_CHECK(hipMemsetAsync(a.counts, 0, size_t(a.num_classes) * sizeof(int), stream));
-    hipLaunchKernelGGL(whenet_yolo_decode_kernel, dim3((a.N + 255) / 256), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(whenet_yolo_nms_kernel, dim3(a.num_classes), dim3(NMS_THREADS), 0, stream, a);
+    const unsigned images = a.images > 1 ? unsigned(a.images) : 1u;
+    WHENET_HIP_CHECK(hipMemsetAsync(a.counts, 0, size_t(images) * a.num_classes * sizeof(int), stream));
+    hipLaunchKernelGGL(whenet_yolo_decode_kernel, dim3((a.N + 255) / 256, images), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(whenet_yolo_nms_kernel, dim3(a.num_classes, images), dim3(NMS_THREADS), 0, stream, a);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

@@ -76,6 +76,15 @@ _PROTOS = {
     "whenet_collect_detect": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, _P, _P, _P, _P, _P]),
     "whenet_op_head_plan": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "whenet_crop_plan": (C.c_int, [_P, _P]),
+    "whenet_clip_begin": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "whenet_clip_detect_heads": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                           C.POINTER(C.c_int)]),
+    "whenet_collect_clip": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "whenet_op_letterbox_batch": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_yolo_eval_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
+    "whenet_op_head_compact": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -114,6 +123,36 @@ def load() -> C.CDLL:
 
 
 RGB, BGR = 0, 1
+MAX_CLIP_FRAMES = 16      # the detector's batch limit
+MAX_CLIP_SLOTS = 1024     # frames x classes x max_boxes of a clip
+MAX_CLIP_HEADS = 256      # rows of a clip's forward
+
+
+def clip_u8(frames) -> np.ndarray:
+    """The frames of a clip as ONE contiguous uint8 [F,H,W,3] block: an array of that shape, or a list of uint8 [H,W,3] frames of
+    one shape (stacked here).  ValueError for frames of different shapes or dtypes, and for F outside 1..16."""
+    if isinstance(frames, np.ndarray):
+        a = frames
+    else:
+        items = [np.asarray(f) for f in frames]
+        if not 1 <= len(items) <= MAX_CLIP_FRAMES:
+            raise ValueError(f"a clip holds 1..{MAX_CLIP_FRAMES} frames, got {len(items)}")
+        for f in items:
+            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError(f"frame must be uint8 [H,W,3], got {f.dtype} {f.shape}")
+            if f.shape != items[0].shape:
+                raise ValueError(f"the frames of a clip have one size: got {items[0].shape} and {f.shape}")
+        a = np.stack(items)
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3 or a.shape[1] < 1 or a.shape[2] < 1:
+        raise ValueError(f"a clip must be uint8 [F,H,W,3], got {a.dtype} {a.shape}")
+    if not 1 <= a.shape[0] <= MAX_CLIP_FRAMES:
+        raise ValueError(f"a clip holds 1..{MAX_CLIP_FRAMES} frames, got {a.shape[0]}")
+    return np.ascontiguousarray(a)
+
+
+def check_max_heads(max_heads) -> None:
+    if max_heads is not None and not 1 <= int(max_heads) <= MAX_CLIP_HEADS:
+        raise ValueError(f"max_heads must be 1..{MAX_CLIP_HEADS}, got {max_heads}")
 
 
 def as_uint8_crops(img) -> np.ndarray:
@@ -484,6 +523,101 @@ class Handle:
                                                     _ptr(rects), _ptr(valid), _ptr(ypr), _ptr(am), _ptr(lg)))
         k = count.value
         return tuple(None if a is None else a[:k].copy() for a in (boxes, scores, classes, rects, valid, ypr, am, lg))
+
+    # ---- clips: F frames per submission ----------------------------------------------------------
+    def clip_begin(self, frames: np.ndarray, bgr: bool = True) -> int:
+        """Upload the F frames of a clip (uint8 [F,H,W,3], one size) once; the ticket goes to clip_detect_heads / collect_clip."""
+        frames = clip_u8(frames)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin(self._h, _ptr(frames), frames.shape[0], frames.shape[1], frames.shape[2],
+                                                BGR if bgr else RGB, C.byref(t)))
+        return t.value
+
+    def clip_detect_heads(self, ticket: int, anchors, num_classes: int, size=(416, 416), score: float = .3, iou: float = .45,
+                          max_boxes: int = 20, max_heads=None) -> int:
+        """frame_detect_heads over the frames of the clip of `ticket` as ONE enqueue-only submission whose forward runs over
+        `max_heads` rows (None: min(F * K, 256)); returns K, the detection slots per frame."""
+        check_max_heads(max_heads)
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 2)
+        k = C.c_int(0)
+        self._check(self._lib.whenet_clip_detect_heads(self._h, int(ticket), int(size[0]), int(size[1]), _ptr(anchors), anchors.shape[0],
+                                                       float(score), float(iou), int(max_boxes), 0 if max_heads is None else int(max_heads),
+                                                       C.byref(k)))
+        return k.value
+
+    def collect_clip(self, ticket: int, frames: int, slots_per_frame: int, want_logits: bool = False):
+        """A `clip_detect_heads` ticket -> (counts [F], boxes [F,K,4], scores [F,K], classes [F,K], rects [F,K,4], valid [F,K],
+        row [F,K], ypr [F,K,3], argmax [F,K,3], logits [F,K,252] or None, rows_used, overflow): slot (f, i) is detection i of frame
+        f; row -1 (no window, beyond counts[f], or over max_heads): NaN / -1 / NaN."""
+        F, K = int(frames), int(slots_per_frame)
+        S = F * K
+        counts = np.zeros(16, np.int32)
+        boxes, scores, classes = np.empty((S, 4), np.float32), np.empty(S, np.float32), np.empty(S, np.int32)
+        rects, valid, row = np.empty((S, 4), np.int32), np.empty(S, np.int32), np.empty(S, np.int32)
+        ypr, am = np.empty((S, 3), np.float32), np.empty((S, 3), np.int32)
+        lg = np.empty((S, 252), np.float32) if want_logits else None
+        nf, used, over = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.whenet_collect_clip(self._h, int(ticket), S, C.byref(nf), _ptr(counts), _ptr(boxes), _ptr(scores),
+                                                  _ptr(classes), _ptr(rects), _ptr(valid), _ptr(row), _ptr(ypr), _ptr(am), _ptr(lg),
+                                                  C.byref(used), C.byref(over)))
+        if nf.value != F:
+            raise ValueError(f"collect_clip: the clip holds {nf.value} frames, not {F}")
+        shaped = tuple(None if a is None else a.reshape((F, K) + a.shape[1:]) for a in (boxes, scores, classes, rects, valid, row, ypr, am, lg))
+        return (counts[:F].copy(),) + shaped + (used.value, over.value)
+
+    def op_letterbox_batch(self, frames: np.ndarray, size=(416, 416), bgr: bool = True, want_u8: bool = True, want_f32: bool = True):
+        """`op_letterbox` of the F frames of a clip (uint8 [F,H,W,3]) in one call: (canvas uint8 [F,h,w,3], image float32 [F,h,w,3])."""
+        frames = clip_u8(frames)
+        F = frames.shape[0]
+        oh, ow, _, _ = self._letterbox_outputs(size, False, False)
+        u8 = np.empty((F, oh, ow, 3), np.uint8) if want_u8 else None
+        f32 = np.empty((F, oh, ow, 3), np.float32) if want_f32 else None
+        self._check(self._lib.whenet_op_letterbox_batch(self._h, _ptr(frames), F, frames.shape[1], frames.shape[2], BGR if bgr else RGB,
+                                                        oh, ow, _ptr(u8), _ptr(f32)))
+        return u8, f32
+
+    def yolo_eval_batch(self, yolo_outputs, anchors, num_classes: int, image_shape, max_boxes: int = 20,
+                        score_threshold: float = .6, iou_threshold: float = .5):
+        """`yolo_eval` of F images that share a shape: maps [F, gh, gw, 3*(5+C)] per layer -> a list of F tuples
+        (boxes [k,4], scores [k], classes [k], index [k]), each what `yolo_eval(..., debug=True)[:4]` returns for that image alone."""
+        maps = [np.ascontiguousarray(m, np.float32) for m in yolo_outputs]
+        F = maps[0].shape[0] if maps and maps[0].ndim == 4 else 0
+        for m in maps:
+            if m.ndim != 4 or m.shape[0] != F or m.shape[3] != 3 * (5 + num_classes):
+                raise ValueError(f"yolo_eval_batch: feature map of shape {m.shape}, expected [{F}, gh, gw, {3 * (5 + num_classes)}]")
+        if not 1 <= F <= MAX_CLIP_FRAMES:
+            raise ValueError(f"yolo_eval_batch: {F} images, expected 1..{MAX_CLIP_FRAMES}")
+        if max_boxes < 1:
+            raise ValueError("yolo_eval_batch: max_boxes must be >= 1")
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 2)
+        L = len(maps)
+        ptrs = (_P * L)(*[_ptr(m) for m in maps])
+        gh = np.array([m.shape[1] for m in maps], np.int32)
+        gw = np.array([m.shape[2] for m in maps], np.int32)
+        n_all = int(sum(m.shape[1] * m.shape[2] * 3 for m in maps))
+        cap = num_classes * min(int(max_boxes), n_all)
+        boxes, scores = np.empty((F, cap, 4), np.float32), np.empty((F, cap), np.float32)
+        classes, index, counts = np.empty((F, cap), np.int32), np.empty((F, cap), np.int32), np.zeros(F, np.int32)
+        self._check(self._lib.whenet_yolo_eval_batch(self._h, ptrs, F, _ptr(gh), _ptr(gw), L, _ptr(anchors), anchors.shape[0], num_classes,
+                                                     float(image_shape[0]), float(image_shape[1]), float(score_threshold),
+                                                     float(iou_threshold), int(max_boxes), _ptr(boxes), _ptr(scores), _ptr(classes),
+                                                     _ptr(index), _ptr(counts)))
+        return [tuple(a[f, :counts[f]].copy() for a in (boxes, scores, classes, index)) for f in range(F)]
+
+    def op_head_compact(self, valid, count, max_heads: int):
+        """The numbering of a clip's heads alone: valid int32 [F,K], count int32 [F] -> (row int32 [F,K], slot_of_row int32
+        [max_heads], rows_used, overflow)."""
+        valid = np.ascontiguousarray(valid, np.int32)
+        count = np.ascontiguousarray(count, np.int32).reshape(-1)
+        if valid.ndim != 2 or valid.shape[0] != count.shape[0]:
+            raise ValueError(f"op_head_compact: valid must be [F,K] and count [F], got {valid.shape} and {count.shape}")
+        check_max_heads(int(max_heads))
+        F, K = valid.shape
+        row, sor = np.empty((F, K), np.int32), np.empty(int(max_heads), np.int32)
+        used, over = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._check(self._lib.whenet_op_head_compact(self._h, _ptr(valid), _ptr(count), F, K, int(max_heads), _ptr(row), _ptr(sor),
+                                                     _ptr(used), _ptr(over)))
+        return row, sor, int(used[0]), int(over[0])
 
     def op_head_plan(self, frame_h: int, frame_w: int, boxes, want_plans: bool = True):
         """The window / crop plan kernel alone on caller boxes [k,4] (y_min, x_min, y_max, x_max), 1 <= k <= 2048:

@@ -21,7 +21,11 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     returns the boxes: a frame goes in, head boxes and head poses come out, with one library;
   * `detect_heads()` takes the place of `detect()` + `heads()`: the boxes stay on the device, a kernel turns them into windows and
     crop plans (`csrc/headplan.hip`), and the call returns as soon as everything is enqueued -- `begin; detect_heads; collect`
-    is one submission per frame, so with `depth` > 1 the next frame is begun and detected while this one is on the GPU.
+    is one submission per frame, so with `depth` > 1 the next frame is begun and detected while this one is on the GPU;
+  * a caller that has the next frames in hand (a video file, a rig of identical cameras) sends a CLIP: `begin_clip(frames)`,
+    `detect_heads_clip()`, `collect_clip()` put F frames of one size through letterbox, detector, selection, head plans, crops
+    and pose as one submission.  The heads that have a window are compacted on the device, so the forward runs over
+    `max_heads` rows, not over F x max_boxes; every frame's result is bit for bit what `begin; detect_heads; collect` returns.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -35,6 +39,33 @@ import numpy as np
 from . import _lib
 
 MAX_INFLIGHT = 4          # WHENET_MAX_INFLIGHT
+_CLIP = "clip"            # in the place of a pending entry's rects: the entry is (ticket, _CLIP, (frames, slots per frame))
+
+
+def clip_slots(size, anchors, num_classes: int, max_boxes: int) -> int:
+    """K of a clip: the detection slots per frame = num_classes x max_boxes, max_boxes cut to the number of boxes the detector's maps
+    hold for the input `size` (3 per cell, one map per three anchors, the coarsest 32 x smaller than the input)."""
+    if int(max_boxes) < 1:
+        raise ValueError("max_boxes must be >= 1")
+    layers = len(np.asarray(anchors).reshape(-1, 2)) // 3
+    held = sum(((int(size[0]) // 32) << l) * ((int(size[1]) // 32) << l) * 3 for l in range(layers))
+    return int(num_classes) * min(int(max_boxes), max(held, 1))
+
+
+def scatter_clip(counts, boxes, scores, classes, rects, valid, row, ypr, detections: bool = False):
+    """The per-frame results of a clip from its slot arrays ([F,K,...] as `Handle.collect_clip` returns them): for frame f a tuple
+    shaped like `collect()` -- (rects [k,4], yaw, pitch, roll) of the heads among its first counts[f] slots that have a window
+    (valid) AND a forward row (row >= 0) -- and with `detections` also (boxes [n,4], scores [n], classes [n], valid [n]) of all
+    n = counts[f] detections."""
+    out = []
+    for f, n in enumerate(np.asarray(counts).tolist()):
+        keep = (valid[f, :n] != 0) & (row[f, :n] >= 0)
+        y = ypr[f, :n][keep]
+        res = (np.ascontiguousarray(rects[f, :n][keep]), y[:, 0].copy(), y[:, 1].copy(), y[:, 2].copy())
+        if detections:
+            res += (boxes[f, :n].copy(), scores[f, :n].copy(), classes[f, :n].copy(), valid[f, :n].copy())
+        out.append(res)
+    return out
 
 
 class FramePipeline:
@@ -58,6 +89,7 @@ class FramePipeline:
         self._pending: Deque[Tuple[int, object, int]] = deque()      # (ticket, rects, 0) or, from detect_heads, (ticket, None, capacity)
         self._detector = None
         self._begun = None         # (ticket, frame_h, frame_w) of the frame begun last, until its heads are enqueued
+        self._begun_clip = None    # (ticket, frames) of the clip begun last, until detect_heads_clip
 
     def __enter__(self):
         return self
@@ -65,8 +97,16 @@ class FramePipeline:
     def __exit__(self, *exc):
         if self._begun is not None:            # a frame without heads: released as a frame with none
             self.heads(np.zeros((0, 4), np.float32))
+        if self._begun_clip is not None:       # a clip without heads: released the same way
+            ticket = self._begun_clip[0]
+            self._begun_clip = None
+            self._h.frame_heads(ticket, np.zeros((0, 4), np.int32))
+            self._pending.append((ticket, np.zeros((0, 4), np.int32), 0))
         while self._pending:
-            self.collect()
+            if self._pending[0][1] is _CLIP:
+                self.collect_clip()
+            else:
+                self.collect()
 
     @property
     def in_flight(self) -> int:
@@ -89,6 +129,8 @@ class FramePipeline:
         places from here until its `collect()`; `heads()` must follow before the next `begin()` / `submit()`."""
         if self._begun is not None:
             raise ValueError("the frame begun last has no heads yet: heads() first")
+        if self._begun_clip is not None:
+            raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
         if len(self._pending) >= self._depth:
             raise ValueError(f"{self._depth} frames already in flight: collect() first")
         frame = np.asarray(frame)
@@ -97,12 +139,69 @@ class FramePipeline:
         ticket = self._h.frame_begin(frame, bgr=self._bgr)
         self._begun = (ticket, frame.shape[0], frame.shape[1])
 
+    def begin_clip(self, frames) -> None:
+        """A clip, step 1: upload F frames (1..16) of ONE size, a uint8 [F,H,W,3] array or a list of uint8 [H,W,3] frames (stacked
+        here), with one copy.  The clip holds one of the `depth` places until its `collect_clip()`; `detect_heads_clip()` must
+        follow before the next `begin()` / `begin_clip()` / `submit()`."""
+        if self._begun is not None:
+            raise ValueError("the frame begun last has no heads yet: heads() first")
+        if self._begun_clip is not None:
+            raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
+        if len(self._pending) >= self._depth:
+            raise ValueError(f"{self._depth} frames already in flight: collect() first")
+        frames = _lib.clip_u8(frames)
+        ticket = self._h.clip_begin(frames, bgr=self._bgr)
+        self._begun_clip = (ticket, frames.shape[0])
+
+    def _begun_frame(self, what: str):
+        """The frame begun last, for the calls that work on ONE frame."""
+        if self._begun is None:
+            if self._begun_clip is not None:
+                raise ValueError(f"{what}: a clip was begun last, not a frame: detect_heads_clip() enqueues it")
+            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        return self._begun
+
+    def detect_heads_clip(self, size=(416, 416), score=.3, iou=.45, max_boxes=20, anchors=None, num_classes=1, max_heads=None) -> None:
+        """A clip, step 2: `detect_heads()` of every frame of the clip begun last as ONE submission; returns as soon as the work is
+        enqueued.  Per frame there are K = num_classes x max_boxes detection slots, F x K <= 1024.  The heads that have a window are
+        numbered in (frame, detection) order and the first `max_heads` of them (1..256, default min(F x K, 256)) are the rows of one
+        forward; `collect_clip()` reports how many rows were used and how many heads overflowed."""
+        from .yolo import check_model_image_size
+        if self._begun_clip is None:
+            if self._begun is not None:
+                raise ValueError("detect_heads_clip: a single frame was begun last, not a clip: detect_heads() enqueues it")
+            raise ValueError("no clip begun (or its heads are already enqueued): begin_clip() first")
+        check_model_image_size(size)
+        _lib.check_max_heads(max_heads)
+        anchors, num_classes = self._anchors(anchors, num_classes)
+        ticket, F = self._begun_clip
+        K = clip_slots(size, anchors, num_classes, max_boxes)
+        if F * K > _lib.MAX_CLIP_SLOTS:
+            raise ValueError(f"detect_heads_clip: frames x classes x max_boxes = {F} x {K} must be 1..{_lib.MAX_CLIP_SLOTS}")
+        k = self._h.clip_detect_heads(ticket, anchors, num_classes, size, score, iou, max_boxes, max_heads)
+        self._begun_clip = None
+        self._pending.append((ticket, _CLIP, (F, k)))
+
+    def collect_clip(self, detections: bool = False):
+        """Oldest submission, a clip -> (frames, (rows_used, overflow)): `frames` is a list of F tuples shaped like `collect()` /
+        `collect(detections=True)`, one per frame of the clip, in which the heads are those with a window inside the frame AND a row
+        of the forward; `rows_used` = rows of the forward that held a head, `overflow` = heads with a window that got no row
+        (max_heads too small).  On a submission that is not a clip: ValueError, and it stays in flight."""
+        if not self._pending:
+            raise ValueError("nothing in flight")
+        ticket, kind, fk = self._pending[0]
+        if kind is not _CLIP:
+            raise ValueError("collect_clip: the oldest submission in flight is not a clip: collect() returns it")
+        res = self._h.collect_clip(ticket, fk[0], fk[1])
+        self._pending.popleft()
+        counts, boxes, scores, classes, rects, valid, row, ypr, _, _, used, over = res
+        return scatter_clip(counts, boxes, scores, classes, rects, valid, row, ypr, detections), (used, over)
+
     def detector_input(self, size=(416, 416), as_uint8: bool = False) -> np.ndarray:
         """Resident form, step 2 (any number of times): float32 [1, h, w, 3], the `image_data` YOLO.detect feeds to
         sess.run, cut from the frame begun last; `size` = (h, w) as `model_image_size`, multiples of 32."""
         from .yolo import check_model_image_size
-        if self._begun is None:
-            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        self._begun_frame("detector_input")
         check_model_image_size(size)
         u8, f32 = self._h.frame_letterbox(self._begun[0], size, want_u8=as_uint8, want_f32=not as_uint8)
         return u8 if as_uint8 else f32[None]
@@ -113,8 +212,7 @@ class FramePipeline:
         and `num_classes` default to those of the `whenet_hip.detector.YOLO` that loaded the detector on this handle (or the
         one given to `attach_detector`)."""
         from .yolo import check_model_image_size
-        if self._begun is None:
-            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        self._begun_frame("detect")
         check_model_image_size(size)
         anchors, num_classes = self._anchors(anchors, num_classes)
         return self._h.frame_detect(self._begun[0], anchors, num_classes, size, score, iou, max_boxes)
@@ -133,8 +231,7 @@ class FramePipeline:
         `collect(detections=True)` the detector's boxes as well.  num_classes x max_boxes <= 64: every slot is a crop of the forward
         (few heads in a large `max_boxes` pay for the padding; `detect()` + `heads()` run the forward at the head count)."""
         from .yolo import check_model_image_size
-        if self._begun is None:
-            raise ValueError("no frame begun (or its heads are already enqueued): begin() first")
+        self._begun_frame("detect_heads")
         check_model_image_size(size)
         anchors, num_classes = self._anchors(anchors, num_classes)
         ticket = self._begun[0]
@@ -150,6 +247,8 @@ class FramePipeline:
     def heads(self, bboxes) -> None:
         """Resident form, step 3: the detector's boxes of the frame begun last (an empty list is fine) -> margins,
         crops, one batched forward, exactly as `submit()`; `collect()` returns them in order with the submitted frames."""
+        if self._begun is None and self._begun_clip is not None:
+            raise ValueError("heads: a clip was begun last, not a frame: detect_heads_clip() enqueues it")
         if self._begun is None:
             raise ValueError("no frame begun: begin() first")
         ticket, fh, fw = self._begun
@@ -166,6 +265,8 @@ class FramePipeline:
         if not self._pending:
             raise ValueError("nothing in flight")
         ticket, rects, cap = self._pending[0]
+        if rects is _CLIP:
+            raise ValueError("collect: the oldest submission in flight is a clip: collect_clip() returns it")
         if rects is None:
             boxes, scores, classes, rects, valid, ypr, _, _ = self._h.collect_detect(ticket, cap)
             self._pending.popleft()

@@ -41,7 +41,9 @@ extern "C" {
  * (round 6, still 4 -- options only: mb7, f2s_mask, se_fuse = 3, fanout_engines, fanout_stage = 2 | 3; the fan-out's default form is 2.)
  * (round 7, still 4 -- option act_layout.)
  * 5 (round 8): whenet_letterbox_plan, whenet_op_letterbox and the resident-frame form whenet_frame_begin / whenet_frame_letterbox /
- * whenet_frame_heads.  (Additions only: a version-4 caller runs unchanged.) */
+ * whenet_frame_heads.  (Additions only: a version-4 caller runs unchanged.)
+ * (still 6 -- clips: whenet_clip_begin / whenet_clip_detect_heads / whenet_collect_clip, whenet_op_letterbox_batch,
+ * whenet_yolo_eval_batch, whenet_op_head_compact.  Additions only.) */
 #define WHENET_ABI_VERSION 6
 #define WHENET_API __attribute__((visibility("default")))
 
@@ -400,6 +402,54 @@ WHENET_API int whenet_collect_detect(whenet_t* h, int ticket, int capacity, int*
 WHENET_API int whenet_op_head_plan(whenet_t* h, int frame_h, int frame_w, const float* boxes, int k, int32_t* rects, int32_t* valid,
                         int32_t* plans);
 WHENET_API int whenet_crop_plan(const int32_t rect[4], int32_t* plan);
+
+/* ---- CLIPS: several frames per submission (additions to ABI 6).  A caller that reads a video file or a rig of identical
+ * cameras has the next frames in hand; a clip sends F of them, 1 <= F <= 16, all of one size and channel order, through
+ * letterbox, detector, selection, head plans, crops and pose as ONE submission.  Every frame's results are bit for bit those of
+ * whenet_frame_begin + whenet_frame_detect_heads + whenet_collect_detect on that frame alone.
+ *   whenet_clip_begin  stands for F iterations of `ret, frame = cap.read()` (demo_video.py:49-53): frames uint8
+ *                  [F][frame_h][frame_w][3] contiguous; one pinned staging copy, one asynchronous H2D; hands out the ticket and holds
+ *                  one submission slot like whenet_frame_begin.  A clip that never gets its heads is released by
+ *                  whenet_frame_heads(h, ticket, NULL, 0) + whenet_collect.
+ *   whenet_clip_detect_heads  stands for F iterations of demo_video.py:54-58 (YOLO.detect, then process_detection per box):
+ *                  ENQUEUE-ONLY like whenet_frame_detect_heads, arguments as there.  Per frame there are
+ *                  *slots_per_frame = K = classes x max_boxes detection slots (max_boxes cut to the number of boxes the maps hold);
+ *                  F x K <= 1024.  The heads that have a window inside the frame are numbered in (frame, detection) order and the
+ *                  r-th of them becomes row r of ONE forward over max_heads rows, 1..256 (0 = min(F x K, 256)); rows without a head
+ *                  are zero crops, heads beyond max_heads are counted in *overflow and get no result.
+ *   whenet_collect_clip  waits once.  Arrays over F x K slots, slot (f, i) at f * K + i: boxes [.][4], scores, classes, rects [.][4],
+ *                  valid as whenet_collect_detect returns them for frame f (slots from counts[f] on: zeros, class -1, valid 0);
+ *                  row [.] = the slot's forward row or -1 (no window, beyond the count, or over max_heads); ypr [.][3], argmax [.][3],
+ *                  logits [.][252] (the last two may be NULL) = the row's results, NaN / -1 / NaN where row is -1.  counts [F],
+ *                  *num_frames = F, *rows_used = forward rows that hold a head, *overflow = heads that got none.  `capacity` = slots the
+ *                  arrays hold, at least F x K; counts holds 16.  WHENET_EINVAL for a ticket whenet_clip_detect_heads did not submit;
+ *                  whenet_collect and whenet_collect_detect answer a clip ticket the same way.  Errors leave the ticket collectable.
+ * whenet_frame_letterbox / _heads (k > 0) / _detect / _detect_heads on a clip ticket and whenet_clip_detect_heads on a frame
+ * ticket are WHENET_EINVAL; the handle stays usable.
+ *   whenet_op_letterbox_batch  letterbox_image (yolo_v3/utils.py:23-34, yolo_postprocess.py:186-196) of F host frames
+ *                  [F][frame_h][frame_w][3] -> canvas_u8 [F][out_h][out_w][3] and / or image_f32, as whenet_op_letterbox per frame
+ *   whenet_yolo_eval_batch  yolo_eval (yolo_v3/model.py:193-232) of num_images images that share shape and thresholds: feats[l] =
+ *                  host map [num_images][grid_h][grid_w][3*(5+C)]; with M = min(max_boxes, boxes the maps hold), image f's
+ *                  detections are rows f * C * M .. + counts[f] of boxes [.][4], scores, classes, index (may be NULL), each as
+ *                  whenet_yolo_eval returns them for that image alone
+ *   whenet_op_head_compact  the numbering of a clip's heads alone (host pointers): valid [F x K], count [F] -> row [F x K],
+ *                  slot_of_row [max_heads] (-1: an empty row), *rows_used, *overflow; F x K <= 1024, max_heads 1..256.  Works on a
+ *                  whenet_create_postproc handle, like the two above. */
+WHENET_API int whenet_clip_begin(whenet_t* h, const uint8_t* frames, int num_frames, int frame_h, int frame_w, int channel_order,
+                      int* ticket);
+WHENET_API int whenet_clip_detect_heads(whenet_t* h, int ticket, int out_h, int out_w, const float* anchors, int num_anchors,
+                             float score_threshold, float iou_threshold, int max_boxes, int max_heads, int* slots_per_frame);
+WHENET_API int whenet_collect_clip(whenet_t* h, int ticket, int capacity, int* num_frames, int32_t* counts, float* boxes, float* scores,
+                        int32_t* classes, int32_t* rects, int32_t* valid, int32_t* row, float* ypr, int32_t* argmax, float* logits,
+                        int* rows_used, int* overflow);
+WHENET_API int whenet_op_letterbox_batch(whenet_t* h, const uint8_t* frames, int num_frames, int frame_h, int frame_w, int channel_order,
+                              int out_h, int out_w, uint8_t* canvas_u8, float* image_f32);
+WHENET_API int whenet_yolo_eval_batch(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w,
+                           int num_layers, const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
+                           float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
+                           int32_t* classes, int32_t* index, int32_t* counts);
+WHENET_API int whenet_op_head_compact(whenet_t* h, const int32_t* valid, const int32_t* count, int num_frames, int slots_per_frame,
+                           int max_heads, int32_t* row, int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
