@@ -731,6 +731,49 @@ int whenet_collect_clip(whenet_t* h, int ticket, int capacity, int* num_frames, 
     });
 }
 
+// ---- clips of frames of different sizes, and the letterbox geometry cache (engine_post.cpp) ----
+int whenet_clip_begin_mixed(whenet_t* h, const uint8_t* const* frames, int num_frames, const int* frame_h, const int* frame_w, int channel_order,
+                            int* ticket) {
+    if (ticket == nullptr || (channel_order != WHENET_RGB && channel_order != WHENET_BGR)) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        // (argument errors before an engine is taken: a refused clip must not shift the round-robin)
+        whenet::Engine::check_mixed_frames("clip_begin_mixed", frames, num_frames, frame_h, frame_w);
+        const size_t idx = h->next % size_t(h->inflight);
+        whenet::Engine& e = h->at(idx);
+        const int t = e.clip_begin_mixed(frames, num_frames, frame_h, frame_w, channel_order == WHENET_BGR);
+        h->next = (h->next + 1) % size_t(h->inflight);
+        *ticket = t * MAX_INFLIGHT_ENGINES + int(idx);
+    });
+}
+
+int whenet_op_letterbox_mixed(whenet_t* h, const uint8_t* const* frames, int num_frames, const int* frame_h, const int* frame_w,
+                              int channel_order, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32) {
+    if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        e.op_letterbox_mixed(frames, num_frames, frame_h, frame_w, channel_order == WHENET_BGR, out_h, out_w, canvas_u8, image_f32);
+    });
+}
+
+int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
+                           const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
+                           float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,
+                           int32_t* counts) {
+    return guarded(h, [&](whenet::Engine& e) {
+        e.yolo_eval_mixed(feats, num_images, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_shapes, score_threshold,
+                          iou_threshold, max_boxes, boxes, scores, classes, index, counts);
+    });
+}
+
+int whenet_letterbox_cache_stats(whenet_t* h, int32_t out[4]) {
+    if (out == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        e.add_letterbox_cache_stats(out);
+        for (const whenet::Engine* r : h->replicas) r->add_letterbox_cache_stats(out);
+        for (const whenet::Engine* r : h->fan) r->add_letterbox_cache_stats(out);
+    });
+}
+
 int whenet_op_letterbox_batch(whenet_t* h, const uint8_t* frames, int num_frames, int frame_h, int frame_w, int channel_order, int out_h,
                               int out_w, uint8_t* canvas_u8, float* image_f32) {
     if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return WHENET_EINVAL;

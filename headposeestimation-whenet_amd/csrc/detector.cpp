@@ -487,7 +487,9 @@ int Engine::clip_detect_heads(int ticket, int out_h, int out_w, const float* anc
     require_detector();
     Slot& slot = resident_slot(ticket, "clip_detect_heads", HOLDS_CLIP);
     const int F = slot.clip_f;
-    (void)letterbox_plan_layout(slot.fh, slot.fw, out_h, out_w);
+    const bool mixed = slot.clip_mixed;                   // frames of their own sizes: the mixed kernels of the size-dependent stages
+    if (mixed) check_mixed_geometry("clip_detect_heads", F, slot.clip_fh, slot.clip_fw, out_h, out_w);
+    else (void)letterbox_plan_layout(slot.fh, slot.fw, out_h, out_w);
     check_detector_input(F, out_h, out_w);
     WHENET_REQUIRE(det_->out_filters % 3 == 0 && det_->out_filters / 3 > 5, WHENET_EINVAL,
                    "detect: the loaded detector's outputs are not 3 anchors x (5 + classes) wide");
@@ -514,12 +516,22 @@ int Engine::clip_detect_heads(int ticket, int out_h, int out_w, const float* anc
     DetPlan& p = detector_plan(F, out_h, out_w);
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
     const uint8_t* d_frames = slot.frame.d.as<uint8_t>();
-    const uint8_t* d_canvas = enqueue_letterbox(d_frames, slot.fh, slot.fw, slot.swap_rb, out_h, out_w, true, false, F).first;
+    const uint8_t* d_canvas =
+        mixed ? enqueue_letterbox_mixed(d_frames, F, slot.clip_fh, slot.clip_fw, slot.clip_off, slot.swap_rb, out_h, out_w, true, false).first
+              : enqueue_letterbox(d_frames, slot.fh, slot.fw, slot.swap_rb, out_h, out_w, true, false, F).first;
     launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img16.as<half_t>(), size_t(F) * out_h * out_w, stream_);
     WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
     const float* feats[3] = {p.maps[0].as<float>(), p.maps[1].as<float>(), p.maps[2].as<float>()};
+    float shapes[2 * MIXED_MAX_FRAMES] = {};
+    HeadPlanSizes sizes{};
+    CropFrames crop_frames{};
+    for (int f = 0; mixed && f < F; ++f) {
+        shapes[2 * f] = float(slot.clip_fh[f]), shapes[2 * f + 1] = float(slot.clip_fw[f]);
+        sizes.frame_h[f] = slot.clip_fh[f], sizes.frame_w[f] = slot.clip_fw[f];
+        crop_frames.frame_off[f] = slot.clip_off[f], crop_frames.fw[f] = slot.clip_fw[f];
+    }
     const YoloArgs y = enqueue_yolo_eval(feats, true, p.gh, p.gw, det_->num_maps, anchors, num_anchors, num_classes, float(slot.fh),
-                                         float(slot.fw), score_threshold, iou_threshold, max_boxes, false, F);
+                                         float(slot.fw), score_threshold, iou_threshold, max_boxes, false, F, mixed ? shapes : nullptr);
     WHENET_REQUIRE(num_classes * y.max_boxes == K, WHENET_EINVAL, "clip_detect_heads: the selection's capacity differs from the plan's");
     void* const d_rows = slot.det.d.as<void>();
     HeadPlanArgs a{};
@@ -527,11 +539,15 @@ int Engine::clip_detect_heads(int ticket, int out_h, int out_w, const float* anc
     a.num_classes = num_classes, a.max_boxes = y.max_boxes, a.frame_h = slot.fh, a.frame_w = slot.fw, a.frames = F;
     a.boxes = rows.boxes(d_rows), a.scores = rows.scores(d_rows), a.classes = rows.classes(d_rows), a.count = rows.count(d_rows);
     a.rects = rows.rects(d_rows), a.valid = rows.valid(d_rows), a.plans = slot.plan.d.as<int32_t>();
-    launch_head_plan(a, stream_);
+    launch_head_plan(a, stream_, mixed ? &sizes : nullptr);
     launch_head_compact(a.valid, a.count, F, K, max_heads, rows.row(d_rows), rows.slot_of_row(d_rows), rows.rows_used(d_rows),
                         rows.overflow(d_rows), stream_);
-    launch_crop_resize_gather(d_frames, frame_bytes, slot.fw, slot.swap_rb, a.plans, K, rows.slot_of_row(d_rows), max_heads,
-                              slot.in.d.as<uint8_t>(), stream_);
+    if (mixed)
+        launch_crop_resize_gather_mixed(d_frames, crop_frames, slot.swap_rb, a.plans, K, rows.slot_of_row(d_rows), max_heads,
+                                        slot.in.d.as<uint8_t>(), stream_);
+    else
+        launch_crop_resize_gather(d_frames, frame_bytes, slot.fw, slot.swap_rb, a.plans, K, rows.slot_of_row(d_rows), max_heads,
+                                  slot.in.d.as<uint8_t>(), stream_);
     run_forward(slot.in.d.as<uint8_t>(), max_heads, slot.dev(), stream_);
     WHENET_HIP_CHECK(hipMemcpyAsync(slot.det.h.as<void>(), d_rows, rows.bytes(), hipMemcpyDeviceToHost, stream_));
     copy_results_async(slot.host(), slot.dev(), max_heads, stream_);

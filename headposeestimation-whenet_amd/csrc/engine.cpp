@@ -257,6 +257,13 @@ void Engine::set_option(const std::string& key, long value) {
     } else if (key == "se_fuse_tiny") {
         WHENET_REQUIRE(value >= 0 && value <= 64, WHENET_EINVAL, "se_fuse_tiny must be 0..64");
         se_fuse_tiny_ = int(value);
+    } else if (key == "letterbox_cache") {
+        // entries of the letterbox geometry cache (engine.h).  The entries go: nothing that reads their tables may be queued.
+        WHENET_REQUIRE(value >= 1 && value <= 32, WHENET_EINVAL, "letterbox_cache must be 1..32");
+        sync();
+        lb_cache_.clear();
+        lb_cache_cap_ = int(value);
+        return;
     } else if (key == "host_lanes") {
         WHENET_REQUIRE(value >= 1 && value <= MAX_LANES, WHENET_EINVAL, "host_lanes must be 1..8");
         host_lanes_ = int(value);
@@ -1141,7 +1148,7 @@ int Engine::finish_submission(Slot& s, int n) {
     s.busy = true;
     s.n = n;
     s.det_cap = -1;
-    s.clip_f = 0, s.clip_cap = -1;
+    s.clip_f = 0, s.clip_cap = -1, s.clip_mixed = false;
     s.ticket = next_ticket_++;
     return s.ticket;
 }

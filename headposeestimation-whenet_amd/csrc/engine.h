@@ -3,6 +3,7 @@
 // pinned-buffer submit/collect pipeline.  One engine = one device + one stream; not thread-safe.
 #pragma once
 
+#include <deque>
 #include <map>
 #include <memory>
 #include <string>
@@ -272,6 +273,21 @@ class Engine {
     void yolo_eval_batch(const float* const* feats, int images, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
                          int num_anchors, int num_classes, float image_h, float image_w, float score_threshold, float iou_threshold,
                          int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* counts);
+    // A MIXED clip: F frames, each of its own size, packed back to back (offsets = prefix sums of fh * fw * 3, no padding) with
+    // one pinned staging copy and one H2D.  clip_detect_heads / collect_clip take its ticket as they take clip_begin's: every
+    // frame's geometry comes from the letterbox cache (pinned while the launches are enqueued), the stages that depend on the
+    // frame size run their mixed kernels, everything from the compaction on is the same code.  Frame f returns the bytes that
+    // frame_begin; frame_detect_heads; collect_detect return for it alone.
+    int clip_begin_mixed(const uint8_t* const* frames, int nframes, const int* fh, const int* fw, int swap_rb);
+    // argument checks of the two calls above without an engine's state (the C ABI runs them before it takes an engine)
+    static void check_mixed_frames(const char* what, const uint8_t* const* frames, int nframes, const int* fh, const int* fw);
+    void op_letterbox_mixed(const uint8_t* const* frames, int nframes, const int* fh, const int* fw, int swap_rb, int out_h, int out_w,
+                            uint8_t* canvas_u8, float* image_f32);
+    // yolo_eval_batch over images of different shapes: image_shapes [images][2] = (h, w)
+    void yolo_eval_mixed(const float* const* feats, int images, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
+                         int num_anchors, int num_classes, const float* image_shapes, float score_threshold, float iou_threshold,
+                         int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* counts);
+    void add_letterbox_cache_stats(int32_t out[4]) const;      // entries, hits, misses, host_waits
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -298,6 +314,9 @@ class Engine {
         int det_cap = -1;                //   (DetRows); >= 0 marks a submission that collect_detect, not collect, returns
         int clip_f = 0;                  // clip_begin: frames held in `frame` (0: a single frame); with clip_detect_heads `det` is a
         int clip_cap = -1, clip_heads = 0;   // ClipRows(clip_f, clip_cap, clip_heads); clip_cap >= 0: collect_clip returns it
+        bool clip_mixed = false;         // clip_begin_mixed: frame f is clip_fh[f] x clip_fw[f] and starts clip_off[f] bytes into `frame`
+        int clip_fh[MIXED_MAX_FRAMES] = {}, clip_fw[MIXED_MAX_FRAMES] = {};
+        size_t clip_off[MIXED_MAX_FRAMES + 1] = {};      // (the last entry: the bytes of the whole clip)
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -392,15 +411,24 @@ class Engine {
     // frames > 1: d_frame is a clip [frames][fh][fw][3], the canvases are [frames][out_h][out_w][3]
     std::pair<uint8_t*, float*> enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, bool want_u8,
                                                   bool want_f32, int frames = 1);
+    // the same for `frames` frames of their own sizes, frame f at d_frames + off[f] (off[frames]: the bytes of them all)
+    std::pair<uint8_t*, float*> enqueue_letterbox_mixed(const uint8_t* d_frames, int frames, const int* fh, const int* fw, const size_t* off,
+                                                        int swap_rb, int out_h, int out_w, bool want_u8, bool want_f32);
+    void ensure_letterbox_outputs(size_t mid_bytes, size_t nout, bool want_u8, bool want_f32);
+    void letterbox_results_to_host(size_t nout, uint8_t* d_u8, float* d_f32, uint8_t* canvas_u8, float* image_f32);
+    // every frame's plan_layout, F <= letterbox_cache: what a mixed clip needs before anything is enqueued
+    void check_mixed_geometry(const char* what, int frames, const int* fh, const int* fw, int out_h, int out_w) const;
     // the argument set-up of yolo_eval (scratch carved and grown, host maps uploaded) and its launches on stream_; no wait, no copy
     // back: the selected boxes stay in yolo_scratch_ (out_boxes / out_scores / out_count of the returned arguments)
     YoloArgs enqueue_yolo_eval(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
                                const float* anchors, int num_anchors, int num_classes, float image_h, float image_w, float score_threshold,
-                               float iou_threshold, int max_boxes, bool want_all_scores, int images = 1);
+                               float iou_threshold, int max_boxes, bool want_all_scores, int images = 1,
+                               const float* image_shapes = nullptr /* [images][2]: every image its own shape */);
     // yolo_eval on maps that are in host memory (uploaded first) or already on the device
     int yolo_eval_maps(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers, const float* anchors,
                        int num_anchors, int num_classes, float image_h, float image_w, float score_threshold, float iou_threshold,
                        int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index, float* all_boxes, float* all_scores);
+    void yolo_batch_to_host(const YoloArgs& a, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* counts);
     void require_detector() const;
     DetPlan& detector_plan(int n, int H, int W);
     void enqueue_detector(DetPlan& p, hipStream_t s);
@@ -479,13 +507,38 @@ class Engine {
     size_t partial_per_crop_ = 0;
     DeviceBuffer yolo_scratch_;     // device scratch of yolo_eval, grown on demand
     std::vector<int> yolo_counts_;               // host staging of the per-class detection counts
-    // letterbox scratch, grown on demand: the tables of the last geometry (kept: a video has one frame size), the horizontal
-    // pass's output, the /255 table, the outputs and their pinned landing zones, the frame of op_letterbox
-    LetterboxPlan lb_plan_{};
-    bool lb_plan_valid_ = false;
+    // letterbox scratch, grown on demand: the horizontal pass's output, the /255 table, the outputs and their pinned landing
+    // zones, the frame of op_letterbox
     std::vector<int32_t> lb_tables_host_;
-    StagedBuffer lb_tables_, lb_u8_, lb_f32_;
+    StagedBuffer lb_u8_, lb_f32_;
     DeviceBuffer lb_mid_, lb_lut_, lb_frame_;
+    // The letterbox geometry cache (option "letterbox_cache", 1..32 entries, default 16), keyed by (ih, iw, oh, ow): several
+    // cameras on one handle, or the frames of a mixed clip, each keep their resample tables on the device.  An entry owns its
+    // plan, its device table block, the pinned block the tables are staged through and an event recorded behind the H2D copy
+    // out of that block.  A hit enqueues nothing and waits for nothing.  A miss builds the tables on the host, takes the least
+    // recently used entry that no clip being enqueued has pinned, waits -- the host, and only if the copy is not done yet -- for
+    // THAT entry's previous copy event before its pinned block is overwritten, and enqueues the new copy on stream_: the launches
+    // that read the evicted tables are ahead of it in stream order.  stream_ itself is never waited for.  (A block that must
+    // GROW is reallocated, as every grown buffer of the engine: blocks are rounded up so that this ends after the first frames.)
+    struct LbEntry {
+        LetterboxPlan plan{};
+        bool valid = false, staged = false;
+        StagedBuffer tables;
+        Event copied;
+        uint64_t last_use = 0;
+        int pins = 0;
+    };
+    struct LbPins {            // the entries a clip holds while its launches are enqueued
+        std::vector<LbEntry*> held;
+        ~LbPins() {
+            for (LbEntry* e : held) --e->pins;
+        }
+    };
+    std::deque<LbEntry> lb_cache_;      // (a deque: entries never move, clips hold pointers to them)
+    int lb_cache_cap_ = 16;
+    uint64_t lb_clock_ = 0;
+    int32_t lb_hits_ = 0, lb_misses_ = 0, lb_host_waits_ = 0;
+    LbEntry& letterbox_entry(int fh, int fw, int out_h, int out_w, LbPins* pins = nullptr);
 
     std::map<GraphKey, hipGraphExec_t> graphs_;
 

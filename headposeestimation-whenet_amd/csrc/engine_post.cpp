@@ -77,58 +77,200 @@ void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, c
     WHENET_HIP_CHECK(hipMemcpy(crops_out, d_out.as<void>(), obytes, hipMemcpyDeviceToHost));
 }
 
-// The detector's pre-processing (yolo_v3/utils.py:23-34 + yolo_postprocess.py:191-195) of a frame that is on the device.
-// The scratch is one per engine and safe because everything that touches it runs in order on stream_.  The callers that wait for
-// their own results leave the stream idle; frame_detect_heads does not, so the one host-side hazard -- re-staging the tables
-// through their single pinned buffer while an earlier copy out of it may still be queued -- waits for the stream, on that branch only.
-std::pair<uint8_t*, float*> Engine::enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w,
-                                                      bool want_u8, bool want_f32, int frames) {
-    if (!(lb_plan_valid_ && lb_plan_.ih == fh && lb_plan_.iw == fw && lb_plan_.oh == out_h && lb_plan_.ow == out_w)) {
-        lb_plan_valid_ = false;
-        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
-        const LetterboxPlan p = build_letterbox_plan(fh, fw, out_h, out_w, &lb_tables_host_);
+// The letterbox geometry cache (engine.h): the entry of (fh, fw, out_h, out_w), its tables on the device or their copy queued
+// on stream_.  pins: the entry is held until the caller's LbPins goes (a clip needs all of its entries live at once).
+Engine::LbEntry& Engine::letterbox_entry(int fh, int fw, int out_h, int out_w, LbPins* pins) {
+    ++lb_clock_;
+    LbEntry* entry = nullptr;
+    for (LbEntry& e : lb_cache_)
+        if (e.valid && e.plan.ih == fh && e.plan.iw == fw && e.plan.oh == out_h && e.plan.ow == out_w) entry = &e;
+    if (entry != nullptr) {
+        ++lb_hits_;
+    } else {
+        const LetterboxPlan p = build_letterbox_plan(fh, fw, out_h, out_w, &lb_tables_host_);      // (throws before anything changes)
+        if (int(lb_cache_.size()) < lb_cache_cap_) {
+            lb_cache_.emplace_back();
+            entry = &lb_cache_.back();
+            entry->copied.create();
+        } else {
+            for (LbEntry& e : lb_cache_)
+                if (e.pins == 0 && (entry == nullptr || e.last_use < entry->last_use)) entry = &e;
+            WHENET_REQUIRE(entry != nullptr, WHENET_EINVAL,
+                           "letterbox: the clip needs more geometries at once than option letterbox_cache = " + std::to_string(lb_cache_cap_) +
+                               " holds");
+        }
+        ++lb_misses_;
+        entry->valid = false;
+        if (entry->staged && hipEventQuery(entry->copied) != hipSuccess) {      // its pinned block may still be read by its last copy
+            (void)hipGetLastError();
+            ++lb_host_waits_;
+            WHENET_HIP_CHECK(hipEventSynchronize(entry->copied));
+        }
         const size_t tbytes = lb_tables_host_.size() * sizeof(int32_t);
-        lb_tables_.h.grow(tbytes);
-        lb_tables_.d.grow(tbytes);
-        std::memcpy(lb_tables_.h.as<void>(), lb_tables_host_.data(), tbytes);
-        WHENET_HIP_CHECK(hipMemcpyAsync(lb_tables_.d.as<void>(), lb_tables_.h.as<void>(), tbytes, hipMemcpyHostToDevice, stream_));
-        lb_plan_ = p;
-        lb_plan_valid_ = true;
+        size_t block = size_t(16) << 10;
+        while (block < tbytes) block <<= 1;
+        entry->tables.h.grow(block);
+        entry->tables.d.grow(block);
+        std::memcpy(entry->tables.h.as<void>(), lb_tables_host_.data(), tbytes);
+        WHENET_HIP_CHECK(hipMemcpyAsync(entry->tables.d.as<void>(), entry->tables.h.as<void>(), tbytes, hipMemcpyHostToDevice, stream_));
+        WHENET_HIP_CHECK(hipEventRecord(entry->copied, stream_));
+        entry->staged = true;
+        entry->plan = p;
+        entry->valid = true;
     }
+    entry->last_use = lb_clock_;
+    if (pins != nullptr) {
+        ++entry->pins;
+        pins->held.push_back(entry);
+    }
+    return *entry;
+}
+
+void Engine::add_letterbox_cache_stats(int32_t out[4]) const {
+    for (const LbEntry& e : lb_cache_) out[0] += e.valid ? 1 : 0;
+    out[1] += lb_hits_, out[2] += lb_misses_, out[3] += lb_host_waits_;
+}
+
+void Engine::ensure_letterbox_outputs(size_t mid_bytes, size_t nout, bool want_u8, bool want_f32) {
     if (lb_lut_.bytes() == 0) {
         float lut[256];
         letterbox_float_table(lut);
         lb_lut_.reset(sizeof(lut));
         WHENET_HIP_CHECK(hipMemcpy(lb_lut_.as<void>(), lut, sizeof(lut), hipMemcpyHostToDevice));
     }
-    const LetterboxPlan& p = lb_plan_;
-    const size_t nout = size_t(frames) * out_h * out_w * 3;
-    lb_mid_.grow(size_t(frames) * fh * p.nw * 3);
+    lb_mid_.grow(mid_bytes);
     if (want_u8) lb_u8_.h.grow(nout), lb_u8_.d.grow(nout);
     if (want_f32) lb_f32_.h.grow(nout * sizeof(float)), lb_f32_.d.grow(nout * sizeof(float));
+}
+
+// The detector's pre-processing (yolo_v3/utils.py:23-34 + yolo_postprocess.py:191-195) of a frame that is on the device.
+// The scratch is one per engine and safe because everything that touches it runs in order on stream_; the tables come from the
+// geometry cache, so a change of the frame size (two cameras alternating on one handle) does not wait for the stream.
+std::pair<uint8_t*, float*> Engine::enqueue_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w,
+                                                      bool want_u8, bool want_f32, int frames) {
+    const LbEntry& e = letterbox_entry(fh, fw, out_h, out_w);
+    const LetterboxPlan& p = e.plan;
+    ensure_letterbox_outputs(size_t(frames) * fh * p.nw * 3, size_t(frames) * out_h * out_w * 3, want_u8, want_f32);
     uint8_t* const d_u8 = want_u8 ? lb_u8_.d.as<uint8_t>() : nullptr;
     float* const d_f32 = want_f32 ? lb_f32_.d.as<float>() : nullptr;
     if (frames == 1)
-        launch_letterbox(d_frame, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32,
+        launch_letterbox(d_frame, p, swap_rb, e.tables.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32,
                          num_cus_, stream_);
     else
-        launch_letterbox_batch(d_frame, frames, p, swap_rb, lb_tables_.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8,
+        launch_letterbox_batch(d_frame, frames, p, swap_rb, e.tables.d.as<int32_t>(), lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8,
                                d_f32, num_cus_, stream_);
     return {d_u8, d_f32};
 }
 
-void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
-                           float* image_f32, int frames) {
-    WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
-    const size_t nout = size_t(frames) * out_h * out_w * 3;
-    const auto dev = enqueue_letterbox(d_frame, fh, fw, swap_rb, out_h, out_w, canvas_u8 != nullptr, image_f32 != nullptr, frames);
-    uint8_t* const d_u8 = dev.first;
-    float* const d_f32 = dev.second;
+// Frames of their own sizes: every geometry is looked up (or added) and pinned first, so that the F entries are live at once;
+// the records go to the two launches by value.
+std::pair<uint8_t*, float*> Engine::enqueue_letterbox_mixed(const uint8_t* d_frames, int frames, const int* fh, const int* fw,
+                                                            const size_t* off, int swap_rb, int out_h, int out_w, bool want_u8,
+                                                            bool want_f32) {
+    LbPins pins;
+    LetterboxMixed clip{};
+    clip.frames = frames;
+    clip.total_bytes = off[frames];
+    size_t mid = 0;
+    int rows = 0;
+    for (int f = 0; f < frames; ++f) {
+        const LbEntry& e = letterbox_entry(fh[f], fw[f], out_h, out_w, &pins);
+        LetterboxMixedFrame& r = clip.f[f];
+        r.frame_off = off[f], r.mid_off = mid, r.tab = e.tables.d.as<int32_t>(), r.p = e.plan, r.row0 = rows;
+        mid += size_t(fh[f]) * e.plan.nw * 3;
+        rows += fh[f];
+    }
+    clip.total_rows = rows;
+    ensure_letterbox_outputs(mid, size_t(frames) * out_h * out_w * 3, want_u8, want_f32);
+    uint8_t* const d_u8 = want_u8 ? lb_u8_.d.as<uint8_t>() : nullptr;
+    float* const d_f32 = want_f32 ? lb_f32_.d.as<float>() : nullptr;
+    launch_letterbox_mixed(d_frames, clip, swap_rb, lb_lut_.as<float>(), lb_mid_.as<uint8_t>(), d_u8, d_f32, num_cus_, stream_);
+    return {d_u8, d_f32};
+}
+
+void Engine::letterbox_results_to_host(size_t nout, uint8_t* d_u8, float* d_f32, uint8_t* canvas_u8, float* image_f32) {
     if (canvas_u8) WHENET_HIP_CHECK(hipMemcpyAsync(lb_u8_.h.as<void>(), d_u8, nout, hipMemcpyDeviceToHost, stream_));
     if (image_f32) WHENET_HIP_CHECK(hipMemcpyAsync(lb_f32_.h.as<void>(), d_f32, nout * sizeof(float), hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     if (canvas_u8) std::memcpy(canvas_u8, lb_u8_.h.as<void>(), nout);
     if (image_f32) std::memcpy(image_f32, lb_f32_.h.as<void>(), nout * sizeof(float));
+}
+
+void Engine::run_letterbox(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
+                           float* image_f32, int frames) {
+    WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
+    const auto dev = enqueue_letterbox(d_frame, fh, fw, swap_rb, out_h, out_w, canvas_u8 != nullptr, image_f32 != nullptr, frames);
+    letterbox_results_to_host(size_t(frames) * out_h * out_w * 3, dev.first, dev.second, canvas_u8, image_f32);
+}
+
+// ---- frames of different sizes ----
+void Engine::check_mixed_frames(const char* what, const uint8_t* const* frames, int nframes, const int* fh, const int* fw) {
+    const std::string w = what;
+    WHENET_REQUIRE(frames != nullptr && fh != nullptr && fw != nullptr, WHENET_EINVAL, w + ": NULL argument");
+    WHENET_REQUIRE(nframes >= 1 && nframes <= MIXED_MAX_FRAMES, WHENET_EINVAL,
+                   w + ": " + std::to_string(nframes) + " frames: a clip holds 1..16 (the detector's batch limit)");
+    for (int f = 0; f < nframes; ++f) {
+        WHENET_REQUIRE(frames[f] != nullptr, WHENET_EINVAL, w + ": frame " + std::to_string(f) + " is NULL");
+        WHENET_REQUIRE(fh[f] >= 1 && fw[f] >= 1 && fh[f] <= LETTERBOX_MAX_FRAME_SIDE && fw[f] <= LETTERBOX_MAX_FRAME_SIDE, WHENET_EINVAL,
+                       w + ": frame " + std::to_string(f) + " is " + std::to_string(fh[f]) + " x " + std::to_string(fw[f]) +
+                           ": sides must be 1.." + std::to_string(LETTERBOX_MAX_FRAME_SIDE));
+    }
+}
+
+void Engine::check_mixed_geometry(const char* what, int frames, const int* fh, const int* fw, int out_h, int out_w) const {
+    WHENET_REQUIRE(frames <= lb_cache_cap_, WHENET_EINVAL,
+                   std::string(what) + ": " + std::to_string(frames) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(frames) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    for (int f = 0; f < frames; ++f) {
+        try {
+            (void)letterbox_plan_layout(fh[f], fw[f], out_h, out_w);
+        } catch (const Error& e) {
+            throw Error(e.code, std::string(what) + ": frame " + std::to_string(f) + ": " + e.what());
+        }
+    }
+}
+
+void Engine::op_letterbox_mixed(const uint8_t* const* frames, int nframes, const int* fh, const int* fw, int swap_rb, int out_h, int out_w,
+                                uint8_t* canvas_u8, float* image_f32) {
+    DeviceGuard guard(device_);
+    check_mixed_frames("op_letterbox_mixed", frames, nframes, fh, fw);
+    WHENET_REQUIRE(canvas_u8 != nullptr || image_f32 != nullptr, WHENET_EINVAL, "letterbox: both outputs are NULL");
+    check_mixed_geometry("op_letterbox_mixed", nframes, fh, fw, out_h, out_w);
+    size_t off[MIXED_MAX_FRAMES + 1] = {};
+    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(fh[f]) * fw[f] * 3;
+    lb_frame_.grow(off[nframes]);
+    for (int f = 0; f < nframes; ++f)
+        WHENET_HIP_CHECK(hipMemcpyAsync(lb_frame_.as<uint8_t>() + off[f], frames[f], off[f + 1] - off[f], hipMemcpyHostToDevice, stream_));
+    const auto dev = enqueue_letterbox_mixed(lb_frame_.as<uint8_t>(), nframes, fh, fw, off, swap_rb, out_h, out_w, canvas_u8 != nullptr,
+                                             image_f32 != nullptr);
+    letterbox_results_to_host(size_t(nframes) * out_h * out_w * 3, dev.first, dev.second, canvas_u8, image_f32);
+}
+
+// clip_begin for frames of their own sizes: packed back to back (a frame's first byte is unaligned in general) into the slot's
+// pinned staging, one H2D; the slot remembers every frame's size and offset.
+int Engine::clip_begin_mixed(const uint8_t* const* frames, int nframes, const int* fh, const int* fw, int swap_rb) {
+    DeviceGuard guard(device_);
+    check_mixed_frames("clip_begin_mixed", frames, nframes, fh, fw);      // (before a slot is taken)
+    WHENET_REQUIRE(nframes <= lb_cache_cap_, WHENET_EINVAL,
+                   "clip_begin_mixed: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    size_t off[MIXED_MAX_FRAMES + 1] = {};
+    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(fh[f]) * fw[f] * 3;
+    const size_t bytes = off[nframes];
+    slot.frame.h.grow(bytes);
+    slot.frame.d.grow(bytes);
+    for (int f = 0; f < nframes; ++f) std::memcpy(slot.frame.h.as<uint8_t>() + off[f], frames[f], off[f + 1] - off[f]);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.frame.d.as<void>(), slot.frame.h.as<void>(), bytes, hipMemcpyHostToDevice, copy_stream()));
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = fh[0], slot.fw = fw[0], slot.swap_rb = swap_rb;
+    for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = fh[f], slot.clip_fw[f] = fw[f];
+    std::copy(off, off + nframes + 1, slot.clip_off);
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = nframes;
+    slot.clip_mixed = true;
+    return slot.frame_ticket;
 }
 
 void Engine::op_letterbox(const uint8_t* frame, int fh, int fw, int swap_rb, int out_h, int out_w, uint8_t* canvas_u8,
@@ -189,6 +331,7 @@ int Engine::clip_begin(const uint8_t* frames, int nframes, int fh, int fw, int s
     slot.fh = fh, slot.fw = fw, slot.swap_rb = swap_rb;
     slot.frame_ticket = finish_submission(slot, 0);
     slot.clip_f = nframes;
+    slot.clip_mixed = false;
     return slot.frame_ticket;
 }
 
@@ -254,7 +397,8 @@ int Engine::yolo_eval(const float* const* feats, const int* grid_h, const int* g
 // on_device: the maps are where the detector body left them (detector.cpp); nothing is uploaded
 YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, const int* grid_h, const int* grid_w, int num_layers,
                                    const float* anchors, int num_anchors, int num_classes, float image_h, float image_w,
-                                   float score_threshold, float iou_threshold, int max_boxes, bool want_all_scores, int images) {
+                                   float score_threshold, float iou_threshold, int max_boxes, bool want_all_scores, int images,
+                                   const float* image_shapes) {
     WHENET_REQUIRE(feats && grid_h && grid_w && anchors, WHENET_EINVAL, "yolo_eval: NULL argument");
     WHENET_REQUIRE(images >= 1 && images <= 16, WHENET_EINVAL, "yolo_eval: 1..16 images");
     WHENET_REQUIRE((num_layers == 3 && num_anchors == 9) || (num_layers == 2 && num_anchors == 6), WHENET_EINVAL,
@@ -274,14 +418,17 @@ YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, co
     a.input_w = float(grid_w[0] * 32);
     a.image_h = image_h;
     a.image_w = image_w;
-    {   // model.py:158-162, float32 like the graph: new_shape = round(image_shape * min(input_shape / image_shape))
-        const float ry = a.input_h / image_h, rx = a.input_w / image_w;
-        const float r = ry < rx ? ry : rx;
-        const float new_h = std::nearbyintf(image_h * r), new_w = std::nearbyintf(image_w * r);      // half to even
-        a.off_y = (a.input_h - new_h) / 2.0f / a.input_h;
-        a.off_x = (a.input_w - new_w) / 2.0f / a.input_w;
-        a.scale_y = a.input_h / new_h;
-        a.scale_x = a.input_w / new_w;
+    {
+        const MixedFrameCorrection c = yolo_correction(a.input_h, a.input_w, image_h, image_w);
+        a.off_y = c.off_y, a.off_x = c.off_x, a.scale_y = c.scale_y, a.scale_x = c.scale_x;
+    }
+    YoloMixed mixed{};                                      // every image its own shape: the values of each, computed as for one image
+    if (image_shapes != nullptr) {
+        for (int f = 0; f < images; ++f) {
+            const float h = image_shapes[2 * f], w = image_shapes[2 * f + 1];
+            WHENET_REQUIRE(h > 0 && w > 0, WHENET_EINVAL, "yolo_eval: bad shape of image " + std::to_string(f));
+            mixed.img[f] = yolo_correction(a.input_h, a.input_w, h, w);
+        }
     }
     a.score_thr = score_threshold;
     a.iou_thr = iou_threshold;
@@ -350,7 +497,7 @@ YoloArgs Engine::enqueue_yolo_eval(const float* const* feats, bool on_device, co
     a.out_scores = reinterpret_cast<float*>(base + o_os);
     a.out_index = reinterpret_cast<int*>(base + o_oi);
     a.out_count = reinterpret_cast<int*>(base + o_oc);
-    launch_yolo_eval(a, stream_);
+    launch_yolo_eval(a, stream_, image_shapes != nullptr ? &mixed : nullptr);
     return a;
 }
 
@@ -436,6 +583,24 @@ void Engine::yolo_eval_batch(const float* const* feats, int images, const int* g
     WHENET_REQUIRE(boxes && scores && classes && counts, WHENET_EINVAL, "yolo_eval_batch: NULL argument");
     const YoloArgs a = enqueue_yolo_eval(feats, false, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_h, image_w,
                                          score_threshold, iou_threshold, max_boxes, false, images);
+    yolo_batch_to_host(a, boxes, scores, classes, index, counts);
+}
+
+void Engine::yolo_eval_mixed(const float* const* feats, int images, const int* grid_h, const int* grid_w, int num_layers,
+                             const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
+                             float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,
+                             int32_t* counts) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(boxes && scores && classes && counts && image_shapes, WHENET_EINVAL, "yolo_eval_mixed: NULL argument");
+    WHENET_REQUIRE(images >= 1 && images <= MIXED_MAX_FRAMES, WHENET_EINVAL, "yolo_eval: 1..16 images");
+    const YoloArgs a = enqueue_yolo_eval(feats, false, grid_h, grid_w, num_layers, anchors, num_anchors, num_classes, image_shapes[0],
+                                         image_shapes[1], score_threshold, iou_threshold, max_boxes, false, images, image_shapes);
+    yolo_batch_to_host(a, boxes, scores, classes, index, counts);
+}
+
+// the selected rows of every image of a batch back in one wait, concatenated class by class per image
+void Engine::yolo_batch_to_host(const YoloArgs& a, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* counts) {
+    const int num_classes = a.num_classes, images = a.images;
     const size_t C = size_t(num_classes), MB = size_t(a.max_boxes), F = size_t(images), S = F * C * MB;
     std::vector<float> ob(S * 4), os(S);
     std::vector<int> oi(S), oc(F * C);
@@ -509,6 +674,7 @@ void Engine::collect_clip(int ticket, int capacity, int* nframes, int32_t* count
     slot->busy = false;
     slot->clip_cap = -1;
     slot->clip_f = 0;
+    slot->clip_mixed = false;
 }
 
 void Engine::op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,

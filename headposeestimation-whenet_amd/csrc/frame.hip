@@ -103,6 +103,24 @@ __global__ __launch_bounds__(256) void whenet_crop_resize_gather_kernel(const ui
                       dx);
 }
 
+// the same for a clip whose frames differ in size: the slot's frame starts at its own byte offset and has its own width
+__global__ __launch_bounds__(256) void whenet_crop_resize_gather_mixed_kernel(const uint8_t* __restrict__ frames, CropFrames cf, int swap_rb,
+                                                                              const int32_t* __restrict__ plan, int slots_per_frame,
+                                                                              const int32_t* __restrict__ slot_of_row,
+                                                                              uint8_t* __restrict__ out) {
+    const int dy = blockIdx.x, r = blockIdx.y, dx = threadIdx.x;
+    if (dx >= OUT) return;
+    uint8_t* orow = out + size_t(r) * OUT * OUT * 3;
+    const int slot = slot_of_row[r];
+    const int f = slot < 0 ? -1 : slot / slots_per_frame;
+    if (f < 0 || f >= MIXED_MAX_FRAMES) {
+        uint8_t* o = orow + (size_t(dy) * OUT + dx) * 3;
+        o[0] = 0, o[1] = 0, o[2] = 0;
+        return;
+    }
+    crop_resize_pixel(frames + size_t(cf.frame_off[f]), cf.fw[f], swap_rb, plan + size_t(slot) * CROP_PLAN_INTS, orow, 0, dy, dx);
+}
+
 // saturate_cast<short>(float): cvRound (round half to even, the default FP rounding mode) + saturation
 inline int32_t to_short(float v) {
     long r = lrintf(v);
@@ -197,6 +215,15 @@ void launch_crop_resize_gather(const uint8_t* d_frames, size_t frame_bytes, int 
     if (rows <= 0) return;
     WHENET_REQUIRE(slots_per_frame >= 1, WHENET_EINVAL, "crop_resize_gather: bad sizes");
     hipLaunchKernelGGL(whenet_crop_resize_gather_kernel, dim3(OUT, rows), dim3(256), 0, stream, d_frames, frame_bytes, fw, swap_rb, d_plan,
+                       slots_per_frame, d_slot_of_row, d_out);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+void launch_crop_resize_gather_mixed(const uint8_t* d_frames, const CropFrames& frames, int swap_rb, const int32_t* d_plan,
+                                     int slots_per_frame, const int32_t* d_slot_of_row, int rows, uint8_t* d_out, hipStream_t stream) {
+    if (rows <= 0) return;
+    WHENET_REQUIRE(slots_per_frame >= 1, WHENET_EINVAL, "crop_resize_gather: bad sizes");
+    hipLaunchKernelGGL(whenet_crop_resize_gather_mixed_kernel, dim3(OUT, rows), dim3(256), 0, stream, d_frames, frames, swap_rb, d_plan,
                        slots_per_frame, d_slot_of_row, d_out);
     WHENET_HIP_CHECK(hipGetLastError());
 }

@@ -14,8 +14,8 @@
 // the per-class counts (at most 64 classes, uniform loads); lane 0 writes the row's box / score / class / window / valid
 // flag; lanes 0..223 each write one entry of the six 224-entry tables (xofs | a0 | a1 | yofs | b0 | b1); the first column
 // that reads a single sample (xmax) is an LDS atomic minimum.  A row beyond the detection count, or one whose window is
-// empty or leaves the frame, gets valid = 0 and a plan of zeros: the crop kernel skips it.  The frames of a clip (one size)
-// are the grid's second dimension; whenet_head_compact_kernel then numbers the clip's live heads so that the forward runs
+// empty or leaves the frame, gets valid = 0 and a plan of zeros: the crop kernel skips it.  The frames of a clip (of one size, or
+// each of its own: the mixed kernel) are the grid's second dimension; whenet_head_compact_kernel then numbers the clip's live heads so that the forward runs
 // over them alone.
 #include <climits>
 
@@ -90,8 +90,8 @@ __device__ __forceinline__ bool axis_entry(int src, bool horizontal, int d, int3
     return single;
 }
 
-__global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
-    __shared__ int s_xmax;
+// one detection slot of frame blockIdx.y, whose size is frame_h x frame_w (s_xmax: one LDS word of the workgroup)
+__device__ __forceinline__ void head_plan_slot(const HeadPlanArgs& a, const int frame_h, const int frame_w, int& s_xmax) {
     const int slot = blockIdx.x, tid = threadIdx.x;         // detection slot of its frame
     const size_t f = blockIdx.y;                            // frame of a clip: inputs [F][C]..., outputs [F][K]..., count [F]
     const size_t row = f * (size_t(a.num_classes) * a.max_boxes) + slot;
@@ -113,8 +113,8 @@ __global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
         const size_t src = (f * a.num_classes + size_t(cls)) * a.max_boxes + pos;
         const float* b = a.in_boxes + src * 4;
         const float b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-        box_rect(a.frame_h, a.frame_w, b0, b1, b2, b3, rect);
-        ok = rect[0] >= 0 && rect[1] >= 0 && rect[2] <= a.frame_h && rect[3] <= a.frame_w && rect[0] < rect[2] && rect[1] < rect[3];
+        box_rect(frame_h, frame_w, b0, b1, b2, b3, rect);
+        ok = rect[0] >= 0 && rect[1] >= 0 && rect[2] <= frame_h && rect[3] <= frame_w && rect[0] < rect[2] && rect[1] < rect[3];
         if (tid == 0) {
             float* ob = a.boxes + row * 4;
             ob[0] = b0, ob[1] = b1, ob[2] = b2, ob[3] = b3;
@@ -152,6 +152,17 @@ __global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
         P[5] = s_xmax;
         P[6] = 0, P[7] = 0;
     }
+}
+
+__global__ __launch_bounds__(256) void whenet_head_plan_kernel(HeadPlanArgs a) {
+    __shared__ int s_xmax;
+    head_plan_slot(a, a.frame_h, a.frame_w, s_xmax);
+}
+
+// the frames of a mixed clip: frame blockIdx.y has its own size
+__global__ __launch_bounds__(256) void whenet_head_plan_mixed_kernel(HeadPlanArgs a, HeadPlanSizes m) {
+    __shared__ int s_xmax;
+    head_plan_slot(a, m.frame_h[blockIdx.y], m.frame_w[blockIdx.y], s_xmax);
 }
 
 // Compaction of a clip's heads (kernels.h): lane s owns slot s.  A wave's ballot numbers its live slots, the 16 wave totals
@@ -199,11 +210,18 @@ __global__ __launch_bounds__(HEAD_COMPACT_MAX_SLOTS) void whenet_head_compact_ke
 
 }  // namespace
 
-void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream) {
-    WHENET_REQUIRE(a.num_classes >= 1 && a.max_boxes >= 1 && a.frame_h > 0 && a.frame_w > 0 && a.frames >= 0 && a.frames <= 65535,
-                   WHENET_EINVAL, "head_plan: bad sizes");
-    hipLaunchKernelGGL(whenet_head_plan_kernel, dim3(unsigned(a.num_classes) * unsigned(a.max_boxes), a.frames > 1 ? unsigned(a.frames) : 1u),
-                       dim3(256), 0, stream, a);
+void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream, const HeadPlanSizes* mixed) {
+    WHENET_REQUIRE(a.num_classes >= 1 && a.max_boxes >= 1 && a.frames >= 0 && a.frames <= 65535, WHENET_EINVAL, "head_plan: bad sizes");
+    const dim3 grid(unsigned(a.num_classes) * unsigned(a.max_boxes), a.frames > 1 ? unsigned(a.frames) : 1u);
+    if (mixed) {
+        WHENET_REQUIRE(grid.y <= unsigned(MIXED_MAX_FRAMES), WHENET_EINVAL, "head_plan: too many frames of different sizes");
+        for (unsigned f = 0; f < grid.y; ++f)
+            WHENET_REQUIRE(mixed->frame_h[f] > 0 && mixed->frame_w[f] > 0, WHENET_EINVAL, "head_plan: bad sizes");
+        hipLaunchKernelGGL(whenet_head_plan_mixed_kernel, grid, dim3(256), 0, stream, a, *mixed);
+    } else {
+        WHENET_REQUIRE(a.frame_h > 0 && a.frame_w > 0, WHENET_EINVAL, "head_plan: bad sizes");
+        hipLaunchKernelGGL(whenet_head_plan_kernel, grid, dim3(256), 0, stream, a);
+    }
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

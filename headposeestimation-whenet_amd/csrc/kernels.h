@@ -367,6 +367,16 @@ void pack_mb7_se(const std::vector<float>& w1t /* [R][C] */, const std::vector<f
 void launch_mb7(const Mb7Args& a, hipStream_t stream);
 std::string kernel_name_mb7(int k, int Cout, bool skip);
 
+// ---- frames of different sizes in one clip (letterbox.hip, yolo.hip, headplan.hip, frame.hip) --
+// The stages before and after the detector body depend on the frame size; their mixed forms take one geometry record per frame,
+// passed BY VALUE in the kernel's argument block (16 records: 1.8 KB): no copy is enqueued and no host buffer can be overwritten
+// while a launch that reads it is still queued.  The frames lie back to back in one buffer, without padding.
+constexpr int MIXED_MAX_FRAMES = 16;
+struct MixedFrameCorrection {                   // yolo_correct_boxes of one image (model.py:158-162), float32 as for one image
+    float image_h, image_w, off_y, off_x, scale_y, scale_x;
+};
+MixedFrameCorrection yolo_correction(float input_h, float input_w, float image_h, float image_w);
+
 // ---- yolo.hip ---------------------------------------------------------------------------
 // YOLOv3 post-processing (yolo_v3/model.py:125-232): decode + score threshold + per-class NMS.
 struct YoloLayer {
@@ -393,7 +403,11 @@ struct YoloArgs {
     int* out_index;                        // [C][max_boxes]
     int* out_count;                        // [C]
 };
-void launch_yolo_eval(const YoloArgs& a, hipStream_t stream);
+struct YoloMixed {                              // the correction of image blockIdx.y instead of the one set in YoloArgs
+    MixedFrameCorrection img[MIXED_MAX_FRAMES];
+};
+// mixed != nullptr: image f of the batch is corrected with mixed->img[f] (a.images <= MIXED_MAX_FRAMES)
+void launch_yolo_eval(const YoloArgs& a, hipStream_t stream, const YoloMixed* mixed = nullptr);
 int yolo_max_select();
 
 // ---- frame.hip --------------------------------------------------------------------------
@@ -412,6 +426,15 @@ void launch_crop_resize_masked(const uint8_t* d_frame, int fw, int swap_rb, cons
 // compaction) with plan d_plan[s], cut from frame s / slots_per_frame; a row with s < 0 is filled with zero bytes.
 void launch_crop_resize_gather(const uint8_t* d_frames, size_t frame_bytes, int fw, int swap_rb, const int32_t* d_plan, int slots_per_frame,
                                const int32_t* d_slot_of_row, int rows, uint8_t* d_out, hipStream_t stream);
+
+// The same over the frames of a MIXED clip: the frame of slot s starts frame_off[s / slots_per_frame] bytes into d_frames and is
+// fw[.] pixels wide.
+struct CropFrames {
+    unsigned long long frame_off[MIXED_MAX_FRAMES];
+    int fw[MIXED_MAX_FRAMES];
+};
+void launch_crop_resize_gather_mixed(const uint8_t* d_frames, const CropFrames& frames, int swap_rb, const int32_t* d_plan,
+                                     int slots_per_frame, const int32_t* d_slot_of_row, int rows, uint8_t* d_out, hipStream_t stream);
 
 // ---- headplan.hip -----------------------------------------------------------------------
 // The detector's selected boxes (yolo.hip's out_boxes / out_scores / out_count, left where launch_yolo_eval wrote them) ->
@@ -433,7 +456,10 @@ struct HeadPlanArgs {
     int32_t* valid;            // [K]
     int32_t* plans;            // [K][CROP_PLAN_INTS] or nullptr; zeros where valid is 0
 };
-void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream);
+struct HeadPlanSizes {                          // a mixed clip: the size of frame blockIdx.y instead of a.frame_h / a.frame_w
+    int frame_h[MIXED_MAX_FRAMES], frame_w[MIXED_MAX_FRAMES];
+};
+void launch_head_plan(const HeadPlanArgs& a, hipStream_t stream, const HeadPlanSizes* mixed = nullptr);
 // Compaction of a clip's heads: slot s = f * K + i (s < F * K <= 1024) is LIVE iff valid[s] != 0 and i < count[f].  The r-th
 // live slot in slot order gets row[s] = r if r < max_heads; every other slot gets row -1.  slot_of_row [max_heads] is the
 // inverse (-1: an empty row), *rows_used = min(live, max_heads), *overflow = live - *rows_used.  One workgroup, no atomics.
@@ -466,6 +492,23 @@ void launch_letterbox(const uint8_t* d_frame, const LetterboxPlan& p, int swap_r
 void launch_letterbox_batch(const uint8_t* d_frames, int frames, const LetterboxPlan& p, int swap_rb, const int32_t* d_tables,
                             const float* d_lut, uint8_t* d_mid, uint8_t* d_canvas_u8, float* d_image_f32, int num_cus,
                             hipStream_t stream);
+// A MIXED clip: F <= 16 frames of different sizes, back to back in d_frames (frame f starts frame_off bytes in; neither that
+// byte nor a row pitch is 16-byte aligned in general) -> canvases [F][oh][ow][3].  Every frame has its own plan, table block
+// and place in d_mid (mid_off, sum of ih * nw * 3 bytes in all); the horizontal pass walks the global rows 0 .. sum ih, frame f's
+// first being row0.  total_bytes: the extent of d_frames that may be read (the 16-byte chunks around a row stay inside it).
+struct LetterboxMixedFrame {
+    unsigned long long frame_off, mid_off;
+    const int32_t* tab;
+    LetterboxPlan p;
+    int row0;
+};
+struct LetterboxMixed {
+    int frames, total_rows;
+    unsigned long long total_bytes;
+    LetterboxMixedFrame f[MIXED_MAX_FRAMES];
+};
+void launch_letterbox_mixed(const uint8_t* d_frames, const LetterboxMixed& clip, int swap_rb, const float* d_lut, uint8_t* d_mid,
+                            uint8_t* d_canvas_u8, float* d_image_f32, int num_cus, hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC binary16 activations: implicit-GEMM convolution on the f16

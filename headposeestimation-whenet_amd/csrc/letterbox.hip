@@ -30,6 +30,45 @@ __device__ inline int clip8(int acc) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
+// The two halves of the horizontal pass, shared by its kernels.
+// The row of row_bytes bytes at address lo, staged into `row` as the 16-byte chunks (counted from lo ALIGNED DOWN) that hold it;
+// [base, base + buf_bytes) is what may be read.  Returns the row's first byte in `row`.  Barriers inside: every thread calls it.
+__device__ __forceinline__ int letterbox_stage_row(uint8_t* row, uintptr_t base, size_t buf_bytes, uintptr_t lo, size_t row_bytes) {
+    const uintptr_t hi = lo + row_bytes;
+    const uintptr_t first = lo & ~uintptr_t(15);
+    const int skew = int(lo - first);
+    const int chunks = int((hi - first + 15) >> 4);
+    __syncthreads();                                     // (the previous row's readers are done)
+    for (int c = threadIdx.x; c < chunks; c += THREADS) {
+        const uintptr_t a = first + (uintptr_t(c) << 4);
+        if (a >= base && a + 16 <= base + buf_bytes) {   // wholly inside the buffer: one 16-byte load
+            *reinterpret_cast<uint4*>(row + (c << 4)) = *reinterpret_cast<const uint4*>(a);
+        } else {                                         // the buffer's first / last partial chunk: its own bytes only
+            for (int b = 0; b < 16; ++b) {
+                const uintptr_t ab = a + b;
+                row[(c << 4) + b] = (ab >= base && ab < base + buf_bytes) ? *reinterpret_cast<const uint8_t*>(ab) : uint8_t(0);
+            }
+        }
+    }
+    __syncthreads();
+    return skew;
+}
+
+// the out_bytes output bytes of one staged row
+__device__ __forceinline__ void letterbox_h_row(const uint8_t* src, uint8_t* __restrict__ dst, int out_bytes, int swap_rb,
+                                                const int32_t* __restrict__ bounds, const int32_t* __restrict__ coeffs, int ksx) {
+    for (int ob = threadIdx.x; ob < out_bytes; ob += THREADS) {
+        const int ox = ob / 3, c = ob - ox * 3;
+        const int cs = swap_rb ? 2 - c : c;
+        const int xmin = bounds[2 * ox], n = bounds[2 * ox + 1];
+        const int32_t* k = coeffs + size_t(ox) * ksx;
+        const uint8_t* s = src + xmin * 3 + cs;
+        int acc = 1 << (PRECISION_BITS - 1);
+        for (int j = 0; j < n; ++j) acc += int(s[j * 3]) * k[j];
+        dst[ob] = uint8_t(clip8(acc));
+    }
+}
+
 // Horizontal pass: frame [ih][iw][3] -> mid [ih][nw][3].  A workgroup owns whole input rows: the row goes into LDS
 // with 16-byte loads of the aligned chunks that cover it (the frame is read once, in whole lines), then thread t
 // forms output BYTES t, t + 256, ... of the row (pixel = byte / 3), so the stores of a wave are contiguous and the
@@ -42,38 +81,30 @@ __global__ __launch_bounds__(THREADS) void whenet_letterbox_h_kernel(const uint8
     const int32_t* __restrict__ coeffs = tab + p.off_cx;
     const size_t row_bytes = size_t(p.iw) * 3, frame_bytes = size_t(p.ih) * row_bytes;
     const int out_bytes = p.nw * 3;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(frame);
     for (int y = blockIdx.x; y < p.ih; y += gridDim.x) {
-        // the 16-byte chunks [c0, c1) of the frame buffer (counted from its ALIGNED-DOWN start) that hold this row
-        const uintptr_t base = reinterpret_cast<uintptr_t>(frame);
-        const uintptr_t lo = base + size_t(y) * row_bytes, hi = lo + row_bytes;
-        const uintptr_t first = lo & ~uintptr_t(15);
-        const int skew = int(lo - first);
-        const int chunks = int((hi - first + 15) >> 4);
-        __syncthreads();                                     // (the previous row's readers are done)
-        for (int c = threadIdx.x; c < chunks; c += THREADS) {
-            const uintptr_t a = first + (uintptr_t(c) << 4);
-            if (a >= base && a + 16 <= base + frame_bytes) { // wholly inside the frame: one 16-byte load
-                *reinterpret_cast<uint4*>(row + (c << 4)) = *reinterpret_cast<const uint4*>(a);
-            } else {                                         // the frame's first / last partial chunk: its own bytes only
-                for (int b = 0; b < 16; ++b) {
-                    const uintptr_t ab = a + b;
-                    row[(c << 4) + b] = (ab >= base && ab < base + frame_bytes) ? *reinterpret_cast<const uint8_t*>(ab) : uint8_t(0);
-                }
-            }
-        }
-        __syncthreads();
-        const uint8_t* src = row + skew;
-        uint8_t* dst = mid + size_t(y) * out_bytes;
-        for (int ob = threadIdx.x; ob < out_bytes; ob += THREADS) {
-            const int ox = ob / 3, c = ob - ox * 3;
-            const int cs = swap_rb ? 2 - c : c;
-            const int xmin = bounds[2 * ox], n = bounds[2 * ox + 1];
-            const int32_t* k = coeffs + size_t(ox) * p.ksx;
-            const uint8_t* s = src + xmin * 3 + cs;
-            int acc = 1 << (PRECISION_BITS - 1);
-            for (int j = 0; j < n; ++j) acc += int(s[j * 3]) * k[j];
-            dst[ob] = uint8_t(clip8(acc));
-        }
+        const int skew = letterbox_stage_row(row, base, frame_bytes, base + size_t(y) * row_bytes, row_bytes);
+        letterbox_h_row(row + skew, mid + size_t(y) * out_bytes, out_bytes, swap_rb, bounds, coeffs, p.ksx);
+    }
+}
+
+// The same over the rows of a MIXED clip: global row g belongs to the last frame whose row0 is <= g (a scan of at most 16
+// values, the same in every lane), and is resampled with that frame's width, bounds and coefficients into its part of mid.
+__global__ __launch_bounds__(THREADS) void whenet_letterbox_h_mixed_kernel(const uint8_t* __restrict__ frames, LetterboxMixed clip,
+                                                                           int swap_rb, uint8_t* __restrict__ mid) {
+    __shared__ __attribute__((aligned(16))) uint8_t row[ROW_LDS_BYTES];
+    const uintptr_t base = reinterpret_cast<uintptr_t>(frames);
+    for (int g = blockIdx.x; g < clip.total_rows; g += gridDim.x) {
+        int f = 0;
+        for (int i = 1; i < clip.frames; ++i)
+            if (clip.f[i].row0 <= g) f = i;
+        const LetterboxMixedFrame& fr = clip.f[f];
+        const int y = g - fr.row0;
+        const size_t row_bytes = size_t(fr.p.iw) * 3;
+        const int out_bytes = fr.p.nw * 3;
+        const int skew = letterbox_stage_row(row, base, size_t(clip.total_bytes), base + size_t(fr.frame_off) + size_t(y) * row_bytes, row_bytes);
+        letterbox_h_row(row + skew, mid + size_t(fr.mid_off) + size_t(y) * out_bytes, out_bytes, swap_rb, fr.tab + fr.p.off_bx,
+                        fr.tab + fr.p.off_cx, fr.p.ksx);
     }
 }
 
@@ -120,6 +151,18 @@ __global__ __launch_bounds__(THREADS) void whenet_letterbox_v_batch_kernel(const
     const size_t f = blockIdx.z;
     const size_t mid_stride = size_t(p.ih) * p.nw * 3, out_stride = size_t(p.oh) * p.ow * 3;
     letterbox_v_byte(mid + f * mid_stride, p, tab, lut, canvas_u8 ? canvas_u8 + f * out_stride : nullptr,
+                     image_f32 ? image_f32 + f * out_stride : nullptr, blockIdx.y, blockIdx.x * THREADS + threadIdx.x);
+}
+
+// The frames of a MIXED clip (grid z): frame f has its own plan, tables and place in mid; the canvases are [F][oh][ow][3].
+__global__ __launch_bounds__(THREADS) void whenet_letterbox_v_mixed_kernel(const uint8_t* __restrict__ mid, LetterboxMixed clip,
+                                                                           const float* __restrict__ lut,
+                                                                           uint8_t* __restrict__ canvas_u8,
+                                                                           float* __restrict__ image_f32) {
+    const size_t f = blockIdx.z;
+    const LetterboxMixedFrame& fr = clip.f[f];
+    const size_t out_stride = size_t(fr.p.oh) * fr.p.ow * 3;
+    letterbox_v_byte(mid + size_t(fr.mid_off), fr.p, fr.tab, lut, canvas_u8 ? canvas_u8 + f * out_stride : nullptr,
                      image_f32 ? image_f32 + f * out_stride : nullptr, blockIdx.y, blockIdx.x * THREADS + threadIdx.x);
 }
 
@@ -245,6 +288,27 @@ void launch_letterbox_batch(const uint8_t* d_frames, int frames, const Letterbox
     WHENET_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(whenet_letterbox_v_batch_kernel, dim3((p.ow * 3 + THREADS - 1) / THREADS, p.oh, frames), dim3(THREADS), 0,
                        stream, d_mid, p, d_tables, d_lut, d_canvas_u8, d_image_f32);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+void launch_letterbox_mixed(const uint8_t* d_frames, const LetterboxMixed& clip, int swap_rb, const float* d_lut, uint8_t* d_mid,
+                            uint8_t* d_canvas_u8, float* d_image_f32, int num_cus, hipStream_t stream) {
+    WHENET_REQUIRE(clip.frames >= 1 && clip.frames <= MIXED_MAX_FRAMES && clip.total_rows >= clip.frames, WHENET_EINVAL,
+                   "letterbox: bad frame count");
+    if (d_canvas_u8 == nullptr && d_image_f32 == nullptr) return;
+    const LetterboxPlan& p0 = clip.f[0].p;
+    for (int f = 0; f < clip.frames; ++f) {
+        const LetterboxMixedFrame& fr = clip.f[f];
+        WHENET_REQUIRE(fr.tab != nullptr && fr.p.oh == p0.oh && fr.p.ow == p0.ow && fr.p.iw >= 1 && fr.p.iw <= LETTERBOX_MAX_FRAME_SIDE &&
+                           fr.frame_off + size_t(fr.p.ih) * fr.p.iw * 3 <= clip.total_bytes &&
+                           fr.row0 + fr.p.ih <= clip.total_rows,
+                       WHENET_EINVAL, "letterbox: inconsistent geometry record of frame " + std::to_string(f));
+    }
+    const int rows_wg = clip.total_rows < num_cus * 8 ? clip.total_rows : num_cus * 8;
+    hipLaunchKernelGGL(whenet_letterbox_h_mixed_kernel, dim3(rows_wg), dim3(THREADS), 0, stream, d_frames, clip, swap_rb, d_mid);
+    WHENET_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(whenet_letterbox_v_mixed_kernel, dim3((p0.ow * 3 + THREADS - 1) / THREADS, p0.oh, clip.frames), dim3(THREADS), 0,
+                       stream, d_mid, clip, d_lut, d_canvas_u8, d_image_f32);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

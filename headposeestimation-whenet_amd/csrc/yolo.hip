@@ -20,6 +20,8 @@
 //      float32 with individually rounded operations), one ballot decides, selected boxes live in LDS.
 // All arithmetic is float32 with the operation order of the reference's graph; exp / sigmoid go through expf,
 // so box coordinates agree with a float32 CPU run to an ulp or two, not bitwise (tests/test_yolo.py).
+#include <cmath>
+
 #include "kernels.h"
 
 namespace whenet {
@@ -28,10 +30,8 @@ namespace {
 
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-__global__ __launch_bounds__(256) void whenet_yolo_decode_kernel(YoloArgs a) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.N) return;
-    const size_t img = blockIdx.y;                              // image of a batch: every array below is [images][...]
+// one box of image img: decode, correction c (that of the image), candidate keys
+__device__ __forceinline__ void yolo_decode_box(const YoloArgs& a, const MixedFrameCorrection& c, const size_t img, const int i) {
     int l = 0;
     while (l + 1 < a.num_layers && i >= a.layer[l + 1].first) ++l;
     const YoloLayer& L = a.layer[l];
@@ -47,26 +47,40 @@ __global__ __launch_bounds__(256) void whenet_yolo_decode_kernel(YoloArgs a) {
     const float bh = __fdiv_rn(__fmul_rn(expf(t[3]), L.anchor[an][1]), a.input_h);
     const float conf = sigmoid_ref(t[4]);
     // yolo_correct_boxes (model.py:155-177): y first
-    const float cy = __fmul_rn(__fsub_rn(by, a.off_y), a.scale_y), cx = __fmul_rn(__fsub_rn(bx, a.off_x), a.scale_x);
-    const float hh = __fmul_rn(bh, a.scale_y), ww = __fmul_rn(bw, a.scale_x);
+    const float cy = __fmul_rn(__fsub_rn(by, c.off_y), c.scale_y), cx = __fmul_rn(__fsub_rn(bx, c.off_x), c.scale_x);
+    const float hh = __fmul_rn(bh, c.scale_y), ww = __fmul_rn(bw, c.scale_x);
     const float hy = __fdiv_rn(hh, 2.0f), hx = __fdiv_rn(ww, 2.0f);
     float4 box;
-    box.x = __fmul_rn(__fsub_rn(cy, hy), a.image_h);
-    box.y = __fmul_rn(__fsub_rn(cx, hx), a.image_w);
-    box.z = __fmul_rn(__fadd_rn(cy, hy), a.image_h);
-    box.w = __fmul_rn(__fadd_rn(cx, hx), a.image_w);
+    box.x = __fmul_rn(__fsub_rn(cy, hy), c.image_h);
+    box.y = __fmul_rn(__fsub_rn(cx, hx), c.image_w);
+    box.z = __fmul_rn(__fadd_rn(cy, hy), c.image_h);
+    box.w = __fmul_rn(__fadd_rn(cx, hx), c.image_w);
     reinterpret_cast<float4*>(a.boxes)[img * a.N + i] = box;
     // yolo_boxes_and_scores (model.py:188) + the mask of yolo_eval (model.py:212)
-    for (int c = 0; c < a.num_classes; ++c) {
-        const float score = __fmul_rn(conf, sigmoid_ref(t[5 + c]));
-        if (a.all_scores) a.all_scores[(img * a.N + i) * a.num_classes + c] = score;
+    for (int cl = 0; cl < a.num_classes; ++cl) {
+        const float score = __fmul_rn(conf, sigmoid_ref(t[5 + cl]));
+        if (a.all_scores) a.all_scores[(img * a.N + i) * a.num_classes + cl] = score;
         if (score >= a.score_thr) {
-            const size_t ic = img * a.num_classes + c;
+            const size_t ic = img * a.num_classes + cl;
             const int slot = atomicAdd(&a.counts[ic], 1);
             a.keys[ic * a.NP + slot] =
                 (static_cast<unsigned long long>(__float_as_uint(score)) << 32) | (0xffffffffu - unsigned(i));
         }
     }
+}
+
+__global__ __launch_bounds__(256) void whenet_yolo_decode_kernel(YoloArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.N) return;
+    const MixedFrameCorrection c{a.image_h, a.image_w, a.off_y, a.off_x, a.scale_y, a.scale_x};
+    yolo_decode_box(a, c, blockIdx.y, i);                       // image of a batch: every array is [images][...]
+}
+
+// images of different shapes (a mixed clip): image blockIdx.y has its own correction values
+__global__ __launch_bounds__(256) void whenet_yolo_decode_mixed_kernel(YoloArgs a, YoloMixed m) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.N) return;
+    yolo_decode_box(a, m.img[blockIdx.y], blockIdx.y, i);
 }
 
 // TensorFlow's IOU() (core/kernels/non_max_suppression_op.cc), float32, every operation rounded on its own
@@ -168,12 +182,28 @@ __global__ __launch_bounds__(NMS_THREADS) void whenet_yolo_nms_kernel(YoloArgs a
 
 int yolo_max_select() { return NMS_MAX_SELECT; }
 
-void launch_yolo_eval(const YoloArgs& a, hipStream_t stream) {
+// model.py:158-162, float32 like the graph: new_shape = round(image_shape * min(input_shape / image_shape))
+MixedFrameCorrection yolo_correction(float input_h, float input_w, float image_h, float image_w) {
+    MixedFrameCorrection c{};
+    c.image_h = image_h, c.image_w = image_w;
+    const float ry = input_h / image_h, rx = input_w / image_w;
+    const float r = ry < rx ? ry : rx;
+    const float new_h = std::nearbyintf(image_h * r), new_w = std::nearbyintf(image_w * r);      // half to even
+    c.off_y = (input_h - new_h) / 2.0f / input_h;
+    c.off_x = (input_w - new_w) / 2.0f / input_w;
+    c.scale_y = input_h / new_h;
+    c.scale_x = input_w / new_w;
+    return c;
+}
+
+void launch_yolo_eval(const YoloArgs& a, hipStream_t stream, const YoloMixed* mixed) {
     WHENET_REQUIRE(a.N > 0 && a.num_classes > 0 && a.max_boxes > 0 && a.max_boxes <= a.N, WHENET_EINVAL,
                    "yolo_eval: bad sizes (max_boxes must be 1..number of boxes)");
     const unsigned images = a.images > 1 ? unsigned(a.images) : 1u;
     WHENET_HIP_CHECK(hipMemsetAsync(a.counts, 0, size_t(images) * a.num_classes * sizeof(int), stream));
-    hipLaunchKernelGGL(whenet_yolo_decode_kernel, dim3((a.N + 255) / 256, images), dim3(256), 0, stream, a);
+    WHENET_REQUIRE(mixed == nullptr || images <= unsigned(MIXED_MAX_FRAMES), WHENET_EINVAL, "yolo_eval: too many images of different shapes");
+    if (mixed) hipLaunchKernelGGL(whenet_yolo_decode_mixed_kernel, dim3((a.N + 255) / 256, images), dim3(256), 0, stream, a, *mixed);
+    else hipLaunchKernelGGL(whenet_yolo_decode_kernel, dim3((a.N + 255) / 256, images), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(whenet_yolo_nms_kernel, dim3(a.num_classes, images), dim3(NMS_THREADS), 0, stream, a);
     WHENET_HIP_CHECK(hipGetLastError());
 }

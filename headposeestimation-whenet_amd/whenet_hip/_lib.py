@@ -84,6 +84,11 @@ _PROTOS = {
     "whenet_op_letterbox_batch": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "whenet_yolo_eval_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float,
                                          C.c_float, C.c_float, C.c_int, _P, _P, _P, _P, _P]),
+    "whenet_clip_begin_mixed": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "whenet_op_letterbox_mixed": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_yolo_eval_mixed": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_float, C.c_float,
+                                         C.c_int, _P, _P, _P, _P, _P]),
+    "whenet_letterbox_cache_stats": (C.c_int, [_P, C.POINTER(C.c_int32 * 4)]),
     "whenet_op_head_compact": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
@@ -148,6 +153,36 @@ def clip_u8(frames) -> np.ndarray:
     if not 1 <= a.shape[0] <= MAX_CLIP_FRAMES:
         raise ValueError(f"a clip holds 1..{MAX_CLIP_FRAMES} frames, got {a.shape[0]}")
     return np.ascontiguousarray(a)
+
+
+MAX_FRAME_SIDE = 8192     # LETTERBOX_MAX_FRAME_SIDE: a frame row is staged in LDS
+
+
+def mixed_u8(frames) -> list:
+    """The frames of a MIXED clip as a list of contiguous uint8 [H_i,W_i,3] arrays, each of its own size: 1..16 frames, sides
+    1..8192.  ValueError otherwise (a single frame, a wrong dtype or rank, an empty or oversized frame)."""
+    if isinstance(frames, np.ndarray):
+        if frames.ndim != 4:
+            raise ValueError(f"a mixed clip is a list of uint8 [H,W,3] frames, got an array of shape {frames.shape}")
+        frames = list(frames)
+    try:
+        items = [np.asarray(f) for f in frames]
+    except TypeError:
+        raise ValueError(f"a mixed clip is a list of uint8 [H,W,3] frames, got {type(frames).__name__}") from None
+    if not 1 <= len(items) <= MAX_CLIP_FRAMES:
+        raise ValueError(f"a clip holds 1..{MAX_CLIP_FRAMES} frames, got {len(items)}")
+    for i, f in enumerate(items):
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+            raise ValueError(f"frame {i} must be uint8 [H,W,3], got {f.dtype} {f.shape}")
+        if not (1 <= f.shape[0] <= MAX_FRAME_SIDE and 1 <= f.shape[1] <= MAX_FRAME_SIDE):
+            raise ValueError(f"frame {i} is {f.shape[0]} x {f.shape[1]}: sides must be 1..{MAX_FRAME_SIDE}")
+    return [np.ascontiguousarray(f) for f in items]
+
+
+def _mixed_args(frames):
+    """(pointer array, heights, widths) of mixed_u8's list, as the three array arguments of the mixed entry points."""
+    ptrs = (_P * len(frames))(*[f.ctypes.data for f in frames])
+    return ptrs, np.array([f.shape[0] for f in frames], np.int32), np.array([f.shape[1] for f in frames], np.int32)
 
 
 def check_max_heads(max_heads) -> None:
@@ -603,6 +638,68 @@ class Handle:
                                                      float(iou_threshold), int(max_boxes), _ptr(boxes), _ptr(scores), _ptr(classes),
                                                      _ptr(index), _ptr(counts)))
         return [tuple(a[f, :counts[f]].copy() for a in (boxes, scores, classes, index)) for f in range(F)]
+
+    # ---- mixed clips: frames of different sizes per submission; the letterbox geometry cache ---------
+    def clip_begin_mixed(self, frames: list, bgr: bool = True) -> int:
+        """Upload the frames of a mixed clip (a list of uint8 [H_i,W_i,3] arrays, each of its own size) once, packed back to back; the
+        ticket goes to clip_detect_heads / collect_clip like `clip_begin`'s."""
+        frames = mixed_u8(frames)
+        ptrs, fh, fw = _mixed_args(frames)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_mixed(self._h, ptrs, len(frames), _ptr(fh), _ptr(fw), BGR if bgr else RGB, C.byref(t)))
+        return t.value
+
+    def op_letterbox_mixed(self, frames: list, size=(416, 416), bgr: bool = True, want_u8: bool = True, want_f32: bool = True):
+        """`op_letterbox` of F frames of their own sizes in one call: (canvas uint8 [F,h,w,3], image float32 [F,h,w,3])."""
+        frames = mixed_u8(frames)
+        F = len(frames)
+        oh, ow, _, _ = self._letterbox_outputs(size, False, False)
+        u8 = np.empty((F, oh, ow, 3), np.uint8) if want_u8 else None
+        f32 = np.empty((F, oh, ow, 3), np.float32) if want_f32 else None
+        ptrs, fh, fw = _mixed_args(frames)
+        self._check(self._lib.whenet_op_letterbox_mixed(self._h, ptrs, F, _ptr(fh), _ptr(fw), BGR if bgr else RGB, oh, ow, _ptr(u8),
+                                                        _ptr(f32)))
+        return u8, f32
+
+    def yolo_eval_mixed(self, yolo_outputs, anchors, num_classes: int, image_shapes, max_boxes: int = 20,
+                        score_threshold: float = .6, iou_threshold: float = .5):
+        """`yolo_eval_batch` of F images that each have their own shape: image_shapes [F,2] = (h, w) per image -> a list of F tuples
+        (boxes [k,4], scores [k], classes [k], index [k]), each what `yolo_eval(..., debug=True)[:4]` returns for that image alone."""
+        maps = [np.ascontiguousarray(m, np.float32) for m in yolo_outputs]
+        F = maps[0].shape[0] if maps and maps[0].ndim == 4 else 0
+        for m in maps:
+            if m.ndim != 4 or m.shape[0] != F or m.shape[3] != 3 * (5 + num_classes):
+                raise ValueError(f"yolo_eval_mixed: feature map of shape {m.shape}, expected [{F}, gh, gw, {3 * (5 + num_classes)}]")
+        if not 1 <= F <= MAX_CLIP_FRAMES:
+            raise ValueError(f"yolo_eval_mixed: {F} images, expected 1..{MAX_CLIP_FRAMES}")
+        try:
+            shapes = np.ascontiguousarray(image_shapes, np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("yolo_eval_mixed: image_shapes must be [F,2] = (h, w) per image") from None
+        if shapes.shape != (F, 2) or not (shapes > 0).all():
+            raise ValueError(f"yolo_eval_mixed: image_shapes must be [{F},2] = positive (h, w) per image, got shape {shapes.shape}")
+        if max_boxes < 1:
+            raise ValueError("yolo_eval_mixed: max_boxes must be >= 1")
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 2)
+        L = len(maps)
+        ptrs = (_P * L)(*[_ptr(m) for m in maps])
+        gh = np.array([m.shape[1] for m in maps], np.int32)
+        gw = np.array([m.shape[2] for m in maps], np.int32)
+        n_all = int(sum(m.shape[1] * m.shape[2] * 3 for m in maps))
+        cap = num_classes * min(int(max_boxes), n_all)
+        boxes, scores = np.empty((F, cap, 4), np.float32), np.empty((F, cap), np.float32)
+        classes, index, counts = np.empty((F, cap), np.int32), np.empty((F, cap), np.int32), np.zeros(F, np.int32)
+        self._check(self._lib.whenet_yolo_eval_mixed(self._h, ptrs, F, _ptr(gh), _ptr(gw), L, _ptr(anchors), anchors.shape[0], num_classes,
+                                                     _ptr(shapes), float(score_threshold), float(iou_threshold), int(max_boxes),
+                                                     _ptr(boxes), _ptr(scores), _ptr(classes), _ptr(index), _ptr(counts)))
+        return [tuple(a[f, :counts[f]].copy() for a in (boxes, scores, classes, index)) for f in range(F)]
+
+    def letterbox_cache_stats(self) -> dict:
+        """The letterbox geometry cache of the handle's engines (option "letterbox_cache", 1..32 entries per engine, default 16):
+        {"entries", "hits", "misses", "host_waits"}.  A warmed set of frame sizes costs no miss and no wait."""
+        out = (C.c_int32 * 4)()
+        self._check(self._lib.whenet_letterbox_cache_stats(self._h, C.byref(out)))
+        return dict(zip(("entries", "hits", "misses", "host_waits"), (int(v) for v in out)))
 
     def op_head_compact(self, valid, count, max_heads: int):
         """The numbering of a clip's heads alone: valid int32 [F,K], count int32 [F] -> (row int32 [F,K], slot_of_row int32

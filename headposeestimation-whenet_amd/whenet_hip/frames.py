@@ -25,7 +25,9 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
   * a caller that has the next frames in hand (a video file, a rig of identical cameras) sends a CLIP: `begin_clip(frames)`,
     `detect_heads_clip()`, `collect_clip()` put F frames of one size through letterbox, detector, selection, head plans, crops
     and pose as one submission.  The heads that have a window are compacted on the device, so the forward runs over
-    `max_heads` rows, not over F x max_boxes; every frame's result is bit for bit what `begin; detect_heads; collect` returns.
+    `max_heads` rows, not over F x max_boxes; every frame's result is bit for bit what `begin; detect_heads; collect` returns;
+  * frames of DIFFERENT sizes (a rig of different cameras, several files behind one handle) travel as a clip too:
+    `begin_clip_mixed(frames)` in the place of `begin_clip`, the other two calls and the contract unchanged.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -152,6 +154,20 @@ class FramePipeline:
         frames = _lib.clip_u8(frames)
         ticket = self._h.clip_begin(frames, bgr=self._bgr)
         self._begun_clip = (ticket, frames.shape[0])
+
+    def begin_clip_mixed(self, frames) -> None:
+        """A clip of frames of DIFFERENT sizes (several cameras, several files), step 1: upload a list of 1..16 uint8 [H_i,W_i,3]
+        frames, packed back to back, with one copy.  From here on it is a clip like `begin_clip()`'s: `detect_heads_clip()` and
+        `collect_clip()` follow, and frame f returns what `begin(); detect_heads(); collect()` return for it alone."""
+        if self._begun is not None:
+            raise ValueError("the frame begun last has no heads yet: heads() first")
+        if self._begun_clip is not None:
+            raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
+        if len(self._pending) >= self._depth:
+            raise ValueError(f"{self._depth} frames already in flight: collect() first")
+        frames = _lib.mixed_u8(frames)
+        ticket = self._h.clip_begin_mixed(frames, bgr=self._bgr)
+        self._begun_clip = (ticket, len(frames))
 
     def _begun_frame(self, what: str):
         """The frame begun last, for the calls that work on ONE frame."""

@@ -451,6 +451,43 @@ WHENET_API int whenet_yolo_eval_batch(whenet_t* h, const float* const* feats, in
 WHENET_API int whenet_op_head_compact(whenet_t* h, const int32_t* valid, const int32_t* count, int num_frames, int slots_per_frame,
                            int max_heads, int32_t* row, int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
 
+/* ---- MIXED CLIPS: frames of different sizes in one submission, and the letterbox geometry cache (additions to ABI 6).  A rig
+ * of different cameras, or several files served by one handle, sends frames whose sizes differ.  Only the stages before and
+ * after the detector body depend on the frame size (the letterbox, the box correction of the decode, the head windows and the
+ * crops); the body, the selection and the forward see [F][out_h][out_w] canvases and slot arrays either way.  Frame f of a
+ * mixed clip returns, bit for bit, what whenet_frame_begin + whenet_frame_detect_heads + whenet_collect_detect return for it alone.
+ *   whenet_clip_begin_mixed  stands for one `ret, frame = cap.read()` (demo_video.py:49-53) on each of F sources, 1 <= F <= 16:
+ *                  frames[f] = uint8 [frame_h[f]][frame_w[f]][3], sides 1..8192, one channel order.  The frames are packed back
+ *                  to back (no padding) with one pinned staging copy and one asynchronous H2D.  The ticket goes to
+ *                  whenet_clip_detect_heads and whenet_collect_clip exactly as whenet_clip_begin's does (demo_video.py:54-58 per
+ *                  frame; the letterbox of every frame is yolo_v3/utils.py:23-34 with that frame's size, the box correction
+ *                  yolo_v3/model.py:153-178 with that frame's image_shape); a clip that never gets its heads is released by
+ *                  whenet_frame_heads(h, ticket, NULL, 0) + whenet_collect.  WHENET_EINVAL, with the frame's index in
+ *                  whenet_last_error and before anything is enqueued or a slot is taken: F outside 1..16, a NULL frame, a side
+ *                  outside 1..8192, more frames than option "letterbox_cache"; from whenet_clip_detect_heads: a frame whose
+ *                  resized image would be empty at that detector input (the ticket stays releasable).
+ *   whenet_op_letterbox_mixed  letterbox_image (yolo_v3/utils.py:23-34, yolo_postprocess.py:186-196) of F host frames of their
+ *                  own sizes -> canvas_u8 [F][out_h][out_w][3] and / or image_f32, as whenet_op_letterbox per frame.
+ *   whenet_yolo_eval_mixed  whenet_yolo_eval_batch (yolo_v3/model.py:193-232) for images of different shapes: image_shapes
+ *                  [num_images][2] = (h, w) of each image, as yolo_correct_boxes (model.py:153-178) takes image_shape, in place
+ *                  of the two scalars; every other argument and the output layout as there.
+ *   whenet_letterbox_cache_stats  out = {entries, hits, misses, host_waits} of the letterbox geometry cache, summed over the
+ *                  handle's engines.  Every engine keeps the resample tables (Pillow's coefficients, utils.py:31) of up to N
+ *                  geometries (frame_h, frame_w, out_h, out_w) on the device, N = option "letterbox_cache", 1..32, default 16
+ *                  (setting it waits for the handle's work and empties the cache).  A frame whose geometry is cached enqueues no
+ *                  table copy and waits for nothing; a new geometry replaces the least recently used one and waits at most --
+ *                  host_waits counts it -- for that entry's own previous table copy, never for the stream: sources of different
+ *                  sizes alternating on one handle keep the pipeline of whenet_frame_detect_heads enqueue-only. */
+WHENET_API int whenet_clip_begin_mixed(whenet_t* h, const uint8_t* const* frames, int num_frames, const int* frame_h, const int* frame_w,
+                            int channel_order, int* ticket);
+WHENET_API int whenet_op_letterbox_mixed(whenet_t* h, const uint8_t* const* frames, int num_frames, const int* frame_h, const int* frame_w,
+                              int channel_order, int out_h, int out_w, uint8_t* canvas_u8, float* image_f32);
+WHENET_API int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w,
+                           int num_layers, const float* anchors, int num_anchors, int num_classes, const float* image_shapes,
+                           float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
+                           int32_t* classes, int32_t* index, int32_t* counts);
+WHENET_API int whenet_letterbox_cache_stats(whenet_t* h, int32_t out[4]);
+
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
  * recorded on the chain's stream between consecutive kernel launches; a launch's time is
