@@ -98,26 +98,43 @@ std::vector<DetLayer> detector_table(int kind, int out_filters) {
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// Keras HWIO kernel (scaled per out-channel) -> dconv.hip's operand image [k-step][32-channel tile][lane][8]: element j of lane l is
-// out-channel 32 nt + (l & 31), tap ks / CS, in-channel 16 (ks % CS) + 8 (l >> 5) + j; zero beyond Cout and beyond the true Cin
-// (the first layer's 3 channels are padded to 16).
-std::vector<half_t> pack_dconv(const float* w, const std::vector<double>& scale, int k, int cin, int cout) {
-    const int cinp = (cin + 15) / 16 * 16, CS = cinp / 16, KS = k * k * CS, NT32 = (cout + 31) / 32;
-    std::vector<half_t> out(size_t(KS) * NT32 * 64 * 8, half_t(0));
+// Keras HWIO kernel (scaled per out-channel) -> dconv.hip's operand image [k-step][32-channel tile][lane][V], V = 8 (binary16) or
+// 4 (float32) elements of a 16-byte fragment: element j of lane l is out-channel 32 nt + (l & 31), tap ks / CS, in-channel
+// 2 V (ks % CS) + V (l >> 5) + j; zero beyond Cout and beyond the true Cin (the first layer's 3 channels are padded to a k-step:
+// 16 / 8).  The float64 product is rounded ONCE to T.
+template <typename T>
+std::vector<T> pack_dconv(const float* w, const std::vector<double>& scale, int k, int cin, int cout) {
+    constexpr int V = Vec<T>::V, KC = 2 * V;
+    const int cinp = (cin + KC - 1) / KC * KC, CS = cinp / KC, KS = k * k * CS, NT32 = (cout + 31) / 32;
+    std::vector<T> out(size_t(KS) * NT32 * 64 * V, T(0));
     for (int ks = 0; ks < KS; ++ks)
         for (int nt = 0; nt < NT32; ++nt)
             for (int l = 0; l < 64; ++l) {
                 const int co = nt * 32 + (l & 31);
                 if (co >= cout) continue;
-                for (int j = 0; j < 8; ++j) {
-                    const int tap = ks / CS, ci = 16 * (ks % CS) + 8 * (l >> 5) + j;
+                for (int j = 0; j < V; ++j) {
+                    const int tap = ks / CS, ci = KC * (ks % CS) + V * (l >> 5) + j;
                     if (ci >= cin) continue;
                     const double v = double(w[(size_t(tap) * cin + ci) * cout + co]) * scale[size_t(co)];
-                    out[((size_t(ks) * NT32 + nt) * 64 + l) * 8 + j] = half_t(v);
+                    out[((size_t(ks) * NT32 + nt) * 64 + l) * V + j] = T(v);
                 }
             }
     return out;
 }
+
+// the image of either storage type on the device
+void upload_dconv(DeviceBuffer& dst, int dtype, const float* w, const std::vector<double>& scale, int k, int cin, int cout) {
+    auto put = [&](const auto& packed) {
+        const size_t bytes = packed.size() * sizeof(packed[0]);
+        dst.reset(bytes, "detector weights");
+        WHENET_HIP_CHECK(hipMemcpy(dst.as<void>(), packed.data(), bytes, hipMemcpyHostToDevice));
+    };
+    if (dtype == WHENET_F32) put(pack_dconv<float>(w, scale, k, cin, cout));
+    else put(pack_dconv<half_t>(w, scale, k, cin, cout));
+}
+
+size_t det_esize(int dtype) { return dtype == WHENET_F32 ? sizeof(float) : sizeof(half_t); }
+int det_kc(int dtype) { return dtype == WHENET_F32 ? 8 : 16; }        // channels of a k-step: what the first layer's 3 are padded to
 
 const RawTensor& need(const std::map<std::string, RawTensor>& t, const std::string& name, std::vector<uint32_t> dims) {
     const auto it = t.find(name);
@@ -147,7 +164,7 @@ struct DetPlan {
     int n = 0, H = 0, W = 0;
     std::vector<int> rh, rw, slot;                 // per row: output height, width and activation slot (-1: an output map)
     std::vector<DeviceBuffer> slots;
-    DeviceBuffer img16, img_f32, partial;
+    DeviceBuffer img, img_f32, partial;           // img: the first layer's input, [n,H,W,16] binary16 or [n,H,W,8] float32
     DeviceBuffer maps[3];
     int gh[3] = {0, 0, 0}, gw[3] = {0, 0, 0};
     hipGraphExec_t exec = nullptr;
@@ -158,6 +175,7 @@ struct DetPlan {
 
 struct Detector {
     int kind = 0, out_filters = 0, num_maps = 0;
+    int dtype = WHENET_F16;                        // storage of weights and activations (option "detector_dtype" when it was loaded)
     std::vector<DetLayer> table;
     std::vector<DetConv> convs;                    // by row (empty for pools)
     DeviceBuffer lut;                              // letterbox.hip's /255 table
@@ -178,6 +196,7 @@ void Engine::detector_load(const void* blob, size_t nbytes) {
                    "detector snapshot: " + det_name("dconv%03d/kernel", nconv - 1) + ": not a convolution kernel");
     auto det = std::make_shared<Detector>();
     det->kind = kind;
+    det->dtype = det_dtype_;
     det->out_filters = int(last.dims[3]);
     det->table = detector_table(kind, det->out_filters);
     det->convs.resize(det->table.size());
@@ -203,11 +222,9 @@ void Engine::detector_load(const void* blob, size_t nbytes) {
             const RawTensor& b = need(t, det_name("dconv%03d/bias", ci), {cout});
             for (uint32_t c = 0; c < cout; ++c) bias[c] = b.data[c];
         }
-        const std::vector<half_t> packed = pack_dconv(w.data, scale, L.k, L.cin, L.cout);
         DetConv& dc = det->convs[r];
-        dc.w.reset(packed.size() * sizeof(half_t), "detector weights");
+        upload_dconv(dc.w, det->dtype, w.data, scale, L.k, L.cin, L.cout);
         dc.bias.reset(bias.size() * sizeof(float), "detector weights");
-        WHENET_HIP_CHECK(hipMemcpy(dc.w.as<void>(), packed.data(), packed.size() * sizeof(half_t), hipMemcpyHostToDevice));
         WHENET_HIP_CHECK(hipMemcpy(dc.bias.as<void>(), bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
         det->num_maps += L.is_output;
         ++ci;
@@ -227,6 +244,7 @@ void Engine::share_detector(const Engine& from) {
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     det_plans_.clear();
     det_ = from.det_;
+    if (det_) det_dtype_ = det_->dtype;
 }
 
 void Engine::require_detector() const {
@@ -252,7 +270,7 @@ void out_dims(const DetLayer& L, int H, int W, int* Ho, int* Wo) {
 
 // The plan of (n, H, W): every row's size, its activation slot (a slot is free again after the last row that reads it: two
 // ping-pong slots plus one per live route / skip tensor), the output maps, the split-K workspace, and the captured forward
-// from the binary16 image to the maps.
+// from the input image (img) to the maps.  Activations and the image are sized by the detector's element type.
 DetPlan& Engine::detector_plan(int n, int H, int W) {
     const Detector& det = *det_;
     const auto key = std::make_tuple(n, H, W);
@@ -277,7 +295,7 @@ DetPlan& Engine::detector_plan(int n, int H, int W) {
         WHENET_REQUIRE(p.rh[r] >= 1 && p.rw[r] >= 1, WHENET_EINVAL, "detector: input too small");
         for (int s : {L.src0, L.src1, L.skip})
             if (s >= 0) last_use[size_t(s)] = int(r);
-        if (!L.is_output) slot_bytes = std::max(slot_bytes, size_t(n) * p.rh[r] * p.rw[r] * L.cout * sizeof(half_t));
+        if (!L.is_output) slot_bytes = std::max(slot_bytes, size_t(n) * p.rh[r] * p.rw[r] * L.cout * det_esize(det.dtype));
         if (L.op == DET_CONV) {
             const int splits = dconv_splits(L.k, std::max(L.cin, 16), L.cout, p.rh[r], p.rw[r]);
             if (splits > 1) partial_floats = std::max(partial_floats, size_t(splits) * n * p.rh[r] * p.rw[r] * (size_t((L.cout + 31) / 32) * 32));
@@ -306,7 +324,7 @@ DetPlan& Engine::detector_plan(int n, int H, int W) {
         owner[s] = int(r);
         p.slot[r] = int(s);
     }
-    p.img16.reset(size_t(n) * H * W * 16 * sizeof(half_t), "detector activations");
+    p.img.reset(size_t(n) * H * W * det_kc(det.dtype) * det_esize(det.dtype), "detector activations");
     p.img_f32.reset(size_t(n) * H * W * 3 * sizeof(float), "detector activations");
     p.partial.reset(partial_floats * sizeof(float), "detector activations");
 
@@ -326,31 +344,32 @@ DetPlan& Engine::detector_plan(int n, int H, int W) {
     return *det_plans_.emplace(key, std::move(plan)).first->second;
 }
 
-// the launches of one forward, binary16 image -> output maps, on s
+// the launches of one forward, input image -> output maps, on s
 void Engine::enqueue_detector(DetPlan& p, hipStream_t s) {
     const Detector& det = *det_;
     int m = 0;
-    auto act = [&](int row) { return row < 0 ? p.img16.as<half_t>() : p.slots[size_t(p.slot[size_t(row)])].as<half_t>(); };
+    auto act = [&](int row) { return row < 0 ? p.img.as<void>() : p.slots[size_t(p.slot[size_t(row)])].as<void>(); };
     for (size_t r = 0; r < det.table.size(); ++r) {
         const DetLayer& L = det.table[r];
         const int full = L.src1 >= 0 ? L.src1 : L.src0;
         const int h = full < 0 ? p.H : p.rh[size_t(full)], w = full < 0 ? p.W : p.rw[size_t(full)];
         if (L.op == DET_POOL) {
-            launch_dpool(act(L.src0), act(int(r)), p.n, h, w, L.cin, L.stride, s);
+            launch_dpool(act(L.src0), act(int(r)), det.dtype, p.n, h, w, L.cin, L.stride, s);
             continue;
         }
         DconvArgs a{};
         a.in0 = act(L.src0);
         a.in1 = L.src1 >= 0 ? act(L.src1) : nullptr;
-        a.w = det.convs[r].w.as<half_t>();
+        a.dtype = det.dtype;
+        a.w = det.convs[r].w.as<void>();
         a.bias = det.convs[r].bias.as<float>();
         a.skip = L.skip >= 0 ? act(L.skip) : nullptr;
-        a.out = L.is_output ? p.maps[m++].as<void>() : static_cast<void*>(act(int(r)));
+        a.out = L.is_output ? p.maps[m++].as<void>() : act(int(r));
         a.partial = p.partial.as<float>();
         a.n = p.n, a.H = h, a.W = w;
-        a.C0 = std::max(L.cin0, 16), a.C1 = L.cin - L.cin0;
+        a.C0 = std::max(L.cin0, det_kc(det.dtype)), a.C1 = L.cin - L.cin0;
         a.Ho = p.rh[r], a.Wo = p.rw[r], a.Cout = L.cout, a.k = L.k, a.stride = L.stride, a.leaky = L.leaky, a.f32_out = L.is_output;
-        a.splits = dconv_splits(L.k, a.C0 + a.C1, L.cout, a.Ho, a.Wo);
+        a.splits = dconv_splits(L.k, std::max(L.cin, 16), L.cout, a.Ho, a.Wo);
         launch_dconv(a, s);
     }
 }
@@ -371,7 +390,7 @@ void Engine::detector_forward(const float* image, int n, int H, int W, float* co
     DetPlan& p = detector_plan(n, H, W);
     const size_t pixels = size_t(n) * H * W;
     WHENET_HIP_CHECK(hipMemcpyAsync(p.img_f32.as<void>(), image, pixels * 3 * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_dimage(p.img_f32.as<float>(), nullptr, nullptr, p.img16.as<half_t>(), pixels, stream_);
+    launch_dimage(p.img_f32.as<float>(), nullptr, nullptr, p.img.as<void>(), det_->dtype, pixels, stream_);
     WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
     for (int m = 0; m < det_->num_maps; ++m)
         WHENET_HIP_CHECK(hipMemcpyAsync(maps[m], p.maps[m].as<void>(), p.maps[m].bytes(), hipMemcpyDeviceToHost, stream_));
@@ -387,7 +406,7 @@ int Engine::detect_device(const uint8_t* d_frame, int fh, int fw, int swap_rb, i
     WHENET_REQUIRE(anchors != nullptr && boxes != nullptr && scores != nullptr && classes != nullptr, WHENET_EINVAL, "detect: NULL argument");
     DetPlan& p = detector_plan(1, out_h, out_w);
     const uint8_t* d_canvas = enqueue_letterbox(d_frame, fh, fw, swap_rb, out_h, out_w, true, false).first;
-    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img16.as<half_t>(), size_t(out_h) * out_w, stream_);
+    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img.as<void>(), det_->dtype, size_t(out_h) * out_w, stream_);
     WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
     const float* feats[3] = {p.maps[0].as<float>(), p.maps[1].as<float>(), p.maps[2].as<float>()};
     return yolo_eval_maps(feats, true, p.gh, p.gw, det_->num_maps, anchors, num_anchors, det_->out_filters / 3 - 5, float(fh), float(fw),
@@ -449,7 +468,7 @@ void Engine::frame_detect_heads(int ticket, int out_h, int out_w, const float* a
     DetPlan& p = detector_plan(1, out_h, out_w);
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
     const uint8_t* d_canvas = enqueue_letterbox(slot.frame.d.as<uint8_t>(), slot.fh, slot.fw, slot.swap_rb, out_h, out_w, true, false).first;
-    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img16.as<half_t>(), size_t(out_h) * out_w, stream_);
+    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img.as<void>(), det_->dtype, size_t(out_h) * out_w, stream_);
     WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
     const float* feats[3] = {p.maps[0].as<float>(), p.maps[1].as<float>(), p.maps[2].as<float>()};
     const YoloArgs y = enqueue_yolo_eval(feats, true, p.gh, p.gw, det_->num_maps, anchors, num_anchors, num_classes, float(slot.fh),
@@ -519,7 +538,7 @@ int Engine::clip_detect_heads(int ticket, int out_h, int out_w, const float* anc
     const uint8_t* d_canvas =
         mixed ? enqueue_letterbox_mixed(d_frames, F, slot.clip_fh, slot.clip_fw, slot.clip_off, slot.swap_rb, out_h, out_w, true, false).first
               : enqueue_letterbox(d_frames, slot.fh, slot.fw, slot.swap_rb, out_h, out_w, true, false, F).first;
-    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img16.as<half_t>(), size_t(F) * out_h * out_w, stream_);
+    launch_dimage(nullptr, d_canvas, det_->lut.as<float>(), p.img.as<void>(), det_->dtype, size_t(F) * out_h * out_w, stream_);
     WHENET_HIP_CHECK(hipGraphLaunch(p.exec, stream_));
     const float* feats[3] = {p.maps[0].as<float>(), p.maps[1].as<float>(), p.maps[2].as<float>()};
     float shapes[2 * MIXED_MAX_FRAMES] = {};
@@ -579,41 +598,43 @@ void Engine::op_dconv(const float* in, int n, int H, int W, int cin, const float
     const size_t N = size_t(n), in_elems = in2 ? N * (H / 2) * (W / 2) * cin : N * H * W * cin, in2_elems = in2 ? N * H * W * cin2 : 0;
     const size_t out_elems = N * Ho * Wo * cout;
     const int ctot = cin + cin2;
-    const std::vector<half_t> packed = pack_dconv(kernel, std::vector<double>(size_t(cout), 1.0), k, ctot, cout);
+    const int dtype = det_dtype_;                          // the kernels of the handle's "detector_dtype"
+    const size_t es = det_esize(dtype);
     std::vector<float> biasp(size_t((cout + 31) / 32) * 32, 0.0f);
     std::copy(bias, bias + cout, biasp.begin());
     TempBufs tmp;
     float* d_f32 = static_cast<float*>(tmp.get(std::max({in_elems, in2_elems, out_elems}) * sizeof(float)));
-    half_t* d_in = static_cast<half_t*>(tmp.get(std::max(in_elems, N * H * W * 16) * sizeof(half_t)));
-    half_t* d_in2 = in2 ? static_cast<half_t*>(tmp.get(in2_elems * sizeof(half_t))) : nullptr;
-    half_t* d_skip = skip ? static_cast<half_t*>(tmp.get(out_elems * sizeof(half_t))) : nullptr;
+    void* d_in = tmp.get(std::max(in_elems, N * H * W * det_kc(dtype)) * es);
+    void* d_in2 = in2 ? tmp.get(in2_elems * es) : nullptr;
+    void* d_skip = skip ? tmp.get(out_elems * es) : nullptr;
     void* d_out = tmp.get(out_elems * sizeof(float));
-    void* d_w = tmp.get(packed.size() * sizeof(half_t));
+    DeviceBuffer d_w;
+    upload_dconv(d_w, dtype, kernel, std::vector<double>(size_t(cout), 1.0), k, ctot, cout);
     float* d_b = static_cast<float*>(tmp.get(biasp.size() * sizeof(float)));
-    WHENET_HIP_CHECK(hipMemcpyAsync(d_w, packed.data(), packed.size() * sizeof(half_t), hipMemcpyHostToDevice, stream_));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_b, biasp.data(), biasp.size() * sizeof(float), hipMemcpyHostToDevice, stream_));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in, in_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-    if (cin == 3) launch_dimage(d_f32, nullptr, nullptr, d_in, N * H * W, stream_);       // the body's own input stage
-    else launch_f32_to_act(d_f32, d_in, in_elems, WHENET_F16, stream_);
+    if (cin == 3) launch_dimage(d_f32, nullptr, nullptr, d_in, dtype, N * H * W, stream_);       // the body's own input stage
+    else launch_f32_to_act(d_f32, d_in, in_elems, dtype, stream_);
     if (in2) {
         WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in2, in2_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-        launch_f32_to_act(d_f32, d_in2, in2_elems, WHENET_F16, stream_);
+        launch_f32_to_act(d_f32, d_in2, in2_elems, dtype, stream_);
     }
     if (skip) {
         WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, skip, out_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-        launch_f32_to_act(d_f32, d_skip, out_elems, WHENET_F16, stream_);
+        launch_f32_to_act(d_f32, d_skip, out_elems, dtype, stream_);
     }
     DconvArgs a{};
-    a.in0 = d_in, a.in1 = d_in2, a.w = static_cast<const half_t*>(d_w), a.bias = d_b, a.skip = d_skip, a.out = d_out;
-    a.n = n, a.H = H, a.W = W, a.C0 = std::max(cin, 16), a.C1 = cin2;
+    a.dtype = dtype;
+    a.in0 = d_in, a.in1 = d_in2, a.w = d_w.as<void>(), a.bias = d_b, a.skip = d_skip, a.out = d_out;
+    a.n = n, a.H = H, a.W = W, a.C0 = std::max(cin, det_kc(dtype)), a.C1 = cin2;
     a.Ho = Ho, a.Wo = Wo, a.Cout = cout, a.k = k, a.stride = stride, a.leaky = leaky != 0, a.f32_out = f32_out != 0;
-    a.splits = dconv_splits(k, a.C0 + a.C1, cout, Ho, Wo);
+    a.splits = dconv_splits(k, std::max(cin, 16) + cin2, cout, Ho, Wo);
     a.partial = static_cast<float*>(tmp.get(dconv_partial_floats(a) * sizeof(float)));
     launch_dconv(a, stream_);
     if (f32_out) {
         WHENET_HIP_CHECK(hipMemcpyAsync(out, d_out, out_elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
     } else {
-        launch_act_to_f32(d_out, d_f32, out_elems, WHENET_F16, stream_);
+        launch_act_to_f32(d_out, d_f32, out_elems, dtype, stream_);
         WHENET_HIP_CHECK(hipMemcpyAsync(out, d_f32, out_elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
     }
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -631,12 +652,13 @@ void Engine::op_dpool(const float* in, int n, int H, int W, int c, int stride, f
     const size_t in_elems = size_t(n) * H * W * c, out_elems = size_t(n) * Ho * Wo * c;
     TempBufs tmp;
     float* d_f32 = static_cast<float*>(tmp.get(in_elems * sizeof(float)));
-    half_t* d_in = static_cast<half_t*>(tmp.get(in_elems * sizeof(half_t)));
-    half_t* d_out = static_cast<half_t*>(tmp.get(out_elems * sizeof(half_t)));
+    const int dtype = det_dtype_;
+    void* d_in = tmp.get(in_elems * det_esize(dtype));
+    void* d_out = tmp.get(out_elems * det_esize(dtype));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in, in_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_f32_to_act(d_f32, d_in, in_elems, WHENET_F16, stream_);
-    launch_dpool(d_in, d_out, n, H, W, c, stride, stream_);
-    launch_act_to_f32(d_out, d_f32, out_elems, WHENET_F16, stream_);
+    launch_f32_to_act(d_f32, d_in, in_elems, dtype, stream_);
+    launch_dpool(d_in, d_out, dtype, n, H, W, c, stride, stream_);
+    launch_act_to_f32(d_out, d_f32, out_elems, dtype, stream_);
     WHENET_HIP_CHECK(hipMemcpyAsync(out, d_f32, out_elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
 }

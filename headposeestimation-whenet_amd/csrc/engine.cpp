@@ -249,6 +249,14 @@ void Engine::set_option(const std::string& key, long value) {
     } else if (key == "split_pw") {
         WHENET_REQUIRE(split_ || value == 0, WHENET_EINVAL, "split_pw: the handle was not created as WHENET_F32S");
         split_pw_ = value != 0;
+    } else if (key == "detector_dtype") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "detector_dtype must be 0 (binary16 storage, default) or 1 (float32)");
+        const int dtype = value == 1 ? WHENET_F32 : WHENET_F16;
+        WHENET_REQUIRE(det_ == nullptr || dtype == det_dtype_, WHENET_EINVAL,
+                       "detector_dtype: a detector is attached and its weights were packed when it was loaded: set the option on a "
+                       "handle without a detector, then load again");
+        det_dtype_ = dtype;
+        return;
     } else if (key == "host_pinned_max") {
         WHENET_REQUIRE(value >= 0 && value <= 4096, WHENET_EINVAL, "host_pinned_max must be 0..4096");
         sync();

@@ -552,6 +552,7 @@ class Engine {
     void ensure_host_out(int n);
     int host_pinned_max_ = 8;      // measured round 5: pinned wins up to 8 crops (B=1 f32 420 vs 445 us), loses at 16-32
     int next_ticket_ = 0;
+    int det_dtype_ = WHENET_F16;       // option "detector_dtype": the storage type detector_load packs for, and of op_dconv / op_dpool
     std::shared_ptr<Detector> det_;    // (declared last: its buffers and graphs go first)
     std::map<std::tuple<int, int, int>, std::shared_ptr<DetPlan>> det_plans_;      // by (n, H, W)
 };

@@ -511,27 +511,29 @@ void launch_letterbox_mixed(const uint8_t* d_frames, const LetterboxMixed& clip,
                             uint8_t* d_canvas_u8, float* d_image_f32, int num_cus, hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
-// The detector body's layers (yolo_v3/model.py:20-122) on NHWC binary16 activations: implicit-GEMM convolution on the f16
-// matrix cores with folded BatchNorm, LeakyReLU, residual add and the upsample + concatenate read; 2x2 max-pools; the
-// image -> binary16 input stage.  Device pointers only.
+// The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16
+// matrix cores; WHENET_F32: float32 storage on v_mfma_f32_32x32x2_f32, nothing rounded to binary16): implicit-GEMM convolution
+// with folded BatchNorm, LeakyReLU, residual add and the upsample + concatenate read; 2x2 max-pools; the image input stage.
+// Device pointers only.
 struct DconvArgs {
-    const half_t* in0;     // [n,H,W,C0]; with in1: the HALF-resolution tensor [n,H/2,W/2,C0], read at (y >> 1, x >> 1)
-    const half_t* in1;     // [n,H,W,C1] route tensor (channels C0.. of the concatenation) or nullptr
-    const half_t* w;       // pack_dconv() image
+    const void* in0;       // [n,H,W,C0]; with in1: the HALF-resolution tensor [n,H/2,W/2,C0], read at (y >> 1, x >> 1)
+    const void* in1;       // [n,H,W,C1] route tensor (channels C0.. of the concatenation) or nullptr
+    const void* w;         // pack_dconv() image of the same dtype
     const float* bias;     // [ceil(Cout / 32) * 32]
-    const half_t* skip;    // [n,Ho,Wo,Cout] residual operand or nullptr
-    void* out;             // [n,Ho,Wo,Cout] binary16, or float32 with f32_out (the output convolutions)
+    const void* skip;      // [n,Ho,Wo,Cout] residual operand or nullptr
+    void* out;             // [n,Ho,Wo,Cout] in dtype, or float32 with f32_out (the output convolutions)
     float* partial;        // split-K workspace, dconv_partial_floats() floats (splits > 1)
     int n, H, W, C0, C1;
     int Ho, Wo, Cout, k, stride, leaky, f32_out, splits;
+    int dtype;             // WHENET_F16 or WHENET_F32: the element type of in0, in1, w, skip and out
 };
 int dconv_tile_n(int cout);
-int dconv_splits(int k, int cin, int cout, int Ho, int Wo);      // a function of the layer and the image size, never of the batch
+int dconv_splits(int k, int cin, int cout, int Ho, int Wo);      // a function of the layer and the image size, never of the batch or the dtype
 size_t dconv_partial_floats(const DconvArgs& a);
 void launch_dconv(const DconvArgs& a, hipStream_t stream);
-void launch_dpool(const half_t* in, half_t* out, int n, int H, int W, int C, int stride, hipStream_t stream);
-// [pixels][3] float32, or uint8 through the /255 table of letterbox.hip -> [pixels][16] binary16 (channels 3.. zero)
-void launch_dimage(const float* f32, const uint8_t* u8, const float* lut, half_t* out, size_t pixels, hipStream_t stream);
+void launch_dpool(const void* in, void* out, int dtype, int n, int H, int W, int C, int stride, hipStream_t stream);
+// [pixels][3] float32, or uint8 through the /255 table of letterbox.hip -> [pixels][16] binary16 or [pixels][8] float32 (channels 3.. zero)
+void launch_dimage(const float* f32, const uint8_t* u8, const float* lut, void* out, int dtype, size_t pixels, hipStream_t stream);
 
 // ---- convert.hip ------------------------------------------------------------------------
 void launch_empty(hipStream_t stream);   // boundary calibration for whenet_profile()

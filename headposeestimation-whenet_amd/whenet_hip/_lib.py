@@ -293,8 +293,12 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_P)
 
 
+DETECTOR_DTYPES = {"f16": 0, "f32": 1}        # option "detector_dtype" (include/whenet_hip.h)
+
+
 class Handle:
     """Owns one whenet_t*."""
+    _detector_dtype = 0                        # what option "detector_dtype" was last set to on this handle
 
     def __init__(self, snapshot, device: int = 0, dtype: int = F32):
         lib = load()
@@ -486,8 +490,14 @@ class Handle:
         return res + (index[:k].copy(), all_boxes, all_scores) if debug else res
 
     # ---- the detector body (csrc/detector.cpp) --------------------------------------------------
-    def detector_load(self, snapshot) -> None:
-        """Attach a detector: packed snapshot bytes or a path (whenet_hip/detector_weights.py)."""
+    def detector_load(self, snapshot, dtype: str = "f16") -> None:
+        """Attach a detector: packed snapshot bytes or a path (whenet_hip/detector_weights.py).  `dtype`: "f16" (binary16 storage,
+        the default) or "f32" (float32 storage, the parity-grade body): option "detector_dtype" of the handle, set before the
+        weights are packed.  A handle that holds a detector keeps its dtype (the library says so)."""
+        if dtype not in DETECTOR_DTYPES:
+            raise ValueError(f"detector dtype must be one of {sorted(DETECTOR_DTYPES)}, got {dtype!r}")
+        if DETECTOR_DTYPES[dtype] != self._detector_dtype:
+            self.set_option("detector_dtype", DETECTOR_DTYPES[dtype])
         if isinstance(snapshot, (bytes, bytearray, memoryview)):
             buf = (C.c_char * len(snapshot)).from_buffer_copy(bytes(snapshot))
             self._check(self._lib.whenet_detector_load_from_memory(self._h, C.cast(buf, _P), len(snapshot)))
@@ -770,6 +780,8 @@ class Handle:
     # ---- misc -------------------------------------------------------------------------
     def set_option(self, key: str, value: int):
         self._check(self._lib.whenet_set_option(self._h, key.encode(), int(value)))
+        if key == "detector_dtype":
+            self._detector_dtype = int(value)
 
     def info(self) -> Info:
         out = Info()

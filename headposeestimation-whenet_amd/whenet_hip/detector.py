@@ -2,8 +2,16 @@
 
 `YOLO(**kwargs)` takes the reference's keyword names and defaults; `detect(image)` returns `(boxes, scores, classes)` as numpy,
 as yolo_postprocess.py:205 does: boxes float32 [k,4] (y_min, x_min, y_max, x_max) in image pixels.  Letterbox
-(csrc/letterbox.hip), the Darknet body (csrc/dconv.hip, binary16 storage, f32 accumulation) and the box selection
-(csrc/yolo.hip) run as one chain on the device (`whenet_op_detect`).
+(csrc/letterbox.hip), the Darknet body (csrc/dconv.hip) and the box selection (csrc/yolo.hip) run as one chain on the device
+(`whenet_op_detect`).
+
+The body's arithmetic is chosen by keyword-only `dtype`:
+  * `'f16'` (default): binary16 storage of weights and activations, f32 accumulation -- the fast form.  Its boxes lie up to a few
+    pixels (tiny body) or tens of pixels (full body, random weights) from a float64 evaluation's, so the integer crop windows
+    `process_detection` derives from them can differ from the reference's.
+  * `'f32'`: float32 from the image to the maps on the f32 matrix instructions, nothing rounded to binary16 -- the parity-grade
+    form.  Its boxes lie within hundredths of a pixel of the float64 evaluation's and give the same crop windows, so the pose
+    parity of `WHENet(dtype='f32' | 'f32s')` carries over to the whole frame path.
 
 Differences a caller sees:
   * `model_path` is a packed WHNPACK1 detector snapshot (a path, bytes, or a dict of arrays: whenet_hip/detector_weights.py).
@@ -11,7 +19,9 @@ Differences a caller sees:
     the detector; a `.h5` path raises ValueError saying so.
   * `anchors_path` / `classes_path` are read as the reference reads them; an array of anchors / a list of names is accepted too.
     The defaults name `yolo_anchors.txt` / `head_classes.txt` beside this module, as the reference's `data_file()` does.
-  * `gpu_num` is accepted and ignored; keyword-only `handle=` (any whenet_hip handle, e.g. `WHENet(...)._handle`) or `device=`.
+  * `gpu_num` is accepted and ignored; keyword-only `handle=` (any whenet_hip handle, e.g. `WHENet(...)._handle`) or `device=`,
+    and `dtype=` (above).  A handle that already holds a detector keeps that detector's dtype: another one is a ValueError from
+    the library.
 There is no CPU fallback: without a gfx950 device construction raises WhenetError (ENODEV).
 """
 from __future__ import annotations
@@ -52,7 +62,10 @@ class YOLO(object):
         else:
             return "Unrecognized attribute name '" + n + "'"
 
-    def __init__(self, *, handle=None, device: int = 0, **kwargs):
+    def __init__(self, *, handle=None, device: int = 0, dtype: str = "f16", **kwargs):
+        if dtype not in _lib.DETECTOR_DTYPES:
+            raise ValueError(f"YOLO(dtype=...) must be one of {sorted(_lib.DETECTOR_DTYPES)}, got {dtype!r}")
+        self.dtype = dtype
         unknown = set(kwargs) - set(self._defaults)
         if unknown:
             raise TypeError(f"YOLO() got unexpected keyword arguments {sorted(unknown)}")
@@ -73,7 +86,7 @@ class YOLO(object):
             raise ValueError("Mismatch between model and given anchor and class sizes")
         self._own = handle is None
         self._handle = _lib.Handle.postproc(device) if handle is None else getattr(handle, "_handle", handle)
-        self._handle.detector_load(snapshot)
+        self._handle.detector_load(snapshot, dtype)
         self._handle.detector = self               # FramePipeline.detect finds the anchors and the class count here
 
     @staticmethod

@@ -332,7 +332,8 @@ WHENET_API int whenet_yolo_eval(whenet_t* h, const float* const* feats, const in
                      float* all_scores);
 
 /* ---- the detector's network on the device (ABI 6): yolo_body / tiny_yolo_body (yolo_v3/model.py:20-122) between the letterbox
- * and whenet_yolo_eval, so that YOLO.detect (yolo_postprocess.py:180-205) needs no TensorFlow.  binary16 storage, f32 accumulation.
+ * and whenet_yolo_eval, so that YOLO.detect (yolo_postprocess.py:180-205) needs no TensorFlow.  binary16 storage with f32
+ * accumulation by default, float32 storage by option "detector_dtype".
  *   whenet_detector_load[_from_memory]  attaches a detector to ANY handle (a model handle or a whenet_create_postproc one); replaces
  *                  tiny_yolo_body / yolo_body + load_weights (yolo_postprocess.py:66-79).  A WHNPACK1 container holding
  *                  dconvNNN/kernel (Keras HWIO), dbnNNN/{gamma,beta,moving_mean,moving_variance} and, for the output convolutions,
@@ -348,12 +349,19 @@ WHENET_API int whenet_yolo_eval(whenet_t* h, const float* const* feats, const in
  *                  whenet_op_*): exactly the kernels the body runs.  in [n,H,W,cin] -- with in2 [n,H,W,cin2] it is the
  *                  HALF-resolution tensor [n,H/2,W/2,cin]; kernel HWIO [k,k,cin+cin2,cout]; bias [cout] (a folded BatchNorm's);
  *                  skip [n,Ho,Wo,cout] or NULL; f32_out selects the output convolutions' float32 store (else one rounding to
- *                  binary16).  cin = 3 runs the body's first-layer input stage.  Pool: 2x2 'same', stride 1 or 2.
+ *                  binary16 under detector_dtype 0).  cin = 3 runs the body's first-layer input stage.  Pool: 2x2 'same', stride 1 or 2.
  *   whenet_detector_forward  the body alone = yolo_model.predict(image_data): image float32 [n,H,W,3] (H, W multiples of 32 in
  *                  32..1024, n 1..16) -> maps[l] float32 [n][H/32 << l][W/32 << l][A*(5+C)], coarsest first (3 maps, tiny 2)
  *   whenet_op_detect  YOLO.detect on a host frame: letterbox -> body -> yolo_eval without leaving the device; outputs as
  *                  whenet_yolo_eval's (boxes [C*max_boxes][4], scores, classes; image shape = the frame's)
  *   whenet_frame_detect  the same on a resident frame, between whenet_frame_begin and whenet_frame_heads
+ *   option "detector_dtype" (whenet_set_option; 0 = binary16 storage, default; 1 = float32): the storage type of the body's weights
+ *                  and activations.  Read by whenet_detector_load[_from_memory], which packs the weights for it; every entry point
+ *                  that runs the body (forward, op_detect, frame_detect, frame / clip_detect_heads) follows the LOADED detector;
+ *                  whenet_op_dconv / whenet_op_dpool run the kernels of the handle's current value.  1 keeps float32 from the image
+ *                  to the maps (v_mfma_f32_32x32x2_f32, BatchNorm folded in float64 and rounded once to float32, nothing rounded to
+ *                  binary16): the parity-grade body, whose boxes give the float64 evaluation's crop windows.  Any other value is
+ *                  WHENET_EINVAL; so is a change while a detector is attached (set it on a handle without one, then load again).
  * A handle without a loaded detector answers forward / detect with WHENET_EINVAL and stays usable. */
 WHENET_API int whenet_detector_load(whenet_t* h, const char* snapshot_path);
 WHENET_API int whenet_detector_load_from_memory(whenet_t* h, const void* snapshot, size_t nbytes);

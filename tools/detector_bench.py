@@ -1,9 +1,10 @@
 """Measurements of the detector body (csrc/dconv.hip, csrc/detector.cpp) on seeded synthetic weights.
 
-  python tools/detector_bench.py [--size 416 416] [--reps 30] [--kinds full tiny] [--batch 1]
+  python tools/detector_bench.py [--size 416 416] [--reps 30] [--kinds full tiny] [--batch 1] [--dtype f16|f32]
       Per body: the FLOP count of one image from the layer table, the host-to-host wall time of whenet_detector_forward
       (image upload, captured forward, maps back) and of whenet_op_detect on a 720p frame (upload, letterbox, body, box
-      selection), median and spread over --reps calls after warm-up.  Put it behind
+      selection), median and spread over --reps calls after warm-up.  --dtype is the detector's storage type (option
+      "detector_dtype": f16 = binary16, the default; f32 = the parity-grade float32 body).  Put it behind
       `rocprofv3 --kernel-trace --stats -- python tools/detector_bench.py --reps 10 --kinds full` for per-kernel times.
 """
 from __future__ import annotations
@@ -55,6 +56,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--kinds", nargs="+", default=["full", "tiny"])
+    ap.add_argument("--dtype", choices=["f16", "f32"], default="f16")
     args = ap.parse_args()
     from whenet_hip import _lib, detector_weights as DW, synth
     h, w = args.size
@@ -66,13 +68,13 @@ def main():
         rows = _lib.detector_spec(kind)
         gf = flops_per_image(rows, h, w) / 1e9
         handle = _lib.Handle.postproc(0)
-        handle.detector_load(DW.pack(DW.synthetic(kind, 77 + kind)))
+        handle.detector_load(DW.pack(DW.synthetic(kind, 77 + kind)), dtype=args.dtype)
         med, lo, hi = timed(lambda: handle.detector_forward(image, kind, 18), args.reps)
-        print(f"{name} {h}x{w} batch {args.batch}: {gf:.2f} GFLOP per image; detector_forward {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) "
+        print(f"{name} {args.dtype} {h}x{w} batch {args.batch}: {gf:.2f} GFLOP per image; detector_forward {med:.3f} ms (min {lo:.3f}, max {hi:.3f}) "
               f"= {gf * args.batch / med:.1f} TFLOP/s host to host")
         anchors = np.array(ANCHORS[kind], np.float32)
         med, lo, hi = timed(lambda: handle.op_detect(frame, anchors, 1, (h, w), 0.3, 0.45), args.reps)
-        print(f"{name} {h}x{w}: op_detect of a 720p frame {med:.3f} ms (min {lo:.3f}, max {hi:.3f})")
+        print(f"{name} {args.dtype} {h}x{w}: op_detect of a 720p frame {med:.3f} ms (min {lo:.3f}, max {hi:.3f})")
         handle.close()
 
 
