@@ -459,9 +459,10 @@ bool Engine::head_fused() const {
 // change.  Blocked iff the producer (the split-K project epilogue, pw.hip) and EVERY consumer (the next block's front7.hip and,
 // through its skip, its split-K project; head7.hip behind block 16) know the layout.  front2.hip (the 14 x 14 blocks: measured, the
 // layout gains nothing there -- docs/experiments.md section 13), mb7.hip, front.hip and the unfused kernels do not: tensors they
-// touch stay NHWC, as do the boundaries of the single-stage entry points.
+// touch stay NHWC, as do the boundaries of the single-stage entry points (whenet_op_block_range: its input and its output; the
+// tensors between its blocks are blocked as in the forward, so that the probes reach the blocked producer and readers).
 bool Engine::act_blocked(int index) const {
-    if (act_layout_ == 0 || dtype_ != WHENET_F16 || pw_impl_ != 0 || single_stage_call_) return false;
+    if (act_layout_ == 0 || dtype_ != WHENET_F16 || pw_impl_ != 0 || (single_stage_call_ && !range_call_)) return false;
     if (index < 1 || index > int(blocks_.size())) return false;
     const DevBlock& b = blocks_[size_t(index - 1)];
     if (block_schedule(b).use_mb7 || b.project.K < 320 || b.spec.cout % 16 != 0) return false;     // producer: the split-K epilogue
@@ -486,7 +487,7 @@ void* Engine::enqueue_blocks(int first, int last, const View& v, void* cur, int 
     for (int i = first; i <= last; ++i) {
         void* nxt = (cur == v.x0) ? v.x1 : v.x0;
         enqueue_block(blocks_[size_t(i - 1)], v, cur, nxt, n, s, rec, fold && i <= 2 ? i : 0, b1_dw_done && i == 1,
-                      i > first && act_blocked(i - 1), i < last || last == int(blocks_.size()) ? act_blocked(i) : false);
+                      i > first && act_blocked(i - 1), i < last || (last == int(blocks_.size()) && !range_call_) ? act_blocked(i) : false);
         cur = nxt;
     }
     return cur;

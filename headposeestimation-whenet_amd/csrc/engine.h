@@ -384,6 +384,8 @@ class Engine {
     int se_fuse_tiny_ = 0;             // option "se_fuse_tiny"
     int f2s_mask_ = -1;                // option "f2s_mask" (probes)
     bool single_stage_call_ = false;   // op_block / op_block_range: the schedule must not depend on the test's batch size
+    bool range_call_ = false;          // op_block_range: the tensors BETWEEN its blocks take the layout the forward gives them (act_blocked);
+                                       // its input and its output are NHWC, as the caller passes and reads them
     int lanes_for(int n, int want) const;     // chains a forward of n crops runs as (want = 0: option "lanes")
     // body(i, off, cnt, st): chain i of `lanes` takes crops [off, off + cnt) on stream st (chain 0: s itself), forked from and joined
     // back into s with events

@@ -80,6 +80,7 @@ void Engine::op_block_range(int first, int last, const float* in, int n, float* 
     const void* res = nullptr;
     {
         FlagGuard single(single_stage_call_);
+        FlagGuard range(range_call_);        // (the tensors between the blocks: blocked where the forward blocks them)
         res = enqueue_blocks(first, last, v, v.x0, n, stream_, nullptr);
     }
     launch_act_to_f32(res, d_f32, out_elems, dtype_, stream_);
@@ -103,7 +104,9 @@ void Engine::op_head(const float* in, int n, float* feat, float* logits, float* 
     const bool fuse_head = head_fuse_ && pw_impl_ == 0 && head7_supported(dtype_, head_.K, head_.N, 49);
     HeadsArgs h{};
     if (fuse_head) {          // the forward's form: head conv + pooling as one kernel (head7.hip), Dense heads on its features
-        launch_head7(head7_args(v.x0, d_feat, n), stream_);
+        Head7Args a = head7_args(v.x0, d_feat, n);
+        a.xcd_grouped = xcd_grouped(4, n);   // (option xcd_map bit 4 with option concurrent, as in the forward; the input stays NHWC)
+        launch_head7(a, stream_);
         h.feat_in = d_feat;
     } else {
         launch_pw(head_pw_args(v.x0, v.hc, n), dtype_, pw_impl_, num_cus_, stream_);

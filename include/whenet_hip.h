@@ -518,7 +518,8 @@ WHENET_API int whenet_op_block(whenet_t* h, int index, const float* in, int n,
                     float* expand_out, float* dw_out, float* gate, float* out);
 /* MBConv blocks first..last (1 <= first <= last <= 16) chained exactly as the forward pass chains them -- including
  * option fold12 (block 1's project folded into block 2's expand) when the range holds blocks 1 and 2 -- on input
- * [n,H,W,Cin] of block `first`; out [n,Ho,Wo,Cout] of block `last`. */
+ * [n,H,W,Cin] of block `first`; out [n,Ho,Wo,Cout] of block `last`.  The input and the output are NHWC; the tensors between
+ * the blocks take the layout the forward gives them (option act_layout). */
 WHENET_API int whenet_op_block_range(whenet_t* h, int first, int last, const float* in, int n, float* out);
 /* head: Conv1x1(1280)+BN+Swish + GAP + Dense heads + decode on input [n,7,7,320]:
  *   feat [n,1280], logits [n,252], ypr [n,3], argmax [n,3] */

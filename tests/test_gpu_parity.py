@@ -230,7 +230,10 @@ def test_front7_group_kernel(blob, taps, golden, dt):
             assert rel_err(r7["dw"], r3["dw"]) < t and rel_err(r7["gate"], r3["gate"]) < 2 * t and rel_err(r7["out"], r3["out"]) < 3 * t
             assert rel_err(r7["dw"], taps[f"b{index}/dw"]) < 2 * t and rel_err(r7["out"], taps[f"b{index}/out"]) < 3 * t
             # the same block on a ragged batch of 21: every crop bitwise what it is alone
-            xs = np.concatenate([x] * 11)[:21]
+            # (21 DIFFERENT crops: the two taps scaled per crop by exact powers of two, 2^-5 .. 2^5 -- a batch without a period, so
+            # that a kernel that reads crop i +- 2 for crop i cannot pass)
+            xs = np.concatenate([x] * 11)[:21] * np.exp2(np.arange(21) // 2 - 5).astype(np.float32).reshape(21, 1, 1, 1)
+            assert len({xs[i].tobytes() for i in range(21)}) == 21
             big = h.op_block(index, xs)
             for i in range(21):
                 assert np.array_equal(big["out"][i], r7_like(h, index, xs[i:i + 1])), (index, i)
