@@ -754,6 +754,45 @@ int whenet_op_letterbox_mixed(whenet_t* h, const uint8_t* const* frames, int num
     });
 }
 
+// ---- YUV 4:2:0 ingest (yuv.hip, engine_post.cpp) ----
+int whenet_yuv_to_bgr_host(const whenet_yuv_frame_t* frame, uint8_t* bgr) {
+    if (frame == nullptr || bgr == nullptr) return WHENET_EINVAL;
+    try {
+        whenet::check_yuv_frames("yuv_to_bgr_host", frame, 1);
+        whenet::yuv_to_bgr_host(*frame, bgr);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
+    }
+}
+
+int whenet_op_yuv_to_bgr(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, uint8_t* const* bgr) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_yuv_to_bgr(frames, num_frames, bgr); });
+}
+
+int whenet_frame_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frame, int* ticket) {
+    if (ticket == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        // (argument errors before an engine is taken: a refused frame must not shift the round-robin)
+        whenet::check_yuv_frames("frame_begin_yuv", frame, 1);
+        const size_t idx = h->next % size_t(h->inflight);
+        const int t = h->at(idx).frame_begin_yuv(*frame);
+        h->next = (h->next + 1) % size_t(h->inflight);
+        *ticket = t * MAX_INFLIGHT_ENGINES + int(idx);
+    });
+}
+
+int whenet_clip_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, int* ticket) {
+    if (ticket == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        whenet::check_yuv_frames("clip_begin_yuv", frames, num_frames);
+        const size_t idx = h->next % size_t(h->inflight);
+        const int t = h->at(idx).clip_begin_yuv(frames, num_frames);
+        h->next = (h->next + 1) % size_t(h->inflight);
+        *ticket = t * MAX_INFLIGHT_ENGINES + int(idx);
+    });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

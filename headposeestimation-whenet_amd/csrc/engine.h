@@ -288,6 +288,14 @@ class Engine {
                          int num_anchors, int num_classes, const float* image_shapes, float score_threshold, float iou_threshold,
                          int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index, int32_t* counts);
     void add_letterbox_cache_stats(int32_t out[4]) const;      // entries, hits, misses, host_waits
+    // YUV 4:2:0 INGEST (yuv.hip): the decoder's planes are staged tight in the slot's pinned staging and travel in ONE H2D of
+    // 1.5 bytes per pixel; the conversion kernel runs on the copy stream behind that copy and BEFORE slot.copied is recorded, so the
+    // slot's frame buffer holds the packed BGR frame for every consumer that waits for the event, none of which changes.  The
+    // callers have run check_yuv_frames.  clip_begin_yuv: frames of one size make a clip_begin slot, otherwise a clip_begin_mixed
+    // slot (the packing is the same: back to back); op_yuv_to_bgr is the kernel alone, host to host, packed the same way.
+    int frame_begin_yuv(const whenet_yuv_frame_t& frame);
+    int clip_begin_yuv(const whenet_yuv_frame_t* frames, int nframes);
+    void op_yuv_to_bgr(const whenet_yuv_frame_t* frames, int nframes, uint8_t* const* bgr);
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -308,6 +316,7 @@ class Engine {
         StagedBuffer in, ypr, amax, logits;
         Event copied, done;
         StagedBuffer frame, plan;        // frame submissions: the frame and the crop plans travel instead of the crops
+        DeviceBuffer yuv;                // YUV ingest: the planes on the device (frame.h stages them, frame.d gets the converted frame)
         int frame_ticket = -1;           // resident frame: the ticket whose frame is held here and still waits for its heads
         int fh = 0, fw = 0, swap_rb = 0; //   (tickets are never reused, so a stale value matches nothing)
         StagedBuffer det;                // frame_detect_heads: count | boxes | scores | classes | rects | valid over det_cap rows
@@ -417,6 +426,10 @@ class Engine {
     std::pair<uint8_t*, float*> enqueue_letterbox_mixed(const uint8_t* d_frames, int frames, const int* fh, const int* fw, const size_t* off,
                                                         int swap_rb, int out_h, int out_w, bool want_u8, bool want_f32);
     void ensure_letterbox_outputs(size_t mid_bytes, size_t nout, bool want_u8, bool want_f32);
+    // the planes of the frames, staged tight and back to back in h_stage -> d_planes (one copy) -> d_bgr (one launch) on `s`; frame
+    // f's output starts off[f] bytes into d_bgr.  The three buffers are large enough (yuv_layout).
+    void enqueue_yuv_ingest(const whenet_yuv_frame_t* frames, int nframes, uint8_t* h_stage, uint8_t* d_planes, uint8_t* d_bgr,
+                            const size_t* off, hipStream_t s);
     void letterbox_results_to_host(size_t nout, uint8_t* d_u8, float* d_f32, uint8_t* canvas_u8, float* image_f32);
     // every frame's plan_layout, F <= letterbox_cache: what a mixed clip needs before anything is enqueued
     void check_mixed_geometry(const char* what, int frames, const int* fh, const int* fw, int out_h, int out_w) const;

@@ -335,6 +335,111 @@ int Engine::clip_begin(const uint8_t* frames, int nframes, int fh, int fw, int s
     return slot.frame_ticket;
 }
 
+// ---- YUV 4:2:0 ingest (yuv.hip) ----
+namespace {
+// where frame f's planes lie in the staging / device plane buffer (src) and its BGR bytes in the frame buffer (dst): both back to
+// back, without padding; entry nframes = the bytes of them all
+struct YuvLayout {
+    size_t src[MIXED_MAX_FRAMES + 1] = {}, dst[MIXED_MAX_FRAMES + 1] = {};
+    YuvLayout(const whenet_yuv_frame_t* frames, int nframes) {
+        for (int f = 0; f < nframes; ++f) {
+            src[f + 1] = src[f] + yuv_plane_bytes(frames[f].h, frames[f].w);
+            dst[f + 1] = dst[f] + size_t(frames[f].h) * frames[f].w * 3;
+        }
+    }
+};
+YuvGeom yuv_geom(const whenet_yuv_frame_t& f, size_t src_off, size_t dst_off) {
+    YuvGeom g{};
+    g.src_off = src_off, g.dst_off = dst_off;
+    g.h = f.h, g.w = f.w, g.format = f.format;
+    g.k = yuv_coeffs(f.matrix);
+    return g;
+}
+}  // namespace
+
+void Engine::enqueue_yuv_ingest(const whenet_yuv_frame_t* frames, int nframes, uint8_t* h_stage, uint8_t* d_planes, uint8_t* d_bgr,
+                                const size_t* off, hipStream_t s) {
+    const YuvLayout lay(frames, nframes);
+    bool uniform = true;
+    for (int f = 0; f < nframes; ++f) {
+        yuv_stage_planes(frames[f], h_stage + lay.src[f]);
+        uniform = uniform && frames[f].h == frames[0].h && frames[f].w == frames[0].w && frames[f].format == frames[0].format &&
+                  frames[f].matrix == frames[0].matrix && off[f] == lay.dst[f];
+    }
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_planes, h_stage, lay.src[nframes], hipMemcpyHostToDevice, s));
+    if (nframes == 1) {
+        launch_yuv_to_bgr(d_planes, d_bgr, yuv_geom(frames[0], 0, off[0]), s);
+    } else if (uniform) {
+        launch_yuv_to_bgr_batch(d_planes, d_bgr, yuv_geom(frames[0], 0, 0), nframes, lay.src[1], lay.dst[1], s);
+    } else {
+        YuvMixed clip{};
+        clip.frames = nframes;
+        for (int f = 0; f < nframes; ++f) clip.f[f] = yuv_geom(frames[f], lay.src[f], off[f]);
+        launch_yuv_to_bgr_mixed(d_planes, d_bgr, clip, s);
+    }
+}
+
+void Engine::op_yuv_to_bgr(const whenet_yuv_frame_t* frames, int nframes, uint8_t* const* bgr) {
+    DeviceGuard guard(device_);
+    check_yuv_frames("op_yuv_to_bgr", frames, nframes);
+    WHENET_REQUIRE(bgr != nullptr, WHENET_EINVAL, "op_yuv_to_bgr: NULL argument");
+    for (int f = 0; f < nframes; ++f) WHENET_REQUIRE(bgr[f] != nullptr, WHENET_EINVAL, "op_yuv_to_bgr: output " + std::to_string(f) + " is NULL");
+    const YuvLayout lay(frames, nframes);
+    PinnedBuffer stage;
+    DeviceBuffer d_planes, d_bgr;
+    stage.reset(lay.src[nframes]);
+    d_planes.reset(lay.src[nframes], "hipMalloc");
+    d_bgr.reset(lay.dst[nframes], "hipMalloc");
+    enqueue_yuv_ingest(frames, nframes, stage.as<uint8_t>(), d_planes.as<uint8_t>(), d_bgr.as<uint8_t>(), lay.dst, stream_);
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int f = 0; f < nframes; ++f)
+        WHENET_HIP_CHECK(hipMemcpy(bgr[f], d_bgr.as<uint8_t>() + lay.dst[f], lay.dst[f + 1] - lay.dst[f], hipMemcpyDeviceToHost));
+}
+
+// frame_begin from a decoder's planes: the slot ends up exactly as frame_begin(bgr frame, WHENET_BGR) leaves it
+int Engine::frame_begin_yuv(const whenet_yuv_frame_t& frame) {
+    DeviceGuard guard(device_);
+    check_yuv_frames("frame_begin_yuv", &frame, 1);      // (before a slot is taken)
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const YuvLayout lay(&frame, 1);
+    slot.frame.h.grow(lay.dst[1]);      // (>= the planes' bytes: the size every other user of the staging grows it to)
+    slot.yuv.grow(lay.src[1]);
+    slot.frame.d.grow(lay.dst[1]);
+    enqueue_yuv_ingest(&frame, 1, slot.frame.h.as<uint8_t>(), slot.yuv.as<uint8_t>(), slot.frame.d.as<uint8_t>(), lay.dst, copy_stream());
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = frame.h, slot.fw = frame.w, slot.swap_rb = 1;
+    slot.frame_ticket = finish_submission(slot, 0);
+    return slot.frame_ticket;
+}
+
+int Engine::clip_begin_yuv(const whenet_yuv_frame_t* frames, int nframes) {
+    DeviceGuard guard(device_);
+    check_yuv_frames("clip_begin_yuv", frames, nframes);      // (before a slot is taken)
+    bool one_size = true;
+    for (int f = 1; f < nframes; ++f) one_size = one_size && frames[f].h == frames[0].h && frames[f].w == frames[0].w;
+    WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
+                   "clip_begin_yuv: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const YuvLayout lay(frames, nframes);
+    slot.frame.h.grow(lay.dst[nframes]);
+    slot.yuv.grow(lay.src[nframes]);
+    slot.frame.d.grow(lay.dst[nframes]);
+    enqueue_yuv_ingest(frames, nframes, slot.frame.h.as<uint8_t>(), slot.yuv.as<uint8_t>(), slot.frame.d.as<uint8_t>(), lay.dst, copy_stream());
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = frames[0].h, slot.fw = frames[0].w, slot.swap_rb = 1;
+    if (!one_size) {
+        for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = frames[f].h, slot.clip_fw[f] = frames[f].w;
+        std::copy(lay.dst, lay.dst + nframes + 1, slot.clip_off);
+    }
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = nframes;
+    slot.clip_mixed = !one_size;
+    return slot.frame_ticket;
+}
+
 Engine::Slot& Engine::resident_slot(int ticket, const char* what, int holds) {
     for (Slot& s : slots_)
         if (s.busy && s.ticket == ticket) {

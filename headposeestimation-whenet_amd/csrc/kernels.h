@@ -510,6 +510,38 @@ struct LetterboxMixed {
 void launch_letterbox_mixed(const uint8_t* d_frames, const LetterboxMixed& clip, int swap_rb, const float* d_lut, uint8_t* d_mid,
                             uint8_t* d_canvas_u8, float* d_image_f32, int num_cus, hipStream_t stream);
 
+// ---- yuv.hip ----------------------------------------------------------------------------
+// 4:2:0 YUV planes (NV12 / I420) -> the packed BGR frame [h][w][3]: the integer conversion of include/whenet_hip.h.  The planes of
+// a frame lie TIGHT (pitch removed) in one device buffer: h rows of w luma bytes, then ch = (h + 1) >> 1 rows of 2 cw interleaved
+// bytes (NV12) or ch rows of cw U bytes and ch rows of cw V bytes (I420), cw = (w + 1) >> 1: yuv_plane_bytes() in all.
+constexpr int YUV_MAX_FRAME_SIDE = 8192;
+struct YuvCoeffs {
+    int yoff, cy, cvr, cug, cvg, cub;
+};
+const YuvCoeffs& yuv_coeffs(int matrix);        // throws WHENET_EINVAL
+inline size_t yuv_plane_bytes(int h, int w) { return size_t(h) * w + 2 * size_t((h + 1) >> 1) * ((w + 1) >> 1); }
+// argument checks of a frame list (what: the caller's name; the failing frame's index goes into the text), and the host forms:
+// the conversion itself, and the tight copy of a frame's planes that the device reads
+void check_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes);
+void yuv_to_bgr_host(const whenet_yuv_frame_t& f, uint8_t* bgr);
+void yuv_stage_planes(const whenet_yuv_frame_t& f, uint8_t* dst);
+struct YuvGeom {                                // one frame of a launch
+    unsigned long long src_off, dst_off;        // its planes in d_planes, its first output byte in d_bgr (any alignment)
+    int h, w, format;
+    YuvCoeffs k;
+    int block0;                                 // (mixed) the first workgroup of the frame
+};
+struct YuvMixed {
+    int frames, total_blocks;
+    YuvGeom f[MIXED_MAX_FRAMES];
+};
+// one frame; `frames` frames of g's size, format and matrix, src_stride / dst_stride bytes apart (the frame is grid dimension y);
+// frames of their own sizes, formats and matrices, the records by value in the argument block
+void launch_yuv_to_bgr(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g, hipStream_t stream);
+void launch_yuv_to_bgr_batch(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g, int frames, size_t src_stride, size_t dst_stride,
+                             hipStream_t stream);
+void launch_yuv_to_bgr_mixed(const uint8_t* d_planes, uint8_t* d_bgr, YuvMixed clip, hipStream_t stream);
+
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16
 // matrix cores; WHENET_F32: float32 storage on v_mfma_f32_32x32x2_f32, nothing rounded to binary16): implicit-GEMM convolution

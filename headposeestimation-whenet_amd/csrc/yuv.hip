@@ -1,0 +1,261 @@
+// Frame ingest from a video decoder: 4:2:0 YUV planes (NV12 / I420) -> the packed BGR frame [h][w][3] that the rest of the frame
+// path reads (letterbox.hip, frame.hip).  The conversion is the integer form stated in include/whenet_hip.h: 20 fractional bits,
+// nearest-neighbour chroma (pixel (y, x) takes the sample (y >> 1, x >> 1)), the coefficient rows WHENET_YUV_COEFFS.
+//
+// A thread owns 4 horizontally adjacent pixels on the two rows of one chroma row: the two chroma pairs are fetched once (one dword
+// of an NV12 row), each luma row is one dword, and the 12 output bytes of a row leave as three dwords.  Adjacent lanes own
+// adjacent groups, so a wave reads 256 contiguous luma bytes per row and writes 768 contiguous output bytes.
+//
+// Nothing here assumes an alignment: in a mixed clip the frames lie back to back, so a frame's planes, its first output byte and
+// its row pitch 3 w are aligned to nothing in general.  A dword load is taken only where the address is a multiple of 4 and the
+// four bytes belong to the row; otherwise the bytes are read one by one.  An output row whose address is r mod 4 stores 4 - r head
+// bytes, two aligned dwords (the 12 bytes funnel-shifted) and r tail bytes.  The last group of a row (1..3 pixels when w is no
+// multiple of 4) stores its own bytes one by one: no thread writes a byte outside its pixels, the neighbouring frame starts there.
+#include <algorithm>
+#include <cstring>
+
+#include "kernels.h"
+
+namespace whenet {
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int SHIFT = 20;
+
+__host__ __device__ inline int yuv_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// the 12 bytes B G R of 4 pixels (luma y4: one byte per pixel; chroma terms of pixels 0-1 and 2-3) as three little-endian dwords
+struct ChromaTerms {
+    int r, g, b;
+};
+__device__ __forceinline__ ChromaTerms chroma_terms(const YuvCoeffs& k, int u, int v) {
+    const int d = u - 128, e = v - 128;
+    return {k.cvr * e, -k.cug * d - k.cvg * e, k.cub * d};
+}
+__device__ __forceinline__ uint32_t pixel_bgr(const YuvCoeffs& k, int y, const ChromaTerms& c) {
+    int l = y - k.yoff;
+    l = l < 0 ? 0 : l;
+    const int base = k.cy * l + (1 << (SHIFT - 1));
+    const uint32_t b = uint32_t(yuv_clip8((base + c.b) >> SHIFT));
+    const uint32_t g = uint32_t(yuv_clip8((base + c.g) >> SHIFT));
+    const uint32_t r = uint32_t(yuv_clip8((base + c.r) >> SHIFT));
+    return b | (g << 8) | (r << 16);
+}
+
+__device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int shift_bits) {      // bits [shift, shift + 32) of hi:lo
+    return uint32_t(((uint64_t(hi) << 32) | lo) >> shift_bits);
+}
+
+// one item of a frame: group gx (pixels 4 gx ..) of chroma row p (luma rows 2 p, 2 p + 1)
+__device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, const YuvGeom& g, int item) {
+    const int w = g.w, h = g.h;
+    const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, gw = (w + 3) >> 2;
+    const int p = item / gw, gx = item - p * gw;
+    if (p >= ch) return;
+    const int x = gx << 2;
+    const int n = min(4, w - x);                    // pixels of the group, 1..4
+    const int y0 = p << 1;
+    const int rows = min(2, h - y0);
+    const int cx = x >> 1;
+    const bool two = n > 2;                         // the group has a second chroma sample (cx + 1 < cw)
+    const uint8_t* const chroma = planes + size_t(h) * w;
+
+    int u0, v0, u1, v1;
+    if (g.format == WHENET_YUV_NV12) {
+        const uint8_t* c = chroma + (size_t(p) * cw + cx) * 2;
+        if (two && (reinterpret_cast<uintptr_t>(c) & 3) == 0) {
+            const uint32_t q = *reinterpret_cast<const uint32_t*>(c);
+            u0 = q & 255, v0 = (q >> 8) & 255, u1 = (q >> 16) & 255, v1 = q >> 24;
+        } else {
+            u0 = c[0], v0 = c[1];
+            u1 = two ? int(c[2]) : u0, v1 = two ? int(c[3]) : v0;
+        }
+    } else {
+        const uint8_t* cu = chroma + size_t(p) * cw + cx;
+        const uint8_t* cv = cu + size_t(ch) * cw;
+        if (two && ((reinterpret_cast<uintptr_t>(cu) | reinterpret_cast<uintptr_t>(cv)) & 1) == 0) {
+            const uint32_t qu = *reinterpret_cast<const uint16_t*>(cu), qv = *reinterpret_cast<const uint16_t*>(cv);
+            u0 = qu & 255, u1 = qu >> 8, v0 = qv & 255, v1 = qv >> 8;
+        } else {
+            u0 = cu[0], v0 = cv[0];
+            u1 = two ? int(cu[1]) : u0, v1 = two ? int(cv[1]) : v0;
+        }
+    }
+    const ChromaTerms c0 = chroma_terms(g.k, u0, v0), c1 = chroma_terms(g.k, u1, v1);
+
+    for (int r = 0; r < rows; ++r) {
+        const uint8_t* yp = planes + size_t(y0 + r) * w + x;
+        uint32_t y4;
+        if (n == 4 && (reinterpret_cast<uintptr_t>(yp) & 3) == 0) {
+            y4 = *reinterpret_cast<const uint32_t*>(yp);
+        } else {
+            y4 = yp[0];
+            if (n > 1) y4 |= uint32_t(yp[1]) << 8;
+            if (n > 2) y4 |= uint32_t(yp[2]) << 16;
+            if (n > 3) y4 |= uint32_t(yp[3]) << 24;
+        }
+        const uint32_t p0 = pixel_bgr(g.k, y4 & 255, c0), p1 = pixel_bgr(g.k, (y4 >> 8) & 255, c0);
+        const uint32_t p2 = pixel_bgr(g.k, (y4 >> 16) & 255, c1), p3 = pixel_bgr(g.k, y4 >> 24, c1);
+        const uint32_t w0 = p0 | (p1 << 24), w1 = (p1 >> 8) | (p2 << 16), w2 = (p2 >> 16) | (p3 << 8);
+        uint8_t* dp = bgr + (size_t(y0 + r) * w + x) * 3;
+        if (n == 4) {
+            const int a = int(reinterpret_cast<uintptr_t>(dp) & 3);
+            if (a == 0) {
+                uint32_t* d = reinterpret_cast<uint32_t*>(dp);
+                d[0] = w0, d[1] = w1, d[2] = w2;
+            } else {
+                const int head = 4 - a;
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (j < head) dp[j] = uint8_t(w0 >> (8 * j));
+                uint32_t* d = reinterpret_cast<uint32_t*>(dp + head);
+                d[0] = funnel(w0, w1, 8 * head), d[1] = funnel(w1, w2, 8 * head);
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (j < a) dp[12 - a + j] = uint8_t(w2 >> (8 * (head + j)));
+            }
+        } else {
+            const int nb = 3 * n;                   // 3, 6 or 9 bytes
+#pragma unroll
+            for (int j = 0; j < 9; ++j) {
+                const uint32_t word = j < 4 ? w0 : (j < 8 ? w1 : w2);
+                if (j < nb) dp[j] = uint8_t(word >> (8 * (j & 3)));
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void whenet_yuv_to_bgr_kernel(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, YuvGeom g) {
+    yuv_item(planes + g.src_off, bgr + g.dst_off, g, int(blockIdx.x) * THREADS + int(threadIdx.x));
+}
+
+// F frames of one size, format and matrix: the frame is grid dimension y
+__global__ __launch_bounds__(THREADS) void whenet_yuv_to_bgr_batch_kernel(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, YuvGeom g,
+                                                                          unsigned long long src_stride, unsigned long long dst_stride) {
+    const size_t f = blockIdx.y;
+    yuv_item(planes + g.src_off + f * src_stride, bgr + g.dst_off + f * dst_stride, g, int(blockIdx.x) * THREADS + int(threadIdx.x));
+}
+
+// Frames of their own sizes: workgroup b belongs to the last frame whose block0 is <= b (a scan of at most 16 values, the same in
+// every lane)
+__global__ __launch_bounds__(THREADS) void whenet_yuv_to_bgr_mixed_kernel(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, YuvMixed clip) {
+    const int b = int(blockIdx.x);
+    int f = 0;
+    for (int i = 1; i < clip.frames; ++i)
+        if (clip.f[i].block0 <= b) f = i;
+    const YuvGeom& g = clip.f[f];
+    yuv_item(planes + g.src_off, bgr + g.dst_off, g, (b - g.block0) * THREADS + int(threadIdx.x));
+}
+
+int yuv_blocks(int h, int w) { return (((w + 3) >> 2) * ((h + 1) >> 1) + THREADS - 1) / THREADS; }
+
+void check_geom(const YuvGeom& g) {
+    WHENET_REQUIRE(g.h >= 1 && g.w >= 1 && g.h <= YUV_MAX_FRAME_SIDE && g.w <= YUV_MAX_FRAME_SIDE &&
+                       (g.format == WHENET_YUV_NV12 || g.format == WHENET_YUV_I420),
+                   WHENET_EINVAL, "yuv_to_bgr: bad frame geometry");
+}
+
+}  // namespace
+
+const YuvCoeffs& yuv_coeffs(int matrix) {
+    static const YuvCoeffs table[WHENET_YUV_MATRICES] = WHENET_YUV_COEFFS;
+    WHENET_REQUIRE(matrix >= 0 && matrix < WHENET_YUV_MATRICES, WHENET_EINVAL, "unknown YUV matrix " + std::to_string(matrix));
+    return table[matrix];
+}
+
+void check_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes) {
+    const std::string w = what;
+    WHENET_REQUIRE(frames != nullptr, WHENET_EINVAL, w + ": NULL argument");
+    WHENET_REQUIRE(nframes >= 1 && nframes <= MIXED_MAX_FRAMES, WHENET_EINVAL,
+                   w + ": " + std::to_string(nframes) + " frames: a clip holds 1..16 (the detector's batch limit)");
+    for (int i = 0; i < nframes; ++i) {
+        const whenet_yuv_frame_t& f = frames[i];
+        const std::string who = w + ": frame " + std::to_string(i);
+        WHENET_REQUIRE(f.format == WHENET_YUV_NV12 || f.format == WHENET_YUV_I420, WHENET_EINVAL,
+                       who + ": unknown format " + std::to_string(f.format) + " (WHENET_YUV_NV12 or WHENET_YUV_I420)");
+        WHENET_REQUIRE(f.matrix >= 0 && f.matrix < WHENET_YUV_MATRICES, WHENET_EINVAL,
+                       who + ": unknown matrix " + std::to_string(f.matrix) + " (WHENET_YUV_BT601, _BT709 or _JFIF)");
+        WHENET_REQUIRE(f.h >= 1 && f.w >= 1 && f.h <= YUV_MAX_FRAME_SIDE && f.w <= YUV_MAX_FRAME_SIDE, WHENET_EINVAL,
+                       who + " is " + std::to_string(f.h) + " x " + std::to_string(f.w) + ": sides must be 1.." +
+                           std::to_string(YUV_MAX_FRAME_SIDE));
+        const int cw = (f.w + 1) >> 1;
+        const int planes = f.format == WHENET_YUV_NV12 ? 2 : 3;
+        const int row_bytes[3] = {f.w, f.format == WHENET_YUV_NV12 ? 2 * cw : cw, cw};
+        for (int p = 0; p < planes; ++p) {
+            WHENET_REQUIRE(f.plane[p] != nullptr, WHENET_EINVAL, who + ": plane " + std::to_string(p) + " is NULL");
+            WHENET_REQUIRE(f.pitch[p] >= row_bytes[p], WHENET_EINVAL,
+                           who + ": pitch " + std::to_string(f.pitch[p]) + " of plane " + std::to_string(p) + " is below its row of " +
+                               std::to_string(row_bytes[p]) + " bytes");
+        }
+    }
+}
+
+void yuv_to_bgr_host(const whenet_yuv_frame_t& f, uint8_t* bgr) {
+    const YuvCoeffs& k = yuv_coeffs(f.matrix);
+    const bool nv12 = f.format == WHENET_YUV_NV12;
+    for (int y = 0; y < f.h; ++y) {
+        const uint8_t* yrow = f.plane[0] + size_t(y) * f.pitch[0];
+        const uint8_t* urow = f.plane[1] + size_t(y >> 1) * f.pitch[1];
+        const uint8_t* vrow = nv12 ? urow + 1 : f.plane[2] + size_t(y >> 1) * f.pitch[2];
+        const int step = nv12 ? 2 : 1;
+        uint8_t* out = bgr + size_t(y) * f.w * 3;
+        for (int x = 0; x < f.w; ++x) {
+            const int c = std::max(0, int(yrow[x]) - k.yoff);
+            const int d = int(urow[(x >> 1) * step]) - 128, e = int(vrow[(x >> 1) * step]) - 128;
+            const int base = k.cy * c + (1 << (SHIFT - 1));
+            out[3 * x + 0] = uint8_t(yuv_clip8((base + k.cub * d) >> SHIFT));
+            out[3 * x + 1] = uint8_t(yuv_clip8((base - k.cug * d - k.cvg * e) >> SHIFT));
+            out[3 * x + 2] = uint8_t(yuv_clip8((base + k.cvr * e) >> SHIFT));
+        }
+    }
+}
+
+void yuv_stage_planes(const whenet_yuv_frame_t& f, uint8_t* dst) {
+    const int cw = (f.w + 1) >> 1, ch = (f.h + 1) >> 1;
+    const bool nv12 = f.format == WHENET_YUV_NV12;
+    const int planes = nv12 ? 2 : 3;
+    const int rows[3] = {f.h, ch, ch};
+    const int row_bytes[3] = {f.w, nv12 ? 2 * cw : cw, cw};
+    for (int p = 0; p < planes; ++p) {
+        const size_t rb = size_t(row_bytes[p]);
+        if (size_t(f.pitch[p]) == rb) {
+            std::memcpy(dst, f.plane[p], rb * rows[p]);
+        } else {
+            for (int r = 0; r < rows[p]; ++r) std::memcpy(dst + r * rb, f.plane[p] + size_t(r) * f.pitch[p], rb);
+        }
+        dst += rb * rows[p];
+    }
+}
+
+void launch_yuv_to_bgr(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g, hipStream_t stream) {
+    check_geom(g);
+    hipLaunchKernelGGL(whenet_yuv_to_bgr_kernel, dim3(yuv_blocks(g.h, g.w)), dim3(THREADS), 0, stream, d_planes, d_bgr, g);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+void launch_yuv_to_bgr_batch(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g, int frames, size_t src_stride, size_t dst_stride,
+                             hipStream_t stream) {
+    check_geom(g);
+    WHENET_REQUIRE(frames >= 1 && frames <= MIXED_MAX_FRAMES && src_stride >= yuv_plane_bytes(g.h, g.w) && dst_stride >= size_t(g.h) * g.w * 3,
+                   WHENET_EINVAL, "yuv_to_bgr_batch: bad frame count or strides");
+    hipLaunchKernelGGL(whenet_yuv_to_bgr_batch_kernel, dim3(yuv_blocks(g.h, g.w), frames), dim3(THREADS), 0, stream, d_planes, d_bgr, g,
+                       (unsigned long long)src_stride, (unsigned long long)dst_stride);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+// block0 / total_blocks are set here
+void launch_yuv_to_bgr_mixed(const uint8_t* d_planes, uint8_t* d_bgr, YuvMixed clip, hipStream_t stream) {
+    WHENET_REQUIRE(clip.frames >= 1 && clip.frames <= MIXED_MAX_FRAMES, WHENET_EINVAL, "yuv_to_bgr_mixed: 1..16 frames");
+    int blocks = 0;
+    for (int f = 0; f < clip.frames; ++f) {
+        check_geom(clip.f[f]);
+        clip.f[f].block0 = blocks;
+        blocks += yuv_blocks(clip.f[f].h, clip.f[f].w);
+    }
+    clip.total_blocks = blocks;
+    hipLaunchKernelGGL(whenet_yuv_to_bgr_mixed_kernel, dim3(blocks), dim3(THREADS), 0, stream, d_planes, d_bgr, clip);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace whenet

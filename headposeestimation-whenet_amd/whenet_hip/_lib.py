@@ -35,6 +35,13 @@ class LaunchStat(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class YuvFrameC(C.Structure):
+    """whenet_yuv_frame_t: the planes of one 4:2:0 frame as a decoder hands them out."""
+    _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("format", C.c_int), ("matrix", C.c_int), ("h", C.c_int), ("w", C.c_int)]
+
+
 _PROTOS = {
     "whenet_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_P)]),
     "whenet_create_from_memory": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -90,6 +97,10 @@ _PROTOS = {
                                          C.c_int, _P, _P, _P, _P, _P]),
     "whenet_letterbox_cache_stats": (C.c_int, [_P, C.POINTER(C.c_int32 * 4)]),
     "whenet_op_head_compact": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "whenet_yuv_to_bgr_host": (C.c_int, [C.POINTER(YuvFrameC), _P]),
+    "whenet_op_yuv_to_bgr": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, C.POINTER(_P)]),
+    "whenet_frame_begin_yuv": (C.c_int, [_P, C.POINTER(YuvFrameC), C.POINTER(C.c_int)]),
+    "whenet_clip_begin_yuv": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, C.POINTER(C.c_int)]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -236,6 +247,27 @@ def crop_plan(rect) -> np.ndarray:
     r = np.ascontiguousarray(rect, np.int32).reshape(4)
     out = np.empty(CROP_PLAN_INTS, np.int32)
     raise_for(load().whenet_crop_plan(_ptr(r), _ptr(out)), f"whenet_crop_plan: empty crop window {r.tolist()}")
+    return out
+
+
+YUV_NV12, YUV_I420 = 0, 1                      # WHENET_YUV_NV12 / WHENET_YUV_I420
+YUV_BT601, YUV_BT709, YUV_JFIF = 0, 1, 2       # WHENET_YUV_BT601 / _BT709 / _JFIF
+
+
+def _yuv_descs(frames):
+    """The whenet_yuv_frame_t array of a list of frames (`whenet_hip.yuv.YUVFrame`s, or YuvFrameC descriptors as they are)."""
+    descs = [f if isinstance(f, YuvFrameC) else f.descriptor() for f in frames]
+    return (YuvFrameC * max(len(descs), 1))(*descs), descs
+
+
+def yuv_to_bgr_host(desc: YuvFrameC) -> np.ndarray:
+    """The YUV -> BGR conversion of include/whenet_hip.h on one frame descriptor -> uint8 [h,w,3] (B, G, R).  Pure host arithmetic
+    inside the library (no GPU needed); a descriptor the library refuses raises ValueError with its text."""
+    lib = load()
+    out = np.empty((max(int(desc.h), 0), max(int(desc.w), 0), 3), np.uint8)
+    rc = lib.whenet_yuv_to_bgr_host(C.byref(desc), _ptr(out) if out.size else None)
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace") if out.size else "yuv_to_bgr_host: frame 0 is empty")
     return out
 
 
@@ -657,6 +689,32 @@ class Handle:
         ptrs, fh, fw = _mixed_args(frames)
         t = C.c_int(-1)
         self._check(self._lib.whenet_clip_begin_mixed(self._h, ptrs, len(frames), _ptr(fh), _ptr(fw), BGR if bgr else RGB, C.byref(t)))
+        return t.value
+
+    # ---- YUV 4:2:0 ingest: a decoder's planes in, the resident BGR frame built on the device ---------
+    def op_yuv_to_bgr(self, frames: list) -> list:
+        """The conversion kernel alone on 1..16 frames (`whenet_hip.yuv.YUVFrame`) of their own sizes, formats and matrices, packed
+        back to back on the device as a mixed clip packs them -> a list of uint8 [H_i,W_i,3] arrays (B, G, R)."""
+        arr, descs = _yuv_descs(frames)
+        outs = [np.empty((max(int(d.h), 0), max(int(d.w), 0), 3), np.uint8) for d in descs]
+        ptrs = (_P * max(len(outs), 1))(*[o.ctypes.data if o.size else None for o in outs])
+        self._check(self._lib.whenet_op_yuv_to_bgr(self._h, arr, len(descs), ptrs))
+        return outs
+
+    def frame_begin_yuv(self, frame) -> int:
+        """`frame_begin` from a decoder's planes: they are uploaded as they are and converted on the device; the ticket is
+        `frame_begin(frame.to_bgr(), bgr=True)`'s in everything that follows."""
+        arr, _ = _yuv_descs([frame])
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin_yuv(self._h, arr, C.byref(t)))
+        return t.value
+
+    def clip_begin_yuv(self, frames: list) -> int:
+        """`clip_begin` (frames of one size) or `clip_begin_mixed` (otherwise) from the planes of 1..16 frames, each with its own
+        format and matrix; the ticket goes to clip_detect_heads / collect_clip."""
+        arr, descs = _yuv_descs(frames)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_yuv(self._h, arr, len(descs), C.byref(t)))
         return t.value
 
     def op_letterbox_mixed(self, frames: list, size=(416, 416), bgr: bool = True, want_u8: bool = True, want_f32: bool = True):

@@ -27,7 +27,10 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     and pose as one submission.  The heads that have a window are compacted on the device, so the forward runs over
     `max_heads` rows, not over F x max_boxes; every frame's result is bit for bit what `begin; detect_heads; collect` returns;
   * frames of DIFFERENT sizes (a rig of different cameras, several files behind one handle) travel as a clip too:
-    `begin_clip_mixed(frames)` in the place of `begin_clip`, the other two calls and the contract unchanged.
+    `begin_clip_mixed(frames)` in the place of `begin_clip`, the other two calls and the contract unchanged;
+  * a caller fed by a video decoder hands over its 4:2:0 planes (`whenet_hip.yuv.YUVFrame`: NV12 or I420) with `begin_yuv(frame)`
+    / `begin_clip_yuv(frames)`: half the bytes cross PCIe and the BGR frame is built on the device (`csrc/yuv.hip`); everything
+    that follows is what `begin(frame.to_bgr())` / `begin_clip...` would have been followed by, bit for bit.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -167,6 +170,40 @@ class FramePipeline:
             raise ValueError(f"{self._depth} frames already in flight: collect() first")
         frames = _lib.mixed_u8(frames)
         ticket = self._h.clip_begin_mixed(frames, bgr=self._bgr)
+        self._begun_clip = (ticket, len(frames))
+
+    def _check_can_begin(self) -> None:
+        if self._begun is not None:
+            raise ValueError("the frame begun last has no heads yet: heads() first")
+        if self._begun_clip is not None:
+            raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
+        if len(self._pending) >= self._depth:
+            raise ValueError(f"{self._depth} frames already in flight: collect() first")
+
+    def begin_yuv(self, frame) -> None:
+        """`begin()` from a decoder's planes (a `whenet_hip.yuv.YUVFrame`): the planes are uploaded as they are, 1.5 bytes per pixel,
+        and the BGR frame is built on the device.  Everything that follows -- `detector_input`, `detect`, `heads`, `detect_heads`,
+        `collect` -- is what it is after `begin(frame.to_bgr())` on a pipeline made with `bgr=True`."""
+        from .yuv import YUVFrame
+        self._check_can_begin()
+        if not isinstance(frame, YUVFrame):
+            raise ValueError(f"begin_yuv takes a whenet_hip.yuv.YUVFrame, got {type(frame).__name__}")
+        ticket = self._h.frame_begin_yuv(frame)
+        self._begun = (ticket, frame.h, frame.w)
+
+    def begin_clip_yuv(self, frames) -> None:
+        """A clip from the planes of 1..16 `YUVFrame`s, each with its own format and matrix: frames of one size make a clip as
+        `begin_clip()` makes it, frames of different sizes one as `begin_clip_mixed()` makes it (at most option "letterbox_cache"
+        of them).  `detect_heads_clip()` and `collect_clip()` follow."""
+        from .yuv import YUVFrame
+        self._check_can_begin()
+        frames = list(frames)
+        if not 1 <= len(frames) <= _lib.MAX_CLIP_FRAMES:
+            raise ValueError(f"a clip holds 1..{_lib.MAX_CLIP_FRAMES} frames, got {len(frames)}")
+        for i, f in enumerate(frames):
+            if not isinstance(f, YUVFrame):
+                raise ValueError(f"begin_clip_yuv: frame {i} must be a whenet_hip.yuv.YUVFrame, got {type(f).__name__}")
+        ticket = self._h.clip_begin_yuv(frames)
         self._begun_clip = (ticket, len(frames))
 
     def _begun_frame(self, what: str):

@@ -1,0 +1,138 @@
+"""4:2:0 YUV frames as video decoders deliver them (NV12, I420), for `FramePipeline.begin_yuv` / `begin_clip_yuv`.
+
+A `YUVFrame` describes the planes where they are: nothing is copied or converted here.  The planes are uploaded as they are (1.5
+bytes per pixel) and the packed BGR frame is built on the device (`csrc/yuv.hip`) by the integer conversion stated in
+include/whenet_hip.h; `to_bgr()` runs the same arithmetic on the host inside the library.
+
+    frame = YUVFrame.from_buffer(decoder_buffer, 1080, 1920, "nv12", pitch=2048, matrix="bt709")
+    fp.begin_yuv(frame); fp.detect_heads(); rects, yaw, pitch, roll = fp.collect()
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+FORMATS = {"nv12": _lib.YUV_NV12, "i420": _lib.YUV_I420}
+MATRICES = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709, "jfif": _lib.YUV_JFIF}
+# {yoff, CY, CVR, CUG, CVG, CUB} per matrix: WHENET_YUV_COEFFS of include/whenet_hip.h (tests/test_yuv_cpu.py holds both to the text)
+COEFFS = {"bt601": (16, 1220542, 1673527, 409993, 852492, 2116026),
+          "bt709": (16, 1220945, 1879825, 223578, 558767, 2215014),
+          "jfif": (0, 1048576, 1470104, 360853, 748826, 1858077)}
+MAX_SIDE = _lib.MAX_FRAME_SIDE
+
+
+def _code(table: dict, value, what: str) -> int:
+    if isinstance(value, str):
+        if value.lower() not in table:
+            raise ValueError(f"unknown {what} {value!r}: one of {sorted(table)}")
+        return table[value.lower()]
+    if value not in table.values():
+        raise ValueError(f"unknown {what} {value!r}: one of {sorted(table)}")
+    return int(value)
+
+
+def _plane(a, rows: int, row_bytes: int, name: str) -> np.ndarray:
+    """A plane as a uint8 array of `rows` rows of `row_bytes` contiguous bytes (an interleaved plane may be [rows, cw, 2]); the row
+    stride is the pitch.  Nothing is copied: a plane whose bytes within a row are not contiguous is refused."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError(f"{name} plane must be uint8, got {a.dtype}")
+    if a.ndim == 3 and a.shape[2] == 2 and a.strides[1:] == (2, 1):
+        a = np.lib.stride_tricks.as_strided(a, (a.shape[0], a.shape[1] * 2), (a.strides[0], 1), writeable=False)
+    if a.ndim != 2 or a.shape != (rows, row_bytes):
+        raise ValueError(f"{name} plane must be uint8 [{rows},{row_bytes}], got shape {a.shape}")
+    if row_bytes > 1 and a.strides[1] != 1:
+        raise ValueError(f"{name} plane: the bytes of a row must be contiguous (strides {a.strides})")
+    if rows > 1 and a.strides[0] < row_bytes:
+        raise ValueError(f"{name} plane: row stride {a.strides[0]} is below its row of {row_bytes} bytes")
+    return a
+
+
+class YUVFrame:
+    """The planes of one 4:2:0 frame of h x w luma samples: `planes` (2 arrays for NV12: Y, interleaved UV; 3 for I420: Y, U, V),
+    their byte `pitches`, `format`, `matrix` (codes of include/whenet_hip.h), `h`, `w`.  The chroma planes have (h + 1) // 2 rows of
+    (w + 1) // 2 samples."""
+
+    def __init__(self, planes, format, matrix, h: int, w: int):
+        self.format = _code(FORMATS, format, "format")
+        self.matrix = _code(MATRICES, matrix, "matrix")
+        self.h, self.w = int(h), int(w)
+        if not (1 <= self.h <= MAX_SIDE and 1 <= self.w <= MAX_SIDE):
+            raise ValueError(f"frame is {self.h} x {self.w}: sides must be 1..{MAX_SIDE}")
+        ch, cw = (self.h + 1) // 2, (self.w + 1) // 2
+        shapes = [(self.h, self.w, "Y"), (ch, 2 * cw, "UV")] if self.format == _lib.YUV_NV12 else \
+                 [(self.h, self.w, "Y"), (ch, cw, "U"), (ch, cw, "V")]
+        planes = list(planes)
+        if len(planes) != len(shapes):
+            raise ValueError(f"{'NV12' if self.format == _lib.YUV_NV12 else 'I420'} has {len(shapes)} planes, got {len(planes)}")
+        self.planes = tuple(_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
+        # a plane of one row has no row stride of its own: its pitch is its row
+        self.pitches = tuple(int(a.strides[0]) if a.shape[0] > 1 else int(a.shape[1]) for a in self.planes)
+
+    @classmethod
+    def nv12(cls, y, uv, matrix="bt601") -> "YUVFrame":
+        """Y uint8 [h,w] and the interleaved chroma plane uint8 [ch, 2 cw] (or [ch, cw, 2]: U, V)."""
+        y = np.asarray(y)
+        if y.ndim != 2:
+            raise ValueError(f"Y plane must be uint8 [h,w], got shape {y.shape}")
+        return cls((y, uv), _lib.YUV_NV12, matrix, y.shape[0], y.shape[1])
+
+    @classmethod
+    def i420(cls, y, u, v, matrix="bt601") -> "YUVFrame":
+        """Y uint8 [h,w], U and V uint8 [ch,cw]."""
+        y = np.asarray(y)
+        if y.ndim != 2:
+            raise ValueError(f"Y plane must be uint8 [h,w], got shape {y.shape}")
+        return cls((y, u, v), _lib.YUV_I420, matrix, y.shape[0], y.shape[1])
+
+    @classmethod
+    def from_buffer(cls, buf, h: int, w: int, format="nv12", pitch=None, matrix="bt601") -> "YUVFrame":
+        """A decoder's single allocation: h rows of luma at `pitch` bytes, then the chroma rows.  NV12: (h + 1) // 2 interleaved
+        rows at the same pitch.  I420: the U rows and then the V rows at (pitch + 1) // 2 bytes.  Without `pitch` the planes are
+        tight: every row is followed by the next.  `buf` is anything with
+        the buffer interface (bytes, a memoryview, a uint8 array); it is not copied."""
+        fmt = _code(FORMATS, format, "format")
+        h, w = int(h), int(w)
+        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+            raise ValueError(f"frame is {h} x {w}: sides must be 1..{MAX_SIDE}")
+        a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+        if a.dtype != np.uint8:
+            raise ValueError(f"buffer must hold uint8, got {a.dtype}")
+        a = a.reshape(-1) if a.flags.c_contiguous else None
+        if a is None:
+            raise ValueError("buffer must be contiguous")
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        crow = 2 * cw if fmt == _lib.YUV_NV12 else cw
+        if pitch is None:               # tight: every plane's pitch is its row
+            pitch, cpitch = w, crow
+        else:
+            pitch = int(pitch)
+            cpitch = pitch if fmt == _lib.YUV_NV12 else (pitch + 1) // 2
+        if pitch < w or cpitch < crow:
+            raise ValueError(f"pitch {pitch} is below a row of the {h} x {w} frame")
+        nchroma = 1 if fmt == _lib.YUV_NV12 else 2
+        need = pitch * h + (nchroma * ch - 1) * cpitch + crow      # (the last row ends with its last sample)
+        if a.size < need:
+            raise ValueError(f"buffer holds {a.size} bytes, the frame needs {need}")
+
+        def view(off, rows, row_bytes, p):
+            return np.lib.stride_tricks.as_strided(a[off:], (rows, row_bytes), (p, 1), writeable=False)
+
+        planes = [view(0, h, w, pitch)]
+        for i in range(nchroma):
+            planes.append(view(pitch * h + i * cpitch * ch, ch, crow, cpitch))
+        return cls(planes, fmt, matrix, h, w)
+
+    def descriptor(self) -> "_lib.YuvFrameC":
+        """The whenet_yuv_frame_t of this frame (it points into the planes: keep the frame alive while it is used)."""
+        d = _lib.YuvFrameC()
+        for i, (a, p) in enumerate(zip(self.planes, self.pitches)):
+            d.plane[i] = a.ctypes.data
+            d.pitch[i] = p
+        d.format, d.matrix, d.h, d.w = self.format, self.matrix, self.h, self.w
+        return d
+
+    def to_bgr(self) -> np.ndarray:
+        """uint8 [h,w,3] in B, G, R order: the frame `begin_yuv` builds on the device, computed on the host inside the library."""
+        return _lib.yuv_to_bgr_host(self.descriptor())

@@ -43,7 +43,9 @@ extern "C" {
  * 5 (round 8): whenet_letterbox_plan, whenet_op_letterbox and the resident-frame form whenet_frame_begin / whenet_frame_letterbox /
  * whenet_frame_heads.  (Additions only: a version-4 caller runs unchanged.)
  * (still 6 -- clips: whenet_clip_begin / whenet_clip_detect_heads / whenet_collect_clip, whenet_op_letterbox_batch,
- * whenet_yolo_eval_batch, whenet_op_head_compact.  Additions only.) */
+ * whenet_yolo_eval_batch, whenet_op_head_compact.  Additions only.)
+ * (still 6 -- YUV 4:2:0 ingest: whenet_yuv_frame_t, whenet_yuv_to_bgr_host, whenet_op_yuv_to_bgr, whenet_frame_begin_yuv,
+ * whenet_clip_begin_yuv.  Additions only.) */
 #define WHENET_ABI_VERSION 6
 #define WHENET_API __attribute__((visibility("default")))
 
@@ -495,6 +497,58 @@ WHENET_API int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, in
                            float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores,
                            int32_t* classes, int32_t* index, int32_t* counts);
 WHENET_API int whenet_letterbox_cache_stats(whenet_t* h, int32_t out[4]);
+
+/* ---- YUV 4:2:0 INGEST: a decoder's planes in, the resident BGR frame built on the device (additions to ABI 6).  Video decoders
+ * and MJPEG cameras deliver 4:2:0 YUV; `cap.read()` (demo_video.py:51) hides a software conversion to BGR.  Here the planes are
+ * uploaded as they are (1.5 bytes per pixel instead of 3) and converted by a kernel (csrc/yuv.hip) on the copy stream, behind the
+ * upload and before the event every consumer of the frame waits for: the slot then holds the packed BGR frame [h][w][3], recorded
+ * as whenet_frame_begin(..., WHENET_BGR) records it, and everything downstream is unchanged.
+ *
+ * The conversion, integers only.  Frame of h x w luma samples, 1 <= h, w <= 8192, odd sizes included; chroma planes of
+ * ch = (h + 1) >> 1 rows by cw = (w + 1) >> 1 samples; pixel (y, x) takes the chroma sample (y >> 1, x >> 1) (nearest neighbour).
+ * With int32 arithmetic and >> an arithmetic shift:
+ *     c = max(0, Y - yoff);  d = U - 128;  e = V - 128
+ *     R = clip8((CY * c           + CVR * e + (1 << 19)) >> 20)
+ *     G = clip8((CY * c - CUG * d - CVG * e + (1 << 19)) >> 20)
+ *     B = clip8((CY * c + CUB * d           + (1 << 19)) >> 20)
+ * and {yoff, CY, CVR, CUG, CVG, CUB} = WHENET_YUV_COEFFS[matrix]:
+ *     WHENET_YUV_BT601  video range, the constants of OpenCV's cvtColor (1.164, 1.596, 0.391, 0.813, 2.018 x 2^20, truncated)
+ *     WHENET_YUV_BT709  video range, rint(2^20 x {255/219, 1.5748 x 255/224, 0.1873 x 255/224, 0.4681 x 255/224, 1.8556 x 255/224})
+ *     WHENET_YUV_JFIF   full range (MJPEG), rint(2^20 x {1, 1.402, 0.344136, 0.714136, 1.772})
+ *   WHENET_YUV_NV12  plane[0] = Y, plane[1] = U and V interleaved (U at 2 (x >> 1), V behind it), plane[2] unused
+ *   WHENET_YUV_I420  plane[0] = Y, plane[1] = U, plane[2] = V
+ * Every plane has its own byte pitch >= its row bytes (w; 2 cw for the interleaved plane; cw).
+ *   whenet_yuv_to_bgr_host  the conversion as pure host arithmetic (no GPU needed): bgr = uint8 [h][w][3]; the text of an error is
+ *                  whenet_last_error(NULL)'s, the frame's index in it is 0
+ *   whenet_op_yuv_to_bgr    the kernel alone, host to host, on 1..16 frames of their own sizes, formats and matrices: bgr[f] = uint8
+ *                  [h_f][w_f][3].  On the device the frames lie back to back as a mixed clip packs them.  Works on a
+ *                  whenet_create_postproc handle.
+ *   whenet_frame_begin_yuv  as whenet_frame_begin: the ticket goes to whenet_frame_letterbox / _detect / _heads / _detect_heads and
+ *                  the collect calls unchanged.
+ *   whenet_clip_begin_yuv   1..16 frames, each with its own format and matrix.  All of one size: a clip as whenet_clip_begin
+ *                  makes it; otherwise a mixed clip as whenet_clip_begin_mixed makes it (at most option "letterbox_cache" frames).
+ * WHENET_EINVAL, with the frame's index in whenet_last_error and before a slot is taken or anything is enqueued: a NULL required
+ * plane, a pitch below the plane's row bytes, an unknown format or matrix, a side outside 1..8192, a frame count outside 1..16. */
+#define WHENET_YUV_NV12 0
+#define WHENET_YUV_I420 1
+#define WHENET_YUV_BT601 0
+#define WHENET_YUV_BT709 1
+#define WHENET_YUV_JFIF 2
+#define WHENET_YUV_MATRICES 3
+#define WHENET_YUV_COEFFS {{16, 1220542, 1673527, 409993, 852492, 2116026}, \
+                           {16, 1220945, 1879825, 223578, 558767, 2215014}, \
+                           {0, 1048576, 1470104, 360853, 748826, 1858077}}
+typedef struct {
+    const uint8_t* plane[3];
+    int pitch[3];
+    int format;
+    int matrix;
+    int h, w;
+} whenet_yuv_frame_t;
+WHENET_API int whenet_yuv_to_bgr_host(const whenet_yuv_frame_t* frame, uint8_t* bgr);
+WHENET_API int whenet_op_yuv_to_bgr(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, uint8_t* const* bgr);
+WHENET_API int whenet_frame_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frame, int* ticket);
+WHENET_API int whenet_clip_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, int* ticket);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
