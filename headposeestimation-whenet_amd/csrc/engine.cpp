@@ -448,9 +448,15 @@ bool Engine::stem_fuse_active() const {
            stemdw_supported(dtype_, b.dw.plan, b.spec.k, b.spec.s, b.spec.h_in, b.spec.cexp());
 }
 
+bool Engine::heads_split_active() const { return split_heads_ && partial_per_crop_ >= size_t(heads_split()) * N_LOGITS; }
+
 bool Engine::head_fused() const {
-    return head_fuse_ && pw_impl_ == 0 && split_heads_ && head7_supported(dtype_, head_.K, head_.N, 49) &&
-           partial_per_crop_ >= size_t(heads_split()) * N_LOGITS;
+    return head_fuse_ && pw_impl_ == 0 && heads_split_active() && head7_supported(dtype_, head_.K, head_.N, 49);
+}
+
+void Engine::launch_heads_stage(const HeadsArgs& h, const View& v, hipStream_t s) {
+    if (heads_split_active()) launch_heads_split(h, v.partial, v.hcount, dtype_, s);
+    else launch_heads(h, dtype_, s);
 }
 
 // The 7 x 7 tensors between the blocks of an f16 handle (outputs of the projects of blocks 12-16) are stored in the order the matrix
@@ -855,7 +861,7 @@ void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, Results 
           [&] { launch_head7(a, s); });
         h.feat_in = reinterpret_cast<const float*>(v.hc);
         R("heads", "heads", "whenet_heads_split_kernel<float, true>", double(n) * ((FEAT + N_LOGITS + 6) * 4.0) + double(FEAT) * N_LOGITS * 4.0,
-          2.0 * n * FEAT * N_LOGITS, [&] { launch_heads_split(h, v.partial, v.hcount, dtype_, s); });
+          2.0 * n * FEAT * N_LOGITS, [&] { launch_heads_stage(h, v, s); });
         return;
     }
     const PwArgs a = head_pw_args(cur, v.hc, n);
@@ -863,14 +869,11 @@ void Engine::enqueue_forward(const View& v, const uint8_t* d_in, int n, Results 
       [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });
     h.x = v.hc;
     // (v.partial is free here: the last squeeze-excite is long done)
-    const bool split = split_heads_ && partial_per_crop_ >= size_t(heads_split()) * N_LOGITS;
+    const bool split = heads_split_active();
     const std::string hname = std::string(split ? "whenet_heads_split_kernel<" : "whenet_heads_kernel<") +
                               (dtype_ == WHENET_F16 ? "_Float16" : "float") + (split ? ", false>" : ">");
     R("heads", "heads", hname.c_str(), double(n) * (HC_ELEMS * es + (N_LOGITS + 6) * 4.0) + double(FEAT) * N_LOGITS * 4.0,
-      2.0 * n * FEAT * N_LOGITS, [&] {
-          if (split) launch_heads_split(h, v.partial, v.hcount, dtype_, s);
-          else launch_heads(h, dtype_, s);
-      });
+      2.0 * n * FEAT * N_LOGITS, [&] { launch_heads_stage(h, v, s); });
 }
 
 hipStream_t Engine::lane_stream(int i) {

@@ -379,6 +379,10 @@ class Engine {
     bool stem_fuse_active() const;
     bool fold12_active() const;
     bool head_fused() const;           // the head conv pools its own output (head7.hip)
+    // The Dense + softmax + decode stage: four workgroups per crop (whenet_heads_split_kernel, partial vectors in v.partial, tickets
+    // in v.hcount) or one (whenet_heads_kernel).  The ONE choice and the ONE launch site of the forward and of op_head.
+    bool heads_split_active() const;
+    void launch_heads_stage(const HeadsArgs& h, const View& v, hipStream_t s);
     // Layout of the OUTPUT of block `index` (1-based) in a whole forward: true = 16-channel blocks [crop][C/16][HW][16]
     // (DESIGN.md section 2), false = NHWC.  A function of the layer and the options only, never of the batch.
     bool act_blocked(int index) const;

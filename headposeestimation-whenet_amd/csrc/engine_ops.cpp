@@ -98,12 +98,14 @@ void Engine::op_head(const float* in, int n, float* feat, float* logits, float* 
     TempBufs tmp;
     float* d_f32 = static_cast<float*>(tmp.get(in_elems * sizeof(float)));
     float* d_feat = static_cast<float*>(tmp.get(N * FEAT * sizeof(float)));
+    float* d_ypr_scratch = static_cast<float*>(tmp.get(N * 3 * sizeof(float)));
     WHENET_HIP_CHECK(hipMemcpyAsync(d_f32, in, in_elems * sizeof(float), hipMemcpyHostToDevice, stream_));
     const View v = view(0);
     launch_f32_to_act(d_f32, v.x0, in_elems, dtype_, stream_);
-    const bool fuse_head = head_fuse_ && pw_impl_ == 0 && head7_supported(dtype_, head_.K, head_.N, 49);
+    // The forward's choices (enqueue_forward): head7.hip + the split heads kernel on its features where head_fused(); else the
+    // head conv as a GEMM (pw.hip) and the heads stage on its output tensor, split (option split_heads) or as one workgroup.
     HeadsArgs h{};
-    if (fuse_head) {          // the forward's form: head conv + pooling as one kernel (head7.hip), Dense heads on its features
+    if (head_fused()) {
         Head7Args a = head7_args(v.x0, d_feat, n);
         a.xcd_grouped = xcd_grouped(4, n);   // (option xcd_map bit 4 with option concurrent, as in the forward; the input stays NHWC)
         launch_head7(a, stream_);
@@ -111,7 +113,20 @@ void Engine::op_head(const float* in, int n, float* feat, float* logits, float* 
     } else {
         launch_pw(head_pw_args(v.x0, v.hc, n), dtype_, pw_impl_, num_cus_, stream_);
         h.x = v.hc;
-        h.feat = d_feat;
+        if (!heads_split_active()) {
+            h.feat = d_feat;
+        } else if (feat) {
+            // The split kernel keeps its pooled features in LDS: the caller's `feat` comes from a launch of the single kernel, whose
+            // decode goes to scratch -- nothing the split launch below is to write (v.out) is touched by it.
+            HeadsArgs f{};
+            f.x = v.hc;
+            f.w = d_dense_w_;
+            f.b = d_dense_b_;
+            f.feat = d_feat;
+            f.ypr = d_ypr_scratch;
+            f.n = n;
+            launch_heads(f, dtype_, stream_);
+        }
     }
     h.w = d_dense_w_;
     h.b = d_dense_b_;
@@ -119,7 +134,7 @@ void Engine::op_head(const float* in, int n, float* feat, float* logits, float* 
     h.ypr = v.out.ypr;
     h.argmax = v.out.amax;
     h.n = n;
-    launch_heads(h, dtype_, stream_);
+    launch_heads_stage(h, v, stream_);
     if (feat) WHENET_HIP_CHECK(hipMemcpyAsync(feat, d_feat, N * FEAT * sizeof(float), hipMemcpyDeviceToHost, stream_));
     if (logits) WHENET_HIP_CHECK(hipMemcpyAsync(logits, v.out.logits, N * N_LOGITS * sizeof(float), hipMemcpyDeviceToHost, stream_));
     if (ypr) WHENET_HIP_CHECK(hipMemcpyAsync(ypr, v.out.ypr, N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream_));

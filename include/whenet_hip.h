@@ -576,7 +576,12 @@ WHENET_API int whenet_op_block(whenet_t* h, int index, const float* in, int n,
  * the blocks take the layout the forward gives them (option act_layout). */
 WHENET_API int whenet_op_block_range(whenet_t* h, int first, int last, const float* in, int n, float* out);
 /* head: Conv1x1(1280)+BN+Swish + GAP + Dense heads + decode on input [n,7,7,320]:
- *   feat [n,1280], logits [n,252], ypr [n,3], argmax [n,3] */
+ *   feat [n,1280], logits [n,252], ypr [n,3], argmax [n,3]
+ * Runs the launches the forward runs under the handle's options: head conv + pooling as one kernel and the four-workgroup heads
+ * kernel on its features (head_fuse = 1 and split_heads = 1, the default); else the head conv as a GEMM and the heads stage on its
+ * output tensor, as four workgroups per crop (split_heads = 1) or as one (split_heads = 0).  The four-workgroup kernel on the
+ * tensor has no feature output: there `feat` comes from a separate launch of the one-workgroup kernel, whose logits, angles and
+ * argmax are discarded.  whenet_op_decode always runs the one-workgroup kernel (the other one has no logits input). */
 WHENET_API int whenet_op_head(whenet_t* h, const float* in, int n,
                    float* feat, float* logits, float* ypr, int32_t* argmax);
 /* decode only (whenet.py:28-33) on caller logits [n,252] -> ypr [n,3], argmax [n,3] */

@@ -26,6 +26,9 @@ n of one sequence, no two crops are equal and the batch has no period.
   "sparse" (dense_expand, dense_project): 1 or 3 impulses per channel (as the bound sum |w||x| < 2048 allows), dealt over a
       permutation of the pixels so that no pixel holds more than its share; stride-2 blocks: over the pixels the centre tap reads.
   Both: the four corners of the image are set.
+
+The heads stage (pooling + Dense + softmax + decode) and the whole forward have families of their own, HEAD_FAMILIES and the forward
+snapshot: see the comment above them at the end of this module.
 """
 from __future__ import annotations
 
@@ -546,3 +549,305 @@ def premise_input() -> np.ndarray:
     lo = np.where(18 + t <= 2048, 18 + t, 0)
     hi = np.where(104 + t <= 2048, 104 + t, 0)
     return np.concatenate([lo, hi], axis=1).reshape(1, b.h_in, b.h_in, b.cin).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the heads stage (pooling + Dense + softmax + decode: head.hip's two kernels) and the whole forward
+#
+# The arithmetic: float32(49 m) * (float32(1) / float32(49)) == m for every integer m of 0..4096 (test_probe_cpu.py) -- a head-conv
+# output that is the SAME integer m at all 49 positions pools to exactly m in every pooling expression of the library (the sum 49 m
+# is exact in any order, the one product rounds back to m).  With integer features and small-integer Dense weights and biases every
+# partial sum of the Dense layer is an integer below 2^24: the logits are ONE bit pattern for the single-workgroup kernel, for the
+# three instantiations of the four-workgroup kernel (whatever the split of the 1280-long contraction over workgroups and waves) and
+# for all three dtypes.
+#
+# Families (the routing snapshot with another head conv and other Dense layers; FAMILIES and its four snapshots do not change):
+#   dense_heads   head conv: feature co reads input channel (7 co + 5) % 320 with a positive integer weight (HEAD_GAIN: features 0 or
+#                 18..2040); Dense kernels dense +-1, +-2; biases non-zero integers.  Expected logits: an exact integer array.
+#   decode        feature 5 j + 3 reads input channel (3 j + 1) % 320 with weight 1 and logit j reads that feature alone with weight
+#                 DECODE_GAIN = 5 (bias 0): logit j of crop i is 5 x (channel (3 j + 1) % 320 of crop i), an injective function of ONE
+#                 input channel -- 252 distinct channels (head_feature() of the four old families collides at j and j + 64).  The
+#                 crops are designed rows (DECODE_ROWS), not random ones.  Levels: 0 and 90, 95 .. 120: a row of 18s and 19s has a
+#                 spread of 5, a one-hot row stands 120 above the rest (exp(-120) is 0 in float32).
+#   forward       the routing snapshot with a routing stem (stem output co reads ONE tap of ONE input channel with weight 1), fed a
+#                 float32 image of 0 or 18..24 through forward_f32, the real-valued entry point (no byte LUT; eager; stem and block
+#                 1's depthwise conv as two kernels).  The routing Dense makes logit j = float32(S) * float32(1/49) with S the exact
+#                 pooled sum of feature head_feature(j): ONE rounding.
+# The uint8 forward (LUT, stemdw.hip, graph replay and lanes) cannot be made exact -- the LUT's values are not integers -- and stays
+# with test_stem_fused_with_block_1_depthwise_is_bitwise_the_two_kernels and test_graph_replay_equals_eager.
+# ------------------------------------------------------------------------------------------------------------------------------
+HEAD_FAMILIES = ("dense_heads", "decode")
+HEAD_GAIN = (1, 2, 3, 5, 8, 13, 40, 85)          # head conv weight of feature co: HEAD_GAIN[co % 8] (85 * 24 = 2040 <= 2048)
+DECODE_GAIN = 5
+HEADS = (("yaw", 0, spec.N_YAW), ("pitch", spec.N_YAW, spec.N_PITCH), ("roll", spec.N_YAW + spec.N_PITCH, spec.N_ROLL))
+INV49 = np.float32(1) / np.float32(49)
+# name -> (bins set to the row's maximum on the 120-bin head, on a 66-bin head).  Every other bin is lower.
+DECODE_MAXIMA = {"max_first": ((0,), (0,)), "max_last": ((119,), (65,)), "max_63": ((63,), (63,)), "max_64": ((64,), (64,)),
+                 "tie_63_64": ((63, 64), (63, 64)),          # across the lane 63 / lane 0 boundary (a lane's second element)
+                 "tie_1_65": ((1, 65), (1, 65)),             # both in lane 1
+                 # a lane's first element against a later lane's second one; on 66 bins (second elements: bins 64 and 65 only)
+                 # against an EARLIER lane's second one, which a reduction ordered by lane alone would prefer
+                 "tie_5_100": ((5, 100), (5, 64))}
+DECODE_ROWS = ("equal", "max_first", "max_last", "max_63", "max_64", "tie_63_64", "tie_1_65", "tie_5_100", "one_hot", "narrow", "wide")
+
+
+def head_const_inputs(family: str, n: int) -> np.ndarray:
+    """float32 [n, 7, 7, 320], every channel constant over the 49 positions, values 0 or 18..24; crop i is a function of i alone.
+    dense_heads: a quarter of the channels 0, the others random.  decode: the designed rows (decode_row) behind the logits'
+    channels, random values in the 68 channels no logit reads."""
+    assert family in HEAD_FAMILIES
+    x = np.zeros((n, 7, 7, 320), np.float32)
+    for i in range(n):
+        rng = np.random.default_rng([10 + HEAD_FAMILIES.index(family), i, 3])
+        v = np.where(rng.integers(4, size=320) == 0, 0, rng.integers(18, 25, size=320))
+        if family == "decode":
+            v[decode_channel(np.arange(spec.N_LOGITS))] = np.concatenate([decode_row(i, h) for h in range(3)])
+        x[i] = v
+    return x
+
+
+def decode_channel(j):
+    return (3 * j + 1) % 320
+
+
+def decode_feature(j):
+    return 5 * j + 3
+
+
+def decode_kind(i: int, head: int) -> str:
+    """Crop i puts a different kind of row on each head; every kind meets every head within 11 consecutive crops."""
+    return DECODE_ROWS[(i + (0, 4, 7)[head]) % len(DECODE_ROWS)]
+
+
+def decode_row(i: int, head: int) -> np.ndarray:
+    """The input values (0 or 18..24; the logits are DECODE_GAIN x these) behind the bins of `head` (0 yaw, 1 pitch, 2 roll) of crop i."""
+    nb = HEADS[head][2]
+    kind = decode_kind(i, head)
+    rng = np.random.default_rng([20, i, head])
+    if kind == "equal":
+        return np.full(nb, 18 + i % 7)
+    if kind == "one_hot":
+        v = np.zeros(nb, np.int64)
+        v[int(rng.integers(nb))] = 24
+        return v
+    if kind == "narrow":                 # logits 90 or 95: half of the bins share the maximum, the others weigh e^-5 each
+        return rng.integers(18, 20, size=nb)
+    if kind == "wide":                   # logits 90, 95 .. 120, the maximum several times
+        return rng.integers(18, 25, size=nb)
+    v = rng.integers(18, 24, size=nb)    # below the maximum: 18..23
+    v[list(DECODE_MAXIMA[kind][0 if nb == spec.N_YAW else 1])] = 24
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def head_snapshot(family: str) -> Dict[str, np.ndarray]:
+    """The weights dict of a heads family (see the comment above): the routing snapshot with its own head conv and Dense layers."""
+    assert family in HEAD_FAMILIES
+    w = dict(snapshot("routing"))
+    co = np.arange(spec.FEAT)
+    j = np.arange(spec.N_LOGITS)
+    rng = np.random.default_rng([30, HEAD_FAMILIES.index(family)])
+    if family == "dense_heads":
+        conv = _routing_1x1((7 * co + 5) % 320, 320, spec.FEAT, np.asarray(HEAD_GAIN)[co % 8])
+        dense = (rng.integers(1, 3, size=(spec.FEAT, spec.N_LOGITS)) * np.where(rng.integers(2, size=(spec.FEAT, spec.N_LOGITS)) == 0, -1, 1))
+        bias = rng.integers(1, 8, size=spec.N_LOGITS) * np.where(rng.integers(2, size=spec.N_LOGITS) == 0, -1, 1)
+    else:
+        src = co % 320
+        src[decode_feature(j)] = decode_channel(j)
+        conv = _routing_1x1(src, 320, spec.FEAT, np.ones(spec.FEAT))
+        dense = np.zeros((spec.FEAT, spec.N_LOGITS))
+        dense[decode_feature(j), j] = DECODE_GAIN
+        bias = np.zeros(spec.N_LOGITS)
+    w["head/conv/kernel"] = conv.astype(np.float32).reshape(1, 1, 320, spec.FEAT)
+    for name, lo, nb in HEADS:
+        w[f"{name}/kernel"] = np.ascontiguousarray(dense[:, lo:lo + nb]).astype(np.float32)
+        w[f"{name}/bias"] = bias[lo:lo + nb].astype(np.float32)
+    for a in w.values():
+        a.setflags(write=False)
+    return w
+
+
+def dense_matrix(w: Dict[str, np.ndarray]):
+    """The three Dense layers as one [1280, 252] kernel and one [252] bias (float64)."""
+    return (np.concatenate([w[f"{name}/kernel"] for name, _, _ in HEADS], axis=1).astype(np.float64),
+            np.concatenate([w[f"{name}/bias"] for name, _, _ in HEADS]).astype(np.float64))
+
+
+def decode_f64(logits: np.ndarray):
+    """The float64 decode of the oracle's arithmetic (utils.softmax + the expectation over the bin indices, x 3 - 180 / - 99),
+    restated: test_probe_cpu.py holds it to oracle.whenet_oracle.decode.  Returns ypr [n, 3]."""
+    lg = np.asarray(logits, np.float64)
+    out = []
+    for h, (_, lo, nb) in enumerate(HEADS):
+        z = lg[:, lo:lo + nb] - lg[:, lo:lo + nb].max(axis=1, keepdims=True)
+        a = np.exp(z)
+        out.append((a / a.sum(axis=1, keepdims=True) * np.arange(nb)).sum(axis=1) * 3 - (180 if h == 0 else 99))
+    return np.stack(out, axis=1)
+
+
+def argmax_first(logits: np.ndarray) -> np.ndarray:
+    return np.stack([np.argmax(logits[:, lo:lo + nb], axis=1) for _, lo, nb in HEADS], axis=1).astype(np.int32)
+
+
+def ref_heads(x: np.ndarray, w: Dict[str, np.ndarray], mut: Optional[dict] = None) -> Dict[str, np.ndarray]:
+    """Head conv, pooling, Dense, argmax and decode on an input that is constant over the 49 positions, in exact integers (float64).
+    `feat` [n, 1280] and `logits` [n, 252] are integers; `argmax` is np.argmax per head (first index among equals), `ypr` the
+    float64 decode.  `bound`: the largest sum |feat||W| + |bias| (every partial sum of the contraction is an integer below it).
+    `mut`: one mutation (what a broken kernel would compute):
+      {"drop_slice": (c0, c1)}   the contraction misses features c0..c1-1
+      {"drop_partial": q}        the partial vector of workgroup q (features 320 q .. 320 q + 319) is not added
+      {"bias_per_workgroup": 1}  every one of the four workgroups adds the bias
+      {"argmax_last": 1}         the last index among equals
+      {"argmax_first_64": 1}     the argmax looks at bins 0..63 of each head only (a lane's first element)
+      {"logits_from": d}         crop i decodes the logits of crop (i + d) % n
+      {"pitch_from": 119}        the pitch head starts at logit 119 instead of 120"""
+    mut = mut or {}
+    x = np.asarray(x, np.float64)
+    assert (x == x[:, :1, :1, :]).all(), "the input must be constant over the 49 positions"
+    pre = x[:, 0, 0, :] @ w["head/conv/kernel"][0, 0].astype(np.float64) + w["head/bn/beta"].astype(np.float64)
+    assert in_exact_set(pre).all()
+    feat = swish_exact(pre)
+    D, bias = dense_matrix(w)
+    f = feat
+    if "drop_slice" in mut:
+        f = feat.copy()
+        f[:, mut["drop_slice"][0]:mut["drop_slice"][1]] = 0
+    if "drop_partial" in mut:
+        f = feat.copy()
+        f[:, 320 * mut["drop_partial"]:320 * mut["drop_partial"] + 320] = 0
+    logits = f @ D + bias * (4 if mut.get("bias_per_workgroup") else 1)
+    seen = np.roll(logits, -mut["logits_from"], axis=0) if "logits_from" in mut else logits
+    heads = [(name, mut.get("pitch_from", lo) if name == "pitch" else lo, nb) for name, lo, nb in HEADS]
+    am = []
+    for _, lo, nb in heads:
+        row = seen[:, lo:lo + nb]
+        if mut.get("argmax_first_64"):
+            row = row[:, :64]
+        am.append(row.shape[1] - 1 - np.argmax(row[:, ::-1], axis=1) if mut.get("argmax_last") else np.argmax(row, axis=1))
+    shifted = np.concatenate([seen[:, lo:lo + nb] for _, lo, nb in heads], axis=1)
+    return {"feat": feat, "logits": logits, "argmax": np.stack(am, axis=1).astype(np.int32), "ypr": decode_f64(shifted),
+            "bound": np.float64((np.abs(feat) @ np.abs(D) + 4 * np.abs(bias)).max())}
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_heads_cached(family: str, n: int):
+    r = ref_heads(head_const_inputs(family, n), head_snapshot(family))
+    out = {"feat": r["feat"].astype(np.float32), "logits": r["logits"].astype(np.float32), "argmax": r["argmax"], "ypr": r["ypr"]}
+    assert np.array_equal(out["feat"], r["feat"]) and np.array_equal(out["logits"], r["logits"])
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def expected_heads(family: str, n: int) -> Dict[str, np.ndarray]:
+    """`feat`, `logits` (float32 images of exact integers), `argmax` (int32) and `ypr` (float64) for head_const_inputs(family, n)."""
+    big = _expected_heads_cached(family, N_MAX if n <= N_MAX else n)
+    return {k: v[:n] for k, v in big.items()}
+
+
+# ---- the whole forward ---------------------------------------------------------------------------------------------------------
+def stem_tap(co):
+    """Stem output co of the forward snapshot reads tap (ky, kx) of input channel ci: all 27 (tap, channel) pairs occur."""
+    t = (5 * np.asarray(co) + 2) % 27
+    return t // 9, (t // 3) % 3, t % 3
+
+
+@functools.lru_cache(maxsize=None)
+def forward_snapshot() -> Dict[str, np.ndarray]:
+    w = dict(snapshot("routing"))
+    k = np.zeros((3, 3, 3, spec.STEM_C), np.float32)
+    co = np.arange(spec.STEM_C)
+    k[stem_tap(co) + (co,)] = 1
+    k.setflags(write=False)
+    w["stem/conv/kernel"] = k
+    return w
+
+
+def forward_images(n: int, first: int = 0) -> np.ndarray:
+    """float32 [n, 224, 224, 3], values 0 or 18..24 on the lines pattern: every channel carries TWO wrapped diagonals whose shifts
+    differ in parity (a stride-2 tap (ky, kx) sees the pixels with row = ky and column = kx modulo 2 only: one diagonal reaches the
+    taps with kx - ky even, the other one the rest; with a single diagonal half of the stem's channels would be zero), along every row
+    or, in the crop's low channels (_hi), along every third row."""
+    x = np.zeros((n, 224, 224, 3), np.float32)
+    for j in range(n):
+        i = first + j
+        rng = np.random.default_rng([40, i])
+        for c in range(3):
+            shift = int(rng.integers(112)) * 2
+            for d in range(2):
+                rows = np.arange(224) if _hi(i, np.array(c)) else np.arange(int(rng.integers(3)), 224, 3)
+                cols = (rows + shift + d + 2 * int(rng.integers(8))) % 224 if (c + d) % 2 == 0 else (shift + d + 2 * int(rng.integers(8)) - rows) % 224
+                x[j, rows, cols, c] = rng.integers(18, 25, size=len(rows))
+        for t, (r, c) in enumerate(((0, 0), (0, 223), (223, 0), (223, 223))):
+            x[j, r, c, (i + t) % 3] = 18 + (i + t) % 7
+    return x
+
+
+def ref_stem(x: np.ndarray, w: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The stem on an integer image: Conv2D 3 x 3, stride 2, 'SAME' as the oracle pads the even 224 input (nothing before, one row
+    and column of zeros after), BatchNorm as the identity plus beta, Swish on the exact set."""
+    x = np.asarray(x, np.float32)
+    n = x.shape[0]
+    out_size, before, after = spec.same_pad(spec.IMG, 3, 2)
+    assert (out_size, before, after) == (112, 0, 1)
+    xp = np.zeros((n, spec.IMG + 1, spec.IMG + 1, 3), np.float32)
+    xp[:, :spec.IMG, :spec.IMG] = x
+    k = w["stem/conv/kernel"]
+    pre = np.zeros((n, 112, 112, spec.STEM_C), np.float32) + w["stem/bn/beta"]
+    bound = np.zeros((n, 112, 112, spec.STEM_C), np.float32) + np.abs(w["stem/bn/beta"])
+    for ky in range(3):
+        for kx in range(3):
+            patch = xp[:, ky:ky + 223:2, kx:kx + 223:2]
+            pre += patch @ k[ky, kx]
+            bound += np.abs(patch) @ np.abs(k[ky, kx])
+    return {"pre": pre, "out": swish_exact(pre), "bound": np.float64(bound.max())}
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_forward_cached(n: int, first: int):
+    w = forward_snapshot()
+    S, stats = [], {"bound": 0.0, "exact": True}
+    for lo in range(0, n, 3):          # (three crops at a time: the 112 x 112 x 96 tensors of block 2)
+        r = ref_stem(forward_images(min(3, n - lo), first + lo), w)
+        stats["bound"] = max(stats["bound"], float(r["bound"]))
+        stats["exact"] = stats["exact"] and bool(in_exact_set(r["pre"]).all())
+        x = r["out"]
+        for index in range(1, 17):
+            b = ref_block(x, w, index)
+            stats["bound"] = max(stats["bound"], float(b["bound"]))
+            stats["exact"] = stats["exact"] and all(bool(in_exact_set(b[k]).all()) for k in ("expand_pre", "dw_pre") if k in b)
+            stats["exact"] = stats["exact"] and bool((b["gate"] == 1).all())
+            x = b["out"]
+        h = ref_head(x, w)
+        stats["bound"] = max(stats["bound"], float(h["bound"]))
+        stats["exact"] = stats["exact"] and bool(in_exact_set(h["pre"]).all()) and float(h["conv"].max()) <= 2048
+        S.append(h["S"])
+    S = np.concatenate(S)
+    S.setflags(write=False)
+    return S, stats
+
+
+def expected_forward(n: int, first: int = 0) -> Dict[str, np.ndarray]:
+    """forward_snapshot() on forward_images(n, first): `S` [n, 1280] the exact pooled sums (float64 integers), `logits` [n, 252] =
+    float32(S[head_feature(j)]) * float32(1/49) (one rounding: the routing Dense multiplies by 1 and adds zeros), `argmax`, `ypr`
+    (float64 decode of those logits), and the chain's `bound` / `exact` (test_probe_cpu.py asserts them)."""
+    S, stats = _expected_forward_cached(N_MAX if (first == 0 and n <= N_MAX) else n, first)
+    S = S[:n]
+    assert S.max() < 2 ** 24
+    logits = S[:, head_feature(np.arange(spec.N_LOGITS))].astype(np.float32) * INV49
+    return {"S": S, "logits": logits, "argmax": argmax_first(logits), "ypr": decode_f64(logits), **stats}
+
+
+def head_pooled_inputs(family: str, n: int) -> np.ndarray:
+    """Head inputs of the routing and dense_expand snapshots that are constant over the 49 positions (their features pool to
+    integers).  routing: the crops of head_const_inputs("dense_heads", .).  dense_expand: ten non-zero channels per crop, which walk
+    with the crop (10 x 24 x 8 = 1920 in the non-positive class: below 2048)."""
+    assert family in ("routing", "dense_expand")
+    x = head_const_inputs("dense_heads", n).copy()
+    if family == "dense_expand":
+        for i in range(n):
+            keep = (7 * i + 32 * np.arange(10)) % 320
+            v = np.zeros(320, np.float32)
+            v[keep] = np.where(x[i, 0, 0, keep] == 0, 18 + i % 7, x[i, 0, 0, keep])
+            x[i] = v
+    return x

@@ -363,3 +363,199 @@ def test_head_probes():
         lg = O.heads(f, w)
         assert np.allclose(lg, r["logits"][:3], rtol=1e-7, atol=1e-12)
         assert len({x[i].tobytes() for i in range(37)}) == 37
+
+
+# ---- the heads stage and the whole forward ----------------------------------------------------------------------------------------
+PACKED_SHA256 = {"routing": "0228c2b29f3be46294bd626d7cad723ed9b331b84057dac93dcb65d2e53f9bd0",
+                 "dense_expand": "4bdc22b725527414b16b03190f02c8bde106dfce8c5cdee3dab10bb11fda936e",
+                 "dense_dw": "c9918f786d6d3b552398ae3be8c7de6ae5bc8087a4cede7ba96697e1759d7649",
+                 "dense_project": "a2b31dc4c0a2464c60b4b3b445d6e6f114308ee799bd6c3feb449bcfad3207df"}
+N_HEADS_BIG = 37          # the largest batch of the heads tests on the GPU (test_probe_gpu.N_XCD_RAGGED)
+
+
+@pytest.mark.parametrize("family", P.FAMILIES)
+def test_the_block_families_pack_to_the_same_bytes(family):
+    """The four families of the MBConv probes are what they were before the heads families were added: the sha256 of W.pack of
+    each, taken before that edit."""
+    import hashlib
+    from whenet_hip import weights as W
+    assert P.FAMILIES == tuple(PACKED_SHA256)
+    assert hashlib.sha256(bytes(W.pack(P.snapshot(family)))).hexdigest() == PACKED_SHA256[family]
+
+
+def test_pooling_49_equal_integers_is_exact():
+    """float32(49 m) * (float32(1) / float32(49)) == m for m = 0..4096 (the rounded constant is 2.05e-8 below 1/49, relatively:
+    less than 2^-25), and 49 m is exact in float32 in any order of the additions (partial sums are multiples of m below 2^24)."""
+    m = np.arange(4097, dtype=np.float32)
+    assert abs(float(P.INV49) * 49 - 1) < 2.0 ** -25
+    assert np.array_equal((m * np.float32(49)) * P.INV49, m)
+    s = np.zeros(4097, np.float32)
+    for _ in range(49):
+        s = s + m
+    assert np.array_equal(s, m * np.float32(49)) and np.array_equal(s * P.INV49, m)
+
+
+@pytest.mark.parametrize("family", P.HEAD_FAMILIES)
+def test_heads_reference_is_the_oracle_and_stays_exact(family):
+    w = P.head_snapshot(family)
+    x = P.head_const_inputs(family, N_HEADS_BIG)
+    assert np.isin(x, [0] + list(range(18, 25))).all() and (x == x[:, :1, :1, :]).all()
+    assert len({x[i].tobytes() for i in range(len(x))}) == len(x)
+    assert np.array_equal(x[:P.N_MAX], P.head_const_inputs(family, P.N_MAX))          # crop i is a function of i alone
+    r = P.ref_heads(x, w)
+    for key in ("feat", "logits"):
+        assert np.array_equal(r[key], np.rint(r[key])), key
+    assert 0 <= r["feat"].min() and r["feat"].max() <= 2048 and r["bound"] < 2 ** 24          # (every partial sum is below `bound`)
+    conv = w["head/conv/kernel"][0, 0]
+    assert ((conv != 0).sum(axis=0) == 1).all() and (conv >= 0).all()          # one positive weight per feature
+    e = P.expected_heads(family, N_HEADS_BIG)
+    assert e["feat"].dtype == np.float32 and np.array_equal(e["logits"], r["logits"]) and np.array_equal(e["argmax"], r["argmax"])
+    # the float64 oracle on the same weights and inputs.  Its own error: Swish(z) = z (1 - e^-z) is short of z by up to 18 e^-18 =
+    # 2.7e-7 per feature (BatchNorm adds 1e-15 of it): 3.5e-8 of the sum |feat||W|, as in test_reference_is_the_oracle_and_stays_exact
+    f = O.swish(O.batchnorm(O.conv2d(x[:5].astype(np.float64), w["head/conv/kernel"], 1), w, "head/bn"))
+    assert np.abs(f - np.rint(f)).max() <= 1e-6 and np.array_equal(np.rint(f.mean(axis=(1, 2))), r["feat"][:5])
+    lg = O.heads(f, w)
+    tol = max(1e-6, 3.5e-8 * float(r["bound"]))
+    assert tol < 0.25 and np.abs(lg - r["logits"][:5]).max() <= tol, (np.abs(lg - r["logits"][:5]).max(), tol)
+    assert np.array_equal(O.argmax_bins(r["logits"]), r["argmax"])
+    assert np.array_equal(np.stack(O.decode(r["logits"]), axis=1), r["ypr"])
+    D, bias = P.dense_matrix(w)
+    if family == "dense_heads":
+        assert (D != 0).all() and set(np.unique(D)) == {-2, -1, 1, 2} and (bias != 0).all() and np.array_equal(bias, np.rint(bias))
+        assert {1, 2, 3, 5, 8, 13, 40, 85} == set(np.unique(conv[conv != 0])) and set(conv.argmax(axis=0)) == set(range(320))
+    else:
+        j = np.arange(spec.N_LOGITS)
+        assert len(set(P.decode_channel(j))) == spec.N_LOGITS and len(set(P.decode_feature(j))) == spec.N_LOGITS
+        assert ((D != 0).sum(axis=0) == 1).all() and np.array_equal(D.argmax(axis=0), P.decode_feature(j))
+        assert np.array_equal(conv.argmax(axis=0)[P.decode_feature(j)], P.decode_channel(j))
+        assert np.array_equal(r["logits"], P.DECODE_GAIN * x[:, 0, 0, P.decode_channel(j)])          # injective in ONE channel
+        # the features behind the logits lie in every workgroup quarter and every 40-channel wave slice
+        assert set(P.decode_feature(j) // 40) == set(range(32))
+
+
+def test_dense_heads_coverage():
+    """In the batch of 17: every one of the 1280 features is non-zero in some crop, and every (workgroup quarter, wave slice) of
+    the contraction -- 40 features for the 8-wave form of the four-workgroup kernel, 80 for its 4-wave form and for the 16 waves of
+    the single-workgroup kernel -- contributes a non-zero amount to every logit in some crop."""
+    w = P.head_snapshot("dense_heads")
+    r = P.ref_heads(P.head_const_inputs("dense_heads", P.N_MAX), w)
+    assert (r["feat"] != 0).any(axis=0).all()
+    D, _ = P.dense_matrix(w)
+    for width in (40, 80, 320):
+        for c0 in range(0, spec.FEAT, width):
+            part = r["feat"][:, c0:c0 + width] @ D[c0:c0 + width]
+            assert (part != 0).any(axis=0).all(), (width, c0)
+
+
+def test_decode_rows_are_what_they_claim():
+    x = P.head_const_inputs("decode", N_HEADS_BIG)
+    e = P.expected_heads("decode", N_HEADS_BIG)
+    lg = e["logits"].astype(np.float64)
+    for n in (P.N_MAX, 15, 11):          # every kind of row on the 120-bin head and on a 66-bin head (on both of them, in fact)
+        for h in range(3):
+            assert {P.decode_kind(i, h) for i in range(n)} == set(P.DECODE_ROWS), (n, h)
+    for i in range(N_HEADS_BIG):
+        for h, (_, lo, nb) in enumerate(P.HEADS):
+            kind, row, am = P.decode_kind(i, h), lg[i, lo:lo + nb], int(e["argmax"][i, h])
+            top = np.flatnonzero(row == row.max())
+            if kind == "equal":
+                assert len(top) == nb and am == 0
+            elif kind in P.DECODE_MAXIMA:
+                assert tuple(top) == P.DECODE_MAXIMA[kind][0 if nb == 120 else 1] and am == top[0]
+            elif kind == "one_hot":
+                assert len(top) == 1 and np.sort(row)[-2] <= row.max() - 104 and np.exp(np.float32(-104)) == 0
+            elif kind == "narrow":
+                assert row.max() - row.min() <= 6 and 0.25 * nb < len(top) < 0.75 * nb
+            else:
+                assert kind == "wide" and len(top) > 1 and row.max() - row.min() == 30 and am == top[0]
+
+
+def softmax_expectation_f32(logits):
+    """utils.softmax plus the expectation, plainly in float32 numpy (what any float32 kernel computes, up to the order of the sums)."""
+    out = []
+    for h, (_, lo, nb) in enumerate(P.HEADS):
+        z = logits[:, lo:lo + nb].astype(np.float32)
+        z = z - z.max(axis=1, keepdims=True)
+        a = np.exp(z)
+        p = a / a.sum(axis=1, keepdims=True, dtype=np.float32)
+        ex = (p * np.arange(nb, dtype=np.float32)).sum(axis=1, dtype=np.float32)
+        out.append(ex * np.float32(3) - np.float32(180 if h == 0 else 99))
+    return np.stack(out, axis=1)
+
+
+def test_decode_reference_sits_inside_the_gpu_bound():
+    """The GPU tests hold ypr to 2e-4 degrees of the float64 decode (the bound of test_decode_kernel): a plain float32 restatement is
+    within 1e-4 degrees of it on every designed row and on the forward probe's logits -- half of that bound is the kernel's own."""
+    e = P.expected_heads("decode", N_HEADS_BIG)
+    got = softmax_expectation_f32(e["logits"])
+    assert got.dtype == np.float32 and np.abs(got - e["ypr"]).max() < 1e-4, np.abs(got - e["ypr"]).max()
+    f = P.expected_forward(P.N_MAX)
+    assert np.abs(softmax_expectation_f32(f["logits"]) - f["ypr"]).max() < 1e-4
+
+
+def test_heads_mutations_are_visible():
+    """What a broken heads kernel would compute, restated, changes an expected tensor that the GPU tests compare -- at every batch
+    size they run (1, 3, 5, 17) where the mutation does not need a neighbour crop or a particular row."""
+    w = P.head_snapshot("dense_heads")
+    for n in (1, 3, 5, P.N_MAX):
+        x = P.head_const_inputs("dense_heads", n)
+        base = P.ref_heads(x, w)
+        for c0 in range(0, spec.FEAT, 40):                    # one 40-channel slice dropped: every logit of every crop moves
+            r = P.ref_heads(x, w, {"drop_slice": (c0, c0 + 40)})
+            assert changed(r["logits"], base["logits"]), (n, c0)
+            assert n < P.N_MAX or (r["logits"] != base["logits"]).any(axis=0).all(), c0
+        for q in range(4):                                    # partial vector p_q dropped (p3 among them)
+            assert changed(P.ref_heads(x, w, {"drop_partial": q})["logits"], base["logits"]), (n, q)
+        assert changed(P.ref_heads(x, w, {"bias_per_workgroup": 1})["logits"], base["logits"]), n
+        assert (P.ref_heads(x, w, {"bias_per_workgroup": 1})["logits"] != base["logits"]).all()
+    w = P.head_snapshot("decode")
+    for n in (3, 5, P.N_MAX):
+        x = P.head_const_inputs("decode", n)
+        base = P.ref_heads(x, w)
+        for mut in ({"logits_from": 1}, {"logits_from": n - 1}, {"pitch_from": 119}):
+            r = P.ref_heads(x, w, mut)
+            assert not np.array_equal(r["argmax"], base["argmax"]), (n, mut)
+            assert (np.abs(r["ypr"] - base["ypr"]) > 1).any(), (n, mut)          # (degrees: far beyond the 2e-4 of the GPU test)
+        assert np.array_equal(P.ref_heads(x, w, {"logits_from": 1})["logits"], base["logits"])
+    x = P.head_const_inputs("decode", P.N_MAX)
+    base = P.ref_heads(x, w)
+    for mut, kinds in (({"argmax_last": 1}, ("equal", "tie_63_64", "tie_1_65", "tie_5_100", "narrow", "wide")),
+                       ({"argmax_first_64": 1}, ("max_64", "max_last"))):
+        r = P.ref_heads(x, w, mut)
+        for h in range(3):
+            for kind in kinds:
+                rows = [i for i in range(P.N_MAX) if P.decode_kind(i, h) == kind]
+                assert rows and all(r["argmax"][i, h] != base["argmax"][i, h] for i in rows), (mut, h, kind)
+    # n = 1: the rows of crop 0 (equal | max_64 | tie_5_100) see both argmax mutations
+    for mut in ({"argmax_last": 1}, {"argmax_first_64": 1}):
+        assert not np.array_equal(P.ref_heads(x[:1], w, mut)["argmax"], base["argmax"][:1]), mut
+
+
+def test_forward_probe_stays_exact_and_is_the_oracle():
+    w = P.forward_snapshot()
+    k = w["stem/conv/kernel"]
+    assert ((k != 0).reshape(27, spec.STEM_C).sum(axis=0) == 1).all() and set(np.unique(k)) == {0, 1}
+    assert (k != 0).reshape(27, spec.STEM_C).any(axis=1).all()                      # every tap of every input channel is read
+    for key in w:
+        if not key.startswith("stem/conv"):
+            assert w[key] is P.snapshot("routing")[key], key
+    x = P.forward_images(P.N_MAX)
+    assert np.isin(x, [0] + list(range(18, 25))).all() and len({x[i].tobytes() for i in range(P.N_MAX)}) == P.N_MAX
+    stem = P.ref_stem(x[:3], w)
+    assert (stem["out"] != 0).any(axis=(0, 1, 2)).all(), "a stem channel is zero: its tap sees no diagonal"
+    e = P.expected_forward(P.N_MAX)
+    assert e["exact"] and e["bound"] < 2048, e["bound"]
+    S = e["S"]
+    assert np.array_equal(S, np.rint(S)) and S.max() < 2 ** 24 and ((S > 0).mean(axis=1) >= 0.3).all(), (S > 0).mean(axis=1).min()
+    lg = e["logits"]
+    assert lg.dtype == np.float32 and len({lg[i].tobytes() for i in range(P.N_MAX)}) == P.N_MAX
+    # one rounding: the float32 product of the exact sum and the rounded constant
+    sel = S[:, P.head_feature(np.arange(spec.N_LOGITS))]
+    assert np.abs(lg.astype(np.float64) - sel / 49).max() <= (2.0 ** -24 + 2.06e-8) * (sel / 49).max()
+    # the other image of the GPU test (run before every compared run) gives other logits
+    assert not np.array_equal(P.expected_forward(3, first=200)["logits"], lg[:3])
+    # the float64 oracle, stem to logits, on two crops.  Its own error: a value passes at most two Swishes per block, one in the stem
+    # and one in the head (34), each short by at most e^-18 of it; the sums have non-negative terms only (routing weights of 1, skips)
+    ref = O.heads(O.backbone(x[:2].astype(np.float64), w), w)
+    want = sel[:2] / 49
+    assert (np.abs(ref - want) <= 34 * np.exp(-18.0) * want + 1e-9).all(), np.abs(ref - want).max()

@@ -3,7 +3,14 @@ equality with the integer reference of tests/probe_cases.py (tests/test_probe_cp
 oracle, and that the probes can see the errors they are for).  Structure, not rounding points: the tolerance tests of
 tests/test_gpu_parity.py, tests/test_f32s.py and tests/test_mb7.py keep doing that.
 
-Every comparison is np.array_equal over every element, except the pooled features and logits of the head (a counted bound)."""
+Every comparison is np.array_equal over every element, except the pooled features and logits of the head on inputs that do not
+pool to integers (a counted bound: test_head) and the angles of the decode (2e-4 degrees of the float64 decode).
+
+The heads stage (pooling + Dense + softmax + decode) runs through op_head, which launches what the forward launches: under
+split_heads 0 / 1 x head_fuse 0 / 1 the single-workgroup kernel and the three instantiations of the four-workgroup kernel
+(test_dense_heads, test_decode_rows, test_ticket_counters).  The whole forward, stem to angles, runs through forward_f32
+(test_forward_probe).  The uint8 forward (byte LUT, stemdw.hip, graph replay, lanes) cannot be made exact -- the LUT's values are
+not integers: it stays with test_stem_fused_with_block_1_depthwise_is_bitwise_the_two_kernels and test_graph_replay_equals_eager."""
 import numpy as np
 import pytest
 
@@ -13,7 +20,7 @@ from whenet_hip import _lib, weights as W
 pytestmark = pytest.mark.gpu
 DTYPES = {"f32": _lib.F32, "f16": _lib.F16, "f32s": _lib.F32S}
 DEFAULTS = {"fuse_front": 1, "front_impl": 1, "se_fuse": 1, "front7": 1, "mb7": 0, "pw_impl": 0, "pw_staged": 1, "split_pw": 1,
-            "act_layout": 1, "xcd_map": 7, "f2s_mask": -1, "fold12": 1, "head_fuse": 1, "concurrent": 0}
+            "act_layout": 1, "xcd_map": 7, "f2s_mask": -1, "fold12": 1, "head_fuse": 1, "concurrent": 0, "split_heads": 1}
 F2S_ALL = (1 << 17) - 1
 # every value Engine::set_option accepts for each option that chooses a kernel form of ONE block, one option at a time against the
 # default, and the pairs.  act_layout does not act on a single block (the boundaries of the single-stage entry points are NHWC): it
@@ -43,7 +50,8 @@ def handles():
 
     def get(family, name):
         if (family, name) not in cache:
-            w = P.premise_snapshot() if family == "premise" else P.snapshot(family)
+            w = (P.premise_snapshot() if family == "premise" else P.forward_snapshot() if family == "forward" else
+                 P.head_snapshot(family) if family in P.HEAD_FAMILIES else P.snapshot(family))
             cache[(family, name)] = _lib.Handle(W.pack(w), device=0, dtype=DTYPES[name])
         return cache[(family, name)]
 
@@ -202,7 +210,8 @@ def test_chained_blocks_on_the_routing_snapshot(handles, name):
     input and output are NHWC; the tensors between its blocks take the layout the forward gives them, so on the f16 handle
     act_layout 1 and 2 run the blocked epilogue of the split-K project GEMM (outputs of blocks 12-15) and the blocked readers of
     front7.hip and of the skip (blocks 13-16), and act_layout 0 the NHWC ones; f32 and f32s handles have no blocked layout (the
-    three values are one schedule there).  head7.hip's blocked reader is reached through `forward` only (tests/test_act_layout.py)."""
+    three values are one schedule there).  head7.hip's blocked reader is reached through a forward only: test_forward_probe
+    below (bitwise) and tests/test_act_layout.py."""
     h = handles("routing", name)
     x = P.chain_inputs("routing")
     other = P.chain_inputs("routing", first=200)
@@ -260,14 +269,18 @@ def test_head(handles, family, name):
     below 2048), their sum S over the 49 positions is exact in float32 in any order; feat = S / 49 is held to
     |feat - S/49| <= r |S/49| with r the roundings between the exact sum and the returned value:
       head_fuse = 0 (csrc/head.hip:55, `(...) * (1.0f / 49.0f)`): the constant 1/49 rounded to float32 (2^-24) and the product
-                    (2^-24); the feature is returned as float32 (head.hip:61), no binary16 rounding;
+                    (2^-24); the feature is returned as float32 (head.hip:61), no binary16 rounding; the logits come from the
+                    four-workgroup kernel's own pooling (head.hip:198-199, the same two roundings; split_heads = 1, the default);
       head_fuse = 1 (csrc/head7.hip:136 for f16, :258 for f32 / f32s, `(...) * (1.0f / 49.0f)`): the same two.
     r = 2 * 2^-24 (+ 2^-48 for their product).  Logit j reads ONE pooled feature with weight 1 and bias 0: the same bound plus one
     float32 rounding for the Dense product and one for the sum (head.hip:76, :85-86).
     head_fuse = 1 also runs with option concurrent and xcd_map 0 / 4 / 7 at n = 15 (8 crop groups of 2: head7.hip's grouped workgroup
     placement relabels all of them) and n = 37 (10 groups of 4: 8 relabelled, 2 behind them, the last ragged); below 8 groups the
     placement is the plain one whatever the option says.
-    Before every compared call the head runs on another family's input (see scrub_block)."""
+    Before every compared call the head runs on another family's input (see scrub_block).
+    On inputs that are constant over the 49 positions (probe_cases.head_pooled_inputs) the sum is 49 m and the product rounds back to
+    m (test_probe_cpu.test_pooling_49_equal_integers_is_exact): there `feat` is BITWISE the integer features, under the same
+    settings and under split_heads = 0."""
     h = handles(family, name)
     r_feat = 2 * U32 + U32 * U32
     r_logit = r_feat + 2 * U32
@@ -288,3 +301,117 @@ def test_head(handles, family, name):
             el = np.abs(r["logits"].astype(np.float64) - ref["logits"])
             assert (ef <= r_feat * np.abs(feat)).all(), (family, name, n, setting, np.argwhere(ef > r_feat * np.abs(feat))[:10].tolist())
             assert (el <= r_logit * np.abs(ref["logits"])).all(), (family, name, n, setting, np.argwhere(el > r_logit * np.abs(ref["logits"]))[:10].tolist())
+        xp = P.head_pooled_inputs(family, n)
+        refp = P.ref_head(xp, w)
+        assert P.in_exact_set(refp["pre"]).all() and refp["bound"] < 2048 and (refp["conv"] == refp["conv"][:, :1, :1]).all()
+        assert (refp["S"] > 0).mean() > 0.3 and len({xp[i].tobytes() for i in range(n)}) == n
+        for setting in [{"head_fuse": 0}, {"head_fuse": 1}, {"head_fuse": 0, "split_heads": 0}] + xcd:
+            with options(h, setting):
+                h.op_head(other)
+                r = h.op_head(xp)
+            same(r["feat"], refp["conv"][:, 0, 0, :], f"{family} {name} n={n} {setting} feat (pooled integers)")
+
+
+# ---- the heads stage: op_head launches what the forward launches ----------------------------------------------------------------
+HEAD_MATRIX = [{"split_heads": s, "head_fuse": f} for s in (0, 1) for f in (0, 1)]
+HEAD_XCD = [{"head_fuse": 1, "concurrent": 1, "xcd_map": v} for v in (0, 4, 7)]
+HEAD_OTHER = {"dense_heads": "decode", "decode": "dense_heads"}
+DEG = 2e-4          # |ypr - float64 decode|: the bound of test_gpu_parity.test_decode_kernel (the float32 reference alone uses < 1e-4)
+
+
+def check_heads(h, family, x, want, setting, what, ypr=False):
+    """op_head(x) under `setting` after op_head on the other heads family's crops under the same setting: every output buffer (and
+    the scratch the features come back through) then holds another input's results -- a workgroup that never drew the last ticket
+    leaves visibly wrong logits, not stale correct ones."""
+    other = P.head_const_inputs(HEAD_OTHER[family], len(x))
+    with options(h, setting):
+        r = h.op_head(other)
+        assert not np.array_equal(r["logits"], want["logits"]) and not np.array_equal(r["feat"], want["feat"])
+        r = h.op_head(x)
+    tag = f"{what} n={len(x)} {setting}"
+    same(r["logits"], want["logits"], tag + " logits")
+    same(r["feat"], want["feat"], tag + " feat")
+    assert np.array_equal(r["argmax"], want["argmax"]), (tag, np.argwhere(r["argmax"] != want["argmax"])[:10].tolist())
+    if ypr:
+        err = np.abs(r["ypr"].astype(np.float64) - want["ypr"])
+        assert (err < DEG).all(), (tag, float(err.max()), np.argwhere(err >= DEG)[:10].tolist())
+
+
+def head_settings(n):
+    return HEAD_MATRIX + (HEAD_XCD if n >= N_XCD else [])
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_dense_heads(handles, name):
+    """Dense +-1, +-2 kernels on integer features (0 or 18..2040): the 252 logits are exact integers, so ONE array holds, bit for
+    bit, for the single-workgroup kernel (split_heads = 0: 16 waves x 80 features) and for the four-workgroup kernel on pooled
+    features (head_fuse = 1: <float, true>, 4 waves x 80) and on the head conv's tensor (head_fuse = 0: <half, false> /
+    <float, false>, 8 waves x 40, its own pooling) -- every feature, every wave slice, every partial vector, the bias once.
+    n = 1, 3, 5, 17, and 15 / 37 with head7.hip's grouped placement as well."""
+    h = handles("dense_heads", name)
+    for n in BATCHES + (N_XCD, N_XCD_RAGGED):
+        x, want = P.head_const_inputs("dense_heads", n), P.expected_heads("dense_heads", n)
+        for setting in head_settings(n):
+            check_heads(h, "dense_heads", x, want, setting, f"dense_heads {name}")
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_decode_rows(handles, name):
+    """Designed logit rows (probe_cases.DECODE_ROWS: all equal, single maxima at bins 0 / 63 / 64 / last, exact ties across the lane
+    63 / lane 0 boundary, within a lane and between a lane's first and another lane's second element, one-hot, narrow, wide) reach
+    the decode of the forward's kernel through routed weights: logits bitwise, argmax the first index among equals, angles within
+    2e-4 degrees of the float64 decode -- under the same matrix of settings; op_decode (the single-workgroup kernel's copy of the
+    decode, fed logits directly) gets the same rows."""
+    h = handles("decode", name)
+    for n in BATCHES + (N_XCD, N_XCD_RAGGED):
+        x, want = P.head_const_inputs("decode", n), P.expected_heads("decode", n)
+        for setting in head_settings(n):
+            check_heads(h, "decode", x, want, setting, f"decode {name}", ypr=True)
+        h.op_decode(np.ascontiguousarray(want["logits"][::-1]))
+        ypr, am = h.op_decode(want["logits"])
+        assert np.array_equal(am, want["argmax"]), (name, n, np.argwhere(am != want["argmax"])[:10].tolist())
+        assert (np.abs(ypr.astype(np.float64) - want["ypr"]) < DEG).all(), (name, n)
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_ticket_counters(handles, name):
+    """split_heads = 1, back to back on one handle with nothing in between: 17 crops, 3, 17, 1 -- each run a different selection of
+    the crops (so that no position finds its own result already there), each bitwise its expectation: the ticket counters are back
+    at zero after every launch and no workgroup reads another crop's partial vectors."""
+    h = handles("dense_heads", name)
+    x, want = P.head_const_inputs("dense_heads", P.N_MAX), P.expected_heads("dense_heads", P.N_MAX)
+    runs = (np.arange(17), np.array([16, 15, 14]), np.arange(17)[::-1], np.array([5]))
+    for fuse in (1, 0):
+        with options(h, {"split_heads": 1, "head_fuse": fuse}):
+            got = [h.op_head(np.ascontiguousarray(x[sel])) for sel in runs]
+        for sel, r in zip(runs, got):
+            tag = f"dense_heads {name} head_fuse={fuse} crops {sel.tolist()}"
+            same(r["logits"], want["logits"][sel], tag + " logits")
+            same(r["feat"], want["feat"][sel], tag + " feat")
+            assert np.array_equal(r["argmax"], want["argmax"][sel]), tag
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_forward_probe(handles, name):
+    """forward_f32 (the real-valued entry point: no byte LUT, eager, stem.hip and block 1's depthwise conv as two kernels) on the
+    routing snapshot with a routing stem, images of 0 or 18..24: stem, blocks 1-16, head conv, pooling, Dense and decode as the
+    forward chains them, at n = 1, 3, 5, 17 under fold12 0 / 1 x head_fuse 0 / 1 x split_heads 0 / 1 and, on the f16 handle,
+    act_layout 0 / 1 / 2 (1 and 2 feed head7.hip its blocked input).  Logit j is float32(S) * float32(1/49) with S the exact
+    pooled sum -- one rounding, in every pooling expression (head.hip:55, :198-199, head7.hip:136, :258: a sum of integers in any
+    order, one product), then x 1 + 0 in the Dense layer: bitwise.  Argmax equal, angles within 2e-4 degrees.  Before every compared
+    run the handle runs another image."""
+    h = handles("forward", name)
+    layouts = (0, 1, 2) if name == "f16" else (1,)
+    for n in BATCHES:
+        x, other, want = P.forward_images(n), P.forward_images(n, first=200), P.expected_forward(n)
+        for lay in layouts:
+            for fold in (0, 1):
+                for setting in HEAD_MATRIX:
+                    setting = dict(setting, act_layout=lay, fold12=fold)
+                    with options(h, setting):
+                        assert not np.array_equal(h.forward_f32(other)[2], want["logits"])
+                        ypr, am, lg = h.forward_f32(x)
+                    tag = f"forward {name} n={n} {setting}"
+                    same(lg, want["logits"], tag + " logits")
+                    assert np.array_equal(am, want["argmax"]), tag
+                    assert (np.abs(ypr.astype(np.float64) - want["ypr"]) < DEG).all(), tag
