@@ -937,6 +937,14 @@ int whenet_front_plan(int dtype, int index, int32_t out[12]) {
     }
 }
 
+int whenet_front2_static_check(int row, int field, int delta) {
+    try {
+        return whenet::front2_static_selftest(row, field, delta) == 0 ? WHENET_OK : WHENET_EINVAL;
+    } catch (...) {
+        return WHENET_EINVAL;
+    }
+}
+
 int whenet_device_alloc(whenet_t* h, size_t nbytes, void** d_ptr) {
     if (d_ptr == nullptr) return WHENET_EINVAL;
     return guarded(h, [&](whenet::Engine& e) { *d_ptr = e.dev_alloc(nbytes); });

@@ -225,6 +225,9 @@ void Engine::set_option(const std::string& key, long value) {
         front7_ = value != 0;
     } else if (key == "fold12") {
         fold12_ = value != 0;
+    } else if (key == "front2_static") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "front2_static must be 0 (runtime tile geometry everywhere) or 1 (per layer, default)");
+        front2_static_ = value != 0;
     } else if (key == "stem_fuse") {
         stem_fuse_ = value != 0;
     } else if (key == "act_layout") {
@@ -487,6 +490,16 @@ bool Engine::act_blocked(int index) const {
     return act_layout_ == 2 || (index <= 16 && WINS[index]);
 }
 
+// front2.hip's static-plan form (the tile geometry of front2_tuned.inc's row as compile-time constants): option front2_static = 1
+// asks for it on the blocks of the per-layer table; launch_front2 still runs the generic form where the launch is not the row's
+// layer and plan (fold12 = 0, WHENET_FRONT_NO_TUNED, WHENET_FRONT_THREADS).  Same bits either way.
+bool Engine::front2_static(int index) const {
+    // [block index]: the blocks whose shapes have a static form (docs/experiments.md section 24 holds the per-layer verdicts)
+    static constexpr bool WINS[17] = {false, false, true, true, true, true, false, true, true, true, true, true, true,
+                                      false, false, false, false};       // blocks 2-5 and 7-12
+    return front2_static_ && index >= 0 && index <= 16 && WINS[index];
+}
+
 void* Engine::enqueue_blocks(int first, int last, const View& v, void* cur, int n, hipStream_t s, LaunchRecorder* rec,
                              bool b1_dw_done) {
     const bool fold = fold12_active() && first <= 1 && last >= 2;
@@ -614,7 +627,9 @@ void Engine::enqueue_front(const DevBlock& b, const BlockSchedule& bs, const Vie
         a.xcd_grouped = xcd_grouped(1, n);
         a.plan = b.f2plan;
         a.plan.threads = front2_threads(b.f2plan, n);
-        R(p + "/front", "front", kernel_name_front2(sp.k, sp.s, a.KSe, a.plan.threads, a.plan.xs, a.in_gate != nullptr).c_str(),
+        a.static_form = front2_static(sp.index);
+        R(p + "/front", "front",
+          kernel_name_front2(sp.k, sp.s, a.KSe, a.plan.threads, a.plan.xs, a.in_gate != nullptr, front2_static_row(a)).c_str(),
           bytes(a.Cin), flops(a.Cin), [&] { launch_front2(a, s); });
     } else if (bs.use_f2s) {
         Front2sArgs a{};

@@ -64,6 +64,70 @@ struct F2Params {
     int ntiles, chunks, n, xcd;       // launch geometry (1-D grid of ntiles * chunks * n workgroups, xcd_unit())
 };
 
+// ---- static plans --------------------------------------------------------------------------------------------------
+// Every geometry field above is the same for every launch of a layer, and each instantiation of the kernel serves one
+// or two layers whose plan is fixed in front2_tuned.inc: the static form of the kernel (whenet_front2_static_kernel)
+// takes them from a constexpr F2Shape instead of F2Params, so the compiler folds the divisions, the strip shapes and
+// the LDS offsets that otherwise sit in front of the workgroup's first load.  The table stays the one place a plan is
+// written down: f2_static_shape() restates make_front2_plan()'s arithmetic as a constexpr function of a table row, and
+// front2_static_check() compares the two field by field at the first launch of each shape.
+struct Tuned2 { int k, s, H, Cexp, CC, TH, TXG, xs, use, threads; };
+constexpr Tuned2 TUNED2[] = {
+#include "front2_tuned.inc"
+};
+constexpr int NTUNED2 = int(sizeof(TUNED2) / sizeof(TUNED2[0]));
+
+struct F2Shape {
+    int H, Ho, Cin, Cexp, pad, NTe;
+    int CC, TH, TXG, tiles_x, tiles_y, EH, EWp, RP, CP;
+    int off_stage, off_red, off_sum;
+    int R, RPse;
+    int ntiles, chunks;
+    int k, s, xs, threads, KS, gated, lds_bytes;      // what selects the instantiation, and the launch's LDS size
+};
+
+constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// The layer a table row stands for (EfficientNet-B0's MBConv6 blocks: Cexp = 6 Cin, squeeze-excite on Cin / 4) and its
+// plan.  Row 0 is block 2 as the default forward runs it: fed by block 1's gated depthwise output (option fold12), i.e.
+// 32 input channels and the GATED kernel.
+constexpr F2Shape f2_static_shape(int row) {
+    const Tuned2 t = TUNED2[row];
+    F2Shape g{};
+    g.k = t.k;  g.s = t.s;  g.xs = t.xs;  g.threads = t.threads;
+    g.gated = (t.k == 3 && t.s == 2 && t.H == 112) ? 1 : 0;
+    g.H = t.H;
+    g.Ho = cdiv(t.H, t.s);
+    g.Cexp = t.Cexp;
+    g.Cin = g.gated ? 32 : t.Cexp / 6;
+    g.KS = cdiv(g.Cin, 16);
+    g.R = t.Cexp / 24;
+    g.RPse = (g.R + 3) & ~3;
+    const int padt = (g.Ho - 1) * t.s + t.k - t.H;
+    g.pad = padt > 0 ? padt / 2 : 0;
+    g.NTe = cdiv(t.Cexp, 32);
+    const int OXG = cdiv(g.Ho, 4), nch = (3 * t.s + t.k + t.xs + 3) / 4;
+    g.CC = t.CC < t.Cexp ? t.CC : t.Cexp;
+    g.TH = t.TH;
+    g.TXG = t.TXG;
+    g.tiles_x = cdiv(OXG, t.TXG);
+    g.tiles_y = g.Ho / t.TH;
+    g.ntiles = g.tiles_x * g.tiles_y;
+    g.chunks = cdiv(t.Cexp, g.CC);
+    g.EH = (t.TH - 1) * t.s + t.k;
+    g.EWp = 4 * (t.s * (t.TXG - 1) + nch);
+    g.RP = g.EWp * 2;
+    int cp = g.EH * g.RP + 8;
+    cp = (cp + 63) / 64 * 64;
+    g.CP = (cp - 32 >= g.EH * g.RP + 8) ? cp - 32 : cp + 32;
+    const int ncq = cdiv((t.TH / RL) * t.TXG, 4);
+    g.off_stage = (g.CC * g.CP + 15) & ~15;
+    g.off_red = g.off_stage + (t.threads / 64) * 2048;
+    g.off_sum = g.off_red + ncq * g.CC * 4;
+    g.lds_bytes = g.off_sum + g.CC * 4;
+    return g;
+}
+
 // BN + Swish of one expand task (32 pixels x 32 channels; this lane: channel ch, four runs of 4 consecutive pixels)
 // into the tile.  EDGE: the strip hangs over the in-image rows / groups -- those runs are skipped.
 template <bool EDGE>
@@ -89,8 +153,15 @@ __device__ __forceinline__ void expand_store(const float16v& acc, float bias, un
 // XS: the tile's x origin is moved XS pixels to the left (7-wide 5x5 layers: XS = 2 puts image column 0 on a group
 // boundary -- 8 instead of 12 pixel slots per row in the expand -- at the price of one more Toeplitz chunk).
 // GATED: the expand contracts (in_gate[crop] * x) -- block 2 fed by block 1's depthwise output (option fold12).
-template <int K, int S, int KS, int NTHR, int XS, bool GATED>
-__global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
+// ROW: -1 = the geometry is read from F2Params; >= 0 = it is f2_static_shape(ROW), folded at compile time (pointers, n, xcd
+// and the gate stay runtime).  One body: GEO(f) is the field either way.
+template <int K, int S, int KS, int NTHR, int XS, bool GATED, int ROW>
+__device__ __forceinline__ void front2_body(const F2Params p) {
+    constexpr F2Shape sg = f2_static_shape(ROW < 0 ? 0 : ROW);
+    static_assert(ROW < 0 || (sg.k == K && sg.s == S && sg.KS == KS && sg.threads == NTHR && sg.xs == XS && (sg.gated != 0) == GATED),
+                  "front2: the static plan belongs to another instantiation");
+#define GEO(f) (ROW >= 0 ? sg.f : p.f)
+    constexpr bool ONE_TILE = ROW >= 0 && sg.CC <= 32;       // a chunk is one 32-channel MFMA tile: every expand task is of tile 0
     constexpr int NCH = (3 * S + K + XS + 3) / 4;     // 4-pixel input chunks a 4-pixel output group reads
     constexpr int NER = (RL - 1) * S + K;             // input rows of a column
     constexpr int NWAVE = NTHR / 64;
@@ -105,17 +176,18 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // (scalar: the task / item loops are uniform)
     const int g = lane >> 5, lm = lane & 31;
     int b, tile, chunk;
-    xcd_front(int(blockIdx.x), p.ntiles, p.chunks, p.n, p.xcd != 0, b, tile, chunk);      // (device_math.h)
-    const int tyi = tile / p.tiles_x, txi = tile - tyi * p.tiles_x;
-    const int c0 = chunk * p.CC;
-    const int ccur = (p.Cexp - c0 < p.CC) ? (p.Cexp - c0) : p.CC;
-    const int H = p.H, Cin = p.Cin, RP = p.RP, CP = p.CP;
-    const int oy0 = tyi * p.TH, ox0 = txi * p.TXG * 4;
-    const int iy0 = oy0 * S - p.pad, ix0 = ox0 * S - p.pad - XS;
+    xcd_front(int(blockIdx.x), GEO(ntiles), GEO(chunks), p.n, p.xcd != 0, b, tile, chunk);      // (device_math.h)
+    const int tyi = tile / GEO(tiles_x), txi = tile - tyi * GEO(tiles_x);
+    const int c0 = chunk * GEO(CC);
+    const int ccur = (ROW >= 0 && sg.Cexp % sg.CC == 0) ? sg.CC                                  // (every chunk is whole)
+                                                        : ((GEO(Cexp) - c0 < GEO(CC)) ? (GEO(Cexp) - c0) : GEO(CC));
+    const int H = GEO(H), Cin = GEO(Cin), RP = GEO(RP), CP = GEO(CP);
+    const int oy0 = tyi * GEO(TH), ox0 = txi * GEO(TXG) * 4;
+    const int iy0 = oy0 * S - GEO(pad), ix0 = ox0 * S - GEO(pad) - XS;
 
     // ---- the in-image part of the tile, in tile coordinates (er, ex) = (iy - iy0, ix - ix0) -----------------
-    const int er_lo = iy0 < 0 ? -iy0 : 0, er_hi = (iy0 + p.EH < H) ? p.EH : H - iy0;
-    const int ex_lo = ix0 < 0 ? -ix0 : 0, ex_hi = (ix0 + p.EWp < H) ? p.EWp : H - ix0;
+    const int er_lo = iy0 < 0 ? -iy0 : 0, er_hi = (iy0 + GEO(EH) < H) ? GEO(EH) : H - iy0;
+    const int ex_lo = ix0 < 0 ? -ix0 : 0, ex_hi = (ix0 + GEO(EWp) < H) ? GEO(EWp) : H - ix0;
     const int g_lo = ex_lo >> 2, g_hi = (ex_hi + 3) >> 2;
     const int NG = g_hi - g_lo, NR = er_hi - er_lo;
     // A strip (the 32 rows of one MFMA tile) = SR rows x SC groups of 4 pixels, SR * SC = 8: every lane's pixels sit
@@ -181,7 +253,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
         for (int ks = 0; ks < KS; ++ks) {
             if constexpr (GATED) {
                 // wep: the same fragment order as the f16 image, 8 floats per lane
-                const float* wq = reinterpret_cast<const float*>(p.wep) + ((size_t(ks) * p.NTe + (c0 >> 5) + tl) * 64 + lane) * 8;
+                const float* wq = reinterpret_cast<const float*>(p.wep) + ((size_t(ks) * GEO(NTe) + (c0 >> 5) + tl) * 64 + lane) * 8;
                 const float4v lo = *reinterpret_cast<const float4v*>(wq) * gq[ks][0];
                 const float4v hi = *reinterpret_cast<const float4v*>(wq + 4) * gq[ks][1];
 #pragma unroll
@@ -190,7 +262,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
                     w[ks][4 + e] = half_t(hi[e]);
                 }
             } else {
-                w[ks] = wf0[(size_t(ks) * p.NTe + tl) * 64];
+                w[ks] = wf0[(size_t(ks) * GEO(NTe) + tl) * 64];
             }
         }
         const int ch = tl * 32 + lm;
@@ -231,10 +303,11 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
             if (++rbi == nsr) rbi = 0;                         // (next channel tile: the strips start over)
         }
     };
-    const bool fix_l = ex_lo > 0, fix_r = p.EWp > ex_hi;       // (tile touches the left / right image border, or has
+    const bool fix_l = ex_lo > 0, fix_r = GEO(EWp) > ex_hi;       // (tile touches the left / right image border, or has
                                                                //  slack groups behind it)
     if (t_begin < t_end) {
-        tl = __builtin_amdgcn_readfirstlane(t_begin / nstrip);          // (keeps the loop state in scalar registers)
+        // (static form with one channel tile per chunk: every task is of tile 0 -- no division in front of the weight fragments)
+        tl = ONE_TILE ? 0 : __builtin_amdgcn_readfirstlane(t_begin / nstrip);          // (keeps the loop state in scalar registers)
         const int st = t_begin - tl * nstrip;
         rb = __builtin_amdgcn_readfirstlane(st / nsc);
         cbk = st - rb * nsc;
@@ -245,7 +318,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
         for (int d = 0; d < D; ++d) issue(d);
     }
     {   // rows of the tile outside the image are 'SAME' zeros of the EXPANDED tensor (top / bottom tiles only)
-        const int nz = er_lo + (p.EH - er_hi);
+        const int nz = er_lo + (GEO(EH) - er_hi);
         if (nz > 0) {                                           // (uniform)
             const float r_nz = __builtin_amdgcn_rcpf(float(nz));
             for (int pr = tid; pr < ccur * nz; pr += NTHR) {
@@ -290,11 +363,11 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
             cbk = 0;
             if (++rb == nsr) {
                 rb = 0;
-                ++tln;
+                if (!ONE_TILE) ++tln;                          // (one channel tile: the strips wrap behind the last task only)
             }
         }
         issue(d);
-        if (t + 1 < t_end && tln != tl) load_w(tln);           // (rare: at most once or twice per wave)
+        if (!ONE_TILE && t + 1 < t_end && tln != tl) load_w(tln);      // (rare: at most once or twice per wave)
         tl = tln;
         if (ch < ccur) {
             if (nr_left >= SR && ng_left >= SC) expand_store<false>(acc, bias, ep, eoff, drd, dcd, nr_left, ng_left);
@@ -324,7 +397,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
                         half_t* rowp = reinterpret_cast<half_t*>(ep0 + dr * RP) - 4 * (g_lo + cbk_this * SC) + ex_hi;
 #pragma unroll
                         for (int q = 0; q < 8; ++q)
-                            if (ex_hi + q < p.EWp) rowp[q] = half_t(0);
+                            if (ex_hi + q < GEO(EWp)) rowp[q] = half_t(0);
                     }
                 }
             }
@@ -335,8 +408,8 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
     STAMP(2);
     // ---- depthwise taps: items (16-channel block, quad of columns), a contiguous range per wave ---------------
     const int ncb = (ccur + 15) >> 4;
-    const int ncol = (p.TH / RL) * p.TXG, ncq = (ncol + 3) >> 2, nitem = ncb * ncq;
-    const float r_txg = __builtin_amdgcn_rcpf(float(p.TXG));
+    const int ncol = (GEO(TH) / RL) * GEO(TXG), ncq = (ncol + 3) >> 2, nitem = ncb * ncq;
+    const float r_txg = __builtin_amdgcn_rcpf(float(GEO(TXG)));
     const int i_begin = (wave * nitem) / NWAVE, i_end = ((wave + 1) * nitem) / NWAVE;
     const int cl = lane >> 2, j = lane & 3;
     half4 A[K][NCH];
@@ -367,8 +440,8 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
         for (int i = 0; i < W1V; ++i) w1v[i] = 0.f;
         // (only the waves that hold an output jo < RPse need them -- block 2: R = 4, i.e. 16 lanes of wave 0; the other seven
         //  waves used to issue the same 16 strided loads and ~70 address instructions for nothing: round 5)
-        if (p.w1t != nullptr && wave * 16 < p.RPse) {          // (uniform; clamped addresses: no lane predicates)
-            const float* wrow = p.w1t + size_t(jo < p.R ? jo : p.R - 1) * p.Cexp + c0;
+        if (p.w1t != nullptr && wave * 16 < GEO(RPse)) {          // (uniform; clamped addresses: no lane predicates)
+            const float* wrow = p.w1t + size_t(jo < GEO(R) ? jo : GEO(R) - 1) * GEO(Cexp) + c0;
 #pragma unroll
             for (int i = 0; i < W1V; ++i) {
                 const int c = q + 4 * i;
@@ -376,18 +449,18 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
             }
         }
     }
-    unsigned char* stg = smem + p.off_stage + wave * 2048;
-    float* s_red = reinterpret_cast<float*>(smem + p.off_red);          // [ncq][CC]
-    float* s_sum = reinterpret_cast<float*>(smem + p.off_sum);          // [CC]
+    unsigned char* stg = smem + GEO(off_stage) + wave * 2048;
+    float* s_red = reinterpret_cast<float*>(smem + GEO(off_red));          // [ncq][CC]
+    float* s_sum = reinterpret_cast<float*>(smem + GEO(off_sum));          // [CC]
     // piece coordinates of this lane in the output stage: slot = (row * 4 + i) * 4 + j, two 16-byte halves per slot
     const int jP = (lane >> 1) & 3, iP = (lane >> 3) & 3, hP = lane & 1, rP = lane >> 5;
-    unsigned char* outb = reinterpret_cast<unsigned char*>(p.out + size_t(b) * p.Ho * p.Ho * p.Cexp);
-    const unsigned row_bytes = unsigned(p.Ho) * unsigned(p.Cexp) * 2u;
+    unsigned char* outb = reinterpret_cast<unsigned char*>(p.out + size_t(b) * GEO(Ho) * GEO(Ho) * GEO(Cexp));
+    const unsigned row_bytes = unsigned(GEO(Ho)) * unsigned(GEO(Cexp)) * 2u;
 
     for (int it = i_begin; it < i_end; ++it) {
         const int col = cq * 4 + j;                            // (this block's taps are in A: loaded in the prologue
         const int colc = col < ncol ? col : ncol - 1;          //  or behind the previous sweep)
-        const int seg = fdiv2(colc, r_txg), xgl = colc - seg * p.TXG;
+        const int seg = fdiv2(colc, r_txg), xgl = colc - seg * GEO(TXG);
         const int c = cb * 16 + cl;
         const unsigned char* bp = E + c * CP + ((c >> 3) & 1) * 8 + (seg * RL * S) * RP + xgl * (8 * S);
         float4v acc[RL];
@@ -423,13 +496,13 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
         const int oxb = ox0 + 4 * xgl;
         float m[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) m[i] = (okc && oxb + i < p.Ho) ? 1.f : 0.f;
+        for (int i = 0; i < 4; ++i) m[i] = (okc && oxb + i < GEO(Ho)) ? 1.f : 0.f;
         const int colP = cq_this * 4 + jP;
         const int colPc = colP < ncol ? colP : ncol - 1;
-        const int segP = fdiv2(colPc, r_txg), xglP = colPc - segP * p.TXG;
+        const int segP = fdiv2(colPc, r_txg), xglP = colPc - segP * GEO(TXG);
         const int oxP = ox0 + 4 * xglP + iP;
-        const bool okP = colP < ncol && oxP < p.Ho;
-        const unsigned obase = (__umul24(unsigned(oy0 + segP * RL + rP), unsigned(p.Ho)) + unsigned(oxP)) * unsigned(p.Cexp) * 2u +
+        const bool okP = colP < ncol && oxP < GEO(Ho);
+        const unsigned obase = (__umul24(unsigned(oy0 + segP * RL + rP), unsigned(GEO(Ho))) + unsigned(oxP)) * unsigned(GEO(Cexp)) * 2u +
                                unsigned(c0 + cb_this * 16 + hP * 8) * 2u;
         float2v sum2 = {0.f, 0.f};
         const float2v m01 = {m[0], m[1]}, m23 = {m[2], m[3]};
@@ -460,7 +533,7 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
         float sum = sum2[0] + sum2[1];
         sum += quad_xor1(sum);                                 // the 4 columns of the quad: (s0 + s1) + (s2 + s3)
         sum += quad_xor2(sum);
-        if (j == 0) s_red[cq_this * p.CC + c] = sum;
+        if (j == 0) s_red[cq_this * GEO(CC) + c] = sum;
     }
     STAMP(4);
     lds_barrier();
@@ -470,8 +543,8 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
     // reduce conv, in a fixed order --------------------------------------------------------------------------
     if (tid < ccur) {
         float t = 0.0f;
-        for (int q = 0; q < ncq; ++q) t += s_red[q * p.CC + tid];
-        if (p.w1t == nullptr) p.rpart[(size_t(b) * p.ntiles + tile) * p.Cexp + c0 + tid] = t;
+        for (int q = 0; q < ncq; ++q) t += s_red[q * GEO(CC) + tid];
+        if (p.w1t == nullptr) p.rpart[(size_t(b) * GEO(ntiles) + tile) * GEO(Cexp) + c0 + tid] = t;
         s_sum[tid] = t;
     }
     if (p.w1t == nullptr) {
@@ -482,10 +555,10 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
     {
         // 4 lanes per output j: lane q sums channels q, q+4, ..; combined (a0+a1)+(a2+a3)
         const int jo = tid >> 2, q = tid & 3;
-        if (jo < p.RPse) {                                      // (whole quads of lanes)
+        if (jo < GEO(RPse)) {                                      // (whole quads of lanes)
             float accr = 0.0f;
-            if (jo < p.R) {
-                const float* wrow = p.w1t + size_t(jo) * p.Cexp + c0;
+            if (jo < GEO(R)) {
+                const float* wrow = p.w1t + size_t(jo) * GEO(Cexp) + c0;
 #pragma unroll
                 for (int i = 0; i < W1V; ++i) {
                     const int c = q + 4 * i;
@@ -496,13 +569,91 @@ __global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
             const float pair = accr + quad_xor1(accr);
             const float tot = pair + quad_xor2(pair);
             if (q == 0)
-                p.rpart[((size_t(b) * p.ntiles + tile) * p.chunks + chunk) * p.RPse + jo] = (jo < p.R) ? tot : 0.0f;
+                p.rpart[((size_t(b) * GEO(ntiles) + tile) * GEO(chunks) + chunk) * GEO(RPse) + jo] = (jo < GEO(R)) ? tot : 0.0f;
         }
     }
     STAMP(6);
 }
+#undef GEO
+
+template <int K, int S, int KS, int NTHR, int XS, bool GATED>
+__global__ __launch_bounds__(NTHR) void whenet_front2_kernel(const F2Params p) {
+    front2_body<K, S, KS, NTHR, XS, GATED, -1>(p);
+}
+
+// The static form: the plan of front2_tuned.inc's row ROW as compile-time constants (same body, same data path, same bits).
+template <int K, int S, int KS, int NTHR, int XS, bool GATED, int ROW>
+__global__ __launch_bounds__(NTHR) void whenet_front2_static_kernel(const F2Params p) {
+    front2_body<K, S, KS, NTHR, XS, GATED, ROW>(p);
+}
 
 }  // namespace
+
+// ---- the static form's host side ---------------------------------------------------------------------------------------
+namespace {
+
+constexpr bool f2_has_static(int row) { return TUNED2[row].use != 0; }      // (the use = 0 rows never reach this kernel by default)
+
+// The first field in which the constexpr plan of a row and a launch's runtime geometry differ, or NULL.
+const char* f2_static_mismatch(const F2Shape& g, const Front2Args& a) {
+    const Front2Plan& pl = a.plan;
+    struct Field { const char* name; long long want, got; };
+    const Field fields[] = {
+        {"H", g.H, a.H}, {"Ho", g.Ho, a.Ho}, {"Cin", g.Cin, a.Cin}, {"Cexp", g.Cexp, a.Cexp}, {"pad", g.pad, a.pad}, {"NTe", g.NTe, a.NTe},
+        {"CC", g.CC, pl.CC}, {"TH", g.TH, pl.TH}, {"TXG", g.TXG, pl.TXG}, {"tiles_x", g.tiles_x, pl.tiles_x}, {"tiles_y", g.tiles_y, pl.tiles_y},
+        {"EH", g.EH, pl.EH}, {"EWp", g.EWp, pl.EWp}, {"RP", g.RP, pl.RP}, {"CP", g.CP, pl.CP},
+        {"off_stage", g.off_stage, pl.off_stage}, {"off_red", g.off_red, pl.off_red}, {"off_sum", g.off_sum, pl.off_sum},
+        {"R", g.R, a.R}, {"RPse", g.RPse, (a.R + 3) & ~3}, {"chunks", g.chunks, pl.chunks}, {"ntiles", g.ntiles, pl.tiles_x * pl.tiles_y},
+        {"k", g.k, a.k}, {"s", g.s, a.s}, {"xs", g.xs, pl.xs}, {"threads", g.threads, pl.threads}, {"KS", g.KS, a.KSe},
+        {"gated", g.gated, a.in_gate != nullptr ? 1 : 0}, {"lds_bytes", g.lds_bytes, (long long)pl.lds_bytes},
+    };
+    for (const Field& f : fields)
+        if (f.want != f.got) return f.name;
+    return nullptr;
+}
+
+void f2_static_require(const F2Shape& g, const Front2Args& a) {
+    const char* bad = f2_static_mismatch(g, a);
+    if (bad != nullptr) throw Error(WHENET_EINVAL, std::string("front2: the static plan differs from the runtime plan in field ") + bad);
+}
+
+}  // namespace
+
+// The row of front2_tuned.inc whose static form serves this launch, or -1: the caller asks for it (Front2Args::static_form), the
+// row has one, and the layer and what DEFINES its plan (CC, TH, TXG, xs, lanes) are the row's.  What make_front2_plan() derives from
+// them is not compared here but checked (front2_static_check): a difference there is an error, not another shape.
+int front2_static_row(const Front2Args& a) {
+    if (!a.static_form) return -1;
+    for (int r = 0; r < NTUNED2; ++r) {
+        if (!f2_has_static(r)) continue;
+        const F2Shape g = f2_static_shape(r);
+        if (g.k == a.k && g.s == a.s && g.H == a.H && g.Ho == a.Ho && g.Cin == a.Cin && g.Cexp == a.Cexp && g.pad == a.pad && g.NTe == a.NTe &&
+            g.KS == a.KSe && g.R == a.R && (g.gated != 0) == (a.in_gate != nullptr) && g.CC == a.plan.CC && g.TH == a.plan.TH &&
+            g.TXG == a.plan.TXG && g.xs == a.plan.xs && g.threads == a.plan.threads)
+            return r;
+    }
+    return -1;
+}
+
+void front2_static_check(int row, const Front2Args& a) {
+    WHENET_REQUIRE(row >= 0 && row < NTUNED2 && f2_has_static(row), WHENET_EINVAL, "front2: no static form for this row of the plan table");
+    f2_static_require(f2_static_shape(row), a);
+}
+
+// For the tests (no GPU): block `index`'s launch as the engine fills it, against its row's static plan with the field-th int of
+// F2Shape moved by delta.  Returns 0 when they agree, throws WHENET_EINVAL as a launch would when they do not.
+int front2_static_selftest(int row, int field, int delta) {
+    WHENET_REQUIRE(row >= 0 && row < NTUNED2 && f2_has_static(row), WHENET_EINVAL, "front2: no static form for this row of the plan table");
+    WHENET_REQUIRE(field >= -1 && field < int(sizeof(F2Shape) / sizeof(int)), WHENET_EINVAL, "front2: no such field");
+    F2Shape g = f2_static_shape(row);
+    Front2Args a{};
+    a.k = g.k;  a.s = g.s;  a.H = g.H;  a.Ho = g.Ho;  a.Cin = g.Cin;  a.Cexp = g.Cexp;  a.pad = g.pad;  a.NTe = g.NTe;  a.KSe = g.KS;  a.R = g.R;
+    a.in_gate = g.gated ? reinterpret_cast<const float*>(&g) : nullptr;      // (only compared with NULL)
+    a.plan = make_front2_plan(g.k, g.s, g.Ho, g.Cexp, TUNED2[row].CC, TUNED2[row].TH, TUNED2[row].TXG, TUNED2[row].threads, TUNED2[row].xs);
+    if (field >= 0) reinterpret_cast<int*>(&g)[field] += delta;
+    f2_static_require(g, a);
+    return 0;
+}
 
 namespace {
 
@@ -512,8 +663,12 @@ struct OncePerDevice {
     OncePerDevice() { for (auto& d : done) d.store(false, std::memory_order_relaxed); }
 };
 
-template <int K, int S, int KS, int NTHR, int XS = 0, bool GATED = false>
+template <int K, int S, int KS, int NTHR, int XS = 0, bool GATED = false, int ROW = -1>
 void launch_f2(const Front2Args& a, hipStream_t stream) {
+    const auto kernel = [] {
+        if constexpr (ROW >= 0) return &whenet_front2_static_kernel<K, S, KS, NTHR, XS, GATED, ROW>;
+        else return &whenet_front2_kernel<K, S, KS, NTHR, XS, GATED>;
+    }();
     const Front2Plan& pl = a.plan;
     F2Params p{};
     p.x = static_cast<const half_t*>(a.x);
@@ -537,13 +692,30 @@ void launch_f2(const Front2Args& a, hipStream_t stream) {
     WHENET_HIP_CHECK(hipGetDevice(&dev));
     if (dev >= 0 && dev < 64 && !attr.done[dev].load(std::memory_order_acquire)) {
         // (two threads may both get here: the call is idempotent, the flag only saves repeating it)
-        WHENET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(whenet_front2_kernel<K, S, KS, NTHR, XS, GATED>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        // (the static form: the first launch of this shape on this device -- its constexpr plan against the runtime one)
+        if constexpr (ROW >= 0) front2_static_check(ROW, a);
+        WHENET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr.done[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((whenet_front2_kernel<K, S, KS, NTHR, XS, GATED>), dim3(unsigned(pl.tiles_x * pl.tiles_y) * unsigned(pl.chunks) * unsigned(a.n)), dim3(NTHR),
+    hipLaunchKernelGGL(kernel, dim3(unsigned(pl.tiles_x * pl.tiles_y) * unsigned(pl.chunks) * unsigned(a.n)), dim3(NTHR),
                        pl.lds_bytes, stream, p);
     WHENET_HIP_CHECK(hipGetLastError());
+}
+
+// The static form of front2_tuned.inc's row `row` (front2_static_row()); the template arguments are checked against the
+// row by the body's static_assert.
+void launch_f2_static(int row, const Front2Args& a, hipStream_t stream) {
+    switch (row) {
+        case 0: launch_f2<3, 2, 2, 512, 0, true, 0>(a, stream); break;       // b2 (gated: fold12)
+        case 1: launch_f2<3, 1, 2, 256, 0, false, 1>(a, stream); break;      // b3
+        case 2: launch_f2<5, 2, 2, 256, 0, false, 2>(a, stream); break;      // b4
+        case 3: launch_f2<5, 1, 3, 256, 0, false, 3>(a, stream); break;      // b5
+        case 5: launch_f2<3, 1, 5, 256, 0, false, 5>(a, stream); break;      // b7, b8
+        case 6: launch_f2<5, 1, 5, 256, 0, false, 6>(a, stream); break;      // b9
+        case 7: launch_f2<5, 1, 7, 256, 0, false, 7>(a, stream); break;      // b10, b11
+        case 8: launch_f2<5, 2, 7, 256, 0, false, 8>(a, stream); break;      // b12
+        default: throw Error(WHENET_EINVAL, "front2: no static form for this row of the plan table");
+    }
 }
 
 template <int NTHR>
@@ -623,13 +795,6 @@ Front2Plan make_front2_plan(int k, int s, int Ho, int Cexp, int CC, int TH, int 
     return p;
 }
 
-namespace {
-struct Tuned2 { int k, s, H, Cexp, CC, TH, TXG, xs, use, threads; };
-const Tuned2 TUNED2[] = {
-#include "front2_tuned.inc"
-};
-}  // namespace
-
 Front2Plan plan_front2(int k, int s, int H, int Ho, int Cexp) {
     static const bool no_tuned = getenv("WHENET_FRONT_NO_TUNED") != nullptr;       // (probes only; read once)
     if (!no_tuned)
@@ -688,13 +853,16 @@ void launch_front2(const Front2Args& a, hipStream_t stream) {
     if (b.plan.threads != 256) {              // the stage / sums offsets depend on the wave count
         b.plan = make_front2_plan(a.k, a.s, a.Ho, a.Cexp, a.plan.CC, a.plan.TH, a.plan.TXG, a.plan.threads, a.plan.xs);
     }
-    if (b.plan.threads == 512) launch_f2_shape<512>(b, stream);
+    const int row = front2_static_row(b);
+    if (row >= 0) launch_f2_static(row, b, stream);
+    else if (b.plan.threads == 512) launch_f2_shape<512>(b, stream);
     else launch_f2_shape<256>(b, stream);
 }
 
-std::string kernel_name_front2(int k, int s, int kse, int threads, int xs, bool gated) {
-    return "whenet_front2_kernel<" + std::to_string(k) + ", " + std::to_string(s) + ", " + std::to_string(kse) + ", " +
-           std::to_string(threads) + ", " + std::to_string(xs) + ", " + (gated ? "true" : "false") + ">";
+std::string kernel_name_front2(int k, int s, int kse, int threads, int xs, bool gated, int static_row) {
+    return std::string(static_row >= 0 ? "whenet_front2_static_kernel<" : "whenet_front2_kernel<") + std::to_string(k) + ", " +
+           std::to_string(s) + ", " + std::to_string(kse) + ", " + std::to_string(threads) + ", " + std::to_string(xs) + ", " +
+           (gated ? "true" : "false") + (static_row >= 0 ? ", " + std::to_string(static_row) : std::string()) + ">";
 }
 
 }  // namespace whenet

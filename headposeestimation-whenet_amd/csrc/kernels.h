@@ -269,9 +269,15 @@ struct Front2Args {
     int k, s, H, Ho, Cin, Cexp, pad, KSe, NTe, n;
     Front2Plan plan;
     bool xcd_grouped = false;       // as FrontArgs::xcd_grouped
+    bool static_form = false;       // run the static-plan form of the kernel where front2_tuned.inc's row has one and this launch
+                                    // is that row's layer and plan (front2_static_row); same bits either way (engine option "front2_static")
 };
 void launch_front2(const Front2Args& a, hipStream_t stream);
-std::string kernel_name_front2(int k, int s, int kse, int threads, int xs, bool gated);
+// static_row >= 0: whenet_front2_static_kernel<..., static_row>, the plan of front2_tuned.inc's row as compile-time constants
+std::string kernel_name_front2(int k, int s, int kse, int threads, int xs, bool gated, int static_row = -1);
+int front2_static_row(const Front2Args& a);                   // the row whose static form launch_front2(a) runs, or -1 (the generic form)
+void front2_static_check(int row, const Front2Args& a);       // throws WHENET_EINVAL unless the row's constexpr plan equals a's, field by field
+int front2_static_selftest(int row, int field, int delta);    // (tests) the same check on a static plan with one field moved
 
 // ---- front2s.hip ------------------------------------------------------------------------
 // WHENET_F32S (float32 storage): the same stage with both convolutions on the matrix cores -- expand as binary16 hi/lo

@@ -146,6 +146,10 @@ WHENET_API int whenet_get_info(const whenet_t* h, whenet_info_t* out);
  *                  output, with block 1's project conv (linear) composed into block 2's expand weights when the
  *                  snapshot is loaded -- one launch and a 112x112x16 round trip through HBM less; 0 = the two convs
  *                  as two steps.  Same function, different rounding points: results agree to f16 rounding),
+ *          "front2_static" (0/1, default 1: the layers of an f16 handle that run front2.hip use, where the per-layer table says so,
+ *                  the form of that kernel whose tile geometry is compile-time constants (the plan of front2_tuned.inc's row; no
+ *                  index divisions or LDS offsets computed in front of the workgroup's first load); 0 = the runtime-geometry
+ *                  form everywhere.  Shapes and plans outside the table always run the runtime form.  Same bits either way),
  *          "poison" (0/1, default 0, debug: the activation arena is filled with NaN bit patterns before every forward --
  *                  a kernel that reads what the forward did not write shows up in the results),
  *          "lanes" (1..8, default 2: concurrent sub-batch chains per forward, never fewer than 16 crops each),
@@ -599,6 +603,12 @@ WHENET_API int whenet_dw_plan(int dtype, int index, int32_t out[12]);
 /* the fused expand+depthwise tile plan of block `index` (2..16) for `dtype` (pure host logic):
  * out = {threads, CC, TH, NSX, tiles_x, tiles_y, chunks, EH, EW, lds_bytes, w_off, Cexp} */
 WHENET_API int whenet_front_plan(int dtype, int index, int32_t out[12]);
+
+/* front2.hip's static-plan check (pure host logic): the constexpr plan of row `row` of the kernel's plan table against the
+ * plan the engine launches for that layer, field by field, with the static plan's field number `field` moved by `delta`
+ * (field = -1: nothing moved).  WHENET_OK when they agree; WHENET_EINVAL when they differ (a launch would refuse to run),
+ * the row has no static form or there is no such field. */
+WHENET_API int whenet_front2_static_check(int row, int field, int delta);
 
 /* raw device-memory helpers so a host without torch can use the device-pointer form */
 WHENET_API int whenet_device_alloc(whenet_t* h, size_t nbytes, void** d_ptr);

@@ -4,6 +4,9 @@
 //   2. timed at 256 / 64 / 16 crops per launch next to round 2's whenet_front_kernel with its tuned plan.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probes/front2_probe.hip -o tools/probes/front2_probe
 // env: ONLY=b5 (one shape), TUNE=1 (time every candidate plan, print the table for front2_tuned.inc), NOCHECK=1
+// Where the default plan has a static form (whenet_front2_static_kernel: front2_static_row() >= 0 -- every use = 1 row but block 2,
+// whose static form is the gated kernel of the folded block-1 project, which this probe does not feed) the check, the stamp
+// timeline (-DWHENET_STAMPS) and the timings are taken for both forms.
 #include "../../headposeestimation-whenet_amd/csrc/front.hip"
 #include "../../headposeestimation-whenet_amd/csrc/front2.hip"
 
@@ -226,11 +229,23 @@ int main() {
                 launch_front2(a2, st);
                 CK(hipStreamSynchronize(st));
                 total_bad += check(def, threads == 256 ? "default plan, 256 lanes" : "default plan, 512 lanes");
+                a2.static_form = true;
+                if (front2_static_row(a2) >= 0) {
+                    CK(hipMemset(d_out, 0xff, size_t(NCHK) * Ho * Ho * Cexp * sizeof(half_t)));
+                    CK(hipMemset(d_rp, 0xff, rp_floats * sizeof(float)));
+                    launch_front2(a2, st);
+                    CK(hipStreamSynchronize(st));
+                    total_bad += check(def, "default plan, static form");
+                }
+                a2.static_form = false;
             }
         }
 #ifdef WHENET_STAMPS
         {   // phase timeline of the default plan at 256 and 16 crops per launch: per-workgroup stamps (wave 0), averaged
+            for (int form = 0; form < 2; ++form)
             for (int n : {256, 16}) {
+                a2.n = n; a2.plan = def; a2.plan.threads = 256; a2.static_form = form != 0;
+                if (form && front2_static_row(a2) < 0) continue;
                 const size_t nwg = size_t(n) * def.ntiles() * def.chunks;
                 long long* d_st; CK(hipMalloc(&d_st, nwg * 8 * sizeof(long long)));
                 CK(hipMemset(d_st, 0, nwg * 8 * sizeof(long long)));
@@ -252,18 +267,25 @@ int main() {
                     t0 = std::min(t0, hs[w * 8]);
                     t1 = std::max(t1, hs[w * 8 + 6]);
                 }
-                printf("  timeline n=%d (%zu workgroups, kernel span %.1f us): workgroup life %.2f us = prologue %.2f | expand %.2f | "
-                       "barrier+fixup %.2f | taps+epilogue %.2f | barrier %.2f | tail %.2f\n", n, nwg, double(t1 - t0) * 0.01,
+                printf("  timeline %s n=%d (%zu workgroups, kernel span %.1f us): workgroup life %.2f us = prologue %.2f | expand %.2f | "
+                       "barrier+fixup %.2f | taps+epilogue %.2f | barrier %.2f | tail %.2f\n", form ? "static " : "generic", n, nwg, double(t1 - t0) * 0.01,
                        life / nwg * 0.01, ph[0] / nwg * 0.01, ph[1] / nwg * 0.01, ph[2] / nwg * 0.01, ph[3] / nwg * 0.01,
                        ph[4] / nwg * 0.01, ph[5] / nwg * 0.01);
                 CK(hipFree(d_st));
             }
+            a2.static_form = false;
         }
 #endif
         const float o256 = time1(256), o64 = time1(64), o16 = time1(16);
         const float n256 = time2(def, 256, 0), n64 = time2(def, 64, 0), n16 = time2(def, 16, 0);
         printf("  round-2 kernel : n=256 %7.2f us  n=64 %7.2f us  n=16 %6.2f us\n", o256, o64, o16);
         printf("  front2 default : n=256 %7.2f us  n=64 %7.2f us  n=16 %6.2f us   (x%.2f at 64)\n", n256, n64, n16, o64 / n64);
+        a2.n = 64; a2.plan = def; a2.plan.threads = front2_threads(def, 64); a2.static_form = true;
+        if (front2_static_row(a2) >= 0) {
+            const float s256 = time2(def, 256, 0), s64 = time2(def, 64, 0), s16 = time2(def, 16, 0);
+            printf("  front2 static  : n=256 %7.2f us  n=64 %7.2f us  n=16 %6.2f us   (x%.2f of the generic form at 64)\n", s256, s64, s16, n64 / s64);
+        }
+        a2.static_form = false;
         sum_old += o64 * (std::string(sh.name) == "b7" ? 2 : (std::string(sh.name) == "b10" ? 2 : (std::string(sh.name) == "b13" ? 3 : 1)));
         sum_new += n64 * (std::string(sh.name) == "b7" ? 2 : (std::string(sh.name) == "b10" ? 2 : (std::string(sh.name) == "b13" ? 3 : 1)));
         fflush(stdout);
