@@ -6,7 +6,9 @@
 // clipping) and OpenCV's INTER_LINEAR coefficient tables (modules/imgproc/src/resize.cpp), exactly as frame.hip's host code
 // restates them.  The results are bit for bit the host's:
 //   * every float32 / float64 operation is rounded on its own -- contraction is switched off in this file's arithmetic (the
-//     host build has no FMA; `float((d + 0.5) * scale - 0.5)` as one FMA rounds differently for some source sizes);
+//     host build has no FMA; `float((d + 0.5) * scale - 0.5)` as one FMA rounds differently for one (source size, entry) pair of
+//     sizes 1..4096: size 32, entry 3 is 0.0 unfused and -2.8e-17 fused, which on the vertical axis turns (yofs, b0, b1) =
+//     (0, 2048, 0) into (-1, 0, 2048) -- tests/test_frame_async_gpu.py checks every size 1..2048 and names that entry);
 //   * float -> short is round half to even (lrintf on the host, rintf here);
 //   * int(float) of a value no int can hold is INT_MIN, as the host's conversion instruction returns it.
 //

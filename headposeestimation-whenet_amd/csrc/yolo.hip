@@ -19,7 +19,9 @@
 //      IOU(): min/max-normalised corners, zero for a box of non-positive area, suppressed when IoU > threshold,
 //      float32 with individually rounded operations), one ballot decides, selected boxes live in LDS.
 // All arithmetic is float32 with the operation order of the reference's graph; exp / sigmoid go through expf,
-// so box coordinates agree with a float32 CPU run to an ulp or two, not bitwise (tests/test_yolo.py).
+// so box coordinates agree with a float32 CPU run to an ulp or two, not bitwise (tests/test_yolo.py).  On the logits where
+// expf is exact (0 and +-128: sigmoid 0.5 / 1 / 0, exp 1 / inf / 0) boxes and scores ARE bitwise the float32 CPU run's, and the
+// selection is the CPU NMS of the device's own decoded rows at every sort size (tests/test_yolo_exact_gpu.py).
 #include <cmath>
 
 #include "kernels.h"
@@ -27,6 +29,16 @@
 namespace whenet {
 
 namespace {
+
+// One float32 operation, rounded on its own.  HIP's __fadd_rn / __fsub_rn / __fmul_rn are the plain operators, and hipcc contracts a
+// plain a * b + c into one FMA: `cy - hy` below was fma(by - off_y, scale_y, -hy), an ulp off the graph's two roundings wherever the
+// letterbox scale is not 1 (tests/test_yolo_exact_gpu.py).  Contraction is off for everything in this file from here on (as in
+// headplan.hip), and every operation goes through these.
+#pragma clang fp contract(off)
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
 
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -41,24 +53,24 @@ __device__ __forceinline__ void yolo_decode_box(const YoloArgs& a, const MixedFr
     const float* t = L.feats + (img * L.gh * L.gw * a.na + size_t(j)) * (5 + a.num_classes);
 
     // yolo_head (model.py:141-145)
-    const float bx = __fdiv_rn(__fadd_rn(sigmoid_ref(t[0]), float(x)), float(L.gw));
-    const float by = __fdiv_rn(__fadd_rn(sigmoid_ref(t[1]), float(y)), float(L.gh));
-    const float bw = __fdiv_rn(__fmul_rn(expf(t[2]), L.anchor[an][0]), a.input_w);
-    const float bh = __fdiv_rn(__fmul_rn(expf(t[3]), L.anchor[an][1]), a.input_h);
+    const float bx = div_rn(add_rn(sigmoid_ref(t[0]), float(x)), float(L.gw));
+    const float by = div_rn(add_rn(sigmoid_ref(t[1]), float(y)), float(L.gh));
+    const float bw = div_rn(mul_rn(expf(t[2]), L.anchor[an][0]), a.input_w);
+    const float bh = div_rn(mul_rn(expf(t[3]), L.anchor[an][1]), a.input_h);
     const float conf = sigmoid_ref(t[4]);
     // yolo_correct_boxes (model.py:155-177): y first
-    const float cy = __fmul_rn(__fsub_rn(by, c.off_y), c.scale_y), cx = __fmul_rn(__fsub_rn(bx, c.off_x), c.scale_x);
-    const float hh = __fmul_rn(bh, c.scale_y), ww = __fmul_rn(bw, c.scale_x);
-    const float hy = __fdiv_rn(hh, 2.0f), hx = __fdiv_rn(ww, 2.0f);
+    const float cy = mul_rn(sub_rn(by, c.off_y), c.scale_y), cx = mul_rn(sub_rn(bx, c.off_x), c.scale_x);
+    const float hh = mul_rn(bh, c.scale_y), ww = mul_rn(bw, c.scale_x);
+    const float hy = div_rn(hh, 2.0f), hx = div_rn(ww, 2.0f);
     float4 box;
-    box.x = __fmul_rn(__fsub_rn(cy, hy), c.image_h);
-    box.y = __fmul_rn(__fsub_rn(cx, hx), c.image_w);
-    box.z = __fmul_rn(__fadd_rn(cy, hy), c.image_h);
-    box.w = __fmul_rn(__fadd_rn(cx, hx), c.image_w);
+    box.x = mul_rn(sub_rn(cy, hy), c.image_h);
+    box.y = mul_rn(sub_rn(cx, hx), c.image_w);
+    box.z = mul_rn(add_rn(cy, hy), c.image_h);
+    box.w = mul_rn(add_rn(cx, hx), c.image_w);
     reinterpret_cast<float4*>(a.boxes)[img * a.N + i] = box;
     // yolo_boxes_and_scores (model.py:188) + the mask of yolo_eval (model.py:212)
     for (int cl = 0; cl < a.num_classes; ++cl) {
-        const float score = __fmul_rn(conf, sigmoid_ref(t[5 + cl]));
+        const float score = mul_rn(conf, sigmoid_ref(t[5 + cl]));
         if (a.all_scores) a.all_scores[(img * a.N + i) * a.num_classes + cl] = score;
         if (score >= a.score_thr) {
             const size_t ic = img * a.num_classes + cl;
@@ -87,13 +99,13 @@ __global__ __launch_bounds__(256) void whenet_yolo_decode_mixed_kernel(YoloArgs 
 __device__ __forceinline__ float iou_tf(const float4 a, const float4 b) {
     const float ymin_a = fminf(a.x, a.z), xmin_a = fminf(a.y, a.w), ymax_a = fmaxf(a.x, a.z), xmax_a = fmaxf(a.y, a.w);
     const float ymin_b = fminf(b.x, b.z), xmin_b = fminf(b.y, b.w), ymax_b = fmaxf(b.x, b.z), xmax_b = fmaxf(b.y, b.w);
-    const float area_a = __fmul_rn(__fsub_rn(ymax_a, ymin_a), __fsub_rn(xmax_a, xmin_a));
-    const float area_b = __fmul_rn(__fsub_rn(ymax_b, ymin_b), __fsub_rn(xmax_b, xmin_b));
+    const float area_a = mul_rn(sub_rn(ymax_a, ymin_a), sub_rn(xmax_a, xmin_a));
+    const float area_b = mul_rn(sub_rn(ymax_b, ymin_b), sub_rn(xmax_b, xmin_b));
     if (area_a <= 0.0f || area_b <= 0.0f) return 0.0f;
     const float iymin = fmaxf(ymin_a, ymin_b), ixmin = fmaxf(xmin_a, xmin_b);
     const float iymax = fminf(ymax_a, ymax_b), ixmax = fminf(xmax_a, xmax_b);
-    const float inter = __fmul_rn(fmaxf(__fsub_rn(iymax, iymin), 0.0f), fmaxf(__fsub_rn(ixmax, ixmin), 0.0f));
-    return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
+    const float inter = mul_rn(fmaxf(sub_rn(iymax, iymin), 0.0f), fmaxf(sub_rn(ixmax, ixmin), 0.0f));
+    return div_rn(inter, sub_rn(add_rn(area_a, area_b), inter));
 }
 
 constexpr int NMS_THREADS = 1024;

@@ -105,9 +105,11 @@ SIDES = (1, 2, 3, 7, 111, 112, 223, 224, 225, 447, 448, 449, 1079, 1919)
 
 def boxes_for_window_sides(limit, axis, sides):
     """For each side s <= limit a box interval (lo, hi) whose window along `axis` (0: rows, margin 1/10; 1: columns, 1/5) is
-    exactly s pixels long on a frame of `limit` pixels, found with the host's own arithmetic (whenet_frame_rects)."""
-    lo = np.repeat(np.array([0.0, 3.25, 40.5], np.float32), 8000)
-    hi = lo + np.tile(np.arange(1, 8001, dtype=np.float32) * np.float32(0.25), 3)
+    exactly s pixels long on a frame of `limit` pixels, found with the host's own arithmetic (whenet_frame_rects).  The candidate
+    lengths go in quarter pixels up to the frame's own (at least 2000 pixels), so every side up to `limit` is found."""
+    steps = max(8000, 4 * limit)
+    lo = np.repeat(np.array([0.0, 3.25, 40.5], np.float32), steps)
+    hi = lo + np.tile(np.arange(1, steps + 1, dtype=np.float32) * np.float32(0.25), 3)
     b = np.zeros((len(lo), 4), np.float32)
     b[:, axis], b[:, axis + 2] = lo, hi
     b[:, 1 - axis], b[:, 3 - axis] = 10.0, 20.0
@@ -138,6 +140,28 @@ def test_plans_equal_the_host_crop_plan_bitwise(post):
     # a window that fails check_rects: zeros in the place of its plan
     rects, valid, plans = post.op_head_plan(fh, fw, np.array([[2000, 10, 2100, 50], [10, 10, 50, 50]], np.float32))
     assert valid.tolist() == [0, 1] and not plans[0].any() and plans[1].tobytes() == _lib.crop_plan(rects[1]).tobytes()
+
+
+def test_plans_equal_the_host_crop_plan_for_every_source_size(post):
+    """Every source size 1..2048 on both axes in one launch of 2048 boxes (op_head_plan's limit): box i has a window of 2049 - s rows
+    by s columns, the pairing of tests/test_head_plan_cpu.py, which holds the host's tables to the oracle for the same sizes."""
+    fh = fw = 2304
+    sizes = list(range(1, 2049))
+    ys, xs = boxes_for_window_sides(fh, 0, sizes), boxes_for_window_sides(fw, 1, sizes)
+    assert sorted(ys) == sizes and sorted(xs) == sizes                          # the search found every size on both axes
+    boxes = np.array([[ys[2049 - s][0], xs[s][0], ys[2049 - s][1], xs[s][1]] for s in sizes], np.float32)
+    rects, valid, plans = post.op_head_plan(fh, fw, boxes)                       # one launch
+    assert rects.tobytes() == _lib.frame_rects(fh, fw, boxes).tobytes() and valid.all()
+    assert [(int(r[2] - r[0]), int(r[3] - r[1])) for r in rects] == [(2049 - s, s) for s in sizes]
+    bad = [(int(r[2] - r[0]), int(r[3] - r[1])) for r, p in zip(rects, plans) if p.tobytes() != _lib.crop_plan(r).tobytes()]
+    assert not bad, bad[:8]
+    # The FMA-sensitive entry: source size 32, d = 3.  float((3 + 0.5) * (32 / 224) - 0.5) is 0.0 with every operation rounded on its
+    # own and -2.8e-17 as one fused multiply-add, the only (size, d) pair of 1..4096 x 0..223 where the two differ.  Vertically that
+    # flips (yofs, b0, b1) from (0, 2048, 0) to (-1, 0, 2048); horizontally the s < 0 clamp hides it.
+    tall = plans[sizes.index(2049 - 32)]
+    assert tall[2] == 32
+    yofs, b0, b1 = tall[8:].reshape(6, 224)[3:]
+    assert (int(yofs[3]), int(b0[3]), int(b1[3])) == (0, 2048, 0)
 
 
 # ---- 3. fused = two-step, bitwise ------------------------------------------------------------------------------------------------
