@@ -149,6 +149,18 @@ int guarded(whenet_t* h, F&& fn) {
     }
 }
 
+// one begin call on the engine whose turn it is; a refused call (the engine throws before it takes a slot) does not shift the round-robin
+template <typename F>
+int begin_on_next_engine(whenet_t* h, int* ticket, F&& begin) {
+    if (ticket == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine&) {
+        const size_t idx = h->next % size_t(h->inflight);
+        const int t = begin(h->at(idx));
+        h->next = (h->next + 1) % size_t(h->inflight);
+        *ticket = t * MAX_INFLIGHT_ENGINES + int(idx);
+    });
+}
+
 int create_impl(const void* blob, size_t nbytes, int device_id, int dtype, whenet_t** out) {
     if (out == nullptr) return WHENET_EINVAL;
     *out = nullptr;
@@ -791,6 +803,47 @@ int whenet_clip_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frames, int num
         h->next = (h->next + 1) % size_t(h->inflight);
         *ticket = t * MAX_INFLIGHT_ENGINES + int(idx);
     });
+}
+
+// ---- ingest from device memory (ingest.hip, yuv.hip, engine_post.cpp) ----
+int whenet_frame_begin_device(whenet_t* h, const uint8_t* d_frame, int pitch, int frame_h, int frame_w, int channel_order, void* stream,
+                              int* ticket) {
+    if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return WHENET_EINVAL;
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        return e.frame_begin_device(d_frame, pitch, frame_h, frame_w, channel_order == WHENET_BGR, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_clip_begin_device(whenet_t* h, const uint8_t* const* d_frames, const int* pitch, int num_frames, const int* frame_h,
+                             const int* frame_w, int channel_order, void* stream, int* ticket) {
+    if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return WHENET_EINVAL;
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        return e.clip_begin_device(d_frames, pitch, num_frames, frame_h, frame_w, channel_order == WHENET_BGR, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_frame_begin_yuv_device(whenet_t* h, const whenet_yuv_frame_t* frame, void* stream, int* ticket) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        whenet::check_yuv_frames("frame_begin_yuv_device", frame, 1);      // (NULL)
+        return e.frame_begin_yuv_device(*frame, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_clip_begin_yuv_device(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, void* stream, int* ticket) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        return e.clip_begin_yuv_device(frames, num_frames, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_op_pack_device(whenet_t* h, const uint8_t* const* d_frames, const int* pitch, int num_frames, const int* frame_h,
+                          const int* frame_w, void* stream, uint8_t* const* out) {
+    return guarded(h, [&](whenet::Engine& e) {
+        e.op_pack_device(d_frames, pitch, num_frames, frame_h, frame_w, static_cast<hipStream_t>(stream), out);
+    });
+}
+
+int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, void* stream, uint8_t* const* bgr) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_yuv_to_bgr_device(frames, num_frames, static_cast<hipStream_t>(stream), bgr); });
 }
 
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,

@@ -296,6 +296,31 @@ class Engine {
     int frame_begin_yuv(const whenet_yuv_frame_t& frame);
     int clip_begin_yuv(const whenet_yuv_frame_t* frames, int nframes);
     void op_yuv_to_bgr(const whenet_yuv_frame_t* frames, int nframes, uint8_t* const* bgr);
+    // INGEST FROM DEVICE MEMORY (ingest.hip, yuv.hip): the twins of frame_begin / clip_begin / clip_begin_mixed / frame_begin_yuv /
+    // clip_begin_yuv for a source that is already in this device's memory -- packed 3-byte pixels with a row pitch, or NV12 / I420
+    // planes with their pitches.  One kernel writes the slot's tight frame buffer; the slot ends up exactly as the host-pointer
+    // twin leaves it and every later call runs unchanged.  No pinned staging is grown or touched.
+    //   ORDER.  `stream` is the caller's hipStream_t (nullptr: the default stream).  An event is recorded on it, the copy stream
+    //   waits for that event, the kernel runs, slot.copied is recorded, and the caller's stream is made to wait for slot.copied.  So:
+    //   work the caller enqueued on `stream` BEFORE the call is seen by the ingest; work it enqueues on `stream` AFTER the call may
+    //   overwrite or free the source; anything else that writes the source -- the host, another stream -- must wait until the
+    //   ticket's collect has returned.  The host never waits here.
+    //   CHECKS, all before a slot is taken or anything is enqueued, WHENET_EINVAL with the frame's index in the text: NULL pointers,
+    //   a pitch below the row bytes, sides outside 1..8192, a frame count outside 1..16, unknown format or matrix; every plane must
+    //   be hipMemoryTypeDevice memory of THIS engine's device (hipPointerGetAttributes: host, managed and other-device pointers
+    //   are refused) and its extent (rows - 1) * pitch + row_bytes must lie inside the allocation hipMemGetAddressRange reports
+    //   for it.  If the runtime cannot report the range, the extent check alone is skipped.
+    // clip_begin_device: frames of one size make a clip_begin slot, otherwise a clip_begin_mixed slot (letterbox_cache limit).
+    // op_pack_device / op_yuv_to_bgr_device: the kernels alone, device to host (out[f] = uint8 [h_f][w_f][3]), packed back to back
+    // on the device as a mixed clip packs them; the host waits.
+    int frame_begin_device(const uint8_t* d_frame, int pitch, int fh, int fw, int swap_rb, hipStream_t stream);
+    int clip_begin_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, int swap_rb,
+                          hipStream_t stream);
+    int frame_begin_yuv_device(const whenet_yuv_frame_t& frame, hipStream_t stream);
+    int clip_begin_yuv_device(const whenet_yuv_frame_t* frames, int nframes, hipStream_t stream);
+    void op_pack_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, hipStream_t stream,
+                        uint8_t* const* out);
+    void op_yuv_to_bgr_device(const whenet_yuv_frame_t* frames, int nframes, hipStream_t stream, uint8_t* const* bgr);
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -315,6 +340,7 @@ class Engine {
         bool busy = false;
         StagedBuffer in, ypr, amax, logits;
         Event copied, done;
+        Event source;                    // device ingest: recorded on the CALLER's stream, the copy stream waits for it (created on first use)
         StagedBuffer frame, plan;        // frame submissions: the frame and the crop plans travel instead of the crops
         DeviceBuffer yuv;                // YUV ingest: the planes on the device (frame.h stages them, frame.d gets the converted frame)
         int frame_ticket = -1;           // resident frame: the ticket whose frame is held here and still waits for its heads
@@ -435,6 +461,13 @@ class Engine {
     // f's output starts off[f] bytes into d_bgr.  The three buffers are large enough (yuv_layout).
     void enqueue_yuv_ingest(const whenet_yuv_frame_t* frames, int nframes, uint8_t* h_stage, uint8_t* d_planes, uint8_t* d_bgr,
                             const size_t* off, hipStream_t s);
+    // device ingest: the argument checks of the packed and the plane form (engine.h ORDER / CHECKS), the launches on the copy
+    // stream between the two event hand-overs, and the kernels alone
+    void check_device_plane(const std::string& who, const uint8_t* p, int rows, int pitch, int row_bytes) const;
+    void check_device_frames(const char* what, const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw) const;
+    void check_device_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes) const;
+    void ingest_after_caller(Slot& slot, hipStream_t caller);      // caller's stream -> slot.source -> copy stream
+    void ingest_done(Slot& slot, hipStream_t caller);              // copy stream -> slot.copied -> caller's stream
     void letterbox_results_to_host(size_t nout, uint8_t* d_u8, float* d_f32, uint8_t* canvas_u8, float* image_f32);
     // every frame's plan_layout, F <= letterbox_cache: what a mixed clip needs before anything is enqueued
     void check_mixed_geometry(const char* what, int frames, const int* fh, const int* fw, int out_h, int out_w) const;

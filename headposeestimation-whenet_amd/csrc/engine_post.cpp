@@ -440,6 +440,235 @@ int Engine::clip_begin_yuv(const whenet_yuv_frame_t* frames, int nframes) {
     return slot.frame_ticket;
 }
 
+// ---- ingest from device memory (ingest.hip, yuv.hip; the contract is in engine.h) ----
+void Engine::check_device_plane(const std::string& who, const uint8_t* p, int rows, int pitch, int row_bytes) const {
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) (void)hipGetLastError();      // (a pointer the runtime does not know: not an error of ours to keep)
+    WHENET_REQUIRE(e == hipSuccess && attr.type == hipMemoryTypeDevice && !attr.isManaged, WHENET_EINVAL,
+                   who + " is not device memory (hipMalloc'ed memory of device " + std::to_string(device_) +
+                       " is needed; host, registered and managed memory go through the host-pointer entry points)");
+    WHENET_REQUIRE(attr.device == device_, WHENET_EINVAL,
+                   who + " lies on device " + std::to_string(attr.device) + ", the handle runs on device " + std::to_string(device_));
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<uint8_t*>(p)) != hipSuccess) {
+        (void)hipGetLastError();                       // the runtime cannot report the range: the extent goes unchecked
+        return;
+    }
+    const size_t extent = size_t(rows - 1) * size_t(pitch) + size_t(row_bytes);
+    const size_t at = size_t(p - static_cast<const uint8_t*>(base));
+    WHENET_REQUIRE(p >= static_cast<const uint8_t*>(base) && at <= size && extent <= size - at, WHENET_EINVAL,
+                   who + " needs " + std::to_string(extent) + " bytes (" + std::to_string(rows) + " rows of " + std::to_string(row_bytes) +
+                       " at pitch " + std::to_string(pitch) + "), its allocation has " + std::to_string(at <= size ? size - at : 0) +
+                       " from there on");
+}
+
+void Engine::check_device_frames(const char* what, const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh,
+                                 const int* fw) const {
+    const std::string w = what;
+    WHENET_REQUIRE(d_frames != nullptr && pitch != nullptr, WHENET_EINVAL, w + ": NULL argument");
+    check_mixed_frames(what, d_frames, nframes, fh, fw);
+    for (int f = 0; f < nframes; ++f) {
+        const std::string who = w + ": frame " + std::to_string(f);
+        WHENET_REQUIRE(pitch[f] >= 3 * fw[f], WHENET_EINVAL,
+                       who + ": pitch " + std::to_string(pitch[f]) + " is below its row of " + std::to_string(3 * fw[f]) + " bytes");
+        check_device_plane(who, d_frames[f], fh[f], pitch[f], 3 * fw[f]);
+    }
+}
+
+void Engine::check_device_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes) const {
+    check_yuv_frames(what, frames, nframes);
+    for (int i = 0; i < nframes; ++i) {
+        const whenet_yuv_frame_t& f = frames[i];
+        const int cw = (f.w + 1) >> 1, ch = (f.h + 1) >> 1;
+        const bool nv12 = f.format == WHENET_YUV_NV12;
+        const int rows[3] = {f.h, ch, ch}, row_bytes[3] = {f.w, nv12 ? 2 * cw : cw, cw};
+        for (int p = 0; p < (nv12 ? 2 : 3); ++p)
+            check_device_plane(std::string(what) + ": frame " + std::to_string(i) + ": plane " + std::to_string(p), f.plane[p], rows[p],
+                               f.pitch[p], row_bytes[p]);
+    }
+}
+
+void Engine::ingest_after_caller(Slot& slot, hipStream_t caller) {
+    if (!slot.source) slot.source.create();
+    WHENET_HIP_CHECK(hipEventRecord(slot.source, caller));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(copy_stream(), slot.source, 0));
+}
+
+void Engine::ingest_done(Slot& slot, hipStream_t caller) {
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(caller, slot.copied, 0));
+}
+
+namespace {
+PackFrames pack_frames(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, const size_t* off) {
+    PackFrames clip{};
+    clip.frames = nframes;
+    for (int f = 0; f < nframes; ++f) {
+        clip.f[f].src = d_frames[f], clip.f[f].dst_off = off[f];
+        clip.f[f].pitch = pitch[f], clip.f[f].h = fh[f], clip.f[f].row_bytes = 3 * fw[f];
+    }
+    return clip;
+}
+YuvPlanes yuv_planes(const whenet_yuv_frame_t* frames, int nframes, const size_t* off) {
+    YuvPlanes clip{};
+    clip.frames = nframes;
+    for (int f = 0; f < nframes; ++f) {
+        YuvPlanesFrame& g = clip.f[f];
+        const bool nv12 = frames[f].format == WHENET_YUV_NV12;
+        for (int p = 0; p < (nv12 ? 2 : 3); ++p) g.plane[p] = frames[f].plane[p], g.pitch[p] = frames[f].pitch[p];
+        g.h = frames[f].h, g.w = frames[f].w, g.format = frames[f].format;
+        g.k = yuv_coeffs(frames[f].matrix);
+        g.dst_off = off[f];
+    }
+    return clip;
+}
+// The landing buffer of the two kernel-alone calls: the frames back to back at off[], between two guard zones, every byte set to
+// a sentinel before the launch.  to_host waits for the stream, refuses (WHENET_EHIP) if a guard byte has changed -- a kernel wrote
+// outside its frames -- and hands every frame to the caller's host array; a byte no thread wrote arrives as the sentinel.
+struct GuardedOutput {
+    static constexpr size_t GUARD = 64;       // (a multiple of 16: the frames keep the alignments they have in a slot's buffer)
+    static constexpr int SENTINEL = 0xA5;
+    DeviceBuffer buf;
+    size_t bytes;
+    GuardedOutput(size_t payload, hipStream_t s) : bytes(payload) {
+        buf.reset(payload + 2 * GUARD, "hipMalloc");
+        WHENET_HIP_CHECK(hipMemsetAsync(buf.as<void>(), SENTINEL, payload + 2 * GUARD, s));
+    }
+    uint8_t* frames() const { return buf.as<uint8_t>() + GUARD; }
+    void to_host(hipStream_t s, const size_t* off, int nframes, uint8_t* const* out, const char* what) const {
+        WHENET_HIP_CHECK(hipStreamSynchronize(s));
+        uint8_t guards[2 * GUARD];
+        WHENET_HIP_CHECK(hipMemcpy(guards, buf.as<uint8_t>(), GUARD, hipMemcpyDeviceToHost));
+        WHENET_HIP_CHECK(hipMemcpy(guards + GUARD, frames() + bytes, GUARD, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < 2 * GUARD; ++i)
+            WHENET_REQUIRE(guards[i] == SENTINEL, WHENET_EHIP, std::string(what) + ": the kernel wrote outside its frames (guard byte " +
+                                                                   std::to_string(i) + ")");
+        for (int f = 0; f < nframes; ++f) WHENET_HIP_CHECK(hipMemcpy(out[f], frames() + off[f], off[f + 1] - off[f], hipMemcpyDeviceToHost));
+    }
+};
+}  // namespace
+
+void Engine::op_pack_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, hipStream_t stream,
+                            uint8_t* const* out) {
+    DeviceGuard guard(device_);
+    check_device_frames("op_pack_device", d_frames, pitch, nframes, fh, fw);
+    WHENET_REQUIRE(out != nullptr, WHENET_EINVAL, "op_pack_device: NULL argument");
+    for (int f = 0; f < nframes; ++f) WHENET_REQUIRE(out[f] != nullptr, WHENET_EINVAL, "op_pack_device: output " + std::to_string(f) + " is NULL");
+    size_t off[MIXED_MAX_FRAMES + 1] = {};
+    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(fh[f]) * fw[f] * 3;
+    const GuardedOutput d_out(off[nframes], stream_);
+    Event after;
+    after.create();
+    WHENET_HIP_CHECK(hipEventRecord(after, stream));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, after, 0));
+    launch_frame_pack(d_out.frames(), pack_frames(d_frames, pitch, nframes, fh, fw, off), stream_);
+    d_out.to_host(stream_, off, nframes, out, "op_pack_device");
+}
+
+void Engine::op_yuv_to_bgr_device(const whenet_yuv_frame_t* frames, int nframes, hipStream_t stream, uint8_t* const* bgr) {
+    DeviceGuard guard(device_);
+    check_device_yuv_frames("op_yuv_to_bgr_device", frames, nframes);
+    WHENET_REQUIRE(bgr != nullptr, WHENET_EINVAL, "op_yuv_to_bgr_device: NULL argument");
+    for (int f = 0; f < nframes; ++f)
+        WHENET_REQUIRE(bgr[f] != nullptr, WHENET_EINVAL, "op_yuv_to_bgr_device: output " + std::to_string(f) + " is NULL");
+    const YuvLayout lay(frames, nframes);
+    const GuardedOutput d_bgr(lay.dst[nframes], stream_);
+    Event after;
+    after.create();
+    WHENET_HIP_CHECK(hipEventRecord(after, stream));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, after, 0));
+    launch_yuv_planes_to_bgr(d_bgr.frames(), yuv_planes(frames, nframes, lay.dst), stream_);
+    d_bgr.to_host(stream_, lay.dst, nframes, bgr, "op_yuv_to_bgr_device");
+}
+
+// frame_begin from device memory: the slot ends up exactly as frame_begin leaves it
+int Engine::frame_begin_device(const uint8_t* d_frame, int pitch, int fh, int fw, int swap_rb, hipStream_t stream) {
+    DeviceGuard guard(device_);
+    check_device_frames("frame_begin_device", &d_frame, &pitch, 1, &fh, &fw);      // (before a slot is taken)
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const size_t off[2] = {0, size_t(fh) * fw * 3};
+    slot.frame.d.grow(off[1]);
+    ingest_after_caller(slot, stream);
+    launch_frame_pack(slot.frame.d.as<uint8_t>(), pack_frames(&d_frame, &pitch, 1, &fh, &fw, off), copy_stream());
+    ingest_done(slot, stream);
+    slot.fh = fh, slot.fw = fw, slot.swap_rb = swap_rb;
+    slot.frame_ticket = finish_submission(slot, 0);
+    return slot.frame_ticket;
+}
+
+int Engine::clip_begin_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, int swap_rb,
+                              hipStream_t stream) {
+    DeviceGuard guard(device_);
+    check_device_frames("clip_begin_device", d_frames, pitch, nframes, fh, fw);      // (before a slot is taken)
+    bool one_size = true;
+    for (int f = 1; f < nframes; ++f) one_size = one_size && fh[f] == fh[0] && fw[f] == fw[0];
+    WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
+                   "clip_begin_device: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    size_t off[MIXED_MAX_FRAMES + 1] = {};
+    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(fh[f]) * fw[f] * 3;
+    slot.frame.d.grow(off[nframes]);
+    ingest_after_caller(slot, stream);
+    launch_frame_pack(slot.frame.d.as<uint8_t>(), pack_frames(d_frames, pitch, nframes, fh, fw, off), copy_stream());
+    ingest_done(slot, stream);
+    slot.fh = fh[0], slot.fw = fw[0], slot.swap_rb = swap_rb;
+    if (!one_size) {
+        for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = fh[f], slot.clip_fw[f] = fw[f];
+        std::copy(off, off + nframes + 1, slot.clip_off);
+    }
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = nframes;
+    slot.clip_mixed = !one_size;
+    return slot.frame_ticket;
+}
+
+// frame_begin_yuv from planes in device memory: the slot ends up exactly as frame_begin_yuv leaves it
+int Engine::frame_begin_yuv_device(const whenet_yuv_frame_t& frame, hipStream_t stream) {
+    DeviceGuard guard(device_);
+    check_device_yuv_frames("frame_begin_yuv_device", &frame, 1);      // (before a slot is taken)
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const YuvLayout lay(&frame, 1);
+    slot.frame.d.grow(lay.dst[1]);
+    ingest_after_caller(slot, stream);
+    launch_yuv_planes_to_bgr(slot.frame.d.as<uint8_t>(), yuv_planes(&frame, 1, lay.dst), copy_stream());
+    ingest_done(slot, stream);
+    slot.fh = frame.h, slot.fw = frame.w, slot.swap_rb = 1;
+    slot.frame_ticket = finish_submission(slot, 0);
+    return slot.frame_ticket;
+}
+
+int Engine::clip_begin_yuv_device(const whenet_yuv_frame_t* frames, int nframes, hipStream_t stream) {
+    DeviceGuard guard(device_);
+    check_device_yuv_frames("clip_begin_yuv_device", frames, nframes);      // (before a slot is taken)
+    bool one_size = true;
+    for (int f = 1; f < nframes; ++f) one_size = one_size && frames[f].h == frames[0].h && frames[f].w == frames[0].w;
+    WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
+                   "clip_begin_yuv_device: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const YuvLayout lay(frames, nframes);
+    slot.frame.d.grow(lay.dst[nframes]);
+    ingest_after_caller(slot, stream);
+    launch_yuv_planes_to_bgr(slot.frame.d.as<uint8_t>(), yuv_planes(frames, nframes, lay.dst), copy_stream());
+    ingest_done(slot, stream);
+    slot.fh = frames[0].h, slot.fw = frames[0].w, slot.swap_rb = 1;
+    if (!one_size) {
+        for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = frames[f].h, slot.clip_fw[f] = frames[f].w;
+        std::copy(lay.dst, lay.dst + nframes + 1, slot.clip_off);
+    }
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = nframes;
+    slot.clip_mixed = !one_size;
+    return slot.frame_ticket;
+}
+
 Engine::Slot& Engine::resident_slot(int ticket, const char* what, int holds) {
     for (Slot& s : slots_)
         if (s.busy && s.ticket == ticket) {

@@ -547,6 +547,38 @@ void launch_yuv_to_bgr(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g
 void launch_yuv_to_bgr_batch(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g, int frames, size_t src_stride, size_t dst_stride,
                              hipStream_t stream);
 void launch_yuv_to_bgr_mixed(const uint8_t* d_planes, uint8_t* d_bgr, YuvMixed clip, hipStream_t stream);
+// The same conversion of planes that are ALREADY in device memory, where a decoder or a tensor left them: every plane has its own
+// address (any alignment) and byte pitch.  At most 16 records by value in the argument block; frame f's output starts dst_off
+// bytes into d_bgr.  plane[2] / pitch[2] are unused for NV12.
+struct YuvPlanesFrame {
+    const uint8_t* plane[3];
+    int pitch[3];
+    int h, w, format;
+    YuvCoeffs k;
+    unsigned long long dst_off;
+    int block0;                                 // the first workgroup of the frame
+};
+struct YuvPlanes {
+    int frames, total_blocks;
+    YuvPlanesFrame f[MIXED_MAX_FRAMES];
+};
+void launch_yuv_planes_to_bgr(uint8_t* d_bgr, YuvPlanes clip, hipStream_t stream);
+
+// ---- ingest.hip -------------------------------------------------------------------------
+// Packed 3-byte pixels that are already in device memory -> the tight frame [h][w][3] the frame path reads: h rows of row_bytes =
+// 3 w bytes, `pitch` bytes apart at src (any alignment), to d_out + dst_off (any alignment).  A byte copy: the channel order is
+// the slot's business.  At most 16 records by value in the argument block.
+struct PackFrame {
+    const uint8_t* src;
+    unsigned long long dst_off;
+    int pitch, h, row_bytes;
+    int block0;                                 // the first workgroup of the frame
+};
+struct PackFrames {
+    int frames, total_blocks;
+    PackFrame f[MIXED_MAX_FRAMES];
+};
+void launch_frame_pack(uint8_t* d_out, PackFrames clip, hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16

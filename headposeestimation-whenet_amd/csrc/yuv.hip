@@ -11,6 +11,11 @@
 // four bytes belong to the row; otherwise the bytes are read one by one.  An output row whose address is r mod 4 stores 4 - r head
 // bytes, two aligned dwords (the 12 bytes funnel-shifted) and r tail bytes.  The last group of a row (1..3 pixels when w is no
 // multiple of 4) stores its own bytes one by one: no thread writes a byte outside its pixels, the neighbouring frame starts there.
+//
+// Two sources.  The host-pointer entry points stage a frame's planes TIGHT in one device buffer (kernels.h) and launch the first
+// three kernels.  whenet_yuv_planes_to_bgr_kernel reads planes that are already in device memory where they are -- a decoder's
+// surface, a tensor: three pointers and three pitches per frame -- through the same per-item function, which takes the planes'
+// addresses and pitches as arguments; the tight form calls it with the pitches w, 2 cw / cw, cw.
 #include <algorithm>
 #include <cstring>
 
@@ -47,10 +52,13 @@ __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int shift_b
     return uint32_t(((uint64_t(hi) << 32) | lo) >> shift_bits);
 }
 
-// one item of a frame: group gx (pixels 4 gx ..) of chroma row p (luma rows 2 p, 2 p + 1)
-__device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, const YuvGeom& g, int item) {
-    const int w = g.w, h = g.h;
-    const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, gw = (w + 3) >> 2;
+// one item of a frame: group gx (pixels 4 gx ..) of chroma row p (luma rows 2 p, 2 p + 1).  The planes are wherever they are:
+// luma rows pitch_y bytes apart at py; NV12: interleaved rows pitch_u apart at pu (pv unused); I420: U rows pitch_u apart at pu,
+// V rows pitch_v apart at pv.
+__device__ __forceinline__ void yuv_item_planes(const uint8_t* __restrict__ py, const uint8_t* __restrict__ pu, const uint8_t* __restrict__ pv,
+                                                size_t pitch_y, size_t pitch_u, size_t pitch_v, uint8_t* __restrict__ bgr, int h, int w,
+                                                int format, const YuvCoeffs& k, int item) {
+    const int ch = (h + 1) >> 1, gw = (w + 3) >> 2;
     const int p = item / gw, gx = item - p * gw;
     if (p >= ch) return;
     const int x = gx << 2;
@@ -59,11 +67,10 @@ __device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uin
     const int rows = min(2, h - y0);
     const int cx = x >> 1;
     const bool two = n > 2;                         // the group has a second chroma sample (cx + 1 < cw)
-    const uint8_t* const chroma = planes + size_t(h) * w;
 
     int u0, v0, u1, v1;
-    if (g.format == WHENET_YUV_NV12) {
-        const uint8_t* c = chroma + (size_t(p) * cw + cx) * 2;
+    if (format == WHENET_YUV_NV12) {
+        const uint8_t* c = pu + size_t(p) * pitch_u + 2 * cx;
         if (two && (reinterpret_cast<uintptr_t>(c) & 3) == 0) {
             const uint32_t q = *reinterpret_cast<const uint32_t*>(c);
             u0 = q & 255, v0 = (q >> 8) & 255, u1 = (q >> 16) & 255, v1 = q >> 24;
@@ -72,8 +79,8 @@ __device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uin
             u1 = two ? int(c[2]) : u0, v1 = two ? int(c[3]) : v0;
         }
     } else {
-        const uint8_t* cu = chroma + size_t(p) * cw + cx;
-        const uint8_t* cv = cu + size_t(ch) * cw;
+        const uint8_t* cu = pu + size_t(p) * pitch_u + cx;
+        const uint8_t* cv = pv + size_t(p) * pitch_v + cx;
         if (two && ((reinterpret_cast<uintptr_t>(cu) | reinterpret_cast<uintptr_t>(cv)) & 1) == 0) {
             const uint32_t qu = *reinterpret_cast<const uint16_t*>(cu), qv = *reinterpret_cast<const uint16_t*>(cv);
             u0 = qu & 255, u1 = qu >> 8, v0 = qv & 255, v1 = qv >> 8;
@@ -82,10 +89,10 @@ __device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uin
             u1 = two ? int(cu[1]) : u0, v1 = two ? int(cv[1]) : v0;
         }
     }
-    const ChromaTerms c0 = chroma_terms(g.k, u0, v0), c1 = chroma_terms(g.k, u1, v1);
+    const ChromaTerms c0 = chroma_terms(k, u0, v0), c1 = chroma_terms(k, u1, v1);
 
     for (int r = 0; r < rows; ++r) {
-        const uint8_t* yp = planes + size_t(y0 + r) * w + x;
+        const uint8_t* yp = py + size_t(y0 + r) * pitch_y + x;
         uint32_t y4;
         if (n == 4 && (reinterpret_cast<uintptr_t>(yp) & 3) == 0) {
             y4 = *reinterpret_cast<const uint32_t*>(yp);
@@ -95,8 +102,8 @@ __device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uin
             if (n > 2) y4 |= uint32_t(yp[2]) << 16;
             if (n > 3) y4 |= uint32_t(yp[3]) << 24;
         }
-        const uint32_t p0 = pixel_bgr(g.k, y4 & 255, c0), p1 = pixel_bgr(g.k, (y4 >> 8) & 255, c0);
-        const uint32_t p2 = pixel_bgr(g.k, (y4 >> 16) & 255, c1), p3 = pixel_bgr(g.k, y4 >> 24, c1);
+        const uint32_t p0 = pixel_bgr(k, y4 & 255, c0), p1 = pixel_bgr(k, (y4 >> 8) & 255, c0);
+        const uint32_t p2 = pixel_bgr(k, (y4 >> 16) & 255, c1), p3 = pixel_bgr(k, y4 >> 24, c1);
         const uint32_t w0 = p0 | (p1 << 24), w1 = (p1 >> 8) | (p2 << 16), w2 = (p2 >> 16) | (p3 << 8);
         uint8_t* dp = bgr + (size_t(y0 + r) * w + x) * 3;
         if (n == 4) {
@@ -126,6 +133,14 @@ __device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uin
     }
 }
 
+// the same item of a frame whose planes lie TIGHT behind one another at `planes` (kernels.h)
+__device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, const YuvGeom& g, int item) {
+    const size_t cw = size_t((g.w + 1) >> 1), ch = size_t((g.h + 1) >> 1);
+    const uint8_t* const chroma = planes + size_t(g.h) * g.w;
+    const bool nv12 = g.format == WHENET_YUV_NV12;
+    yuv_item_planes(planes, chroma, chroma + ch * cw, size_t(g.w), nv12 ? 2 * cw : cw, cw, bgr, g.h, g.w, g.format, g.k, item);
+}
+
 __global__ __launch_bounds__(THREADS) void whenet_yuv_to_bgr_kernel(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, YuvGeom g) {
     yuv_item(planes + g.src_off, bgr + g.dst_off, g, int(blockIdx.x) * THREADS + int(threadIdx.x));
 }
@@ -146,6 +161,18 @@ __global__ __launch_bounds__(THREADS) void whenet_yuv_to_bgr_mixed_kernel(const 
         if (clip.f[i].block0 <= b) f = i;
     const YuvGeom& g = clip.f[f];
     yuv_item(planes + g.src_off, bgr + g.dst_off, g, (b - g.block0) * THREADS + int(threadIdx.x));
+}
+
+// Planes where a decoder (or a tensor) left them in device memory, each with its own pitch: the records travel by value in the
+// argument block, the frame of a workgroup is found as in the mixed kernel above
+__global__ __launch_bounds__(THREADS) void whenet_yuv_planes_to_bgr_kernel(uint8_t* __restrict__ bgr, YuvPlanes clip) {
+    const int b = int(blockIdx.x);
+    int f = 0;
+    for (int i = 1; i < clip.frames; ++i)
+        if (clip.f[i].block0 <= b) f = i;
+    const YuvPlanesFrame& g = clip.f[f];
+    yuv_item_planes(g.plane[0], g.plane[1], g.plane[2], size_t(g.pitch[0]), size_t(g.pitch[1]), size_t(g.pitch[2]), bgr + g.dst_off, g.h, g.w,
+                    g.format, g.k, (b - g.block0) * THREADS + int(threadIdx.x));
 }
 
 int yuv_blocks(int h, int w) { return (((w + 3) >> 2) * ((h + 1) >> 1) + THREADS - 1) / THREADS; }
@@ -255,6 +282,27 @@ void launch_yuv_to_bgr_mixed(const uint8_t* d_planes, uint8_t* d_bgr, YuvMixed c
     }
     clip.total_blocks = blocks;
     hipLaunchKernelGGL(whenet_yuv_to_bgr_mixed_kernel, dim3(blocks), dim3(THREADS), 0, stream, d_planes, d_bgr, clip);
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+// block0 / total_blocks are set here.  The callers have checked the planes (Engine::check_device_plane): the kernel reads
+// rows x row bytes of each at its pitch and nothing else.
+void launch_yuv_planes_to_bgr(uint8_t* d_bgr, YuvPlanes clip, hipStream_t stream) {
+    WHENET_REQUIRE(clip.frames >= 1 && clip.frames <= MIXED_MAX_FRAMES, WHENET_EINVAL, "yuv_planes_to_bgr: 1..16 frames");
+    int blocks = 0;
+    for (int f = 0; f < clip.frames; ++f) {
+        const YuvPlanesFrame& g = clip.f[f];
+        const int cw = (g.w + 1) >> 1;
+        const bool nv12 = g.format == WHENET_YUV_NV12;
+        WHENET_REQUIRE(g.h >= 1 && g.w >= 1 && g.h <= YUV_MAX_FRAME_SIDE && g.w <= YUV_MAX_FRAME_SIDE && (nv12 || g.format == WHENET_YUV_I420) &&
+                           g.plane[0] != nullptr && g.plane[1] != nullptr && (nv12 || g.plane[2] != nullptr) && g.pitch[0] >= g.w &&
+                           g.pitch[1] >= (nv12 ? 2 * cw : cw) && (nv12 || g.pitch[2] >= cw),
+                       WHENET_EINVAL, "yuv_planes_to_bgr: bad frame geometry");
+        clip.f[f].block0 = blocks;
+        blocks += yuv_blocks(g.h, g.w);
+    }
+    clip.total_blocks = blocks;
+    hipLaunchKernelGGL(whenet_yuv_planes_to_bgr_kernel, dim3(blocks), dim3(THREADS), 0, stream, d_bgr, clip);
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

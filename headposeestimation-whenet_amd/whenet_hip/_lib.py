@@ -101,6 +101,12 @@ _PROTOS = {
     "whenet_op_yuv_to_bgr": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, C.POINTER(_P)]),
     "whenet_frame_begin_yuv": (C.c_int, [_P, C.POINTER(YuvFrameC), C.POINTER(C.c_int)]),
     "whenet_clip_begin_yuv": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, C.POINTER(C.c_int)]),
+    "whenet_frame_begin_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
+    "whenet_clip_begin_device": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, _P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "whenet_frame_begin_yuv_device": (C.c_int, [_P, C.POINTER(YuvFrameC), _P, C.POINTER(C.c_int)]),
+    "whenet_clip_begin_yuv_device": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, _P, C.POINTER(C.c_int)]),
+    "whenet_op_pack_device": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, _P, _P, _P, C.POINTER(_P)]),
+    "whenet_op_yuv_to_bgr_device": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, _P, C.POINTER(_P)]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -195,6 +201,135 @@ def _mixed_args(frames):
     """(pointer array, heights, widths) of mixed_u8's list, as the three array arguments of the mixed entry points."""
     ptrs = (_P * len(frames))(*[f.ctypes.data for f in frames])
     return ptrs, np.array([f.shape[0] for f in frames], np.int32), np.array([f.shape[1] for f in frames], np.int32)
+
+
+# ---- device arrays: anything that exposes __cuda_array_interface__ (torch-ROCm tensors, CuPy arrays); no torch import here ----
+class DeviceView:
+    """A strided view of uint8 device memory: `ptr` (an integer address), `shape`, byte `strides`, and `owner`, the object whose
+    memory it is (kept alive with the view).  It exposes `__cuda_array_interface__` itself, so it is a device array too."""
+
+    def __init__(self, ptr: int, shape, strides, owner=None):
+        self.ptr, self.shape, self.strides, self.owner = int(ptr), tuple(int(v) for v in shape), tuple(int(v) for v in strides), owner
+
+    @property
+    def __cuda_array_interface__(self):
+        return dict(shape=self.shape, typestr="|u1", data=(self.ptr, True), strides=self.strides, version=3)
+
+
+def is_device_array(a) -> bool:
+    return hasattr(a, "__cuda_array_interface__")
+
+
+def device_view(a, what: str = "device array") -> DeviceView:
+    """The `__cuda_array_interface__` of `a` as a DeviceView: uint8 only, a non-NULL pointer, non-negative strides (None: C
+    order).  The read-only flag is accepted: the library only reads.  ValueError otherwise; nothing is ever copied."""
+    cai = a.__cuda_array_interface__
+    if not isinstance(cai, dict) or "shape" not in cai or "typestr" not in cai or "data" not in cai:
+        raise ValueError(f"{what}: malformed __cuda_array_interface__")
+    if cai["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
+        raise ValueError(f"{what} must be uint8, got typestr {cai['typestr']!r}")
+    shape = tuple(int(v) for v in cai["shape"])
+    strides = cai.get("strides")
+    if strides is None:
+        strides, acc = [], 1
+        for n in reversed(shape):
+            strides.append(acc)
+            acc *= n
+        strides = tuple(reversed(strides))
+    strides = tuple(int(v) for v in strides)
+    if len(strides) != len(shape) or any(v < 0 for v in strides):
+        raise ValueError(f"{what}: strides {strides} do not fit shape {shape} (negative strides are not supported)")
+    ptr = cai["data"][0]
+    if not ptr and all(shape):
+        raise ValueError(f"{what}: NULL device pointer")
+    return DeviceView(int(ptr or 0), shape, strides, a)
+
+
+class DeviceFrame:
+    """One packed 3-byte-pixel frame in device memory as the device entry points take it: `ptr`, byte `pitch`, `h`, `w`
+    (`owner`: what keeps the memory alive)."""
+
+    def __init__(self, ptr: int, pitch: int, h: int, w: int, owner=None):
+        self.ptr, self.pitch, self.h, self.w, self.owner = int(ptr), int(pitch), int(h), int(w), owner
+
+    def __repr__(self):
+        return f"DeviceFrame(ptr=0x{self.ptr:x}, pitch={self.pitch}, h={self.h}, w={self.w})"
+
+
+def _device_frame_of_view(v: DeviceView, what: str) -> DeviceFrame:
+    if len(v.shape) != 3 or v.shape[2] != 3:
+        raise ValueError(f"{what} must be uint8 [H,W,3], got shape {v.shape}")
+    h, w = v.shape[0], v.shape[1]
+    if not (1 <= h <= MAX_FRAME_SIDE and 1 <= w <= MAX_FRAME_SIDE):
+        raise ValueError(f"{what} is {h} x {w}: sides must be 1..{MAX_FRAME_SIDE}")
+    if v.strides[2] != 1 or (w > 1 and v.strides[1] != 3):
+        raise ValueError(f"{what}: the pixels of a row must be packed (inner strides (3, 1), got {v.strides[1:]}); "
+                         "a device frame is never copied: make it contiguous on the device first")
+    pitch = v.strides[0] if h > 1 else 3 * w           # (a frame of one row has no row stride of its own)
+    if pitch < 3 * w:
+        raise ValueError(f"{what}: row stride {pitch} is below its row of {3 * w} bytes")
+    return DeviceFrame(v.ptr, pitch, h, w, v.owner)
+
+
+def device_frame(a, what: str = "frame") -> DeviceFrame:
+    """A uint8 [H,W,3] device array -> DeviceFrame: the inner strides must be (3, 1), the row stride is the pitch (a DeviceFrame
+    is returned as it is).  ValueError for anything else; nothing is copied."""
+    if isinstance(a, DeviceFrame):
+        return a
+    return _device_frame_of_view(device_view(a, what), what)
+
+
+def device_frames(frames, one_size: bool = False) -> list:
+    """The frames of a clip in device memory -> a list of 1..16 DeviceFrames: a list of uint8 [H,W,3] device arrays (or
+    DeviceFrames), or ONE uint8 [F,H,W,3] device array.  one_size: all frames must have one size.  A list that mixes host and
+    device frames is a ValueError."""
+    if is_device_array(frames):
+        v = device_view(frames, "clip")
+        if len(v.shape) != 4:
+            raise ValueError(f"a device clip must be uint8 [F,H,W,3] or a list of uint8 [H,W,3] device arrays, got shape {v.shape}")
+        items = [_device_frame_of_view(DeviceView(v.ptr + f * v.strides[0], v.shape[1:], v.strides[1:], v.owner), f"frame {f}")
+                 for f in range(v.shape[0])]
+    else:
+        frames = list(frames)
+        on_device = [isinstance(f, DeviceFrame) or is_device_array(f) for f in frames]
+        if any(on_device) and not all(on_device):
+            raise ValueError("a clip's frames are all in device memory or all in host memory, not mixed: frames " +
+                             str([i for i, d in enumerate(on_device) if not d]) + " are host arrays")
+        items = [device_frame(f, f"frame {i}") for i, f in enumerate(frames)]
+    if not 1 <= len(items) <= MAX_CLIP_FRAMES:
+        raise ValueError(f"a clip holds 1..{MAX_CLIP_FRAMES} frames, got {len(items)}")
+    if one_size:
+        for f in items:
+            if (f.h, f.w) != (items[0].h, items[0].w):
+                raise ValueError(f"the frames of a clip have one size: got {(items[0].h, items[0].w)} and {(f.h, f.w)}")
+    return items
+
+
+def any_on_device(frames) -> bool:
+    """Whether a clip argument (an array or a list of frames) holds device memory anywhere."""
+    if isinstance(frames, np.ndarray):
+        return False
+    if is_device_array(frames) or isinstance(frames, DeviceFrame):
+        return True
+    try:
+        return any(isinstance(f, DeviceFrame) or is_device_array(f) for f in frames)
+    except TypeError:
+        return False
+
+
+def _device_args(frames):
+    """(pointer array, pitches, heights, widths) of a list of DeviceFrames, as the array arguments of the device entry points."""
+    ptrs = (_P * max(len(frames), 1))(*[f.ptr for f in frames])
+    return (ptrs,) + tuple(np.array([getattr(f, k) for f in frames], np.int32) for k in ("pitch", "h", "w"))
+
+
+def _stream(stream):
+    """A stream argument -> void*: None (the default stream) or an integer stream handle (torch: `s.cuda_stream`)."""
+    if stream is None or stream == 0:
+        return None
+    if not isinstance(stream, int):
+        raise ValueError(f"stream must be None or an integer stream handle (torch.cuda.current_stream().cuda_stream), got {type(stream).__name__}")
+    return _P(stream)
 
 
 def check_max_heads(max_heads) -> None:
@@ -717,6 +852,58 @@ class Handle:
         t = C.c_int(-1)
         self._check(self._lib.whenet_clip_begin_yuv(self._h, arr, len(descs), C.byref(t)))
         return t.value
+
+    # ---- ingest from device memory: the frame (or its planes) is already in HBM ------------------------
+    def frame_begin_device(self, frame, bgr: bool = True, stream=None) -> int:
+        """`frame_begin` of a uint8 [H,W,3] device array (or a DeviceFrame): no host copy, no PCIe; ordered on `stream` (None: the
+        default stream; torch: `torch.cuda.current_stream().cuda_stream`)."""
+        f = device_frame(frame)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin_device(self._h, f.ptr, f.pitch, f.h, f.w, BGR if bgr else RGB, _stream(stream), C.byref(t)))
+        return t.value
+
+    def clip_begin_device(self, frames, bgr: bool = True, stream=None) -> int:
+        """`clip_begin` (frames of one size) or `clip_begin_mixed` (otherwise) of frames in device memory: a list of uint8 [H,W,3]
+        device arrays or one [F,H,W,3] device array."""
+        items = device_frames(frames)
+        ptrs, pitch, fh, fw = _device_args(items)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_device(self._h, ptrs, _ptr(pitch), len(items), _ptr(fh), _ptr(fw), BGR if bgr else RGB,
+                                                       _stream(stream), C.byref(t)))
+        return t.value
+
+    def frame_begin_yuv_device(self, frame, stream=None) -> int:
+        """`frame_begin_yuv` of a frame whose planes are in device memory (a `YUVFrame` with `on_device`, or a YuvFrameC)."""
+        arr, _ = _yuv_descs([frame])
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin_yuv_device(self._h, arr, _stream(stream), C.byref(t)))
+        return t.value
+
+    def clip_begin_yuv_device(self, frames: list, stream=None) -> int:
+        """`clip_begin_yuv` of frames whose planes are in device memory."""
+        arr, descs = _yuv_descs(frames)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_yuv_device(self._h, arr, len(descs), _stream(stream), C.byref(t)))
+        return t.value
+
+    def op_pack_device(self, frames, stream=None) -> list:
+        """The packing kernel alone on 1..16 frames in device memory (uint8 [H_i,W_i,3] device arrays or DeviceFrames), packed back
+        to back on the device as a mixed clip packs them -> a list of tight uint8 [H_i,W_i,3] host arrays."""
+        items = device_frames(frames) if len(frames) else []
+        ptrs, pitch, fh, fw = _device_args(items)
+        outs = [np.empty((max(f.h, 0), max(f.w, 0), 3), np.uint8) for f in items]
+        optrs = (_P * max(len(outs), 1))(*[o.ctypes.data if o.size else None for o in outs])
+        self._check(self._lib.whenet_op_pack_device(self._h, ptrs, _ptr(pitch), len(items), _ptr(fh), _ptr(fw), _stream(stream), optrs))
+        return outs
+
+    def op_yuv_to_bgr_device(self, frames: list, stream=None) -> list:
+        """The plane kernel alone on 1..16 frames whose planes are in device memory, with their pitches -> a list of uint8
+        [H_i,W_i,3] host arrays (B, G, R): the device twin of `op_yuv_to_bgr`."""
+        arr, descs = _yuv_descs(frames)
+        outs = [np.empty((max(int(d.h), 0), max(int(d.w), 0), 3), np.uint8) for d in descs]
+        ptrs = (_P * max(len(outs), 1))(*[o.ctypes.data if o.size else None for o in outs])
+        self._check(self._lib.whenet_op_yuv_to_bgr_device(self._h, arr, len(descs), _stream(stream), ptrs))
+        return outs
 
     def op_letterbox_mixed(self, frames: list, size=(416, 416), bgr: bool = True, want_u8: bool = True, want_f32: bool = True):
         """`op_letterbox` of F frames of their own sizes in one call: (canvas uint8 [F,h,w,3], image float32 [F,h,w,3])."""

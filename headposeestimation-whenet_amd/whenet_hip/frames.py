@@ -32,6 +32,13 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     / `begin_clip_yuv(frames)`: half the bytes cross PCIe and the BGR frame is built on the device (`csrc/yuv.hip`); everything
     that follows is what `begin(frame.to_bgr())` / `begin_clip...` would have been followed by, bit for bit.
 
+  * a frame that is ALREADY in device memory -- a hardware decoder's surface, a torch-ROCm tensor, a CuPy array: anything that
+    exposes `__cuda_array_interface__` -- goes to the same calls: `begin(tensor, stream=...)`, `begin_clip`, `begin_clip_mixed`,
+    and `begin_yuv` / `begin_clip_yuv` with a `YUVFrame` whose planes are device arrays.  One kernel (`csrc/ingest.hip`,
+    `csrc/yuv.hip`) reads it where it is, with its row pitch, ordered on the caller's stream: no host copy, no PCIe, no host
+    wait, and the same results bit for bit.  A device frame is never copied to make it fit: uint8 [H,W,3] with inner strides
+    (3, 1) or a ValueError.  Not built: BGRA / 4-channel, float or CHW tensors, 10-bit surfaces, memory of another GPU.
+
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
 from __future__ import annotations
@@ -129,45 +136,68 @@ class FramePipeline:
         ticket = self._h.submit_frame(frame, rects, bgr=self._bgr)
         self._pending.append((ticket, rects, 0))
 
-    def begin(self, frame: np.ndarray) -> None:
+    def begin(self, frame: np.ndarray, stream=None) -> None:
         """Resident form, step 1: upload the frame (it crosses PCIe once).  The frame holds one of the `depth`
-        places from here until its `collect()`; `heads()` must follow before the next `begin()` / `submit()`."""
+        places from here until its `collect()`; `heads()` must follow before the next `begin()` / `submit()`.
+
+        A uint8 [H,W,3] DEVICE array (inner strides (3, 1), the row stride is the pitch) is read where it is, ordered on `stream`:
+        an integer stream handle, `None` = the default stream, which is where torch enqueues unless told otherwise:
+
+            fp.begin(tensor, stream=torch.cuda.current_stream().cuda_stream)
+
+        What was enqueued on `stream` before the call is seen; what is enqueued on it afterwards may overwrite the tensor; any
+        other writer (the host, another stream) waits until `collect()` has returned.  `stream` is ignored for host frames."""
         if self._begun is not None:
             raise ValueError("the frame begun last has no heads yet: heads() first")
         if self._begun_clip is not None:
             raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
         if len(self._pending) >= self._depth:
             raise ValueError(f"{self._depth} frames already in flight: collect() first")
+        if _lib.is_device_array(frame) or isinstance(frame, _lib.DeviceFrame):
+            f = _lib.device_frame(frame)
+            ticket = self._h.frame_begin_device(f, bgr=self._bgr, stream=stream)
+            self._begun = (ticket, f.h, f.w)
+            return
         frame = np.asarray(frame)
         if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
             raise ValueError(f"frame must be uint8 [H,W,3], got {frame.dtype} {frame.shape}")
         ticket = self._h.frame_begin(frame, bgr=self._bgr)
         self._begun = (ticket, frame.shape[0], frame.shape[1])
 
-    def begin_clip(self, frames) -> None:
+    def begin_clip(self, frames, stream=None) -> None:
         """A clip, step 1: upload F frames (1..16) of ONE size, a uint8 [F,H,W,3] array or a list of uint8 [H,W,3] frames (stacked
         here), with one copy.  The clip holds one of the `depth` places until its `collect_clip()`; `detect_heads_clip()` must
-        follow before the next `begin()` / `begin_clip()` / `submit()`."""
+        follow before the next `begin()` / `begin_clip()` / `submit()`.  Frames in device memory (one [F,H,W,3] device array or a
+        list of [H,W,3] device arrays, all of them) are read where they are, ordered on `stream` as in `begin()`."""
         if self._begun is not None:
             raise ValueError("the frame begun last has no heads yet: heads() first")
         if self._begun_clip is not None:
             raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
         if len(self._pending) >= self._depth:
             raise ValueError(f"{self._depth} frames already in flight: collect() first")
+        if _lib.any_on_device(frames):
+            items = _lib.device_frames(frames, one_size=True)
+            self._begun_clip = (self._h.clip_begin_device(items, bgr=self._bgr, stream=stream), len(items))
+            return
         frames = _lib.clip_u8(frames)
         ticket = self._h.clip_begin(frames, bgr=self._bgr)
         self._begun_clip = (ticket, frames.shape[0])
 
-    def begin_clip_mixed(self, frames) -> None:
+    def begin_clip_mixed(self, frames, stream=None) -> None:
         """A clip of frames of DIFFERENT sizes (several cameras, several files), step 1: upload a list of 1..16 uint8 [H_i,W_i,3]
         frames, packed back to back, with one copy.  From here on it is a clip like `begin_clip()`'s: `detect_heads_clip()` and
-        `collect_clip()` follow, and frame f returns what `begin(); detect_heads(); collect()` return for it alone."""
+        `collect_clip()` follow, and frame f returns what `begin(); detect_heads(); collect()` return for it alone.  A list of
+        device arrays (all of them) is packed by one kernel on the device, ordered on `stream` as in `begin()`."""
         if self._begun is not None:
             raise ValueError("the frame begun last has no heads yet: heads() first")
         if self._begun_clip is not None:
             raise ValueError("the clip begun last has no heads yet: detect_heads_clip() first")
         if len(self._pending) >= self._depth:
             raise ValueError(f"{self._depth} frames already in flight: collect() first")
+        if _lib.any_on_device(frames):
+            items = _lib.device_frames(frames)
+            self._begun_clip = (self._h.clip_begin_device(items, bgr=self._bgr, stream=stream), len(items))
+            return
         frames = _lib.mixed_u8(frames)
         ticket = self._h.clip_begin_mixed(frames, bgr=self._bgr)
         self._begun_clip = (ticket, len(frames))
@@ -180,21 +210,23 @@ class FramePipeline:
         if len(self._pending) >= self._depth:
             raise ValueError(f"{self._depth} frames already in flight: collect() first")
 
-    def begin_yuv(self, frame) -> None:
+    def begin_yuv(self, frame, stream=None) -> None:
         """`begin()` from a decoder's planes (a `whenet_hip.yuv.YUVFrame`): the planes are uploaded as they are, 1.5 bytes per pixel,
         and the BGR frame is built on the device.  Everything that follows -- `detector_input`, `detect`, `heads`, `detect_heads`,
-        `collect` -- is what it is after `begin(frame.to_bgr())` on a pipeline made with `bgr=True`."""
+        `collect` -- is what it is after `begin(frame.to_bgr())` on a pipeline made with `bgr=True`.  A frame whose planes are in
+        device memory (`frame.on_device`) is converted where it is, ordered on `stream` as in `begin()`."""
         from .yuv import YUVFrame
         self._check_can_begin()
         if not isinstance(frame, YUVFrame):
             raise ValueError(f"begin_yuv takes a whenet_hip.yuv.YUVFrame, got {type(frame).__name__}")
-        ticket = self._h.frame_begin_yuv(frame)
+        ticket = self._h.frame_begin_yuv_device(frame, stream=stream) if frame.on_device else self._h.frame_begin_yuv(frame)
         self._begun = (ticket, frame.h, frame.w)
 
-    def begin_clip_yuv(self, frames) -> None:
+    def begin_clip_yuv(self, frames, stream=None) -> None:
         """A clip from the planes of 1..16 `YUVFrame`s, each with its own format and matrix: frames of one size make a clip as
         `begin_clip()` makes it, frames of different sizes one as `begin_clip_mixed()` makes it (at most option "letterbox_cache"
-        of them).  `detect_heads_clip()` and `collect_clip()` follow."""
+        of them).  `detect_heads_clip()` and `collect_clip()` follow.  The frames' planes are all in device memory (converted
+        where they are, ordered on `stream` as in `begin()`) or all in host memory."""
         from .yuv import YUVFrame
         self._check_can_begin()
         frames = list(frames)
@@ -203,7 +235,10 @@ class FramePipeline:
         for i, f in enumerate(frames):
             if not isinstance(f, YUVFrame):
                 raise ValueError(f"begin_clip_yuv: frame {i} must be a whenet_hip.yuv.YUVFrame, got {type(f).__name__}")
-        ticket = self._h.clip_begin_yuv(frames)
+        if len({f.on_device for f in frames}) > 1:
+            raise ValueError("begin_clip_yuv: a clip's frames are all in device memory or all in host memory, not mixed: frames " +
+                             str([i for i, f in enumerate(frames) if not f.on_device]) + " are host frames")
+        ticket = self._h.clip_begin_yuv_device(frames, stream=stream) if frames[0].on_device else self._h.clip_begin_yuv(frames)
         self._begun_clip = (ticket, len(frames))
 
     def _begun_frame(self, what: str):

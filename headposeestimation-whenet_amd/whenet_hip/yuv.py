@@ -6,6 +6,14 @@ include/whenet_hip.h; `to_bgr()` runs the same arithmetic on the host inside the
 
     frame = YUVFrame.from_buffer(decoder_buffer, 1080, 1920, "nv12", pitch=2048, matrix="bt709")
     fp.begin_yuv(frame); fp.detect_heads(); rects, yaw, pitch, roll = fp.collect()
+
+The planes may also lie in DEVICE memory -- a hardware decoder's surface, torch-ROCm tensors, CuPy arrays: anything that exposes
+`__cuda_array_interface__` is taken as a plane (all planes of a frame on the device, or all on the host; `on_device` tells which).
+`begin_yuv` then converts them where they are (no host copy, no PCIe), ordered on the caller's stream:
+
+    surface = torch.empty(2048 * 1620, dtype=torch.uint8, device="cuda")          # filled by the decoder
+    frame = YUVFrame.from_buffer(surface, 1080, 1920, "nv12", pitch=2048, matrix="bt709")
+    fp.begin_yuv(frame, stream=torch.cuda.current_stream().cuda_stream)
 """
 from __future__ import annotations
 
@@ -49,6 +57,21 @@ def _plane(a, rows: int, row_bytes: int, name: str) -> np.ndarray:
     return a
 
 
+def _device_plane(a, rows: int, row_bytes: int, name: str) -> "_lib.DeviceView":
+    """`_plane` for a plane in device memory: the same shapes and stride rules, read from `__cuda_array_interface__`."""
+    v = _lib.device_view(a, f"{name} plane")
+    shape, strides = v.shape, v.strides
+    if len(shape) == 3 and shape[2] == 2 and strides[1:] == (2, 1):
+        shape, strides = (shape[0], shape[1] * 2), (strides[0], 1)
+    if len(shape) != 2 or shape != (rows, row_bytes):
+        raise ValueError(f"{name} plane must be uint8 [{rows},{row_bytes}], got shape {v.shape}")
+    if row_bytes > 1 and strides[1] != 1:
+        raise ValueError(f"{name} plane: the bytes of a row must be contiguous (strides {strides})")
+    if rows > 1 and strides[0] < row_bytes:
+        raise ValueError(f"{name} plane: row stride {strides[0]} is below its row of {row_bytes} bytes")
+    return _lib.DeviceView(v.ptr, shape, strides, v.owner)
+
+
 class YUVFrame:
     """The planes of one 4:2:0 frame of h x w luma samples: `planes` (2 arrays for NV12: Y, interleaved UV; 3 for I420: Y, U, V),
     their byte `pitches`, `format`, `matrix` (codes of include/whenet_hip.h), `h`, `w`.  The chroma planes have (h + 1) // 2 rows of
@@ -66,42 +89,64 @@ class YUVFrame:
         planes = list(planes)
         if len(planes) != len(shapes):
             raise ValueError(f"{'NV12' if self.format == _lib.YUV_NV12 else 'I420'} has {len(shapes)} planes, got {len(planes)}")
-        self.planes = tuple(_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
+        on_device = [_lib.is_device_array(a) for a in planes]
+        if any(on_device) and not all(on_device):
+            raise ValueError("the planes of a frame are all in device memory or all in host memory, got " +
+                             ", ".join(f"{n}: {'device' if d else 'host'}" for (_, _, n), d in zip(shapes, on_device)))
+        self.on_device = all(on_device)       # the planes are device memory (`_lib.DeviceView`s), not numpy arrays
+        if self.on_device:
+            self.planes = tuple(_device_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
+        else:
+            self.planes = tuple(_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
         # a plane of one row has no row stride of its own: its pitch is its row
         self.pitches = tuple(int(a.strides[0]) if a.shape[0] > 1 else int(a.shape[1]) for a in self.planes)
 
     @classmethod
     def nv12(cls, y, uv, matrix="bt601") -> "YUVFrame":
         """Y uint8 [h,w] and the interleaved chroma plane uint8 [ch, 2 cw] (or [ch, cw, 2]: U, V)."""
-        y = np.asarray(y)
-        if y.ndim != 2:
-            raise ValueError(f"Y plane must be uint8 [h,w], got shape {y.shape}")
-        return cls((y, uv), _lib.YUV_NV12, matrix, y.shape[0], y.shape[1])
+        h, w = cls._luma_size(y)
+        return cls((y, uv), _lib.YUV_NV12, matrix, h, w)
 
     @classmethod
     def i420(cls, y, u, v, matrix="bt601") -> "YUVFrame":
         """Y uint8 [h,w], U and V uint8 [ch,cw]."""
-        y = np.asarray(y)
-        if y.ndim != 2:
-            raise ValueError(f"Y plane must be uint8 [h,w], got shape {y.shape}")
-        return cls((y, u, v), _lib.YUV_I420, matrix, y.shape[0], y.shape[1])
+        h, w = cls._luma_size(y)
+        return cls((y, u, v), _lib.YUV_I420, matrix, h, w)
+
+    @staticmethod
+    def _luma_size(y):
+        shape = tuple(y.__cuda_array_interface__["shape"]) if _lib.is_device_array(y) else np.asarray(y).shape
+        if len(shape) != 2:
+            raise ValueError(f"Y plane must be uint8 [h,w], got shape {shape}")
+        return int(shape[0]), int(shape[1])
 
     @classmethod
     def from_buffer(cls, buf, h: int, w: int, format="nv12", pitch=None, matrix="bt601") -> "YUVFrame":
         """A decoder's single allocation: h rows of luma at `pitch` bytes, then the chroma rows.  NV12: (h + 1) // 2 interleaved
         rows at the same pitch.  I420: the U rows and then the V rows at (pitch + 1) // 2 bytes.  Without `pitch` the planes are
         tight: every row is followed by the next.  `buf` is anything with
-        the buffer interface (bytes, a memoryview, a uint8 array); it is not copied."""
+        the buffer interface (bytes, a memoryview, a uint8 array), or a contiguous uint8 DEVICE array (the decoder's surface in
+        device memory: the frame is then `on_device`); it is not copied."""
         fmt = _code(FORMATS, format, "format")
         h, w = int(h), int(w)
         if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
             raise ValueError(f"frame is {h} x {w}: sides must be 1..{MAX_SIDE}")
-        a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
-        if a.dtype != np.uint8:
-            raise ValueError(f"buffer must hold uint8, got {a.dtype}")
-        a = a.reshape(-1) if a.flags.c_contiguous else None
-        if a is None:
-            raise ValueError("buffer must be contiguous")
+        dev = None
+        if _lib.is_device_array(buf):
+            dev = _lib.device_view(buf, "buffer")
+            size, acc = int(np.prod(dev.shape, dtype=np.int64)), 1
+            for n, st in zip(reversed(dev.shape), reversed(dev.strides)):
+                if n > 1 and st != acc:
+                    raise ValueError("buffer must be contiguous")
+                acc *= n
+        else:
+            a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+            if a.dtype != np.uint8:
+                raise ValueError(f"buffer must hold uint8, got {a.dtype}")
+            a = a.reshape(-1) if a.flags.c_contiguous else None
+            if a is None:
+                raise ValueError("buffer must be contiguous")
+            size = a.size
         ch, cw = (h + 1) // 2, (w + 1) // 2
         crow = 2 * cw if fmt == _lib.YUV_NV12 else cw
         if pitch is None:               # tight: every plane's pitch is its row
@@ -113,10 +158,12 @@ class YUVFrame:
             raise ValueError(f"pitch {pitch} is below a row of the {h} x {w} frame")
         nchroma = 1 if fmt == _lib.YUV_NV12 else 2
         need = pitch * h + (nchroma * ch - 1) * cpitch + crow      # (the last row ends with its last sample)
-        if a.size < need:
-            raise ValueError(f"buffer holds {a.size} bytes, the frame needs {need}")
+        if size < need:
+            raise ValueError(f"buffer holds {size} bytes, the frame needs {need}")
 
         def view(off, rows, row_bytes, p):
+            if dev is not None:
+                return _lib.DeviceView(dev.ptr + off, (rows, row_bytes), (p, 1), dev.owner)
             return np.lib.stride_tricks.as_strided(a[off:], (rows, row_bytes), (p, 1), writeable=False)
 
         planes = [view(0, h, w, pitch)]
@@ -128,11 +175,14 @@ class YUVFrame:
         """The whenet_yuv_frame_t of this frame (it points into the planes: keep the frame alive while it is used)."""
         d = _lib.YuvFrameC()
         for i, (a, p) in enumerate(zip(self.planes, self.pitches)):
-            d.plane[i] = a.ctypes.data
+            d.plane[i] = a.ptr if self.on_device else a.ctypes.data
             d.pitch[i] = p
         d.format, d.matrix, d.h, d.w = self.format, self.matrix, self.h, self.w
         return d
 
     def to_bgr(self) -> np.ndarray:
         """uint8 [h,w,3] in B, G, R order: the frame `begin_yuv` builds on the device, computed on the host inside the library."""
+        if self.on_device:
+            raise ValueError("to_bgr() runs on the host and this frame's planes are in device memory: Handle.op_yuv_to_bgr_device([frame]) "
+                             "converts them on the device")
         return _lib.yuv_to_bgr_host(self.descriptor())

@@ -554,6 +554,41 @@ WHENET_API int whenet_op_yuv_to_bgr(whenet_t* h, const whenet_yuv_frame_t* frame
 WHENET_API int whenet_frame_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frame, int* ticket);
 WHENET_API int whenet_clip_begin_yuv(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, int* ticket);
 
+/* ---- INGEST FROM DEVICE MEMORY: pitched BGR / RGB and NV12 / I420 surfaces that are already in HBM (additions to ABI 6).  The
+ * card's video decoder writes its surfaces into device memory and a PyTorch-ROCm pipeline holds frames as uint8 device tensors:
+ * the entry points above would have such a caller copy the frame to the host so that the library can copy it back.  These begin
+ * a frame, a clip or a mixed clip from device pointers; one kernel (csrc/ingest.hip for packed pixels, csrc/yuv.hip for planes)
+ * writes the slot's frame buffer, no pinned staging is touched, and everything after `begin` is unchanged: the results are bit
+ * for bit those of the host-pointer call each one replaces.
+ *   whenet_frame_begin_device      replaces whenet_frame_begin: d_frame = frame_h rows of 3 frame_w bytes, `pitch` bytes apart
+ *   whenet_clip_begin_device       replaces whenet_clip_begin (frames all of one size) and whenet_clip_begin_mixed (otherwise; at
+ *                  most option "letterbox_cache" frames): 1..16 frames, each with its own pointer, pitch and size
+ *   whenet_frame_begin_yuv_device  replaces whenet_frame_begin_yuv: frame->plane[] are DEVICE pointers
+ *   whenet_clip_begin_yuv_device   replaces whenet_clip_begin_yuv the same way
+ *   whenet_op_pack_device          the packing kernel alone, device to host: out[f] = uint8 [h_f][w_f][3] (host), the frames packed
+ *                  back to back on the device as a mixed clip packs them.  Works on a whenet_create_postproc handle; the host waits.
+ *   whenet_op_yuv_to_bgr_device    the plane kernel alone, device to host, the device twin of whenet_op_yuv_to_bgr
+ * ORDER.  `stream` is the caller's hipStream_t (NULL: the default stream).  The library records an event on it, lets its copy
+ * stream wait for that event, runs the kernel, and makes `stream` wait for the kernel's end.  Work enqueued on `stream` BEFORE the
+ * call is seen by the ingest; work enqueued on `stream` AFTER the call may overwrite or free the source; anything else that
+ * writes the source (the host, another stream) must wait until the ticket's collect call has returned.  The host never waits.
+ * WHENET_EINVAL, with the frame's index in whenet_last_error and before a slot is taken or anything is enqueued: a NULL pointer,
+ * a pitch below the row bytes, a side outside 1..8192, a frame count outside 1..16, an unknown format or matrix; a pointer that
+ * hipPointerGetAttributes does not report as hipMemoryTypeDevice memory of the handle's device (host, registered, managed and
+ * other-device memory are refused); a plane whose extent (rows - 1) * pitch + row_bytes leaves the allocation that
+ * hipMemGetAddressRange reports for it.  If the runtime cannot report that range, the extent check alone is skipped.
+ * Not built: BGRA / 4-channel, float or CHW sources, 10-bit surfaces, memory of another GPU, IPC handles, capture of a begin
+ * call into a caller's graph. */
+WHENET_API int whenet_frame_begin_device(whenet_t* h, const uint8_t* d_frame, int pitch, int frame_h, int frame_w, int channel_order,
+                              void* stream, int* ticket);
+WHENET_API int whenet_clip_begin_device(whenet_t* h, const uint8_t* const* d_frames, const int* pitch, int num_frames, const int* frame_h,
+                             const int* frame_w, int channel_order, void* stream, int* ticket);
+WHENET_API int whenet_frame_begin_yuv_device(whenet_t* h, const whenet_yuv_frame_t* frame, void* stream, int* ticket);
+WHENET_API int whenet_clip_begin_yuv_device(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, void* stream, int* ticket);
+WHENET_API int whenet_op_pack_device(whenet_t* h, const uint8_t* const* d_frames, const int* pitch, int num_frames, const int* frame_h,
+                          const int* frame_w, void* stream, uint8_t* const* out);
+WHENET_API int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, void* stream, uint8_t* const* bgr);
+
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
  * recorded on the chain's stream between consecutive kernel launches; a launch's time is
