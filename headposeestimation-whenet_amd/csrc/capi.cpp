@@ -998,6 +998,22 @@ int whenet_front2_static_check(int row, int field, int delta) {
     }
 }
 
+int whenet_front_static_check(int row, int field, int delta) {
+    try {
+        return whenet::front_static_selftest(row, field, delta) == 0 ? WHENET_OK : WHENET_EINVAL;
+    } catch (...) {
+        return WHENET_EINVAL;
+    }
+}
+
+int whenet_pw_static_check(int row, int field, int delta) {
+    try {
+        return whenet::pw_static_selftest(row, field, delta) == 0 ? WHENET_OK : WHENET_EINVAL;
+    } catch (...) {
+        return WHENET_EINVAL;
+    }
+}
+
 int whenet_device_alloc(whenet_t* h, size_t nbytes, void** d_ptr) {
     if (d_ptr == nullptr) return WHENET_EINVAL;
     return guarded(h, [&](whenet::Engine& e) { *d_ptr = e.dev_alloc(nbytes); });

@@ -228,6 +228,12 @@ void Engine::set_option(const std::string& key, long value) {
     } else if (key == "front2_static") {
         WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "front2_static must be 0 (runtime tile geometry everywhere) or 1 (per layer, default)");
         front2_static_ = value != 0;
+    } else if (key == "front_static") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "front_static must be 0 (runtime tile geometry everywhere) or 1 (per layer, default)");
+        front_static_ = value != 0;
+    } else if (key == "pw_static") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "pw_static must be 0 (runtime layer shapes everywhere) or 1 (per layer, default)");
+        pw_static_ = value != 0;
     } else if (key == "stem_fuse") {
         stem_fuse_ = value != 0;
     } else if (key == "act_layout") {
@@ -500,6 +506,30 @@ bool Engine::front2_static(int index) const {
     return front2_static_ && index >= 0 && index <= 16 && WINS[index];
 }
 
+// pw.hip's static-shape form of the project GEMMs (the layer's K, N, HW, tile counts and squeeze-excite sizes as compile-time
+// constants): option pw_static = 1 asks for it on the blocks of the per-layer table, with the default squeeze-excite placement
+// only; launch_pw still runs the generic form where the launch is not a row of its shape table (other batch-dependent blocking,
+// act_layout / pw_staged / se_fuse_tiny, the single-stage entry points with other shapes).  Same bits either way.
+bool Engine::pw_static(int index) const {
+    // [block index]: the blocks whose project layer has a static form (docs/experiments.md section 26 holds the per-layer verdicts)
+    // (one chain of 64 crops, static against generic, us: b2 16.1 -> 13.8, b3 20.8 -> 17.6, b4 13.7 -> 10.6, b7 12.4 -> 11.9,
+    //  b9 12.0 -> 11.6, b13-15 12.9 -> 11.7, b16 15.0 -> 14.0; b8 12.1 -> 11.8 is inside its own spread of 0.31; b12 lost in an
+    //  earlier build; b5, b6, b10, b11 have no static form: profiles/r15/layers_b64.txt)
+    static constexpr bool WINS[17] = {false, false, true, true, true, false, false, true, false, true, false, false, false,
+                                      true, true, true, true};           // blocks 2-4, 7, 9, 13-16
+    return pw_static_ && se_fuse_ == 1 && index >= 0 && index <= 16 && WINS[index];
+}
+
+// front.hip's static-shape form (block 6 of an f16 handle, the one block of the default forward that runs front.hip): option
+// front_static = 1 asks for it on the blocks of the per-layer table; launch_front still runs the generic form where the launch is
+// not the row's layer and plan (512-lane launches of at most 32 crops, WHENET_FRONT_NO_TUNED, WHENET_FRONT_THREADS).  Same bits.
+bool Engine::front_static(int index) const {
+    // (one chain of 64 crops: 18.9 -> 16.4 us, profiles/r15/layers_b64.txt)
+    static constexpr bool WINS[17] = {false, false, false, false, false, false, true, false, false, false, false, false, false,
+                                      false, false, false, false};       // block 6
+    return front_static_ && index >= 0 && index <= 16 && WINS[index];
+}
+
 void* Engine::enqueue_blocks(int first, int last, const View& v, void* cur, int n, hipStream_t s, LaunchRecorder* rec,
                              bool b1_dw_done) {
     const bool fold = fold12_active() && first <= 1 && last >= 2;
@@ -667,7 +697,8 @@ void Engine::enqueue_front(const DevBlock& b, const BlockSchedule& bs, const Vie
         a.xcd_grouped = xcd_grouped(1, n);
         a.plan = b.fplan;
         a.plan.threads = front_threads(b.fplan, n);
-        R(p + "/front", "front", kernel_name_front(dtype_, sp.k, sp.s, a.plan.threads).c_str(), bytes(a.Cin), flops(a.Cin),
+        a.static_form = front_static(sp.index);
+        R(p + "/front", "front", kernel_name_front(dtype_, sp.k, sp.s, a.plan.threads, front_static_row(a, dtype_)).c_str(), bytes(a.Cin), flops(a.Cin),
           [&] { launch_front(a, dtype_, s); });
     }
 }
@@ -785,6 +816,7 @@ void Engine::enqueue_project(const DevBlock& b, const SeFuse& sef, bool se_fused
     a.res = sp.has_skip() ? in : nullptr;
     a.out_blocked = out_blocked;
     a.res_blocked = in_blocked && sp.has_skip();
+    a.static_form = pw_static(sp.index);
     R("b" + std::to_string(sp.index) + "/project", "pw", kernel_name_pw(a, dtype_, pw_impl_, num_cus_).c_str(),
       double(a.M) * (a.K + a.N + (sp.has_skip() ? a.N : 0)) * double(esz()), 2.0 * a.M * a.K * a.N,
       [&] { launch_pw(a, dtype_, pw_impl_, num_cus_, s); });

@@ -412,6 +412,8 @@ class Engine {
     // Layout of the OUTPUT of block `index` (1-based) in a whole forward: true = 16-channel blocks [crop][C/16][HW][16]
     // (DESIGN.md section 2), false = NHWC.  A function of the layer and the options only, never of the batch.
     bool act_blocked(int index) const;
+    bool front_static(int index) const;      // block `index` asks front.hip for its static-shape form (option "front_static")
+    bool pw_static(int index) const;         // block `index` asks pw.hip for the static-shape form of its project GEMM (option "pw_static")
     bool front2_static(int index) const;     // block `index` asks front2.hip for its static-plan form (option "front2_static")
     int act_layout_ = 1;               // option "act_layout": 0 = NHWC everywhere, 1 = the per-layer table, 2 = blocked wherever supported
     struct BlockSchedule {     // which kernels a block runs under the current options
@@ -519,6 +521,8 @@ class Engine {
         return (xcd_map_ & bit) != 0 && (xcd_always_ || n >= 128);     // launch of >= 128 crops; one small forward alone loses 1 % with it
     }
     bool stem_fuse_ = true;     // option "stem_fuse": uint8 input -- the stem conv is computed inside block 1's depthwise kernel (stemdw.hip)
+    bool front_static_ = true;  // option "front_static": front.hip with the layer's geometry as compile-time constants, per layer
+    bool pw_static_ = true;     // option "pw_static": the project GEMMs with the layer's shape as compile-time constants, per layer
     bool front2_static_ = true; // option "front2_static": front2.hip with the tile geometry as compile-time constants, per layer
     bool fold12_ = true;        // option "fold12": block 1's project folded into block 2's expand (f16 + front2.hip on block 2)
     int lanes_ = 2;             // concurrent sub-batch chains per forward (option "lanes"; round 3: 2 -- with the faster

@@ -44,16 +44,80 @@ constexpr int VC = 4;
 // this kernel used to spend a third of its VALU cycles in them.
 __device__ __forceinline__ int fdiv(int q, float rinv) { return int((float(q) + 0.5f) * rinv); }
 
-template <typename T, int K, int S, int NTHR, bool SP = false, bool GATED = false>
+// ---- static layer shape ------------------------------------------------------------------------------------------------
+// Every geometry argument of the kernel below is the same for every launch of a layer.  Block 6 is the one block of the f16
+// forward that still runs this kernel: its static form (ROW >= 0) takes the geometry from a constexpr FShape instead of the
+// arguments, so the divisions, the strip shapes and the LDS offsets fold.  Same body, same bits.  f_static_shape() restates
+// plan_front_candidates()' arithmetic for the row's (CC, TH, NSX, pitch padding); front_static_check() compares it field by
+// field with the launch at the first launch of the shape.
+struct FRow { int k, s, H, Cin, Cexp, CC, TH, NSX, padding, threads; };
+constexpr FRow F_ROWS[] = {
+    {3, 2, 28, 40, 240, 32, 7, 2, 16, 256},      // 0: b6 (front_tuned_f16.inc's plan; 256 lanes: launches of more than 32 crops)
+};
+constexpr int NF_ROWS = int(sizeof(F_ROWS) / sizeof(F_ROWS[0]));
+
+struct FShape {
+    int H, Ho, Cin, Cexp, pad, KSe, NTe;
+    int CC, TH, NSX, tiles_x, tiles_y, EH, EW, EP, w_off;
+    int R, RP;
+    int ntiles, chunks;
+    int k, s, threads, lds_bytes;                // what selects the instantiation, and the launch's LDS size
+};
+
+constexpr FShape f_static_shape(int row) {
+    const FRow t = F_ROWS[row];
+    FShape g{};
+    g.k = t.k;  g.s = t.s;  g.threads = t.threads;
+    g.H = t.H;
+    g.Ho = (t.H + t.s - 1) / t.s;
+    g.Cin = t.Cin;
+    g.Cexp = t.Cexp;
+    const int padt = (g.Ho - 1) * t.s + t.k - t.H;
+    g.pad = padt > 0 ? padt / 2 : 0;
+    g.KSe = (t.Cin + 15) / 16;                   // binary16: 16-deep k-steps
+    g.NTe = (t.Cexp + 31) / 32;
+    g.CC = t.CC < t.Cexp ? t.CC : t.Cexp;
+    g.TH = t.TH;
+    g.NSX = t.NSX;
+    g.tiles_x = g.Ho / P / t.NSX;
+    g.tiles_y = (g.Ho + t.TH - 1) / t.TH;
+    g.EH = (t.TH - 1) * t.s + t.k;
+    g.EW = (t.NSX * P - 1) * t.s + t.k;
+    g.EP = g.CC * 2 + t.padding;
+    const int tile_bytes = g.EH * g.EW * g.EP, red_bytes = 256 * VC * 4;
+    g.w_off = ((tile_bytes > red_bytes ? tile_bytes : red_bytes) + 15) & ~15;
+    g.lds_bytes = g.w_off + t.k * t.k * g.CC * 4;
+    g.R = t.Cin / 4;                             // MBConv6: squeeze-excite on Cin / 4
+    g.RP = (g.R + 3) & ~3;
+    g.ntiles = g.tiles_x * g.tiles_y;
+    g.chunks = (t.Cexp + g.CC - 1) / g.CC;
+    return g;
+}
+
+// ROW: -1 = the geometry is read from the arguments; >= 0 = it is f_static_shape(ROW), folded at compile time (the pointers, n,
+// xcd and wsi stay runtime, the geometry arguments are ignored).  One body: FGEO(f, argument) is the field either way.
+#define FGEO(f, arg) (ROW >= 0 ? sg.f : (arg))
+template <typename T, int K, int S, int NTHR, bool SP = false, bool GATED = false, int ROW = -1>
 __global__ __launch_bounds__(NTHR, 4) void whenet_front_kernel(const T* __restrict__ x, const T* __restrict__ wep,
                                                             const float* __restrict__ be,
                                                             const float* __restrict__ wd,
                                                             const float* __restrict__ bd, T* __restrict__ out,
-                                                            float* __restrict__ rpart, int H, int Ho, int Cin,
-                                                            int Cexp, int pad, int KSe, int NTe, int CC, int TH,
-                                                            int NSX, int tiles_x, int EH, int EW, int EP, int w_off,
-                                                            const float* __restrict__ w1t, int R, int RP, float wsi,
-                                                            const float* __restrict__ in_gate, int ntiles, int chunks, int n, int xcd) {
+                                                            float* __restrict__ rpart, int H_, int Ho_, int Cin_,
+                                                            int Cexp_, int pad_, int KSe_, int NTe_, int CC_, int TH_,
+                                                            int NSX_, int tiles_x_, int EH_, int EW_, int EP_, int w_off_,
+                                                            const float* __restrict__ w1t, int R_, int RP_, float wsi,
+                                                            const float* __restrict__ in_gate, int ntiles_, int chunks_, int n, int xcd) {
+    constexpr FShape sg = f_static_shape(ROW < 0 ? 0 : ROW);
+    static_assert(ROW < 0 || (sg.k == K && sg.s == S && sg.threads == NTHR && sizeof(T) == 2 && !SP && !GATED),
+                  "front: the static shape belongs to another instantiation");
+    const int H = FGEO(H, H_), Ho = FGEO(Ho, Ho_), Cin = FGEO(Cin, Cin_), Cexp = FGEO(Cexp, Cexp_), pad = FGEO(pad, pad_),
+              KSe = FGEO(KSe, KSe_), NTe = FGEO(NTe, NTe_), CC = FGEO(CC, CC_), TH = FGEO(TH, TH_), NSX = FGEO(NSX, NSX_),
+              tiles_x = FGEO(tiles_x, tiles_x_), R = FGEO(R, R_), RP = FGEO(RP, RP_), ntiles = FGEO(ntiles, ntiles_),
+              chunks = FGEO(chunks, chunks_);
+    // The LDS tile's shape stays an argument in both forms (the check still holds it to the row's): as constants the compiler
+    // allocates the static form 120 VGPRs against the generic form's 97; with these four run-time it needs 86 and 35 more
+    // instructions of 1,204 (tools/isa_table.py).
+    const int EH = EH_, EW = EW_, EP = EP_, w_off = w_off_;
     // GATED (SP only, round 6): the expand contracts (in_gate[crop] * x) -- block 2 fed by block 1's depthwise output with block 1's
     // project folded into the expand weights (engine.cpp, option fold12); the gate multiplies the float32 operand before it is split.
     // SP (T = float, WHENET_F32S): the expand products as binary16 hi/lo pairs on the f16 matrix cores (device_math.h PwOps);
@@ -355,7 +419,79 @@ __global__ __launch_bounds__(NTHR, 4) void whenet_front_kernel(const T* __restri
     STAMP(6);
 }
 
-template <typename T, int K, int S, int NTHR, bool SP = false, bool GATED = false>
+}  // namespace
+
+// ---- the static form's host side ---------------------------------------------------------------------------------------
+namespace {
+
+// The first field in which the constexpr shape of a row and a launch's runtime geometry differ, or NULL.
+const char* f_static_mismatch(const FShape& g, const FrontArgs& a) {
+    const FrontPlan& pl = a.plan;
+    struct Field { const char* name; long long want, got; };
+    const Field fields[] = {
+        {"H", g.H, a.H}, {"Ho", g.Ho, a.Ho}, {"Cin", g.Cin, a.Cin}, {"Cexp", g.Cexp, a.Cexp}, {"pad", g.pad, a.pad}, {"KSe", g.KSe, a.KSe},
+        {"NTe", g.NTe, a.NTe}, {"CC", g.CC, pl.CC}, {"TH", g.TH, pl.TH}, {"NSX", g.NSX, pl.NSX}, {"tiles_x", g.tiles_x, pl.tiles_x},
+        {"tiles_y", g.tiles_y, pl.tiles_y}, {"EH", g.EH, pl.EH}, {"EW", g.EW, pl.EW}, {"EP", g.EP, pl.EP}, {"w_off", g.w_off, pl.w_off},
+        {"R", g.R, a.R}, {"RP", g.RP, (a.R + 3) & ~3}, {"ntiles", g.ntiles, pl.tiles_x * pl.tiles_y}, {"chunks", g.chunks, pl.chunks},
+        {"k", g.k, a.k}, {"s", g.s, a.s}, {"threads", g.threads, pl.threads}, {"lds_bytes", g.lds_bytes, (long long)pl.lds_bytes},
+    };
+    static_assert(sizeof(fields) / sizeof(fields[0]) == sizeof(FShape) / sizeof(int), "front: every field of FShape is compared");
+    for (const Field& f : fields)
+        if (f.want != f.got) return f.name;
+    return nullptr;
+}
+
+void f_static_require(const FShape& g, const FrontArgs& a) {
+    const char* bad = f_static_mismatch(g, a);
+    if (bad != nullptr) throw Error(WHENET_EINVAL, std::string("front: the static shape differs from the launch in field ") + bad);
+}
+
+}  // namespace
+
+// The row of F_ROWS whose static form serves this launch, or -1: the caller asks for it (FrontArgs::static_form), the launch is
+// the binary16 form without a gate, and the layer and what DEFINES its plan (CC, TH, NSX, pixel pitch, lanes) are the row's.
+// What plan_front() derives from them is not compared here but checked (front_static_check).
+int front_static_row(const FrontArgs& a, int dtype) {
+    if (!a.static_form || dtype != WHENET_F16 || a.split || a.in_gate != nullptr || a.w1t == nullptr) return -1;
+    for (int r = 0; r < NF_ROWS; ++r) {
+        const FShape g = f_static_shape(r);
+        if (g.k == a.k && g.s == a.s && g.H == a.H && g.Ho == a.Ho && g.Cin == a.Cin && g.Cexp == a.Cexp && g.pad == a.pad &&
+            g.KSe == a.KSe && g.NTe == a.NTe && g.R == a.R && g.CC == a.plan.CC && g.TH == a.plan.TH && g.NSX == a.plan.NSX &&
+            g.EP == a.plan.EP && g.threads == a.plan.threads)
+            return r;
+    }
+    return -1;
+}
+
+void front_static_check(int row, const FrontArgs& a) {
+    WHENET_REQUIRE(row >= 0 && row < NF_ROWS, WHENET_EINVAL, "front: no such row of the static shape table");
+    f_static_require(f_static_shape(row), a);
+}
+
+// For the tests (no GPU): the row's layer as the engine fills its launch (plan_front()'s plan, 256 lanes), against the row's
+// static shape with the field-th int of FShape moved by delta.  Returns 0 when they agree, throws WHENET_EINVAL as a launch would.
+int front_static_selftest(int row, int field, int delta) {
+    WHENET_REQUIRE(row >= 0 && row < NF_ROWS, WHENET_EINVAL, "front: no such row of the static shape table");
+    WHENET_REQUIRE(field >= -1 && field < int(sizeof(FShape) / sizeof(int)), WHENET_EINVAL, "front: no such field");
+    FShape g = f_static_shape(row);
+    const FRow t = F_ROWS[row];
+    FrontArgs a{};
+    a.k = t.k;  a.s = t.s;  a.H = t.H;  a.Ho = ceil_div(t.H, t.s);  a.Cin = t.Cin;  a.Cexp = t.Cexp;
+    const int padt = (a.Ho - 1) * t.s + t.k - t.H;
+    a.pad = padt > 0 ? padt / 2 : 0;
+    a.KSe = ceil_div(t.Cin, 16);
+    a.NTe = ceil_div(t.Cexp, 32);
+    a.R = t.Cin / 4;
+    a.plan = plan_front(WHENET_F16, t.k, t.s, t.H, a.Ho, t.Cexp);
+    a.plan.threads = t.threads;
+    if (field >= 0) reinterpret_cast<int*>(&g)[field] += delta;
+    f_static_require(g, a);
+    return 0;
+}
+
+namespace {
+
+template <typename T, int K, int S, int NTHR, bool SP = false, bool GATED = false, int ROW = -1>
 void launch_t(const FrontArgs& a, hipStream_t stream) {
     const FrontPlan& p = a.plan;
     dim3 grid(unsigned(p.tiles_x * p.tiles_y) * unsigned(p.chunks) * unsigned(a.n));     // 1-D: the kernel deals the workgroups to the XCDs (xcd_unit())
@@ -363,12 +499,19 @@ void launch_t(const FrontArgs& a, hipStream_t stream) {
     static std::atomic<bool> attr[64];           // (zero-initialised, one per instantiation; handles are one per host thread)
     int dev = 0;
     WHENET_HIP_CHECK(hipGetDevice(&dev));
+    if constexpr (ROW >= 0) {                    // the first launch of this shape on this device: constexpr against runtime
+        static std::atomic<bool> checked[64];
+        if (dev >= 0 && dev < 64 && !checked[dev].load(std::memory_order_acquire)) {
+            front_static_check(ROW, a);
+            checked[dev].store(true, std::memory_order_release);
+        }
+    }
     if (p.lds_bytes > 64 * 1024 && dev >= 0 && dev < 64 && !attr[dev].load(std::memory_order_acquire)) {
-        WHENET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(whenet_front_kernel<T, K, S, NTHR, SP, GATED>),
+        WHENET_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(whenet_front_kernel<T, K, S, NTHR, SP, GATED, ROW>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr[dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((whenet_front_kernel<T, K, S, NTHR, SP, GATED>), grid, dim3(NTHR), p.lds_bytes, stream,
+    hipLaunchKernelGGL((whenet_front_kernel<T, K, S, NTHR, SP, GATED, ROW>), grid, dim3(NTHR), p.lds_bytes, stream,
                        static_cast<const T*>(a.x), static_cast<const T*>(SP ? a.weps : a.wep), a.be, a.wd, a.bd,
                        static_cast<T*>(a.out), a.rpart, a.H, a.Ho, a.Cin, a.Cexp, a.pad, SP ? a.KSes : a.KSe, a.NTe, p.CC, p.TH, p.NSX,
                        p.tiles_x, p.EH, p.EW, p.EP, p.w_off, a.w1t, a.R, (a.R + 3) & ~3, a.wsi, a.in_gate, p.tiles_x * p.tiles_y, p.chunks, a.n, a.xcd_grouped ? 1 : 0);
@@ -581,14 +724,17 @@ void launch_front(const FrontArgs& a, int dtype, hipStream_t stream) {
     WHENET_REQUIRE(!a.split || (dtype == WHENET_F32 && a.weps != nullptr && a.KSes == ceil_div(a.Cin, 16)), WHENET_EINVAL,
                    "front: the split-product form needs float32 storage and the split weight images");
     WHENET_REQUIRE(a.in_gate == nullptr || a.split, WHENET_EINVAL, "front: the gated-input form needs the split-product form");
-    if (dtype == WHENET_F16) launch_thr<half_t>(a, stream);
+    const int row = front_static_row(a, dtype);
+    if (row == 0) launch_t<half_t, 3, 2, 256, false, false, 0>(a, stream);       // b6
+    else if (dtype == WHENET_F16) launch_thr<half_t>(a, stream);
     else if (a.split) launch_thr<float, true>(a, stream);
     else launch_thr<float>(a, stream);
 }
 
-std::string kernel_name_front(int dtype, int k, int s, int threads) {
+std::string kernel_name_front(int dtype, int k, int s, int threads, int static_row) {
     return std::string("whenet_front_kernel<") + (dtype == WHENET_F16 ? "_Float16" : "float") + ", " +
-           std::to_string(k) + ", " + std::to_string(s) + ", " + std::to_string(threads) + ">";
+           std::to_string(k) + ", " + std::to_string(s) + ", " + std::to_string(threads) +
+           (static_row >= 0 ? ", false, false, " + std::to_string(static_row) : std::string()) + ">";
 }
 
 }  // namespace whenet

@@ -115,8 +115,13 @@ struct PwArgs {
     bool staged = true;            // K >= 320: activation rows fetched coalesced and staged through LDS (whenet_pw_splitk_staged_kernel)
     // f16 split-K kernels (K >= 320): `out` / `res` in the 16-channel blocked layout [crop][N/16][HW][16]
     bool out_blocked = false, res_blocked = false;
+    bool static_form = false;      // ask for the kernel with the layer's shape as compile-time constants; taken only where the launch
+                                   // is a row of pw.hip's shape table (pw_static_row); same bits either way (engine option "pw_static")
 };
 void launch_pw(const PwArgs& a, int dtype, int impl, int num_cus, hipStream_t stream);
+int pw_static_row(const PwArgs& a, int dtype, int impl, int num_cus);   // the row whose static form launch_pw(a) runs, or -1 (the generic form)
+void pw_static_check(int row, const PwArgs& a, int num_cus);            // throws WHENET_EINVAL unless the row's constexpr shape equals a's, field by field
+int pw_static_selftest(int row, int field, int delta);                  // (tests) the same check on a static shape with one field moved
 
 // ---- head.hip ---------------------------------------------------------------------------
 // GlobalAveragePooling2D + Dense(120|66|66) + softmax-expectation decode + argmax
@@ -227,9 +232,15 @@ struct FrontArgs {
     const float* in_gate = nullptr; // split only: [n][Cin] f32 -- the expand contracts (in_gate[crop] * x): block 2 fed by block 1's
                                     // depthwise output with block 1's project folded into weps (engine.cpp, option fold12)
     bool xcd_grouped = false;       // the channel chunks of a (crop, tile) on one XCD (device_math.h xcd_unit; engine option "xcd_map")
+    bool static_form = false;       // ask for the kernel with the layer's geometry as compile-time constants; taken only where the launch
+                                    // is a row of front.hip's shape table (front_static_row); same bits either way (engine option "front_static")
 };
 void launch_front(const FrontArgs& a, int dtype, hipStream_t stream);
-std::string kernel_name_front(int dtype, int k, int s, int threads);
+// static_row >= 0: whenet_front_kernel<..., false, false, static_row>, the row's geometry as compile-time constants
+std::string kernel_name_front(int dtype, int k, int s, int threads, int static_row = -1);
+int front_static_row(const FrontArgs& a, int dtype);            // the row whose static form launch_front(a) runs, or -1 (the generic form)
+void front_static_check(int row, const FrontArgs& a);           // throws WHENET_EINVAL unless the row's constexpr shape equals a's, field by field
+int front_static_selftest(int row, int field, int delta);       // (tests) the same check on a static shape with one field moved
 
 // ---- front2.hip -------------------------------------------------------------------------
 // f16: the same stage with the depthwise taps on the matrix cores (per-channel Toeplitz products,

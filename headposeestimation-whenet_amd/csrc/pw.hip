@@ -27,6 +27,9 @@
 // adjacent in time: they hit the same XCD's L2 for the shared activation rows.
 //
 // HBM bytes per launch: M*(K + N)*sizeof(T) (+ M*N*sizeof(T) skip) ; FLOPs 2*M*K*N.
+#include <atomic>
+#include <cstring>
+
 #include "device_math.h"
 #include "kernels.h"
 #include "se_device.h"
@@ -40,12 +43,88 @@ namespace whenet {
 
 namespace {
 
+// ---- static layer shapes ------------------------------------------------------------------------------------------------------
+// K, N, HW, KS, NTILES, NCH and the squeeze-excite sizes are the same for every launch of a layer: only M = n * HW (and MT with
+// it) follows the batch.  The f16 project convs of the default forward have a static form of their kernel
+// (the ROW >= 0 instantiations) that takes these fields from a constexpr PwShape instead of the kernel's arguments, so the compiler
+// folds the divisions by HW and NCH, the k-loop's clamps and trip counts, the weight strides and the epilogue's layout branches
+// that otherwise sit in front of a workgroup's first load.  One body serves both forms: same tiles, same k-group ownership, same
+// summation and combine order, same bits.  pw_static_shape() restates what launch_pw() and Engine::pw_args() derive;
+// pw_static_check() compares the two field by field at the first launch of each shape.
+enum { PW_TILE = 0, PW_SPLITK = 1, PW_STAGED = 2 };
+// {K, N, HW, kernel family, B2 (tile kernel: NT), GM, RES, lay (out_blocked | res_blocked << 1), np, R, use}: one row per f16 project
+// layer as the default forward runs it at the flagship batch (64 crops per chain); np and R only where the project computes the
+// gate itself (GM = 2: np = the producer's tiles x chunks partial vectors per crop, R = Cin / 4).  use = 0: no static form is
+// built -- either the compiler allocates it more VGPRs than the layer's generic kernel (tools/isa_table.py: K = 240 tile 120
+// against 108, b10 / b11 staged 220 against 212; same occupancy, but a static form may not cost registers), whatever stays
+// run-time in it, or it measured slower than the generic kernel (docs/experiments.md section 26).
+struct PwRow { int K, N, HW, family, B2, GM, RES, lay, np, R, use; };
+constexpr PwRow PW_ROWS[] = {
+    {96, 24, 3136, PW_TILE, 1, 1, 0, 0, 0, 0, 1},          // 0: b2
+    {144, 24, 3136, PW_TILE, 1, 1, 1, 0, 0, 0, 1},         // 1: b3
+    {144, 40, 784, PW_TILE, 1, 2, 0, 0, 20, 6, 1},         // 2: b4
+    {240, 40, 784, PW_TILE, 1, 2, 1, 0, 16, 10, 0},        // 3: b5
+    {240, 80, 196, PW_TILE, 1, 2, 0, 0, 16, 10, 0},        // 4: b6
+    {480, 80, 196, PW_SPLITK, 2, 1, 1, 0, 0, 0, 1},        // 5: b7, b8
+    {480, 112, 196, PW_SPLITK, 2, 1, 0, 0, 0, 0, 1},       // 6: b9
+    {672, 112, 196, PW_STAGED, 2, 1, 1, 0, 0, 0, 0},       // 7: b10, b11
+    {672, 192, 49, PW_SPLITK, 2, 1, 0, 1, 0, 0, 0},        // 8: b12 (blocked output): measured slower, 10.23 -> 10.55 us at 64 crops
+    {1152, 192, 49, PW_STAGED, 2, 1, 1, 3, 0, 0, 1},       // 9: b13 - b15 (blocked output and skip)
+    {1152, 320, 49, PW_STAGED, 2, 1, 0, 1, 0, 0, 1},       // 10: b16 (blocked output)
+};
+constexpr int NPW_ROWS = int(sizeof(PW_ROWS) / sizeof(PW_ROWS[0]));
+constexpr bool pw_has_static(int row) { return PW_ROWS[row].use != 0; }
+
+struct PwShape {
+    int K, N, HW, KS, NTILES, NCH;
+    int family, B2, GM, RES, lay;
+    int np, R, RP;                    // (GM = 2) SeFuse's sizes; inv_hw is 1 / HW
+};
+
+constexpr PwShape pw_static_shape(int row) {
+    const PwRow t = PW_ROWS[row];
+    PwShape g{};
+    g.K = t.K;  g.N = t.N;  g.HW = t.HW;
+    g.KS = (t.K + 15) / 16;                       // binary16: 16-deep k-steps (snapshot.cpp::pack_pw)
+    g.NTILES = (t.N + 31) / 32;
+    g.NCH = (g.NTILES + t.B2 - 1) / t.B2;         // launch_splitk(): ceil(NTILES / B2); choose_pw(): ceil(NTILES / NT)
+    g.family = t.family;  g.B2 = t.B2;  g.GM = t.GM;  g.RES = t.RES;  g.lay = t.lay;
+    g.np = t.np;  g.R = t.R;  g.RP = (t.R + 3) & ~3;
+    return g;
+}
+// the row's static fields in front of a kernel's arguments (ROW < 0: the arguments)
+#define PW_GEO(f, arg) (ROW >= 0 ? sg.f : (arg))
+
+// (GM = 2) the squeeze-excite sizes of the static form as constants: se_fused_to_lds()'s loops over np and RP then have fixed trips
+template <int ROW>
+__device__ __forceinline__ SeFuse pw_static_se(const SeFuse& se) {
+    constexpr PwShape sg = pw_static_shape(ROW);
+    SeFuse r = se;
+    r.np = sg.np;  r.R = sg.R;  r.RP = sg.RP;
+    r.inv_hw = 1.0f / float(sg.HW);
+    return r;
+}
+template <int ROW, int GM>
+__device__ __forceinline__ decltype(auto) pw_se(const SeFuse& se) {
+    if constexpr (ROW >= 0 && GM == 2) return pw_static_se<ROW>(se);
+    else return (se);
+}
+#define PW_SE(se) pw_se<ROW, GM>(se)
+// Behind the activation requests of the next k-group (static forms only; the generic kernels are untouched): with the k-step
+// skips folded or the k-loop unrolled the trip is straight-line code, and the scheduler would sink these loads to just in front
+// of the LDS stores that wait for them -- the group would no longer travel while the current one is multiplied.  Nothing is
+// moved across this point.  (Staged kernel: fencing the weight requests as well costs 220 VGPRs against the generic 212.)
+#define PW_ISSUED() do { if constexpr (ROW >= 0) __builtin_amdgcn_sched_barrier(0); } while (0)
+
 // Combine of the four waves' partial accumulators + bias / activation / skip / store (both split-K kernels): wave p owns a quarter of
 // the accumulators, receives the other three waves' share through LDS and adds them in wave order ((p0 + p1) + p2) + p3.
-template <typename T, int B2, bool RES, int ACT, bool SP>
+template <typename T, int B2, bool RES, int ACT, bool SP, int ROW = -1>
 __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], float* s_red, int kpart, int lane, int mt, int nt0, int M,
-                                                     int N, int NTILES, const float* __restrict__ bias, const T* __restrict__ res,
-                                                     T* __restrict__ out, float wsi, int HW, int lay) {
+                                                     int N_, int NTILES_, const float* __restrict__ bias, const T* __restrict__ res,
+                                                     T* __restrict__ out, float wsi, int HW_, int lay_) {
+    constexpr PwShape sg = pw_static_shape(ROW < 0 ? 0 : ROW);
+    const int N = PW_GEO(N, N_), NTILES = PW_GEO(NTILES, NTILES_), HW = PW_GEO(HW, HW_), lay = PW_GEO(lay, lay_);
+    constexpr bool FULLT = ROW >= 0 && sg.NTILES % B2 == 0;        // every chunk of the layer is B2 whole tiles
     using OT = T __attribute__((ext_vector_type(4)));
     constexpr int MB = B2, NT = B2;
     constexpr int NACC = MB * NT * 16, SL = NACC / 4;
@@ -54,7 +133,7 @@ __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], fl
     const int f0 = kpart * SL;                       // first flattened accumulator of this wave's slice
     const int own_tile = f0 >> 4, own_mb = own_tile / NT, own_t = own_tile % NT;
     const int own_row = (mt * MB + own_mb) * 32 + (lane & 31);
-    const bool own_valid = own_row < M && nt0 + own_t < NTILES;
+    const bool own_valid = own_row < M && (FULLT || nt0 + own_t < NTILES);
     // lay (PwArgs::out_blocked | res_blocked << 1): that operand is [crop][N/16][HW][16] instead of [row][N].  A lane's four
     // channels stay one 8-byte piece; the 32 rows of a store then fall into 1 KB (8-10 cache lines) instead of 32 lines.
     // Both forms are  base + (n0 >> 4) * s16 + (n0 & 15):  NHWC base = row * N, s16 = 16;  blocked base = crop * N * HW + pix * 16,
@@ -62,10 +141,16 @@ __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], fl
     const size_t row_base = size_t(own_row) * N;
     size_t blk_base = row_base;
     if (lay != 0) {                                  // (uniform) row -> (crop, pixel): float estimate, made exact
-        int crop = int(float(own_row) * __builtin_amdgcn_rcpf(float(HW)));
-        int pix = own_row - crop * HW;
-        if (pix < 0) { --crop; pix += HW; }
-        if (pix >= HW) { ++crop; pix -= HW; }
+        int crop, pix;
+        if constexpr (ROW >= 0) {                    // (a division by a constant: the same quotient)
+            crop = own_row / HW;
+            pix = own_row - crop * HW;
+        } else {
+            crop = int(float(own_row) * __builtin_amdgcn_rcpf(float(HW)));
+            pix = own_row - crop * HW;
+            if (pix < 0) { --crop; pix += HW; }
+            if (pix >= HW) { ++crop; pix -= HW; }
+        }
         blk_base = size_t(crop) * size_t(N) * HW + size_t(pix) * 16;
     }
     const bool out_blk = (lay & 1) != 0, res_blk = (lay & 2) != 0;
@@ -155,11 +240,19 @@ __device__ __forceinline__ void splitk_combine_store(float16v (&acc)[B2][B2], fl
 //     through LDS and runs bias / skip / store for it.
 // GM: 0 = no gate, 1 = gate [n][K] from global memory (block 1, and every block with option se_fuse=0), 2 = the
 // workgroup computes the gate rows of its own crops from the producer's squeeze-excite partial vectors (se_device.h)
-template <typename T, int B2, int GM, bool RES, int ACT, bool SP = false>
+// ROW: -1 = the layer's shape is read from the arguments; >= 0 = it is pw_static_shape(ROW), folded at compile time (the
+// pointers, M, MT and wsi stay runtime, the shape arguments are ignored).  One body: PW_GEO(f, argument) is the field either way.
+template <typename T, int B2, int GM, bool RES, int ACT, bool SP = false, int ROW = -1>
 __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
     const T* __restrict__ A, const T* __restrict__ Wp, const float* __restrict__ bias, const T* __restrict__ gate,
-    const T* __restrict__ res, T* __restrict__ out, int M, int K, int N, int KS, int NTILES, int HW, int MT, int NCH,
-    const SeFuse se, float wsi, int lay) {
+    const T* __restrict__ res, T* __restrict__ out, int M, int K_, int N_, int KS_, int NTILES_, int HW_, int MT, int NCH_,
+    const SeFuse se, float wsi, int lay_) {
+    constexpr PwShape sg = pw_static_shape(ROW < 0 ? 0 : ROW);
+    static_assert(ROW < 0 || (sg.family == PW_SPLITK && sg.B2 == B2 && sg.GM == GM && (sg.RES != 0) == RES && sizeof(T) == 2 && !SP),
+                  "pointwise: the static shape belongs to another instantiation");
+    const int K = PW_GEO(K, K_), N = PW_GEO(N, N_), KS = PW_GEO(KS, KS_), NTILES = PW_GEO(NTILES, NTILES_), HW = PW_GEO(HW, HW_),
+              NCH = PW_GEO(NCH, NCH_), lay = PW_GEO(lay, lay_);
+    constexpr bool FULLT = ROW >= 0 && sg.NTILES % B2 == 0;        // every chunk of the layer is B2 whole tiles
     constexpr bool GATE = GM != 0;
     using OPS = PwOps<T, SP>;
     constexpr int V = OPS::V;                       // k elements per lane and k-step (SP: 8 floats)
@@ -238,7 +331,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
             const int k1c = k1 < KS ? k1 : KS - 1;                     // (wave-uniform)
             const size_t wk = w_lane + size_t(k1c) * NTILES * 64;
 #pragma unroll
-            for (int t = 0; t < NT; ++t) o.w[u][t] = OPS::load_w(Wp, wk + (nt0 + t < NTILES ? t : 0) * 64, w_lo);
+            for (int t = 0; t < NT; ++t) o.w[u][t] = OPS::load_w(Wp, wk + (FULLT || nt0 + t < NTILES ? t : 0) * 64, w_lo);
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) o.a[u][mb] = OPS::load_a(ap[mb] + k1c * 2 * V);
         }
@@ -255,7 +348,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
                 const typename OPS::P pa = OPS::prep(a);
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    if (nt0 + t < NTILES) OPS::step(o.w[u][t], pa, acc[mb][t]);
+                    if (FULLT || nt0 + t < NTILES) OPS::step(o.w[u][t], pa, acc[mb][t]);
             }
         }
     };
@@ -273,7 +366,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
         }
         lds_barrier();
     }
-    if constexpr (GM == 2) se_fused_to_lds<T, 256>(se, crop_lo, ncrop, K, s_gate, s_r);    // (operands already in flight)
+    if constexpr (GM == 2) se_fused_to_lds<T, 256>(PW_SE(se), crop_lo, ncrop, K, s_gate, s_r);    // (operands already in flight)
     STAMP(1);
     for (int ks = kpart; ks < KS; ks += D * U * SK) {
 #pragma unroll
@@ -284,7 +377,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
     }
     STAMP(2);
 
-    splitk_combine_store<T, B2, RES, ACT, SP>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi, HW, lay);
+    splitk_combine_store<T, B2, RES, ACT, SP, ROW>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi, HW, lay);
 }
 
 // Round 5: the same product with the activation rows fetched COALESCED and handed to the matrix cores through LDS.
@@ -300,11 +393,17 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_kernel(
 //     piece q) are both bank-conflict free;
 //   * weights (already linear 1 KB per instruction), gate staging, the combine and the epilogue are the kernel's above.
 // Summation order: wave p's partial sum now runs over its k-GROUPS; the combine order is unchanged -- a function of the layer only.
-template <typename T, int B2, int GM, bool RES, int ACT, bool SP = false>
+template <typename T, int B2, int GM, bool RES, int ACT, bool SP = false, int ROW = -1>
 __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_kernel(
     const T* __restrict__ A, const T* __restrict__ Wp, const float* __restrict__ bias, const T* __restrict__ gate,
-    const T* __restrict__ res, T* __restrict__ out, int M, int K, int N, int KS, int NTILES, int HW, int MT, int NCH,
-    const SeFuse se, float wsi, int lay) {
+    const T* __restrict__ res, T* __restrict__ out, int M, int K_, int N_, int KS_, int NTILES_, int HW_, int MT, int NCH_,
+    const SeFuse se, float wsi, int lay_) {
+    constexpr PwShape sg = pw_static_shape(ROW < 0 ? 0 : ROW);
+    static_assert(ROW < 0 || (sg.family == PW_STAGED && sg.B2 == B2 && sg.GM == GM && (sg.RES != 0) == RES && sizeof(T) == 2 && !SP),
+                  "pointwise: the static shape belongs to another instantiation");
+    const int K = PW_GEO(K, K_), N = PW_GEO(N, N_), KS = PW_GEO(KS, KS_), NTILES = PW_GEO(NTILES, NTILES_), HW = PW_GEO(HW, HW_),
+              NCH = PW_GEO(NCH, NCH_), lay = PW_GEO(lay, lay_);
+    constexpr bool FULLT = ROW >= 0 && sg.NTILES % B2 == 0;        // every chunk of the layer is B2 whole tiles
     constexpr bool GATE = GM != 0;
     using OPS = PwOps<T, SP>;
     constexpr int V = OPS::V;
@@ -411,7 +510,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
             const int k1c = k1 < KS ? k1 : KS - 1;
             const size_t wk = w_lane + size_t(k1c) * NTILES * 64;
 #pragma unroll
-            for (int t = 0; t < NT; ++t) w[s][t] = OPS::load_w(Wp, wk + (nt0 + t < NTILES ? t : 0) * 64, w_lo);
+            for (int t = 0; t < NT; ++t) w[s][t] = OPS::load_w(Wp, wk + (FULLT || nt0 + t < NTILES ? t : 0) * 64, w_lo);
         }
     };
     auto stage = [&](const VT (&an)[NLD]) {
@@ -437,7 +536,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
                 const typename OPS::P pa = OPS::prep(a);
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    if (nt0 + t < NTILES) OPS::step(w[s][t], pa, acc[mb][t]);
+                    if (FULLT || nt0 + t < NTILES) OPS::step(w[s][t], pa, acc[mb][t]);
             }
         }
     };
@@ -538,11 +637,12 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
         }
         lds_barrier();
     }
-    if constexpr (GM == 2) se_fused_to_lds<T, 256>(se, crop_lo, ncrop, K, s_gate, s_r);
+    if constexpr (GM == 2) se_fused_to_lds<T, 256>(PW_SE(se), crop_lo, ncrop, K, s_gate, s_r);
     gate_group(kpart, g0);
     stage(an);
     for (int gi = kpart; gi < NG; gi += 8) {                // two groups per trip: the weight registers swap roles
         issue_a(gi + 4, an);
+        PW_ISSUED();
         issue_w(gi + 4, w1);
         issue_g(gi + 4, g1);
         compute(gi, w0);
@@ -550,6 +650,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
         stage(an);
         if (gi + 4 < NG) {                                  // (wave-uniform)
             issue_a(gi + 8, an);
+            PW_ISSUED();
             issue_w(gi + 8, w0);
             issue_g(gi + 8, g0);
             compute(gi + 4, w1);
@@ -558,7 +659,7 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
         }
     }
     lds_barrier();                                          // every wave is done with its staging region: s_red may overwrite it
-    splitk_combine_store<T, B2, RES, ACT, SP>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi, HW, lay);
+    splitk_combine_store<T, B2, RES, ACT, SP, ROW>(acc, s_red, kpart, lane, mt, nt0, M, N, NTILES, bias, res, out, wsi, HW, lay);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -574,13 +675,19 @@ __global__ __launch_bounds__(256, B2 == 2 ? 2 : 3) void whenet_pw_splitk_staged_
 //     lane stores 16 bytes and a wave-instruction writes whole 128-byte row segments of the
 //     NHWC output (the direct form scatters 8-byte pieces: the write path, not the MFMA, was
 //     what bounded the 6x-expanding layers).
-template <typename T, int NT, int GM, bool RES, int ACT, bool SP = false>
+template <typename T, int NT, int GM, bool RES, int ACT, bool SP = false, int ROW = -1>
 __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict__ A, const T* __restrict__ Wp,
                                                              const float* __restrict__ bias,
                                                              const T* __restrict__ gate,
                                                              const T* __restrict__ res, T* __restrict__ out, int M,
-                                                             int K, int N, int KS, int NTILES, int HW, int MT,
-                                                             int NCH, const SeFuse se, float wsi) {
+                                                             int K_, int N_, int KS_, int NTILES_, int HW_, int MT,
+                                                             int NCH_, const SeFuse se, float wsi) {
+    constexpr PwShape sg = pw_static_shape(ROW < 0 ? 0 : ROW);
+    static_assert(ROW < 0 || (sg.family == PW_TILE && sg.B2 == NT && sg.GM == GM && (sg.RES != 0) == RES && sizeof(T) == 2 && !SP),
+                  "pointwise: the static shape belongs to another instantiation");
+    const int K = PW_GEO(K, K_), N = PW_GEO(N, N_), KS = PW_GEO(KS, KS_), NTILES = PW_GEO(NTILES, NTILES_), HW = PW_GEO(HW, HW_),
+              NCH = PW_GEO(NCH, NCH_);
+    constexpr bool FULLT = ROW >= 0 && sg.NTILES % NT == 0;        // every chunk of the layer is NT whole tiles
     constexpr bool GATE = GM != 0;
     constexpr int TGK = 256;                                // K < 320 here: block 6's 240 is the widest gated layer
     __shared__ __attribute__((aligned(16))) T s_gate[GATE ? 2 * TGK : 8];        // 128 rows touch <= 2 crops (HW >= 196)
@@ -662,7 +769,7 @@ __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict
             const int ks = grp * UK + u;
             const int tj = j >> 6;                          // staged fragment: tile tj (SP: tj >= NT is tile tj - NT of the lo image)
             const int tl = SP && tj >= NT ? tj - NT : tj;
-            const int jc = nt0 + tl < NTILES ? tl * 64 + (j & 63) : (j & 63);
+            const int jc = FULLT || nt0 + tl < NTILES ? tl * 64 + (j & 63) : (j & 63);
             wreg[c] = wsrc[(SP && tj >= NT ? w_lo : 0) + size_t(ks < KS ? ks : KS - 1) * NTILES * 64 + jc];
         }
     };
@@ -670,7 +777,9 @@ __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict
 #pragma unroll
         for (int c = 0; c < CPT; ++c) {
             const int i = c * 256 + tid;
-            if (i < STAGE_VECS) s_w[buf * STAGE_VECS + i] = wreg[c];
+            // (static form: every lane stores, CPT * 256 == STAGE_VECS -- under the lane condition the compiler sinks the stage's
+            //  weight fetch of the unrolled k-loop into this branch and waits for it with vmcnt(0) in front of the barrier)
+            if ((ROW >= 0 && CPT * 256 == STAGE_VECS) || i < STAGE_VECS) s_w[buf * STAGE_VECS + i] = wreg[c];
         }
     };
 
@@ -687,7 +796,7 @@ __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict
         for (int i = tid; i < cnt; i += 256) reinterpret_cast<VT*>(s_gate)[i] = src[i];
     }
     if constexpr (GM == 2)                                  // ... or computed from the producer's squeeze-excite partial vectors
-        se_fused_to_lds<T, 256>(se, crop_lo, row_last / HW - crop_lo + 1, K, s_gate, s_r);
+        se_fused_to_lds<T, 256>(PW_SE(se), crop_lo, row_last / HW - crop_lo + 1, K, s_gate, s_r);
     store_w(0);
     __syncthreads();
 #pragma unroll
@@ -699,13 +808,14 @@ __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict
         fetch_w(grp + 1);
 #pragma unroll
         for (int u = 0; u < UK; ++u) anext[u] = load_raw((grp + 1) * UK + u);
+        PW_ISSUED();                                        // (static: the unrolled groups keep the loop's order and its register use)
         const VT* wl = s_w + (grp & 1) * STAGE_VECS + lane;
 #pragma unroll
         for (int u = 0; u < UK; ++u) {
             if (grp * UK + u < KS) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    if (nt0 + t < NTILES) {
+                    if (FULLT || nt0 + t < NTILES) {
                         typename OPS::W wf;
                         if constexpr (SP) {
                             wf.hi = __builtin_bit_cast(half8, wl[(u * WT + t) * 64]);
@@ -750,7 +860,8 @@ __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = lane + 64 * i;
-            const int r = int((float(idx) + 0.5f) * rvc);                         // idx / vc, exact (see front.hip)
+            // idx / vc, exact (see front.hip); a division by a constant where the layer is one chunk wide
+            const int r = (ROW >= 0 && sg.NCH == 1) ? idx / vcs : int((float(idx) + 0.5f) * rvc);
             sr[i] = r;
             sch[i] = idx - r * vcs;
             if constexpr (RES) {
@@ -763,7 +874,7 @@ __global__ __launch_bounds__(256) void whenet_pw_tile_kernel(const T* __restrict
 #pragma unroll
         for (int tt = 0; tt < TPS; ++tt) {
             const int t = t0 + tt;
-            if (t < NT && nt0 + t < NTILES) {
+            if (t < NT && (FULLT || nt0 + t < NTILES)) {
 #pragma unroll
                 for (int qq = 0; qq < 4; ++qq) {
                     const int n = (nt0 + t) * 32 + 8 * qq + 4 * g;
@@ -966,6 +1077,158 @@ void launch_dtype(const PwArgs& a, int impl, int num_cus, hipStream_t stream) {
     else throw Error(WHENET_EINVAL, "pointwise: unsupported epilogue combination");
 }
 
+// ---- the static form's host side ---------------------------------------------------------------------------------------------
+int pw_gm(const PwArgs& a) { return a.se.rpart != nullptr ? (a.se.w2p != nullptr ? 3 : 2) : (a.gate != nullptr ? 1 : 0); }
+int pw_lay(const PwArgs& a) { return (a.out_blocked ? 1 : 0) | (a.res_blocked ? 2 : 0); }
+
+// The kernel family and register blocking launch_variant() picks for a binary16 launch, and the chunk count it launches with
+struct PwPick { int family, B2, NCH; };
+PwPick pw_pick(const PwArgs& a, int num_cus) {
+    const PwChoice ch = choose_pw(a, num_cus);
+    if (ch.kind != 1) return PwPick{PW_TILE, ch.NT, ch.NCH};
+    const int b2 = use_split2(a.M, a.NTILES) ? 2 : 1;
+    return PwPick{pw_gm(a) == 3 || use_staged(a, false) ? PW_STAGED : PW_SPLITK, b2, ceil_div(a.NTILES, b2)};
+}
+
+// The first field in which the constexpr shape of a row and a launch's runtime fields differ, or NULL.
+const char* pw_static_mismatch(const PwShape& g, const PwArgs& a, int num_cus) {
+    const PwPick pk = pw_pick(a, num_cus);
+    const int gm = pw_gm(a);
+    struct Field { const char* name; long long want, got; };
+    const Field fields[] = {
+        {"K", g.K, a.K}, {"N", g.N, a.N}, {"HW", g.HW, a.HW}, {"KS", g.KS, a.KS}, {"NTILES", g.NTILES, a.NTILES}, {"NCH", g.NCH, pk.NCH},
+        {"family", g.family, pk.family}, {"B2", g.B2, pk.B2}, {"GM", g.GM, gm}, {"RES", g.RES, a.res != nullptr ? 1 : 0}, {"lay", g.lay, pw_lay(a)},
+        {"np", g.np, gm == 2 ? a.se.np : 0}, {"R", g.R, gm == 2 ? a.se.R : 0}, {"RP", g.RP, gm == 2 ? a.se.RP : 0},
+    };
+    static_assert(sizeof(fields) / sizeof(fields[0]) == sizeof(PwShape) / sizeof(int), "pointwise: every field of PwShape is compared");
+    for (const Field& f : fields)
+        if (f.want != f.got) return f.name;
+    if (g.GM == 2) {                                    // the kernel's constant 1 / HW against the engine's, as bits
+        const float want = 1.0f / float(g.HW), got = a.se.inv_hw;
+        if (std::memcmp(&want, &got, sizeof(float)) != 0) return "inv_hw";
+    }
+    return nullptr;
+}
+
+void pw_static_require(const PwShape& g, const PwArgs& a, int num_cus) {
+    const char* bad = pw_static_mismatch(g, a, num_cus);
+    if (bad != nullptr) throw Error(WHENET_EINVAL, std::string("pointwise: the static shape differs from the launch in field ") + bad);
+}
+
+}  // namespace
+
+// The row of PW_ROWS whose static form serves this launch, or -1: the caller asks for it (PwArgs::static_form), the launch is a
+// binary16 MFMA launch, and the layer and what SELECTS its kernel (family, blocking, gate mode, skip, layouts, the producer's
+// partial-vector count) are the row's.  What launch_pw() derives from them is not compared here but checked (pw_static_check).
+int pw_static_row(const PwArgs& a, int dtype, int impl, int num_cus) {
+    if (!a.static_form || dtype != WHENET_F16 || impl != 0 || a.split || a.act != ACT_NONE || a.M <= 0) return -1;
+    const PwPick pk = pw_pick(a, num_cus);
+    const int gm = pw_gm(a), lay = pw_lay(a), resv = a.res != nullptr ? 1 : 0;
+    for (int r = 0; r < NPW_ROWS; ++r) {
+        if (!pw_has_static(r)) continue;
+        const PwShape g = pw_static_shape(r);
+        if (g.K == a.K && g.N == a.N && g.HW == a.HW && g.family == pk.family && g.B2 == pk.B2 && g.GM == gm && g.RES == resv &&
+            g.lay == lay && (gm != 2 || g.np == a.se.np))
+            return r;
+    }
+    return -1;
+}
+
+void pw_static_check(int row, const PwArgs& a, int num_cus) {
+    WHENET_REQUIRE(row >= 0 && row < NPW_ROWS && pw_has_static(row), WHENET_EINVAL, "pointwise: no static form for this row of the shape table");
+    pw_static_require(pw_static_shape(row), a, num_cus);
+}
+
+// For the tests (no GPU): the row's layer as the engine launches it at 64 crops -- restated here from the network's geometry
+// (KS and NTILES as snapshot.cpp packs them, the squeeze-excite sizes from the producer's tile plan) -- against the row's static
+// shape with the field-th int of PwShape moved by delta.  Returns 0 when they agree, throws WHENET_EINVAL as a launch would.
+int pw_static_selftest(int row, int field, int delta) {
+    WHENET_REQUIRE(row >= 0 && row < NPW_ROWS, WHENET_EINVAL, "pointwise: no such row of the shape table");      // (use = 0 rows too)
+    WHENET_REQUIRE(field >= -1 && field < int(sizeof(PwShape) / sizeof(int)), WHENET_EINVAL, "pointwise: no such field");
+    PwShape g = pw_static_shape(row);
+    const PwRow t = PW_ROWS[row];
+    PwArgs a{};
+    a.M = 64 * t.HW;  a.K = t.K;  a.N = t.N;  a.HW = t.HW;  a.act = ACT_NONE;
+    a.KS = ceil_div(t.K, 16);
+    a.NTILES = ceil_div(t.N, 32);
+    a.staged = true;
+    a.static_form = true;
+    const void* some = &g;                                  // (pointers are only compared with NULL)
+    a.gate = t.GM == 1 ? some : nullptr;
+    a.res = t.RES ? some : nullptr;
+    a.out_blocked = (t.lay & 1) != 0;
+    a.res_blocked = (t.lay & 2) != 0;
+    if (t.GM == 2) {
+        // the producers of the three self-gating layers: b4 and b5 run front2.hip, b6 front.hip; {k, s, H, Ho} of the block
+        const int geo[3][4] = {{5, 2, 56, 28}, {5, 1, 28, 28}, {3, 2, 28, 14}};
+        WHENET_REQUIRE(row >= 2 && row <= 4, WHENET_EINVAL, "pointwise: a self-gating row without a producer");
+        const int* e = geo[row - 2];
+        a.se.rpart = static_cast<const float*>(some);
+        if (row < 4) { const Front2Plan p = plan_front2(e[0], e[1], e[2], e[3], t.K);  a.se.np = p.ntiles() * p.chunks; }
+        else { const FrontPlan p = plan_front(WHENET_F16, e[0], e[1], e[2], e[3], t.K);  a.se.np = p.ntiles() * p.chunks; }
+        a.se.R = t.K / 24;                                  // MBConv6: Cexp = 6 Cin, squeeze-excite on Cin / 4
+        a.se.RP = se_padded_r(a.se.R);
+        a.se.inv_hw = 1.0f / float(t.HW);
+    }
+    if (field >= 0) reinterpret_cast<int*>(&g)[field] += delta;
+    pw_static_require(g, a, 256);
+    return 0;
+}
+
+namespace {
+
+struct OncePerDevice {
+    std::atomic<bool> done[64];
+    OncePerDevice() { for (auto& d : done) d.store(false, std::memory_order_relaxed); }
+};
+
+// The static form of row ROW: the instantiation follows from the row (the bodies' static_asserts hold the two together)
+template <int ROW>
+void launch_pw_static_row(const PwArgs& a, int num_cus, hipStream_t stream) {
+    constexpr PwShape g = pw_static_shape(ROW);
+    static OncePerDevice checked;                       // the first launch of this shape on this device: constexpr against runtime
+    int dev = 0;
+    WHENET_HIP_CHECK(hipGetDevice(&dev));
+    if (dev >= 0 && dev < 64 && !checked.done[dev].load(std::memory_order_acquire)) {
+        pw_static_check(ROW, a, num_cus);
+        checked.done[dev].store(true, std::memory_order_release);
+    }
+    const half_t* A = static_cast<const half_t*>(a.a);
+    const half_t* W = static_cast<const half_t*>(a.wp);
+    const half_t* gate = static_cast<const half_t*>(a.gate);
+    const half_t* res = static_cast<const half_t*>(a.res);
+    half_t* out = static_cast<half_t*>(a.out);
+    if constexpr (g.family == PW_TILE) {
+        const int MT = ceil_div(a.M, 128);
+        hipLaunchKernelGGL((whenet_pw_tile_kernel<half_t, g.B2, g.GM, g.RES != 0, ACT_NONE, false, ROW>),
+                           dim3(8 * ceil_div(MT, 8) * g.NCH), dim3(256), 0, stream, A, W, a.bias, gate, res, out, a.M, a.K, a.N, a.KS,
+                           a.NTILES, a.HW, MT, g.NCH, a.se, a.wsi);
+    } else {
+        const int MT = ceil_div(a.M, 32 * g.B2);
+        if constexpr (g.family == PW_STAGED)
+            hipLaunchKernelGGL((whenet_pw_splitk_staged_kernel<half_t, g.B2, g.GM, g.RES != 0, ACT_NONE, false, ROW>),
+                               dim3(8 * ceil_div(MT, 8) * g.NCH), dim3(256), 0, stream, A, W, a.bias, gate, res, out, a.M, a.K, a.N, a.KS,
+                               a.NTILES, a.HW, MT, g.NCH, a.se, a.wsi, g.lay);
+        else
+            hipLaunchKernelGGL((whenet_pw_splitk_kernel<half_t, g.B2, g.GM, g.RES != 0, ACT_NONE, false, ROW>),
+                               dim3(8 * ceil_div(MT, 8) * g.NCH), dim3(256), 0, stream, A, W, a.bias, gate, res, out, a.M, a.K, a.N, a.KS,
+                               a.NTILES, a.HW, MT, g.NCH, a.se, a.wsi, g.lay);
+    }
+}
+
+void launch_pw_static(int row, const PwArgs& a, int num_cus, hipStream_t stream) {
+    switch (row) {
+        case 0: launch_pw_static_row<0>(a, num_cus, stream); break;
+        case 1: launch_pw_static_row<1>(a, num_cus, stream); break;
+        case 2: launch_pw_static_row<2>(a, num_cus, stream); break;
+        case 5: launch_pw_static_row<5>(a, num_cus, stream); break;
+        case 6: launch_pw_static_row<6>(a, num_cus, stream); break;
+        case 9: launch_pw_static_row<9>(a, num_cus, stream); break;
+        case 10: launch_pw_static_row<10>(a, num_cus, stream); break;
+        default: throw Error(WHENET_EINVAL, "pointwise: no static form for this row of the shape table");
+    }
+}
+
 }  // namespace
 
 void launch_pw(const PwArgs& a, int dtype, int impl, int num_cus, hipStream_t stream) {
@@ -987,7 +1250,9 @@ void launch_pw(const PwArgs& a, int dtype, int impl, int num_cus, hipStream_t st
     const bool split = a.split && impl == 0;          // (the scalar check kernel multiplies the f32 weights themselves)
     WHENET_REQUIRE(!a.split || (dtype == WHENET_F32 && a.wps != nullptr && a.KSs == ceil_div(a.K, 16)), WHENET_EINVAL,
                    "pointwise: the split-product form needs float32 storage and the split weight images");
-    if (dtype == WHENET_F16) launch_dtype<half_t>(a, impl, num_cus, stream);
+    const int row = pw_static_row(a, dtype, impl, num_cus);
+    if (row >= 0) launch_pw_static(row, a, num_cus, stream);
+    else if (dtype == WHENET_F16) launch_dtype<half_t>(a, impl, num_cus, stream);
     else if (split) launch_dtype<float, true>(a, impl, num_cus, stream);
     else launch_dtype<float>(a, impl, num_cus, stream);
     WHENET_HIP_CHECK(hipGetLastError());
@@ -998,8 +1263,15 @@ std::string kernel_name_pw(const PwArgs& a, int dtype, int impl, int num_cus) {
     const char* t = dtype == WHENET_F16 ? "_Float16" : "float";
     const char* gate = a.se.rpart ? (a.se.w2p ? "3" : "2") : (a.gate ? "1" : "0");
     const char* res = a.res ? "true" : "false";
-    char buf[96];
-    if (impl == 1) {
+    char buf[128];
+    const int row = pw_static_row(a, dtype, impl, num_cus);
+    if (row >= 0) {
+        const PwShape g = pw_static_shape(row);
+        // (the instantiation's last argument is the row; SP = false in front of it is not spelled: whenet_launch_stat_t::kernel
+        //  holds 63 characters)
+        std::snprintf(buf, sizeof(buf), "whenet_pw_%s_kernel<%s, %d, %s, %s, %d, %d>",
+                      g.family == PW_TILE ? "tile" : (g.family == PW_STAGED ? "splitk_staged" : "splitk"), t, g.B2, gate, res, a.act, row);
+    } else if (impl == 1) {
         std::snprintf(buf, sizeof(buf), "whenet_pw_check_kernel<%s, %s, %s, %d>", t, a.gate ? "true" : "false", res, a.act);
     } else {
         const PwChoice ch = choose_pw(a, num_cus);

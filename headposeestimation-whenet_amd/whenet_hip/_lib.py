@@ -117,6 +117,8 @@ _PROTOS = {
     "whenet_dw_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32 * 12)]),
     "whenet_front_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32 * 12)]),
     "whenet_front2_static_check": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "whenet_pw_static_check": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "whenet_front_static_check": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "whenet_device_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "whenet_device_free": (C.c_int, [_P, _P]),
     "whenet_memcpy_h2d": (C.c_int, [_P, _P, _P, C.c_size_t]),

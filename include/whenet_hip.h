@@ -150,6 +150,16 @@ WHENET_API int whenet_get_info(const whenet_t* h, whenet_info_t* out);
  *                  the form of that kernel whose tile geometry is compile-time constants (the plan of front2_tuned.inc's row; no
  *                  index divisions or LDS offsets computed in front of the workgroup's first load); 0 = the runtime-geometry
  *                  form everywhere.  Shapes and plans outside the table always run the runtime form.  Same bits either way),
+ *          "front_static" (0/1, default 1: block 6 of an f16 handle -- the one block of the default forward that runs front.hip -- uses
+ *                  the form of that kernel whose tile geometry is compile-time constants (the layer's plan of front_tuned_f16.inc);
+ *                  0 = the runtime-geometry form.  Launches of at most 32 crops (512-lane workgroups) and plans outside the table
+ *                  always run the runtime form.  Same bits either way),
+ *          "pw_static" (0/1, default 1: the project 1x1 GEMMs of an f16 handle use, where the per-layer table says so, the form of
+ *                  their kernel whose layer shape -- K, N, the pixels per crop, the tile and chunk counts, the squeeze-excite sizes --
+ *                  is compile-time constants (a row of pw.hip's shape table: no divisions by run-time sizes and no clamps against
+ *                  them in front of a workgroup's first load); 0 = the runtime-shape form everywhere.  Launches outside the table
+ *                  (another blocking at small batches, se_fuse / act_layout / pw_staged other than the defaults) always run the
+ *                  runtime form.  Same bits either way),
  *          "poison" (0/1, default 0, debug: the activation arena is filled with NaN bit patterns before every forward --
  *                  a kernel that reads what the forward did not write shows up in the results),
  *          "lanes" (1..8, default 2: concurrent sub-batch chains per forward, never fewer than 16 crops each),
@@ -644,6 +654,16 @@ WHENET_API int whenet_front_plan(int dtype, int index, int32_t out[12]);
  * (field = -1: nothing moved).  WHENET_OK when they agree; WHENET_EINVAL when they differ (a launch would refuse to run),
  * the row has no static form or there is no such field. */
 WHENET_API int whenet_front2_static_check(int row, int field, int delta);
+
+/* The same for pw.hip's static-shape form of the project GEMMs: row 0..10 of its shape table (b2, b3, b4, b5, b6, b7/b8, b9, b10/b11,
+ * b12, b13-15, b16; also the rows whose static form is not built) as the engine launches the layer at 64 crops, against the row's constexpr shape with its field-th int
+ * (K, N, HW, KS, NTILES, NCH, family, B2, GM, RES, lay, np, R, RP) moved by delta (field = -1: nothing moved). */
+WHENET_API int whenet_pw_static_check(int row, int field, int delta);
+
+/* The same for front.hip's static-shape form: row 0 (block 6) with plan_front()'s plan and 256 lanes, against the row's constexpr
+ * shape with its field-th int (H, Ho, Cin, Cexp, pad, KSe, NTe, CC, TH, NSX, tiles_x, tiles_y, EH, EW, EP, w_off, R, RP, ntiles,
+ * chunks, k, s, threads, lds_bytes) moved by delta. */
+WHENET_API int whenet_front_static_check(int row, int field, int delta);
 
 /* raw device-memory helpers so a host without torch can use the device-pointer form */
 WHENET_API int whenet_device_alloc(whenet_t* h, size_t nbytes, void** d_ptr);
