@@ -846,6 +846,48 @@ int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t* frames, i
     return guarded(h, [&](whenet::Engine& e) { e.op_yuv_to_bgr_device(frames, num_frames, static_cast<hipStream_t>(stream), bgr); });
 }
 
+// ---- pose overlay (overlay.hip, overlay_host.h, engine_post.cpp) ----
+int whenet_overlay_segments(const int32_t rect[4], float yaw, float pitch, float roll, int32_t segments[16], int32_t* flags) {
+    if (rect == nullptr || segments == nullptr) return WHENET_EINVAL;
+    if (!whenet::overlay_rect_in_range(rect)) {
+        g_create_error = "overlay_segments: a window coordinate outside -4096..8192";
+        return WHENET_EINVAL;
+    }
+    const int f = whenet::overlay_segments(rect, 1, double(yaw), double(pitch), double(roll), segments);
+    if (flags) *flags = f;
+    return WHENET_OK;
+}
+
+int whenet_annotate_host(const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects, const int32_t* valid,
+                         const float* ypr, int k, const whenet_surface_t* dst) {
+    try {
+        const char* bad = whenet::overlay_check(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, dst);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("annotate_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "annotate_host: the surface must be host memory (on_device = 0)");
+        whenet::overlay_annotate_host(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, *dst);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
+    }
+}
+
+int whenet_op_annotate(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
+                       const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_annotate: NULL argument");
+        e.op_annotate(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, *dst);
+    });
+}
+
+int whenet_frame_annotate(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream) {
+    return guarded(h, [&](whenet::Engine&) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "frame_annotate: NULL argument");
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "frame_annotate: unknown ticket " + std::to_string(ticket));
+        h->at(size_t(idx)).frame_annotate(ticket / MAX_INFLIGHT_ENGINES, frame_index, *dst, static_cast<hipStream_t>(stream));
+    });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

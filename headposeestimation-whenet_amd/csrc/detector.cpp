@@ -491,6 +491,7 @@ void Engine::frame_detect_heads(int ticket, int out_h, int out_w, const float* a
     slot.n = K;
     slot.det_cap = K;
     slot.frame_ticket = -1;
+    slot.ann_kind = Slot::ANN_DET;
 }
 
 // clip_begin -> clip_detect_heads -> collect_clip: frame_detect_heads over the F frames of a clip (demo_video.py:49-63 with the
@@ -575,6 +576,7 @@ int Engine::clip_detect_heads(int ticket, int out_h, int out_w, const float* anc
     slot.clip_cap = K;
     slot.clip_heads = max_heads;
     slot.frame_ticket = -1;
+    slot.ann_kind = Slot::ANN_CLIP;
     return K;
 }
 

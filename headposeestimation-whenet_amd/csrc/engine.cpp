@@ -1208,6 +1208,8 @@ int Engine::finish_submission(Slot& s, int n) {
     s.n = n;
     s.det_cap = -1;
     s.clip_f = 0, s.clip_cap = -1, s.clip_mixed = false;
+    s.ann_kind = Slot::ANN_NONE, s.ann_mask = 0;
+    s.ann_host.clear();
     s.ticket = next_ticket_++;
     return s.ticket;
 }
@@ -1246,7 +1248,7 @@ void Engine::abandon_submissions() {
     DeviceGuard guard(device_);
     (void)hipStreamSynchronize(stream_);
     if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
-    for (Slot& s : slots_) s.busy = false;
+    for (Slot& s : slots_) s.busy = false, s.ann_host.clear();
 }
 
 void Engine::collect(int ticket, float* ypr, int32_t* argmax, float* logits) {
@@ -1260,6 +1262,7 @@ void Engine::collect(int ticket, float* ypr, int32_t* argmax, float* logits) {
     WHENET_REQUIRE(slot->clip_cap < 0, WHENET_EINVAL,
                    "collect: ticket " + std::to_string(ticket) + " was submitted by clip_detect_heads: collect_clip returns it");
     WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
+    finish_annotations(*slot);
     copy_results_host(Results{ypr, argmax, logits}, slot->host(), slot->n);
     slot->busy = false;
 }

@@ -321,6 +321,18 @@ class Engine {
     void op_pack_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, hipStream_t stream,
                         uint8_t* const* out);
     void op_yuv_to_bgr_device(const whenet_yuv_frame_t* frames, int nframes, hipStream_t stream, uint8_t* const* bgr);
+    // POSE OVERLAY (overlay.hip; the contract is in include/whenet_hip.h).  frame_annotate: between the call that enqueues a ticket's
+    // heads and its collect -- the plan kernel (windows, valid flags and angles where the heads' launches leave them: the crop
+    // plans of submit_frame / frame_heads, the DetRows of frame_detect_heads, the ClipRows + row map of clip_detect_heads) and the
+    // draw kernel go on stream_ behind the forward, slot.done is recorded again behind them.  ENQUEUE-ONLY.
+    //   Device destination: written in place; with `stream` the engine's stream first waits for what the caller enqueued on it (the
+    //   previous reader of the surface) and `stream` then waits for the kernel's end.  Host destination: the kernel writes tight
+    //   planes in the slot's staging (one buffer pair per frame index), one D2H behind it; the collect call copies the rows out.
+    //   Every refusal (WHENET_EINVAL) comes before anything is enqueued and leaves the ticket as it was.
+    // op_annotate: the two kernels alone, host to host.
+    void frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream);
+    void op_annotate(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* rects, const int32_t* valid, const float* ypr,
+                     int k, const whenet_surface_t& dst);
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -352,6 +364,20 @@ class Engine {
         bool clip_mixed = false;         // clip_begin_mixed: frame f is clip_fh[f] x clip_fw[f] and starts clip_off[f] bytes into `frame`
         int clip_fh[MIXED_MAX_FRAMES] = {}, clip_fw[MIXED_MAX_FRAMES] = {};
         size_t clip_off[MIXED_MAX_FRAMES + 1] = {};      // (the last entry: the bytes of the whole clip)
+        // frame_annotate: what the ticket's heads left on the device (ANN_NONE: nothing to annotate -- crops only, no frame uploaded,
+        // or the heads are not enqueued yet), the frames annotated so far, the table of the plan kernel, the event a caller's stream
+        // waits for, and the host destinations that the collect call fills from their staging
+        enum { ANN_NONE = 0, ANN_PLANS = 1, ANN_DET = 2, ANN_CLIP = 3 };
+        int ann_kind = ANN_NONE;
+        unsigned ann_mask = 0;
+        DeviceBuffer ann_table;
+        Event ann_done;
+        struct AnnHost {
+            whenet_surface_t dst;
+            int frame_index, fh, fw;
+        };
+        std::vector<AnnHost> ann_host;
+        StagedBuffer ann_stage[MIXED_MAX_FRAMES];
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -470,6 +496,8 @@ class Engine {
     void check_device_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes) const;
     void ingest_after_caller(Slot& slot, hipStream_t caller);      // caller's stream -> slot.source -> copy stream
     void ingest_done(Slot& slot, hipStream_t caller);              // copy stream -> slot.copied -> caller's stream
+    void finish_annotations(Slot& slot);                            // collect calls, behind their wait: staging -> the callers' host surfaces
+    void check_surface(const char* what, const whenet_surface_t& dst, int fh, int fw) const;      // overlay_check's surface part + memory kind
     void letterbox_results_to_host(size_t nout, uint8_t* d_u8, float* d_f32, uint8_t* canvas_u8, float* image_f32);
     // every frame's plan_layout, F <= letterbox_cache: what a mixed clip needs before anything is enqueued
     void check_mixed_geometry(const char* what, int frames, const int* fh, const int* fw, int out_h, int out_w) const;

@@ -54,7 +54,9 @@ int Engine::submit_frame(const uint8_t* frame, int fh, int fw, int swap_rb, cons
     } else {
         ensure_slot(slot, 1);
     }
-    return finish_submission(slot, k);
+    const int ticket = finish_submission(slot, k);
+    if (k > 0) slot.fh = fh, slot.fw = fw, slot.swap_rb = swap_rb, slot.ann_kind = Slot::ANN_PLANS;      // (k = 0 uploads no frame)
+    return ticket;
 }
 
 void Engine::op_crop_resize(const uint8_t* frame, int fh, int fw, int swap_rb, const int32_t* rects, int k,
@@ -715,6 +717,7 @@ void Engine::frame_heads(int ticket, const int32_t* rects, int k) {
     WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));
     slot.n = k;
     slot.frame_ticket = -1;
+    if (slot.clip_f == 0) slot.ann_kind = Slot::ANN_PLANS;      // (a released clip has nothing to annotate)
 }
 
 // yolo_eval (yolo_v3/model.py:193-232) on host feature maps: H2D, decode + NMS on the device, the selected boxes
@@ -885,6 +888,7 @@ int Engine::collect_detect(int ticket, int capacity, float* boxes, float* scores
                    "collect_detect: capacity " + std::to_string(capacity) + " is below the submission's " + std::to_string(slot->det_cap) +
                        " rows (classes x max_boxes)");
     WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
+    finish_annotations(*slot);
     const DetRows rows(slot->det_cap);
     void* const base = slot->det.h.as<void>();
     const int count = std::max(0, std::min(*rows.count(base), slot->det_cap));
@@ -977,6 +981,7 @@ void Engine::collect_clip(int ticket, int capacity, int* nframes, int32_t* count
                    "collect_clip: capacity " + std::to_string(capacity) + " is below the submission's " + std::to_string(F * K) +
                        " rows (frames x classes x max_boxes)");
     WHENET_HIP_CHECK(hipEventSynchronize(slot->done));
+    finish_annotations(*slot);
     const ClipRows rows(F, K, M);
     void* const base = slot->det.h.as<void>();
     const size_t S = rows.S;
@@ -1059,6 +1064,188 @@ void Engine::op_head_plan(int fh, int fw, const float* boxes, int k, int32_t* re
     WHENET_HIP_CHECK(hipMemcpyAsync(valid, a.valid, size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
     if (plans) WHENET_HIP_CHECK(hipMemcpyAsync(plans, d_plans, plan_bytes, hipMemcpyDeviceToHost, stream_));
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+// ---- pose overlay (overlay.hip; the contract is in engine.h and include/whenet_hip.h) ----
+namespace {
+// a surface's planes laid TIGHT behind one another: plane p starts off[p] bytes in, off[planes] bytes in all
+int tight_surface(int format, int fh, int fw, int rows[3], int row_bytes[3], size_t off[4]) {
+    const int planes = overlay_surface_planes(format, fh, fw, rows, row_bytes);
+    off[0] = 0;
+    for (int p = 0; p < planes; ++p) off[p + 1] = off[p] + size_t(rows[p]) * size_t(row_bytes[p]);
+    return planes;
+}
+OverlayDrawArgs draw_args(const uint8_t* d_frame, int fh, int fw, int channel_order, const int32_t* d_segs, const int32_t* d_flags, int k,
+                          int format, int matrix) {
+    OverlayDrawArgs a{};
+    a.frame = d_frame, a.fh = fh, a.fw = fw, a.channel_order = channel_order;
+    a.segs = d_segs, a.flags = d_flags, a.k = k, a.format = format;
+    if (format != WHENET_SURF_PACKED) WHENET_REQUIRE(bgr2yuv_coeffs(matrix, a.kc), WHENET_EINVAL, "unknown matrix " + std::to_string(matrix));
+    return a;
+}
+}  // namespace
+
+void Engine::check_surface(const char* what, const whenet_surface_t& dst, int fh, int fw) const {
+    const std::string w = what;
+    int rows[3], row_bytes[3];
+    const int planes = overlay_surface_planes(dst.format, fh, fw, rows, row_bytes);
+    WHENET_REQUIRE(planes > 0, WHENET_EINVAL,
+                   w + ": unknown surface format " + std::to_string(dst.format) + " (WHENET_SURF_PACKED, WHENET_YUV_NV12 or WHENET_YUV_I420)");
+    WHENET_REQUIRE(dst.format == WHENET_SURF_PACKED || (dst.matrix >= 0 && dst.matrix < WHENET_YUV_MATRICES), WHENET_EINVAL,
+                   w + ": unknown matrix " + std::to_string(dst.matrix) + " (WHENET_YUV_BT601, _BT709 or _JFIF)");
+    for (int p = 0; p < planes; ++p) {
+        const std::string who = w + ": plane " + std::to_string(p);
+        WHENET_REQUIRE(dst.plane[p] != nullptr, WHENET_EINVAL, who + " is NULL");
+        WHENET_REQUIRE(dst.pitch[p] >= row_bytes[p], WHENET_EINVAL,
+                       who + ": pitch " + std::to_string(dst.pitch[p]) + " is below its row of " + std::to_string(row_bytes[p]) + " bytes");
+        if (dst.on_device) {
+            check_device_plane(who, static_cast<const uint8_t*>(dst.plane[p]), rows[p], dst.pitch[p], row_bytes[p]);
+        } else {
+            hipPointerAttribute_t attr{};
+            const hipError_t e = hipPointerGetAttributes(&attr, dst.plane[p]);
+            if (e != hipSuccess) (void)hipGetLastError();      // (ordinary host memory: the runtime does not know it)
+            WHENET_REQUIRE(e != hipSuccess || attr.type != hipMemoryTypeDevice, WHENET_EINVAL,
+                           who + " is device memory, the surface says on_device = 0");
+        }
+    }
+}
+
+void Engine::op_annotate(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* rects, const int32_t* valid, const float* ypr,
+                         int k, const whenet_surface_t& dst) {
+    DeviceGuard guard(device_);
+    const char* bad = overlay_check(frame, fh, fw, channel_order, rects, valid, ypr, k, &dst);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_annotate: ") + (bad ? bad : ""));
+    WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_annotate: the surface must be host memory (on_device = 0)");
+    check_surface("op_annotate", dst, fh, fw);
+    int rows[3], row_bytes[3];
+    size_t off[4];
+    const int planes = tight_surface(dst.format, fh, fw, rows, row_bytes, off);
+    const size_t fbytes = size_t(fh) * fw * 3, K = size_t(std::max(k, 1));
+    TempBufs tmp;
+    uint8_t* const d_frame = static_cast<uint8_t*>(tmp.get(fbytes));
+    int32_t* const d_rects = static_cast<int32_t*>(tmp.get(K * 4 * sizeof(int32_t)));
+    int32_t* const d_valid = static_cast<int32_t*>(tmp.get(K * sizeof(int32_t)));
+    float* const d_ypr = static_cast<float*>(tmp.get(K * 3 * sizeof(float)));
+    int32_t* const d_segs = static_cast<int32_t*>(tmp.get(K * (OVERLAY_SEG_INTS + 1) * sizeof(int32_t)));
+    int32_t* const d_flags = d_segs + K * OVERLAY_SEG_INTS;
+    std::vector<uint8_t> out(off[planes]);
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_frame, frame, fbytes, hipMemcpyHostToDevice, stream_));
+    if (k > 0) {
+        WHENET_HIP_CHECK(hipMemcpyAsync(d_rects, rects, K * 4 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        if (valid) WHENET_HIP_CHECK(hipMemcpyAsync(d_valid, valid, K * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        WHENET_HIP_CHECK(hipMemcpyAsync(d_ypr, ypr, K * 3 * sizeof(float), hipMemcpyHostToDevice, stream_));
+        OverlayPlanArgs p{};
+        p.rects = d_rects, p.valid = valid ? d_valid : nullptr, p.row = nullptr, p.ypr = d_ypr;
+        p.k = k, p.rect_stride = 4, p.rect_is_size = 0, p.segs = d_segs, p.flags = d_flags;
+        launch_overlay_plan(p, stream_);
+    }
+    // the landing buffer between two guard zones, as the other kernel-alone calls have it: a byte no lane wrote arrives as the sentinel
+    const GuardedOutput d_out(off[planes], stream_);
+    OverlayDrawArgs a = draw_args(d_frame, fh, fw, channel_order, d_segs, d_flags, k, dst.format, dst.matrix);
+    for (int p = 0; p < planes; ++p) a.plane[p] = d_out.frames() + off[p], a.pitch[p] = row_bytes[p];
+    launch_overlay_draw(a, stream_);
+    uint8_t* const one = out.data();
+    const size_t span[2] = {0, off[planes]};
+    d_out.to_host(stream_, span, 1, &one, "op_annotate");
+    for (int p = 0; p < planes; ++p)
+        for (int r = 0; r < rows[p]; ++r)
+            std::memcpy(static_cast<uint8_t*>(dst.plane[p]) + size_t(r) * size_t(dst.pitch[p]), out.data() + off[p] + size_t(r) * row_bytes[p],
+                        size_t(row_bytes[p]));
+}
+
+void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream) {
+    DeviceGuard guard(device_);
+    Slot* found = nullptr;
+    for (Slot& s : slots_)
+        if (s.busy && s.ticket == ticket) found = &s;
+    WHENET_REQUIRE(found != nullptr, WHENET_EINVAL, "frame_annotate: unknown or already collected ticket " + std::to_string(ticket));
+    Slot& slot = *found;
+    WHENET_REQUIRE(slot.frame_ticket != ticket, WHENET_EINVAL,
+                   "frame_annotate: the heads of ticket " + std::to_string(ticket) + " are not enqueued yet (frame_heads, frame_detect_heads "
+                   "or clip_detect_heads first)");
+    WHENET_REQUIRE(slot.ann_kind != Slot::ANN_NONE, WHENET_EINVAL,
+                   "frame_annotate: ticket " + std::to_string(ticket) + " holds no frame with heads (crops only, a released frame, or a "
+                   "submit_frame without heads)");
+    const int F = slot.ann_kind == Slot::ANN_CLIP ? slot.clip_f : 1;
+    WHENET_REQUIRE(frame_index >= 0 && frame_index < F, WHENET_EINVAL,
+                   "frame_annotate: frame index " + std::to_string(frame_index) + " outside 0.." + std::to_string(F - 1));
+    WHENET_REQUIRE((slot.ann_mask & (1u << frame_index)) == 0, WHENET_EINVAL,
+                   "frame_annotate: frame " + std::to_string(frame_index) + " of ticket " + std::to_string(ticket) + " is annotated already");
+    const int k = slot.ann_kind == Slot::ANN_PLANS ? slot.n : (slot.ann_kind == Slot::ANN_DET ? slot.det_cap : slot.clip_cap);
+    WHENET_REQUIRE(k <= OVERLAY_MAX_HEADS, WHENET_EINVAL,
+                   "frame_annotate: " + std::to_string(k) + " head slots per frame, the overlay takes at most " + std::to_string(OVERLAY_MAX_HEADS));
+    const bool mixed = slot.ann_kind == Slot::ANN_CLIP && slot.clip_mixed;
+    const int fh = mixed ? slot.clip_fh[frame_index] : slot.fh, fw = mixed ? slot.clip_fw[frame_index] : slot.fw;
+    const size_t frame_off = mixed ? slot.clip_off[frame_index] : size_t(frame_index) * size_t(fh) * fw * 3;
+    check_surface("frame_annotate", dst, fh, fw);
+    int rows[3], row_bytes[3];
+    size_t off[4];
+    const int planes = tight_surface(dst.format, fh, fw, rows, row_bytes, off);
+    const int channel_order = slot.swap_rb ? WHENET_BGR : WHENET_RGB;
+    // allocations and the events first: nothing is enqueued yet if one of them fails
+    const size_t S = size_t(F) * size_t(std::max(k, 1));
+    slot.ann_table.grow(S * (OVERLAY_SEG_INTS + 1) * sizeof(int32_t));
+    StagedBuffer& stage = slot.ann_stage[frame_index];
+    if (!dst.on_device) stage.h.grow(off[planes]), stage.d.grow(off[planes]);
+    if (!slot.ann_done) slot.ann_done.create();
+    if (dst.on_device && stream != nullptr && !slot.source) slot.source.create();
+    int32_t* const d_segs = slot.ann_table.as<int32_t>() + size_t(frame_index) * size_t(k) * OVERLAY_SEG_INTS;
+    int32_t* const d_flags = slot.ann_table.as<int32_t>() + S * OVERLAY_SEG_INTS + size_t(frame_index) * size_t(k);
+    OverlayDrawArgs a = draw_args(slot.frame.d.as<uint8_t>() + frame_off, fh, fw, channel_order, d_segs, d_flags, k, dst.format, dst.matrix);
+    for (int p = 0; p < planes; ++p) {
+        a.plane[p] = dst.on_device ? static_cast<uint8_t*>(dst.plane[p]) : stage.d.as<uint8_t>() + off[p];
+        a.pitch[p] = dst.on_device ? dst.pitch[p] : row_bytes[p];
+    }
+    // The frame was written on the copy stream (H2D, pack or conversion kernel) behind slot.copied.  The calls that enqueue heads
+    // make stream_ wait for that event -- but frame_heads with k = 0 enqueues nothing and waits for nothing, and its frame is
+    // annotated all the same: the wait is made here for every form (an event already waited for costs nothing).
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
+    if (k > 0) {
+        OverlayPlanArgs p{};
+        p.ypr = slot.dev().ypr, p.k = k, p.segs = d_segs, p.flags = d_flags;
+        if (slot.ann_kind == Slot::ANN_PLANS) {
+            p.rects = slot.plan.d.as<int32_t>(), p.rect_stride = CROP_PLAN_INTS, p.rect_is_size = 1;
+        } else if (slot.ann_kind == Slot::ANN_DET) {
+            const DetRows r(slot.det_cap);
+            p.rects = r.rects(slot.det.d.as<void>()), p.valid = r.valid(slot.det.d.as<void>()), p.rect_stride = 4;
+        } else {
+            const ClipRows r(slot.clip_f, slot.clip_cap, slot.clip_heads);
+            const size_t first = size_t(frame_index) * size_t(k);
+            p.rects = r.rects(slot.det.d.as<void>()) + first * 4, p.valid = r.valid(slot.det.d.as<void>()) + first;
+            p.row = r.row(slot.det.d.as<void>()) + first, p.rect_stride = 4;
+        }
+        launch_overlay_plan(p, stream_);
+    }
+    if (dst.on_device && stream != nullptr) {      // the surface's previous reader on the caller's stream goes first
+        WHENET_HIP_CHECK(hipEventRecord(slot.source, stream));
+        WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.source, 0));
+    }
+    launch_overlay_draw(a, stream_);
+    if (dst.on_device) {
+        if (stream != nullptr) {
+            WHENET_HIP_CHECK(hipEventRecord(slot.ann_done, stream_));
+            WHENET_HIP_CHECK(hipStreamWaitEvent(stream, slot.ann_done, 0));
+        }
+    } else {
+        WHENET_HIP_CHECK(hipMemcpyAsync(stage.h.as<void>(), stage.d.as<void>(), off[planes], hipMemcpyDeviceToHost, stream_));
+        slot.ann_host.push_back({dst, frame_index, fh, fw});
+    }
+    WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));      // the collect call waits for the overlay as well
+    slot.ann_mask |= 1u << frame_index;
+}
+
+void Engine::finish_annotations(Slot& slot) {
+    for (const Slot::AnnHost& h : slot.ann_host) {
+        int rows[3], row_bytes[3];
+        size_t off[4];
+        const int planes = tight_surface(h.dst.format, h.fh, h.fw, rows, row_bytes, off);
+        const uint8_t* src = slot.ann_stage[h.frame_index].h.as<uint8_t>();
+        for (int p = 0; p < planes; ++p)
+            for (int r = 0; r < rows[p]; ++r)
+                std::memcpy(static_cast<uint8_t*>(h.dst.plane[p]) + size_t(r) * size_t(h.dst.pitch[p]), src + off[p] + size_t(r) * row_bytes[p],
+                            size_t(row_bytes[p]));
+    }
+    slot.ann_host.clear();
 }
 
 }  // namespace whenet

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "overlay_host.h"
 
 namespace whenet {
 
@@ -590,6 +591,35 @@ struct PackFrames {
     PackFrame f[MIXED_MAX_FRAMES];
 };
 void launch_frame_pack(uint8_t* d_out, PackFrames clip, hipStream_t stream);
+
+// ---- overlay.hip ------------------------------------------------------------------------
+// The pose overlay (include/whenet_hip.h, POSE OVERLAY; the arithmetic is overlay_host.h's).  Plan: head i of k (<= 1024: the slots
+// of a clip) takes its window from rects + i * rect_stride -- (y0, x0, y1, x1), or a crop plan's {y0, x0, h, w} with rect_is_size --
+// its valid flag (nullptr: 1) and the angles of forward row row[i] (nullptr: row i; a negative row paints nothing), and writes
+// segs [k][16] and flags [k].  Draw: reads the tight frame [fh][fw][3] and the table of k <= 256 heads, writes the surface's planes
+// (device memory, any alignment, their own pitches).
+struct OverlayPlanArgs {
+    const int32_t* rects;
+    const int32_t* valid;
+    const int32_t* row;
+    const float* ypr;
+    int k, rect_stride, rect_is_size;
+    int32_t* segs;
+    int32_t* flags;
+};
+struct OverlayDrawArgs {
+    const uint8_t* frame;
+    int fh, fw, channel_order;
+    const int32_t* segs;
+    const int32_t* flags;
+    int k;
+    uint8_t* plane[3];
+    int pitch[3];
+    int format;
+    Bgr2YuvCoeffs kc;
+};
+void launch_overlay_plan(const OverlayPlanArgs& a, hipStream_t stream);
+void launch_overlay_draw(const OverlayDrawArgs& a, hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16

@@ -42,6 +42,11 @@ class YuvFrameC(C.Structure):
     _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("format", C.c_int), ("matrix", C.c_int), ("h", C.c_int), ("w", C.c_int)]
 
 
+class SurfaceC(C.Structure):
+    """whenet_surface_t: a destination of the pose overlay (packed pixels, NV12 or I420; host or device memory)."""
+    _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("format", C.c_int), ("matrix", C.c_int), ("on_device", C.c_int)]
+
+
 _PROTOS = {
     "whenet_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_P)]),
     "whenet_create_from_memory": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -107,6 +112,10 @@ _PROTOS = {
     "whenet_clip_begin_yuv_device": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, _P, C.POINTER(C.c_int)]),
     "whenet_op_pack_device": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, _P, _P, _P, C.POINTER(_P)]),
     "whenet_op_yuv_to_bgr_device": (C.c_int, [_P, C.POINTER(YuvFrameC), C.c_int, _P, C.POINTER(_P)]),
+    "whenet_overlay_segments": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, _P, C.POINTER(C.c_int32)]),
+    "whenet_annotate_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC)]),
+    "whenet_op_annotate": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC)]),
+    "whenet_frame_annotate": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SurfaceC), _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -407,6 +416,51 @@ def yuv_to_bgr_host(desc: YuvFrameC) -> np.ndarray:
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace") if out.size else "yuv_to_bgr_host: frame 0 is empty")
     return out
+
+
+SURF_PACKED = 2                                # WHENET_SURF_PACKED, beside YUV_NV12 / YUV_I420
+MAX_OVERLAY_HEADS = 256
+
+
+def overlay_segments(rect, yaw: float, pitch: float, roll: float):
+    """The segments of one head (include/whenet_hip.h, POSE OVERLAY): window (y0, x0, y1, x1) and float32 angles in degrees ->
+    (int32 [16] = x0, y0, x1, y1 of the rectangle, then P and Q of the X, Y and Z axis as (x, y) pairs, flags: 1 rectangle | 2 axes).
+    Pure host arithmetic inside the library (no GPU needed)."""
+    lib = load()
+    r = np.ascontiguousarray(rect, np.int32).reshape(4)
+    seg = np.empty(16, np.int32)
+    flags = C.c_int32(0)
+    rc = lib.whenet_overlay_segments(_ptr(r), float(np.float32(yaw)), float(np.float32(pitch)), float(np.float32(roll)), _ptr(seg), C.byref(flags))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return seg, int(flags.value)
+
+
+def overlay_heads(rects, valid, ypr):
+    """The head arrays of an annotate call: rects int32 [k,4], valid int32 [k] or None, ypr float32 [k,3], k = 0..256."""
+    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    ypr = np.ascontiguousarray(ypr, np.float32).reshape(-1, 3)
+    if valid is not None:
+        valid = np.ascontiguousarray(valid, np.int32).reshape(-1)
+    k = rects.shape[0]
+    if ypr.shape[0] != k or (valid is not None and valid.shape[0] != k):
+        raise ValueError(f"annotate: {k} windows, {ypr.shape[0]} angle rows" + ("" if valid is None else f", {valid.shape[0]} valid flags"))
+    if k > MAX_OVERLAY_HEADS:
+        raise ValueError(f"annotate: {k} heads, the overlay takes at most {MAX_OVERLAY_HEADS}")
+    return rects, valid, ypr
+
+
+def annotate_host(frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: bool = True) -> None:
+    """`whenet_annotate_host`: the overlay as pure host arithmetic inside the library (no GPU needed), written into a host surface."""
+    lib = load()
+    frame = np.ascontiguousarray(frame, np.uint8)
+    if frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError(f"frame must be uint8 [H,W,3], got {frame.shape}")
+    rects, valid, ypr = overlay_heads(rects, valid, ypr)
+    rc = lib.whenet_annotate_host(_ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects), _ptr(valid), _ptr(ypr),
+                                  rects.shape[0], C.byref(surface))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
 
 
 def normalise_lut() -> np.ndarray:
@@ -1017,6 +1071,20 @@ class Handle:
         out = np.empty((n, Ho, Wo, c), np.float32)
         self._check(self._lib.whenet_op_dpool(self._h, _ptr(x), n, H, W, c, int(stride), _ptr(out)))
         return out
+
+    def op_annotate(self, frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: bool = True) -> None:
+        """`whenet_op_annotate`: the overlay kernels alone, host to host (works on a postproc handle)."""
+        frame = np.ascontiguousarray(frame, np.uint8)
+        if frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError(f"frame must be uint8 [H,W,3], got {frame.shape}")
+        rects, valid, ypr = overlay_heads(rects, valid, ypr)
+        self._check(self._lib.whenet_op_annotate(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects),
+                                                 _ptr(valid), _ptr(ypr), rects.shape[0], C.byref(surface)))
+
+    def frame_annotate(self, ticket: int, frame_index: int, surface: SurfaceC, stream=None) -> None:
+        """`whenet_frame_annotate`: enqueue the annotated frame of a ticket whose heads are enqueued.  A host surface is complete
+        when the ticket's collect call returns: the caller keeps its memory alive until then."""
+        self._check(self._lib.whenet_frame_annotate(self._h, int(ticket), int(frame_index), C.byref(surface), _stream(stream)))
 
     def collect(self, ticket: int, n: int, want_logits: bool = False):
         ypr = np.empty((n, 3), np.float32)

@@ -102,6 +102,8 @@ class FramePipeline:
         self._detector = None
         self._begun = None         # (ticket, frame_h, frame_w) of the frame begun last, until its heads are enqueued
         self._begun_clip = None    # (ticket, frames) of the clip begun last, until detect_heads_clip
+        self._last_sizes = None    # (h, w) of every frame of the submission begun last: what annotate() checks its destination against
+        self._annotated = None     # the ticket annotated last
 
     def __enter__(self):
         return self
@@ -134,6 +136,7 @@ class FramePipeline:
             raise ValueError(f"frame must be uint8 [H,W,3], got {frame.dtype} {frame.shape}")
         rects = _lib.frame_rects(frame.shape[0], frame.shape[1], bboxes)
         ticket = self._h.submit_frame(frame, rects, bgr=self._bgr)
+        self._last_sizes = [frame.shape[:2]]
         self._pending.append((ticket, rects, 0))
 
     def begin(self, frame: np.ndarray, stream=None) -> None:
@@ -157,12 +160,14 @@ class FramePipeline:
             f = _lib.device_frame(frame)
             ticket = self._h.frame_begin_device(f, bgr=self._bgr, stream=stream)
             self._begun = (ticket, f.h, f.w)
+            self._last_sizes = [(f.h, f.w)]
             return
         frame = np.asarray(frame)
         if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
             raise ValueError(f"frame must be uint8 [H,W,3], got {frame.dtype} {frame.shape}")
         ticket = self._h.frame_begin(frame, bgr=self._bgr)
         self._begun = (ticket, frame.shape[0], frame.shape[1])
+        self._last_sizes = [frame.shape[:2]]
 
     def begin_clip(self, frames, stream=None) -> None:
         """A clip, step 1: upload F frames (1..16) of ONE size, a uint8 [F,H,W,3] array or a list of uint8 [H,W,3] frames (stacked
@@ -178,10 +183,12 @@ class FramePipeline:
         if _lib.any_on_device(frames):
             items = _lib.device_frames(frames, one_size=True)
             self._begun_clip = (self._h.clip_begin_device(items, bgr=self._bgr, stream=stream), len(items))
+            self._last_sizes = [(f.h, f.w) for f in items]
             return
         frames = _lib.clip_u8(frames)
         ticket = self._h.clip_begin(frames, bgr=self._bgr)
         self._begun_clip = (ticket, frames.shape[0])
+        self._last_sizes = [frames.shape[1:3]] * frames.shape[0]
 
     def begin_clip_mixed(self, frames, stream=None) -> None:
         """A clip of frames of DIFFERENT sizes (several cameras, several files), step 1: upload a list of 1..16 uint8 [H_i,W_i,3]
@@ -197,10 +204,12 @@ class FramePipeline:
         if _lib.any_on_device(frames):
             items = _lib.device_frames(frames)
             self._begun_clip = (self._h.clip_begin_device(items, bgr=self._bgr, stream=stream), len(items))
+            self._last_sizes = [(f.h, f.w) for f in items]
             return
         frames = _lib.mixed_u8(frames)
         ticket = self._h.clip_begin_mixed(frames, bgr=self._bgr)
         self._begun_clip = (ticket, len(frames))
+        self._last_sizes = [f.shape[:2] for f in frames]
 
     def _check_can_begin(self) -> None:
         if self._begun is not None:
@@ -221,6 +230,7 @@ class FramePipeline:
             raise ValueError(f"begin_yuv takes a whenet_hip.yuv.YUVFrame, got {type(frame).__name__}")
         ticket = self._h.frame_begin_yuv_device(frame, stream=stream) if frame.on_device else self._h.frame_begin_yuv(frame)
         self._begun = (ticket, frame.h, frame.w)
+        self._last_sizes = [(frame.h, frame.w)]
 
     def begin_clip_yuv(self, frames, stream=None) -> None:
         """A clip from the planes of 1..16 `YUVFrame`s, each with its own format and matrix: frames of one size make a clip as
@@ -240,6 +250,7 @@ class FramePipeline:
                              str([i for i, f in enumerate(frames) if not f.on_device]) + " are host frames")
         ticket = self._h.clip_begin_yuv_device(frames, stream=stream) if frames[0].on_device else self._h.clip_begin_yuv(frames)
         self._begun_clip = (ticket, len(frames))
+        self._last_sizes = [(f.h, f.w) for f in frames]
 
     def _begun_frame(self, what: str):
         """The frame begun last, for the calls that work on ONE frame."""
@@ -367,6 +378,55 @@ class FramePipeline:
         k = rects.shape[0]
         ypr, _, _ = self._h.collect(ticket, k)
         return rects, ypr[:, 0].copy(), ypr[:, 1].copy(), ypr[:, 2].copy()
+
+    def annotate(self, out, stream=None) -> None:
+        """The annotated frame of the frame submitted last -- every head's window as a rectangle and its pose as three axes
+        (demo_video.py:26-29, utils.py:13-43; `whenet_hip.overlay`) -- enqueued behind its forward; returns without waiting.  Call
+        it once, after `submit()`, `heads()` or `detect_heads()`, before the next `begin()` and before that frame's `collect()`.
+        `out`: a writable uint8 [H,W,3] numpy array (complete when the frame's `collect()` returns), a uint8 [H,W,3] device array
+        with inner strides (3, 1), or a `YUVFrame` (NV12 / I420 with its matrix) whose planes are writable host or device arrays.
+        The caller keeps a destination alive until that `collect()`: nothing here holds a reference.  A device destination is
+        written in place: with `stream` (an integer stream handle) the kernel waits for what was enqueued on it before the call
+        and work enqueued on it afterwards sees the annotated surface; without it the surface is complete when `collect()`
+        returns.  Anything else -- a read-only array, another shape, CHW, float -- is a ValueError, never a silent copy.  The
+        values `collect()` returns are unchanged."""
+        from .overlay import surface_of
+        if not self._pending or self._pending[-1][1] is _CLIP:
+            raise ValueError("annotate: no frame with its heads enqueued (submit(), heads() or detect_heads() first; a clip takes "
+                             "annotate_clip())")
+        if self._begun is not None or self._begun_clip is not None:
+            raise ValueError("annotate: another frame or clip was begun since: annotate() follows the heads of the frame it paints, "
+                             "before the next begin()")
+        ticket = self._pending[-1][0]
+        if self._annotated == ticket:
+            raise ValueError("annotate: the frame submitted last is annotated already")
+        (h, w), = self._last_sizes
+        surface, _ = surface_of(out, int(h), int(w))
+        self._h.frame_annotate(ticket, 0, surface, stream=stream)
+        self._annotated = ticket
+
+    def annotate_clip(self, outs, stream=None) -> None:
+        """`annotate()` for the clip submitted last (after `detect_heads_clip()`, before its `collect_clip()`): `outs` holds one
+        destination per frame of the clip, each as in `annotate()`; `None` leaves a frame out."""
+        from .overlay import surface_of
+        if not self._pending or self._pending[-1][1] is not _CLIP:
+            raise ValueError("annotate_clip: no clip with its heads enqueued (detect_heads_clip() first)")
+        if self._begun is not None or self._begun_clip is not None:
+            raise ValueError("annotate_clip: another frame or clip was begun since: annotate_clip() follows detect_heads_clip(), "
+                             "before the next begin")
+        ticket = self._pending[-1][0]
+        if self._annotated == ticket:
+            raise ValueError("annotate_clip: the clip submitted last is annotated already")
+        sizes = self._last_sizes
+        outs = list(outs)
+        if len(outs) != len(sizes):
+            raise ValueError(f"annotate_clip: the clip has {len(sizes)} frames, got {len(outs)} destinations")
+        surfaces = [None if o is None else surface_of(o, int(h), int(w), f"outs[{i}]")[0] for i, (o, (h, w)) in enumerate(zip(outs, sizes))]
+        for i, surface in enumerate(surfaces):      # (every destination is checked before the first is enqueued)
+            if surface is not None:
+                self._h.frame_annotate(ticket, i, surface, stream=stream)
+        self._annotated = ticket                   # (after the last call: a clip the library refused part-way can be annotated again,
+                                                   #  the library itself refuses the frames that are done)
 
     def process(self, frame: np.ndarray, bboxes):
         """Synchronous form: one frame in, its heads' angles out."""

@@ -72,12 +72,25 @@ def _device_plane(a, rows: int, row_bytes: int, name: str) -> "_lib.DeviceView":
     return _lib.DeviceView(v.ptr, shape, strides, v.owner)
 
 
+def _array_writable(a) -> bool:
+    """Whether a plane's memory may be written: numpy's `writeable` flag, or the read-only flag of `__cuda_array_interface__` (of
+    the owner, for a `_lib.DeviceView`: a view carries no flag of its own)."""
+    if isinstance(a, _lib.DeviceView):
+        if a.owner is None:
+            return True
+        a = a.owner
+    if _lib.is_device_array(a):
+        data = a.__cuda_array_interface__.get("data", (0, True))
+        return not bool(data[1])
+    return bool(np.asarray(a).flags.writeable)
+
+
 class YUVFrame:
     """The planes of one 4:2:0 frame of h x w luma samples: `planes` (2 arrays for NV12: Y, interleaved UV; 3 for I420: Y, U, V),
     their byte `pitches`, `format`, `matrix` (codes of include/whenet_hip.h), `h`, `w`.  The chroma planes have (h + 1) // 2 rows of
     (w + 1) // 2 samples."""
 
-    def __init__(self, planes, format, matrix, h: int, w: int):
+    def __init__(self, planes, format, matrix, h: int, w: int, _writable=None):
         self.format = _code(FORMATS, format, "format")
         self.matrix = _code(MATRICES, matrix, "matrix")
         self.h, self.w = int(h), int(w)
@@ -94,6 +107,9 @@ class YUVFrame:
             raise ValueError("the planes of a frame are all in device memory or all in host memory, got " +
                              ", ".join(f"{n}: {'device' if d else 'host'}" for (_, _, n), d in zip(shapes, on_device)))
         self.on_device = all(on_device)       # the planes are device memory (`_lib.DeviceView`s), not numpy arrays
+        # whether the memory behind every plane may be written (a destination of `FramePipeline.annotate`): asked of the arrays as
+        # they were handed in -- the views kept in `planes` are read-only whatever their memory is
+        self.writable = bool(_writable) if _writable is not None else all(_array_writable(a) for a in planes)
         if self.on_device:
             self.planes = tuple(_device_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
         else:
@@ -132,6 +148,7 @@ class YUVFrame:
         if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
             raise ValueError(f"frame is {h} x {w}: sides must be 1..{MAX_SIDE}")
         dev = None
+        writable = _array_writable(buf) if _lib.is_device_array(buf) or isinstance(buf, np.ndarray) else not memoryview(buf).readonly
         if _lib.is_device_array(buf):
             dev = _lib.device_view(buf, "buffer")
             size, acc = int(np.prod(dev.shape, dtype=np.int64)), 1
@@ -169,7 +186,7 @@ class YUVFrame:
         planes = [view(0, h, w, pitch)]
         for i in range(nchroma):
             planes.append(view(pitch * h + i * cpitch * ch, ch, crow, cpitch))
-        return cls(planes, fmt, matrix, h, w)
+        return cls(planes, fmt, matrix, h, w, _writable=writable)
 
     def descriptor(self) -> "_lib.YuvFrameC":
         """The whenet_yuv_frame_t of this frame (it points into the planes: keep the frame alive while it is used)."""

@@ -45,7 +45,9 @@ extern "C" {
  * (still 6 -- clips: whenet_clip_begin / whenet_clip_detect_heads / whenet_collect_clip, whenet_op_letterbox_batch,
  * whenet_yolo_eval_batch, whenet_op_head_compact.  Additions only.)
  * (still 6 -- YUV 4:2:0 ingest: whenet_yuv_frame_t, whenet_yuv_to_bgr_host, whenet_op_yuv_to_bgr, whenet_frame_begin_yuv,
- * whenet_clip_begin_yuv.  Additions only.) */
+ * whenet_clip_begin_yuv.  Additions only.)
+ * (still 6 -- pose overlay: whenet_surface_t, whenet_overlay_segments, whenet_annotate_host, whenet_op_annotate,
+ * whenet_frame_annotate.  Additions only.) */
 #define WHENET_ABI_VERSION 6
 #define WHENET_API __attribute__((visibility("default")))
 
@@ -598,6 +600,99 @@ WHENET_API int whenet_clip_begin_yuv_device(whenet_t* h, const whenet_yuv_frame_
 WHENET_API int whenet_op_pack_device(whenet_t* h, const uint8_t* const* d_frames, const int* pitch, int num_frames, const int* frame_h,
                           const int* frame_w, void* stream, uint8_t* const* out);
 WHENET_API int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t* frames, int num_frames, void* stream, uint8_t* const* bgr);
+
+/* ---- POSE OVERLAY: the annotated frame, produced on the device (additions to ABI 6).  demo_video.py:26-29 draws, for every head,
+ * `cv2.rectangle` of its window and `draw_axis` (utils.py:13-43: three `cv2.line`s from the window's centre), then writes the frame
+ * out (demo_video.py:60).  The frame, the windows and the angles are in device memory when the forward ends, so the annotated
+ * frame is produced there (csrc/overlay.hip) -- into a host array, or into a pitched BGR / NV12 / I420 surface in device memory
+ * for an encoder.  Built of the reference's drawing: draw_axis and the rectangle of process_detection.  Not built: putText labels,
+ * thickness / colour options, 10-bit surfaces.
+ *
+ * The overlay, integers only.
+ * SEGMENTS OF A HEAD.  Inputs: the window (y0, x0, y1, x1) as whenet_frame_rects / the collect calls return it, and the float32
+ * angles yaw, pitch, roll in degrees.  In double precision tdx = (x0 + x1) / 2, tdy = (y0 + y1) / 2, size = (x1 - x0) // 2 (floor);
+ * the angles are widened to double and go through exactly the expressions of utils.py:15-38 (every operation rounded on its own);
+ * every endpoint is (int)-truncated as utils.py:40-42 does: the call INTEGRATION.md section 4 documents,
+ * draw_axis(frame, y, p, r, tdx=(x0+x1)/2, tdy=(y0+y1)/2, size=(x1-x0)//2).  A head is four primitives, painted in this order:
+ *     1. the rectangle outline, colour (0,0,0): the four segments (x0,y0)-(x1,y0)-(x1,y1)-(x0,y1)-(x0,y0)
+ *     2. the X axis, red      (int tdx, int tdy) -> (int x1', int y1')      utils.py:28-29, :40
+ *     3. the Y axis, green                       -> (int x2', int y2')      utils.py:33-34, :41
+ *     4. the Z axis, blue                        -> (int x3', int y3')      utils.py:37-38, :42
+ * Colours are those of utils.py:40-42 in the frame's channel order: on a WHENET_RGB frame the X axis is still red.
+ * whenet_overlay_segments returns the 16 ints {x0, y0, x1, y1, then P and Q of the X, the Y and the Z axis as (x, y) pairs}.
+ * A head with valid == 0, or without a forward row (clip overflow), paints nothing; a head whose angles are not all finite
+ * paints its rectangle only (the ints of its axes are 0).
+ * RASTER RULE.  The project's own: OpenCV has never run next to this code, so no claim is made about cv2.line's pixels.  A pixel
+ * (x, y) is painted by a segment P -> Q iff its Euclidean distance to the closed segment is <= 1 -- thickness 2 with round caps --
+ * decided exactly in 64-bit integers.  With d = Q - P, v = X - P, L2 = d.d:
+ *     v.d <= 0:   painted iff |v|^2 <= 1
+ *     v.d >= L2:  painted iff |X - Q|^2 <= 1
+ *     otherwise:  painted iff (v x d)^2 <= L2
+ * P = Q is a disc.  BOUNDS: frame sides are 1..8192 and the window coordinates of a painted head lie in -4096..8192 (a valid head
+ * outside that range is WHENET_EINVAL at the host-pointer entry points; on the device it paints nothing), so every endpoint is below
+ * 2^14 in magnitude, every difference below 2^15, |v x d| < 2^31 and its square fits a signed 64-bit integer.
+ * Primitives are painted head by head in row order; where several cover a pixel the LAST one in that order wins.  Pixels outside
+ * the frame are clipped.  The source frame is never modified (the head crops and the letterbox read it).
+ * BGR -> 4:2:0, the inverse leg of the YUV ingest above.  ch = (h + 1) >> 1, cw = (w + 1) >> 1; the chroma sample (cy, cx) is
+ * taken from the sums Rs, Gs, Bs over the four pixels (min(2 cy + dy, h - 1), min(2 cx + dx, w - 1)), dy, dx = 0, 1.  With int32
+ * arithmetic and >> an arithmetic shift:
+ *     Y = clip8(((RY * R  + GY * G  + BY * B  + (1 << 19)) >> 20) + yoff)
+ *     U = clip8(((RU * Rs + GU * Gs + BU * Bs + (1 << 21)) >> 22) + 128)
+ *     V = clip8(((RV * Rs + GV * Gs + BV * Bs + (1 << 21)) >> 22) + 128)
+ * and {RY, GY, BY, RU, GU, BU, RV, GV, BV, yoff} = WHENET_BGR2YUV_COEFFS[matrix] = rint(2^20 x) of
+ *     Kr sy, Kg sy, Kb sy | -Kr / (2 (1 - Kb)) sc, -Kg / (2 (1 - Kb)) sc, 0.5 sc | 0.5 sc, -Kg / (2 (1 - Kr)) sc, -Kb / (2 (1 - Kr)) sc
+ * with (Kr, Kb) = (.299, .114) for BT.601 and JFIF, (.2126, .0722) for BT.709, Kg = 1 - Kr - Kb, and (sy, sc, yoff) =
+ * (219/255, 224/255, 16) for video range, (1, 1, 0) for JFIF.  Plane layout and pitches are those of the ingest section.
+ *
+ * A destination is a whenet_surface_t: format WHENET_SURF_PACKED (plane[0] = rows of 3 w bytes in the frame's channel order),
+ * WHENET_YUV_NV12 or WHENET_YUV_I420 (planes as whenet_yuv_frame_t, `matrix` read for these two only); every plane its own byte pitch
+ * >= its row bytes; on_device = 1 for planes in the handle's device memory, 0 for host memory.  Only the rows' bytes are ever
+ * written: pitch padding and whatever lies behind a plane belong to the caller.
+ *   whenet_overlay_segments  pure host: window + angles -> the 16 ints above; *flags (may be NULL) = 1 rectangle | 2 axes
+ *   whenet_annotate_host     the whole overlay as pure host arithmetic (no GPU): frame uint8 [frame_h][frame_w][3], rects [k][4],
+ *                  valid [k] (may be NULL: all valid), ypr [k][3], k = 0..256 -> a host surface.  The statement the kernels are held to.
+ *                  The text of an error is whenet_last_error(NULL)'s.
+ *   whenet_op_annotate       the kernels alone, host to host, same arguments: the primitive table is built on the device from the
+ *                  windows and angles (whenet_overlay_plan_kernel), one pass reads the frame and writes the surface
+ *                  (whenet_overlay_draw_kernel).  Works on a whenet_create_postproc handle.  dst->on_device must be 0.
+ * WHENET_EINVAL: a NULL argument or plane, a pitch below the row bytes, an unknown format / matrix / channel order, a side outside
+ * 1..8192, k outside 0..256, a valid head's window outside -4096..8192.
+ *   whenet_frame_annotate    the annotated frame of a ticket, from what its heads left on the device.  Call it after the ticket's
+ *                  heads are enqueued (whenet_submit_frame, whenet_frame_heads, whenet_frame_detect_heads, whenet_clip_detect_heads)
+ *                  and before its collect call; frame_index is 0 for a frame, 0..F-1 for a clip; at most one call per (ticket,
+ *                  frame_index).  ENQUEUE-ONLY: the two kernels go on the engine's stream behind the forward; buffers are allocated
+ *                  on the first call for a size.  The windows, valid flags and angles are those the ticket's collect call returns
+ *                  (a clip's head without a forward row paints nothing); the channel order is the frame's (YUV ingest: BGR).
+ *                  Host destination (on_device = 0): it travels through pinned staging and is complete when the ticket's collect
+ *                  call returns; the pointers must stay valid until then.  Device destination (on_device = 1): the kernel writes
+ *                  it in place.  ORDER, the ingest section's paragraph mirrored: with `stream` (the caller's hipStream_t) given,
+ *                  the kernel waits for the work enqueued on `stream` BEFORE the call (the surface's previous reader) and `stream`
+ *                  waits for the kernel's end, so work enqueued on it AFTER the call sees the annotated surface; the host never
+ *                  waits.  With stream == NULL the surface is complete when the collect call returns.  The collect call's results
+ *                  are bit for bit those of the same submission without an annotate.
+ *                  WHENET_EINVAL, before anything is enqueued and with the handle usable and the ticket still collectable: an
+ *                  unknown ticket; heads not yet enqueued; a ticket without a frame (whenet_submit_u8, a whenet_submit_frame with
+ *                  k = 0 -- it uploads no frame -- or a released clip); a second call; a frame index outside the clip; more than
+ *                  256 head slots per frame; a NULL plane, a pitch below the row bytes, an unknown format / matrix; a device plane
+ *                  that fails the checks of the device ingest (memory type, device, extent inside its allocation); a host pointer
+ *                  marked on_device, or device memory marked as host. */
+#define WHENET_SURF_PACKED 2    /* beside WHENET_YUV_NV12 (0) and WHENET_YUV_I420 (1) */
+#define WHENET_BGR2YUV_COEFFS {{269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897, 16}, \
+                               {191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230, 16}, \
+                               {313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262, 0}}
+typedef struct {
+    void* plane[3];
+    int pitch[3];
+    int format;
+    int matrix;
+    int on_device;
+} whenet_surface_t;
+WHENET_API int whenet_overlay_segments(const int32_t rect[4], float yaw, float pitch, float roll, int32_t segments[16], int32_t* flags);
+WHENET_API int whenet_annotate_host(const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
+                         const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst);
+WHENET_API int whenet_op_annotate(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
+                       const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst);
+WHENET_API int whenet_frame_annotate(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
