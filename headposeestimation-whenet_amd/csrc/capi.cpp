@@ -858,13 +858,48 @@ int whenet_overlay_segments(const int32_t rect[4], float yaw, float pitch, float
     return WHENET_OK;
 }
 
+int whenet_overlay_labels(const int32_t rect[4], float yaw, float pitch, float roll, char text[3][16], int32_t origin[3][2], int32_t* flags) {
+    if (rect == nullptr || text == nullptr || origin == nullptr) return WHENET_EINVAL;
+    if (!whenet::overlay_rect_in_range(rect)) {
+        g_create_error = "overlay_labels: a window coordinate outside -4096..8192";
+        return WHENET_EINVAL;
+    }
+    int32_t seg[whenet::OVERLAY_SEG_INTS];
+    whenet::OverlayLine lines[3];
+    int f = whenet::overlay_segments(rect, 1, double(yaw), double(pitch), double(roll), seg);
+    f |= whenet::overlay_labels(seg, f, yaw, pitch, roll, lines, origin);
+    const char* const glyphs = WHENET_OVERLAY_GLYPHS;
+    for (int l = 0; l < 3; ++l) {
+        std::memset(text[l], 0, 16);
+        for (int i = 0; i < whenet::overlay_line_length(lines[l]); ++i) text[l][i] = glyphs[whenet::overlay_line_glyph(lines[l], i)];
+    }
+    if (flags) *flags = f;
+    return WHENET_OK;
+}
+
+int whenet_overlay_glyph(int ch, int32_t segs[8][4]) {
+    const int g = whenet::overlay_glyph_index(ch);
+    if (segs == nullptr || g < 0) return WHENET_EINVAL;
+    const int8_t* row = whenet::OVERLAY_FONT.seg[g];
+    for (int s = 0; s < whenet::OVERLAY_GLYPH_SEGS; ++s)
+        for (int j = 0; j < 4; ++j) segs[s][j] = row[1 + 4 * s + j];
+    return row[0];
+}
+
 int whenet_annotate_host(const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects, const int32_t* valid,
                          const float* ypr, int k, const whenet_surface_t* dst) {
+    return whenet_annotate_host_ex(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, dst, WHENET_DISPLAY_SIMPLE);
+}
+
+int whenet_annotate_host_ex(const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects, const int32_t* valid,
+                            const float* ypr, int k, const whenet_surface_t* dst, int display) {
     try {
         const char* bad = whenet::overlay_check(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, dst);
         WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("annotate_host: ") + (bad ? bad : ""));
         WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "annotate_host: the surface must be host memory (on_device = 0)");
-        whenet::overlay_annotate_host(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, *dst);
+        WHENET_REQUIRE(display == WHENET_DISPLAY_SIMPLE || display == WHENET_DISPLAY_FULL, WHENET_EINVAL,
+                       "annotate_host: unknown display " + std::to_string(display) + " (WHENET_DISPLAY_SIMPLE or WHENET_DISPLAY_FULL)");
+        whenet::overlay_annotate_host(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, *dst, display);
         return WHENET_OK;
     } catch (...) {
         return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
@@ -873,18 +908,27 @@ int whenet_annotate_host(const uint8_t* frame, int frame_h, int frame_w, int cha
 
 int whenet_op_annotate(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
                        const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst) {
+    return whenet_op_annotate_ex(h, frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, dst, WHENET_DISPLAY_SIMPLE);
+}
+
+int whenet_op_annotate_ex(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
+                          const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst, int display) {
     return guarded(h, [&](whenet::Engine& e) {
         WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_annotate: NULL argument");
-        e.op_annotate(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, *dst);
+        e.op_annotate(frame, frame_h, frame_w, channel_order, rects, valid, ypr, k, *dst, display);
     });
 }
 
 int whenet_frame_annotate(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream) {
+    return whenet_frame_annotate_ex(h, ticket, frame_index, dst, stream, WHENET_DISPLAY_SIMPLE);
+}
+
+int whenet_frame_annotate_ex(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream, int display) {
     return guarded(h, [&](whenet::Engine&) {
         WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "frame_annotate: NULL argument");
         const int idx = ticket % MAX_INFLIGHT_ENGINES;
         WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "frame_annotate: unknown ticket " + std::to_string(ticket));
-        h->at(size_t(idx)).frame_annotate(ticket / MAX_INFLIGHT_ENGINES, frame_index, *dst, static_cast<hipStream_t>(stream));
+        h->at(size_t(idx)).frame_annotate(ticket / MAX_INFLIGHT_ENGINES, frame_index, *dst, static_cast<hipStream_t>(stream), display);
     });
 }
 

@@ -330,9 +330,11 @@ class Engine {
     //   planes in the slot's staging (one buffer pair per frame index), one D2H behind it; the collect call copies the rows out.
     //   Every refusal (WHENET_EINVAL) comes before anything is enqueued and leaves the ticket as it was.
     // op_annotate: the two kernels alone, host to host.
-    void frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream);
+    // display: WHENET_DISPLAY_SIMPLE, or WHENET_DISPLAY_FULL -- the plan kernel then also writes the heads' label records (one more
+    // per-slot table) and the draw kernel's other instantiation paints them.
+    void frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream, int display);
     void op_annotate(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* rects, const int32_t* valid, const float* ypr,
-                     int k, const whenet_surface_t& dst);
+                     int k, const whenet_surface_t& dst, int display);
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -371,6 +373,7 @@ class Engine {
         int ann_kind = ANN_NONE;
         unsigned ann_mask = 0;
         DeviceBuffer ann_table;
+        DeviceBuffer ann_labels;         // display full: the label records, [frames][head slots][3 lines][4 words]
         Event ann_done;
         struct AnnHost {
             whenet_surface_t dst;

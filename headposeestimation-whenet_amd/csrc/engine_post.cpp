@@ -1076,12 +1076,16 @@ int tight_surface(int format, int fh, int fw, int rows[3], int row_bytes[3], siz
     return planes;
 }
 OverlayDrawArgs draw_args(const uint8_t* d_frame, int fh, int fw, int channel_order, const int32_t* d_segs, const int32_t* d_flags, int k,
-                          int format, int matrix) {
+                          int format, int matrix, const uint32_t* d_labels, int display) {
     OverlayDrawArgs a{};
     a.frame = d_frame, a.fh = fh, a.fw = fw, a.channel_order = channel_order;
-    a.segs = d_segs, a.flags = d_flags, a.k = k, a.format = format;
+    a.segs = d_segs, a.flags = d_flags, a.k = k, a.format = format, a.labels = d_labels, a.display = display;
     if (format != WHENET_SURF_PACKED) WHENET_REQUIRE(bgr2yuv_coeffs(matrix, a.kc), WHENET_EINVAL, "unknown matrix " + std::to_string(matrix));
     return a;
+}
+void check_display(const char* what, int display) {
+    WHENET_REQUIRE(display == WHENET_DISPLAY_SIMPLE || display == WHENET_DISPLAY_FULL, WHENET_EINVAL,
+                   std::string(what) + ": unknown display " + std::to_string(display) + " (WHENET_DISPLAY_SIMPLE or WHENET_DISPLAY_FULL)");
 }
 }  // namespace
 
@@ -1111,8 +1115,9 @@ void Engine::check_surface(const char* what, const whenet_surface_t& dst, int fh
 }
 
 void Engine::op_annotate(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* rects, const int32_t* valid, const float* ypr,
-                         int k, const whenet_surface_t& dst) {
+                         int k, const whenet_surface_t& dst, int display) {
     DeviceGuard guard(device_);
+    check_display("op_annotate", display);
     const char* bad = overlay_check(frame, fh, fw, channel_order, rects, valid, ypr, k, &dst);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_annotate: ") + (bad ? bad : ""));
     WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_annotate: the surface must be host memory (on_device = 0)");
@@ -1128,6 +1133,8 @@ void Engine::op_annotate(const uint8_t* frame, int fh, int fw, int channel_order
     float* const d_ypr = static_cast<float*>(tmp.get(K * 3 * sizeof(float)));
     int32_t* const d_segs = static_cast<int32_t*>(tmp.get(K * (OVERLAY_SEG_INTS + 1) * sizeof(int32_t)));
     int32_t* const d_flags = d_segs + K * OVERLAY_SEG_INTS;
+    uint32_t* const d_labels =
+        display == WHENET_DISPLAY_FULL ? static_cast<uint32_t*>(tmp.get(K * OVERLAY_LABEL_WORDS * sizeof(uint32_t))) : nullptr;
     std::vector<uint8_t> out(off[planes]);
     WHENET_HIP_CHECK(hipMemcpyAsync(d_frame, frame, fbytes, hipMemcpyHostToDevice, stream_));
     if (k > 0) {
@@ -1136,12 +1143,12 @@ void Engine::op_annotate(const uint8_t* frame, int fh, int fw, int channel_order
         WHENET_HIP_CHECK(hipMemcpyAsync(d_ypr, ypr, K * 3 * sizeof(float), hipMemcpyHostToDevice, stream_));
         OverlayPlanArgs p{};
         p.rects = d_rects, p.valid = valid ? d_valid : nullptr, p.row = nullptr, p.ypr = d_ypr;
-        p.k = k, p.rect_stride = 4, p.rect_is_size = 0, p.segs = d_segs, p.flags = d_flags;
+        p.k = k, p.rect_stride = 4, p.rect_is_size = 0, p.segs = d_segs, p.flags = d_flags, p.labels = d_labels;
         launch_overlay_plan(p, stream_);
     }
     // the landing buffer between two guard zones, as the other kernel-alone calls have it: a byte no lane wrote arrives as the sentinel
     const GuardedOutput d_out(off[planes], stream_);
-    OverlayDrawArgs a = draw_args(d_frame, fh, fw, channel_order, d_segs, d_flags, k, dst.format, dst.matrix);
+    OverlayDrawArgs a = draw_args(d_frame, fh, fw, channel_order, d_segs, d_flags, k, dst.format, dst.matrix, d_labels, display);
     for (int p = 0; p < planes; ++p) a.plane[p] = d_out.frames() + off[p], a.pitch[p] = row_bytes[p];
     launch_overlay_draw(a, stream_);
     uint8_t* const one = out.data();
@@ -1153,8 +1160,9 @@ void Engine::op_annotate(const uint8_t* frame, int fh, int fw, int channel_order
                         size_t(row_bytes[p]));
 }
 
-void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream) {
+void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream, int display) {
     DeviceGuard guard(device_);
+    check_display("frame_annotate", display);
     Slot* found = nullptr;
     for (Slot& s : slots_)
         if (s.busy && s.ticket == ticket) found = &s;
@@ -1185,13 +1193,17 @@ void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t&
     // allocations and the events first: nothing is enqueued yet if one of them fails
     const size_t S = size_t(F) * size_t(std::max(k, 1));
     slot.ann_table.grow(S * (OVERLAY_SEG_INTS + 1) * sizeof(int32_t));
+    const bool full = display == WHENET_DISPLAY_FULL;
+    if (full) slot.ann_labels.grow(S * OVERLAY_LABEL_WORDS * sizeof(uint32_t));
     StagedBuffer& stage = slot.ann_stage[frame_index];
     if (!dst.on_device) stage.h.grow(off[planes]), stage.d.grow(off[planes]);
     if (!slot.ann_done) slot.ann_done.create();
     if (dst.on_device && stream != nullptr && !slot.source) slot.source.create();
     int32_t* const d_segs = slot.ann_table.as<int32_t>() + size_t(frame_index) * size_t(k) * OVERLAY_SEG_INTS;
     int32_t* const d_flags = slot.ann_table.as<int32_t>() + S * OVERLAY_SEG_INTS + size_t(frame_index) * size_t(k);
-    OverlayDrawArgs a = draw_args(slot.frame.d.as<uint8_t>() + frame_off, fh, fw, channel_order, d_segs, d_flags, k, dst.format, dst.matrix);
+    uint32_t* const d_labels = full ? slot.ann_labels.as<uint32_t>() + size_t(frame_index) * size_t(k) * OVERLAY_LABEL_WORDS : nullptr;
+    OverlayDrawArgs a =
+        draw_args(slot.frame.d.as<uint8_t>() + frame_off, fh, fw, channel_order, d_segs, d_flags, k, dst.format, dst.matrix, d_labels, display);
     for (int p = 0; p < planes; ++p) {
         a.plane[p] = dst.on_device ? static_cast<uint8_t*>(dst.plane[p]) : stage.d.as<uint8_t>() + off[p];
         a.pitch[p] = dst.on_device ? dst.pitch[p] : row_bytes[p];
@@ -1202,7 +1214,7 @@ void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t&
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, slot.copied, 0));
     if (k > 0) {
         OverlayPlanArgs p{};
-        p.ypr = slot.dev().ypr, p.k = k, p.segs = d_segs, p.flags = d_flags;
+        p.ypr = slot.dev().ypr, p.k = k, p.segs = d_segs, p.flags = d_flags, p.labels = d_labels;
         if (slot.ann_kind == Slot::ANN_PLANS) {
             p.rects = slot.plan.d.as<int32_t>(), p.rect_stride = CROP_PLAN_INTS, p.rect_is_size = 1;
         } else if (slot.ann_kind == Slot::ANN_DET) {

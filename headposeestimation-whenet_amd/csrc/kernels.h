@@ -596,8 +596,9 @@ void launch_frame_pack(uint8_t* d_out, PackFrames clip, hipStream_t stream);
 // The pose overlay (include/whenet_hip.h, POSE OVERLAY; the arithmetic is overlay_host.h's).  Plan: head i of k (<= 1024: the slots
 // of a clip) takes its window from rects + i * rect_stride -- (y0, x0, y1, x1), or a crop plan's {y0, x0, h, w} with rect_is_size --
 // its valid flag (nullptr: 1) and the angles of forward row row[i] (nullptr: row i; a negative row paints nothing), and writes
-// segs [k][16] and flags [k].  Draw: reads the tight frame [fh][fw][3] and the table of k <= 256 heads, writes the surface's planes
-// (device memory, any alignment, their own pitches).
+// segs [k][16] and flags [k]; with `labels` (nullptr: WHENET_DISPLAY_SIMPLE) also the head's label record, labels [k][3][4] words
+// (overlay_host.h, OverlayLine), and OVERLAY_LABELS in its flags.  Draw: reads the tight frame [fh][fw][3] and the table of k <= 256
+// heads, writes the surface's planes (device memory, any alignment, their own pitches); display WHENET_DISPLAY_FULL reads `labels`.
 struct OverlayPlanArgs {
     const int32_t* rects;
     const int32_t* valid;
@@ -606,6 +607,7 @@ struct OverlayPlanArgs {
     int k, rect_stride, rect_is_size;
     int32_t* segs;
     int32_t* flags;
+    uint32_t* labels;
 };
 struct OverlayDrawArgs {
     const uint8_t* frame;
@@ -617,6 +619,8 @@ struct OverlayDrawArgs {
     int pitch[3];
     int format;
     Bgr2YuvCoeffs kc;
+    const uint32_t* labels;
+    int display;
 };
 void launch_overlay_plan(const OverlayPlanArgs& a, hipStream_t stream);
 void launch_overlay_draw(const OverlayDrawArgs& a, hipStream_t stream);

@@ -4,7 +4,9 @@
 // include/whenet_hip.h, shared with the host statement through overlay_host.h: the bytes are those of whenet_annotate_host.
 //
 // whenet_overlay_plan_kernel: one lane per head.  Window + float32 angles -> the 16 endpoint ints and the flags word (utils.py:15-42
-// in double, every operation rounded on its own: contraction is off for this file as it is for headplan.hip's arithmetic).
+// in double, every operation rounded on its own: contraction is off for this file as it is for headplan.hip's arithmetic).  With a
+// label table it also writes the head's three lines of text as glyph indices (rintf and integer digits, float32 only) and sets
+// OVERLAY_LABELS.
 //
 // whenet_overlay_draw_kernel: one pass, source frame in, destination out.  A workgroup of 256 lanes owns a tile of 128 x 16 pixels.
 //   1. Lane t takes head t: its (up to) seven segments are tested against the tile's bounding box grown by the raster's reach of 1.
@@ -19,7 +21,15 @@
 //      No lane writes a byte outside its pixels: pitch padding and the neighbouring surface belong to the caller.
 // Adjacent lanes own adjacent groups: a wave reads and writes 384 contiguous bytes on each of 4 rows.  The pixel arrays are indexed
 // by unrolled constants only (no scratch).
+//
+// The draw kernel has two instantiations.  WHENET_DISPLAY_SIMPLE is the kernel above.  WHENET_DISPLAY_FULL puts, behind a head's
+// seven segments, one list entry per line of text whose box meets the tile -- the origin as P, head * 3 + line and the line's length
+// as Q, LINE_TAG as the colour -- so the list holds at most 256 x 10 entries (24 KB of LDS with the counts) however much text there
+// is.  For such an entry a lane tests the line's box against its 4 x 2 block, loads the line's 16 bytes from the label table and asks
+// overlay_text_hit for each of its pixels: the character cell is (x - ox) / 7, the glyph's row a byte of the 400-byte constant table
+// that overlay_host.h builds from the header's strokes by the thin rule.
 #include <algorithm>
+#include <string>
 
 #include "kernels.h"
 #include "overlay_host.h"
@@ -30,7 +40,12 @@ namespace {
 
 constexpr int THREADS = 256;
 constexpr int TILE_W = 128, TILE_H = 16;      // 32 lanes x 4 pixels, 8 lane rows x 2 rows
-constexpr int MAX_SEGS = OVERLAY_MAX_HEADS * 7;
+constexpr int LINE_TAG = 4;                   // the colour byte of a list entry that is a line of text
+
+__device__ __forceinline__ OverlayLine load_line(const uint32_t* labels, int index) {
+    const uint4 w = *reinterpret_cast<const uint4*>(labels + size_t(index) * 4);
+    return {uint64_t(w.x) | (uint64_t(w.y) << 32), uint64_t(w.z) | (uint64_t(w.w) << 32)};
+}
 
 __global__ __launch_bounds__(THREADS) void whenet_overlay_plan_kernel(OverlayPlanArgs a) {
     const int i = int(blockIdx.x) * THREADS + int(threadIdx.x);
@@ -46,7 +61,16 @@ __global__ __launch_bounds__(THREADS) void whenet_overlay_plan_kernel(OverlayPla
     }
     const float* y = a.ypr + size_t(row) * 3;
     int32_t seg[OVERLAY_SEG_INTS];
-    const int flags = overlay_segments(rect, valid, double(y[0]), double(y[1]), double(y[2]), seg);
+    int flags = overlay_segments(rect, valid, double(y[0]), double(y[1]), double(y[2]), seg);
+    if (a.labels != nullptr) {
+        OverlayLine lines[3];
+        int32_t origin[3][2];
+        flags |= overlay_labels(seg, flags, y[0], y[1], y[2], lines, origin);
+        uint4* rec = reinterpret_cast<uint4*>(a.labels + size_t(i) * OVERLAY_LABEL_WORDS);
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+            rec[l] = make_uint4(uint32_t(lines[l].lo), uint32_t(lines[l].lo >> 32), uint32_t(lines[l].hi), uint32_t(lines[l].hi >> 32));
+    }
     int32_t* out = a.segs + size_t(i) * OVERLAY_SEG_INTS;
 #pragma unroll
     for (int j = 0; j < OVERLAY_SEG_INTS; ++j) out[j] = seg[j];
@@ -89,7 +113,10 @@ __device__ __forceinline__ void store_pixels(uint8_t* dp, int n, uint32_t w0, ui
     }
 }
 
+template <int DISPLAY>
 __global__ __launch_bounds__(THREADS) void whenet_overlay_draw_kernel(OverlayDrawArgs a) {
+    constexpr bool FULL = DISPLAY == WHENET_DISPLAY_FULL;
+    constexpr int MAX_SEGS = OVERLAY_MAX_HEADS * (FULL ? 10 : 7);
     __shared__ uint32_t s_p[MAX_SEGS], s_q[MAX_SEGS];
     __shared__ uint8_t s_c[MAX_SEGS];
     __shared__ int s_cnt[THREADS];
@@ -103,6 +130,7 @@ __global__ __launch_bounds__(THREADS) void whenet_overlay_draw_kernel(OverlayDra
         int32_t seg[OVERLAY_SEG_INTS];
         int nseg = 0;
         unsigned mask = 0;
+        [[maybe_unused]] int len[3] = {0, 0, 0};
         if (tid < a.k) {
             const int f = a.flags[tid];
             nseg = (f & OVERLAY_RECT) ? ((f & OVERLAY_AXES) ? 7 : 4) : 0;
@@ -116,6 +144,18 @@ __global__ __launch_bounds__(THREADS) void whenet_overlay_draw_kernel(OverlayDra
                     overlay_head_segment(seg, s, px, py, qx, qy, colour);
                     const bool in = s < nseg && min(px, qx) <= bx1 && max(px, qx) >= bx0 && min(py, qy) <= by1 && max(py, qy) >= by0;
                     mask |= in ? (1u << s) : 0u;
+                }
+                if constexpr (FULL) {
+                    if (f & OVERLAY_LABELS) {
+#pragma unroll
+                        for (int l = 0; l < 3; ++l) {      // the box of a line: its characters' boxes, nothing around them
+                            len[l] = int(a.labels[(size_t(tid) * 3 + l) * 4 + 3] >> 24);
+                            const int ox = seg[0], oy = seg[1] - OVERLAY_LINE_STEP * l;
+                            const bool in = ox <= bx1 - 1 && ox + OVERLAY_ADVANCE * len[l] - 2 >= bx0 + 1 && oy + OVERLAY_GLYPH_TOP <= by1 - 1 &&
+                                            oy + OVERLAY_GLYPH_TOP + OVERLAY_GLYPH_ROWS - 1 >= by0 + 1;
+                            mask |= in ? (1u << (7 + l)) : 0u;
+                        }
+                    }
                 }
             }
         }
@@ -135,6 +175,15 @@ __global__ __launch_bounds__(THREADS) void whenet_overlay_draw_kernel(OverlayDra
                     s_p[base] = pack_xy(px, py), s_q[base] = pack_xy(qx, qy), s_c[base] = uint8_t(colour);
                     ++base;
                 }
+            }
+            if constexpr (FULL) {
+#pragma unroll
+                for (int l = 0; l < 3; ++l)
+                    if (mask & (1u << (7 + l))) {
+                        s_p[base] = pack_xy(seg[0], seg[1] - OVERLAY_LINE_STEP * l);
+                        s_q[base] = uint32_t(tid * 3 + l) | (uint32_t(len[l]) << 16), s_c[base] = uint8_t(LINE_TAG);
+                        ++base;
+                    }
             }
         }
         __syncthreads();
@@ -173,6 +222,22 @@ __global__ __launch_bounds__(THREADS) void whenet_overlay_draw_kernel(OverlayDra
     }
     for (int s = 0; s < total; ++s) {
         const uint32_t p = s_p[s], q = s_q[s];
+        if constexpr (FULL) {
+            if (s_c[s] == LINE_TAG) {
+                const int ox = unpack_x(p), oy = unpack_y(p), n_chars = int(q >> 16);
+                if (ox > x0 + 3 || ox + OVERLAY_ADVANCE * n_chars - 2 < x0 || oy + OVERLAY_GLYPH_TOP > y0 + 1 ||
+                    oy + OVERLAY_GLYPH_TOP + OVERLAY_GLYPH_ROWS - 1 < y0)
+                    continue;
+                const OverlayLine t = load_line(a.labels, int(q & 0xFFFFu));
+                const uint32_t c = overlay_label_colour(a.channel_order);
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (overlay_text_hit(t, ox, oy, x0 + j, y0 + r)) pix[r][j] = c;
+                continue;
+            }
+        }
         const int px = unpack_x(p), py = unpack_y(p), qx = unpack_x(q), qy = unpack_y(q);
         if (min(px, qx) > x0 + 4 || max(px, qx) < x0 - 1 || min(py, qy) > y0 + 2 || max(py, qy) < y0 - 1) continue;
         const uint32_t c = overlay_colour(int(s_c[s]), a.channel_order);
@@ -277,7 +342,13 @@ void launch_overlay_draw(const OverlayDrawArgs& a, hipStream_t stream) {
     for (int p = 0; p < planes; ++p)
         WHENET_REQUIRE(a.plane[p] != nullptr && a.pitch[p] >= row_bytes[p], WHENET_EINVAL, "overlay_draw: bad surface");
     const dim3 grid((a.fw + TILE_W - 1) / TILE_W, (a.fh + TILE_H - 1) / TILE_H);
-    hipLaunchKernelGGL(whenet_overlay_draw_kernel, grid, dim3(THREADS), 0, stream, a);
+    if (a.display == WHENET_DISPLAY_FULL) {
+        WHENET_REQUIRE(a.k == 0 || a.labels != nullptr, WHENET_EINVAL, "overlay_draw: display full without a label table");
+        hipLaunchKernelGGL(whenet_overlay_draw_kernel<WHENET_DISPLAY_FULL>, grid, dim3(THREADS), 0, stream, a);
+    } else {
+        WHENET_REQUIRE(a.display == WHENET_DISPLAY_SIMPLE, WHENET_EINVAL, "overlay_draw: unknown display " + std::to_string(a.display));
+        hipLaunchKernelGGL(whenet_overlay_draw_kernel<WHENET_DISPLAY_SIMPLE>, grid, dim3(THREADS), 0, stream, a);
+    }
     WHENET_HIP_CHECK(hipGetLastError());
 }
 

@@ -6,6 +6,8 @@
 // Reference: utils.py:13-43 (`draw_axis`: angles to radians, six sin / cos products, `int()` of every endpoint, three cv2.line calls
 // of thickness 2) and demo_video.py:26-29 (`cv2.rectangle` of the window, colour (0,0,0), then draw_axis from the window's centre).
 // The raster of a segment is the project's own rule (OpenCV has never run next to this code): distance to the closed segment <= 1.
+// demo_video.py:31-34 (`--display full`: three cv2.putText lines per head): the text is the executed reference's, "{}".format(np.round(a)),
+// built from rintf and integer digits; the font and its thin raster (distance <= 1/2) are the project's own, stated in the header.
 #pragma once
 
 #include <cmath>
@@ -28,7 +30,12 @@ constexpr int OVERLAY_SEG_INTS = 16;          // (x, y) of: window corner 0, win
 constexpr int OVERLAY_COORD_MIN = -4096;      // window coordinates a head may have: |endpoint| < 2^14 follows (header, BOUNDS)
 constexpr int OVERLAY_COORD_MAX = 8192;
 constexpr int OVERLAY_MAX_FRAME_SIDE = 8192;
-enum { OVERLAY_RECT = 1, OVERLAY_AXES = 2 };  // flags of a head: what it paints
+enum { OVERLAY_RECT = 1, OVERLAY_AXES = 2, OVERLAY_LABELS = 4 };  // flags of a head: what it paints
+constexpr int OVERLAY_REACH_THICK = 2, OVERLAY_REACH_THIN = 1;     // twice the distance a segment paints to: 1 (axes, rectangle), 1/2 (glyphs)
+constexpr int OVERLAY_GLYPHS = 25, OVERLAY_GLYPH_SEGS = 8;
+constexpr int OVERLAY_GLYPH_W = 6, OVERLAY_GLYPH_TOP = -9, OVERLAY_GLYPH_ROWS = 13, OVERLAY_ADVANCE = 7;      // a glyph's box, the pen's step
+constexpr int OVERLAY_LINE_CHARS = 14, OVERLAY_LINE_STEP = 15;     // "pitch: -9999.0"; the baselines of a head's lines are 15 rows apart
+constexpr int OVERLAY_LABEL_WORDS = 12;                            // a head's label record: 3 lines x 4 words
 
 struct Bgr2YuvCoeffs {
     int ry, gy, by, ru, gu, bu, rv, gv, bv, yoff;
@@ -70,18 +77,135 @@ WHENET_HD inline int overlay_segments(const int32_t rect[4], int valid, double y
     return OVERLAY_RECT | OVERLAY_AXES;
 }
 
-// the raster rule: is pixel (x, y) within distance 1 of the closed segment P -> Q?  64-bit integers, exact.
-WHENET_HD inline bool overlay_hit(int px, int py, int qx, int qy, int x, int y) {
+// the raster rule: is pixel (x, y) within distance reach / 2 of the closed segment P -> Q?  64-bit integers, exact.  reach 2 is the
+// rule of the axes and the rectangle (4 d^2 <= 4 L2 is divided through: no product leaves 64 bits at the header's bounds); reach 1
+// is the glyphs' rule, applied in a character cell's own coordinates, where every number is below 2^5.
+WHENET_HD constexpr inline bool overlay_hit(int px, int py, int qx, int qy, int x, int y, int reach = OVERLAY_REACH_THICK) {
     const int64_t dx = qx - px, dy = qy - py, vx = x - px, vy = y - py;
     const int64_t L2 = dx * dx + dy * dy, t = vx * dx + vy * dy;
-    if (t <= 0) return vx * vx + vy * vy <= 1;
+    const int64_t r2 = reach == OVERLAY_REACH_THICK ? 1 : 0;              // floor(reach^2 / 4): what an integer |v|^2 is compared with
+    if (t <= 0) return vx * vx + vy * vy <= r2;
     if (t >= L2) {
         const int64_t wx = x - qx, wy = y - qy;
-        return wx * wx + wy * wy <= 1;
+        return wx * wx + wy * wy <= r2;
     }
     const int64_t c = vx * dy - vy * dx;
-    return c * c <= L2;
+    return reach == OVERLAY_REACH_THICK ? c * c <= L2 : 4 * c * c <= L2;
 }
+
+// ---- the labels: font, text, hit test ----
+// The stroke font of the header (WHENET_OVERLAY_GLYPHS, WHENET_OVERLAY_FONT) and, built from it at compile time by the thin rule,
+// every glyph's 13 rows of 6 bits: bit cx of rows[g][cy + 9] says whether the glyph paints (cx, cy) of its cell.  A glyph's strokes
+// lie inside its box and reach 1/2 paints no pixel off a stroke's own rows and columns, so the rows ARE the glyph.
+struct OverlayFont {
+    int8_t seg[OVERLAY_GLYPHS][1 + 4 * OVERLAY_GLYPH_SEGS];
+    uint8_t rows[OVERLAY_GLYPHS][16];
+};
+constexpr OverlayFont overlay_make_font() {
+    constexpr int table[OVERLAY_GLYPHS][1 + 4 * OVERLAY_GLYPH_SEGS] = WHENET_OVERLAY_FONT;
+    OverlayFont f{};
+    for (int g = 0; g < OVERLAY_GLYPHS; ++g) {
+        for (int j = 0; j < 1 + 4 * OVERLAY_GLYPH_SEGS; ++j) f.seg[g][j] = int8_t(table[g][j]);
+        for (int cy = 0; cy < OVERLAY_GLYPH_ROWS; ++cy) {
+            unsigned bits = 0;
+            for (int cx = 0; cx < OVERLAY_GLYPH_W; ++cx)
+                for (int s = 0; s < table[g][0]; ++s) {
+                    const int* e = table[g] + 1 + 4 * s;
+                    if (overlay_hit(e[0], e[1], e[2], e[3], cx, cy + OVERLAY_GLYPH_TOP, OVERLAY_REACH_THIN)) bits |= 1u << cx;
+                }
+            f.rows[g][cy] = uint8_t(bits);
+        }
+    }
+    return f;
+}
+#if defined(__HIPCC__)
+__device__ __constant__ constexpr OverlayFont OVERLAY_FONT_DEVICE = overlay_make_font();
+#endif
+constexpr OverlayFont OVERLAY_FONT = overlay_make_font();
+WHENET_HD inline unsigned overlay_glyph_row(int g, int row) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return OVERLAY_FONT_DEVICE.rows[g][row];
+#else
+    return OVERLAY_FONT.rows[g][row];
+#endif
+}
+
+// index of a character in WHENET_OVERLAY_GLYPHS, or -1
+inline int overlay_glyph_index(int ch) {
+    const char* all = WHENET_OVERLAY_GLYPHS;
+    for (int g = 0; g < OVERLAY_GLYPHS; ++g)
+        if (all[g] == ch) return g;
+    return -1;
+}
+
+// A line of text as glyph indices, one per byte: characters 0..7 in `lo`, 8..14 in `hi` (byte 0 first), the length in hi's top byte.
+// In memory four little-endian words {lo, lo >> 32, hi, hi >> 32}: the label record of a head is three of them (yaw, pitch, roll).
+struct OverlayLine {
+    uint64_t lo, hi;
+};
+WHENET_HD inline int overlay_line_length(const OverlayLine& t) { return int(t.hi >> 56); }
+WHENET_HD inline int overlay_line_glyph(const OverlayLine& t, int i) { return int(((i < 8 ? t.lo >> (8 * i) : t.hi >> (8 * (i - 8)))) & 255u); }
+WHENET_HD inline void overlay_line_put(OverlayLine& t, int& n, int g) {
+    if (n < 8) t.lo |= uint64_t(g) << (8 * n);
+    else t.hi |= uint64_t(g) << (8 * (n - 8));
+    ++n;
+}
+
+// Line `line` (0 yaw, 1 pitch, 2 roll) for the float32 angle a: the name, ": ", then "{}".format(np.round(a)) -- r = rintf(a) (half
+// to even), '-' if signbit(r), the digits of |r| without leading zeros, ".0".  false (and no text): |r| > 9999 or r is not a number.
+WHENET_HD inline bool overlay_label_line(int line, float a, OverlayLine& t) {
+    enum { A = 10, C, H, I, L, O, P, R, T, W, Y, COLON, SPACE, MINUS, DOT };
+    t.lo = 0, t.hi = 0;
+    const float r = rintf(a);
+    if (!(fabsf(r) <= 9999.f)) return false;
+    int n = 0;
+    if (line == 0) {
+        overlay_line_put(t, n, Y), overlay_line_put(t, n, A), overlay_line_put(t, n, W);
+    } else if (line == 1) {
+        overlay_line_put(t, n, P), overlay_line_put(t, n, I), overlay_line_put(t, n, T), overlay_line_put(t, n, C), overlay_line_put(t, n, H);
+    } else {
+        overlay_line_put(t, n, R), overlay_line_put(t, n, O), overlay_line_put(t, n, L), overlay_line_put(t, n, L);
+    }
+    overlay_line_put(t, n, COLON), overlay_line_put(t, n, SPACE);
+    if (std::signbit(r)) overlay_line_put(t, n, MINUS);
+    const int v = int(fabsf(r));
+    const int d3 = v / 1000, d2 = v / 100 % 10, d1 = v / 10 % 10, d0 = v % 10;
+    if (v >= 1000) overlay_line_put(t, n, d3);
+    if (v >= 100) overlay_line_put(t, n, d2);
+    if (v >= 10) overlay_line_put(t, n, d1);
+    overlay_line_put(t, n, d0), overlay_line_put(t, n, DOT), overlay_line_put(t, n, 0);
+    t.hi |= uint64_t(n) << 56;
+    return true;
+}
+
+// The labels of a head whose segments and flags overlay_segments returned: the three lines and their baseline-left origins
+// (x0, y0), (x0, y0 - 15), (x0, y0 - 30).  Returns OVERLAY_LABELS, or 0 (lines cleared): the head paints no axes, or a rounded angle
+// is beyond +-9999.
+WHENET_HD inline int overlay_labels(const int32_t seg[OVERLAY_SEG_INTS], int flags, float yaw, float pitch, float roll, OverlayLine lines[3],
+                                    int32_t origin[3][2]) {
+    bool ok = (flags & OVERLAY_AXES) != 0;
+    ok = overlay_label_line(0, yaw, lines[0]) && ok;
+    ok = overlay_label_line(1, pitch, lines[1]) && ok;
+    ok = overlay_label_line(2, roll, lines[2]) && ok;
+    for (int i = 0; i < 3; ++i) {
+        origin[i][0] = seg[0], origin[i][1] = seg[1] - OVERLAY_LINE_STEP * i;
+        if (!ok) lines[i].lo = 0, lines[i].hi = 0;
+    }
+    return ok ? OVERLAY_LABELS : 0;
+}
+
+// does the line with origin (ox, oy) paint pixel (x, y)?  The pixel lies in at most one character's cell: column (x - ox) / 7, and
+// only the first 6 of a cell's 7 columns belong to the glyph's box.
+WHENET_HD inline bool overlay_text_hit(const OverlayLine& t, int ox, int oy, int x, int y) {
+    const int dx = x - ox, row = y - oy - OVERLAY_GLYPH_TOP;
+    if (dx < 0 || row < 0 || row >= OVERLAY_GLYPH_ROWS) return false;
+    const int cell = dx / OVERLAY_ADVANCE, cx = dx - cell * OVERLAY_ADVANCE;
+    if (cell >= overlay_line_length(t) || cx >= OVERLAY_GLYPH_W) return false;
+    return ((overlay_glyph_row(overlay_line_glyph(t, cell), row) >> cx) & 1u) != 0;
+}
+
+// the labels' colour (100, 255, 0) as B, G, R, in the frame's channel order, as overlay_colour packs a pixel
+WHENET_HD inline uint32_t overlay_label_colour(int channel_order) { return channel_order == WHENET_BGR ? 0x00FF64u : 0x64FF00u; }
 
 // The seven segments of a head in paint order (rectangle sides, then X, Y, Z): segment i of `seg` as P, Q and its colour index
 // (0 = the rectangle's black, 1 = X red, 2 = Y green, 3 = Z blue).
@@ -166,9 +290,10 @@ inline const char* overlay_check(const void* frame, int fh, int fw, int channel_
 }
 
 // The overlay as pure host arithmetic: what the kernels are held to.  `frame` uint8 [fh][fw][3] tight; segs [k][16], flags [k] as
-// overlay_segments returns them; the surface's planes are host memory.  Only the rows' bytes are written.
+// overlay_segments returns them; the surface's planes are host memory.  Only the rows' bytes are written.  lines [k][3]: the label
+// records, read for the heads whose flags hold OVERLAY_LABELS (nullptr: none does).
 inline void overlay_paint_host(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* segs, const int32_t* flags, int k,
-                               const whenet_surface_t& dst) {
+                               const whenet_surface_t& dst, const OverlayLine* lines = nullptr) {
     // the annotated frame, packed, row by row (two rows at a time for 4:2:0)
     const bool packed = dst.format == WHENET_SURF_PACKED;
     Bgr2YuvCoeffs kc{};
@@ -195,6 +320,18 @@ inline void overlay_paint_host(const uint8_t* frame, int fh, int fw, int channel
                     const uint32_t c = overlay_colour(colour, channel_order);
                     for (int x = xlo; x <= xhi; ++x)
                         if (overlay_hit(px, py, qx, qy, x, y)) {
+                            row[3 * x + 0] = uint8_t(c), row[3 * x + 1] = uint8_t(c >> 8), row[3 * x + 2] = uint8_t(c >> 16);
+                        }
+                }
+                if (lines == nullptr || !(flags[h] & OVERLAY_LABELS)) continue;
+                for (int l = 0; l < 3; ++l) {                      // the yaw, the pitch and the roll line, behind the head's segments
+                    const OverlayLine& t = lines[size_t(h) * 3 + l];
+                    const int ox = segs[size_t(h) * OVERLAY_SEG_INTS], oy = segs[size_t(h) * OVERLAY_SEG_INTS + 1] - OVERLAY_LINE_STEP * l;
+                    if (y < oy + OVERLAY_GLYPH_TOP || y >= oy + OVERLAY_GLYPH_TOP + OVERLAY_GLYPH_ROWS) continue;
+                    const int xlo = ox < 0 ? 0 : ox, xend = ox + OVERLAY_ADVANCE * overlay_line_length(t) - 1;
+                    const uint32_t c = overlay_label_colour(channel_order);
+                    for (int x = xlo; x < xend && x < fw; ++x)
+                        if (overlay_text_hit(t, ox, oy, x, y)) {
                             row[3 * x + 0] = uint8_t(c), row[3 * x + 1] = uint8_t(c >> 8), row[3 * x + 2] = uint8_t(c >> 16);
                         }
                 }
@@ -227,16 +364,23 @@ inline void overlay_paint_host(const uint8_t* frame, int fh, int fw, int channel
     }
 }
 
-// whenet_annotate_host behind its argument checks
+// whenet_annotate_host_ex behind its argument checks (display: WHENET_DISPLAY_SIMPLE or WHENET_DISPLAY_FULL)
 inline void overlay_annotate_host(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* rects, const int32_t* valid,
-                                  const float* ypr, int k, const whenet_surface_t& dst) {
+                                  const float* ypr, int k, const whenet_surface_t& dst, int display = WHENET_DISPLAY_SIMPLE) {
     std::vector<int32_t> table(size_t(k > 0 ? k : 1) * (OVERLAY_SEG_INTS + 1));
     int32_t* const segs = table.data();
     int32_t* const flags = segs + size_t(k > 0 ? k : 1) * OVERLAY_SEG_INTS;
-    for (int i = 0; i < k; ++i)
+    std::vector<OverlayLine> lines(display == WHENET_DISPLAY_FULL ? size_t(k) * 3 : 0);
+    for (int i = 0; i < k; ++i) {
         flags[i] = overlay_segments(rects + 4 * i, valid ? valid[i] : 1, double(ypr[3 * i]), double(ypr[3 * i + 1]), double(ypr[3 * i + 2]),
                                     segs + size_t(i) * OVERLAY_SEG_INTS);
-    overlay_paint_host(frame, fh, fw, channel_order, segs, flags, k, dst);
+        if (display == WHENET_DISPLAY_FULL) {
+            int32_t origin[3][2];
+            flags[i] |= overlay_labels(segs + size_t(i) * OVERLAY_SEG_INTS, flags[i], ypr[3 * i], ypr[3 * i + 1], ypr[3 * i + 2],
+                                       lines.data() + size_t(i) * 3, origin);
+        }
+    }
+    overlay_paint_host(frame, fh, fw, channel_order, segs, flags, k, dst, lines.empty() ? nullptr : lines.data());
 }
 
 }  // namespace whenet

@@ -116,6 +116,11 @@ _PROTOS = {
     "whenet_annotate_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC)]),
     "whenet_op_annotate": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC)]),
     "whenet_frame_annotate": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SurfaceC), _P]),
+    "whenet_overlay_labels": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, _P, _P, C.POINTER(C.c_int32)]),
+    "whenet_overlay_glyph": (C.c_int, [C.c_int, _P]),
+    "whenet_annotate_host_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC), C.c_int]),
+    "whenet_op_annotate_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC), C.c_int]),
+    "whenet_frame_annotate_ex": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SurfaceC), _P, C.c_int]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -420,6 +425,47 @@ def yuv_to_bgr_host(desc: YuvFrameC) -> np.ndarray:
 
 SURF_PACKED = 2                                # WHENET_SURF_PACKED, beside YUV_NV12 / YUV_I420
 MAX_OVERLAY_HEADS = 256
+DISPLAY_SIMPLE, DISPLAY_FULL = 0, 1            # WHENET_DISPLAY_SIMPLE / _FULL: demo_video.py's --display
+OVERLAY_GLYPHS = "0123456789achiloprtwy: -."   # WHENET_OVERLAY_GLYPHS: the characters of the labels' font
+
+
+def display_code(display) -> int:
+    """'simple' | 'full' -> WHENET_DISPLAY_SIMPLE | WHENET_DISPLAY_FULL; anything else is a ValueError."""
+    if display == "simple":
+        return DISPLAY_SIMPLE
+    if display == "full":
+        return DISPLAY_FULL
+    raise ValueError(f"display must be 'simple' or 'full', got {display!r}")
+
+
+def overlay_labels(rect, yaw: float, pitch: float, roll: float):
+    """The labels of one head (include/whenet_hip.h, LABELS): window (y0, x0, y1, x1) and float32 angles in degrees ->
+    (the three texts 'yaw: 10.0', 'pitch: -5.0', 'roll: 2.0', their baseline-left origins int32 [3,2] as (x, y), flags: 1 rectangle |
+    2 axes | 4 labels).  Without the 4 the texts are empty.  Pure host arithmetic inside the library (no GPU needed)."""
+    lib = load()
+    r = np.ascontiguousarray(rect, np.int32).reshape(4)
+    text = C.create_string_buffer(48)
+    origin = np.zeros((3, 2), np.int32)
+    flags = C.c_int32(0)
+    rc = lib.whenet_overlay_labels(_ptr(r), float(np.float32(yaw)), float(np.float32(pitch)), float(np.float32(roll)), text, _ptr(origin),
+                                   C.byref(flags))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    raw = text.raw
+    return [raw[16 * i:16 * i + 16].split(b"\0", 1)[0].decode() for i in range(3)], origin, int(flags.value)
+
+
+def overlay_glyph(ch: str) -> np.ndarray:
+    """The strokes of one character of the labels' font: int32 [n,4] rows of x0, y0, x1, y1 relative to the character's origin
+    (y grows downward, the baseline is 0), n = 0..8.  ValueError for a character the font does not have."""
+    lib = load()
+    if not isinstance(ch, str) or len(ch) != 1:
+        raise ValueError(f"glyph: one character, got {ch!r}")
+    segs = np.zeros((8, 4), np.int32)
+    n = lib.whenet_overlay_glyph(ord(ch), _ptr(segs))
+    if n < 0:
+        raise ValueError(f"glyph: {ch!r} is not one of {OVERLAY_GLYPHS!r}")
+    return segs[:n].copy()
 
 
 def overlay_segments(rect, yaw: float, pitch: float, roll: float):
@@ -450,15 +496,15 @@ def overlay_heads(rects, valid, ypr):
     return rects, valid, ypr
 
 
-def annotate_host(frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: bool = True) -> None:
-    """`whenet_annotate_host`: the overlay as pure host arithmetic inside the library (no GPU needed), written into a host surface."""
+def annotate_host(frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: bool = True, display: int = DISPLAY_SIMPLE) -> None:
+    """`whenet_annotate_host_ex`: the overlay as pure host arithmetic inside the library (no GPU needed), written into a host surface."""
     lib = load()
     frame = np.ascontiguousarray(frame, np.uint8)
     if frame.ndim != 3 or frame.shape[2] != 3:
         raise ValueError(f"frame must be uint8 [H,W,3], got {frame.shape}")
     rects, valid, ypr = overlay_heads(rects, valid, ypr)
-    rc = lib.whenet_annotate_host(_ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects), _ptr(valid), _ptr(ypr),
-                                  rects.shape[0], C.byref(surface))
+    rc = lib.whenet_annotate_host_ex(_ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects), _ptr(valid), _ptr(ypr),
+                                     rects.shape[0], C.byref(surface), int(display))
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
 
@@ -1072,19 +1118,19 @@ class Handle:
         self._check(self._lib.whenet_op_dpool(self._h, _ptr(x), n, H, W, c, int(stride), _ptr(out)))
         return out
 
-    def op_annotate(self, frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: bool = True) -> None:
-        """`whenet_op_annotate`: the overlay kernels alone, host to host (works on a postproc handle)."""
+    def op_annotate(self, frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: bool = True, display: int = DISPLAY_SIMPLE) -> None:
+        """`whenet_op_annotate_ex`: the overlay kernels alone, host to host (works on a postproc handle)."""
         frame = np.ascontiguousarray(frame, np.uint8)
         if frame.ndim != 3 or frame.shape[2] != 3:
             raise ValueError(f"frame must be uint8 [H,W,3], got {frame.shape}")
         rects, valid, ypr = overlay_heads(rects, valid, ypr)
-        self._check(self._lib.whenet_op_annotate(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects),
-                                                 _ptr(valid), _ptr(ypr), rects.shape[0], C.byref(surface)))
+        self._check(self._lib.whenet_op_annotate_ex(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects),
+                                                    _ptr(valid), _ptr(ypr), rects.shape[0], C.byref(surface), int(display)))
 
-    def frame_annotate(self, ticket: int, frame_index: int, surface: SurfaceC, stream=None) -> None:
-        """`whenet_frame_annotate`: enqueue the annotated frame of a ticket whose heads are enqueued.  A host surface is complete
+    def frame_annotate(self, ticket: int, frame_index: int, surface: SurfaceC, stream=None, display: int = DISPLAY_SIMPLE) -> None:
+        """`whenet_frame_annotate_ex`: enqueue the annotated frame of a ticket whose heads are enqueued.  A host surface is complete
         when the ticket's collect call returns: the caller keeps its memory alive until then."""
-        self._check(self._lib.whenet_frame_annotate(self._h, int(ticket), int(frame_index), C.byref(surface), _stream(stream)))
+        self._check(self._lib.whenet_frame_annotate_ex(self._h, int(ticket), int(frame_index), C.byref(surface), _stream(stream), int(display)))
 
     def collect(self, ticket: int, n: int, want_logits: bool = False):
         ypr = np.empty((n, 3), np.float32)

@@ -379,7 +379,7 @@ class FramePipeline:
         ypr, _, _ = self._h.collect(ticket, k)
         return rects, ypr[:, 0].copy(), ypr[:, 1].copy(), ypr[:, 2].copy()
 
-    def annotate(self, out, stream=None) -> None:
+    def annotate(self, out, stream=None, display: str = "simple") -> None:
         """The annotated frame of the frame submitted last -- every head's window as a rectangle and its pose as three axes
         (demo_video.py:26-29, utils.py:13-43; `whenet_hip.overlay`) -- enqueued behind its forward; returns without waiting.  Call
         it once, after `submit()`, `heads()` or `detect_heads()`, before the next `begin()` and before that frame's `collect()`.
@@ -389,8 +389,11 @@ class FramePipeline:
         written in place: with `stream` (an integer stream handle) the kernel waits for what was enqueued on it before the call
         and work enqueued on it afterwards sees the annotated surface; without it the surface is complete when `collect()`
         returns.  Anything else -- a read-only array, another shape, CHW, float -- is a ValueError, never a silent copy.  The
-        values `collect()` returns are unchanged."""
+        values `collect()` returns are unchanged.  `display="full"` adds the three text lines of demo_video.py's `--display full`
+        to every head ('yaw: 10.0', 'pitch: -5.0', 'roll: 2.0' at the window's corner; `whenet_hip.overlay.labels`); the default
+        paints exactly what it painted before."""
         from .overlay import surface_of
+        extra = {"display": _lib.DISPLAY_FULL} if _lib.display_code(display) == _lib.DISPLAY_FULL else {}
         if not self._pending or self._pending[-1][1] is _CLIP:
             raise ValueError("annotate: no frame with its heads enqueued (submit(), heads() or detect_heads() first; a clip takes "
                              "annotate_clip())")
@@ -402,13 +405,14 @@ class FramePipeline:
             raise ValueError("annotate: the frame submitted last is annotated already")
         (h, w), = self._last_sizes
         surface, _ = surface_of(out, int(h), int(w))
-        self._h.frame_annotate(ticket, 0, surface, stream=stream)
+        self._h.frame_annotate(ticket, 0, surface, stream=stream, **extra)
         self._annotated = ticket
 
-    def annotate_clip(self, outs, stream=None) -> None:
+    def annotate_clip(self, outs, stream=None, display: str = "simple") -> None:
         """`annotate()` for the clip submitted last (after `detect_heads_clip()`, before its `collect_clip()`): `outs` holds one
-        destination per frame of the clip, each as in `annotate()`; `None` leaves a frame out."""
+        destination per frame of the clip, each as in `annotate()`; `None` leaves a frame out; `display` as in `annotate()`."""
         from .overlay import surface_of
+        extra = {"display": _lib.DISPLAY_FULL} if _lib.display_code(display) == _lib.DISPLAY_FULL else {}
         if not self._pending or self._pending[-1][1] is not _CLIP:
             raise ValueError("annotate_clip: no clip with its heads enqueued (detect_heads_clip() first)")
         if self._begun is not None or self._begun_clip is not None:
@@ -424,7 +428,7 @@ class FramePipeline:
         surfaces = [None if o is None else surface_of(o, int(h), int(w), f"outs[{i}]")[0] for i, (o, (h, w)) in enumerate(zip(outs, sizes))]
         for i, surface in enumerate(surfaces):      # (every destination is checked before the first is enqueued)
             if surface is not None:
-                self._h.frame_annotate(ticket, i, surface, stream=stream)
+                self._h.frame_annotate(ticket, i, surface, stream=stream, **extra)
         self._annotated = ticket                   # (after the last call: a clip the library refused part-way can be annotated again,
                                                    #  the library itself refuses the frames that are done)
 

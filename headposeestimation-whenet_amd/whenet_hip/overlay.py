@@ -30,6 +30,20 @@ def segments(rect, yaw: float, pitch: float, roll: float):
     return _lib.overlay_segments(rect, yaw, pitch, roll)
 
 
+def labels(rect, yaw: float, pitch: float, roll: float):
+    """Window (y0, x0, y1, x1) + angles in degrees -> (texts, origins int32 [3,2], flags): the three lines `--display full` writes
+    next to a head -- 'yaw: 10.0', 'pitch: -5.0', 'roll: 2.0', the numbers as the reference's `"{}".format(np.round(a))` prints
+    them -- and the (x, y) each starts at, the arguments of the reference's three `cv2.putText` calls.  flags: 1 rectangle | 2 axes |
+    4 labels; a head without the 4 (angles not finite, or a rounded angle beyond +-9999) has empty texts."""
+    return _lib.overlay_labels(rect, yaw, pitch, roll)
+
+
+def glyph(ch: str):
+    """The strokes of a character of the labels' font (the project's own: include/whenet_hip.h, WHENET_OVERLAY_FONT) as int32
+    [n,4] rows of x0, y0, x1, y1 relative to the character's baseline-left origin, y growing downward."""
+    return _lib.overlay_glyph(ch)
+
+
 def surface_of(out, h: int, w: int, what: str = "out"):
     """A destination of an h x w frame -> (`_lib.SurfaceC`, the object that keeps its memory alive).  ValueError for anything that
     would need a copy or a conversion: a read-only array, another shape or dtype, CHW, pixels that are not packed."""
@@ -94,24 +108,29 @@ def _ypr(yaw, pitch, roll) -> np.ndarray:
     return np.stack(cols, axis=1) if cols[0].shape[0] else np.zeros((0, 3), np.float32)
 
 
-def annotate(model, frame, rects, yaw, pitch, roll, out=None, format="bgr", matrix="bt601", valid=None, bgr: bool = True):
+def annotate(model, frame, rects, yaw, pitch, roll, out=None, format="bgr", matrix="bt601", valid=None, bgr: bool = True,
+             display: str = "simple"):
     """The stage alone, on the device: `frame` uint8 [H,W,3] (BGR unless `bgr=False`) with the k heads `rects` int32 [k,4]
     (y0, x0, y1, x1 as `collect()` returns them) and their angles painted in -> `out` (a host destination; `out=None` allocates one
-    of `format` / `matrix`), which is returned.  `model` is a `whenet.WHENet` or a `_lib.Handle` (a postproc handle will do)."""
+    of `format` / `matrix`), which is returned.  `model` is a `whenet.WHENet` or a `_lib.Handle` (a postproc handle will do).
+    `display="full"` adds the three labels of every head (`labels()`), as demo_video.py's `--display full` does."""
+    code = _lib.display_code(display)
     frame = _frame_u8(frame)
     if out is None:
         out = new_output(frame.shape[0], frame.shape[1], format, matrix)
     surface, _ = surface_of(out, frame.shape[0], frame.shape[1])
     handle = getattr(model, "_handle", model)
-    handle.op_annotate(frame, rects, valid, _ypr(yaw, pitch, roll), surface, bgr=bgr)
+    handle.op_annotate(frame, rects, valid, _ypr(yaw, pitch, roll), surface, bgr=bgr, display=code)
     return out
 
 
-def annotate_host(frame, rects, yaw, pitch, roll, out=None, format="bgr", matrix="bt601", valid=None, bgr: bool = True):
+def annotate_host(frame, rects, yaw, pitch, roll, out=None, format="bgr", matrix="bt601", valid=None, bgr: bool = True,
+                  display: str = "simple"):
     """`annotate()` as pure host arithmetic inside the library (no GPU): the statement the kernels are held to, byte for byte."""
+    code = _lib.display_code(display)
     frame = _frame_u8(frame)
     if out is None:
         out = new_output(frame.shape[0], frame.shape[1], format, matrix)
     surface, _ = surface_of(out, frame.shape[0], frame.shape[1])
-    _lib.annotate_host(frame, rects, valid, _ypr(yaw, pitch, roll), surface, bgr=bgr)
+    _lib.annotate_host(frame, rects, valid, _ypr(yaw, pitch, roll), surface, bgr=bgr, display=code)
     return out

@@ -47,7 +47,9 @@ extern "C" {
  * (still 6 -- YUV 4:2:0 ingest: whenet_yuv_frame_t, whenet_yuv_to_bgr_host, whenet_op_yuv_to_bgr, whenet_frame_begin_yuv,
  * whenet_clip_begin_yuv.  Additions only.)
  * (still 6 -- pose overlay: whenet_surface_t, whenet_overlay_segments, whenet_annotate_host, whenet_op_annotate,
- * whenet_frame_annotate.  Additions only.) */
+ * whenet_frame_annotate.  Additions only.)
+ * (still 6 -- the overlay's labels: whenet_overlay_labels, whenet_overlay_glyph, whenet_annotate_host_ex, whenet_op_annotate_ex,
+ * whenet_frame_annotate_ex.  Additions only.) */
 #define WHENET_ABI_VERSION 6
 #define WHENET_API __attribute__((visibility("default")))
 
@@ -605,8 +607,9 @@ WHENET_API int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t
  * `cv2.rectangle` of its window and `draw_axis` (utils.py:13-43: three `cv2.line`s from the window's centre), then writes the frame
  * out (demo_video.py:60).  The frame, the windows and the angles are in device memory when the forward ends, so the annotated
  * frame is produced there (csrc/overlay.hip) -- into a host array, or into a pitched BGR / NV12 / I420 surface in device memory
- * for an encoder.  Built of the reference's drawing: draw_axis and the rectangle of process_detection.  Not built: putText labels,
- * thickness / colour options, 10-bit surfaces.
+ * for an encoder.  Built of the reference's drawing: the whole of process_detection -- the rectangle, draw_axis and, with
+ * WHENET_DISPLAY_FULL, the three putText labels of `--display full` (LABELS below).  Not built: thickness / colour / font options,
+ * 10-bit surfaces.
  *
  * The overlay, integers only.
  * SEGMENTS OF A HEAD.  Inputs: the window (y0, x0, y1, x1) as whenet_frame_rects / the collect calls return it, and the float32
@@ -633,6 +636,26 @@ WHENET_API int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t
  * 2^14 in magnitude, every difference below 2^15, |v x d| < 2^31 and its square fits a signed 64-bit integer.
  * Primitives are painted head by head in row order; where several cover a pixel the LAST one in that order wins.  Pixels outside
  * the frame are clipped.  The source frame is never modified (the head crops and the letterbox read it).
+ * LABELS (display = WHENET_DISPLAY_FULL; demo_video.py:31-34).  A head paints three lines of text iff it paints its axes (flags
+ * include 2: window valid and in range, all three angles finite) and every rounded angle r satisfies |r| <= 9999; otherwise it
+ * paints no line and its rectangle and axes are unaffected.  Its flags then include 4.
+ *     TEXT.  Line i is "yaw: ", "pitch: " or "roll: " followed by the number the executed reference prints,
+ *     "{}".format(np.round(a)) for the float32 angle a: r = rintf(a) in float32 (round half to even); '-' iff signbit(r), so -0.3
+ *     gives "-0.0"; the decimal digits of |r| without leading zeros; ".0".  2.5 -> "2.0", 3.5 -> "4.0", -179.6 -> "-180.0".  A line
+ *     has at most 14 characters ("pitch: -9999.0").
+ *     ORIGINS.  (x0, y0), (x0, y0 - 15), (x0, y0 - 30) for yaw, pitch, roll, (x0, y0) the window's corner (segments[0], [1]): as in
+ *     OpenCV the baseline-left point of the line.
+ *     FONT, the project's own: restated, unpinned.  OpenCV has never run next to this code and Hershey's stroke data is not part of
+ *     it, so no claim is made about cv2.putText's pixels (FONT_HERSHEY_SIMPLEX, scale 0.4, thickness 1 is what the reference asks
+ *     for).  WHENET_OVERLAY_GLYPHS names the 25 characters, WHENET_OVERLAY_FONT holds for each {n, then 8 rows of x0, y0, x1, y1}:
+ *     its n <= 8 strokes with integer endpoints inside x in [0,5], y in [-9,3] relative to the character's origin, y growing
+ *     downward, the baseline at 0 (only 'p' and 'y' go below it).  The advance is 7 pixels for every character.
+ *     THIN RASTER RULE.  A pixel is painted by a stroke iff its distance to the closed segment is <= 1/2, in the integers of the
+ *     raster rule above: v.d <= 0: iff X = P;  v.d >= L2: iff X = Q;  otherwise iff 4 (v x d)^2 <= L2.  A glyph therefore paints
+ *     only pixels of its own 6 x 13 box, and a pixel belongs to at most one character of a line.
+ *     COLOUR (100, 255, 0) as B, G, R, in the frame's channel order like the axes' colours.
+ *     PAINT ORDER.  Heads in order; within a head the rectangle's sides, X, Y, Z, then the yaw, the pitch and the roll line: a later
+ *     head's rectangle paints over an earlier head's text.
  * BGR -> 4:2:0, the inverse leg of the YUV ingest above.  ch = (h + 1) >> 1, cw = (w + 1) >> 1; the chroma sample (cy, cx) is
  * taken from the sums Rs, Gs, Bs over the four pixels (min(2 cy + dy, h - 1), min(2 cx + dx, w - 1)), dy, dx = 0, 1.  With int32
  * arithmetic and >> an arithmetic shift:
@@ -680,6 +703,36 @@ WHENET_API int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t
 #define WHENET_BGR2YUV_COEFFS {{269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897, 16}, \
                                {191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230, 16}, \
                                {313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262, 0}}
+#define WHENET_DISPLAY_SIMPLE 0  /* demo_video.py --display simple: rectangle and axes */
+#define WHENET_DISPLAY_FULL 1    /* ... full: and the three labels */
+/* the font of the labels: the characters, and for each {n, then 8 rows of x0, y0, x1, y1 (the rows behind the n-th are 0)} */
+#define WHENET_OVERLAY_GLYPHS "0123456789achiloprtwy: -."
+#define WHENET_OVERLAY_FONT { \
+    {8, 1,-8,3,-8, 3,-8,4,-7, 4,-7,4,-1, 4,-1,3,0, 3,0,1,0, 1,0,0,-1, 0,-1,0,-7, 0,-7,1,-8}, \
+    {3, 1,-6,2,-8, 2,-8,2,0, 1,0,3,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {5, 0,-8,4,-8, 4,-8,4,-4, 4,-4,0,-4, 0,-4,0,0, 0,0,4,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {4, 0,-8,4,-8, 4,-8,4,0, 4,0,0,0, 1,-4,4,-4, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {3, 3,-8,0,-3, 0,-3,4,-3, 3,-8,3,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {5, 4,-8,0,-8, 0,-8,0,-4, 0,-4,4,-4, 4,-4,4,0, 4,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {5, 4,-8,0,-8, 0,-8,0,0, 0,0,4,0, 4,0,4,-4, 4,-4,0,-4, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {2, 0,-8,4,-8, 4,-8,1,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {5, 0,-8,4,-8, 4,-8,4,0, 4,0,0,0, 0,0,0,-8, 0,-4,4,-4, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {5, 4,-4,0,-4, 0,-4,0,-8, 0,-8,4,-8, 4,-8,4,0, 4,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {8, 4,-5,4,0, 1,-5,3,-5, 3,-5,4,-4, 4,-1,3,0, 3,0,1,0, 1,0,0,-1, 0,-1,0,-4, 0,-4,1,-5}, \
+    {7, 1,-5,3,-5, 3,-5,4,-4, 4,-1,3,0, 3,0,1,0, 1,0,0,-1, 0,-1,0,-4, 0,-4,1,-5, 0,0,0,0}, \
+    {5, 0,-8,0,0, 0,-4,1,-5, 1,-5,3,-5, 3,-5,4,-4, 4,-4,4,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {4, 1,-5,2,-5, 2,-5,2,0, 1,0,3,0, 2,-7,2,-7, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {2, 2,-8,2,-1, 2,-1,3,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {8, 1,-5,3,-5, 3,-5,4,-4, 4,-4,4,-1, 4,-1,3,0, 3,0,1,0, 1,0,0,-1, 0,-1,0,-4, 0,-4,1,-5}, \
+    {8, 0,-5,0,3, 1,-5,3,-5, 3,-5,4,-4, 4,-4,4,-1, 4,-1,3,0, 3,0,1,0, 1,0,0,-1, 0,-4,1,-5}, \
+    {3, 0,-5,0,0, 0,-3,2,-5, 2,-5,4,-5, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {4, 2,-8,2,-1, 2,-1,3,0, 3,0,4,0, 0,-5,4,-5, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {4, 0,-5,1,0, 1,0,2,-3, 2,-3,3,0, 3,0,4,-5, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {3, 0,-5,2,0, 4,-5,1,3, 1,3,0,3, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {2, 2,-5,2,-4, 2,-1,2,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {1, 0,-4,4,-4, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}, \
+    {2, 2,-1,2,0, 3,-1,3,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0, 0,0,0,0}}
 typedef struct {
     void* plane[3];
     int pitch[3];
@@ -693,6 +746,22 @@ WHENET_API int whenet_annotate_host(const uint8_t* frame, int frame_h, int frame
 WHENET_API int whenet_op_annotate(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
                        const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst);
 WHENET_API int whenet_frame_annotate(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream);
+/* The labels (additions to ABI 6).
+ *   whenet_overlay_labels    pure host: window + float32 angles -> the three NUL-terminated texts, their origins (x, y) and *flags
+ *                  (may be NULL) = what the head paints: 1 rectangle | 2 axes | 4 labels.  Without the 4 the texts are empty.
+ *   whenet_overlay_glyph     pure host: the strokes of character `ch` as rows of x0, y0, x1, y1; returns their number 0..8, or
+ *                  WHENET_EINVAL for a character outside WHENET_OVERLAY_GLYPHS or a NULL pointer.
+ *   whenet_annotate_host_ex, whenet_op_annotate_ex, whenet_frame_annotate_ex: the three calls above with `display` =
+ *                  WHENET_DISPLAY_SIMPLE (their bytes, their cost) or WHENET_DISPLAY_FULL; any other value is WHENET_EINVAL.  The
+ *                  calls without _ex are these with WHENET_DISPLAY_SIMPLE. */
+WHENET_API int whenet_overlay_labels(const int32_t rect[4], float yaw, float pitch, float roll, char text[3][16], int32_t origin[3][2],
+                          int32_t* flags);
+WHENET_API int whenet_overlay_glyph(int ch, int32_t segs[8][4]);
+WHENET_API int whenet_annotate_host_ex(const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
+                            const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst, int display);
+WHENET_API int whenet_op_annotate_ex(whenet_t* h, const uint8_t* frame, int frame_h, int frame_w, int channel_order, const int32_t* rects,
+                          const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst, int display);
+WHENET_API int whenet_frame_annotate_ex(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream, int display);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

@@ -7,9 +7,11 @@
 
 on 16 seeded frames held as resident device planes (uploaded before the clock starts), seeded tiny detector at 416 x 416, seeded
 f16 pose model, depth 2.  `--max-boxes` sets the head slots per frame (1 and 16: with the low score threshold used here the
-seeded detector fills them; the heads painted in the last frame are reported).
+seeded detector fills them; the heads painted in the last frame are reported).  `--display full` lets the annotate arms paint the
+three text labels of every head as well (demo_video.py's `--display full`); every line says which display it ran.
 
   python tools/annotate_ab.py [--sizes 720x1280 1080x1920] [--max-boxes 1 16] [--frames 480] [--rounds 6] [--passes 2]
+  python tools/annotate_ab.py --arms nv12 --display simple full       # the labels' cost: the two displays alternate like two arms
   WHENET_HIP_PKG=/another/checkout/headposeestimation-whenet_amd python tools/annotate_ab.py --arms none --label parent      # the same loop on another build
 
 Every (size, heads, pass, arm) is one child process under its own `timeout`, the arms alternating; the first child that fails ends
@@ -33,10 +35,12 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.environ.get("WHENET_HIP_PKG") or os.path.join(ROOT, "headposeestimation-whenet_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from yuv_ingest_ab import ANCHORS, DETECTOR_SEED, nv12_planes      # noqa: E402
+
+# after the import above: yuv_ingest_ab puts this checkout's package in front of the path, and the other build has to come first
+sys.path.insert(0, os.environ.get("WHENET_HIP_PKG") or os.path.join(ROOT, "headposeestimation-whenet_amd"))
 
 
 def window(fp, begin, annotate, frames, kw, total: int, depth: int):
@@ -69,6 +73,7 @@ def worker(args):
     from whenet_hip import detector_weights as DW, synth
     from whenet_hip.frames import FramePipeline
     from whenet_hip.yuv import YUVFrame
+    from whenet_hip import _lib
     arm, depth, max_boxes = args.arms[0], args.depth, args.max_boxes[0]
     h, w = (int(v) for v in args.sizes[0].split("x"))
     ch, cw = (h + 1) // 2, (w + 1) // 2
@@ -88,18 +93,20 @@ def worker(args):
             arrays = [np.empty((h, w, 3), np.uint8) for _ in range(depth)]
             if not hasattr(fp, "annotate"):
                 assert arm == "none", "this build has no annotate"
-            annotate = {"none": lambda i: None, "nv12": lambda i: fp.annotate(surfaces[i % depth], stream=stream),
-                        "host": lambda i: fp.annotate(arrays[i % depth])}[arm]
+            display = args.display[0]
+            more = {"display": "full"} if display == "full" else {}      # (a build without the keyword still runs `simple`)
+            annotate = {"none": lambda i: None, "nv12": lambda i: fp.annotate(surfaces[i % depth], stream=stream, **more),
+                        "host": lambda i: fp.annotate(arrays[i % depth], **more)}[arm]
             torch.cuda.synchronize()
             window(fp, begin, annotate, frames, kw, max(20, 4 * depth), depth)              # warm-up: allocations, graph captures
             res = [window(fp, begin, annotate, frames, kw, args.frames, depth) for _ in range(args.rounds)]
         fps = [r[0] for r in res]
         med = lambda i: round(statistics.median([x for r in res for x in r[i]]) * 1e3, 4)
-        print(json.dumps({"arm": arm, "frame": [h, w], "max_boxes": max_boxes, "depth": depth, "frames": args.frames, "rounds": args.rounds,
+        print(json.dumps({"arm": arm, "display": display if arm != "none" else None, "frame": [h, w], "max_boxes": max_boxes, "depth": depth, "frames": args.frames, "rounds": args.rounds,
                           "fps_median": round(statistics.median(fps), 1), "fps_min": round(min(fps), 1), "fps_max": round(max(fps), 1),
                           "us_per_frame_median": round(1e6 / statistics.median(fps), 1), "annotate_call_ms_median": med(2),
                           "enqueue_ms_median": med(3), "latency_ms_median": med(1), "heads_last_frame": res[-1][4],
-                          "build": args.label}), flush=True)
+                          "build": args.label, "library": os.path.relpath(os.path.realpath(_lib.LIB_PATH), ROOT)}), flush=True)
     finally:
         m.close()
 
@@ -108,6 +115,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arms", nargs="+", default=["none", "nv12", "host"], choices=["none", "nv12", "host"])
     ap.add_argument("--sizes", nargs="+", default=["720x1280", "1080x1920"], help="frame sizes, HxW")
+    ap.add_argument("--display", nargs="+", default=["simple"], choices=["simple", "full"], help="what the annotate arms paint")
     ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709", "jfif"])
     ap.add_argument("--max-boxes", type=int, nargs="+", default=[1, 16])
     ap.add_argument("--depth", type=int, default=2)
@@ -126,13 +134,13 @@ def main():
     for size in args.sizes:
         for boxes in args.max_boxes:
             for _ in range(args.passes):
-                for arm in args.arms:
+                for arm, display in [(a, d) for a in args.arms for d in (args.display if a != "none" else args.display[:1])]:
                     cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--worker", "--arms", arm,
-                           "--sizes", size, "--matrix", args.matrix, "--max-boxes", str(boxes), "--depth", str(args.depth), "--size",
+                           "--display", display, "--sizes", size, "--matrix", args.matrix, "--max-boxes", str(boxes), "--depth", str(args.depth), "--size",
                            *map(str, args.size), "--frames", str(args.frames), "--rounds", str(args.rounds), "--score", str(args.score), "--label", args.label]
                     rc = subprocess.run(cmd).returncode
                     if rc != 0:                  # a fault, an abort or a time limit: nothing more is started on the GPU
-                        print(f"annotate_ab: {size} max_boxes {boxes} arm {arm} ended with status {rc}; stopping", file=sys.stderr)
+                        print(f"annotate_ab: {size} max_boxes {boxes} arm {arm} display {display} ended with status {rc}; stopping", file=sys.stderr)
                         return rc
     return 0
 

@@ -2,7 +2,10 @@
 // as a stand-alone program for the HOST sanitizers: it walks a case table -- the frame sizes of tests/overlay_cases.py, windows
 // inside, across and outside the frame, NaN / Inf angles, invalid heads, 64 and 256 overlapping heads, both channel orders, every
 // format and matrix, pitches above the row bytes -- with every plane in its own exact-size heap block, so that a byte read or
-// written outside a row's bytes is a sanitizer report.  It needs no GPU and no HIP runtime and is never loaded into Python.
+// written outside a row's bytes is a sanitizer report.  Every case runs with WHENET_DISPLAY_SIMPLE and with WHENET_DISPLAY_FULL; the
+// labels add heads whose lines leave the frame on every side, angles at the edges of the printed range, the label lines of a sweep
+// of float32 angles, and the font's compile-time rows against the strokes rastered here, three pixels beyond every glyph's box.
+// It needs no GPU and no HIP runtime and is never loaded into Python.
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/probes/overlay_host_probe.cpp \
 //       -o tools/probes/overlay_host_probe && tools/probes/overlay_host_probe
@@ -34,7 +37,7 @@ struct Heads {
     int k() const { return int(valid.size()); }
 };
 
-long run(const std::vector<uint8_t>& frame, int h, int w, int order, const Heads& heads, int format, int matrix, int extra) {
+long run(const std::vector<uint8_t>& frame, int h, int w, int order, const Heads& heads, int format, int matrix, int extra, int display) {
     int rows[3], row_bytes[3];
     const int planes = overlay_surface_planes(format, h, w, rows, row_bytes);
     std::unique_ptr<uint8_t[]> mem[3];
@@ -54,7 +57,7 @@ long run(const std::vector<uint8_t>& frame, int h, int w, int order, const Heads
         std::exit(1);
     }
     overlay_annotate_host(frame.data(), h, w, order, heads.rects.data(), heads.with_valid ? heads.valid.data() : nullptr, heads.ypr.data(),
-                          heads.k(), s);
+                          heads.k(), s, display);
     long sum = 0;
     for (int p = 0; p < planes; ++p)
         for (int r = 0; r < rows[p]; ++r) {
@@ -80,7 +83,7 @@ int main() {
         const int h = hw[0], w = hw[1];
         std::vector<uint8_t> frame(size_t(h) * w * 3);
         for (uint8_t& b : frame) b = uint8_t(rnd() >> 24);
-        std::vector<Heads> table(9);
+        std::vector<Heads> table(10);
         table[1].add(0, 0, h, w, 0, 0, 0);
         table[2].add(h / 4, w / 4, 3 * h / 4 + 1, 3 * w / 4 + 1, 30.5f, -20.25f, 45.f);
         table[3].add(-h, -w, 2 * h, 2 * w, 40, 30, 80);                       // endpoints outside every edge
@@ -102,13 +105,22 @@ int main() {
             table[8].add(y0, x0, y0 + rnd_in(0, 60), x0 + rnd_in(0, 80), float(rnd_in(-180, 180)) + .5f, float(rnd_in(-99, 99)), float(rnd_in(-99, 99)),
                          rnd() % 10 != 0);
         }
+        table[9].add(3, -30, h, w, -179.6f, 9999.4f, -9999.4f);                // lines off the top and the left edge, 14 characters
+        table[9].add(h - 1, w - 3, h + 20, w + 40, -0.3f, 2.5f, 99.49999f);    // ... off the right edge
+        table[9].add(h + 5, 0, h + 9, 4, 1, 2, 3);                            // ... the yaw line below the frame
+        table[9].add(0, 0, h, w, 9999.5f, 0, 0);                              // a rounded angle of 10000: no line
+        table[9].add(-4096, -4096, 8192, 8192, 1, 2, 3);
+        table[9].add(8192, 8192, 8192, 8192, 1, 2, 3);
         for (size_t c = 0; c < table.size(); ++c)
             for (int format : {WHENET_SURF_PACKED, WHENET_YUV_NV12, WHENET_YUV_I420})
                 for (int matrix = 0; matrix < WHENET_YUV_MATRICES; ++matrix) {
                     if (format == WHENET_SURF_PACKED && matrix > 0) continue;
                     const int extras[4] = {0, 1, 5, 64};
-                    total += run(frame, h, w, (int(c) + matrix) & 1 ? WHENET_RGB : WHENET_BGR, table[c], format, matrix, extras[(c + size_t(matrix)) & 3]);
-                    ++runs;
+                    for (int display : {WHENET_DISPLAY_SIMPLE, WHENET_DISPLAY_FULL}) {
+                        total += run(frame, h, w, (int(c) + matrix) & 1 ? WHENET_RGB : WHENET_BGR, table[c], format, matrix,
+                                     extras[(c + size_t(matrix)) & 3], display);
+                        ++runs;
+                    }
                 }
     }
     // the segments alone, at the corners of their range and on angles of every kind
@@ -119,6 +131,37 @@ int main() {
         for (float y : angles)
             for (float p : angles)
                 for (float r : angles) total += overlay_segments(rect, 1, double(y), double(p), double(r), seg) + seg[6] + seg[15];
+    // the font: the rows built at compile time are the strokes under the thin rule, and no stroke paints outside its glyph's box
+    for (int g = 0; g < OVERLAY_GLYPHS; ++g)
+        for (int y = OVERLAY_GLYPH_TOP - 3; y < OVERLAY_GLYPH_TOP + OVERLAY_GLYPH_ROWS + 3; ++y)
+            for (int x = -3; x < OVERLAY_GLYPH_W + 3; ++x) {
+                bool hit = false;
+                for (int s = 0; s < OVERLAY_FONT.seg[g][0]; ++s) {
+                    const int8_t* e = OVERLAY_FONT.seg[g] + 1 + 4 * s;
+                    hit = hit || overlay_hit(e[0], e[1], e[2], e[3], x, y, OVERLAY_REACH_THIN);
+                }
+                const bool inside = x >= 0 && x < OVERLAY_GLYPH_W && y >= OVERLAY_GLYPH_TOP && y < OVERLAY_GLYPH_TOP + OVERLAY_GLYPH_ROWS;
+                const bool row = inside && ((overlay_glyph_row(g, y - OVERLAY_GLYPH_TOP) >> x) & 1u);
+                if (hit != row) {
+                    std::printf("glyph %d: pixel (%d, %d) is %d by its strokes, %d by its rows\n", g, x, y, int(hit), int(row));
+                    return 1;
+                }
+            }
+    // the label lines of a sweep of float32 angles: every eighth up to +-10025, and angles of every kind
+    const float kinds[] = {0.f, -0.f, 1e-45f, -1e-45f, 9999.49f, 9999.5f, -9999.5f, 1e30f, -1e30f, 3.4e38f, nan, inf, -inf};
+    OverlayLine line{};
+    for (int k8 = -80200; k8 <= 80200; ++k8)
+        for (int l = 0; l < 3; ++l) {
+            const bool ok = overlay_label_line(l, float(k8) / 8.f, line);
+            const int n = overlay_line_length(line);
+            if (n > OVERLAY_LINE_CHARS || (ok && n < 8) || (!ok && n != 0)) {
+                std::printf("label line %d of %g: length %d\n", l, double(k8) / 8, n);
+                return 1;
+            }
+            for (int i = 0; i < n; ++i) total += overlay_line_glyph(line, i) < OVERLAY_GLYPHS ? 1 : 1 << 20;
+        }
+    for (float a : kinds)
+        for (int l = 0; l < 3; ++l) total += overlay_label_line(l, a, line) + overlay_line_length(line);
     std::printf("overlay_host_probe: %d annotate runs, checksum %ld: clean\n", runs, total);
     return 0;
 }
