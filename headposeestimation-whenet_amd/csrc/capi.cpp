@@ -932,6 +932,70 @@ int whenet_frame_annotate_ex(whenet_t* h, int ticket, int frame_index, const whe
     });
 }
 
+// ---- JPEG encoder (jpeg.hip, jpeg_host.h, engine_post.cpp) ----
+int whenet_jpeg_header(int h, int w, int quality, uint8_t* out, int cap, int32_t qtables[2][64]) {
+    const char* bad = whenet::jpeg_check_size(h, w, quality);
+    if (bad == nullptr && out != nullptr && cap < whenet::JPEG_HEADER_BYTES) bad = "the header has 629 bytes, the capacity is below that";
+    if (bad != nullptr) {
+        g_create_error = std::string("jpeg_header: ") + bad;
+        return WHENET_EINVAL;
+    }
+    whenet::JpegTables t;
+    whenet::jpeg_build_tables(h, w, quality, t);
+    if (out) std::memcpy(out, t.header, whenet::JPEG_HEADER_BYTES);
+    if (qtables) std::memcpy(qtables, t.q, sizeof(t.q));
+    return whenet::JPEG_HEADER_BYTES;
+}
+
+int64_t whenet_jpeg_bound(int h, int w) {
+    if (const char* bad = whenet::jpeg_check_size(h, w, WHENET_JPEG_DEFAULT_QUALITY)) {
+        g_create_error = std::string("jpeg_bound: ") + bad;
+        return WHENET_EINVAL;
+    }
+    return whenet::jpeg_bound(h, w);
+}
+
+int whenet_jpeg_encode_host(const whenet_surface_t* src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size) {
+    try {
+        const char* bad = whenet::jpeg_check(src, h, w, channel_order, quality, out, cap, size);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_encode_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(src->on_device == 0, WHENET_EINVAL, "jpeg_encode_host: the surface must be host memory (on_device = 0)");
+        std::unique_ptr<whenet::JpegTables> t(new whenet::JpegTables);
+        whenet::jpeg_build_tables(h, w, quality, *t);
+        *size = whenet::jpeg_encode_host(whenet::jpeg_source(*src, h, w, channel_order), *t, out, cap);
+        WHENET_REQUIRE(*size <= cap, WHENET_EOVERFLOW,
+                       "jpeg_encode_host: the stream has " + std::to_string(*size) + " bytes, the capacity is " + std::to_string(cap));
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
+    }
+}
+
+int whenet_op_jpeg_encode(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, uint8_t* out, int64_t cap,
+                          int64_t* size) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(src != nullptr, WHENET_EINVAL, "op_jpeg_encode: NULL argument");
+        e.op_jpeg_encode(*src, hh, ww, channel_order, quality, out, cap, size);
+    });
+}
+
+int whenet_jpeg_encode_device(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, void* dst, int64_t cap,
+                              int64_t* dsize, void* stream) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(src != nullptr, WHENET_EINVAL, "jpeg_encode_device: NULL argument");
+        e.jpeg_encode_device(*src, hh, ww, channel_order, quality, dst, cap, dsize, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size,
+                               int32_t* status) {
+    return guarded(h, [&](whenet::Engine&) {
+        const int idx = ticket % MAX_INFLIGHT_ENGINES;
+        WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "frame_annotate_jpeg: unknown ticket " + std::to_string(ticket));
+        h->at(size_t(idx)).frame_annotate_jpeg(ticket / MAX_INFLIGHT_ENGINES, frame_index, display, quality, out, cap, size, status);
+    });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

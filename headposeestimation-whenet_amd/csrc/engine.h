@@ -335,6 +335,18 @@ class Engine {
     void frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream, int display);
     void op_annotate(const uint8_t* frame, int fh, int fw, int channel_order, const int32_t* rects, const int32_t* valid, const float* ypr,
                      int k, const whenet_surface_t& dst, int display);
+    // JPEG ENCODER (jpeg.hip; the contract is in include/whenet_hip.h).  op_jpeg_encode: the kernels alone, host to host: the planes
+    // are uploaded tight, the stream lands between two guard zones and min(size, cap) bytes of it go to the caller; the host waits.
+    // jpeg_encode_device: ENQUEUE-ONLY on stream_ between the two event hand-overs of the device ingest; the work buffers are the
+    // engine's (grown on the first call for a size), the tables and header of an (h, w, quality) are uploaded once and kept.
+    void op_jpeg_encode(const whenet_surface_t& src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size);
+    void jpeg_encode_device(const whenet_surface_t& src, int h, int w, int channel_order, int quality, void* dst, int64_t cap, int64_t* dsize,
+                            hipStream_t stream);
+    // frame_annotate_jpeg: frame_annotate into a surface of the slot's own (tight I420, JFIF matrix), the encoder behind it on stream_
+    // into a landing buffer in device memory, and a flush kernel that copies min(length, cap) bytes and the length into pinned host
+    // memory -- the total is data-dependent and the call must not wait, so no copy of a size known to the host can stand there.
+    // ENQUEUE-ONLY; the collect call hands the bytes, the length and the status to the caller.  It counts as the frame's one annotate.
+    void frame_annotate_jpeg(int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size, int32_t* status);
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -381,6 +393,22 @@ class Engine {
         };
         std::vector<AnnHost> ann_host;
         StagedBuffer ann_stage[MIXED_MAX_FRAMES];
+        // frame_annotate_jpeg, per frame index: the engine's tight I420 JFIF surface, the stream's landing buffer in device memory
+        // (capacity rounded up to 16 bytes, the int64 length behind it) and its pinned twin, which the flush kernel fills with
+        // min(length, capacity) bytes and the length; and the callers' destinations that the collect call fills from the pinned twins
+        struct JpegStage {
+            DeviceBuffer surface, stream;
+            PinnedBuffer host;
+        };
+        JpegStage jpg_stage[MIXED_MAX_FRAMES];
+        struct JpegHost {
+            uint8_t* out;
+            int64_t cap, staged_cap;
+            int64_t* size;
+            int32_t* status;
+            int frame_index;
+        };
+        std::vector<JpegHost> jpg_host;
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -499,6 +527,8 @@ class Engine {
     void check_device_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes) const;
     void ingest_after_caller(Slot& slot, hipStream_t caller);      // caller's stream -> slot.source -> copy stream
     void ingest_done(Slot& slot, hipStream_t caller);              // copy stream -> slot.copied -> caller's stream
+    // the argument checks of frame_annotate that concern the ticket; returns its slot, the head slots per frame and the frame's geometry
+    Slot& annotate_target(int ticket, int frame_index, int& k, int& fh, int& fw, size_t& frame_off);
     void finish_annotations(Slot& slot);                            // collect calls, behind their wait: staging -> the callers' host surfaces
     void check_surface(const char* what, const whenet_surface_t& dst, int fh, int fw) const;      // overlay_check's surface part + memory kind
     void letterbox_results_to_host(size_t nout, uint8_t* d_u8, float* d_f32, uint8_t* canvas_u8, float* image_f32);
@@ -520,6 +550,16 @@ class Engine {
     void enqueue_detector(DetPlan& p, hipStream_t s);
     int detect_device(const uint8_t* d_frame, int fh, int fw, int swap_rb, int out_h, int out_w, const float* anchors, int num_anchors,
                       float score_threshold, float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes);
+
+    // the JPEG encoder's device-resident tables of (h, w, quality), kept (at most 8 sets: a full cache waits for stream_ and empties)
+    struct JpegTableSet {
+        int h, w, quality;
+        DeviceBuffer d;
+    };
+    std::vector<JpegTableSet> jpeg_tables_;
+    DeviceBuffer jpeg_scratch_;
+    Event jpeg_source_, jpeg_done_;
+    const JpegTables* jpeg_device_tables(int h, int w, int quality);
 
     void open_device(int device_id);
     void require_model() const;

@@ -547,7 +547,8 @@ struct GuardedOutput {
         for (size_t i = 0; i < 2 * GUARD; ++i)
             WHENET_REQUIRE(guards[i] == SENTINEL, WHENET_EHIP, std::string(what) + ": the kernel wrote outside its frames (guard byte " +
                                                                    std::to_string(i) + ")");
-        for (int f = 0; f < nframes; ++f) WHENET_HIP_CHECK(hipMemcpy(out[f], frames() + off[f], off[f + 1] - off[f], hipMemcpyDeviceToHost));
+        for (int f = 0; f < nframes; ++f)
+            if (off[f + 1] > off[f]) WHENET_HIP_CHECK(hipMemcpy(out[f], frames() + off[f], off[f + 1] - off[f], hipMemcpyDeviceToHost));
     }
 };
 }  // namespace
@@ -1160,9 +1161,7 @@ void Engine::op_annotate(const uint8_t* frame, int fh, int fw, int channel_order
                         size_t(row_bytes[p]));
 }
 
-void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream, int display) {
-    DeviceGuard guard(device_);
-    check_display("frame_annotate", display);
+Engine::Slot& Engine::annotate_target(int ticket, int frame_index, int& k, int& fh, int& fw, size_t& frame_off) {
     Slot* found = nullptr;
     for (Slot& s : slots_)
         if (s.busy && s.ticket == ticket) found = &s;
@@ -1179,12 +1178,22 @@ void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t&
                    "frame_annotate: frame index " + std::to_string(frame_index) + " outside 0.." + std::to_string(F - 1));
     WHENET_REQUIRE((slot.ann_mask & (1u << frame_index)) == 0, WHENET_EINVAL,
                    "frame_annotate: frame " + std::to_string(frame_index) + " of ticket " + std::to_string(ticket) + " is annotated already");
-    const int k = slot.ann_kind == Slot::ANN_PLANS ? slot.n : (slot.ann_kind == Slot::ANN_DET ? slot.det_cap : slot.clip_cap);
+    k = slot.ann_kind == Slot::ANN_PLANS ? slot.n : (slot.ann_kind == Slot::ANN_DET ? slot.det_cap : slot.clip_cap);
     WHENET_REQUIRE(k <= OVERLAY_MAX_HEADS, WHENET_EINVAL,
                    "frame_annotate: " + std::to_string(k) + " head slots per frame, the overlay takes at most " + std::to_string(OVERLAY_MAX_HEADS));
     const bool mixed = slot.ann_kind == Slot::ANN_CLIP && slot.clip_mixed;
-    const int fh = mixed ? slot.clip_fh[frame_index] : slot.fh, fw = mixed ? slot.clip_fw[frame_index] : slot.fw;
-    const size_t frame_off = mixed ? slot.clip_off[frame_index] : size_t(frame_index) * size_t(fh) * fw * 3;
+    fh = mixed ? slot.clip_fh[frame_index] : slot.fh, fw = mixed ? slot.clip_fw[frame_index] : slot.fw;
+    frame_off = mixed ? slot.clip_off[frame_index] : size_t(frame_index) * size_t(fh) * fw * 3;
+    return slot;
+}
+
+void Engine::frame_annotate(int ticket, int frame_index, const whenet_surface_t& dst, hipStream_t stream, int display) {
+    DeviceGuard guard(device_);
+    check_display("frame_annotate", display);
+    int k, fh, fw;
+    size_t frame_off;
+    Slot& slot = annotate_target(ticket, frame_index, k, fh, fw, frame_off);
+    const int F = slot.ann_kind == Slot::ANN_CLIP ? slot.clip_f : 1;
     check_surface("frame_annotate", dst, fh, fw);
     int rows[3], row_bytes[3];
     size_t off[4];
@@ -1258,6 +1267,145 @@ void Engine::finish_annotations(Slot& slot) {
                             size_t(row_bytes[p]));
     }
     slot.ann_host.clear();
+    for (const Slot::JpegHost& j : slot.jpg_host) {      // the streams of frame_annotate_jpeg: pinned landing buffer -> the caller
+        const size_t cap16 = (size_t(j.staged_cap) + 15) & ~size_t(15);
+        const uint8_t* src = slot.jpg_stage[j.frame_index].host.as<uint8_t>();
+        long long total = 0;
+        std::memcpy(&total, src + cap16, sizeof(total));
+        if (std::min<long long>(total, j.staged_cap) > 0) std::memcpy(j.out, src, size_t(std::min<long long>(total, j.staged_cap)));
+        *j.size = total;
+        *j.status = total <= j.cap ? WHENET_OK : WHENET_EOVERFLOW;
+    }
+    slot.jpg_host.clear();
+}
+
+// ---- JPEG encoder (jpeg.hip; the contract is in engine.h and include/whenet_hip.h) ----
+void Engine::op_jpeg_encode(const whenet_surface_t& src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size) {
+    DeviceGuard guard(device_);
+    const char* bad = jpeg_check(&src, h, w, channel_order, quality, out, cap, size);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_encode: ") + (bad ? bad : ""));
+    WHENET_REQUIRE(src.on_device == 0, WHENET_EINVAL, "op_jpeg_encode: the surface must be host memory (on_device = 0)");
+    check_surface("op_jpeg_encode", src, h, w);
+    int rows[3], row_bytes[3];
+    size_t off[4];
+    const int planes = tight_surface(src.format, h, w, rows, row_bytes, off);
+    JpegTables tables;
+    jpeg_build_tables(h, w, quality, tables);
+    const JpegScratch lay(h, w);
+    TempBufs tmp;
+    uint8_t* const d_planes = static_cast<uint8_t*>(tmp.get(off[planes]));
+    JpegTables* const d_tables = static_cast<JpegTables*>(tmp.get(sizeof(JpegTables)));
+    void* const d_scratch = tmp.get(lay.bytes);
+    long long* const d_size = static_cast<long long*>(tmp.get(sizeof(long long)));
+    JpegSource s = jpeg_source(src, h, w, channel_order);
+    for (int p = 0; p < planes; ++p) {
+        WHENET_HIP_CHECK(hipMemcpy2DAsync(d_planes + off[p], size_t(row_bytes[p]), src.plane[p], size_t(src.pitch[p]), size_t(row_bytes[p]),
+                                          size_t(rows[p]), hipMemcpyHostToDevice, stream_));
+        s.plane[p] = d_planes + off[p], s.pitch[p] = row_bytes[p];
+    }
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_tables, &tables, sizeof(tables), hipMemcpyHostToDevice, stream_));
+    WHENET_HIP_CHECK(hipMemsetAsync(d_size, 0, sizeof(long long), stream_));
+    // no stream is longer than the bound: a landing buffer of min(cap, bound) bytes answers as one of cap bytes would
+    const int64_t dcap = std::min<int64_t>(cap, jpeg_bound(h, w));
+    const GuardedOutput d_out(size_t(dcap), stream_);
+    launch_jpeg_encode(jpeg_args(s, d_tables, d_scratch, lay, d_out.frames(), dcap, d_size), lay, stream_);
+    WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+    long long total = 0;
+    WHENET_HIP_CHECK(hipMemcpy(&total, d_size, sizeof(total), hipMemcpyDeviceToHost));
+    WHENET_REQUIRE(total >= JPEG_HEADER_BYTES + 2 && total <= jpeg_bound(h, w), WHENET_EHIP,
+                   "op_jpeg_encode: the kernels report a stream of " + std::to_string(total) + " bytes");
+    const size_t span[2] = {0, size_t(std::min<int64_t>(total, dcap))};
+    d_out.to_host(stream_, span, 1, &out, "op_jpeg_encode");
+    *size = total;
+    WHENET_REQUIRE(total <= cap, WHENET_EOVERFLOW,
+                   "op_jpeg_encode: the stream has " + std::to_string(total) + " bytes, the capacity is " + std::to_string(cap));
+}
+
+const JpegTables* Engine::jpeg_device_tables(int h, int w, int quality) {
+    for (const JpegTableSet& t : jpeg_tables_)
+        if (t.h == h && t.w == w && t.quality == quality) return t.d.as<JpegTables>();
+    if (jpeg_tables_.size() >= 8) {      // an earlier call's kernels may still read a set
+        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+        jpeg_tables_.clear();
+    }
+    JpegTables tables;
+    jpeg_build_tables(h, w, quality, tables);
+    JpegTableSet set{h, w, quality, DeviceBuffer()};
+    set.d.reset(sizeof(JpegTables));
+    WHENET_HIP_CHECK(hipMemcpy(set.d.as<void>(), &tables, sizeof(tables), hipMemcpyHostToDevice));
+    jpeg_tables_.push_back(std::move(set));
+    return jpeg_tables_.back().d.as<JpegTables>();
+}
+
+void Engine::jpeg_encode_device(const whenet_surface_t& src, int h, int w, int channel_order, int quality, void* dst, int64_t cap, int64_t* dsize,
+                                hipStream_t stream) {
+    DeviceGuard guard(device_);
+    const char* bad = jpeg_check(&src, h, w, channel_order, quality, dst, cap, dsize);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_encode_device: ") + (bad ? bad : ""));
+    WHENET_REQUIRE(src.on_device == 1, WHENET_EINVAL, "jpeg_encode_device: the surface must be device memory (on_device = 1)");
+    WHENET_REQUIRE(cap <= std::numeric_limits<int>::max(), WHENET_EINVAL, "jpeg_encode_device: a capacity above 2^31 - 1 bytes");
+    check_surface("jpeg_encode_device", src, h, w);
+    if (cap > 0) check_device_plane("jpeg_encode_device: dst", static_cast<const uint8_t*>(dst), 1, int(cap), int(cap));
+    check_device_plane("jpeg_encode_device: dsize", reinterpret_cast<const uint8_t*>(dsize), 1, 8, 8);
+    WHENET_REQUIRE(reinterpret_cast<uintptr_t>(dsize) % 8 == 0, WHENET_EINVAL, "jpeg_encode_device: dsize is not aligned to 8 bytes");
+    // allocations, the tables and the events first: nothing is enqueued yet if one of them fails
+    const JpegScratch lay(h, w);
+    if (lay.bytes > jpeg_scratch_.bytes()) {      // (the buffer in hand may still be read by an earlier call's kernels)
+        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+        jpeg_scratch_.reset(lay.bytes);
+    }
+    const JpegTables* d_tables = jpeg_device_tables(h, w, quality);
+    if (!jpeg_source_) jpeg_source_.create();
+    if (!jpeg_done_) jpeg_done_.create();
+    const JpegArgs a = jpeg_args(jpeg_source(src, h, w, channel_order), d_tables, jpeg_scratch_.as<void>(), lay, dst, cap, dsize);
+    WHENET_HIP_CHECK(hipEventRecord(jpeg_source_, stream));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, jpeg_source_, 0));
+    launch_jpeg_encode(a, lay, stream_);
+    WHENET_HIP_CHECK(hipEventRecord(jpeg_done_, stream_));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream, jpeg_done_, 0));
+}
+
+void Engine::frame_annotate_jpeg(int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size,
+                                 int32_t* status) {
+    DeviceGuard guard(device_);
+    check_display("frame_annotate_jpeg", display);
+    WHENET_REQUIRE(size != nullptr && status != nullptr && (out != nullptr || cap == 0), WHENET_EINVAL, "frame_annotate_jpeg: NULL argument");
+    WHENET_REQUIRE(cap >= 0, WHENET_EINVAL, "frame_annotate_jpeg: negative capacity");
+    WHENET_REQUIRE(quality >= 1 && quality <= 100, WHENET_EINVAL, "frame_annotate_jpeg: quality must be 1..100");
+    int k, fh, fw;
+    size_t frame_off;
+    Slot& slot = annotate_target(ticket, frame_index, k, fh, fw, frame_off);
+    // allocations and the tables first: nothing is enqueued yet if one of them fails
+    int rows[3], row_bytes[3];
+    size_t off[4];
+    (void)tight_surface(WHENET_YUV_I420, fh, fw, rows, row_bytes, off);
+    const long long staged_cap = std::min<long long>(cap, jpeg_bound(fh, fw));      // no stream is longer than the bound
+    const size_t cap16 = (size_t(staged_cap) + 15) & ~size_t(15);
+    Slot::JpegStage& stage = slot.jpg_stage[frame_index];
+    stage.surface.grow(off[3]);
+    stage.stream.grow(cap16 + 16);
+    stage.host.grow(cap16 + 16);
+    const JpegScratch lay(fh, fw);
+    if (lay.bytes > jpeg_scratch_.bytes()) {      // (the buffer in hand may still be read by an earlier call's kernels)
+        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+        jpeg_scratch_.reset(lay.bytes);
+    }
+    const JpegTables* d_tables = jpeg_device_tables(fh, fw, quality);
+    void* h_dev = nullptr;                         // the pinned buffer as the device addresses it
+    WHENET_HIP_CHECK(hipHostGetDevicePointer(&h_dev, stage.host.as<void>(), 0));
+    whenet_surface_t surf{};
+    for (int p = 0; p < 3; ++p) surf.plane[p] = stage.surface.as<uint8_t>() + off[p], surf.pitch[p] = row_bytes[p];
+    surf.format = WHENET_YUV_I420, surf.matrix = WHENET_YUV_JFIF, surf.on_device = 1;
+    // the overlay into the engine's surface (it counts as the frame's one annotate call), the encoder behind it on the same stream,
+    // then min(size, cap) bytes and the size into the pinned buffer: the only bytes that cross the link
+    frame_annotate(ticket, frame_index, surf, nullptr, display);
+    uint8_t* const d_stream = stage.stream.as<uint8_t>();
+    long long* const d_size = reinterpret_cast<long long*>(d_stream + cap16);
+    launch_jpeg_encode(jpeg_args(jpeg_source(surf, fh, fw, WHENET_BGR), d_tables, jpeg_scratch_.as<void>(), lay, d_stream, staged_cap, d_size), lay,
+                       stream_);
+    launch_jpeg_flush(d_stream, h_dev, d_size, staged_cap, reinterpret_cast<long long*>(static_cast<uint8_t*>(h_dev) + cap16), stream_);
+    WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));      // the collect call waits for the stream's bytes as well
+    slot.jpg_host.push_back({out, cap, staged_cap, size, status, frame_index});
 }
 
 }  // namespace whenet

@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "overlay_host.h"
+#include "jpeg_host.h"
 
 namespace whenet {
 
@@ -624,6 +625,41 @@ struct OverlayDrawArgs {
 };
 void launch_overlay_plan(const OverlayPlanArgs& a, hipStream_t stream);
 void launch_overlay_draw(const OverlayDrawArgs& a, hipStream_t stream);
+
+// ---- jpeg.hip ---------------------------------------------------------------------------
+// The baseline JPEG encoder (include/whenet_hip.h, JPEG ENCODER; the arithmetic is jpeg_host.h's) of ONE frame whose planes are in
+// device memory (any alignment, their own pitches).  Five launches behind one memset of `bits`:
+//   dct     8 lanes per 8 x 8 block, 32 blocks per workgroup: samples -> both DCT passes -> quantiser -> coef [R * B][64] (zigzag)
+//   pack    one workgroup per restart interval (MCU row): the blocks' bit lengths, their exclusive scan in steps of 256 blocks with
+//           a carry (an interval has up to 3,072 blocks), then every block's code words OR-ed into the interval's zeroed bit buffer
+//           (atomicOr on dwords: the bytes do not depend on the order); the last byte padded with 1-bits; ulen [R]
+//   count   the 0xFF bytes of every interval -> slen [R] = the interval's stuffed length
+//   write   the header, every interval's stuffed bytes at 629 + sum of (slen + 2) before it, RSTm / EOI, and the total length
+//           into *size -- every byte store checked against `cap`, so a stream that does not fit leaves dst's tail untouched.
+// R = ceil(h / 16) intervals of B = 6 ceil(w / 16) blocks.  JpegScratch lays the work buffers out in one allocation.
+struct JpegScratch {
+    int R, B, interval_dwords;
+    size_t coef, bits, bits_bytes, ulen, slen, bytes;      // byte offsets, the memset's extent, the allocation's size
+    JpegScratch(int h, int w);
+};
+struct JpegArgs {
+    JpegSource src;
+    const JpegTables* tables;      // device memory
+    int16_t* coef;
+    uint32_t* bits;
+    int32_t* ulen;
+    int32_t* slen;
+    uint8_t* dst;                  // cap bytes
+    long long cap;
+    long long* size;               // one int64: the full length
+    int R, B, interval_dwords;
+};
+JpegArgs jpeg_args(const JpegSource& src, const JpegTables* d_tables, void* d_scratch, const JpegScratch& lay, void* d_dst, long long cap,
+                   void* d_size);
+void launch_jpeg_encode(const JpegArgs& a, const JpegScratch& lay, hipStream_t stream);
+// min(*d_size, cap) bytes of a stream, rounded up to whole 16-byte vectors, from d_stream to `to` (both 16-byte aligned and
+// ceil(cap / 16) vectors long), and *d_size to *to_size: `to` may be pinned host memory as the device addresses it
+void launch_jpeg_flush(const void* d_stream, void* to, const long long* d_size, long long cap, long long* to_size, hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16

@@ -13,6 +13,7 @@ import numpy as np
 ABI_VERSION = 6
 F32, F16, F32S = 0, 1, 2          # include/whenet_hip.h WHENET_F32 / WHENET_F16 / WHENET_F32S
 OK, ENOENT, EIO, ENOMEM, ENODEV, EINVAL, EFORMAT, EHIP = 0, -2, -5, -12, -19, -22, -74, -1000
+EOVERFLOW = -75                   # WHENET_EOVERFLOW: the result does not fit the caller's capacity
 MAX_INFLIGHT = 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -121,6 +122,12 @@ _PROTOS = {
     "whenet_annotate_host_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC), C.c_int]),
     "whenet_op_annotate_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(SurfaceC), C.c_int]),
     "whenet_frame_annotate_ex": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SurfaceC), _P, C.c_int]),
+    "whenet_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "whenet_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
+    "whenet_jpeg_encode_host": (C.c_int, [C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "whenet_op_jpeg_encode": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "whenet_jpeg_encode_device": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    "whenet_frame_annotate_jpeg": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -507,6 +514,51 @@ def annotate_host(frame: np.ndarray, rects, valid, ypr, surface: SurfaceC, bgr: 
                                      rects.shape[0], C.byref(surface), int(display))
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+
+
+JPEG_HEADER_BYTES = 629           # WHENET_JPEG_HEADER_BYTES
+JPEG_DEFAULT_QUALITY = 95
+
+
+class CapacityError(RuntimeError):
+    """WHENET_EOVERFLOW: a result that does not fit the capacity it was given; `needed` is the size it has."""
+
+    def __init__(self, needed: int, msg: str):
+        super().__init__(msg)
+        self.needed = int(needed)
+
+
+def jpeg_header(h: int, w: int, quality: int = JPEG_DEFAULT_QUALITY):
+    """`whenet_jpeg_header`: (the 629 header bytes SOI..SOS of an h x w stream, the two scaled quantiser tables int32 [2,64] in
+    natural order).  Pure host arithmetic inside the library (no GPU needed)."""
+    lib = load()
+    out = np.empty(JPEG_HEADER_BYTES, np.uint8)
+    q = np.empty((2, 64), np.int32)
+    n = lib.whenet_jpeg_header(int(h), int(w), int(quality), _ptr(out), out.size, _ptr(q))
+    if n < 0:
+        raise_for(n, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return out[:n].tobytes(), q
+
+
+def jpeg_bound(h: int, w: int) -> int:
+    """`whenet_jpeg_bound`: a capacity no stream of an h x w frame exceeds."""
+    lib = load()
+    n = int(lib.whenet_jpeg_bound(int(h), int(w)))
+    if n < 0:
+        raise_for(n, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return n
+
+
+def jpeg_encode_host(surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, out: np.ndarray):
+    """`whenet_jpeg_encode_host` into the uint8 array `out` (its size is the capacity): (return code, the stream's full length).
+    The code is OK or EOVERFLOW; anything else raises."""
+    lib = load()
+    size = C.c_int64(0)
+    rc = lib.whenet_jpeg_encode_host(C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality), _ptr(out) if out.size else None,
+                                     int(out.size), C.byref(size))
+    if rc not in (OK, EOVERFLOW):
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return rc, int(size.value)
 
 
 def normalise_lut() -> np.ndarray:
@@ -1126,6 +1178,30 @@ class Handle:
         rects, valid, ypr = overlay_heads(rects, valid, ypr)
         self._check(self._lib.whenet_op_annotate_ex(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects),
                                                     _ptr(valid), _ptr(ypr), rects.shape[0], C.byref(surface), int(display)))
+
+    def op_jpeg_encode(self, surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, out: np.ndarray):
+        """`whenet_op_jpeg_encode`: the encoder's kernels alone, host to host (works on a postproc handle), into the uint8 array
+        `out` (its size is the capacity): (return code OK or EOVERFLOW, the stream's full length)."""
+        size = C.c_int64(0)
+        rc = self._lib.whenet_op_jpeg_encode(self._h, C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality),
+                                             _ptr(out) if out.size else None, int(out.size), C.byref(size))
+        if rc != EOVERFLOW:
+            self._check(rc)
+        return rc, int(size.value)
+
+    def jpeg_encode_device(self, surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, dst: int, cap: int, dsize: int, stream=None) -> None:
+        """`whenet_jpeg_encode_device`: enqueue the encoder on a surface in device memory; `dst` (cap bytes) and `dsize` (one int64)
+        are device addresses.  The host does not wait."""
+        self._check(self._lib.whenet_jpeg_encode_device(self._h, C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality),
+                                                        _P(int(dst)), int(cap), _P(int(dsize)), _stream(stream)))
+
+    def frame_annotate_jpeg(self, ticket: int, frame_index: int, display: int, quality: int, out: np.ndarray, result: np.ndarray) -> None:
+        """`whenet_frame_annotate_jpeg`: enqueue the annotated frame of a ticket as a JPEG stream into the uint8 array `out` (its size
+        is the capacity); result = int64 [2]: the stream's length and the status.  Both are complete when the ticket's collect call
+        returns and must stay alive until then."""
+        status = result[1:].view(np.int32)
+        self._check(self._lib.whenet_frame_annotate_jpeg(self._h, int(ticket), int(frame_index), int(display), int(quality),
+                                                         _ptr(out) if out.size else None, int(out.size), _ptr(result), _ptr(status)))
 
     def frame_annotate(self, ticket: int, frame_index: int, surface: SurfaceC, stream=None, display: int = DISPLAY_SIMPLE) -> None:
         """`whenet_frame_annotate_ex`: enqueue the annotated frame of a ticket whose heads are enqueued.  A host surface is complete

@@ -80,6 +80,31 @@ def scatter_clip(counts, boxes, scores, classes, rects, valid, row, ypr, detecti
     return out
 
 
+class JpegFrame:
+    """The JPEG stream of one annotated frame (`FramePipeline.annotate_jpeg`): `width`, `height`; `tobytes()` after the frame's
+    collect call.  It owns the memory the library writes into."""
+
+    def __init__(self, width: int, height: int, capacity: int):
+        if capacity < 0:
+            raise ValueError(f"capacity must not be negative, got {capacity}")
+        self.width, self.height = width, height
+        self._out = np.empty(capacity, np.uint8)
+        self._result = np.zeros(2, np.int64)       # the stream's length; the status (an int32 in the first half)
+        self._done = False
+
+    @property
+    def ready(self) -> bool:
+        return self._done
+
+    def tobytes(self) -> bytes:
+        if not self._done:
+            raise ValueError("JpegFrame.tobytes(): the frame is not collected yet (collect() / collect_clip() first)")
+        size, status = int(self._result[0]), int(self._result[1:].view(np.int32)[0])
+        if status == _lib.EOVERFLOW:
+            raise _lib.CapacityError(size, f"the JPEG stream has {size} bytes, the capacity is {self._out.size}")
+        return self._out[:size].tobytes()
+
+
 class FramePipeline:
     """`with FramePipeline(model) as fp:` ... `fp.submit(frame_bgr, bboxes)` ... `fp.collect()`.
 
@@ -293,6 +318,7 @@ class FramePipeline:
             raise ValueError("collect_clip: the oldest submission in flight is not a clip: collect() returns it")
         res = self._h.collect_clip(ticket, fk[0], fk[1])
         self._pending.popleft()
+        self._finish_jpeg(ticket)
         counts, boxes, scores, classes, rects, valid, row, ypr, _, _, used, over = res
         return scatter_clip(counts, boxes, scores, classes, rects, valid, row, ypr, detections), (used, over)
 
@@ -369,6 +395,7 @@ class FramePipeline:
         if rects is None:
             boxes, scores, classes, rects, valid, ypr, _, _ = self._h.collect_detect(ticket, cap)
             self._pending.popleft()
+            self._finish_jpeg(ticket)
             keep = valid != 0
             res = (np.ascontiguousarray(rects[keep]), ypr[keep, 0].copy(), ypr[keep, 1].copy(), ypr[keep, 2].copy())
             return res + (boxes, scores, classes, valid) if detections else res
@@ -377,6 +404,7 @@ class FramePipeline:
         self._pending.popleft()
         k = rects.shape[0]
         ypr, _, _ = self._h.collect(ticket, k)
+        self._finish_jpeg(ticket)
         return rects, ypr[:, 0].copy(), ypr[:, 1].copy(), ypr[:, 2].copy()
 
     def annotate(self, out, stream=None, display: str = "simple") -> None:
@@ -431,6 +459,57 @@ class FramePipeline:
                 self._h.frame_annotate(ticket, i, surface, stream=stream, **extra)
         self._annotated = ticket                   # (after the last call: a clip the library refused part-way can be annotated again,
                                                    #  the library itself refuses the frames that are done)
+
+    _jpeg = None                   # ticket -> the JpegFrames of annotate_jpeg / annotate_clip_jpeg, until its collect call
+
+    def _finish_jpeg(self, ticket) -> None:
+        for f in (self._jpeg.pop(ticket, ()) if self._jpeg else ()):
+            f._done = True
+
+    def _jpeg_frame(self, ticket, index, h, w, quality, display, capacity) -> "JpegFrame":
+        from . import jpeg
+        f = JpegFrame(int(w), int(h), jpeg.bound(int(h), int(w)) if capacity is None else int(capacity))
+        self._h.frame_annotate_jpeg(ticket, index, _lib.display_code(display), quality, f._out, f._result)
+        if self._jpeg is None:
+            self._jpeg = {}
+        self._jpeg.setdefault(ticket, []).append(f)
+        return f
+
+    def annotate_jpeg(self, quality: int = 95, display: str = "simple", capacity=None) -> "JpegFrame":
+        """`annotate()` with the annotated frame compressed where it lies: the overlay goes into an I420 JFIF surface in device memory
+        that the library owns, the JPEG encoder (`whenet_hip.jpeg`, csrc/jpeg.hip) runs behind it, and only the stream's bytes come
+        back (demo_video.py:60, `out.write(frame)` into an MJPG writer).  Returns at once; the `JpegFrame`'s `tobytes()` is valid
+        after the frame's `collect()` and raises before it.  `capacity` (default: `whenet_hip.jpeg.bound(h, w)`) is the room for the
+        stream: one that does not fit raises `whenet_hip.jpeg.CapacityError`, naming the needed size, at `tobytes()`.  Call order as
+        `annotate()`: it is the frame's one annotate call.  The values `collect()` returns are unchanged."""
+        if not self._pending or self._pending[-1][1] is _CLIP:
+            raise ValueError("annotate_jpeg: no frame with its heads enqueued (submit(), heads() or detect_heads() first; a clip takes "
+                             "annotate_clip_jpeg())")
+        if self._begun is not None or self._begun_clip is not None:
+            raise ValueError("annotate_jpeg: another frame or clip was begun since: annotate_jpeg() follows the heads of the frame it "
+                             "paints, before the next begin()")
+        ticket = self._pending[-1][0]
+        if self._annotated == ticket:
+            raise ValueError("annotate_jpeg: the frame submitted last is annotated already")
+        (h, w), = self._last_sizes
+        f = self._jpeg_frame(ticket, 0, h, w, quality, display, capacity)
+        self._annotated = ticket
+        return f
+
+    def annotate_clip_jpeg(self, quality: int = 95, display: str = "simple", capacity=None):
+        """`annotate_jpeg()` for every frame of the clip submitted last (after `detect_heads_clip()`, before its `collect_clip()`):
+        a list of one `JpegFrame` per frame, valid after `collect_clip()`."""
+        if not self._pending or self._pending[-1][1] is not _CLIP:
+            raise ValueError("annotate_clip_jpeg: no clip with its heads enqueued (detect_heads_clip() first)")
+        if self._begun is not None or self._begun_clip is not None:
+            raise ValueError("annotate_clip_jpeg: another frame or clip was begun since: it follows detect_heads_clip(), before the "
+                             "next begin")
+        ticket = self._pending[-1][0]
+        if self._annotated == ticket:
+            raise ValueError("annotate_clip_jpeg: the clip submitted last is annotated already")
+        out = [self._jpeg_frame(ticket, i, h, w, quality, display, capacity) for i, (h, w) in enumerate(self._last_sizes)]
+        self._annotated = ticket
+        return out
 
     def process(self, frame: np.ndarray, bboxes):
         """Synchronous form: one frame in, its heads' angles out."""

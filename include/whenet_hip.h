@@ -763,6 +763,77 @@ WHENET_API int whenet_op_annotate_ex(whenet_t* h, const uint8_t* frame, int fram
                           const int32_t* valid, const float* ypr, int k, const whenet_surface_t* dst, int display);
 WHENET_API int whenet_frame_annotate_ex(whenet_t* h, int ticket, int frame_index, const whenet_surface_t* dst, void* stream, int display);
 
+/* ---- JPEG ENCODER: a frame in, a baseline JPEG stream out (additions to ABI 6).  demo_video.py:46-47, :60 store the annotated frame
+ * as Motion-JPEG; the overlay already leaves a JFIF-matrix 4:2:0 surface in device memory, which is a baseline encoder's input
+ * (csrc/jpeg.hip; the arithmetic is csrc/jpeg_host.h's).  Integers only.  The Annex K tables and the zigzag order are the JPEG
+ * standard's (ITU-T T.81), written out as data in csrc/jpeg_host.h.
+ * FORMAT.  Baseline sequential DCT, 8 bit, three components, 4:2:0: Y id 1, 2x2 sampling, quantiser 0, Huffman tables 0; Cb id 2 and
+ * Cr id 3, 1x1, quantiser 1, Huffman tables 1.  The stream, in this order: SOI; APP0 "JFIF\0" version 1.01, units 0, density 1:1,
+ * no thumbnail; two DQT segments (8 bit, zigzag order, table 0 then table 1); SOF0; four DHT segments (DC0, AC0, DC1, AC1: Annex K's
+ * "typical" tables); DRI with the interval ceil(w / 16), ONE RESTART INTERVAL PER MCU ROW; SOS (Ss 0, Se 63, Ah/Al 0); the
+ * entropy-coded data; EOI.  The header (SOI..SOS) has WHENET_JPEG_HEADER_BYTES = 629 bytes and depends on (h, w, quality) only.
+ * SOURCE.  A whenet_surface_t of h x w pixels, sides 1..8192: WHENET_YUV_I420 or WHENET_YUV_NV12 with matrix WHENET_YUV_JFIF (any
+ * other matrix is WHENET_EINVAL: JFIF is full-range BT.601), or WHENET_SURF_PACKED with a channel order, whose planes are BY
+ * DEFINITION those of "BGR -> 4:2:0" above with the JFIF row: encoding a packed frame equals, bit for bit, encoding the I420
+ * surface whenet_annotate_host writes from it.
+ * MCU.  16 x 16 luma pixels, blocks in the order Y00, Y01, Y10, Y11, Cb, Cr.  A sample beyond the right or bottom edge of its plane
+ * (h x w luma, ceil(h/2) x ceil(w/2) chroma) is the last column's or row's.
+ * FORWARD DCT.  T[u][x] = rint(4096 s(u) cos((2x+1) u pi / 16)), s(0) = sqrt(1/8), s(u>0) = 1/2: WHENET_JPEG_DCT below.  With
+ * p = sample - 128, int32 arithmetic and >> an arithmetic shift:
+ *     a[y][u] = sum_x T[u][x] p[y][x]        r[y][u] = (a[y][u] + 256) >> 9
+ *     b[v][u] = sum_y T[v][y] r[y][u]        (the coefficient scaled by 2^15; |b| < 2^25)
+ * QUANTISER.  Annex K's luminance and chrominance tables scaled the IJG way: scale = 5000 / quality (integer division) for quality
+ * < 50, else 200 - 2 quality; Q = clamp((base scale + 50) / 100, 1, 255); quality 1..100.
+ *     k = sign(b) ((|b| + (Q << 14)) / (Q << 15))     (integer division: rounds half away from zero)
+ * AC coefficients are clamped to +-1023; DC needs no clamp.
+ * ENTROPY CODING.  Huffman coding of the DC differences (category + extra bits) and of the (run, size) AC symbols with ZRL and EOB;
+ * no EOB when coefficient 63 is non-zero.  The DC predictors are 0 at the start of every restart interval.  The last byte of an
+ * interval is padded with 1-bits; behind every interval but the last stands RSTm, m = interval index mod 8.  Inside the entropy
+ * data every 0xFF byte is followed by 0x00.
+ *   whenet_jpeg_header  pure host: the header bytes into out (cap >= WHENET_JPEG_HEADER_BYTES) and the two quantiser tables in
+ *                  NATURAL order into qtables (either may be NULL); returns the header's length, or WHENET_EINVAL
+ *   whenet_jpeg_bound   pure host: a capacity no stream of an h x w frame exceeds (WHENET_EINVAL for a side outside 1..8192).  A block
+ *                  is at most 11 + 11 bits of DC and 63 x (16 + 10) bits of AC = 1660 bits; an interval of B = 6 ceil(w / 16)
+ *                  blocks at most U = ceil(1660 B / 8) bytes, 2 U when every byte is stuffed, and 2 more for its RSTm or EOI:
+ *                  bound = 629 + ceil(h / 16) (2 U + 2).
+ *   whenet_jpeg_encode_host  the whole encoder as pure host arithmetic (no GPU): the statement the kernels are held to.  *size is
+ *                  always the stream's full length; when it exceeds cap, nothing beyond out[cap - 1] is written and the call
+ *                  returns WHENET_EOVERFLOW.  src->on_device must be 0; channel_order is read for WHENET_SURF_PACKED only.
+ *   whenet_op_jpeg_encode    the kernels alone, host to host, same arguments and results.  Works on a whenet_create_postproc handle.
+ *   whenet_jpeg_encode_device  source planes, dst (cap bytes) and dsize (one int64: the full length, also on overflow) in the
+ *                  handle's device memory, ENQUEUE-ONLY on the engine's stream and ordered against `stream` by events as the
+ *                  ingest section's ORDER paragraph states; the device-pointer checks of the device ingest apply to every
+ *                  plane, to dst and to dsize; cap <= 2^31 - 1.  A stream that does not fit leaves dst's bytes from cap on untouched.
+   whenet_frame_annotate_jpeg  the annotated frame of a ticket as a JPEG stream: what whenet_frame_annotate_ex does, into an I420
+ *                  JFIF surface in device memory that the engine owns (allocated on the first call for a size), and the encoder
+ *                  behind it on the engine's stream.  ENQUEUE-ONLY.  The stream's length is known on the device only and the call
+ *                  must not wait: the encoder lands the stream in device memory and one more kernel copies min(length, cap) bytes
+ *                  and the length into pinned host memory that the device addresses -- the compressed bytes are all that crosses
+ *                  the link.  out[0 .. min(*size, cap)), *size (always the full length) and *status (WHENET_OK or WHENET_EOVERFLOW)
+ *                  are complete when the ticket's collect call returns; the pointers must stay valid until then.  Call order and
+ *                  WHENET_EINVAL cases as whenet_frame_annotate (and a quality outside 1..100); it counts as the (ticket,
+ *                  frame_index)'s one annotate call; the collect call's own results are bit for bit those of the same submission
+ *                  without it.
+ * WHENET_EINVAL: a NULL argument or plane, a pitch below the row bytes, an unknown format / channel order, a YUV source whose
+ * matrix is not WHENET_YUV_JFIF, a side outside 1..8192, quality outside 1..100, cap < 0. */
+#define WHENET_EOVERFLOW (-75)  /* the result does not fit the caller's capacity; the needed size is reported */
+#define WHENET_JPEG_HEADER_BYTES 629
+#define WHENET_JPEG_DEFAULT_QUALITY 95
+#define WHENET_JPEG_DCT {{1448, 1448, 1448, 1448, 1448, 1448, 1448, 1448}, {2009, 1703, 1138, 400, -400, -1138, -1703, -2009}, \
+                         {1892, 784, -784, -1892, -1892, -784, 784, 1892}, {1703, -400, -2009, -1138, 1138, 2009, 400, -1703}, \
+                         {1448, -1448, -1448, 1448, 1448, -1448, -1448, 1448}, {1138, -2009, 400, 1703, -1703, -400, 2009, -1138}, \
+                         {784, -1892, 1892, -784, -784, 1892, -1892, 784}, {400, -1138, 1703, -2009, 2009, -1703, 1138, -400}}
+WHENET_API int whenet_jpeg_header(int h, int w, int quality, uint8_t* out, int cap, int32_t qtables[2][64]);
+WHENET_API int64_t whenet_jpeg_bound(int h, int w);
+WHENET_API int whenet_jpeg_encode_host(const whenet_surface_t* src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap,
+                            int64_t* size);
+WHENET_API int whenet_op_jpeg_encode(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, uint8_t* out,
+                          int64_t cap, int64_t* size);
+WHENET_API int whenet_jpeg_encode_device(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, void* dst,
+                              int64_t cap, int64_t* dsize, void* stream);
+WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap,
+                               int64_t* size, int32_t* status);
+
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
  * recorded on the chain's stream between consecutive kernel launches; a launch's time is
