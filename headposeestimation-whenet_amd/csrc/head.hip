@@ -3,7 +3,8 @@
 // Reference: /root/reference/whenet.py:10 (GAP over the 7x7x1280 head-conv output),
 // whenet.py:11-13 (three linear Dense heads), utils.py:7-11 (softmax: subtract row max, exp,
 // divide by the sum) and whenet.py:28-33 (expectation over bin indices, *3 - 180 / - 99).
-// "Bin argmax" (north-star) = first index of the maximum logit, as np.argmax.
+// "Bin argmax" (north-star) = first index of the maximum logit, as np.argmax: NaN counts as the maximum and the
+// first NaN wins (0 for a row of NaN, 0 for a row of -inf); the angle of a row that holds NaN, +inf or only -inf is NaN.
 //
 // One workgroup per crop, all f32: 0.1 % of the network's MACs; fused so the 1280 features and
 // the 252 logits never leave the CU.  Fixed reduction orders -> bitwise reproducible.
@@ -15,6 +16,13 @@ namespace whenet {
 namespace {
 
 constexpr int HW = 49;
+
+// np.argmax's order on (value, index) pairs: NaN above every number, then the larger value, then the smaller index.  On a row
+// without NaN or -inf this is `v > mx`, with `oi < mi` among equals: the same maximum, the same index.
+__device__ __forceinline__ void argmax_take(float v, int j, float& mx, int& mi) {
+    const bool vn = v != v, mn = mx != mx;
+    if (vn ? (!mn || j < mi) : (!mn && (v > mx || (v == mx && j < mi)))) { mx = v; mi = j; }
+}
 
 template <typename T>
 __global__ __launch_bounds__(1024) void whenet_heads_kernel(const T* __restrict__ x, const float* __restrict__ feat_in,
@@ -101,13 +109,13 @@ __global__ __launch_bounds__(1024) void whenet_heads_kernel(const T* __restrict_
     int mi = 0x7fffffff;
     for (int j = lane; j < nb; j += 64) {
         const float v = s_logit[lo + j];
-        if (v > mx) { mx = v; mi = j; }
+        argmax_take(v, j, mx, mi);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const float ov = __shfl_xor(mx, off, 64);
         const int oi = __shfl_xor(mi, off, 64);
-        if (ov > mx || (ov == mx && oi < mi)) { mx = ov; mi = oi; }
+        argmax_take(ov, oi, mx, mi);
     }
     // a = exp(x - max); b = sum(a); expectation = sum(a/b * idx)
     float se = 0.0f;
@@ -259,13 +267,13 @@ __global__ __launch_bounds__(FEAT_IN ? 256 : 512) void whenet_heads_split_kernel
     int mi = 0x7fffffff;
     for (int j = lane; j < nb; j += 64) {
         const float v = s_logit[lo + j];
-        if (v > mx) { mx = v; mi = j; }
+        argmax_take(v, j, mx, mi);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const float ov = __shfl_xor(mx, off, 64);
         const int oi = __shfl_xor(mi, off, 64);
-        if (ov > mx || (ov == mx && oi < mi)) { mx = ov; mi = oi; }
+        argmax_take(ov, oi, mx, mi);
     }
     float se = 0.0f;
     float e[2];

@@ -163,8 +163,9 @@ __global__ __launch_bounds__(256) void whenet_stem_mfma_kernel(const uint8_t* __
     }
     auto pack = [](float v) -> uint32_t {
         // hi + lo in binary16 (22 bits kept).  Real-valued input beyond the binary16 range saturates at +-65504
-        // (a normalised pixel of that size is ~3.7 million grey levels): without the clamp hi = inf, lo = nan
-        if constexpr (INF32) v = fminf(fmaxf(v, -65504.0f), 65504.0f);
+        // (a normalised pixel of that size is ~3.7 million grey levels): without the clamp hi = inf, lo = nan.  That is what a
+        // NaN or an infinite input has to give, and fmaxf / fminf would answer NaN with -65504: only finite values are clamped
+        if constexpr (INF32) v = __builtin_isfinite(v) ? fminf(fmaxf(v, -65504.0f), 65504.0f) : v;
         const half_t hi = half_t(v), lo = half_t(v - float(hi));
         return uint32_t(__builtin_bit_cast(unsigned short, hi)) | (uint32_t(__builtin_bit_cast(unsigned short, lo)) << 16);
     };

@@ -22,7 +22,8 @@ Extras that the reference does not have (keyword-only, all optional):
                       as 'f32' (the exact-float32 configuration) at 1.37 x its throughput and 0.9 x its batch-1 latency.  Its
                       precondition is activations inside binary16's range (|x| <= 65504): should a snapshot break it the angles
                       come out NaN, and this class then switches the handle to the exact-f32 kernels (option split_pw = 0) and
-                      repeats the call -- a warning says so
+                      repeats the call -- a warning says so.  A real-valued crop that is itself NaN / Inf returns NaN angles
+                      and changes nothing (WHENet._guarded)
   inflight=1..4       engines of the handle for callers that keep several forwards in flight themselves (whenet_forward_u8_device /
                       submit); one large get_angle call (N >= 256) is cut into 128-crop chunks over the library's own fan-out engines
                       whatever this is (include/whenet_hip.h "fanout_min", "fanout_engines")
@@ -150,30 +151,47 @@ class WHENet:
     FANOUT_MIN = 256          # include/whenet_hip.h "fanout_min": the library cuts larger blocking calls into chunks over its own
                               # fan-out engines (created on the first such call; "inflight" and the other entry points are not touched)
 
-    def _out_of_range(self, ypr) -> bool:
-        """WHENET_F32S splits activations into binary16 hi/lo halves: beyond |x| = 65504 the hi half is inf and the angles NaN (never a
+    def _guarded(self, call, x=None):
+        """call() -> (ypr, argmax, logits) on the handle; x is the real-valued input of the call, None for byte crops.
+
+        WHENET_F32S splits activations into binary16 hi/lo halves: beyond |x| = 65504 the hi half is inf and the angles NaN (never a
         silently wrong number).  Not reachable with EfficientNet-B0 behind BatchNorm in practice; if a snapshot does it, the handle
-        goes over to the exact-float32 kernels for good (option split_pw = 0: bitwise a WHENET_F32 handle)."""
-        if self._dtype != _lib.F32S or np.isfinite(ypr).all():
-            return False
+        goes over to the exact-float32 kernels for good (option split_pw = 0: bitwise a WHENET_F32 handle).  NaN angles alone do
+        not say that this happened:
+          * a real-valued crop that is itself NaN / Inf gives NaN angles under every dtype.  Where every crop with non-finite angles
+            has a non-finite input, the result is returned as it is: no warning, no switch, no second run;
+          * otherwise the call is repeated with the exact-float32 kernels.  The switch stays -- with the warning -- only if that
+            answers every crop whose input is finite with finite angles; if not (a snapshot that overflows float32 too), the
+            handle goes back to f32s, the first result is returned and the warning says so."""
+        res = call()
+        if self._dtype != _lib.F32S:
+            return res
+        bad = ~np.isfinite(res[0]).all(axis=1)
+        if not bad.any():
+            return res
+        clean_in = np.ones(len(bad), bool) if x is None else np.isfinite(x.reshape(len(bad), -1)).all(axis=1)
+        if not (bad & clean_in).any():
+            return res
         import warnings
-        warnings.warn("whenet: activations outside binary16's range with dtype='f32s'; this model now runs the exact-float32 kernels "
-                      "(option split_pw=0)", RuntimeWarning, stacklevel=3)
         self._handle.set_option("split_pw", 0)
-        self._dtype = _lib.F32
-        return True
+        exact = call()
+        if np.isfinite(exact[0][clean_in]).all():
+            warnings.warn("whenet: activations outside binary16's range with dtype='f32s'; this model now runs the exact-float32 "
+                          "kernels (option split_pw=0)", RuntimeWarning, stacklevel=4)
+            self._dtype = _lib.F32
+            return exact
+        self._handle.set_option("split_pw", 1)
+        warnings.warn("whenet: non-finite angles from finite crops with dtype='f32s' and with the exact-float32 kernels alike "
+                      "(the snapshot overflows float32); the model stays f32s and returns them as NaN", RuntimeWarning, stacklevel=4)
+        return res
 
     def _forward(self, u8: np.ndarray):
-        ypr, am, lg = self._handle.forward(u8, want_logits=True)
-        if self._out_of_range(ypr):
-            ypr, am, lg = self._handle.forward(u8, want_logits=True)
+        ypr, am, lg = self._guarded(lambda: self._handle.forward(u8, want_logits=True))
         self.last_logits, self.last_argmax = lg, am
         return ypr, am, lg
 
     def _forward_f32(self, x: np.ndarray):
-        ypr, am, lg = self._handle.forward_f32(x, want_logits=True)
-        if self._out_of_range(ypr):
-            ypr, am, lg = self._handle.forward_f32(x, want_logits=True)
+        ypr, am, lg = self._guarded(lambda: self._handle.forward_f32(x, want_logits=True), x)
         self.last_logits, self.last_argmax = lg, am
         return ypr, am, lg
 

@@ -232,7 +232,9 @@ WHENET_API int whenet_set_option(whenet_t* h, const char* key, long value);
  * normalise (23-26) -> Model.predict (27) -> softmax-expectation decode (28-33).
  *   crops   uint8 [n,224,224,3] RGB
  *   ypr     float [n,3]   yaw, pitch, roll in degrees           (required)
- *   argmax  int32 [n,3]   argmax bin of each head's logits      (may be NULL)
+ *   argmax  int32 [n,3]   argmax bin of each head's logits      (may be NULL): the first index of the maximum, as np.argmax --
+ *                         NaN counts as the maximum and the first NaN wins, so a crop with NaN logits gives 0, 0, 0; always
+ *                         inside the head's 120 / 66 / 66 bins
  *   logits  float [n,252] what Model.predict returns, concatenated (may be NULL)
  * Host-pointer form: copies in, runs, copies out, returns when the results are in place. */
 WHENET_API int whenet_forward_u8(whenet_t* h, const uint8_t* crops, int n,
@@ -243,7 +245,10 @@ WHENET_API int whenet_forward_u8(whenet_t* h, const uint8_t* crops, int n,
  * the caller as whenet.py:23-26 does (float64, then cast).  whenet.py:25 divides any numeric array
  * by 255, so crops that are not 8-bit integers (no byte LUT applies) take this entry point; the
  * drop-in get_angle routes them here.  Host pointers, blocking, eager launches.  An f16 handle computes in
- * binary16 activations: normalised inputs beyond +-65504 saturate there (an f32 handle takes any finite float32). */
+ * binary16 activations: finite normalised inputs beyond +-65504 saturate there (an f32 handle takes any finite float32).
+ * NON-FINITE INPUT: a crop that holds a NaN or an infinite element comes back with NaN angles and NaN logits (all 3 and all
+ * 252: the squeeze-excite gates spread it over the crop), and its argmax is np.argmax of those logits: 0, 0, 0.  Every other
+ * crop of the call is untouched: bitwise what the same call gives with a finite crop in that place. */
 WHENET_API int whenet_forward_f32(whenet_t* h, const float* image, int n,
                        float* ypr, int32_t* argmax, float* logits);
 

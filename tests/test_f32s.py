@@ -356,6 +356,92 @@ def test_f32s_is_the_class_default_and_leaves_binary16_range_loudly():
         assert all(np.array_equal(a, b) for a, b in zip(got2, want))
 
 
+def whenet_warnings(record):
+    return [str(w.message) for w in record if str(w.message).startswith("whenet:")]
+
+
+def real_valued_crops(n=5):
+    """[n,224,224,3] float64 that is not byte-valued (get_angle then normalises on the host and runs forward_f32), and the same
+    batch with crop 2 poisoned (tests/nonfinite_cases.py: nan_all)."""
+    from tests import nonfinite_cases as NF
+    a = C.crops64()[:n].astype(np.float64) + 0.25
+    bad = a.copy()
+    bad[2] = NF.poison(a[2].astype(np.float32), "nan_all")
+    return a, bad
+
+
+def test_f32s_class_returns_a_nan_crop_as_nan_and_stays_f32s():
+    """A real-valued batch with one crop NaN throughout: NaN angles for that crop are the caller's own NaN, not a binary16 range
+    overflow.  The other crops are bitwise those of the same call with a finite crop in its place; no warning; the model stays
+    f32s (on the parent commit it went over to the exact-float32 kernels for good: _dtype == F32, and every later call ran at
+    the exact-f32 rate with other bits)."""
+    import warnings
+    import whenet
+    a, bad = real_valued_crops()
+    u8 = C.crops64()[:9]
+    with whenet.WHENet() as m, whenet.WHENet(dtype="f32s") as fresh:
+        want = fresh.get_angle(a)
+        with warnings.catch_warnings(record=True) as record:
+            warnings.simplefilter("always")
+            got = m.get_angle(bad)
+        assert whenet_warnings(record) == [] and not any("binary16" in str(w.message) for w in record)
+        keep = np.arange(len(a)) != 2
+        for g, w in zip(got, want):
+            assert np.isnan(g[2]) and np.isfinite(w).all()
+            assert g[keep].tobytes() == w[keep].tobytes()
+        assert m.last_argmax[2].tolist() == [0, 0, 0]
+        assert m._dtype == _lib.F32S
+        assert all(g.tobytes() == w.tobytes() for g, w in zip(m.get_angle(u8), fresh.get_angle(u8)))
+
+
+def test_f32s_model_predict_returns_a_nan_crop_as_nan_and_stays_f32s():
+    """The same through Model.predict (the normalised image in, the three logit arrays out)."""
+    import warnings
+    import whenet
+    a, bad = real_valued_crops()
+    norm = lambda v: ((v / 255 - list(spec.MEAN)) / list(spec.STD)).astype(np.float32)
+    u8 = C.crops64()[:9]
+    with whenet.WHENet() as m, whenet.WHENet(dtype="f32s") as fresh:
+        want = fresh.model.predict(norm(a))
+        with warnings.catch_warnings(record=True) as record:
+            warnings.simplefilter("always")
+            got = m.model.predict(norm(bad))
+        assert whenet_warnings(record) == [] and not any("binary16" in str(w.message) for w in record)
+        keep = np.arange(len(a)) != 2
+        for g, w in zip(got, want):
+            assert np.isnan(g[2]).all() and np.isfinite(w).all()
+            assert g[keep].tobytes() == w[keep].tobytes()
+        assert m._dtype == _lib.F32S
+        assert all(g.tobytes() == w.tobytes() for g, w in zip(m.get_angle(u8), fresh.get_angle(u8)))
+
+
+def test_f32s_class_keeps_f32s_where_exact_f32_is_nan_too():
+    """A snapshot whose activations overflow float32 itself (the stem's and block 1's depthwise BatchNorm scales times 1e30 each:
+    the loader refuses a snapshot that HOLDS a non-finite value -- tests/test_capi_cpu.py::test_create_error_codes -- so the NaN is
+    made by finite weights): byte crops give NaN angles under dtype='f32' as well.  The exact-float32 kernels are no cure, so the
+    class tries them, goes back to f32s, returns the NaNs, and its warning does not blame binary16's range."""
+    import whenet
+    crops = C.crops64()[:4]
+    w = dict(W.synthetic(1234))
+    for key in ("stem/bn/gamma", "b1/dw_bn/gamma"):
+        w[key] = w[key] * np.float32(1e30)
+    big = W.pack(w)
+    with whenet.WHENet(big, dtype="f32") as m32:
+        assert all(np.isnan(a).all() for a in m32.get_angle(crops))            # (the premise)
+        k32 = m32._handle.info().n_kernels_per_forward
+    with whenet.WHENet(big, dtype="f32s") as ms:
+        ks = ms._handle.info().n_kernels_per_forward
+    assert ks != k32                      # (f32s folds block 1's project conv into block 2's expand conv; exact f32 never does)
+    with whenet.WHENet(big) as m:
+        for _ in range(2):                # (every call says so: nothing was switched)
+            with pytest.warns(RuntimeWarning) as record:
+                got = m.get_angle(crops)
+            said = whenet_warnings(record)
+            assert len(said) == 1 and "binary16" not in said[0] and "stays f32s" in said[0], said
+            assert all(np.isnan(a).all() for a in got)
+            assert m._dtype == _lib.F32S and m._handle.info().n_kernels_per_forward == ks
+
+
 @pytest.mark.parametrize("dtype", ["f16", "f32s"])
 def test_staged_splitk_option(blob, dtype):
     """Option pw_staged (round 5): the K >= 1152 / 14x14 K = 672 project GEMMs fetch their activation rows coalesced through per-wave
