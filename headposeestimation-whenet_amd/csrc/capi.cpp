@@ -996,6 +996,90 @@ int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_index, int dis
     });
 }
 
+// ---- JPEG decoder (jpeg_dec.hip, jpeg_dec_host.h, engine_post.cpp) ----
+namespace {
+// the header of a stream for the pure-host calls: WHENET_OK, or the code with the text in whenet_last_error(NULL)
+int parse_for_host(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info) {
+    if (data == nullptr || size < 1) {
+        g_create_error = std::string(what) + ": NULL argument or size < 1";
+        return WHENET_EINVAL;
+    }
+    if (const char* bad = whenet::jpeg_parse(data, size, info)) {
+        g_create_error = std::string(what) + ": " + bad;
+        return WHENET_EFORMAT;
+    }
+    return WHENET_OK;
+}
+}  // namespace
+
+int whenet_jpeg_parse(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info) {
+    if (info == nullptr) {
+        g_create_error = "jpeg_parse: NULL argument";
+        return WHENET_EINVAL;
+    }
+    return parse_for_host("jpeg_parse", data, size, *info);
+}
+
+int whenet_jpeg_decode_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int32_t status[2]) {
+    try {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_host: NULL argument");
+        whenet_jpeg_info_t info;
+        if (const int rc = parse_for_host("jpeg_decode_host", data, size, info)) return rc;
+        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_host: the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), planes, status);
+        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
+    }
+}
+
+int whenet_jpeg_decode_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int32_t status[2]) {
+    try {
+        WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_planes_host: NULL argument");
+        whenet_jpeg_info_t info;
+        if (const int rc = parse_for_host("jpeg_decode_planes_host", data, size, info)) return rc;
+        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
+        for (int c = 0; c < g.comps; ++c) {
+            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
+            WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
+                           "jpeg_decode_planes_host: plane " + std::to_string(c) + " is NULL or its pitch is below its " + std::to_string(cw) + " samples");
+        }
+        whenet::JpegDecPlanes pl;
+        whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), pl, status);
+        for (int c = 0; c < g.comps; ++c) {
+            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
+            for (int y = 0; y < ch; ++y)
+                std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
+        }
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_op_jpeg_decode(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int32_t status[2]) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
+        e.op_jpeg_decode(data, size, *dst, channel_order, status);
+    });
+}
+
+int whenet_jpeg_decode_device(whenet_t* h, const whenet_jpeg_info_t* info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t* dst,
+                              int channel_order, int32_t* d_status, void* stream) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(info != nullptr && dst != nullptr, WHENET_EINVAL, "jpeg_decode_device: NULL argument");
+        e.jpeg_decode_device(*info, d_entropy, nbytes, *dst, channel_order, d_status, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_frame_begin_jpeg(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int* ticket, int32_t* status) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status); });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

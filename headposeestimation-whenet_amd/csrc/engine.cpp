@@ -1210,6 +1210,7 @@ int Engine::finish_submission(Slot& s, int n) {
     s.clip_f = 0, s.clip_cap = -1, s.clip_mixed = false;
     s.ann_kind = Slot::ANN_NONE, s.ann_mask = 0;
     s.ann_host.clear(), s.jpg_host.clear();
+    s.jpg_dec_out = nullptr;
     s.ticket = next_ticket_++;
     return s.ticket;
 }
@@ -1248,7 +1249,7 @@ void Engine::abandon_submissions() {
     DeviceGuard guard(device_);
     (void)hipStreamSynchronize(stream_);
     if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
-    for (Slot& s : slots_) s.busy = false, s.ann_host.clear(), s.jpg_host.clear();
+    for (Slot& s : slots_) s.busy = false, s.ann_host.clear(), s.jpg_host.clear(), s.jpg_dec_out = nullptr;
 }
 
 void Engine::collect(int ticket, float* ypr, int32_t* argmax, float* logits) {

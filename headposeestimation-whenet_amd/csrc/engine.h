@@ -347,6 +347,17 @@ class Engine {
     // memory -- the total is data-dependent and the call must not wait, so no copy of a size known to the host can stand there.
     // ENQUEUE-ONLY; the collect call hands the bytes, the length and the status to the caller.  It counts as the frame's one annotate.
     void frame_annotate_jpeg(int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size, int32_t* status);
+    // JPEG DECODER (jpeg_dec.hip; the contract is in include/whenet_hip.h).  Every entry point parses (or checks the info) on the host
+    // first: a refused stream is WHENET_EFORMAT before a slot is taken or anything is enqueued.
+    // op_jpeg_decode: the kernels alone, host to host; the destination lands at the caller's pitches between two guard zones.
+    // jpeg_decode_device: ENQUEUE-ONLY on stream_ between the two event hand-overs of the device ingest; the work buffers are the
+    // engine's (grown on the first call for a size).
+    // frame_begin_jpeg: frame_begin whose H2D carries the compressed bytes (and the decode tables, one copy) and whose kernels run
+    // on the copy stream before slot.copied; the two status words come back through pinned memory with the ticket's collect call.
+    void op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status);
+    void jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
+                            int channel_order, int32_t* d_status, hipStream_t stream);
+    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status);
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -409,6 +420,11 @@ class Engine {
             int frame_index;
         };
         std::vector<JpegHost> jpg_host;
+        // frame_begin_jpeg: the decoder's work buffers (tables | compressed bytes | starts | coefficients | planes | status), the
+        // pinned landing of the two status words, and the caller's destination that the collect call fills (nullptr: none pending)
+        DeviceBuffer jpg_dec;
+        PinnedBuffer jpg_dec_status;
+        int32_t* jpg_dec_out = nullptr;
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -560,6 +576,9 @@ class Engine {
     DeviceBuffer jpeg_scratch_;
     Event jpeg_source_, jpeg_done_;
     const JpegTables* jpeg_device_tables(int h, int w, int quality);
+    DeviceBuffer jpeg_dec_scratch_;      // jpeg_decode_device's work buffers, and the decode tables of its last stream (kept while
+    DeviceBuffer jpeg_dec_tables_d_;     // the next stream's are the same: an MJPG stream repeats its tables)
+    std::vector<JpegDecTables> jpeg_dec_tables_h_;
 
     void open_device(int device_id);
     void require_model() const;

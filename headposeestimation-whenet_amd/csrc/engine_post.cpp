@@ -1277,6 +1277,11 @@ void Engine::finish_annotations(Slot& slot) {
         *j.status = total <= j.cap ? WHENET_OK : WHENET_EOVERFLOW;
     }
     slot.jpg_host.clear();
+    if (slot.jpg_dec_out != nullptr) {      // frame_begin_jpeg: the status words, written to pinned memory by the decode on the copy stream
+        WHENET_HIP_CHECK(hipEventSynchronize(slot.copied));      // (a ticket collected without heads has waited for nothing yet)
+        std::memcpy(slot.jpg_dec_out, slot.jpg_dec_status.as<void>(), 2 * sizeof(int32_t));
+        slot.jpg_dec_out = nullptr;
+    }
 }
 
 // ---- JPEG encoder (jpeg.hip; the contract is in engine.h and include/whenet_hip.h) ----
@@ -1406,6 +1411,146 @@ void Engine::frame_annotate_jpeg(int ticket, int frame_index, int display, int q
     launch_jpeg_flush(d_stream, h_dev, d_size, staged_cap, reinterpret_cast<long long*>(static_cast<uint8_t*>(h_dev) + cap16), stream_);
     WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));      // the collect call waits for the stream's bytes as well
     slot.jpg_host.push_back({out, cap, staged_cap, size, status, frame_index});
+}
+
+// ---- JPEG decoder (jpeg_dec.hip; the contract is in engine.h and include/whenet_hip.h) ----
+namespace {
+// the header of a stream, or WHENET_EFORMAT with the parser's reason
+whenet_jpeg_info_t parse_or_refuse(const char* what, const uint8_t* data, int64_t size) {
+    WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
+    whenet_jpeg_info_t info;
+    const char* bad = jpeg_parse(data, size, info);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
+    return info;
+}
+}  // namespace
+
+void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
+    const whenet_jpeg_info_t info = parse_or_refuse("op_jpeg_decode", data, size);
+    const char* bad = jpeg_dec_check_dst(info, &dst, channel_order);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_decode: ") + (bad ? bad : ""));
+    WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_jpeg_decode: the surface must be host memory (on_device = 0)");
+    check_surface("op_jpeg_decode", dst, info.h, info.w);
+    const JpegDecGeom g = jpeg_dec_geom(info);
+    const size_t nbytes = size_t(size - info.data_offset);
+    const JpegDecScratch lay(g, nbytes);
+    std::vector<JpegDecTables> tables(1);
+    jpeg_dec_build_tables(info, tables[0]);
+    // the destination on the device: every plane at the caller's pitch and at the caller's address modulo 16, between two guard
+    // zones and over a sentinel, so that a store outside the rows' bytes is seen
+    int rows[3], row_bytes[3];
+    const int planes = overlay_surface_planes(dst.format, info.h, info.w, rows, row_bytes);
+    size_t off[4] = {0, 0, 0, 0}, total = 0;
+    for (int p = 0; p < planes; ++p) {
+        off[p] = ((total + 15) & ~size_t(15)) + (reinterpret_cast<uintptr_t>(dst.plane[p]) & 15);
+        total = off[p] + size_t(rows[p] - 1) * size_t(dst.pitch[p]) + size_t(row_bytes[p]);
+    }
+    TempBufs tmp;
+    char* const d_scratch = static_cast<char*>(tmp.get(lay.bytes));
+    int32_t* const d_status = static_cast<int32_t*>(tmp.get(2 * sizeof(int32_t)));
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.tables, tables.data(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream_));
+    if (nbytes > 0) WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.data, data + info.data_offset, nbytes, hipMemcpyHostToDevice, stream_));
+    const GuardedOutput d_out(total, stream_);
+    whenet_surface_t d_dst = dst;
+    for (int p = 0; p < planes; ++p) d_dst.plane[p] = d_out.frames() + off[p];
+    launch_jpeg_decode(jpeg_dec_args(g, d_scratch, lay, reinterpret_cast<const uint8_t*>(d_scratch + lay.data), (long long)(nbytes), d_dst,
+                                     channel_order, d_status),
+                       lay, stream_);
+    d_out.to_host(stream_, off, 0, nullptr, "op_jpeg_decode");      // waits, checks the guard zones
+    std::vector<uint8_t> back(total);
+    WHENET_HIP_CHECK(hipMemcpy(back.data(), d_out.frames(), total, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> is_row(total, 0);
+    for (int p = 0; p < planes; ++p)
+        for (int r = 0; r < rows[p]; ++r) {
+            const size_t at = off[p] + size_t(r) * size_t(dst.pitch[p]);
+            std::memset(is_row.data() + at, 1, size_t(row_bytes[p]));
+            std::memcpy(static_cast<uint8_t*>(dst.plane[p]) + size_t(r) * size_t(dst.pitch[p]), back.data() + at, size_t(row_bytes[p]));
+        }
+    for (size_t i = 0; i < total; ++i)
+        WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
+                       "op_jpeg_decode: the kernel wrote outside the rows of the surface (byte " + std::to_string(i) + ")");
+    WHENET_HIP_CHECK(hipMemcpy(status, d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+}
+
+void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
+                                int channel_order, int32_t* d_status, hipStream_t stream) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(d_entropy != nullptr && d_status != nullptr, WHENET_EINVAL, "jpeg_decode_device: NULL argument");
+    WHENET_REQUIRE(nbytes >= 1 && nbytes <= JPEG_DEC_MAX_BYTES, WHENET_EINVAL, "jpeg_decode_device: nbytes must be 1..2^31 - 1");
+    const char* bad = jpeg_dec_check_info(info);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_device: info: ") + (bad ? bad : ""));
+    bad = jpeg_dec_check_dst(info, &dst, channel_order);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_device: ") + (bad ? bad : ""));
+    WHENET_REQUIRE(dst.on_device == 1, WHENET_EINVAL, "jpeg_decode_device: the surface must be device memory (on_device = 1)");
+    check_surface("jpeg_decode_device", dst, info.h, info.w);
+    check_device_plane("jpeg_decode_device: d_entropy", d_entropy, 1, int(nbytes), int(nbytes));
+    check_device_plane("jpeg_decode_device: d_status", reinterpret_cast<const uint8_t*>(d_status), 1, 8, 8);
+    WHENET_REQUIRE(reinterpret_cast<uintptr_t>(d_status) % 4 == 0, WHENET_EINVAL, "jpeg_decode_device: d_status is not aligned to 4 bytes");
+    // allocations, the tables and the events first: nothing is enqueued yet if one of them fails
+    const JpegDecGeom g = jpeg_dec_geom(info);
+    const JpegDecScratch lay(g, 0);
+    if (lay.bytes > jpeg_dec_scratch_.bytes()) {      // (the buffer in hand may still be read by an earlier call's kernels)
+        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+        jpeg_dec_scratch_.reset(lay.bytes);
+    }
+    std::vector<JpegDecTables> tables(1);
+    jpeg_dec_build_tables(info, tables[0]);
+    if (jpeg_dec_tables_d_.bytes() == 0 || std::memcmp(&jpeg_dec_tables_h_[0], tables.data(), sizeof(JpegDecTables)) != 0) {
+        // other tables than the last call's (an MJPG stream repeats its own): the set in hand may still be read
+        WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
+        jpeg_dec_tables_d_.grow(sizeof(JpegDecTables));
+        WHENET_HIP_CHECK(hipMemcpy(jpeg_dec_tables_d_.as<void>(), tables.data(), sizeof(JpegDecTables), hipMemcpyHostToDevice));
+        jpeg_dec_tables_h_ = tables;
+    }
+    if (!jpeg_source_) jpeg_source_.create();
+    if (!jpeg_done_) jpeg_done_.create();
+    JpegDecArgs a = jpeg_dec_args(g, jpeg_dec_scratch_.as<void>(), lay, d_entropy, nbytes, dst, channel_order, d_status);
+    a.tables = jpeg_dec_tables_d_.as<JpegDecTables>();
+    WHENET_HIP_CHECK(hipEventRecord(jpeg_source_, stream));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, jpeg_source_, 0));
+    launch_jpeg_decode(a, lay, stream_);
+    WHENET_HIP_CHECK(hipEventRecord(jpeg_done_, stream_));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream, jpeg_done_, 0));
+}
+
+// frame_begin from a JPEG stream: the slot ends up exactly as frame_begin(decoded frame, channel_order) leaves it
+int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "frame_begin_jpeg: NULL argument");
+    WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "frame_begin_jpeg: unknown channel order");
+    const whenet_jpeg_info_t info = parse_or_refuse("frame_begin_jpeg", data, size);      // (before a slot is taken)
+    const JpegDecGeom g = jpeg_dec_geom(info);
+    const size_t nbytes = size_t(size - info.data_offset);
+    const JpegDecScratch lay(g, nbytes);
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const size_t fbytes = size_t(info.h) * info.w * 3;
+    slot.frame.h.grow(std::max(fbytes, lay.upload_bytes));      // (>= the frame's bytes: the size every other user of the staging grows it to)
+    slot.frame.d.grow(fbytes);
+    slot.jpg_dec.grow(lay.bytes);
+    slot.jpg_dec_status.grow(16);
+    void* d_status = nullptr;                      // the pinned status words as the device addresses them
+    WHENET_HIP_CHECK(hipHostGetDevicePointer(&d_status, slot.jpg_dec_status.as<void>(), 0));
+    // tables | compressed bytes: the staging's front, one H2D
+    uint8_t* const stage = slot.frame.h.as<uint8_t>();
+    std::vector<JpegDecTables> tables(1);
+    jpeg_dec_build_tables(info, tables[0]);
+    std::memset(stage, 0, lay.data);
+    std::memcpy(stage + lay.tables, tables.data(), sizeof(JpegDecTables));
+    if (nbytes > 0) std::memcpy(stage + lay.data, data + info.data_offset, nbytes);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, lay.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
+    whenet_surface_t dst{};
+    dst.plane[0] = slot.frame.d.as<void>(), dst.pitch[0] = 3 * info.w, dst.format = WHENET_SURF_PACKED, dst.on_device = 1;
+    launch_jpeg_decode(jpeg_dec_args(g, slot.jpg_dec.as<void>(), lay, slot.jpg_dec.as<uint8_t>() + lay.data, (long long)(nbytes), dst,
+                                     channel_order, static_cast<int32_t*>(d_status)),
+                       lay, copy_stream());
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = info.h, slot.fw = info.w, slot.swap_rb = channel_order == WHENET_BGR;
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.jpg_dec_out = status;
+    return slot.frame_ticket;
 }
 
 }  // namespace whenet

@@ -1,0 +1,356 @@
+// The baseline JPEG decoder on the device: the entropy data of one stream in, the frame out.  The format and every formula are in
+// include/whenet_hip.h (JPEG DECODER); the arithmetic -- bit reader, Huffman decode of a block, inverse DCT pass, the pixel rule --
+// is jpeg_dec_host.h's, the same functions the host statement runs.  Integers only.
+//
+// Reference: demo.py (`cv2.imread`) and demo_video.py:49-53 (`cap.read()` of a camera or an MJPG file).
+//
+// Restart intervals are what makes a baseline stream parallel: the DC predictors start at 0 in each and its bits start at a byte of
+// their own.  The interval count comes from the header, so every launch size is known on the host and nothing waits.
+//   whenet_jpeg_dec_scan_kernel     one workgroup.  A lane owns 16 bytes of the entropy data per step and finds its 0xFF 0xD0..0xD7
+//                                   pairs (the byte behind its run included: a pair may straddle two runs); the counts are scanned in
+//                                   order (wave shuffles + LDS totals, a carry from step to step) and marker k writes the start of
+//                                   interval k + 1.  The numbers (k mod 8) and the count are checked: meta = the first bad interval.
+//   whenet_jpeg_dec_entropy_kernel  one restart interval per lane, 16 intervals per workgroup (a wave's lanes diverge in the Huffman
+//                                   walk: few lanes per wave, many waves).  The decode tables lie in LDS.  Dequantised, clamped int16
+//                                   coefficients go into records [block][64] that a memset zeroed.  A stream without DRI is ONE lane.
+//   whenet_jpeg_dec_idct_kernel     8 lanes per block: lane u runs the column pass of column u, the rounded values go through LDS,
+//                                   lane y runs the row pass of row y and stores its 8 samples as one 8-byte store.  The component
+//                                   planes are padded to whole MCUs, so every block lies inside its plane.  Writes the status words.
+//   whenet_jpeg_dec_frame_kernel    planes -> packed pixels, 4 pixels of a row per lane: one luma dword, the chroma samples of
+//                                   (x >> (hs - 1), y >> (vs - 1)), 12 bytes out with the head / funnel-shift / tail stores of yuv.hip.
+//                                   A tight BGR destination of a 4:2:0 stream goes through yuv.hip's own plane kernel instead.
+//   whenet_jpeg_dec_yuv_kernel      4:2:0 planes -> an I420 or NV12 surface (a copy).
+#include <algorithm>
+#include <string>
+
+#include "kernels.h"
+#include "jpeg_dec_host.h"
+
+namespace whenet {
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int WAVES = THREADS / 64;
+constexpr int SCAN_BYTES = 16;                  // bytes per lane and step of the scan kernel
+constexpr int ENT_THREADS = 64;                 // the entropy kernel's workgroup: all lanes load the tables,
+constexpr int ENT_LANES = 16;                   // ... the first 16 decode an interval each
+constexpr int IDCT_BLOCKS = THREADS / 8;        // blocks per workgroup of the idct kernel
+
+static_assert(sizeof(JpegDecTables) % 4 == 0, "the tables are copied to LDS by dwords");
+
+// exclusive scan of one int per lane over the workgroup (every lane calls it); total = the sum
+__device__ inline int block_exclusive_scan(int v, int* s_wave, int& total) {
+    const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const int t = s_wave[w];
+        base += w < wave ? t : 0;
+        total += t;
+    }
+    __syncthreads();
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_scan_kernel(JpegDecArgs a) {
+    __shared__ int s_wave[WAVES];
+    __shared__ int s_bad;
+    const int tid = int(threadIdx.x), N = a.g.intervals;
+    if (tid == 0) s_bad = JPEG_DEC_NO_BAD;
+    __syncthreads();
+    const long long nbytes = a.nbytes;
+    int carry = 0;
+    for (long long base = 0; base < nbytes; base += THREADS * SCAN_BYTES) {
+        const long long first = base + tid * SCAN_BYTES;
+        const uint8_t* p = a.data + first;
+        uint32_t w[SCAN_BYTES / 4 + 1] = {0u, 0u, 0u, 0u, 0u};      // the run's 16 bytes and the byte behind it; 0 beyond the data
+        if (first + SCAN_BYTES <= nbytes && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+            const uint4 q = *reinterpret_cast<const uint4*>(p);
+            w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < SCAN_BYTES; ++j)
+                if (first + j < nbytes) w[j >> 2] |= uint32_t(p[j]) << (8 * (j & 3));
+        }
+        if (first + SCAN_BYTES < nbytes) w[4] = p[SCAN_BYTES];
+        unsigned marks = 0;
+#pragma unroll
+        for (int j = 0; j < SCAN_BYTES; ++j) {
+            const uint32_t cur = (w[j >> 2] >> (8 * (j & 3))) & 255u, nx = (w[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 255u;
+            if (cur == 0xFFu && (nx & 0xF8u) == 0xD0u) marks |= 1u << j;
+        }
+        int total;
+        int k = carry + block_exclusive_scan(__popc(marks), s_wave, total);
+#pragma unroll
+        for (int j = 0; j < SCAN_BYTES; ++j) {
+            if (marks & (1u << j)) {
+                const int m = int((w[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 7u);
+                if (k >= N - 1) atomicMin(&s_bad, N - 1);
+                else if (m != (k & 7)) atomicMin(&s_bad, k);
+                if (k + 1 < N) a.start[k + 1] = int(first + j + 2);
+                ++k;
+            }
+        }
+        carry += total;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int bad = s_bad;
+        if (carry < N - 1 && carry < bad) bad = carry;
+        a.start[0] = 0;
+        a.meta[0] = bad, a.meta[1] = bad;      // what the markers say; lowered by the entropy decode
+    }
+}
+
+__global__ __launch_bounds__(ENT_THREADS) void whenet_jpeg_dec_entropy_kernel(JpegDecArgs a) {
+    __shared__ JpegDecTables s_t;
+    __shared__ __attribute__((aligned(16))) int16_t s_block[ENT_LANES][64 + 8];      // a lane's block in hand (144-byte rows)
+    const int tid = int(threadIdx.x);
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.tables);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&s_t);
+        for (int i = tid; i < int(sizeof(JpegDecTables) / 4); i += ENT_THREADS) dst[i] = src[i];
+    }
+    __syncthreads();
+    const long long i = (long long)(blockIdx.x) * ENT_LANES + tid;
+    if (tid >= ENT_LANES || i >= a.g.intervals || i > a.meta[0]) return;
+    if (!jpeg_dec_interval(a.data, a.nbytes, a.start[i], s_t, a.g, int(i), a.coef, 0, s_block[tid])) atomicMin(&a.meta[1], int(i));
+}
+
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecArgs a) {
+    __shared__ int s_r[IDCT_BLOCKS][8][9];
+    const int tid = int(threadIdx.x), lb = tid >> 3, l = tid & 7;
+    const long long g = (long long)(blockIdx.x) * IDCT_BLOCKS + lb;
+    const long long total = (long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm;
+    const bool live = g < total;
+    if (live) {
+        const int16_t* c = a.coef + size_t(g) * 64;
+        int col[8], o[8];
+#pragma unroll
+        for (int v = 0; v < 8; ++v) col[v] = c[v * 8 + l];
+        jpeg_idct8(col, o);
+#pragma unroll
+        for (int y = 0; y < 8; ++y) s_r[lb][y][l] = jpeg_idct_round(o[y]);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {      // (the entropy kernel has ended: a kernel boundary lies between)
+        const int bad = a.meta[1];
+        a.status[0] = bad == JPEG_DEC_NO_BAD ? WHENET_OK : WHENET_EFORMAT;
+        a.status[1] = bad == JPEG_DEC_NO_BAD ? -1 : bad;
+    }
+    if (!live) return;
+    int row[8], b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) row[u] = s_r[lb][l][u];
+    jpeg_idct8(row, b);
+    const long long m = g / a.g.bpm;
+    int comp, y0, x0;
+    jpeg_dec_block_origin(a.g, m, int(g - m * a.g.bpm), comp, y0, x0);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) lo |= uint32_t(jpeg_idct_sample(b[x])) << (8 * x), hi |= uint32_t(jpeg_idct_sample(b[x + 4])) << (8 * x);
+    // the planes are padded to whole MCUs and 8-byte aligned: the block's row lies inside its plane
+    *reinterpret_cast<uint2*>(a.plane[comp] + size_t(y0 + l) * size_t(a.g.plane_pitch[comp]) + size_t(x0)) = make_uint2(lo, hi);
+}
+
+__device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int shift_bits) {      // bits [shift, shift + 32) of hi:lo
+    return uint32_t(((uint64_t(hi) << 32) | lo) >> shift_bits);
+}
+
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_kernel(JpegDecArgs a) {
+    const int h = a.g.h, w = a.g.w, gw = (w + 3) >> 2;
+    const long long item = (long long)(blockIdx.x) * THREADS + threadIdx.x;
+    const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
+    if (y >= h) return;
+    const int x = gx << 2;
+    const int n = min(4, w - x);                    // pixels of the group, 1..4
+    // (x is a multiple of 4 and the planes' pitches are multiples of 8: the loads are aligned and inside the padded planes)
+    const uint32_t y4 = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
+    const int hsh = a.g.hs - 1, vsh = a.g.vs - 1;
+    uint32_t u4 = 0, v4 = 0;
+    if (a.g.comps == 3) {
+        const size_t ci = size_t(y >> vsh) * size_t(a.g.plane_pitch[1]) + size_t(x >> hsh);
+        if (hsh) {
+            u4 = *reinterpret_cast<const uint16_t*>(a.plane[1] + ci), v4 = *reinterpret_cast<const uint16_t*>(a.plane[2] + ci);
+        } else {
+            u4 = *reinterpret_cast<const uint32_t*>(a.plane[1] + ci), v4 = *reinterpret_cast<const uint32_t*>(a.plane[2] + ci);
+        }
+    }
+    const int rsh = a.channel_order == WHENET_BGR ? 16 : 0;
+    uint32_t px[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int yy = int((y4 >> (8 * j)) & 255u);
+        int b = yy, g = yy, r = yy;
+        if (a.g.comps == 3) jpeg_dec_pixel(yy, int((u4 >> (8 * (j >> hsh))) & 255u), int((v4 >> (8 * (j >> hsh))) & 255u), b, g, r);
+        px[j] = (uint32_t(r) << rsh) | (uint32_t(g) << 8) | (uint32_t(b) << (16 - rsh));
+    }
+    const uint32_t w0 = px[0] | (px[1] << 24), w1 = (px[1] >> 8) | (px[2] << 16), w2 = (px[2] >> 16) | (px[3] << 8);
+    uint8_t* dp = a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x) * 3;
+    if (n == 4) {
+        const int al = int(reinterpret_cast<uintptr_t>(dp) & 3);
+        if (al == 0) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(dp);
+            d[0] = w0, d[1] = w1, d[2] = w2;
+        } else {
+            const int head = 4 - al;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < head) dp[j] = uint8_t(w0 >> (8 * j));
+            uint32_t* d = reinterpret_cast<uint32_t*>(dp + head);
+            d[0] = funnel(w0, w1, 8 * head), d[1] = funnel(w1, w2, 8 * head);
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < al) dp[12 - al + j] = uint8_t(w2 >> (8 * (head + j)));
+        }
+    } else {
+        const int nb = 3 * n;                       // 3, 6 or 9 bytes: the row ends here, the bytes behind it are not the frame's
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const uint32_t word = j < 4 ? w0 : (j < 8 ? w1 : w2);
+            if (j < nb) dp[j] = uint8_t(word >> (8 * (j & 3)));
+        }
+    }
+}
+
+// up to 4 bytes of `word` to dp: one dword where all four are the row's and dp is aligned
+__device__ __forceinline__ void store_bytes(uint8_t* dp, uint32_t word, int n) {
+    if (n == 4 && (reinterpret_cast<uintptr_t>(dp) & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(dp) = word;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < n) dp[j] = uint8_t(word >> (8 * j));
+    }
+}
+
+// items: the luma plane's 4-byte groups row by row, then the chroma rows' groups of 4 samples (U and V of a group by one lane)
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArgs a) {
+    const int h = a.g.h, w = a.g.w, ch = (h + 1) >> 1, cw = (w + 1) >> 1, gw = (w + 3) >> 2, cgw = (cw + 3) >> 2;
+    long long item = (long long)(blockIdx.x) * THREADS + threadIdx.x;
+    const long long luma_items = (long long)(h) * gw;
+    if (item < luma_items) {
+        const int y = int(item / gw), x = int(item - (long long)(y) * gw) << 2;
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
+        store_bytes(a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x), v, min(4, w - x));
+        return;
+    }
+    item -= luma_items;
+    const int y = int(item / cgw), x = int(item - (long long)(y) * cgw) << 2;
+    if (y >= ch) return;
+    const int n = min(4, cw - x);
+    const size_t ci = size_t(y) * size_t(a.g.plane_pitch[1]) + size_t(x);
+    const uint32_t u = *reinterpret_cast<const uint32_t*>(a.plane[1] + ci), v = *reinterpret_cast<const uint32_t*>(a.plane[2] + ci);
+    if (a.format == WHENET_YUV_I420) {
+        store_bytes(a.dst[1] + size_t(y) * size_t(a.dst_pitch[1]) + size_t(x), u, n);
+        store_bytes(a.dst[2] + size_t(y) * size_t(a.dst_pitch[2]) + size_t(x), v, n);
+    } else {
+        uint8_t* dp = a.dst[1] + size_t(y) * size_t(a.dst_pitch[1]) + 2 * size_t(x);
+        const uint32_t lo = (u & 255u) | ((v & 255u) << 8) | ((u & 0xFF00u) << 8) | ((v & 0xFF00u) << 16);
+        const uint32_t hi = ((u >> 16) & 255u) | (((v >> 16) & 255u) << 8) | ((u >> 24) << 16) | ((v >> 24) << 24);
+        store_bytes(dp, lo, min(4, 2 * n));
+        if (n > 2) store_bytes(dp + 4, hi, 2 * n - 4);
+    }
+}
+
+}  // namespace
+
+JpegDecScratch::JpegDecScratch(const JpegDecGeom& g, size_t data_bytes) {
+    const auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    tables = 0;
+    data = up(sizeof(JpegDecTables));
+    upload_bytes = data + data_bytes;
+    start = up(upload_bytes);
+    meta = up(start + size_t(g.intervals) * sizeof(int32_t));
+    coef = up(meta + 4 * sizeof(int32_t));
+    zero_bytes = coef - start;
+    coef_bytes = size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm) * 64 * sizeof(int16_t);
+    size_t at = up(coef + coef_bytes);
+    for (int c = 0; c < 3; ++c) {
+        plane[c] = at;
+        if (c < g.comps) at = up(at + size_t(g.plane_pitch[c]) * size_t(g.plane_rows[c]));
+    }
+    bytes = at;
+}
+
+JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
+                          const whenet_surface_t& dst, int channel_order, int32_t* d_status) {
+    JpegDecArgs a{};
+    char* const s = static_cast<char*>(d_scratch);
+    a.g = g;
+    a.tables = reinterpret_cast<const JpegDecTables*>(s + lay.tables);
+    a.data = d_data, a.nbytes = int(nbytes);
+    a.start = reinterpret_cast<int32_t*>(s + lay.start), a.meta = reinterpret_cast<int32_t*>(s + lay.meta);
+    a.coef = reinterpret_cast<int16_t*>(s + lay.coef);
+    for (int c = 0; c < 3; ++c) {
+        a.plane[c] = reinterpret_cast<uint8_t*>(s + lay.plane[c]);
+        a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
+    }
+    a.format = dst.format, a.channel_order = channel_order;
+    a.status = d_status;
+    return a;
+}
+
+void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream) {
+    const JpegDecGeom& g = a.g;
+    int rows[3], row_bytes[3];
+    const int planes = overlay_surface_planes(a.format, g.h, g.w, rows, row_bytes);
+    WHENET_REQUIRE(planes > 0 && g.h >= 1 && g.w >= 1 && g.h <= JPEG_MAX_SIDE && g.w <= JPEG_MAX_SIDE && (g.comps == 1 || g.comps == 3) &&
+                       (g.hs == 1 || g.hs == 2) && (g.vs == 1 || g.vs == 2) && g.bpm == (g.comps == 3 ? g.hs * g.vs + 2 : 1) &&
+                       g.mcu_cols == (g.w + 8 * g.hs - 1) / (8 * g.hs) && g.mcu_rows == (g.h + 8 * g.vs - 1) / (8 * g.vs) && g.ri >= 1 &&
+                       (long long)(g.intervals) == ((long long)(g.mcu_cols) * g.mcu_rows + g.ri - 1) / g.ri,
+                   WHENET_EINVAL, "jpeg_decode: bad geometry");
+    WHENET_REQUIRE(a.tables != nullptr && a.data != nullptr && a.nbytes >= 0 && a.start != nullptr && a.meta != nullptr && a.coef != nullptr &&
+                       a.status != nullptr && (a.format == WHENET_SURF_PACKED || (g.comps == 3 && g.hs == 2 && g.vs == 2)),
+                   WHENET_EINVAL, "jpeg_decode: bad arguments");
+    for (int c = 0; c < g.comps; ++c)
+        WHENET_REQUIRE(a.plane[c] != nullptr && reinterpret_cast<uintptr_t>(a.plane[c]) % 8 == 0 && g.plane_pitch[c] % 8 == 0 &&
+                           g.plane_pitch[c] >= (c == 0 ? g.w : (g.w + g.hs - 1) / g.hs) && g.plane_rows[c] >= (c == 0 ? g.h : (g.h + g.vs - 1) / g.vs),
+                       WHENET_EINVAL, "jpeg_decode: bad component plane " + std::to_string(c));
+    for (int p = 0; p < planes; ++p)
+        WHENET_REQUIRE(a.dst[p] != nullptr && a.dst_pitch[p] >= row_bytes[p], WHENET_EINVAL, "jpeg_decode: bad destination plane " + std::to_string(p));
+    WHENET_REQUIRE(a.format != WHENET_SURF_PACKED || a.channel_order == WHENET_RGB || a.channel_order == WHENET_BGR, WHENET_EINVAL,
+                   "jpeg_decode: unknown channel order");
+    WHENET_REQUIRE(lay.coef_bytes == size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm) * 128, WHENET_EINVAL,
+                   "jpeg_decode: the work buffers are not those of the stream's geometry");
+    // start | meta (contiguous) and the coefficient records start from zero
+    WHENET_HIP_CHECK(hipMemsetAsync(a.start, 0, lay.zero_bytes, stream));
+    WHENET_HIP_CHECK(hipMemsetAsync(a.coef, 0, lay.coef_bytes, stream));
+    hipLaunchKernelGGL(whenet_jpeg_dec_scan_kernel, dim3(1), dim3(THREADS), 0, stream, a);
+    WHENET_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(whenet_jpeg_dec_entropy_kernel, dim3((g.intervals + ENT_LANES - 1) / ENT_LANES), dim3(ENT_THREADS), 0, stream, a);
+    WHENET_HIP_CHECK(hipGetLastError());
+    const long long nblocks = (long long)(g.mcu_cols) * g.mcu_rows * g.bpm;
+    hipLaunchKernelGGL(whenet_jpeg_dec_idct_kernel, dim3(unsigned((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(THREADS), 0, stream, a);
+    WHENET_HIP_CHECK(hipGetLastError());
+    if (a.format == WHENET_SURF_PACKED) {
+        if (g.comps == 3 && g.hs == 2 && g.vs == 2 && a.channel_order == WHENET_BGR && a.dst_pitch[0] == 3 * g.w) {
+            // a tight BGR frame of a 4:2:0 stream: the plane kernel of the YUV ingest, JFIF row
+            YuvPlanes clip{};
+            clip.frames = 1;
+            YuvPlanesFrame& f = clip.f[0];
+            for (int c = 0; c < 3; ++c) f.plane[c] = a.plane[c], f.pitch[c] = g.plane_pitch[c];
+            f.h = g.h, f.w = g.w, f.format = WHENET_YUV_I420, f.k = yuv_coeffs(WHENET_YUV_JFIF), f.dst_off = 0;
+            launch_yuv_planes_to_bgr(a.dst[0], clip, stream);
+            return;
+        }
+        const long long items = (long long)(g.h) * ((g.w + 3) >> 2);
+        hipLaunchKernelGGL(whenet_jpeg_dec_frame_kernel, dim3(unsigned((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a);
+    } else {
+        const long long items = (long long)(g.h) * ((g.w + 3) >> 2) + (long long)((g.h + 1) >> 1) * ((((g.w + 1) >> 1) + 3) >> 2);
+        hipLaunchKernelGGL(whenet_jpeg_dec_yuv_kernel, dim3(unsigned((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a);
+    }
+    WHENET_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace whenet

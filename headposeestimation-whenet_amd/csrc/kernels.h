@@ -8,6 +8,7 @@
 #include "common.h"
 #include "overlay_host.h"
 #include "jpeg_host.h"
+#include "jpeg_dec_host.h"
 
 namespace whenet {
 
@@ -660,6 +661,40 @@ void launch_jpeg_encode(const JpegArgs& a, const JpegScratch& lay, hipStream_t s
 // min(*d_size, cap) bytes of a stream, rounded up to whole 16-byte vectors, from d_stream to `to` (both 16-byte aligned and
 // ceil(cap / 16) vectors long), and *d_size to *to_size: `to` may be pinned host memory as the device addresses it
 void launch_jpeg_flush(const void* d_stream, void* to, const long long* d_size, long long cap, long long* to_size, hipStream_t stream);
+
+// ---- jpeg_dec.hip -----------------------------------------------------------------------
+// The baseline JPEG decoder (include/whenet_hip.h, JPEG DECODER; the arithmetic is jpeg_dec_host.h's) of ONE stream whose entropy
+// data is in device memory (any alignment).  Four launches behind two memsets (interval starts + meta, coefficient records):
+//   scan     one workgroup: the RSTm pairs of the data -> start [intervals], meta[0] = meta[1] = the first interval the markers make
+//            bad (JPEG_DEC_NO_BAD: none)
+//   entropy  one interval per lane, 16 per workgroup, tables in LDS: Huffman decode, dequantise, clamp -> coef [blocks][64] (natural
+//            order, block = MCU * bpm + its index in the MCU); a damaged interval lowers meta[1]
+//   idct     8 lanes per block: both passes -> the component planes (padded to whole MCUs, pitches multiples of 8); status[0..1]
+//   frame    planes -> the destination: packed pixels in either channel order at any pitch (a tight BGR frame of a 4:2:0 stream:
+//            launch_yuv_planes_to_bgr), or an I420 / NV12 surface for a 4:2:0 stream.  No thread stores outside the rows' bytes.
+// JpegDecScratch lays the work buffers out in one allocation; tables | data at its front are what a caller uploads in one copy
+// (data_bytes = 0: the data lies elsewhere).
+struct JpegDecScratch {
+    size_t tables, data, upload_bytes, start, meta, zero_bytes, coef, coef_bytes, plane[3], bytes;      // byte offsets and extents
+    JpegDecScratch(const JpegDecGeom& g, size_t data_bytes);
+};
+struct JpegDecArgs {
+    JpegDecGeom g;
+    const JpegDecTables* tables;   // device memory
+    const uint8_t* data;           // the entropy data: nbytes bytes from the stream's data_offset on
+    int nbytes;
+    int32_t* start;
+    int32_t* meta;
+    int16_t* coef;
+    uint8_t* plane[3];
+    uint8_t* dst[3];
+    int dst_pitch[3];
+    int format, channel_order;
+    int32_t* status;               // two int32
+};
+JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
+                          const whenet_surface_t& dst, int channel_order, int32_t* d_status);
+void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16

@@ -48,6 +48,14 @@ class SurfaceC(C.Structure):
     _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("format", C.c_int), ("matrix", C.c_int), ("on_device", C.c_int)]
 
 
+class JpegInfoC(C.Structure):
+    """whenet_jpeg_info_t: the header SOI..SOS of a baseline JPEG stream, self-contained."""
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("qt", C.c_int32 * 3), ("dc", C.c_int32 * 3), ("ac", C.c_int32 * 3), ("restart_interval", C.c_int32),
+                ("intervals", C.c_int32), ("data_offset", C.c_int64), ("q", (C.c_uint8 * 64) * 4), ("q_present", C.c_uint8 * 4),
+                ("huff_counts", (C.c_uint8 * 16) * 4), ("huff_values", (C.c_uint8 * 256) * 4), ("huff_present", C.c_uint8 * 4)]
+
+
 _PROTOS = {
     "whenet_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_P)]),
     "whenet_create_from_memory": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -128,6 +136,12 @@ _PROTOS = {
     "whenet_op_jpeg_encode": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "whenet_jpeg_encode_device": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "whenet_frame_annotate_jpeg": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    "whenet_jpeg_parse": (C.c_int, [_P, C.c_int64, C.POINTER(JpegInfoC)]),
+    "whenet_jpeg_decode_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, _P]),
+    "whenet_jpeg_decode_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, _P]),
+    "whenet_op_jpeg_decode": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, _P]),
+    "whenet_jpeg_decode_device": (C.c_int, [_P, C.POINTER(JpegInfoC), _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, _P, _P]),
+    "whenet_frame_begin_jpeg": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -559,6 +573,52 @@ def jpeg_encode_host(surface: SurfaceC, h: int, w: int, bgr: bool, quality: int,
     if rc not in (OK, EOVERFLOW):
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return rc, int(size.value)
+
+
+def _stream_array(data) -> np.ndarray:
+    """The bytes of a JPEG stream as a contiguous uint8 array (bytes, bytearray, memoryview or a uint8 array; never reinterpreted)."""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise ValueError(f"a JPEG stream must be bytes or a 1-D uint8 array, got {data.dtype} {data.shape}")
+        return np.ascontiguousarray(data)
+    return np.frombuffer(bytes(data), np.uint8)
+
+
+def jpeg_parse(data) -> JpegInfoC:
+    """`whenet_jpeg_parse`: the header SOI..SOS of a stream.  ValueError with the reason for anything but a baseline stream the
+    decoder accepts.  Pure host arithmetic inside the library (no GPU needed)."""
+    lib = load()
+    a = _stream_array(data)
+    info = JpegInfoC()
+    rc = lib.whenet_jpeg_parse(_ptr(a) if a.size else None, int(a.size), C.byref(info))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return info
+
+
+def jpeg_decode_host(data, surface: SurfaceC, bgr: bool) -> np.ndarray:
+    """`whenet_jpeg_decode_host` into a host surface: the two status words int32 [2] (OK or EFORMAT, the first bad interval or -1)."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    rc = lib.whenet_jpeg_decode_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB, _ptr(status))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status
+
+
+def jpeg_decode_planes_host(data, planes: list) -> np.ndarray:
+    """`whenet_jpeg_decode_planes_host` into the uint8 [rows, width] arrays `planes` (one per component, rows contiguous): the two
+    status words."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    ptrs = (_P * 3)(*[p.ctypes.data for p in planes] + [None] * (3 - len(planes)))
+    pitch = np.array([int(p.strides[0]) if p.shape[0] > 1 else int(p.shape[1]) for p in planes] + [0] * (3 - len(planes)), np.int32)
+    rc = lib.whenet_jpeg_decode_planes_host(_ptr(a) if a.size else None, int(a.size), ptrs, _ptr(pitch), _ptr(status))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status
 
 
 def normalise_lut() -> np.ndarray:
@@ -1202,6 +1262,32 @@ class Handle:
         status = result[1:].view(np.int32)
         self._check(self._lib.whenet_frame_annotate_jpeg(self._h, int(ticket), int(frame_index), int(display), int(quality),
                                                          _ptr(out) if out.size else None, int(out.size), _ptr(result), _ptr(status)))
+
+    def op_jpeg_decode(self, data, surface: SurfaceC, bgr: bool) -> np.ndarray:
+        """`whenet_op_jpeg_decode`: the decoder's kernels alone, host to host (works on a postproc handle), into a host surface: the
+        two status words int32 [2] (OK or EFORMAT, the first bad interval or -1)."""
+        a = _stream_array(data)
+        status = np.zeros(2, np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
+                                                    BGR if bgr else RGB, _ptr(status)))
+        return status
+
+    def jpeg_decode_device(self, info: JpegInfoC, d_entropy: int, nbytes: int, surface: SurfaceC, bgr: bool, d_status: int, stream=None) -> None:
+        """`whenet_jpeg_decode_device`: enqueue the decoder on entropy data in device memory; `d_entropy` (nbytes bytes) and
+        `d_status` (two int32) are device addresses, `surface` is a device surface.  The host does not wait."""
+        self._check(self._lib.whenet_jpeg_decode_device(self._h, C.byref(info), _P(int(d_entropy)), int(nbytes), C.byref(surface),
+                                                        BGR if bgr else RGB, _P(int(d_status)), _stream(stream)))
+
+    def frame_begin_jpeg(self, data, status: np.ndarray, bgr: bool = True) -> int:
+        """`whenet_frame_begin_jpeg`: `frame_begin` from the bytes of a JPEG stream, decoded on the device.  status = int32 [2], complete
+        when the ticket's collect call returns; it must stay alive until then."""
+        a = _stream_array(data)
+        if status.dtype != np.int32 or status.size != 2 or not status.flags.c_contiguous:
+            raise ValueError("status must be a contiguous int32 [2] array")
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin_jpeg(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB, C.byref(t),
+                                                      _ptr(status)))
+        return t.value
 
     def frame_annotate(self, ticket: int, frame_index: int, surface: SurfaceC, stream=None, display: int = DISPLAY_SIMPLE) -> None:
         """`whenet_frame_annotate_ex`: enqueue the annotated frame of a ticket whose heads are enqueued.  A host surface is complete

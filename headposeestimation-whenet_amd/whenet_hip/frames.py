@@ -105,6 +105,33 @@ class JpegFrame:
         return self._out[:size].tobytes()
 
 
+class JpegStatus:
+    """What the decoder says about the stream of one `FramePipeline.begin_jpeg` frame, after the frame's collect call: `ok`, and
+    `interval` = the first damaged restart interval (-1: none).  A damaged stream still gives a fully defined frame.  It owns the
+    memory the library writes into."""
+
+    def __init__(self):
+        self._status = np.zeros(2, np.int32)
+        self._done = False
+
+    @property
+    def ready(self) -> bool:
+        return self._done
+
+    def _read(self, i: int) -> int:
+        if not self._done:
+            raise ValueError("JpegStatus: the frame is not collected yet (collect() first)")
+        return int(self._status[i])
+
+    @property
+    def ok(self) -> bool:
+        return self._read(0) == _lib.OK
+
+    @property
+    def interval(self) -> int:
+        return self._read(1)
+
+
 class FramePipeline:
     """`with FramePipeline(model) as fp:` ... `fp.submit(frame_bgr, bboxes)` ... `fp.collect()`.
 
@@ -256,6 +283,24 @@ class FramePipeline:
         ticket = self._h.frame_begin_yuv_device(frame, stream=stream) if frame.on_device else self._h.frame_begin_yuv(frame)
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
+
+    def begin_jpeg(self, data) -> "JpegStatus":
+        """`begin()` from the bytes of a baseline JPEG stream (a still, or one frame of an MJPG file: `whenet_hip.mjpeg.MJPGReader`):
+        what stands for `cv2.imread` / `cap.read()`.  Only the compressed bytes cross the link; the frame is decoded on the device
+        (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
+        `begin(jpeg.decode_host(data, bgr=...))`.  A stream the decoder does not accept (progressive, arithmetic, 12 bit, ...) is a
+        ValueError with the reason and takes no place.  Returns a `JpegStatus`, valid after the frame's `collect()`: damaged entropy
+        data does not raise, it yields a defined frame and `ok == False`."""
+        self._check_can_begin()
+        info = _lib.jpeg_parse(data)
+        st = JpegStatus()
+        ticket = self._h.frame_begin_jpeg(data, st._status, bgr=self._bgr)
+        if self._jpeg is None:
+            self._jpeg = {}
+        self._jpeg.setdefault(ticket, []).append(st)
+        self._begun = (ticket, info.h, info.w)
+        self._last_sizes = [(info.h, info.w)]
+        return st
 
     def begin_clip_yuv(self, frames, stream=None) -> None:
         """A clip from the planes of 1..16 `YUVFrame`s, each with its own format and matrix: frames of one size make a clip as

@@ -93,3 +93,71 @@ def encode_host(frame, quality: int = DEFAULT_QUALITY, bgr: bool = True, capacit
     out = np.empty(bound(h, w) if capacity is None else int(capacity), np.uint8)
     rc, size = _lib.jpeg_encode_host(s, h, w, bgr, quality, out)
     return _finish(rc, size, out)
+
+
+# ---- the decoder: JPEG bytes in, a frame out (csrc/jpeg_dec.hip, include/whenet_hip.h JPEG DECODER) ----
+class DecodeError(ValueError):
+    """Damaged entropy data (status WHENET_EFORMAT): `interval` is the first bad restart interval, `frame` the fully defined frame
+    the decoder still produced (damaged intervals end in zero coefficients)."""
+
+    def __init__(self, interval: int, frame: np.ndarray):
+        super().__init__(f"the JPEG stream is damaged from restart interval {interval} on")
+        self.interval = int(interval)
+        self.frame = frame
+
+
+def info(data) -> dict:
+    """The header SOI..SOS of a stream (`whenet_jpeg_parse`): h, w, components, sampling (hs, vs), restart_interval, intervals,
+    data_offset, the quantisers uint8 [4,64] in natural order and the table ids.  ValueError with the reason for anything but a
+    baseline stream the decoder accepts (progressive, arithmetic, 12 bit, 4 components, several scans, ...)."""
+    i = _lib.jpeg_parse(data)
+    return {"h": i.h, "w": i.w, "components": i.components, "sampling": (i.hs, i.vs), "restart_interval": i.restart_interval,
+            "intervals": i.intervals, "data_offset": i.data_offset, "quantisers": np.ctypeslib.as_array(i.q).copy(),
+            "quantiser_ids": tuple(i.qt[:i.components]), "dc_ids": tuple(i.dc[:i.components]), "ac_ids": tuple(i.ac[:i.components])}
+
+
+def packed_surface(frame: np.ndarray) -> "_lib.SurfaceC":
+    """A uint8 [H,W,3] host array whose rows' pixels are packed (any row stride) as a destination surface."""
+    s = _lib.SurfaceC()
+    s.plane[0], s.pitch[0] = frame.ctypes.data, int(frame.strides[0]) if frame.shape[0] > 1 else 3 * frame.shape[1]
+    s.format, s.matrix, s.on_device = _lib.SURF_PACKED, 0, 0
+    return s
+
+
+def _result(frame: np.ndarray, status: np.ndarray, strict: bool):
+    if strict and status[0] != _lib.OK:
+        raise DecodeError(int(status[1]), frame)
+    return frame
+
+
+def decode(data, handle=None, bgr: bool = True, strict: bool = True) -> np.ndarray:
+    """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
+    (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
+    Damaged data raises `DecodeError` (strict=False: returns the defined frame).  A stream without restart markers is one interval:
+    its entropy decode is one lane, correct and slow."""
+    i = _lib.jpeg_parse(data)
+    frame = np.empty((i.h, i.w, 3), np.uint8)
+    if handle is None:
+        with _lib.Handle.postproc(0) as own:
+            status = own.op_jpeg_decode(data, packed_surface(frame), bgr)
+    else:
+        status = _handle_of(handle).op_jpeg_decode(data, packed_surface(frame), bgr)
+    return _result(frame, status, strict)
+
+
+def decode_host(data, bgr: bool = True, strict: bool = True) -> np.ndarray:
+    """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
+    held to."""
+    i = _lib.jpeg_parse(data)
+    frame = np.empty((i.h, i.w, 3), np.uint8)
+    return _result(frame, _lib.jpeg_decode_host(data, packed_surface(frame), bgr), strict)
+
+
+def decode_planes_host(data):
+    """(the component planes [Y] or [Y, Cb, Cr] as uint8 arrays -- luma h x w, chroma ceil(h / vs) x ceil(w / hs) -- and the status
+    int32 [2]) by the host statement: what the tests compare."""
+    i = _lib.jpeg_parse(data)
+    shapes = [(i.h, i.w)] + [((i.h + i.vs - 1) // i.vs, (i.w + i.hs - 1) // i.hs)] * (i.components - 1)
+    planes = [np.empty(s, np.uint8) for s in shapes]
+    status = _lib.jpeg_decode_planes_host(data, planes)
+    return planes, status

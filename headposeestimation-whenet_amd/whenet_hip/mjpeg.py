@@ -15,6 +15,9 @@ THE FILE.  RIFF 'AVI ' with
     'idx1':       one 16-byte entry per frame: '00dc', AVIIF_KEYFRAME, the chunk's offset from the 'movi' fourcc, its size
 Sizes and counts are patched on close(); all integers little-endian.  Files are limited to the 4 GiB of a RIFF size field.
 
+`MJPGReader(path)` is the other direction: it walks the same tree and yields every '00dc' chunk's bytes (demo_video.py:49-53,
+`cap.read()` of such a file), for `FramePipeline.begin_jpeg` or `whenet_hip.jpeg.decode`.
+
 PINNED: the test suite walks the file chunk by chunk and Pillow decodes every frame.  UNPINNED: that OpenCV or a player opens the
 file -- neither has run next to this code -- and no claim is made to reproduce the bytes OpenCV's own MJPG writer emits.
 """
@@ -92,6 +95,115 @@ class MJPGWriter:
             f.write(self._headers(with_index=True))
         finally:
             f.close()
+
+
+class MJPGReader:
+    """`MJPGReader(path)`: the frames of a Motion-JPEG AVI as bytes, one complete JPEG stream each -- what `cap.read()`
+    (demo_video.py:49-53) decodes on the host, ready for `FramePipeline.begin_jpeg` / `whenet_hip.jpeg.decode`.
+
+        with MJPGReader("in.avi") as src:
+            for data in src: fp.begin_jpeg(data); ...
+
+    Pure Python: it walks the RIFF tree ('RIFF' 'AVI ' > LIST 'hdrl' > 'avih', LIST 'strl' > 'strh' / 'strf'; LIST 'movi' > the 'NNdc'
+    chunks of the first video stream, also inside 'rec ' lists) and keeps every video chunk's position; `width`, `height`, `fps`, `len()`, indexing and
+    iteration read from those.  The index chunk is not needed.  ValueError for anything that is not an MJPG AVI: no RIFF / 'AVI '
+    header, a video stream whose handler and compression are not MJPG, no 'movi' list, a chunk that passes the end of the file
+    (a truncated file)."""
+
+    def __init__(self, path):
+        self._f = open(path, "rb")
+        try:
+            self._f.seek(0, 2)
+            self._size = self._f.tell()
+            self._frames = []          # (offset, size) of every '00dc' payload
+            self.width = self.height = 0
+            self.fps = 0.0
+            self._handler = self._compression = None
+            self._streams, self._video = 0, None      # 'strh' chunks seen; the number of the first video stream: its chunks are 'NNdc'
+            self._movi = False
+            head = self._read(0, 12)
+            if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+                raise ValueError("not an AVI file (no RIFF 'AVI ' header)")
+            riff_end = 8 + struct.unpack("<I", head[4:8])[0]
+            if riff_end > self._size:
+                raise ValueError(f"truncated file: the RIFF chunk says {riff_end} bytes, the file has {self._size}")
+            self._walk(12, riff_end)
+            if not self._movi:
+                raise ValueError("no 'movi' list: not a complete AVI file")
+            if self._handler is None or self._compression is None:
+                raise ValueError("no video stream header ('strh' / 'strf')")
+            if self._handler.upper() != b"MJPG" or self._compression.upper() != b"MJPG":
+                raise ValueError(f"not a Motion-JPEG AVI: the video stream is {self._handler!r} / {self._compression!r}, not b'MJPG'")
+        except Exception:
+            self._f.close()
+            self._f = None
+            raise
+
+    def _read(self, at: int, n: int) -> bytes:
+        self._f.seek(at)
+        return self._f.read(n)
+
+    def _walk(self, at: int, end: int) -> None:
+        while at + 8 <= end:
+            fourcc, size = struct.unpack("<4sI", self._read(at, 8))
+            body = at + 8
+            if body + size > end:
+                raise ValueError(f"truncated file: chunk {fourcc!r} at {at} has {size} bytes, its parent ends at {end}")
+            if fourcc == b"LIST":
+                if size < 4:
+                    raise ValueError(f"a LIST chunk of {size} bytes at {at}")
+                kind = self._read(body, 4)
+                if kind == b"movi":
+                    self._movi = True
+                if kind in (b"hdrl", b"strl", b"movi", b"rec "):
+                    self._walk(body + 4, body + size)
+            elif fourcc == b"avih" and size >= 40:
+                v = struct.unpack("<10I", self._read(body, 40))
+                self.width, self.height = v[8], v[9]
+                if v[0]:
+                    self.fps = 1_000_000 / v[0]
+            elif fourcc == b"strh" and size >= 32:
+                v = struct.unpack("<4s4sIHHIII", self._read(body, 28))
+                self._streams += 1
+                if v[0] == b"vids" and self._handler is None:
+                    self._handler, self._video = v[1], self._streams - 1
+                    if v[6]:
+                        self.fps = v[7] / v[6]
+            elif fourcc == b"strf" and size >= 40 and self._handler is not None and self._compression is None:
+                v = struct.unpack("<IiiHH4s", self._read(body, 20))
+                self._compression = v[5]
+                self.width, self.height = v[1], abs(v[2])
+            elif fourcc[2:] in (b"dc", b"db") and fourcc[:2].isdigit() and int(fourcc[:2]) == self._video:
+                if size > 0:                 # (the chunks of that one stream: another video stream's frames are not mixed in)
+                    self._frames.append((body, size))
+            at = body + size + (size & 1)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def __len__(self) -> int:
+        return len(self._frames)
+
+    def __getitem__(self, i: int) -> bytes:
+        if self._f is None:
+            raise ValueError("read from a closed MJPGReader")
+        at, size = self._frames[i]
+        data = self._read(at, size)
+        if len(data) != size:
+            raise ValueError(f"truncated file: frame {i} has {len(data)} of {size} bytes")
+        return data
+
+    def __iter__(self):
+        for i in range(len(self._frames)):
+            yield self[i]
 
 
 def _chunk(fourcc: bytes, payload: bytes) -> bytes:

@@ -839,6 +839,94 @@ WHENET_API int whenet_jpeg_encode_device(whenet_t* h, const whenet_surface_t* sr
 WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap,
                                int64_t* size, int32_t* status);
 
+/* ---- JPEG DECODER: a JPEG still or an MJPG frame in, the resident frame out (additions to ABI 6).  demo.py starts with `cv2.imread`
+ * of a JPEG, demo_video.py:49-53 with `cap.read()` -- for a camera or an MJPG file a Motion-JPEG decode.  Here the compressed bytes
+ * are what crosses the link; the kernels of csrc/jpeg_dec.hip decode them (the arithmetic is csrc/jpeg_dec_host.h's).  Integers only.
+ * ACCEPTED.  Baseline sequential DCT (SOF0), 8 bit, one interleaved scan, Huffman coding.  Three components are Y, Cb, Cr (JFIF) with
+ * luma sampling 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4) and chroma sampling 1x1; one component is grey.  8-bit DQT with ids 0..3 and
+ * DHT with ids 0..1 per class, several tables per segment allowed; any DRI or none; APPn and COM are skipped; sides 1..8192; streams
+ * below 2^31 bytes.  Everything else -- SOF1, SOF2 and later frame types, arithmetic coding, 12 bit, 4 components, a scan that does
+ * not hold every component, 16-bit DQT, other sampling factors, a missing table, a header that ends early -- is WHENET_EFORMAT from
+ * the host parser with the reason in whenet_last_error (NULL handle for the pure-host calls), before anything is enqueued.
+ * PARSE.  SOI .. SOS into a whenet_jpeg_info_t: size, components, the luma sampling factors hs, vs (1 or 2), per component the
+ * quantiser id qt and the Huffman ids dc, ac; restart_interval Ri in MCUs (0: none); intervals = ceil(MCUs / Ri), 1 without DRI;
+ * data_offset of the entropy data; the quantisers q in NATURAL order; the Huffman tables at index 2 id + class (DC0, AC0, DC1, AC1) as
+ * counts[16] and values.  The struct is self-contained: a decode needs it and the bytes from data_offset on only.
+ * An MCU is 8 hs x 8 vs luma samples: hs vs luma blocks in row order, then Cb, then Cr (grey: one block, 8 x 8).
+ * INTERVALS.  The restart markers are the pairs 0xFF 0xD0..0xD7 of the entropy data, in order.  Interval 0 begins at the data's
+ * first byte, interval k + 1 behind marker k.  Marker k must be RST(k mod 8) and there must be intervals - 1 markers: the first k
+ * whose marker has another number, or intervals - 1 if there are more, or the number of markers if there are fewer, is a bad
+ * interval; it is still decoded from its start, the intervals behind it are not (their coefficients are zero).
+ * ENTROPY DECODE.  T.81 F.2 Huffman decoding, the DC predictors 0 at the start of every interval and kept inside -32768..32767.
+ * 0xFF 0x00 yields one 0xFF data byte; at any other byte pair that begins with 0xFF, and at the end of the data, the interval's
+ * bits end.  An AC symbol (r, s): s > 0 skips r coefficients and reads one; (15, 0) skips 16; any other (r, 0) ends the block.
+ * Coefficient k is clamp(value x Q[k], -2048, 2047) in natural order: every legitimate coefficient of an 8-bit image lies inside,
+ * the clamp keeps every stream inside the int32 arithmetic below.
+ * DAMAGE.  A code that is no code word, a run that passes coefficient 63, bits that end inside a symbol: the block in hand keeps
+ * what was decoded of it, the remaining blocks of the interval are zero coefficients (DC included), and the interval is bad.
+ * Nothing faults and nothing is read or written outside its buffer.  status[0] = WHENET_OK, or WHENET_EFORMAT with status[1] = the
+ * first bad interval (else -1); the output is fully defined either way and the kernels' equals the host statement's byte for byte.
+ * INVERSE DCT.  T = WHENET_JPEG_DCT, c = a block's coefficients [v][u], int32 arithmetic, >> an arithmetic shift:
+ *     a[y][u] = sum_v T[v][y] c[v][u]        r[y][u] = (a[y][u] + 128) >> 8
+ *     b[y][x] = sum_u T[u][x] r[y][u]        sample  = clamp(((b[y][x] + 32768) >> 16) + 128, 0, 255)
+ * The columns of |T| sum to at most 10,822, so |a| < 2.3e7, |r| < 8.7e4, |b| < 9.5e8.  Within 1 level of the rounded float64
+ * inverse DCT (about 2 % of the samples differ from it by one).
+ * PLANES.  The luma plane is h x w samples, the chroma planes ceil(h / vs) x ceil(w / hs); blocks beyond those edges are decoded
+ * and their samples dropped.
+ * FRAME.  WHENET_SURF_PACKED: pixel (x, y) takes the chroma sample (x >> (hs - 1), y >> (vs - 1)) and the JFIF row of the YUV
+ * ingest's conversion; channel_order says where R and B go; grey gives B = G = R = Y.  For a 4:2:0 stream this is bit for bit
+ * whenet_yuv_to_bgr_host of the decoded I420 planes.  A 4:2:0 stream also decodes into a WHENET_YUV_I420 or WHENET_YUV_NV12 surface
+ * whose matrix is WHENET_YUV_JFIF (other samplings, another matrix: WHENET_EINVAL).  Nearest-neighbour chroma is a stated
+ * difference from libjpeg's default triangle filter: the frame is the project's own, not cv2.imread's bytes.
+ *   whenet_jpeg_parse        pure host: the stream's header into *info
+ *   whenet_jpeg_decode_host  the whole decoder as pure host arithmetic (no GPU): the statement the kernels are held to.  dst: a
+ *                  host surface (on_device = 0) of the stream's size; channel_order is read for WHENET_SURF_PACKED only
+ *   whenet_jpeg_decode_planes_host  the same up to the component planes: plane[c] = rows of the component's width, pitch[c] bytes
+ *                  apart (>= the width), c < components
+ *   whenet_op_jpeg_decode    the kernels alone, host to host, same arguments and results.  Works on a whenet_create_postproc handle.
+ *   whenet_jpeg_decode_device  info (host memory, from whenet_jpeg_parse of the header bytes), d_entropy = the nbytes bytes of the
+ *                  stream from data_offset on, dst (on_device = 1) and d_status (two int32) in the handle's device memory.
+ *                  ENQUEUE-ONLY on the engine's stream and ordered against `stream` as the ingest section's ORDER paragraph states
+ *                  -- with two exceptions in which the host WAITS for the engine's stream first: a call whose stream needs larger
+ *                  work buffers than any call before it, and a call whose quantisers or Huffman tables differ from the previous
+ *                  call's (then followed by one blocking copy of the 6 KB of decode tables).  The first call always waits; the
+ *                  frames of one MJPG stream, which repeat their tables and their size, do not;
+ *                  the device-pointer checks of the device ingest apply to d_entropy, every plane and d_status.  The stream
+ *                  whenet_jpeg_encode_device left in device memory decodes this way with whenet_jpeg_header's bytes parsed on the
+ *                  host; where the stream's length is known on the device only, nbytes may be the capacity of a buffer that was
+ *                  zero-filled before the encode: bytes behind EOI are scanned for restart markers like the rest, zeros hold none.
+ *   whenet_frame_begin_jpeg  stands for cv2.imread / cap.read(): parses on the host (a refused stream takes no slot), copies only
+ *                  the compressed bytes into pinned staging, one asynchronous H2D, and the decode kernels on the copy stream into the
+ *                  slot's frame buffer, before the event every consumer waits for -- where csrc/yuv.hip runs for
+ *                  whenet_frame_begin_yuv.  The ticket then behaves as whenet_frame_begin's with the same channel_order.  status[0..1]
+ *                  are complete when the ticket's collect call returns; the pointer must stay valid until then.  Damaged data still
+ *                  gives a ticket and a fully defined frame.
+ * A stream without DRI is ONE interval: its entropy decode is one lane walking the whole picture, correct and serial.  Measured on one
+ * MI355X (docs/experiments.md section 31) the decoder is slower than a host decoder in every case: one restart interval per lane.
+ * Not built: clips of JPEG streams, parallel decoding of streams without restart markers, progressive / arithmetic / 12-bit streams.
+ * WHENET_EINVAL: a NULL argument or plane, size < 1, a pitch below the row bytes, an unknown format / channel order. */
+typedef struct {
+    int32_t h, w, components;
+    int32_t hs, vs;                  /* luma sampling factors (1 or 2); chroma is 1 x 1 */
+    int32_t qt[3], dc[3], ac[3];     /* per component: quantiser id, DC and AC Huffman table ids */
+    int32_t restart_interval;        /* Ri in MCUs; 0: no DRI */
+    int32_t intervals;               /* ceil(MCUs / Ri); 1 without DRI */
+    int64_t data_offset;             /* where the entropy data begins in the stream */
+    uint8_t q[4][64];                /* natural order */
+    uint8_t q_present[4];
+    uint8_t huff_counts[4][16];      /* index 2 id + class: DC0, AC0, DC1, AC1 */
+    uint8_t huff_values[4][256];
+    uint8_t huff_present[4];
+} whenet_jpeg_info_t;
+WHENET_API int whenet_jpeg_parse(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info);
+WHENET_API int whenet_jpeg_decode_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int32_t status[2]);
+WHENET_API int whenet_jpeg_decode_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int32_t status[2]);
+WHENET_API int whenet_op_jpeg_decode(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order,
+                          int32_t status[2]);
+WHENET_API int whenet_jpeg_decode_device(whenet_t* h, const whenet_jpeg_info_t* info, const uint8_t* d_entropy, int64_t nbytes,
+                              const whenet_surface_t* dst, int channel_order, int32_t* d_status, void* stream);
+WHENET_API int whenet_frame_begin_jpeg(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int* ticket, int32_t* status);
+
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event
  * recorded on the chain's stream between consecutive kernel launches; a launch's time is

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""What the device JPEG decoder costs and what it replaces, for 1920 x 1080 and 640 x 480 frames (recorded, not gated):
+
+    (i)   decode_us             device time of the decoder alone on entropy bytes that are resident in device memory
+                                (whenet_jpeg_decode_device into a tight BGR frame): events around back-to-back calls, for three
+                                streams of the same picture:
+                                    own        the library's encoder at quality 95: one restart interval per MCU row (68 / 30)
+                                    pillow_rst Pillow at quality 95, 4:2:0, restart_marker_rows=1
+                                    pillow     the same without DRI: ONE interval, the entropy decode is one lane
+                                decode_call_host_us = the host's time inside one call (the kernels' own times come from a kernel
+                                trace of this tool)
+    (ii)  begin_us, begin_jpeg_us
+                                one frame with 4 heads, begin -> heads -> collect, from the BGR frame (the parent commit's path)
+                                and from the stream (begin_jpeg), depth 1, the median of single frames
+    (iii) pillow_decode_us, h2d_us
+                                what it replaces: Pillow's decode of the stream on one core, and the H2D of 3 bytes per pixel
+    (iv)  bytes_frame, bytes_jpeg
+                                bytes over PCIe per frame, both ways
+
+  python tools/jpeg_dec_bench.py [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30]
+
+Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
+events on the stream the work is enqueued on.  The frames the streams decode to are checked against the host statement first.
+One JSON line per size.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.environ.get("WHENET_HIP_PKG") or os.path.join(ROOT, "headposeestimation-whenet_amd"))
+
+
+def median_us(fn, rounds, sync):
+    out = []
+    for _ in range(rounds):
+        sync()
+        t = time.perf_counter()
+        fn()
+        sync()
+        out.append((time.perf_counter() - t) * 1e6)
+    return statistics.median(out)
+
+
+def streams_of(frame_bgr, quality=95):
+    from PIL import Image
+    from whenet_hip import jpeg
+    im = Image.fromarray(np.ascontiguousarray(frame_bgr[..., ::-1]))
+    out = {"own": jpeg.encode_host(frame_bgr, quality)}
+    for name, kw in (("pillow_rst", {"restart_marker_rows": 1}), ("pillow", {})):
+        buf = io.BytesIO()
+        im.save(buf, "JPEG", quality=quality, subsampling=2, **kw)
+        out[name] = buf.getvalue()
+    return out
+
+
+def size_leg(m, h, w, args):
+    import torch
+    from PIL import Image
+    from whenet_hip import _lib, jpeg, synth
+    from whenet_hip.frames import FramePipeline
+    hnd = m._handle
+    frame, boxes = synth.video_frame(h, w), synth.head_boxes(4, h, w)
+    sync = torch.cuda.synchronize
+    stream = torch.cuda.current_stream().cuda_stream or None
+    res = {"frame": [h, w], "heads": 4, "bytes_frame": 3 * h * w}
+    dst = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    s = _lib.SurfaceC()
+    s.plane[0], s.pitch[0], s.format, s.on_device = dst.data_ptr(), 3 * w, _lib.SURF_PACKED, 1
+    status = torch.zeros(2, dtype=torch.int32, device="cuda")
+    torch.set_num_threads(1)
+    for name, data in streams_of(frame).items():
+        info = _lib.jpeg_parse(data)
+        ent = torch.from_numpy(np.frombuffer(data, np.uint8)[info.data_offset:].copy()).cuda()
+        decode = lambda: hnd.jpeg_decode_device(info, ent.data_ptr(), ent.numel(), s, True, status.data_ptr(), stream=stream)
+        iters = max(1, args.iters // 10) if info.intervals == 1 else args.iters
+        for _ in range(2):
+            decode()
+        sync()
+        want = jpeg.decode_host(data)
+        r = {"intervals": info.intervals, "bytes_jpeg": len(data), "equals_host": bool(np.array_equal(dst.cpu().numpy(), want)),
+             "status": status.cpu().tolist()}
+        times, calls = [], []
+        for _ in range(args.rounds):                      # (i): events around `iters` decodes on the caller's stream
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            sync()
+            a.record()
+            t = time.perf_counter()
+            for _ in range(iters):
+                decode()
+            calls.append((time.perf_counter() - t) * 1e6 / iters)
+            b.record()
+            sync()
+            times.append(a.elapsed_time(b) * 1e3 / iters)
+        r["decode_us"] = round(statistics.median(times), 1)
+        r["decode_call_host_us"] = round(statistics.median(calls), 1)
+
+        def pillow():                                     # (iii): the decode it replaces, one core
+            im = Image.open(io.BytesIO(data))
+            im.load()
+        r["pillow_decode_us"] = round(median_us(pillow, args.rounds, lambda: None), 1)
+        with FramePipeline(m, depth=1) as fp:             # (ii): one frame from the stream
+            def one_jpeg():
+                fp.begin_jpeg(data)
+                fp.heads(boxes)
+                fp.collect()
+            for _ in range(3):
+                one_jpeg()
+            n = max(1, iters // 2)
+            r["begin_jpeg_us"] = round(median_us(lambda: [one_jpeg() for _ in range(n)], args.rounds, sync) / n, 1)
+        res[name] = r
+    with FramePipeline(m, depth=1) as fp:                 # (ii): the same frame as BGR pixels, the parent commit's path
+        def one():
+            fp.begin(frame)
+            fp.heads(boxes)
+            fp.collect()
+        for _ in range(5):
+            one()
+        res["begin_us"] = round(median_us(lambda: [one() for _ in range(args.iters)], args.rounds, sync) / args.iters, 1)
+    pinned = torch.from_numpy(frame).pin_memory()
+    res["h2d_us"] = round(median_us(lambda: dst.copy_(pinned, non_blocking=True), args.rounds, sync), 1)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=30)
+    args = ap.parse_args()
+    import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
+    import whenet
+    m = whenet.WHENet(dtype="f16")
+    try:
+        for size in args.sizes:
+            h, w = (int(v) for v in size.split("x"))
+            print(json.dumps(size_leg(m, h, w, args)), flush=True)
+    finally:
+        m.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
