@@ -1061,6 +1061,85 @@ int whenet_jpeg_decode_planes_host(const uint8_t* data, int64_t size, uint8_t* c
     }
 }
 
+int whenet_jpeg_decode_segmented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int seg_bytes, int window,
+                                      int32_t status[2], int64_t stats[8]) {
+    try {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_segmented_host: NULL argument");
+        WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL, "jpeg_decode_segmented_host: seg_bytes must be a power of two in 4..4096");
+        WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, "jpeg_decode_segmented_host: window must be 1..1024");
+        whenet_jpeg_info_t info;
+        if (const int rc = parse_for_host("jpeg_decode_segmented_host", data, size, info)) return rc;
+        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_segmented_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_segmented_host: the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, planes, status, stats);
+        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_jpeg_decode_segmented_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int seg_bytes, int window,
+                                             int32_t status[2], int64_t stats[8]) {
+    try {
+        WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_segmented_planes_host: NULL argument");
+        WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "jpeg_decode_segmented_planes_host: seg_bytes must be a power of two in 4..4096");
+        WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, "jpeg_decode_segmented_planes_host: window must be 1..1024");
+        whenet_jpeg_info_t info;
+        if (const int rc = parse_for_host("jpeg_decode_segmented_planes_host", data, size, info)) return rc;
+        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
+        for (int c = 0; c < g.comps; ++c) {
+            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
+            WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
+                           "jpeg_decode_segmented_planes_host: plane " + std::to_string(c) + " is NULL or its pitch is below its " + std::to_string(cw) +
+                               " samples");
+        }
+        whenet::JpegDecPlanes pl;
+        whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, pl, status, stats);
+        for (int c = 0; c < g.comps; ++c) {
+            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
+            for (int y = 0; y < ch; ++y)
+                std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
+        }
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_jpeg_seg_dc_scan_host(const int32_t* diff, int64_t n, int chunk, int32_t* pred) {
+    if (n < 0 || chunk < 1 || (n > 0 && (diff == nullptr || pred == nullptr))) {
+        g_create_error = "jpeg_seg_dc_scan_host: NULL argument, n < 0 or chunk < 1";
+        return WHENET_EINVAL;
+    }
+    whenet::jpeg_seg_dc_scan_host(diff, n, chunk, pred);
+    return WHENET_OK;
+}
+
+int whenet_op_jpeg_decode_ex(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
+                             int seg_bytes, int32_t status[2], int64_t stats[8]) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_ex: NULL argument");
+        WHENET_REQUIRE(entropy == 0 || entropy == 1, WHENET_EINVAL, "op_jpeg_decode_ex: entropy must be 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy == 0 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_ex: seg_bytes must be a power of two in 4..4096");
+        e.op_jpeg_decode(data, size, *dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, stats);
+    });
+}
+
+int whenet_jpeg_decode_counters(whenet_t* h, int64_t out[4]) {
+    if (out == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        e.add_jpeg_decode_counters(out);
+        for (const whenet::Engine* r : h->replicas) r->add_jpeg_decode_counters(out);
+        for (const whenet::Engine* r : h->fan) r->add_jpeg_decode_counters(out);
+    });
+}
+
 int whenet_op_jpeg_decode(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int32_t status[2]) {
     return guarded(h, [&](whenet::Engine& e) {
         WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");

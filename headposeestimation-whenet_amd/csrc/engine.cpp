@@ -281,6 +281,18 @@ void Engine::set_option(const std::string& key, long value) {
         lb_cache_.clear();
         lb_cache_cap_ = int(value);
         return;
+    } else if (key == "jpeg_entropy") {
+        WHENET_REQUIRE(value >= 0 && value <= 2, WHENET_EINVAL, "jpeg_entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto, default)");
+        jpeg_entropy_ = int(value);
+        return;
+    } else if (key == "jpeg_seg_lanes") {
+        WHENET_REQUIRE(value == 0 || value == 16 || value == 32 || value == 64, WHENET_EINVAL, "jpeg_seg_lanes must be 0 (default), 16, 32 or 64");
+        jpeg_seg_lanes_ = int(value);
+        return;
+    } else if (key == "jpeg_seg_bytes") {
+        WHENET_REQUIRE(jpeg_seg_bytes_ok(value), WHENET_EINVAL, "jpeg_seg_bytes must be a power of two in 4..4096");
+        jpeg_seg_bytes_ = int(value);
+        return;
     } else if (key == "host_lanes") {
         WHENET_REQUIRE(value >= 1 && value <= MAX_LANES, WHENET_EINVAL, "host_lanes must be 1..8");
         host_lanes_ = int(value);

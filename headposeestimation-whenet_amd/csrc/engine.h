@@ -354,7 +354,12 @@ class Engine {
     // engine's (grown on the first call for a size).
     // frame_begin_jpeg: frame_begin whose H2D carries the compressed bytes (and the decode tables, one copy) and whose kernels run
     // on the copy stream before slot.copied; the two status words come back through pinned memory with the ticket's collect call.
-    void op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status);
+    // The entropy stage's form (0: an interval per lane, 1: segmented, jpeg_dec_seg.hip) follows the options "jpeg_entropy" (2: auto,
+    // by the bytes per interval) and "jpeg_seg_bytes"; op_jpeg_decode takes them from its arguments where entropy >= 0 and reads the
+    // segmented form's statistics back into stats (8 int64, may be nullptr).
+    void op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy = -1,
+                        int seg_bytes = 0, int64_t* stats = nullptr);
+    void add_jpeg_decode_counters(int64_t out[4]) const;      // decodes launched in form 0, in form 1
     void jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
                             int channel_order, int32_t* d_status, hipStream_t stream);
     int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status);
@@ -579,6 +584,11 @@ class Engine {
     DeviceBuffer jpeg_dec_scratch_;      // jpeg_decode_device's work buffers, and the decode tables of its last stream (kept while
     DeviceBuffer jpeg_dec_tables_d_;     // the next stream's are the same: an MJPG stream repeats its tables)
     std::vector<JpegDecTables> jpeg_dec_tables_h_;
+    int jpeg_entropy_ = 2, jpeg_seg_bytes_ = JPEG_SEG_DEFAULT_BYTES;      // options "jpeg_entropy", "jpeg_seg_bytes"
+    int jpeg_seg_lanes_ = 0;                                             // option "jpeg_seg_lanes" (a measurement knob; 0: the default)
+    int64_t jpeg_dec_launched_[2] = {0, 0};                              // decodes launched in form 0, form 1
+    // the layout of a decode's work buffers in the form the options (or `entropy` >= 0, `seg_bytes` > 0) give this stream
+    JpegDecScratch jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy = -1, int seg_bytes = 0) const;
 
     void open_device(int device_id);
     void require_model() const;

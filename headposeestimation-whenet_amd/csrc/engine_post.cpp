@@ -1425,7 +1425,17 @@ whenet_jpeg_info_t parse_or_refuse(const char* what, const uint8_t* data, int64_
 }
 }  // namespace
 
-void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status) {
+JpegDecScratch Engine::jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy, int seg_bytes) const {
+    const int form = jpeg_dec_form(entropy >= 0 ? entropy : jpeg_entropy_, nbytes, g.intervals);
+    JpegDecScratch lay(g, data_bytes, nbytes, form, seg_bytes > 0 ? seg_bytes : jpeg_seg_bytes_);
+    lay.seg_lanes = jpeg_seg_lanes_;
+    return lay;
+}
+
+void Engine::add_jpeg_decode_counters(int64_t out[4]) const { out[0] += jpeg_dec_launched_[0], out[1] += jpeg_dec_launched_[1]; }
+
+void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy,
+                            int seg_bytes, int64_t* stats) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
     const whenet_jpeg_info_t info = parse_or_refuse("op_jpeg_decode", data, size);
@@ -1435,7 +1445,7 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
     check_surface("op_jpeg_decode", dst, info.h, info.w);
     const JpegDecGeom g = jpeg_dec_geom(info);
     const size_t nbytes = size_t(size - info.data_offset);
-    const JpegDecScratch lay(g, nbytes);
+    const JpegDecScratch lay = jpeg_dec_layout(g, nbytes, int64_t(nbytes), entropy, seg_bytes);
     std::vector<JpegDecTables> tables(1);
     jpeg_dec_build_tables(info, tables[0]);
     // the destination on the device: every plane at the caller's pitch and at the caller's address modulo 16, between two guard
@@ -1458,6 +1468,7 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
     launch_jpeg_decode(jpeg_dec_args(g, d_scratch, lay, reinterpret_cast<const uint8_t*>(d_scratch + lay.data), (long long)(nbytes), d_dst,
                                      channel_order, d_status),
                        lay, stream_);
+    ++jpeg_dec_launched_[lay.form];
     d_out.to_host(stream_, off, 0, nullptr, "op_jpeg_decode");      // waits, checks the guard zones
     std::vector<uint8_t> back(total);
     WHENET_HIP_CHECK(hipMemcpy(back.data(), d_out.frames(), total, hipMemcpyDeviceToHost));
@@ -1472,6 +1483,16 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
         WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
                        "op_jpeg_decode: the kernel wrote outside the rows of the surface (byte " + std::to_string(i) + ")");
     WHENET_HIP_CHECK(hipMemcpy(status, d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (stats != nullptr) {
+        if (lay.form == 1) {
+            WHENET_HIP_CHECK(hipMemcpy(stats, d_scratch + lay.seg_stats, 8 * sizeof(int64_t), hipMemcpyDeviceToHost));
+        } else {      // an interval per lane: the intervals it decoded are those up to the first one the markers make bad
+            int32_t meta0 = 0;
+            WHENET_HIP_CHECK(hipMemcpy(&meta0, d_scratch + lay.meta, sizeof(int32_t), hipMemcpyDeviceToHost));
+            std::fill(stats, stats + 8, int64_t(0));
+            stats[0] = std::min(meta0, g.intervals - 1) + 1;
+        }
+    }
 }
 
 void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
@@ -1490,7 +1511,7 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     WHENET_REQUIRE(reinterpret_cast<uintptr_t>(d_status) % 4 == 0, WHENET_EINVAL, "jpeg_decode_device: d_status is not aligned to 4 bytes");
     // allocations, the tables and the events first: nothing is enqueued yet if one of them fails
     const JpegDecGeom g = jpeg_dec_geom(info);
-    const JpegDecScratch lay(g, 0);
+    const JpegDecScratch lay = jpeg_dec_layout(g, 0, nbytes);
     if (lay.bytes > jpeg_dec_scratch_.bytes()) {      // (the buffer in hand may still be read by an earlier call's kernels)
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         jpeg_dec_scratch_.reset(lay.bytes);
@@ -1511,6 +1532,7 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     WHENET_HIP_CHECK(hipEventRecord(jpeg_source_, stream));
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, jpeg_source_, 0));
     launch_jpeg_decode(a, lay, stream_);
+    ++jpeg_dec_launched_[lay.form];
     WHENET_HIP_CHECK(hipEventRecord(jpeg_done_, stream_));
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream, jpeg_done_, 0));
 }
@@ -1523,7 +1545,7 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     const whenet_jpeg_info_t info = parse_or_refuse("frame_begin_jpeg", data, size);      // (before a slot is taken)
     const JpegDecGeom g = jpeg_dec_geom(info);
     const size_t nbytes = size_t(size - info.data_offset);
-    const JpegDecScratch lay(g, nbytes);
+    const JpegDecScratch lay = jpeg_dec_layout(g, nbytes, int64_t(nbytes));
     Slot& slot = *free_slot();
     ensure_slot(slot, 1);
     const size_t fbytes = size_t(info.h) * info.w * 3;
@@ -1546,6 +1568,7 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     launch_jpeg_decode(jpeg_dec_args(g, slot.jpg_dec.as<void>(), lay, slot.jpg_dec.as<uint8_t>() + lay.data, (long long)(nbytes), dst,
                                      channel_order, static_cast<int32_t*>(d_status)),
                        lay, copy_stream());
+    ++jpeg_dec_launched_[lay.form];
     WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
     slot.fh = info.h, slot.fw = info.w, slot.swap_rb = channel_order == WHENET_BGR;
     slot.frame_ticket = finish_submission(slot, 0);

@@ -265,20 +265,32 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArg
 
 }  // namespace
 
-JpegDecScratch::JpegDecScratch(const JpegDecGeom& g, size_t data_bytes) {
+JpegDecScratch::JpegDecScratch(const JpegDecGeom& g, size_t data_bytes, long long nbytes, int form_, int seg_bytes_) {
     const auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
     tables = 0;
     data = up(sizeof(JpegDecTables));
     upload_bytes = data + data_bytes;
     start = up(upload_bytes);
     meta = up(start + size_t(g.intervals) * sizeof(int32_t));
-    coef = up(meta + 4 * sizeof(int32_t));
+    seg_stats = meta + 64;
+    coef = up(seg_stats + 8 * sizeof(long long));
     zero_bytes = coef - start;
     coef_bytes = size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm) * 64 * sizeof(int16_t);
     size_t at = up(coef + coef_bytes);
     for (int c = 0; c < 3; ++c) {
         plane[c] = at;
         if (c < g.comps) at = up(at + size_t(g.plane_pitch[c]) * size_t(g.plane_rows[c]));
+    }
+    form = form_, seg_bytes = form_ == 1 ? seg_bytes_ : 0, seg_cap = 0;
+    first_seg = seg_exit = seg_count = seg_blk = at;
+    if (form == 1) {
+        WHENET_REQUIRE(jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL, "jpeg_decode: seg_bytes must be a power of two in 4..4096");
+        seg_cap = jpeg_seg_bound(nbytes < 0 ? (long long)(data_bytes) : nbytes, g.intervals, seg_bytes);
+        WHENET_REQUIRE(seg_cap < 0x7FFFFFFF, WHENET_EINVAL, "jpeg_decode: more segments than an int32 counts");
+        first_seg = at, at = up(at + (size_t(g.intervals) + 1) * sizeof(int32_t));
+        seg_exit = at, at = up(at + size_t(seg_cap) * sizeof(uint64_t));
+        seg_count = at, at = up(at + size_t(seg_cap) * sizeof(JpegSegCount));
+        seg_blk = at, at = up(at + size_t(seg_cap) * 4 * sizeof(int32_t));
     }
     bytes = at;
 }
@@ -298,6 +310,10 @@ JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecSc
     }
     a.format = dst.format, a.channel_order = channel_order;
     a.status = d_status;
+    a.form = lay.form, a.seg_bytes = lay.seg_bytes, a.seg_cap = int(lay.seg_cap), a.seg_lanes = lay.seg_lanes;
+    a.seg_stats = reinterpret_cast<long long*>(s + lay.seg_stats);
+    a.first_seg = reinterpret_cast<int32_t*>(s + lay.first_seg), a.seg_exit = reinterpret_cast<uint64_t*>(s + lay.seg_exit);
+    a.seg_count = reinterpret_cast<JpegSegCount*>(s + lay.seg_count), a.seg_blk = reinterpret_cast<int32_t*>(s + lay.seg_blk);
     return a;
 }
 
@@ -328,7 +344,17 @@ void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStre
     WHENET_HIP_CHECK(hipMemsetAsync(a.coef, 0, lay.coef_bytes, stream));
     hipLaunchKernelGGL(whenet_jpeg_dec_scan_kernel, dim3(1), dim3(THREADS), 0, stream, a);
     WHENET_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(whenet_jpeg_dec_entropy_kernel, dim3((g.intervals + ENT_LANES - 1) / ENT_LANES), dim3(ENT_THREADS), 0, stream, a);
+    // the entropy stage in the form the caller's layout was made for: an interval per lane, or the segmented form (jpeg_dec_seg.hip)
+    WHENET_REQUIRE(a.form == 0 || a.form == 1, WHENET_EINVAL, "jpeg_decode: the entropy form must be 0 or 1");
+    if (a.form == 1) {
+        WHENET_REQUIRE(lay.form == 1 && jpeg_seg_bytes_ok(a.seg_bytes) && a.seg_bytes == lay.seg_bytes &&
+                           (long long)(a.seg_cap) == jpeg_seg_bound(a.nbytes, g.intervals, a.seg_bytes) && (long long)(a.seg_cap) <= lay.seg_cap &&
+                           a.seg_stats != nullptr && a.first_seg != nullptr && a.seg_exit != nullptr && a.seg_count != nullptr && a.seg_blk != nullptr,
+                       WHENET_EINVAL, "jpeg_decode: the work buffers are not those of the segmented form of this stream");
+        launch_jpeg_decode_segmented(a, stream);
+    } else {
+        hipLaunchKernelGGL(whenet_jpeg_dec_entropy_kernel, dim3((g.intervals + ENT_LANES - 1) / ENT_LANES), dim3(ENT_THREADS), 0, stream, a);
+    }
     WHENET_HIP_CHECK(hipGetLastError());
     const long long nblocks = (long long)(g.mcu_cols) * g.mcu_rows * g.bpm;
     hipLaunchKernelGGL(whenet_jpeg_dec_idct_kernel, dim3(unsigned((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(THREADS), 0, stream, a);

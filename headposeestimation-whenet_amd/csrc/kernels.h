@@ -9,6 +9,7 @@
 #include "overlay_host.h"
 #include "jpeg_host.h"
 #include "jpeg_dec_host.h"
+#include "jpeg_dec_seg_host.h"
 
 namespace whenet {
 
@@ -674,9 +675,23 @@ void launch_jpeg_flush(const void* d_stream, void* to, const long long* d_size, 
 //            launch_yuv_planes_to_bgr), or an I420 / NV12 surface for a 4:2:0 stream.  No thread stores outside the rows' bytes.
 // JpegDecScratch lays the work buffers out in one allocation; tables | data at its front are what a caller uploads in one copy
 // (data_bytes = 0: the data lies elsewhere).
+// The entropy stage has a second form (jpeg_dec_seg.hip; the arithmetic is jpeg_dec_seg_host.h's): form = 1 decodes every interval
+// with many lanes, a lane per segment of seg_bytes of the data.  Behind the scan, six launches stand for `entropy`:
+//   segtab   one workgroup: the segments of every decoded interval -> first_seg [intervals + 1] (an exclusive scan), the totals
+//   sync     one workgroup per window of WHENET_JPEG_SEG_WINDOW segments, states in LDS: the exit state of every segment
+//   stitch   one lane per interval: the true state over each window boundary inside the interval
+//   count    one lane per segment: its blocks and their DC differences as saturating maps
+//   segscan  one workgroup per interval: every segment's first block and entry predictors
+//   write    one lane per segment: its blocks -> coef, through an LDS stage; damage lowers meta[1]
+// Every grid is sized from seg_cap = ceil(nbytes / seg_bytes) + intervals, the host's bound; surplus lanes exit.
 struct JpegDecScratch {
     size_t tables, data, upload_bytes, start, meta, zero_bytes, coef, coef_bytes, plane[3], bytes;      // byte offsets and extents
-    JpegDecScratch(const JpegDecGeom& g, size_t data_bytes);
+    size_t seg_stats, first_seg, seg_exit, seg_count, seg_blk;      // seg_stats: 8 int64 inside the zeroed bytes; the others: form 1 only
+    int form, seg_bytes;
+    int seg_lanes = 0;      // decoding lanes per wave of the segmented form's kernels: 16, 32 or 64 (0: the default)
+    long long seg_cap;
+    // nbytes: the length of the entropy data (< 0: data_bytes)
+    JpegDecScratch(const JpegDecGeom& g, size_t data_bytes, long long nbytes = -1, int form = 0, int seg_bytes = 0);
 };
 struct JpegDecArgs {
     JpegDecGeom g;
@@ -691,7 +706,17 @@ struct JpegDecArgs {
     int dst_pitch[3];
     int format, channel_order;
     int32_t* status;               // two int32
+    // the segmented form (form = 1)
+    int form, seg_bytes, seg_cap;
+    int seg_lanes;                 // decoding lanes per wave of the sync and write kernels: 16, 32 or 64 (0: the default)
+    long long* seg_stats;          // 8, zeroed with start | meta
+    int32_t* first_seg;            // [intervals + 1]
+    uint64_t* seg_exit;            // [seg_cap] exit states
+    JpegSegCount* seg_count;       // [seg_cap]
+    int32_t* seg_blk;              // [seg_cap][4]: the first block's index in the interval, the three predictors there
 };
+// the segmented form's launches (jpeg_dec_seg.hip), behind the scan kernel and in front of the inverse DCT
+void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream);
 JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
                           const whenet_surface_t& dst, int channel_order, int32_t* d_status);
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream);

@@ -141,6 +141,11 @@ _PROTOS = {
     "whenet_jpeg_decode_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, _P]),
     "whenet_op_jpeg_decode": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, _P]),
     "whenet_jpeg_decode_device": (C.c_int, [_P, C.POINTER(JpegInfoC), _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, _P, _P]),
+    "whenet_jpeg_decode_segmented_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_jpeg_decode_segmented_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, C.c_int, C.c_int, _P, _P]),
+    "whenet_op_jpeg_decode_ex": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_jpeg_decode_counters": (C.c_int, [_P, C.POINTER(C.c_int64 * 4)]),
+    "whenet_jpeg_seg_dc_scan_host": (C.c_int, [_P, C.c_int64, C.c_int, _P]),
     "whenet_frame_begin_jpeg": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
@@ -619,6 +624,48 @@ def jpeg_decode_planes_host(data, planes: list) -> np.ndarray:
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return status
+
+
+JPEG_SEG_WINDOW = 256          # WHENET_JPEG_SEG_WINDOW: the segments of one sync window (one workgroup)
+JPEG_SEG_AUTO_BYTES = 4096     # option jpeg_entropy = 2 takes the segmented form from this many bytes per restart interval on
+JPEG_ENTROPY = {"interval": 0, "segmented": 1, "auto": 2}
+
+
+def jpeg_decode_segmented_host(data, surface: SurfaceC, bgr: bool, seg_bytes: int, window: int):
+    """`whenet_jpeg_decode_segmented_host` into a host surface: (the two status words int32 [2], the statistics int64 [8])."""
+    lib = load()
+    a = _stream_array(data)
+    status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+    rc = lib.whenet_jpeg_decode_segmented_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB, int(seg_bytes),
+                                               int(window), _ptr(status), _ptr(stats))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status, stats
+
+
+def jpeg_decode_segmented_planes_host(data, planes: list, seg_bytes: int, window: int):
+    """`whenet_jpeg_decode_segmented_planes_host` into the uint8 [rows, width] arrays `planes`: (status int32 [2], statistics int64 [8])."""
+    lib = load()
+    a = _stream_array(data)
+    status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+    ptrs = (_P * 3)(*[p.ctypes.data for p in planes] + [None] * (3 - len(planes)))
+    pitch = np.array([int(p.strides[0]) if p.shape[0] > 1 else int(p.shape[1]) for p in planes] + [0] * (3 - len(planes)), np.int32)
+    rc = lib.whenet_jpeg_decode_segmented_planes_host(_ptr(a) if a.size else None, int(a.size), ptrs, _ptr(pitch), int(seg_bytes), int(window),
+                                                      _ptr(status), _ptr(stats))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status, stats
+
+
+def jpeg_seg_dc_scan_host(diff, chunk: int) -> np.ndarray:
+    """`whenet_jpeg_seg_dc_scan_host`: the DC predictor behind every difference of int32 [n] `diff` (from 0, kept inside
+    -32768..32767 after every step), computed as the segmented decoder does: saturating maps composed over chunks of `chunk`."""
+    d = np.ascontiguousarray(diff, np.int32)
+    out = np.zeros(d.size, np.int32)
+    rc = load().whenet_jpeg_seg_dc_scan_host(_ptr(d) if d.size else None, int(d.size), int(chunk), _ptr(out) if d.size else None)
+    if rc != OK:
+        raise_for(rc, (load().whenet_last_error(None) or b"").decode(errors="replace"))
+    return out
 
 
 def normalise_lut() -> np.ndarray:
@@ -1271,6 +1318,22 @@ class Handle:
         self._check(self._lib.whenet_op_jpeg_decode(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
                                                     BGR if bgr else RGB, _ptr(status)))
         return status
+
+    def op_jpeg_decode_ex(self, data, surface: SurfaceC, bgr: bool, entropy: int, seg_bytes: int = 128):
+        """`whenet_op_jpeg_decode_ex`: `op_jpeg_decode` with the entropy stage's form forced (0: an interval per lane, 1: segmented with
+        segments of `seg_bytes`): (the two status words, the statistics int64 [8] read back from the device)."""
+        a = _stream_array(data)
+        status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+        self._check(self._lib.whenet_op_jpeg_decode_ex(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
+                                                       BGR if bgr else RGB, int(entropy), int(seg_bytes), _ptr(status), _ptr(stats)))
+        return status, stats
+
+    def jpeg_decode_counters(self) -> dict:
+        """Host-side counts of the JPEG decodes the handle's engines launched in each form of the entropy stage:
+        {"interval": form 0, "segmented": form 1} (options "jpeg_entropy", "jpeg_seg_bytes")."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.whenet_jpeg_decode_counters(self._h, C.byref(out)))
+        return {"interval": int(out[0]), "segmented": int(out[1])}
 
     def jpeg_decode_device(self, info: JpegInfoC, d_entropy: int, nbytes: int, surface: SurfaceC, bgr: bool, d_status: int, stream=None) -> None:
         """`whenet_jpeg_decode_device`: enqueue the decoder on entropy data in device memory; `d_entropy` (nbytes bytes) and

@@ -290,7 +290,8 @@ class FramePipeline:
         (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
         `begin(jpeg.decode_host(data, bgr=...))`.  A stream the decoder does not accept (progressive, arithmetic, 12 bit, ...) is a
         ValueError with the reason and takes no place.  Returns a `JpegStatus`, valid after the frame's `collect()`: damaged entropy
-        data does not raise, it yields a defined frame and `ok == False`."""
+        data does not raise, it yields a defined frame and `ok == False`.  The entropy stage's form follows the handle's options
+        "jpeg_entropy" (0: an interval per lane, 1: segmented, 2: auto, the default) and "jpeg_seg_bytes"; the frame is the same."""
         self._check_can_begin()
         info = _lib.jpeg_parse(data)
         st = JpegStatus()

@@ -130,19 +130,35 @@ def _result(frame: np.ndarray, status: np.ndarray, strict: bool):
     return frame
 
 
-def decode(data, handle=None, bgr: bool = True, strict: bool = True) -> np.ndarray:
+def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False):
     """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
     (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
-    Damaged data raises `DecodeError` (strict=False: returns the defined frame).  A stream without restart markers is one interval:
-    its entropy decode is one lane, correct and slow."""
+    Damaged data raises `DecodeError` (strict=False: returns the defined frame).  `entropy`: the form of the entropy stage --
+    "interval" (one restart interval per lane: a stream without restart markers is one lane, correct and slow), "segmented" (every
+    interval by many lanes, `seg_bytes` of the data each: a power of two in 4..4096, None = 128) or "auto" (the handle's options
+    "jpeg_entropy" / "jpeg_seg_bytes": by default segmented from 4096 bytes per interval on).  The frame is the same, bit for bit.
+    stats=True: (frame, the statistics int64 [8] of `whenet_op_jpeg_decode_ex`); with "auto" the form is then chosen here by the
+    same rule."""
+    if entropy not in _lib.JPEG_ENTROPY:
+        raise ValueError("entropy must be 'auto', 'interval' or 'segmented'")
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
+    form, seg = _lib.JPEG_ENTROPY[entropy], 128 if seg_bytes is None else int(seg_bytes)
+    if form == 2 and (stats or seg_bytes is not None):
+        form = 1 if (int(_lib._stream_array(data).size) - i.data_offset) // max(i.intervals, 1) >= _lib.JPEG_SEG_AUTO_BYTES else 0
+
+    def run(h):
+        if form == 2:
+            return h.op_jpeg_decode(data, packed_surface(frame), bgr), None
+        return h.op_jpeg_decode_ex(data, packed_surface(frame), bgr, form, seg)
+
     if handle is None:
         with _lib.Handle.postproc(0) as own:
-            status = own.op_jpeg_decode(data, packed_surface(frame), bgr)
+            status, st = run(own)
     else:
-        status = _handle_of(handle).op_jpeg_decode(data, packed_surface(frame), bgr)
-    return _result(frame, status, strict)
+        status, st = run(_handle_of(handle))
+    out = _result(frame, status, strict)
+    return (out, st) if stats else out
 
 
 def decode_host(data, bgr: bool = True, strict: bool = True) -> np.ndarray:
@@ -151,6 +167,28 @@ def decode_host(data, bgr: bool = True, strict: bool = True) -> np.ndarray:
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
     return _result(frame, _lib.jpeg_decode_host(data, packed_surface(frame), bgr), strict)
+
+
+def decode_segmented_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SEG_WINDOW, bgr: bool = True, strict: bool = True,
+                          stats: bool = False):
+    """`decode_host` with the entropy stage run as the host emulation of the segmented form (`whenet_jpeg_decode_segmented_host`):
+    segments of `seg_bytes`, sync windows of `window` segments, lanes in a plain loop.  The same frame, bit for bit.
+    stats=True: (frame, status int32 [2], statistics int64 [8]) and damaged data does not raise."""
+    i = _lib.jpeg_parse(data)
+    frame = np.empty((i.h, i.w, 3), np.uint8)
+    status, st = _lib.jpeg_decode_segmented_host(data, packed_surface(frame), bgr, seg_bytes, window)
+    if stats:
+        return frame, status, st
+    return _result(frame, status, strict)
+
+
+def decode_segmented_planes_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SEG_WINDOW):
+    """`decode_planes_host` by the segmented form's host emulation: (planes, status int32 [2], statistics int64 [8])."""
+    i = _lib.jpeg_parse(data)
+    shapes = [(i.h, i.w)] + [((i.h + i.vs - 1) // i.vs, (i.w + i.hs - 1) // i.hs)] * (i.components - 1)
+    planes = [np.empty(s, np.uint8) for s in shapes]
+    status, st = _lib.jpeg_decode_segmented_planes_host(data, planes, seg_bytes, window)
+    return planes, status, st
 
 
 def decode_planes_host(data):

@@ -901,10 +901,47 @@ WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_ind
  *                  whenet_frame_begin_yuv.  The ticket then behaves as whenet_frame_begin's with the same channel_order.  status[0..1]
  *                  are complete when the ticket's collect call returns; the pointer must stay valid until then.  Damaged data still
  *                  gives a ticket and a fully defined frame.
- * A stream without DRI is ONE interval: its entropy decode is one lane walking the whole picture, correct and serial.  Measured on one
- * MI355X (docs/experiments.md section 31) the decoder is slower than a host decoder in every case: one restart interval per lane.
- * Not built: clips of JPEG streams, parallel decoding of streams without restart markers, progressive / arithmetic / 12-bit streams.
- * WHENET_EINVAL: a NULL argument or plane, size < 1, a pitch below the row bytes, an unknown format / channel order. */
+ * ENTROPY FORMS.  The entropy stage has two forms with the same output, bit for bit, damaged streams included.  Form 0 runs one
+ * restart interval per lane: a stream without DRI is ONE interval, one lane walking the whole picture, correct and serial.  Form 1,
+ * the SEGMENTED form (csrc/jpeg_dec_seg.hip, the arithmetic is csrc/jpeg_dec_seg_host.h's), decodes every interval with many lanes
+ * by the self-synchronisation of Huffman streams.  The bytes of interval i (from its start to the next restart marker or the end of
+ * the data) are cut into segments of seg_bytes, a power of two in 4..4096, numbered flat over the decoded intervals; the host bounds
+ * their number by ceil(nbytes / seg_bytes) + intervals and sizes every launch from that, nothing waits for the device.  A SYNC STATE
+ * is what a decoder needs between two code words: the raw byte and the bit offset of the next unread bit, the block's index in its
+ * MCU and the zigzag index, or DEAD (damage met, or the interval's bits have ended); equal states continue alike.  SYNC: a window of
+ * WHENET_JPEG_SEG_WINDOW consecutive segments is one workgroup's; an interval's first segment starts from its true state, every
+ * other one from a guess (its first byte -- behind the 0x00 of a stuffed pair that began in the segment before -- block 0, a DC
+ * symbol next); in round 0 lane j walks its segment to the first code-word boundary at or behind its end and stores the exit state,
+ * in round r it walks segment j + r from its running state and either meets the stored exit state there (done) or replaces it,
+ * stores behind a barrier, chains never cross an interval start, at most `window` rounds.  STITCH: one lane per interval carries the
+ * true state over each window boundary inside it until it meets a stored state.  COUNT: a block belongs to the segment in which its
+ * DC code word begins; from its true entry state a lane counts its blocks and composes their DC differences per component as maps
+ * x -> min(max(x + a, L), H), which compose associatively where a sum of differences under the -32768..32767 clamp does not; an
+ * exclusive scan over an interval's segments gives every segment its first block's index and its three predictors.  WRITE: a lane
+ * decodes the blocks it owns, the tail in later segments included, by the block decode of form 0, and stops at the interval's block
+ * count (bytes behind are padding); damage lowers the first bad interval exactly as DAMAGE states, and every later segment starts
+ * DEAD and writes nothing.  The marker scan, the inverse DCT and the frame kernels are those of form 0.
+ *   option "jpeg_entropy"    0: form 0; 1: form 1; 2: auto -- form 1 where nbytes / intervals >= 4096 bytes (default, see
+ *                  docs/experiments.md section 32).  Read by whenet_op_jpeg_decode, whenet_jpeg_decode_device, whenet_frame_begin_jpeg.
+ *   option "jpeg_seg_bytes"  seg_bytes of form 1, a power of two in 4..4096, default 128
+ *   option "jpeg_seg_lanes"  a measurement knob: decoding lanes per 64-lane wave of form 1's sync, count and write kernels, 16, 32
+ *                  or 64 (0: the default, 32); the output does not depend on it
+ *   whenet_jpeg_decode_segmented_host  whenet_jpeg_decode_host with the entropy stage run as the host emulation of form 1 (lanes in
+ *                  a plain loop), window in 1..1024.  stats (may be NULL): [0] intervals decoded, [1] segments, [2] windows, [3] the
+ *                  largest number of sync rounds in a window, [4] segments walked by the stitch, [5] the largest number of bytes a
+ *                  lane fetched during sync, [6] seg_bytes, [7] the form that ran (0 or 1)
+ *   whenet_jpeg_decode_segmented_planes_host  the same up to the component planes, as whenet_jpeg_decode_planes_host
+ *   whenet_op_jpeg_decode_ex  whenet_op_jpeg_decode with the form forced (entropy 0 or 1; seg_bytes is read for 1); stats as above,
+ *                  read back from the device (form 0: [0] and [7] only)
+ *   whenet_jpeg_decode_counters  out = {decodes launched in form 0, in form 1, 0, 0} over the engines of the handle (host-side counts)
+ *   whenet_jpeg_seg_dc_scan_host  the saturating scan alone: pred[i] = the predictor behind difference i, by maps over chunks
+ * Measured on one MI355X (docs/experiments.md section 32): a 1080p stream without DRI decodes in 15.7 ms in form 1 against 1.03 s in
+ * form 0, one with 68 intervals in 5.2-6.6 ms against 32 ms; a host decoder on one core takes 8.6 ms, and is still faster at 480p.
+ * Not built: clips of JPEG streams, a stitch of several lanes per interval, a marker scan of several workgroups, progressive /
+ * arithmetic / 12-bit streams.
+ * WHENET_EINVAL: a NULL argument or plane, size < 1, a pitch below the row bytes, an unknown format / channel order, a seg_bytes,
+ * window or entropy value outside its range. */
+#define WHENET_JPEG_SEG_WINDOW 256
 typedef struct {
     int32_t h, w, components;
     int32_t hs, vs;                  /* luma sampling factors (1 or 2); chroma is 1 x 1 */
@@ -926,6 +963,14 @@ WHENET_API int whenet_op_jpeg_decode(whenet_t* h, const uint8_t* data, int64_t s
 WHENET_API int whenet_jpeg_decode_device(whenet_t* h, const whenet_jpeg_info_t* info, const uint8_t* d_entropy, int64_t nbytes,
                               const whenet_surface_t* dst, int channel_order, int32_t* d_status, void* stream);
 WHENET_API int whenet_frame_begin_jpeg(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int* ticket, int32_t* status);
+WHENET_API int whenet_jpeg_decode_segmented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int seg_bytes,
+                                      int window, int32_t status[2], int64_t stats[8]);
+WHENET_API int whenet_jpeg_decode_segmented_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int seg_bytes,
+                                             int window, int32_t status[2], int64_t stats[8]);
+WHENET_API int whenet_op_jpeg_decode_ex(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
+                             int seg_bytes, int32_t status[2], int64_t stats[8]);
+WHENET_API int whenet_jpeg_decode_counters(whenet_t* h, int64_t out[4]);
+WHENET_API int whenet_jpeg_seg_dc_scan_host(const int32_t* diff, int64_t n, int chunk, int32_t* pred);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

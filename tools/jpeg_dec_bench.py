@@ -9,6 +9,11 @@
                                     pillow     the same without DRI: ONE interval, the entropy decode is one lane
                                 decode_call_host_us = the host's time inside one call (the kernels' own times come from a kernel
                                 trace of this tool)
+                                The entropy stage's two forms side by side: decode_us is a map {"interval": .., "seg64": ..,
+                                "seg128": .., ...}, one entry per value of --entropy (0: an interval per lane, 1: segmented, 2: the
+                                handle's auto choice) and, for the segmented form, per value of --seg-bytes; "forms" says which form
+                                each entry ran in (whenet_jpeg_decode_counters).  --lanes: decoding lanes per wave of the segmented
+                                kernels (option jpeg_seg_lanes; 0: the default).  --only-decode skips (ii) and (iii).
     (ii)  begin_us, begin_jpeg_us
                                 one frame with 4 heads, begin -> heads -> collect, from the BGR frame (the parent commit's path)
                                 and from the stream (begin_jpeg), depth 1, the median of single frames
@@ -17,7 +22,8 @@
     (iv)  bytes_frame, bytes_jpeg
                                 bytes over PCIe per frame, both ways
 
-  python tools/jpeg_dec_bench.py [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30]
+  python tools/jpeg_dec_bench.py [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
+                                 [--lanes 0] [--only-decode]
 
 Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
 events on the stream the work is enqueued on.  The frames the streams decode to are checked against the host statement first.
@@ -81,27 +87,44 @@ def size_leg(m, h, w, args):
         info = _lib.jpeg_parse(data)
         ent = torch.from_numpy(np.frombuffer(data, np.uint8)[info.data_offset:].copy()).cuda()
         decode = lambda: hnd.jpeg_decode_device(info, ent.data_ptr(), ent.numel(), s, True, status.data_ptr(), stream=stream)
-        iters = max(1, args.iters // 10) if info.intervals == 1 else args.iters
-        for _ in range(2):
-            decode()
-        sync()
         want = jpeg.decode_host(data)
-        r = {"intervals": info.intervals, "bytes_jpeg": len(data), "equals_host": bool(np.array_equal(dst.cpu().numpy(), want)),
-             "status": status.cpu().tolist()}
-        times, calls = [], []
-        for _ in range(args.rounds):                      # (i): events around `iters` decodes on the caller's stream
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            sync()
-            a.record()
-            t = time.perf_counter()
-            for _ in range(iters):
+        r = {"intervals": info.intervals, "bytes_jpeg": len(data), "equals_host": True, "decode_us": {}, "decode_call_host_us": {}, "forms": {}}
+        configs = []
+        for e in args.entropy:
+            configs += [(e, sb) for sb in args.seg_bytes] if e != 0 else [(0, args.seg_bytes[0])]
+        for entropy, seg_bytes in configs:
+            key = "interval" if entropy == 0 else ("seg" if entropy == 1 else "auto") + str(seg_bytes)
+            hnd.set_option("jpeg_entropy", entropy)
+            hnd.set_option("jpeg_seg_bytes", seg_bytes)
+            before = hnd.jpeg_decode_counters()
+            dst.zero_()
+            for _ in range(2):
                 decode()
-            calls.append((time.perf_counter() - t) * 1e6 / iters)
-            b.record()
             sync()
-            times.append(a.elapsed_time(b) * 1e3 / iters)
-        r["decode_us"] = round(statistics.median(times), 1)
-        r["decode_call_host_us"] = round(statistics.median(calls), 1)
+            after = hnd.jpeg_decode_counters()
+            r["forms"][key] = "segmented" if after["segmented"] > before["segmented"] else "interval"
+            serial = info.intervals == 1 and r["forms"][key] == "interval"      # one lane walks the whole picture: fewer repeats
+            iters = max(1, args.iters // 10) if serial else args.iters
+            r["equals_host"] = r["equals_host"] and bool(np.array_equal(dst.cpu().numpy(), want)) and status.cpu().tolist() == [0, -1]
+            times, calls = [], []
+            for _ in range(args.rounds):                  # (i): events around `iters` decodes on the caller's stream
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                sync()
+                a.record()
+                t = time.perf_counter()
+                for _ in range(iters):
+                    decode()
+                calls.append((time.perf_counter() - t) * 1e6 / iters)
+                b.record()
+                sync()
+                times.append(a.elapsed_time(b) * 1e3 / iters)
+            r["decode_us"][key] = round(statistics.median(times), 1)
+            r["decode_call_host_us"][key] = round(statistics.median(calls), 1)
+        hnd.set_option("jpeg_entropy", 2)
+        hnd.set_option("jpeg_seg_bytes", 128)
+        if args.only_decode:
+            res[name] = r
+            continue
 
         def pillow():                                     # (iii): the decode it replaces, one core
             im = Image.open(io.BytesIO(data))
@@ -117,6 +140,8 @@ def size_leg(m, h, w, args):
             n = max(1, iters // 2)
             r["begin_jpeg_us"] = round(median_us(lambda: [one_jpeg() for _ in range(n)], args.rounds, sync) / n, 1)
         res[name] = r
+    if args.only_decode:
+        return res
     with FramePipeline(m, depth=1) as fp:                 # (ii): the same frame as BGR pixels, the parent commit's path
         def one():
             fp.begin(frame)
@@ -135,10 +160,15 @@ def main():
     ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--entropy", type=int, nargs="+", default=[0, 1], choices=[0, 1, 2], help="forms of the entropy stage to time")
+    ap.add_argument("--seg-bytes", type=int, nargs="+", default=[128], help="segment sizes of the segmented form")
+    ap.add_argument("--lanes", type=int, default=0, choices=[0, 16, 32, 64], help="decoding lanes per wave of the segmented kernels")
+    ap.add_argument("--only-decode", action="store_true", help="rows (i) only")
     args = ap.parse_args()
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
     import whenet
     m = whenet.WHENet(dtype="f16")
+    m._handle.set_option("jpeg_seg_lanes", args.lanes)
     try:
         for size in args.sizes:
             h, w = (int(v) for v in size.split("x"))
