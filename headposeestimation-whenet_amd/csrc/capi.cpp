@@ -1159,6 +1159,58 @@ int whenet_frame_begin_jpeg(whenet_t* h, const uint8_t* data, int64_t size, int 
     return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status); });
 }
 
+// ---- clips of JPEG streams ----
+static_assert(WHENET_JPEG_CLIP_PLAN_FRAME_WORDS == whenet::JPEG_CLIP_PLAN_FRAME_WORDS &&
+                  WHENET_JPEG_CLIP_PLAN_TOTAL_WORDS == whenet::JPEG_CLIP_PLAN_TOTAL_WORDS,
+              "the header states the plan's words");
+int whenet_clip_begin_jpeg(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int* ticket,
+                           int32_t* status) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.clip_begin_jpeg(data, size, num_frames, channel_order, status); });
+}
+
+int whenet_op_jpeg_decode_clip(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, const whenet_surface_t* dst,
+                               int channel_order, int32_t* status, int entropy, int seg_bytes) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       "op_jpeg_decode_clip: entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_clip: seg_bytes must be a power of two in 4..4096");
+        e.op_jpeg_decode_clip(data, size, num_frames, dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0);
+    });
+}
+
+int whenet_jpeg_clip_plan(const whenet_jpeg_info_t* infos, const int64_t* nbytes, int num_frames, int entropy, int seg_bytes, int64_t* out) {
+    const char* bad = nullptr;
+    if (infos == nullptr || nbytes == nullptr || out == nullptr) bad = "NULL argument";
+    else if (num_frames < 1 || num_frames > whenet::JPEG_CLIP_MAX_FRAMES) bad = "a clip holds 1..16 frames";
+    whenet::JpegDecGeom g[whenet::JPEG_CLIP_MAX_FRAMES];
+    for (int f = 0; bad == nullptr && f < num_frames; ++f) {
+        if ((bad = whenet::jpeg_dec_check_info(infos[f])) != nullptr) {
+            g_create_error = "jpeg_clip_plan: frame " + std::to_string(f) + ": info: " + bad;
+            return WHENET_EINVAL;
+        }
+        g[f] = whenet::jpeg_dec_geom(infos[f]);
+    }
+    whenet::JpegClipPlan plan;
+    if (bad == nullptr) bad = whenet::jpeg_clip_plan(g, nbytes, num_frames, entropy, seg_bytes, plan);
+    if (bad != nullptr) {
+        g_create_error = std::string("jpeg_clip_plan: ") + bad;
+        return WHENET_EINVAL;
+    }
+    whenet::jpeg_clip_plan_words(plan, out);
+    return WHENET_OK;
+}
+
+int whenet_jpeg_clip_counters(whenet_t* h, int64_t out[4]) {
+    if (out == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        e.add_jpeg_clip_counters(out);
+        for (const whenet::Engine* r : h->replicas) r->add_jpeg_clip_counters(out);
+        for (const whenet::Engine* r : h->fan) r->add_jpeg_clip_counters(out);
+    });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

@@ -363,6 +363,18 @@ class Engine {
     void jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
                             int channel_order, int32_t* d_status, hipStream_t stream);
     int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status);
+    // A CLIP of 1..16 JPEG streams (frame f: data[f], size[f] bytes), each with its own size, sampling, tables, DRI and entropy
+    // form (the options are applied stream by stream): one plan (jpeg_dec_clip_host.h), ONE H2D of records | tables | entropy bytes,
+    // one memset and every stage in one launch for all frames (launch_jpeg_decode_clip).  Refusals -- a frame count outside 1..16, a
+    // NULL pointer or a size < 1, a stream the parser refuses (WHENET_EFORMAT), more sizes than letterbox_cache -- name the frame
+    // and come before a slot is taken.
+    // clip_begin_jpeg: the slot ends up as clip_begin (one size) or clip_begin_mixed (frames back to back) leaves it for the decoded
+    // frames; status [frames][2] comes back through pinned memory with the ticket's collect call.
+    // op_jpeg_decode_clip: the clip kernels alone, host to host, frame f into dst[f] at the caller's pitches between guard zones.
+    int clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status);
+    void op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
+                             int32_t* status, int entropy = -1, int seg_bytes = 0);
+    void add_jpeg_clip_counters(int64_t out[4]) const;      // clip decodes, their frames, their launches + memsets, their H2D copies
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
     void op_dconv(const float* in, int n, int H, int W, int cin, const float* in2, int cin2, const float* kernel, const float* bias, int k,
@@ -430,6 +442,7 @@ class Engine {
         DeviceBuffer jpg_dec;
         PinnedBuffer jpg_dec_status;
         int32_t* jpg_dec_out = nullptr;
+        int jpg_dec_pairs = 1;           // the status pairs jpg_dec_out takes: 1, or the frames of clip_begin_jpeg
         Results host() const { return {ypr.h.as<float>(), amax.h.as<int32_t>(), logits.h.as<float>()}; }
         Results dev() const { return {ypr.d.as<float>(), amax.d.as<int32_t>(), logits.d.as<float>()}; }
     };
@@ -587,6 +600,13 @@ class Engine {
     int jpeg_entropy_ = 2, jpeg_seg_bytes_ = JPEG_SEG_DEFAULT_BYTES;      // options "jpeg_entropy", "jpeg_seg_bytes"
     int jpeg_seg_lanes_ = 0;                                             // option "jpeg_seg_lanes" (a measurement knob; 0: the default)
     int64_t jpeg_dec_launched_[2] = {0, 0};                              // decodes launched in form 0, form 1
+    int64_t jpeg_clip_counts_[4] = {0, 0, 0, 0};                         // add_jpeg_clip_counters
+    struct JpegClipJob;      // the parsed headers, geometries and the plan of a clip (engine_post.cpp)
+    void jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes,
+                           JpegClipJob& job) const;
+    // records | tables | entropy bytes into `stage` (plan.upload_bytes), the records for a work buffer at d_base; recs: the same records
+    void jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,
+                         int channel_order, int32_t* d_status, JpegDecArgs* recs) const;
     // the layout of a decode's work buffers in the form the options (or `entropy` >= 0, `seg_bytes` > 0) give this stream
     JpegDecScratch jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy = -1, int seg_bytes = 0) const;
 

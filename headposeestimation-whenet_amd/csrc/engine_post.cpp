@@ -1279,7 +1279,7 @@ void Engine::finish_annotations(Slot& slot) {
     slot.jpg_host.clear();
     if (slot.jpg_dec_out != nullptr) {      // frame_begin_jpeg: the status words, written to pinned memory by the decode on the copy stream
         WHENET_HIP_CHECK(hipEventSynchronize(slot.copied));      // (a ticket collected without heads has waited for nothing yet)
-        std::memcpy(slot.jpg_dec_out, slot.jpg_dec_status.as<void>(), 2 * sizeof(int32_t));
+        std::memcpy(slot.jpg_dec_out, slot.jpg_dec_status.as<void>(), size_t(slot.jpg_dec_pairs) * 2 * sizeof(int32_t));
         slot.jpg_dec_out = nullptr;
     }
 }
@@ -1415,6 +1415,8 @@ void Engine::frame_annotate_jpeg(int ticket, int frame_index, int display, int q
 
 // ---- JPEG decoder (jpeg_dec.hip; the contract is in engine.h and include/whenet_hip.h) ----
 namespace {
+// a slot's pinned status words: a pair per frame of the largest clip
+constexpr size_t JPEG_STATUS_BYTES = size_t(MIXED_MAX_FRAMES) * 2 * sizeof(int32_t);
 // the header of a stream, or WHENET_EFORMAT with the parser's reason
 whenet_jpeg_info_t parse_or_refuse(const char* what, const uint8_t* data, int64_t size) {
     WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
@@ -1552,7 +1554,7 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     slot.frame.h.grow(std::max(fbytes, lay.upload_bytes));      // (>= the frame's bytes: the size every other user of the staging grows it to)
     slot.frame.d.grow(fbytes);
     slot.jpg_dec.grow(lay.bytes);
-    slot.jpg_dec_status.grow(16);
+    slot.jpg_dec_status.grow(JPEG_STATUS_BYTES);
     void* d_status = nullptr;                      // the pinned status words as the device addresses them
     WHENET_HIP_CHECK(hipHostGetDevicePointer(&d_status, slot.jpg_dec_status.as<void>(), 0));
     // tables | compressed bytes: the staging's front, one H2D
@@ -1572,8 +1574,185 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
     slot.fh = info.h, slot.fw = info.w, slot.swap_rb = channel_order == WHENET_BGR;
     slot.frame_ticket = finish_submission(slot, 0);
-    slot.jpg_dec_out = status;
+    slot.jpg_dec_out = status, slot.jpg_dec_pairs = 1;
     return slot.frame_ticket;
+}
+
+// ---- clips of JPEG streams (the contract is in engine.h) ----
+struct Engine::JpegClipJob {
+    int frames = 0;
+    std::vector<whenet_jpeg_info_t> info;
+    JpegDecGeom g[MIXED_MAX_FRAMES];
+    int64_t nbytes[MIXED_MAX_FRAMES];
+    JpegClipPlan plan;
+};
+
+void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes,
+                               JpegClipJob& job) const {
+    const std::string w(what);
+    WHENET_REQUIRE(nframes >= 1 && nframes <= MIXED_MAX_FRAMES, WHENET_EINVAL,
+                   w + ": " + std::to_string(nframes) + " frames: a clip holds 1..16 (the detector's batch limit)");
+    WHENET_REQUIRE(data != nullptr && size != nullptr, WHENET_EINVAL, w + ": NULL argument");
+    job.frames = nframes;
+    job.info.resize(size_t(nframes));
+    for (int f = 0; f < nframes; ++f) {
+        const std::string who = w + ": frame " + std::to_string(f);
+        job.info[f] = parse_or_refuse(who.c_str(), data[f], size[f]);
+        job.g[f] = jpeg_dec_geom(job.info[f]);
+        job.nbytes[f] = size[f] - job.info[f].data_offset;
+    }
+    const char* bad = jpeg_clip_plan(job.g, job.nbytes, nframes, entropy >= 0 ? entropy : jpeg_entropy_, seg_bytes > 0 ? seg_bytes : jpeg_seg_bytes_,
+                                     job.plan);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, w + ": " + (bad ? bad : ""));
+}
+
+void Engine::jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,
+                             int channel_order, int32_t* d_status, JpegDecArgs* recs) const {
+    const JpegClipPlan& p = job.plan;
+    char* const s = static_cast<char*>(d_base);
+    std::memset(stage + p.records.off, 0, p.records.len);
+    for (int f = 0; f < job.frames; ++f) {
+        const JpegClipFrame& q = p.f[f];
+        JpegDecArgs a{};
+        a.g = job.g[f];
+        a.tables = reinterpret_cast<const JpegDecTables*>(s + q.tables.off);
+        a.data = reinterpret_cast<const uint8_t*>(s + q.data.off), a.nbytes = int(job.nbytes[f]);
+        a.start = reinterpret_cast<int32_t*>(s + q.start.off), a.meta = reinterpret_cast<int32_t*>(s + q.meta.off);
+        a.coef = reinterpret_cast<int16_t*>(s + q.coef.off);
+        for (int c = 0; c < 3; ++c) {
+            a.plane[c] = reinterpret_cast<uint8_t*>(s + q.plane[c].off);
+            a.dst[c] = static_cast<uint8_t*>(dst[f].plane[c]), a.dst_pitch[c] = dst[f].pitch[c];
+        }
+        a.format = dst[f].format, a.channel_order = channel_order;
+        a.status = d_status + 2 * f;
+        a.form = q.form, a.seg_bytes = q.seg_bytes, a.seg_cap = int(q.seg_cap), a.seg_lanes = jpeg_seg_lanes_;
+        a.seg_stats = reinterpret_cast<long long*>(s + q.seg_stats.off);
+        a.first_seg = reinterpret_cast<int32_t*>(s + q.first_seg.off), a.seg_exit = reinterpret_cast<uint64_t*>(s + q.seg_exit.off);
+        a.seg_count = reinterpret_cast<JpegSegCount*>(s + q.seg_count.off), a.seg_blk = reinterpret_cast<int32_t*>(s + q.seg_blk.off);
+        recs[f] = a;
+        std::memcpy(stage + p.records.off + size_t(f) * JPEG_CLIP_RECORD_BYTES, &a, sizeof(a));
+        JpegDecTables* const t = reinterpret_cast<JpegDecTables*>(stage + q.tables.off);      // (256-byte aligned in pinned or vector memory)
+        jpeg_dec_build_tables(job.info[f], *t);
+        if (q.data.len > 0) std::memcpy(stage + q.data.off, data[f] + job.info[f].data_offset, q.data.len);
+    }
+}
+
+void Engine::add_jpeg_clip_counters(int64_t out[4]) const {
+    for (int i = 0; i < 4; ++i) out[i] += jpeg_clip_counts_[i];
+}
+
+int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "clip_begin_jpeg: NULL argument");
+    WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "clip_begin_jpeg: unknown channel order");
+    JpegClipJob job;
+    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, job);      // (before a slot is taken)
+    bool one_size = true;
+    for (int f = 1; f < nframes; ++f) one_size = one_size && job.info[f].h == job.info[0].h && job.info[f].w == job.info[0].w;
+    WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
+                   "clip_begin_jpeg: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    size_t off[MIXED_MAX_FRAMES + 1] = {};
+    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(job.info[f].h) * job.info[f].w * 3;
+    const JpegClipPlan& plan = job.plan;
+    slot.frame.h.grow(std::max(off[nframes], plan.upload_bytes));      // (>= the frames' bytes: the size every other user of the staging grows it to)
+    slot.frame.d.grow(off[nframes]);
+    slot.jpg_dec.grow(plan.bytes);
+    slot.jpg_dec_status.grow(JPEG_STATUS_BYTES);
+    void* d_status = nullptr;                      // the pinned status words as the device addresses them
+    WHENET_HIP_CHECK(hipHostGetDevicePointer(&d_status, slot.jpg_dec_status.as<void>(), 0));
+    whenet_surface_t dst[MIXED_MAX_FRAMES] = {};
+    for (int f = 0; f < nframes; ++f)
+        dst[f].plane[0] = slot.frame.d.as<uint8_t>() + off[f], dst[f].pitch[0] = 3 * job.info[f].w, dst[f].format = WHENET_SURF_PACKED, dst[f].on_device = 1;
+    JpegDecArgs recs[MIXED_MAX_FRAMES];
+    uint8_t* const stage = slot.frame.h.as<uint8_t>();
+    jpeg_clip_stage(job, data, stage, slot.jpg_dec.as<void>(), dst, channel_order, static_cast<int32_t*>(d_status), recs);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, plan.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
+    launch_jpeg_decode_clip(recs, slot.jpg_dec.as<char>() + plan.records.off, nframes, slot.jpg_dec.as<char>() + plan.zero.off, plan.zero.len,
+                            copy_stream(), &jpeg_clip_counts_[2]);
+    ++jpeg_clip_counts_[0], jpeg_clip_counts_[1] += nframes, ++jpeg_clip_counts_[3];
+    for (int f = 0; f < nframes; ++f) ++jpeg_dec_launched_[plan.f[f].form];
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = job.info[0].h, slot.fw = job.info[0].w, slot.swap_rb = channel_order == WHENET_BGR;
+    if (!one_size) {
+        for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = job.info[f].h, slot.clip_fw[f] = job.info[f].w;
+        std::copy(off, off + nframes + 1, slot.clip_off);
+    }
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = nframes;
+    slot.clip_mixed = !one_size;
+    slot.jpg_dec_out = status, slot.jpg_dec_pairs = nframes;
+    return slot.frame_ticket;
+}
+
+void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
+                                 int32_t* status, int entropy, int seg_bytes) {
+    DeviceGuard guard(device_);
+    WHENET_REQUIRE(status != nullptr && dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_clip: NULL argument");
+    JpegClipJob job;
+    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, job);
+    // every plane of every destination on the device at the caller's pitch and at the caller's address modulo 16, between two guard
+    // zones and over a sentinel, so that a store outside the rows' bytes -- into a neighbouring frame as well -- is seen
+    struct Plane {
+        size_t off;
+        int rows, row_bytes, pitch;
+        uint8_t* host;
+    };
+    std::vector<Plane> planes;
+    whenet_surface_t d_dst[MIXED_MAX_FRAMES];
+    size_t total = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const std::string who = "op_jpeg_decode_clip: frame " + std::to_string(f);
+        const char* bad = jpeg_dec_check_dst(job.info[f], &dst[f], channel_order);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, who + ": " + (bad ? bad : ""));
+        WHENET_REQUIRE(dst[f].on_device == 0, WHENET_EINVAL, who + ": the surface must be host memory (on_device = 0)");
+        check_surface(who.c_str(), dst[f], job.info[f].h, job.info[f].w);
+        int rows[3], row_bytes[3];
+        const int np = overlay_surface_planes(dst[f].format, job.info[f].h, job.info[f].w, rows, row_bytes);
+        d_dst[f] = dst[f];
+        for (int p = 0; p < np; ++p) {
+            const size_t at = ((total + 15) & ~size_t(15)) + (reinterpret_cast<uintptr_t>(dst[f].plane[p]) & 15);
+            total = at + size_t(rows[p] - 1) * size_t(dst[f].pitch[p]) + size_t(row_bytes[p]);
+            planes.push_back({at, rows[p], row_bytes[p], dst[f].pitch[p], static_cast<uint8_t*>(dst[f].plane[p])});
+        }
+    }
+    const JpegClipPlan& plan = job.plan;
+    TempBufs tmp;
+    char* const d_work = static_cast<char*>(tmp.get(plan.bytes));
+    int32_t* const d_status = static_cast<int32_t*>(tmp.get(size_t(nframes) * 2 * sizeof(int32_t)));
+    const GuardedOutput d_out(total, stream_);
+    {
+        size_t k = 0;
+        for (int f = 0; f < nframes; ++f) {
+            int rows[3], row_bytes[3];
+            const int np = overlay_surface_planes(dst[f].format, job.info[f].h, job.info[f].w, rows, row_bytes);
+            for (int p = 0; p < np; ++p) d_dst[f].plane[p] = d_out.frames() + planes[k++].off;
+        }
+    }
+    std::vector<uint8_t> stage(plan.upload_bytes + 256);
+    uint8_t* const st = stage.data() + ((256 - (reinterpret_cast<uintptr_t>(stage.data()) & 255)) & 255);
+    JpegDecArgs recs[MIXED_MAX_FRAMES];
+    jpeg_clip_stage(job, data, st, d_work, d_dst, channel_order, d_status, recs);
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_work, st, plan.upload_bytes, hipMemcpyHostToDevice, stream_));
+    launch_jpeg_decode_clip(recs, d_work + plan.records.off, nframes, d_work + plan.zero.off, plan.zero.len, stream_, &jpeg_clip_counts_[2]);
+    ++jpeg_clip_counts_[0], jpeg_clip_counts_[1] += nframes, ++jpeg_clip_counts_[3];
+    for (int f = 0; f < nframes; ++f) ++jpeg_dec_launched_[plan.f[f].form];
+    const size_t none[1] = {0};
+    d_out.to_host(stream_, none, 0, nullptr, "op_jpeg_decode_clip");      // waits, checks the guard zones
+    std::vector<uint8_t> back(total), is_row(total, 0);
+    WHENET_HIP_CHECK(hipMemcpy(back.data(), d_out.frames(), total, hipMemcpyDeviceToHost));
+    for (const Plane& pl : planes)
+        for (int r = 0; r < pl.rows; ++r) {
+            const size_t at = pl.off + size_t(r) * size_t(pl.pitch);
+            std::memset(is_row.data() + at, 1, size_t(pl.row_bytes));
+            std::memcpy(pl.host + size_t(r) * size_t(pl.pitch), back.data() + at, size_t(pl.row_bytes));
+        }
+    for (size_t i = 0; i < total; ++i)
+        WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
+                       "op_jpeg_decode_clip: the kernel wrote outside the rows of the surfaces (byte " + std::to_string(i) + ")");
+    WHENET_HIP_CHECK(hipMemcpy(status, d_status, size_t(nframes) * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
 }
 
 }  // namespace whenet

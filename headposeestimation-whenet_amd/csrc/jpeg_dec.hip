@@ -62,7 +62,10 @@ __device__ inline int block_exclusive_scan(int v, int* s_wave, int& total) {
     return base + inc - v;
 }
 
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_scan_kernel(JpegDecArgs a) {
+// ---- the bodies: what a workgroup does for ONE stream, given that stream's record and the workgroup's index within the stream's
+// share of the grid (bx).  The single-stream kernels call them with their own argument and blockIdx.x, the clip kernels with the
+// record of the frame the workgroup belongs to.
+__device__ __forceinline__ void scan_body(const JpegDecArgs& a) {
     __shared__ int s_wave[WAVES];
     __shared__ int s_bad;
     const int tid = int(threadIdx.x), N = a.g.intervals;
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_scan_kernel(JpegDecAr
     }
 }
 
-__global__ __launch_bounds__(ENT_THREADS) void whenet_jpeg_dec_entropy_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void entropy_body(const JpegDecArgs& a, int bx) {
     __shared__ JpegDecTables s_t;
     __shared__ __attribute__((aligned(16))) int16_t s_block[ENT_LANES][64 + 8];      // a lane's block in hand (144-byte rows)
     const int tid = int(threadIdx.x);
@@ -122,15 +125,15 @@ __global__ __launch_bounds__(ENT_THREADS) void whenet_jpeg_dec_entropy_kernel(Jp
         for (int i = tid; i < int(sizeof(JpegDecTables) / 4); i += ENT_THREADS) dst[i] = src[i];
     }
     __syncthreads();
-    const long long i = (long long)(blockIdx.x) * ENT_LANES + tid;
+    const long long i = (long long)(bx) * ENT_LANES + tid;
     if (tid >= ENT_LANES || i >= a.g.intervals || i > a.meta[0]) return;
     if (!jpeg_dec_interval(a.data, a.nbytes, a.start[i], s_t, a.g, int(i), a.coef, 0, s_block[tid])) atomicMin(&a.meta[1], int(i));
 }
 
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void idct_body(const JpegDecArgs& a, int bx) {
     __shared__ int s_r[IDCT_BLOCKS][8][9];
     const int tid = int(threadIdx.x), lb = tid >> 3, l = tid & 7;
-    const long long g = (long long)(blockIdx.x) * IDCT_BLOCKS + lb;
+    const long long g = (long long)(bx) * IDCT_BLOCKS + lb;
     const long long total = (long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm;
     const bool live = g < total;
     if (live) {
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecAr
         for (int y = 0; y < 8; ++y) s_r[lb][y][l] = jpeg_idct_round(o[y]);
     }
     __syncthreads();
-    if (blockIdx.x == 0 && tid == 0) {      // (the entropy kernel has ended: a kernel boundary lies between)
+    if (bx == 0 && tid == 0) {      // (the entropy kernel has ended: a kernel boundary lies between)
         const int bad = a.meta[1];
         a.status[0] = bad == JPEG_DEC_NO_BAD ? WHENET_OK : WHENET_EFORMAT;
         a.status[1] = bad == JPEG_DEC_NO_BAD ? -1 : bad;
@@ -167,9 +170,9 @@ __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int shift_b
     return uint32_t(((uint64_t(hi) << 32) | lo) >> shift_bits);
 }
 
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
     const int h = a.g.h, w = a.g.w, gw = (w + 3) >> 2;
-    const long long item = (long long)(blockIdx.x) * THREADS + threadIdx.x;
+    const long long item = (long long)(bx) * THREADS + threadIdx.x;
     const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
     if (y >= h) return;
     const int x = gx << 2;
@@ -235,9 +238,9 @@ __device__ __forceinline__ void store_bytes(uint8_t* dp, uint32_t word, int n) {
 }
 
 // items: the luma plane's 4-byte groups row by row, then the chroma rows' groups of 4 samples (U and V of a group by one lane)
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void yuv_body(const JpegDecArgs& a, int bx) {
     const int h = a.g.h, w = a.g.w, ch = (h + 1) >> 1, cw = (w + 1) >> 1, gw = (w + 3) >> 2, cgw = (cw + 3) >> 2;
-    long long item = (long long)(blockIdx.x) * THREADS + threadIdx.x;
+    long long item = (long long)(bx) * THREADS + threadIdx.x;
     const long long luma_items = (long long)(h) * gw;
     if (item < luma_items) {
         const int y = int(item / gw), x = int(item - (long long)(y) * gw) << 2;
@@ -261,6 +264,76 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArg
         store_bytes(dp, lo, min(4, 2 * n));
         if (n > 2) store_bytes(dp + 4, hi, 2 * n - 4);
     }
+}
+
+// ---- the single-stream kernels: the record by value, the grid that stream's ----
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_scan_kernel(JpegDecArgs a) { scan_body(a); }
+__global__ __launch_bounds__(ENT_THREADS) void whenet_jpeg_dec_entropy_kernel(JpegDecArgs a) { entropy_body(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecArgs a) { idct_body(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_kernel(JpegDecArgs a) { frame_body(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArgs a) { yuv_body(a, int(blockIdx.x)); }
+
+// ---- the clip kernels: up to 16 records in device memory (recs), the frames' workgroups back to back in one grid.  A workgroup
+// finds its frame (kernels.h, jpeg_clip_frame_of: wave-uniform), copies that frame's record -- the address is the same for every
+// lane and the memory is read-only for the kernel: scalar loads -- and runs the body with its index inside the frame's share.  A
+// workgroup never straddles two frames (the LDS tables of the entropy body are one frame's): a frame's last workgroup has idle
+// lanes instead.  A workgroup behind the grid's total exits before it touches memory.
+// The record is read where it lies (a reference, not a copy: a copy whose address the non-inlined decode functions take went to
+// 296 bytes of scratch per lane).  Resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), VGPRs of
+// the clip form / of the single-stream form, no scratch in either, the same LDS: scan 44 / 44, entropy 47 / 48, idct 47 / 47,
+// frame 18 / 18, yuv 14 / 14; SGPRs grow by up to 21 (the prefix sums and the record's address).
+#define WHENET_JPEG_CLIP_KERNEL(name, threads, call)                                                                       \
+    __global__ __launch_bounds__(threads) void name(const void* __restrict__ recs, JpegClipGrid grid) {                    \
+        const int b = int(blockIdx.x);                                                                                     \
+        if (b >= grid.total) return;                                                                                       \
+        const int f = jpeg_clip_frame_of(grid, b);                                                                         \
+        const JpegDecArgs& a = jpeg_clip_record(recs, f);                                                                  \
+        const int bx = b - grid.first[f];                                                                                  \
+        (void)bx;                                                                                                          \
+        call;                                                                                                              \
+    }
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_scan_kernel, THREADS, scan_body(a))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_entropy_kernel, ENT_THREADS, entropy_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_idct_kernel, THREADS, idct_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_kernel, THREADS, frame_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_yuv_kernel, THREADS, yuv_body(a, bx))
+#undef WHENET_JPEG_CLIP_KERNEL
+
+static_assert(sizeof(JpegDecArgs) <= JPEG_CLIP_RECORD_BYTES && JPEG_CLIP_RECORD_BYTES % 16 == 0, "a record fits its stride");
+
+// everything launch_jpeg_decode asks of one stream's record, the layout apart
+void check_jpeg_dec_args(const JpegDecArgs& a) {
+    const JpegDecGeom& g = a.g;
+    int rows[3], row_bytes[3];
+    const int planes = overlay_surface_planes(a.format, g.h, g.w, rows, row_bytes);
+    WHENET_REQUIRE(planes > 0 && g.h >= 1 && g.w >= 1 && g.h <= JPEG_MAX_SIDE && g.w <= JPEG_MAX_SIDE && (g.comps == 1 || g.comps == 3) &&
+                       (g.hs == 1 || g.hs == 2) && (g.vs == 1 || g.vs == 2) && g.bpm == (g.comps == 3 ? g.hs * g.vs + 2 : 1) &&
+                       g.mcu_cols == (g.w + 8 * g.hs - 1) / (8 * g.hs) && g.mcu_rows == (g.h + 8 * g.vs - 1) / (8 * g.vs) && g.ri >= 1 &&
+                       (long long)(g.intervals) == ((long long)(g.mcu_cols) * g.mcu_rows + g.ri - 1) / g.ri,
+                   WHENET_EINVAL, "jpeg_decode: bad geometry");
+    WHENET_REQUIRE(a.tables != nullptr && a.data != nullptr && a.nbytes >= 0 && a.start != nullptr && a.meta != nullptr && a.coef != nullptr &&
+                       a.status != nullptr && (a.format == WHENET_SURF_PACKED || (g.comps == 3 && g.hs == 2 && g.vs == 2)),
+                   WHENET_EINVAL, "jpeg_decode: bad arguments");
+    for (int c = 0; c < g.comps; ++c)
+        WHENET_REQUIRE(a.plane[c] != nullptr && reinterpret_cast<uintptr_t>(a.plane[c]) % 8 == 0 && g.plane_pitch[c] % 8 == 0 &&
+                           g.plane_pitch[c] >= (c == 0 ? g.w : (g.w + g.hs - 1) / g.hs) && g.plane_rows[c] >= (c == 0 ? g.h : (g.h + g.vs - 1) / g.vs),
+                       WHENET_EINVAL, "jpeg_decode: bad component plane " + std::to_string(c));
+    for (int p = 0; p < planes; ++p)
+        WHENET_REQUIRE(a.dst[p] != nullptr && a.dst_pitch[p] >= row_bytes[p], WHENET_EINVAL, "jpeg_decode: bad destination plane " + std::to_string(p));
+    WHENET_REQUIRE(a.format != WHENET_SURF_PACKED || a.channel_order == WHENET_RGB || a.channel_order == WHENET_BGR, WHENET_EINVAL,
+                   "jpeg_decode: unknown channel order");
+    WHENET_REQUIRE(a.form == 0 || a.form == 1, WHENET_EINVAL, "jpeg_decode: the entropy form must be 0 or 1");
+    if (a.form == 1)
+        WHENET_REQUIRE(jpeg_seg_bytes_ok(a.seg_bytes) && (long long)(a.seg_cap) == jpeg_seg_bound(a.nbytes, g.intervals, a.seg_bytes) &&
+                           a.seg_stats != nullptr && a.first_seg != nullptr && a.seg_exit != nullptr && a.seg_count != nullptr && a.seg_blk != nullptr,
+                       WHENET_EINVAL, "jpeg_decode: the work buffers are not those of the segmented form of this stream");
+}
+
+// the colour path of a stream: 0 the plane kernel of the YUV ingest (a tight BGR frame of a 4:2:0 stream), 1 the frame kernel, 2 the
+// I420 / NV12 copy
+int colour_path(const JpegDecArgs& a) {
+    if (a.format != WHENET_SURF_PACKED) return 2;
+    return a.g.comps == 3 && a.g.hs == 2 && a.g.vs == 2 && a.channel_order == WHENET_BGR && a.dst_pitch[0] == 3 * a.g.w ? 0 : 1;
 }
 
 }  // namespace
@@ -319,24 +392,7 @@ JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecSc
 
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream) {
     const JpegDecGeom& g = a.g;
-    int rows[3], row_bytes[3];
-    const int planes = overlay_surface_planes(a.format, g.h, g.w, rows, row_bytes);
-    WHENET_REQUIRE(planes > 0 && g.h >= 1 && g.w >= 1 && g.h <= JPEG_MAX_SIDE && g.w <= JPEG_MAX_SIDE && (g.comps == 1 || g.comps == 3) &&
-                       (g.hs == 1 || g.hs == 2) && (g.vs == 1 || g.vs == 2) && g.bpm == (g.comps == 3 ? g.hs * g.vs + 2 : 1) &&
-                       g.mcu_cols == (g.w + 8 * g.hs - 1) / (8 * g.hs) && g.mcu_rows == (g.h + 8 * g.vs - 1) / (8 * g.vs) && g.ri >= 1 &&
-                       (long long)(g.intervals) == ((long long)(g.mcu_cols) * g.mcu_rows + g.ri - 1) / g.ri,
-                   WHENET_EINVAL, "jpeg_decode: bad geometry");
-    WHENET_REQUIRE(a.tables != nullptr && a.data != nullptr && a.nbytes >= 0 && a.start != nullptr && a.meta != nullptr && a.coef != nullptr &&
-                       a.status != nullptr && (a.format == WHENET_SURF_PACKED || (g.comps == 3 && g.hs == 2 && g.vs == 2)),
-                   WHENET_EINVAL, "jpeg_decode: bad arguments");
-    for (int c = 0; c < g.comps; ++c)
-        WHENET_REQUIRE(a.plane[c] != nullptr && reinterpret_cast<uintptr_t>(a.plane[c]) % 8 == 0 && g.plane_pitch[c] % 8 == 0 &&
-                           g.plane_pitch[c] >= (c == 0 ? g.w : (g.w + g.hs - 1) / g.hs) && g.plane_rows[c] >= (c == 0 ? g.h : (g.h + g.vs - 1) / g.vs),
-                       WHENET_EINVAL, "jpeg_decode: bad component plane " + std::to_string(c));
-    for (int p = 0; p < planes; ++p)
-        WHENET_REQUIRE(a.dst[p] != nullptr && a.dst_pitch[p] >= row_bytes[p], WHENET_EINVAL, "jpeg_decode: bad destination plane " + std::to_string(p));
-    WHENET_REQUIRE(a.format != WHENET_SURF_PACKED || a.channel_order == WHENET_RGB || a.channel_order == WHENET_BGR, WHENET_EINVAL,
-                   "jpeg_decode: unknown channel order");
+    check_jpeg_dec_args(a);
     WHENET_REQUIRE(lay.coef_bytes == size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm) * 128, WHENET_EINVAL,
                    "jpeg_decode: the work buffers are not those of the stream's geometry");
     // start | meta (contiguous) and the coefficient records start from zero
@@ -377,6 +433,64 @@ void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStre
         hipLaunchKernelGGL(whenet_jpeg_dec_yuv_kernel, dim3(unsigned((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a);
     }
     WHENET_HIP_CHECK(hipGetLastError());
+}
+
+void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, void* d_zero, size_t zero_bytes, hipStream_t stream,
+                             int64_t* enqueues) {
+    WHENET_REQUIRE(h_recs != nullptr && d_recs != nullptr && d_zero != nullptr && frames >= 1 && frames <= MIXED_MAX_FRAMES, WHENET_EINVAL,
+                   "jpeg_decode_clip: NULL argument, or a frame count outside 1..16");
+    for (int f = 0; f < frames; ++f) {
+        const JpegDecArgs& a = h_recs[f];
+        check_jpeg_dec_args(a);
+        // what the one memset must cover: the frame's start | meta | seg_stats and its coefficient records
+        const char *z0 = static_cast<const char*>(d_zero), *z1 = z0 + zero_bytes;
+        const size_t coef_bytes = size_t(a.g.mcu_cols) * size_t(a.g.mcu_rows) * size_t(a.g.bpm) * 128;
+        const auto zeroed = [&](const void* p, size_t n) { return static_cast<const char*>(p) >= z0 && static_cast<const char*>(p) + n <= z1; };
+        WHENET_REQUIRE(zeroed(a.start, size_t(a.g.intervals) * 4) && zeroed(a.meta, 8) && zeroed(a.seg_stats, 64) && zeroed(a.coef, coef_bytes),
+                       WHENET_EINVAL, "jpeg_decode_clip: frame " + std::to_string(f) + ": its zeroed regions lie outside the clip's");
+    }
+    int64_t n = 0;
+    JpegClipGrid grid;
+    const auto launch = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(unsigned(grid.total)), dim3(unsigned(threads)), 0, stream, d_recs, grid);
+        WHENET_HIP_CHECK(hipGetLastError());
+        ++n;
+    };
+    WHENET_HIP_CHECK(hipMemsetAsync(d_zero, 0, zero_bytes, stream));
+    ++n;
+    jpeg_clip_grid(h_recs, frames, [](const JpegDecArgs&) { return 1; }, grid);
+    launch(whenet_jpeg_dec_clip_scan_kernel, THREADS);
+    if (jpeg_clip_grid(h_recs, frames, [](const JpegDecArgs& a) { return a.form == 0 ? (a.g.intervals + ENT_LANES - 1) / ENT_LANES : 0; }, grid))
+        launch(whenet_jpeg_dec_clip_entropy_kernel, ENT_THREADS);
+    launch_jpeg_decode_segmented_clip(h_recs, d_recs, frames, stream, &n);
+    jpeg_clip_grid(h_recs, frames,
+              [](const JpegDecArgs& a) { return ((long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm + IDCT_BLOCKS - 1) / IDCT_BLOCKS; }, grid);
+    launch(whenet_jpeg_dec_clip_idct_kernel, THREADS);
+    // the colour stage: each of the three paths once, for the frames that take it
+    YuvPlanes tight{};
+    uintptr_t base = ~uintptr_t(0);
+    for (int f = 0; f < frames; ++f)
+        if (colour_path(h_recs[f]) == 0) base = std::min(base, reinterpret_cast<uintptr_t>(h_recs[f].dst[0]));
+    for (int f = 0; f < frames; ++f) {
+        const JpegDecArgs& a = h_recs[f];
+        if (colour_path(a) != 0) continue;
+        YuvPlanesFrame& y = tight.f[tight.frames++];
+        for (int c = 0; c < 3; ++c) y.plane[c] = a.plane[c], y.pitch[c] = a.g.plane_pitch[c];
+        y.h = a.g.h, y.w = a.g.w, y.format = WHENET_YUV_I420, y.k = yuv_coeffs(WHENET_YUV_JFIF);
+        y.dst_off = reinterpret_cast<uintptr_t>(a.dst[0]) - base;
+    }
+    if (tight.frames > 0) launch_yuv_planes_to_bgr(reinterpret_cast<uint8_t*>(base), tight, stream), ++n;
+    if (jpeg_clip_grid(h_recs, frames,
+                  [](const JpegDecArgs& a) { return colour_path(a) == 1 ? ((long long)(a.g.h) * ((a.g.w + 3) >> 2) + THREADS - 1) / THREADS : 0; }, grid))
+        launch(whenet_jpeg_dec_clip_frame_kernel, THREADS);
+    if (jpeg_clip_grid(h_recs, frames,
+                  [](const JpegDecArgs& a) {
+                      const long long items = (long long)(a.g.h) * ((a.g.w + 3) >> 2) + (long long)((a.g.h + 1) >> 1) * ((((a.g.w + 1) >> 1) + 3) >> 2);
+                      return colour_path(a) == 2 ? (items + THREADS - 1) / THREADS : 0;
+                  },
+                  grid))
+        launch(whenet_jpeg_dec_clip_yuv_kernel, THREADS);
+    if (enqueues != nullptr) *enqueues += n;
 }
 
 }  // namespace whenet

@@ -1,0 +1,114 @@
+// A clip of JPEG streams: where every frame's share of the upload block and of the work buffer lies, and in which entropy form it
+// runs.  One plan serves the engine (clip_begin_jpeg, op_jpeg_decode_clip) and whenet_jpeg_clip_plan, so the layout the kernels of
+// jpeg_dec.hip / jpeg_dec_seg.hip get is the one the CPU tests see.  Nothing here needs the HIP runtime: a plain C++17 compiler
+// builds this header (tools/jpeg_dec_clip_host_check.cpp does, under the host sanitizers).
+//
+// Reference: demo_video.py:49-53 (`cap.read()` in a loop: consecutive frames of one MJPG file).
+//
+// One allocation, offsets in bytes, every region at a multiple of 256 (the kernels need 8 for the planes and 16 for vector loads):
+//   upload block   records [frames] of JPEG_CLIP_RECORD_BYTES | per frame: tables | entropy data        -- ONE H2D
+//   zeroed bytes   per frame: start [intervals] | meta (64) | seg_stats (64); then per frame: coef        -- ONE memset
+//   work           per frame: the component planes; per frame of form 1: first_seg | seg_exit | seg_count | seg_blk
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "jpeg_dec_seg_host.h"
+
+namespace whenet {
+
+constexpr int JPEG_CLIP_MAX_FRAMES = 16;
+constexpr int JPEG_CLIP_RECORD_BYTES = 512;      // the stride of the argument records (>= sizeof(JpegDecArgs), checked in jpeg_dec.hip)
+constexpr int JPEG_CLIP_PLAN_FRAME_WORDS = 32;   // whenet_jpeg_clip_plan: int64 words per frame ...
+constexpr int JPEG_CLIP_PLAN_TOTAL_WORDS = 8;    // ... and behind the last frame
+
+struct JpegClipRegion {
+    size_t off, len;
+};
+struct JpegClipFrame {
+    int form, seg_bytes;      // seg_bytes: 0 in form 0
+    int64_t seg_cap;          // 0 in form 0
+    // in the order whenet_jpeg_clip_plan writes them
+    JpegClipRegion tables, data, start, meta, seg_stats, coef, plane[3], first_seg, seg_exit, seg_count, seg_blk;
+};
+struct JpegClipPlan {
+    int frames, forms[2];     // forms[k]: the frames of form k
+    JpegClipFrame f[JPEG_CLIP_MAX_FRAMES];
+    JpegClipRegion records, zero;
+    size_t upload_bytes, bytes;
+};
+
+// entropy: 0, 1 or 2 (auto), applied to every stream alone; seg_bytes: a power of two in 4..4096.  nullptr, or what is wrong.
+inline const char* jpeg_clip_plan(const JpegDecGeom* g, const int64_t* nbytes, int frames, int entropy, int seg_bytes, JpegClipPlan& p) {
+    if (g == nullptr || nbytes == nullptr) return "NULL argument";
+    if (frames < 1 || frames > JPEG_CLIP_MAX_FRAMES) return "a clip holds 1..16 frames";
+    if (entropy < 0 || entropy > 2) return "entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto)";
+    if (!jpeg_seg_bytes_ok(seg_bytes)) return "seg_bytes must be a power of two in 4..4096";
+    for (int f = 0; f < frames; ++f) {
+        if (nbytes[f] < 0 || nbytes[f] > JPEG_DEC_MAX_BYTES) return "nbytes must be 0..2^31 - 1";
+        if (g[f].intervals < 1 || g[f].mcu_cols < 1 || g[f].mcu_rows < 1 || g[f].bpm < 1 || g[f].comps < 1 || g[f].comps > 3) return "bad geometry";
+    }
+    const auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    p = JpegClipPlan{};
+    p.frames = frames;
+    size_t at = 0;
+    const auto take = [&](JpegClipRegion& r, size_t len) { r.off = at, r.len = len, at = up(at + len); };
+    take(p.records, size_t(frames) * JPEG_CLIP_RECORD_BYTES);
+    for (int f = 0; f < frames; ++f) {
+        JpegClipFrame& q = p.f[f];
+        q.form = jpeg_dec_form(entropy, nbytes[f], g[f].intervals);
+        q.seg_bytes = q.form == 1 ? seg_bytes : 0;
+        q.seg_cap = q.form == 1 ? jpeg_seg_bound(nbytes[f], g[f].intervals, seg_bytes) : 0;
+        if (q.seg_cap >= 0x7FFFFFFF) return "more segments than an int32 counts";
+        ++p.forms[q.form];
+        take(q.tables, sizeof(JpegDecTables));
+        take(q.data, size_t(nbytes[f]));
+    }
+    p.upload_bytes = at;
+    p.zero.off = at;
+    for (int f = 0; f < frames; ++f) {
+        JpegClipFrame& q = p.f[f];
+        take(q.start, size_t(g[f].intervals) * sizeof(int32_t));
+        q.meta = {at, 64}, q.seg_stats = {at + 64, 8 * sizeof(int64_t)}, at = up(at + 128);
+    }
+    for (int f = 0; f < frames; ++f)
+        take(p.f[f].coef, size_t(g[f].mcu_cols) * size_t(g[f].mcu_rows) * size_t(g[f].bpm) * 64 * sizeof(int16_t));
+    p.zero.len = at - p.zero.off;
+    for (int f = 0; f < frames; ++f)
+        for (int c = 0; c < 3; ++c) {
+            if (c < g[f].comps) take(p.f[f].plane[c], size_t(g[f].plane_pitch[c]) * size_t(g[f].plane_rows[c]));
+            else p.f[f].plane[c] = {at, 0};
+        }
+    for (int f = 0; f < frames; ++f) {
+        JpegClipFrame& q = p.f[f];
+        if (q.form == 1) {
+            take(q.first_seg, (size_t(g[f].intervals) + 1) * sizeof(int32_t));
+            take(q.seg_exit, size_t(q.seg_cap) * sizeof(uint64_t));
+            take(q.seg_count, size_t(q.seg_cap) * sizeof(JpegSegCount));
+            take(q.seg_blk, size_t(q.seg_cap) * 4 * sizeof(int32_t));
+        } else {
+            q.first_seg = q.seg_exit = q.seg_count = q.seg_blk = {at, 0};
+        }
+    }
+    p.bytes = at;
+    return nullptr;
+}
+
+// the plan as whenet_jpeg_clip_plan hands it out: frames * 32 + 8 words
+inline void jpeg_clip_plan_words(const JpegClipPlan& p, int64_t* out) {
+    for (int f = 0; f < p.frames; ++f) {
+        const JpegClipFrame& q = p.f[f];
+        int64_t* o = out + size_t(f) * JPEG_CLIP_PLAN_FRAME_WORDS;
+        o[0] = q.form, o[1] = q.seg_bytes, o[2] = q.seg_cap, o[3] = 0;
+        const JpegClipRegion* r[13] = {&q.tables,   &q.data,     &q.start,     &q.meta,     &q.seg_stats, &q.coef,   &q.plane[0],
+                                       &q.plane[1], &q.plane[2], &q.first_seg, &q.seg_exit, &q.seg_count, &q.seg_blk};
+        for (int k = 0; k < 13; ++k) o[4 + 2 * k] = int64_t(r[k]->off), o[5 + 2 * k] = int64_t(r[k]->len);
+        o[30] = o[31] = 0;
+    }
+    int64_t* t = out + size_t(p.frames) * JPEG_CLIP_PLAN_FRAME_WORDS;
+    t[0] = int64_t(p.records.off), t[1] = int64_t(p.records.len), t[2] = int64_t(p.upload_bytes), t[3] = int64_t(p.zero.off);
+    t[4] = int64_t(p.zero.len), t[5] = int64_t(p.bytes), t[6] = p.forms[0], t[7] = p.forms[1];
+}
+
+}  // namespace whenet

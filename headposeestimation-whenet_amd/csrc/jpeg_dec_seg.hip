@@ -44,7 +44,8 @@ __device__ inline void load_tables(JpegDecTables& s_t, const JpegDecTables* tabl
 // the intervals the form decodes: those up to the first one the markers make bad
 __device__ inline int decoded_intervals(const JpegDecArgs& a) { return min(a.meta[0], a.g.intervals - 1) + 1; }
 
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_segtab_kernel(JpegDecArgs a) {
+// ---- the bodies (as in jpeg_dec.hip): one stream's record, bx = the workgroup's index within that stream's share of the grid ----
+__device__ __forceinline__ void segtab_body(const JpegDecArgs& a) {
     __shared__ int s_wave[WAVES];
     const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6, N = a.g.intervals, nd = decoded_intervals(a);
     long long carry = 0;
@@ -81,11 +82,11 @@ __device__ inline void stat_max(long long* p, long long v) { atomicMax(reinterpr
 
 // L decoding lanes per wave: the workgroup has WINDOW / L waves
 template <int L>
-__global__ __launch_bounds__(WINDOW * 64 / L) void whenet_jpeg_dec_sync_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void sync_body(const JpegDecArgs& a, int bx) {
     __shared__ JpegDecTables s_t;
     __shared__ uint64_t s_exit[WINDOW];
     const int tid = int(threadIdx.x), lane = tid & 63, j = (tid >> 6) * L + lane;
-    const int S = a.first_seg[a.g.intervals], base = int(blockIdx.x) * WINDOW;
+    const int S = a.first_seg[a.g.intervals], base = bx * WINDOW;
     if (base >= S) return;      // (the whole workgroup)
     load_tables(s_t, a.tables);
     const int n = min(WINDOW, S - base);
@@ -126,10 +127,10 @@ __global__ __launch_bounds__(WINDOW * 64 / L) void whenet_jpeg_dec_sync_kernel(J
     if (tid == 0) stat_max(&a.seg_stats[3], rounds);
 }
 
-__global__ __launch_bounds__(64) void whenet_jpeg_dec_stitch_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void stitch_body(const JpegDecArgs& a, int bx) {
     __shared__ JpegDecTables s_t;
     load_tables(s_t, a.tables);
-    const long long i = (long long)(blockIdx.x) * 64 + threadIdx.x;
+    const long long i = (long long)(bx) * 64 + threadIdx.x;
     if (i >= decoded_intervals(a)) return;
     const int s0 = a.first_seg[i], s1 = a.first_seg[i + 1];
     long long walked = 0, bytes = 0;
@@ -148,9 +149,9 @@ __global__ __launch_bounds__(64) void whenet_jpeg_dec_stitch_kernel(JpegDecArgs 
 
 // the segment of a lane of the count and write kernels (L decoding lanes per wave), or -1
 template <int L>
-__device__ inline int lane_segment(const JpegDecArgs& a) {
+__device__ inline int lane_segment(const JpegDecArgs& a, int bx) {
     const int tid = int(threadIdx.x), lane = tid & 63;
-    const long long s = (long long)(blockIdx.x) * (WAVES * L) + (tid >> 6) * L + lane;
+    const long long s = (long long)(bx) * (WAVES * L) + (tid >> 6) * L + lane;
     return lane < L && s < a.first_seg[a.g.intervals] ? int(s) : -1;
 }
 __device__ inline uint64_t entry_state(const JpegDecArgs& a, const JpegSeg& sg, int s) {
@@ -158,11 +159,11 @@ __device__ inline uint64_t entry_state(const JpegDecArgs& a, const JpegSeg& sg, 
 }
 
 template <int L>
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_count_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void count_body(const JpegDecArgs& a, int bx) {
     __shared__ JpegDecTables s_t;
-    if ((long long)(blockIdx.x) * (WAVES * L) >= a.first_seg[a.g.intervals]) return;      // (the whole workgroup)
+    if ((long long)(bx) * (WAVES * L) >= a.first_seg[a.g.intervals]) return;      // (the whole workgroup)
     load_tables(s_t, a.tables);
-    const int s = lane_segment<L>(a);
+    const int s = lane_segment<L>(a, bx);
     if (s < 0) return;
     const JpegSeg sg = jpeg_seg_at(a.start, a.first_seg, decoded_intervals(a), a.seg_bytes, s);
     JpegSegCount c = jpeg_seg_count_blocks(a.data, a.nbytes, s_t, a.g, entry_state(a, sg, s), sg.end);
@@ -187,10 +188,10 @@ __device__ inline JpegSegCount count_none() {
     return r;
 }
 
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_segscan_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void segscan_body(const JpegDecArgs& a, int bx) {
     __shared__ JpegSegCount s_e[2][THREADS];
     __shared__ JpegSegCount s_carry;      // what the steps before this one add up to
-    const int i = int(blockIdx.x), tid = int(threadIdx.x);
+    const int i = bx, tid = int(threadIdx.x);
     if (i >= decoded_intervals(a)) return;      // (the whole workgroup)
     const int s0 = a.first_seg[i], s1 = a.first_seg[i + 1];
     if (tid == 0) s_carry = count_none();
@@ -221,12 +222,12 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_segscan_kernel(JpegDe
 }
 
 template <int L>
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_write_kernel(JpegDecArgs a) {
+__device__ __forceinline__ void write_body(const JpegDecArgs& a, int bx) {
     __shared__ JpegDecTables s_t;
     __shared__ __attribute__((aligned(16))) int16_t s_block[WAVES * L][64 + 8];      // a lane's block in hand (144-byte rows)
-    if ((long long)(blockIdx.x) * (WAVES * L) >= a.first_seg[a.g.intervals]) return;      // (the whole workgroup)
+    if ((long long)(bx) * (WAVES * L) >= a.first_seg[a.g.intervals]) return;      // (the whole workgroup)
     load_tables(s_t, a.tables);
-    const int s = lane_segment<L>(a);
+    const int s = lane_segment<L>(a, bx);
     if (s < 0) return;
     const JpegSeg sg = jpeg_seg_at(a.start, a.first_seg, decoded_intervals(a), a.seg_bytes, s);
     const int4 bp = *reinterpret_cast<const int4*>(a.seg_blk + size_t(s) * 4);
@@ -236,6 +237,63 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_write_kernel(JpegDecA
     if (!jpeg_seg_write(a.data, a.nbytes, s_t, a.g, entry_state(a, sg, s), sg.end, bp.x, pred, jpeg_seg_interval_blocks(a.g, sg.interval), rec0,
                         s_block[slot]))
         atomicMin(&a.meta[1], sg.interval);
+}
+
+// ---- the single-stream kernels: the record by value, the grid that stream's ----
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_segtab_kernel(JpegDecArgs a) { segtab_body(a); }
+template <int L>
+__global__ __launch_bounds__(WINDOW * 64 / L) void whenet_jpeg_dec_sync_kernel(JpegDecArgs a) { sync_body<L>(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(64) void whenet_jpeg_dec_stitch_kernel(JpegDecArgs a) { stitch_body(a, int(blockIdx.x)); }
+template <int L>
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_count_kernel(JpegDecArgs a) { count_body<L>(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_segscan_kernel(JpegDecArgs a) { segscan_body(a, int(blockIdx.x)); }
+template <int L>
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_write_kernel(JpegDecArgs a) { write_body<L>(a, int(blockIdx.x)); }
+
+// ---- the clip kernels (as in jpeg_dec.hip): the records of up to 16 frames in device memory, the form-1 frames' windows, groups
+// and intervals back to back in one grid; a workgroup finds its frame, copies its record and runs the body.  Every frame has its
+// own seg_stats, first_seg, seg_exit, seg_count and seg_blk regions and its own seg_cap: nothing is shared between frames.
+// Resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), VGPRs of the clip form / of the
+// single-stream form, no scratch in either, the same LDS: segtab 26 / 27, sync 45 / 48, stitch 47 / 47, count 84 / 50 (the one
+// kernel that grows by more than the lookup: 4 above the 48..80 of the single-stream kernels), segscan 82 / 80, write 53 / 72.
+#define WHENET_JPEG_CLIP_KERNEL(prefix, name, threads, call)                                                               \
+    prefix __global__ __launch_bounds__(threads) void name(const void* __restrict__ recs, JpegClipGrid grid) {             \
+        const int b = int(blockIdx.x);                                                                                     \
+        if (b >= grid.total) return;                                                                                       \
+        const int f = jpeg_clip_frame_of(grid, b);                                                                         \
+        const JpegDecArgs& a = jpeg_clip_record(recs, f);                                                                  \
+        const int bx = b - grid.first[f];                                                                                  \
+        (void)bx;                                                                                                          \
+        call;                                                                                                              \
+    }
+WHENET_JPEG_CLIP_KERNEL(, whenet_jpeg_dec_clip_segtab_kernel, THREADS, segtab_body(a))
+WHENET_JPEG_CLIP_KERNEL(template <int L>, whenet_jpeg_dec_clip_sync_kernel, WINDOW * 64 / L, sync_body<L>(a, bx))
+WHENET_JPEG_CLIP_KERNEL(, whenet_jpeg_dec_clip_stitch_kernel, 64, stitch_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(template <int L>, whenet_jpeg_dec_clip_count_kernel, THREADS, count_body<L>(a, bx))
+WHENET_JPEG_CLIP_KERNEL(, whenet_jpeg_dec_clip_segscan_kernel, THREADS, segscan_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(template <int L>, whenet_jpeg_dec_clip_write_kernel, THREADS, write_body<L>(a, bx))
+#undef WHENET_JPEG_CLIP_KERNEL
+
+template <int L>
+void launch_lanes_clip(const JpegDecArgs* h, const void* d_recs, int frames, hipStream_t stream, int64_t& n) {
+    JpegClipGrid grid;
+    const auto launch = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(unsigned(grid.total)), dim3(unsigned(threads)), 0, stream, d_recs, grid);
+        WHENET_HIP_CHECK(hipGetLastError());
+        ++n;
+    };
+    const auto windows = [](const JpegDecArgs& a) { return a.form == 1 ? (a.seg_cap + WINDOW - 1) / WINDOW : 0; };
+    const auto groups = [](const JpegDecArgs& a) { return a.form == 1 ? (a.seg_cap + WAVES * L - 1) / (WAVES * L) : 0; };
+    jpeg_clip_grid(h, frames, windows, grid);
+    launch(whenet_jpeg_dec_clip_sync_kernel<L>, WINDOW * 64 / L);
+    jpeg_clip_grid(h, frames, [](const JpegDecArgs& a) { return a.form == 1 ? (a.g.intervals + 63) / 64 : 0; }, grid);
+    launch(whenet_jpeg_dec_clip_stitch_kernel, 64);
+    jpeg_clip_grid(h, frames, groups, grid);
+    launch(whenet_jpeg_dec_clip_count_kernel<L>, THREADS);
+    jpeg_clip_grid(h, frames, [](const JpegDecArgs& a) { return a.form == 1 ? a.g.intervals : 0; }, grid);
+    launch(whenet_jpeg_dec_clip_segscan_kernel, THREADS);
+    jpeg_clip_grid(h, frames, groups, grid);
+    launch(whenet_jpeg_dec_clip_write_kernel<L>, THREADS);
 }
 
 template <int L>
@@ -265,6 +323,35 @@ void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream) {
     if (lanes == 16) launch_lanes<16>(a, stream);
     else if (lanes == 32) launch_lanes<32>(a, stream);
     else launch_lanes<64>(a, stream);
+}
+
+// the six launches over the form-1 frames of a clip (none: nothing is launched); seg_lanes is the first form-1 frame's, an option of
+// the engine and so the same for all
+void launch_jpeg_decode_segmented_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, hipStream_t stream, int64_t* enqueues) {
+    WHENET_REQUIRE(h_recs != nullptr && d_recs != nullptr && frames >= 1 && frames <= MIXED_MAX_FRAMES, WHENET_EINVAL,
+                   "jpeg_decode_clip: NULL argument, or a frame count outside 1..16");
+    int lanes = -1;
+    for (int f = 0; f < frames; ++f) {
+        const JpegDecArgs& a = h_recs[f];
+        if (a.form != 1) continue;
+        WHENET_REQUIRE(jpeg_seg_bytes_ok(a.seg_bytes) && a.seg_cap >= 1 && a.g.intervals >= 1, WHENET_EINVAL,
+                       "jpeg_decode_clip: bad arguments of the segmented form");
+        const int l = a.seg_lanes == 0 ? DEFAULT_LANES : a.seg_lanes;
+        WHENET_REQUIRE(l == 16 || l == 32 || l == 64, WHENET_EINVAL, "jpeg_decode: the decoding lanes per wave must be 16, 32 or 64");
+        WHENET_REQUIRE(lanes < 0 || lanes == l, WHENET_EINVAL, "jpeg_decode_clip: the frames of a clip share the decoding lanes per wave");
+        lanes = l;
+    }
+    if (lanes < 0) return;
+    int64_t n = 0;
+    JpegClipGrid grid;
+    jpeg_clip_grid(h_recs, frames, [](const JpegDecArgs& a) { return a.form == 1 ? 1 : 0; }, grid);
+    hipLaunchKernelGGL(whenet_jpeg_dec_clip_segtab_kernel, dim3(unsigned(grid.total)), dim3(THREADS), 0, stream, d_recs, grid);
+    WHENET_HIP_CHECK(hipGetLastError());
+    ++n;
+    if (lanes == 16) launch_lanes_clip<16>(h_recs, d_recs, frames, stream, n);
+    else if (lanes == 32) launch_lanes_clip<32>(h_recs, d_recs, frames, stream, n);
+    else launch_lanes_clip<64>(h_recs, d_recs, frames, stream, n);
+    if (enqueues != nullptr) *enqueues += n;
 }
 
 }  // namespace whenet

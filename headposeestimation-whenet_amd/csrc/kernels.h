@@ -10,6 +10,7 @@
 #include "jpeg_host.h"
 #include "jpeg_dec_host.h"
 #include "jpeg_dec_seg_host.h"
+#include "jpeg_dec_clip_host.h"
 
 namespace whenet {
 
@@ -720,6 +721,49 @@ void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream);
 JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
                           const whenet_surface_t& dst, int channel_order, int32_t* d_status);
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream);
+// A CLIP of 1..16 streams, every stage in ONE launch for all of them: the same bodies, a workgroup first finds its frame in the
+// prefix sums of the per-frame workgroup counts (JpegClipGrid, by value) and reads that frame's record from d_recs -- device
+// memory, records JPEG_CLIP_RECORD_BYTES apart (jpeg_dec_clip_host.h), part of the clip's one upload.  h_recs: the same records on
+// the host, the launch sizes come from them.  d_zero / zero_bytes: every frame's start | meta | seg_stats and coefficient records
+// (one memset).  Frames of form 0 and of form 1, and of any colour path, may stand in one clip: a stage's kernel is launched once
+// if any frame needs it, so the number of enqueues depends on the forms and paths that occur, never on the frame count.
+// enqueues (may be nullptr): += the launches and memsets enqueued.
+struct JpegClipGrid {
+    int frames, total;
+    int first[MIXED_MAX_FRAMES + 1];      // frame f owns workgroups first[f] .. first[f + 1] - 1 (none: the two are equal)
+};
+// the grid of a stage: count(record) workgroups for every frame (0: the frame does not take part); false where no frame does
+template <class Count>
+inline bool jpeg_clip_grid(const JpegDecArgs* recs, int frames, Count count, JpegClipGrid& grid) {
+    grid = JpegClipGrid{};
+    grid.frames = frames;
+    long long at = 0;
+    for (int f = 0; f < frames; ++f) {
+        grid.first[f] = int(at);
+        at += count(recs[f]);
+        WHENET_REQUIRE(at < 0x7FFFFFFF, WHENET_EINVAL, "jpeg_decode_clip: more workgroups than an int32 counts");
+    }
+    for (int f = frames; f <= MIXED_MAX_FRAMES; ++f) grid.first[f] = int(at);
+    grid.total = int(at);
+    return at > 0;
+}
+
+#if defined(__HIPCC__)
+// the frame of workgroup b: the last one whose first workgroup is not behind b (a scan of at most 16 prefix sums, the same for
+// every lane: b is a workgroup index), and that frame's record
+__device__ __forceinline__ int jpeg_clip_frame_of(const JpegClipGrid& grid, int b) {
+    int f = 0;
+#pragma unroll
+    for (int i = 1; i < MIXED_MAX_FRAMES; ++i) f = (i < grid.frames && b >= grid.first[i]) ? i : f;
+    return f;
+}
+__device__ __forceinline__ const JpegDecArgs& jpeg_clip_record(const void* recs, int f) {
+    return *reinterpret_cast<const JpegDecArgs*>(static_cast<const char*>(recs) + size_t(f) * JPEG_CLIP_RECORD_BYTES);
+}
+#endif
+void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, void* d_zero, size_t zero_bytes, hipStream_t stream,
+                             int64_t* enqueues);
+void launch_jpeg_decode_segmented_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, hipStream_t stream, int64_t* enqueues);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16

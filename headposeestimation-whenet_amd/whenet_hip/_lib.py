@@ -147,6 +147,10 @@ _PROTOS = {
     "whenet_jpeg_decode_counters": (C.c_int, [_P, C.POINTER(C.c_int64 * 4)]),
     "whenet_jpeg_seg_dc_scan_host": (C.c_int, [_P, C.c_int64, C.c_int, _P]),
     "whenet_frame_begin_jpeg": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.POINTER(C.c_int), _P]),
+    "whenet_clip_begin_jpeg": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
+    "whenet_op_jpeg_decode_clip": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int]),
+    "whenet_jpeg_clip_plan": (C.c_int, [C.POINTER(JpegInfoC), _P, C.c_int, C.c_int, C.c_int, _P]),
+    "whenet_jpeg_clip_counters": (C.c_int, [_P, C.POINTER(C.c_int64 * 4)]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -655,6 +659,46 @@ def jpeg_decode_segmented_planes_host(data, planes: list, seg_bytes: int, window
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return status, stats
+
+
+JPEG_CLIP_PLAN_FRAME_WORDS, JPEG_CLIP_PLAN_TOTAL_WORDS = 32, 8
+JPEG_CLIP_REGIONS = ("tables", "data", "start", "meta", "seg_stats", "coef", "plane0", "plane1", "plane2", "first_seg", "seg_exit",
+                     "seg_count", "seg_blk")
+
+
+def jpeg_clip_plan(infos, nbytes, entropy: int = 2, seg_bytes: int = 128) -> dict:
+    """`whenet_jpeg_clip_plan` (pure host): the layout a clip of JPEG streams gets.  infos: `JpegInfoC` per frame, nbytes: the length
+    of each frame's entropy data; entropy 0, 1 or 2 (auto).  {"frames": [{"form", "seg_bytes", "seg_cap", region: (offset, length)
+    for region in JPEG_CLIP_REGIONS}], "records": (offset, length), "upload_bytes", "zero": (offset, length), "bytes", "forms":
+    (frames of form 0, of form 1)}."""
+    n = len(infos)
+    arr = (JpegInfoC * max(n, 1))(*infos)
+    nb = np.ascontiguousarray(nbytes, np.int64)
+    if nb.size != n:
+        raise ValueError("one nbytes per info is needed")
+    out = np.zeros(max(n, 0) * JPEG_CLIP_PLAN_FRAME_WORDS + JPEG_CLIP_PLAN_TOTAL_WORDS, np.int64)
+    lib = load()
+    rc = lib.whenet_jpeg_clip_plan(arr, _ptr(nb if nb.size else np.zeros(1, np.int64)), n, int(entropy), int(seg_bytes), _ptr(out))
+    if rc != OK:
+        raise ValueError(lib.whenet_last_error(None).decode())
+    frames = []
+    for f in range(n):
+        o = out[f * JPEG_CLIP_PLAN_FRAME_WORDS:(f + 1) * JPEG_CLIP_PLAN_FRAME_WORDS]
+        d = {"form": int(o[0]), "seg_bytes": int(o[1]), "seg_cap": int(o[2])}
+        for k, name in enumerate(JPEG_CLIP_REGIONS):
+            d[name] = (int(o[4 + 2 * k]), int(o[5 + 2 * k]))
+        frames.append(d)
+    t = out[n * JPEG_CLIP_PLAN_FRAME_WORDS:]
+    return {"frames": frames, "records": (int(t[0]), int(t[1])), "upload_bytes": int(t[2]), "zero": (int(t[3]), int(t[4])),
+            "bytes": int(t[5]), "forms": (int(t[6]), int(t[7]))}
+
+
+def _clip_streams(datas):
+    """The streams of a clip as (arrays kept alive, void* [F], int64 [F])."""
+    arrs = [_stream_array(d) for d in datas]
+    ptrs = (_P * max(len(arrs), 1))(*[_ptr(a) if a.size else None for a in arrs])
+    sizes = np.array([a.size for a in arrs], np.int64)
+    return arrs, ptrs, sizes
 
 
 def jpeg_seg_dc_scan_host(diff, chunk: int) -> np.ndarray:
@@ -1351,6 +1395,35 @@ class Handle:
         self._check(self._lib.whenet_frame_begin_jpeg(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB, C.byref(t),
                                                       _ptr(status)))
         return t.value
+
+    def clip_begin_jpeg(self, datas, status: np.ndarray, bgr: bool = True) -> int:
+        """`whenet_clip_begin_jpeg`: `clip_begin` / `clip_begin_mixed` from the bytes of 1..16 JPEG streams, decoded on the device in one
+        submission.  status = int32 [F,2], complete when the ticket's collect call returns; it must stay alive until then."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        if status.dtype != np.int32 or status.size != 2 * len(arrs) or not status.flags.c_contiguous:
+            raise ValueError("status must be a contiguous int32 [F,2] array")
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_jpeg(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), BGR if bgr else RGB,
+                                                     C.byref(t), _ptr(status) if status.size else None))
+        return t.value
+
+    def op_jpeg_decode_clip(self, datas, surfaces, bgr: bool, entropy: int = -1, seg_bytes: int = 128) -> np.ndarray:
+        """`whenet_op_jpeg_decode_clip`: the clip kernels alone, host to host (works on a postproc handle), stream f into host surface
+        f; entropy -1 (the handle's options), 0 or 1.  The status words int32 [F,2]."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        surf = (SurfaceC * max(len(surfaces), 1))(*surfaces)
+        status = np.zeros((len(arrs), 2), np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_clip(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
+                                                         BGR if bgr else RGB, _ptr(status) if status.size else None, int(entropy),
+                                                         int(seg_bytes)))
+        return status
+
+    def jpeg_clip_counters(self) -> dict:
+        """`whenet_jpeg_clip_counters`: host-side counts over the handle's engines: {"clips", "frames", "enqueues" (kernel launches plus
+        memsets), "h2d"}."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.whenet_jpeg_clip_counters(self._h, C.byref(out)))
+        return {"clips": int(out[0]), "frames": int(out[1]), "enqueues": int(out[2]), "h2d": int(out[3])}
 
     def frame_annotate(self, ticket: int, frame_index: int, surface: SurfaceC, stream=None, display: int = DISPLAY_SIMPLE) -> None:
         """`whenet_frame_annotate_ex`: enqueue the annotated frame of a ticket whose heads are enqueued.  A host surface is complete

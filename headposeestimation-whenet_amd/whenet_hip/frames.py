@@ -303,6 +303,38 @@ class FramePipeline:
         self._last_sizes = [(info.h, info.w)]
         return st
 
+    def begin_clip_jpeg(self, datas) -> list:
+        """A clip from the bytes of 1..16 baseline JPEG streams (consecutive frames of an MJPG file: `MJPGReader.clips(16)`), each
+        with its own size, sampling, tables and DRI: one upload of the compressed bytes, every decoder stage in one launch for all
+        frames.  Frame f is what `begin_jpeg(datas[f])` makes; frames of one size make a clip as `begin_clip()` makes it, frames of
+        different sizes one as `begin_clip_mixed()` makes it (at most option "letterbox_cache" of them).  `detect_heads_clip()` and
+        `collect_clip()` follow.  One stream the decoder does not accept is a ValueError that names the frame, and the clip takes no
+        place.  Returns a `JpegStatus` per frame, valid after `collect_clip()`: a damaged stream does not raise, it yields its own
+        defined frame and `ok == False` and leaves the other frames untouched."""
+        self._check_can_begin()
+        datas = list(datas)
+        if not 1 <= len(datas) <= _lib.MAX_CLIP_FRAMES:
+            raise ValueError(f"a clip holds 1..{_lib.MAX_CLIP_FRAMES} frames, got {len(datas)}")
+        infos = []
+        for i, d in enumerate(datas):
+            try:
+                infos.append(_lib.jpeg_parse(d))
+            except ValueError as e:
+                raise ValueError(f"begin_clip_jpeg: frame {i}: {e}") from None
+        block = np.zeros((len(datas), 2), np.int32)      # (one array for the library to write; every JpegStatus is a row of it)
+        ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr)
+        sts = []
+        for f in range(len(datas)):
+            st = JpegStatus()
+            st._status = block[f]
+            sts.append(st)
+        if self._jpeg is None:
+            self._jpeg = {}
+        self._jpeg.setdefault(ticket, []).extend(sts)
+        self._begun_clip = (ticket, len(datas))
+        self._last_sizes = [(i.h, i.w) for i in infos]
+        return sts
+
     def begin_clip_yuv(self, frames, stream=None) -> None:
         """A clip from the planes of 1..16 `YUVFrame`s, each with its own format and matrix: frames of one size make a clip as
         `begin_clip()` makes it, frames of different sizes one as `begin_clip_mixed()` makes it (at most option "letterbox_cache"

@@ -161,6 +161,42 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     return (out, st) if stats else out
 
 
+def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True):
+    """(frames, statuses) of 1..16 baseline JPEG streams decoded as ONE clip by the kernels (`whenet_op_jpeg_decode_clip`): a list of
+    uint8 [H_f,W_f,3] frames and the status words int32 [F,2].  Frame f is `decode(datas[f])`, bit for bit.  `entropy`: None or
+    "auto" (the handle's options, stream by stream), "interval" or "segmented" (`seg_bytes`: None = 128).  A stream the decoder does
+    not accept is a ValueError that names the frame; a damaged one raises `DecodeError` with the frame's index in its text
+    (strict=False: its defined frame and status are returned with the others)."""
+    if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
+        raise ValueError("entropy must be None, 'auto', 'interval' or 'segmented'")
+    datas = list(datas)
+    if not 1 <= len(datas) <= _lib.MAX_CLIP_FRAMES:
+        raise ValueError(f"a clip holds 1..{_lib.MAX_CLIP_FRAMES} frames, got {len(datas)}")
+    frames = []
+    for f, d in enumerate(datas):
+        try:
+            i = _lib.jpeg_parse(d)
+        except ValueError as e:
+            raise ValueError(f"decode_clip: frame {f}: {e}") from None
+        frames.append(np.empty((i.h, i.w, 3), np.uint8))
+    form = -1 if entropy in (None, "auto") else _lib.JPEG_ENTROPY[entropy]
+    seg = 128 if seg_bytes is None else int(seg_bytes)
+    surfaces = [packed_surface(fr) for fr in frames]
+    if handle is None:
+        with _lib.Handle.postproc(0) as own:
+            status = own.op_jpeg_decode_clip(datas, surfaces, bgr, form, seg)
+    else:
+        status = _handle_of(handle).op_jpeg_decode_clip(datas, surfaces, bgr, form, seg)
+    if strict:
+        for f in range(len(frames)):
+            if status[f, 0] != _lib.OK:
+                e = DecodeError(int(status[f, 1]), frames[f])
+                e.args = (f"frame {f}: {e.args[0]}",)
+                e.index = f
+                raise e
+    return frames, status
+
+
 def decode_host(data, bgr: bool = True, strict: bool = True) -> np.ndarray:
     """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
     held to."""

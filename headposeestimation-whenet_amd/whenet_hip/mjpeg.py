@@ -205,6 +205,14 @@ class MJPGReader:
         for i in range(len(self._frames)):
             yield self[i]
 
+    def clips(self, n: int):
+        """Lists of up to `n` consecutive frames' bytes, ready for `FramePipeline.begin_clip_jpeg`: every list but the last has n
+        entries, none is empty."""
+        if int(n) < 1:
+            raise ValueError("clips(n): n must be at least 1")
+        for first in range(0, len(self._frames), int(n)):
+            yield [self[i] for i in range(first, min(first + int(n), len(self._frames)))]
+
 
 def _chunk(fourcc: bytes, payload: bytes) -> bytes:
     return fourcc + struct.pack("<I", len(payload)) + payload + (b"\0" if len(payload) & 1 else b"")

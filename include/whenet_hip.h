@@ -937,11 +937,42 @@ WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_ind
  *   whenet_jpeg_seg_dc_scan_host  the saturating scan alone: pred[i] = the predictor behind difference i, by maps over chunks
  * Measured on one MI355X (docs/experiments.md section 32): a 1080p stream without DRI decodes in 15.7 ms in form 1 against 1.03 s in
  * form 0, one with 68 intervals in 5.2-6.6 ms against 32 ms; a host decoder on one core takes 8.6 ms, and is still faster at 480p.
- * Not built: clips of JPEG streams, a stitch of several lanes per interval, a marker scan of several workgroups, progressive /
- * arithmetic / 12-bit streams.
+ * CLIPS OF JPEG STREAMS (four entry points, 101 in all, ABI still 6).  Up to 16 streams per submission, as whenet_clip_begin and
+ * its kin take up to 16 frames.  Frame f is exactly what whenet_frame_begin_jpeg(data[f]) makes: the same frame bytes, the same two
+ * status words.  Every stream keeps its own size, sampling, tables and DRI, and gets its own entropy form: "jpeg_entropy" and
+ * "jpeg_seg_bytes" are applied stream by stream, so under auto a clip may hold streams of both forms.  A damaged stream gives its own
+ * defined frame and status and leaves every other frame untouched.  Records, decode tables and entropy bytes of all frames travel
+ * as ONE H2D; every stage runs for all frames in one launch (one memset in front), so the number of enqueues depends on the forms
+ * and colour paths that occur in the clip, never on the frame count.
+ *   whenet_clip_begin_jpeg   ENQUEUE-ONLY.  The slot ends up as whenet_clip_begin leaves it where every frame has one size, else as
+ *                  whenet_clip_begin_mixed leaves it (frames back to back, unaligned; at most option letterbox_cache frames);
+ *                  whenet_clip_detect_heads, the annotate calls and whenet_collect_clip then work unchanged.  status: int32
+ *                  [num_frames][2], complete when the ticket's collect call returns; the pointer must stay valid until then.
+ *                  Refusals come before a slot is taken and name the frame: num_frames outside 1..16, a NULL pointer or a size
+ *                  < 1 (WHENET_EINVAL), a stream the parser refuses (WHENET_EFORMAT: one refused stream refuses the whole call).
+ *   whenet_op_jpeg_decode_clip  the clip kernels alone, host to host: frame f into dst[f] (host surfaces at the caller's pitches;
+ *                  packed, or I420 / NV12 for a 4:2:0 stream), status [num_frames][2].  entropy -1: the handle's options; 0 / 1
+ *                  and seg_bytes as in whenet_op_jpeg_decode_ex.  Works on a whenet_create_postproc handle.
+ *   whenet_jpeg_clip_plan    pure host, no GPU: the layout the engine uses.  infos: the parsed headers, nbytes[f]: the length of
+ *                  frame f's entropy data (size - data_offset), entropy 0, 1 or 2 (auto), seg_bytes a power of two in 4..4096.
+ *                  out: num_frames * WHENET_JPEG_CLIP_PLAN_FRAME_WORDS + WHENET_JPEG_CLIP_PLAN_TOTAL_WORDS int64.  Per frame:
+ *                  [0] the form, [1] seg_bytes (0 in form 0), [2] seg_cap (0 in form 0), [3] 0, then (offset, length) in bytes of
+ *                  tables, data, start, meta, seg_stats, coef, plane 0, 1, 2, first_seg, seg_exit, seg_count, seg_blk ([4]..[29];
+ *                  length 0: the frame has no such region), [30..31] 0.  Behind the last frame: [0..1] offset and length of the
+ *                  argument records, [2] the bytes of the upload block (records | per frame tables | data, from offset 0),
+ *                  [3..4] offset and length of the zeroed bytes (every frame's start | meta | seg_stats, then every frame's
+ *                  coef), [5] the bytes of the whole buffer, [6] frames of form 0, [7] frames of form 1.  Every region starts at a
+ *                  multiple of 256, but seg_stats, which lies 64 bytes behind meta.
+ *   whenet_jpeg_clip_counters  out = {clip decodes enqueued, frames in them, kernel launches plus memsets enqueued for them, H2D
+ *                  copies enqueued for them} over the engines of the handle (host-side counts).  A clip decode also counts each of
+ *                  its frames into whenet_jpeg_decode_counters' form-0 or form-1 word.
+ * Not built: clips of streams already in device memory, a stitch of several lanes per interval, a marker scan of several
+ * workgroups, progressive / arithmetic / 12-bit streams.
  * WHENET_EINVAL: a NULL argument or plane, size < 1, a pitch below the row bytes, an unknown format / channel order, a seg_bytes,
  * window or entropy value outside its range. */
 #define WHENET_JPEG_SEG_WINDOW 256
+#define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
+#define WHENET_JPEG_CLIP_PLAN_TOTAL_WORDS 8
 typedef struct {
     int32_t h, w, components;
     int32_t hs, vs;                  /* luma sampling factors (1 or 2); chroma is 1 x 1 */
@@ -971,6 +1002,13 @@ WHENET_API int whenet_op_jpeg_decode_ex(whenet_t* h, const uint8_t* data, int64_
                              int seg_bytes, int32_t status[2], int64_t stats[8]);
 WHENET_API int whenet_jpeg_decode_counters(whenet_t* h, int64_t out[4]);
 WHENET_API int whenet_jpeg_seg_dc_scan_host(const int32_t* diff, int64_t n, int chunk, int32_t* pred);
+WHENET_API int whenet_clip_begin_jpeg(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int* ticket,
+                           int32_t* status);
+WHENET_API int whenet_op_jpeg_decode_clip(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, const whenet_surface_t* dst,
+                               int channel_order, int32_t* status, int entropy, int seg_bytes);
+WHENET_API int whenet_jpeg_clip_plan(const whenet_jpeg_info_t* infos, const int64_t* nbytes, int num_frames, int entropy, int seg_bytes,
+                          int64_t* out);
+WHENET_API int whenet_jpeg_clip_counters(whenet_t* h, int64_t out[4]);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

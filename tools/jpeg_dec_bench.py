@@ -22,8 +22,16 @@
     (iv)  bytes_frame, bytes_jpeg
                                 bytes over PCIe per frame, both ways
 
+    (v)   --clip F [F ...]      clips of JPEG streams (recorded, not gated), INSTEAD of (i)-(iv): for the `own` stream (one restart
+                                interval per MCU row) and the `pillow` stream (no DRI) of each size, F frames as ONE
+                                whenet_clip_begin_jpeg against the same F frames as F whenet_frame_begin_jpeg submissions, in the
+                                same process; each submission is released without heads and collected (the collect waits for the
+                                decode and hands the status words over).  ms per frame: the median of --clip-samples (>= 20)
+                                single regions after a warm-up, and their 10th..90th percentile spread; "enqueues" / "h2d" per clip
+                                are whenet_jpeg_clip_counters' differences.  The handle's options stay at their defaults (auto).
+
   python tools/jpeg_dec_bench.py [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
-                                 [--lanes 0] [--only-decode]
+                                 [--lanes 0] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
 
 Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
 events on the stream the work is enqueued on.  The frames the streams decode to are checked against the host statement first.
@@ -155,6 +163,55 @@ def size_leg(m, h, w, args):
     return res
 
 
+def clip_leg(m, h, w, args):
+    import torch
+    from whenet_hip import jpeg, synth
+    hnd = m._handle
+    sync = torch.cuda.synchronize
+    no_heads = np.zeros((0, 4), np.int32)
+    res = {"frame": [h, w], "clip": {}}
+    streams = streams_of(synth.video_frame(h, w))
+    for name in ("own", "pillow"):
+        data = streams[name]
+        want = jpeg.decode_host(data)
+        got, _ = jpeg.decode_clip([data] * 3, handle=hnd)      # the clip kernels on this stream against the host statement first
+        r = {"bytes_jpeg": len(data), "equals_host": all(np.array_equal(g, want) for g in got)}
+        for F in args.clip:
+            datas, status, single = [data] * F, np.zeros((F, 2), np.int32), np.zeros(2, np.int32)
+
+            def clip():
+                t = hnd.clip_begin_jpeg(datas, status)
+                hnd.frame_heads(t, no_heads)
+                hnd.collect(t, 0)
+
+            def singles():
+                for d in datas:
+                    t = hnd.frame_begin_jpeg(d, single)
+                    hnd.frame_heads(t, no_heads)
+                    hnd.collect(t, 0)
+
+            before = hnd.jpeg_clip_counters()
+            clip()
+            after = hnd.jpeg_clip_counters()
+            assert status.tolist() == [[0, -1]] * F and after["h2d"] - before["h2d"] == 1
+            out = {"enqueues": after["enqueues"] - before["enqueues"], "h2d": 1}
+            for key, fn in (("clip", clip), ("singles", singles)):
+                for _ in range(3):
+                    fn()
+                ms = []
+                for _ in range(max(20, args.clip_samples)):
+                    sync()
+                    t = time.perf_counter()
+                    fn()
+                    ms.append((time.perf_counter() - t) * 1e3 / F)
+                q = np.percentile(ms, [10, 50, 90])
+                out[key + "_ms_per_frame"] = round(float(q[1]), 3)
+                out[key + "_p10_p90"] = [round(float(q[0]), 3), round(float(q[2]), 3)]
+            r[str(F)] = out
+        res["clip"][name] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
@@ -164,6 +221,8 @@ def main():
     ap.add_argument("--seg-bytes", type=int, nargs="+", default=[128], help="segment sizes of the segmented form")
     ap.add_argument("--lanes", type=int, default=0, choices=[0, 16, 32, 64], help="decoding lanes per wave of the segmented kernels")
     ap.add_argument("--only-decode", action="store_true", help="rows (i) only")
+    ap.add_argument("--clip", type=int, nargs="+", default=None, help="row (v) only: frames per clip of JPEG streams, 1..16 each")
+    ap.add_argument("--clip-samples", type=int, default=20, help="regions per figure of row (v), at least 20")
     args = ap.parse_args()
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
     import whenet
@@ -172,7 +231,7 @@ def main():
     try:
         for size in args.sizes:
             h, w = (int(v) for v in size.split("x"))
-            print(json.dumps(size_leg(m, h, w, args)), flush=True)
+            print(json.dumps(clip_leg(m, h, w, args) if args.clip else size_leg(m, h, w, args)), flush=True)
     finally:
         m.close()
     return 0
