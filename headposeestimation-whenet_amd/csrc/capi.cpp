@@ -1211,6 +1211,78 @@ int whenet_jpeg_clip_counters(whenet_t* h, int64_t out[4]) {
     });
 }
 
+// ---- the decode rule as an argument (JPEG DECODER, RULE 1): the calls above with `rule` beside their arguments ----
+int whenet_jpeg_decode_rule_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule, int32_t status[2]) {
+    try {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_rule_host: NULL argument");
+        whenet_jpeg_info_t info;
+        if (const int rc = parse_for_host("jpeg_decode_rule_host", data, size, info)) return rc;
+        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_rule_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_rule_host: the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), planes, status, rule);
+        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_jpeg_decode_segmented_rule_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int seg_bytes,
+                                           int window, int rule, int32_t status[2], int64_t stats[8]) {
+    try {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_segmented_rule_host: NULL argument");
+        WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "jpeg_decode_segmented_rule_host: seg_bytes must be a power of two in 4..4096");
+        WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, "jpeg_decode_segmented_rule_host: window must be 1..1024");
+        whenet_jpeg_info_t info;
+        if (const int rc = parse_for_host("jpeg_decode_segmented_rule_host", data, size, info)) return rc;
+        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_segmented_rule_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_segmented_rule_host: the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, planes, status, stats, rule);
+        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_op_jpeg_decode_rule(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
+                               int seg_bytes, int rule, int32_t status[2], int64_t stats[8]) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_rule: NULL argument");
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       "op_jpeg_decode_rule: entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_rule: seg_bytes must be a power of two in 4..4096");
+        e.op_jpeg_decode(data, size, *dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, stats, rule);
+    });
+}
+
+int whenet_op_jpeg_decode_clip_rule(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, const whenet_surface_t* dst,
+                                    int channel_order, int32_t* status, int entropy, int seg_bytes, int rule) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       "op_jpeg_decode_clip_rule: entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_clip_rule: seg_bytes must be a power of two in 4..4096");
+        e.op_jpeg_decode_clip(data, size, num_frames, dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, rule);
+    });
+}
+
+int whenet_frame_begin_jpeg_rule(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int* ticket, int32_t* status) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status, rule); });
+}
+
+int whenet_clip_begin_jpeg_rule(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int rule,
+                                int* ticket, int32_t* status) {
+    return begin_on_next_engine(h, ticket,
+                                [&](whenet::Engine& e) { return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule); });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

@@ -285,6 +285,10 @@ void Engine::set_option(const std::string& key, long value) {
         WHENET_REQUIRE(value >= 0 && value <= 2, WHENET_EINVAL, "jpeg_entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto, default)");
         jpeg_entropy_ = int(value);
         return;
+    } else if (key == "jpeg_rule") {
+        WHENET_REQUIRE(jpeg_rule_ok(value), WHENET_EINVAL, "jpeg_rule must be 0 (the project's own rule, default) or 1 (libjpeg's bytes)");
+        jpeg_rule_ = int(value);
+        return;
     } else if (key == "jpeg_seg_lanes") {
         WHENET_REQUIRE(value == 0 || value == 16 || value == 32 || value == 64, WHENET_EINVAL, "jpeg_seg_lanes must be 0 (default), 16, 32 or 64");
         jpeg_seg_lanes_ = int(value);

@@ -357,12 +357,14 @@ class Engine {
     // The entropy stage's form (0: an interval per lane, 1: segmented, jpeg_dec_seg.hip) follows the options "jpeg_entropy" (2: auto,
     // by the bytes per interval) and "jpeg_seg_bytes"; op_jpeg_decode takes them from its arguments where entropy >= 0 and reads the
     // segmented form's statistics back into stats (8 int64, may be nullptr).
+    // The decode RULE (0: the project's own inverse DCT, nearest chroma and JFIF row; 1: libjpeg's bytes -- jidctint, fancy
+    // upsampling, jdcolor -- into packed destinations only) follows the option "jpeg_rule" (default 0) wherever `rule` is -1.
     void op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy = -1,
-                        int seg_bytes = 0, int64_t* stats = nullptr);
+                        int seg_bytes = 0, int64_t* stats = nullptr, int rule = -1);
     void add_jpeg_decode_counters(int64_t out[4]) const;      // decodes launched in form 0, in form 1
     void jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
                             int channel_order, int32_t* d_status, hipStream_t stream);
-    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status);
+    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule = -1);
     // A CLIP of 1..16 JPEG streams (frame f: data[f], size[f] bytes), each with its own size, sampling, tables, DRI and entropy
     // form (the options are applied stream by stream): one plan (jpeg_dec_clip_host.h), ONE H2D of records | tables | entropy bytes,
     // one memset and every stage in one launch for all frames (launch_jpeg_decode_clip).  Refusals -- a frame count outside 1..16, a
@@ -371,9 +373,9 @@ class Engine {
     // clip_begin_jpeg: the slot ends up as clip_begin (one size) or clip_begin_mixed (frames back to back) leaves it for the decoded
     // frames; status [frames][2] comes back through pinned memory with the ticket's collect call.
     // op_jpeg_decode_clip: the clip kernels alone, host to host, frame f into dst[f] at the caller's pitches between guard zones.
-    int clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status);
+    int clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule = -1);
     void op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
-                             int32_t* status, int entropy = -1, int seg_bytes = 0);
+                             int32_t* status, int entropy = -1, int seg_bytes = 0, int rule = -1);
     void add_jpeg_clip_counters(int64_t out[4]) const;      // clip decodes, their frames, their launches + memsets, their H2D copies
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
@@ -598,11 +600,14 @@ class Engine {
     DeviceBuffer jpeg_dec_tables_d_;     // the next stream's are the same: an MJPG stream repeats its tables)
     std::vector<JpegDecTables> jpeg_dec_tables_h_;
     int jpeg_entropy_ = 2, jpeg_seg_bytes_ = JPEG_SEG_DEFAULT_BYTES;      // options "jpeg_entropy", "jpeg_seg_bytes"
+    int jpeg_rule_ = JPEG_RULE_OWN;                                       // option "jpeg_rule"
+    // the rule of a call: its argument, or the option where that is -1; anything else is WHENET_EINVAL
+    int jpeg_rule_of(const char* what, int rule) const;
     int jpeg_seg_lanes_ = 0;                                             // option "jpeg_seg_lanes" (a measurement knob; 0: the default)
     int64_t jpeg_dec_launched_[2] = {0, 0};                              // decodes launched in form 0, form 1
     int64_t jpeg_clip_counts_[4] = {0, 0, 0, 0};                         // add_jpeg_clip_counters
     struct JpegClipJob;      // the parsed headers, geometries and the plan of a clip (engine_post.cpp)
-    void jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes,
+    void jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes, int rule,
                            JpegClipJob& job) const;
     // records | tables | entropy bytes into `stage` (plan.upload_bytes), the records for a work buffer at d_base; recs: the same records
     void jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,

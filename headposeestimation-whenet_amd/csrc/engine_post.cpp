@@ -1434,14 +1434,21 @@ JpegDecScratch Engine::jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, 
     return lay;
 }
 
+int Engine::jpeg_rule_of(const char* what, int rule) const {
+    WHENET_REQUIRE(rule == -1 || jpeg_rule_ok(rule), WHENET_EINVAL,
+                   std::string(what) + ": rule must be -1 (the handle's option), 0 (the project's own) or 1 (libjpeg)");
+    return rule == -1 ? jpeg_rule_ : rule;
+}
+
 void Engine::add_jpeg_decode_counters(int64_t out[4]) const { out[0] += jpeg_dec_launched_[0], out[1] += jpeg_dec_launched_[1]; }
 
 void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy,
-                            int seg_bytes, int64_t* stats) {
+                            int seg_bytes, int64_t* stats, int rule) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
+    rule = jpeg_rule_of("op_jpeg_decode", rule);
     const whenet_jpeg_info_t info = parse_or_refuse("op_jpeg_decode", data, size);
-    const char* bad = jpeg_dec_check_dst(info, &dst, channel_order);
+    const char* bad = jpeg_dec_check_dst(info, &dst, channel_order, rule);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_decode: ") + (bad ? bad : ""));
     WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_jpeg_decode: the surface must be host memory (on_device = 0)");
     check_surface("op_jpeg_decode", dst, info.h, info.w);
@@ -1468,7 +1475,7 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
     whenet_surface_t d_dst = dst;
     for (int p = 0; p < planes; ++p) d_dst.plane[p] = d_out.frames() + off[p];
     launch_jpeg_decode(jpeg_dec_args(g, d_scratch, lay, reinterpret_cast<const uint8_t*>(d_scratch + lay.data), (long long)(nbytes), d_dst,
-                                     channel_order, d_status),
+                                     channel_order, d_status, rule),
                        lay, stream_);
     ++jpeg_dec_launched_[lay.form];
     d_out.to_host(stream_, off, 0, nullptr, "op_jpeg_decode");      // waits, checks the guard zones
@@ -1504,7 +1511,7 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     WHENET_REQUIRE(nbytes >= 1 && nbytes <= JPEG_DEC_MAX_BYTES, WHENET_EINVAL, "jpeg_decode_device: nbytes must be 1..2^31 - 1");
     const char* bad = jpeg_dec_check_info(info);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_device: info: ") + (bad ? bad : ""));
-    bad = jpeg_dec_check_dst(info, &dst, channel_order);
+    bad = jpeg_dec_check_dst(info, &dst, channel_order, jpeg_rule_);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_device: ") + (bad ? bad : ""));
     WHENET_REQUIRE(dst.on_device == 1, WHENET_EINVAL, "jpeg_decode_device: the surface must be device memory (on_device = 1)");
     check_surface("jpeg_decode_device", dst, info.h, info.w);
@@ -1529,7 +1536,7 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     }
     if (!jpeg_source_) jpeg_source_.create();
     if (!jpeg_done_) jpeg_done_.create();
-    JpegDecArgs a = jpeg_dec_args(g, jpeg_dec_scratch_.as<void>(), lay, d_entropy, nbytes, dst, channel_order, d_status);
+    JpegDecArgs a = jpeg_dec_args(g, jpeg_dec_scratch_.as<void>(), lay, d_entropy, nbytes, dst, channel_order, d_status, jpeg_rule_);
     a.tables = jpeg_dec_tables_d_.as<JpegDecTables>();
     WHENET_HIP_CHECK(hipEventRecord(jpeg_source_, stream));
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, jpeg_source_, 0));
@@ -1540,9 +1547,10 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
 }
 
 // frame_begin from a JPEG stream: the slot ends up exactly as frame_begin(decoded frame, channel_order) leaves it
-int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status) {
+int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "frame_begin_jpeg: NULL argument");
+    rule = jpeg_rule_of("frame_begin_jpeg", rule);
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "frame_begin_jpeg: unknown channel order");
     const whenet_jpeg_info_t info = parse_or_refuse("frame_begin_jpeg", data, size);      // (before a slot is taken)
     const JpegDecGeom g = jpeg_dec_geom(info);
@@ -1568,7 +1576,7 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     whenet_surface_t dst{};
     dst.plane[0] = slot.frame.d.as<void>(), dst.pitch[0] = 3 * info.w, dst.format = WHENET_SURF_PACKED, dst.on_device = 1;
     launch_jpeg_decode(jpeg_dec_args(g, slot.jpg_dec.as<void>(), lay, slot.jpg_dec.as<uint8_t>() + lay.data, (long long)(nbytes), dst,
-                                     channel_order, static_cast<int32_t*>(d_status)),
+                                     channel_order, static_cast<int32_t*>(d_status), rule),
                        lay, copy_stream());
     ++jpeg_dec_launched_[lay.form];
     WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
@@ -1585,11 +1593,13 @@ struct Engine::JpegClipJob {
     JpegDecGeom g[MIXED_MAX_FRAMES];
     int64_t nbytes[MIXED_MAX_FRAMES];
     JpegClipPlan plan;
+    int rule = JPEG_RULE_OWN;      // the clip's decode rule: one for all of its frames
 };
 
 void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes,
-                               JpegClipJob& job) const {
+                               int rule, JpegClipJob& job) const {
     const std::string w(what);
+    job.rule = jpeg_rule_of(what, rule);
     WHENET_REQUIRE(nframes >= 1 && nframes <= MIXED_MAX_FRAMES, WHENET_EINVAL,
                    w + ": " + std::to_string(nframes) + " frames: a clip holds 1..16 (the detector's batch limit)");
     WHENET_REQUIRE(data != nullptr && size != nullptr, WHENET_EINVAL, w + ": NULL argument");
@@ -1623,7 +1633,7 @@ void Engine::jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data,
             a.plane[c] = reinterpret_cast<uint8_t*>(s + q.plane[c].off);
             a.dst[c] = static_cast<uint8_t*>(dst[f].plane[c]), a.dst_pitch[c] = dst[f].pitch[c];
         }
-        a.format = dst[f].format, a.channel_order = channel_order;
+        a.format = dst[f].format, a.channel_order = channel_order, a.rule = job.rule;
         a.status = d_status + 2 * f;
         a.form = q.form, a.seg_bytes = q.seg_bytes, a.seg_cap = int(q.seg_cap), a.seg_lanes = jpeg_seg_lanes_;
         a.seg_stats = reinterpret_cast<long long*>(s + q.seg_stats.off);
@@ -1641,12 +1651,12 @@ void Engine::add_jpeg_clip_counters(int64_t out[4]) const {
     for (int i = 0; i < 4; ++i) out[i] += jpeg_clip_counts_[i];
 }
 
-int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status) {
+int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "clip_begin_jpeg: NULL argument");
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "clip_begin_jpeg: unknown channel order");
     JpegClipJob job;
-    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, job);      // (before a slot is taken)
+    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, rule, job);      // (before a slot is taken)
     bool one_size = true;
     for (int f = 1; f < nframes; ++f) one_size = one_size && job.info[f].h == job.info[0].h && job.info[f].w == job.info[0].w;
     WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
@@ -1688,11 +1698,11 @@ int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int
 }
 
 void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
-                                 int32_t* status, int entropy, int seg_bytes) {
+                                 int32_t* status, int entropy, int seg_bytes, int rule) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr && dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_clip: NULL argument");
     JpegClipJob job;
-    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, job);
+    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, rule, job);
     // every plane of every destination on the device at the caller's pitch and at the caller's address modulo 16, between two guard
     // zones and over a sentinel, so that a store outside the rows' bytes -- into a neighbouring frame as well -- is seen
     struct Plane {
@@ -1705,7 +1715,7 @@ void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size
     size_t total = 0;
     for (int f = 0; f < nframes; ++f) {
         const std::string who = "op_jpeg_decode_clip: frame " + std::to_string(f);
-        const char* bad = jpeg_dec_check_dst(job.info[f], &dst[f], channel_order);
+        const char* bad = jpeg_dec_check_dst(job.info[f], &dst[f], channel_order, job.rule);
         WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, who + ": " + (bad ? bad : ""));
         WHENET_REQUIRE(dst[f].on_device == 0, WHENET_EINVAL, who + ": the surface must be host memory (on_device = 0)");
         check_surface(who.c_str(), dst[f], job.info[f].h, job.info[f].w);

@@ -20,6 +20,11 @@
 //                                   (x >> (hs - 1), y >> (vs - 1)), 12 bytes out with the head / funnel-shift / tail stores of yuv.hip.
 //                                   A tight BGR destination of a 4:2:0 stream goes through yuv.hip's own plane kernel instead.
 //   whenet_jpeg_dec_yuv_kernel      4:2:0 planes -> an I420 or NV12 surface (a copy).
+// RULE 1 (libjpeg's bytes; the header's JPEG DECODER, RULE 1) has its own forms of two of them, the rule fixed at compile time:
+//   whenet_jpeg_dec_idct_libjpeg_kernel   the same mapping, jidctint's two passes (the row pass in int64), the same status words.
+//   whenet_jpeg_dec_frame_libjpeg_kernel  the same 4 pixels per lane and the same stores; chroma by fancy upsampling from the lane's two
+//                                   columns, the two neighbour columns and one vertical neighbour row, every index clamped to the
+//                                   real plane, then jdcolor's row.  Every packed frame of rule 1 takes it, the tight 4:2:0 BGR one too.
 #include <algorithm>
 #include <string>
 
@@ -130,6 +135,8 @@ __device__ __forceinline__ void entropy_body(const JpegDecArgs& a, int bx) {
     if (!jpeg_dec_interval(a.data, a.nbytes, a.start[i], s_t, a.g, int(i), a.coef, 0, s_block[tid])) atomicMin(&a.meta[1], int(i));
 }
 
+// RULE: the decode rule, fixed at compile time (0: the project's own passes, 1: jidctint's, whose row pass is 64-bit)
+template <int RULE>
 __device__ __forceinline__ void idct_body(const JpegDecArgs& a, int bx) {
     __shared__ int s_r[IDCT_BLOCKS][8][9];
     const int tid = int(threadIdx.x), lb = tid >> 3, l = tid & 7;
@@ -141,9 +148,10 @@ __device__ __forceinline__ void idct_body(const JpegDecArgs& a, int bx) {
         int col[8], o[8];
 #pragma unroll
         for (int v = 0; v < 8; ++v) col[v] = c[v * 8 + l];
-        jpeg_idct8(col, o);
+        if constexpr (RULE == JPEG_RULE_LIBJPEG) jpeg_idct8_islow<int>(col, o);
+        else jpeg_idct8(col, o);
 #pragma unroll
-        for (int y = 0; y < 8; ++y) s_r[lb][y][l] = jpeg_idct_round(o[y]);
+        for (int y = 0; y < 8; ++y) s_r[lb][y][l] = RULE == JPEG_RULE_LIBJPEG ? jpeg_islow_round1(o[y]) : jpeg_idct_round(o[y]);
     }
     __syncthreads();
     if (bx == 0 && tid == 0) {      // (the entropy kernel has ended: a kernel boundary lies between)
@@ -152,22 +160,61 @@ __device__ __forceinline__ void idct_body(const JpegDecArgs& a, int bx) {
         a.status[1] = bad == JPEG_DEC_NO_BAD ? -1 : bad;
     }
     if (!live) return;
-    int row[8], b[8];
+    uint32_t lo = 0, hi = 0;
+    if constexpr (RULE == JPEG_RULE_LIBJPEG) {
+        long long row[8], b[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) row[u] = s_r[lb][l][u];
-    jpeg_idct8(row, b);
+        for (int u = 0; u < 8; ++u) row[u] = s_r[lb][l][u];
+        jpeg_idct8_islow<long long>(row, b);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) lo |= uint32_t(jpeg_islow_sample(b[x])) << (8 * x), hi |= uint32_t(jpeg_islow_sample(b[x + 4])) << (8 * x);
+    } else {
+        int row[8], b[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) row[u] = s_r[lb][l][u];
+        jpeg_idct8(row, b);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) lo |= uint32_t(jpeg_idct_sample(b[x])) << (8 * x), hi |= uint32_t(jpeg_idct_sample(b[x + 4])) << (8 * x);
+    }
     const long long m = g / a.g.bpm;
     int comp, y0, x0;
     jpeg_dec_block_origin(a.g, m, int(g - m * a.g.bpm), comp, y0, x0);
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) lo |= uint32_t(jpeg_idct_sample(b[x])) << (8 * x), hi |= uint32_t(jpeg_idct_sample(b[x + 4])) << (8 * x);
     // the planes are padded to whole MCUs and 8-byte aligned: the block's row lies inside its plane
     *reinterpret_cast<uint2*>(a.plane[comp] + size_t(y0 + l) * size_t(a.g.plane_pitch[comp]) + size_t(x0)) = make_uint2(lo, hi);
 }
 
 __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int shift_bits) {      // bits [shift, shift + 32) of hi:lo
     return uint32_t(((uint64_t(hi) << 32) | lo) >> shift_bits);
+}
+
+// the 1..4 packed pixels px of a lane's group to dp: 12 bytes as dwords where the group is whole (a head and a tail of bytes where dp
+// is not aligned), else the 3, 6 or 9 bytes the row still has -- never a byte behind the row
+__device__ __forceinline__ void store_group(uint8_t* dp, const uint32_t px[4], int n) {
+    const uint32_t w0 = px[0] | (px[1] << 24), w1 = (px[1] >> 8) | (px[2] << 16), w2 = (px[2] >> 16) | (px[3] << 8);
+    if (n == 4) {
+        const int al = int(reinterpret_cast<uintptr_t>(dp) & 3);
+        if (al == 0) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(dp);
+            d[0] = w0, d[1] = w1, d[2] = w2;
+        } else {
+            const int head = 4 - al;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < head) dp[j] = uint8_t(w0 >> (8 * j));
+            uint32_t* d = reinterpret_cast<uint32_t*>(dp + head);
+            d[0] = funnel(w0, w1, 8 * head), d[1] = funnel(w1, w2, 8 * head);
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < al) dp[12 - al + j] = uint8_t(w2 >> (8 * (head + j)));
+        }
+    } else {
+        const int nb = 3 * n;                       // 3, 6 or 9 bytes: the row ends here, the bytes behind it are not the frame's
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const uint32_t word = j < 4 ? w0 : (j < 8 ? w1 : w2);
+            if (j < nb) dp[j] = uint8_t(word >> (8 * (j & 3)));
+        }
+    }
 }
 
 __device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
@@ -198,32 +245,65 @@ __device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
         if (a.g.comps == 3) jpeg_dec_pixel(yy, int((u4 >> (8 * (j >> hsh))) & 255u), int((v4 >> (8 * (j >> hsh))) & 255u), b, g, r);
         px[j] = (uint32_t(r) << rsh) | (uint32_t(g) << 8) | (uint32_t(b) << (16 - rsh));
     }
-    const uint32_t w0 = px[0] | (px[1] << 24), w1 = (px[1] >> 8) | (px[2] << 16), w2 = (px[2] >> 16) | (px[3] << 8);
-    uint8_t* dp = a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x) * 3;
-    if (n == 4) {
-        const int al = int(reinterpret_cast<uintptr_t>(dp) & 3);
-        if (al == 0) {
-            uint32_t* d = reinterpret_cast<uint32_t*>(dp);
-            d[0] = w0, d[1] = w1, d[2] = w2;
+    store_group(a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x) * 3, px, n);
+}
+
+// Rule 1 (libjpeg): fancy upsampling and jdcolor's row.  A lane's 4 pixels lie over the chroma columns i and i + 1 (x = 2 i); it
+// needs those and the two neighbour columns i - 1 and i + 2, from its own chroma row and, for 4:2:0, the one vertical neighbour
+// (above for even y, below for odd y).  Every index is clamped to the REAL plane (ch x cw): what the padding holds never enters.
+__device__ __forceinline__ void frame_body_libjpeg(const JpegDecArgs& a, int bx) {
+    const int h = a.g.h, w = a.g.w, gw = (w + 3) >> 2;
+    const long long item = (long long)(bx) * THREADS + threadIdx.x;
+    const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
+    if (y >= h) return;
+    const int x = gx << 2;
+    const int n = min(4, w - x);
+    const uint32_t y4 = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
+    const int hsh = a.g.hs - 1, vsh = a.g.vs - 1;
+    const int ch = (h + a.g.vs - 1) >> vsh, cw = (w + a.g.hs - 1) >> hsh;
+    int uv[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // Cb, Cr of the 4 pixels
+    if (a.g.comps == 3) {
+        const int cr = y >> vsh;
+        if (hsh == 0) {                               // 4:4:4: the samples themselves (x + 3 lies inside the padded plane)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint32_t v = *reinterpret_cast<const uint32_t*>(a.plane[c + 1] + size_t(cr) * size_t(a.g.plane_pitch[c + 1]) + size_t(x));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) uv[c][j] = int((v >> (8 * j)) & 255u);
+            }
+        } else if (cw <= 2) {                         // libjpeg's own switch: replication, no vertical filter either
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint8_t* row = a.plane[c + 1] + size_t(cr) * size_t(a.g.plane_pitch[c + 1]);
+                const int s0 = row[0], s1 = row[cw - 1];      // x = 0: columns 0 and min(1, cw - 1)
+                uv[c][0] = uv[c][1] = s0, uv[c][2] = uv[c][3] = s1;
+            }
         } else {
-            const int head = 4 - al;
+            const bool v2 = vsh != 0;
+            const int cn = v2 ? min(max(cr + ((y & 1) ? 1 : -1), 0), ch - 1) : cr;
+            const int i = x >> 1;                     // < cw: x < w
+            const int cm = max(i - 1, 0), c1 = min(i + 1, cw - 1), c2 = min(i + 2, cw - 1);
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
-                if (j < head) dp[j] = uint8_t(w0 >> (8 * j));
-            uint32_t* d = reinterpret_cast<uint32_t*>(dp + head);
-            d[0] = funnel(w0, w1, 8 * head), d[1] = funnel(w1, w2, 8 * head);
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                if (j < al) dp[12 - al + j] = uint8_t(w2 >> (8 * (head + j)));
-        }
-    } else {
-        const int nb = 3 * n;                       // 3, 6 or 9 bytes: the row ends here, the bytes behind it are not the frame's
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const uint32_t word = j < 4 ? w0 : (j < 8 ? w1 : w2);
-            if (j < nb) dp[j] = uint8_t(word >> (8 * (j & 3)));
+            for (int c = 0; c < 2; ++c) {
+                const uint8_t* row = a.plane[c + 1] + size_t(cr) * size_t(a.g.plane_pitch[c + 1]);
+                const uint8_t* other = a.plane[c + 1] + size_t(cn) * size_t(a.g.plane_pitch[c + 1]);
+                const int sm = jpeg_fancy_col(row[cm], other[cm], v2), s0 = jpeg_fancy_col(row[i], other[i], v2);
+                const int s1 = jpeg_fancy_col(row[c1], other[c1], v2), s2 = jpeg_fancy_col(row[c2], other[c2], v2);
+                uv[c][0] = jpeg_fancy_up(s0, sm, false, v2), uv[c][1] = jpeg_fancy_up(s0, s1, true, v2);
+                uv[c][2] = jpeg_fancy_up(s1, s0, false, v2), uv[c][3] = jpeg_fancy_up(s1, s2, true, v2);
+            }
         }
     }
+    const int rsh = a.channel_order == WHENET_BGR ? 16 : 0;
+    uint32_t px[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int yy = int((y4 >> (8 * j)) & 255u);
+        int b = yy, g = yy, r = yy;
+        if (a.g.comps == 3) jpeg_ycc_pixel(yy, uv[0][j], uv[1][j], b, g, r);
+        px[j] = (uint32_t(r) << rsh) | (uint32_t(g) << 8) | (uint32_t(b) << (16 - rsh));
+    }
+    store_group(a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x) * 3, px, n);
 }
 
 // up to 4 bytes of `word` to dp: one dword where all four are the row's and dp is aligned
@@ -269,8 +349,11 @@ __device__ __forceinline__ void yuv_body(const JpegDecArgs& a, int bx) {
 // ---- the single-stream kernels: the record by value, the grid that stream's ----
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_scan_kernel(JpegDecArgs a) { scan_body(a); }
 __global__ __launch_bounds__(ENT_THREADS) void whenet_jpeg_dec_entropy_kernel(JpegDecArgs a) { entropy_body(a, int(blockIdx.x)); }
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecArgs a) { idct_body(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecArgs a) { idct_body<JPEG_RULE_OWN>(a, int(blockIdx.x)); }
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_kernel(JpegDecArgs a) { frame_body(a, int(blockIdx.x)); }
+// rule 1 (libjpeg): the same mappings, its arithmetic
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_libjpeg_kernel(JpegDecArgs a) { idct_body<JPEG_RULE_LIBJPEG>(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_libjpeg_kernel(JpegDecArgs a) { frame_body_libjpeg(a, int(blockIdx.x)); }
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArgs a) { yuv_body(a, int(blockIdx.x)); }
 
 // ---- the clip kernels: up to 16 records in device memory (recs), the frames' workgroups back to back in one grid.  A workgroup
@@ -281,7 +364,7 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArg
 // The record is read where it lies (a reference, not a copy: a copy whose address the non-inlined decode functions take went to
 // 296 bytes of scratch per lane).  Resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), VGPRs of
 // the clip form / of the single-stream form, no scratch in either, the same LDS: scan 44 / 44, entropy 47 / 48, idct 47 / 47,
-// frame 18 / 18, yuv 14 / 14; SGPRs grow by up to 21 (the prefix sums and the record's address).
+// frame 18 / 18, yuv 14 / 14; SGPRs grow by up to 21 (the prefix sums and the record's address).  Rule 1: idct 36 / 36, frame 38 / 38.
 #define WHENET_JPEG_CLIP_KERNEL(name, threads, call)                                                                       \
     __global__ __launch_bounds__(threads) void name(const void* __restrict__ recs, JpegClipGrid grid) {                    \
         const int b = int(blockIdx.x);                                                                                     \
@@ -294,8 +377,10 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArg
     }
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_scan_kernel, THREADS, scan_body(a))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_entropy_kernel, ENT_THREADS, entropy_body(a, bx))
-WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_idct_kernel, THREADS, idct_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_idct_kernel, THREADS, idct_body<JPEG_RULE_OWN>(a, bx))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_kernel, THREADS, frame_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_idct_libjpeg_kernel, THREADS, idct_body<JPEG_RULE_LIBJPEG>(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_libjpeg_kernel, THREADS, frame_body_libjpeg(a, bx))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_yuv_kernel, THREADS, yuv_body(a, bx))
 #undef WHENET_JPEG_CLIP_KERNEL
 
@@ -323,16 +408,19 @@ void check_jpeg_dec_args(const JpegDecArgs& a) {
     WHENET_REQUIRE(a.format != WHENET_SURF_PACKED || a.channel_order == WHENET_RGB || a.channel_order == WHENET_BGR, WHENET_EINVAL,
                    "jpeg_decode: unknown channel order");
     WHENET_REQUIRE(a.form == 0 || a.form == 1, WHENET_EINVAL, "jpeg_decode: the entropy form must be 0 or 1");
+    WHENET_REQUIRE(jpeg_rule_ok(a.rule) && (a.rule == JPEG_RULE_OWN || a.format == WHENET_SURF_PACKED), WHENET_EINVAL,
+                   "jpeg_decode: the rule must be 0 or 1, and rule 1 (libjpeg) decodes to WHENET_SURF_PACKED only");
     if (a.form == 1)
         WHENET_REQUIRE(jpeg_seg_bytes_ok(a.seg_bytes) && (long long)(a.seg_cap) == jpeg_seg_bound(a.nbytes, g.intervals, a.seg_bytes) &&
                            a.seg_stats != nullptr && a.first_seg != nullptr && a.seg_exit != nullptr && a.seg_count != nullptr && a.seg_blk != nullptr,
                        WHENET_EINVAL, "jpeg_decode: the work buffers are not those of the segmented form of this stream");
 }
 
-// the colour path of a stream: 0 the plane kernel of the YUV ingest (a tight BGR frame of a 4:2:0 stream), 1 the frame kernel, 2 the
-// I420 / NV12 copy
+// the colour path of a stream: 0 the plane kernel of the YUV ingest (a tight BGR frame of a 4:2:0 stream under rule 0), 1 the frame
+// kernel of the stream's rule, 2 the I420 / NV12 copy
 int colour_path(const JpegDecArgs& a) {
     if (a.format != WHENET_SURF_PACKED) return 2;
+    if (a.rule == JPEG_RULE_LIBJPEG) return 1;
     return a.g.comps == 3 && a.g.hs == 2 && a.g.vs == 2 && a.channel_order == WHENET_BGR && a.dst_pitch[0] == 3 * a.g.w ? 0 : 1;
 }
 
@@ -369,7 +457,7 @@ JpegDecScratch::JpegDecScratch(const JpegDecGeom& g, size_t data_bytes, long lon
 }
 
 JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
-                          const whenet_surface_t& dst, int channel_order, int32_t* d_status) {
+                          const whenet_surface_t& dst, int channel_order, int32_t* d_status, int rule) {
     JpegDecArgs a{};
     char* const s = static_cast<char*>(d_scratch);
     a.g = g;
@@ -381,7 +469,7 @@ JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecSc
         a.plane[c] = reinterpret_cast<uint8_t*>(s + lay.plane[c]);
         a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
     }
-    a.format = dst.format, a.channel_order = channel_order;
+    a.format = dst.format, a.channel_order = channel_order, a.rule = rule;
     a.status = d_status;
     a.form = lay.form, a.seg_bytes = lay.seg_bytes, a.seg_cap = int(lay.seg_cap), a.seg_lanes = lay.seg_lanes;
     a.seg_stats = reinterpret_cast<long long*>(s + lay.seg_stats);
@@ -413,10 +501,11 @@ void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStre
     }
     WHENET_HIP_CHECK(hipGetLastError());
     const long long nblocks = (long long)(g.mcu_cols) * g.mcu_rows * g.bpm;
-    hipLaunchKernelGGL(whenet_jpeg_dec_idct_kernel, dim3(unsigned((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(THREADS), 0, stream, a);
+    hipLaunchKernelGGL(a.rule == JPEG_RULE_LIBJPEG ? whenet_jpeg_dec_idct_libjpeg_kernel : whenet_jpeg_dec_idct_kernel,
+                       dim3(unsigned((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(THREADS), 0, stream, a);
     WHENET_HIP_CHECK(hipGetLastError());
     if (a.format == WHENET_SURF_PACKED) {
-        if (g.comps == 3 && g.hs == 2 && g.vs == 2 && a.channel_order == WHENET_BGR && a.dst_pitch[0] == 3 * g.w) {
+        if (colour_path(a) == 0) {
             // a tight BGR frame of a 4:2:0 stream: the plane kernel of the YUV ingest, JFIF row
             YuvPlanes clip{};
             clip.frames = 1;
@@ -427,7 +516,8 @@ void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStre
             return;
         }
         const long long items = (long long)(g.h) * ((g.w + 3) >> 2);
-        hipLaunchKernelGGL(whenet_jpeg_dec_frame_kernel, dim3(unsigned((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a);
+        hipLaunchKernelGGL(a.rule == JPEG_RULE_LIBJPEG ? whenet_jpeg_dec_frame_libjpeg_kernel : whenet_jpeg_dec_frame_kernel,
+                           dim3(unsigned((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a);
     } else {
         const long long items = (long long)(g.h) * ((g.w + 3) >> 2) + (long long)((g.h + 1) >> 1) * ((((g.w + 1) >> 1) + 3) >> 2);
         hipLaunchKernelGGL(whenet_jpeg_dec_yuv_kernel, dim3(unsigned((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a);
@@ -446,6 +536,7 @@ void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int 
         const char *z0 = static_cast<const char*>(d_zero), *z1 = z0 + zero_bytes;
         const size_t coef_bytes = size_t(a.g.mcu_cols) * size_t(a.g.mcu_rows) * size_t(a.g.bpm) * 128;
         const auto zeroed = [&](const void* p, size_t n) { return static_cast<const char*>(p) >= z0 && static_cast<const char*>(p) + n <= z1; };
+        WHENET_REQUIRE(a.rule == h_recs[0].rule, WHENET_EINVAL, "jpeg_decode_clip: the frames of a clip are decoded by one rule");
         WHENET_REQUIRE(zeroed(a.start, size_t(a.g.intervals) * 4) && zeroed(a.meta, 8) && zeroed(a.seg_stats, 64) && zeroed(a.coef, coef_bytes),
                        WHENET_EINVAL, "jpeg_decode_clip: frame " + std::to_string(f) + ": its zeroed regions lie outside the clip's");
     }
@@ -465,7 +556,10 @@ void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int 
     launch_jpeg_decode_segmented_clip(h_recs, d_recs, frames, stream, &n);
     jpeg_clip_grid(h_recs, frames,
               [](const JpegDecArgs& a) { return ((long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm + IDCT_BLOCKS - 1) / IDCT_BLOCKS; }, grid);
-    launch(whenet_jpeg_dec_clip_idct_kernel, THREADS);
+    // (one rule per clip: its idct and frame kernels stand for rule 0's, the number of launches does not grow)
+    const bool libjpeg = h_recs[0].rule == JPEG_RULE_LIBJPEG;
+    if (libjpeg) launch(whenet_jpeg_dec_clip_idct_libjpeg_kernel, THREADS);
+    else launch(whenet_jpeg_dec_clip_idct_kernel, THREADS);
     // the colour stage: each of the three paths once, for the frames that take it
     YuvPlanes tight{};
     uintptr_t base = ~uintptr_t(0);
@@ -482,7 +576,7 @@ void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int 
     if (tight.frames > 0) launch_yuv_planes_to_bgr(reinterpret_cast<uint8_t*>(base), tight, stream), ++n;
     if (jpeg_clip_grid(h_recs, frames,
                   [](const JpegDecArgs& a) { return colour_path(a) == 1 ? ((long long)(a.g.h) * ((a.g.w + 3) >> 2) + THREADS - 1) / THREADS : 0; }, grid))
-        launch(whenet_jpeg_dec_clip_frame_kernel, THREADS);
+        libjpeg ? launch(whenet_jpeg_dec_clip_frame_libjpeg_kernel, THREADS) : launch(whenet_jpeg_dec_clip_frame_kernel, THREADS);
     if (jpeg_clip_grid(h_recs, frames,
                   [](const JpegDecArgs& a) {
                       const long long items = (long long)(a.g.h) * ((a.g.w + 3) >> 2) + (long long)((a.g.h + 1) >> 1) * ((((a.g.w + 1) >> 1) + 3) >> 2);

@@ -1,7 +1,8 @@
 // The baseline JPEG decoder as arithmetic, shared by the host statement (whenet_jpeg_parse, whenet_jpeg_decode_host,
 // whenet_jpeg_decode_planes_host) and the kernels of jpeg_dec.hip: the marker parser, the decode tables of a DHT, the bit reader,
 // the Huffman decode of a block, the inverse DCT and the planes -> pixel rule, each exactly as include/whenet_hip.h states it
-// (JPEG DECODER).  Integers only.  Nothing here needs the HIP runtime: a plain C++17 compiler builds this header
+// (JPEG DECODER), and for rule 1 (libjpeg's bytes) jidctint's pass, the fancy upsampling and jdcolor's row (JPEG DECODER, RULE 1).
+// Integers only.  Nothing here needs the HIP runtime: a plain C++17 compiler builds this header
 // (tools/jpeg_dec_host_check.cpp does, under the host sanitizers).
 //
 // Reference: demo.py (`cv2.imread` of Sample/*.jpeg) and demo_video.py:49-53 (`cap.read()`: for a camera or an MJPG file a
@@ -418,6 +419,82 @@ WHENET_HD inline void jpeg_dec_pixel(int y, int u, int v, int& b, int& g, int& r
     b = jpeg_dec_clamp((base + K[WHENET_YUV_JFIF][5] * d) >> 20, 0, 255);
 }
 
+// ---- rule 1: libjpeg's bytes (include/whenet_hip.h, JPEG DECODER, RULE 1) ----
+constexpr int JPEG_RULE_OWN = 0, JPEG_RULE_LIBJPEG = 1;
+inline bool jpeg_rule_ok(long long v) { return v == JPEG_RULE_OWN || v == JPEG_RULE_LIBJPEG; }
+
+// One 8-point pass of jidctint's inverse DCT (13 constant bits), exact integer arithmetic in T, outputs before the descale.  The
+// pass is linear: out[k] = sum_j C[j][k] in[j], and the columns of |C| sum to at most 61,214.  Pass 1 (|in| <= 2048): |out| <=
+// 1.26e8 and every intermediate below 3.5e8, T = int32.  Its descaled results are at most 61,214 in size, so pass 2 reaches
+// 61,214^2 = 3.75e9 > 2^31: T = int64 there, on the host and in the kernel alike.
+template <class T>
+WHENET_HD inline void jpeg_idct8_islow(const T i[8], T out[8]) {
+    T z1 = (i[2] + i[6]) * 4433;
+    const T t2 = z1 - i[6] * 15137, t3 = z1 + i[2] * 6270;
+    const T t0 = (i[0] + i[4]) * 8192, t1 = (i[0] - i[4]) * 8192;      // (<< 13 of a value that may be negative)
+    const T t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    T a0 = i[7], a1 = i[5], a2 = i[3], a3 = i[1];
+    z1 = a0 + a3;
+    T z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const T z5 = (z3 + z4) * 9633;
+    a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299;
+    z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4;
+    out[0] = t10 + a3, out[1] = t11 + a2, out[2] = t12 + a1, out[3] = t13 + a0;
+    out[4] = t13 - a0, out[5] = t12 - a1, out[6] = t11 - a2, out[7] = t10 - a3;
+}
+WHENET_HD inline int jpeg_islow_round1(int a) { return (a + 1024) >> 11; }
+WHENET_HD inline int jpeg_islow_sample(long long b) {
+    const long long v = ((b + 131072) >> 18) + 128;
+    return int(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// Fancy upsampling (jdsample.c).  A chroma column's value is the sample itself (4:2:2) or 3 x the row's + the vertical neighbour's
+// (4:2:0: v2); a pixel takes 3 x its own column + the horizontal neighbour's: the left one for even x, the right one for odd x.
+WHENET_HD inline int jpeg_fancy_col(int own_row, int other_row, bool v2) { return v2 ? 3 * own_row + other_row : own_row; }
+WHENET_HD inline int jpeg_fancy_up(int own, int other, bool odd, bool v2) {
+    return v2 ? (3 * own + other + (odd ? 7 : 8)) >> 4 : (3 * own + other + (odd ? 2 : 1)) >> 2;
+}
+// B, G, R of a pixel by jdcolor.c's tables: F(x) = int(x 65536 + 0.5)
+WHENET_HD inline void jpeg_ycc_pixel(int y, int u, int v, int& b, int& g, int& r) {
+    const int d = u - 128, e = v - 128;
+    r = jpeg_dec_clamp(y + ((91881 * e + 32768) >> 16), 0, 255);
+    b = jpeg_dec_clamp(y + ((116130 * d + 32768) >> 16), 0, 255);
+    g = jpeg_dec_clamp(y + ((-22554 * d + 32768 - 46802 * e) >> 16), 0, 255);
+}
+
+// a block's 64 records -> its 8 x 8 samples by the rule's two passes (the statement the idct kernels are held to)
+inline void jpeg_dec_block_samples(const int16_t* cf, int rule, uint8_t s[8][8]) {
+    if (rule == JPEG_RULE_LIBJPEG) {
+        int r[8][8];
+        for (int u = 0; u < 8; ++u) {
+            int col[8], a[8];
+            for (int v = 0; v < 8; ++v) col[v] = cf[v * 8 + u];
+            jpeg_idct8_islow<int>(col, a);
+            for (int y = 0; y < 8; ++y) r[y][u] = jpeg_islow_round1(a[y]);
+        }
+        for (int y = 0; y < 8; ++y) {
+            long long row[8], bb[8];
+            for (int u = 0; u < 8; ++u) row[u] = r[y][u];
+            jpeg_idct8_islow<long long>(row, bb);
+            for (int x = 0; x < 8; ++x) s[y][x] = uint8_t(jpeg_islow_sample(bb[x]));
+        }
+        return;
+    }
+    int r[8][8];
+    for (int u = 0; u < 8; ++u) {
+        int col[8], a[8];
+        for (int v = 0; v < 8; ++v) col[v] = cf[v * 8 + u];
+        jpeg_idct8(col, a);
+        for (int y = 0; y < 8; ++y) r[y][u] = jpeg_idct_round(a[y]);
+    }
+    for (int y = 0; y < 8; ++y) {
+        int bb[8];
+        jpeg_idct8(r[y], bb);
+        for (int x = 0; x < 8; ++x) s[y][x] = uint8_t(jpeg_idct_sample(bb[x]));
+    }
+}
+
 // ---- the host statement ----
 // The restart markers of the entropy data (0xFF 0xD0..0xD7 pairs, in order): start[i] = where interval i's bits begin, for every
 // interval that has a start; returns the first interval the markers make bad, or JPEG_DEC_NO_BAD: marker k must be RST(k mod 8)
@@ -444,7 +521,8 @@ struct JpegDecPlanes {
 };
 
 // entropy data -> the padded component planes; status[0] = WHENET_OK or WHENET_EFORMAT, status[1] = the first bad interval or -1
-inline void jpeg_dec_planes_host(const whenet_jpeg_info_t& in, const uint8_t* data, int size, JpegDecPlanes& out, int32_t status[2]) {
+inline void jpeg_dec_planes_host(const whenet_jpeg_info_t& in, const uint8_t* data, int size, JpegDecPlanes& out, int32_t status[2],
+                                 int rule = JPEG_RULE_OWN) {
     const JpegDecGeom g = jpeg_dec_geom(in);
     std::vector<JpegDecTables> tables(1);
     jpeg_dec_build_tables(in, tables[0]);
@@ -465,20 +543,12 @@ inline void jpeg_dec_planes_host(const whenet_jpeg_info_t& in, const uint8_t* da
         for (long long m = 0; m < count; ++m)
             for (int b = 0; b < g.bpm; ++b) {
                 const int16_t* cf = coef.data() + (size_t(m) * size_t(g.bpm) + size_t(b)) * 64;
-                int comp, y0, x0, r[8][8];
+                int comp, y0, x0;
+                uint8_t smp[8][8];
                 jpeg_dec_block_origin(g, first + m, b, comp, y0, x0);
-                for (int u = 0; u < 8; ++u) {
-                    int col[8], a[8];
-                    for (int v = 0; v < 8; ++v) col[v] = cf[v * 8 + u];
-                    jpeg_idct8(col, a);
-                    for (int y = 0; y < 8; ++y) r[y][u] = jpeg_idct_round(a[y]);
-                }
+                jpeg_dec_block_samples(cf, rule, smp);
                 uint8_t* dst = out.plane[comp].data() + size_t(y0) * size_t(g.plane_pitch[comp]) + size_t(x0);
-                for (int y = 0; y < 8; ++y) {
-                    int bb[8];
-                    jpeg_idct8(r[y], bb);
-                    for (int x = 0; x < 8; ++x) dst[size_t(y) * size_t(g.plane_pitch[comp]) + size_t(x)] = uint8_t(jpeg_idct_sample(bb[x]));
-                }
+                for (int y = 0; y < 8; ++y) std::memcpy(dst + size_t(y) * size_t(g.plane_pitch[comp]), smp[y], 8);
             }
     }
     status[0] = bad == JPEG_DEC_NO_BAD ? WHENET_OK : WHENET_EFORMAT;
@@ -486,14 +556,16 @@ inline void jpeg_dec_planes_host(const whenet_jpeg_info_t& in, const uint8_t* da
 }
 
 // Argument errors of a decode destination, as a text (nullptr: none)
-inline const char* jpeg_dec_check_dst(const whenet_jpeg_info_t& in, const whenet_surface_t* dst, int channel_order) {
+inline const char* jpeg_dec_check_dst(const whenet_jpeg_info_t& in, const whenet_surface_t* dst, int channel_order, int rule = JPEG_RULE_OWN) {
     if (dst == nullptr) return "NULL argument";
+    if (!jpeg_rule_ok(rule)) return "the rule must be 0 (the project's own) or 1 (libjpeg)";
     int rows[3], row_bytes[3];
     const int planes = overlay_surface_planes(dst->format, in.h, in.w, rows, row_bytes);
     if (planes == 0) return "unknown surface format (WHENET_SURF_PACKED, WHENET_YUV_NV12 or WHENET_YUV_I420)";
     if (dst->format == WHENET_SURF_PACKED) {
         if (channel_order != WHENET_RGB && channel_order != WHENET_BGR) return "unknown channel order";
     } else {
+        if (rule == JPEG_RULE_LIBJPEG) return "rule 1 (libjpeg) decodes to WHENET_SURF_PACKED only";
         if (in.components != 3 || in.hs != 2 || in.vs != 2) return "only a 4:2:0 stream decodes into an I420 or NV12 surface";
         if (dst->matrix != WHENET_YUV_JFIF) return "a YUV destination must have the matrix WHENET_YUV_JFIF (JFIF is full-range BT.601)";
     }
@@ -505,8 +577,41 @@ inline const char* jpeg_dec_check_dst(const whenet_jpeg_info_t& in, const whenet
 }
 
 // the padded planes -> the destination surface (host memory)
-inline void jpeg_dec_frame_host(const JpegDecGeom& g, const JpegDecPlanes& pl, const whenet_surface_t& dst, int channel_order) {
+// (rule 1: a packed destination only, jpeg_dec_check_dst; the chroma planes' rows >= ch and columns >= cw are never read)
+inline void jpeg_dec_frame_host(const JpegDecGeom& g, const JpegDecPlanes& pl, const whenet_surface_t& dst, int channel_order,
+                                int rule = JPEG_RULE_OWN) {
     const int hsh = g.hs - 1, vsh = g.vs - 1;
+    if (dst.format == WHENET_SURF_PACKED && rule == JPEG_RULE_LIBJPEG) {
+        const int ri = channel_order == WHENET_BGR ? 2 : 0;
+        const int ch = (g.h + g.vs - 1) / g.vs, cw = (g.w + g.hs - 1) / g.hs;
+        const bool fancy = g.comps == 3 && g.hs == 2 && cw > 2, v2 = g.vs == 2;
+        for (int y = 0; y < g.h; ++y) {
+            uint8_t* o = static_cast<uint8_t*>(dst.plane[0]) + size_t(y) * size_t(dst.pitch[0]);
+            const uint8_t* yr = pl.plane[0].data() + size_t(y) * size_t(g.plane_pitch[0]);
+            const int cr = y >> vsh, cn = v2 ? jpeg_dec_clamp(cr + ((y & 1) ? 1 : -1), 0, ch - 1) : cr;
+            for (int x = 0; x < g.w; ++x) {
+                int b, gg, r;
+                if (g.comps == 1) {
+                    b = gg = r = yr[x];
+                } else {
+                    int uv[2];
+                    for (int c = 1; c < 3; ++c) {
+                        const uint8_t* row = pl.plane[c].data() + size_t(cr) * size_t(g.plane_pitch[c]);
+                        const uint8_t* other = pl.plane[c].data() + size_t(cn) * size_t(g.plane_pitch[c]);
+                        if (fancy) {
+                            const int i = x >> 1, n = jpeg_dec_clamp(i + ((x & 1) ? 1 : -1), 0, cw - 1);
+                            uv[c - 1] = jpeg_fancy_up(jpeg_fancy_col(row[i], other[i], v2), jpeg_fancy_col(row[n], other[n], v2), (x & 1) != 0, v2);
+                        } else {
+                            uv[c - 1] = row[x >> hsh];
+                        }
+                    }
+                    jpeg_ycc_pixel(yr[x], uv[0], uv[1], b, gg, r);
+                }
+                o[3 * x + ri] = uint8_t(r), o[3 * x + 1] = uint8_t(gg), o[3 * x + 2 - ri] = uint8_t(b);
+            }
+        }
+        return;
+    }
     if (dst.format == WHENET_SURF_PACKED) {
         const int ri = channel_order == WHENET_BGR ? 2 : 0;
         for (int y = 0; y < g.h; ++y) {

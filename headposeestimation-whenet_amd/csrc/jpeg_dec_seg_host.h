@@ -390,26 +390,18 @@ inline int jpeg_dec_coef_seg_host(const JpegDecGeom& g, const JpegDecTables& t, 
 }
 
 // one block's records -> its 8 x 8 samples on its component's plane (the two passes as jpeg_dec_planes_host runs them)
-inline void jpeg_dec_block_to_plane(const JpegDecGeom& g, const int16_t* cf, long long m, int b, JpegDecPlanes& out) {
-    int comp, y0, x0, r[8][8];
+inline void jpeg_dec_block_to_plane(const JpegDecGeom& g, const int16_t* cf, long long m, int b, JpegDecPlanes& out, int rule = JPEG_RULE_OWN) {
+    int comp, y0, x0;
+    uint8_t smp[8][8];
     jpeg_dec_block_origin(g, m, b, comp, y0, x0);
-    for (int u = 0; u < 8; ++u) {
-        int col[8], a[8];
-        for (int v = 0; v < 8; ++v) col[v] = cf[v * 8 + u];
-        jpeg_idct8(col, a);
-        for (int y = 0; y < 8; ++y) r[y][u] = jpeg_idct_round(a[y]);
-    }
+    jpeg_dec_block_samples(cf, rule, smp);
     uint8_t* dst = out.plane[comp].data() + size_t(y0) * size_t(g.plane_pitch[comp]) + size_t(x0);
-    for (int y = 0; y < 8; ++y) {
-        int bb[8];
-        jpeg_idct8(r[y], bb);
-        for (int x = 0; x < 8; ++x) dst[size_t(y) * size_t(g.plane_pitch[comp]) + size_t(x)] = uint8_t(jpeg_idct_sample(bb[x]));
-    }
+    for (int y = 0; y < 8; ++y) std::memcpy(dst + size_t(y) * size_t(g.plane_pitch[comp]), smp[y], 8);
 }
 
 // entropy data -> the padded component planes, the entropy stage in the segmented form: what jpeg_dec_planes_host gives
 inline void jpeg_dec_planes_seg_host(const whenet_jpeg_info_t& in, const uint8_t* data, int size, int seg_bytes, int window, JpegDecPlanes& out,
-                                     int32_t status[2], int64_t stats[8]) {
+                                     int32_t status[2], int64_t stats[8], int rule = JPEG_RULE_OWN) {
     const JpegDecGeom g = jpeg_dec_geom(in);
     std::vector<JpegDecTables> tables(1);
     jpeg_dec_build_tables(in, tables[0]);
@@ -418,7 +410,7 @@ inline void jpeg_dec_planes_seg_host(const whenet_jpeg_info_t& in, const uint8_t
     for (int c = 0; c < g.comps; ++c) out.plane[c].assign(size_t(g.plane_pitch[c]) * size_t(g.plane_rows[c]), 0);
     const long long mcus = (long long)(g.mcu_cols) * g.mcu_rows;
     for (long long m = 0; m < mcus; ++m)
-        for (int b = 0; b < g.bpm; ++b) jpeg_dec_block_to_plane(g, coef.data() + (size_t(m) * size_t(g.bpm) + size_t(b)) * 64, m, b, out);
+        for (int b = 0; b < g.bpm; ++b) jpeg_dec_block_to_plane(g, coef.data() + (size_t(m) * size_t(g.bpm) + size_t(b)) * 64, m, b, out, rule);
     status[0] = bad == JPEG_DEC_NO_BAD ? WHENET_OK : WHENET_EFORMAT;
     status[1] = bad == JPEG_DEC_NO_BAD ? -1 : bad;
 }

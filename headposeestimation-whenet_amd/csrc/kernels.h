@@ -674,6 +674,7 @@ void launch_jpeg_flush(const void* d_stream, void* to, const long long* d_size, 
 //   idct     8 lanes per block: both passes -> the component planes (padded to whole MCUs, pitches multiples of 8); status[0..1]
 //   frame    planes -> the destination: packed pixels in either channel order at any pitch (a tight BGR frame of a 4:2:0 stream:
 //            launch_yuv_planes_to_bgr), or an I420 / NV12 surface for a 4:2:0 stream.  No thread stores outside the rows' bytes.
+// JpegDecArgs::rule = 1 (libjpeg's bytes, packed destinations only) runs the rule-1 forms of idct and frame in their places.
 // JpegDecScratch lays the work buffers out in one allocation; tables | data at its front are what a caller uploads in one copy
 // (data_bytes = 0: the data lies elsewhere).
 // The entropy stage has a second form (jpeg_dec_seg.hip; the arithmetic is jpeg_dec_seg_host.h's): form = 1 decodes every interval
@@ -706,6 +707,7 @@ struct JpegDecArgs {
     uint8_t* dst[3];
     int dst_pitch[3];
     int format, channel_order;
+    int rule;                      // 0: the project's own inverse DCT and pixel rule, 1: libjpeg's (packed destinations only)
     int32_t* status;               // two int32
     // the segmented form (form = 1)
     int form, seg_bytes, seg_cap;
@@ -719,7 +721,7 @@ struct JpegDecArgs {
 // the segmented form's launches (jpeg_dec_seg.hip), behind the scan kernel and in front of the inverse DCT
 void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream);
 JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
-                          const whenet_surface_t& dst, int channel_order, int32_t* d_status);
+                          const whenet_surface_t& dst, int channel_order, int32_t* d_status, int rule = JPEG_RULE_OWN);
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream);
 // A CLIP of 1..16 streams, every stage in ONE launch for all of them: the same bodies, a workgroup first finds its frame in the
 // prefix sums of the per-frame workgroup counts (JpegClipGrid, by value) and reads that frame's record from d_recs -- device

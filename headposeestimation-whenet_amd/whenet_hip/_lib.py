@@ -151,6 +151,12 @@ _PROTOS = {
     "whenet_op_jpeg_decode_clip": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int]),
     "whenet_jpeg_clip_plan": (C.c_int, [C.POINTER(JpegInfoC), _P, C.c_int, C.c_int, C.c_int, _P]),
     "whenet_jpeg_clip_counters": (C.c_int, [_P, C.POINTER(C.c_int64 * 4)]),
+    "whenet_jpeg_decode_rule_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, _P]),
+    "whenet_jpeg_decode_segmented_rule_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_op_jpeg_decode_rule": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_op_jpeg_decode_clip_rule": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int, C.c_int]),
+    "whenet_frame_begin_jpeg_rule": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
+    "whenet_clip_begin_jpeg_rule": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -656,6 +662,44 @@ def jpeg_decode_segmented_planes_host(data, planes: list, seg_bytes: int, window
     pitch = np.array([int(p.strides[0]) if p.shape[0] > 1 else int(p.shape[1]) for p in planes] + [0] * (3 - len(planes)), np.int32)
     rc = lib.whenet_jpeg_decode_segmented_planes_host(_ptr(a) if a.size else None, int(a.size), ptrs, _ptr(pitch), int(seg_bytes), int(window),
                                                       _ptr(status), _ptr(stats))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status, stats
+
+
+JPEG_RULE = {"own": 0, "libjpeg": 1}      # the decode rule: the project's own (default), or libjpeg's bytes (option "jpeg_rule")
+
+
+def jpeg_rule_code(rule) -> int:
+    """"own" -> 0, "libjpeg" -> 1, None -> -1 (the handle's option "jpeg_rule")."""
+    if rule is None:
+        return -1
+    if rule not in JPEG_RULE:
+        raise ValueError("rule must be 'own' or 'libjpeg'")
+    return JPEG_RULE[rule]
+
+
+def jpeg_decode_rule_host(data, surface: SurfaceC, bgr: bool, rule: str = "own") -> np.ndarray:
+    """`whenet_jpeg_decode_rule_host` into a packed host surface: `jpeg_decode_host` by the rule "own" or "libjpeg"; the two status
+    words."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    rc = lib.whenet_jpeg_decode_rule_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB,
+                                          jpeg_rule_code(rule), _ptr(status))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status
+
+
+def jpeg_decode_segmented_rule_host(data, surface: SurfaceC, bgr: bool, seg_bytes: int, window: int, rule: str = "own"):
+    """`whenet_jpeg_decode_segmented_rule_host`: `jpeg_decode_segmented_host` by the rule "own" or "libjpeg": (status, statistics)."""
+    lib = load()
+    a = _stream_array(data)
+    status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+    rc = lib.whenet_jpeg_decode_segmented_rule_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB,
+                                                    int(seg_bytes), int(window), jpeg_rule_code(rule),
+                                                    _ptr(status), _ptr(stats))
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return status, stats
@@ -1372,6 +1416,16 @@ class Handle:
                                                        BGR if bgr else RGB, int(entropy), int(seg_bytes), _ptr(status), _ptr(stats)))
         return status, stats
 
+    def op_jpeg_decode_rule(self, data, surface: SurfaceC, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None):
+        """`whenet_op_jpeg_decode_rule`: the decoder's kernels alone by the rule "own", "libjpeg" or None (the handle's option
+        "jpeg_rule"); entropy -1 (the handle's options), 0 or 1: (the two status words, the statistics int64 [8])."""
+        a = _stream_array(data)
+        status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+        self._check(self._lib.whenet_op_jpeg_decode_rule(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
+                                                         BGR if bgr else RGB, int(entropy), int(seg_bytes), jpeg_rule_code(rule),
+                                                         _ptr(status), _ptr(stats)))
+        return status, stats
+
     def jpeg_decode_counters(self) -> dict:
         """Host-side counts of the JPEG decodes the handle's engines launched in each form of the entropy stage:
         {"interval": form 0, "segmented": form 1} (options "jpeg_entropy", "jpeg_seg_bytes")."""
@@ -1385,24 +1439,34 @@ class Handle:
         self._check(self._lib.whenet_jpeg_decode_device(self._h, C.byref(info), _P(int(d_entropy)), int(nbytes), C.byref(surface),
                                                         BGR if bgr else RGB, _P(int(d_status)), _stream(stream)))
 
-    def frame_begin_jpeg(self, data, status: np.ndarray, bgr: bool = True) -> int:
+    def frame_begin_jpeg(self, data, status: np.ndarray, bgr: bool = True, rule=None) -> int:
         """`whenet_frame_begin_jpeg`: `frame_begin` from the bytes of a JPEG stream, decoded on the device.  status = int32 [2], complete
-        when the ticket's collect call returns; it must stay alive until then."""
+        when the ticket's collect call returns; it must stay alive until then.  rule: None (the handle's option "jpeg_rule"), or "own" /
+        "libjpeg" for this call (`whenet_frame_begin_jpeg_rule`)."""
         a = _stream_array(data)
         if status.dtype != np.int32 or status.size != 2 or not status.flags.c_contiguous:
             raise ValueError("status must be a contiguous int32 [2] array")
         t = C.c_int(-1)
+        if rule is not None:
+            self._check(self._lib.whenet_frame_begin_jpeg_rule(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB,
+                                                               jpeg_rule_code(rule), C.byref(t), _ptr(status)))
+            return t.value
         self._check(self._lib.whenet_frame_begin_jpeg(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB, C.byref(t),
                                                       _ptr(status)))
         return t.value
 
-    def clip_begin_jpeg(self, datas, status: np.ndarray, bgr: bool = True) -> int:
+    def clip_begin_jpeg(self, datas, status: np.ndarray, bgr: bool = True, rule=None) -> int:
         """`whenet_clip_begin_jpeg`: `clip_begin` / `clip_begin_mixed` from the bytes of 1..16 JPEG streams, decoded on the device in one
-        submission.  status = int32 [F,2], complete when the ticket's collect call returns; it must stay alive until then."""
+        submission.  status = int32 [F,2], complete when the ticket's collect call returns; it must stay alive until then.  rule: as
+        `frame_begin_jpeg` (`whenet_clip_begin_jpeg_rule`)."""
         arrs, ptrs, sizes = _clip_streams(datas)
         if status.dtype != np.int32 or status.size != 2 * len(arrs) or not status.flags.c_contiguous:
             raise ValueError("status must be a contiguous int32 [F,2] array")
         t = C.c_int(-1)
+        if rule is not None:
+            self._check(self._lib.whenet_clip_begin_jpeg_rule(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), BGR if bgr else RGB,
+                                                              jpeg_rule_code(rule), C.byref(t), _ptr(status) if status.size else None))
+            return t.value
         self._check(self._lib.whenet_clip_begin_jpeg(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), BGR if bgr else RGB,
                                                      C.byref(t), _ptr(status) if status.size else None))
         return t.value
@@ -1416,6 +1480,16 @@ class Handle:
         self._check(self._lib.whenet_op_jpeg_decode_clip(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
                                                          BGR if bgr else RGB, _ptr(status) if status.size else None, int(entropy),
                                                          int(seg_bytes)))
+        return status
+
+    def op_jpeg_decode_clip_rule(self, datas, surfaces, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None) -> np.ndarray:
+        """`whenet_op_jpeg_decode_clip_rule`: `op_jpeg_decode_clip` by the rule "own", "libjpeg" or None (the handle's option)."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        surf = (SurfaceC * max(len(surfaces), 1))(*surfaces)
+        status = np.zeros((len(arrs), 2), np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_clip_rule(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
+                                                              BGR if bgr else RGB, _ptr(status) if status.size else None, int(entropy),
+                                                              int(seg_bytes), jpeg_rule_code(rule)))
         return status
 
     def jpeg_clip_counters(self) -> dict:

@@ -284,18 +284,22 @@ class FramePipeline:
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
 
-    def begin_jpeg(self, data) -> "JpegStatus":
+    def begin_jpeg(self, data, rule=None) -> "JpegStatus":
         """`begin()` from the bytes of a baseline JPEG stream (a still, or one frame of an MJPG file: `whenet_hip.mjpeg.MJPGReader`):
         what stands for `cv2.imread` / `cap.read()`.  Only the compressed bytes cross the link; the frame is decoded on the device
         (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
         `begin(jpeg.decode_host(data, bgr=...))`.  A stream the decoder does not accept (progressive, arithmetic, 12 bit, ...) is a
         ValueError with the reason and takes no place.  Returns a `JpegStatus`, valid after the frame's `collect()`: damaged entropy
         data does not raise, it yields a defined frame and `ok == False`.  The entropy stage's form follows the handle's options
-        "jpeg_entropy" (0: an interval per lane, 1: segmented, 2: auto, the default) and "jpeg_seg_bytes"; the frame is the same."""
+        "jpeg_entropy" (0: an interval per lane, 1: segmented, 2: auto, the default) and "jpeg_seg_bytes"; the frame is the same.
+        The decode rule follows the handle's option "jpeg_rule" (0: the project's own, the default; 1: libjpeg's bytes, what
+        `cv2.imread` gives) unless `rule` says "own" or "libjpeg" for this frame; the frame is then what
+        `jpeg.decode_host(data, rule=...)` makes."""
         self._check_can_begin()
+        _lib.jpeg_rule_code(rule)
         info = _lib.jpeg_parse(data)
         st = JpegStatus()
-        ticket = self._h.frame_begin_jpeg(data, st._status, bgr=self._bgr)
+        ticket = self._h.frame_begin_jpeg(data, st._status, bgr=self._bgr, rule=rule)
         if self._jpeg is None:
             self._jpeg = {}
         self._jpeg.setdefault(ticket, []).append(st)
@@ -303,15 +307,16 @@ class FramePipeline:
         self._last_sizes = [(info.h, info.w)]
         return st
 
-    def begin_clip_jpeg(self, datas) -> list:
+    def begin_clip_jpeg(self, datas, rule=None) -> list:
         """A clip from the bytes of 1..16 baseline JPEG streams (consecutive frames of an MJPG file: `MJPGReader.clips(16)`), each
         with its own size, sampling, tables and DRI: one upload of the compressed bytes, every decoder stage in one launch for all
         frames.  Frame f is what `begin_jpeg(datas[f])` makes; frames of one size make a clip as `begin_clip()` makes it, frames of
         different sizes one as `begin_clip_mixed()` makes it (at most option "letterbox_cache" of them).  `detect_heads_clip()` and
         `collect_clip()` follow.  One stream the decoder does not accept is a ValueError that names the frame, and the clip takes no
         place.  Returns a `JpegStatus` per frame, valid after `collect_clip()`: a damaged stream does not raise, it yields its own
-        defined frame and `ok == False` and leaves the other frames untouched."""
+        defined frame and `ok == False` and leaves the other frames untouched.  `rule`: as `begin_jpeg`, one rule for the clip."""
         self._check_can_begin()
+        _lib.jpeg_rule_code(rule)
         datas = list(datas)
         if not 1 <= len(datas) <= _lib.MAX_CLIP_FRAMES:
             raise ValueError(f"a clip holds 1..{_lib.MAX_CLIP_FRAMES} frames, got {len(datas)}")
@@ -322,7 +327,7 @@ class FramePipeline:
             except ValueError as e:
                 raise ValueError(f"begin_clip_jpeg: frame {i}: {e}") from None
         block = np.zeros((len(datas), 2), np.int32)      # (one array for the library to write; every JpegStatus is a row of it)
-        ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr)
+        ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr, rule=rule)
         sts = []
         for f in range(len(datas)):
             st = JpegStatus()

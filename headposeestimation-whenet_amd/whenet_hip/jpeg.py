@@ -130,7 +130,8 @@ def _result(frame: np.ndarray, status: np.ndarray, strict: bool):
     return frame
 
 
-def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False):
+def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False,
+           rule: str = "own"):
     """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
     (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
     Damaged data raises `DecodeError` (strict=False: returns the defined frame).  `entropy`: the form of the entropy stage --
@@ -138,9 +139,12 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     interval by many lanes, `seg_bytes` of the data each: a power of two in 4..4096, None = 128) or "auto" (the handle's options
     "jpeg_entropy" / "jpeg_seg_bytes": by default segmented from 4096 bytes per interval on).  The frame is the same, bit for bit.
     stats=True: (frame, the statistics int64 [8] of `whenet_op_jpeg_decode_ex`); with "auto" the form is then chosen here by the
-    same rule."""
+    same rule.  `rule`: "own" (the project's inverse DCT, nearest chroma, JFIF row: the default) or "libjpeg" (the bytes of a
+    libjpeg-turbo decode with its defaults: what `cv2.imread` and Pillow give; `whenet_op_jpeg_decode_rule`).  "own" goes through
+    the calls that read the handle's option "jpeg_rule", whose default it is."""
     if entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be 'auto', 'interval' or 'segmented'")
+    _lib.jpeg_rule_code(rule)
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
     form, seg = _lib.JPEG_ENTROPY[entropy], 128 if seg_bytes is None else int(seg_bytes)
@@ -148,6 +152,8 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
         form = 1 if (int(_lib._stream_array(data).size) - i.data_offset) // max(i.intervals, 1) >= _lib.JPEG_SEG_AUTO_BYTES else 0
 
     def run(h):
+        if rule != "own":
+            return h.op_jpeg_decode_rule(data, packed_surface(frame), bgr, -1 if form == 2 else form, seg, rule)
         if form == 2:
             return h.op_jpeg_decode(data, packed_surface(frame), bgr), None
         return h.op_jpeg_decode_ex(data, packed_surface(frame), bgr, form, seg)
@@ -161,12 +167,13 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     return (out, st) if stats else out
 
 
-def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True):
+def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True, rule: str = "own"):
     """(frames, statuses) of 1..16 baseline JPEG streams decoded as ONE clip by the kernels (`whenet_op_jpeg_decode_clip`): a list of
     uint8 [H_f,W_f,3] frames and the status words int32 [F,2].  Frame f is `decode(datas[f])`, bit for bit.  `entropy`: None or
     "auto" (the handle's options, stream by stream), "interval" or "segmented" (`seg_bytes`: None = 128).  A stream the decoder does
     not accept is a ValueError that names the frame; a damaged one raises `DecodeError` with the frame's index in its text
-    (strict=False: its defined frame and status are returned with the others)."""
+    (strict=False: its defined frame and status are returned with the others).  `rule`: "own" or "libjpeg", as `decode`."""
+    _lib.jpeg_rule_code(rule)
     if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be None, 'auto', 'interval' or 'segmented'")
     datas = list(datas)
@@ -182,11 +189,16 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     form = -1 if entropy in (None, "auto") else _lib.JPEG_ENTROPY[entropy]
     seg = 128 if seg_bytes is None else int(seg_bytes)
     surfaces = [packed_surface(fr) for fr in frames]
+    def run(h):
+        if rule != "own":
+            return h.op_jpeg_decode_clip_rule(datas, surfaces, bgr, form, seg, rule)
+        return h.op_jpeg_decode_clip(datas, surfaces, bgr, form, seg)
+
     if handle is None:
         with _lib.Handle.postproc(0) as own:
-            status = own.op_jpeg_decode_clip(datas, surfaces, bgr, form, seg)
+            status = run(own)
     else:
-        status = _handle_of(handle).op_jpeg_decode_clip(datas, surfaces, bgr, form, seg)
+        status = run(_handle_of(handle))
     if strict:
         for f in range(len(frames)):
             if status[f, 0] != _lib.OK:
@@ -197,22 +209,29 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     return frames, status
 
 
-def decode_host(data, bgr: bool = True, strict: bool = True) -> np.ndarray:
+def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own") -> np.ndarray:
     """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
-    held to."""
+    held to.  `rule`: "own" or "libjpeg", as `decode` (`whenet_jpeg_decode_rule_host`)."""
+    _lib.jpeg_rule_code(rule)
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
+    if rule != "own":
+        return _result(frame, _lib.jpeg_decode_rule_host(data, packed_surface(frame), bgr, rule), strict)
     return _result(frame, _lib.jpeg_decode_host(data, packed_surface(frame), bgr), strict)
 
 
 def decode_segmented_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SEG_WINDOW, bgr: bool = True, strict: bool = True,
-                          stats: bool = False):
+                          stats: bool = False, rule: str = "own"):
     """`decode_host` with the entropy stage run as the host emulation of the segmented form (`whenet_jpeg_decode_segmented_host`):
     segments of `seg_bytes`, sync windows of `window` segments, lanes in a plain loop.  The same frame, bit for bit.
-    stats=True: (frame, status int32 [2], statistics int64 [8]) and damaged data does not raise."""
+    stats=True: (frame, status int32 [2], statistics int64 [8]) and damaged data does not raise.  `rule`: as `decode_host`."""
+    _lib.jpeg_rule_code(rule)
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
-    status, st = _lib.jpeg_decode_segmented_host(data, packed_surface(frame), bgr, seg_bytes, window)
+    if rule != "own":
+        status, st = _lib.jpeg_decode_segmented_rule_host(data, packed_surface(frame), bgr, seg_bytes, window, rule)
+    else:
+        status, st = _lib.jpeg_decode_segmented_host(data, packed_surface(frame), bgr, seg_bytes, window)
     if stats:
         return frame, status, st
     return _result(frame, status, strict)

@@ -876,8 +876,8 @@ WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_ind
  * FRAME.  WHENET_SURF_PACKED: pixel (x, y) takes the chroma sample (x >> (hs - 1), y >> (vs - 1)) and the JFIF row of the YUV
  * ingest's conversion; channel_order says where R and B go; grey gives B = G = R = Y.  For a 4:2:0 stream this is bit for bit
  * whenet_yuv_to_bgr_host of the decoded I420 planes.  A 4:2:0 stream also decodes into a WHENET_YUV_I420 or WHENET_YUV_NV12 surface
- * whose matrix is WHENET_YUV_JFIF (other samplings, another matrix: WHENET_EINVAL).  Nearest-neighbour chroma is a stated
- * difference from libjpeg's default triangle filter: the frame is the project's own, not cv2.imread's bytes.
+ * whose matrix is WHENET_YUV_JFIF (other samplings, another matrix: WHENET_EINVAL).  This is RULE 0, the default.  It differs from
+ * libjpeg's bytes (nearest-neighbour chroma against a triangle filter, another inverse DCT, another YCbCr row); rule 1 below does not.
  *   whenet_jpeg_parse        pure host: the stream's header into *info
  *   whenet_jpeg_decode_host  the whole decoder as pure host arithmetic (no GPU): the statement the kernels are held to.  dst: a
  *                  host surface (on_device = 0) of the stream's size; channel_order is read for WHENET_SURF_PACKED only
@@ -966,10 +966,53 @@ WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_ind
  *   whenet_jpeg_clip_counters  out = {clip decodes enqueued, frames in them, kernel launches plus memsets enqueued for them, H2D
  *                  copies enqueued for them} over the engines of the handle (host-side counts).  A clip decode also counts each of
  *                  its frames into whenet_jpeg_decode_counters' form-0 or form-1 word.
+ * JPEG DECODER, RULE 1 (six entry points, 107 in all, ABI still 6).  A second rule for the inverse DCT, the chroma upsampling and
+ * the colour row, chosen per handle (option "jpeg_rule") and per call: a packed frame whose bytes are those of a libjpeg-turbo
+ * decode with its defaults (JDCT_ISLOW, fancy upsampling, YCC to RGB) -- what cv2.imread and cap.read() hand the reference's first
+ * line.  Rule 0 above stays the default and none of its bytes change.  ACCEPTED, PARSE, INTERVALS, ENTROPY DECODE (both forms), the
+ * coefficient records clamp(value x Q, -2048, 2047) and DAMAGE with its status words are shared and the same under both rules.
+ * Integer arithmetic, >> an arithmetic shift.
+ * INVERSE DCT (jidctint.c: 13 constant bits, 2 pass-1 bits).  One 8-point pass on inputs i0..i7:
+ *     z1 = (i2+i6) 4433      t2 = z1 - i6 15137     t3 = z1 + i2 6270      t0 = (i0+i4) << 13     t1 = (i0-i4) << 13
+ *     t10 = t0+t3            t13 = t0-t3            t11 = t1+t2            t12 = t1-t2
+ *     a0 = i7   a1 = i5   a2 = i3   a3 = i1         z1 = a0+a3   z2 = a1+a2   z3 = a0+a2   z4 = a1+a3   z5 = (z3+z4) 9633
+ *     a0 *= 2446             a1 *= 16819            a2 *= 25172            a3 *= 12299
+ *     z1 *= -7373            z2 *= -20995           z3 = z3 (-16069) + z5  z4 = z4 (-3196) + z5
+ *     a0 += z1+z3            a1 += z2+z4            a2 += z2+z3            a3 += z1+z4
+ *     outputs 0..7 = t10+a3, t11+a2, t12+a1, t13+a0, t13-a0, t12-a1, t11-a2, t10-a3, each descaled as (x + 2^(s-1)) >> s
+ * Pass 1 runs down the columns with s = 11, pass 2 along the rows of its results with s = 18; sample = clamp(result + 128, 0, 255).
+ * (libjpeg's shortcuts for all-zero AC columns and rows give the same values.)  A pass is exact and linear, out[k] = sum_j C[j][k]
+ * i[j], and the columns of |C| sum to at most 61,214.  With |coefficient| <= 2048 pass 1 stays below 1.26e8 (every intermediate
+ * below 3.5e8): int32.  Its results reach 61,214, so pass 2 reaches 61,214^2 = 3.75e9, above 2^31: pass 2 is int64, on the host
+ * and in the kernel, for every clamped coefficient block, damaged ones included.
+ * CHROMA (jdsample.c, fancy).  The chroma planes are ch = ceil(h / vs) rows of cw = ceil(w / hs) samples; rows >= ch and columns
+ * >= cw of the padded working planes never enter a result: neighbour indices are clamped to 0..ch-1 and 0..cw-1.  4:4:4 and grey:
+ * nothing to do.  4:2:2 with cw > 2: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2.  4:2:0 with
+ * cw > 2: output row 2r uses s[i] = 3 in[r][i] + in[r-1][i], row 2r+1 uses 3 in[r][i] + in[r+1][i]; then out[2i] = (3 s[i] + s[i-1]
+ * + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4.  cw <= 2, either sampling: replication, in[y >> (vs-1)][x >> (hs-1)], with no
+ * vertical filter either (libjpeg's own switch).  The output is cropped to h x w.
+ * COLOUR (jdcolor.c).  d = Cb - 128, e = Cr - 128, F(x) = int(x 65536 + 0.5), clamp to 0..255:
+ *     R = clamp(Y + ((F(1.402) e + 32768) >> 16))        B = clamp(Y + ((F(1.772) d + 32768) >> 16))
+ *     G = clamp(Y + ((-F(0.34414) d + 32768 - F(0.71414) e) >> 16))
+ * Grey gives R = G = B = Y; channel_order places R and B as under rule 0.
+ * SCOPE.  Rule 1 equals libjpeg's bytes wherever no dequantised coefficient is touched by the +-2048 clamp -- every stream an
+ * encoder makes from 8-bit samples; libjpeg's range-limit table wraps on wilder values where this clamps.  For damaged or
+ * adversarial streams the output is still fully defined, kernel = host statement byte for byte, status as under rule 0.  The pin is
+ * executed Pillow (bundled libjpeg-turbo), byte for byte on every stream of the tests; OpenCV has never run here.
+ * Rule 1 decodes to WHENET_SURF_PACKED only: an I420 / NV12 destination under rule 1 is WHENET_EINVAL.  The kernels are rule-1 forms
+ * of the inverse DCT and frame kernels (the rule is fixed at compile time in each); a clip is decoded by one rule and enqueues no more
+ * than under rule 0.
+ *   option "jpeg_rule"       0: rule 0 (default); 1: rule 1.  Read by whenet_frame_begin_jpeg, whenet_clip_begin_jpeg,
+ *                  whenet_jpeg_decode_device, whenet_op_jpeg_decode[_ex] and whenet_op_jpeg_decode_clip.
+ *   The six calls below are the calls they are named after with `rule` beside their arguments: 0 or 1, and for the calls on a handle
+ *   -1 = the handle's option (as entropy -1 = the handle's entropy options, which whenet_op_jpeg_decode_rule accepts too).
+ *   whenet_jpeg_decode_rule_host, whenet_jpeg_decode_segmented_rule_host   the host statement, plain and segmented
+ *   whenet_op_jpeg_decode_rule, whenet_op_jpeg_decode_clip_rule            the kernels alone, one stream and a clip
+ *   whenet_frame_begin_jpeg_rule, whenet_clip_begin_jpeg_rule              the resident-frame calls
  * Not built: clips of streams already in device memory, a stitch of several lanes per interval, a marker scan of several
- * workgroups, progressive / arithmetic / 12-bit streams.
+ * workgroups, progressive / arithmetic / 12-bit streams, YUV surfaces under rule 1, OpenCV's own bytes.
  * WHENET_EINVAL: a NULL argument or plane, size < 1, a pitch below the row bytes, an unknown format / channel order, a seg_bytes,
- * window or entropy value outside its range. */
+ * window, entropy or rule value outside its range. */
 #define WHENET_JPEG_SEG_WINDOW 256
 #define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
 #define WHENET_JPEG_CLIP_PLAN_TOTAL_WORDS 8
@@ -1009,6 +1052,18 @@ WHENET_API int whenet_op_jpeg_decode_clip(whenet_t* h, const uint8_t* const* dat
 WHENET_API int whenet_jpeg_clip_plan(const whenet_jpeg_info_t* infos, const int64_t* nbytes, int num_frames, int entropy, int seg_bytes,
                           int64_t* out);
 WHENET_API int whenet_jpeg_clip_counters(whenet_t* h, int64_t out[4]);
+WHENET_API int whenet_jpeg_decode_rule_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                                 int32_t status[2]);
+WHENET_API int whenet_jpeg_decode_segmented_rule_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order,
+                                           int seg_bytes, int window, int rule, int32_t status[2], int64_t stats[8]);
+WHENET_API int whenet_op_jpeg_decode_rule(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
+                               int seg_bytes, int rule, int32_t status[2], int64_t stats[8]);
+WHENET_API int whenet_op_jpeg_decode_clip_rule(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames,
+                                    const whenet_surface_t* dst, int channel_order, int32_t* status, int entropy, int seg_bytes, int rule);
+WHENET_API int whenet_frame_begin_jpeg_rule(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int* ticket,
+                                 int32_t* status);
+WHENET_API int whenet_clip_begin_jpeg_rule(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int rule,
+                                int* ticket, int32_t* status);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

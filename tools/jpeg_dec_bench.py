@@ -14,6 +14,11 @@
                                 handle's auto choice) and, for the segmented form, per value of --seg-bytes; "forms" says which form
                                 each entry ran in (whenet_jpeg_decode_counters).  --lanes: decoding lanes per wave of the segmented
                                 kernels (option jpeg_seg_lanes; 0: the default).  --only-decode skips (ii) and (iii).
+                                --rule 0 | 1: the decode rule of every decode of the run (option jpeg_rule: 0 the project's own,
+                                1 libjpeg's bytes), checked against the host statement of the same rule; "rule" in the output.
+                                Under rule 1 the colour stage of the tight BGR frame is the rule's frame kernel, under rule 0 the
+                                plane kernel of the YUV ingest: a kernel trace of two runs gives the per-kernel times side by side.
+                                --rgb decodes into R, G, B order, which takes the frame kernel under rule 0 as well.
     (ii)  begin_us, begin_jpeg_us
                                 one frame with 4 heads, begin -> heads -> collect, from the BGR frame (the parent commit's path)
                                 and from the stream (begin_jpeg), depth 1, the median of single frames
@@ -31,7 +36,7 @@
                                 are whenet_jpeg_clip_counters' differences.  The handle's options stay at their defaults (auto).
 
   python tools/jpeg_dec_bench.py [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
-                                 [--lanes 0] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
+                                 [--lanes 0] [--rule 0] [--rgb] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
 
 Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
 events on the stream the work is enqueued on.  The frames the streams decode to are checked against the host statement first.
@@ -51,6 +56,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.environ.get("WHENET_HIP_PKG") or os.path.join(ROOT, "headposeestimation-whenet_amd"))
+
+
+RULES = ("own", "libjpeg")      # --rule 0, 1
 
 
 def median_us(fn, rounds, sync):
@@ -85,7 +93,7 @@ def size_leg(m, h, w, args):
     frame, boxes = synth.video_frame(h, w), synth.head_boxes(4, h, w)
     sync = torch.cuda.synchronize
     stream = torch.cuda.current_stream().cuda_stream or None
-    res = {"frame": [h, w], "heads": 4, "bytes_frame": 3 * h * w}
+    res = {"frame": [h, w], "heads": 4, "bytes_frame": 3 * h * w, "rule": args.rule}
     dst = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
     s = _lib.SurfaceC()
     s.plane[0], s.pitch[0], s.format, s.on_device = dst.data_ptr(), 3 * w, _lib.SURF_PACKED, 1
@@ -94,8 +102,8 @@ def size_leg(m, h, w, args):
     for name, data in streams_of(frame).items():
         info = _lib.jpeg_parse(data)
         ent = torch.from_numpy(np.frombuffer(data, np.uint8)[info.data_offset:].copy()).cuda()
-        decode = lambda: hnd.jpeg_decode_device(info, ent.data_ptr(), ent.numel(), s, True, status.data_ptr(), stream=stream)
-        want = jpeg.decode_host(data)
+        decode = lambda: hnd.jpeg_decode_device(info, ent.data_ptr(), ent.numel(), s, not args.rgb, status.data_ptr(), stream=stream)
+        want = jpeg.decode_host(data, bgr=not args.rgb, rule=RULES[args.rule])
         r = {"intervals": info.intervals, "bytes_jpeg": len(data), "equals_host": True, "decode_us": {}, "decode_call_host_us": {}, "forms": {}}
         configs = []
         for e in args.entropy:
@@ -169,12 +177,12 @@ def clip_leg(m, h, w, args):
     hnd = m._handle
     sync = torch.cuda.synchronize
     no_heads = np.zeros((0, 4), np.int32)
-    res = {"frame": [h, w], "clip": {}}
+    res = {"frame": [h, w], "rule": args.rule, "clip": {}}
     streams = streams_of(synth.video_frame(h, w))
     for name in ("own", "pillow"):
         data = streams[name]
-        want = jpeg.decode_host(data)
-        got, _ = jpeg.decode_clip([data] * 3, handle=hnd)      # the clip kernels on this stream against the host statement first
+        want = jpeg.decode_host(data, rule=RULES[args.rule])
+        got, _ = jpeg.decode_clip([data] * 3, handle=hnd, rule=RULES[args.rule])      # the clip kernels on this stream against the host statement first
         r = {"bytes_jpeg": len(data), "equals_host": all(np.array_equal(g, want) for g in got)}
         for F in args.clip:
             datas, status, single = [data] * F, np.zeros((F, 2), np.int32), np.zeros(2, np.int32)
@@ -220,6 +228,8 @@ def main():
     ap.add_argument("--entropy", type=int, nargs="+", default=[0, 1], choices=[0, 1, 2], help="forms of the entropy stage to time")
     ap.add_argument("--seg-bytes", type=int, nargs="+", default=[128], help="segment sizes of the segmented form")
     ap.add_argument("--lanes", type=int, default=0, choices=[0, 16, 32, 64], help="decoding lanes per wave of the segmented kernels")
+    ap.add_argument("--rule", type=int, default=0, choices=[0, 1], help="the decode rule: 0 the project's own, 1 libjpeg's bytes")
+    ap.add_argument("--rgb", action="store_true", help="row (i) decodes into R, G, B order (rule 0 then takes its frame kernel too)")
     ap.add_argument("--only-decode", action="store_true", help="rows (i) only")
     ap.add_argument("--clip", type=int, nargs="+", default=None, help="row (v) only: frames per clip of JPEG streams, 1..16 each")
     ap.add_argument("--clip-samples", type=int, default=20, help="regions per figure of row (v), at least 20")
@@ -228,6 +238,7 @@ def main():
     import whenet
     m = whenet.WHENet(dtype="f16")
     m._handle.set_option("jpeg_seg_lanes", args.lanes)
+    m._handle.set_option("jpeg_rule", args.rule)
     try:
         for size in args.sizes:
             h, w = (int(v) for v in size.split("x"))

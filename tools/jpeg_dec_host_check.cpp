@@ -5,13 +5,16 @@
 // heap block of exactly its size and decoded into a frame of exactly h * w * 3 bytes, so that a byte fetched behind the data or
 // stored outside the frame is a sanitizer report.  Then the stream is damaged here as well: cut behind every one of its first and
 // last 300 entropy bytes (and at 64 places between), and with seeded byte flips, each copy again in its own exact-size block.  A bit
-// reader is where a one-byte overrun hides.  It needs no GPU and no HIP runtime and is never loaded into Python.
+// reader is where a one-byte overrun hides.  Every decode, of a stream and of each cut or flipped copy, is run under RULE 1 (libjpeg's
+// inverse DCT, fancy upsampling and colour row) as well: its clamped neighbour indices are where a read outside a plane would hide,
+// its 64-bit row pass where a signed overflow would.  It needs no GPU and no HIP runtime and is never loaded into Python.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/jpeg_dec_host_check.cpp \
 //       -o tools/jpeg_dec_host_check && tools/jpeg_dec_host_check stream.jpg ...
 //
 // Output, one line per file: "<file name> status <code> <first bad interval> crc <crc32 of the BGR frame>", or "<file name> refused
-// <reason>".  Exit status 0 unless a file cannot be read or a mutated stream changes what it must not.
+// <reason>"; for a decoded file a second line "rule1:<file name> status <code> <first bad interval> crc <crc32 of rule 1's BGR frame>".
+// Exit status 0 unless a file cannot be read, a mutated stream changes what it must not, or the two rules disagree on a status.
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -37,7 +40,8 @@ uint32_t crc32(const uint8_t* p, size_t n) {
 }
 
 // decode `size` bytes held in a heap block of exactly that size; false: refused (reason)
-bool decode(const uint8_t* src, size_t size, int32_t status[2], uint32_t& crc, const char*& reason, whenet_jpeg_info_t& info) {
+bool decode(const uint8_t* src, size_t size, int32_t status[2], uint32_t& crc, const char*& reason, whenet_jpeg_info_t& info,
+            uint32_t* crc_rule1 = nullptr) {
     std::unique_ptr<uint8_t[]> data(new uint8_t[size ? size : 1]);
     std::memcpy(data.get(), src, size);
     reason = jpeg_parse(data.get(), int64_t(size), info);
@@ -72,6 +76,24 @@ bool decode(const uint8_t* src, size_t size, int32_t status[2], uint32_t& crc, c
             }
             if (jpeg_dec_check_dst(info, &s, WHENET_BGR) != nullptr) std::exit(3);
             jpeg_dec_frame_host(jpeg_dec_geom(info), planes, s, WHENET_BGR);
+            if (jpeg_dec_check_dst(info, &s, WHENET_BGR, JPEG_RULE_LIBJPEG) == nullptr) std::exit(4);      // rule 1: packed only
+        }
+    }
+    {      // rule 1 from the same bytes: the same status words, a frame of its own in an exact-size block, both channel orders
+        JpegDecPlanes p1;
+        int32_t st1[2] = {0, 0};
+        jpeg_dec_planes_host(info, data.get() + info.data_offset, int(int64_t(size) - info.data_offset), p1, st1, JPEG_RULE_LIBJPEG);
+        if (st1[0] != status[0] || st1[1] != status[1]) {
+            std::printf("rule 1 gives the status %d %d where rule 0 gives %d %d\n", st1[0], st1[1], status[0], status[1]);
+            std::exit(5);
+        }
+        if (jpeg_dec_check_dst(info, &dst, WHENET_BGR, JPEG_RULE_LIBJPEG) != nullptr) std::exit(6);
+        for (int order : {WHENET_RGB, WHENET_BGR}) {
+            std::unique_ptr<uint8_t[]> f1(new uint8_t[fbytes]);
+            whenet_surface_t d1 = dst;
+            d1.plane[0] = f1.get();
+            jpeg_dec_frame_host(jpeg_dec_geom(info), p1, d1, order, JPEG_RULE_LIBJPEG);
+            if (crc_rule1 != nullptr) *crc_rule1 = crc32(f1.get(), fbytes);
         }
     }
     return true;
@@ -97,7 +119,8 @@ int main(int argc, char** argv) {
         uint32_t crc = 0;
         const char* reason = nullptr;
         whenet_jpeg_info_t info;
-        if (!decode(bytes.data(), bytes.size(), status, crc, reason, info)) {
+        uint32_t crc1 = 0;
+        if (!decode(bytes.data(), bytes.size(), status, crc, reason, info, &crc1)) {
             std::printf("%s refused %s\n", name.c_str(), reason);
             for (size_t cut = 0; cut < bytes.size() && cut < 700; ++cut) {      // a refused header, cut anywhere, stays refused
                 int32_t st[2];
@@ -112,6 +135,7 @@ int main(int argc, char** argv) {
             continue;
         }
         std::printf("%s status %d %d crc %08x\n", name.c_str(), status[0], status[1], crc);
+        std::printf("rule1:%s status %d %d crc %08x\n", name.c_str(), status[0], status[1], crc1);
         // the same stream cut short: every length of the header is refused, every length of the data decodes to something
         const size_t off = size_t(info.data_offset), n = bytes.size() - off;
         if (size_t(info.h) * size_t(info.w) > 20000) continue;      // (the large streams are decoded once: the walk is quadratic)
