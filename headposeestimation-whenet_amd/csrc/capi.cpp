@@ -1283,6 +1283,132 @@ int whenet_clip_begin_jpeg_rule(whenet_t* h, const uint8_t* const* data, const i
                                 [&](whenet::Engine& e) { return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule); });
 }
 
+// ---- progressive JPEG streams (jpeg_prog.hip, jpeg_prog_host.h) ----
+namespace {
+int parse_scans_for_host(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info, whenet::JpegProgPlan& plan) {
+    if (data == nullptr || size < 1) {
+        g_create_error = std::string(what) + ": NULL argument or size < 1";
+        return WHENET_EINVAL;
+    }
+    if (const char* bad = whenet::jpeg_prog_parse(data, size, info, plan)) {
+        g_create_error = std::string(what) + ": " + bad;
+        return WHENET_EFORMAT;
+    }
+    return WHENET_OK;
+}
+}  // namespace
+
+int whenet_jpeg_parse_scans(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info, whenet_jpeg_scan_t* scans, int cap, int* num_scans) {
+    try {
+        WHENET_REQUIRE(info != nullptr && num_scans != nullptr && (scans != nullptr || cap == 0) && cap >= 0, WHENET_EINVAL,
+                       "jpeg_parse_scans: NULL argument");
+        whenet::JpegProgPlan plan;
+        if (const int rc = parse_scans_for_host("jpeg_parse_scans", data, size, *info, plan)) return rc;
+        *num_scans = int(plan.scans.size());
+        WHENET_REQUIRE(cap >= *num_scans, WHENET_EINVAL,
+                       "jpeg_parse_scans: the stream has " + std::to_string(*num_scans) + " scans, the capacity is " + std::to_string(cap));
+        for (size_t i = 0; i < plan.scans.size(); ++i) scans[i] = plan.scans[i];
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_jpeg_decode_progressive_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                                        int32_t status[2]) {
+    try {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_progressive_host: NULL argument");
+        whenet_jpeg_info_t info;
+        whenet::JpegProgPlan plan;
+        if (const int rc = parse_scans_for_host("jpeg_decode_progressive_host", data, size, info, plan)) return rc;
+        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_progressive_host: ") + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_progressive_host: the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        whenet::jpeg_prog_decode_planes_host(info, plan, data, size, planes, status, rule);
+        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_jpeg_decode_progressive_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int rule,
+                                               int32_t status[2]) {
+    try {
+        WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_progressive_planes_host: NULL argument");
+        WHENET_REQUIRE(whenet::jpeg_rule_ok(rule), WHENET_EINVAL, "jpeg_decode_progressive_planes_host: the rule must be 0 or 1");
+        whenet_jpeg_info_t info;
+        whenet::JpegProgPlan plan;
+        if (const int rc = parse_scans_for_host("jpeg_decode_progressive_planes_host", data, size, info, plan)) return rc;
+        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
+        for (int c = 0; c < g.comps; ++c) {
+            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
+            WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
+                           "jpeg_decode_progressive_planes_host: plane " + std::to_string(c) + " is NULL or its pitch is below its " +
+                               std::to_string(cw) + " samples");
+        }
+        whenet::JpegDecPlanes pl;
+        whenet::jpeg_prog_decode_planes_host(info, plan, data, size, pl, status, rule);
+        for (int c = 0; c < g.comps; ++c) {
+            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
+            for (int y = 0; y < ch; ++y)
+                std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
+        }
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_jpeg_progressive_coefficients_host(const uint8_t* data, int64_t size, int16_t* coef, int16_t* raw, int64_t cap_blocks,
+                                              int64_t counters[8], int32_t status[2]) {
+    try {
+        WHENET_REQUIRE(coef != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_progressive_coefficients_host: NULL argument");
+        whenet_jpeg_info_t info;
+        whenet::JpegProgPlan plan;
+        if (const int rc = parse_scans_for_host("jpeg_progressive_coefficients_host", data, size, info, plan)) return rc;
+        WHENET_REQUIRE(!plan.baseline, WHENET_EINVAL, "jpeg_progressive_coefficients_host: a baseline (SOF0) stream has no scan plan");
+        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
+        const int64_t blocks = int64_t(g.mcu_cols) * g.mcu_rows * g.bpm;
+        WHENET_REQUIRE(cap_blocks >= blocks, WHENET_EINVAL,
+                       "jpeg_progressive_coefficients_host: the stream has " + std::to_string(blocks) + " blocks, the capacity is " +
+                           std::to_string(cap_blocks));
+        whenet::JpegProgResult r;
+        whenet::jpeg_prog_coefficients_host(info, plan, data + plan.data_base, r, status);
+        std::memcpy(coef, r.coef.data(), r.coef.size() * sizeof(int16_t));
+        if (raw != nullptr) std::memcpy(raw, r.raw.data(), r.raw.size() * sizeof(int16_t));
+        if (counters != nullptr)
+            for (int i = 0; i < 8; ++i) counters[i] = r.cnt[i];
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+int whenet_op_jpeg_decode_progressive(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                                      int32_t status[2], int64_t stats[8]) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_progressive: NULL argument");
+        e.op_jpeg_decode(data, size, *dst, channel_order, status, -1, 0, stats, rule, 1);
+    });
+}
+
+int whenet_frame_begin_jpeg_progressive(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int* ticket,
+                                        int32_t* status) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status, rule, 1); });
+}
+
+int whenet_jpeg_progressive_counters(whenet_t* h, int64_t out[4]) {
+    if (out == nullptr) return WHENET_EINVAL;
+    return guarded(h, [&](whenet::Engine& e) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        e.add_jpeg_progressive_counters(out);
+        for (const whenet::Engine* r : h->replicas) r->add_jpeg_progressive_counters(out);
+        for (const whenet::Engine* r : h->fan) r->add_jpeg_progressive_counters(out);
+    });
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

@@ -285,6 +285,14 @@ void Engine::set_option(const std::string& key, long value) {
         WHENET_REQUIRE(value >= 0 && value <= 2, WHENET_EINVAL, "jpeg_entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto, default)");
         jpeg_entropy_ = int(value);
         return;
+    } else if (key == "jpeg_progressive") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "jpeg_progressive must be 0 (SOF2 streams are refused, default) or 1 (they are decoded)");
+        jpeg_progressive_ = int(value);
+        return;
+    } else if (key == "jpeg_prog_levels") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "jpeg_prog_levels must be 1 (a launch per level, default) or 0 (a launch per scan)");
+        jpeg_prog_levels_ = int(value);
+        return;
     } else if (key == "jpeg_rule") {
         WHENET_REQUIRE(jpeg_rule_ok(value), WHENET_EINVAL, "jpeg_rule must be 0 (the project's own rule, default) or 1 (libjpeg's bytes)");
         jpeg_rule_ = int(value);

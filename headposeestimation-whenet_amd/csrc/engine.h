@@ -359,12 +359,16 @@ class Engine {
     // segmented form's statistics back into stats (8 int64, may be nullptr).
     // The decode RULE (0: the project's own inverse DCT, nearest chroma and JFIF row; 1: libjpeg's bytes -- jidctint, fancy
     // upsampling, jdcolor -- into packed destinations only) follows the option "jpeg_rule" (default 0) wherever `rule` is -1.
+    // PROGRESSIVE streams (SOF2; jpeg_prog.hip, JPEG DECODER, PROGRESSIVE in the header) are opt-in: progressive = 1, or -1 with the
+    // option "jpeg_progressive" set.  Then a SOF2 stream runs the scan plan (one H2D), a memset, a scan-kernel launch per level
+    // (option "jpeg_prog_levels" = 0: per scan) and the finish in front of the inverse DCT; a SOF0 stream runs as ever.
     void op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy = -1,
-                        int seg_bytes = 0, int64_t* stats = nullptr, int rule = -1);
+                        int seg_bytes = 0, int64_t* stats = nullptr, int rule = -1, int progressive = -1);
+    void add_jpeg_progressive_counters(int64_t out[4]) const;      // decodes enqueued, scan-kernel launches, scans in them
     void add_jpeg_decode_counters(int64_t out[4]) const;      // decodes launched in form 0, in form 1
     void jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
                             int channel_order, int32_t* d_status, hipStream_t stream);
-    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule = -1);
+    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule = -1, int progressive = -1);
     // A CLIP of 1..16 JPEG streams (frame f: data[f], size[f] bytes), each with its own size, sampling, tables, DRI and entropy
     // form (the options are applied stream by stream): one plan (jpeg_dec_clip_host.h), ONE H2D of records | tables | entropy bytes,
     // one memset and every stage in one launch for all frames (launch_jpeg_decode_clip).  Refusals -- a frame count outside 1..16, a
@@ -601,6 +605,8 @@ class Engine {
     std::vector<JpegDecTables> jpeg_dec_tables_h_;
     int jpeg_entropy_ = 2, jpeg_seg_bytes_ = JPEG_SEG_DEFAULT_BYTES;      // options "jpeg_entropy", "jpeg_seg_bytes"
     int jpeg_rule_ = JPEG_RULE_OWN;                                       // option "jpeg_rule"
+    int jpeg_progressive_ = 0, jpeg_prog_levels_ = 1;                     // options "jpeg_progressive", "jpeg_prog_levels"
+    int64_t jpeg_prog_counts_[3] = {0, 0, 0};                             // decodes enqueued, scan-kernel launches, scans in them
     // the rule of a call: its argument, or the option where that is -1; anything else is WHENET_EINVAL
     int jpeg_rule_of(const char* what, int rule) const;
     int jpeg_seg_lanes_ = 0;                                             // option "jpeg_seg_lanes" (a measurement knob; 0: the default)

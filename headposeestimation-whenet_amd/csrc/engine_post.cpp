@@ -1425,6 +1425,31 @@ whenet_jpeg_info_t parse_or_refuse(const char* what, const uint8_t* data, int64_
     WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
     return info;
 }
+// the same through the parser that accepts progressive streams too: the scan plan beside the header
+whenet_jpeg_info_t parse_scans_or_refuse(const char* what, const uint8_t* data, int64_t size, JpegProgPlan& plan) {
+    WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
+    whenet_jpeg_info_t info;
+    const char* bad = jpeg_prog_parse(data, size, info, plan);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
+    return info;
+}
+// a baseline record over a progressive layout: what launch_jpeg_decode_tail reads of it
+JpegDecArgs jpeg_prog_tail_args(const JpegDecGeom& g, void* d_scratch, const JpegProgLayout& lay, const whenet_surface_t& dst, int channel_order,
+                                int32_t* d_status, int rule, int nbytes) {
+    JpegDecArgs a{};
+    char* const s = static_cast<char*>(d_scratch);
+    a.g = g;
+    a.tables = reinterpret_cast<const JpegDecTables*>(s + lay.huff);      // (not read behind the entropy stage)
+    a.data = reinterpret_cast<const uint8_t*>(s + lay.data), a.nbytes = nbytes;
+    a.start = reinterpret_cast<int32_t*>(s + lay.items), a.meta = reinterpret_cast<int32_t*>(s + lay.meta);
+    a.coef = reinterpret_cast<int16_t*>(s + lay.coef);
+    for (int c = 0; c < 3; ++c) {
+        a.plane[c] = reinterpret_cast<uint8_t*>(s + lay.plane[c]);
+        a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
+    }
+    a.format = dst.format, a.channel_order = channel_order, a.rule = rule, a.status = d_status, a.form = 0;
+    return a;
+}
 }  // namespace
 
 JpegDecScratch Engine::jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy, int seg_bytes) const {
@@ -1441,22 +1466,29 @@ int Engine::jpeg_rule_of(const char* what, int rule) const {
 }
 
 void Engine::add_jpeg_decode_counters(int64_t out[4]) const { out[0] += jpeg_dec_launched_[0], out[1] += jpeg_dec_launched_[1]; }
+void Engine::add_jpeg_progressive_counters(int64_t out[4]) const {
+    for (int i = 0; i < 3; ++i) out[i] += jpeg_prog_counts_[i];
+}
 
 void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy,
-                            int seg_bytes, int64_t* stats, int rule) {
+                            int seg_bytes, int64_t* stats, int rule, int progressive) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
     rule = jpeg_rule_of("op_jpeg_decode", rule);
-    const whenet_jpeg_info_t info = parse_or_refuse("op_jpeg_decode", data, size);
+    JpegProgPlan plan;
+    const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
+    const whenet_jpeg_info_t info = accept ? parse_scans_or_refuse("op_jpeg_decode", data, size, plan) : parse_or_refuse("op_jpeg_decode", data, size);
+    const bool prog = accept && !plan.baseline;
     const char* bad = jpeg_dec_check_dst(info, &dst, channel_order, rule);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_decode: ") + (bad ? bad : ""));
     WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_jpeg_decode: the surface must be host memory (on_device = 0)");
     check_surface("op_jpeg_decode", dst, info.h, info.w);
     const JpegDecGeom g = jpeg_dec_geom(info);
     const size_t nbytes = size_t(size - info.data_offset);
-    const JpegDecScratch lay = jpeg_dec_layout(g, nbytes, int64_t(nbytes), entropy, seg_bytes);
+    const JpegDecScratch lay = jpeg_dec_layout(g, prog ? 0 : nbytes, prog ? 0 : int64_t(nbytes), prog ? 0 : entropy, seg_bytes);
+    const JpegProgLayout play(g, plan);
     std::vector<JpegDecTables> tables(1);
-    jpeg_dec_build_tables(info, tables[0]);
+    if (!prog) jpeg_dec_build_tables(info, tables[0]);
     // the destination on the device: every plane at the caller's pitch and at the caller's address modulo 16, between two guard
     // zones and over a sentinel, so that a store outside the rows' bytes is seen
     int rows[3], row_bytes[3];
@@ -1467,17 +1499,31 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
         total = off[p] + size_t(rows[p] - 1) * size_t(dst.pitch[p]) + size_t(row_bytes[p]);
     }
     TempBufs tmp;
-    char* const d_scratch = static_cast<char*>(tmp.get(lay.bytes));
+    char* const d_scratch = static_cast<char*>(tmp.get(prog ? play.bytes : lay.bytes));
     int32_t* const d_status = static_cast<int32_t*>(tmp.get(2 * sizeof(int32_t)));
-    WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.tables, tables.data(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream_));
-    if (nbytes > 0) WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.data, data + info.data_offset, nbytes, hipMemcpyHostToDevice, stream_));
+    std::vector<uint8_t> upload;      // (alive until the wait below)
+    if (prog) {
+        upload.resize(play.upload_bytes);
+        jpeg_prog_stage(plan, play, data + plan.data_base, upload.data());
+        WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch, upload.data(), play.upload_bytes, hipMemcpyHostToDevice, stream_));
+    } else {
+        WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.tables, tables.data(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream_));
+        if (nbytes > 0) WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.data, data + info.data_offset, nbytes, hipMemcpyHostToDevice, stream_));
+    }
     const GuardedOutput d_out(total, stream_);
     whenet_surface_t d_dst = dst;
     for (int p = 0; p < planes; ++p) d_dst.plane[p] = d_out.frames() + off[p];
-    launch_jpeg_decode(jpeg_dec_args(g, d_scratch, lay, reinterpret_cast<const uint8_t*>(d_scratch + lay.data), (long long)(nbytes), d_dst,
-                                     channel_order, d_status, rule),
-                       lay, stream_);
-    ++jpeg_dec_launched_[lay.form];
+    int64_t prog_launches = 0;
+    if (prog) {
+        launch_jpeg_decode_progressive(jpeg_prog_tail_args(g, d_scratch, play, d_dst, channel_order, d_status, rule, int(plan.data_bytes)), plan, play,
+                                       d_scratch, jpeg_prog_levels_, stream_, &prog_launches);
+        ++jpeg_prog_counts_[0], jpeg_prog_counts_[1] += prog_launches, jpeg_prog_counts_[2] += int64_t(plan.dev.size());
+    } else {
+        launch_jpeg_decode(jpeg_dec_args(g, d_scratch, lay, reinterpret_cast<const uint8_t*>(d_scratch + lay.data), (long long)(nbytes), d_dst,
+                                         channel_order, d_status, rule),
+                           lay, stream_);
+        ++jpeg_dec_launched_[lay.form];
+    }
     d_out.to_host(stream_, off, 0, nullptr, "op_jpeg_decode");      // waits, checks the guard zones
     std::vector<uint8_t> back(total);
     WHENET_HIP_CHECK(hipMemcpy(back.data(), d_out.frames(), total, hipMemcpyDeviceToHost));
@@ -1492,7 +1538,10 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
         WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
                        "op_jpeg_decode: the kernel wrote outside the rows of the surface (byte " + std::to_string(i) + ")");
     WHENET_HIP_CHECK(hipMemcpy(status, d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (stats != nullptr) {
+    if (stats != nullptr && prog) {
+        std::fill(stats, stats + 8, int64_t(0));
+        stats[0] = plan.total_items, stats[1] = plan.levels, stats[2] = int64_t(plan.dev.size()), stats[3] = prog_launches;
+    } else if (stats != nullptr) {
         if (lay.form == 1) {
             WHENET_HIP_CHECK(hipMemcpy(stats, d_scratch + lay.seg_stats, 8 * sizeof(int64_t), hipMemcpyDeviceToHost));
         } else {      // an interval per lane: the intervals it decoded are those up to the first one the markers make bad
@@ -1547,38 +1596,57 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
 }
 
 // frame_begin from a JPEG stream: the slot ends up exactly as frame_begin(decoded frame, channel_order) leaves it
-int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule) {
+int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule, int progressive) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "frame_begin_jpeg: NULL argument");
     rule = jpeg_rule_of("frame_begin_jpeg", rule);
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "frame_begin_jpeg: unknown channel order");
-    const whenet_jpeg_info_t info = parse_or_refuse("frame_begin_jpeg", data, size);      // (before a slot is taken)
+    JpegProgPlan plan;
+    const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
+    const whenet_jpeg_info_t info =      // (before a slot is taken)
+        accept ? parse_scans_or_refuse("frame_begin_jpeg", data, size, plan) : parse_or_refuse("frame_begin_jpeg", data, size);
     const JpegDecGeom g = jpeg_dec_geom(info);
+    // the work buffers of the stream's decoder: the baseline one's (tables | compressed bytes | ...) or, for a progressive stream,
+    // the scan plan's; either way the front of the buffer is what the pinned staging uploads as ONE H2D
+    const bool prog = accept && !plan.baseline;
     const size_t nbytes = size_t(size - info.data_offset);
-    const JpegDecScratch lay = jpeg_dec_layout(g, nbytes, int64_t(nbytes));
+    const JpegDecScratch lay = jpeg_dec_layout(g, prog ? 0 : nbytes, prog ? 0 : int64_t(nbytes));
+    const JpegProgLayout play(g, plan);
+    const size_t upload_bytes = prog ? play.upload_bytes : lay.upload_bytes, work_bytes = prog ? play.bytes : lay.bytes;
     Slot& slot = *free_slot();
     ensure_slot(slot, 1);
     const size_t fbytes = size_t(info.h) * info.w * 3;
-    slot.frame.h.grow(std::max(fbytes, lay.upload_bytes));      // (>= the frame's bytes: the size every other user of the staging grows it to)
+    slot.frame.h.grow(std::max(fbytes, upload_bytes));      // (>= the frame's bytes: the size every other user of the staging grows it to)
     slot.frame.d.grow(fbytes);
-    slot.jpg_dec.grow(lay.bytes);
+    slot.jpg_dec.grow(work_bytes);
     slot.jpg_dec_status.grow(JPEG_STATUS_BYTES);
     void* d_status = nullptr;                      // the pinned status words as the device addresses them
     WHENET_HIP_CHECK(hipHostGetDevicePointer(&d_status, slot.jpg_dec_status.as<void>(), 0));
-    // tables | compressed bytes: the staging's front, one H2D
     uint8_t* const stage = slot.frame.h.as<uint8_t>();
-    std::vector<JpegDecTables> tables(1);
-    jpeg_dec_build_tables(info, tables[0]);
-    std::memset(stage, 0, lay.data);
-    std::memcpy(stage + lay.tables, tables.data(), sizeof(JpegDecTables));
-    if (nbytes > 0) std::memcpy(stage + lay.data, data + info.data_offset, nbytes);
-    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, lay.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
+    if (prog) {
+        jpeg_prog_stage(plan, play, data + plan.data_base, stage);
+    } else {      // tables | compressed bytes
+        std::vector<JpegDecTables> tables(1);
+        jpeg_dec_build_tables(info, tables[0]);
+        std::memset(stage, 0, lay.data);
+        std::memcpy(stage + lay.tables, tables.data(), sizeof(JpegDecTables));
+        if (nbytes > 0) std::memcpy(stage + lay.data, data + info.data_offset, nbytes);
+    }
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, upload_bytes, hipMemcpyHostToDevice, copy_stream()));
     whenet_surface_t dst{};
     dst.plane[0] = slot.frame.d.as<void>(), dst.pitch[0] = 3 * info.w, dst.format = WHENET_SURF_PACKED, dst.on_device = 1;
-    launch_jpeg_decode(jpeg_dec_args(g, slot.jpg_dec.as<void>(), lay, slot.jpg_dec.as<uint8_t>() + lay.data, (long long)(nbytes), dst,
-                                     channel_order, static_cast<int32_t*>(d_status), rule),
-                       lay, copy_stream());
-    ++jpeg_dec_launched_[lay.form];
+    if (prog) {      // memset, a scan-kernel launch per level, the finish, then the stages the baseline decoder ends with
+        int64_t launches = 0;
+        launch_jpeg_decode_progressive(jpeg_prog_tail_args(g, slot.jpg_dec.as<void>(), play, dst, channel_order, static_cast<int32_t*>(d_status), rule,
+                                                           int(plan.data_bytes)),
+                                       plan, play, slot.jpg_dec.as<void>(), jpeg_prog_levels_, copy_stream(), &launches);
+        ++jpeg_prog_counts_[0], jpeg_prog_counts_[1] += launches, jpeg_prog_counts_[2] += int64_t(plan.dev.size());
+    } else {
+        launch_jpeg_decode(jpeg_dec_args(g, slot.jpg_dec.as<void>(), lay, slot.jpg_dec.as<uint8_t>() + lay.data, (long long)(nbytes), dst,
+                                         channel_order, static_cast<int32_t*>(d_status), rule),
+                           lay, copy_stream());
+        ++jpeg_dec_launched_[lay.form];
+    }
     WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
     slot.fh = info.h, slot.fw = info.w, slot.swap_rb = channel_order == WHENET_BGR;
     slot.frame_ticket = finish_submission(slot, 0);

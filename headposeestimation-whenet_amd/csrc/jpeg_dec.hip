@@ -500,6 +500,12 @@ void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStre
         hipLaunchKernelGGL(whenet_jpeg_dec_entropy_kernel, dim3((g.intervals + ENT_LANES - 1) / ENT_LANES), dim3(ENT_THREADS), 0, stream, a);
     }
     WHENET_HIP_CHECK(hipGetLastError());
+    launch_jpeg_decode_tail(a, stream);
+}
+
+void launch_jpeg_decode_tail(const JpegDecArgs& a, hipStream_t stream) {
+    const JpegDecGeom& g = a.g;
+    check_jpeg_dec_args(a);
     const long long nblocks = (long long)(g.mcu_cols) * g.mcu_rows * g.bpm;
     hipLaunchKernelGGL(a.rule == JPEG_RULE_LIBJPEG ? whenet_jpeg_dec_idct_libjpeg_kernel : whenet_jpeg_dec_idct_kernel,
                        dim3(unsigned((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(THREADS), 0, stream, a);

@@ -1,0 +1,628 @@
+// The progressive JPEG decoder (SOF2) as arithmetic, shared by the host statement (whenet_jpeg_parse_scans,
+// whenet_jpeg_decode_progressive_host, ..._planes_host, whenet_jpeg_progressive_coefficients_host) and the kernels of jpeg_prog.hip:
+// the parser of a stream of several scans with its scan plan, the four scan kinds of T.81 annex G (G.1.2 / G.2, as jdphuff.c
+// executes them) and the finish that turns the raw coefficients into the records the inverse DCT of jpeg_dec_host.h reads.  The
+// contract is in include/whenet_hip.h (JPEG DECODER, PROGRESSIVE).  Integers only; nothing here needs the HIP runtime: a plain
+// C++17 compiler builds this header (tools/jpeg_prog_host_check.cpp does, under the host sanitizers).
+//
+// Reference: demo.py (`cv2.imread` of Sample/*.jpeg): stills are where progressive streams are common.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "jpeg_dec_host.h"
+
+namespace whenet {
+
+constexpr int JPEG_PROG_MAX_SCANS = WHENET_JPEG_PROG_MAX_SCANS;
+constexpr int JPEG_PROG_LANES = 16;      // items per workgroup of the scan kernel: the item lists are padded to it scan by scan
+enum { JPEG_PROG_DC_FIRST = 0, JPEG_PROG_DC_REFINE = 1, JPEG_PROG_AC_FIRST = 2, JPEG_PROG_AC_REFINE = 3 };
+// the counter block of whenet_jpeg_progressive_coefficients_host
+enum { JPEG_PROG_CNT_SCANS = 0, JPEG_PROG_CNT_ITEMS, JPEG_PROG_CNT_LEVELS, JPEG_PROG_CNT_EOBRUN, JPEG_PROG_CNT_REFINE_ZRL,
+       JPEG_PROG_CNT_CORRECTION_BITS, JPEG_PROG_CNT_CORRECTIONS, JPEG_PROG_CNT_WORDS = 8 };
+
+// A scan as the decode reads it (host and device).  Positions are relative to the plan's first entropy byte.
+struct JpegProgScan {
+    int32_t ns, comp[3];          // its components: indices into the frame's
+    int32_t ss, se, ah, al, kind;
+    int32_t ri, intervals;        // in the SCAN's MCUs: the frame's for an interleaved scan, single blocks for a scan of one component
+    int32_t units;                // the scan's MCUs
+    int32_t bw, bh;               // a scan of one component: its block grid ceil(cw / 8) x ceil(ch / 8), raster order
+    int32_t first_item, level;    // level: 0-based here
+    int32_t data_off, data_end;   // its entropy data
+    int32_t list_off, list_cnt;   // its share of the item list (list_cnt: a multiple of JPEG_PROG_LANES)
+    int32_t items;                // the intervals listed there: 0 .. items - 1, those whose start the data holds, up to the first one
+                                  // the scan's markers make bad
+};
+// One (scan, interval) item.  scan < 0: padding
+struct JpegProgItem {
+    int32_t scan, interval, start, end;
+};
+
+struct JpegProgPlan {
+    bool baseline = false;                     // SOF0: one scan, decoded by the baseline decoder
+    std::vector<whenet_jpeg_scan_t> scans;     // the public records
+    std::vector<JpegProgScan> dev;
+    std::vector<JpegDecHuff> huff;             // 3 per scan: the table of the scan's i-th component (DC first), [0] for an AC scan
+    int16_t qz[3][64] = {};                    // per component: its quantiser in ZIGZAG order
+    std::vector<JpegProgItem> items;           // level by level, inside a level scan by scan, each scan's share padded
+    std::vector<int32_t> level_off, level_cnt; // a level's share of `items`
+    int levels = 0, total_items = 0;
+    int first_bad = JPEG_DEC_NO_BAD;           // what the host knows before the decode: a bad marker's item, or total_items where the
+                                               // progression is incomplete
+    int64_t data_base = 0, data_bytes = 0;     // the stream's bytes [data_base, data_base + data_bytes): every scan's entropy data
+};
+
+inline void jpeg_prog_build_huff(const uint8_t counts[16], const uint8_t values[256], JpegDecHuff& h) {
+    std::memset(&h, 0, sizeof(h));
+    std::memcpy(h.vals, values, 256);
+    unsigned code = 0;
+    int n = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int cnt = counts[l - 1];
+        h.valoff[l] = n - int(code);
+        h.maxcode[l] = cnt > 0 ? int(code) + cnt - 1 : -1;
+        for (int i = 0; i < cnt; ++i, ++n, ++code)
+            if (l <= JPEG_DEC_LOOK_BITS) {
+                const int first = int(code) << (JPEG_DEC_LOOK_BITS - l);
+                for (int j = 0; j < (1 << (JPEG_DEC_LOOK_BITS - l)); ++j) h.look[first + j] = uint16_t((l << 8) | h.vals[n]);
+            }
+        code <<= 1;
+    }
+    h.maxcode[0] = -1, h.valoff[0] = 0;
+}
+
+// ---- parse (pure host) ----
+// SOI .. the last scan into `in` and `plan`; returns nullptr, or the reason the stream is refused.  A SOF0 stream is jpeg_parse's
+// (plan.baseline, one scan record).  For SOF2 `in` holds the frame, the quantisers and the first scan's data_offset and DRI; its
+// Huffman fields stay empty (the tables change between scans: they are the plan's).
+inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in, JpegProgPlan& plan) {
+    plan = JpegProgPlan();
+    std::memset(&in, 0, sizeof(in));
+    if (size > JPEG_DEC_MAX_BYTES) return "a stream above 2^31 - 1 bytes";
+    if (size < 4 || d[0] != 0xFF || d[1] != 0xD8) return "no SOI marker at the start: not a JPEG stream";
+    {   // which frame?  (the first SOFn decides; anything else is the baseline parser's to refuse)
+        int64_t p = 2;
+        int sof = 0;
+        while (p + 4 <= size && d[p] == 0xFF) {
+            const int m = d[p + 1];
+            if (m == 0xFF) {
+                ++p;
+                continue;
+            }
+            if (m == 0xD8 || m == 0xD9 || m == 0x01 || (m >= 0xD0 && m <= 0xD7) || m == 0xDA) break;
+            if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+                sof = m;
+                break;
+            }
+            p += 2 + ((d[p + 2] << 8) | d[p + 3]);
+        }
+        if (sof != 0xC2) {
+            const char* bad = jpeg_parse(d, size, in);
+            if (bad != nullptr) return bad;
+            plan.baseline = true;
+            whenet_jpeg_scan_t s{};
+            s.ns = in.components;
+            for (int c = 0; c < in.components; ++c) s.comp[c] = c, s.dc[c] = in.dc[c], s.ac[c] = in.ac[c];
+            s.ss = 0, s.se = 63, s.level = 1;
+            s.ri = jpeg_dec_geom(in).ri, s.intervals = in.intervals;
+            s.data_offset = in.data_offset, s.data_bytes = size - in.data_offset;
+            plan.scans.push_back(s);
+            plan.levels = 1, plan.total_items = in.intervals;
+            return nullptr;
+        }
+    }
+    uint8_t hc[2][4][16], hv[2][4][256];      // the Huffman tables in force: [class][id]
+    bool hp[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    int dht_seen = 0;
+    int cur_al[3][64];                        // per component and coefficient: -1 (no scan yet) or the Al it has reached
+    for (auto& c : cur_al)
+        for (int& v : c) v = -1;
+    int comp_id[3] = {0, 0, 0};
+    bool sof = false;
+    int dri = 0;
+    JpegDecGeom g{};
+    int64_t p = 2;
+    for (;;) {
+        const bool scanned = !plan.dev.empty();
+        // behind the first scan the end of the bytes ends the stream (an incomplete progression is decoded from what it holds)
+        if (p + 2 > size) {
+            if (scanned) break;
+            return "the header ends before SOS (truncated)";
+        }
+        if (d[p] != 0xFF) return "a marker is expected in the header";
+        const int m = d[p + 1];
+        if (m == 0xFF) {
+            ++p;
+            continue;
+        }
+        p += 2;
+        if (m == 0xD9) {
+            if (scanned) break;
+            return "EOI before SOS: the stream has no scan";
+        }
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) return "an unexpected marker without a segment in the header";
+        if (p + 2 > size) {
+            if (scanned) break;
+            return "the header ends before SOS (truncated)";
+        }
+        const int len = (d[p] << 8) | d[p + 1];
+        if (len < 2 || p + len > size) {
+            if (scanned) break;
+            return "a segment passes the end of the stream (truncated)";
+        }
+        const uint8_t* s = d + p + 2;
+        const int n = len - 2;
+        if (m == 0xC2) {
+            if (sof) return "a second SOF2";
+            if (n < 6) return "a short SOF2";
+            if (s[0] == 12) return "12-bit samples: 8-bit streams only";
+            if (s[0] != 8) return "the sample precision is not 8 bit";
+            in.h = (s[1] << 8) | s[2], in.w = (s[3] << 8) | s[4], in.components = s[5];
+            if (in.components == 4) return "4 components (CMYK / YCCK): 1 or 3 only";
+            if (in.components != 1 && in.components != 3) return "the frame must have 1 or 3 components";
+            if (in.h < 1 || in.w < 1 || in.h > JPEG_MAX_SIDE || in.w > JPEG_MAX_SIDE) return "frame sides must be 1..8192";
+            if (n != 6 + 3 * in.components) return "the length of SOF2 does not match its components";
+            for (int c = 0; c < in.components; ++c) {
+                comp_id[c] = s[6 + 3 * c];
+                const int hv2 = s[7 + 3 * c], tq = s[8 + 3 * c];
+                if (tq > 3) return "a quantiser id above 3";
+                in.qt[c] = tq;
+                if (in.components == 1) {
+                    in.hs = in.vs = 1;
+                } else if (c == 0) {
+                    if (hv2 != 0x22 && hv2 != 0x21 && hv2 != 0x11) return "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
+                    in.hs = hv2 >> 4, in.vs = hv2 & 15;
+                } else if (hv2 != 0x11) {
+                    return "chroma sampling must be 1x1";
+                }
+            }
+            if (in.components == 3 && (comp_id[0] == comp_id[1] || comp_id[0] == comp_id[2] || comp_id[1] == comp_id[2]))
+                return "two components of the frame share an id";
+            sof = true;
+        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4) {
+            return "a second frame header in a progressive stream";
+        } else if (m == 0xDB) {
+            if (scanned) return "a quantiser table (DQT) behind the first scan of a progressive stream";
+            for (int i = 0; i < n;) {
+                const int pq = s[i] >> 4, tq = s[i] & 15;
+                if (pq != 0) return "a 16-bit quantiser table (DQT): 8-bit tables only";
+                if (tq > 3) return "a quantiser id above 3";
+                if (i + 65 > n) return "a short DQT";
+                for (int k = 0; k < 64; ++k) {
+                    if (s[i + 1 + k] == 0) return "a quantiser of 0";
+                    in.q[tq][JPEG_ZIGZAG[k]] = s[i + 1 + k];
+                }
+                in.q_present[tq] = 1;
+                i += 65;
+            }
+        } else if (m == 0xC4) {
+            for (int i = 0; i < n;) {
+                const int tc = s[i] >> 4, th = s[i] & 15;
+                if (tc > 1 || th > 3) return "a Huffman table class above 1 or id above 3";
+                if (i + 17 > n) return "a short DHT";
+                int total = 0;
+                unsigned code = 0;
+                for (int l = 1; l <= 16; ++l) {
+                    const int cnt = s[i + l];
+                    total += cnt, code += unsigned(cnt);
+                    if (code > (1u << l)) return "a DHT whose code lengths are no prefix code";
+                    code <<= 1;
+                }
+                if (total > 256 || i + 17 + total > n) return "a short DHT";
+                std::memcpy(hc[tc][th], s + i + 1, 16);
+                std::memset(hv[tc][th], 0, 256);
+                std::memcpy(hv[tc][th], s + i + 17, size_t(total));
+                if (tc == 0)
+                    for (int k = 0; k < total; ++k)
+                        if (hv[tc][th][k] > 11) return "a DC Huffman symbol above 11";
+                hp[tc][th] = true;
+                i += 17 + total;
+            }
+            ++dht_seen;
+        } else if (m == 0xDD) {
+            if (n != 2) return "a DRI of the wrong length";
+            dri = (s[0] << 8) | s[1];
+        } else if (m == 0xDA) {
+            if (!sof) return "SOS before SOF2";
+            if (n < 1) return "a short SOS";
+            const int ns = s[0];
+            if (ns == 2) return "a scan of two components: scans hold one component or all of them";
+            if (ns != 1 && ns != in.components) return "a scan must hold one component or all of the frame's";
+            if (n != 4 + 2 * ns) return "the length of SOS does not match its components";
+            if (int(plan.dev.size()) >= JPEG_PROG_MAX_SCANS) return "more than 128 scans";
+            JpegProgScan sc{};
+            whenet_jpeg_scan_t pub{};
+            sc.ns = ns;
+            for (int i = 0; i < ns; ++i) {
+                int c = -1;
+                for (int j = 0; j < in.components; ++j)
+                    if (s[1 + 2 * i] == comp_id[j]) c = j;
+                if (c < 0 || (ns > 1 && c != i)) return "the scan's components are not the frame's, in order";
+                sc.comp[i] = c;
+                pub.comp[i] = c, pub.dc[i] = s[2 + 2 * i] >> 4, pub.ac[i] = s[2 + 2 * i] & 15;
+                if (pub.dc[i] > 3 || pub.ac[i] > 3) return "a Huffman table id above 3";
+            }
+            sc.ss = s[1 + 2 * ns], sc.se = s[2 + 2 * ns], sc.ah = s[3 + 2 * ns] >> 4, sc.al = s[3 + 2 * ns] & 15;
+            if (sc.ss > sc.se || sc.se > 63) return "a spectral selection with Ss > Se or Se > 63";
+            if (sc.ss == 0 && sc.se != 0) return "a scan of DC and AC coefficients together (Ss = 0 with Se != 0)";
+            if (sc.ss > 0 && ns > 1) return "an interleaved AC scan (Ss > 0 with several components)";
+            if (sc.ah > 13 || sc.al > 13) return "a successive approximation bit position above 13";
+            for (int i = 0; i < ns; ++i) {
+                int* const al = cur_al[sc.comp[i]];
+                if (sc.ss > 0 && al[0] < 0) return "an AC scan of a component whose DC coefficient has had no scan";
+                for (int k = sc.ss; k <= sc.se; ++k) {
+                    if (sc.ah == 0) {
+                        if (al[k] >= 0) return "a first scan of a coefficient that already had one";
+                    } else if (al[k] < 0) {
+                        return "a refinement scan of a coefficient that has had no first scan";
+                    } else if (al[k] != sc.ah || sc.al != sc.ah - 1) {
+                        return "a refinement scan whose Ah is not the coefficient's bit position, or whose Al is not Ah - 1";
+                    }
+                }
+            }
+            for (int i = 0; i < ns; ++i)
+                for (int k = sc.ss; k <= sc.se; ++k) cur_al[sc.comp[i]][k] = sc.al;
+            for (int c = 0; c < in.components; ++c)
+                if (!in.q_present[in.qt[c]]) return "a missing quantiser table (DQT)";
+            sc.kind = sc.ss == 0 ? (sc.ah == 0 ? JPEG_PROG_DC_FIRST : JPEG_PROG_DC_REFINE) : (sc.ah == 0 ? JPEG_PROG_AC_FIRST : JPEG_PROG_AC_REFINE);
+            JpegDecHuff hu[3];
+            std::memset(hu, 0, sizeof(hu));
+            if (sc.kind == JPEG_PROG_DC_FIRST) {
+                for (int i = 0; i < ns; ++i) {
+                    if (!hp[0][pub.dc[i]]) return "a missing Huffman table (DHT)";
+                    jpeg_prog_build_huff(hc[0][pub.dc[i]], hv[0][pub.dc[i]], hu[i]);
+                }
+            } else if (sc.ss > 0) {
+                if (!hp[1][pub.ac[0]]) return "a missing Huffman table (DHT)";
+                jpeg_prog_build_huff(hc[1][pub.ac[0]], hv[1][pub.ac[0]], hu[0]);
+            }
+            if (plan.dev.empty()) {
+                in.restart_interval = dri, in.data_offset = p + len;
+                g = jpeg_dec_geom(in);
+                in.intervals = g.intervals;
+            }
+            // geometry: the frame's MCUs, or the component's own block grid
+            if (ns > 1 || in.components == 1) {
+                sc.bw = g.mcu_cols, sc.bh = g.mcu_rows;
+            } else {
+                const int c = sc.comp[0];
+                const int cw = c == 0 ? in.w : (in.w + g.hs - 1) / g.hs, ch = c == 0 ? in.h : (in.h + g.vs - 1) / g.vs;
+                sc.bw = (cw + 7) / 8, sc.bh = (ch + 7) / 8;
+            }
+            sc.units = sc.bw * sc.bh;
+            sc.ri = dri > 0 && dri < sc.units ? dri : sc.units;
+            sc.intervals = (sc.units + sc.ri - 1) / sc.ri;
+            // levels: 1 + the largest level of an earlier scan that shares a component and overlaps the band
+            sc.level = 0;
+            for (const JpegProgScan& e : plan.dev) {
+                bool share = false;
+                for (int i = 0; i < ns; ++i)
+                    for (int j = 0; j < e.ns; ++j) share = share || sc.comp[i] == e.comp[j];
+                if (share && e.ss <= sc.se && sc.ss <= e.se) sc.level = std::max(sc.level, e.level + 1);
+            }
+            // the scan's end and its restart markers
+            const int64_t from = p + len;
+            if (plan.dev.empty()) plan.data_base = from;
+            // (list_off: for now the scan's place in `items`; the lists are laid out below.  An item is listed where the data holds
+            //  its start -- interval 0, and interval k + 1 behind marker k --, so the list is bounded by the bytes, never by what a
+            //  header claims: 8192 x 8192 with DRI 1 claims a million intervals per scan)
+            sc.list_off = int32_t(plan.items.size()), sc.list_cnt = 0;
+            plan.items.push_back({int32_t(plan.dev.size()), 0, int32_t(from - plan.data_base), 0});
+            int bad = JPEG_DEC_NO_BAD, k = 0;
+            int64_t q = from;
+            for (;;) {
+                const void* f = q < size ? std::memchr(d + q, 0xFF, size_t(size - q)) : nullptr;
+                if (f == nullptr) {
+                    q = size;
+                    break;
+                }
+                q = static_cast<const uint8_t*>(f) - d;
+                if (q + 1 >= size) {      // a lone 0xFF at the end: the bit reader stops there
+                    q = size;
+                    break;
+                }
+                const int b = d[q + 1];
+                if (b == 0) {
+                    q += 2;
+                } else if (b == 0xFF) {
+                    ++q;
+                } else if (b >= 0xD0 && b <= 0xD7) {
+                    if (k >= sc.intervals - 1) bad = std::min(bad, sc.intervals - 1);
+                    else if ((b & 7) != (k & 7)) bad = std::min(bad, k);
+                    if (k + 1 < sc.intervals) plan.items.push_back({int32_t(plan.dev.size()), k + 1, int32_t(q + 2 - plan.data_base), 0});
+                    ++k, q += 2;
+                } else {
+                    break;      // another marker: the scan ends in front of it
+                }
+            }
+            if (k < sc.intervals - 1) bad = std::min(bad, k);
+            sc.data_off = int32_t(from - plan.data_base), sc.data_end = int32_t(q - plan.data_base);
+            sc.first_item = plan.total_items;
+            plan.total_items += sc.intervals;
+            if (bad != JPEG_DEC_NO_BAD) plan.first_bad = std::min(plan.first_bad, sc.first_item + bad);
+            plan.data_bytes = q - plan.data_base;
+            // the intervals behind the one the markers make bad are not decoded: not listed either
+            while (plan.items.back().interval > bad) plan.items.pop_back();
+            sc.items = int32_t(plan.items.size()) - sc.list_off;
+            for (int i = 0; i < sc.items; ++i) plan.items[size_t(sc.list_off + i)].end = sc.data_end;
+            pub.ns = ns, pub.ss = sc.ss, pub.se = sc.se, pub.ah = sc.ah, pub.al = sc.al, pub.tables = dht_seen;
+            pub.ri = sc.ri, pub.intervals = sc.intervals, pub.level = sc.level + 1, pub.first_item = sc.first_item, pub.progressive = 1;
+            pub.data_offset = from, pub.data_bytes = q - from;
+            plan.scans.push_back(pub), plan.dev.push_back(sc);
+            for (const JpegDecHuff& h : hu) plan.huff.push_back(h);
+            p = q;
+            continue;
+        } else if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
+            // APPn, COM: skipped
+        } else {
+            return "an unexpected marker in the header";
+        }
+        p += len;
+    }
+    // the item lists: level by level, a scan's share padded to whole workgroups
+    std::vector<JpegProgItem> flat;
+    flat.swap(plan.items);
+    for (const JpegProgScan& sc : plan.dev) plan.levels = std::max(plan.levels, sc.level + 1);
+    for (int l = 0; l < plan.levels; ++l) {
+        plan.level_off.push_back(int32_t(plan.items.size()));
+        for (JpegProgScan& sc : plan.dev) {
+            if (sc.level != l) continue;
+            const int from = sc.list_off;
+            sc.list_off = int32_t(plan.items.size());
+            for (int i = 0; i < sc.items; ++i) plan.items.push_back(flat[size_t(from + i)]);
+            while (plan.items.size() % JPEG_PROG_LANES) plan.items.push_back({-1, 0, 0, 0});
+            sc.list_cnt = int32_t(plan.items.size()) - sc.list_off;
+        }
+        plan.level_cnt.push_back(int32_t(plan.items.size()) - plan.level_off.back());
+    }
+    for (int c = 0; c < in.components; ++c)
+        for (int k = 0; k < 64; ++k) {
+            plan.qz[c][k] = int16_t(in.q[in.qt[c]][JPEG_ZIGZAG[k]]);
+            if (cur_al[c][k] != 0) plan.first_bad = std::min(plan.first_bad, plan.total_items);      // incomplete progression
+        }
+    return nullptr;
+}
+
+// ---- the scan decode (host and device) ----
+// k <= 16 raw bits; false: the data ends inside them
+WHENET_HD inline bool jpeg_prog_bits(JpegBitReader& br, int k, int& v) {
+    v = 0;
+    if (k == 0) return true;
+    br.fill();
+    if (k > br.n) return false;
+    v = int((br.acc >> (br.n - k)) & ((1u << k) - 1u));
+    br.n -= k;
+    return true;
+}
+WHENET_HD inline int16_t jpeg_prog_i16(int v) { return int16_t(jpeg_dec_clamp(v, -32768, 32767)); }
+
+// the record of unit u of a scan (b: the block inside the MCU of an interleaved scan)
+WHENET_HD inline long long jpeg_prog_record(const JpegDecGeom& g, const JpegProgScan& sc, int u, int b) {
+    if (sc.ns > 1) return (long long)(u) * g.bpm + b;
+    if (g.comps == 1) return u;
+    const int by = u / sc.bw, bx = u - by * sc.bw;
+    if (sc.comp[0] == 0) return ((long long)(by / g.vs) * g.mcu_cols + bx / g.hs) * g.bpm + (by % g.vs) * g.hs + bx % g.hs;
+    return ((long long)(by) * g.mcu_cols + bx) * g.bpm + (g.bpm - 2) + (sc.comp[0] - 1);
+}
+
+// one correction bit for a coefficient that is already non-zero; false: the data ends inside it
+WHENET_HD inline bool jpeg_prog_correct(JpegBitReader& br, int16_t& coef, int p1, long long* cnt) {
+    int bit;
+    if (!jpeg_prog_bits(br, 1, bit)) return false;
+    if (cnt != nullptr) ++cnt[JPEG_PROG_CNT_CORRECTION_BITS];
+    if (bit != 0 && (int(coef) & p1) == 0) {
+        coef = jpeg_prog_i16(int(coef) + (coef >= 0 ? p1 : -p1));
+        if (cnt != nullptr) ++cnt[JPEG_PROG_CNT_CORRECTIONS];
+    }
+    return true;
+}
+
+// One (scan, interval) item into raw ([block][64] int16, zigzag order inside a record).  Only the int16s of the scan's band are
+// stored: scans of one level write other bands of the same records at the same time.  false: the interval is damaged; the block in
+// hand keeps what was written, the rest of the interval is not touched.
+// (stage: nullptr, or 64 int16 of fast memory: an AC refinement copies its band there, works on it and stores the band back.
+//  cnt: nullptr, or the counter block)
+WHENET_HD inline bool jpeg_prog_item(const uint8_t* data, int start, int end, const JpegProgScan& sc, const JpegDecHuff* huff, const JpegDecGeom& g,
+                                     int interval, int16_t* raw, int16_t* stage = nullptr, long long* cnt = nullptr) {
+    JpegBitReader br(data, start, end);
+    const int first = interval * sc.ri;
+    const int last = first + sc.ri < sc.units ? first + sc.ri : sc.units;
+    const int p1 = 1 << sc.al;
+    if (sc.kind == JPEG_PROG_DC_FIRST) {
+        int pred0 = 0, pred1 = 0, pred2 = 0;
+        const int nb = sc.ns > 1 ? g.bpm : 1, ny = g.bpm - 2;
+        for (int u = first; u < last; ++u)
+            for (int b = 0; b < nb; ++b) {
+                const int i = sc.ns > 1 && b >= ny ? b - ny + 1 : 0;      // the scan's i-th component
+                int v;
+                const int s = br.decode(huff[i]);
+                if (s < 0 || !br.receive(s & 15, v)) return false;
+                int& pred = i == 0 ? pred0 : (i == 1 ? pred1 : pred2);
+                pred = jpeg_dec_clamp(pred + v, -32768, 32767);
+                raw[jpeg_prog_record(g, sc, u, b) * 64] = jpeg_prog_i16(pred * p1);
+            }
+        return true;
+    }
+    if (sc.kind == JPEG_PROG_DC_REFINE) {
+        const int nb = sc.ns > 1 ? g.bpm : 1;
+        for (int u = first; u < last; ++u)
+            for (int b = 0; b < nb; ++b) {
+                int bit;
+                if (!jpeg_prog_bits(br, 1, bit)) return false;
+                int16_t* const rec = raw + jpeg_prog_record(g, sc, u, b) * 64;
+                if (bit != 0) rec[0] = int16_t(rec[0] | p1);
+            }
+        return true;
+    }
+    int eobrun = 0;
+    if (sc.kind == JPEG_PROG_AC_FIRST) {
+        for (int u = first; u < last; ++u) {
+            if (eobrun > 0) {
+                --eobrun;
+                continue;
+            }
+            int16_t* const rec = raw + jpeg_prog_record(g, sc, u, 0) * 64;
+            for (int k = sc.ss; k <= sc.se;) {
+                const int sym = br.decode(huff[0]);
+                if (sym < 0) return false;
+                const int r = sym >> 4, s = sym & 15;
+                int v;
+                if (s != 0) {
+                    k += r;
+                    if (k > sc.se || !br.receive(s, v)) return false;
+                    rec[k] = jpeg_prog_i16(v * p1);
+                    ++k;
+                } else if (r == 15) {
+                    k += 16;
+                    if (k > sc.se + 1) return false;
+                } else {
+                    if (!jpeg_prog_bits(br, r, v)) return false;
+                    eobrun = (1 << r) + v;
+                    if (cnt != nullptr && eobrun > cnt[JPEG_PROG_CNT_EOBRUN]) cnt[JPEG_PROG_CNT_EOBRUN] = eobrun;
+                    if (u + eobrun > last) return false;      // the run passes the interval's last block
+                    --eobrun;
+                    break;
+                }
+            }
+        }
+        return true;
+    }
+    // AC refinement (G.1.2.3)
+    for (int u = first; u < last; ++u) {
+        int16_t* const rec = raw + jpeg_prog_record(g, sc, u, 0) * 64;
+        int16_t* const w = stage != nullptr ? stage : rec;
+        if (stage != nullptr)
+            for (int k = sc.ss; k <= sc.se; ++k) stage[k] = rec[k];
+        bool ok = true;
+        int k = sc.ss;
+        if (eobrun == 0) {
+            while (k <= sc.se) {
+                const int sym = br.decode(huff[0]);
+                if (sym < 0) {
+                    ok = false;
+                    break;
+                }
+                int r = sym >> 4, s = sym & 15, v = 0;
+                if (s != 0) {
+                    if (s != 1 || !jpeg_prog_bits(br, 1, v)) {
+                        ok = false;
+                        break;
+                    }
+                    v = v != 0 ? p1 : -p1;
+                } else if (r != 15) {
+                    if (!jpeg_prog_bits(br, r, v)) {
+                        ok = false;
+                        break;
+                    }
+                    eobrun = (1 << r) + v;
+                    if (cnt != nullptr && eobrun > cnt[JPEG_PROG_CNT_EOBRUN]) cnt[JPEG_PROG_CNT_EOBRUN] = eobrun;
+                    if (u + eobrun > last) ok = false, eobrun = 0;
+                    break;
+                } else if (cnt != nullptr) {
+                    ++cnt[JPEG_PROG_CNT_REFINE_ZRL];
+                }
+                // over r coefficients without a history; every one with a history on the way reads its correction bit
+                bool placed = false;
+                for (; k <= sc.se; ++k) {
+                    if (w[k] != 0) {
+                        if (!jpeg_prog_correct(br, w[k], p1, cnt)) {
+                            ok = false;
+                            break;
+                        }
+                    } else if (--r < 0) {
+                        placed = true;
+                        break;
+                    }
+                }
+                if (!ok) break;
+                if (!placed) {      // the run passes Se
+                    ok = false;
+                    break;
+                }
+                if (s != 0) w[k] = jpeg_prog_i16(v);
+                ++k;
+            }
+        }
+        if (ok && eobrun > 0) {
+            for (; k <= sc.se; ++k)
+                if (w[k] != 0 && !jpeg_prog_correct(br, w[k], p1, cnt)) {
+                    ok = false;
+                    break;
+                }
+            --eobrun;
+        }
+        if (stage != nullptr)
+            for (int j = sc.ss; j <= sc.se; ++j) rec[j] = stage[j];
+        if (!ok) return false;
+    }
+    return true;
+}
+
+// the finish of one value: record[natural k] = clamp(raw[zigzag k] x Q[k], -2048, 2047)
+WHENET_HD inline int16_t jpeg_prog_finish_value(int raw, int q) { return int16_t(jpeg_dec_clamp(raw * q, -2048, 2047)); }
+
+// ---- the host statement ----
+struct JpegProgResult {
+    std::vector<int16_t> raw, coef;      // [blocks][64]: zigzag order as the scans left them; natural order, dequantised, clamped
+    long long cnt[JPEG_PROG_CNT_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// every scan in stream order (a scan depends on earlier scans only, and the scans of one level touch different values), then the
+// finish; status[0] = WHENET_OK or WHENET_EFORMAT, status[1] = the smallest bad flat item (the item count for an incomplete
+// progression) or -1
+inline void jpeg_prog_coefficients_host(const whenet_jpeg_info_t& in, const JpegProgPlan& plan, const uint8_t* data, JpegProgResult& out,
+                                        int32_t status[2]) {
+    const JpegDecGeom g = jpeg_dec_geom(in);
+    const size_t blocks = size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm);
+    out.raw.assign(blocks * 64, 0), out.coef.assign(blocks * 64, 0);
+    int bad = plan.first_bad;
+    int16_t stage[64];
+    for (const JpegProgScan& sc : plan.dev)
+        for (int i = 0; i < sc.items; ++i) {
+            const JpegProgItem& it = plan.items[size_t(sc.list_off + i)];
+            const size_t s = size_t(&sc - plan.dev.data());
+            if (!jpeg_prog_item(data, it.start, it.end, sc, plan.huff.data() + 3 * s, g, it.interval, out.raw.data(), stage, out.cnt))
+                bad = std::min(bad, sc.first_item + it.interval);
+        }
+    for (size_t b = 0; b < blocks; ++b) {
+        const int bi = int(b % size_t(g.bpm)), c = g.comps == 1 || bi < g.bpm - 2 ? 0 : bi - (g.bpm - 2) + 1;
+        for (int k = 0; k < 64; ++k) out.coef[b * 64 + JPEG_ZIGZAG[k]] = jpeg_prog_finish_value(out.raw[b * 64 + size_t(k)], plan.qz[c][k]);
+    }
+    out.cnt[JPEG_PROG_CNT_SCANS] = (long long)(plan.dev.size()), out.cnt[JPEG_PROG_CNT_ITEMS] = plan.total_items;
+    out.cnt[JPEG_PROG_CNT_LEVELS] = plan.levels;
+    status[0] = bad == JPEG_DEC_NO_BAD ? WHENET_OK : WHENET_EFORMAT;
+    status[1] = bad == JPEG_DEC_NO_BAD ? -1 : bad;
+}
+
+// finished records -> the padded component planes by the rule's inverse DCT
+inline void jpeg_prog_planes_host(const JpegDecGeom& g, const std::vector<int16_t>& coef, JpegDecPlanes& out, int rule) {
+    for (int c = 0; c < g.comps; ++c) out.plane[c].assign(size_t(g.plane_pitch[c]) * size_t(g.plane_rows[c]), 0);
+    const long long mcus = (long long)(g.mcu_cols) * g.mcu_rows;
+    for (long long m = 0; m < mcus; ++m)
+        for (int b = 0; b < g.bpm; ++b) {
+            int comp, y0, x0;
+            uint8_t smp[8][8];
+            jpeg_dec_block_origin(g, m, b, comp, y0, x0);
+            jpeg_dec_block_samples(coef.data() + (size_t(m) * size_t(g.bpm) + size_t(b)) * 64, rule, smp);
+            uint8_t* dst = out.plane[comp].data() + size_t(y0) * size_t(g.plane_pitch[comp]) + size_t(x0);
+            for (int y = 0; y < 8; ++y) std::memcpy(dst + size_t(y) * size_t(g.plane_pitch[comp]), smp[y], 8);
+        }
+}
+
+// a whole stream -> planes: a SOF0 stream by the baseline statement, a SOF2 stream by the above
+inline void jpeg_prog_decode_planes_host(const whenet_jpeg_info_t& in, const JpegProgPlan& plan, const uint8_t* d, int64_t size, JpegDecPlanes& out,
+                                         int32_t status[2], int rule) {
+    if (plan.baseline) {
+        jpeg_dec_planes_host(in, d + in.data_offset, int(size - in.data_offset), out, status, rule);
+        return;
+    }
+    JpegProgResult r;
+    jpeg_prog_coefficients_host(in, plan, d + plan.data_base, r, status);
+    jpeg_prog_planes_host(jpeg_dec_geom(in), r.coef, out, rule);
+}
+
+}  // namespace whenet

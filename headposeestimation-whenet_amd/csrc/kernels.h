@@ -11,6 +11,7 @@
 #include "jpeg_dec_host.h"
 #include "jpeg_dec_seg_host.h"
 #include "jpeg_dec_clip_host.h"
+#include "jpeg_prog_host.h"
 
 namespace whenet {
 
@@ -723,6 +724,43 @@ void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream);
 JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
                           const whenet_surface_t& dst, int channel_order, int32_t* d_status, int rule = JPEG_RULE_OWN);
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream);
+// the stages behind the entropy decode on their own: the inverse DCT of a.coef (which writes the status words from a.meta[1]) and
+// the colour stage of the record's rule and destination
+void launch_jpeg_decode_tail(const JpegDecArgs& a, hipStream_t stream);
+
+// ---- jpeg_prog.hip ----------------------------------------------------------------------
+// The progressive decoder's entropy stage (include/whenet_hip.h, JPEG DECODER, PROGRESSIVE; the arithmetic is jpeg_prog_host.h's)
+// in front of launch_jpeg_decode_tail.  JpegProgLayout lays one allocation out: scans | huff | qz | items | data are the plan's one
+// upload; meta | raw (one memset); coef; the padded planes.
+//   whenet_jpeg_prog_scan_kernel    one (scan, interval) item per decoding lane, 16 per 64-lane workgroup, all of ONE scan (the
+//            lists are padded): the scan's record and its <= 3 JpegDecHuff lie in LDS, the scan kind is uniform.  A lane stores
+//            int16s inside its scan's band only; a damaged item raises meta[0] = JPEG_DEC_NO_BAD - item (atomicMax).
+//   whenet_jpeg_prog_finish_kernel  8 lanes per block: raw (zigzag) x Q, clamp -> coef (natural order), 16-byte loads and stores
+//            through LDS; folds meta[1] = the first bad item (the decode's, or what the host knew: first_bad).
+// levels = 1: a launch per level; 0: a launch per scan in stream order.  scan_launches (may be nullptr): += the launches.
+struct JpegProgLayout {
+    size_t scans, huff, qz, items, data, upload_bytes, meta, raw, zero_bytes, coef, coef_bytes, plane[3], bytes;
+    JpegProgLayout(const JpegDecGeom& g, const JpegProgPlan& plan);
+};
+struct JpegProgArgs {
+    JpegDecGeom g;
+    const JpegProgScan* scans;
+    const JpegDecHuff* huff;       // 3 per scan
+    const int16_t* qz;             // [3][64]
+    const JpegProgItem* items;
+    const uint8_t* data;
+    int nbytes;
+    int16_t* raw;
+    int16_t* coef;
+    int32_t* meta;
+    int first_bad;
+};
+// the plan's upload, laid out at `stage` (host memory of lay.upload_bytes; data: the stream's bytes from plan.data_base on)
+void jpeg_prog_stage(const JpegProgPlan& plan, const JpegProgLayout& lay, const uint8_t* data, uint8_t* stage);
+// memset + scan launches + finish + tail.  a: a baseline record over the same scratch (coef, meta, planes, destination, rule)
+void launch_jpeg_decode_progressive(const JpegDecArgs& a, const JpegProgPlan& plan, const JpegProgLayout& lay, void* d_scratch, int levels,
+                                    hipStream_t stream, int64_t* scan_launches);
+
 // A CLIP of 1..16 streams, every stage in ONE launch for all of them: the same bodies, a workgroup first finds its frame in the
 // prefix sums of the per-frame workgroup counts (JpegClipGrid, by value) and reads that frame's record from d_recs -- device
 // memory, records JPEG_CLIP_RECORD_BYTES apart (jpeg_dec_clip_host.h), part of the clip's one upload.  h_recs: the same records on

@@ -56,6 +56,17 @@ class JpegInfoC(C.Structure):
                 ("huff_counts", (C.c_uint8 * 16) * 4), ("huff_values", (C.c_uint8 * 256) * 4), ("huff_present", C.c_uint8 * 4)]
 
 
+class JpegScanC(C.Structure):
+    """whenet_jpeg_scan_t: one scan of a (progressive) JPEG stream."""
+    _fields_ = [("ns", C.c_int32), ("comp", C.c_int32 * 3), ("ss", C.c_int32), ("se", C.c_int32), ("ah", C.c_int32), ("al", C.c_int32),
+                ("dc", C.c_int32 * 3), ("ac", C.c_int32 * 3), ("tables", C.c_int32), ("ri", C.c_int32), ("intervals", C.c_int32),
+                ("level", C.c_int32), ("first_item", C.c_int32), ("progressive", C.c_int32), ("data_offset", C.c_int64),
+                ("data_bytes", C.c_int64)]
+
+
+JPEG_PROG_MAX_SCANS = 128
+JPEG_PROG_COUNTERS = ("scans", "items", "levels", "max_eobrun", "refine_zrl", "correction_bits", "corrections")
+
 _PROTOS = {
     "whenet_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_P)]),
     "whenet_create_from_memory": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -157,6 +168,13 @@ _PROTOS = {
     "whenet_op_jpeg_decode_clip_rule": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "whenet_frame_begin_jpeg_rule": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_clip_begin_jpeg_rule": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
+    "whenet_jpeg_parse_scans": (C.c_int, [_P, C.c_int64, C.POINTER(JpegInfoC), C.POINTER(JpegScanC), C.c_int, C.POINTER(C.c_int)]),
+    "whenet_jpeg_decode_progressive_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, _P]),
+    "whenet_jpeg_decode_progressive_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, C.c_int, _P]),
+    "whenet_jpeg_progressive_coefficients_host": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "whenet_op_jpeg_decode_progressive": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, _P, _P]),
+    "whenet_frame_begin_jpeg_progressive": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
+    "whenet_jpeg_progressive_counters": (C.c_int, [_P, C.POINTER(C.c_int64 * 4)]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -609,6 +627,55 @@ def jpeg_parse(data) -> JpegInfoC:
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return info
+
+
+def _host_rc(lib, rc):
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+
+
+def jpeg_parse_scans(data):
+    """`whenet_jpeg_parse_scans`: (the header, the list of `JpegScanC` records) of a baseline OR progressive stream.  ValueError with
+    the reason for a stream neither decoder accepts.  Pure host arithmetic inside the library."""
+    lib = load()
+    a = _stream_array(data)
+    info, scans, n = JpegInfoC(), (JpegScanC * JPEG_PROG_MAX_SCANS)(), C.c_int(0)
+    _host_rc(lib, lib.whenet_jpeg_parse_scans(_ptr(a) if a.size else None, int(a.size), C.byref(info), scans, JPEG_PROG_MAX_SCANS, C.byref(n)))
+    return info, [scans[i] for i in range(n.value)]
+
+
+def jpeg_decode_progressive_host(data, surface: SurfaceC, bgr: bool, rule: str = "own") -> np.ndarray:
+    """`whenet_jpeg_decode_progressive_host` into a host surface: the two status words (OK or EFORMAT, the first bad item or -1)."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    _host_rc(lib, lib.whenet_jpeg_decode_progressive_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB,
+                                                          jpeg_rule_code(rule), _ptr(status)))
+    return status
+
+
+def jpeg_decode_progressive_planes_host(data, planes, rule: str = "own") -> np.ndarray:
+    """`whenet_jpeg_decode_progressive_planes_host` into uint8 2-D arrays (contiguous rows): the two status words."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    ptrs = (_P * 3)(*[p.ctypes.data for p in planes])
+    pitch = np.array([p.strides[0] for p in planes] + [0] * (3 - len(planes)), np.int32)
+    _host_rc(lib, lib.whenet_jpeg_decode_progressive_planes_host(_ptr(a) if a.size else None, int(a.size), ptrs, _ptr(pitch),
+                                                                 jpeg_rule_code(rule), _ptr(status)))
+    return status
+
+
+def jpeg_progressive_coefficients_host(data, blocks: int):
+    """`whenet_jpeg_progressive_coefficients_host`: (finished records int16 [blocks,64] in natural order, raw records int16 [blocks,64]
+    in zigzag order, the counters as a dict, the two status words) of a SOF2 stream of `blocks` blocks."""
+    lib = load()
+    a = _stream_array(data)
+    coef, raw = np.zeros((blocks, 64), np.int16), np.zeros((blocks, 64), np.int16)
+    cnt, status = np.zeros(8, np.int64), np.zeros(2, np.int32)
+    _host_rc(lib, lib.whenet_jpeg_progressive_coefficients_host(_ptr(a) if a.size else None, int(a.size), _ptr(coef), _ptr(raw), int(blocks),
+                                                                _ptr(cnt), _ptr(status)))
+    return coef, raw, {k: int(cnt[i]) for i, k in enumerate(JPEG_PROG_COUNTERS)}, status
 
 
 def jpeg_decode_host(data, surface: SurfaceC, bgr: bool) -> np.ndarray:
@@ -1426,6 +1493,22 @@ class Handle:
                                                          _ptr(status), _ptr(stats)))
         return status, stats
 
+    def op_jpeg_decode_progressive(self, data, surface: SurfaceC, bgr: bool, rule=None):
+        """`whenet_op_jpeg_decode_progressive`: the kernels alone on a baseline or progressive stream: (the two status words, the
+        statistics int64 [8]: for a progressive stream items, levels, scans, scan-kernel launches)."""
+        a = _stream_array(data)
+        status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+        self._check(self._lib.whenet_op_jpeg_decode_progressive(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
+                                                                BGR if bgr else RGB, jpeg_rule_code(rule), _ptr(status), _ptr(stats)))
+        return status, stats
+
+    def jpeg_progressive_counters(self) -> dict:
+        """Host-side counts of the progressive decodes the handle's engines enqueued: {"decodes", "launches" of the scan kernel (a
+        level each by default), "scans" in them}."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.whenet_jpeg_progressive_counters(self._h, C.byref(out)))
+        return {"decodes": int(out[0]), "launches": int(out[1]), "scans": int(out[2])}
+
     def jpeg_decode_counters(self) -> dict:
         """Host-side counts of the JPEG decodes the handle's engines launched in each form of the entropy stage:
         {"interval": form 0, "segmented": form 1} (options "jpeg_entropy", "jpeg_seg_bytes")."""
@@ -1439,7 +1522,7 @@ class Handle:
         self._check(self._lib.whenet_jpeg_decode_device(self._h, C.byref(info), _P(int(d_entropy)), int(nbytes), C.byref(surface),
                                                         BGR if bgr else RGB, _P(int(d_status)), _stream(stream)))
 
-    def frame_begin_jpeg(self, data, status: np.ndarray, bgr: bool = True, rule=None) -> int:
+    def frame_begin_jpeg(self, data, status: np.ndarray, bgr: bool = True, rule=None, progressive=None) -> int:
         """`whenet_frame_begin_jpeg`: `frame_begin` from the bytes of a JPEG stream, decoded on the device.  status = int32 [2], complete
         when the ticket's collect call returns; it must stay alive until then.  rule: None (the handle's option "jpeg_rule"), or "own" /
         "libjpeg" for this call (`whenet_frame_begin_jpeg_rule`)."""
@@ -1447,6 +1530,10 @@ class Handle:
         if status.dtype != np.int32 or status.size != 2 or not status.flags.c_contiguous:
             raise ValueError("status must be a contiguous int32 [2] array")
         t = C.c_int(-1)
+        if progressive:      # (None / False: the handle's option "jpeg_progressive" decides, as in the calls below)
+            self._check(self._lib.whenet_frame_begin_jpeg_progressive(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB,
+                                                                      jpeg_rule_code(rule), C.byref(t), _ptr(status)))
+            return t.value
         if rule is not None:
             self._check(self._lib.whenet_frame_begin_jpeg_rule(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB,
                                                                jpeg_rule_code(rule), C.byref(t), _ptr(status)))

@@ -284,22 +284,24 @@ class FramePipeline:
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
 
-    def begin_jpeg(self, data, rule=None) -> "JpegStatus":
+    def begin_jpeg(self, data, rule=None, progressive=None) -> "JpegStatus":
         """`begin()` from the bytes of a baseline JPEG stream (a still, or one frame of an MJPG file: `whenet_hip.mjpeg.MJPGReader`):
         what stands for `cv2.imread` / `cap.read()`.  Only the compressed bytes cross the link; the frame is decoded on the device
         (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
-        `begin(jpeg.decode_host(data, bgr=...))`.  A stream the decoder does not accept (progressive, arithmetic, 12 bit, ...) is a
+        `begin(jpeg.decode_host(data, bgr=...))`.  A stream the decoder does not accept (progressive unless turned on, arithmetic, 12 bit, ...) is a
         ValueError with the reason and takes no place.  Returns a `JpegStatus`, valid after the frame's `collect()`: damaged entropy
         data does not raise, it yields a defined frame and `ok == False`.  The entropy stage's form follows the handle's options
         "jpeg_entropy" (0: an interval per lane, 1: segmented, 2: auto, the default) and "jpeg_seg_bytes"; the frame is the same.
         The decode rule follows the handle's option "jpeg_rule" (0: the project's own, the default; 1: libjpeg's bytes, what
         `cv2.imread` gives) unless `rule` says "own" or "libjpeg" for this frame; the frame is then what
-        `jpeg.decode_host(data, rule=...)` makes."""
+        `jpeg.decode_host(data, rule=...)` makes.  `progressive`: True also accepts a progressive (SOF2) stream -- the frame is then
+        `jpeg.decode_host(data, progressive=True, rule=...)`, and `JpegStatus.interval` is the flat (scan, interval) item; None
+        (the default) follows the handle's option "jpeg_progressive" (0: refused, the default)."""
         self._check_can_begin()
         _lib.jpeg_rule_code(rule)
-        info = _lib.jpeg_parse(data)
+        info = _lib.jpeg_parse(data) if progressive is False else _lib.jpeg_parse_scans(data)[0]
         st = JpegStatus()
-        ticket = self._h.frame_begin_jpeg(data, st._status, bgr=self._bgr, rule=rule)
+        ticket = self._h.frame_begin_jpeg(data, st._status, bgr=self._bgr, rule=rule, progressive=progressive)
         if self._jpeg is None:
             self._jpeg = {}
         self._jpeg.setdefault(ticket, []).append(st)

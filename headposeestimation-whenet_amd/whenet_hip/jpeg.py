@@ -97,7 +97,8 @@ def encode_host(frame, quality: int = DEFAULT_QUALITY, bgr: bool = True, capacit
 
 # ---- the decoder: JPEG bytes in, a frame out (csrc/jpeg_dec.hip, include/whenet_hip.h JPEG DECODER) ----
 class DecodeError(ValueError):
-    """Damaged entropy data (status WHENET_EFORMAT): `interval` is the first bad restart interval, `frame` the fully defined frame
+    """Damaged entropy data (status WHENET_EFORMAT): `interval` is the first bad restart interval -- for a progressive stream the
+    first bad flat (scan, interval) item, or the item count where the progression is incomplete --, `frame` the fully defined frame
     the decoder still produced (damaged intervals end in zero coefficients)."""
 
     def __init__(self, interval: int, frame: np.ndarray):
@@ -106,14 +107,26 @@ class DecodeError(ValueError):
         self.frame = frame
 
 
-def info(data) -> dict:
+def info(data, progressive: bool = False) -> dict:
     """The header SOI..SOS of a stream (`whenet_jpeg_parse`): h, w, components, sampling (hs, vs), restart_interval, intervals,
     data_offset, the quantisers uint8 [4,64] in natural order and the table ids.  ValueError with the reason for anything but a
-    baseline stream the decoder accepts (progressive, arithmetic, 12 bit, 4 components, several scans, ...)."""
-    i = _lib.jpeg_parse(data)
-    return {"h": i.h, "w": i.w, "components": i.components, "sampling": (i.hs, i.vs), "restart_interval": i.restart_interval,
-            "intervals": i.intervals, "data_offset": i.data_offset, "quantisers": np.ctypeslib.as_array(i.q).copy(),
-            "quantiser_ids": tuple(i.qt[:i.components]), "dc_ids": tuple(i.dc[:i.components]), "ac_ids": tuple(i.ac[:i.components])}
+    baseline stream the decoder accepts (progressive, arithmetic, 12 bit, 4 components, several scans, ...).
+    progressive=True (`whenet_jpeg_parse_scans`): a progressive (SOF2) stream is accepted too, and "scans" lists every scan as a
+    dict: components, ss, se, ah, al, dc_ids, ac_ids, tables, ri, intervals, level, first_item, data_offset, data_bytes."""
+    scans = None
+    if progressive:
+        i, recs = _lib.jpeg_parse_scans(data)
+        scans = [{"components": tuple(r.comp[:r.ns]), "ss": r.ss, "se": r.se, "ah": r.ah, "al": r.al, "dc_ids": tuple(r.dc[:r.ns]),
+                  "ac_ids": tuple(r.ac[:r.ns]), "tables": r.tables, "ri": r.ri, "intervals": r.intervals, "level": r.level,
+                  "first_item": r.first_item, "data_offset": r.data_offset, "data_bytes": r.data_bytes} for r in recs]
+    else:
+        i = _lib.jpeg_parse(data)
+    out = {"h": i.h, "w": i.w, "components": i.components, "sampling": (i.hs, i.vs), "restart_interval": i.restart_interval,
+           "intervals": i.intervals, "data_offset": i.data_offset, "quantisers": np.ctypeslib.as_array(i.q).copy(),
+           "quantiser_ids": tuple(i.qt[:i.components]), "dc_ids": tuple(i.dc[:i.components]), "ac_ids": tuple(i.ac[:i.components])}
+    if scans is not None:
+        out["scans"] = scans
+    return out
 
 
 def packed_surface(frame: np.ndarray) -> "_lib.SurfaceC":
@@ -131,7 +144,7 @@ def _result(frame: np.ndarray, status: np.ndarray, strict: bool):
 
 
 def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False,
-           rule: str = "own"):
+           rule: str = "own", progressive: bool = False):
     """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
     (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
     Damaged data raises `DecodeError` (strict=False: returns the defined frame).  `entropy`: the form of the entropy stage --
@@ -141,10 +154,23 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     stats=True: (frame, the statistics int64 [8] of `whenet_op_jpeg_decode_ex`); with "auto" the form is then chosen here by the
     same rule.  `rule`: "own" (the project's inverse DCT, nearest chroma, JFIF row: the default) or "libjpeg" (the bytes of a
     libjpeg-turbo decode with its defaults: what `cv2.imread` and Pillow give; `whenet_op_jpeg_decode_rule`).  "own" goes through
-    the calls that read the handle's option "jpeg_rule", whose default it is."""
+    the calls that read the handle's option "jpeg_rule", whose default it is.  progressive=True also accepts a progressive (SOF2)
+    stream (`whenet_op_jpeg_decode_progressive`; `DecodeError.interval` is then the flat (scan, interval) item, and stats are items,
+    levels, scans, scan-kernel launches); `entropy` and `seg_bytes` apply where the stream is baseline and are ignored otherwise."""
     if entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be 'auto', 'interval' or 'segmented'")
     _lib.jpeg_rule_code(rule)
+    if progressive:
+        i, scans = _lib.jpeg_parse_scans(data)
+        if scans[0].progressive:      # a SOF2 stream
+            frame = np.empty((i.h, i.w, 3), np.uint8)
+            if handle is None:
+                with _lib.Handle.postproc(0) as own:
+                    status, st = own.op_jpeg_decode_progressive(data, packed_surface(frame), bgr, rule)
+            else:
+                status, st = _handle_of(handle).op_jpeg_decode_progressive(data, packed_surface(frame), bgr, rule)
+            out = _result(frame, status, strict)
+            return (out, st) if stats else out
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
     form, seg = _lib.JPEG_ENTROPY[entropy], 128 if seg_bytes is None else int(seg_bytes)
@@ -209,10 +235,15 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     return frames, status
 
 
-def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own") -> np.ndarray:
+def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", progressive: bool = False) -> np.ndarray:
     """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
-    held to.  `rule`: "own" or "libjpeg", as `decode` (`whenet_jpeg_decode_rule_host`)."""
+    held to.  `rule`: "own" or "libjpeg", as `decode` (`whenet_jpeg_decode_rule_host`).  progressive=True: a progressive (SOF2)
+    stream is accepted too (`whenet_jpeg_decode_progressive_host`)."""
     _lib.jpeg_rule_code(rule)
+    if progressive:
+        i = _lib.jpeg_parse_scans(data)[0]
+        frame = np.empty((i.h, i.w, 3), np.uint8)
+        return _result(frame, _lib.jpeg_decode_progressive_host(data, packed_surface(frame), bgr, rule), strict)
     i = _lib.jpeg_parse(data)
     frame = np.empty((i.h, i.w, 3), np.uint8)
     if rule != "own":
@@ -246,11 +277,17 @@ def decode_segmented_planes_host(data, seg_bytes: int = 128, window: int = _lib.
     return planes, status, st
 
 
-def decode_planes_host(data):
+def decode_planes_host(data, progressive: bool = False, rule: str = "own"):
     """(the component planes [Y] or [Y, Cb, Cr] as uint8 arrays -- luma h x w, chroma ceil(h / vs) x ceil(w / hs) -- and the status
-    int32 [2]) by the host statement: what the tests compare."""
-    i = _lib.jpeg_parse(data)
+    int32 [2]) by the host statement: what the tests compare.  progressive=True: a progressive stream is accepted too, and `rule`
+    chooses the inverse DCT (`whenet_jpeg_decode_progressive_planes_host`)."""
+    _lib.jpeg_rule_code(rule)
+    i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
+    if rule != "own" and not progressive:
+        raise ValueError("decode_planes_host: the planes of rule 'libjpeg' come from the progressive=True call (which takes baseline streams too)")
     shapes = [(i.h, i.w)] + [((i.h + i.vs - 1) // i.vs, (i.w + i.hs - 1) // i.hs)] * (i.components - 1)
     planes = [np.empty(s, np.uint8) for s in shapes]
+    if progressive:
+        return planes, _lib.jpeg_decode_progressive_planes_host(data, planes, rule)
     status = _lib.jpeg_decode_planes_host(data, planes)
     return planes, status

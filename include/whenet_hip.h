@@ -1010,10 +1010,65 @@ WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_ind
  *   whenet_op_jpeg_decode_rule, whenet_op_jpeg_decode_clip_rule            the kernels alone, one stream and a clip
  *   whenet_frame_begin_jpeg_rule, whenet_clip_begin_jpeg_rule              the resident-frame calls
  * Not built: clips of streams already in device memory, a stitch of several lanes per interval, a marker scan of several
- * workgroups, progressive / arithmetic / 12-bit streams, YUV surfaces under rule 1, OpenCV's own bytes.
+ * workgroups, arithmetic / 12-bit streams, YUV surfaces under rule 1, OpenCV's own bytes (progressive streams: the next section).
  * WHENET_EINVAL: a NULL argument or plane, size < 1, a pitch below the row bytes, an unknown format / channel order, a seg_bytes,
- * window, entropy or rule value outside its range. */
+ * window, entropy or rule value outside its range.
+ *
+ * JPEG DECODER, PROGRESSIVE (seven entry points, ABI still 6; csrc/jpeg_prog.hip, the arithmetic is csrc/jpeg_prog_host.h's).
+ * Stills are where progressive streams (SOF2) are common, and cv2.imread opens them without a word.  The decoder for them is OPT-IN:
+ * every call above keeps refusing SOF2 with its defaults ("progressive DCT (SOF2) ..."), every clip call always does.  The calls
+ * named ..._progressive, and whenet_frame_begin_jpeg[_rule] / whenet_op_jpeg_decode[_ex|_rule] on a handle whose option
+ * "jpeg_progressive" is 1 (default 0), accept them.  A SOF0 stream through those calls is the baseline decoder's result, byte for
+ * byte (its entropy options apply; for SOF2 they are ignored): one call serves a folder of mixed files.
+ * ACCEPTED.  SOF2, 8 bit, 1 or 3 components, the samplings, sides and 8-bit DQT of the baseline parser.  Between scans: DHT (class
+ * 0..1, ids 0..3; libjpeg writes optimised tables in front of almost every scan), DRI (a scan uses the value in force at its SOS),
+ * APPn and COM; a DQT behind the first SOS is refused.  A scan holds all components (interleaved: the frame's MCUs) or ONE; a scan
+ * of one component of a 3-component frame has single blocks as its MCUs and covers ceil(cw / 8) x ceil(ch / 8) blocks of that
+ * component in raster order, cw = ceil(w hs_c / hs_max) -- NOT the plane padded to whole frame MCUs; blocks of the padded plane
+ * outside that grid receive DC only.  Refused with the reason (WHENET_EFORMAT, on the host, before anything is enqueued): Ns = 2;
+ * Ss > Se or Se > 63; Ss = 0 with Se != 0; Ss > 0 with Ns > 1; Ah or Al > 13; a first scan (Ah = 0) of a coefficient that already
+ * had one; a refinement of a coefficient without a first scan, or with Ah != the coefficient's current Al or Al != Ah - 1; an AC
+ * scan of a component whose DC has had no scan; more than WHENET_JPEG_PROG_MAX_SCANS scans; a missing table.
+ * SCAN PLAN.  The host walks the entropy data for 0xFF pairs to find each scan's end and its restart markers (INTERVALS above, per
+ * scan); the starts of all (scan, interval) ITEMS travel with the plan and no device marker scan runs.  Items are numbered scan by
+ * scan in stream order, an item per interval.  level(s) = 1 + the largest level of an earlier scan that shares a component and
+ * overlaps its band [Ss, Se] (else 1): the scans of one level touch different values.  libjpeg's default script has 3 levels.
+ * SCAN DECODE (T.81 G.1.2 / G.2 as jdphuff.c executes it).  Raw coefficients are int16 [block][64], record order as above, ZIGZAG
+ * order inside a record, zero at the start, computed in int32 and clamped to -32768..32767 at every store.  DC first: the baseline
+ * DC symbol and EXTEND, predictors 0 at every interval start; coefficient 0 = pred << Al.  DC refine: one bit per block; 1: |= 1 <<
+ * Al.  AC first: (r, s > 0) skips r, coefficient k = EXTEND(s bits) << Al; (15, 0) skips 16; (r < 15, 0): EOBRUN = (1 << r) + r
+ * extra bits, which ends this block and the next EOBRUN - 1 blocks of the interval.  AC refine, p1 = 1 << Al: a symbol with s != 0
+ * must have s = 1 and reads a sign bit; on the way over r coefficients without a history every non-zero coefficient reads one
+ * correction bit (1 and (coef & p1) == 0: coef moves by p1 away from zero); then the new +-p1 is placed; (15, 0) passes 16 such
+ * coefficients the same way; inside an EOB run and behind an EOB the non-zero coefficients of the band still read their bits.
+ * DAMAGE makes the ITEM bad: no code word; bits ending inside a symbol, a sign or a correction bit; a run that passes Se; s > 1
+ * in a refinement; an EOBRUN that passes the interval's last block.  The block in hand keeps what was written, the scan does not
+ * touch the rest of that interval, OTHER SCANS GO ON and see what the raw coefficients hold.  status[0] = WHENET_OK or
+ * WHENET_EFORMAT, status[1] = the smallest bad item (else -1).  INCOMPLETE PROGRESSION -- EOI or the end of the bytes before every
+ * coefficient of every component reached Al = 0 -- is decoded from what the scans hold: WHENET_EFORMAT with status[1] = the item
+ * count.  There is NO block smoothing (libjpeg smooths the blocks of an incomplete progression; here they are not).
+ * FINISH.  record[natural k] = clamp(raw[zigzag k] x Q[k], -2048, 2047): the records the inverse DCT above reads; planes, frame and
+ * YUV surfaces follow unchanged under both rules (rule 1's SCOPE paragraph applies as written).
+ *   whenet_jpeg_parse_scans   pure host: *info (for SOF2 its Huffman fields stay empty) and up to cap whenet_jpeg_scan_t records;
+ *                  *num_scans = the stream's scans (cap below it: WHENET_EINVAL).  A SOF0 stream is one scan (0..63, Ah = Al = 0).
+ *   whenet_jpeg_decode_progressive_host, ..._planes_host   the host statement, as the calls they are named after, with `rule`
+ *   whenet_jpeg_progressive_coefficients_host   the finished records int16 [blocks][64] and, where not NULL, the raw ones and the
+ *                  counters int64 [8]: scans, items, levels, the largest EOBRUN met, ZRLs in refinement scans, correction bits read,
+ *                  correction bits that changed a coefficient, 0.  blocks = MCUs x blocks per MCU (cap_blocks below it:
+ *                  WHENET_EINVAL); SOF2 only.
+ *   whenet_op_jpeg_decode_progressive   the kernels alone, host to host; rule as whenet_op_jpeg_decode_rule; stats (may be NULL)
+ *                  int64 [8]: for SOF2 items, levels, scans, launches of the scan kernel; for SOF0 whenet_op_jpeg_decode_ex's.
+ *   whenet_frame_begin_jpeg_progressive   the twin of whenet_frame_begin_jpeg_rule: ONE H2D of the plan (scan records, per-scan
+ *                  tables, item lists, the bytes from the first scan's data on), one memset, a launch per level, the finish, then
+ *                  the inverse DCT and colour kernels: enqueue-only on the copy stream.
+ *   whenet_jpeg_progressive_counters   out[0..2]: decodes enqueued, scan-kernel launches, scans in them.
+ *   option "jpeg_progressive"  0 (default) / 1, above.   option "jpeg_prog_levels"  1 (default): a launch per level; 0: a launch per
+ *                  scan in stream order (a measurement knob: the bytes are the same).
+ * Not built: a segmented (many lanes per interval) form for progressive scans -- a scan without DRI is ONE lane --, progressive
+ * streams in clips, SOF0 / SOF1 streams of several scans, scans of two components, arithmetic, 12-bit and CMYK streams, block
+ * smoothing, a progressive encoder, streams already in device memory. */
 #define WHENET_JPEG_SEG_WINDOW 256
+#define WHENET_JPEG_PROG_MAX_SCANS 128
 #define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
 #define WHENET_JPEG_CLIP_PLAN_TOTAL_WORDS 8
 typedef struct {
@@ -1029,6 +1084,17 @@ typedef struct {
     uint8_t huff_values[4][256];
     uint8_t huff_present[4];
 } whenet_jpeg_info_t;
+typedef struct {
+    int32_t ns, comp[3];             /* the scan's components: indices into the frame's */
+    int32_t ss, se, ah, al;
+    int32_t dc[3], ac[3];            /* per scan component: the table ids of its SOS */
+    int32_t tables;                  /* the snapshot of the Huffman tables in force at its SOS: DHT segments seen so far */
+    int32_t ri, intervals;           /* Ri in the scan's own MCUs, ceil(scan MCUs / Ri) */
+    int32_t level;                   /* 1.. */
+    int32_t first_item;              /* its first flat item index */
+    int32_t progressive;             /* 1: a scan of a SOF2 frame; 0: the one scan of a SOF0 frame */
+    int64_t data_offset, data_bytes; /* its entropy data in the stream */
+} whenet_jpeg_scan_t;
 WHENET_API int whenet_jpeg_parse(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info);
 WHENET_API int whenet_jpeg_decode_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int32_t status[2]);
 WHENET_API int whenet_jpeg_decode_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int32_t status[2]);
@@ -1064,6 +1130,20 @@ WHENET_API int whenet_frame_begin_jpeg_rule(whenet_t* h, const uint8_t* data, in
                                  int32_t* status);
 WHENET_API int whenet_clip_begin_jpeg_rule(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int rule,
                                 int* ticket, int32_t* status);
+
+WHENET_API int whenet_jpeg_parse_scans(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info, whenet_jpeg_scan_t* scans, int cap,
+                            int* num_scans);
+WHENET_API int whenet_jpeg_decode_progressive_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                                        int32_t status[2]);
+WHENET_API int whenet_jpeg_decode_progressive_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int rule,
+                                               int32_t status[2]);
+WHENET_API int whenet_jpeg_progressive_coefficients_host(const uint8_t* data, int64_t size, int16_t* coef, int16_t* raw, int64_t cap_blocks,
+                                              int64_t counters[8], int32_t status[2]);
+WHENET_API int whenet_op_jpeg_decode_progressive(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order,
+                                      int rule, int32_t status[2], int64_t stats[8]);
+WHENET_API int whenet_frame_begin_jpeg_progressive(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int* ticket,
+                                        int32_t* status);
+WHENET_API int whenet_jpeg_progressive_counters(whenet_t* h, int64_t out[4]);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

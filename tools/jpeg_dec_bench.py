@@ -35,7 +35,16 @@
                                 single regions after a warm-up, and their 10th..90th percentile spread; "enqueues" / "h2d" per clip
                                 are whenet_jpeg_clip_counters' differences.  The handle's options stay at their defaults (auto).
 
-  python tools/jpeg_dec_bench.py [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
+    (vi)  --progressive         progressive streams (recorded, not gated), INSTEAD of (i)-(v): Pillow's progressive stream of the
+                                picture (quality 95, 4:2:0; without DRI and with one interval per MCU row) through
+                                whenet_frame_begin_jpeg_progressive, ms per frame for begin -> release -> collect, with option
+                                jpeg_prog_levels 1 (a launch per level) and 0 (a launch per scan); "cumulative_level_ms": the same
+                                for the stream cut behind level 1, 2, ... (differences: the time per level); next to it the baseline
+                                twin (the same picture with optimize=True) through whenet_frame_begin_jpeg with the entropy stage
+                                in form 0 and in the auto form, and Pillow's decode of the progressive stream on one core.  Medians
+                                of --clip-samples (>= 20) regions and their 10th..90th percentiles.
+
+  python tools/jpeg_dec_bench.py [--progressive] [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
                                  [--lanes 0] [--rule 0] [--rgb] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
 
 Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
@@ -220,6 +229,78 @@ def clip_leg(m, h, w, args):
     return res
 
 
+def prog_leg(m, h, w, args):
+    """row (vi): progressive streams (SOF2), one frame per submission: whenet_frame_begin_jpeg_progressive -> release without heads
+    -> collect, the wall time of the whole region (plan, one H2D, the launches, the wait), next to the baseline twin of the same
+    picture through whenet_frame_begin_jpeg with the entropy stage in form 0 (an interval per lane: what the parent commit had for
+    such a picture) and in the handle's auto form, and Pillow's decode of the progressive stream on one core."""
+    import torch
+    from PIL import Image
+    from whenet_hip import _lib, jpeg, synth
+    hnd = m._handle
+    sync = torch.cuda.synchronize
+    no_heads = np.zeros((0, 4), np.int32)
+    torch.set_num_threads(1)
+    im = Image.fromarray(np.ascontiguousarray(synth.video_frame(h, w)[..., ::-1]))
+    res = {"frame": [h, w], "rule": args.rule, "progressive": {}}
+
+    def stream(**kw):
+        buf = io.BytesIO()
+        im.save(buf, "JPEG", quality=95, subsampling=2, **kw)
+        return buf.getvalue()
+
+    def region(fn):
+        for _ in range(3):
+            fn()
+        ms = []
+        for _ in range(max(20, args.clip_samples)):
+            sync()
+            t = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t) * 1e3)
+        q = np.percentile(ms, [10, 50, 90])
+        return {"ms": round(float(q[1]), 3), "p10_p90": [round(float(q[0]), 3), round(float(q[2]), 3)]}
+
+    status = np.zeros(2, np.int32)
+
+    def begin(data, progressive):
+        t = hnd.frame_begin_jpeg(data, status, progressive=progressive)
+        hnd.frame_heads(t, no_heads)
+        hnd.collect(t, 0)
+
+    for name, kw in (("no_dri", {}), ("row_intervals", {"restart_marker_rows": 1})):
+        data, twin = stream(progressive=True, **kw), stream(optimize=True, **kw)
+        info, scans = _lib.jpeg_parse_scans(data)
+        want = jpeg.decode_host(data, rule=RULES[args.rule], progressive=True)
+        r = {"bytes_jpeg": len(data), "bytes_twin": len(twin), "scans": len(scans), "levels": max(s.level for s in scans),
+             "items": sum(s.intervals for s in scans),
+             "equals_host": bool(np.array_equal(jpeg.decode(data, handle=hnd, rule=RULES[args.rule], progressive=True), want)),
+             "equals_twin": bool(np.array_equal(want, jpeg.decode_host(twin, rule=RULES[args.rule])))}
+        for levels in (1, 0):
+            hnd.set_option("jpeg_prog_levels", levels)
+            r["per_level_launches" if levels else "per_scan_launches"] = region(lambda: begin(data, True))
+        hnd.set_option("jpeg_prog_levels", 1)
+        # time per level: the stream cut behind the last scan of levels 1..L is an incomplete progression of L levels
+        r["cumulative_level_ms"] = []
+        for level in range(1, r["levels"] + 1):
+            last = max(i for i, s in enumerate(scans) if s.level <= level)
+            if any(s.level > level for s in scans[:last]):
+                break      # (the script's scans are not in level order: no prefix holds exactly these levels)
+            cut = data[:scans[last].data_offset + scans[last].data_bytes] + b"\xff\xd9"
+            r["cumulative_level_ms"].append(region(lambda: begin(cut, True))["ms"])
+        for key, entropy in (("twin_form0", 0), ("twin_auto", 2)):
+            hnd.set_option("jpeg_entropy", entropy)
+            r[key] = region(lambda: begin(twin, False))
+        hnd.set_option("jpeg_entropy", 2)
+
+        def pillow():
+            Image.open(io.BytesIO(data)).convert("RGB").load()
+
+        r["pillow_one_core"] = region(pillow)
+        res["progressive"][name] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
@@ -233,6 +314,7 @@ def main():
     ap.add_argument("--only-decode", action="store_true", help="rows (i) only")
     ap.add_argument("--clip", type=int, nargs="+", default=None, help="row (v) only: frames per clip of JPEG streams, 1..16 each")
     ap.add_argument("--clip-samples", type=int, default=20, help="regions per figure of row (v), at least 20")
+    ap.add_argument("--progressive", action="store_true", help="row (vi) only: progressive streams against their baseline twins")
     args = ap.parse_args()
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
     import whenet
@@ -242,7 +324,8 @@ def main():
     try:
         for size in args.sizes:
             h, w = (int(v) for v in size.split("x"))
-            print(json.dumps(clip_leg(m, h, w, args) if args.clip else size_leg(m, h, w, args)), flush=True)
+            leg = prog_leg if args.progressive else (clip_leg if args.clip else size_leg)
+            print(json.dumps(leg(m, h, w, args)), flush=True)
     finally:
         m.close()
     return 0
