@@ -934,35 +934,60 @@ int whenet_frame_annotate_ex(whenet_t* h, int ticket, int frame_index, const whe
 
 // ---- JPEG encoder (jpeg.hip, jpeg_host.h, engine_post.cpp) ----
 int whenet_jpeg_header(int h, int w, int quality, uint8_t* out, int cap, int32_t qtables[2][64]) {
+    return whenet_jpeg_header_ex(h, w, quality, WHENET_JPEG_420, out, cap, qtables);
+}
+
+int whenet_jpeg_header_ex(int h, int w, int quality, int sampling, uint8_t* out, int cap, int32_t qtables[2][64]) {
     const char* bad = whenet::jpeg_check_size(h, w, quality);
+    if (bad == nullptr && !whenet::jpeg_sampling_ok(sampling)) bad = "unknown sampling (WHENET_JPEG_420, WHENET_JPEG_422 or WHENET_JPEG_444)";
     if (bad == nullptr && out != nullptr && cap < whenet::JPEG_HEADER_BYTES) bad = "the header has 629 bytes, the capacity is below that";
     if (bad != nullptr) {
         g_create_error = std::string("jpeg_header: ") + bad;
         return WHENET_EINVAL;
     }
     whenet::JpegTables t;
-    whenet::jpeg_build_tables(h, w, quality, t);
+    whenet::jpeg_build_tables(h, w, quality, t, sampling);
     if (out) std::memcpy(out, t.header, whenet::JPEG_HEADER_BYTES);
     if (qtables) std::memcpy(qtables, t.q, sizeof(t.q));
     return whenet::JPEG_HEADER_BYTES;
 }
 
-int64_t whenet_jpeg_bound(int h, int w) {
-    if (const char* bad = whenet::jpeg_check_size(h, w, WHENET_JPEG_DEFAULT_QUALITY)) {
+int64_t whenet_jpeg_bound(int h, int w) { return whenet_jpeg_bound_ex(h, w, WHENET_JPEG_420); }
+
+int64_t whenet_jpeg_bound_ex(int h, int w, int sampling) {
+    const char* bad = whenet::jpeg_check_size(h, w, WHENET_JPEG_DEFAULT_QUALITY);
+    if (bad == nullptr && !whenet::jpeg_sampling_ok(sampling)) bad = "unknown sampling (WHENET_JPEG_420, WHENET_JPEG_422 or WHENET_JPEG_444)";
+    if (bad != nullptr) {
         g_create_error = std::string("jpeg_bound: ") + bad;
         return WHENET_EINVAL;
     }
-    return whenet::jpeg_bound(h, w);
+    return whenet::jpeg_bound(h, w, sampling);
+}
+
+int whenet_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256], int* count) {
+    bool any = false;
+    for (int i = 0; freq != nullptr && i < 256; ++i) any = any || freq[i] != 0;
+    if (freq == nullptr || bits == nullptr || vals == nullptr || count == nullptr || !any) {
+        g_create_error = any ? "jpeg_optimal_table: NULL argument" : "jpeg_optimal_table: NULL argument or no symbol occurs";
+        return WHENET_EINVAL;
+    }
+    *count = whenet::jpeg_optimal_table(freq, bits, vals);
+    return WHENET_OK;
 }
 
 int whenet_jpeg_encode_host(const whenet_surface_t* src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size) {
+    return whenet_jpeg_encode_host_ex(src, h, w, channel_order, quality, WHENET_JPEG_420, 0, out, cap, size, nullptr);
+}
+
+int whenet_jpeg_encode_host_ex(const whenet_surface_t* src, int h, int w, int channel_order, int quality, int sampling, int optimize, uint8_t* out,
+                               int64_t cap, int64_t* size, uint32_t hist[4][256]) {
     try {
-        const char* bad = whenet::jpeg_check(src, h, w, channel_order, quality, out, cap, size);
+        const char* bad = whenet::jpeg_check(src, h, w, channel_order, quality, out, cap, size, sampling);
         WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_encode_host: ") + (bad ? bad : ""));
         WHENET_REQUIRE(src->on_device == 0, WHENET_EINVAL, "jpeg_encode_host: the surface must be host memory (on_device = 0)");
         std::unique_ptr<whenet::JpegTables> t(new whenet::JpegTables);
-        whenet::jpeg_build_tables(h, w, quality, *t);
-        *size = whenet::jpeg_encode_host(whenet::jpeg_source(*src, h, w, channel_order), *t, out, cap);
+        whenet::jpeg_build_tables(h, w, quality, *t, sampling);
+        *size = whenet::jpeg_encode_host(whenet::jpeg_source(*src, h, w, channel_order), *t, out, cap, sampling, optimize != 0, hist);
         WHENET_REQUIRE(*size <= cap, WHENET_EOVERFLOW,
                        "jpeg_encode_host: the stream has " + std::to_string(*size) + " bytes, the capacity is " + std::to_string(cap));
         return WHENET_OK;
@@ -973,26 +998,42 @@ int whenet_jpeg_encode_host(const whenet_surface_t* src, int h, int w, int chann
 
 int whenet_op_jpeg_encode(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, uint8_t* out, int64_t cap,
                           int64_t* size) {
+    return whenet_op_jpeg_encode_ex(h, src, hh, ww, channel_order, quality, WHENET_JPEG_420, 0, out, cap, size, nullptr);
+}
+
+int whenet_op_jpeg_encode_ex(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, int sampling, int optimize,
+                             uint8_t* out, int64_t cap, int64_t* size, uint32_t hist[4][256]) {
     return guarded(h, [&](whenet::Engine& e) {
         WHENET_REQUIRE(src != nullptr, WHENET_EINVAL, "op_jpeg_encode: NULL argument");
-        e.op_jpeg_encode(*src, hh, ww, channel_order, quality, out, cap, size);
+        e.op_jpeg_encode(*src, hh, ww, channel_order, quality, out, cap, size, sampling, optimize != 0, hist);
     });
 }
 
 int whenet_jpeg_encode_device(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, void* dst, int64_t cap,
                               int64_t* dsize, void* stream) {
+    return whenet_jpeg_encode_device_ex(h, src, hh, ww, channel_order, quality, WHENET_JPEG_420, 0, dst, cap, dsize, stream);
+}
+
+int whenet_jpeg_encode_device_ex(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, int sampling,
+                                 int optimize, void* dst, int64_t cap, int64_t* dsize, void* stream) {
     return guarded(h, [&](whenet::Engine& e) {
         WHENET_REQUIRE(src != nullptr, WHENET_EINVAL, "jpeg_encode_device: NULL argument");
-        e.jpeg_encode_device(*src, hh, ww, channel_order, quality, dst, cap, dsize, static_cast<hipStream_t>(stream));
+        e.jpeg_encode_device(*src, hh, ww, channel_order, quality, dst, cap, dsize, static_cast<hipStream_t>(stream), sampling, optimize != 0);
     });
 }
 
 int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size,
                                int32_t* status) {
+    return whenet_frame_annotate_jpeg_ex(h, ticket, frame_index, display, quality, WHENET_JPEG_420, 0, out, cap, size, status);
+}
+
+int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_index, int display, int quality, int sampling, int optimize, uint8_t* out,
+                                  int64_t cap, int64_t* size, int32_t* status) {
     return guarded(h, [&](whenet::Engine&) {
         const int idx = ticket % MAX_INFLIGHT_ENGINES;
         WHENET_REQUIRE(ticket >= 0 && idx < h->inflight, WHENET_EINVAL, "frame_annotate_jpeg: unknown ticket " + std::to_string(ticket));
-        h->at(size_t(idx)).frame_annotate_jpeg(ticket / MAX_INFLIGHT_ENGINES, frame_index, display, quality, out, cap, size, status);
+        h->at(size_t(idx)).frame_annotate_jpeg(ticket / MAX_INFLIGHT_ENGINES, frame_index, display, quality, out, cap, size, status, sampling,
+                                               optimize != 0);
     });
 }
 

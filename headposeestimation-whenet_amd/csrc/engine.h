@@ -339,14 +339,18 @@ class Engine {
     // are uploaded tight, the stream lands between two guard zones and min(size, cap) bytes of it go to the caller; the host waits.
     // jpeg_encode_device: ENQUEUE-ONLY on stream_ between the two event hand-overs of the device ingest; the work buffers are the
     // engine's (grown on the first call for a size), the tables and header of an (h, w, quality) are uploaded once and kept.
-    void op_jpeg_encode(const whenet_surface_t& src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size);
+    // sampling / optimize: include/whenet_hip.h, SAMPLING AND OPTIMISED TABLES; hist (host, may be nullptr): the device histograms.
+    void op_jpeg_encode(const whenet_surface_t& src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size,
+                        int sampling = WHENET_JPEG_420, bool optimize = false, uint32_t (*hist)[256] = nullptr);
     void jpeg_encode_device(const whenet_surface_t& src, int h, int w, int channel_order, int quality, void* dst, int64_t cap, int64_t* dsize,
-                            hipStream_t stream);
+                            hipStream_t stream, int sampling = WHENET_JPEG_420, bool optimize = false);
     // frame_annotate_jpeg: frame_annotate into a surface of the slot's own (tight I420, JFIF matrix), the encoder behind it on stream_
     // into a landing buffer in device memory, and a flush kernel that copies min(length, cap) bytes and the length into pinned host
     // memory -- the total is data-dependent and the call must not wait, so no copy of a size known to the host can stand there.
     // ENQUEUE-ONLY; the collect call hands the bytes, the length and the status to the caller.  It counts as the frame's one annotate.
-    void frame_annotate_jpeg(int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size, int32_t* status);
+    // At 4:2:2 / 4:4:4 the slot's surface is PACKED pixels in the frame's channel order: an I420 surface cannot carry their chroma.
+    void frame_annotate_jpeg(int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size, int32_t* status,
+                             int sampling = WHENET_JPEG_420, bool optimize = false);
     // JPEG DECODER (jpeg_dec.hip; the contract is in include/whenet_hip.h).  Every entry point parses (or checks the info) on the host
     // first: a refused stream is WHENET_EFORMAT before a slot is taken or anything is enqueued.
     // op_jpeg_decode: the kernels alone, host to host; the destination lands at the caller's pitches between two guard zones.
@@ -593,13 +597,13 @@ class Engine {
 
     // the JPEG encoder's device-resident tables of (h, w, quality), kept (at most 8 sets: a full cache waits for stream_ and empties)
     struct JpegTableSet {
-        int h, w, quality;
+        int h, w, quality, sampling;
         DeviceBuffer d;
     };
     std::vector<JpegTableSet> jpeg_tables_;
     DeviceBuffer jpeg_scratch_;
     Event jpeg_source_, jpeg_done_;
-    const JpegTables* jpeg_device_tables(int h, int w, int quality);
+    const JpegTables* jpeg_device_tables(int h, int w, int quality, int sampling);
     DeviceBuffer jpeg_dec_scratch_;      // jpeg_decode_device's work buffers, and the decode tables of its last stream (kept while
     DeviceBuffer jpeg_dec_tables_d_;     // the next stream's are the same: an MJPG stream repeats its tables)
     std::vector<JpegDecTables> jpeg_dec_tables_h_;

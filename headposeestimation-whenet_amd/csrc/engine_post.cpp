@@ -1285,9 +1285,10 @@ void Engine::finish_annotations(Slot& slot) {
 }
 
 // ---- JPEG encoder (jpeg.hip; the contract is in engine.h and include/whenet_hip.h) ----
-void Engine::op_jpeg_encode(const whenet_surface_t& src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size) {
+void Engine::op_jpeg_encode(const whenet_surface_t& src, int h, int w, int channel_order, int quality, uint8_t* out, int64_t cap, int64_t* size,
+                            int sampling, bool optimize, uint32_t (*hist)[256]) {
     DeviceGuard guard(device_);
-    const char* bad = jpeg_check(&src, h, w, channel_order, quality, out, cap, size);
+    const char* bad = jpeg_check(&src, h, w, channel_order, quality, out, cap, size, sampling);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_encode: ") + (bad ? bad : ""));
     WHENET_REQUIRE(src.on_device == 0, WHENET_EINVAL, "op_jpeg_encode: the surface must be host memory (on_device = 0)");
     check_surface("op_jpeg_encode", src, h, w);
@@ -1295,8 +1296,8 @@ void Engine::op_jpeg_encode(const whenet_surface_t& src, int h, int w, int chann
     size_t off[4];
     const int planes = tight_surface(src.format, h, w, rows, row_bytes, off);
     JpegTables tables;
-    jpeg_build_tables(h, w, quality, tables);
-    const JpegScratch lay(h, w);
+    jpeg_build_tables(h, w, quality, tables, sampling);
+    const JpegScratch lay(h, w, sampling);
     TempBufs tmp;
     uint8_t* const d_planes = static_cast<uint8_t*>(tmp.get(off[planes]));
     JpegTables* const d_tables = static_cast<JpegTables*>(tmp.get(sizeof(JpegTables)));
@@ -1311,13 +1312,16 @@ void Engine::op_jpeg_encode(const whenet_surface_t& src, int h, int w, int chann
     WHENET_HIP_CHECK(hipMemcpyAsync(d_tables, &tables, sizeof(tables), hipMemcpyHostToDevice, stream_));
     WHENET_HIP_CHECK(hipMemsetAsync(d_size, 0, sizeof(long long), stream_));
     // no stream is longer than the bound: a landing buffer of min(cap, bound) bytes answers as one of cap bytes would
-    const int64_t dcap = std::min<int64_t>(cap, jpeg_bound(h, w));
+    const int64_t dcap = std::min<int64_t>(cap, jpeg_bound(h, w, sampling));
     const GuardedOutput d_out(size_t(dcap), stream_);
-    launch_jpeg_encode(jpeg_args(s, d_tables, d_scratch, lay, d_out.frames(), dcap, d_size), lay, stream_);
+    const JpegArgs a = jpeg_args(s, d_tables, d_scratch, lay, d_out.frames(), dcap, d_size, optimize);
+    launch_jpeg_encode(a, lay, stream_);
     WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
     long long total = 0;
     WHENET_HIP_CHECK(hipMemcpy(&total, d_size, sizeof(total), hipMemcpyDeviceToHost));
-    WHENET_REQUIRE(total >= JPEG_HEADER_BYTES + 2 && total <= jpeg_bound(h, w), WHENET_EHIP,
+    if (optimize && hist != nullptr) WHENET_HIP_CHECK(hipMemcpy(hist, a.opt->hist, sizeof(a.opt->hist), hipMemcpyDeviceToHost));
+    // (an optimised header lists the occurring symbols only: SOI .. SOF0, four DHT of at least one symbol, DRI, SOS)
+    WHENET_REQUIRE(total >= (optimize ? 177 + 4 * 22 + 20 : JPEG_HEADER_BYTES) + 2 && total <= jpeg_bound(h, w, sampling), WHENET_EHIP,
                    "op_jpeg_encode: the kernels report a stream of " + std::to_string(total) + " bytes");
     const size_t span[2] = {0, size_t(std::min<int64_t>(total, dcap))};
     d_out.to_host(stream_, span, 1, &out, "op_jpeg_encode");
@@ -1326,16 +1330,16 @@ void Engine::op_jpeg_encode(const whenet_surface_t& src, int h, int w, int chann
                    "op_jpeg_encode: the stream has " + std::to_string(total) + " bytes, the capacity is " + std::to_string(cap));
 }
 
-const JpegTables* Engine::jpeg_device_tables(int h, int w, int quality) {
+const JpegTables* Engine::jpeg_device_tables(int h, int w, int quality, int sampling) {
     for (const JpegTableSet& t : jpeg_tables_)
-        if (t.h == h && t.w == w && t.quality == quality) return t.d.as<JpegTables>();
+        if (t.h == h && t.w == w && t.quality == quality && t.sampling == sampling) return t.d.as<JpegTables>();
     if (jpeg_tables_.size() >= 8) {      // an earlier call's kernels may still read a set
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         jpeg_tables_.clear();
     }
     JpegTables tables;
-    jpeg_build_tables(h, w, quality, tables);
-    JpegTableSet set{h, w, quality, DeviceBuffer()};
+    jpeg_build_tables(h, w, quality, tables, sampling);
+    JpegTableSet set{h, w, quality, sampling, DeviceBuffer()};
     set.d.reset(sizeof(JpegTables));
     WHENET_HIP_CHECK(hipMemcpy(set.d.as<void>(), &tables, sizeof(tables), hipMemcpyHostToDevice));
     jpeg_tables_.push_back(std::move(set));
@@ -1343,9 +1347,9 @@ const JpegTables* Engine::jpeg_device_tables(int h, int w, int quality) {
 }
 
 void Engine::jpeg_encode_device(const whenet_surface_t& src, int h, int w, int channel_order, int quality, void* dst, int64_t cap, int64_t* dsize,
-                                hipStream_t stream) {
+                                hipStream_t stream, int sampling, bool optimize) {
     DeviceGuard guard(device_);
-    const char* bad = jpeg_check(&src, h, w, channel_order, quality, dst, cap, dsize);
+    const char* bad = jpeg_check(&src, h, w, channel_order, quality, dst, cap, dsize, sampling);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_encode_device: ") + (bad ? bad : ""));
     WHENET_REQUIRE(src.on_device == 1, WHENET_EINVAL, "jpeg_encode_device: the surface must be device memory (on_device = 1)");
     WHENET_REQUIRE(cap <= std::numeric_limits<int>::max(), WHENET_EINVAL, "jpeg_encode_device: a capacity above 2^31 - 1 bytes");
@@ -1354,15 +1358,15 @@ void Engine::jpeg_encode_device(const whenet_surface_t& src, int h, int w, int c
     check_device_plane("jpeg_encode_device: dsize", reinterpret_cast<const uint8_t*>(dsize), 1, 8, 8);
     WHENET_REQUIRE(reinterpret_cast<uintptr_t>(dsize) % 8 == 0, WHENET_EINVAL, "jpeg_encode_device: dsize is not aligned to 8 bytes");
     // allocations, the tables and the events first: nothing is enqueued yet if one of them fails
-    const JpegScratch lay(h, w);
+    const JpegScratch lay(h, w, sampling);
     if (lay.bytes > jpeg_scratch_.bytes()) {      // (the buffer in hand may still be read by an earlier call's kernels)
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         jpeg_scratch_.reset(lay.bytes);
     }
-    const JpegTables* d_tables = jpeg_device_tables(h, w, quality);
+    const JpegTables* d_tables = jpeg_device_tables(h, w, quality, sampling);
     if (!jpeg_source_) jpeg_source_.create();
     if (!jpeg_done_) jpeg_done_.create();
-    const JpegArgs a = jpeg_args(jpeg_source(src, h, w, channel_order), d_tables, jpeg_scratch_.as<void>(), lay, dst, cap, dsize);
+    const JpegArgs a = jpeg_args(jpeg_source(src, h, w, channel_order), d_tables, jpeg_scratch_.as<void>(), lay, dst, cap, dsize, optimize);
     WHENET_HIP_CHECK(hipEventRecord(jpeg_source_, stream));
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, jpeg_source_, 0));
     launch_jpeg_encode(a, lay, stream_);
@@ -1371,9 +1375,11 @@ void Engine::jpeg_encode_device(const whenet_surface_t& src, int h, int w, int c
 }
 
 void Engine::frame_annotate_jpeg(int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap, int64_t* size,
-                                 int32_t* status) {
+                                 int32_t* status, int sampling, bool optimize) {
     DeviceGuard guard(device_);
     check_display("frame_annotate_jpeg", display);
+    WHENET_REQUIRE(jpeg_sampling_ok(sampling), WHENET_EINVAL,
+                   "frame_annotate_jpeg: unknown sampling (WHENET_JPEG_420, WHENET_JPEG_422 or WHENET_JPEG_444)");
     WHENET_REQUIRE(size != nullptr && status != nullptr && (out != nullptr || cap == 0), WHENET_EINVAL, "frame_annotate_jpeg: NULL argument");
     WHENET_REQUIRE(cap >= 0, WHENET_EINVAL, "frame_annotate_jpeg: negative capacity");
     WHENET_REQUIRE(quality >= 1 && quality <= 100, WHENET_EINVAL, "frame_annotate_jpeg: quality must be 1..100");
@@ -1383,31 +1389,35 @@ void Engine::frame_annotate_jpeg(int ticket, int frame_index, int display, int q
     // allocations and the tables first: nothing is enqueued yet if one of them fails
     int rows[3], row_bytes[3];
     size_t off[4];
-    (void)tight_surface(WHENET_YUV_I420, fh, fw, rows, row_bytes, off);
-    const long long staged_cap = std::min<long long>(cap, jpeg_bound(fh, fw));      // no stream is longer than the bound
+    // 4:2:0: a tight I420 JFIF surface; 4:2:2 / 4:4:4: tight packed pixels in the frame's channel order (full-resolution chroma)
+    const int format = sampling == WHENET_JPEG_420 ? WHENET_YUV_I420 : WHENET_SURF_PACKED;
+    const int planes = tight_surface(format, fh, fw, rows, row_bytes, off);
+    const long long staged_cap = std::min<long long>(cap, jpeg_bound(fh, fw, sampling));      // no stream is longer than the bound
     const size_t cap16 = (size_t(staged_cap) + 15) & ~size_t(15);
     Slot::JpegStage& stage = slot.jpg_stage[frame_index];
-    stage.surface.grow(off[3]);
+    stage.surface.grow(off[planes]);
     stage.stream.grow(cap16 + 16);
     stage.host.grow(cap16 + 16);
-    const JpegScratch lay(fh, fw);
+    const JpegScratch lay(fh, fw, sampling);
     if (lay.bytes > jpeg_scratch_.bytes()) {      // (the buffer in hand may still be read by an earlier call's kernels)
         WHENET_HIP_CHECK(hipStreamSynchronize(stream_));
         jpeg_scratch_.reset(lay.bytes);
     }
-    const JpegTables* d_tables = jpeg_device_tables(fh, fw, quality);
+    const JpegTables* d_tables = jpeg_device_tables(fh, fw, quality, sampling);
     void* h_dev = nullptr;                         // the pinned buffer as the device addresses it
     WHENET_HIP_CHECK(hipHostGetDevicePointer(&h_dev, stage.host.as<void>(), 0));
     whenet_surface_t surf{};
-    for (int p = 0; p < 3; ++p) surf.plane[p] = stage.surface.as<uint8_t>() + off[p], surf.pitch[p] = row_bytes[p];
-    surf.format = WHENET_YUV_I420, surf.matrix = WHENET_YUV_JFIF, surf.on_device = 1;
+    for (int p = 0; p < planes; ++p) surf.plane[p] = stage.surface.as<uint8_t>() + off[p], surf.pitch[p] = row_bytes[p];
+    surf.format = format, surf.matrix = format == WHENET_YUV_I420 ? WHENET_YUV_JFIF : 0, surf.on_device = 1;
+    const int channel_order = slot.swap_rb ? WHENET_BGR : WHENET_RGB;      // (read for the packed surface only: frame_annotate wrote it so)
     // the overlay into the engine's surface (it counts as the frame's one annotate call), the encoder behind it on the same stream,
     // then min(size, cap) bytes and the size into the pinned buffer: the only bytes that cross the link
     frame_annotate(ticket, frame_index, surf, nullptr, display);
     uint8_t* const d_stream = stage.stream.as<uint8_t>();
     long long* const d_size = reinterpret_cast<long long*>(d_stream + cap16);
-    launch_jpeg_encode(jpeg_args(jpeg_source(surf, fh, fw, WHENET_BGR), d_tables, jpeg_scratch_.as<void>(), lay, d_stream, staged_cap, d_size), lay,
-                       stream_);
+    launch_jpeg_encode(
+        jpeg_args(jpeg_source(surf, fh, fw, channel_order), d_tables, jpeg_scratch_.as<void>(), lay, d_stream, staged_cap, d_size, optimize), lay,
+        stream_);
     launch_jpeg_flush(d_stream, h_dev, d_size, staged_cap, reinterpret_cast<long long*>(static_cast<uint8_t*>(h_dev) + cap16), stream_);
     WHENET_HIP_CHECK(hipEventRecord(slot.done, stream_));      // the collect call waits for the stream's bytes as well
     slot.jpg_host.push_back({out, cap, staged_cap, size, status, frame_index});

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <memory>
 
 #include "overlay_host.h"
 
@@ -18,7 +19,9 @@ namespace whenet {
 constexpr int JPEG_MAX_SIDE = 8192;
 constexpr int JPEG_HEADER_BYTES = WHENET_JPEG_HEADER_BYTES;
 constexpr int JPEG_BLOCK_MAX_BITS = 11 + 11 + 63 * (16 + 10);      // DC code + extra bits, 63 x (AC code + extra bits): no EOB then
-constexpr int JPEG_MCU_BLOCKS = 6;                                  // Y00, Y01, Y10, Y11, Cb, Cr
+constexpr int JPEG_MCU_BLOCKS = 6;                                  // 4:2:0: Y00, Y01, Y10, Y11, Cb, Cr
+constexpr int JPEG_MAX_INTERVAL_BLOCKS = (JPEG_MAX_SIDE / 16) * JPEG_MCU_BLOCKS;      // 3,072: the most blocks of an interval, any sampling
+constexpr int JPEG_HUFF_MAX_LEN = 257;                              // no code of 257 symbols is longer before the lengths are limited
 constexpr int JPEG_CODE_MAX_BITS = 26;                              // the longest code word with its extra bits
 
 // zigzag position -> natural index v * 8 + u (T.81 figure A.6)
@@ -62,6 +65,17 @@ struct JpegTables {
     uint8_t header[JPEG_HEADER_BYTES + 3];
 };
 
+// The MCU of a sampling (WHENET_JPEG_420 / 422 / 444): hs x vs luma blocks in row order, then Cb, then Cr; the chroma planes are
+// ceil(h / vs) x ceil(w / hs).  A restart interval is one MCU row: ceil(w / 8 hs) MCUs.
+struct JpegGeom {
+    int sampling, hs, vs, luma, blocks;      // luma = hs vs blocks of Y in an MCU, blocks = luma + 2
+};
+WHENET_HD constexpr JpegGeom jpeg_geom(int sampling) {
+    return sampling == WHENET_JPEG_444 ? JpegGeom{WHENET_JPEG_444, 1, 1, 1, 3}
+                                       : (sampling == WHENET_JPEG_422 ? JpegGeom{WHENET_JPEG_422, 2, 1, 2, 4} : JpegGeom{WHENET_JPEG_420, 2, 2, 4, 6});
+}
+inline bool jpeg_sampling_ok(int sampling) { return sampling == WHENET_JPEG_420 || sampling == WHENET_JPEG_422 || sampling == WHENET_JPEG_444; }
+
 // One source frame: planes (host or device memory), their pitches, and the JFIF row of the BGR -> 4:2:0 rule for packed pixels
 struct JpegSource {
     const uint8_t* plane[3];
@@ -70,12 +84,16 @@ struct JpegSource {
     Bgr2YuvCoeffs kc;
 };
 
-inline int jpeg_mcu_cols(int w) { return (w + 15) >> 4; }
-inline int jpeg_mcu_rows(int h) { return (h + 15) >> 4; }
+inline int jpeg_mcu_cols(int w, int sampling = WHENET_JPEG_420) { return (w + 8 * jpeg_geom(sampling).hs - 1) / (8 * jpeg_geom(sampling).hs); }
+inline int jpeg_mcu_rows(int h, int sampling = WHENET_JPEG_420) { return (h + 8 * jpeg_geom(sampling).vs - 1) / (8 * jpeg_geom(sampling).vs); }
 // the unstuffed bytes an interval (one MCU row) can have at most, and the bound of the whole stream (header, every byte stuffed,
 // RSTm behind every interval but the last, EOI behind the last)
-inline int64_t jpeg_interval_bytes(int w) { return (int64_t(jpeg_mcu_cols(w)) * JPEG_MCU_BLOCKS * JPEG_BLOCK_MAX_BITS + 7) / 8; }
-inline int64_t jpeg_bound(int h, int w) { return JPEG_HEADER_BYTES + int64_t(jpeg_mcu_rows(h)) * (2 * jpeg_interval_bytes(w) + 2); }
+inline int64_t jpeg_interval_bytes(int w, int sampling = WHENET_JPEG_420) {
+    return (int64_t(jpeg_mcu_cols(w, sampling)) * jpeg_geom(sampling).blocks * JPEG_BLOCK_MAX_BITS + 7) / 8;
+}
+inline int64_t jpeg_bound(int h, int w, int sampling = WHENET_JPEG_420) {
+    return JPEG_HEADER_BYTES + int64_t(jpeg_mcu_rows(h, sampling)) * (2 * jpeg_interval_bytes(w, sampling) + 2);
+}
 
 inline int jpeg_scaled_q(int base, int quality) {
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
@@ -92,8 +110,11 @@ inline const char* jpeg_check_size(int h, int w, int quality) {
 
 // ... and of a whole encode call
 inline const char* jpeg_check(const whenet_surface_t* src, int h, int w, int channel_order, int quality, const void* out, int64_t cap,
-                              const void* size) {
+                              const void* size, int sampling = WHENET_JPEG_420) {
     if (src == nullptr || size == nullptr || (out == nullptr && cap > 0)) return "NULL argument";
+    if (!jpeg_sampling_ok(sampling)) return "unknown sampling (WHENET_JPEG_420, WHENET_JPEG_422 or WHENET_JPEG_444)";
+    if (sampling != WHENET_JPEG_420 && (src->format == WHENET_YUV_NV12 || src->format == WHENET_YUV_I420))
+        return "an NV12 / I420 source carries 4:2:0 chroma: 4:2:2 and 4:4:4 streams take packed pixels (WHENET_SURF_PACKED)";
     if (cap < 0) return "negative capacity";
     if (const char* bad = jpeg_check_size(h, w, quality)) return bad;
     int rows[3], row_bytes[3];
@@ -119,8 +140,9 @@ inline JpegSource jpeg_source(const whenet_surface_t& src, int h, int w, int cha
     return s;
 }
 
-// The tables and the header of (h, w, quality), all three valid
-inline void jpeg_build_tables(int h, int w, int quality, JpegTables& t) {
+// The tables and the header of (h, w, quality, sampling), all four valid
+inline void jpeg_build_tables(int h, int w, int quality, JpegTables& t, int sampling = WHENET_JPEG_420) {
+    const JpegGeom g = jpeg_geom(sampling);
     std::memset(&t, 0, sizeof(t));
     for (int c = 0; c < 2; ++c)
         for (int i = 0; i < 64; ++i) t.q[c][i] = jpeg_scaled_q(JPEG_QBASE[c][i], quality);
@@ -147,18 +169,21 @@ inline void jpeg_build_tables(int h, int w, int quality, JpegTables& t) {
         for (int k = 0; k < 64; ++k) put(t.q[c][JPEG_ZIGZAG[k]]);
     }
     put(0xFF), put(0xC0), put16(17), put(8), put16(h), put16(w), put(3);      // SOF0
-    put(1), put(0x22), put(0), put(2), put(0x11), put(1), put(3), put(0x11), put(1);
+    put(1), put((g.hs << 4) | g.vs), put(0), put(2), put(0x11), put(1), put(3), put(0x11), put(1);
     for (int tb = 0; tb < 4; ++tb) {                                   // DHT: DC0, AC0, DC1, AC1
         put(0xFF), put(0xC4), put16(2 + 1 + 16 + JPEG_HUFF_COUNT[tb]), put(((tb & 1) << 4) | (tb >> 1));
         for (int l = 0; l < 16; ++l) put(JPEG_HUFF_BITS[tb][l]);
         for (int i = 0; i < JPEG_HUFF_COUNT[tb]; ++i) put(JPEG_HUFF_VALS[tb][i]);
     }
-    put(0xFF), put(0xDD), put16(4), put16(jpeg_mcu_cols(w));           // DRI: one interval per MCU row
+    put(0xFF), put(0xDD), put16(4), put16(jpeg_mcu_cols(w, sampling));      // DRI: one interval per MCU row
     put(0xFF), put(0xDA), put16(12), put(3), put(1), put(0x00), put(2), put(0x11), put(3), put(0x11), put(0), put(63), put(0);      // SOS
 }
 
-// The sample (y, x) of component comp (0 Y, 1 Cb, 2 Cr) on its own plane, the edge replicated
+// The sample (y, x) of component comp (0 Y, 1 Cb, 2 Cr) on its own plane, the edge replicated.  A chroma sample of packed pixels is
+// overlay_cb / overlay_cr of R, G, B sums worth four pixels: the hs x vs pixels it covers, times 4 / (hs vs).
+template <int S = WHENET_JPEG_420>
 WHENET_HD inline int jpeg_sample(const JpegSource& s, int comp, int y, int x) {
+    constexpr JpegGeom g = jpeg_geom(S);
     if (comp == 0) {
         y = y < s.h - 1 ? y : s.h - 1, x = x < s.w - 1 ? x : s.w - 1;
         if (s.format != WHENET_SURF_PACKED) return s.plane[0][size_t(y) * size_t(s.pitch[0]) + size_t(x)];
@@ -166,36 +191,46 @@ WHENET_HD inline int jpeg_sample(const JpegSource& s, int comp, int y, int x) {
         const int ri = s.channel_order == WHENET_BGR ? 2 : 0;
         return overlay_luma(s.kc, p[ri], p[1], p[2 - ri]);
     }
-    const int ch = (s.h + 1) >> 1, cw = (s.w + 1) >> 1;
+    const int ch = (s.h + g.vs - 1) / g.vs, cw = (s.w + g.hs - 1) / g.hs;
     y = y < ch - 1 ? y : ch - 1, x = x < cw - 1 ? x : cw - 1;
     if (s.format == WHENET_YUV_I420) return s.plane[comp][size_t(y) * size_t(s.pitch[comp]) + size_t(x)];
     if (s.format == WHENET_YUV_NV12) return s.plane[1][size_t(y) * size_t(s.pitch[1]) + 2 * size_t(x) + size_t(comp - 1)];
     const int ri = s.channel_order == WHENET_BGR ? 2 : 0;
     int rs = 0, gs = 0, bs = 0;
-    for (int dy = 0; dy < 2; ++dy)
-        for (int dx = 0; dx < 2; ++dx) {
-            const int yy = 2 * y + dy < s.h - 1 ? 2 * y + dy : s.h - 1, xx = 2 * x + dx < s.w - 1 ? 2 * x + dx : s.w - 1;
+    for (int dy = 0; dy < g.vs; ++dy)
+        for (int dx = 0; dx < g.hs; ++dx) {
+            const int yy = g.vs * y + dy < s.h - 1 ? g.vs * y + dy : s.h - 1, xx = g.hs * x + dx < s.w - 1 ? g.hs * x + dx : s.w - 1;
             const uint8_t* p = s.plane[0] + size_t(yy) * size_t(s.pitch[0]) + 3 * size_t(xx);
             rs += p[ri], gs += p[1], bs += p[2 - ri];
         }
-    return comp == 1 ? overlay_cb(s.kc, rs, gs, bs) : overlay_cr(s.kc, rs, gs, bs);
+    constexpr int k = 4 / (g.hs * g.vs);
+    return comp == 1 ? overlay_cb(s.kc, k * rs, k * gs, k * bs) : overlay_cr(s.kc, k * rs, k * gs, k * bs);
 }
 
-// block i of an interval's 6 * mcu_cols blocks: its component and the first sample of it on the component's plane
+// block i of an interval's blocks: its component and the first sample of it on the component's plane
+template <int S = WHENET_JPEG_420>
 WHENET_HD inline void jpeg_block_origin(int interval, int i, int& comp, int& y0, int& x0) {
-    const int m = i / JPEG_MCU_BLOCKS, c = i - m * JPEG_MCU_BLOCKS;
-    if (c < 4) {
-        comp = 0, y0 = interval * 16 + (c >> 1) * 8, x0 = m * 16 + (c & 1) * 8;
+    constexpr JpegGeom g = jpeg_geom(S);
+    const int m = i / g.blocks, c = i - m * g.blocks;
+    if (c < g.luma) {
+        comp = 0, y0 = (interval * g.vs + c / g.hs) * 8, x0 = (m * g.hs + c % g.hs) * 8;
     } else {
-        comp = c - 3, y0 = interval * 8, x0 = m * 8;
+        comp = c - g.luma + 1, y0 = interval * 8, x0 = m * 8;
     }
 }
 // ... and the block before it of the same component in the interval, whose DC is its predictor (-1: none, the predictor is 0)
+template <int S = WHENET_JPEG_420>
 WHENET_HD inline int jpeg_block_before(int i) {
-    const int m = i / JPEG_MCU_BLOCKS, c = i - m * JPEG_MCU_BLOCKS;
-    if (c >= 1 && c <= 3) return i - 1;
+    constexpr JpegGeom g = jpeg_geom(S);
+    const int m = i / g.blocks, c = i - m * g.blocks;
+    if (c >= 1 && c < g.luma) return i - 1;
     if (m == 0) return -1;
-    return c == 0 ? i - 3 : i - JPEG_MCU_BLOCKS;
+    return c == 0 ? i - g.blocks + g.luma - 1 : i - g.blocks;      // the last luma block of the MCU before, or the same chroma block of it
+}
+// ... and whether it is a luma block (tables 0) or a chroma block (tables 1)
+template <int S = WHENET_JPEG_420>
+WHENET_HD inline bool jpeg_block_is_luma(int i) {
+    return i % jpeg_geom(S).blocks < jpeg_geom(S).luma;
 }
 
 // out[u] = sum_x T[u][x] in[x]: one pass of the forward DCT over 8 values
@@ -286,11 +321,12 @@ struct JpegBitWriter {
     }
 };
 
+template <int S = WHENET_JPEG_420>
 inline void jpeg_block_host(const JpegSource& s, const JpegTables& t, int comp, int y0, int x0, int16_t zz[64]) {
     int r[8][8], col[8], b[8];
     for (int y = 0; y < 8; ++y) {
         int p[8], a[8];
-        for (int x = 0; x < 8; ++x) p[x] = jpeg_sample(s, comp, y0 + y, x0 + x) - 128;
+        for (int x = 0; x < 8; ++x) p[x] = jpeg_sample<S>(s, comp, y0 + y, x0 + x) - 128;
         jpeg_dct8(p, a);
         for (int u = 0; u < 8; ++u) r[y][u] = jpeg_dct_round(a[u]);
     }
@@ -302,27 +338,193 @@ inline void jpeg_block_host(const JpegSource& s, const JpegTables& t, int comp, 
     }
 }
 
-// The whole stream to out[0 .. cap); returns its full length
-inline int64_t jpeg_encode_host(const JpegSource& s, const JpegTables& t, uint8_t* out, int64_t cap) {
+// ---- optimised Huffman tables (T.81 K.2, figures K.1 - K.4, ties as libjpeg's jpeg_gen_optimal_table breaks them) ----
+// The symbols of a block, in order, to sink.symbol(cls, sym): cls 0 the DC category, cls 1 a (run, size) symbol, ZRL or EOB.  The
+// walk of jpeg_block_codes without the tables.
+template <typename Sink>
+WHENET_HD inline void jpeg_block_symbols(const int16_t* zz, int pred, Sink& sink) {
+    sink.symbol(0, jpeg_bit_size(int(zz[0]) - pred));
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+        const int c = zz[k];
+        if (c == 0) {
+            ++run;
+            continue;
+        }
+        for (; run > 15; run -= 16) sink.symbol(1, 0xF0);
+        sink.symbol(1, (run << 4) | jpeg_bit_size(c));
+        run = 0;
+    }
+    if (run > 0) sink.symbol(1, 0x00);
+}
+
+// What an optimised encode builds for itself: the four histograms (DC0, AC0, DC1, AC1), the codes the pack stage reads, and the
+// header with DHT segments that list the occurring symbols only (at most JPEG_HEADER_BYTES long)
+struct JpegOptTables {
+    uint32_t hist[4][256];
+    uint16_t code[4][256];
+    uint8_t len[4][256];
+    uint8_t header[JPEG_HEADER_BYTES + 3];
+    int32_t header_bytes;
+};
+
+// The work arrays of one table's construction (LDS on the device): frequencies with the reserved code point at 256, the code size
+// and the chain of every symbol, the number of codes of each length
+struct JpegHuffWork {
+    uint64_t freq[257];      // (the sum of 256 uint32 frequencies fits)
+    int16_t codesize[257];
+    int16_t others[257];
+    int16_t bits[JPEG_HUFF_MAX_LEN + 1];
+    int16_t pos[JPEG_HUFF_MAX_LEN + 1];
+};
+
+inline void jpeg_huff_begin(const uint32_t freq[256], JpegHuffWork& k) {
+    for (int i = 0; i < 256; ++i) k.freq[i] = freq[i], k.codesize[i] = 0, k.others[i] = -1;
+    k.freq[256] = 1, k.codesize[256] = 0, k.others[256] = -1;      // the reserved code point: no code is all ones
+}
+// the symbol of least non-zero frequency other than `skip`, the LARGER value on a tie (-1: none): figure K.1's search (the host's
+// form; the table kernel runs the same search as a wave-wide minimum)
+inline int jpeg_huff_least(const JpegHuffWork& k, int skip) {
+    int c = -1;
+    uint64_t v = ~uint64_t(0);
+    for (int i = 0; i <= 256; ++i)
+        if (k.freq[i] != 0 && k.freq[i] <= v && i != skip) v = k.freq[i], c = i;
+    return c;
+}
+// figure K.1's merge of the two least frequent trees
+WHENET_HD inline void jpeg_huff_merge(JpegHuffWork& k, int c1, int c2) {
+    k.freq[c1] += k.freq[c2], k.freq[c2] = 0;
+    for (++k.codesize[c1]; k.others[c1] >= 0;) c1 = k.others[c1], ++k.codesize[c1];
+    k.others[c1] = int16_t(c2);
+    for (++k.codesize[c2]; k.others[c2] >= 0;) c2 = k.others[c2], ++k.codesize[c2];
+}
+// figures K.2 - K.4: the number of codes of each length, limited to 16, the reserved code point removed; the symbols by code size,
+// then by value.  Returns the number of symbols.
+WHENET_HD inline int jpeg_huff_finish(JpegHuffWork& k, uint8_t bits[16], uint8_t vals[256]) {
+    for (int l = 0; l <= JPEG_HUFF_MAX_LEN; ++l) k.bits[l] = 0;
+    for (int i = 0; i <= 256; ++i)
+        if (k.codesize[i] > 0) ++k.bits[k.codesize[i]];
+    int n = 0;      // where the symbols of a code size begin: the sizes, not the limited lengths, order the symbols
+    for (int l = 1; l <= JPEG_HUFF_MAX_LEN; ++l) k.pos[l] = int16_t(n), n += k.bits[l] - (k.codesize[256] == l ? 1 : 0);
+    for (int i = 0; i < 256; ++i)
+        if (k.codesize[i] > 0) vals[k.pos[k.codesize[i]]++] = uint8_t(i);
+    for (int i = JPEG_HUFF_MAX_LEN; i > 16; --i)
+        while (k.bits[i] > 0) {
+            int j = i - 2;
+            while (k.bits[j] == 0) --j;
+            k.bits[i] -= 2, ++k.bits[i - 1], k.bits[j + 1] += 2, --k.bits[j];
+        }
+    int last = 16;
+    while (last > 0 && k.bits[last] == 0) --last;
+    if (last > 0) --k.bits[last];      // (last = 0: no symbol occurs at all, a table that is never built)
+    for (int l = 1; l <= 16; ++l) bits[l - 1] = uint8_t(k.bits[l]);
+    return n;
+}
+// The table of a histogram: whenet_jpeg_optimal_table
+inline int jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256]) {
+    JpegHuffWork k;
+    jpeg_huff_begin(freq, k);
+    for (;;) {
+        const int c1 = jpeg_huff_least(k, -1), c2 = jpeg_huff_least(k, c1);
+        if (c2 < 0) break;
+        jpeg_huff_merge(k, c1, c2);
+    }
+    return jpeg_huff_finish(k, bits, vals);
+}
+// (bits, vals) -> the code and length of every symbol: the canonical codes of T.81 annex C
+WHENET_HD inline void jpeg_huff_codes(const uint8_t bits[16], const uint8_t* vals, uint16_t code[256], uint8_t len[256]) {
+    for (int i = 0; i < 256; ++i) code[i] = 0, len[i] = 0;
+    unsigned c = 0;
+    int n = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < bits[l - 1]; ++i, ++n) code[vals[n]] = uint16_t(c++), len[vals[n]] = uint8_t(l);
+        c <<= 1;
+    }
+}
+// The header of an optimised stream from the standard one of the same (h, w, quality, sampling): everything but the DHT segments
+// is copied (SOI .. SOF0 in front of them, DRI and SOS behind).  Returns its length.
+WHENET_HD inline int jpeg_opt_header(const uint8_t* std_header, const uint8_t bits[4][16], const uint8_t vals[4][256], const int count[4],
+                                     uint8_t* out) {
+    constexpr int front = 2 + 18 + 2 * 69 + 19, tail = 6 + 14;      // SOI APP0 DQT DQT SOF0 | DRI SOS
+    int p = 0;
+    for (int i = 0; i < front; ++i) out[p++] = std_header[i];
+    for (int tb = 0; tb < 4; ++tb) {
+        const int n = 2 + 1 + 16 + count[tb];
+        out[p++] = 0xFF, out[p++] = 0xC4, out[p++] = uint8_t(n >> 8), out[p++] = uint8_t(n & 255), out[p++] = uint8_t(((tb & 1) << 4) | (tb >> 1));
+        for (int l = 0; l < 16; ++l) out[p++] = bits[tb][l];
+        for (int i = 0; i < count[tb]; ++i) out[p++] = vals[tb][i];
+    }
+    for (int i = 0; i < tail; ++i) out[p++] = std_header[JPEG_HEADER_BYTES - tail + i];
+    return p;
+}
+
+struct JpegHistSink {
+    uint32_t* hist;      // [2][256]: the component's DC and AC histogram
+    void symbol(int cls, int sym) { ++hist[cls * 256 + sym]; }
+};
+
+// The whole stream to out[0 .. cap); returns its full length.  optimize: the tables are built from the frame's own symbols first
+// (hist, when not NULL, receives the four histograms)
+template <int S>
+inline int64_t jpeg_encode_host_s(const JpegSource& s, const JpegTables& t, uint8_t* out, int64_t cap, bool optimize, uint32_t (*hist)[256]) {
+    constexpr JpegGeom g = jpeg_geom(S);
     JpegByteSink o{out, cap, 0};
-    for (int i = 0; i < JPEG_HEADER_BYTES; ++i) o.byte(t.header[i]);
-    const int R = jpeg_mcu_rows(s.h), B = jpeg_mcu_cols(s.w) * JPEG_MCU_BLOCKS;
+    const int R = jpeg_mcu_rows(s.h, S), B = jpeg_mcu_cols(s.w, S) * g.blocks;
+    const uint16_t(*code)[256] = t.code;
+    const uint8_t(*len)[256] = t.len;
+    const uint8_t* header = t.header;
+    int header_bytes = JPEG_HEADER_BYTES;
+    std::unique_ptr<JpegOptTables> opt;
+    if (optimize) {
+        opt.reset(new JpegOptTables);
+        std::memset(opt.get(), 0, sizeof(JpegOptTables));
+        for (int r = 0; r < R; ++r) {
+            int pred[3] = {0, 0, 0};
+            for (int i = 0; i < B; ++i) {
+                int comp, y0, x0;
+                int16_t zz[64];
+                jpeg_block_origin<S>(r, i, comp, y0, x0);
+                jpeg_block_host<S>(s, t, comp, y0, x0, zz);
+                JpegHistSink sink{opt->hist[comp == 0 ? 0 : 2]};
+                jpeg_block_symbols(zz, pred[comp], sink);
+                pred[comp] = zz[0];
+            }
+        }
+        uint8_t bits[4][16], vals[4][256];
+        int count[4];
+        for (int tb = 0; tb < 4; ++tb) {
+            count[tb] = jpeg_optimal_table(opt->hist[tb], bits[tb], vals[tb]);
+            jpeg_huff_codes(bits[tb], vals[tb], opt->code[tb], opt->len[tb]);
+        }
+        opt->header_bytes = jpeg_opt_header(t.header, bits, vals, count, opt->header);
+        code = opt->code, len = opt->len, header = opt->header, header_bytes = opt->header_bytes;
+        if (hist != nullptr) std::memcpy(hist, opt->hist, sizeof(opt->hist));
+    }
+    for (int i = 0; i < header_bytes; ++i) o.byte(header[i]);
     for (int r = 0; r < R; ++r) {
         JpegBitWriter bw{o};
         int pred[3] = {0, 0, 0};
         for (int i = 0; i < B; ++i) {
             int comp, y0, x0;
             int16_t zz[64];
-            jpeg_block_origin(r, i, comp, y0, x0);
-            jpeg_block_host(s, t, comp, y0, x0, zz);
+            jpeg_block_origin<S>(r, i, comp, y0, x0);
+            jpeg_block_host<S>(s, t, comp, y0, x0, zz);
             const int tb = comp == 0 ? 0 : 2;
-            jpeg_block_codes(zz, pred[comp], t.code[tb], t.len[tb], t.code[tb + 1], t.len[tb + 1], bw);
+            jpeg_block_codes(zz, pred[comp], code[tb], len[tb], code[tb + 1], len[tb + 1], bw);
             pred[comp] = zz[0];
         }
         bw.pad();
         o.byte(0xFF), o.byte(r + 1 < R ? 0xD0 + (r & 7) : 0xD9);      // RSTm, or EOI behind the last interval
     }
     return o.pos;
+}
+
+// `t`: the tables of jpeg_build_tables for the same sampling
+inline int64_t jpeg_encode_host(const JpegSource& s, const JpegTables& t, uint8_t* out, int64_t cap, int sampling = WHENET_JPEG_420,
+                                bool optimize = false, uint32_t (*hist)[256] = nullptr) {
+    if (sampling == WHENET_JPEG_444) return jpeg_encode_host_s<WHENET_JPEG_444>(s, t, out, cap, optimize, hist);
+    if (sampling == WHENET_JPEG_422) return jpeg_encode_host_s<WHENET_JPEG_422>(s, t, out, cap, optimize, hist);
+    return jpeg_encode_host_s<WHENET_JPEG_420>(s, t, out, cap, optimize, hist);
 }
 
 }  // namespace whenet

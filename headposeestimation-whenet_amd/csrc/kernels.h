@@ -640,11 +640,18 @@ void launch_overlay_draw(const OverlayDrawArgs& a, hipStream_t stream);
 //   count   the 0xFF bytes of every interval -> slen [R] = the interval's stuffed length
 //   write   the header, every interval's stuffed bytes at 629 + sum of (slen + 2) before it, RSTm / EOI, and the total length
 //           into *size -- every byte store checked against `cap`, so a stream that does not fit leaves dst's tail untouched.
-// R = ceil(h / 16) intervals of B = 6 ceil(w / 16) blocks.  JpegScratch lays the work buffers out in one allocation.
+// R = ceil(h / 16) intervals of B = 6 ceil(w / 16) blocks at 4:2:0; 4:2:2 and 4:4:4 have R = ceil(h / 8) intervals of 4 ceil(w / 16)
+// and 3 ceil(w / 8) blocks (JpegGeom; dct, hist and pack are instantiated per sampling, so 4:2:0 keeps its code).  An optimised
+// encode runs two more kernels between dct and pack, behind a memset of its four histograms:
+//   hist    one workgroup per interval, a lane per block: the blocks' symbols into 4 x 256 LDS counters, those into the global ones
+//   table   one workgroup: T.81 K.2 on the four histograms -> this encode's codes, header (occurring symbols only) and header length
+// pack then reads the codes, write the header and its length, from the encode's own JpegOptTables in the work buffers.
+// JpegScratch lays the work buffers out in one allocation.
 struct JpegScratch {
     int R, B, interval_dwords;
-    size_t coef, bits, bits_bytes, ulen, slen, bytes;      // byte offsets, the memset's extent, the allocation's size
-    JpegScratch(int h, int w);
+    JpegGeom geom;
+    size_t coef, bits, bits_bytes, ulen, slen, opt, bytes;      // byte offsets, the memset's extent, the allocation's size
+    JpegScratch(int h, int w, int sampling = WHENET_JPEG_420);
 };
 struct JpegArgs {
     JpegSource src;
@@ -657,9 +664,15 @@ struct JpegArgs {
     long long cap;
     long long* size;               // one int64: the full length
     int R, B, interval_dwords;
+    JpegGeom geom;
+    const uint16_t (*code)[256];   // what pack reads: the tables' or the encode's own
+    const uint8_t (*len)[256];
+    const uint8_t* header;         // what write copies: the tables' (629 bytes) or the encode's own (*header_bytes)
+    const int32_t* header_bytes;   // nullptr: JPEG_HEADER_BYTES
+    JpegOptTables* opt;            // nullptr: the standard tables
 };
 JpegArgs jpeg_args(const JpegSource& src, const JpegTables* d_tables, void* d_scratch, const JpegScratch& lay, void* d_dst, long long cap,
-                   void* d_size);
+                   void* d_size, bool optimize = false);
 void launch_jpeg_encode(const JpegArgs& a, const JpegScratch& lay, hipStream_t stream);
 // min(*d_size, cap) bytes of a stream, rounded up to whole 16-byte vectors, from d_stream to `to` (both 16-byte aligned and
 // ceil(cap / 16) vectors long), and *d_size to *to_size: `to` may be pinned host memory as the device addresses it

@@ -147,6 +147,16 @@ _PROTOS = {
     "whenet_op_jpeg_encode": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "whenet_jpeg_encode_device": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "whenet_frame_annotate_jpeg": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    "whenet_jpeg_optimal_table": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
+    "whenet_jpeg_header_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "whenet_jpeg_bound_ex": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "whenet_jpeg_encode_host_ex": (C.c_int, [C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64,
+                                             C.POINTER(C.c_int64), _P]),
+    "whenet_op_jpeg_encode_ex": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64,
+                                           C.POINTER(C.c_int64), _P]),
+    "whenet_jpeg_encode_device_ex": (C.c_int, [_P, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64,
+                                               _P, _P]),
+    "whenet_frame_annotate_jpeg_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "whenet_jpeg_parse": (C.c_int, [_P, C.c_int64, C.POINTER(JpegInfoC)]),
     "whenet_jpeg_decode_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, _P]),
     "whenet_jpeg_decode_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, _P]),
@@ -575,37 +585,68 @@ class CapacityError(RuntimeError):
         self.needed = int(needed)
 
 
-def jpeg_header(h: int, w: int, quality: int = JPEG_DEFAULT_QUALITY):
-    """`whenet_jpeg_header`: (the 629 header bytes SOI..SOS of an h x w stream, the two scaled quantiser tables int32 [2,64] in
-    natural order).  Pure host arithmetic inside the library (no GPU needed)."""
+JPEG_SAMPLING = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}      # WHENET_JPEG_420 / 422 / 444
+
+
+def jpeg_sampling_code(sampling) -> int:
+    if sampling not in JPEG_SAMPLING:
+        raise ValueError(f"sampling must be '4:2:0', '4:2:2' or '4:4:4', got {sampling!r}")
+    return JPEG_SAMPLING[sampling]
+
+
+def jpeg_header(h: int, w: int, quality: int = JPEG_DEFAULT_QUALITY, sampling: str = "4:2:0"):
+    """`whenet_jpeg_header_ex`: (the 629 header bytes SOI..SOS of an h x w stream with the standard tables, the two scaled quantiser
+    tables int32 [2,64] in natural order).  Pure host arithmetic inside the library (no GPU needed)."""
     lib = load()
     out = np.empty(JPEG_HEADER_BYTES, np.uint8)
     q = np.empty((2, 64), np.int32)
-    n = lib.whenet_jpeg_header(int(h), int(w), int(quality), _ptr(out), out.size, _ptr(q))
+    n = lib.whenet_jpeg_header_ex(int(h), int(w), int(quality), jpeg_sampling_code(sampling), _ptr(out), out.size, _ptr(q))
     if n < 0:
         raise_for(n, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return out[:n].tobytes(), q
 
 
-def jpeg_bound(h: int, w: int) -> int:
-    """`whenet_jpeg_bound`: a capacity no stream of an h x w frame exceeds."""
+def jpeg_bound(h: int, w: int, sampling: str = "4:2:0") -> int:
+    """`whenet_jpeg_bound_ex`: a capacity no stream of an h x w frame exceeds."""
     lib = load()
-    n = int(lib.whenet_jpeg_bound(int(h), int(w)))
+    n = int(lib.whenet_jpeg_bound_ex(int(h), int(w), jpeg_sampling_code(sampling)))
     if n < 0:
         raise_for(n, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return n
 
 
-def jpeg_encode_host(surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, out: np.ndarray):
-    """`whenet_jpeg_encode_host` into the uint8 array `out` (its size is the capacity): (return code, the stream's full length).
-    The code is OK or EOVERFLOW; anything else raises."""
+def jpeg_optimal_table(freq):
+    """`whenet_jpeg_optimal_table`: the frequencies uint32 [256] of a table's symbols -> (bits uint8 [16], the number of codes of each
+    length 1..16; vals uint8 [count], the symbols in code order).  Pure host arithmetic inside the library."""
+    lib = load()
+    freq = np.ascontiguousarray(freq, np.uint32)
+    if freq.shape != (256,):
+        raise ValueError(f"freq must be uint32 [256], got {freq.shape}")
+    bits, vals, count = np.zeros(16, np.uint8), np.zeros(256, np.uint8), C.c_int(0)
+    rc = lib.whenet_jpeg_optimal_table(_ptr(freq), _ptr(bits), _ptr(vals), C.byref(count))
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return bits, vals[:count.value].copy()
+
+
+def jpeg_encode_host(surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, out: np.ndarray, sampling: str = "4:2:0",
+                     optimize: bool = False, hist=None):
+    """`whenet_jpeg_encode_host_ex` into the uint8 array `out` (its size is the capacity): (return code, the stream's full length).
+    The code is OK or EOVERFLOW; anything else raises.  `hist`: None or a uint32 [4,256] array for the histograms of optimize=True."""
     lib = load()
     size = C.c_int64(0)
-    rc = lib.whenet_jpeg_encode_host(C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality), _ptr(out) if out.size else None,
-                                     int(out.size), C.byref(size))
+    rc = lib.whenet_jpeg_encode_host_ex(C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality), jpeg_sampling_code(sampling),
+                                        int(bool(optimize)), _ptr(out) if out.size else None, int(out.size), C.byref(size),
+                                        None if hist is None else _ptr(_hist_array(hist)))
     if rc not in (OK, EOVERFLOW):
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
     return rc, int(size.value)
+
+
+def _hist_array(hist) -> np.ndarray:
+    if not isinstance(hist, np.ndarray) or hist.dtype != np.uint32 or hist.shape != (4, 256) or not hist.flags.c_contiguous:
+        raise ValueError("hist must be a C-contiguous uint32 [4,256] array")
+    return hist
 
 
 def _stream_array(data) -> np.ndarray:
@@ -1441,29 +1482,36 @@ class Handle:
         self._check(self._lib.whenet_op_annotate_ex(self._h, _ptr(frame), frame.shape[0], frame.shape[1], BGR if bgr else RGB, _ptr(rects),
                                                     _ptr(valid), _ptr(ypr), rects.shape[0], C.byref(surface), int(display)))
 
-    def op_jpeg_encode(self, surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, out: np.ndarray):
-        """`whenet_op_jpeg_encode`: the encoder's kernels alone, host to host (works on a postproc handle), into the uint8 array
-        `out` (its size is the capacity): (return code OK or EOVERFLOW, the stream's full length)."""
+    def op_jpeg_encode(self, surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, out: np.ndarray, sampling: str = "4:2:0",
+                       optimize: bool = False, hist=None):
+        """`whenet_op_jpeg_encode_ex`: the encoder's kernels alone, host to host (works on a postproc handle), into the uint8 array
+        `out` (its size is the capacity): (return code OK or EOVERFLOW, the stream's full length).  `hist`: None or a uint32 [4,256]
+        array for the device histograms of optimize=True."""
         size = C.c_int64(0)
-        rc = self._lib.whenet_op_jpeg_encode(self._h, C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality),
-                                             _ptr(out) if out.size else None, int(out.size), C.byref(size))
+        rc = self._lib.whenet_op_jpeg_encode_ex(self._h, C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality),
+                                                jpeg_sampling_code(sampling), int(bool(optimize)), _ptr(out) if out.size else None,
+                                                int(out.size), C.byref(size), None if hist is None else _ptr(_hist_array(hist)))
         if rc != EOVERFLOW:
             self._check(rc)
         return rc, int(size.value)
 
-    def jpeg_encode_device(self, surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, dst: int, cap: int, dsize: int, stream=None) -> None:
-        """`whenet_jpeg_encode_device`: enqueue the encoder on a surface in device memory; `dst` (cap bytes) and `dsize` (one int64)
-        are device addresses.  The host does not wait."""
-        self._check(self._lib.whenet_jpeg_encode_device(self._h, C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality),
-                                                        _P(int(dst)), int(cap), _P(int(dsize)), _stream(stream)))
+    def jpeg_encode_device(self, surface: SurfaceC, h: int, w: int, bgr: bool, quality: int, dst: int, cap: int, dsize: int, stream=None,
+                           sampling: str = "4:2:0", optimize: bool = False) -> None:
+        """`whenet_jpeg_encode_device_ex`: enqueue the encoder on a surface in device memory; `dst` (cap bytes) and `dsize` (one
+        int64) are device addresses.  The host does not wait."""
+        self._check(self._lib.whenet_jpeg_encode_device_ex(self._h, C.byref(surface), int(h), int(w), BGR if bgr else RGB, int(quality),
+                                                           jpeg_sampling_code(sampling), int(bool(optimize)), _P(int(dst)), int(cap),
+                                                           _P(int(dsize)), _stream(stream)))
 
-    def frame_annotate_jpeg(self, ticket: int, frame_index: int, display: int, quality: int, out: np.ndarray, result: np.ndarray) -> None:
-        """`whenet_frame_annotate_jpeg`: enqueue the annotated frame of a ticket as a JPEG stream into the uint8 array `out` (its size
-        is the capacity); result = int64 [2]: the stream's length and the status.  Both are complete when the ticket's collect call
-        returns and must stay alive until then."""
+    def frame_annotate_jpeg(self, ticket: int, frame_index: int, display: int, quality: int, out: np.ndarray, result: np.ndarray,
+                            sampling: str = "4:2:0", optimize: bool = False) -> None:
+        """`whenet_frame_annotate_jpeg_ex`: enqueue the annotated frame of a ticket as a JPEG stream into the uint8 array `out` (its
+        size is the capacity); result = int64 [2]: the stream's length and the status.  Both are complete when the ticket's collect
+        call returns and must stay alive until then."""
         status = result[1:].view(np.int32)
-        self._check(self._lib.whenet_frame_annotate_jpeg(self._h, int(ticket), int(frame_index), int(display), int(quality),
-                                                         _ptr(out) if out.size else None, int(out.size), _ptr(result), _ptr(status)))
+        self._check(self._lib.whenet_frame_annotate_jpeg_ex(self._h, int(ticket), int(frame_index), int(display), int(quality),
+                                                            jpeg_sampling_code(sampling), int(bool(optimize)),
+                                                            _ptr(out) if out.size else None, int(out.size), _ptr(result), _ptr(status)))
 
     def op_jpeg_decode(self, data, surface: SurfaceC, bgr: bool) -> np.ndarray:
         """`whenet_op_jpeg_decode`: the decoder's kernels alone, host to host (works on a postproc handle), into a host surface: the

@@ -551,22 +551,26 @@ class FramePipeline:
         for f in (self._jpeg.pop(ticket, ()) if self._jpeg else ()):
             f._done = True
 
-    def _jpeg_frame(self, ticket, index, h, w, quality, display, capacity) -> "JpegFrame":
+    def _jpeg_frame(self, ticket, index, h, w, quality, display, capacity, sampling="4:2:0", optimize=False) -> "JpegFrame":
         from . import jpeg
-        f = JpegFrame(int(w), int(h), jpeg.bound(int(h), int(w)) if capacity is None else int(capacity))
-        self._h.frame_annotate_jpeg(ticket, index, _lib.display_code(display), quality, f._out, f._result)
+        f = JpegFrame(int(w), int(h), jpeg.bound(int(h), int(w), sampling) if capacity is None else int(capacity))
+        self._h.frame_annotate_jpeg(ticket, index, _lib.display_code(display), quality, f._out, f._result, sampling, optimize)
         if self._jpeg is None:
             self._jpeg = {}
         self._jpeg.setdefault(ticket, []).append(f)
         return f
 
-    def annotate_jpeg(self, quality: int = 95, display: str = "simple", capacity=None) -> "JpegFrame":
+    def annotate_jpeg(self, quality: int = 95, display: str = "simple", capacity=None, sampling: str = "4:2:0",
+                      optimize: bool = False) -> "JpegFrame":
         """`annotate()` with the annotated frame compressed where it lies: the overlay goes into an I420 JFIF surface in device memory
         that the library owns, the JPEG encoder (`whenet_hip.jpeg`, csrc/jpeg.hip) runs behind it, and only the stream's bytes come
         back (demo_video.py:60, `out.write(frame)` into an MJPG writer).  Returns at once; the `JpegFrame`'s `tobytes()` is valid
         after the frame's `collect()` and raises before it.  `capacity` (default: `whenet_hip.jpeg.bound(h, w)`) is the room for the
         stream: one that does not fit raises `whenet_hip.jpeg.CapacityError`, naming the needed size, at `tobytes()`.  Call order as
-        `annotate()`: it is the frame's one annotate call.  The values `collect()` returns are unchanged."""
+        `annotate()`: it is the frame's one annotate call.  The values `collect()` returns are unchanged.  `sampling` "4:2:2" /
+        "4:4:4": the overlay goes into a packed surface in the pipeline's channel order instead (an I420 surface cannot carry the
+        chroma of one-pixel axes and text strokes), and the stream is `jpeg.encode_host(overlay.annotate_host(frame, ...),
+        sampling=...)`'s.  optimize=True: Huffman tables of the frame's own symbols, built on the device; still enqueue-only."""
         if not self._pending or self._pending[-1][1] is _CLIP:
             raise ValueError("annotate_jpeg: no frame with its heads enqueued (submit(), heads() or detect_heads() first; a clip takes "
                              "annotate_clip_jpeg())")
@@ -577,11 +581,11 @@ class FramePipeline:
         if self._annotated == ticket:
             raise ValueError("annotate_jpeg: the frame submitted last is annotated already")
         (h, w), = self._last_sizes
-        f = self._jpeg_frame(ticket, 0, h, w, quality, display, capacity)
+        f = self._jpeg_frame(ticket, 0, h, w, quality, display, capacity, sampling, optimize)
         self._annotated = ticket
         return f
 
-    def annotate_clip_jpeg(self, quality: int = 95, display: str = "simple", capacity=None):
+    def annotate_clip_jpeg(self, quality: int = 95, display: str = "simple", capacity=None, sampling: str = "4:2:0", optimize: bool = False):
         """`annotate_jpeg()` for every frame of the clip submitted last (after `detect_heads_clip()`, before its `collect_clip()`):
         a list of one `JpegFrame` per frame, valid after `collect_clip()`."""
         if not self._pending or self._pending[-1][1] is not _CLIP:
@@ -592,7 +596,7 @@ class FramePipeline:
         ticket = self._pending[-1][0]
         if self._annotated == ticket:
             raise ValueError("annotate_clip_jpeg: the clip submitted last is annotated already")
-        out = [self._jpeg_frame(ticket, i, h, w, quality, display, capacity) for i, (h, w) in enumerate(self._last_sizes)]
+        out = [self._jpeg_frame(ticket, i, h, w, quality, display, capacity, sampling, optimize) for i, (h, w) in enumerate(self._last_sizes)]
         self._annotated = ticket
         return out
 

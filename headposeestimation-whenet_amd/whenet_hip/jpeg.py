@@ -25,9 +25,10 @@ HEADER_BYTES = _lib.JPEG_HEADER_BYTES
 CapacityError = _lib.CapacityError
 
 
-def header(h: int, w: int, quality: int = DEFAULT_QUALITY) -> bytes:
-    """The 629 bytes SOI..SOS of the stream of an h x w frame: they depend on (h, w, quality) only."""
-    return _lib.jpeg_header(h, w, quality)[0]
+def header(h: int, w: int, quality: int = DEFAULT_QUALITY, sampling: str = "4:2:0") -> bytes:
+    """The 629 bytes SOI..SOS of the stream of an h x w frame with the standard tables: they depend on (h, w, quality, sampling)
+    only.  (An optimize=True stream carries its own, shorter, DHT segments.)"""
+    return _lib.jpeg_header(h, w, quality, sampling)[0]
 
 
 def quantisers(quality: int = DEFAULT_QUALITY) -> np.ndarray:
@@ -35,9 +36,15 @@ def quantisers(quality: int = DEFAULT_QUALITY) -> np.ndarray:
     return _lib.jpeg_header(16, 16, quality)[1]
 
 
-def bound(h: int, w: int) -> int:
-    """A capacity no stream of an h x w frame exceeds (`whenet_jpeg_bound`)."""
-    return _lib.jpeg_bound(h, w)
+def bound(h: int, w: int, sampling: str = "4:2:0") -> int:
+    """A capacity no stream of an h x w frame exceeds (`whenet_jpeg_bound_ex`); it does not depend on `optimize`."""
+    return _lib.jpeg_bound(h, w, sampling)
+
+
+def optimal_table(freq):
+    """(bits uint8 [16], vals uint8 [n]): the Huffman table T.81 K.2 gives the symbol frequencies uint32 [256], ties broken as libjpeg
+    breaks them (`whenet_jpeg_optimal_table`): what optimize=True builds from a frame's histograms."""
+    return _lib.jpeg_optimal_table(freq)
 
 
 def source_of(frame, what: str = "frame"):
@@ -72,26 +79,30 @@ def _handle_of(handle):
     return getattr(handle, "_handle", handle)      # a WHENet model or a _lib.Handle
 
 
-def encode(frame, quality: int = DEFAULT_QUALITY, handle=None, bgr: bool = True, capacity=None) -> bytes:
-    """The stream of `frame`, written by the kernels (`whenet_op_jpeg_encode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None
-    opens a postproc handle on device 0 for the call.  `capacity` (default: `bound(h, w)`) below the stream's length raises
-    `CapacityError` with the needed size."""
+def encode(frame, quality: int = DEFAULT_QUALITY, handle=None, bgr: bool = True, capacity=None, sampling: str = "4:2:0",
+           optimize: bool = False, hist=None) -> bytes:
+    """The stream of `frame`, written by the kernels (`whenet_op_jpeg_encode_ex`).  `handle`: a `WHENet` model or a `_lib.Handle`; None
+    opens a postproc handle on device 0 for the call.  `capacity` (default: `bound(h, w, sampling)`) below the stream's length raises
+    `CapacityError` with the needed size.  `sampling`: "4:2:0" (the default), "4:2:2" or "4:4:4" -- the last two take packed pixels
+    only (a YUVFrame carries 4:2:0 chroma).  optimize=True: Huffman tables built on the device from the frame's own symbols -- the
+    same pixels in a smaller stream; `hist`: a uint32 [4,256] array that receives the device histograms then."""
     s, h, w, _keep = source_of(frame)
-    out = np.empty(bound(h, w) if capacity is None else int(capacity), np.uint8)
+    out = np.empty(bound(h, w, sampling) if capacity is None else int(capacity), np.uint8)
     if handle is None:
         with _lib.Handle.postproc(0) as own:
-            rc, size = own.op_jpeg_encode(s, h, w, bgr, quality, out)
+            rc, size = own.op_jpeg_encode(s, h, w, bgr, quality, out, sampling, optimize, hist)
     else:
-        rc, size = _handle_of(handle).op_jpeg_encode(s, h, w, bgr, quality, out)
+        rc, size = _handle_of(handle).op_jpeg_encode(s, h, w, bgr, quality, out, sampling, optimize, hist)
     return _finish(rc, size, out)
 
 
-def encode_host(frame, quality: int = DEFAULT_QUALITY, bgr: bool = True, capacity=None) -> bytes:
-    """The same stream by pure host arithmetic inside the library (`whenet_jpeg_encode_host`, no GPU): the statement the kernels are
-    held to."""
+def encode_host(frame, quality: int = DEFAULT_QUALITY, bgr: bool = True, capacity=None, sampling: str = "4:2:0", optimize: bool = False,
+                hist=None) -> bytes:
+    """The same stream by pure host arithmetic inside the library (`whenet_jpeg_encode_host_ex`, no GPU): the statement the kernels
+    are held to."""
     s, h, w, _keep = source_of(frame)
-    out = np.empty(bound(h, w) if capacity is None else int(capacity), np.uint8)
-    rc, size = _lib.jpeg_encode_host(s, h, w, bgr, quality, out)
+    out = np.empty(bound(h, w, sampling) if capacity is None else int(capacity), np.uint8)
+    rc, size = _lib.jpeg_encode_host(s, h, w, bgr, quality, out, sampling, optimize, hist)
     return _finish(rc, size, out)
 
 

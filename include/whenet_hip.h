@@ -820,7 +820,41 @@ WHENET_API int whenet_frame_annotate_ex(whenet_t* h, int ticket, int frame_index
  *                  frame_index)'s one annotate call; the collect call's own results are bit for bit those of the same submission
  *                  without it.
  * WHENET_EINVAL: a NULL argument or plane, a pitch below the row bytes, an unknown format / channel order, a YUV source whose
- * matrix is not WHENET_YUV_JFIF, a side outside 1..8192, quality outside 1..100, cap < 0. */
+ * matrix is not WHENET_YUV_JFIF, a side outside 1..8192, quality outside 1..100, cap < 0.
+ * SAMPLING AND OPTIMISED TABLES (the _ex calls; additions to ABI 6).  Each _ex call is the call of the same name with two more
+ * arguments; sampling = WHENET_JPEG_420 and optimize = 0 give that call's bytes.
+ * SAMPLING.  WHENET_JPEG_420 (above), WHENET_JPEG_422 (H2V1) or WHENET_JPEG_444; any other value is WHENET_EINVAL.  The luma sampling
+ * factors hs x vs are 2x2, 2x1, 1x1; the MCU is 8 hs x 8 vs luma pixels: hs vs luma blocks in row order, then Cb, then Cr (Y0 Y1 Cb
+ * Cr at 4:2:2, Y Cb Cr at 4:4:4).  One restart interval per MCU row of that sampling: ceil(h / 8 vs) intervals, DRI = ceil(w / 8 hs).
+ * The SOF0 sampling byte of Y (0x22, 0x21, 0x11) and the DRI value are the only header bytes that differ.  The chroma planes are
+ * ceil(h / vs) x ceil(w / hs).  A chroma sample of packed pixels keeps the one rule of "BGR -> 4:2:0": overlay_cb / overlay_cr of
+ * R, G, B SUMS WORTH FOUR PIXELS -- 4:4:4 passes 4 x the pixel, 4:2:2 passes 2 x the sum of the two horizontal neighbours (the
+ * right edge replicated): Cb = clamp(((RU r + GU g + BU b + 2^21) >> 22) + 128) of those sums, which for 4:4:4 is
+ * ((RU R + GU G + BU B + 2^19) >> 20) + 128 of the pixel.  NV12 / I420 sources carry 4:2:0 chroma: with another sampling they are
+ * WHENET_EINVAL.
+ * OPTIMISED TABLES.  optimize != 0: the four Huffman tables are built from the frame's own symbols.  The histograms count, per
+ * table (DC0, AC0, DC1, AC1), the DC categories and the (run, size) / ZRL / EOB symbols exactly as the entropy coder emits them.
+ * A table follows T.81 K.2 (figures K.1 - K.4): a 257th symbol of frequency 1 is added (so no code is all ones); the two trees of
+ * least non-zero frequency are merged until one is left, ties broken towards the LARGER symbol value, as libjpeg's
+ * jpeg_gen_optimal_table does; code lengths above 16 are shortened by figure K.3; the reserved symbol is removed from the longest
+ * length; the symbols are listed by code size, then by value.  The DHT segments list the occurring symbols only, so the header
+ * SOI..SOS is shorter than WHENET_JPEG_HEADER_BYTES (at most 12 + 162 symbols occur per table pair: never longer).  The pixels of
+ * the decoded stream are those of the standard tables' stream.
+ * BOUND.  With B_s = (hs vs + 2) ceil(w / 8 hs) blocks per interval: bound = 629 + ceil(h / 8 vs) (2 ceil(1660 B_s / 8) + 2); it does
+ * not depend on optimize.
+ *   whenet_jpeg_optimal_table  pure host: freq[256] -> bits[16] (the codes of each length 1..16), vals (the symbols in code order)
+ *                  and *count (their number).  WHENET_EINVAL for a NULL pointer or when no frequency is non-zero.
+ *   whenet_jpeg_header_ex, whenet_jpeg_bound_ex   the standard-table header and the bound of a sampling.
+ *   whenet_jpeg_encode_host_ex, whenet_op_jpeg_encode_ex   hist (may be NULL) receives the four histograms when optimize != 0.
+ *   whenet_jpeg_encode_device_ex   as whenet_jpeg_encode_device: ENQUEUE-ONLY also with optimize (the histogram and table kernels
+ *                  run between the DCT and the pack kernel on the engine's stream; the tables, the header and its length are
+ *                  the encode's own device memory).
+ *   whenet_frame_annotate_jpeg_ex  at WHENET_JPEG_422 / 444 the overlay goes into a PACKED surface the engine owns, in the frame's
+ *                  channel order, and the encoder reads that: the stream is whenet_jpeg_encode_host_ex of whenet_annotate_host_ex's
+ *                  packed frame.  At WHENET_JPEG_420 the I420 surface above. */
+#define WHENET_JPEG_420 0
+#define WHENET_JPEG_422 1
+#define WHENET_JPEG_444 2
 #define WHENET_EOVERFLOW (-75)  /* the result does not fit the caller's capacity; the needed size is reported */
 #define WHENET_JPEG_HEADER_BYTES 629
 #define WHENET_JPEG_DEFAULT_QUALITY 95
@@ -838,6 +872,17 @@ WHENET_API int whenet_jpeg_encode_device(whenet_t* h, const whenet_surface_t* sr
                               int64_t cap, int64_t* dsize, void* stream);
 WHENET_API int whenet_frame_annotate_jpeg(whenet_t* h, int ticket, int frame_index, int display, int quality, uint8_t* out, int64_t cap,
                                int64_t* size, int32_t* status);
+WHENET_API int whenet_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256], int* count);
+WHENET_API int whenet_jpeg_header_ex(int h, int w, int quality, int sampling, uint8_t* out, int cap, int32_t qtables[2][64]);
+WHENET_API int64_t whenet_jpeg_bound_ex(int h, int w, int sampling);
+WHENET_API int whenet_jpeg_encode_host_ex(const whenet_surface_t* src, int h, int w, int channel_order, int quality, int sampling, int optimize,
+                               uint8_t* out, int64_t cap, int64_t* size, uint32_t hist[4][256]);
+WHENET_API int whenet_op_jpeg_encode_ex(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality, int sampling,
+                             int optimize, uint8_t* out, int64_t cap, int64_t* size, uint32_t hist[4][256]);
+WHENET_API int whenet_jpeg_encode_device_ex(whenet_t* h, const whenet_surface_t* src, int hh, int ww, int channel_order, int quality,
+                                 int sampling, int optimize, void* dst, int64_t cap, int64_t* dsize, void* stream);
+WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_index, int display, int quality, int sampling, int optimize,
+                                  uint8_t* out, int64_t cap, int64_t* size, int32_t* status);
 
 /* ---- JPEG DECODER: a JPEG still or an MJPG frame in, the resident frame out (additions to ABI 6).  demo.py starts with `cv2.imread`
  * of a JPEG, demo_video.py:49-53 with `cap.read()` -- for a camera or an MJPG file a Motion-JPEG decode.  Here the compressed bytes

@@ -14,7 +14,10 @@
     (v)   frame_pipeline_k4     the loop of bench.py's `frame_pipeline` leg (1280 x 720, k = 4: sync median, pipelined frames/s) as
                                 it is -- the code path of the parent commit -- next to the same loop with annotate_jpeg
 
-  python tools/jpeg_bench.py [--sizes 1080x1920 480x640] [--quality 95] [--rounds 7] [--iters 50]
+  python tools/jpeg_bench.py [--sizes 1080x1920 480x640] [--quality 95] [--rounds 7] [--iters 50] [--sampling 4:2:0] [--optimize]
+
+--sampling 4:2:2 / 4:4:4: the encoder is timed on a resident PACKED surface (what annotate_jpeg paints for these samplings) and
+Pillow encodes with the same `subsampling`; --optimize: Huffman tables of the frame's own symbols, on both sides.
 
 Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
 events on the stream the work is enqueued on.  One JSON line per size, one for (v).
@@ -57,11 +60,17 @@ def size_leg(m, h, w, args):
     ch, cw = (h + 1) // 2, (w + 1) // 2
     sync = torch.cuda.synchronize
 
+    packed = args.sampling != "4:2:0"
+    pillow_kw = dict(quality=args.quality, subsampling={"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}[args.sampling], optimize=args.optimize)
+    keywords = dict(sampling=args.sampling, optimize=args.optimize)
+
     def device_surface():
+        if packed:
+            return torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
         return YUVFrame.i420(torch.empty((h, w), dtype=torch.uint8, device="cuda"), torch.empty((ch, cw), dtype=torch.uint8, device="cuda"),
                              torch.empty((ch, cw), dtype=torch.uint8, device="cuda"), matrix="jfif")
 
-    res = {"frame": [h, w], "quality": args.quality, "heads": 4}
+    res = {"frame": [h, w], "quality": args.quality, "heads": 4, "sampling": args.sampling, "optimize": bool(args.optimize)}
     with FramePipeline(m, depth=1) as fp:
         # the annotated surface the encoder is timed on
         surf = device_surface()
@@ -70,11 +79,11 @@ def size_leg(m, h, w, args):
         fp.collect()
         sync()
         s, _ = overlay.surface_of(surf, h, w)
-        cap = jpeg.bound(h, w)
+        cap = jpeg.bound(h, w, args.sampling)
         dst = torch.empty(cap, dtype=torch.uint8, device="cuda")
         dsize = torch.zeros(1, dtype=torch.int64, device="cuda")
         stream = torch.cuda.current_stream().cuda_stream or None
-        encode = lambda: hnd.jpeg_encode_device(s, h, w, True, args.quality, dst.data_ptr(), cap, dsize.data_ptr(), stream=stream)
+        encode = lambda: hnd.jpeg_encode_device(s, h, w, True, args.quality, dst.data_ptr(), cap, dsize.data_ptr(), stream=stream, **keywords)
         for _ in range(5):
             encode()
         sync()
@@ -93,28 +102,30 @@ def size_leg(m, h, w, args):
         res["encoder_us"] = round(statistics.median(times), 1)
         res["encoder_call_host_us"] = round(statistics.median(calls), 1)      # the host's time in the enqueue-only call
         nbytes = int(dsize.item())
-        res["bytes_jpeg"], res["bytes_surface"] = nbytes, h * w + 2 * ch * cw
+        res["bytes_jpeg"], res["bytes_surface"] = nbytes, 3 * h * w if packed else h * w + 2 * ch * cw
         stream_bytes = dst[:nbytes].cpu().numpy().tobytes()
         # (ii): one frame, submit -> annotate -> collect, both ways
         def one(annotate):
             fp.submit(frame, boxes)
             annotate()
             fp.collect()
-        for annotate in (lambda: fp.annotate(surf), lambda: fp.annotate_jpeg(quality=args.quality)):
+        for annotate in (lambda: fp.annotate(surf), lambda: fp.annotate_jpeg(quality=args.quality, **keywords)):
             for _ in range(5):
                 one(annotate)
         res["annotate_us"] = round(median_us(lambda: [one(lambda: fp.annotate(surf)) for _ in range(args.iters)], args.rounds, sync) / args.iters, 1)
         res["annotate_jpeg_us"] = round(
-            median_us(lambda: [one(lambda: fp.annotate_jpeg(quality=args.quality)) for _ in range(args.iters)], args.rounds, sync) / args.iters, 1)
+            median_us(lambda: [one(lambda: fp.annotate_jpeg(quality=args.quality, **keywords)) for _ in range(args.iters)], args.rounds, sync) / args.iters, 1)
         res["added_us"] = round(res["annotate_jpeg_us"] - res["annotate_us"], 1)
         # the stream annotate_jpeg returns is the encoder's
         fp.submit(frame, boxes)
-        jf = fp.annotate_jpeg(quality=args.quality)
+        jf = fp.annotate_jpeg(quality=args.quality, **keywords)
         fp.collect()
         res["annotate_jpeg_equals_encoder"] = jf.tobytes() == stream_bytes
     # (iii): what it replaces
     planes_dev = [torch.empty((h, w), dtype=torch.uint8, device="cuda"), torch.empty((ch, cw), dtype=torch.uint8, device="cuda"),
                   torch.empty((ch, cw), dtype=torch.uint8, device="cuda")]
+    if packed:
+        planes_dev = [torch.empty((h, 3 * w), dtype=torch.uint8, device="cuda")]
     pinned = [torch.empty(p.shape, dtype=torch.uint8).pin_memory() for p in planes_dev]
 
     def d2h():
@@ -125,12 +136,15 @@ def size_leg(m, h, w, args):
     im.draft("YCbCr", im.size)
     ycc = im.copy()                                       # the same picture as full-resolution YCbCr for Pillow's encoder
     torch.set_num_threads(1)
+    from PIL import ImageFile
+    if args.optimize:
+        ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 3 * h * w)      # Pillow's optimize=True needs the whole stream in one buffer
 
     def pillow():
-        ycc.save(io.BytesIO(), format="JPEG", quality=args.quality, subsampling=2)
+        ycc.save(io.BytesIO(), format="JPEG", **pillow_kw)
     res["pillow_encode_us"] = round(median_us(pillow, args.rounds, lambda: None), 1)
     buf = io.BytesIO()
-    ycc.save(buf, format="JPEG", quality=args.quality, subsampling=2)
+    ycc.save(buf, format="JPEG", **pillow_kw)
     res["bytes_pillow"] = len(buf.getvalue())
     return res
 
@@ -140,10 +154,11 @@ def pipeline_leg(m, args):
     from whenet_hip import synth
     from whenet_hip.frames import FramePipeline
     frame, boxes = synth.video_frame(), synth.head_boxes(4)
-    out = {"frame": list(frame.shape[:2]), "heads": 4, "quality": args.quality}
+    out = {"frame": list(frame.shape[:2]), "heads": 4, "quality": args.quality, "sampling": args.sampling, "optimize": bool(args.optimize)}
+    keywords = dict(sampling=args.sampling, optimize=args.optimize)
     for arm in ("none", "annotate_jpeg"):
         with FramePipeline(m, depth=2) as fp:
-            extra = (lambda: fp.annotate_jpeg(quality=args.quality)) if arm == "annotate_jpeg" else (lambda: None)
+            extra = (lambda: fp.annotate_jpeg(quality=args.quality, **keywords)) if arm == "annotate_jpeg" else (lambda: None)
             lat = []
             for _ in range(260):
                 a = time.perf_counter()
@@ -172,6 +187,8 @@ def main():
     ap.add_argument("--quality", type=int, default=95)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--sampling", choices=["4:2:0", "4:2:2", "4:4:4"], default="4:2:0")
+    ap.add_argument("--optimize", action="store_true", help="Huffman tables of the frame's own symbols")
     args = ap.parse_args()
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
     import whenet
