@@ -1450,6 +1450,52 @@ int whenet_jpeg_progressive_counters(whenet_t* h, int64_t out[4]) {
     });
 }
 
+// ---- progressive streams in clips (jpeg_dec_clip_host.h: jpeg_clip_plan_progressive; jpeg_prog.hip) ----
+static_assert(WHENET_JPEG_CLIP_PROG_PLAN_FRAME_WORDS == whenet::JPEG_CLIP_PROG_PLAN_FRAME_WORDS &&
+                  WHENET_JPEG_CLIP_PROG_PLAN_TOTAL_WORDS == whenet::JPEG_CLIP_PROG_PLAN_TOTAL_WORDS,
+              "the header states the plan's words");
+int whenet_op_jpeg_decode_clip_progressive(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, const whenet_surface_t* dst,
+                                           int channel_order, int32_t* status, int entropy, int seg_bytes, int rule) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       "op_jpeg_decode_clip_progressive: entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_clip_progressive: seg_bytes must be a power of two in 4..4096");
+        e.op_jpeg_decode_clip(data, size, num_frames, dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, rule, 1);
+    });
+}
+
+int whenet_clip_begin_jpeg_progressive(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int rule,
+                                       int* ticket, int32_t* status) {
+    return begin_on_next_engine(h, ticket,
+                                [&](whenet::Engine& e) { return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule, 1); });
+}
+
+int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t* size, int num_frames, int entropy, int seg_bytes, int64_t* out) {
+    try {
+        WHENET_REQUIRE(num_frames >= 1 && num_frames <= whenet::JPEG_CLIP_MAX_FRAMES, WHENET_EINVAL,
+                       "jpeg_clip_plan_progressive: a clip holds 1..16 frames");
+        WHENET_REQUIRE(data != nullptr && size != nullptr && out != nullptr, WHENET_EINVAL, "jpeg_clip_plan_progressive: NULL argument");
+        std::vector<whenet::JpegProgPlan> plans(static_cast<size_t>(num_frames));
+        const whenet::JpegProgPlan* ptr[whenet::JPEG_CLIP_MAX_FRAMES];
+        whenet::JpegDecGeom g[whenet::JPEG_CLIP_MAX_FRAMES];
+        int64_t nbytes[whenet::JPEG_CLIP_MAX_FRAMES];
+        for (int f = 0; f < num_frames; ++f) {
+            whenet_jpeg_info_t info;
+            const std::string who = "jpeg_clip_plan_progressive: frame " + std::to_string(f);
+            if (const int rc = parse_scans_for_host(who.c_str(), data[f], size[f], info, plans[size_t(f)])) return rc;
+            g[f] = whenet::jpeg_dec_geom(info), nbytes[f] = size[f] - info.data_offset, ptr[f] = &plans[size_t(f)];
+        }
+        whenet::JpegClipProgPlan plan;
+        const char* bad = whenet::jpeg_clip_plan_progressive(g, nbytes, ptr, num_frames, entropy, seg_bytes, plan);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_clip_plan_progressive: ") + (bad ? bad : ""));
+        whenet::jpeg_clip_plan_progressive_words(plan, out);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

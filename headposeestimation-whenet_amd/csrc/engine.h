@@ -381,9 +381,16 @@ class Engine {
     // clip_begin_jpeg: the slot ends up as clip_begin (one size) or clip_begin_mixed (frames back to back) leaves it for the decoded
     // frames; status [frames][2] comes back through pinned memory with the ticket's collect call.
     // op_jpeg_decode_clip: the clip kernels alone, host to host, frame f into dst[f] at the caller's pitches between guard zones.
-    int clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule = -1);
+    // progressive = 1 (an argument only: clips do not read the option "jpeg_progressive"): a frame may be a SOF2 stream.  It is parsed
+    // with its scan plan, refused by that parser's reason before a slot is taken, and laid out by jpeg_clip_plan_progressive; the clip
+    // stays one H2D and one memset, launch L of the scan kernel covers level L of every progressive frame (always by level:
+    // "jpeg_prog_levels" is the single-stream path's knob), one finish launch, then the clip's inverse DCT and colour launches
+    // (launch_jpeg_decode_clip_progressive).  A baseline frame keeps the form it has in a baseline clip.  The progressive counters
+    // add a decode per progressive frame, the clip's scan launches and the scans of its frames.
+    int clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule = -1,
+                        int progressive = 0);
     void op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
-                             int32_t* status, int entropy = -1, int seg_bytes = 0, int rule = -1);
+                             int32_t* status, int entropy = -1, int seg_bytes = 0, int rule = -1, int progressive = 0);
     void add_jpeg_clip_counters(int64_t out[4]) const;      // clip decodes, their frames, their launches + memsets, their H2D copies
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
@@ -618,10 +625,13 @@ class Engine {
     int64_t jpeg_clip_counts_[4] = {0, 0, 0, 0};                         // add_jpeg_clip_counters
     struct JpegClipJob;      // the parsed headers, geometries and the plan of a clip (engine_post.cpp)
     void jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes, int rule,
-                           JpegClipJob& job) const;
+                           JpegClipJob& job, int progressive = 0) const;
     // records | tables | entropy bytes into `stage` (plan.upload_bytes), the records for a work buffer at d_base; recs: the same records
+    // (a progressive frame: its scan plan's share, a record as jpeg_prog_tail_args makes it, and its progressive record in precs)
     void jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,
-                         int channel_order, int32_t* d_status, JpegDecArgs* recs) const;
+                         int channel_order, int32_t* d_status, JpegDecArgs* recs, JpegProgArgs* precs) const;
+    // the clip's launches behind its upload, and its counters
+    void jpeg_clip_launch(const JpegClipJob& job, const JpegDecArgs* recs, const JpegProgArgs* precs, char* d_base, hipStream_t stream);
     // the layout of a decode's work buffers in the form the options (or `entropy` >= 0, `seg_bytes` > 0) give this stream
     JpegDecScratch jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy = -1, int seg_bytes = 0) const;
 

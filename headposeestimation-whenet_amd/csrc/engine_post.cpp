@@ -1672,10 +1672,15 @@ struct Engine::JpegClipJob {
     int64_t nbytes[MIXED_MAX_FRAMES];
     JpegClipPlan plan;
     int rule = JPEG_RULE_OWN;      // the clip's decode rule: one for all of its frames
+    // a clip that accepts progressive streams: every frame's scan plan (`baseline` for a SOF0 stream) and the layout; `plan` is its base
+    bool progressive = false;
+    std::vector<JpegProgPlan> prog;
+    JpegClipProgPlan pplan;
+    bool is_prog(int f) const { return progressive && !prog[size_t(f)].baseline; }
 };
 
 void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes,
-                               int rule, JpegClipJob& job) const {
+                               int rule, JpegClipJob& job, int progressive) const {
     const std::string w(what);
     job.rule = jpeg_rule_of(what, rule);
     WHENET_REQUIRE(nframes >= 1 && nframes <= MIXED_MAX_FRAMES, WHENET_EINVAL,
@@ -1683,24 +1688,58 @@ void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, con
     WHENET_REQUIRE(data != nullptr && size != nullptr, WHENET_EINVAL, w + ": NULL argument");
     job.frames = nframes;
     job.info.resize(size_t(nframes));
+    job.progressive = progressive != 0;
+    if (job.progressive) job.prog.resize(size_t(nframes));
     for (int f = 0; f < nframes; ++f) {
         const std::string who = w + ": frame " + std::to_string(f);
-        job.info[f] = parse_or_refuse(who.c_str(), data[f], size[f]);
+        job.info[f] = job.progressive ? parse_scans_or_refuse(who.c_str(), data[f], size[f], job.prog[size_t(f)])
+                                      : parse_or_refuse(who.c_str(), data[f], size[f]);
         job.g[f] = jpeg_dec_geom(job.info[f]);
         job.nbytes[f] = size[f] - job.info[f].data_offset;
     }
-    const char* bad = jpeg_clip_plan(job.g, job.nbytes, nframes, entropy >= 0 ? entropy : jpeg_entropy_, seg_bytes > 0 ? seg_bytes : jpeg_seg_bytes_,
-                                     job.plan);
+    const int ent = entropy >= 0 ? entropy : jpeg_entropy_, seg = seg_bytes > 0 ? seg_bytes : jpeg_seg_bytes_;
+    const char* bad = nullptr;
+    if (job.progressive) {
+        const JpegProgPlan* plans[MIXED_MAX_FRAMES];
+        for (int f = 0; f < nframes; ++f) plans[f] = &job.prog[size_t(f)];
+        bad = jpeg_clip_plan_progressive(job.g, job.nbytes, plans, nframes, ent, seg, job.pplan);
+        job.plan = job.pplan.base;
+    } else {
+        bad = jpeg_clip_plan(job.g, job.nbytes, nframes, ent, seg, job.plan);
+    }
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, w + ": " + (bad ? bad : ""));
 }
 
 void Engine::jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,
-                             int channel_order, int32_t* d_status, JpegDecArgs* recs) const {
+                             int channel_order, int32_t* d_status, JpegDecArgs* recs, JpegProgArgs* precs) const {
     const JpegClipPlan& p = job.plan;
     char* const s = static_cast<char*>(d_base);
     std::memset(stage + p.records.off, 0, p.records.len);
     for (int f = 0; f < job.frames; ++f) {
         const JpegClipFrame& q = p.f[f];
+        precs[f] = JpegProgArgs{};
+        if (job.is_prog(f)) {
+            // the frame's record as jpeg_prog_tail_args makes it, its progressive record behind it, its scan plan's share of the upload
+            const JpegClipProgFrame& r = job.pplan.pf[f];
+            const JpegProgPlan& plan = job.prog[size_t(f)];
+            JpegProgLayout lay(job.g[f], plan);      // (the offsets of this frame's regions in the clip's allocation)
+            lay.scans = r.scans.off, lay.huff = r.huff.off, lay.qz = r.qz.off, lay.items = r.items.off, lay.data = q.data.off;
+            lay.meta = q.meta.off, lay.raw = r.raw.off, lay.coef = q.coef.off;
+            for (int c = 0; c < 3; ++c) lay.plane[c] = q.plane[c].off;
+            const JpegDecArgs a = jpeg_prog_tail_args(job.g[f], d_base, lay, dst[f], channel_order, d_status + 2 * f, job.rule, int(plan.data_bytes));
+            JpegProgArgs x{};
+            x.g = job.g[f];
+            x.scans = reinterpret_cast<const JpegProgScan*>(s + r.scans.off), x.huff = reinterpret_cast<const JpegDecHuff*>(s + r.huff.off);
+            x.qz = reinterpret_cast<const int16_t*>(s + r.qz.off), x.items = reinterpret_cast<const JpegProgItem*>(s + r.items.off);
+            x.data = reinterpret_cast<const uint8_t*>(s + q.data.off), x.nbytes = int(plan.data_bytes);
+            x.raw = reinterpret_cast<int16_t*>(s + r.raw.off), x.coef = a.coef, x.meta = a.meta, x.first_bad = plan.first_bad;
+            recs[f] = a, precs[f] = x;
+            uint8_t* const rec = stage + p.records.off + size_t(f) * JPEG_CLIP_RECORD_BYTES;
+            std::memcpy(rec, &a, sizeof(a));
+            std::memcpy(rec + JPEG_CLIP_PROG_RECORD_OFFSET, &x, sizeof(x));
+            jpeg_clip_stage_progressive(plan, q, r, data[f] + plan.data_base, stage);
+            continue;
+        }
         JpegDecArgs a{};
         a.g = job.g[f];
         a.tables = reinterpret_cast<const JpegDecTables*>(s + q.tables.off);
@@ -1729,12 +1768,31 @@ void Engine::add_jpeg_clip_counters(int64_t out[4]) const {
     for (int i = 0; i < 4; ++i) out[i] += jpeg_clip_counts_[i];
 }
 
-int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule) {
+void Engine::jpeg_clip_launch(const JpegClipJob& job, const JpegDecArgs* recs, const JpegProgArgs* precs, char* d_base, hipStream_t stream) {
+    const JpegClipPlan& plan = job.plan;
+    const int nframes = job.frames;
+    if (job.progressive) {
+        const JpegProgPlan* plans[MIXED_MAX_FRAMES];
+        for (int f = 0; f < nframes; ++f) plans[f] = job.is_prog(f) ? &job.prog[size_t(f)] : nullptr;
+        launch_jpeg_decode_clip_progressive(recs, precs, plans, d_base + plan.records.off, nframes, d_base + plan.zero.off, plan.zero.len, stream,
+                                            &jpeg_clip_counts_[2], &jpeg_prog_counts_[1]);
+    } else {
+        launch_jpeg_decode_clip(recs, d_base + plan.records.off, nframes, d_base + plan.zero.off, plan.zero.len, stream, &jpeg_clip_counts_[2]);
+    }
+    ++jpeg_clip_counts_[0], jpeg_clip_counts_[1] += nframes, ++jpeg_clip_counts_[3];
+    for (int f = 0; f < nframes; ++f) {
+        if (job.is_prog(f)) ++jpeg_prog_counts_[0], jpeg_prog_counts_[2] += int64_t(job.prog[size_t(f)].dev.size());
+        else ++jpeg_dec_launched_[plan.f[f].form];
+    }
+}
+
+int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule,
+                            int progressive) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "clip_begin_jpeg: NULL argument");
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "clip_begin_jpeg: unknown channel order");
     JpegClipJob job;
-    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, rule, job);      // (before a slot is taken)
+    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, rule, job, progressive);      // (before a slot is taken)
     bool one_size = true;
     for (int f = 1; f < nframes; ++f) one_size = one_size && job.info[f].h == job.info[0].h && job.info[f].w == job.info[0].w;
     WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
@@ -1755,13 +1813,11 @@ int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int
     for (int f = 0; f < nframes; ++f)
         dst[f].plane[0] = slot.frame.d.as<uint8_t>() + off[f], dst[f].pitch[0] = 3 * job.info[f].w, dst[f].format = WHENET_SURF_PACKED, dst[f].on_device = 1;
     JpegDecArgs recs[MIXED_MAX_FRAMES];
+    JpegProgArgs precs[MIXED_MAX_FRAMES];
     uint8_t* const stage = slot.frame.h.as<uint8_t>();
-    jpeg_clip_stage(job, data, stage, slot.jpg_dec.as<void>(), dst, channel_order, static_cast<int32_t*>(d_status), recs);
+    jpeg_clip_stage(job, data, stage, slot.jpg_dec.as<void>(), dst, channel_order, static_cast<int32_t*>(d_status), recs, precs);
     WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, plan.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
-    launch_jpeg_decode_clip(recs, slot.jpg_dec.as<char>() + plan.records.off, nframes, slot.jpg_dec.as<char>() + plan.zero.off, plan.zero.len,
-                            copy_stream(), &jpeg_clip_counts_[2]);
-    ++jpeg_clip_counts_[0], jpeg_clip_counts_[1] += nframes, ++jpeg_clip_counts_[3];
-    for (int f = 0; f < nframes; ++f) ++jpeg_dec_launched_[plan.f[f].form];
+    jpeg_clip_launch(job, recs, precs, slot.jpg_dec.as<char>(), copy_stream());
     WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
     slot.fh = job.info[0].h, slot.fw = job.info[0].w, slot.swap_rb = channel_order == WHENET_BGR;
     if (!one_size) {
@@ -1776,11 +1832,11 @@ int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int
 }
 
 void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
-                                 int32_t* status, int entropy, int seg_bytes, int rule) {
+                                 int32_t* status, int entropy, int seg_bytes, int rule, int progressive) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr && dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_clip: NULL argument");
     JpegClipJob job;
-    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, rule, job);
+    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, rule, job, progressive);
     // every plane of every destination on the device at the caller's pitch and at the caller's address modulo 16, between two guard
     // zones and over a sentinel, so that a store outside the rows' bytes -- into a neighbouring frame as well -- is seen
     struct Plane {
@@ -1822,11 +1878,10 @@ void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size
     std::vector<uint8_t> stage(plan.upload_bytes + 256);
     uint8_t* const st = stage.data() + ((256 - (reinterpret_cast<uintptr_t>(stage.data()) & 255)) & 255);
     JpegDecArgs recs[MIXED_MAX_FRAMES];
-    jpeg_clip_stage(job, data, st, d_work, d_dst, channel_order, d_status, recs);
+    JpegProgArgs precs[MIXED_MAX_FRAMES];
+    jpeg_clip_stage(job, data, st, d_work, d_dst, channel_order, d_status, recs, precs);
     WHENET_HIP_CHECK(hipMemcpyAsync(d_work, st, plan.upload_bytes, hipMemcpyHostToDevice, stream_));
-    launch_jpeg_decode_clip(recs, d_work + plan.records.off, nframes, d_work + plan.zero.off, plan.zero.len, stream_, &jpeg_clip_counts_[2]);
-    ++jpeg_clip_counts_[0], jpeg_clip_counts_[1] += nframes, ++jpeg_clip_counts_[3];
-    for (int f = 0; f < nframes; ++f) ++jpeg_dec_launched_[plan.f[f].form];
+    jpeg_clip_launch(job, recs, precs, d_work, stream_);
     const size_t none[1] = {0};
     d_out.to_host(stream_, none, 0, nullptr, "op_jpeg_decode_clip");      // waits, checks the guard zones
     std::vector<uint8_t> back(total), is_row(total, 0);

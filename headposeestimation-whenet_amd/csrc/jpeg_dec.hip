@@ -533,8 +533,15 @@ void launch_jpeg_decode_tail(const JpegDecArgs& a, hipStream_t stream) {
 
 void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, void* d_zero, size_t zero_bytes, hipStream_t stream,
                              int64_t* enqueues) {
+    launch_jpeg_decode_clip_entropy(h_recs, d_recs, frames, d_zero, zero_bytes, stream, enqueues, nullptr);
+    launch_jpeg_decode_clip_tail(h_recs, d_recs, frames, stream, enqueues);
+}
+
+void launch_jpeg_decode_clip_entropy(const JpegDecArgs* h_recs, const void* d_recs, int frames, void* d_zero, size_t zero_bytes, hipStream_t stream,
+                                     int64_t* enqueues, const uint8_t* progressive) {
     WHENET_REQUIRE(h_recs != nullptr && d_recs != nullptr && d_zero != nullptr && frames >= 1 && frames <= MIXED_MAX_FRAMES, WHENET_EINVAL,
                    "jpeg_decode_clip: NULL argument, or a frame count outside 1..16");
+    const auto prog = [&](int f) { return progressive != nullptr && progressive[f] != 0; };
     for (int f = 0; f < frames; ++f) {
         const JpegDecArgs& a = h_recs[f];
         check_jpeg_dec_args(a);
@@ -543,7 +550,9 @@ void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int 
         const size_t coef_bytes = size_t(a.g.mcu_cols) * size_t(a.g.mcu_rows) * size_t(a.g.bpm) * 128;
         const auto zeroed = [&](const void* p, size_t n) { return static_cast<const char*>(p) >= z0 && static_cast<const char*>(p) + n <= z1; };
         WHENET_REQUIRE(a.rule == h_recs[0].rule, WHENET_EINVAL, "jpeg_decode_clip: the frames of a clip are decoded by one rule");
-        WHENET_REQUIRE(zeroed(a.start, size_t(a.g.intervals) * 4) && zeroed(a.meta, 8) && zeroed(a.seg_stats, 64) && zeroed(a.coef, coef_bytes),
+        // (a progressive frame: meta here, its raw coefficients in launch_jpeg_decode_clip_progressive; form 0 keeps it out of the segmented stages)
+        WHENET_REQUIRE(prog(f) ? zeroed(a.meta, 8) && a.form == 0
+                               : zeroed(a.start, size_t(a.g.intervals) * 4) && zeroed(a.meta, 8) && zeroed(a.seg_stats, 64) && zeroed(a.coef, coef_bytes),
                        WHENET_EINVAL, "jpeg_decode_clip: frame " + std::to_string(f) + ": its zeroed regions lie outside the clip's");
     }
     int64_t n = 0;
@@ -555,11 +564,26 @@ void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int 
     };
     WHENET_HIP_CHECK(hipMemsetAsync(d_zero, 0, zero_bytes, stream));
     ++n;
-    jpeg_clip_grid(h_recs, frames, [](const JpegDecArgs&) { return 1; }, grid);
-    launch(whenet_jpeg_dec_clip_scan_kernel, THREADS);
-    if (jpeg_clip_grid(h_recs, frames, [](const JpegDecArgs& a) { return a.form == 0 ? (a.g.intervals + ENT_LANES - 1) / ENT_LANES : 0; }, grid))
+    // (the counts see the records only: a progressive frame is told by its address in h_recs)
+    const auto base = [&](const JpegDecArgs& a) { return !prog(int(&a - h_recs)); };
+    if (jpeg_clip_grid(h_recs, frames, [&](const JpegDecArgs& a) { return base(a) ? 1 : 0; }, grid)) launch(whenet_jpeg_dec_clip_scan_kernel, THREADS);
+    if (jpeg_clip_grid(h_recs, frames,
+                       [&](const JpegDecArgs& a) { return base(a) && a.form == 0 ? (a.g.intervals + ENT_LANES - 1) / ENT_LANES : 0; }, grid))
         launch(whenet_jpeg_dec_clip_entropy_kernel, ENT_THREADS);
-    launch_jpeg_decode_segmented_clip(h_recs, d_recs, frames, stream, &n);
+    if (enqueues != nullptr) *enqueues += n;
+    launch_jpeg_decode_segmented_clip(h_recs, d_recs, frames, stream, enqueues);
+}
+
+void launch_jpeg_decode_clip_tail(const JpegDecArgs* h_recs, const void* d_recs, int frames, hipStream_t stream, int64_t* enqueues) {
+    WHENET_REQUIRE(h_recs != nullptr && d_recs != nullptr && frames >= 1 && frames <= MIXED_MAX_FRAMES, WHENET_EINVAL,
+                   "jpeg_decode_clip: NULL argument, or a frame count outside 1..16");
+    int64_t n = 0;
+    JpegClipGrid grid;
+    const auto launch = [&](auto kernel, int threads) {
+        hipLaunchKernelGGL(kernel, dim3(unsigned(grid.total)), dim3(unsigned(threads)), 0, stream, d_recs, grid);
+        WHENET_HIP_CHECK(hipGetLastError());
+        ++n;
+    };
     jpeg_clip_grid(h_recs, frames,
               [](const JpegDecArgs& a) { return ((long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm + IDCT_BLOCKS - 1) / IDCT_BLOCKS; }, grid);
     // (one rule per clip: its idct and frame kernels stand for rule 0's, the number of launches does not grow)

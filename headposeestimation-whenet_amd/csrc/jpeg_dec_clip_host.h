@@ -13,8 +13,10 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "jpeg_dec_seg_host.h"
+#include "jpeg_prog_host.h"
 
 namespace whenet {
 
@@ -109,6 +111,170 @@ inline void jpeg_clip_plan_words(const JpegClipPlan& p, int64_t* out) {
     int64_t* t = out + size_t(p.frames) * JPEG_CLIP_PLAN_FRAME_WORDS;
     t[0] = int64_t(p.records.off), t[1] = int64_t(p.records.len), t[2] = int64_t(p.upload_bytes), t[3] = int64_t(p.zero.off);
     t[4] = int64_t(p.zero.len), t[5] = int64_t(p.bytes), t[6] = p.forms[0], t[7] = p.forms[1];
+}
+
+// ---- clips that may hold PROGRESSIVE streams (jpeg_prog_host.h): a second plan, the first one stays as it is ----
+// A frame is baseline (its JpegProgPlan is nullptr or says `baseline`: laid out as above, in the form the rule gives it alone) or
+// progressive (form JPEG_CLIP_FORM_PROGRESSIVE).  The same three blocks:
+//   upload block   records | per frame: tables | data, or, progressive: scans | huff | qz | items | data (what jpeg_prog_stage
+//                  writes for the stream alone; list_off / level_off stay indices into the frame's OWN item list)   -- ONE H2D
+//   zeroed bytes   per frame: start | meta | seg_stats, or meta; then per frame: coef, or, progressive: the raw coefficients -- ONE memset
+//   work           per progressive frame: its finished coef; per frame: the planes; per frame of form 1: the segmented regions
+// A clip without a progressive frame gets, region for region, the plan above.  A frame's progressive record (JpegProgArgs) lies in
+// the frame's own argument record, JPEG_CLIP_PROG_RECORD_OFFSET bytes behind its start (checked in jpeg_prog.hip).
+constexpr int JPEG_CLIP_FORM_PROGRESSIVE = 2;
+constexpr int JPEG_CLIP_PROG_RECORD_OFFSET = 320;
+constexpr int JPEG_CLIP_PROG_PLAN_FRAME_WORDS = 48;      // whenet_jpeg_clip_plan_progressive: the 32 words above + 16 ...
+constexpr int JPEG_CLIP_PROG_PLAN_TOTAL_WORDS = 16;      // ... and the 8 above + 8 behind the last frame
+
+struct JpegClipProgFrame {
+    JpegClipRegion scans, huff, qz, items, raw;      // empty for a baseline frame
+    int nscans, levels, list;                        // list: the entries of the item list (a multiple of JPEG_PROG_LANES)
+};
+struct JpegClipProgPlan {
+    // a progressive frame there: form 2, seg_bytes = seg_cap = 0; data (every scan's entropy bytes), meta, coef and plane[] are its
+    // regions, tables / start / seg_stats / the segmented regions are empty; forms[] count the baseline frames only
+    JpegClipPlan base;
+    JpegClipProgFrame pf[JPEG_CLIP_MAX_FRAMES];
+    int progressive;       // the progressive frames
+    int scan_launches;     // the largest level count among them: launch L of the scan kernel covers level L of every frame that has one
+};
+
+inline bool jpeg_clip_is_progressive(const JpegProgPlan* plan) { return plan != nullptr && !plan->baseline; }
+
+// nbytes[f] is read for baseline frames only; prog may be nullptr (no progressive frame).  nullptr, or what is wrong.
+inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_t* nbytes, const JpegProgPlan* const* prog, int frames, int entropy,
+                                              int seg_bytes, JpegClipProgPlan& pp) {
+    if (g == nullptr || nbytes == nullptr) return "NULL argument";
+    if (frames < 1 || frames > JPEG_CLIP_MAX_FRAMES) return "a clip holds 1..16 frames";
+    if (entropy < 0 || entropy > 2) return "entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto)";
+    if (!jpeg_seg_bytes_ok(seg_bytes)) return "seg_bytes must be a power of two in 4..4096";
+    const auto is_prog = [&](int f) { return prog != nullptr && jpeg_clip_is_progressive(prog[f]); };
+    for (int f = 0; f < frames; ++f) {
+        if (g[f].intervals < 1 || g[f].mcu_cols < 1 || g[f].mcu_rows < 1 || g[f].bpm < 1 || g[f].comps < 1 || g[f].comps > 3) return "bad geometry";
+        if (is_prog(f)) {
+            const JpegProgPlan& s = *prog[f];
+            if (s.dev.empty() || s.huff.size() != 3 * s.dev.size() || s.items.empty() || s.items.size() % JPEG_PROG_LANES != 0 || s.levels < 1 ||
+                s.level_off.size() != size_t(s.levels) || s.level_cnt.size() != size_t(s.levels) || s.data_bytes < 0 || s.data_bytes > JPEG_DEC_MAX_BYTES)
+                return "not the plan of a progressive stream";
+        } else if (nbytes[f] < 0 || nbytes[f] > JPEG_DEC_MAX_BYTES) {
+            return "nbytes must be 0..2^31 - 1";
+        }
+    }
+    const auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    pp = JpegClipProgPlan{};
+    JpegClipPlan& p = pp.base;
+    p.frames = frames;
+    size_t at = 0;
+    const auto take = [&](JpegClipRegion& r, size_t len) { r.off = at, r.len = len, at = up(at + len); };
+    const auto none = [&](JpegClipRegion& r) { r = {at, 0}; };
+    take(p.records, size_t(frames) * JPEG_CLIP_RECORD_BYTES);
+    for (int f = 0; f < frames; ++f) {
+        JpegClipFrame& q = p.f[f];
+        JpegClipProgFrame& r = pp.pf[f];
+        if (is_prog(f)) {
+            const JpegProgPlan& s = *prog[f];
+            q.form = JPEG_CLIP_FORM_PROGRESSIVE, q.seg_bytes = 0, q.seg_cap = 0;
+            r.nscans = int(s.dev.size()), r.levels = s.levels, r.list = int(s.items.size());
+            ++pp.progressive;
+            if (s.levels > pp.scan_launches) pp.scan_launches = s.levels;
+            none(q.tables);
+            take(r.scans, s.dev.size() * sizeof(JpegProgScan));
+            take(r.huff, s.huff.size() * sizeof(JpegDecHuff));
+            take(r.qz, sizeof(s.qz));
+            take(r.items, s.items.size() * sizeof(JpegProgItem));
+            take(q.data, size_t(s.data_bytes));
+            continue;
+        }
+        q.form = jpeg_dec_form(entropy, nbytes[f], g[f].intervals);
+        q.seg_bytes = q.form == 1 ? seg_bytes : 0;
+        q.seg_cap = q.form == 1 ? jpeg_seg_bound(nbytes[f], g[f].intervals, seg_bytes) : 0;
+        if (q.seg_cap >= 0x7FFFFFFF) return "more segments than an int32 counts";
+        ++p.forms[q.form];
+        take(q.tables, sizeof(JpegDecTables));
+        take(q.data, size_t(nbytes[f]));
+        none(r.scans), none(r.huff), none(r.qz), none(r.items);
+    }
+    p.upload_bytes = at;
+    p.zero.off = at;
+    for (int f = 0; f < frames; ++f) {
+        JpegClipFrame& q = p.f[f];
+        if (q.form == JPEG_CLIP_FORM_PROGRESSIVE) {
+            none(q.start);
+            q.meta = {at, 64}, q.seg_stats = {at + 64, 0}, at = up(at + 64);
+            continue;
+        }
+        take(q.start, size_t(g[f].intervals) * sizeof(int32_t));
+        q.meta = {at, 64}, q.seg_stats = {at + 64, 8 * sizeof(int64_t)}, at = up(at + 128);
+    }
+    for (int f = 0; f < frames; ++f) {
+        const size_t coef_bytes = size_t(g[f].mcu_cols) * size_t(g[f].mcu_rows) * size_t(g[f].bpm) * 64 * sizeof(int16_t);
+        if (p.f[f].form == JPEG_CLIP_FORM_PROGRESSIVE) {
+            take(pp.pf[f].raw, coef_bytes);
+        } else {
+            take(p.f[f].coef, coef_bytes);
+            none(pp.pf[f].raw);
+        }
+    }
+    p.zero.len = at - p.zero.off;
+    for (int f = 0; f < frames; ++f)
+        if (p.f[f].form == JPEG_CLIP_FORM_PROGRESSIVE)
+            take(p.f[f].coef, size_t(g[f].mcu_cols) * size_t(g[f].mcu_rows) * size_t(g[f].bpm) * 64 * sizeof(int16_t));
+    for (int f = 0; f < frames; ++f)
+        for (int c = 0; c < 3; ++c) {
+            if (c < g[f].comps) take(p.f[f].plane[c], size_t(g[f].plane_pitch[c]) * size_t(g[f].plane_rows[c]));
+            else none(p.f[f].plane[c]);
+        }
+    for (int f = 0; f < frames; ++f) {
+        JpegClipFrame& q = p.f[f];
+        if (q.form == 1) {
+            take(q.first_seg, (size_t(g[f].intervals) + 1) * sizeof(int32_t));
+            take(q.seg_exit, size_t(q.seg_cap) * sizeof(uint64_t));
+            take(q.seg_count, size_t(q.seg_cap) * sizeof(JpegSegCount));
+            take(q.seg_blk, size_t(q.seg_cap) * 4 * sizeof(int32_t));
+        } else {
+            none(q.first_seg), none(q.seg_exit), none(q.seg_count), none(q.seg_blk);
+        }
+    }
+    p.bytes = at;
+    return nullptr;
+}
+
+// a progressive frame's share of the upload block into `stage` (the block's first byte; data: the stream's bytes from
+// plan.data_base on): the content jpeg_prog_stage writes, the padding between the regions zeroed
+inline void jpeg_clip_stage_progressive(const JpegProgPlan& plan, const JpegClipFrame& q, const JpegClipProgFrame& r, const uint8_t* data,
+                                        uint8_t* stage) {
+    std::memset(stage + r.scans.off, 0, q.data.off - r.scans.off);
+    std::memcpy(stage + r.scans.off, plan.dev.data(), r.scans.len);
+    std::memcpy(stage + r.huff.off, plan.huff.data(), r.huff.len);
+    std::memcpy(stage + r.qz.off, plan.qz, r.qz.len);
+    std::memcpy(stage + r.items.off, plan.items.data(), r.items.len);
+    if (q.data.len > 0) std::memcpy(stage + q.data.off, data, q.data.len);
+}
+
+// the plan as whenet_jpeg_clip_plan_progressive hands it out: frames * 48 + 16 words.  A frame's words 0..31 and the totals' words
+// 0..7 are jpeg_clip_plan_words' (form 2: a progressive frame); a frame's words 32..41: (offset, length) of scans, huff, qz, items,
+// raw; 42: its scans, 43: its levels, 44: the entries of its item list; 45..47: 0.  Totals 8: the progressive frames, 9: the
+// scan-kernel launches, 10: the stride of the argument records, 11: where a frame's progressive record lies in its own; 12..15: 0.
+inline void jpeg_clip_plan_progressive_words(const JpegClipProgPlan& pp, int64_t* out) {
+    const JpegClipPlan& p = pp.base;
+    for (int f = 0; f < p.frames; ++f) {
+        const JpegClipFrame& q = p.f[f];
+        const JpegClipProgFrame& x = pp.pf[f];
+        int64_t* o = out + size_t(f) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS;
+        o[0] = q.form, o[1] = q.seg_bytes, o[2] = q.seg_cap, o[3] = 0;
+        const JpegClipRegion* r[18] = {&q.tables,    &q.data,     &q.start,     &q.meta,    &q.seg_stats, &q.coef, &q.plane[0], &q.plane[1], &q.plane[2],
+                                       &q.first_seg, &q.seg_exit, &q.seg_count, &q.seg_blk, &x.scans,     &x.huff, &x.qz,       &x.items,    &x.raw};
+        for (int k = 0; k < 13; ++k) o[4 + 2 * k] = int64_t(r[k]->off), o[5 + 2 * k] = int64_t(r[k]->len);
+        o[30] = o[31] = 0;
+        for (int k = 13; k < 18; ++k) o[6 + 2 * k] = int64_t(r[k]->off), o[7 + 2 * k] = int64_t(r[k]->len);
+        o[42] = x.nscans, o[43] = x.levels, o[44] = x.list, o[45] = o[46] = o[47] = 0;
+    }
+    int64_t* t = out + size_t(p.frames) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS;
+    t[0] = int64_t(p.records.off), t[1] = int64_t(p.records.len), t[2] = int64_t(p.upload_bytes), t[3] = int64_t(p.zero.off);
+    t[4] = int64_t(p.zero.len), t[5] = int64_t(p.bytes), t[6] = p.forms[0], t[7] = p.forms[1];
+    t[8] = pp.progressive, t[9] = pp.scan_launches, t[10] = JPEG_CLIP_RECORD_BYTES, t[11] = JPEG_CLIP_PROG_RECORD_OFFSET;
+    t[12] = t[13] = t[14] = t[15] = 0;
 }
 
 }  // namespace whenet

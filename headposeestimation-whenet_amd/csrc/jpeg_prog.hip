@@ -16,6 +16,10 @@
 //   whenet_jpeg_prog_finish_kernel  8 lanes per block: lane l loads the record's zigzag positions 8 l .. 8 l + 7 as 16 bytes,
 //                                   multiplies by the quantiser, clamps, scatters to natural order in LDS, and stores the natural
 //                                   positions 8 l .. 8 l + 7 as 16 bytes.
+//   whenet_jpeg_prog_clip_scan_kernel, whenet_jpeg_prog_clip_finish_kernel
+//                                   the same bodies for a CLIP of up to 16 streams (jpeg_dec_clip_host.h: jpeg_clip_plan_progressive):
+//                                   launch L of the scan kernel covers level L of every progressive frame that has one, the finish
+//                                   kernel all progressive frames; a workgroup finds its frame in the per-frame workgroup counts.
 #include <string>
 
 #include "kernels.h"
@@ -35,13 +39,15 @@ __constant__ uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 1
 
 static_assert(sizeof(JpegDecHuff) % 4 == 0 && sizeof(JpegProgScan) % 4 == 0, "copied to LDS by dwords");
 
-// group: the workgroup's index in the item list (16 items each)
-__global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_prog_scan_kernel(JpegProgArgs a, int first_group) {
+// ---- the bodies: what a workgroup does for ONE stream, given that stream's record.  The single-stream kernels call them with their
+// own argument and blockIdx.x, the clip kernels with the record of the frame the workgroup belongs to (as jpeg_dec.hip's do).
+// group: the workgroup's index in the stream's item list (16 items each)
+__device__ __forceinline__ void scan_body(const JpegProgArgs& a, long long group) {
     __shared__ JpegDecHuff s_h[3];
     __shared__ JpegProgScan s_sc;
     __shared__ int16_t s_band[JPEG_PROG_LANES][64 + 2];      // an AC refinement's band in hand (132-byte rows)
     const int tid = int(threadIdx.x);
-    const long long base = ((long long)(first_group) + blockIdx.x) * JPEG_PROG_LANES;
+    const long long base = group * JPEG_PROG_LANES;
     const int s = a.items[base].scan;      // (a scan's share begins with a real item: uniform over the workgroup)
     if (s < 0) return;
     {
@@ -62,13 +68,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_prog_scan_kernel(Jpe
         atomicMax(&a.meta[0], JPEG_DEC_NO_BAD - (s_sc.first_item + it.interval));
 }
 
-__global__ __launch_bounds__(FIN_THREADS) void whenet_jpeg_prog_finish_kernel(JpegProgArgs a) {
+// bx: the workgroup's index among the stream's (32 blocks each)
+__device__ __forceinline__ void finish_body(const JpegProgArgs& a, int bx) {
     __shared__ __attribute__((aligned(16))) int16_t s_rec[FIN_BLOCKS][64 + 8];
     __shared__ int16_t s_q[3][64];
     const int tid = int(threadIdx.x), lb = tid >> 3, l = tid & 7;
     if (tid < 192) s_q[tid >> 6][tid & 63] = a.qz[tid];
     __syncthreads();
-    const long long blk = (long long)(blockIdx.x) * FIN_BLOCKS + lb;
+    const long long blk = (long long)(bx) * FIN_BLOCKS + lb;
     const long long total = (long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm;
     const bool live = blk < total;
     if (live) {
@@ -83,12 +90,61 @@ __global__ __launch_bounds__(FIN_THREADS) void whenet_jpeg_prog_finish_kernel(Jp
         }
     }
     __syncthreads();
-    if (blockIdx.x == 0 && tid == 0) {      // (the scan kernels have ended: kernel boundaries lie between)
+    if (bx == 0 && tid == 0) {      // (the scan kernels have ended: kernel boundaries lie between)
         const int m = a.meta[0];
         const int bad = m > 0 ? JPEG_DEC_NO_BAD - m : JPEG_DEC_NO_BAD;
         a.meta[1] = bad < a.first_bad ? bad : a.first_bad;
     }
     if (live) *reinterpret_cast<uint4*>(a.coef + size_t(blk) * 64 + 8 * l) = *reinterpret_cast<const uint4*>(&s_rec[lb][8 * l]);
+}
+
+// ---- the single-stream kernels: the record by value, the grid that stream's ----
+__global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_prog_scan_kernel(JpegProgArgs a, int first_group) {
+    scan_body(a, (long long)(first_group) + blockIdx.x);
+}
+__global__ __launch_bounds__(FIN_THREADS) void whenet_jpeg_prog_finish_kernel(JpegProgArgs a) { finish_body(a, int(blockIdx.x)); }
+
+// ---- the clip kernels: the frames' workgroups back to back in one grid (kernels.h, JpegClipGrid).  A workgroup finds its frame, reads
+// that frame's progressive record where it lies in the uploaded records (the same address for every lane, read-only for the kernel) and
+// runs the body with its index inside the frame's share; a workgroup never straddles two frames, and one behind the grid's total
+// exits before it touches memory.  Frames share no record and no item list: inside a frame the lanes store single int16s of their own
+// band, as in the single-stream kernel.
+// Resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), clip form / single-stream form, no scratch in
+// either: scan 90 / 103 VGPRs, 106 / 106 SGPRs, 6452 / 6452 bytes of LDS; finish 23 / 23 VGPRs, 46 / 34 SGPRs, 4992 / 4992 bytes of LDS.
+__global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_prog_clip_scan_kernel(const void* __restrict__ recs, JpegClipGrid grid,
+                                                                                  JpegProgClipLevel level) {
+    const int b = int(blockIdx.x);
+    if (b >= grid.total) return;
+    const int f = jpeg_clip_frame_of(grid, b);
+    scan_body(jpeg_clip_prog_record(recs, f), (long long)(level.first_group[f]) + (b - grid.first[f]));
+}
+__global__ __launch_bounds__(FIN_THREADS) void whenet_jpeg_prog_clip_finish_kernel(const void* __restrict__ recs, JpegClipGrid grid) {
+    const int b = int(blockIdx.x);
+    if (b >= grid.total) return;
+    const int f = jpeg_clip_frame_of(grid, b);
+    finish_body(jpeg_clip_prog_record(recs, f), b - grid.first[f]);
+}
+
+static_assert(sizeof(JpegDecArgs) <= JPEG_CLIP_PROG_RECORD_OFFSET && JPEG_CLIP_PROG_RECORD_OFFSET % 16 == 0 &&
+                  JPEG_CLIP_PROG_RECORD_OFFSET + sizeof(JpegProgArgs) <= JPEG_CLIP_RECORD_BYTES,
+              "a frame's two records fit the stride");
+
+// what a lane may index: every item inside its scan and the data, every scan's units inside the frame's records
+void check_jpeg_prog_plan(const JpegDecGeom& g, const JpegProgPlan& plan) {
+    WHENET_REQUIRE(!plan.baseline && !plan.dev.empty() && plan.huff.size() == 3 * plan.dev.size() && plan.items.size() % JPEG_PROG_LANES == 0 &&
+                       plan.data_bytes >= 0 && plan.data_bytes <= JPEG_DEC_MAX_BYTES,
+                   WHENET_EINVAL, "jpeg_decode_progressive: not the plan of a progressive stream");
+    for (const JpegProgScan& sc : plan.dev) {
+        const long long frame_units = sc.ns > 1 || g.comps == 1 ? (long long)(g.mcu_cols) * g.mcu_rows : -1;
+        WHENET_REQUIRE(sc.units >= 1 && sc.ri >= 1 && sc.intervals == (sc.units + sc.ri - 1) / sc.ri && sc.ss >= 0 && sc.ss <= sc.se && sc.se <= 63 &&
+                           sc.al >= 0 && sc.al <= 13 && sc.ns >= 1 && sc.ns <= g.comps && sc.bw >= 1 && sc.units == sc.bw * sc.bh &&
+                           (frame_units < 0 ? (sc.comp[0] >= 0 && sc.comp[0] < 3 && sc.bw <= g.mcu_cols * (sc.comp[0] == 0 ? g.hs : 1) &&
+                                               sc.bh <= g.mcu_rows * (sc.comp[0] == 0 ? g.vs : 1))
+                                            : sc.units == frame_units) &&
+                           sc.list_off >= 0 && sc.items >= 1 && sc.items <= sc.intervals && sc.list_cnt >= sc.items && sc.list_off % JPEG_PROG_LANES == 0 && sc.list_cnt % JPEG_PROG_LANES == 0 &&
+                           size_t(sc.list_off) + size_t(sc.list_cnt) <= plan.items.size(),
+                       WHENET_EINVAL, "jpeg_decode_progressive: a scan record outside the frame");
+    }
 }
 
 }  // namespace
@@ -127,24 +183,11 @@ void launch_jpeg_decode_progressive(const JpegDecArgs& a, const JpegProgPlan& pl
                                     hipStream_t stream, int64_t* scan_launches) {
     const JpegDecGeom& g = a.g;
     char* const s = static_cast<char*>(d_scratch);
-    WHENET_REQUIRE(d_scratch != nullptr && !plan.baseline && !plan.dev.empty() && plan.huff.size() == 3 * plan.dev.size() &&
-                       plan.items.size() % JPEG_PROG_LANES == 0 && plan.data_bytes >= 0 && plan.data_bytes <= JPEG_DEC_MAX_BYTES,
-                   WHENET_EINVAL, "jpeg_decode_progressive: not the plan of a progressive stream");
+    WHENET_REQUIRE(d_scratch != nullptr, WHENET_EINVAL, "jpeg_decode_progressive: not the plan of a progressive stream");
+    check_jpeg_prog_plan(g, plan);
     WHENET_REQUIRE(lay.coef_bytes == size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm) * 128 && a.coef == reinterpret_cast<int16_t*>(s + lay.coef) &&
                        a.meta == reinterpret_cast<int32_t*>(s + lay.meta),
                    WHENET_EINVAL, "jpeg_decode_progressive: the work buffers are not those of the stream's geometry");
-    // what a lane may index: every item inside its scan and the data, every scan's units inside the frame's records
-    for (const JpegProgScan& sc : plan.dev) {
-        const long long frame_units = sc.ns > 1 || g.comps == 1 ? (long long)(g.mcu_cols) * g.mcu_rows : -1;
-        WHENET_REQUIRE(sc.units >= 1 && sc.ri >= 1 && sc.intervals == (sc.units + sc.ri - 1) / sc.ri && sc.ss >= 0 && sc.ss <= sc.se && sc.se <= 63 &&
-                           sc.al >= 0 && sc.al <= 13 && sc.ns >= 1 && sc.ns <= g.comps && sc.bw >= 1 && sc.units == sc.bw * sc.bh &&
-                           (frame_units < 0 ? (sc.comp[0] >= 0 && sc.comp[0] < 3 && sc.bw <= g.mcu_cols * (sc.comp[0] == 0 ? g.hs : 1) &&
-                                               sc.bh <= g.mcu_rows * (sc.comp[0] == 0 ? g.vs : 1))
-                                            : sc.units == frame_units) &&
-                           sc.list_off >= 0 && sc.items >= 1 && sc.items <= sc.intervals && sc.list_cnt >= sc.items && sc.list_off % JPEG_PROG_LANES == 0 && sc.list_cnt % JPEG_PROG_LANES == 0 &&
-                           size_t(sc.list_off) + size_t(sc.list_cnt) <= plan.items.size(),
-                       WHENET_EINVAL, "jpeg_decode_progressive: a scan record outside the frame");
-    }
     JpegProgArgs p{};
     p.g = g;
     p.scans = reinterpret_cast<const JpegProgScan*>(s + lay.scans), p.huff = reinterpret_cast<const JpegDecHuff*>(s + lay.huff);
@@ -168,6 +211,71 @@ void launch_jpeg_decode_progressive(const JpegDecArgs& a, const JpegProgPlan& pl
     hipLaunchKernelGGL(whenet_jpeg_prog_finish_kernel, dim3(unsigned((nblocks + FIN_BLOCKS - 1) / FIN_BLOCKS)), dim3(FIN_THREADS), 0, stream, p);
     WHENET_HIP_CHECK(hipGetLastError());
     launch_jpeg_decode_tail(a, stream);
+}
+
+void launch_jpeg_decode_clip_progressive(const JpegDecArgs* h_recs, const JpegProgArgs* h_prog, const JpegProgPlan* const* plans, const void* d_recs,
+                                         int frames, void* d_zero, size_t zero_bytes, hipStream_t stream, int64_t* enqueues, int64_t* scan_launches) {
+    WHENET_REQUIRE(h_recs != nullptr && h_prog != nullptr && plans != nullptr && d_recs != nullptr && d_zero != nullptr && frames >= 1 &&
+                       frames <= MIXED_MAX_FRAMES,
+                   WHENET_EINVAL, "jpeg_decode_clip: NULL argument, or a frame count outside 1..16");
+    uint8_t prog[MIXED_MAX_FRAMES] = {};
+    int levels = 0;
+    for (int f = 0; f < frames; ++f) {
+        if (!jpeg_clip_is_progressive(plans[f])) continue;
+        const JpegProgPlan& plan = *plans[f];
+        const JpegProgArgs& p = h_prog[f];
+        const JpegDecGeom& g = h_recs[f].g;
+        prog[f] = 1;
+        check_jpeg_prog_plan(g, plan);
+        const std::string who = "jpeg_decode_clip: frame " + std::to_string(f);
+        WHENET_REQUIRE(plan.levels >= 1 && plan.level_off.size() == size_t(plan.levels) && plan.level_cnt.size() == size_t(plan.levels), WHENET_EINVAL,
+                       who + ": not the plan of a progressive stream");
+        size_t at = 0;      // the levels tile the item list, each a whole number of workgroups
+        for (int l = 0; l < plan.levels; ++l) {
+            WHENET_REQUIRE(plan.level_off[size_t(l)] >= 0 && size_t(plan.level_off[size_t(l)]) == at && plan.level_cnt[size_t(l)] >= 0 &&
+                               plan.level_cnt[size_t(l)] % JPEG_PROG_LANES == 0,
+                           WHENET_EINVAL, who + ": a level outside the item list");
+            at += size_t(plan.level_cnt[size_t(l)]);
+        }
+        WHENET_REQUIRE(at == plan.items.size(), WHENET_EINVAL, who + ": a level outside the item list");
+        // the record the kernels read: this geometry, the frame's own buffers, raw inside the zeroed bytes
+        const size_t coef_bytes = size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm) * 128;
+        const char *z0 = static_cast<const char*>(d_zero), *z1 = z0 + zero_bytes, *raw = reinterpret_cast<const char*>(p.raw);
+        WHENET_REQUIRE(std::memcmp(&p.g, &g, sizeof(g)) == 0 && p.scans != nullptr && p.huff != nullptr && p.qz != nullptr && p.items != nullptr &&
+                           p.data != nullptr && p.nbytes == int(plan.data_bytes) && p.raw != nullptr && raw >= z0 && raw + coef_bytes <= z1 &&
+                           reinterpret_cast<uintptr_t>(p.raw) % 16 == 0 && p.coef == h_recs[f].coef && reinterpret_cast<uintptr_t>(p.coef) % 16 == 0 &&
+                           p.meta == h_recs[f].meta && p.first_bad == plan.first_bad,
+                       WHENET_EINVAL, who + ": the progressive record is not that of the frame's plan and buffers");
+        levels = std::max(levels, plan.levels);
+    }
+    launch_jpeg_decode_clip_entropy(h_recs, d_recs, frames, d_zero, zero_bytes, stream, enqueues, prog);      // checks, the one memset, the baseline frames
+    int64_t n = 0;
+    JpegClipGrid grid;
+    for (int l = 0; l < levels; ++l) {
+        JpegProgClipLevel level{};
+        const auto count = [&](const JpegDecArgs& a) {
+            const int f = int(&a - h_recs);
+            return prog[f] && l < plans[f]->levels ? plans[f]->level_cnt[size_t(l)] / JPEG_PROG_LANES : 0;
+        };
+        for (int f = 0; f < frames; ++f)
+            if (count(h_recs[f]) > 0) level.first_group[f] = plans[f]->level_off[size_t(l)] / JPEG_PROG_LANES;
+        if (!jpeg_clip_grid(h_recs, frames, count, grid)) continue;
+        hipLaunchKernelGGL(whenet_jpeg_prog_clip_scan_kernel, dim3(unsigned(grid.total)), dim3(SCAN_THREADS), 0, stream, d_recs, grid, level);
+        WHENET_HIP_CHECK(hipGetLastError());
+        ++n;
+        if (scan_launches != nullptr) ++*scan_launches;
+    }
+    if (jpeg_clip_grid(h_recs, frames,
+                       [&](const JpegDecArgs& a) {
+                           return prog[&a - h_recs] ? ((long long)(a.g.mcu_cols) * a.g.mcu_rows * a.g.bpm + FIN_BLOCKS - 1) / FIN_BLOCKS : 0;
+                       },
+                       grid)) {
+        hipLaunchKernelGGL(whenet_jpeg_prog_clip_finish_kernel, dim3(unsigned(grid.total)), dim3(FIN_THREADS), 0, stream, d_recs, grid);
+        WHENET_HIP_CHECK(hipGetLastError());
+        ++n;
+    }
+    if (enqueues != nullptr) *enqueues += n;
+    launch_jpeg_decode_clip_tail(h_recs, d_recs, frames, stream, enqueues);
 }
 
 }  // namespace whenet

@@ -817,6 +817,32 @@ __device__ __forceinline__ const JpegDecArgs& jpeg_clip_record(const void* recs,
 void launch_jpeg_decode_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, void* d_zero, size_t zero_bytes, hipStream_t stream,
                              int64_t* enqueues);
 void launch_jpeg_decode_segmented_clip(const JpegDecArgs* h_recs, const void* d_recs, int frames, hipStream_t stream, int64_t* enqueues);
+// launch_jpeg_decode_clip in its two halves.  entropy: the checks, the one memset, then marker scan | entropy | segmented stages for
+// the frames whose `progressive` byte is 0 (nullptr: all) -- a stage no frame needs is not launched.  tail: inverse DCT and colour
+// for all frames (a progressive frame's record presents coef and meta[1] as a baseline one's).
+void launch_jpeg_decode_clip_entropy(const JpegDecArgs* h_recs, const void* d_recs, int frames, void* d_zero, size_t zero_bytes, hipStream_t stream,
+                                     int64_t* enqueues, const uint8_t* progressive);
+void launch_jpeg_decode_clip_tail(const JpegDecArgs* h_recs, const void* d_recs, int frames, hipStream_t stream, int64_t* enqueues);
+
+// A clip that may hold PROGRESSIVE frames (jpeg_prog.hip): plans[f] is the scan plan of frame f (nullptr, or a baseline one: the frame
+// runs as in launch_jpeg_decode_clip), h_prog[f] its progressive record, which also lies in the frame's uploaded record at
+// JPEG_CLIP_PROG_RECORD_OFFSET (jpeg_dec_clip_host.h); h_recs[f] is then what jpeg_prog_tail_args makes (form 0, coef, meta).
+//   whenet_jpeg_prog_clip_scan_kernel    launch L covers level L of every frame that has one: a frame's share of the grid is
+//            level_cnt[L] / 16 workgroups (0 for a frame with fewer levels and for a baseline frame), its first workgroup reads the
+//            frame's item list from level_off[L] / 16 on (JpegProgClipLevel).  The launches: the largest level count, <= 14.
+//   whenet_jpeg_prog_clip_finish_kernel  one launch for all progressive frames.
+// The bodies are the single-stream kernels'.  Always by level: the per-scan launches of option "jpeg_prog_levels" = 0 are a
+// measurement knob of the single-stream path.  enqueues / scan_launches (may be nullptr): += launches + memsets / scan-kernel launches.
+struct JpegProgClipLevel {
+    int first_group[MIXED_MAX_FRAMES];      // per frame: the level's first workgroup in the frame's own item list
+};
+#if defined(__HIPCC__)
+__device__ __forceinline__ const JpegProgArgs& jpeg_clip_prog_record(const void* recs, int f) {
+    return *reinterpret_cast<const JpegProgArgs*>(static_cast<const char*>(recs) + size_t(f) * JPEG_CLIP_RECORD_BYTES + JPEG_CLIP_PROG_RECORD_OFFSET);
+}
+#endif
+void launch_jpeg_decode_clip_progressive(const JpegDecArgs* h_recs, const JpegProgArgs* h_prog, const JpegProgPlan* const* plans, const void* d_recs,
+                                         int frames, void* d_zero, size_t zero_bytes, hipStream_t stream, int64_t* enqueues, int64_t* scan_launches);
 
 // ---- dconv.hip --------------------------------------------------------------------------
 // The detector body's layers (yolo_v3/model.py:20-122) on NHWC activations of `dtype` (WHENET_F16: binary16 storage on the f16

@@ -185,6 +185,10 @@ _PROTOS = {
     "whenet_op_jpeg_decode_progressive": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, _P, _P]),
     "whenet_frame_begin_jpeg_progressive": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_jpeg_progressive_counters": (C.c_int, [_P, C.POINTER(C.c_int64 * 4)]),
+    "whenet_op_jpeg_decode_clip_progressive": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int,
+                                                         C.c_int]),
+    "whenet_clip_begin_jpeg_progressive": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
+    "whenet_jpeg_clip_plan_progressive": (C.c_int, [C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -851,6 +855,39 @@ def _clip_streams(datas):
     ptrs = (_P * max(len(arrs), 1))(*[_ptr(a) if a.size else None for a in arrs])
     sizes = np.array([a.size for a in arrs], np.int64)
     return arrs, ptrs, sizes
+
+
+JPEG_CLIP_PROG_PLAN_FRAME_WORDS, JPEG_CLIP_PROG_PLAN_TOTAL_WORDS = 48, 16
+JPEG_CLIP_FORM_PROGRESSIVE = 2
+JPEG_CLIP_PROG_REGIONS = ("scans", "huff", "qz", "items", "raw")
+
+
+def jpeg_clip_plan_progressive(datas, entropy: int = 2, seg_bytes: int = 128) -> dict:
+    """`whenet_jpeg_clip_plan_progressive` (pure host): the layout a clip gets that may hold progressive streams, from the streams
+    themselves.  The dict of `jpeg_clip_plan`; a frame of form 2 is progressive, and every frame also has (offset, length) for the
+    regions of JPEG_CLIP_PROG_REGIONS (empty for a baseline frame) and the counts "nscans", "levels" and "list" (the entries of its
+    item list); the totals add "progressive" (frames), "scan_launches", "record_stride" and "prog_record_offset".  ValueError that
+    names the frame for a stream the scan parser refuses."""
+    arrs, ptrs, sizes = _clip_streams(datas)
+    n = len(arrs)
+    out = np.zeros(max(n, 0) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS + JPEG_CLIP_PROG_PLAN_TOTAL_WORDS, np.int64)
+    lib = load()
+    rc = lib.whenet_jpeg_clip_plan_progressive(ptrs, _ptr(sizes) if sizes.size else None, n, int(entropy), int(seg_bytes), _ptr(out))
+    if rc != OK:
+        raise ValueError(lib.whenet_last_error(None).decode())
+    frames = []
+    for f in range(n):
+        o = out[f * JPEG_CLIP_PROG_PLAN_FRAME_WORDS:(f + 1) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS]
+        d = {"form": int(o[0]), "seg_bytes": int(o[1]), "seg_cap": int(o[2])}
+        for k, name in enumerate(JPEG_CLIP_REGIONS + JPEG_CLIP_PROG_REGIONS):
+            at = 4 + 2 * k if k < len(JPEG_CLIP_REGIONS) else 6 + 2 * k
+            d[name] = (int(o[at]), int(o[at + 1]))
+        d["nscans"], d["levels"], d["list"] = int(o[42]), int(o[43]), int(o[44])
+        frames.append(d)
+    t = out[n * JPEG_CLIP_PROG_PLAN_FRAME_WORDS:]
+    return {"frames": frames, "records": (int(t[0]), int(t[1])), "upload_bytes": int(t[2]), "zero": (int(t[3]), int(t[4])),
+            "bytes": int(t[5]), "forms": (int(t[6]), int(t[7])), "progressive": int(t[8]), "scan_launches": int(t[9]),
+            "record_stride": int(t[10]), "prog_record_offset": int(t[11])}
 
 
 def jpeg_seg_dc_scan_host(diff, chunk: int) -> np.ndarray:
@@ -1590,14 +1627,20 @@ class Handle:
                                                       _ptr(status)))
         return t.value
 
-    def clip_begin_jpeg(self, datas, status: np.ndarray, bgr: bool = True, rule=None) -> int:
+    def clip_begin_jpeg(self, datas, status: np.ndarray, bgr: bool = True, rule=None, progressive: bool = False) -> int:
         """`whenet_clip_begin_jpeg`: `clip_begin` / `clip_begin_mixed` from the bytes of 1..16 JPEG streams, decoded on the device in one
         submission.  status = int32 [F,2], complete when the ticket's collect call returns; it must stay alive until then.  rule: as
-        `frame_begin_jpeg` (`whenet_clip_begin_jpeg_rule`)."""
+        `frame_begin_jpeg` (`whenet_clip_begin_jpeg_rule`).  progressive=True: progressive (SOF2) streams are accepted too
+        (`whenet_clip_begin_jpeg_progressive`); the handle's option "jpeg_progressive" is not read here."""
         arrs, ptrs, sizes = _clip_streams(datas)
         if status.dtype != np.int32 or status.size != 2 * len(arrs) or not status.flags.c_contiguous:
             raise ValueError("status must be a contiguous int32 [F,2] array")
         t = C.c_int(-1)
+        if progressive:
+            self._check(self._lib.whenet_clip_begin_jpeg_progressive(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs),
+                                                                     BGR if bgr else RGB, jpeg_rule_code(rule), C.byref(t),
+                                                                     _ptr(status) if status.size else None))
+            return t.value
         if rule is not None:
             self._check(self._lib.whenet_clip_begin_jpeg_rule(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), BGR if bgr else RGB,
                                                               jpeg_rule_code(rule), C.byref(t), _ptr(status) if status.size else None))
@@ -1625,6 +1668,16 @@ class Handle:
         self._check(self._lib.whenet_op_jpeg_decode_clip_rule(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
                                                               BGR if bgr else RGB, _ptr(status) if status.size else None, int(entropy),
                                                               int(seg_bytes), jpeg_rule_code(rule)))
+        return status
+
+    def op_jpeg_decode_clip_progressive(self, datas, surfaces, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None) -> np.ndarray:
+        """`whenet_op_jpeg_decode_clip_progressive`: `op_jpeg_decode_clip_rule` for clips that may hold progressive (SOF2) streams."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        surf = (SurfaceC * max(len(surfaces), 1))(*surfaces)
+        status = np.zeros((len(arrs), 2), np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_clip_progressive(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
+                                                                     BGR if bgr else RGB, _ptr(status) if status.size else None,
+                                                                     int(entropy), int(seg_bytes), jpeg_rule_code(rule)))
         return status
 
     def jpeg_clip_counters(self) -> dict:

@@ -309,14 +309,18 @@ class FramePipeline:
         self._last_sizes = [(info.h, info.w)]
         return st
 
-    def begin_clip_jpeg(self, datas, rule=None) -> list:
+    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False) -> list:
         """A clip from the bytes of 1..16 baseline JPEG streams (consecutive frames of an MJPG file: `MJPGReader.clips(16)`), each
         with its own size, sampling, tables and DRI: one upload of the compressed bytes, every decoder stage in one launch for all
         frames.  Frame f is what `begin_jpeg(datas[f])` makes; frames of one size make a clip as `begin_clip()` makes it, frames of
         different sizes one as `begin_clip_mixed()` makes it (at most option "letterbox_cache" of them).  `detect_heads_clip()` and
         `collect_clip()` follow.  One stream the decoder does not accept is a ValueError that names the frame, and the clip takes no
         place.  Returns a `JpegStatus` per frame, valid after `collect_clip()`: a damaged stream does not raise, it yields its own
-        defined frame and `ok == False` and leaves the other frames untouched.  `rule`: as `begin_jpeg`, one rule for the clip."""
+        defined frame and `ok == False` and leaves the other frames untouched.  `rule`: as `begin_jpeg`, one rule for the clip.
+        progressive=True: progressive (SOF2) streams are accepted too, alone or mixed with baseline ones (a folder of stills:
+        `demo.py` walks Sample/*.jpeg) -- frame f is then what `begin_jpeg(datas[f], progressive=True)` makes, and
+        `JpegStatus.interval` of a progressive frame is its flat (scan, interval) item.  Clips do not read the handle's option
+        "jpeg_progressive": only this argument accepts SOF2."""
         self._check_can_begin()
         _lib.jpeg_rule_code(rule)
         datas = list(datas)
@@ -325,11 +329,11 @@ class FramePipeline:
         infos = []
         for i, d in enumerate(datas):
             try:
-                infos.append(_lib.jpeg_parse(d))
+                infos.append(_lib.jpeg_parse_scans(d)[0] if progressive else _lib.jpeg_parse(d))
             except ValueError as e:
                 raise ValueError(f"begin_clip_jpeg: frame {i}: {e}") from None
         block = np.zeros((len(datas), 2), np.int32)      # (one array for the library to write; every JpegStatus is a row of it)
-        ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr, rule=rule)
+        ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr, rule=rule, progressive=progressive)
         sts = []
         for f in range(len(datas)):
             st = JpegStatus()

@@ -204,12 +204,17 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     return (out, st) if stats else out
 
 
-def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True, rule: str = "own"):
+def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True, rule: str = "own",
+                progressive: bool = False):
     """(frames, statuses) of 1..16 baseline JPEG streams decoded as ONE clip by the kernels (`whenet_op_jpeg_decode_clip`): a list of
     uint8 [H_f,W_f,3] frames and the status words int32 [F,2].  Frame f is `decode(datas[f])`, bit for bit.  `entropy`: None or
     "auto" (the handle's options, stream by stream), "interval" or "segmented" (`seg_bytes`: None = 128).  A stream the decoder does
     not accept is a ValueError that names the frame; a damaged one raises `DecodeError` with the frame's index in its text
-    (strict=False: its defined frame and status are returned with the others).  `rule`: "own" or "libjpeg", as `decode`."""
+    (strict=False: its defined frame and status are returned with the others).  `rule`: "own" or "libjpeg", as `decode`.
+    progressive=True (`whenet_op_jpeg_decode_clip_progressive`): progressive (SOF2) streams are accepted too, alone or next to
+    baseline ones -- a folder of stills as one clip.  Frame f is then `decode_host(datas[f], rule=rule, progressive=True)` with its
+    status; the scan kernel is launched once per level for all progressive frames together, and `entropy` / `seg_bytes` apply to
+    the baseline frames.  The handle's option "jpeg_progressive" is not read by clips: only this argument accepts SOF2."""
     _lib.jpeg_rule_code(rule)
     if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be None, 'auto', 'interval' or 'segmented'")
@@ -219,7 +224,7 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     frames = []
     for f, d in enumerate(datas):
         try:
-            i = _lib.jpeg_parse(d)
+            i = _lib.jpeg_parse_scans(d)[0] if progressive else _lib.jpeg_parse(d)
         except ValueError as e:
             raise ValueError(f"decode_clip: frame {f}: {e}") from None
         frames.append(np.empty((i.h, i.w, 3), np.uint8))
@@ -227,6 +232,8 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     seg = 128 if seg_bytes is None else int(seg_bytes)
     surfaces = [packed_surface(fr) for fr in frames]
     def run(h):
+        if progressive:
+            return h.op_jpeg_decode_clip_progressive(datas, surfaces, bgr, form, seg, rule)
         if rule != "own":
             return h.op_jpeg_decode_clip_rule(datas, surfaces, bgr, form, seg, rule)
         return h.op_jpeg_decode_clip(datas, surfaces, bgr, form, seg)

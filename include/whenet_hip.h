@@ -1061,7 +1061,7 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  *
  * JPEG DECODER, PROGRESSIVE (seven entry points, ABI still 6; csrc/jpeg_prog.hip, the arithmetic is csrc/jpeg_prog_host.h's).
  * Stills are where progressive streams (SOF2) are common, and cv2.imread opens them without a word.  The decoder for them is OPT-IN:
- * every call above keeps refusing SOF2 with its defaults ("progressive DCT (SOF2) ..."), every clip call always does.  The calls
+ * every call above keeps refusing SOF2 with its defaults ("progressive DCT (SOF2) ..."), every clip call above always does.  The calls
  * named ..._progressive, and whenet_frame_begin_jpeg[_rule] / whenet_op_jpeg_decode[_ex|_rule] on a handle whose option
  * "jpeg_progressive" is 1 (default 0), accept them.  A SOF0 stream through those calls is the baseline decoder's result, byte for
  * byte (its entropy options apply; for SOF2 they are ignored): one call serves a folder of mixed files.
@@ -1108,14 +1108,39 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  *                  the inverse DCT and colour kernels: enqueue-only on the copy stream.
  *   whenet_jpeg_progressive_counters   out[0..2]: decodes enqueued, scan-kernel launches, scans in them.
  *   option "jpeg_progressive"  0 (default) / 1, above.   option "jpeg_prog_levels"  1 (default): a launch per level; 0: a launch per
- *                  scan in stream order (a measurement knob: the bytes are the same).
- * Not built: a segmented (many lanes per interval) form for progressive scans -- a scan without DRI is ONE lane --, progressive
- * streams in clips, SOF0 / SOF1 streams of several scans, scans of two components, arithmetic, 12-bit and CMYK streams, block
- * smoothing, a progressive encoder, streams already in device memory. */
+ *                  scan in stream order (a measurement knob of the SINGLE-STREAM path: the bytes are the same; clips always launch
+ *                  by level).
+ * PROGRESSIVE STREAMS IN CLIPS (three more entry points, ABI still 6).  The clip calls above keep refusing SOF2 and do not read the
+ * option "jpeg_progressive"; the three below accept it.  Frame f of such a clip is whenet_jpeg_decode_progressive_host(data[f],
+ * rule) with its status pair, byte for byte, whether the stream is SOF2, SOF0 or the clip a mix of both; a SOF0 frame keeps the
+ * entropy form it has in a baseline clip; a damaged stream damages its own frame only; a stream the scan parser refuses is
+ * WHENET_EFORMAT "frame N: <the parser's reason>" before anything is enqueued.  Limits as above: 1..16 frames, one rule per clip,
+ * option "letterbox_cache" for frames of different sizes.  Still ONE H2D (records | per frame tables | data, or, SOF2: scans | huff |
+ * qz | items | data) and ONE memset (per frame start | meta | seg_stats | coef, or, SOF2: meta | raw coefficients).  Launch L of
+ * the clip scan kernel covers level L of every SOF2 frame that has one, so their number is the LARGEST level count among the
+ * frames (<= 14), not the sum; one finish launch; then the clip's inverse DCT and colour launches for all frames.  The marker
+ * scan, entropy and segmented launches run for the SOF0 frames only, and not at all without one.
+ *   whenet_op_jpeg_decode_clip_progressive   the arguments of whenet_op_jpeg_decode_clip_rule
+ *   whenet_clip_begin_jpeg_progressive       the arguments of whenet_clip_begin_jpeg_rule
+ *   whenet_jpeg_clip_plan_progressive        pure host, from the streams themselves: the layout such a clip gets.  out: num_frames *
+ *                  WHENET_JPEG_CLIP_PROG_PLAN_FRAME_WORDS + WHENET_JPEG_CLIP_PROG_PLAN_TOTAL_WORDS int64.  A frame's words 0..31
+ *                  and the totals' words 0..7 are whenet_jpeg_clip_plan's, form 2 marking a SOF2 frame (data, meta, coef and the
+ *                  planes are its regions; tables, start, seg_stats and the segmented regions are empty).  A frame's words 32..41:
+ *                  (offset, length) of scans, huff, qz, items, raw (empty for SOF0); 42..44: its scans, levels, item-list entries;
+ *                  45..47: 0.  Totals 8: SOF2 frames, 9: scan-kernel launches, 10: the stride of the argument records, 11: where
+ *                  a frame's progressive record lies inside its own; 12..15: 0.  Without a SOF2 frame the words 0..31 / 0..7
+ *                  equal whenet_jpeg_clip_plan's.  entropy 0, 1 or 2 (auto), as there.
+ * whenet_jpeg_clip_counters counts these clips as the others; whenet_jpeg_progressive_counters adds a decode per SOF2 frame, the
+ * scan launches once per clip and the scans of all its frames.
+ * Not built: a segmented (many lanes per interval) form for progressive scans -- a scan without DRI is ONE lane --, SOF0 / SOF1
+ * streams of several scans, scans of two components, arithmetic, 12-bit and CMYK streams, block smoothing, a progressive
+ * encoder, streams already in device memory. */
 #define WHENET_JPEG_SEG_WINDOW 256
 #define WHENET_JPEG_PROG_MAX_SCANS 128
 #define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
 #define WHENET_JPEG_CLIP_PLAN_TOTAL_WORDS 8
+#define WHENET_JPEG_CLIP_PROG_PLAN_FRAME_WORDS 48
+#define WHENET_JPEG_CLIP_PROG_PLAN_TOTAL_WORDS 16
 typedef struct {
     int32_t h, w, components;
     int32_t hs, vs;                  /* luma sampling factors (1 or 2); chroma is 1 x 1 */
@@ -1189,6 +1214,13 @@ WHENET_API int whenet_op_jpeg_decode_progressive(whenet_t* h, const uint8_t* dat
 WHENET_API int whenet_frame_begin_jpeg_progressive(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int* ticket,
                                         int32_t* status);
 WHENET_API int whenet_jpeg_progressive_counters(whenet_t* h, int64_t out[4]);
+WHENET_API int whenet_op_jpeg_decode_clip_progressive(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames,
+                                           const whenet_surface_t* dst, int channel_order, int32_t* status, int entropy, int seg_bytes,
+                                           int rule);
+WHENET_API int whenet_clip_begin_jpeg_progressive(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order,
+                                       int rule, int* ticket, int32_t* status);
+WHENET_API int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t* size, int num_frames, int entropy, int seg_bytes,
+                                      int64_t* out);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

@@ -44,8 +44,18 @@
                                 in form 0 and in the auto form, and Pillow's decode of the progressive stream on one core.  Medians
                                 of --clip-samples (>= 20) regions and their 10th..90th percentiles.
 
+    (vii) --clip F [F ...] --progressive
+                                clips of progressive streams (recorded, not gated), INSTEAD of (i)-(vi): F copies of Pillow's
+                                progressive stream (quality 95, 4:2:0; without DRI and with one interval per MCU row) as ONE
+                                whenet_clip_begin_jpeg_progressive against F whenet_frame_begin_jpeg_progressive submissions, as row
+                                (v) measures baseline clips: ms per frame, the median of --clip-samples (>= 20) regions after 3
+                                warm-up regions, with the 10th..90th percentiles; where ONE region takes more than --slow-seconds (a
+                                1080p stream without DRI: seconds per frame), --slow-samples regions after one warm-up region, and
+                                "..._regions" says how many were taken.  "enqueues", "h2d", "scan_launches" per clip: the counters.
+
   python tools/jpeg_dec_bench.py [--progressive] [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
                                  [--lanes 0] [--rule 0] [--rgb] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
+                                 [--slow-seconds 5] [--slow-samples 20]
 
 Every figure is the median of `--rounds` regions bracketed by a device synchronisation on both sides; device times come from
 events on the stream the work is enqueued on.  The frames the streams decode to are checked against the host statement first.
@@ -301,6 +311,69 @@ def prog_leg(m, h, w, args):
     return res
 
 
+def prog_clip_leg(m, h, w, args):
+    """row (vii): clips of progressive streams: F copies of Pillow's progressive stream of the picture as ONE
+    whenet_clip_begin_jpeg_progressive against the same F streams as F whenet_frame_begin_jpeg_progressive submissions (the
+    capability without clips), in the same process; each submission is released without heads and collected."""
+    import torch
+    from PIL import Image
+    from whenet_hip import _lib, jpeg, synth
+    hnd = m._handle
+    sync = torch.cuda.synchronize
+    no_heads = np.zeros((0, 4), np.int32)
+    im = Image.fromarray(np.ascontiguousarray(synth.video_frame(h, w)[..., ::-1]))
+    res = {"frame": [h, w], "rule": args.rule, "progressive_clip": {}}
+    for name, kw in (("no_dri", {}), ("row_intervals", {"restart_marker_rows": 1})):
+        buf = io.BytesIO()
+        im.save(buf, "JPEG", quality=95, subsampling=2, progressive=True, **kw)
+        data = buf.getvalue()
+        scans = _lib.jpeg_parse_scans(data)[1]
+        want = jpeg.decode_host(data, rule=RULES[args.rule], progressive=True)
+        got, _ = jpeg.decode_clip([data] * 3, handle=hnd, rule=RULES[args.rule], progressive=True)      # against the host statement first
+        r = {"bytes_jpeg": len(data), "scans": len(scans), "levels": max(s.level for s in scans), "items": sum(s.intervals for s in scans),
+             "equals_host": all(np.array_equal(g, want) for g in got)}
+        for F in args.clip:
+            datas, status, single = [data] * F, np.zeros((F, 2), np.int32), np.zeros(2, np.int32)
+
+            def clip():
+                t = hnd.clip_begin_jpeg(datas, status, progressive=True)
+                hnd.frame_heads(t, no_heads)
+                hnd.collect(t, 0)
+
+            def singles():
+                for d in datas:
+                    t = hnd.frame_begin_jpeg(d, single, progressive=True)
+                    hnd.frame_heads(t, no_heads)
+                    hnd.collect(t, 0)
+
+            before, pbefore = hnd.jpeg_clip_counters(), hnd.jpeg_progressive_counters()
+            clip()
+            after, pafter = hnd.jpeg_clip_counters(), hnd.jpeg_progressive_counters()
+            assert status.tolist() == [[0, -1]] * F and after["h2d"] - before["h2d"] == 1
+            out = {"enqueues": after["enqueues"] - before["enqueues"], "h2d": 1, "scan_launches": pafter["launches"] - pbefore["launches"]}
+            for key, fn in (("clip", clip), ("singles", singles)):
+                sync()
+                t = time.perf_counter()
+                fn()                                      # a warm-up region, timed: a region of many seconds gets --slow-samples regions
+                slow = time.perf_counter() - t > args.slow_seconds
+                for _ in range(0 if slow else 2):
+                    fn()
+                ms = []
+                for _ in range(args.slow_samples if slow else max(20, args.clip_samples)):
+                    sync()
+                    t = time.perf_counter()
+                    fn()
+                    ms.append((time.perf_counter() - t) * 1e3 / F)
+                q = np.percentile(ms, [10, 50, 90])
+                out[key + "_ms_per_frame"] = round(float(q[1]), 3)
+                out[key + "_p10_p90"] = [round(float(q[0]), 3), round(float(q[2]), 3)]
+                out[key + "_regions"] = len(ms)
+                print(f"{h}x{w} {name} F={F} {key}: {out[key + '_ms_per_frame']} ms per frame", file=sys.stderr, flush=True)
+            r[str(F)] = out
+        res["progressive_clip"][name] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
@@ -314,7 +387,9 @@ def main():
     ap.add_argument("--only-decode", action="store_true", help="rows (i) only")
     ap.add_argument("--clip", type=int, nargs="+", default=None, help="row (v) only: frames per clip of JPEG streams, 1..16 each")
     ap.add_argument("--clip-samples", type=int, default=20, help="regions per figure of row (v), at least 20")
-    ap.add_argument("--progressive", action="store_true", help="row (vi) only: progressive streams against their baseline twins")
+    ap.add_argument("--progressive", action="store_true", help="row (vi) only: progressive streams against their baseline twins; with --clip: row (vii)")
+    ap.add_argument("--slow-seconds", type=float, default=5.0, help="row (vii): a region longer than this counts as slow")
+    ap.add_argument("--slow-samples", type=int, default=20, help="row (vii): regions per figure where one region is slow (after ONE warm-up region)")
     args = ap.parse_args()
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
     import whenet
@@ -324,7 +399,7 @@ def main():
     try:
         for size in args.sizes:
             h, w = (int(v) for v in size.split("x"))
-            leg = prog_leg if args.progressive else (clip_leg if args.clip else size_leg)
+            leg = (prog_clip_leg if args.clip else prog_leg) if args.progressive else (clip_leg if args.clip else size_leg)
             print(json.dumps(leg(m, h, w, args)), flush=True)
     finally:
         m.close()
