@@ -178,6 +178,87 @@ int create_impl(const void* blob, size_t nbytes, int device_id, int dtype, whene
     }
 }
 
+// ---- the JPEG decoder's host statements (jpeg_dec_host.h, jpeg_dec_seg_host.h, jpeg_prog_host.h) ----
+// No handle: the text of a refusal is whenet_last_error(NULL)'s.  Each exported function (below, JPEG decoder) checks its own
+// arguments in its own order and names itself in every text; what they share is here (templates cannot stand inside extern "C").
+using whenet::detail::jpeg_parse_or_refuse;
+
+// the body's exception as the return code, its text in whenet_last_error(NULL)
+template <typename F>
+int host_statement(F&& body) {
+    try {
+        body();
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
+}
+
+void require_seg_args(const std::string& what, int seg_bytes, int window) {
+    WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL, what + ": seg_bytes must be a power of two in 4..4096");
+    WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, what + ": window must be 1..1024");
+}
+
+// One stream into a host surface: the header (plan: nullptr, or where the scan plan of a stream that may be progressive goes), the
+// destination's checks, the padded planes by make_planes(info, planes), the pixel rule
+template <typename F>
+void decode_into_host_surface(const std::string& what, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                              whenet::JpegProgPlan* plan, F&& make_planes) {
+    whenet_jpeg_info_t info;
+    jpeg_parse_or_refuse(what.c_str(), data, size, info, plan);
+    const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, what + ": " + (bad ? bad : ""));
+    WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, what + ": the surface must be host memory (on_device = 0)");
+    whenet::JpegDecPlanes planes;
+    make_planes(info, planes);
+    whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
+}
+
+// One stream into the caller's component planes: the header, the plane arguments, the padded planes by make_planes(info, planes),
+// their rows out at the caller's pitch
+template <typename F>
+void decode_into_host_planes(const std::string& what, const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch,
+                             whenet::JpegProgPlan* plan, F&& make_planes) {
+    whenet_jpeg_info_t info;
+    jpeg_parse_or_refuse(what.c_str(), data, size, info, plan);
+    const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
+    for (int c = 0; c < g.comps; ++c) {
+        const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
+        WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
+                       what + ": plane " + std::to_string(c) + " is NULL or its pitch is below its " + std::to_string(cw) + " samples");
+    }
+    whenet::JpegDecPlanes pl;
+    make_planes(info, pl);
+    for (int c = 0; c < g.comps; ++c) {
+        const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
+        for (int y = 0; y < ch; ++y)
+            std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
+    }
+}
+
+// whenet_jpeg_decode_host and whenet_jpeg_decode_rule_host
+int decode_host_as(const std::string& what, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                   int32_t status[2]) {
+    return host_statement([&] {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        decode_into_host_surface(what, data, size, dst, channel_order, rule, nullptr, [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+            whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), pl, status, rule);
+        });
+    });
+}
+
+// whenet_jpeg_decode_segmented_host and whenet_jpeg_decode_segmented_rule_host
+int decode_segmented_host_as(const std::string& what, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order,
+                             int seg_bytes, int window, int rule, int32_t status[2], int64_t stats[8]) {
+    return host_statement([&] {
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        require_seg_args(what, seg_bytes, window);
+        decode_into_host_surface(what, data, size, dst, channel_order, rule, nullptr, [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+            whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, pl, status, stats, rule);
+        });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1038,117 +1119,44 @@ int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_index, int 
 }
 
 // ---- JPEG decoder (jpeg_dec.hip, jpeg_dec_host.h, engine_post.cpp) ----
-namespace {
-// the header of a stream for the pure-host calls: WHENET_OK, or the code with the text in whenet_last_error(NULL)
-int parse_for_host(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info) {
-    if (data == nullptr || size < 1) {
-        g_create_error = std::string(what) + ": NULL argument or size < 1";
-        return WHENET_EINVAL;
-    }
-    if (const char* bad = whenet::jpeg_parse(data, size, info)) {
-        g_create_error = std::string(what) + ": " + bad;
-        return WHENET_EFORMAT;
-    }
-    return WHENET_OK;
-}
-}  // namespace
-
 int whenet_jpeg_parse(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info) {
-    if (info == nullptr) {
-        g_create_error = "jpeg_parse: NULL argument";
-        return WHENET_EINVAL;
-    }
-    return parse_for_host("jpeg_parse", data, size, *info);
+    return host_statement([&] {
+        WHENET_REQUIRE(info != nullptr, WHENET_EINVAL, "jpeg_parse: NULL argument");
+        jpeg_parse_or_refuse("jpeg_parse", data, size, *info);
+    });
 }
 
 int whenet_jpeg_decode_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int32_t status[2]) {
-    try {
-        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_host: NULL argument");
-        whenet_jpeg_info_t info;
-        if (const int rc = parse_for_host("jpeg_decode_host", data, size, info)) return rc;
-        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order);
-        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_host: ") + (bad ? bad : ""));
-        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_host: the surface must be host memory (on_device = 0)");
-        whenet::JpegDecPlanes planes;
-        whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), planes, status);
-        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order);
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
-    }
+    return decode_host_as("jpeg_decode_host", data, size, dst, channel_order, whenet::JPEG_RULE_OWN, status);
 }
 
 int whenet_jpeg_decode_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int32_t status[2]) {
-    try {
+    return host_statement([&] {
         WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_planes_host: NULL argument");
-        whenet_jpeg_info_t info;
-        if (const int rc = parse_for_host("jpeg_decode_planes_host", data, size, info)) return rc;
-        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
-        for (int c = 0; c < g.comps; ++c) {
-            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
-            WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
-                           "jpeg_decode_planes_host: plane " + std::to_string(c) + " is NULL or its pitch is below its " + std::to_string(cw) + " samples");
-        }
-        whenet::JpegDecPlanes pl;
-        whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), pl, status);
-        for (int c = 0; c < g.comps; ++c) {
-            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
-            for (int y = 0; y < ch; ++y)
-                std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
-        }
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+        decode_into_host_planes("jpeg_decode_planes_host", data, size, planes, pitch, nullptr,
+                                [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+                                    whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), pl, status);
+                                });
+    });
 }
 
 int whenet_jpeg_decode_segmented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int seg_bytes, int window,
                                       int32_t status[2], int64_t stats[8]) {
-    try {
-        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_segmented_host: NULL argument");
-        WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL, "jpeg_decode_segmented_host: seg_bytes must be a power of two in 4..4096");
-        WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, "jpeg_decode_segmented_host: window must be 1..1024");
-        whenet_jpeg_info_t info;
-        if (const int rc = parse_for_host("jpeg_decode_segmented_host", data, size, info)) return rc;
-        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order);
-        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_segmented_host: ") + (bad ? bad : ""));
-        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_segmented_host: the surface must be host memory (on_device = 0)");
-        whenet::JpegDecPlanes planes;
-        whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, planes, status, stats);
-        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order);
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+    return decode_segmented_host_as("jpeg_decode_segmented_host", data, size, dst, channel_order, seg_bytes, window, whenet::JPEG_RULE_OWN, status,
+                                    stats);
 }
 
 int whenet_jpeg_decode_segmented_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int seg_bytes, int window,
                                              int32_t status[2], int64_t stats[8]) {
-    try {
+    return host_statement([&] {
         WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_segmented_planes_host: NULL argument");
-        WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
-                       "jpeg_decode_segmented_planes_host: seg_bytes must be a power of two in 4..4096");
-        WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, "jpeg_decode_segmented_planes_host: window must be 1..1024");
-        whenet_jpeg_info_t info;
-        if (const int rc = parse_for_host("jpeg_decode_segmented_planes_host", data, size, info)) return rc;
-        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
-        for (int c = 0; c < g.comps; ++c) {
-            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
-            WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
-                           "jpeg_decode_segmented_planes_host: plane " + std::to_string(c) + " is NULL or its pitch is below its " + std::to_string(cw) +
-                               " samples");
-        }
-        whenet::JpegDecPlanes pl;
-        whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, pl, status, stats);
-        for (int c = 0; c < g.comps; ++c) {
-            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
-            for (int y = 0; y < ch; ++y)
-                std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
-        }
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+        require_seg_args("jpeg_decode_segmented_planes_host", seg_bytes, window);
+        decode_into_host_planes("jpeg_decode_segmented_planes_host", data, size, planes, pitch, nullptr,
+                                [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+                                    whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, pl,
+                                                                     status, stats);
+                                });
+    });
 }
 
 int whenet_jpeg_seg_dc_scan_host(const int32_t* diff, int64_t n, int chunk, int32_t* pred) {
@@ -1254,41 +1262,12 @@ int whenet_jpeg_clip_counters(whenet_t* h, int64_t out[4]) {
 
 // ---- the decode rule as an argument (JPEG DECODER, RULE 1): the calls above with `rule` beside their arguments ----
 int whenet_jpeg_decode_rule_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule, int32_t status[2]) {
-    try {
-        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_rule_host: NULL argument");
-        whenet_jpeg_info_t info;
-        if (const int rc = parse_for_host("jpeg_decode_rule_host", data, size, info)) return rc;
-        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
-        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_rule_host: ") + (bad ? bad : ""));
-        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_rule_host: the surface must be host memory (on_device = 0)");
-        whenet::JpegDecPlanes planes;
-        whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), planes, status, rule);
-        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+    return decode_host_as("jpeg_decode_rule_host", data, size, dst, channel_order, rule, status);
 }
 
 int whenet_jpeg_decode_segmented_rule_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int seg_bytes,
                                            int window, int rule, int32_t status[2], int64_t stats[8]) {
-    try {
-        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_segmented_rule_host: NULL argument");
-        WHENET_REQUIRE(whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
-                       "jpeg_decode_segmented_rule_host: seg_bytes must be a power of two in 4..4096");
-        WHENET_REQUIRE(window >= 1 && window <= whenet::JPEG_SEG_MAX_WINDOW, WHENET_EINVAL, "jpeg_decode_segmented_rule_host: window must be 1..1024");
-        whenet_jpeg_info_t info;
-        if (const int rc = parse_for_host("jpeg_decode_segmented_rule_host", data, size, info)) return rc;
-        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
-        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_segmented_rule_host: ") + (bad ? bad : ""));
-        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_segmented_rule_host: the surface must be host memory (on_device = 0)");
-        whenet::JpegDecPlanes planes;
-        whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, planes, status, stats, rule);
-        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+    return decode_segmented_host_as("jpeg_decode_segmented_rule_host", data, size, dst, channel_order, seg_bytes, window, rule, status, stats);
 }
 
 int whenet_op_jpeg_decode_rule(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
@@ -1325,90 +1304,51 @@ int whenet_clip_begin_jpeg_rule(whenet_t* h, const uint8_t* const* data, const i
 }
 
 // ---- progressive JPEG streams (jpeg_prog.hip, jpeg_prog_host.h) ----
-namespace {
-int parse_scans_for_host(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info, whenet::JpegProgPlan& plan) {
-    if (data == nullptr || size < 1) {
-        g_create_error = std::string(what) + ": NULL argument or size < 1";
-        return WHENET_EINVAL;
-    }
-    if (const char* bad = whenet::jpeg_prog_parse(data, size, info, plan)) {
-        g_create_error = std::string(what) + ": " + bad;
-        return WHENET_EFORMAT;
-    }
-    return WHENET_OK;
-}
-}  // namespace
-
 int whenet_jpeg_parse_scans(const uint8_t* data, int64_t size, whenet_jpeg_info_t* info, whenet_jpeg_scan_t* scans, int cap, int* num_scans) {
-    try {
+    return host_statement([&] {
         WHENET_REQUIRE(info != nullptr && num_scans != nullptr && (scans != nullptr || cap == 0) && cap >= 0, WHENET_EINVAL,
                        "jpeg_parse_scans: NULL argument");
         whenet::JpegProgPlan plan;
-        if (const int rc = parse_scans_for_host("jpeg_parse_scans", data, size, *info, plan)) return rc;
+        jpeg_parse_or_refuse("jpeg_parse_scans", data, size, *info, &plan);
         *num_scans = int(plan.scans.size());
         WHENET_REQUIRE(cap >= *num_scans, WHENET_EINVAL,
                        "jpeg_parse_scans: the stream has " + std::to_string(*num_scans) + " scans, the capacity is " + std::to_string(cap));
         for (size_t i = 0; i < plan.scans.size(); ++i) scans[i] = plan.scans[i];
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+    });
 }
 
 int whenet_jpeg_decode_progressive_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
                                         int32_t status[2]) {
-    try {
+    return host_statement([&] {
         WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_progressive_host: NULL argument");
-        whenet_jpeg_info_t info;
         whenet::JpegProgPlan plan;
-        if (const int rc = parse_scans_for_host("jpeg_decode_progressive_host", data, size, info, plan)) return rc;
-        const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
-        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_progressive_host: ") + (bad ? bad : ""));
-        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, "jpeg_decode_progressive_host: the surface must be host memory (on_device = 0)");
-        whenet::JpegDecPlanes planes;
-        whenet::jpeg_prog_decode_planes_host(info, plan, data, size, planes, status, rule);
-        whenet::jpeg_dec_frame_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule);
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+        decode_into_host_surface("jpeg_decode_progressive_host", data, size, dst, channel_order, rule, &plan,
+                                 [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+                                     whenet::jpeg_prog_decode_planes_host(info, plan, data, size, pl, status, rule);
+                                 });
+    });
 }
 
 int whenet_jpeg_decode_progressive_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int rule,
                                                int32_t status[2]) {
-    try {
+    return host_statement([&] {
         WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_decode_progressive_planes_host: NULL argument");
         WHENET_REQUIRE(whenet::jpeg_rule_ok(rule), WHENET_EINVAL, "jpeg_decode_progressive_planes_host: the rule must be 0 or 1");
-        whenet_jpeg_info_t info;
         whenet::JpegProgPlan plan;
-        if (const int rc = parse_scans_for_host("jpeg_decode_progressive_planes_host", data, size, info, plan)) return rc;
-        const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
-        for (int c = 0; c < g.comps; ++c) {
-            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
-            WHENET_REQUIRE(planes[c] != nullptr && pitch[c] >= cw, WHENET_EINVAL,
-                           "jpeg_decode_progressive_planes_host: plane " + std::to_string(c) + " is NULL or its pitch is below its " +
-                               std::to_string(cw) + " samples");
-        }
-        whenet::JpegDecPlanes pl;
-        whenet::jpeg_prog_decode_planes_host(info, plan, data, size, pl, status, rule);
-        for (int c = 0; c < g.comps; ++c) {
-            const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs, ch = c == 0 ? g.h : (g.h + g.vs - 1) / g.vs;
-            for (int y = 0; y < ch; ++y)
-                std::memcpy(planes[c] + size_t(y) * size_t(pitch[c]), pl.plane[c].data() + size_t(y) * size_t(g.plane_pitch[c]), size_t(cw));
-        }
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+        decode_into_host_planes("jpeg_decode_progressive_planes_host", data, size, planes, pitch, &plan,
+                                [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+                                    whenet::jpeg_prog_decode_planes_host(info, plan, data, size, pl, status, rule);
+                                });
+    });
 }
 
 int whenet_jpeg_progressive_coefficients_host(const uint8_t* data, int64_t size, int16_t* coef, int16_t* raw, int64_t cap_blocks,
                                               int64_t counters[8], int32_t status[2]) {
-    try {
+    return host_statement([&] {
         WHENET_REQUIRE(coef != nullptr && status != nullptr, WHENET_EINVAL, "jpeg_progressive_coefficients_host: NULL argument");
         whenet_jpeg_info_t info;
         whenet::JpegProgPlan plan;
-        if (const int rc = parse_scans_for_host("jpeg_progressive_coefficients_host", data, size, info, plan)) return rc;
+        jpeg_parse_or_refuse("jpeg_progressive_coefficients_host", data, size, info, &plan);
         WHENET_REQUIRE(!plan.baseline, WHENET_EINVAL, "jpeg_progressive_coefficients_host: a baseline (SOF0) stream has no scan plan");
         const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
         const int64_t blocks = int64_t(g.mcu_cols) * g.mcu_rows * g.bpm;
@@ -1421,10 +1361,7 @@ int whenet_jpeg_progressive_coefficients_host(const uint8_t* data, int64_t size,
         if (raw != nullptr) std::memcpy(raw, r.raw.data(), r.raw.size() * sizeof(int16_t));
         if (counters != nullptr)
             for (int i = 0; i < 8; ++i) counters[i] = r.cnt[i];
-        return WHENET_OK;
-    } catch (...) {
-        return translate_exception(g_create_error);
-    }
+    });
 }
 
 int whenet_op_jpeg_decode_progressive(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
@@ -1483,7 +1420,7 @@ int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t*
         for (int f = 0; f < num_frames; ++f) {
             whenet_jpeg_info_t info;
             const std::string who = "jpeg_clip_plan_progressive: frame " + std::to_string(f);
-            if (const int rc = parse_scans_for_host(who.c_str(), data[f], size[f], info, plans[size_t(f)])) return rc;
+            whenet::detail::jpeg_parse_or_refuse(who.c_str(), data[f], size[f], info, &plans[size_t(f)]);
             g[f] = whenet::jpeg_dec_geom(info), nbytes[f] = size[f] - info.data_offset, ptr[f] = &plans[size_t(f)];
         }
         whenet::JpegClipProgPlan plan;

@@ -627,13 +627,22 @@ class Engine {
     void jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes, int rule,
                            JpegClipJob& job, int progressive = 0) const;
     // records | tables | entropy bytes into `stage` (plan.upload_bytes), the records for a work buffer at d_base; recs: the same records
-    // (a progressive frame: its scan plan's share, a record as jpeg_prog_tail_args makes it, and its progressive record in precs)
+    // (a progressive frame: its scan plan's share, a record as jpeg_dec_args makes it of its regions, and its progressive record in precs)
     void jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,
                          int channel_order, int32_t* d_status, JpegDecArgs* recs, JpegProgArgs* precs) const;
     // the clip's launches behind its upload, and its counters
     void jpeg_clip_launch(const JpegClipJob& job, const JpegDecArgs* recs, const JpegProgArgs* precs, char* d_base, hipStream_t stream);
     // the layout of a decode's work buffers in the form the options (or `entropy` >= 0, `seg_bytes` > 0) give this stream
     JpegDecScratch jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy = -1, int seg_bytes = 0) const;
+    // one stream through the single-stream kernels (op_jpeg_decode, frame_begin_jpeg): its layouts; stage + one H2D + launches + counters
+    struct JpegStreamJob;
+    int64_t jpeg_stream_launch(const JpegStreamJob& job, const uint8_t* data, uint8_t* stage, void* d_work, const whenet_surface_t& dst,
+                               int channel_order, int32_t* d_status, int rule, hipStream_t stream);
+    // the slot of frame_begin_jpeg / clip_begin_jpeg: its buffers, destination surfaces and status words; its state and ticket
+    Slot& jpeg_slot_begin(const whenet_jpeg_info_t* info, int nframes, size_t upload_bytes, size_t work_bytes, size_t* off, whenet_surface_t* dst,
+                          int32_t*& d_status);
+    int jpeg_slot_finish(Slot& slot, const whenet_jpeg_info_t* info, const size_t* off, int clip_frames, bool one_size, int channel_order,
+                         int32_t* status);
 
     void open_device(int device_id);
     void require_model() const;

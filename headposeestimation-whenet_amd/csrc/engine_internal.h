@@ -34,6 +34,15 @@ struct TempBufs {     // hipMalloc'd scratch of the single-stage entry points
     }
 };
 
+// The header of a JPEG stream into `info`, for the engine and for the host statements of capi.cpp alike.  plan: nullptr (baseline
+// streams only), or where the scan plan goes (the parser that accepts progressive streams too).  WHENET_EINVAL, or WHENET_EFORMAT
+// with the parser's reason.
+inline void jpeg_parse_or_refuse(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info, JpegProgPlan* plan = nullptr) {
+    WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
+    const char* bad = plan != nullptr ? jpeg_prog_parse(data, size, info, *plan) : jpeg_parse(data, size, info);
+    WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
+}
+
 struct FlagGuard {    // sets a flag for a scope
     bool& flag;
     explicit FlagGuard(bool& f) : flag(f) { flag = true; }

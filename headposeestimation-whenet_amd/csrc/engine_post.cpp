@@ -551,6 +551,53 @@ struct GuardedOutput {
             if (off[f + 1] > off[f]) WHENET_HIP_CHECK(hipMemcpy(out[f], frames() + off[f], off[f + 1] - off[f], hipMemcpyDeviceToHost));
     }
 };
+
+// Host SURFACES as a kernel's destination (op_jpeg_decode: one, op_jpeg_decode_clip: one per frame): every plane of every surface
+// lies in one GuardedOutput at the caller's pitch and at the caller's address modulo 16, so that a store outside the rows' bytes --
+// between two rows, into a neighbouring surface -- meets the sentinel and is seen.  add() every surface, alloc(), launch into
+// device(f), to_host().
+struct GuardedSurfaces {
+    struct Plane {
+        size_t off;
+        int rows, row_bytes, pitch, surface, index;
+        uint8_t* host;
+    };
+    std::vector<Plane> planes;
+    std::vector<whenet_surface_t> d_dst;
+    size_t total = 0;
+    std::unique_ptr<GuardedOutput> out;
+    void add(const whenet_surface_t& dst, int h, int w) {
+        int rows[3], row_bytes[3];
+        const int np = overlay_surface_planes(dst.format, h, w, rows, row_bytes);
+        for (int p = 0; p < np; ++p) {
+            const size_t at = ((total + 15) & ~size_t(15)) + (reinterpret_cast<uintptr_t>(dst.plane[p]) & 15);
+            total = at + size_t(rows[p] - 1) * size_t(dst.pitch[p]) + size_t(row_bytes[p]);
+            planes.push_back({at, rows[p], row_bytes[p], dst.pitch[p], int(d_dst.size()), p, static_cast<uint8_t*>(dst.plane[p])});
+        }
+        d_dst.push_back(dst);
+    }
+    void alloc(hipStream_t s) {
+        out.reset(new GuardedOutput(total, s));
+        for (const Plane& pl : planes) d_dst[size_t(pl.surface)].plane[pl.index] = out->frames() + pl.off;
+    }
+    const whenet_surface_t* device() const { return d_dst.data(); }
+    // waits, checks the guard zones and the bytes between the rows, hands the rows to the caller's surfaces.  whose: "the surface" / "the surfaces"
+    void to_host(hipStream_t s, const std::string& what, const char* whose) const {
+        const size_t none[1] = {0};
+        out->to_host(s, none, 0, nullptr, what.c_str());
+        std::vector<uint8_t> back(total), is_row(total, 0);
+        WHENET_HIP_CHECK(hipMemcpy(back.data(), out->frames(), total, hipMemcpyDeviceToHost));
+        for (const Plane& pl : planes)
+            for (int r = 0; r < pl.rows; ++r) {
+                const size_t at = pl.off + size_t(r) * size_t(pl.pitch);
+                std::memset(is_row.data() + at, 1, size_t(pl.row_bytes));
+                std::memcpy(pl.host + size_t(r) * size_t(pl.pitch), back.data() + at, size_t(pl.row_bytes));
+            }
+        for (size_t i = 0; i < total; ++i)
+            WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
+                           what + ": the kernel wrote outside the rows of " + whose + " (byte " + std::to_string(i) + ")");
+    }
+};
 }  // namespace
 
 void Engine::op_pack_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, hipStream_t stream,
@@ -1427,39 +1474,6 @@ void Engine::frame_annotate_jpeg(int ticket, int frame_index, int display, int q
 namespace {
 // a slot's pinned status words: a pair per frame of the largest clip
 constexpr size_t JPEG_STATUS_BYTES = size_t(MIXED_MAX_FRAMES) * 2 * sizeof(int32_t);
-// the header of a stream, or WHENET_EFORMAT with the parser's reason
-whenet_jpeg_info_t parse_or_refuse(const char* what, const uint8_t* data, int64_t size) {
-    WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
-    whenet_jpeg_info_t info;
-    const char* bad = jpeg_parse(data, size, info);
-    WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
-    return info;
-}
-// the same through the parser that accepts progressive streams too: the scan plan beside the header
-whenet_jpeg_info_t parse_scans_or_refuse(const char* what, const uint8_t* data, int64_t size, JpegProgPlan& plan) {
-    WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
-    whenet_jpeg_info_t info;
-    const char* bad = jpeg_prog_parse(data, size, info, plan);
-    WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
-    return info;
-}
-// a baseline record over a progressive layout: what launch_jpeg_decode_tail reads of it
-JpegDecArgs jpeg_prog_tail_args(const JpegDecGeom& g, void* d_scratch, const JpegProgLayout& lay, const whenet_surface_t& dst, int channel_order,
-                                int32_t* d_status, int rule, int nbytes) {
-    JpegDecArgs a{};
-    char* const s = static_cast<char*>(d_scratch);
-    a.g = g;
-    a.tables = reinterpret_cast<const JpegDecTables*>(s + lay.huff);      // (not read behind the entropy stage)
-    a.data = reinterpret_cast<const uint8_t*>(s + lay.data), a.nbytes = nbytes;
-    a.start = reinterpret_cast<int32_t*>(s + lay.items), a.meta = reinterpret_cast<int32_t*>(s + lay.meta);
-    a.coef = reinterpret_cast<int16_t*>(s + lay.coef);
-    for (int c = 0; c < 3; ++c) {
-        a.plane[c] = reinterpret_cast<uint8_t*>(s + lay.plane[c]);
-        a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
-    }
-    a.format = dst.format, a.channel_order = channel_order, a.rule = rule, a.status = d_status, a.form = 0;
-    return a;
-}
 }  // namespace
 
 JpegDecScratch Engine::jpeg_dec_layout(const JpegDecGeom& g, size_t data_bytes, int64_t nbytes, int entropy, int seg_bytes) const {
@@ -1480,85 +1494,89 @@ void Engine::add_jpeg_progressive_counters(int64_t out[4]) const {
     for (int i = 0; i < 3; ++i) out[i] += jpeg_prog_counts_[i];
 }
 
+// One parsed stream for the single-stream kernels (op_jpeg_decode, frame_begin_jpeg): the work buffer of its decoder -- the baseline
+// one's (tables | compressed bytes | ...) or, for a progressive stream, the scan plan's; either way the front of the buffer is what
+// ONE H2D uploads
+struct Engine::JpegStreamJob {
+    const whenet_jpeg_info_t& info;
+    const JpegProgPlan& plan;      // (empty where the stream was parsed without one)
+    const bool prog;
+    const JpegDecGeom g;
+    const size_t nbytes;           // the bytes behind data_offset
+    const JpegDecScratch lay;
+    const JpegProgLayout play;
+    JpegStreamJob(const Engine& e, const whenet_jpeg_info_t& in, const JpegProgPlan& p, bool accept, int64_t size, int entropy, int seg_bytes)
+        : info(in), plan(p), prog(accept && !p.baseline), g(jpeg_dec_geom(in)), nbytes(size_t(size - in.data_offset)),
+          lay(e.jpeg_dec_layout(g, prog ? 0 : nbytes, prog ? 0 : int64_t(nbytes), prog ? 0 : entropy, seg_bytes)), play(g, p) {}
+    size_t upload_bytes() const { return prog ? play.upload_bytes : lay.upload_bytes; }
+    size_t work_bytes() const { return prog ? play.bytes : lay.bytes; }
+};
+
+// The stream's upload block laid out at `stage` (host memory of job.upload_bytes()), its one H2D into d_work and its launches on
+// `stream`: memset, a scan-kernel launch per level and the finish, then the stages the baseline decoder ends with; or the baseline
+// decoder.  Returns the scan-kernel launches.
+int64_t Engine::jpeg_stream_launch(const JpegStreamJob& job, const uint8_t* data, uint8_t* stage, void* d_work, const whenet_surface_t& dst,
+                                   int channel_order, int32_t* d_status, int rule, hipStream_t stream) {
+    if (job.prog) {
+        jpeg_prog_stage(job.plan, job.play, data + job.plan.data_base, stage);
+    } else {      // tables | compressed bytes
+        std::vector<JpegDecTables> tables(1);
+        jpeg_dec_build_tables(job.info, tables[0]);
+        std::memset(stage, 0, job.lay.data);
+        std::memcpy(stage + job.lay.tables, tables.data(), sizeof(JpegDecTables));
+        if (job.nbytes > 0) std::memcpy(stage + job.lay.data, data + job.info.data_offset, job.nbytes);
+    }
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_work, stage, job.upload_bytes(), hipMemcpyHostToDevice, stream));
+    int64_t launches = 0;
+    if (job.prog) {
+        launch_jpeg_decode_progressive(
+            jpeg_dec_args(job.g, d_work, job.play.regions(), job.plan.data_bytes, dst, channel_order, d_status, rule, 0), job.plan, job.play, d_work,
+            jpeg_prog_levels_, stream, &launches);
+        ++jpeg_prog_counts_[0], jpeg_prog_counts_[1] += launches, jpeg_prog_counts_[2] += int64_t(job.plan.dev.size());
+    } else {
+        launch_jpeg_decode(
+            jpeg_dec_args(job.g, d_work, job.lay.regions(), (long long)(job.nbytes), dst, channel_order, d_status, rule, job.lay.seg_lanes), job.lay,
+            stream);
+        ++jpeg_dec_launched_[job.lay.form];
+    }
+    return launches;
+}
+
 void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy,
                             int seg_bytes, int64_t* stats, int rule, int progressive) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
     rule = jpeg_rule_of("op_jpeg_decode", rule);
+    whenet_jpeg_info_t info;
     JpegProgPlan plan;
     const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
-    const whenet_jpeg_info_t info = accept ? parse_scans_or_refuse("op_jpeg_decode", data, size, plan) : parse_or_refuse("op_jpeg_decode", data, size);
-    const bool prog = accept && !plan.baseline;
+    jpeg_parse_or_refuse("op_jpeg_decode", data, size, info, accept ? &plan : nullptr);
     const char* bad = jpeg_dec_check_dst(info, &dst, channel_order, rule);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_decode: ") + (bad ? bad : ""));
     WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_jpeg_decode: the surface must be host memory (on_device = 0)");
     check_surface("op_jpeg_decode", dst, info.h, info.w);
-    const JpegDecGeom g = jpeg_dec_geom(info);
-    const size_t nbytes = size_t(size - info.data_offset);
-    const JpegDecScratch lay = jpeg_dec_layout(g, prog ? 0 : nbytes, prog ? 0 : int64_t(nbytes), prog ? 0 : entropy, seg_bytes);
-    const JpegProgLayout play(g, plan);
-    std::vector<JpegDecTables> tables(1);
-    if (!prog) jpeg_dec_build_tables(info, tables[0]);
-    // the destination on the device: every plane at the caller's pitch and at the caller's address modulo 16, between two guard
-    // zones and over a sentinel, so that a store outside the rows' bytes is seen
-    int rows[3], row_bytes[3];
-    const int planes = overlay_surface_planes(dst.format, info.h, info.w, rows, row_bytes);
-    size_t off[4] = {0, 0, 0, 0}, total = 0;
-    for (int p = 0; p < planes; ++p) {
-        off[p] = ((total + 15) & ~size_t(15)) + (reinterpret_cast<uintptr_t>(dst.plane[p]) & 15);
-        total = off[p] + size_t(rows[p] - 1) * size_t(dst.pitch[p]) + size_t(row_bytes[p]);
-    }
+    const JpegStreamJob job(*this, info, plan, accept, size, entropy, seg_bytes);
+    GuardedSurfaces out;
+    out.add(dst, info.h, info.w);
     TempBufs tmp;
-    char* const d_scratch = static_cast<char*>(tmp.get(prog ? play.bytes : lay.bytes));
+    char* const d_scratch = static_cast<char*>(tmp.get(job.work_bytes()));
     int32_t* const d_status = static_cast<int32_t*>(tmp.get(2 * sizeof(int32_t)));
-    std::vector<uint8_t> upload;      // (alive until the wait below)
-    if (prog) {
-        upload.resize(play.upload_bytes);
-        jpeg_prog_stage(plan, play, data + plan.data_base, upload.data());
-        WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch, upload.data(), play.upload_bytes, hipMemcpyHostToDevice, stream_));
-    } else {
-        WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.tables, tables.data(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream_));
-        if (nbytes > 0) WHENET_HIP_CHECK(hipMemcpyAsync(d_scratch + lay.data, data + info.data_offset, nbytes, hipMemcpyHostToDevice, stream_));
-    }
-    const GuardedOutput d_out(total, stream_);
-    whenet_surface_t d_dst = dst;
-    for (int p = 0; p < planes; ++p) d_dst.plane[p] = d_out.frames() + off[p];
-    int64_t prog_launches = 0;
-    if (prog) {
-        launch_jpeg_decode_progressive(jpeg_prog_tail_args(g, d_scratch, play, d_dst, channel_order, d_status, rule, int(plan.data_bytes)), plan, play,
-                                       d_scratch, jpeg_prog_levels_, stream_, &prog_launches);
-        ++jpeg_prog_counts_[0], jpeg_prog_counts_[1] += prog_launches, jpeg_prog_counts_[2] += int64_t(plan.dev.size());
-    } else {
-        launch_jpeg_decode(jpeg_dec_args(g, d_scratch, lay, reinterpret_cast<const uint8_t*>(d_scratch + lay.data), (long long)(nbytes), d_dst,
-                                         channel_order, d_status, rule),
-                           lay, stream_);
-        ++jpeg_dec_launched_[lay.form];
-    }
-    d_out.to_host(stream_, off, 0, nullptr, "op_jpeg_decode");      // waits, checks the guard zones
-    std::vector<uint8_t> back(total);
-    WHENET_HIP_CHECK(hipMemcpy(back.data(), d_out.frames(), total, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> is_row(total, 0);
-    for (int p = 0; p < planes; ++p)
-        for (int r = 0; r < rows[p]; ++r) {
-            const size_t at = off[p] + size_t(r) * size_t(dst.pitch[p]);
-            std::memset(is_row.data() + at, 1, size_t(row_bytes[p]));
-            std::memcpy(static_cast<uint8_t*>(dst.plane[p]) + size_t(r) * size_t(dst.pitch[p]), back.data() + at, size_t(row_bytes[p]));
-        }
-    for (size_t i = 0; i < total; ++i)
-        WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
-                       "op_jpeg_decode: the kernel wrote outside the rows of the surface (byte " + std::to_string(i) + ")");
+    std::vector<uint8_t> upload(job.upload_bytes());      // (alive until the wait below)
+    out.alloc(stream_);
+    const int64_t prog_launches = jpeg_stream_launch(job, data, upload.data(), d_scratch, out.device()[0], channel_order, d_status, rule, stream_);
+    out.to_host(stream_, "op_jpeg_decode", "the surface");      // waits
     WHENET_HIP_CHECK(hipMemcpy(status, d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (stats != nullptr && prog) {
+    if (stats != nullptr && job.prog) {
         std::fill(stats, stats + 8, int64_t(0));
         stats[0] = plan.total_items, stats[1] = plan.levels, stats[2] = int64_t(plan.dev.size()), stats[3] = prog_launches;
     } else if (stats != nullptr) {
-        if (lay.form == 1) {
-            WHENET_HIP_CHECK(hipMemcpy(stats, d_scratch + lay.seg_stats, 8 * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (job.lay.form == 1) {
+            WHENET_HIP_CHECK(hipMemcpy(stats, d_scratch + job.lay.seg_stats, 8 * sizeof(int64_t), hipMemcpyDeviceToHost));
         } else {      // an interval per lane: the intervals it decoded are those up to the first one the markers make bad
             int32_t meta0 = 0;
-            WHENET_HIP_CHECK(hipMemcpy(&meta0, d_scratch + lay.meta, sizeof(int32_t), hipMemcpyDeviceToHost));
+            WHENET_HIP_CHECK(hipMemcpy(&meta0, d_scratch + job.lay.meta, sizeof(int32_t), hipMemcpyDeviceToHost));
             std::fill(stats, stats + 8, int64_t(0));
-            stats[0] = std::min(meta0, g.intervals - 1) + 1;
+            stats[0] = std::min(meta0, job.g.intervals - 1) + 1;
         }
     }
 }
@@ -1595,8 +1613,8 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     }
     if (!jpeg_source_) jpeg_source_.create();
     if (!jpeg_done_) jpeg_done_.create();
-    JpegDecArgs a = jpeg_dec_args(g, jpeg_dec_scratch_.as<void>(), lay, d_entropy, nbytes, dst, channel_order, d_status, jpeg_rule_);
-    a.tables = jpeg_dec_tables_d_.as<JpegDecTables>();
+    JpegDecArgs a = jpeg_dec_args(g, jpeg_dec_scratch_.as<void>(), lay.regions(), nbytes, dst, channel_order, d_status, jpeg_rule_, lay.seg_lanes);
+    a.tables = jpeg_dec_tables_d_.as<JpegDecTables>(), a.data = d_entropy;      // (neither lies in the work buffer)
     WHENET_HIP_CHECK(hipEventRecord(jpeg_source_, stream));
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, jpeg_source_, 0));
     launch_jpeg_decode(a, lay, stream_);
@@ -1605,63 +1623,63 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     WHENET_HIP_CHECK(hipStreamWaitEvent(stream, jpeg_done_, 0));
 }
 
+// A free slot for the decoded frames of frame_begin_jpeg / clip_begin_jpeg: the pinned staging for an upload of upload_bytes, the
+// frame buffer (frame f at off[f], tight), the decoder's work buffer and the status words.  dst[f]: frame f as the packed surface
+// the kernels write; d_status: the pinned status words as the device addresses them.
+Engine::Slot& Engine::jpeg_slot_begin(const whenet_jpeg_info_t* info, int nframes, size_t upload_bytes, size_t work_bytes, size_t* off,
+                                      whenet_surface_t* dst, int32_t*& d_status) {
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    off[0] = 0;
+    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(info[f].h) * info[f].w * 3;
+    slot.frame.h.grow(std::max(off[nframes], upload_bytes));      // (>= the frames' bytes: the size every other user of the staging grows it to)
+    slot.frame.d.grow(off[nframes]);
+    slot.jpg_dec.grow(work_bytes);
+    slot.jpg_dec_status.grow(JPEG_STATUS_BYTES);
+    void* p = nullptr;
+    WHENET_HIP_CHECK(hipHostGetDevicePointer(&p, slot.jpg_dec_status.as<void>(), 0));
+    d_status = static_cast<int32_t*>(p);
+    for (int f = 0; f < nframes; ++f) {
+        dst[f] = whenet_surface_t{};
+        dst[f].plane[0] = slot.frame.d.as<uint8_t>() + off[f], dst[f].pitch[0] = 3 * info[f].w, dst[f].format = WHENET_SURF_PACKED, dst[f].on_device = 1;
+    }
+    return slot;
+}
+
+// ... and its end, behind the launches on the copy stream: the slot as frame_begin (clip_frames = 0), clip_begin (frames of one size)
+// or clip_begin_mixed (frames back to back at off) leaves it for the decoded frames; the ticket
+int Engine::jpeg_slot_finish(Slot& slot, const whenet_jpeg_info_t* info, const size_t* off, int clip_frames, bool one_size, int channel_order,
+                             int32_t* status) {
+    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    slot.fh = info[0].h, slot.fw = info[0].w, slot.swap_rb = channel_order == WHENET_BGR;
+    if (!one_size) {
+        for (int f = 0; f < clip_frames; ++f) slot.clip_fh[f] = info[f].h, slot.clip_fw[f] = info[f].w;
+        std::copy(off, off + clip_frames + 1, slot.clip_off);
+    }
+    slot.frame_ticket = finish_submission(slot, 0);
+    slot.clip_f = clip_frames;
+    slot.clip_mixed = !one_size;
+    slot.jpg_dec_out = status, slot.jpg_dec_pairs = std::max(clip_frames, 1);
+    return slot.frame_ticket;
+}
+
 // frame_begin from a JPEG stream: the slot ends up exactly as frame_begin(decoded frame, channel_order) leaves it
 int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule, int progressive) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "frame_begin_jpeg: NULL argument");
     rule = jpeg_rule_of("frame_begin_jpeg", rule);
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "frame_begin_jpeg: unknown channel order");
+    whenet_jpeg_info_t info;
     JpegProgPlan plan;
     const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
-    const whenet_jpeg_info_t info =      // (before a slot is taken)
-        accept ? parse_scans_or_refuse("frame_begin_jpeg", data, size, plan) : parse_or_refuse("frame_begin_jpeg", data, size);
-    const JpegDecGeom g = jpeg_dec_geom(info);
-    // the work buffers of the stream's decoder: the baseline one's (tables | compressed bytes | ...) or, for a progressive stream,
-    // the scan plan's; either way the front of the buffer is what the pinned staging uploads as ONE H2D
-    const bool prog = accept && !plan.baseline;
-    const size_t nbytes = size_t(size - info.data_offset);
-    const JpegDecScratch lay = jpeg_dec_layout(g, prog ? 0 : nbytes, prog ? 0 : int64_t(nbytes));
-    const JpegProgLayout play(g, plan);
-    const size_t upload_bytes = prog ? play.upload_bytes : lay.upload_bytes, work_bytes = prog ? play.bytes : lay.bytes;
-    Slot& slot = *free_slot();
-    ensure_slot(slot, 1);
-    const size_t fbytes = size_t(info.h) * info.w * 3;
-    slot.frame.h.grow(std::max(fbytes, upload_bytes));      // (>= the frame's bytes: the size every other user of the staging grows it to)
-    slot.frame.d.grow(fbytes);
-    slot.jpg_dec.grow(work_bytes);
-    slot.jpg_dec_status.grow(JPEG_STATUS_BYTES);
-    void* d_status = nullptr;                      // the pinned status words as the device addresses them
-    WHENET_HIP_CHECK(hipHostGetDevicePointer(&d_status, slot.jpg_dec_status.as<void>(), 0));
-    uint8_t* const stage = slot.frame.h.as<uint8_t>();
-    if (prog) {
-        jpeg_prog_stage(plan, play, data + plan.data_base, stage);
-    } else {      // tables | compressed bytes
-        std::vector<JpegDecTables> tables(1);
-        jpeg_dec_build_tables(info, tables[0]);
-        std::memset(stage, 0, lay.data);
-        std::memcpy(stage + lay.tables, tables.data(), sizeof(JpegDecTables));
-        if (nbytes > 0) std::memcpy(stage + lay.data, data + info.data_offset, nbytes);
-    }
-    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, upload_bytes, hipMemcpyHostToDevice, copy_stream()));
-    whenet_surface_t dst{};
-    dst.plane[0] = slot.frame.d.as<void>(), dst.pitch[0] = 3 * info.w, dst.format = WHENET_SURF_PACKED, dst.on_device = 1;
-    if (prog) {      // memset, a scan-kernel launch per level, the finish, then the stages the baseline decoder ends with
-        int64_t launches = 0;
-        launch_jpeg_decode_progressive(jpeg_prog_tail_args(g, slot.jpg_dec.as<void>(), play, dst, channel_order, static_cast<int32_t*>(d_status), rule,
-                                                           int(plan.data_bytes)),
-                                       plan, play, slot.jpg_dec.as<void>(), jpeg_prog_levels_, copy_stream(), &launches);
-        ++jpeg_prog_counts_[0], jpeg_prog_counts_[1] += launches, jpeg_prog_counts_[2] += int64_t(plan.dev.size());
-    } else {
-        launch_jpeg_decode(jpeg_dec_args(g, slot.jpg_dec.as<void>(), lay, slot.jpg_dec.as<uint8_t>() + lay.data, (long long)(nbytes), dst,
-                                         channel_order, static_cast<int32_t*>(d_status), rule),
-                           lay, copy_stream());
-        ++jpeg_dec_launched_[lay.form];
-    }
-    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
-    slot.fh = info.h, slot.fw = info.w, slot.swap_rb = channel_order == WHENET_BGR;
-    slot.frame_ticket = finish_submission(slot, 0);
-    slot.jpg_dec_out = status, slot.jpg_dec_pairs = 1;
-    return slot.frame_ticket;
+    jpeg_parse_or_refuse("frame_begin_jpeg", data, size, info, accept ? &plan : nullptr);      // (before a slot is taken)
+    const JpegStreamJob job(*this, info, plan, accept, size, -1, 0);
+    size_t off[2];
+    whenet_surface_t dst;
+    int32_t* d_status = nullptr;
+    Slot& slot = jpeg_slot_begin(&info, 1, job.upload_bytes(), job.work_bytes(), off, &dst, d_status);
+    jpeg_stream_launch(job, data, slot.frame.h.as<uint8_t>(), slot.jpg_dec.as<void>(), dst, channel_order, d_status, rule, copy_stream());
+    return jpeg_slot_finish(slot, &info, off, 0, true, channel_order, status);
 }
 
 // ---- clips of JPEG streams (the contract is in engine.h) ----
@@ -1692,8 +1710,7 @@ void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, con
     if (job.progressive) job.prog.resize(size_t(nframes));
     for (int f = 0; f < nframes; ++f) {
         const std::string who = w + ": frame " + std::to_string(f);
-        job.info[f] = job.progressive ? parse_scans_or_refuse(who.c_str(), data[f], size[f], job.prog[size_t(f)])
-                                      : parse_or_refuse(who.c_str(), data[f], size[f]);
+        jpeg_parse_or_refuse(who.c_str(), data[f], size[f], job.info[f], job.progressive ? &job.prog[size_t(f)] : nullptr);
         job.g[f] = jpeg_dec_geom(job.info[f]);
         job.nbytes[f] = size[f] - job.info[f].data_offset;
     }
@@ -1718,46 +1735,29 @@ void Engine::jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data,
     for (int f = 0; f < job.frames; ++f) {
         const JpegClipFrame& q = p.f[f];
         precs[f] = JpegProgArgs{};
+        uint8_t* const rec = stage + p.records.off + size_t(f) * JPEG_CLIP_RECORD_BYTES;
         if (job.is_prog(f)) {
-            // the frame's record as jpeg_prog_tail_args makes it, its progressive record behind it, its scan plan's share of the upload
+            // the frame's record over its progressive regions (tables: the scans' Huffman tables, start: the item list), its progressive
+            // record behind it, its scan plan's share of the upload
             const JpegClipProgFrame& r = job.pplan.pf[f];
             const JpegProgPlan& plan = job.prog[size_t(f)];
-            JpegProgLayout lay(job.g[f], plan);      // (the offsets of this frame's regions in the clip's allocation)
-            lay.scans = r.scans.off, lay.huff = r.huff.off, lay.qz = r.qz.off, lay.items = r.items.off, lay.data = q.data.off;
-            lay.meta = q.meta.off, lay.raw = r.raw.off, lay.coef = q.coef.off;
-            for (int c = 0; c < 3; ++c) lay.plane[c] = q.plane[c].off;
-            const JpegDecArgs a = jpeg_prog_tail_args(job.g[f], d_base, lay, dst[f], channel_order, d_status + 2 * f, job.rule, int(plan.data_bytes));
+            JpegClipFrame regions = q;
+            regions.tables = r.huff, regions.start = r.items;
+            const JpegDecArgs a = jpeg_dec_args(job.g[f], d_base, regions, plan.data_bytes, dst[f], channel_order, d_status + 2 * f, job.rule, 0);
             JpegProgArgs x{};
             x.g = job.g[f];
             x.scans = reinterpret_cast<const JpegProgScan*>(s + r.scans.off), x.huff = reinterpret_cast<const JpegDecHuff*>(s + r.huff.off);
             x.qz = reinterpret_cast<const int16_t*>(s + r.qz.off), x.items = reinterpret_cast<const JpegProgItem*>(s + r.items.off);
-            x.data = reinterpret_cast<const uint8_t*>(s + q.data.off), x.nbytes = int(plan.data_bytes);
+            x.data = a.data, x.nbytes = a.nbytes;
             x.raw = reinterpret_cast<int16_t*>(s + r.raw.off), x.coef = a.coef, x.meta = a.meta, x.first_bad = plan.first_bad;
             recs[f] = a, precs[f] = x;
-            uint8_t* const rec = stage + p.records.off + size_t(f) * JPEG_CLIP_RECORD_BYTES;
             std::memcpy(rec, &a, sizeof(a));
             std::memcpy(rec + JPEG_CLIP_PROG_RECORD_OFFSET, &x, sizeof(x));
             jpeg_clip_stage_progressive(plan, q, r, data[f] + plan.data_base, stage);
             continue;
         }
-        JpegDecArgs a{};
-        a.g = job.g[f];
-        a.tables = reinterpret_cast<const JpegDecTables*>(s + q.tables.off);
-        a.data = reinterpret_cast<const uint8_t*>(s + q.data.off), a.nbytes = int(job.nbytes[f]);
-        a.start = reinterpret_cast<int32_t*>(s + q.start.off), a.meta = reinterpret_cast<int32_t*>(s + q.meta.off);
-        a.coef = reinterpret_cast<int16_t*>(s + q.coef.off);
-        for (int c = 0; c < 3; ++c) {
-            a.plane[c] = reinterpret_cast<uint8_t*>(s + q.plane[c].off);
-            a.dst[c] = static_cast<uint8_t*>(dst[f].plane[c]), a.dst_pitch[c] = dst[f].pitch[c];
-        }
-        a.format = dst[f].format, a.channel_order = channel_order, a.rule = job.rule;
-        a.status = d_status + 2 * f;
-        a.form = q.form, a.seg_bytes = q.seg_bytes, a.seg_cap = int(q.seg_cap), a.seg_lanes = jpeg_seg_lanes_;
-        a.seg_stats = reinterpret_cast<long long*>(s + q.seg_stats.off);
-        a.first_seg = reinterpret_cast<int32_t*>(s + q.first_seg.off), a.seg_exit = reinterpret_cast<uint64_t*>(s + q.seg_exit.off);
-        a.seg_count = reinterpret_cast<JpegSegCount*>(s + q.seg_count.off), a.seg_blk = reinterpret_cast<int32_t*>(s + q.seg_blk.off);
-        recs[f] = a;
-        std::memcpy(stage + p.records.off + size_t(f) * JPEG_CLIP_RECORD_BYTES, &a, sizeof(a));
+        recs[f] = jpeg_dec_args(job.g[f], d_base, q, job.nbytes[f], dst[f], channel_order, d_status + 2 * f, job.rule, jpeg_seg_lanes_);
+        std::memcpy(rec, &recs[f], sizeof(JpegDecArgs));
         JpegDecTables* const t = reinterpret_cast<JpegDecTables*>(stage + q.tables.off);      // (256-byte aligned in pinned or vector memory)
         jpeg_dec_build_tables(job.info[f], *t);
         if (q.data.len > 0) std::memcpy(stage + q.data.off, data[f] + job.info[f].data_offset, q.data.len);
@@ -1798,37 +1798,17 @@ int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int
     WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
                    "clip_begin_jpeg: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
                        std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
-    Slot& slot = *free_slot();
-    ensure_slot(slot, 1);
-    size_t off[MIXED_MAX_FRAMES + 1] = {};
-    for (int f = 0; f < nframes; ++f) off[f + 1] = off[f] + size_t(job.info[f].h) * job.info[f].w * 3;
-    const JpegClipPlan& plan = job.plan;
-    slot.frame.h.grow(std::max(off[nframes], plan.upload_bytes));      // (>= the frames' bytes: the size every other user of the staging grows it to)
-    slot.frame.d.grow(off[nframes]);
-    slot.jpg_dec.grow(plan.bytes);
-    slot.jpg_dec_status.grow(JPEG_STATUS_BYTES);
-    void* d_status = nullptr;                      // the pinned status words as the device addresses them
-    WHENET_HIP_CHECK(hipHostGetDevicePointer(&d_status, slot.jpg_dec_status.as<void>(), 0));
-    whenet_surface_t dst[MIXED_MAX_FRAMES] = {};
-    for (int f = 0; f < nframes; ++f)
-        dst[f].plane[0] = slot.frame.d.as<uint8_t>() + off[f], dst[f].pitch[0] = 3 * job.info[f].w, dst[f].format = WHENET_SURF_PACKED, dst[f].on_device = 1;
+    size_t off[MIXED_MAX_FRAMES + 1];
+    whenet_surface_t dst[MIXED_MAX_FRAMES];
+    int32_t* d_status = nullptr;
+    Slot& slot = jpeg_slot_begin(job.info.data(), nframes, job.plan.upload_bytes, job.plan.bytes, off, dst, d_status);
     JpegDecArgs recs[MIXED_MAX_FRAMES];
     JpegProgArgs precs[MIXED_MAX_FRAMES];
     uint8_t* const stage = slot.frame.h.as<uint8_t>();
-    jpeg_clip_stage(job, data, stage, slot.jpg_dec.as<void>(), dst, channel_order, static_cast<int32_t*>(d_status), recs, precs);
-    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, plan.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
+    jpeg_clip_stage(job, data, stage, slot.jpg_dec.as<void>(), dst, channel_order, d_status, recs, precs);
+    WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, job.plan.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
     jpeg_clip_launch(job, recs, precs, slot.jpg_dec.as<char>(), copy_stream());
-    WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
-    slot.fh = job.info[0].h, slot.fw = job.info[0].w, slot.swap_rb = channel_order == WHENET_BGR;
-    if (!one_size) {
-        for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = job.info[f].h, slot.clip_fw[f] = job.info[f].w;
-        std::copy(off, off + nframes + 1, slot.clip_off);
-    }
-    slot.frame_ticket = finish_submission(slot, 0);
-    slot.clip_f = nframes;
-    slot.clip_mixed = !one_size;
-    slot.jpg_dec_out = status, slot.jpg_dec_pairs = nframes;
-    return slot.frame_ticket;
+    return jpeg_slot_finish(slot, job.info.data(), off, nframes, one_size, channel_order, status);
 }
 
 void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
@@ -1837,64 +1817,28 @@ void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size
     WHENET_REQUIRE(status != nullptr && dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_clip: NULL argument");
     JpegClipJob job;
     jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, rule, job, progressive);
-    // every plane of every destination on the device at the caller's pitch and at the caller's address modulo 16, between two guard
-    // zones and over a sentinel, so that a store outside the rows' bytes -- into a neighbouring frame as well -- is seen
-    struct Plane {
-        size_t off;
-        int rows, row_bytes, pitch;
-        uint8_t* host;
-    };
-    std::vector<Plane> planes;
-    whenet_surface_t d_dst[MIXED_MAX_FRAMES];
-    size_t total = 0;
+    GuardedSurfaces out;
     for (int f = 0; f < nframes; ++f) {
         const std::string who = "op_jpeg_decode_clip: frame " + std::to_string(f);
         const char* bad = jpeg_dec_check_dst(job.info[f], &dst[f], channel_order, job.rule);
         WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, who + ": " + (bad ? bad : ""));
         WHENET_REQUIRE(dst[f].on_device == 0, WHENET_EINVAL, who + ": the surface must be host memory (on_device = 0)");
         check_surface(who.c_str(), dst[f], job.info[f].h, job.info[f].w);
-        int rows[3], row_bytes[3];
-        const int np = overlay_surface_planes(dst[f].format, job.info[f].h, job.info[f].w, rows, row_bytes);
-        d_dst[f] = dst[f];
-        for (int p = 0; p < np; ++p) {
-            const size_t at = ((total + 15) & ~size_t(15)) + (reinterpret_cast<uintptr_t>(dst[f].plane[p]) & 15);
-            total = at + size_t(rows[p] - 1) * size_t(dst[f].pitch[p]) + size_t(row_bytes[p]);
-            planes.push_back({at, rows[p], row_bytes[p], dst[f].pitch[p], static_cast<uint8_t*>(dst[f].plane[p])});
-        }
+        out.add(dst[f], job.info[f].h, job.info[f].w);
     }
     const JpegClipPlan& plan = job.plan;
     TempBufs tmp;
     char* const d_work = static_cast<char*>(tmp.get(plan.bytes));
     int32_t* const d_status = static_cast<int32_t*>(tmp.get(size_t(nframes) * 2 * sizeof(int32_t)));
-    const GuardedOutput d_out(total, stream_);
-    {
-        size_t k = 0;
-        for (int f = 0; f < nframes; ++f) {
-            int rows[3], row_bytes[3];
-            const int np = overlay_surface_planes(dst[f].format, job.info[f].h, job.info[f].w, rows, row_bytes);
-            for (int p = 0; p < np; ++p) d_dst[f].plane[p] = d_out.frames() + planes[k++].off;
-        }
-    }
+    out.alloc(stream_);
     std::vector<uint8_t> stage(plan.upload_bytes + 256);
     uint8_t* const st = stage.data() + ((256 - (reinterpret_cast<uintptr_t>(stage.data()) & 255)) & 255);
     JpegDecArgs recs[MIXED_MAX_FRAMES];
     JpegProgArgs precs[MIXED_MAX_FRAMES];
-    jpeg_clip_stage(job, data, st, d_work, d_dst, channel_order, d_status, recs, precs);
+    jpeg_clip_stage(job, data, st, d_work, out.device(), channel_order, d_status, recs, precs);
     WHENET_HIP_CHECK(hipMemcpyAsync(d_work, st, plan.upload_bytes, hipMemcpyHostToDevice, stream_));
     jpeg_clip_launch(job, recs, precs, d_work, stream_);
-    const size_t none[1] = {0};
-    d_out.to_host(stream_, none, 0, nullptr, "op_jpeg_decode_clip");      // waits, checks the guard zones
-    std::vector<uint8_t> back(total), is_row(total, 0);
-    WHENET_HIP_CHECK(hipMemcpy(back.data(), d_out.frames(), total, hipMemcpyDeviceToHost));
-    for (const Plane& pl : planes)
-        for (int r = 0; r < pl.rows; ++r) {
-            const size_t at = pl.off + size_t(r) * size_t(pl.pitch);
-            std::memset(is_row.data() + at, 1, size_t(pl.row_bytes));
-            std::memcpy(pl.host + size_t(r) * size_t(pl.pitch), back.data() + at, size_t(pl.row_bytes));
-        }
-    for (size_t i = 0; i < total; ++i)
-        WHENET_REQUIRE(is_row[i] || back[i] == GuardedOutput::SENTINEL, WHENET_EHIP,
-                       "op_jpeg_decode_clip: the kernel wrote outside the rows of the surfaces (byte " + std::to_string(i) + ")");
+    out.to_host(stream_, "op_jpeg_decode_clip", "the surfaces");      // waits
     WHENET_HIP_CHECK(hipMemcpy(status, d_status, size_t(nframes) * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
 }
 

@@ -456,28 +456,6 @@ JpegDecScratch::JpegDecScratch(const JpegDecGeom& g, size_t data_bytes, long lon
     bytes = at;
 }
 
-JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
-                          const whenet_surface_t& dst, int channel_order, int32_t* d_status, int rule) {
-    JpegDecArgs a{};
-    char* const s = static_cast<char*>(d_scratch);
-    a.g = g;
-    a.tables = reinterpret_cast<const JpegDecTables*>(s + lay.tables);
-    a.data = d_data, a.nbytes = int(nbytes);
-    a.start = reinterpret_cast<int32_t*>(s + lay.start), a.meta = reinterpret_cast<int32_t*>(s + lay.meta);
-    a.coef = reinterpret_cast<int16_t*>(s + lay.coef);
-    for (int c = 0; c < 3; ++c) {
-        a.plane[c] = reinterpret_cast<uint8_t*>(s + lay.plane[c]);
-        a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
-    }
-    a.format = dst.format, a.channel_order = channel_order, a.rule = rule;
-    a.status = d_status;
-    a.form = lay.form, a.seg_bytes = lay.seg_bytes, a.seg_cap = int(lay.seg_cap), a.seg_lanes = lay.seg_lanes;
-    a.seg_stats = reinterpret_cast<long long*>(s + lay.seg_stats);
-    a.first_seg = reinterpret_cast<int32_t*>(s + lay.first_seg), a.seg_exit = reinterpret_cast<uint64_t*>(s + lay.seg_exit);
-    a.seg_count = reinterpret_cast<JpegSegCount*>(s + lay.seg_count), a.seg_blk = reinterpret_cast<int32_t*>(s + lay.seg_blk);
-    return a;
-}
-
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream) {
     const JpegDecGeom& g = a.g;
     check_jpeg_dec_args(a);

@@ -1,6 +1,7 @@
 // A clip of JPEG streams: where every frame's share of the upload block and of the work buffer lies, and in which entropy form it
-// runs.  One plan serves the engine (clip_begin_jpeg, op_jpeg_decode_clip) and whenet_jpeg_clip_plan, so the layout the kernels of
-// jpeg_dec.hip / jpeg_dec_seg.hip get is the one the CPU tests see.  Nothing here needs the HIP runtime: a plain C++17 compiler
+// runs.  One planner (jpeg_clip_plan_progressive; jpeg_clip_plan is it without scan plans) serves the engine (clip_begin_jpeg,
+// op_jpeg_decode_clip) and whenet_jpeg_clip_plan / whenet_jpeg_clip_plan_progressive, so the layout the kernels of jpeg_dec.hip /
+// jpeg_dec_seg.hip / jpeg_prog.hip get is the one the CPU tests see.  Nothing here needs the HIP runtime: a plain C++17 compiler
 // builds this header (tools/jpeg_dec_clip_host_check.cpp does, under the host sanitizers).
 //
 // Reference: demo_video.py:49-53 (`cap.read()` in a loop: consecutive frames of one MJPG file).
@@ -41,87 +42,16 @@ struct JpegClipPlan {
     size_t upload_bytes, bytes;
 };
 
-// entropy: 0, 1 or 2 (auto), applied to every stream alone; seg_bytes: a power of two in 4..4096.  nullptr, or what is wrong.
-inline const char* jpeg_clip_plan(const JpegDecGeom* g, const int64_t* nbytes, int frames, int entropy, int seg_bytes, JpegClipPlan& p) {
-    if (g == nullptr || nbytes == nullptr) return "NULL argument";
-    if (frames < 1 || frames > JPEG_CLIP_MAX_FRAMES) return "a clip holds 1..16 frames";
-    if (entropy < 0 || entropy > 2) return "entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto)";
-    if (!jpeg_seg_bytes_ok(seg_bytes)) return "seg_bytes must be a power of two in 4..4096";
-    for (int f = 0; f < frames; ++f) {
-        if (nbytes[f] < 0 || nbytes[f] > JPEG_DEC_MAX_BYTES) return "nbytes must be 0..2^31 - 1";
-        if (g[f].intervals < 1 || g[f].mcu_cols < 1 || g[f].mcu_rows < 1 || g[f].bpm < 1 || g[f].comps < 1 || g[f].comps > 3) return "bad geometry";
-    }
-    const auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    p = JpegClipPlan{};
-    p.frames = frames;
-    size_t at = 0;
-    const auto take = [&](JpegClipRegion& r, size_t len) { r.off = at, r.len = len, at = up(at + len); };
-    take(p.records, size_t(frames) * JPEG_CLIP_RECORD_BYTES);
-    for (int f = 0; f < frames; ++f) {
-        JpegClipFrame& q = p.f[f];
-        q.form = jpeg_dec_form(entropy, nbytes[f], g[f].intervals);
-        q.seg_bytes = q.form == 1 ? seg_bytes : 0;
-        q.seg_cap = q.form == 1 ? jpeg_seg_bound(nbytes[f], g[f].intervals, seg_bytes) : 0;
-        if (q.seg_cap >= 0x7FFFFFFF) return "more segments than an int32 counts";
-        ++p.forms[q.form];
-        take(q.tables, sizeof(JpegDecTables));
-        take(q.data, size_t(nbytes[f]));
-    }
-    p.upload_bytes = at;
-    p.zero.off = at;
-    for (int f = 0; f < frames; ++f) {
-        JpegClipFrame& q = p.f[f];
-        take(q.start, size_t(g[f].intervals) * sizeof(int32_t));
-        q.meta = {at, 64}, q.seg_stats = {at + 64, 8 * sizeof(int64_t)}, at = up(at + 128);
-    }
-    for (int f = 0; f < frames; ++f)
-        take(p.f[f].coef, size_t(g[f].mcu_cols) * size_t(g[f].mcu_rows) * size_t(g[f].bpm) * 64 * sizeof(int16_t));
-    p.zero.len = at - p.zero.off;
-    for (int f = 0; f < frames; ++f)
-        for (int c = 0; c < 3; ++c) {
-            if (c < g[f].comps) take(p.f[f].plane[c], size_t(g[f].plane_pitch[c]) * size_t(g[f].plane_rows[c]));
-            else p.f[f].plane[c] = {at, 0};
-        }
-    for (int f = 0; f < frames; ++f) {
-        JpegClipFrame& q = p.f[f];
-        if (q.form == 1) {
-            take(q.first_seg, (size_t(g[f].intervals) + 1) * sizeof(int32_t));
-            take(q.seg_exit, size_t(q.seg_cap) * sizeof(uint64_t));
-            take(q.seg_count, size_t(q.seg_cap) * sizeof(JpegSegCount));
-            take(q.seg_blk, size_t(q.seg_cap) * 4 * sizeof(int32_t));
-        } else {
-            q.first_seg = q.seg_exit = q.seg_count = q.seg_blk = {at, 0};
-        }
-    }
-    p.bytes = at;
-    return nullptr;
-}
-
-// the plan as whenet_jpeg_clip_plan hands it out: frames * 32 + 8 words
-inline void jpeg_clip_plan_words(const JpegClipPlan& p, int64_t* out) {
-    for (int f = 0; f < p.frames; ++f) {
-        const JpegClipFrame& q = p.f[f];
-        int64_t* o = out + size_t(f) * JPEG_CLIP_PLAN_FRAME_WORDS;
-        o[0] = q.form, o[1] = q.seg_bytes, o[2] = q.seg_cap, o[3] = 0;
-        const JpegClipRegion* r[13] = {&q.tables,   &q.data,     &q.start,     &q.meta,     &q.seg_stats, &q.coef,   &q.plane[0],
-                                       &q.plane[1], &q.plane[2], &q.first_seg, &q.seg_exit, &q.seg_count, &q.seg_blk};
-        for (int k = 0; k < 13; ++k) o[4 + 2 * k] = int64_t(r[k]->off), o[5 + 2 * k] = int64_t(r[k]->len);
-        o[30] = o[31] = 0;
-    }
-    int64_t* t = out + size_t(p.frames) * JPEG_CLIP_PLAN_FRAME_WORDS;
-    t[0] = int64_t(p.records.off), t[1] = int64_t(p.records.len), t[2] = int64_t(p.upload_bytes), t[3] = int64_t(p.zero.off);
-    t[4] = int64_t(p.zero.len), t[5] = int64_t(p.bytes), t[6] = p.forms[0], t[7] = p.forms[1];
-}
-
-// ---- clips that may hold PROGRESSIVE streams (jpeg_prog_host.h): a second plan, the first one stays as it is ----
+// ---- clips that may hold PROGRESSIVE streams (jpeg_prog_host.h): the same planner, with a scan plan per such frame ----
 // A frame is baseline (its JpegProgPlan is nullptr or says `baseline`: laid out as above, in the form the rule gives it alone) or
 // progressive (form JPEG_CLIP_FORM_PROGRESSIVE).  The same three blocks:
 //   upload block   records | per frame: tables | data, or, progressive: scans | huff | qz | items | data (what jpeg_prog_stage
 //                  writes for the stream alone; list_off / level_off stay indices into the frame's OWN item list)   -- ONE H2D
 //   zeroed bytes   per frame: start | meta | seg_stats, or meta; then per frame: coef, or, progressive: the raw coefficients -- ONE memset
 //   work           per progressive frame: its finished coef; per frame: the planes; per frame of form 1: the segmented regions
-// A clip without a progressive frame gets, region for region, the plan above.  A frame's progressive record (JpegProgArgs) lies in
-// the frame's own argument record, JPEG_CLIP_PROG_RECORD_OFFSET bytes behind its start (checked in jpeg_prog.hip).
+// A clip without a progressive frame gets the layout at the head of this file: jpeg_clip_plan is this planner called without
+// plans.  A frame's progressive record (JpegProgArgs) lies in the frame's own argument record, JPEG_CLIP_PROG_RECORD_OFFSET bytes
+// behind its start (checked in jpeg_prog.hip).
 constexpr int JPEG_CLIP_FORM_PROGRESSIVE = 2;
 constexpr int JPEG_CLIP_PROG_RECORD_OFFSET = 320;
 constexpr int JPEG_CLIP_PROG_PLAN_FRAME_WORDS = 48;      // whenet_jpeg_clip_plan_progressive: the 32 words above + 16 ...
@@ -142,22 +72,33 @@ struct JpegClipProgPlan {
 
 inline bool jpeg_clip_is_progressive(const JpegProgPlan* plan) { return plan != nullptr && !plan->baseline; }
 
-// nbytes[f] is read for baseline frames only; prog may be nullptr (no progressive frame).  nullptr, or what is wrong.
-inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_t* nbytes, const JpegProgPlan* const* prog, int frames, int entropy,
-                                              int seg_bytes, JpegClipProgPlan& pp) {
+// what both planners refuse first, and the two per-frame checks each of them makes in its own order
+inline const char* jpeg_clip_check_args(const JpegDecGeom* g, const int64_t* nbytes, int frames, int entropy, int seg_bytes) {
     if (g == nullptr || nbytes == nullptr) return "NULL argument";
     if (frames < 1 || frames > JPEG_CLIP_MAX_FRAMES) return "a clip holds 1..16 frames";
     if (entropy < 0 || entropy > 2) return "entropy must be 0 (an interval per lane), 1 (segmented) or 2 (auto)";
     if (!jpeg_seg_bytes_ok(seg_bytes)) return "seg_bytes must be a power of two in 4..4096";
+    return nullptr;
+}
+inline bool jpeg_clip_nbytes_ok(int64_t nbytes) { return nbytes >= 0 && nbytes <= JPEG_DEC_MAX_BYTES; }
+inline bool jpeg_clip_geom_ok(const JpegDecGeom& g) {
+    return g.intervals >= 1 && g.mcu_cols >= 1 && g.mcu_rows >= 1 && g.bpm >= 1 && g.comps >= 1 && g.comps <= 3;
+}
+
+// entropy: 0, 1 or 2 (auto), applied to every baseline stream alone; seg_bytes: a power of two in 4..4096.  nbytes[f] is read for
+// baseline frames only; prog may be nullptr (no progressive frame).  nullptr, or what is wrong.
+inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_t* nbytes, const JpegProgPlan* const* prog, int frames, int entropy,
+                                              int seg_bytes, JpegClipProgPlan& pp) {
+    if (const char* bad = jpeg_clip_check_args(g, nbytes, frames, entropy, seg_bytes)) return bad;
     const auto is_prog = [&](int f) { return prog != nullptr && jpeg_clip_is_progressive(prog[f]); };
     for (int f = 0; f < frames; ++f) {
-        if (g[f].intervals < 1 || g[f].mcu_cols < 1 || g[f].mcu_rows < 1 || g[f].bpm < 1 || g[f].comps < 1 || g[f].comps > 3) return "bad geometry";
+        if (!jpeg_clip_geom_ok(g[f])) return "bad geometry";
         if (is_prog(f)) {
             const JpegProgPlan& s = *prog[f];
             if (s.dev.empty() || s.huff.size() != 3 * s.dev.size() || s.items.empty() || s.items.size() % JPEG_PROG_LANES != 0 || s.levels < 1 ||
                 s.level_off.size() != size_t(s.levels) || s.level_cnt.size() != size_t(s.levels) || s.data_bytes < 0 || s.data_bytes > JPEG_DEC_MAX_BYTES)
                 return "not the plan of a progressive stream";
-        } else if (nbytes[f] < 0 || nbytes[f] > JPEG_DEC_MAX_BYTES) {
+        } else if (!jpeg_clip_nbytes_ok(nbytes[f])) {
             return "nbytes must be 0..2^31 - 1";
         }
     }
@@ -240,6 +181,35 @@ inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_
     return nullptr;
 }
 
+// A clip of baseline streams: the planner above without plans (its own order of the per-frame checks: nbytes first)
+inline const char* jpeg_clip_plan(const JpegDecGeom* g, const int64_t* nbytes, int frames, int entropy, int seg_bytes, JpegClipPlan& p) {
+    if (const char* bad = jpeg_clip_check_args(g, nbytes, frames, entropy, seg_bytes)) return bad;
+    for (int f = 0; f < frames; ++f) {
+        if (!jpeg_clip_nbytes_ok(nbytes[f])) return "nbytes must be 0..2^31 - 1";
+        if (!jpeg_clip_geom_ok(g[f])) return "bad geometry";
+    }
+    JpegClipProgPlan pp;
+    const char* bad = jpeg_clip_plan_progressive(g, nbytes, nullptr, frames, entropy, seg_bytes, pp);
+    p = pp.base;
+    return bad;
+}
+
+// the plan as whenet_jpeg_clip_plan hands it out: frames * 32 + 8 words (frame_words: the stride of a frame's words)
+inline void jpeg_clip_plan_words(const JpegClipPlan& p, int64_t* out, int frame_words = JPEG_CLIP_PLAN_FRAME_WORDS) {
+    for (int f = 0; f < p.frames; ++f) {
+        const JpegClipFrame& q = p.f[f];
+        int64_t* o = out + size_t(f) * size_t(frame_words);
+        o[0] = q.form, o[1] = q.seg_bytes, o[2] = q.seg_cap, o[3] = 0;
+        const JpegClipRegion* r[13] = {&q.tables,   &q.data,     &q.start,     &q.meta,     &q.seg_stats, &q.coef,   &q.plane[0],
+                                       &q.plane[1], &q.plane[2], &q.first_seg, &q.seg_exit, &q.seg_count, &q.seg_blk};
+        for (int k = 0; k < 13; ++k) o[4 + 2 * k] = int64_t(r[k]->off), o[5 + 2 * k] = int64_t(r[k]->len);
+        o[30] = o[31] = 0;
+    }
+    int64_t* t = out + size_t(p.frames) * size_t(frame_words);
+    t[0] = int64_t(p.records.off), t[1] = int64_t(p.records.len), t[2] = int64_t(p.upload_bytes), t[3] = int64_t(p.zero.off);
+    t[4] = int64_t(p.zero.len), t[5] = int64_t(p.bytes), t[6] = p.forms[0], t[7] = p.forms[1];
+}
+
 // a progressive frame's share of the upload block into `stage` (the block's first byte; data: the stream's bytes from
 // plan.data_base on): the content jpeg_prog_stage writes, the padding between the regions zeroed
 inline void jpeg_clip_stage_progressive(const JpegProgPlan& plan, const JpegClipFrame& q, const JpegClipProgFrame& r, const uint8_t* data,
@@ -257,24 +227,17 @@ inline void jpeg_clip_stage_progressive(const JpegProgPlan& plan, const JpegClip
 // raw; 42: its scans, 43: its levels, 44: the entries of its item list; 45..47: 0.  Totals 8: the progressive frames, 9: the
 // scan-kernel launches, 10: the stride of the argument records, 11: where a frame's progressive record lies in its own; 12..15: 0.
 inline void jpeg_clip_plan_progressive_words(const JpegClipProgPlan& pp, int64_t* out) {
-    const JpegClipPlan& p = pp.base;
-    for (int f = 0; f < p.frames; ++f) {
-        const JpegClipFrame& q = p.f[f];
+    jpeg_clip_plan_words(pp.base, out, JPEG_CLIP_PROG_PLAN_FRAME_WORDS);
+    for (int f = 0; f < pp.base.frames; ++f) {
         const JpegClipProgFrame& x = pp.pf[f];
-        int64_t* o = out + size_t(f) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS;
-        o[0] = q.form, o[1] = q.seg_bytes, o[2] = q.seg_cap, o[3] = 0;
-        const JpegClipRegion* r[18] = {&q.tables,    &q.data,     &q.start,     &q.meta,    &q.seg_stats, &q.coef, &q.plane[0], &q.plane[1], &q.plane[2],
-                                       &q.first_seg, &q.seg_exit, &q.seg_count, &q.seg_blk, &x.scans,     &x.huff, &x.qz,       &x.items,    &x.raw};
-        for (int k = 0; k < 13; ++k) o[4 + 2 * k] = int64_t(r[k]->off), o[5 + 2 * k] = int64_t(r[k]->len);
-        o[30] = o[31] = 0;
-        for (int k = 13; k < 18; ++k) o[6 + 2 * k] = int64_t(r[k]->off), o[7 + 2 * k] = int64_t(r[k]->len);
-        o[42] = x.nscans, o[43] = x.levels, o[44] = x.list, o[45] = o[46] = o[47] = 0;
+        int64_t* o = out + size_t(f) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS + JPEG_CLIP_PLAN_FRAME_WORDS;
+        const JpegClipRegion* r[5] = {&x.scans, &x.huff, &x.qz, &x.items, &x.raw};
+        for (int k = 0; k < 5; ++k) o[2 * k] = int64_t(r[k]->off), o[2 * k + 1] = int64_t(r[k]->len);
+        o[10] = x.nscans, o[11] = x.levels, o[12] = x.list, o[13] = o[14] = o[15] = 0;
     }
-    int64_t* t = out + size_t(p.frames) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS;
-    t[0] = int64_t(p.records.off), t[1] = int64_t(p.records.len), t[2] = int64_t(p.upload_bytes), t[3] = int64_t(p.zero.off);
-    t[4] = int64_t(p.zero.len), t[5] = int64_t(p.bytes), t[6] = p.forms[0], t[7] = p.forms[1];
-    t[8] = pp.progressive, t[9] = pp.scan_launches, t[10] = JPEG_CLIP_RECORD_BYTES, t[11] = JPEG_CLIP_PROG_RECORD_OFFSET;
-    t[12] = t[13] = t[14] = t[15] = 0;
+    int64_t* t = out + size_t(pp.base.frames) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS + JPEG_CLIP_PLAN_TOTAL_WORDS;
+    t[0] = pp.progressive, t[1] = pp.scan_launches, t[2] = JPEG_CLIP_RECORD_BYTES, t[3] = JPEG_CLIP_PROG_RECORD_OFFSET;
+    t[4] = t[5] = t[6] = t[7] = 0;
 }
 
 }  // namespace whenet

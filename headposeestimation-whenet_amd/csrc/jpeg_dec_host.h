@@ -2,6 +2,8 @@
 // whenet_jpeg_decode_planes_host) and the kernels of jpeg_dec.hip: the marker parser, the decode tables of a DHT, the bit reader,
 // the Huffman decode of a block, the inverse DCT and the planes -> pixel rule, each exactly as include/whenet_hip.h states it
 // (JPEG DECODER), and for rule 1 (libjpeg's bytes) jidctint's pass, the fancy upsampling and jdcolor's row (JPEG DECODER, RULE 1).
+// The marker walk, the SOF / DQT / DHT readers and the builder of a decode table are written once here: the progressive parser
+// (jpeg_prog_host.h) walks the same grammar with them.
 // Integers only.  Nothing here needs the HIP runtime: a plain C++17 compiler builds this header
 // (tools/jpeg_dec_host_check.cpp does, under the host sanitizers).
 //
@@ -60,6 +62,113 @@ inline JpegDecGeom jpeg_dec_geom(const whenet_jpeg_info_t& in) {
     return g;
 }
 
+// ---- the segment readers (pure host): one grammar for jpeg_parse below and jpeg_prog_parse (jpeg_prog_host.h) ----
+// Each returns nullptr, or the reason the stream is refused.  The order of the checks is part of the contract: it decides which
+// text a stream with two defects gets (tests/test_jpeg_parse_pins_cpu.py).
+
+// One step of the marker walk: the segment at p, fill bytes skipped, as its marker m and the n bytes s behind its length; p ends up
+// behind the segment.  scanned: behind the first scan of a progressive stream EOI or the end of the bytes ends the stream (an
+// incomplete progression is decoded from what it holds): m = 0xD9 then.
+inline const char* jpeg_next_segment(const uint8_t* d, int64_t size, bool scanned, int64_t& p, int& m, const uint8_t*& s, int& n) {
+    m = 0xD9;
+    for (;; ++p) {
+        if (p + 2 > size) return scanned ? nullptr : "the header ends before SOS (truncated)";
+        if (d[p] != 0xFF) return "a marker is expected in the header";
+        if (d[p + 1] != 0xFF) break;      // (0xFF 0xFF: a fill byte)
+    }
+    const int marker = d[p + 1];
+    p += 2;
+    if (marker == 0xD8 || marker == 0x01 || (marker >= 0xD0 && marker <= 0xD7)) return "an unexpected marker without a segment in the header";
+    if (marker == 0xD9) return scanned ? nullptr : "EOI before SOS: the stream has no scan";
+    if (p + 2 > size) return scanned ? nullptr : "the header ends before SOS (truncated)";
+    const int len = (d[p] << 8) | d[p + 1];
+    if (len < 2 || p + len > size) return scanned ? nullptr : "a segment passes the end of the stream (truncated)";
+    m = marker, s = d + p + 2, n = len - 2, p += len;
+    return nullptr;
+}
+
+// SOF0, or SOF2 (sof2: the name in the texts): the frame into `in`, its component ids into comp_id
+inline const char* jpeg_read_sof(const uint8_t* s, int n, bool sof2, whenet_jpeg_info_t& in, int comp_id[3]) {
+    if (n < 6) return sof2 ? "a short SOF2" : "a short SOF0";
+    if (s[0] == 12) return "12-bit samples: 8-bit streams only";
+    if (s[0] != 8) return "the sample precision is not 8 bit";
+    in.h = (s[1] << 8) | s[2], in.w = (s[3] << 8) | s[4], in.components = s[5];
+    if (in.components == 4) return "4 components (CMYK / YCCK): 1 or 3 only";
+    if (in.components != 1 && in.components != 3) return "the frame must have 1 or 3 components";
+    if (in.h < 1 || in.w < 1 || in.h > JPEG_MAX_SIDE || in.w > JPEG_MAX_SIDE) return "frame sides must be 1..8192";
+    if (n != 6 + 3 * in.components) return sof2 ? "the length of SOF2 does not match its components" : "the length of SOF0 does not match its components";
+    for (int c = 0; c < in.components; ++c) {
+        comp_id[c] = s[6 + 3 * c];
+        const int hv = s[7 + 3 * c], tq = s[8 + 3 * c];
+        if (tq > 3) return "a quantiser id above 3";
+        in.qt[c] = tq;
+        if (in.components == 1) {
+            in.hs = in.vs = 1;      // one component: the MCU is one block whatever the factors say
+        } else if (c == 0) {
+            if (hv != 0x22 && hv != 0x21 && hv != 0x11) return "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
+            in.hs = hv >> 4, in.vs = hv & 15;
+        } else if (hv != 0x11) {
+            return "chroma sampling must be 1x1";
+        }
+    }
+    return nullptr;
+}
+
+// DQT: its tables into in.q (natural order)
+inline const char* jpeg_read_dqt(const uint8_t* s, int n, whenet_jpeg_info_t& in) {
+    for (int i = 0; i < n; i += 65) {
+        const int pq = s[i] >> 4, tq = s[i] & 15;
+        if (pq != 0) return "a 16-bit quantiser table (DQT): 8-bit tables only";
+        if (tq > 3) return "a quantiser id above 3";
+        if (i + 65 > n) return "a short DQT";
+        for (int k = 0; k < 64; ++k) {
+            if (s[i + 1 + k] == 0) return "a quantiser of 0";
+            in.q[tq][JPEG_ZIGZAG[k]] = s[i + 1 + k];
+        }
+        in.q_present[tq] = 1;
+    }
+    return nullptr;
+}
+
+// The 16 code-length counts of a Huffman table: the symbols they count, or -1 where they are no prefix code
+inline int jpeg_huff_symbols(const uint8_t counts[16]) {
+    int total = 0;
+    unsigned code = 0;
+    for (int l = 1; l <= 16; ++l) {
+        total += counts[l - 1], code += counts[l - 1];
+        if (code > (1u << l)) return -1;
+        code <<= 1;
+    }
+    return total;
+}
+// a DC table's symbols are the categories 0..11
+inline bool jpeg_huff_dc_symbols_ok(const uint8_t* values, int total) {
+    for (int k = 0; k < total; ++k)
+        if (values[k] > 11) return false;
+    return true;
+}
+
+// DHT: its tables into counts / values / present at index 2 id + class (the order of JpegDecTables::huff); ids 0..max_id
+inline const char* jpeg_read_dht(const uint8_t* s, int n, int max_id, uint8_t (*counts)[16], uint8_t (*values)[256], uint8_t* present) {
+    for (int i = 0; i < n;) {
+        const int tc = s[i] >> 4, th = s[i] & 15;
+        if (tc > 1 || th > max_id)
+            return max_id == 1 ? "a Huffman table class or id above 1 (baseline: ids 0..1)" : "a Huffman table class above 1 or id above 3";
+        if (i + 17 > n) return "a short DHT";
+        const int tb = 2 * th + tc;
+        const int total = jpeg_huff_symbols(s + i + 1);
+        if (total < 0) return "a DHT whose code lengths are no prefix code";
+        if (total > 256 || i + 17 + total > n) return "a short DHT";
+        std::memcpy(counts[tb], s + i + 1, 16);
+        std::memset(values[tb], 0, 256);
+        std::memcpy(values[tb], s + i + 17, size_t(total));
+        if (tc == 0 && !jpeg_huff_dc_symbols_ok(values[tb], total)) return "a DC Huffman symbol above 11";
+        present[tb] = 1;
+        i += 17 + total;
+    }
+    return nullptr;
+}
+
 // ---- parse (pure host) ----
 // SOI .. SOS into `in`; returns nullptr, or the reason the stream is refused.
 inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in) {
@@ -70,21 +179,10 @@ inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t
     bool sof = false;
     int comp_id[3] = {0, 0, 0};
     for (;;) {
-        if (p + 2 > size) return "the header ends before SOS (truncated)";
-        if (d[p] != 0xFF) return "a marker is expected in the header";
-        int m = d[p + 1];
-        if (m == 0xFF) {      // fill byte
-            ++p;
-            continue;
-        }
-        p += 2;
-        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) return "an unexpected marker without a segment in the header";
-        if (m == 0xD9) return "EOI before SOS: the stream has no scan";
-        if (p + 2 > size) return "the header ends before SOS (truncated)";
-        const int len = (d[p] << 8) | d[p + 1];
-        if (len < 2 || p + len > size) return "a segment passes the end of the stream (truncated)";
-        const uint8_t* s = d + p + 2;
-        const int n = len - 2;
+        int m, n;
+        const uint8_t* s;
+        const char* bad = jpeg_next_segment(d, size, false, p, m, s, n);
+        if (bad != nullptr) return bad;
         if (m == 0xC2) return "progressive DCT (SOF2): baseline sequential streams only";
         if (m == 0xC1) return "extended sequential DCT (SOF1): baseline sequential streams only";
         if (m == 0xC3 || (m >= 0xC5 && m <= 0xC7)) return "a lossless, differential or hierarchical frame (SOF3, SOF5-7): baseline only";
@@ -92,66 +190,12 @@ inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t
         if (m == 0xC8) return "a reserved marker (JPG)";
         if (m == 0xC0) {
             if (sof) return "a second SOF0";
-            if (n < 6) return "a short SOF0";
-            if (s[0] == 12) return "12-bit samples: 8-bit streams only";
-            if (s[0] != 8) return "the sample precision is not 8 bit";
-            in.h = (s[1] << 8) | s[2], in.w = (s[3] << 8) | s[4], in.components = s[5];
-            if (in.components == 4) return "4 components (CMYK / YCCK): 1 or 3 only";
-            if (in.components != 1 && in.components != 3) return "the frame must have 1 or 3 components";
-            if (in.h < 1 || in.w < 1 || in.h > JPEG_MAX_SIDE || in.w > JPEG_MAX_SIDE) return "frame sides must be 1..8192";
-            if (n != 6 + 3 * in.components) return "the length of SOF0 does not match its components";
-            for (int c = 0; c < in.components; ++c) {
-                comp_id[c] = s[6 + 3 * c];
-                const int hv = s[7 + 3 * c], tq = s[8 + 3 * c];
-                if (tq > 3) return "a quantiser id above 3";
-                in.qt[c] = tq;
-                if (in.components == 1) {
-                    in.hs = in.vs = 1;      // one component: the MCU is one block whatever the factors say
-                } else if (c == 0) {
-                    if (hv != 0x22 && hv != 0x21 && hv != 0x11) return "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
-                    in.hs = hv >> 4, in.vs = hv & 15;
-                } else if (hv != 0x11) {
-                    return "chroma sampling must be 1x1";
-                }
-            }
+            bad = jpeg_read_sof(s, n, false, in, comp_id);
             sof = true;
         } else if (m == 0xDB) {
-            for (int i = 0; i < n;) {
-                const int pq = s[i] >> 4, tq = s[i] & 15;
-                if (pq != 0) return "a 16-bit quantiser table (DQT): 8-bit tables only";
-                if (tq > 3) return "a quantiser id above 3";
-                if (i + 65 > n) return "a short DQT";
-                for (int k = 0; k < 64; ++k) {
-                    if (s[i + 1 + k] == 0) return "a quantiser of 0";
-                    in.q[tq][JPEG_ZIGZAG[k]] = s[i + 1 + k];
-                }
-                in.q_present[tq] = 1;
-                i += 65;
-            }
+            bad = jpeg_read_dqt(s, n, in);
         } else if (m == 0xC4) {
-            for (int i = 0; i < n;) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                if (tc > 1 || th > 1) return "a Huffman table class or id above 1 (baseline: ids 0..1)";
-                if (i + 17 > n) return "a short DHT";
-                const int tb = 2 * th + tc;
-                int total = 0;
-                unsigned code = 0;
-                for (int l = 1; l <= 16; ++l) {
-                    const int cnt = s[i + l];
-                    total += cnt, code += unsigned(cnt);
-                    if (code > (1u << l)) return "a DHT whose code lengths are no prefix code";
-                    code <<= 1;
-                }
-                if (total > 256 || i + 17 + total > n) return "a short DHT";
-                std::memcpy(in.huff_counts[tb], s + i + 1, 16);
-                std::memset(in.huff_values[tb], 0, 256);
-                std::memcpy(in.huff_values[tb], s + i + 17, size_t(total));
-                if (tc == 0)
-                    for (int k = 0; k < total; ++k)
-                        if (in.huff_values[tb][k] > 11) return "a DC Huffman symbol above 11";
-                in.huff_present[tb] = 1;
-                i += 17 + total;
-            }
+            bad = jpeg_read_dht(s, n, 1, in.huff_counts, in.huff_values, in.huff_present);
         } else if (m == 0xDD) {
             if (n != 2) return "a DRI of the wrong length";
             in.restart_interval = (s[0] << 8) | s[1];
@@ -172,16 +216,13 @@ inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t
                 if (!in.q_present[in.qt[c]]) return "a missing quantiser table (DQT)";
                 if (!in.huff_present[2 * in.dc[c]] || !in.huff_present[2 * in.ac[c] + 1]) return "a missing Huffman table (DHT)";
             }
-            in.data_offset = p + len;
-            const JpegDecGeom g = jpeg_dec_geom(in);
-            in.intervals = g.intervals;
+            in.data_offset = p;
+            in.intervals = jpeg_dec_geom(in).intervals;
             return nullptr;
-        } else if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
-            // APPn, COM: skipped
-        } else {
+        } else if (!((m >= 0xE0 && m <= 0xEF) || m == 0xFE)) {      // (APPn, COM: skipped)
             return "an unexpected marker in the header";
         }
-        p += len;
+        if (bad != nullptr) return bad;
     }
 }
 
@@ -200,46 +241,43 @@ inline const char* jpeg_dec_check_info(const whenet_jpeg_info_t& in) {
     }
     for (int tb = 0; tb < 4; ++tb) {
         if (!in.huff_present[tb]) continue;
-        int total = 0;
-        unsigned code = 0;
-        for (int l = 1; l <= 16; ++l) {
-            total += in.huff_counts[tb][l - 1], code += in.huff_counts[tb][l - 1];
-            if (code > (1u << l)) return "a Huffman table whose code lengths are no prefix code";
-            code <<= 1;
-        }
+        const int total = jpeg_huff_symbols(in.huff_counts[tb]);
+        if (total < 0) return "a Huffman table whose code lengths are no prefix code";
         if (total > 256) return "a Huffman table of more than 256 symbols";
-        if ((tb & 1) == 0)
-            for (int k = 0; k < total; ++k)
-                if (in.huff_values[tb][k] > 11) return "a DC Huffman symbol above 11";
+        if ((tb & 1) == 0 && !jpeg_huff_dc_symbols_ok(in.huff_values[tb], total)) return "a DC Huffman symbol above 11";
     }
     if (in.intervals != jpeg_dec_geom(in).intervals) return "the interval count is not that of the size, the sampling and the restart interval";
     return nullptr;
 }
 
 // ---- decode tables (pure host) ----
+// One table as the decoder reads it, from the 16 counts and the symbols of its DHT
+inline void jpeg_dec_build_huff(const uint8_t counts[16], const uint8_t values[256], JpegDecHuff& h) {
+    std::memset(&h, 0, sizeof(h));
+    std::memcpy(h.vals, values, 256);
+    unsigned code = 0;
+    int n = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int cnt = counts[l - 1];
+        h.valoff[l] = n - int(code);
+        h.maxcode[l] = cnt > 0 ? int(code) + cnt - 1 : -1;
+        for (int i = 0; i < cnt; ++i, ++n, ++code)
+            if (l <= JPEG_DEC_LOOK_BITS) {
+                const int first = int(code) << (JPEG_DEC_LOOK_BITS - l);
+                for (int j = 0; j < (1 << (JPEG_DEC_LOOK_BITS - l)); ++j) h.look[first + j] = uint16_t((l << 8) | h.vals[n]);
+            }
+        code <<= 1;
+    }
+    h.maxcode[0] = -1, h.valoff[0] = 0;
+}
+
 inline void jpeg_dec_build_tables(const whenet_jpeg_info_t& in, JpegDecTables& t) {
+    static const uint8_t no_codes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // an absent table
     std::memset(&t, 0, sizeof(t));
     for (int i = 0; i < 4; ++i)
         for (int k = 0; k < 64; ++k) t.q[i][k] = int16_t(in.q[i][k]);
     for (int k = 0; k < 64; ++k) t.zz[k] = JPEG_ZIGZAG[k];
-    for (int tb = 0; tb < 4; ++tb) {
-        JpegDecHuff& h = t.huff[tb];
-        std::memcpy(h.vals, in.huff_values[tb], 256);
-        unsigned code = 0;
-        int n = 0;
-        for (int l = 1; l <= 16; ++l) {
-            const int cnt = in.huff_present[tb] ? in.huff_counts[tb][l - 1] : 0;
-            h.valoff[l] = n - int(code);
-            h.maxcode[l] = cnt > 0 ? int(code) + cnt - 1 : -1;
-            for (int i = 0; i < cnt; ++i, ++n, ++code)
-                if (l <= JPEG_DEC_LOOK_BITS) {
-                    const int first = int(code) << (JPEG_DEC_LOOK_BITS - l);
-                    for (int j = 0; j < (1 << (JPEG_DEC_LOOK_BITS - l)); ++j) h.look[first + j] = uint16_t((l << 8) | h.vals[n]);
-                }
-            code <<= 1;
-        }
-        h.maxcode[0] = -1, h.valoff[0] = 0;
-    }
+    for (int tb = 0; tb < 4; ++tb) jpeg_dec_build_huff(in.huff_present[tb] ? in.huff_counts[tb] : no_codes, in.huff_values[tb], t.huff[tb]);
 }
 
 // ---- the bit reader (host and device) ----

@@ -56,29 +56,11 @@ struct JpegProgPlan {
     int64_t data_base = 0, data_bytes = 0;     // the stream's bytes [data_base, data_base + data_bytes): every scan's entropy data
 };
 
-inline void jpeg_prog_build_huff(const uint8_t counts[16], const uint8_t values[256], JpegDecHuff& h) {
-    std::memset(&h, 0, sizeof(h));
-    std::memcpy(h.vals, values, 256);
-    unsigned code = 0;
-    int n = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int cnt = counts[l - 1];
-        h.valoff[l] = n - int(code);
-        h.maxcode[l] = cnt > 0 ? int(code) + cnt - 1 : -1;
-        for (int i = 0; i < cnt; ++i, ++n, ++code)
-            if (l <= JPEG_DEC_LOOK_BITS) {
-                const int first = int(code) << (JPEG_DEC_LOOK_BITS - l);
-                for (int j = 0; j < (1 << (JPEG_DEC_LOOK_BITS - l)); ++j) h.look[first + j] = uint16_t((l << 8) | h.vals[n]);
-            }
-        code <<= 1;
-    }
-    h.maxcode[0] = -1, h.valoff[0] = 0;
-}
-
 // ---- parse (pure host) ----
 // SOI .. the last scan into `in` and `plan`; returns nullptr, or the reason the stream is refused.  A SOF0 stream is jpeg_parse's
 // (plan.baseline, one scan record).  For SOF2 `in` holds the frame, the quantisers and the first scan's data_offset and DRI; its
-// Huffman fields stay empty (the tables change between scans: they are the plan's).
+// Huffman fields stay empty (the tables change between scans: they are the plan's).  The walk and the SOF / DQT / DHT readers are
+// jpeg_dec_host.h's, shared with jpeg_parse.
 inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in, JpegProgPlan& plan) {
     plan = JpegProgPlan();
     std::memset(&in, 0, sizeof(in));
@@ -115,8 +97,8 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             return nullptr;
         }
     }
-    uint8_t hc[2][4][16], hv[2][4][256];      // the Huffman tables in force: [class][id]
-    bool hp[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    uint8_t hc[8][16], hv[8][256];            // the Huffman tables in force, at index 2 id + class
+    uint8_t hp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int dht_seen = 0;
     int cur_al[3][64];                        // per component and coefficient: -1 (no scan yet) or the Al it has reached
     for (auto& c : cur_al)
@@ -127,101 +109,25 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
     JpegDecGeom g{};
     int64_t p = 2;
     for (;;) {
+        int m, n;
+        const uint8_t* s;
         const bool scanned = !plan.dev.empty();
-        // behind the first scan the end of the bytes ends the stream (an incomplete progression is decoded from what it holds)
-        if (p + 2 > size) {
-            if (scanned) break;
-            return "the header ends before SOS (truncated)";
-        }
-        if (d[p] != 0xFF) return "a marker is expected in the header";
-        const int m = d[p + 1];
-        if (m == 0xFF) {
-            ++p;
-            continue;
-        }
-        p += 2;
-        if (m == 0xD9) {
-            if (scanned) break;
-            return "EOI before SOS: the stream has no scan";
-        }
-        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) return "an unexpected marker without a segment in the header";
-        if (p + 2 > size) {
-            if (scanned) break;
-            return "the header ends before SOS (truncated)";
-        }
-        const int len = (d[p] << 8) | d[p + 1];
-        if (len < 2 || p + len > size) {
-            if (scanned) break;
-            return "a segment passes the end of the stream (truncated)";
-        }
-        const uint8_t* s = d + p + 2;
-        const int n = len - 2;
+        const char* refused = jpeg_next_segment(d, size, scanned, p, m, s, n);
+        if (refused != nullptr) return refused;
+        if (m == 0xD9) break;      // (behind the first scan: EOI, or the end of the bytes)
         if (m == 0xC2) {
             if (sof) return "a second SOF2";
-            if (n < 6) return "a short SOF2";
-            if (s[0] == 12) return "12-bit samples: 8-bit streams only";
-            if (s[0] != 8) return "the sample precision is not 8 bit";
-            in.h = (s[1] << 8) | s[2], in.w = (s[3] << 8) | s[4], in.components = s[5];
-            if (in.components == 4) return "4 components (CMYK / YCCK): 1 or 3 only";
-            if (in.components != 1 && in.components != 3) return "the frame must have 1 or 3 components";
-            if (in.h < 1 || in.w < 1 || in.h > JPEG_MAX_SIDE || in.w > JPEG_MAX_SIDE) return "frame sides must be 1..8192";
-            if (n != 6 + 3 * in.components) return "the length of SOF2 does not match its components";
-            for (int c = 0; c < in.components; ++c) {
-                comp_id[c] = s[6 + 3 * c];
-                const int hv2 = s[7 + 3 * c], tq = s[8 + 3 * c];
-                if (tq > 3) return "a quantiser id above 3";
-                in.qt[c] = tq;
-                if (in.components == 1) {
-                    in.hs = in.vs = 1;
-                } else if (c == 0) {
-                    if (hv2 != 0x22 && hv2 != 0x21 && hv2 != 0x11) return "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
-                    in.hs = hv2 >> 4, in.vs = hv2 & 15;
-                } else if (hv2 != 0x11) {
-                    return "chroma sampling must be 1x1";
-                }
-            }
-            if (in.components == 3 && (comp_id[0] == comp_id[1] || comp_id[0] == comp_id[2] || comp_id[1] == comp_id[2]))
+            refused = jpeg_read_sof(s, n, true, in, comp_id);
+            if (refused == nullptr && in.components == 3 && (comp_id[0] == comp_id[1] || comp_id[0] == comp_id[2] || comp_id[1] == comp_id[2]))
                 return "two components of the frame share an id";
             sof = true;
         } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4) {
             return "a second frame header in a progressive stream";
         } else if (m == 0xDB) {
             if (scanned) return "a quantiser table (DQT) behind the first scan of a progressive stream";
-            for (int i = 0; i < n;) {
-                const int pq = s[i] >> 4, tq = s[i] & 15;
-                if (pq != 0) return "a 16-bit quantiser table (DQT): 8-bit tables only";
-                if (tq > 3) return "a quantiser id above 3";
-                if (i + 65 > n) return "a short DQT";
-                for (int k = 0; k < 64; ++k) {
-                    if (s[i + 1 + k] == 0) return "a quantiser of 0";
-                    in.q[tq][JPEG_ZIGZAG[k]] = s[i + 1 + k];
-                }
-                in.q_present[tq] = 1;
-                i += 65;
-            }
+            refused = jpeg_read_dqt(s, n, in);
         } else if (m == 0xC4) {
-            for (int i = 0; i < n;) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                if (tc > 1 || th > 3) return "a Huffman table class above 1 or id above 3";
-                if (i + 17 > n) return "a short DHT";
-                int total = 0;
-                unsigned code = 0;
-                for (int l = 1; l <= 16; ++l) {
-                    const int cnt = s[i + l];
-                    total += cnt, code += unsigned(cnt);
-                    if (code > (1u << l)) return "a DHT whose code lengths are no prefix code";
-                    code <<= 1;
-                }
-                if (total > 256 || i + 17 + total > n) return "a short DHT";
-                std::memcpy(hc[tc][th], s + i + 1, 16);
-                std::memset(hv[tc][th], 0, 256);
-                std::memcpy(hv[tc][th], s + i + 17, size_t(total));
-                if (tc == 0)
-                    for (int k = 0; k < total; ++k)
-                        if (hv[tc][th][k] > 11) return "a DC Huffman symbol above 11";
-                hp[tc][th] = true;
-                i += 17 + total;
-            }
+            refused = jpeg_read_dht(s, n, 3, hc, hv, hp);
             ++dht_seen;
         } else if (m == 0xDD) {
             if (n != 2) return "a DRI of the wrong length";
@@ -273,15 +179,15 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             std::memset(hu, 0, sizeof(hu));
             if (sc.kind == JPEG_PROG_DC_FIRST) {
                 for (int i = 0; i < ns; ++i) {
-                    if (!hp[0][pub.dc[i]]) return "a missing Huffman table (DHT)";
-                    jpeg_prog_build_huff(hc[0][pub.dc[i]], hv[0][pub.dc[i]], hu[i]);
+                    if (!hp[2 * pub.dc[i]]) return "a missing Huffman table (DHT)";
+                    jpeg_dec_build_huff(hc[2 * pub.dc[i]], hv[2 * pub.dc[i]], hu[i]);
                 }
             } else if (sc.ss > 0) {
-                if (!hp[1][pub.ac[0]]) return "a missing Huffman table (DHT)";
-                jpeg_prog_build_huff(hc[1][pub.ac[0]], hv[1][pub.ac[0]], hu[0]);
+                if (!hp[2 * pub.ac[0] + 1]) return "a missing Huffman table (DHT)";
+                jpeg_dec_build_huff(hc[2 * pub.ac[0] + 1], hv[2 * pub.ac[0] + 1], hu[0]);
             }
             if (plan.dev.empty()) {
-                in.restart_interval = dri, in.data_offset = p + len;
+                in.restart_interval = dri, in.data_offset = p;
                 g = jpeg_dec_geom(in);
                 in.intervals = g.intervals;
             }
@@ -305,7 +211,7 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
                 if (share && e.ss <= sc.se && sc.ss <= e.se) sc.level = std::max(sc.level, e.level + 1);
             }
             // the scan's end and its restart markers
-            const int64_t from = p + len;
+            const int64_t from = p;
             if (plan.dev.empty()) plan.data_base = from;
             // (list_off: for now the scan's place in `items`; the lists are laid out below.  An item is listed where the data holds
             //  its start -- interval 0, and interval k + 1 behind marker k --, so the list is bounded by the bytes, never by what a
@@ -356,12 +262,10 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             for (const JpegDecHuff& h : hu) plan.huff.push_back(h);
             p = q;
             continue;
-        } else if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
-            // APPn, COM: skipped
-        } else {
+        } else if (!((m >= 0xE0 && m <= 0xEF) || m == 0xFE)) {      // (APPn, COM: skipped)
             return "an unexpected marker in the header";
         }
-        p += len;
+        if (refused != nullptr) return refused;
     }
     // the item lists: level by level, a scan's share padded to whole workgroups
     std::vector<JpegProgItem> flat;

@@ -708,6 +708,15 @@ struct JpegDecScratch {
     long long seg_cap;
     // nbytes: the length of the entropy data (< 0: data_bytes)
     JpegDecScratch(const JpegDecGeom& g, size_t data_bytes, long long nbytes = -1, int form = 0, int seg_bytes = 0);
+    // the offsets as the region table jpeg_dec_args reads (lengths are not filled in)
+    JpegClipFrame regions() const {
+        JpegClipFrame q{};
+        q.form = form, q.seg_bytes = seg_bytes, q.seg_cap = seg_cap;
+        q.tables.off = tables, q.data.off = data, q.start.off = start, q.meta.off = meta, q.seg_stats.off = seg_stats, q.coef.off = coef;
+        for (int c = 0; c < 3; ++c) q.plane[c].off = plane[c];
+        q.first_seg.off = first_seg, q.seg_exit.off = seg_exit, q.seg_count.off = seg_count, q.seg_blk.off = seg_blk;
+        return q;
+    }
 };
 struct JpegDecArgs {
     JpegDecGeom g;
@@ -734,8 +743,31 @@ struct JpegDecArgs {
 };
 // the segmented form's launches (jpeg_dec_seg.hip), behind the scan kernel and in front of the inverse DCT
 void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream);
-JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_scratch, const JpegDecScratch& lay, const uint8_t* d_data, long long nbytes,
-                          const whenet_surface_t& dst, int channel_order, int32_t* d_status, int rule = JPEG_RULE_OWN);
+// The record of one stream from a table of regions, offsets into d_base (a clip's JpegClipFrame; JpegDecScratch::regions(),
+// JpegProgLayout::regions()).  Form 2, a progressive stream: a baseline record over the progressive layout -- what
+// launch_jpeg_decode_tail reads of it (coef, meta, planes, destination, rule; form 0) --, the fields of the segmented form empty.
+inline JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_base, const JpegClipFrame& q, long long nbytes, const whenet_surface_t& dst,
+                                 int channel_order, int32_t* d_status, int rule, int seg_lanes) {
+    JpegDecArgs a{};
+    char* const s = static_cast<char*>(d_base);
+    a.g = g;
+    a.tables = reinterpret_cast<const JpegDecTables*>(s + q.tables.off);
+    a.data = reinterpret_cast<const uint8_t*>(s + q.data.off), a.nbytes = int(nbytes);
+    a.start = reinterpret_cast<int32_t*>(s + q.start.off), a.meta = reinterpret_cast<int32_t*>(s + q.meta.off);
+    a.coef = reinterpret_cast<int16_t*>(s + q.coef.off);
+    for (int c = 0; c < 3; ++c) {
+        a.plane[c] = reinterpret_cast<uint8_t*>(s + q.plane[c].off);
+        a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
+    }
+    a.format = dst.format, a.channel_order = channel_order, a.rule = rule;
+    a.status = d_status;
+    if (q.form == JPEG_CLIP_FORM_PROGRESSIVE) return a;
+    a.form = q.form, a.seg_bytes = q.seg_bytes, a.seg_cap = int(q.seg_cap), a.seg_lanes = seg_lanes;
+    a.seg_stats = reinterpret_cast<long long*>(s + q.seg_stats.off);
+    a.first_seg = reinterpret_cast<int32_t*>(s + q.first_seg.off), a.seg_exit = reinterpret_cast<uint64_t*>(s + q.seg_exit.off);
+    a.seg_count = reinterpret_cast<JpegSegCount*>(s + q.seg_count.off), a.seg_blk = reinterpret_cast<int32_t*>(s + q.seg_blk.off);
+    return a;
+}
 void launch_jpeg_decode(const JpegDecArgs& a, const JpegDecScratch& lay, hipStream_t stream);
 // the stages behind the entropy decode on their own: the inverse DCT of a.coef (which writes the status words from a.meta[1]) and
 // the colour stage of the record's rule and destination
@@ -754,6 +786,15 @@ void launch_jpeg_decode_tail(const JpegDecArgs& a, hipStream_t stream);
 struct JpegProgLayout {
     size_t scans, huff, qz, items, data, upload_bytes, meta, raw, zero_bytes, coef, coef_bytes, plane[3], bytes;
     JpegProgLayout(const JpegDecGeom& g, const JpegProgPlan& plan);
+    // the offsets as the region table jpeg_dec_args reads: form 2, the Huffman tables for `tables` and the item list for `start`
+    // (neither is read behind the entropy stage)
+    JpegClipFrame regions() const {
+        JpegClipFrame q{};
+        q.form = JPEG_CLIP_FORM_PROGRESSIVE;
+        q.tables.off = huff, q.data.off = data, q.start.off = items, q.meta.off = meta, q.coef.off = coef;
+        for (int c = 0; c < 3; ++c) q.plane[c].off = plane[c];
+        return q;
+    }
 };
 struct JpegProgArgs {
     JpegDecGeom g;
@@ -826,7 +867,7 @@ void launch_jpeg_decode_clip_tail(const JpegDecArgs* h_recs, const void* d_recs,
 
 // A clip that may hold PROGRESSIVE frames (jpeg_prog.hip): plans[f] is the scan plan of frame f (nullptr, or a baseline one: the frame
 // runs as in launch_jpeg_decode_clip), h_prog[f] its progressive record, which also lies in the frame's uploaded record at
-// JPEG_CLIP_PROG_RECORD_OFFSET (jpeg_dec_clip_host.h); h_recs[f] is then what jpeg_prog_tail_args makes (form 0, coef, meta).
+// JPEG_CLIP_PROG_RECORD_OFFSET (jpeg_dec_clip_host.h); h_recs[f] is then what jpeg_dec_args makes of a form-2 region table (form 0, coef, meta).
 //   whenet_jpeg_prog_clip_scan_kernel    launch L covers level L of every frame that has one: a frame's share of the grid is
 //            level_cnt[L] / 16 workgroups (0 for a frame with fewer levels and for a baseline frame), its first workgroup reads the
 //            frame's item list from level_off[L] / 16 on (JpegProgClipLevel).  The launches: the largest level count, <= 14.

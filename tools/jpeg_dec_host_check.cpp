@@ -12,8 +12,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/jpeg_dec_host_check.cpp \
 //       -o tools/jpeg_dec_host_check && tools/jpeg_dec_host_check stream.jpg ...
 //
-// Output, one line per file: "<file name> status <code> <first bad interval> crc <crc32 of the BGR frame>", or "<file name> refused
-// <reason>"; for a decoded file a second line "rule1:<file name> status <code> <first bad interval> crc <crc32 of rule 1's BGR frame>".
+// Output, one line per file: "<file name> status <code> <first bad interval> crc <crc32 of the BGR frame> tables <64-bit FNV-1a of the
+// stream's JpegDecTables, the bytes the device gets>", or "<file name> refused <reason>"; for a decoded file a second line "rule1:<file name> status <code> <first bad interval> crc <crc32 of rule 1's BGR frame>".
 // Exit status 0 unless a file cannot be read, a mutated stream changes what it must not, or the two rules disagree on a status.
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +37,11 @@ uint32_t crc32(const uint8_t* p, size_t n) {
         for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
     }
     return ~c;
+}
+
+uint64_t fnv1a(const void* p, size_t n, uint64_t h = 0xCBF29CE484222325ull) {
+    for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const uint8_t*>(p)[i]) * 0x100000001B3ull;
+    return h;
 }
 
 // decode `size` bytes held in a heap block of exactly that size; false: refused (reason)
@@ -134,7 +139,10 @@ int main(int argc, char** argv) {
             }
             continue;
         }
-        std::printf("%s status %d %d crc %08x\n", name.c_str(), status[0], status[1], crc);
+        std::unique_ptr<JpegDecTables> tables(new JpegDecTables);
+        jpeg_dec_build_tables(info, *tables);
+        std::printf("%s status %d %d crc %08x tables %016llx\n", name.c_str(), status[0], status[1], crc,
+                    (unsigned long long)(fnv1a(tables.get(), sizeof(JpegDecTables))));
         std::printf("rule1:%s status %d %d crc %08x\n", name.c_str(), status[0], status[1], crc1);
         // the same stream cut short: every length of the header is refused, every length of the data decodes to something
         const size_t off = size_t(info.data_offset), n = bytes.size() - off;

@@ -12,8 +12,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/jpeg_prog_host_check.cpp \
 //       -o tools/jpeg_prog_host_check && tools/jpeg_prog_host_check stream.jpg ...
 //
-// Output, one line per file: "<file name> status <code> <first bad item> crc <crc32 of rule 0's BGR frame> <crc32 of rule 1's>", or
-// "<file name> refused <reason>".  Exit status 0 unless a file cannot be read or the two rules disagree on a status.
+// Output, one line per file: "<file name> status <code> <first bad item> crc <crc32 of rule 0's BGR frame> <crc32 of rule 1's> plan
+// <64-bit FNV-1a of the scan plan's huff, dev and items, the bytes the device gets>", or "<file name> refused <reason>".  Exit status 0 unless a file cannot be read or the two rules disagree on a status.
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -38,8 +38,15 @@ uint32_t crc32(const uint8_t* p, size_t n) {
     return ~c;
 }
 
+uint64_t fnv1a(const void* p, size_t n, uint64_t h = 0xCBF29CE484222325ull) {
+    for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const uint8_t*>(p)[i]) * 0x100000001B3ull;
+    return h;
+}
+
 // one decode of `size` bytes held in an exact-size heap block; false: refused (reason in *why)
-bool decode(const uint8_t* src, size_t size, int rule, int32_t status[2], uint32_t* crc, const char** why, long long max_pixels = 1 << 20) {
+// (plan_sum: nullptr, or where the checksum of the scan plan goes)
+bool decode(const uint8_t* src, size_t size, int rule, int32_t status[2], uint32_t* crc, const char** why, long long max_pixels = 1 << 20,
+            uint64_t* plan_sum = nullptr) {
     std::unique_ptr<uint8_t[]> d(new uint8_t[size ? size : 1]);
     std::memcpy(d.get(), src, size);
     whenet_jpeg_info_t info;
@@ -47,6 +54,11 @@ bool decode(const uint8_t* src, size_t size, int rule, int32_t status[2], uint32
     if (const char* bad = jpeg_prog_parse(d.get(), int64_t(size), info, plan)) {
         *why = bad;
         return false;
+    }
+    if (plan_sum != nullptr) {
+        *plan_sum = fnv1a(plan.huff.data(), plan.huff.size() * sizeof(JpegDecHuff));
+        *plan_sum = fnv1a(plan.dev.data(), plan.dev.size() * sizeof(JpegProgScan), *plan_sum);
+        *plan_sum = fnv1a(plan.items.data(), plan.items.size() * sizeof(JpegProgItem), *plan_sum);
     }
     const JpegDecGeom g = jpeg_dec_geom(info);
     if ((long long)(g.h) * g.w > max_pixels) {      // (a large picture, or a flipped size byte: the decode would only take long)
@@ -81,7 +93,8 @@ int main(int argc, char** argv) {
         int32_t st0[2] = {0, 0}, st1[2] = {0, 0};
         uint32_t c0 = 0, c1 = 0;
         const char* why = "";
-        if (!decode(data.data(), data.size(), JPEG_RULE_OWN, st0, &c0, &why)) {
+        uint64_t plan_sum = 0;
+        if (!decode(data.data(), data.size(), JPEG_RULE_OWN, st0, &c0, &why, 1 << 20, &plan_sum)) {
             std::printf("%s refused %s\n", name.c_str(), why);
         } else {
             decode(data.data(), data.size(), JPEG_RULE_LIBJPEG, st1, &c1, &why);
@@ -89,7 +102,7 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "%s: the rules disagree on the status\n", name.c_str());
                 return 1;
             }
-            std::printf("%s status %d %d crc %08x %08x\n", name.c_str(), st0[0], st0[1], c0, c1);
+            std::printf("%s status %d %d crc %08x %08x plan %016llx\n", name.c_str(), st0[0], st0[1], c0, c1, (unsigned long long)(plan_sum));
         }
         constexpr long long SMALL = 1 << 14;      // mutated copies are decoded up to 128 x 128 pixels
         // cuts
