@@ -10,7 +10,11 @@ Stored: rects int32 [n,4], ypr float32 [n,3], lines int32 [n,3,4] = (Px, Py, Qx,
 [n,3,3] and thickness int32 [n,3] as passed.  tests/test_overlay_cpu.py compares `whenet_overlay_segments` with it and, wherever
 the reference tree is present, reproduces it live.
 
-    python tests/golden/make_overlay_fixture.py
+The same call on the exact-ratio table of tests/overlay_lattice_cases.py -- every sensitive head and every 7th other head of every
+window, in the table's order -- -> tests/golden/reference_draw_axis_lattice.npz: index int32 [n] = window * 65536 + the head's row
+in its window's table, lines int16 [n,3,4].  The colours and the thickness are those of the first fixture (asserted, not stored).
+
+    python tests/golden/make_overlay_fixture.py [seeded] [lattice]
 """
 import os
 import sys
@@ -21,9 +25,11 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, ROOT)
 
 from tests import overlay_cases as OC  # noqa: E402
+from tests import overlay_lattice_cases as LC  # noqa: E402
 from tests import refharness  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "reference_draw_axis.npz")
+OUT_LATTICE = os.path.join(ROOT, "tests", "golden", "reference_draw_axis_lattice.npz")
 
 
 def run_reference(rects, ypr):
@@ -48,12 +54,37 @@ def run_reference(rects, ypr):
     return lines, colours, thick
 
 
-def main():
-    rects, ypr = OC.reference_heads()
+def lattice_heads():
+    """(index int32 [n], rects int32 [n,4], ypr float32 [n,3]) of the recorded heads of the exact-ratio table."""
+    index, rects, ypr = [], [], []
+    for T in LC.tables():
+        rows = T.recorded()
+        index.append(T.index * 65536 + rows)
+        rects.append(T.rects[rows])
+        ypr.append(T.ypr[rows])
+    return np.concatenate(index).astype(np.int32), np.concatenate(rects), np.concatenate(ypr)
+
+
+def run_reference_lattice():
+    """-> (index int32 [n], lines int16 [n,3,4]) of the executed reference on lattice_heads()."""
+    index, rects, ypr = lattice_heads()
     lines, colours, thick = run_reference(rects, ypr)
-    np.savez_compressed(OUT, rects=rects, ypr=ypr, lines=lines, colours=colours, thickness=thick)
-    print(f"{OUT}: {len(rects)} heads, {os.path.getsize(OUT)} bytes")
+    assert (colours == np.array([(0, 0, 255), (0, 255, 0), (255, 0, 0)])).all() and (thick == 2).all()
+    assert np.abs(lines).max() < 1 << 15
+    return index, lines.astype(np.int16)
+
+
+def main(which):
+    if "seeded" in which:
+        rects, ypr = OC.reference_heads()
+        lines, colours, thick = run_reference(rects, ypr)
+        np.savez_compressed(OUT, rects=rects, ypr=ypr, lines=lines, colours=colours, thickness=thick)
+        print(f"{OUT}: {len(rects)} heads, {os.path.getsize(OUT)} bytes")
+    if "lattice" in which:
+        index, lines = run_reference_lattice()
+        np.savez_compressed(OUT_LATTICE, index=index, lines=lines)
+        print(f"{OUT_LATTICE}: {len(index)} heads, {os.path.getsize(OUT_LATTICE)} bytes")
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:] or ["seeded", "lattice"])

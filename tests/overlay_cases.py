@@ -48,9 +48,21 @@ def axis_coordinates(yaw, pitch, roll, tdx, tdy, size):
     operations is the reference's (utils.py:15-38) -- degrees times pi, then divided by 180; the yaw negated; every product
     associated left to right; the centre added last -- because every one of them rounds; the wording is this project's
     (csrc/overlay_host.h states the same arithmetic in C++)."""
+    return axis_coordinates_of(axis_trig(yaw, pitch, roll), tdx, tdy, size)
+
+
+def axis_trig(yaw, pitch, roll):
+    """(cos y, sin y, cos p, sin p, cos r, sin r) of the radian arguments, from Python's math module: the host's libm."""
     to_rad = lambda deg: deg * math.pi / 180
     p, y, r = to_rad(pitch), -to_rad(yaw), to_rad(roll)
-    cos_y, sin_y, cos_p, sin_p, cos_r, sin_r = math.cos(y), math.sin(y), math.cos(p), math.sin(p), math.cos(r), math.sin(r)
+    return math.cos(y), math.sin(y), math.cos(p), math.sin(p), math.cos(r), math.sin(r)
+
+
+def axis_coordinates_of(trig, tdx, tdy, size):
+    """axis_coordinates from the six sines and cosines onward.  Python floats give six floats; float64 arrays of one shape give
+    six arrays, every operation rounded on its own as in the scalar form (tests/overlay_lattice_cases.py moves one value of the
+    six by one ulp and looks at what int() then returns)."""
+    cos_y, sin_y, cos_p, sin_p, cos_r, sin_r = trig
     x_axis = (size * (cos_y * cos_r) + tdx, size * (cos_p * sin_r + cos_r * sin_p * sin_y) + tdy)
     y_axis = (size * (-cos_y * sin_r) + tdx, size * (cos_p * cos_r - sin_p * sin_y * sin_r) + tdy)
     z_axis = (size * sin_y + tdx, size * (-cos_y * sin_p) + tdy)
@@ -260,7 +272,8 @@ def reference_heads():
     # The draw order is part of the fixture: origins, then the sides as one [n,2] draw, then the angles as one [n,3] draw of
     # (-1, 1) scaled.  With it every coordinate that is computed with a rounding (size >= 1) lies 1.78e-6 or more from an integer
     # (integer_margin; test_overlay_cpu asserts >= 1e-6), so an implementation's last-bit differences in sin / cos cannot move an
-    # int().  Other orders of the same seed gave 4.6e-8 .. 8.6e-7: such a set would test the libm, not the overlay.
+    # int().  Other orders of the same seed gave 4.6e-8 .. 8.6e-7: such a set would test the libm, not the overlay.  (The heads that
+    # do sit on an integer, on purpose, are the table of tests/overlay_lattice_cases.py.)
     x0, y0 = rng.integers(0, 1800, n), rng.integers(0, 1000, n)
     sides = rng.integers(1, 700, (n, 2))
     rects = np.stack([y0, x0, y0 + sides[:, 1], x0 + sides[:, 0]], axis=1).astype(np.int32)

@@ -1,5 +1,6 @@
 """The pose overlay without a GPU: the segments against the EXECUTED reference (utils.draw_axis under tests/refharness.py, committed
-as tests/golden/reference_draw_axis.npz), `whenet_annotate_host` against the numpy statement of tests/overlay_cases.py on the case
+as tests/golden/reference_draw_axis.npz, and reference_draw_axis_lattice.npz for the exact-ratio table of
+tests/overlay_lattice_cases.py, where one ulp of a sine moves a pixel), `whenet_annotate_host` against the numpy statement of tests/overlay_cases.py on the case
 table, the BGR -> 4:2:0 coefficient rows against their expressions, executed Pillow and the round trip through the ingest's
 conversion, and the plumbing: header, exports, every WHENET_EINVAL that needs no device, the ValueErrors of the Python layer."""
 import ctypes as C
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import overlay_cases as OC
+from tests import overlay_lattice_cases as LC
 from tests import refharness
 from whenet_hip import _lib, overlay
 from whenet_hip.frames import FramePipeline
@@ -17,6 +19,7 @@ from whenet_hip.yuv import YUVFrame
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_draw_axis.npz")
+GOLDEN_LATTICE = os.path.join(ROOT, "tests", "golden", "reference_draw_axis_lattice.npz")
 HEADER = os.path.join(ROOT, "include", "whenet_hip.h")
 MAT_NAME = {OC.BT601: "bt601", OC.BT709: "bt709", OC.JFIF: "jfif"}
 
@@ -82,6 +85,93 @@ def test_segments_flags_and_range():
     assert overlay.segments((-4096, -4096, 8192, 8192), 1, 2, 3)[1] == 3
     # size = (x1 - x0) // 2 floors
     assert overlay.segments((0, 10, 4, 7), 0, 0, 0)[0].tolist() == OC.segments((0, 10, 4, 7), 0, 0, 0)[0]
+
+
+# ---- 1b. the exact-ratio table: where a last bit of a sine decides a pixel (tests/overlay_lattice_cases.py) -----------------------
+@pytest.fixture(scope="module")
+def lattice():
+    return LC.tables()
+
+
+def test_lattice_table_holds_the_sensitive_heads(lattice):
+    count = lambda family: sum(int((T.sensitive & (T.family == family)).sum()) for T in lattice)
+    heads = lambda family: sum(int((T.family == family).sum()) for T in lattice)
+    print(f"sensitive: lattice {count(LC.LATTICE)} of {heads(LC.LATTICE)}, bin centres {count(LC.BIN)} of {heads(LC.BIN)}, "
+          f"controls {count(LC.CONTROL)} of {heads(LC.CONTROL)}; per window {[int(T.sensitive.sum()) for T in lattice]}; "
+          f"frames {[(T.h, T.w) for T in lattice]}")
+    assert (heads(LC.LATTICE), heads(LC.BIN), heads(LC.CONTROL)) == (25350, 5760, 1812)
+    assert count(LC.LATTICE) >= 2900 and count(LC.BIN) >= 90 and count(LC.CONTROL) == 0
+    for T in lattice:                                             # every endpoint, moved or not, grown by the reach, is in the frame
+        ends = np.concatenate([T.segments[None], T.perturbed]).reshape(-1, 8, 2)
+        assert ends.min() >= 0 and ends[..., 0].max() + LC.REACH < T.w and ends[..., 1].max() + LC.REACH < T.h
+        assert np.array_equal(T.sensitive, LC.sensitivity(T.rect, T.ypr))
+        # one float32 step is far more than one ulp of a sine: the controls are the lattice's neighbours, not the lattice
+        assert not T.sensitive[T.family == LC.CONTROL].any()
+
+
+def test_every_lattice_perturbation_is_visible_in_the_picture(lattice):
+    """Every sensitive head, painted alone on its window's frame: at least one of its moved segment sets gives another picture,
+    so a kernel whose sine differs there by one ulp fails tests/test_overlay_gpu.py's byte comparison -- with one exception that
+    the paint order makes, not the table: where the moved axis lies along an axis painted after it and is the shorter of the two
+    (yaw -180, pitch 90, roll -60 on (0, 0, 8, 8): X ends at (1, 4) or (2, 4), Y at (0, 4)), no picture shows its end.  37 of the
+    2,998 sensitive heads are of that kind (11, 9, 4, 7, 0, 6 per window); only a head's segments could tell them apart."""
+    visible, hidden = 0, [0] * len(lattice)
+    for T in lattice:
+        frame = T.frame()
+        for n, i in enumerate(np.flatnonzero(T.sensitive)):
+            base = LC.paint_segments(frame, T.segments[i])
+            if n % 50 == 0:                                          # the boxed raster is the whole-frame statement
+                assert np.array_equal(base, OC.paint(frame, OC.BGR, [T.rect], None, [T.ypr[i]])), T.describe(i)
+            moved = np.unique(T.perturbed[:, i][(T.perturbed[:, i] != T.segments[i]).any(axis=1)], axis=0)
+            assert len(moved) >= 1
+            shows = [not np.array_equal(LC.paint_segments(frame, m), base) for m in moved]
+            covered = [LC.hidden_by_a_later_axis(T.segments[i], m) for m in moved]
+            assert shows == [not c for c in covered], (T.describe(i), moved[:, 4:].tolist())      # hidden exactly where the rule says
+            visible += any(shows)
+            hidden[T.index] += not any(shows)
+    print(f"sensitive heads with a visible perturbation: {visible}; hidden behind a later axis, per window: {hidden}")
+    assert visible >= 2900 and sum(hidden) <= 40
+
+
+def test_host_segments_equal_numpy_on_the_lattice_table(lattice):
+    for T in lattice:
+        for i in range(len(T.ypr)):
+            seg, flags = overlay.segments(T.rect, *T.ypr[i])
+            assert flags == 3 and seg.tolist() == T.segments[i].tolist(), T.describe(i)
+            if T.sensitive[i] or i % 7 == 0:                          # (the vectorised statement is the scalar one)
+                assert OC.segments(T.rect, *T.ypr[i])[0] == seg.tolist(), T.describe(i)
+
+
+@pytest.fixture(scope="module")
+def recorded_lattice():
+    return dict(np.load(GOLDEN_LATTICE))
+
+
+def _overlay_fixture_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_overlay_fixture", os.path.join(ROOT, "tests", "golden", "make_overlay_fixture.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_lattice_segments_equal_the_recorded_cv2_line_calls(lattice, recorded_lattice):
+    index, lines = recorded_lattice["index"], recorded_lattice["lines"]
+    assert lines.dtype == np.int16 and lines.shape == (len(index), 3, 4)
+    want = np.concatenate([T.index * 65536 + T.recorded() for T in lattice])
+    assert np.array_equal(index, want)                                # every sensitive head and every 7th other one, in table order
+    assert len(index) >= sum(int(T.sensitive.sum()) for T in lattice) + 4000
+    for code, line in zip(index, lines):
+        T, i = lattice[code >> 16], code & 0xFFFF
+        seg, _ = overlay.segments(T.rect, *T.ypr[i])
+        assert np.array_equal(seg[4:].reshape(3, 4), line), T.describe(i)
+
+
+@pytest.mark.skipif(not refharness.available(), reason="the reference tree is not present")
+def test_live_reference_run_reproduces_the_lattice_fixture(recorded_lattice):
+    index, lines = _overlay_fixture_module().run_reference_lattice()
+    assert np.array_equal(index, recorded_lattice["index"]) and np.array_equal(lines, recorded_lattice["lines"])
+    assert lines.dtype == recorded_lattice["lines"].dtype
 
 
 # ---- 2. the host function against the numpy statement ----------------------------------------------------------------------

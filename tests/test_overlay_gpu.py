@@ -1,6 +1,7 @@
 """The pose overlay on the GPU (csrc/overlay.hip; Engine::op_annotate / frame_annotate of csrc/engine_post.cpp;
 FramePipeline.annotate / annotate_clip).  There is no tolerance anywhere: the kernels return the bytes of `whenet_annotate_host`,
-which tests/test_overlay_cpu.py holds to the numpy statement; a device destination keeps every byte outside its rows; the collect
+which tests/test_overlay_cpu.py holds to the numpy statement -- also at the exact-ratio angles of tests/overlay_lattice_cases.py,
+where a last bit of the device's sines would move a pixel; a device destination keeps every byte outside its rows; the collect
 calls return what they return without an annotate."""
 import json
 import os
@@ -11,6 +12,7 @@ import torch
 
 from tests import detector_cases as DC
 from tests import overlay_cases as OC
+from tests import overlay_lattice_cases as LC
 from tests.test_clip_gpu import assert_same, kwargs
 from tests.test_yuv_gpu import seeded_model
 from whenet_hip import _lib, overlay
@@ -119,6 +121,62 @@ def test_op_annotate_refuses_what_the_host_function_refuses(post):
         post.op_annotate(frame, np.zeros((0, 4), np.int32), None, np.zeros((0, 3), np.float32), s)
     assert not out.any() and not t.any().item()
     assert np.array_equal(overlay.annotate(post, frame, np.zeros((0, 4), np.int32), [], [], [], out=out), frame)      # the handle is usable
+
+
+# ---- 5b. the exact-ratio table: the plan kernel's sines against the host's (tests/overlay_lattice_cases.py) ---------------------------
+CALL_HEADS = 256           # the most heads a call takes
+
+
+def lattice_differences(post, T, rows, batch, fmt=OC.PACKED, display="simple"):
+    """The heads `rows` of window table T through op_annotate in calls of `batch` heads -> the first row of every call whose bytes
+    are not those of annotate_host."""
+    frame, bad = T.frame(), []
+    got, want = overlay.new_output(T.h, T.w, FMT_NAME[fmt]), overlay.new_output(T.h, T.w, FMT_NAME[fmt])
+    for at in range(0, len(rows), batch):
+        r = rows[at:at + batch]
+        args = (frame, T.rects[r], T.ypr[r, 0], T.ypr[r, 1], T.ypr[r, 2])
+        overlay.annotate(post, *args, out=got, display=display)
+        overlay.annotate_host(*args, out=want, display=display)
+        if any(g.tobytes() != w.tobytes() for g, w in zip(planes_of(got), planes_of(want))):
+            bad.append(int(r[0]))
+    return bad
+
+
+def explain(T, i, post):
+    """A sensitive head whose picture differs: which one-ulp moves of a sine reproduce the device's picture, and by how many pixels."""
+    got = overlay.annotate(post, T.frame(), T.rects[i:i + 1], *T.ypr[i:i + 1].T)
+    moves = sorted({tuple(m) for m in T.perturbed[:, i].tolist() if np.array_equal(LC.paint_segments(T.frame(), m), got)})
+    shift = [int(np.abs(np.asarray(m) - T.segments[i]).max()) for m in moves]
+    return f"{T.describe(i)}; the device's picture is that of {[list(m[4:]) for m in moves]} (largest endpoint move {shift} px)"
+
+
+@pytest.mark.parametrize("window", range(len(LC.WINDOWS)))
+def test_every_sensitive_head_alone_equals_the_host_function(post, window):
+    """One head per call, so nothing overpaints a moved endpoint and a failure names its head."""
+    T = LC.table(window)
+    rows = np.flatnonzero(T.sensitive)
+    assert len(rows) >= 14 and T.h <= 352 and T.w <= 502
+    bad = lattice_differences(post, T, rows, 1)
+    assert not bad, (f"{len(bad)} of {len(rows)} sensitive heads differ between the kernels and whenet_annotate_host",
+                     [explain(T, i, post) for i in bad[:8]])
+
+
+@pytest.mark.parametrize("window", range(len(LC.WINDOWS)))
+def test_the_whole_lattice_table_in_calls_of_256_heads(post, window):
+    """Lattice, bin centres and controls, 256 co-centred heads per call: the draw kernel's list at its longest, both displays."""
+    T = LC.table(window)
+    rows = np.arange(len(T.ypr))
+    for display in ("simple", "full"):
+        bad = lattice_differences(post, T, rows, CALL_HEADS, display=display)
+        assert not bad, (display, f"{len(bad)} calls differ; they begin at", [T.describe(i) for i in bad[:8]])
+
+
+def test_the_largest_window_into_an_nv12_destination(post):
+    T = max(LC.tables(), key=lambda t: t.h * t.w)
+    assert T.rect == (100, 200, 300, 500)
+    rows = np.flatnonzero(T.sensitive)
+    bad = lattice_differences(post, T, rows, CALL_HEADS, fmt=OC.NV12)  # the 4:2:0 leg sees the same endpoints
+    assert not bad, [T.describe(i) for i in bad[:8]]
 
 
 # ---- 6. device destinations ---------------------------------------------------------------------------------------------------------
