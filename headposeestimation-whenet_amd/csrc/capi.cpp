@@ -1433,6 +1433,83 @@ int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t*
     }
 }
 
+// ---- oriented decode (JPEG DECODER, ORIENTATION; jpeg_dec_host.h: jpeg_exif_orientation, jpeg_dec.hip: the oriented frame kernels) ----
+int whenet_jpeg_orientation(const uint8_t* data, int64_t size) { return whenet::jpeg_exif_orientation(data, size); }
+
+int whenet_jpeg_decode_oriented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule, int progressive,
+                                     int32_t status[2]) {
+    return host_statement([&] {
+        const std::string what = "jpeg_decode_oriented_host";
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        WHENET_REQUIRE(progressive == 0 || progressive == 1, WHENET_EINVAL, what + ": progressive must be 0 or 1");
+        whenet_jpeg_info_t info;
+        whenet::JpegProgPlan plan;
+        jpeg_parse_or_refuse(what.c_str(), data, size, info, progressive ? &plan : nullptr);
+        const int o = whenet::jpeg_exif_orientation(data, size);
+        WHENET_REQUIRE(o <= 1 || (dst->format != WHENET_YUV_I420 && dst->format != WHENET_YUV_NV12), WHENET_EINVAL,
+                       what + ": the stream's orientation is " + std::to_string(o) +
+                           ": an oriented decode writes packed surfaces only (WHENET_SURF_PACKED)");
+        const whenet_jpeg_info_t landed = whenet::jpeg_orient_info(info, o);
+        const char* bad = whenet::jpeg_dec_check_dst(landed, dst, channel_order, rule);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, what + ": " + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, what + ": the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        if (progressive) whenet::jpeg_prog_decode_planes_host(info, plan, data, size, planes, status, rule);
+        else whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), planes, status, rule);
+        whenet::jpeg_dec_frame_oriented_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule, o);
+    });
+}
+
+int whenet_op_jpeg_decode_oriented(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
+                                   int seg_bytes, int rule, int progressive, int orient, int32_t status[2], int64_t stats[8], int32_t* orientation) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_oriented: NULL argument");
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       "op_jpeg_decode_oriented: entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_oriented: seg_bytes must be a power of two in 4..4096");
+        WHENET_REQUIRE(progressive >= -1 && progressive <= 1, WHENET_EINVAL, "op_jpeg_decode_oriented: progressive must be -1 (the handle's option), 0 or 1");
+        int applied = 1;
+        e.op_jpeg_decode(data, size, *dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, stats, rule, progressive, orient, &applied);
+        if (orientation != nullptr) *orientation = applied;
+    });
+}
+
+int whenet_op_jpeg_decode_clip_oriented(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, const whenet_surface_t* dst,
+                                        int channel_order, int32_t* status, int entropy, int seg_bytes, int rule, int progressive, int orient,
+                                        int32_t* orientation) {
+    return guarded(h, [&](whenet::Engine& e) {
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       "op_jpeg_decode_clip_oriented: entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL,
+                       "op_jpeg_decode_clip_oriented: seg_bytes must be a power of two in 4..4096");
+        WHENET_REQUIRE(progressive == 0 || progressive == 1, WHENET_EINVAL, "op_jpeg_decode_clip_oriented: progressive must be 0 or 1");
+        int applied[whenet::JPEG_CLIP_MAX_FRAMES];
+        e.op_jpeg_decode_clip(data, size, num_frames, dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, rule, progressive, orient,
+                              applied);
+        if (orientation != nullptr) std::copy(applied, applied + num_frames, orientation);
+    });
+}
+
+int whenet_frame_begin_jpeg_oriented(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int progressive, int orient,
+                                     int* ticket, int32_t* status, int32_t* orientation) {
+    int applied = 1;
+    const int rc = begin_on_next_engine(
+        h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status, rule, progressive, orient, &applied); });
+    if (rc == WHENET_OK && orientation != nullptr) *orientation = applied;
+    return rc;
+}
+
+int whenet_clip_begin_jpeg_oriented(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int rule,
+                                    int progressive, int orient, int* ticket, int32_t* status, int32_t* orientation) {
+    int applied[whenet::JPEG_CLIP_MAX_FRAMES];
+    const int rc = begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule, progressive, orient, applied);
+    });
+    if (rc == WHENET_OK && orientation != nullptr) std::copy(applied, applied + num_frames, orientation);
+    return rc;
+}
+
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,
                            const float* anchors, int num_anchors, int num_classes, const float* image_shapes, float score_threshold,
                            float iou_threshold, int max_boxes, float* boxes, float* scores, int32_t* classes, int32_t* index,

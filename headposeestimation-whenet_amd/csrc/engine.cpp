@@ -289,6 +289,11 @@ void Engine::set_option(const std::string& key, long value) {
         WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "jpeg_progressive must be 0 (SOF2 streams are refused, default) or 1 (they are decoded)");
         jpeg_progressive_ = int(value);
         return;
+    } else if (key == "jpeg_orient") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL,
+                       "jpeg_orient must be 0 (the EXIF orientation is ignored, default) or 1 (single streams are decoded upright)");
+        jpeg_orient_ = int(value);
+        return;
     } else if (key == "jpeg_prog_levels") {
         WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "jpeg_prog_levels must be 1 (a launch per level, default) or 0 (a launch per scan)");
         jpeg_prog_levels_ = int(value);

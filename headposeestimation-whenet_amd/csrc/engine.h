@@ -366,13 +366,19 @@ class Engine {
     // PROGRESSIVE streams (SOF2; jpeg_prog.hip, JPEG DECODER, PROGRESSIVE in the header) are opt-in: progressive = 1, or -1 with the
     // option "jpeg_progressive" set.  Then a SOF2 stream runs the scan plan (one H2D), a memset, a scan-kernel launch per level
     // (option "jpeg_prog_levels" = 0: per scan) and the finish in front of the inverse DCT; a SOF0 stream runs as ever.
+    // ORIENTED decode (JPEG DECODER, ORIENTATION in the header) is opt-in: orient = 1, or -1 with the option "jpeg_orient" set (the
+    // single-stream calls; clips take the argument only).  Then the stream's EXIF orientation (jpeg_exif_orientation, 1..8) goes into
+    // the record and the frame kernel's place is taken by the oriented one: the destination, the slot's frame and its sizes are the
+    // ORIENTED frame's (5..8: w rows of h pixels), no upright frame exists anywhere and no launch is added (a clip: at most one).
+    // applied (may be nullptr): the value applied, 1 where the decode is not oriented; a clip's: one per frame.
     void op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy = -1,
-                        int seg_bytes = 0, int64_t* stats = nullptr, int rule = -1, int progressive = -1);
+                        int seg_bytes = 0, int64_t* stats = nullptr, int rule = -1, int progressive = -1, int orient = -1, int* applied = nullptr);
     void add_jpeg_progressive_counters(int64_t out[4]) const;      // decodes enqueued, scan-kernel launches, scans in them
     void add_jpeg_decode_counters(int64_t out[4]) const;      // decodes launched in form 0, in form 1
     void jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d_entropy, int64_t nbytes, const whenet_surface_t& dst,
                             int channel_order, int32_t* d_status, hipStream_t stream);
-    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule = -1, int progressive = -1);
+    int frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule = -1, int progressive = -1,
+                         int orient = -1, int* applied = nullptr);
     // A CLIP of 1..16 JPEG streams (frame f: data[f], size[f] bytes), each with its own size, sampling, tables, DRI and entropy
     // form (the options are applied stream by stream): one plan (jpeg_dec_clip_host.h), ONE H2D of records | tables | entropy bytes,
     // one memset and every stage in one launch for all frames (launch_jpeg_decode_clip).  Refusals -- a frame count outside 1..16, a
@@ -388,9 +394,10 @@ class Engine {
     // (launch_jpeg_decode_clip_progressive).  A baseline frame keeps the form it has in a baseline clip.  The progressive counters
     // add a decode per progressive frame, the clip's scan launches and the scans of its frames.
     int clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule = -1,
-                        int progressive = 0);
+                        int progressive = 0, int orient = 0, int* applied = nullptr);
     void op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
-                             int32_t* status, int entropy = -1, int seg_bytes = 0, int rule = -1, int progressive = 0);
+                             int32_t* status, int entropy = -1, int seg_bytes = 0, int rule = -1, int progressive = 0, int orient = 0,
+                             int* applied = nullptr);
     void add_jpeg_clip_counters(int64_t out[4]) const;      // clip decodes, their frames, their launches + memsets, their H2D copies
     void op_head_compact(const int32_t* valid, const int32_t* count, int frames, int slots_per_frame, int max_heads, int32_t* row,
                          int32_t* slot_of_row, int32_t* rows_used, int32_t* overflow);
@@ -617,6 +624,9 @@ class Engine {
     int jpeg_entropy_ = 2, jpeg_seg_bytes_ = JPEG_SEG_DEFAULT_BYTES;      // options "jpeg_entropy", "jpeg_seg_bytes"
     int jpeg_rule_ = JPEG_RULE_OWN;                                       // option "jpeg_rule"
     int jpeg_progressive_ = 0, jpeg_prog_levels_ = 1;                     // options "jpeg_progressive", "jpeg_prog_levels"
+    int jpeg_orient_ = 0;                                                 // option "jpeg_orient"
+    // the orientation a single-stream call applies: the stream's tag where `orient` is 1, or -1 with the option set; else 1
+    int jpeg_orient_of(const char* what, int orient, const uint8_t* data, int64_t size) const;
     int64_t jpeg_prog_counts_[3] = {0, 0, 0};                             // decodes enqueued, scan-kernel launches, scans in them
     // the rule of a call: its argument, or the option where that is -1; anything else is WHENET_EINVAL
     int jpeg_rule_of(const char* what, int rule) const;
@@ -625,7 +635,7 @@ class Engine {
     int64_t jpeg_clip_counts_[4] = {0, 0, 0, 0};                         // add_jpeg_clip_counters
     struct JpegClipJob;      // the parsed headers, geometries and the plan of a clip (engine_post.cpp)
     void jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes, int rule,
-                           JpegClipJob& job, int progressive = 0) const;
+                           JpegClipJob& job, int progressive = 0, int orient = 0) const;
     // records | tables | entropy bytes into `stage` (plan.upload_bytes), the records for a work buffer at d_base; recs: the same records
     // (a progressive frame: its scan plan's share, a record as jpeg_dec_args makes it of its regions, and its progressive record in precs)
     void jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data, uint8_t* stage, void* d_base, const whenet_surface_t* dst,
@@ -637,8 +647,9 @@ class Engine {
     // one stream through the single-stream kernels (op_jpeg_decode, frame_begin_jpeg): its layouts; stage + one H2D + launches + counters
     struct JpegStreamJob;
     int64_t jpeg_stream_launch(const JpegStreamJob& job, const uint8_t* data, uint8_t* stage, void* d_work, const whenet_surface_t& dst,
-                               int channel_order, int32_t* d_status, int rule, hipStream_t stream);
+                               int channel_order, int32_t* d_status, int rule, hipStream_t stream, int orient = 1);
     // the slot of frame_begin_jpeg / clip_begin_jpeg: its buffers, destination surfaces and status words; its state and ticket
+    // (info: the headers with the sides of the frames as they land -- jpeg_orient_info of an oriented decode)
     Slot& jpeg_slot_begin(const whenet_jpeg_info_t* info, int nframes, size_t upload_bytes, size_t work_bytes, size_t* off, whenet_surface_t* dst,
                           int32_t*& d_status);
     int jpeg_slot_finish(Slot& slot, const whenet_jpeg_info_t* info, const size_t* off, int clip_frames, bool one_size, int channel_order,

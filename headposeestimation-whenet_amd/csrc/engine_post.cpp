@@ -1489,6 +1489,19 @@ int Engine::jpeg_rule_of(const char* what, int rule) const {
     return rule == -1 ? jpeg_rule_ : rule;
 }
 
+int Engine::jpeg_orient_of(const char* what, int orient, const uint8_t* data, int64_t size) const {
+    WHENET_REQUIRE(orient >= -1 && orient <= 1, WHENET_EINVAL,
+                   std::string(what) + ": orient must be -1 (the handle's option), 0 (the orientation is ignored) or 1 (it is applied)");
+    return (orient == -1 ? jpeg_orient_ != 0 : orient != 0) ? jpeg_exif_orientation(data, size) : 1;
+}
+
+// an oriented decode (2..8) into an I420 / NV12 destination
+static void jpeg_orient_require_packed(const std::string& what, int orient, const whenet_surface_t& dst) {
+    WHENET_REQUIRE(orient <= 1 || (dst.format != WHENET_YUV_I420 && dst.format != WHENET_YUV_NV12), WHENET_EINVAL,
+                   what + ": the stream's orientation is " + std::to_string(orient) +
+                       ": an oriented decode writes packed surfaces only (WHENET_SURF_PACKED)");
+}
+
 void Engine::add_jpeg_decode_counters(int64_t out[4]) const { out[0] += jpeg_dec_launched_[0], out[1] += jpeg_dec_launched_[1]; }
 void Engine::add_jpeg_progressive_counters(int64_t out[4]) const {
     for (int i = 0; i < 3; ++i) out[i] += jpeg_prog_counts_[i];
@@ -1516,7 +1529,7 @@ struct Engine::JpegStreamJob {
 // `stream`: memset, a scan-kernel launch per level and the finish, then the stages the baseline decoder ends with; or the baseline
 // decoder.  Returns the scan-kernel launches.
 int64_t Engine::jpeg_stream_launch(const JpegStreamJob& job, const uint8_t* data, uint8_t* stage, void* d_work, const whenet_surface_t& dst,
-                                   int channel_order, int32_t* d_status, int rule, hipStream_t stream) {
+                                   int channel_order, int32_t* d_status, int rule, hipStream_t stream, int orient) {
     if (job.prog) {
         jpeg_prog_stage(job.plan, job.play, data + job.plan.data_base, stage);
     } else {      // tables | compressed bytes
@@ -1530,20 +1543,21 @@ int64_t Engine::jpeg_stream_launch(const JpegStreamJob& job, const uint8_t* data
     int64_t launches = 0;
     if (job.prog) {
         launch_jpeg_decode_progressive(
-            jpeg_dec_args(job.g, d_work, job.play.regions(), job.plan.data_bytes, dst, channel_order, d_status, rule, 0), job.plan, job.play, d_work,
+            jpeg_dec_args(job.g, d_work, job.play.regions(), job.plan.data_bytes, dst, channel_order, d_status, rule, 0, orient), job.plan, job.play,
+            d_work,
             jpeg_prog_levels_, stream, &launches);
         ++jpeg_prog_counts_[0], jpeg_prog_counts_[1] += launches, jpeg_prog_counts_[2] += int64_t(job.plan.dev.size());
     } else {
         launch_jpeg_decode(
-            jpeg_dec_args(job.g, d_work, job.lay.regions(), (long long)(job.nbytes), dst, channel_order, d_status, rule, job.lay.seg_lanes), job.lay,
-            stream);
+            jpeg_dec_args(job.g, d_work, job.lay.regions(), (long long)(job.nbytes), dst, channel_order, d_status, rule, job.lay.seg_lanes, orient),
+            job.lay, stream);
         ++jpeg_dec_launched_[job.lay.form];
     }
     return launches;
 }
 
 void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surface_t& dst, int channel_order, int32_t* status, int entropy,
-                            int seg_bytes, int64_t* stats, int rule, int progressive) {
+                            int seg_bytes, int64_t* stats, int rule, int progressive, int orient, int* applied) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "op_jpeg_decode: NULL argument");
     rule = jpeg_rule_of("op_jpeg_decode", rule);
@@ -1551,19 +1565,23 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
     JpegProgPlan plan;
     const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
     jpeg_parse_or_refuse("op_jpeg_decode", data, size, info, accept ? &plan : nullptr);
-    const char* bad = jpeg_dec_check_dst(info, &dst, channel_order, rule);
+    const int o = jpeg_orient_of("op_jpeg_decode", orient, data, size);
+    jpeg_orient_require_packed("op_jpeg_decode", o, dst);
+    const whenet_jpeg_info_t landed = jpeg_orient_info(info, o);      // (the destination is the oriented frame)
+    const char* bad = jpeg_dec_check_dst(landed, &dst, channel_order, rule);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("op_jpeg_decode: ") + (bad ? bad : ""));
     WHENET_REQUIRE(dst.on_device == 0, WHENET_EINVAL, "op_jpeg_decode: the surface must be host memory (on_device = 0)");
-    check_surface("op_jpeg_decode", dst, info.h, info.w);
+    check_surface("op_jpeg_decode", dst, landed.h, landed.w);
     const JpegStreamJob job(*this, info, plan, accept, size, entropy, seg_bytes);
     GuardedSurfaces out;
-    out.add(dst, info.h, info.w);
+    out.add(dst, landed.h, landed.w);
     TempBufs tmp;
     char* const d_scratch = static_cast<char*>(tmp.get(job.work_bytes()));
     int32_t* const d_status = static_cast<int32_t*>(tmp.get(2 * sizeof(int32_t)));
     std::vector<uint8_t> upload(job.upload_bytes());      // (alive until the wait below)
     out.alloc(stream_);
-    const int64_t prog_launches = jpeg_stream_launch(job, data, upload.data(), d_scratch, out.device()[0], channel_order, d_status, rule, stream_);
+    const int64_t prog_launches = jpeg_stream_launch(job, data, upload.data(), d_scratch, out.device()[0], channel_order, d_status, rule, stream_, o);
+    if (applied != nullptr) *applied = o;
     out.to_host(stream_, "op_jpeg_decode", "the surface");      // waits
     WHENET_HIP_CHECK(hipMemcpy(status, d_status, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (stats != nullptr && job.prog) {
@@ -1664,7 +1682,8 @@ int Engine::jpeg_slot_finish(Slot& slot, const whenet_jpeg_info_t* info, const s
 }
 
 // frame_begin from a JPEG stream: the slot ends up exactly as frame_begin(decoded frame, channel_order) leaves it
-int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule, int progressive) {
+int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_order, int32_t* status, int rule, int progressive, int orient,
+                             int* applied) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "frame_begin_jpeg: NULL argument");
     rule = jpeg_rule_of("frame_begin_jpeg", rule);
@@ -1673,19 +1692,25 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     JpegProgPlan plan;
     const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
     jpeg_parse_or_refuse("frame_begin_jpeg", data, size, info, accept ? &plan : nullptr);      // (before a slot is taken)
+    const int o = jpeg_orient_of("frame_begin_jpeg", orient, data, size);
+    const whenet_jpeg_info_t landed = jpeg_orient_info(info, o);      // (the slot's frame is the oriented one: the same byte count)
     const JpegStreamJob job(*this, info, plan, accept, size, -1, 0);
     size_t off[2];
     whenet_surface_t dst;
     int32_t* d_status = nullptr;
-    Slot& slot = jpeg_slot_begin(&info, 1, job.upload_bytes(), job.work_bytes(), off, &dst, d_status);
-    jpeg_stream_launch(job, data, slot.frame.h.as<uint8_t>(), slot.jpg_dec.as<void>(), dst, channel_order, d_status, rule, copy_stream());
-    return jpeg_slot_finish(slot, &info, off, 0, true, channel_order, status);
+    Slot& slot = jpeg_slot_begin(&landed, 1, job.upload_bytes(), job.work_bytes(), off, &dst, d_status);
+    jpeg_stream_launch(job, data, slot.frame.h.as<uint8_t>(), slot.jpg_dec.as<void>(), dst, channel_order, d_status, rule, copy_stream(), o);
+    if (applied != nullptr) *applied = o;
+    return jpeg_slot_finish(slot, &landed, off, 0, true, channel_order, status);
 }
 
 // ---- clips of JPEG streams (the contract is in engine.h) ----
 struct Engine::JpegClipJob {
     int frames = 0;
     std::vector<whenet_jpeg_info_t> info;
+    // the orientation each frame's kernel applies (1: upright) and the headers with the sides of the frames as they land
+    int orient[MIXED_MAX_FRAMES];
+    std::vector<whenet_jpeg_info_t> landed;
     JpegDecGeom g[MIXED_MAX_FRAMES];
     int64_t nbytes[MIXED_MAX_FRAMES];
     JpegClipPlan plan;
@@ -1698,14 +1723,16 @@ struct Engine::JpegClipJob {
 };
 
 void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, const int64_t* size, int nframes, int entropy, int seg_bytes,
-                               int rule, JpegClipJob& job, int progressive) const {
+                               int rule, JpegClipJob& job, int progressive, int orient) const {
     const std::string w(what);
     job.rule = jpeg_rule_of(what, rule);
     WHENET_REQUIRE(nframes >= 1 && nframes <= MIXED_MAX_FRAMES, WHENET_EINVAL,
                    w + ": " + std::to_string(nframes) + " frames: a clip holds 1..16 (the detector's batch limit)");
     WHENET_REQUIRE(data != nullptr && size != nullptr, WHENET_EINVAL, w + ": NULL argument");
+    WHENET_REQUIRE(orient == 0 || orient == 1, WHENET_EINVAL, w + ": orient must be 0 (the orientation is ignored) or 1 (it is applied)");
     job.frames = nframes;
     job.info.resize(size_t(nframes));
+    job.landed.resize(size_t(nframes));
     job.progressive = progressive != 0;
     if (job.progressive) job.prog.resize(size_t(nframes));
     for (int f = 0; f < nframes; ++f) {
@@ -1713,6 +1740,8 @@ void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, con
         jpeg_parse_or_refuse(who.c_str(), data[f], size[f], job.info[f], job.progressive ? &job.prog[size_t(f)] : nullptr);
         job.g[f] = jpeg_dec_geom(job.info[f]);
         job.nbytes[f] = size[f] - job.info[f].data_offset;
+        job.orient[f] = orient != 0 ? jpeg_exif_orientation(data[f], size[f]) : 1;
+        job.landed[f] = jpeg_orient_info(job.info[f], job.orient[f]);
     }
     const int ent = entropy >= 0 ? entropy : jpeg_entropy_, seg = seg_bytes > 0 ? seg_bytes : jpeg_seg_bytes_;
     const char* bad = nullptr;
@@ -1743,7 +1772,8 @@ void Engine::jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data,
             const JpegProgPlan& plan = job.prog[size_t(f)];
             JpegClipFrame regions = q;
             regions.tables = r.huff, regions.start = r.items;
-            const JpegDecArgs a = jpeg_dec_args(job.g[f], d_base, regions, plan.data_bytes, dst[f], channel_order, d_status + 2 * f, job.rule, 0);
+            const JpegDecArgs a =
+                jpeg_dec_args(job.g[f], d_base, regions, plan.data_bytes, dst[f], channel_order, d_status + 2 * f, job.rule, 0, job.orient[f]);
             JpegProgArgs x{};
             x.g = job.g[f];
             x.scans = reinterpret_cast<const JpegProgScan*>(s + r.scans.off), x.huff = reinterpret_cast<const JpegDecHuff*>(s + r.huff.off);
@@ -1756,7 +1786,7 @@ void Engine::jpeg_clip_stage(const JpegClipJob& job, const uint8_t* const* data,
             jpeg_clip_stage_progressive(plan, q, r, data[f] + plan.data_base, stage);
             continue;
         }
-        recs[f] = jpeg_dec_args(job.g[f], d_base, q, job.nbytes[f], dst[f], channel_order, d_status + 2 * f, job.rule, jpeg_seg_lanes_);
+        recs[f] = jpeg_dec_args(job.g[f], d_base, q, job.nbytes[f], dst[f], channel_order, d_status + 2 * f, job.rule, jpeg_seg_lanes_, job.orient[f]);
         std::memcpy(rec, &recs[f], sizeof(JpegDecArgs));
         JpegDecTables* const t = reinterpret_cast<JpegDecTables*>(stage + q.tables.off);      // (256-byte aligned in pinned or vector memory)
         jpeg_dec_build_tables(job.info[f], *t);
@@ -1787,44 +1817,46 @@ void Engine::jpeg_clip_launch(const JpegClipJob& job, const JpegDecArgs* recs, c
 }
 
 int Engine::clip_begin_jpeg(const uint8_t* const* data, const int64_t* size, int nframes, int channel_order, int32_t* status, int rule,
-                            int progressive) {
+                            int progressive, int orient, int* applied) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr, WHENET_EINVAL, "clip_begin_jpeg: NULL argument");
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "clip_begin_jpeg: unknown channel order");
     JpegClipJob job;
-    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, rule, job, progressive);      // (before a slot is taken)
-    bool one_size = true;
-    for (int f = 1; f < nframes; ++f) one_size = one_size && job.info[f].h == job.info[0].h && job.info[f].w == job.info[0].w;
+    jpeg_clip_prepare("clip_begin_jpeg", data, size, nframes, -1, 0, rule, job, progressive, orient);      // (before a slot is taken)
+    bool one_size = true;      // (by the sizes of the frames as they land)
+    for (int f = 1; f < nframes; ++f) one_size = one_size && job.landed[f].h == job.landed[0].h && job.landed[f].w == job.landed[0].w;
     WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
                    "clip_begin_jpeg: " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
                        std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
     size_t off[MIXED_MAX_FRAMES + 1];
     whenet_surface_t dst[MIXED_MAX_FRAMES];
     int32_t* d_status = nullptr;
-    Slot& slot = jpeg_slot_begin(job.info.data(), nframes, job.plan.upload_bytes, job.plan.bytes, off, dst, d_status);
+    Slot& slot = jpeg_slot_begin(job.landed.data(), nframes, job.plan.upload_bytes, job.plan.bytes, off, dst, d_status);
     JpegDecArgs recs[MIXED_MAX_FRAMES];
     JpegProgArgs precs[MIXED_MAX_FRAMES];
     uint8_t* const stage = slot.frame.h.as<uint8_t>();
     jpeg_clip_stage(job, data, stage, slot.jpg_dec.as<void>(), dst, channel_order, d_status, recs, precs);
     WHENET_HIP_CHECK(hipMemcpyAsync(slot.jpg_dec.as<void>(), stage, job.plan.upload_bytes, hipMemcpyHostToDevice, copy_stream()));
     jpeg_clip_launch(job, recs, precs, slot.jpg_dec.as<char>(), copy_stream());
-    return jpeg_slot_finish(slot, job.info.data(), off, nframes, one_size, channel_order, status);
+    if (applied != nullptr) std::copy(job.orient, job.orient + nframes, applied);
+    return jpeg_slot_finish(slot, job.landed.data(), off, nframes, one_size, channel_order, status);
 }
 
 void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size, int nframes, const whenet_surface_t* dst, int channel_order,
-                                 int32_t* status, int entropy, int seg_bytes, int rule, int progressive) {
+                                 int32_t* status, int entropy, int seg_bytes, int rule, int progressive, int orient, int* applied) {
     DeviceGuard guard(device_);
     WHENET_REQUIRE(status != nullptr && dst != nullptr, WHENET_EINVAL, "op_jpeg_decode_clip: NULL argument");
     JpegClipJob job;
-    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, rule, job, progressive);
+    jpeg_clip_prepare("op_jpeg_decode_clip", data, size, nframes, entropy, seg_bytes, rule, job, progressive, orient);
     GuardedSurfaces out;
     for (int f = 0; f < nframes; ++f) {
         const std::string who = "op_jpeg_decode_clip: frame " + std::to_string(f);
-        const char* bad = jpeg_dec_check_dst(job.info[f], &dst[f], channel_order, job.rule);
+        jpeg_orient_require_packed(who, job.orient[f], dst[f]);
+        const char* bad = jpeg_dec_check_dst(job.landed[f], &dst[f], channel_order, job.rule);
         WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, who + ": " + (bad ? bad : ""));
         WHENET_REQUIRE(dst[f].on_device == 0, WHENET_EINVAL, who + ": the surface must be host memory (on_device = 0)");
-        check_surface(who.c_str(), dst[f], job.info[f].h, job.info[f].w);
-        out.add(dst[f], job.info[f].h, job.info[f].w);
+        check_surface(who.c_str(), dst[f], job.landed[f].h, job.landed[f].w);
+        out.add(dst[f], job.landed[f].h, job.landed[f].w);
     }
     const JpegClipPlan& plan = job.plan;
     TempBufs tmp;
@@ -1838,6 +1870,7 @@ void Engine::op_jpeg_decode_clip(const uint8_t* const* data, const int64_t* size
     jpeg_clip_stage(job, data, st, d_work, out.device(), channel_order, d_status, recs, precs);
     WHENET_HIP_CHECK(hipMemcpyAsync(d_work, st, plan.upload_bytes, hipMemcpyHostToDevice, stream_));
     jpeg_clip_launch(job, recs, precs, d_work, stream_);
+    if (applied != nullptr) std::copy(job.orient, job.orient + nframes, applied);
     out.to_host(stream_, "op_jpeg_decode_clip", "the surfaces");      // waits
     WHENET_HIP_CHECK(hipMemcpy(status, d_status, size_t(nframes) * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
 }

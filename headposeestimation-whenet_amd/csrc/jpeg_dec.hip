@@ -20,6 +20,10 @@
 //                                   (x >> (hs - 1), y >> (vs - 1)), 12 bytes out with the head / funnel-shift / tail stores of yuv.hip.
 //                                   A tight BGR destination of a 4:2:0 stream goes through yuv.hip's own plane kernel instead.
 //   whenet_jpeg_dec_yuv_kernel      4:2:0 planes -> an I420 or NV12 surface (a copy).
+//   whenet_jpeg_dec_frame_oriented_kernel   in the frame kernel's place where the record's EXIF orientation is 2..8 (the header's JPEG
+//                                   DECODER, ORIENTATION): the same pixel values at the oriented frame's addresses -- 2..4 a reversed
+//                                   group in a mirrored row, 5..8 a 32 x 32 tile of the destination gathered in LDS.  No upright frame
+//                                   is written anywhere.  27 VGPRs, 66 SGPRs, 4,224 B LDS, no scratch (rule 1's form: 44 / 76).
 // RULE 1 (libjpeg's bytes; the header's JPEG DECODER, RULE 1) has its own forms of two of them, the rule fixed at compile time:
 //   whenet_jpeg_dec_idct_libjpeg_kernel   the same mapping, jidctint's two passes (the row pass in int64), the same status words.
 //   whenet_jpeg_dec_frame_libjpeg_kernel  the same 4 pixels per lane and the same stores; chroma by fancy upsampling from the lane's two
@@ -217,13 +221,14 @@ __device__ __forceinline__ void store_group(uint8_t* dp, const uint32_t px[4], i
     }
 }
 
-__device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
-    const int h = a.g.h, w = a.g.w, gw = (w + 3) >> 2;
-    const long long item = (long long)(bx) * THREADS + threadIdx.x;
-    const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
-    if (y >= h) return;
-    const int x = gx << 2;
-    const int n = min(4, w - x);                    // pixels of the group, 1..4
+// The packed pixels px of the 4-pixel group at (y, x) of the UPRIGHT frame, x a multiple of 4 below w, y < h, by the stream's rule:
+// what the upright frame kernels store at (y, x) and the oriented ones at the place the orientation gives each pixel.  (The pixels
+// of a group behind the row's end are computed from the planes' padding and never stored.)
+template <int RULE>
+__device__ __forceinline__ void frame_group(const JpegDecArgs& a, int y, int x, uint32_t px[4]);
+
+template <>
+__device__ __forceinline__ void frame_group<JPEG_RULE_OWN>(const JpegDecArgs& a, int y, int x, uint32_t px[4]) {
     // (x is a multiple of 4 and the planes' pitches are multiples of 8: the loads are aligned and inside the padded planes)
     const uint32_t y4 = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
     const int hsh = a.g.hs - 1, vsh = a.g.vs - 1;
@@ -237,7 +242,6 @@ __device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
         }
     }
     const int rsh = a.channel_order == WHENET_BGR ? 16 : 0;
-    uint32_t px[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int yy = int((y4 >> (8 * j)) & 255u);
@@ -245,19 +249,14 @@ __device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
         if (a.g.comps == 3) jpeg_dec_pixel(yy, int((u4 >> (8 * (j >> hsh))) & 255u), int((v4 >> (8 * (j >> hsh))) & 255u), b, g, r);
         px[j] = (uint32_t(r) << rsh) | (uint32_t(g) << 8) | (uint32_t(b) << (16 - rsh));
     }
-    store_group(a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x) * 3, px, n);
 }
 
 // Rule 1 (libjpeg): fancy upsampling and jdcolor's row.  A lane's 4 pixels lie over the chroma columns i and i + 1 (x = 2 i); it
 // needs those and the two neighbour columns i - 1 and i + 2, from its own chroma row and, for 4:2:0, the one vertical neighbour
 // (above for even y, below for odd y).  Every index is clamped to the REAL plane (ch x cw): what the padding holds never enters.
-__device__ __forceinline__ void frame_body_libjpeg(const JpegDecArgs& a, int bx) {
-    const int h = a.g.h, w = a.g.w, gw = (w + 3) >> 2;
-    const long long item = (long long)(bx) * THREADS + threadIdx.x;
-    const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
-    if (y >= h) return;
-    const int x = gx << 2;
-    const int n = min(4, w - x);
+template <>
+__device__ __forceinline__ void frame_group<JPEG_RULE_LIBJPEG>(const JpegDecArgs& a, int y, int x, uint32_t px[4]) {
+    const int h = a.g.h, w = a.g.w;
     const uint32_t y4 = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
     const int hsh = a.g.hs - 1, vsh = a.g.vs - 1;
     const int ch = (h + a.g.vs - 1) >> vsh, cw = (w + a.g.hs - 1) >> hsh;
@@ -295,7 +294,6 @@ __device__ __forceinline__ void frame_body_libjpeg(const JpegDecArgs& a, int bx)
         }
     }
     const int rsh = a.channel_order == WHENET_BGR ? 16 : 0;
-    uint32_t px[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int yy = int((y4 >> (8 * j)) & 255u);
@@ -303,7 +301,102 @@ __device__ __forceinline__ void frame_body_libjpeg(const JpegDecArgs& a, int bx)
         if (a.g.comps == 3) jpeg_ycc_pixel(yy, uv[0][j], uv[1][j], b, g, r);
         px[j] = (uint32_t(r) << rsh) | (uint32_t(g) << 8) | (uint32_t(b) << (16 - rsh));
     }
+}
+
+// the upright frame: a lane's group goes where it came from
+template <int RULE>
+__device__ __forceinline__ void frame_body(const JpegDecArgs& a, int bx) {
+    const int h = a.g.h, w = a.g.w, gw = (w + 3) >> 2;
+    const long long item = (long long)(bx) * THREADS + threadIdx.x;
+    const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
+    if (y >= h) return;
+    const int x = gx << 2;
+    const int n = min(4, w - x);                    // pixels of the group, 1..4
+    uint32_t px[4];
+    frame_group<RULE>(a, y, x, px);
     store_group(a.dst[0] + size_t(y) * size_t(a.dst_pitch[0]) + size_t(x) * 3, px, n);
+}
+
+// ---- the ORIENTED frame (JpegDecArgs::orient = 2..8; jpeg_dec_host.h: jpeg_orient_source): the pixel of source position (y, x) is
+// frame_group's, only its destination differs.
+//   2, 3, 4 (rows stay rows): the upright mapping, a group per lane.  The destination row is y or h - 1 - y; where x runs against the
+//            destination the group's pixels are reversed and stored at w - x - n: generally unaligned, which store_group's head and
+//            tail bytes take, and the row's short group (n < 4) lands at the row's START with exactly its 3 n bytes.
+//   5..8 (rows become columns): a workgroup owns a 32 x 32 tile of the DESTINATION (oh = w rows, ow = h columns).  The source pixels
+//            that map into it are a block of <= 32 rows and <= 32 columns whose first column need not be a multiple of 4 (7 and 8:
+//            x = w - 1 - Y): the lanes compute the <= 9 aligned source groups per row that cover it (plane reads along rows) and
+//            put each pixel that lies inside the tile into LDS at its DESTINATION place, a dword per pixel, rows 33 dwords apart
+//            (the four pixels of a group go to four tile rows, the lanes of a source row to one tile column: with a pitch of 32
+//            the <= 9 lanes of a source row would store to ONE bank, with 33 they are 4 banks apart: a 32-lane group of a whole
+//            tile -- 4 source rows of 8 groups -- stores to 32 different banks, and so do the dword reads behind the barrier).
+//            After the barrier lane t stores group t & 7 of tile row t >> 3: eight lanes write 96 contiguous bytes of a
+//            destination row.  Tiling the destination keeps every stored group on the destination's own 4-pixel grid, so the
+//            row's tail is the short one.
+constexpr int ORIENT_TILE = 32, ORIENT_PITCH = ORIENT_TILE + 1;
+static_assert(ORIENT_TILE * (ORIENT_TILE / 4) == THREADS, "a lane stores one group of the tile");
+
+// workgroups of the oriented frame kernel for one stream
+inline long long orient_workgroups(const JpegDecGeom& g, int orient) {
+    if (orient < 5) return ((long long)(g.h) * ((g.w + 3) >> 2) + THREADS - 1) / THREADS;
+    return (long long)((g.w + ORIENT_TILE - 1) / ORIENT_TILE) * ((g.h + ORIENT_TILE - 1) / ORIENT_TILE);
+}
+
+template <int RULE>
+__device__ __forceinline__ void frame_oriented_body(const JpegDecArgs& a, int bx) {
+    // (one kernel for the seven values, so that a clip's turned frames are ONE launch: the 4,224 B tile is allocated for the values 2..4
+    // as well, which never touch it -- at 27 / 44 VGPRs the LDS does not bound the workgroups per CU)
+    __shared__ uint32_t s_tile[ORIENT_TILE * ORIENT_PITCH];
+    const int h = a.g.h, w = a.g.w, o = a.orient;
+    const bool fx = jpeg_orient_flip_x(o), fy = jpeg_orient_flip_y(o);
+    const int tid = int(threadIdx.x);
+    if (o < 5) {
+        const int gw = (w + 3) >> 2;
+        const long long item = (long long)(bx) * THREADS + tid;
+        const int y = int(item / gw), gx = int(item - (long long)(y) * gw);
+        if (y >= h) return;
+        const int x = gx << 2;
+        const int n = min(4, w - x);
+        uint32_t px[4];
+        frame_group<RULE>(a, y, x, px);
+        if (fx) {      // pixel j of the n goes to n - 1 - j
+            uint32_t r[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = px[j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) px[j] = n == 4 ? r[3 - j] : (n == 3 ? r[(2 - j) & 3] : (n == 2 ? r[(1 - j) & 3] : r[0]));
+        }
+        const int Y = fy ? h - 1 - y : y, X = fx ? w - x - n : x;      // X + n <= w
+        store_group(a.dst[0] + size_t(Y) * size_t(a.dst_pitch[0]) + size_t(X) * 3, px, n);
+        return;
+    }
+    // the destination is w rows of h pixels
+    const int tiles_x = (h + ORIENT_TILE - 1) / ORIENT_TILE;
+    const int Y0 = (bx / tiles_x) * ORIENT_TILE, X0 = (bx % tiles_x) * ORIENT_TILE;
+    const int rows = min(ORIENT_TILE, w - Y0), cols = min(ORIENT_TILE, h - X0);      // of the tile, inside the destination: >= 1
+    // the source block: x over the tile's rows, y over its columns
+    const int xlo = fx ? w - Y0 - rows : Y0, xhi = xlo + rows - 1, ylo = fy ? h - X0 - cols : X0;
+    const int g0 = xlo >> 2, ng = (xhi >> 2) - g0 + 1;      // <= 9 groups per source row
+    for (int it = tid; it < cols * ng; it += THREADS) {
+        const int r = it / ng, gi = it - r * ng;
+        const int y = ylo + r, x = (g0 + gi) << 2;            // y < h, x <= xhi < w
+        uint32_t px[4];
+        frame_group<RULE>(a, y, x, px);
+        const int Xl = (fy ? h - 1 - y : y) - X0;             // 0 .. cols - 1
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int xx = x + j;
+            const int Yl = (fx ? w - 1 - xx : xx) - Y0;       // inside the tile where xlo <= xx <= xhi
+            if (xx >= xlo && xx <= xhi) s_tile[Yl * ORIENT_PITCH + Xl] = px[j];
+        }
+    }
+    __syncthreads();
+    const int Yl = tid >> 3, Xl = (tid & 7) << 2;
+    if (Yl >= rows || Xl >= cols) return;
+    const int n = min(4, cols - Xl);
+    uint32_t px[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) px[j] = j < n ? s_tile[Yl * ORIENT_PITCH + Xl + j] : 0u;
+    store_group(a.dst[0] + size_t(Y0 + Yl) * size_t(a.dst_pitch[0]) + size_t(X0 + Xl) * 3, px, n);
 }
 
 // up to 4 bytes of `word` to dp: one dword where all four are the row's and dp is aligned
@@ -350,10 +443,15 @@ __device__ __forceinline__ void yuv_body(const JpegDecArgs& a, int bx) {
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_scan_kernel(JpegDecArgs a) { scan_body(a); }
 __global__ __launch_bounds__(ENT_THREADS) void whenet_jpeg_dec_entropy_kernel(JpegDecArgs a) { entropy_body(a, int(blockIdx.x)); }
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_kernel(JpegDecArgs a) { idct_body<JPEG_RULE_OWN>(a, int(blockIdx.x)); }
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_kernel(JpegDecArgs a) { frame_body(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_kernel(JpegDecArgs a) { frame_body<JPEG_RULE_OWN>(a, int(blockIdx.x)); }
 // rule 1 (libjpeg): the same mappings, its arithmetic
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_idct_libjpeg_kernel(JpegDecArgs a) { idct_body<JPEG_RULE_LIBJPEG>(a, int(blockIdx.x)); }
-__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_libjpeg_kernel(JpegDecArgs a) { frame_body_libjpeg(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_libjpeg_kernel(JpegDecArgs a) { frame_body<JPEG_RULE_LIBJPEG>(a, int(blockIdx.x)); }
+// the oriented frame (orient 2..8) under either rule, in the frame kernel's place
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_oriented_kernel(JpegDecArgs a) { frame_oriented_body<JPEG_RULE_OWN>(a, int(blockIdx.x)); }
+__global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_frame_oriented_libjpeg_kernel(JpegDecArgs a) {
+    frame_oriented_body<JPEG_RULE_LIBJPEG>(a, int(blockIdx.x));
+}
 __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArgs a) { yuv_body(a, int(blockIdx.x)); }
 
 // ---- the clip kernels: up to 16 records in device memory (recs), the frames' workgroups back to back in one grid.  A workgroup
@@ -365,6 +463,7 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArg
 // 296 bytes of scratch per lane).  Resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), VGPRs of
 // the clip form / of the single-stream form, no scratch in either, the same LDS: scan 44 / 44, entropy 47 / 48, idct 47 / 47,
 // frame 18 / 18, yuv 14 / 14; SGPRs grow by up to 21 (the prefix sums and the record's address).  Rule 1: idct 36 / 36, frame 38 / 38.
+// The oriented frame kernels: 28 / 27 under rule 0 and 44 / 44 under rule 1, 4,224 B of LDS in all four, no scratch.
 #define WHENET_JPEG_CLIP_KERNEL(name, threads, call)                                                                       \
     __global__ __launch_bounds__(threads) void name(const void* __restrict__ recs, JpegClipGrid grid) {                    \
         const int b = int(blockIdx.x);                                                                                     \
@@ -378,9 +477,11 @@ __global__ __launch_bounds__(THREADS) void whenet_jpeg_dec_yuv_kernel(JpegDecArg
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_scan_kernel, THREADS, scan_body(a))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_entropy_kernel, ENT_THREADS, entropy_body(a, bx))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_idct_kernel, THREADS, idct_body<JPEG_RULE_OWN>(a, bx))
-WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_kernel, THREADS, frame_body(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_kernel, THREADS, frame_body<JPEG_RULE_OWN>(a, bx))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_idct_libjpeg_kernel, THREADS, idct_body<JPEG_RULE_LIBJPEG>(a, bx))
-WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_libjpeg_kernel, THREADS, frame_body_libjpeg(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_libjpeg_kernel, THREADS, frame_body<JPEG_RULE_LIBJPEG>(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_oriented_kernel, THREADS, frame_oriented_body<JPEG_RULE_OWN>(a, bx))
+WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_frame_oriented_libjpeg_kernel, THREADS, frame_oriented_body<JPEG_RULE_LIBJPEG>(a, bx))
 WHENET_JPEG_CLIP_KERNEL(whenet_jpeg_dec_clip_yuv_kernel, THREADS, yuv_body(a, bx))
 #undef WHENET_JPEG_CLIP_KERNEL
 
@@ -390,7 +491,10 @@ static_assert(sizeof(JpegDecArgs) <= JPEG_CLIP_RECORD_BYTES && JPEG_CLIP_RECORD_
 void check_jpeg_dec_args(const JpegDecArgs& a) {
     const JpegDecGeom& g = a.g;
     int rows[3], row_bytes[3];
-    const int planes = overlay_surface_planes(a.format, g.h, g.w, rows, row_bytes);
+    WHENET_REQUIRE(a.orient >= 0 && a.orient <= 8 && (a.orient <= 1 || a.format == WHENET_SURF_PACKED), WHENET_EINVAL,
+                   "jpeg_decode: the orientation must be 0..8, and an oriented decode (2..8) writes packed surfaces only");
+    // (the destination is the ORIENTED frame: for 5..8 g.w rows of 3 g.h bytes)
+    const int planes = overlay_surface_planes(a.format, jpeg_orient_h(a.orient, g.h, g.w), jpeg_orient_w(a.orient, g.h, g.w), rows, row_bytes);
     WHENET_REQUIRE(planes > 0 && g.h >= 1 && g.w >= 1 && g.h <= JPEG_MAX_SIDE && g.w <= JPEG_MAX_SIDE && (g.comps == 1 || g.comps == 3) &&
                        (g.hs == 1 || g.hs == 2) && (g.vs == 1 || g.vs == 2) && g.bpm == (g.comps == 3 ? g.hs * g.vs + 2 : 1) &&
                        g.mcu_cols == (g.w + 8 * g.hs - 1) / (8 * g.hs) && g.mcu_rows == (g.h + 8 * g.vs - 1) / (8 * g.vs) && g.ri >= 1 &&
@@ -417,9 +521,10 @@ void check_jpeg_dec_args(const JpegDecArgs& a) {
 }
 
 // the colour path of a stream: 0 the plane kernel of the YUV ingest (a tight BGR frame of a 4:2:0 stream under rule 0), 1 the frame
-// kernel of the stream's rule, 2 the I420 / NV12 copy
+// kernel of the stream's rule, 2 the I420 / NV12 copy, 3 the oriented frame kernel of the stream's rule (orient 2..8)
 int colour_path(const JpegDecArgs& a) {
     if (a.format != WHENET_SURF_PACKED) return 2;
+    if (a.orient > 1) return 3;
     if (a.rule == JPEG_RULE_LIBJPEG) return 1;
     return a.g.comps == 3 && a.g.hs == 2 && a.g.vs == 2 && a.channel_order == WHENET_BGR && a.dst_pitch[0] == 3 * a.g.w ? 0 : 1;
 }
@@ -488,7 +593,10 @@ void launch_jpeg_decode_tail(const JpegDecArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(a.rule == JPEG_RULE_LIBJPEG ? whenet_jpeg_dec_idct_libjpeg_kernel : whenet_jpeg_dec_idct_kernel,
                        dim3(unsigned((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(THREADS), 0, stream, a);
     WHENET_HIP_CHECK(hipGetLastError());
-    if (a.format == WHENET_SURF_PACKED) {
+    if (colour_path(a) == 3) {
+        hipLaunchKernelGGL(a.rule == JPEG_RULE_LIBJPEG ? whenet_jpeg_dec_frame_oriented_libjpeg_kernel : whenet_jpeg_dec_frame_oriented_kernel,
+                           dim3(unsigned(orient_workgroups(g, a.orient))), dim3(THREADS), 0, stream, a);
+    } else if (a.format == WHENET_SURF_PACKED) {
         if (colour_path(a) == 0) {
             // a tight BGR frame of a 4:2:0 stream: the plane kernel of the YUV ingest, JFIF row
             YuvPlanes clip{};
@@ -585,6 +693,9 @@ void launch_jpeg_decode_clip_tail(const JpegDecArgs* h_recs, const void* d_recs,
     if (jpeg_clip_grid(h_recs, frames,
                   [](const JpegDecArgs& a) { return colour_path(a) == 1 ? ((long long)(a.g.h) * ((a.g.w + 3) >> 2) + THREADS - 1) / THREADS : 0; }, grid))
         libjpeg ? launch(whenet_jpeg_dec_clip_frame_libjpeg_kernel, THREADS) : launch(whenet_jpeg_dec_clip_frame_kernel, THREADS);
+    // (the turned frames of the clip: one launch more where there are any, whatever their number)
+    if (jpeg_clip_grid(h_recs, frames, [](const JpegDecArgs& a) { return colour_path(a) == 3 ? orient_workgroups(a.g, a.orient) : 0; }, grid))
+        libjpeg ? launch(whenet_jpeg_dec_clip_frame_oriented_libjpeg_kernel, THREADS) : launch(whenet_jpeg_dec_clip_frame_oriented_kernel, THREADS);
     if (jpeg_clip_grid(h_recs, frames,
                   [](const JpegDecArgs& a) {
                       const long long items = (long long)(a.g.h) * ((a.g.w + 3) >> 2) + (long long)((a.g.h + 1) >> 1) * ((((a.g.w + 1) >> 1) + 3) >> 2);

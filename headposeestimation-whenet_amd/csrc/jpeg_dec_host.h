@@ -226,6 +226,60 @@ inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t
     }
 }
 
+// ---- EXIF orientation (pure host; include/whenet_hip.h, JPEG DECODER, ORIENTATION) ----
+// The orientation tag (0x0112) of a stream, 1..8: from IFD0 of the FIRST APP1 segment in front of SOS whose payload starts with
+// "Exif\0\0" (an XMP APP1 in front of it is passed, a second Exif APP1 is never read), count 1, type SHORT or LONG, either byte
+// order.  Anything else -- no such segment, a bad TIFF header, an offset, an entry count or an entry that leaves the segment, another
+// type or count, a value outside 1..8 -- is 1: broken EXIF never refuses a stream.  Every byte is read inside [0, size).
+inline int jpeg_exif_orientation(const uint8_t* d, int64_t size) {
+    if (d == nullptr || size < 4 || size > JPEG_DEC_MAX_BYTES || d[0] != 0xFF || d[1] != 0xD8) return 1;
+    int64_t p = 2;
+    for (;;) {
+        int m, n;
+        const uint8_t* s;
+        if (jpeg_next_segment(d, size, false, p, m, s, n) != nullptr || m == 0xDA) return 1;
+        if (m != 0xE1 || n < 6 || std::memcmp(s, "Exif\0\0", 6) != 0) continue;
+        const uint8_t* const t = s + 6;      // the TIFF header: offsets count from here
+        const int64_t tn = n - 6;
+        if (tn < 8) return 1;
+        const bool le = t[0] == 'I' && t[1] == 'I';
+        if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+        const auto rd16 = [&](int64_t at) { return le ? int64_t(t[at]) | int64_t(t[at + 1]) << 8 : int64_t(t[at]) << 8 | int64_t(t[at + 1]); };
+        const auto rd32 = [&](int64_t at) { return le ? rd16(at) | rd16(at + 2) << 16 : rd16(at) << 16 | rd16(at + 2); };
+        if (rd16(2) != 42) return 1;
+        const int64_t ifd = rd32(4);
+        if (ifd > tn - 2) return 1;
+        const int64_t entries = rd16(ifd);
+        if (ifd + 2 + 12 * entries > tn) return 1;
+        for (int64_t e = ifd + 2; e < ifd + 2 + 12 * entries; e += 12) {
+            if (rd16(e) != 0x0112) continue;
+            const int64_t type = rd16(e + 2), count = rd32(e + 4);
+            if (count != 1 || (type != 3 && type != 4)) return 1;
+            const int64_t v = type == 3 ? rd16(e + 8) : rd32(e + 8);
+            return v >= 1 && v <= 8 ? int(v) : 1;
+        }
+        return 1;
+    }
+}
+
+// The oriented frame D of an upright frame u [h][w] (the EXIF standard's eight values; 5..8 turn rows into columns: D is w x h):
+// D[Y][X] = u[y][x].  Host and device.
+WHENET_HD inline bool jpeg_orient_ok(long long o) { return o >= 1 && o <= 8; }
+WHENET_HD inline int jpeg_orient_h(int o, int h, int w) { return o >= 5 ? w : h; }
+WHENET_HD inline int jpeg_orient_w(int o, int h, int w) { return o >= 5 ? h : w; }
+WHENET_HD inline bool jpeg_orient_flip_x(int o) { return o == 2 || o == 3 || o == 7 || o == 8; }      // x runs against its destination axis
+WHENET_HD inline bool jpeg_orient_flip_y(int o) { return o == 3 || o == 4 || o == 6 || o == 7; }
+WHENET_HD inline void jpeg_orient_source(int o, int h, int w, int Y, int X, int& y, int& x) {
+    const int sy = o >= 5 ? X : Y, sx = o >= 5 ? Y : X;
+    y = jpeg_orient_flip_y(o) ? h - 1 - sy : sy, x = jpeg_orient_flip_x(o) ? w - 1 - sx : sx;
+}
+// the header of a stream as the oriented frame's: the sides swapped for 5..8 (what a destination is checked and sized against)
+inline whenet_jpeg_info_t jpeg_orient_info(const whenet_jpeg_info_t& in, int o) {
+    whenet_jpeg_info_t out = in;
+    out.h = jpeg_orient_h(o, in.h, in.w), out.w = jpeg_orient_w(o, in.h, in.w);
+    return out;
+}
+
 // What a whenet_jpeg_info_t must satisfy before anything is computed from it (the parser's own output does; a caller of
 // whenet_jpeg_decode_device may have filled one by hand): a text, or nullptr
 inline const char* jpeg_dec_check_info(const whenet_jpeg_info_t& in) {
@@ -682,6 +736,26 @@ inline void jpeg_dec_frame_host(const JpegDecGeom& g, const JpegDecPlanes& pl, c
                 for (int x = 0; x < cw; ++x) o[2 * x] = s[x];
             }
         }
+}
+
+// the padded planes -> the ORIENTED frame in a packed destination of jpeg_orient_h x jpeg_orient_w pixels: the table of
+// jpeg_orient_source applied to the upright frame of the same rule (the statement the oriented frame kernels are held to)
+inline void jpeg_dec_frame_oriented_host(const JpegDecGeom& g, const JpegDecPlanes& pl, const whenet_surface_t& dst, int channel_order, int rule,
+                                         int orient) {
+    if (orient <= 1) return jpeg_dec_frame_host(g, pl, dst, channel_order, rule);
+    std::vector<uint8_t> up(size_t(g.h) * size_t(g.w) * 3);
+    whenet_surface_t u{};
+    u.plane[0] = up.data(), u.pitch[0] = 3 * g.w, u.format = WHENET_SURF_PACKED;
+    jpeg_dec_frame_host(g, pl, u, channel_order, rule);
+    const int oh = jpeg_orient_h(orient, g.h, g.w), ow = jpeg_orient_w(orient, g.h, g.w);
+    for (int Y = 0; Y < oh; ++Y) {
+        uint8_t* o = static_cast<uint8_t*>(dst.plane[0]) + size_t(Y) * size_t(dst.pitch[0]);
+        for (int X = 0; X < ow; ++X) {
+            int y, x;
+            jpeg_orient_source(orient, g.h, g.w, Y, X, y, x);
+            std::memcpy(o + 3 * X, up.data() + (size_t(y) * size_t(g.w) + size_t(x)) * 3, 3);
+        }
+    }
 }
 
 }  // namespace whenet

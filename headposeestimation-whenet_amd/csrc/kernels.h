@@ -688,6 +688,8 @@ void launch_jpeg_flush(const void* d_stream, void* to, const long long* d_size, 
 //   idct     8 lanes per block: both passes -> the component planes (padded to whole MCUs, pitches multiples of 8); status[0..1]
 //   frame    planes -> the destination: packed pixels in either channel order at any pitch (a tight BGR frame of a 4:2:0 stream:
 //            launch_yuv_planes_to_bgr), or an I420 / NV12 surface for a 4:2:0 stream.  No thread stores outside the rows' bytes.
+//            JpegDecArgs::orient = 2..8: the oriented frame kernel in its place (one launch all the same, no upright intermediate):
+//            the same pixel values at the destination addresses of the EXIF orientation, 5..8 through a 32 x 32 LDS tile.
 // JpegDecArgs::rule = 1 (libjpeg's bytes, packed destinations only) runs the rule-1 forms of idct and frame in their places.
 // JpegDecScratch lays the work buffers out in one allocation; tables | data at its front are what a caller uploads in one copy
 // (data_bytes = 0: the data lies elsewhere).
@@ -731,6 +733,8 @@ struct JpegDecArgs {
     int dst_pitch[3];
     int format, channel_order;
     int rule;                      // 0: the project's own inverse DCT and pixel rule, 1: libjpeg's (packed destinations only)
+    int orient;                    // the EXIF orientation the frame kernel applies: 0 or 1 upright; 2..8 (packed destinations only): dst is
+                                   // the oriented frame, jpeg_orient_h x jpeg_orient_w pixels (jpeg_dec_host.h)
     int32_t* status;               // two int32
     // the segmented form (form = 1)
     int form, seg_bytes, seg_cap;
@@ -747,7 +751,7 @@ void launch_jpeg_decode_segmented(const JpegDecArgs& a, hipStream_t stream);
 // JpegProgLayout::regions()).  Form 2, a progressive stream: a baseline record over the progressive layout -- what
 // launch_jpeg_decode_tail reads of it (coef, meta, planes, destination, rule; form 0) --, the fields of the segmented form empty.
 inline JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_base, const JpegClipFrame& q, long long nbytes, const whenet_surface_t& dst,
-                                 int channel_order, int32_t* d_status, int rule, int seg_lanes) {
+                                 int channel_order, int32_t* d_status, int rule, int seg_lanes, int orient = 1) {
     JpegDecArgs a{};
     char* const s = static_cast<char*>(d_base);
     a.g = g;
@@ -759,7 +763,7 @@ inline JpegDecArgs jpeg_dec_args(const JpegDecGeom& g, void* d_base, const JpegC
         a.plane[c] = reinterpret_cast<uint8_t*>(s + q.plane[c].off);
         a.dst[c] = static_cast<uint8_t*>(dst.plane[c]), a.dst_pitch[c] = dst.pitch[c];
     }
-    a.format = dst.format, a.channel_order = channel_order, a.rule = rule;
+    a.format = dst.format, a.channel_order = channel_order, a.rule = rule, a.orient = orient;
     a.status = d_status;
     if (q.form == JPEG_CLIP_FORM_PROGRESSIVE) return a;
     a.form = q.form, a.seg_bytes = q.seg_bytes, a.seg_cap = int(q.seg_cap), a.seg_lanes = seg_lanes;

@@ -189,6 +189,14 @@ _PROTOS = {
                                                          C.c_int]),
     "whenet_clip_begin_jpeg_progressive": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_jpeg_clip_plan_progressive": (C.c_int, [C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, _P]),
+    "whenet_jpeg_orientation": (C.c_int, [_P, C.c_int64]),
+    "whenet_jpeg_decode_oriented_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, _P]),
+    "whenet_op_jpeg_decode_oriented": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                                 _P, _P]),
+    "whenet_op_jpeg_decode_clip_oriented": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, _P]),
+    "whenet_frame_begin_jpeg_oriented": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "whenet_clip_begin_jpeg_oriented": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
     "whenet_profile": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(LaunchStat), C.c_int, C.POINTER(C.c_int)]),
     "whenet_op_stem": (C.c_int, [_P, _P, C.c_int, _P]),
     "whenet_op_block": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
@@ -801,6 +809,29 @@ def jpeg_decode_rule_host(data, surface: SurfaceC, bgr: bool, rule: str = "own")
                                           jpeg_rule_code(rule), _ptr(status))
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return status
+
+
+def jpeg_orientation(data) -> int:
+    """`whenet_jpeg_orientation`: the EXIF orientation (tag 0x0112 in IFD0 of the first Exif APP1) of a stream, 1..8; 1 for a stream
+    without one and for any broken EXIF structure.  Pure host arithmetic inside the library."""
+    lib = load()
+    a = _stream_array(data)
+    return int(lib.whenet_jpeg_orientation(_ptr(a) if a.size else None, int(a.size)))
+
+
+def jpeg_tristate(v) -> int:
+    """None -> -1 (the handle's option), else 0 / 1."""
+    return -1 if v is None else int(bool(v))
+
+
+def jpeg_decode_oriented_host(data, surface: SurfaceC, bgr: bool, rule: str = "own", progressive: bool = False) -> np.ndarray:
+    """`whenet_jpeg_decode_oriented_host` into a packed host surface of the ORIENTED size: the two status words."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    _host_rc(lib, lib.whenet_jpeg_decode_oriented_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB,
+                                                       jpeg_rule_code(rule), int(bool(progressive)), _ptr(status)))
     return status
 
 
@@ -1679,6 +1710,54 @@ class Handle:
                                                                      BGR if bgr else RGB, _ptr(status) if status.size else None,
                                                                      int(entropy), int(seg_bytes), jpeg_rule_code(rule)))
         return status
+
+    def op_jpeg_decode_oriented(self, data, surface: SurfaceC, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None,
+                                progressive=None, orient=True):
+        """`whenet_op_jpeg_decode_oriented`: the kernels alone into a surface of the ORIENTED size; progressive / orient: None (the
+        handle's option), False or True: (the two status words, the statistics int64 [8], the orientation applied)."""
+        a = _stream_array(data)
+        status, stats, applied = np.zeros(2, np.int32), np.zeros(8, np.int64), np.ones(1, np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_oriented(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
+                                                             BGR if bgr else RGB, int(entropy), int(seg_bytes), jpeg_rule_code(rule),
+                                                             jpeg_tristate(progressive), jpeg_tristate(orient), _ptr(status), _ptr(stats),
+                                                             _ptr(applied)))
+        return status, stats, int(applied[0])
+
+    def op_jpeg_decode_clip_oriented(self, datas, surfaces, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None,
+                                     progressive: bool = False, orient: bool = True):
+        """`whenet_op_jpeg_decode_clip_oriented`: (the status words int32 [F,2], the orientation applied to each frame int32 [F])."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        surf = (SurfaceC * max(len(surfaces), 1))(*surfaces)
+        status, applied = np.zeros((len(arrs), 2), np.int32), np.ones(max(len(arrs), 1), np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_clip_oriented(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
+                                                                  BGR if bgr else RGB, _ptr(status) if status.size else None, int(entropy),
+                                                                  int(seg_bytes), jpeg_rule_code(rule), int(bool(progressive)),
+                                                                  int(bool(orient)), _ptr(applied)))
+        return status, applied[:len(arrs)]
+
+    def frame_begin_jpeg_oriented(self, data, status: np.ndarray, bgr: bool = True, rule=None, progressive=None, orient=True):
+        """`whenet_frame_begin_jpeg_oriented`: `frame_begin_jpeg` whose frame is the oriented one; progressive / orient: None (the
+        handle's option), False or True: (ticket, the orientation applied)."""
+        a = _stream_array(data)
+        if status.dtype != np.int32 or status.size != 2 or not status.flags.c_contiguous:
+            raise ValueError("status must be a contiguous int32 [2] array")
+        t, applied = C.c_int(-1), np.ones(1, np.int32)
+        self._check(self._lib.whenet_frame_begin_jpeg_oriented(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB,
+                                                               jpeg_rule_code(rule), jpeg_tristate(progressive), jpeg_tristate(orient),
+                                                               C.byref(t), _ptr(status), _ptr(applied)))
+        return t.value, int(applied[0])
+
+    def clip_begin_jpeg_oriented(self, datas, status: np.ndarray, bgr: bool = True, rule=None, progressive: bool = False, orient: bool = True):
+        """`whenet_clip_begin_jpeg_oriented`: `clip_begin_jpeg` whose frames are the oriented ones: (ticket, the orientations int32 [F])."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        if status.dtype != np.int32 or status.size != 2 * len(arrs) or not status.flags.c_contiguous:
+            raise ValueError("status must be a contiguous int32 [F,2] array")
+        t, applied = C.c_int(-1), np.ones(max(len(arrs), 1), np.int32)
+        self._check(self._lib.whenet_clip_begin_jpeg_oriented(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs),
+                                                              BGR if bgr else RGB, jpeg_rule_code(rule), int(bool(progressive)),
+                                                              int(bool(orient)), C.byref(t), _ptr(status) if status.size else None,
+                                                              _ptr(applied)))
+        return t.value, applied[:len(arrs)]
 
     def jpeg_clip_counters(self) -> dict:
         """`whenet_jpeg_clip_counters`: host-side counts over the handle's engines: {"clips", "frames", "enqueues" (kernel launches plus

@@ -113,6 +113,12 @@ class JpegStatus:
     def __init__(self):
         self._status = np.zeros(2, np.int32)
         self._done = False
+        self._orientation = 1
+
+    @property
+    def orientation(self) -> int:
+        """The EXIF orientation that was applied to the frame, 1..8 (1 where the decode was not an oriented one)."""
+        return self._orientation
 
     @property
     def ready(self) -> bool:
@@ -284,7 +290,7 @@ class FramePipeline:
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
 
-    def begin_jpeg(self, data, rule=None, progressive=None) -> "JpegStatus":
+    def begin_jpeg(self, data, rule=None, progressive=None, orient=None) -> "JpegStatus":
         """`begin()` from the bytes of a baseline JPEG stream (a still, or one frame of an MJPG file: `whenet_hip.mjpeg.MJPGReader`):
         what stands for `cv2.imread` / `cap.read()`.  Only the compressed bytes cross the link; the frame is decoded on the device
         (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
@@ -296,20 +302,28 @@ class FramePipeline:
         `cv2.imread` gives) unless `rule` says "own" or "libjpeg" for this frame; the frame is then what
         `jpeg.decode_host(data, rule=...)` makes.  `progressive`: True also accepts a progressive (SOF2) stream -- the frame is then
         `jpeg.decode_host(data, progressive=True, rule=...)`, and `JpegStatus.interval` is the flat (scan, interval) item; None
-        (the default) follows the handle's option "jpeg_progressive" (0: refused, the default)."""
+        (the default) follows the handle's option "jpeg_progressive" (0: refused, the default).  `orient`: True applies the
+        stream's EXIF orientation as `cv2.imread` does -- the frame is `jpeg.decode_host(data, orient=True, ...)`, turned by the
+        kernel that writes it, and everything that follows (boxes included) is in the upright picture's coordinates; None (the
+        default) follows the handle's option "jpeg_orient" (0: the tag is ignored, the default).  `JpegStatus.orientation` is
+        the value applied."""
         self._check_can_begin()
         _lib.jpeg_rule_code(rule)
         info = _lib.jpeg_parse(data) if progressive is False else _lib.jpeg_parse_scans(data)[0]
         st = JpegStatus()
-        ticket = self._h.frame_begin_jpeg(data, st._status, bgr=self._bgr, rule=rule, progressive=progressive)
+        # (always the call that carries `orient`: False must switch the turn off on a handle whose option is on; and as in
+        # Handle.frame_begin_jpeg a progressive of False leaves SOF2 to the handle's option)
+        ticket, st._orientation = self._h.frame_begin_jpeg_oriented(data, st._status, bgr=self._bgr, rule=rule,
+                                                                    progressive=progressive or None, orient=orient)
         if self._jpeg is None:
             self._jpeg = {}
         self._jpeg.setdefault(ticket, []).append(st)
-        self._begun = (ticket, info.h, info.w)
-        self._last_sizes = [(info.h, info.w)]
+        h, w = (info.w, info.h) if st._orientation >= 5 else (info.h, info.w)
+        self._begun = (ticket, h, w)
+        self._last_sizes = [(h, w)]
         return st
 
-    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False) -> list:
+    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False, orient: bool = False) -> list:
         """A clip from the bytes of 1..16 baseline JPEG streams (consecutive frames of an MJPG file: `MJPGReader.clips(16)`), each
         with its own size, sampling, tables and DRI: one upload of the compressed bytes, every decoder stage in one launch for all
         frames.  Frame f is what `begin_jpeg(datas[f])` makes; frames of one size make a clip as `begin_clip()` makes it, frames of
@@ -320,7 +334,9 @@ class FramePipeline:
         progressive=True: progressive (SOF2) streams are accepted too, alone or mixed with baseline ones (a folder of stills:
         `demo.py` walks Sample/*.jpeg) -- frame f is then what `begin_jpeg(datas[f], progressive=True)` makes, and
         `JpegStatus.interval` of a progressive frame is its flat (scan, interval) item.  Clips do not read the handle's option
-        "jpeg_progressive": only this argument accepts SOF2."""
+        "jpeg_progressive": only this argument accepts SOF2.  orient=True: every frame by its own EXIF orientation, as
+        `begin_jpeg(datas[f], orient=True)`; a clip is one-size by the sizes of the turned frames.  Clips do not read the option
+        "jpeg_orient" either."""
         self._check_can_begin()
         _lib.jpeg_rule_code(rule)
         datas = list(datas)
@@ -333,17 +349,22 @@ class FramePipeline:
             except ValueError as e:
                 raise ValueError(f"begin_clip_jpeg: frame {i}: {e}") from None
         block = np.zeros((len(datas), 2), np.int32)      # (one array for the library to write; every JpegStatus is a row of it)
-        ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr, rule=rule, progressive=progressive)
+        applied = np.ones(len(datas), np.int32)
+        if orient:
+            ticket, applied = self._h.clip_begin_jpeg_oriented(datas, block, bgr=self._bgr, rule=rule, progressive=progressive, orient=True)
+        else:
+            ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr, rule=rule, progressive=progressive)
         sts = []
         for f in range(len(datas)):
             st = JpegStatus()
             st._status = block[f]
+            st._orientation = int(applied[f])
             sts.append(st)
         if self._jpeg is None:
             self._jpeg = {}
         self._jpeg.setdefault(ticket, []).extend(sts)
         self._begun_clip = (ticket, len(datas))
-        self._last_sizes = [(i.h, i.w) for i in infos]
+        self._last_sizes = [(i.w, i.h) if o >= 5 else (i.h, i.w) for i, o in zip(infos, applied)]
         return sts
 
     def begin_clip_yuv(self, frames, stream=None) -> None:

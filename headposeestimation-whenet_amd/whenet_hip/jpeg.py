@@ -140,6 +140,17 @@ def info(data, progressive: bool = False) -> dict:
     return out
 
 
+def orientation(data) -> int:
+    """The EXIF orientation of a stream, 1..8 (`whenet_jpeg_orientation`): tag 0x0112 in IFD0 of the first Exif APP1 in front of SOS,
+    either byte order, type SHORT or LONG.  1 for a stream without the tag and for any broken EXIF structure: it never raises."""
+    return _lib.jpeg_orientation(data)
+
+
+def oriented_shape(h: int, w: int, value: int):
+    """(rows, columns) of the oriented frame of an h x w stream: the sides swap for the values 5..8."""
+    return (w, h) if value >= 5 else (h, w)
+
+
 def packed_surface(frame: np.ndarray) -> "_lib.SurfaceC":
     """A uint8 [H,W,3] host array whose rows' pixels are packed (any row stride) as a destination surface."""
     s = _lib.SurfaceC()
@@ -154,8 +165,16 @@ def _result(frame: np.ndarray, status: np.ndarray, strict: bool):
     return frame
 
 
+def _run_decode(handle, data, frame, bgr, entropy, seg_bytes, rule, progressive, orient):
+    """(status, statistics) of `whenet_op_jpeg_decode_oriented` into `frame`; handle None: a postproc handle on device 0 for the call"""
+    if handle is None:
+        with _lib.Handle.postproc(0) as own:
+            return own.op_jpeg_decode_oriented(data, packed_surface(frame), bgr, entropy, seg_bytes, rule, progressive, orient)[:2]
+    return _handle_of(handle).op_jpeg_decode_oriented(data, packed_surface(frame), bgr, entropy, seg_bytes, rule, progressive, orient)[:2]
+
+
 def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False,
-           rule: str = "own", progressive: bool = False):
+           rule: str = "own", progressive: bool = False, orient: bool = False):
     """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
     (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
     Damaged data raises `DecodeError` (strict=False: returns the defined frame).  `entropy`: the form of the entropy stage --
@@ -167,19 +186,28 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     libjpeg-turbo decode with its defaults: what `cv2.imread` and Pillow give; `whenet_op_jpeg_decode_rule`).  "own" goes through
     the calls that read the handle's option "jpeg_rule", whose default it is.  progressive=True also accepts a progressive (SOF2)
     stream (`whenet_op_jpeg_decode_progressive`; `DecodeError.interval` is then the flat (scan, interval) item, and stats are items,
-    levels, scans, scan-kernel launches); `entropy` and `seg_bytes` apply where the stream is baseline and are ignored otherwise."""
+    levels, scans, scan-kernel launches); `entropy` and `seg_bytes` apply where the stream is baseline and are ignored otherwise.
+    orient=True (`whenet_op_jpeg_decode_oriented`): the stream's EXIF orientation (`orientation(data)`) is applied by the frame kernel
+    itself, as `cv2.imread` applies it: the frame is `decode_host(data, orient=True, ...)`, its sides swapped for the values 5..8.
+    orient=False is an upright decode on every handle: every path here goes through that call with `orient` stated, so the handle's
+    option "jpeg_orient" (which the plain C calls read) never turns a frame this function sized upright."""
     if entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be 'auto', 'interval' or 'segmented'")
     _lib.jpeg_rule_code(rule)
+    if orient:
+        i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
+        frame = np.empty(oriented_shape(i.h, i.w, orientation(data)) + (3,), np.uint8)
+        form, seg = _lib.JPEG_ENTROPY[entropy], 128 if seg_bytes is None else int(seg_bytes)
+        if form == 2 and seg_bytes is not None:
+            form = 1 if (int(_lib._stream_array(data).size) - i.data_offset) // max(i.intervals, 1) >= _lib.JPEG_SEG_AUTO_BYTES else 0
+        status, st = _run_decode(handle, data, frame, bgr, -1 if form == 2 else form, seg, rule, bool(progressive), True)
+        out = _result(frame, status, strict)
+        return (out, st) if stats else out
     if progressive:
         i, scans = _lib.jpeg_parse_scans(data)
         if scans[0].progressive:      # a SOF2 stream
             frame = np.empty((i.h, i.w, 3), np.uint8)
-            if handle is None:
-                with _lib.Handle.postproc(0) as own:
-                    status, st = own.op_jpeg_decode_progressive(data, packed_surface(frame), bgr, rule)
-            else:
-                status, st = _handle_of(handle).op_jpeg_decode_progressive(data, packed_surface(frame), bgr, rule)
+            status, st = _run_decode(handle, data, frame, bgr, -1, 128, rule, True, False)      # (what whenet_op_jpeg_decode_progressive runs)
             out = _result(frame, status, strict)
             return (out, st) if stats else out
     i = _lib.jpeg_parse(data)
@@ -188,24 +216,14 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     if form == 2 and (stats or seg_bytes is not None):
         form = 1 if (int(_lib._stream_array(data).size) - i.data_offset) // max(i.intervals, 1) >= _lib.JPEG_SEG_AUTO_BYTES else 0
 
-    def run(h):
-        if rule != "own":
-            return h.op_jpeg_decode_rule(data, packed_surface(frame), bgr, -1 if form == 2 else form, seg, rule)
-        if form == 2:
-            return h.op_jpeg_decode(data, packed_surface(frame), bgr), None
-        return h.op_jpeg_decode_ex(data, packed_surface(frame), bgr, form, seg)
-
-    if handle is None:
-        with _lib.Handle.postproc(0) as own:
-            status, st = run(own)
-    else:
-        status, st = run(_handle_of(handle))
+    # (rule "own" and SOF2 are left to the handle's options "jpeg_rule" / "jpeg_progressive", as whenet_op_jpeg_decode[_ex] leave them)
+    status, st = _run_decode(handle, data, frame, bgr, -1 if form == 2 else form, seg, None if rule == "own" else rule, None, False)
     out = _result(frame, status, strict)
     return (out, st) if stats else out
 
 
 def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True, rule: str = "own",
-                progressive: bool = False):
+                progressive: bool = False, orient: bool = False):
     """(frames, statuses) of 1..16 baseline JPEG streams decoded as ONE clip by the kernels (`whenet_op_jpeg_decode_clip`): a list of
     uint8 [H_f,W_f,3] frames and the status words int32 [F,2].  Frame f is `decode(datas[f])`, bit for bit.  `entropy`: None or
     "auto" (the handle's options, stream by stream), "interval" or "segmented" (`seg_bytes`: None = 128).  A stream the decoder does
@@ -214,7 +232,9 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     progressive=True (`whenet_op_jpeg_decode_clip_progressive`): progressive (SOF2) streams are accepted too, alone or next to
     baseline ones -- a folder of stills as one clip.  Frame f is then `decode_host(datas[f], rule=rule, progressive=True)` with its
     status; the scan kernel is launched once per level for all progressive frames together, and `entropy` / `seg_bytes` apply to
-    the baseline frames.  The handle's option "jpeg_progressive" is not read by clips: only this argument accepts SOF2."""
+    the baseline frames.  The handle's option "jpeg_progressive" is not read by clips: only this argument accepts SOF2.
+    orient=True (`whenet_op_jpeg_decode_clip_oriented`): every frame by its own EXIF orientation -- frame f is
+    `decode_host(datas[f], orient=True, ...)` --, upright and turned frames in one clip, at most one launch more than without."""
     _lib.jpeg_rule_code(rule)
     if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be None, 'auto', 'interval' or 'segmented'")
@@ -227,11 +247,13 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
             i = _lib.jpeg_parse_scans(d)[0] if progressive else _lib.jpeg_parse(d)
         except ValueError as e:
             raise ValueError(f"decode_clip: frame {f}: {e}") from None
-        frames.append(np.empty((i.h, i.w, 3), np.uint8))
+        frames.append(np.empty((oriented_shape(i.h, i.w, orientation(d)) if orient else (i.h, i.w)) + (3,), np.uint8))
     form = -1 if entropy in (None, "auto") else _lib.JPEG_ENTROPY[entropy]
     seg = 128 if seg_bytes is None else int(seg_bytes)
     surfaces = [packed_surface(fr) for fr in frames]
     def run(h):
+        if orient:
+            return h.op_jpeg_decode_clip_oriented(datas, surfaces, bgr, form, seg, rule, bool(progressive), True)[0]
         if progressive:
             return h.op_jpeg_decode_clip_progressive(datas, surfaces, bgr, form, seg, rule)
         if rule != "own":
@@ -253,11 +275,17 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     return frames, status
 
 
-def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", progressive: bool = False) -> np.ndarray:
+def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", progressive: bool = False, orient: bool = False) -> np.ndarray:
     """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
     held to.  `rule`: "own" or "libjpeg", as `decode` (`whenet_jpeg_decode_rule_host`).  progressive=True: a progressive (SOF2)
-    stream is accepted too (`whenet_jpeg_decode_progressive_host`)."""
+    stream is accepted too (`whenet_jpeg_decode_progressive_host`).  orient=True (`whenet_jpeg_decode_oriented_host`): the EXIF
+    orientation applied to that frame -- with u the upright frame and t = u.transpose(1, 0, 2): 1 u, 2 u[:, ::-1], 3 u[::-1, ::-1],
+    4 u[::-1], 5 t, 6 t[:, ::-1], 7 t[::-1, ::-1], 8 t[::-1]."""
     _lib.jpeg_rule_code(rule)
+    if orient:
+        i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
+        frame = np.empty(oriented_shape(i.h, i.w, orientation(data)) + (3,), np.uint8)
+        return _result(frame, _lib.jpeg_decode_oriented_host(data, packed_surface(frame), bgr, rule, progressive), strict)
     if progressive:
         i = _lib.jpeg_parse_scans(data)[0]
         frame = np.empty((i.h, i.w, 3), np.uint8)

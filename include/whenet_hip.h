@@ -1134,7 +1134,41 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  * scan launches once per clip and the scans of all its frames.
  * Not built: a segmented (many lanes per interval) form for progressive scans -- a scan without DRI is ONE lane --, SOF0 / SOF1
  * streams of several scans, scans of two components, arithmetic, 12-bit and CMYK streams, block smoothing, a progressive
- * encoder, streams already in device memory. */
+ * encoder, streams already in device memory.
+ *
+ * JPEG DECODER, ORIENTATION (six entry points, ABI still 6; the parser is csrc/jpeg_dec_host.h's jpeg_exif_orientation, the kernels
+ * are the oriented frame kernels of csrc/jpeg_dec.hip).  Phone and camera stills are stored in sensor order with the EXIF
+ * orientation tag (0x0112) set, and cv2.imread returns them upright.  The oriented decode is OPT-IN: every call above ignores the
+ * tag, the six below apply it, and whenet_frame_begin_jpeg[_rule|_progressive] / whenet_op_jpeg_decode[_ex|_rule|_progressive] on a
+ * handle whose option "jpeg_orient" is 1 (default 0) apply it too; the clip calls take the argument only.
+ * THE TAG.  The marker segments from SOI to the first SOS; the FIRST APP1 whose payload starts with "Exif\0\0" (an XMP APP1 in front
+ * of it is passed, a second Exif APP1 is never read); behind it the TIFF header ("II" or "MM", 42, the offset of IFD0); in IFD0
+ * only, at any position, the entry with tag 0x0112, count 1 and type SHORT (3) or LONG (4).  A value outside 1..8, another type or
+ * count, a bad header, an offset, an entry count or an entry that leaves the segment, no such segment: 1.  Broken EXIF never
+ * refuses a stream and never changes its status; SOF0 and SOF2 streams are read alike.
+ * THE FRAME.  With u the upright frame [h][w] of the same rule and t its transpose [w][h], the oriented frame is
+ *     1: u    2: u[:, ::-1]    3: u[::-1, ::-1]    4: u[::-1]           (h x w)
+ *     5: t    6: t[:, ::-1]    7: t[::-1, ::-1]    8: t[::-1]           (w x h)
+ * byte for byte, under both rules and both channel orders: the pixel of source position (y, x) is what the upright kernels compute,
+ * only its destination differs.  The destination (and a slot's frame, with everything behind it: letterbox, detector, crops,
+ * overlay, boxes) has the ORIENTED size: for 5..8 w rows of at least 3 h bytes.  The oriented frame kernel takes the frame kernel's
+ * place: 2..4 reverse and mirror a lane's 4-pixel group, 5..8 stage a 32 x 32 tile of the DESTINATION through LDS; no upright frame
+ * exists in device memory, the work buffers do not grow, a single decode enqueues what the upright one enqueues and a clip with
+ * turned frames at most one launch more.  A stream with value 1 runs exactly the upright launches.  Damage: the status pair is
+ * the upright decode's, the frame the orientation of its defined frame.  Oriented decodes write WHENET_SURF_PACKED only: a stream
+ * with a value 2..8 and an I420 / NV12 destination is WHENET_EINVAL (nothing is enqueued).
+ *   whenet_jpeg_orientation             pure host: 1..8 (NULL or no stream: 1)
+ *   whenet_jpeg_decode_oriented_host    the host statement: the table applied to the host decode by `rule` (0 / 1); progressive = 1
+ *                  also accepts SOF2
+ *   whenet_op_jpeg_decode_oriented      the kernels alone; entropy, seg_bytes, rule as whenet_op_jpeg_decode_rule; progressive and
+ *                  orient -1 (the handle's option), 0 or 1; *orientation (may be NULL) = the value applied, 1 where orient is off
+ *   whenet_op_jpeg_decode_clip_oriented the arguments of whenet_op_jpeg_decode_clip_rule, progressive and orient 0 or 1, orientation
+ *                  (may be NULL) int32 [num_frames]; every frame has its own value; upright and turned frames share a clip
+ *   whenet_frame_begin_jpeg_oriented, whenet_clip_begin_jpeg_oriented   the resident-frame calls, the same arguments: the slot is what
+ *                  whenet_frame_begin / whenet_clip_begin[_mixed] of the oriented frames leaves; a clip is one-size by its ORIENTED sizes
+ *   option "jpeg_orient"   0 (default) / 1, above.
+ * Not built: oriented I420 / NV12 destinations, whenet_jpeg_decode_device (it sees no header), an orientation stored anywhere but IFD0
+ * of the first Exif APP1, other EXIF tags. */
 #define WHENET_JPEG_SEG_WINDOW 256
 #define WHENET_JPEG_PROG_MAX_SCANS 128
 #define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
@@ -1221,6 +1255,20 @@ WHENET_API int whenet_clip_begin_jpeg_progressive(whenet_t* h, const uint8_t* co
                                        int rule, int* ticket, int32_t* status);
 WHENET_API int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t* size, int num_frames, int entropy, int seg_bytes,
                                       int64_t* out);
+
+WHENET_API int whenet_jpeg_orientation(const uint8_t* data, int64_t size);
+WHENET_API int whenet_jpeg_decode_oriented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
+                                     int progressive, int32_t status[2]);
+WHENET_API int whenet_op_jpeg_decode_oriented(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order,
+                                   int entropy, int seg_bytes, int rule, int progressive, int orient, int32_t status[2], int64_t stats[8],
+                                   int32_t* orientation);
+WHENET_API int whenet_op_jpeg_decode_clip_oriented(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames,
+                                        const whenet_surface_t* dst, int channel_order, int32_t* status, int entropy, int seg_bytes, int rule,
+                                        int progressive, int orient, int32_t* orientation);
+WHENET_API int whenet_frame_begin_jpeg_oriented(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int progressive,
+                                     int orient, int* ticket, int32_t* status, int32_t* orientation);
+WHENET_API int whenet_clip_begin_jpeg_oriented(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order,
+                                    int rule, int progressive, int orient, int* ticket, int32_t* status, int32_t* orientation);
 
 /* ---- measurement: run `iters` eager forwards of `n` device-resident crops exactly as the
  * timed path runs them (same concurrent sub-batch chains, same streams) with ONE HIP event

@@ -53,7 +53,16 @@
                                 1080p stream without DRI: seconds per frame), --slow-samples regions after one warm-up region, and
                                 "..._regions" says how many were taken.  "enqueues", "h2d", "scan_launches" per clip: the counters.
 
-  python tools/jpeg_dec_bench.py [--progressive] [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
+    (viii) --orient N [N ...]   the oriented decode (recorded, not gated), INSTEAD of (i)-(vii): Pillow's stream of the picture (quality
+                                95, 4:2:0, one interval per MCU row) with an Exif APP1 of each value N spliced in, through
+                                whenet_frame_begin_jpeg_oriented in the same process: ms per frame for begin -> release without heads ->
+                                collect, the median of --clip-samples (>= 20) regions after 3 warm-up ones and their 10th..90th
+                                percentiles (the method of row (vi)); every frame is checked against the host statement first.  Value 1
+                                runs the upright launches, 2..4 the oriented frame kernel's row form, 5..8 its LDS tile form: the
+                                kernels' own times come from a kernel trace of this row (--rgb or --rule 1 puts the upright frame
+                                through the frame kernel too, so that the three can be read side by side).
+
+  python tools/jpeg_dec_bench.py [--progressive] [--orient 1 3 6] [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
                                  [--lanes 0] [--rule 0] [--rgb] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
                                  [--slow-seconds 5] [--slow-samples 20]
 
@@ -374,6 +383,52 @@ def prog_clip_leg(m, h, w, args):
     return res
 
 
+def exif_app1(value):
+    """a big-endian Exif APP1 whose IFD0 holds the orientation tag alone"""
+    import struct
+    tiff = b"MM" + struct.pack(">HI", 42, 8) + struct.pack(">H", 1) + struct.pack(">HHIHH", 0x0112, 3, 1, value, 0) + struct.pack(">I", 0)
+    payload = b"Exif\0\0" + tiff
+    return b"\xff\xe1" + struct.pack(">H", len(payload) + 2) + payload
+
+
+def orient_leg(m, h, w, args):
+    """row (viii): one stream per orientation value through whenet_frame_begin_jpeg_oriented, begin -> release -> collect"""
+    import torch
+    from PIL import Image
+    from whenet_hip import jpeg, synth
+    hnd = m._handle
+    sync = torch.cuda.synchronize
+    no_heads = np.zeros((0, 4), np.int32)
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(synth.video_frame(h, w)[..., ::-1])).save(buf, "JPEG", quality=95, subsampling=2, restart_marker_rows=1)
+    plain = buf.getvalue()
+    app0_end = 4 + ((plain[4] << 8) | plain[5])
+    res = {"frame": [h, w], "rule": args.rule, "rgb": bool(args.rgb), "bytes_jpeg": len(plain), "orient": {}}
+    status = np.zeros(2, np.int32)
+    for value in args.orient:
+        data = plain[:app0_end] + exif_app1(value) + plain[app0_end:]
+        want = jpeg.decode_host(data, bgr=not args.rgb, rule=RULES[args.rule], orient=True)
+        got = jpeg.decode(data, handle=hnd, bgr=not args.rgb, rule=RULES[args.rule], orient=True)
+
+        def begin():
+            t, _ = hnd.frame_begin_jpeg_oriented(data, status, bgr=not args.rgb)
+            hnd.frame_heads(t, no_heads)
+            hnd.collect(t, 0)
+
+        for _ in range(3):
+            begin()
+        ms = []
+        for _ in range(max(20, args.clip_samples)):
+            sync()
+            t = time.perf_counter()
+            begin()
+            ms.append((time.perf_counter() - t) * 1e3)
+        q = np.percentile(ms, [10, 50, 90])
+        res["orient"][str(value)] = {"applied": jpeg.orientation(data), "shape": list(want.shape[:2]), "equals_host": bool(np.array_equal(got, want)),
+                                     "ms": round(float(q[1]), 3), "p10_p90": [round(float(q[0]), 3), round(float(q[2]), 3)]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
@@ -388,6 +443,7 @@ def main():
     ap.add_argument("--clip", type=int, nargs="+", default=None, help="row (v) only: frames per clip of JPEG streams, 1..16 each")
     ap.add_argument("--clip-samples", type=int, default=20, help="regions per figure of row (v), at least 20")
     ap.add_argument("--progressive", action="store_true", help="row (vi) only: progressive streams against their baseline twins; with --clip: row (vii)")
+    ap.add_argument("--orient", type=int, nargs="+", default=None, choices=range(1, 9), help="row (viii) only: EXIF orientation values to time")
     ap.add_argument("--slow-seconds", type=float, default=5.0, help="row (vii): a region longer than this counts as slow")
     ap.add_argument("--slow-samples", type=int, default=20, help="row (vii): regions per figure where one region is slow (after ONE warm-up region)")
     args = ap.parse_args()
@@ -400,6 +456,8 @@ def main():
         for size in args.sizes:
             h, w = (int(v) for v in size.split("x"))
             leg = (prog_clip_leg if args.clip else prog_leg) if args.progressive else (clip_leg if args.clip else size_leg)
+            if args.orient:
+                leg = orient_leg
             print(json.dumps(leg(m, h, w, args)), flush=True)
     finally:
         m.close()
