@@ -1436,6 +1436,17 @@ int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t*
 // ---- oriented decode (JPEG DECODER, ORIENTATION; jpeg_dec_host.h: jpeg_exif_orientation, jpeg_dec.hip: the oriented frame kernels) ----
 int whenet_jpeg_orientation(const uint8_t* data, int64_t size) { return whenet::jpeg_exif_orientation(data, size); }
 
+// ---- default Huffman tables (JPEG DECODER, DEFAULT TABLES; jpeg_dec_host.h: jpeg_add_default_tables) ----
+int whenet_jpeg_add_default_tables(const uint8_t* data, int64_t size, uint8_t* out, int64_t capacity, int64_t* out_size) {
+    return host_statement([&] {
+        WHENET_REQUIRE(data != nullptr && out != nullptr && out_size != nullptr, WHENET_EINVAL, "jpeg_add_default_tables: NULL argument");
+        WHENET_REQUIRE(size >= 0 && capacity >= 0 && capacity - whenet::JPEG_DEFAULT_TABLES_MAX >= size, WHENET_EINVAL,
+                       "jpeg_add_default_tables: capacity " + std::to_string(capacity) + " is below size + " +
+                           std::to_string(whenet::JPEG_DEFAULT_TABLES_MAX) + " = " + std::to_string(size + whenet::JPEG_DEFAULT_TABLES_MAX));
+        *out_size = whenet::jpeg_add_default_tables(data, size, out);
+    });
+}
+
 int whenet_jpeg_decode_oriented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule, int progressive,
                                      int32_t status[2]) {
     return host_statement([&] {

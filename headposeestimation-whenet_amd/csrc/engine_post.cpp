@@ -345,7 +345,7 @@ struct YuvLayout {
     size_t src[MIXED_MAX_FRAMES + 1] = {}, dst[MIXED_MAX_FRAMES + 1] = {};
     YuvLayout(const whenet_yuv_frame_t* frames, int nframes) {
         for (int f = 0; f < nframes; ++f) {
-            src[f + 1] = src[f] + yuv_plane_bytes(frames[f].h, frames[f].w);
+            src[f + 1] = src[f] + yuv_plane_bytes(frames[f].h, frames[f].w, frames[f].format);
             dst[f + 1] = dst[f] + size_t(frames[f].h) * frames[f].w * 3;
         }
     }
@@ -405,7 +405,8 @@ int Engine::frame_begin_yuv(const whenet_yuv_frame_t& frame) {
     Slot& slot = *free_slot();
     ensure_slot(slot, 1);
     const YuvLayout lay(&frame, 1);
-    slot.frame.h.grow(lay.dst[1]);      // (>= the planes' bytes: the size every other user of the staging grows it to)
+    // (the size every other user of the staging grows it to; the planes are fewer bytes, but for a packed 4:2:2 frame 1 pixel wide)
+    slot.frame.h.grow(std::max(lay.dst[1], lay.src[1]));
     slot.yuv.grow(lay.src[1]);
     slot.frame.d.grow(lay.dst[1]);
     enqueue_yuv_ingest(&frame, 1, slot.frame.h.as<uint8_t>(), slot.yuv.as<uint8_t>(), slot.frame.d.as<uint8_t>(), lay.dst, copy_stream());
@@ -426,7 +427,7 @@ int Engine::clip_begin_yuv(const whenet_yuv_frame_t* frames, int nframes) {
     Slot& slot = *free_slot();
     ensure_slot(slot, 1);
     const YuvLayout lay(frames, nframes);
-    slot.frame.h.grow(lay.dst[nframes]);
+    slot.frame.h.grow(std::max(lay.dst[nframes], lay.src[nframes]));
     slot.yuv.grow(lay.src[nframes]);
     slot.frame.d.grow(lay.dst[nframes]);
     enqueue_yuv_ingest(frames, nframes, slot.frame.h.as<uint8_t>(), slot.yuv.as<uint8_t>(), slot.frame.d.as<uint8_t>(), lay.dst, copy_stream());
@@ -483,12 +484,9 @@ void Engine::check_device_yuv_frames(const char* what, const whenet_yuv_frame_t*
     check_yuv_frames(what, frames, nframes);
     for (int i = 0; i < nframes; ++i) {
         const whenet_yuv_frame_t& f = frames[i];
-        const int cw = (f.w + 1) >> 1, ch = (f.h + 1) >> 1;
-        const bool nv12 = f.format == WHENET_YUV_NV12;
-        const int rows[3] = {f.h, ch, ch}, row_bytes[3] = {f.w, nv12 ? 2 * cw : cw, cw};
-        for (int p = 0; p < (nv12 ? 2 : 3); ++p)
-            check_device_plane(std::string(what) + ": frame " + std::to_string(i) + ": plane " + std::to_string(p), f.plane[p], rows[p],
-                               f.pitch[p], row_bytes[p]);
+        for (int p = 0; p < yuv_plane_count(f.format); ++p)
+            check_device_plane(std::string(what) + ": frame " + std::to_string(i) + ": plane " + std::to_string(p), f.plane[p],
+                               yuv_plane_rows(f.format, p, f.h), f.pitch[p], yuv_plane_row_bytes(f.format, p, f.w));
     }
 }
 
@@ -518,8 +516,7 @@ YuvPlanes yuv_planes(const whenet_yuv_frame_t* frames, int nframes, const size_t
     clip.frames = nframes;
     for (int f = 0; f < nframes; ++f) {
         YuvPlanesFrame& g = clip.f[f];
-        const bool nv12 = frames[f].format == WHENET_YUV_NV12;
-        for (int p = 0; p < (nv12 ? 2 : 3); ++p) g.plane[p] = frames[f].plane[p], g.pitch[p] = frames[f].pitch[p];
+        for (int p = 0; p < yuv_plane_count(frames[f].format); ++p) g.plane[p] = frames[f].plane[p], g.pitch[p] = frames[f].pitch[p];
         g.h = frames[f].h, g.w = frames[f].w, g.format = frames[f].format;
         g.k = yuv_coeffs(frames[f].matrix);
         g.dst_off = off[f];

@@ -226,6 +226,54 @@ inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t
     }
 }
 
+// ---- default Huffman tables (pure host; include/whenet_hip.h, JPEG DECODER, DEFAULT TABLES) ----
+// MJPG frames of UVC cameras and of many AVI writers carry no DHT: their tables are T.81's Annex K ones, which every player installs
+// (libjpeg's std_huff_tables).  This copies the stream to `out` with ONE DHT segment directly in front of the first SOS marker that
+// holds, in the order DC 0, AC 0, DC 1, AC 1, the Annex K table (jpeg_host.h: K.3 / K.5 for id 0, K.4 / K.6 for id 1) of every one
+// of these four slots that no DHT in front of that SOS defines: at most JPEG_DEFAULT_TABLES_MAX bytes more.  A stream that defines
+// all four, and a header the walker cannot follow to an SOS (no SOI, a truncated or malformed segment, a DHT jpeg_read_dht
+// refuses), is copied byte for byte: this never refuses a stream, the decoder gives its own reason.  Ids 2 and 3 are never filled.
+// `out` has room for size + JPEG_DEFAULT_TABLES_MAX bytes; returns the bytes written.  Every byte is read inside [0, size).
+constexpr int JPEG_DEFAULT_TABLES_MAX = 4 + 4 * 17 + 12 + 162 + 12 + 162;      // 420
+inline int64_t jpeg_add_default_tables(const uint8_t* d, int64_t size, uint8_t* out) {
+    int64_t sos = -1;                                   // where the first SOS marker stands
+    uint8_t present[8] = {};
+    if (size <= JPEG_DEC_MAX_BYTES && size >= 4 && d[0] == 0xFF && d[1] == 0xD8) {
+        std::vector<uint8_t> scratch(8 * (16 + 256));   // (jpeg_read_dht writes the tables it reads somewhere)
+        uint8_t(*counts)[16] = reinterpret_cast<uint8_t(*)[16]>(scratch.data());
+        uint8_t(*values)[256] = reinterpret_cast<uint8_t(*)[256]>(scratch.data() + 8 * 16);
+        for (int64_t p = 2;;) {
+            int m, n;
+            const uint8_t* s;
+            if (jpeg_next_segment(d, size, false, p, m, s, n) != nullptr) break;
+            if (m == 0xC4 && jpeg_read_dht(s, n, 3, counts, values, present) != nullptr) break;
+            if (m == 0xDA) {
+                sos = p - n - 4;
+                break;
+            }
+        }
+    }
+    const bool missing = sos >= 0 && !(present[0] && present[1] && present[2] && present[3]);
+    if (!missing) {
+        if (size > 0) std::memcpy(out, d, size_t(size));
+        return size;
+    }
+    std::memcpy(out, d, size_t(sos));
+    uint8_t* q = out + sos;
+    uint8_t* const seg = q;
+    q += 4;
+    for (int t = 0; t < 4; ++t) {                       // index 2 id + class: DC 0, AC 0, DC 1, AC 1
+        if (present[t]) continue;
+        *q++ = uint8_t(((t & 1) << 4) | (t >> 1));
+        std::memcpy(q, JPEG_HUFF_BITS[t], 16), q += 16;
+        std::memcpy(q, JPEG_HUFF_VALS[t], size_t(JPEG_HUFF_COUNT[t])), q += JPEG_HUFF_COUNT[t];
+    }
+    const int len = int(q - seg) - 2;
+    seg[0] = 0xFF, seg[1] = 0xC4, seg[2] = uint8_t(len >> 8), seg[3] = uint8_t(len & 255);
+    std::memcpy(q, d + sos, size_t(size - sos));
+    return int64_t(q - out) + (size - sos);
+}
+
 // ---- EXIF orientation (pure host; include/whenet_hip.h, JPEG DECODER, ORIENTATION) ----
 // The orientation tag (0x0112) of a stream, 1..8: from IFD0 of the FIRST APP1 segment in front of SOS whose payload starts with
 // "Exif\0\0" (an XMP APP1 in front of it is passed, a second Exif APP1 is never read), count 1, type SHORT or LONG, either byte

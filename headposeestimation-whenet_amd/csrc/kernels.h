@@ -534,15 +534,28 @@ void launch_letterbox_mixed(const uint8_t* d_frames, const LetterboxMixed& clip,
                             uint8_t* d_canvas_u8, float* d_image_f32, int num_cus, hipStream_t stream);
 
 // ---- yuv.hip ----------------------------------------------------------------------------
-// 4:2:0 YUV planes (NV12 / I420) -> the packed BGR frame [h][w][3]: the integer conversion of include/whenet_hip.h.  The planes of
-// a frame lie TIGHT (pitch removed) in one device buffer: h rows of w luma bytes, then ch = (h + 1) >> 1 rows of 2 cw interleaved
-// bytes (NV12) or ch rows of cw U bytes and ch rows of cw V bytes (I420), cw = (w + 1) >> 1: yuv_plane_bytes() in all.
+// 4:2:0 YUV planes (NV12 / I420) and packed 4:2:2 frames (YUYV / UYVY) -> the packed BGR frame [h][w][3]: the integer conversion of
+// include/whenet_hip.h.  The planes of a frame lie TIGHT (pitch removed) in one device buffer: h rows of w luma bytes, then
+// ch = (h + 1) >> 1 rows of 2 cw interleaved bytes (NV12) or ch rows of cw U bytes and ch rows of cw V bytes (I420),
+// cw = (w + 1) >> 1; a packed frame is its one plane, h rows of 4 cw bytes: yuv_plane_bytes() in all.
 constexpr int YUV_MAX_FRAME_SIDE = 8192;
 struct YuvCoeffs {
     int yoff, cy, cvr, cug, cvg, cub;
 };
 const YuvCoeffs& yuv_coeffs(int matrix);        // throws WHENET_EINVAL
-inline size_t yuv_plane_bytes(int h, int w) { return size_t(h) * w + 2 * size_t((h + 1) >> 1) * ((w + 1) >> 1); }
+inline bool yuv_is_packed(int format) { return format == WHENET_YUV_YUYV || format == WHENET_YUV_UYVY; }
+inline size_t yuv_plane_bytes(int h, int w, int format) {
+    if (yuv_is_packed(format)) return size_t(h) * 4 * size_t((w + 1) >> 1);
+    return size_t(h) * w + 2 * size_t((h + 1) >> 1) * ((w + 1) >> 1);
+}
+// the planes a format has (1..3), and plane p's rows and row bytes in a frame of h x w
+inline int yuv_plane_count(int format) { return yuv_is_packed(format) ? 1 : (format == WHENET_YUV_NV12 ? 2 : 3); }
+inline int yuv_plane_rows(int format, int p, int h) { return p == 0 ? h : (h + 1) >> 1; }
+inline int yuv_plane_row_bytes(int format, int p, int w) {
+    const int cw = (w + 1) >> 1;
+    if (yuv_is_packed(format)) return 4 * cw;
+    return p == 0 ? w : (format == WHENET_YUV_NV12 ? 2 * cw : cw);
+}
 // argument checks of a frame list (what: the caller's name; the failing frame's index goes into the text), and the host forms:
 // the conversion itself, and the tight copy of a frame's planes that the device reads
 void check_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes);
@@ -566,7 +579,7 @@ void launch_yuv_to_bgr_batch(const uint8_t* d_planes, uint8_t* d_bgr, const YuvG
 void launch_yuv_to_bgr_mixed(const uint8_t* d_planes, uint8_t* d_bgr, YuvMixed clip, hipStream_t stream);
 // The same conversion of planes that are ALREADY in device memory, where a decoder or a tensor left them: every plane has its own
 // address (any alignment) and byte pitch.  At most 16 records by value in the argument block; frame f's output starts dst_off
-// bytes into d_bgr.  plane[2] / pitch[2] are unused for NV12.
+// bytes into d_bgr.  plane[2] / pitch[2] are unused for NV12, plane[1..2] / pitch[1..2] for YUYV / UYVY.
 struct YuvPlanesFrame {
     const uint8_t* plane[3];
     int pitch[3];

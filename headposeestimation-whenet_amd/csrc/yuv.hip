@@ -1,6 +1,8 @@
 // Frame ingest from a video decoder: 4:2:0 YUV planes (NV12 / I420) -> the packed BGR frame [h][w][3] that the rest of the frame
 // path reads (letterbox.hip, frame.hip).  The conversion is the integer form stated in include/whenet_hip.h: 20 fractional bits,
-// nearest-neighbour chroma (pixel (y, x) takes the sample (y >> 1, x >> 1)), the coefficient rows WHENET_YUV_COEFFS.
+// nearest-neighbour chroma (pixel (y, x) takes the sample (y >> 1, x >> 1)), the coefficient rows WHENET_YUV_COEFFS.  And from a
+// camera: packed 4:2:2 frames (YUYV / UYVY), the same arithmetic with every row's own chroma -- yuv_item_packed below, on the same
+// item grid and through the same store stage.
 //
 // A thread owns 4 horizontally adjacent pixels on the two rows of one chroma row: the two chroma pairs are fetched once (one dword
 // of an NV12 row), each luma row is one dword, and the 12 output bytes of a row leave as three dwords.  Adjacent lanes own
@@ -50,6 +52,37 @@ __device__ __forceinline__ uint32_t pixel_bgr(const YuvCoeffs& k, int y, const C
 
 __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int shift_bits) {      // bits [shift, shift + 32) of hi:lo
     return uint32_t(((uint64_t(hi) << 32) | lo) >> shift_bits);
+}
+
+// the output stage of an item function: the pixels p0..p3 (B | G << 8 | R << 16) of a group of n = 1..4 pixels go to dp, which is
+// aligned to nothing in general.  n == 4: 12 bytes as three dwords, or 4 - a head bytes, two aligned dwords (funnel-shifted) and a
+// tail bytes where dp is a mod 4.  n < 4 (the last group of a row): 3 n bytes one by one, the next frame starts behind them.
+__device__ __forceinline__ void store_group(uint8_t* __restrict__ dp, int n, uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3) {
+    const uint32_t w0 = p0 | (p1 << 24), w1 = (p1 >> 8) | (p2 << 16), w2 = (p2 >> 16) | (p3 << 8);
+    if (n == 4) {
+        const int a = int(reinterpret_cast<uintptr_t>(dp) & 3);
+        if (a == 0) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(dp);
+            d[0] = w0, d[1] = w1, d[2] = w2;
+        } else {
+            const int head = 4 - a;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < head) dp[j] = uint8_t(w0 >> (8 * j));
+            uint32_t* d = reinterpret_cast<uint32_t*>(dp + head);
+            d[0] = funnel(w0, w1, 8 * head), d[1] = funnel(w1, w2, 8 * head);
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < a) dp[12 - a + j] = uint8_t(w2 >> (8 * (head + j)));
+        }
+    } else {
+        const int nb = 3 * n;                   // 3, 6 or 9 bytes
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const uint32_t word = j < 4 ? w0 : (j < 8 ? w1 : w2);
+            if (j < nb) dp[j] = uint8_t(word >> (8 * (j & 3)));
+        }
+    }
 }
 
 // one item of a frame: group gx (pixels 4 gx ..) of chroma row p (luma rows 2 p, 2 p + 1).  The planes are wherever they are:
@@ -104,38 +137,62 @@ __device__ __forceinline__ void yuv_item_planes(const uint8_t* __restrict__ py, 
         }
         const uint32_t p0 = pixel_bgr(k, y4 & 255, c0), p1 = pixel_bgr(k, (y4 >> 8) & 255, c0);
         const uint32_t p2 = pixel_bgr(k, (y4 >> 16) & 255, c1), p3 = pixel_bgr(k, y4 >> 24, c1);
-        const uint32_t w0 = p0 | (p1 << 24), w1 = (p1 >> 8) | (p2 << 16), w2 = (p2 >> 16) | (p3 << 8);
-        uint8_t* dp = bgr + (size_t(y0 + r) * w + x) * 3;
-        if (n == 4) {
-            const int a = int(reinterpret_cast<uintptr_t>(dp) & 3);
-            if (a == 0) {
-                uint32_t* d = reinterpret_cast<uint32_t*>(dp);
-                d[0] = w0, d[1] = w1, d[2] = w2;
-            } else {
-                const int head = 4 - a;
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    if (j < head) dp[j] = uint8_t(w0 >> (8 * j));
-                uint32_t* d = reinterpret_cast<uint32_t*>(dp + head);
-                d[0] = funnel(w0, w1, 8 * head), d[1] = funnel(w1, w2, 8 * head);
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    if (j < a) dp[12 - a + j] = uint8_t(w2 >> (8 * (head + j)));
-            }
-        } else {
-            const int nb = 3 * n;                   // 3, 6 or 9 bytes
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const uint32_t word = j < 4 ? w0 : (j < 8 ? w1 : w2);
-                if (j < nb) dp[j] = uint8_t(word >> (8 * (j & 3)));
-            }
-        }
+        store_group(bgr + (size_t(y0 + r) * w + x) * 3, n, p0, p1, p2, p3);
     }
 }
 
-// the same item of a frame whose planes lie TIGHT behind one another at `planes` (kernels.h)
+// The same item of a PACKED 4:2:2 frame (YUYV: Y0 U Y1 V per pixel pair, UYVY: U Y0 V Y1): rows of 4 cw bytes, `pitch` bytes apart
+// at src.  The group's 4 pixels are 2 pairs = 8 source bytes at 2 x of each row (one pair = 4 bytes where n <= 2: the row ends
+// there, and the last pair of an odd row is whole in memory).  Every row has its own chroma, so both ChromaTerms are built per row.
+// One 8-byte load where the address is a multiple of 8 and the 8 bytes belong to the row, dwords at a multiple of 4, bytes otherwise:
+// adjacent lanes own adjacent groups, so a wave reads 512 contiguous source bytes per row and writes 768.
+__device__ __forceinline__ void yuv_item_packed(const uint8_t* __restrict__ src, size_t pitch, uint8_t* __restrict__ bgr, int h, int w, int format,
+                                                const YuvCoeffs& k, int item) {
+    const int ch = (h + 1) >> 1, gw = (w + 3) >> 2;
+    const int p = item / gw, gx = item - p * gw;
+    if (p >= ch) return;
+    const int x = gx << 2;
+    const int n = min(4, w - x);                    // pixels of the group, 1..4
+    const int y0 = p << 1;
+    const int rows = min(2, h - y0);
+    const bool two = n > 2;                         // the group has a second pair (x / 2 + 1 < cw)
+
+    for (int r = 0; r < rows; ++r) {
+        const uint8_t* sp = src + size_t(y0 + r) * pitch + 2 * size_t(x);
+        const uintptr_t a = reinterpret_cast<uintptr_t>(sp);
+        uint32_t q0, q1 = 0;
+        if (two && (a & 7) == 0) {
+            const uint2 q = *reinterpret_cast<const uint2*>(sp);
+            q0 = q.x, q1 = q.y;
+        } else if ((a & 3) == 0) {
+            q0 = *reinterpret_cast<const uint32_t*>(sp);
+            if (two) q1 = *reinterpret_cast<const uint32_t*>(sp + 4);
+        } else {
+            q0 = uint32_t(sp[0]) | (uint32_t(sp[1]) << 8) | (uint32_t(sp[2]) << 16) | (uint32_t(sp[3]) << 24);
+            if (two) q1 = uint32_t(sp[4]) | (uint32_t(sp[5]) << 8) | (uint32_t(sp[6]) << 16) | (uint32_t(sp[7]) << 24);
+        }
+        if (format == WHENET_YUV_UYVY) {            // U Y0 V Y1 -> Y0 U Y1 V: the bytes of every 16-bit half swapped
+            q0 = ((q0 >> 8) & 0x00FF00FFu) | ((q0 & 0x00FF00FFu) << 8);
+            q1 = ((q1 >> 8) & 0x00FF00FFu) | ((q1 & 0x00FF00FFu) << 8);
+        }
+        if (!two) q1 = q0;                          // (pixels 2, 3 are not stored)
+        const ChromaTerms c0 = chroma_terms(k, (q0 >> 8) & 255, q0 >> 24), c1 = chroma_terms(k, (q1 >> 8) & 255, q1 >> 24);
+        const uint32_t p0 = pixel_bgr(k, q0 & 255, c0), p1 = pixel_bgr(k, (q0 >> 16) & 255, c0);
+        const uint32_t p2 = pixel_bgr(k, q1 & 255, c1), p3 = pixel_bgr(k, (q1 >> 16) & 255, c1);
+        store_group(bgr + (size_t(y0 + r) * w + x) * 3, n, p0, p1, p2, p3);
+    }
+}
+
+__device__ __forceinline__ bool packed_format(int format) { return format == WHENET_YUV_YUYV || format == WHENET_YUV_UYVY; }
+
+// the same item of a frame whose planes lie TIGHT behind one another at `planes` (kernels.h).  The format is the frame's and a
+// workgroup belongs to one frame: the branch is the same in every lane.
 __device__ __forceinline__ void yuv_item(const uint8_t* __restrict__ planes, uint8_t* __restrict__ bgr, const YuvGeom& g, int item) {
     const size_t cw = size_t((g.w + 1) >> 1), ch = size_t((g.h + 1) >> 1);
+    if (packed_format(g.format)) {
+        yuv_item_packed(planes, 4 * cw, bgr, g.h, g.w, g.format, g.k, item);
+        return;
+    }
     const uint8_t* const chroma = planes + size_t(g.h) * g.w;
     const bool nv12 = g.format == WHENET_YUV_NV12;
     yuv_item_planes(planes, chroma, chroma + ch * cw, size_t(g.w), nv12 ? 2 * cw : cw, cw, bgr, g.h, g.w, g.format, g.k, item);
@@ -171,6 +228,10 @@ __global__ __launch_bounds__(THREADS) void whenet_yuv_planes_to_bgr_kernel(uint8
     for (int i = 1; i < clip.frames; ++i)
         if (clip.f[i].block0 <= b) f = i;
     const YuvPlanesFrame& g = clip.f[f];
+    if (packed_format(g.format)) {
+        yuv_item_packed(g.plane[0], size_t(g.pitch[0]), bgr + g.dst_off, g.h, g.w, g.format, g.k, (b - g.block0) * THREADS + int(threadIdx.x));
+        return;
+    }
     yuv_item_planes(g.plane[0], g.plane[1], g.plane[2], size_t(g.pitch[0]), size_t(g.pitch[1]), size_t(g.pitch[2]), bgr + g.dst_off, g.h, g.w,
                     g.format, g.k, (b - g.block0) * THREADS + int(threadIdx.x));
 }
@@ -179,7 +240,7 @@ int yuv_blocks(int h, int w) { return (((w + 3) >> 2) * ((h + 1) >> 1) + THREADS
 
 void check_geom(const YuvGeom& g) {
     WHENET_REQUIRE(g.h >= 1 && g.w >= 1 && g.h <= YUV_MAX_FRAME_SIDE && g.w <= YUV_MAX_FRAME_SIDE &&
-                       (g.format == WHENET_YUV_NV12 || g.format == WHENET_YUV_I420),
+                       (g.format == WHENET_YUV_NV12 || g.format == WHENET_YUV_I420 || yuv_is_packed(g.format)),
                    WHENET_EINVAL, "yuv_to_bgr: bad frame geometry");
 }
 
@@ -199,27 +260,43 @@ void check_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nf
     for (int i = 0; i < nframes; ++i) {
         const whenet_yuv_frame_t& f = frames[i];
         const std::string who = w + ": frame " + std::to_string(i);
-        WHENET_REQUIRE(f.format == WHENET_YUV_NV12 || f.format == WHENET_YUV_I420, WHENET_EINVAL,
-                       who + ": unknown format " + std::to_string(f.format) + " (WHENET_YUV_NV12 or WHENET_YUV_I420)");
+        WHENET_REQUIRE(f.format == WHENET_YUV_NV12 || f.format == WHENET_YUV_I420 || yuv_is_packed(f.format), WHENET_EINVAL,
+                       who + ": unknown format " + std::to_string(f.format) +
+                           " (WHENET_YUV_NV12, WHENET_YUV_I420, WHENET_YUV_YUYV or WHENET_YUV_UYVY)");
         WHENET_REQUIRE(f.matrix >= 0 && f.matrix < WHENET_YUV_MATRICES, WHENET_EINVAL,
                        who + ": unknown matrix " + std::to_string(f.matrix) + " (WHENET_YUV_BT601, _BT709 or _JFIF)");
         WHENET_REQUIRE(f.h >= 1 && f.w >= 1 && f.h <= YUV_MAX_FRAME_SIDE && f.w <= YUV_MAX_FRAME_SIDE, WHENET_EINVAL,
                        who + " is " + std::to_string(f.h) + " x " + std::to_string(f.w) + ": sides must be 1.." +
                            std::to_string(YUV_MAX_FRAME_SIDE));
-        const int cw = (f.w + 1) >> 1;
-        const int planes = f.format == WHENET_YUV_NV12 ? 2 : 3;
-        const int row_bytes[3] = {f.w, f.format == WHENET_YUV_NV12 ? 2 * cw : cw, cw};
-        for (int p = 0; p < planes; ++p) {
+        for (int p = 0; p < yuv_plane_count(f.format); ++p) {
+            const int row_bytes = yuv_plane_row_bytes(f.format, p, f.w);
             WHENET_REQUIRE(f.plane[p] != nullptr, WHENET_EINVAL, who + ": plane " + std::to_string(p) + " is NULL");
-            WHENET_REQUIRE(f.pitch[p] >= row_bytes[p], WHENET_EINVAL,
+            WHENET_REQUIRE(f.pitch[p] >= row_bytes, WHENET_EINVAL,
                            who + ": pitch " + std::to_string(f.pitch[p]) + " of plane " + std::to_string(p) + " is below its row of " +
-                               std::to_string(row_bytes[p]) + " bytes");
+                               std::to_string(row_bytes) + " bytes");
         }
     }
 }
 
 void yuv_to_bgr_host(const whenet_yuv_frame_t& f, uint8_t* bgr) {
     const YuvCoeffs& k = yuv_coeffs(f.matrix);
+    if (yuv_is_packed(f.format)) {                  // pair x >> 1 of the pixel's own row: Y0 U Y1 V, or U Y0 V Y1
+        const int yat = f.format == WHENET_YUV_YUYV ? 0 : 1, uat = 1 - yat, vat = 3 - yat;
+        for (int y = 0; y < f.h; ++y) {
+            const uint8_t* row = f.plane[0] + size_t(y) * f.pitch[0];
+            uint8_t* out = bgr + size_t(y) * f.w * 3;
+            for (int x = 0; x < f.w; ++x) {
+                const uint8_t* pair = row + 4 * (x >> 1);
+                const int c = std::max(0, int(pair[yat + 2 * (x & 1)]) - k.yoff);
+                const int d = int(pair[uat]) - 128, e = int(pair[vat]) - 128;
+                const int base = k.cy * c + (1 << (SHIFT - 1));
+                out[3 * x + 0] = uint8_t(yuv_clip8((base + k.cub * d) >> SHIFT));
+                out[3 * x + 1] = uint8_t(yuv_clip8((base - k.cug * d - k.cvg * e) >> SHIFT));
+                out[3 * x + 2] = uint8_t(yuv_clip8((base + k.cvr * e) >> SHIFT));
+            }
+        }
+        return;
+    }
     const bool nv12 = f.format == WHENET_YUV_NV12;
     for (int y = 0; y < f.h; ++y) {
         const uint8_t* yrow = f.plane[0] + size_t(y) * f.pitch[0];
@@ -239,19 +316,15 @@ void yuv_to_bgr_host(const whenet_yuv_frame_t& f, uint8_t* bgr) {
 }
 
 void yuv_stage_planes(const whenet_yuv_frame_t& f, uint8_t* dst) {
-    const int cw = (f.w + 1) >> 1, ch = (f.h + 1) >> 1;
-    const bool nv12 = f.format == WHENET_YUV_NV12;
-    const int planes = nv12 ? 2 : 3;
-    const int rows[3] = {f.h, ch, ch};
-    const int row_bytes[3] = {f.w, nv12 ? 2 * cw : cw, cw};
-    for (int p = 0; p < planes; ++p) {
-        const size_t rb = size_t(row_bytes[p]);
+    for (int p = 0; p < yuv_plane_count(f.format); ++p) {
+        const size_t rb = size_t(yuv_plane_row_bytes(f.format, p, f.w));
+        const int rows = yuv_plane_rows(f.format, p, f.h);
         if (size_t(f.pitch[p]) == rb) {
-            std::memcpy(dst, f.plane[p], rb * rows[p]);
+            std::memcpy(dst, f.plane[p], rb * rows);
         } else {
-            for (int r = 0; r < rows[p]; ++r) std::memcpy(dst + r * rb, f.plane[p] + size_t(r) * f.pitch[p], rb);
+            for (int r = 0; r < rows; ++r) std::memcpy(dst + r * rb, f.plane[p] + size_t(r) * f.pitch[p], rb);
         }
-        dst += rb * rows[p];
+        dst += rb * rows;
     }
 }
 
@@ -264,7 +337,7 @@ void launch_yuv_to_bgr(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g
 void launch_yuv_to_bgr_batch(const uint8_t* d_planes, uint8_t* d_bgr, const YuvGeom& g, int frames, size_t src_stride, size_t dst_stride,
                              hipStream_t stream) {
     check_geom(g);
-    WHENET_REQUIRE(frames >= 1 && frames <= MIXED_MAX_FRAMES && src_stride >= yuv_plane_bytes(g.h, g.w) && dst_stride >= size_t(g.h) * g.w * 3,
+    WHENET_REQUIRE(frames >= 1 && frames <= MIXED_MAX_FRAMES && src_stride >= yuv_plane_bytes(g.h, g.w, g.format) && dst_stride >= size_t(g.h) * g.w * 3,
                    WHENET_EINVAL, "yuv_to_bgr_batch: bad frame count or strides");
     hipLaunchKernelGGL(whenet_yuv_to_bgr_batch_kernel, dim3(yuv_blocks(g.h, g.w), frames), dim3(THREADS), 0, stream, d_planes, d_bgr, g,
                        (unsigned long long)src_stride, (unsigned long long)dst_stride);
@@ -292,12 +365,11 @@ void launch_yuv_planes_to_bgr(uint8_t* d_bgr, YuvPlanes clip, hipStream_t stream
     int blocks = 0;
     for (int f = 0; f < clip.frames; ++f) {
         const YuvPlanesFrame& g = clip.f[f];
-        const int cw = (g.w + 1) >> 1;
-        const bool nv12 = g.format == WHENET_YUV_NV12;
-        WHENET_REQUIRE(g.h >= 1 && g.w >= 1 && g.h <= YUV_MAX_FRAME_SIDE && g.w <= YUV_MAX_FRAME_SIDE && (nv12 || g.format == WHENET_YUV_I420) &&
-                           g.plane[0] != nullptr && g.plane[1] != nullptr && (nv12 || g.plane[2] != nullptr) && g.pitch[0] >= g.w &&
-                           g.pitch[1] >= (nv12 ? 2 * cw : cw) && (nv12 || g.pitch[2] >= cw),
-                       WHENET_EINVAL, "yuv_planes_to_bgr: bad frame geometry");
+        bool good = g.h >= 1 && g.w >= 1 && g.h <= YUV_MAX_FRAME_SIDE && g.w <= YUV_MAX_FRAME_SIDE &&
+                    (g.format == WHENET_YUV_NV12 || g.format == WHENET_YUV_I420 || yuv_is_packed(g.format));
+        for (int p = 0; good && p < yuv_plane_count(g.format); ++p)
+            good = g.plane[p] != nullptr && g.pitch[p] >= yuv_plane_row_bytes(g.format, p, g.w);
+        WHENET_REQUIRE(good, WHENET_EINVAL, "yuv_planes_to_bgr: bad frame geometry");
         clip.f[f].block0 = blocks;
         blocks += yuv_blocks(g.h, g.w);
     }

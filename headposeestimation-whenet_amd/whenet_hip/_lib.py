@@ -190,6 +190,7 @@ _PROTOS = {
     "whenet_clip_begin_jpeg_progressive": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P]),
     "whenet_jpeg_clip_plan_progressive": (C.c_int, [C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, _P]),
     "whenet_jpeg_orientation": (C.c_int, [_P, C.c_int64]),
+    "whenet_jpeg_add_default_tables": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "whenet_jpeg_decode_oriented_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, _P]),
     "whenet_op_jpeg_decode_oriented": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                                  _P, _P]),
@@ -479,6 +480,7 @@ def crop_plan(rect) -> np.ndarray:
 
 
 YUV_NV12, YUV_I420 = 0, 1                      # WHENET_YUV_NV12 / WHENET_YUV_I420
+YUV_YUYV, YUV_UYVY = 3, 4                      # WHENET_YUV_YUYV / WHENET_YUV_UYVY: packed 4:2:2, one plane (2 is SURF_PACKED)
 YUV_BT601, YUV_BT709, YUV_JFIF = 0, 1, 2       # WHENET_YUV_BT601 / _BT709 / _JFIF
 
 
@@ -818,6 +820,23 @@ def jpeg_orientation(data) -> int:
     lib = load()
     a = _stream_array(data)
     return int(lib.whenet_jpeg_orientation(_ptr(a) if a.size else None, int(a.size)))
+
+
+JPEG_DEFAULT_TABLES_MAX = 420      # bytes `whenet_jpeg_add_default_tables` adds at most (one DHT segment of the four Annex K tables)
+
+
+def jpeg_add_default_tables(data) -> bytes:
+    """`whenet_jpeg_add_default_tables`: the stream with the Annex K Huffman tables (what libjpeg installs) for every slot DC 0, AC 0,
+    DC 1, AC 1 that no DHT before the first SOS defines, in one DHT segment directly in front of that SOS.  A complete stream and a
+    header that cannot be followed come back byte for byte.  Pure host arithmetic inside the library."""
+    lib = load()
+    a = _stream_array(data)
+    out = np.empty(int(a.size) + JPEG_DEFAULT_TABLES_MAX, np.uint8)
+    n = C.c_int64(0)
+    rc = lib.whenet_jpeg_add_default_tables(_ptr(a) if a.size else _ptr(out), int(a.size), _ptr(out), int(out.size), C.byref(n))
+    if rc != 0:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace"))
+    return out[:n.value].tobytes()
 
 
 def jpeg_tristate(v) -> int:

@@ -28,7 +28,7 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     `max_heads` rows, not over F x max_boxes; every frame's result is bit for bit what `begin; detect_heads; collect` returns;
   * frames of DIFFERENT sizes (a rig of different cameras, several files behind one handle) travel as a clip too:
     `begin_clip_mixed(frames)` in the place of `begin_clip`, the other two calls and the contract unchanged;
-  * a caller fed by a video decoder hands over its 4:2:0 planes (`whenet_hip.yuv.YUVFrame`: NV12 or I420) with `begin_yuv(frame)`
+  * a caller fed by a video decoder hands over its 4:2:0 planes or a camera's packed 4:2:2 frame (`whenet_hip.yuv.YUVFrame`: NV12, I420, YUYV or UYVY) with `begin_yuv(frame)`
     / `begin_clip_yuv(frames)`: half the bytes cross PCIe and the BGR frame is built on the device (`csrc/yuv.hip`); everything
     that follows is what `begin(frame.to_bgr())` / `begin_clip...` would have been followed by, bit for bit.
 
@@ -290,7 +290,7 @@ class FramePipeline:
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
 
-    def begin_jpeg(self, data, rule=None, progressive=None, orient=None) -> "JpegStatus":
+    def begin_jpeg(self, data, rule=None, progressive=None, orient=None, default_tables: bool = False) -> "JpegStatus":
         """`begin()` from the bytes of a baseline JPEG stream (a still, or one frame of an MJPG file: `whenet_hip.mjpeg.MJPGReader`):
         what stands for `cv2.imread` / `cap.read()`.  Only the compressed bytes cross the link; the frame is decoded on the device
         (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
@@ -306,8 +306,11 @@ class FramePipeline:
         stream's EXIF orientation as `cv2.imread` does -- the frame is `jpeg.decode_host(data, orient=True, ...)`, turned by the
         kernel that writes it, and everything that follows (boxes included) is in the upright picture's coordinates; None (the
         default) follows the handle's option "jpeg_orient" (0: the tag is ignored, the default).  `JpegStatus.orientation` is
-        the value applied."""
+        the value applied.  default_tables=True: the stream is completed by `jpeg.add_default_tables` first -- the MJPG frame of a
+        UVC camera or of an AVI whose writer left the DHT segment out, which is refused otherwise."""
         self._check_can_begin()
+        if default_tables:
+            data = _lib.jpeg_add_default_tables(data)
         _lib.jpeg_rule_code(rule)
         info = _lib.jpeg_parse(data) if progressive is False else _lib.jpeg_parse_scans(data)[0]
         st = JpegStatus()
@@ -323,7 +326,7 @@ class FramePipeline:
         self._last_sizes = [(h, w)]
         return st
 
-    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False, orient: bool = False) -> list:
+    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False, orient: bool = False, default_tables: bool = False) -> list:
         """A clip from the bytes of 1..16 baseline JPEG streams (consecutive frames of an MJPG file: `MJPGReader.clips(16)`), each
         with its own size, sampling, tables and DRI: one upload of the compressed bytes, every decoder stage in one launch for all
         frames.  Frame f is what `begin_jpeg(datas[f])` makes; frames of one size make a clip as `begin_clip()` makes it, frames of
@@ -336,10 +339,10 @@ class FramePipeline:
         `JpegStatus.interval` of a progressive frame is its flat (scan, interval) item.  Clips do not read the handle's option
         "jpeg_progressive": only this argument accepts SOF2.  orient=True: every frame by its own EXIF orientation, as
         `begin_jpeg(datas[f], orient=True)`; a clip is one-size by the sizes of the turned frames.  Clips do not read the option
-        "jpeg_orient" either."""
+        "jpeg_orient" either.  default_tables=True: every stream is completed by `jpeg.add_default_tables` first."""
         self._check_can_begin()
         _lib.jpeg_rule_code(rule)
-        datas = list(datas)
+        datas = [_lib.jpeg_add_default_tables(d) for d in datas] if default_tables else list(datas)
         if not 1 <= len(datas) <= _lib.MAX_CLIP_FRAMES:
             raise ValueError(f"a clip holds 1..{_lib.MAX_CLIP_FRAMES} frames, got {len(datas)}")
         infos = []

@@ -118,12 +118,27 @@ class DecodeError(ValueError):
         self.frame = frame
 
 
-def info(data, progressive: bool = False) -> dict:
+def add_default_tables(data) -> bytes:
+    """The stream completed by the Huffman tables a UVC camera's or an AVI writer's MJPG frame leaves out
+    (`whenet_jpeg_add_default_tables`): for each of the slots DC 0, AC 0, DC 1, AC 1 that no DHT in front of the first SOS defines,
+    T.81's Annex K table (what libjpeg's std_huff_tables installs there), all in one DHT segment directly in front of that SOS, at
+    most 420 bytes more.  A stream that defines all four comes back byte for byte, and so does anything whose header cannot be
+    followed to an SOS: this never raises for a stream, the decoder gives its own reason.  Ids 2 and 3 are never filled."""
+    return _lib.jpeg_add_default_tables(data)
+
+
+def _completed(data, default_tables: bool):
+    return _lib.jpeg_add_default_tables(data) if default_tables else data
+
+
+def info(data, progressive: bool = False, default_tables: bool = False) -> dict:
     """The header SOI..SOS of a stream (`whenet_jpeg_parse`): h, w, components, sampling (hs, vs), restart_interval, intervals,
     data_offset, the quantisers uint8 [4,64] in natural order and the table ids.  ValueError with the reason for anything but a
     baseline stream the decoder accepts (progressive, arithmetic, 12 bit, 4 components, several scans, ...).
     progressive=True (`whenet_jpeg_parse_scans`): a progressive (SOF2) stream is accepted too, and "scans" lists every scan as a
-    dict: components, ss, se, ah, al, dc_ids, ac_ids, tables, ri, intervals, level, first_item, data_offset, data_bytes."""
+    dict: components, ss, se, ah, al, dc_ids, ac_ids, tables, ri, intervals, level, first_item, data_offset, data_bytes.
+    default_tables=True: the header of `add_default_tables(data)` (offsets are that stream's)."""
+    data = _completed(data, default_tables)
     scans = None
     if progressive:
         i, recs = _lib.jpeg_parse_scans(data)
@@ -174,7 +189,7 @@ def _run_decode(handle, data, frame, bgr, entropy, seg_bytes, rule, progressive,
 
 
 def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False,
-           rule: str = "own", progressive: bool = False, orient: bool = False):
+           rule: str = "own", progressive: bool = False, orient: bool = False, default_tables: bool = False):
     """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
     (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
     Damaged data raises `DecodeError` (strict=False: returns the defined frame).  `entropy`: the form of the entropy stage --
@@ -190,7 +205,9 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     orient=True (`whenet_op_jpeg_decode_oriented`): the stream's EXIF orientation (`orientation(data)`) is applied by the frame kernel
     itself, as `cv2.imread` applies it: the frame is `decode_host(data, orient=True, ...)`, its sides swapped for the values 5..8.
     orient=False is an upright decode on every handle: every path here goes through that call with `orient` stated, so the handle's
-    option "jpeg_orient" (which the plain C calls read) never turns a frame this function sized upright."""
+    option "jpeg_orient" (which the plain C calls read) never turns a frame this function sized upright.
+    default_tables=True: `add_default_tables(data)` is decoded in its place (an MJPG frame without DHT; refused otherwise)."""
+    data = _completed(data, default_tables)
     if entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be 'auto', 'interval' or 'segmented'")
     _lib.jpeg_rule_code(rule)
@@ -223,7 +240,7 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
 
 
 def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True, rule: str = "own",
-                progressive: bool = False, orient: bool = False):
+                progressive: bool = False, orient: bool = False, default_tables: bool = False):
     """(frames, statuses) of 1..16 baseline JPEG streams decoded as ONE clip by the kernels (`whenet_op_jpeg_decode_clip`): a list of
     uint8 [H_f,W_f,3] frames and the status words int32 [F,2].  Frame f is `decode(datas[f])`, bit for bit.  `entropy`: None or
     "auto" (the handle's options, stream by stream), "interval" or "segmented" (`seg_bytes`: None = 128).  A stream the decoder does
@@ -234,11 +251,12 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     status; the scan kernel is launched once per level for all progressive frames together, and `entropy` / `seg_bytes` apply to
     the baseline frames.  The handle's option "jpeg_progressive" is not read by clips: only this argument accepts SOF2.
     orient=True (`whenet_op_jpeg_decode_clip_oriented`): every frame by its own EXIF orientation -- frame f is
-    `decode_host(datas[f], orient=True, ...)` --, upright and turned frames in one clip, at most one launch more than without."""
+    `decode_host(datas[f], orient=True, ...)` --, upright and turned frames in one clip, at most one launch more than without.
+    default_tables=True: every stream is completed by `add_default_tables` first."""
     _lib.jpeg_rule_code(rule)
     if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be None, 'auto', 'interval' or 'segmented'")
-    datas = list(datas)
+    datas = [_completed(d, default_tables) for d in datas]
     if not 1 <= len(datas) <= _lib.MAX_CLIP_FRAMES:
         raise ValueError(f"a clip holds 1..{_lib.MAX_CLIP_FRAMES} frames, got {len(datas)}")
     frames = []
@@ -275,12 +293,14 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     return frames, status
 
 
-def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", progressive: bool = False, orient: bool = False) -> np.ndarray:
+def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", progressive: bool = False, orient: bool = False,
+                default_tables: bool = False) -> np.ndarray:
     """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
     held to.  `rule`: "own" or "libjpeg", as `decode` (`whenet_jpeg_decode_rule_host`).  progressive=True: a progressive (SOF2)
     stream is accepted too (`whenet_jpeg_decode_progressive_host`).  orient=True (`whenet_jpeg_decode_oriented_host`): the EXIF
     orientation applied to that frame -- with u the upright frame and t = u.transpose(1, 0, 2): 1 u, 2 u[:, ::-1], 3 u[::-1, ::-1],
-    4 u[::-1], 5 t, 6 t[:, ::-1], 7 t[::-1, ::-1], 8 t[::-1]."""
+    4 u[::-1], 5 t, 6 t[:, ::-1], 7 t[::-1, ::-1], 8 t[::-1].  default_tables=True: `add_default_tables(data)` is decoded in its place."""
+    data = _completed(data, default_tables)
     _lib.jpeg_rule_code(rule)
     if orient:
         i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
@@ -323,10 +343,12 @@ def decode_segmented_planes_host(data, seg_bytes: int = 128, window: int = _lib.
     return planes, status, st
 
 
-def decode_planes_host(data, progressive: bool = False, rule: str = "own"):
+def decode_planes_host(data, progressive: bool = False, rule: str = "own", default_tables: bool = False):
     """(the component planes [Y] or [Y, Cb, Cr] as uint8 arrays -- luma h x w, chroma ceil(h / vs) x ceil(w / hs) -- and the status
     int32 [2]) by the host statement: what the tests compare.  progressive=True: a progressive stream is accepted too, and `rule`
-    chooses the inverse DCT (`whenet_jpeg_decode_progressive_planes_host`)."""
+    chooses the inverse DCT (`whenet_jpeg_decode_progressive_planes_host`).  default_tables=True: `add_default_tables(data)` is
+    decoded in its place."""
+    data = _completed(data, default_tables)
     _lib.jpeg_rule_code(rule)
     i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
     if rule != "own" and not progressive:

@@ -108,9 +108,14 @@ class MJPGReader:
     chunks of the first video stream, also inside 'rec ' lists) and keeps every video chunk's position; `width`, `height`, `fps`, `len()`, indexing and
     iteration read from those.  The index chunk is not needed.  ValueError for anything that is not an MJPG AVI: no RIFF / 'AVI '
     header, a video stream whose handler and compression are not MJPG, no 'movi' list, a chunk that passes the end of the file
-    (a truncated file)."""
+    (a truncated file).
 
-    def __init__(self, path):
+    `MJPGReader(path, default_tables=True)`: UVC cameras and many AVI writers leave the DHT segment out of every frame (the tables
+    are T.81's Annex K ones); indexing, iteration and `clips()` then return every frame completed by
+    `whenet_hip.jpeg.add_default_tables`.  The default returns the chunks' bytes as they are."""
+
+    def __init__(self, path, default_tables: bool = False):
+        self._default_tables = bool(default_tables)
         self._f = open(path, "rb")
         try:
             self._f.seek(0, 2)
@@ -199,6 +204,9 @@ class MJPGReader:
         data = self._read(at, size)
         if len(data) != size:
             raise ValueError(f"truncated file: frame {i} has {len(data)} of {size} bytes")
+        if self._default_tables:
+            from . import _lib
+            data = _lib.jpeg_add_default_tables(data)
         return data
 
     def __iter__(self):

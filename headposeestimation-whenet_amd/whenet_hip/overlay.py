@@ -49,6 +49,9 @@ def surface_of(out, h: int, w: int, what: str = "out"):
     would need a copy or a conversion: a read-only array, another shape or dtype, CHW, pixels that are not packed."""
     s = _lib.SurfaceC()
     if isinstance(out, YUVFrame):
+        if out.format not in (_lib.YUV_NV12, _lib.YUV_I420):
+            raise ValueError(f"{what}: a packed 4:2:2 frame (YUYV / UYVY) as a destination is not built: destinations are packed "
+                             "BGR / RGB, NV12 or I420")
         if (out.h, out.w) != (h, w):
             raise ValueError(f"{what}: the surface is {out.h} x {out.w}, the frame {h} x {w}")
         if not out.writable:
@@ -86,7 +89,8 @@ def new_output(h: int, w: int, format="bgr", matrix="bt601"):
     `YUVFrame` for 'nv12' / 'i420'."""
     if isinstance(format, str) and format.lower() in PACKED_NAMES:
         return np.empty((h, w, 3), np.uint8)
-    fmt = _code(FORMATS, format, "format")
+    # (the planar formats only: a packed 4:2:2 destination is not built, its names are unknown formats here as they were)
+    fmt = _code({k: v for k, v in FORMATS.items() if v in (_lib.YUV_NV12, _lib.YUV_I420)}, format, "format")
     ch, cw = (h + 1) // 2, (w + 1) // 2
     y = np.empty((h, w), np.uint8)
     if fmt == _lib.YUV_NV12:

@@ -1,7 +1,8 @@
-"""4:2:0 YUV frames as video decoders deliver them (NV12, I420), for `FramePipeline.begin_yuv` / `begin_clip_yuv`.
+"""YUV frames as video decoders and cameras deliver them -- 4:2:0 planes (NV12, I420) and packed 4:2:2 (YUYV alias YUY2, UYVY: the
+raw formats of V4L2 / UVC cameras and capture cards) -- for `FramePipeline.begin_yuv` / `begin_clip_yuv`.
 
 A `YUVFrame` describes the planes where they are: nothing is copied or converted here.  The planes are uploaded as they are (1.5
-bytes per pixel) and the packed BGR frame is built on the device (`csrc/yuv.hip`) by the integer conversion stated in
+bytes per pixel for 4:2:0, 2 for packed 4:2:2) and the packed BGR frame is built on the device (`csrc/yuv.hip`) by the integer conversion stated in
 include/whenet_hip.h; `to_bgr()` runs the same arithmetic on the host inside the library.
 
     frame = YUVFrame.from_buffer(decoder_buffer, 1080, 1920, "nv12", pitch=2048, matrix="bt709")
@@ -21,7 +22,9 @@ import numpy as np
 
 from . import _lib
 
-FORMATS = {"nv12": _lib.YUV_NV12, "i420": _lib.YUV_I420}
+FORMATS = {"nv12": _lib.YUV_NV12, "i420": _lib.YUV_I420, "yuyv": _lib.YUV_YUYV, "yuy2": _lib.YUV_YUYV, "uyvy": _lib.YUV_UYVY}
+PACKED = (_lib.YUV_YUYV, _lib.YUV_UYVY)        # one plane of h rows of 4 * ((w + 1) // 2) bytes
+_NAMES = {_lib.YUV_NV12: "NV12", _lib.YUV_I420: "I420", _lib.YUV_YUYV: "YUYV", _lib.YUV_UYVY: "UYVY"}
 MATRICES = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709, "jfif": _lib.YUV_JFIF}
 # {yoff, CY, CVR, CUG, CVG, CUB} per matrix: WHENET_YUV_COEFFS of include/whenet_hip.h (tests/test_yuv_cpu.py holds both to the text)
 COEFFS = {"bt601": (16, 1220542, 1673527, 409993, 852492, 2116026),
@@ -86,9 +89,11 @@ def _array_writable(a) -> bool:
 
 
 class YUVFrame:
-    """The planes of one 4:2:0 frame of h x w luma samples: `planes` (2 arrays for NV12: Y, interleaved UV; 3 for I420: Y, U, V),
-    their byte `pitches`, `format`, `matrix` (codes of include/whenet_hip.h), `h`, `w`.  The chroma planes have (h + 1) // 2 rows of
-    (w + 1) // 2 samples."""
+    """The planes of one frame of h x w luma samples: `planes` (2 arrays for NV12: Y, interleaved UV; 3 for I420: Y, U, V; 1 for the
+    packed 4:2:2 formats YUYV / UYVY), their byte `pitches`, `format`, `matrix` (codes of include/whenet_hip.h), `h`, `w`.  The
+    chroma planes of a 4:2:0 frame have (h + 1) // 2 rows of (w + 1) // 2 samples.  A packed frame is one plane of h rows of
+    4 * ((w + 1) // 2) bytes (Y0 U Y1 V, or U Y0 V Y1, per pixel pair; every row has its own chroma); for even w it may be handed
+    in as [h, w, 2]."""
 
     def __init__(self, planes, format, matrix, h: int, w: int, _writable=None):
         self.format = _code(FORMATS, format, "format")
@@ -97,11 +102,15 @@ class YUVFrame:
         if not (1 <= self.h <= MAX_SIDE and 1 <= self.w <= MAX_SIDE):
             raise ValueError(f"frame is {self.h} x {self.w}: sides must be 1..{MAX_SIDE}")
         ch, cw = (self.h + 1) // 2, (self.w + 1) // 2
-        shapes = [(self.h, self.w, "Y"), (ch, 2 * cw, "UV")] if self.format == _lib.YUV_NV12 else \
-                 [(self.h, self.w, "Y"), (ch, cw, "U"), (ch, cw, "V")]
+        if self.format in PACKED:
+            shapes = [(self.h, 4 * cw, _NAMES[self.format])]
+        elif self.format == _lib.YUV_NV12:
+            shapes = [(self.h, self.w, "Y"), (ch, 2 * cw, "UV")]
+        else:
+            shapes = [(self.h, self.w, "Y"), (ch, cw, "U"), (ch, cw, "V")]
         planes = list(planes)
         if len(planes) != len(shapes):
-            raise ValueError(f"{'NV12' if self.format == _lib.YUV_NV12 else 'I420'} has {len(shapes)} planes, got {len(planes)}")
+            raise ValueError(f"{_NAMES[self.format]} has {len(shapes)} plane{'s' if len(shapes) > 1 else ''}, got {len(planes)}")
         on_device = [_lib.is_device_array(a) for a in planes]
         if any(on_device) and not all(on_device):
             raise ValueError("the planes of a frame are all in device memory or all in host memory, got " +
@@ -129,6 +138,31 @@ class YUVFrame:
         h, w = cls._luma_size(y)
         return cls((y, u, v), _lib.YUV_I420, matrix, h, w)
 
+    @classmethod
+    def yuyv(cls, buf, matrix="bt601", w=None) -> "YUVFrame":
+        """The one plane of a YUYV (YUY2) frame: uint8 [h, 4 cw] (bytes Y0 U Y1 V per pixel pair), or [h, w, 2] for even w.  The
+        width is 2 cw unless `w` says that the last pair's second pixel is not part of the frame (w = 2 cw - 1)."""
+        return cls._packed(buf, _lib.YUV_YUYV, matrix, w)
+
+    @classmethod
+    def uyvy(cls, buf, matrix="bt601", w=None) -> "YUVFrame":
+        """The one plane of a UYVY frame: as `yuyv`, bytes U Y0 V Y1 per pixel pair."""
+        return cls._packed(buf, _lib.YUV_UYVY, matrix, w)
+
+    @classmethod
+    def _packed(cls, buf, fmt, matrix, w):
+        shape = tuple(buf.__cuda_array_interface__["shape"]) if _lib.is_device_array(buf) else np.asarray(buf).shape
+        if len(shape) == 3 and shape[2] == 2 and shape[1] % 2 == 0:
+            full = int(shape[1])
+        elif len(shape) == 2 and shape[1] % 4 == 0 and shape[1] > 0:
+            full = int(shape[1]) // 2
+        else:
+            raise ValueError(f"{_NAMES[fmt]} plane must be uint8 [h, 4 cw] or [h, w, 2] with even w, got shape {shape}")
+        w = full if w is None else int(w)
+        if w not in (full, full - 1):
+            raise ValueError(f"a {_NAMES[fmt]} plane of {2 * full} bytes per row holds a frame {full - 1} or {full} wide, got w = {w}")
+        return cls((buf,), fmt, matrix, int(shape[0]), w)
+
     @staticmethod
     def _luma_size(y):
         shape = tuple(y.__cuda_array_interface__["shape"]) if _lib.is_device_array(y) else np.asarray(y).shape
@@ -139,7 +173,8 @@ class YUVFrame:
     @classmethod
     def from_buffer(cls, buf, h: int, w: int, format="nv12", pitch=None, matrix="bt601") -> "YUVFrame":
         """A decoder's single allocation: h rows of luma at `pitch` bytes, then the chroma rows.  NV12: (h + 1) // 2 interleaved
-        rows at the same pitch.  I420: the U rows and then the V rows at (pitch + 1) // 2 bytes.  Without `pitch` the planes are
+        rows at the same pitch.  I420: the U rows and then the V rows at (pitch + 1) // 2 bytes.  YUYV (YUY2) / UYVY: h rows of
+        4 * ((w + 1) // 2) bytes at `pitch` and nothing else.  Without `pitch` the planes are
         tight: every row is followed by the next.  `buf` is anything with
         the buffer interface (bytes, a memoryview, a uint8 array), or a contiguous uint8 DEVICE array (the decoder's surface in
         device memory: the frame is then `on_device`); it is not copied."""
@@ -165,6 +200,22 @@ class YUVFrame:
                 raise ValueError("buffer must be contiguous")
             size = a.size
         ch, cw = (h + 1) // 2, (w + 1) // 2
+
+        def view(off, rows, row_bytes, p):
+            if dev is not None:
+                return _lib.DeviceView(dev.ptr + off, (rows, row_bytes), (p, 1), dev.owner)
+            return np.lib.stride_tricks.as_strided(a[off:], (rows, row_bytes), (p, 1), writeable=False)
+
+        if fmt in PACKED:
+            row = 4 * cw
+            pitch = row if pitch is None else int(pitch)
+            if pitch < row:
+                raise ValueError(f"pitch {pitch} is below a row of the {h} x {w} frame ({row} bytes)")
+            need = pitch * (h - 1) + row
+            if size < need:
+                raise ValueError(f"buffer holds {size} bytes, the frame needs {need} in format {_NAMES[fmt]} ({h} rows of {row} bytes, "
+                                 f"2 per pixel, at pitch {pitch})")
+            return cls([view(0, h, row, pitch)], fmt, matrix, h, w, _writable=writable)
         crow = 2 * cw if fmt == _lib.YUV_NV12 else cw
         if pitch is None:               # tight: every plane's pitch is its row
             pitch, cpitch = w, crow
@@ -177,12 +228,6 @@ class YUVFrame:
         need = pitch * h + (nchroma * ch - 1) * cpitch + crow      # (the last row ends with its last sample)
         if size < need:
             raise ValueError(f"buffer holds {size} bytes, the frame needs {need}")
-
-        def view(off, rows, row_bytes, p):
-            if dev is not None:
-                return _lib.DeviceView(dev.ptr + off, (rows, row_bytes), (p, 1), dev.owner)
-            return np.lib.stride_tricks.as_strided(a[off:], (rows, row_bytes), (p, 1), writeable=False)
-
         planes = [view(0, h, w, pitch)]
         for i in range(nchroma):
             planes.append(view(pitch * h + i * cpitch * ch, ch, crow, cpitch))

@@ -541,6 +541,17 @@ WHENET_API int whenet_letterbox_cache_stats(whenet_t* h, int32_t out[4]);
  *   WHENET_YUV_NV12  plane[0] = Y, plane[1] = U and V interleaved (U at 2 (x >> 1), V behind it), plane[2] unused
  *   WHENET_YUV_I420  plane[0] = Y, plane[1] = U, plane[2] = V
  * Every plane has its own byte pitch >= its row bytes (w; 2 cw for the interleaved plane; cw).
+ * PACKED 4:2:2 (what a V4L2 / UVC camera or a capture card delivers raw), through the same struct and the same ten calls:
+ *   WHENET_YUV_YUYV  (also called YUY2) bytes Y0 U Y1 V per pixel pair
+ *   WHENET_YUV_UYVY  bytes U Y0 V Y1 per pixel pair
+ * One plane: plane[0] has h rows of 4 cw bytes, cw = (w + 1) >> 1, pitch[0] >= 4 cw; plane[1..2] and pitch[1..2] are ignored (NULL
+ * is allowed).  Sides 1..8192, odd widths included: the last pair of an odd row is whole in memory and its second luma byte is not
+ * used.  Pixel (y, x) takes luma Y[x & 1] of pair x >> 1 of row y and THAT pair's U and V: nearest neighbour horizontally and NO
+ * vertical sharing (every row has its own chroma), the one difference from the 4:2:0 rule above.  The arithmetic is the one above,
+ * unchanged: c = max(0, Y - yoff), 20 fractional bits, the three WHENET_YUV_COEFFS rows.  BT.601 stays restated, unpinned for
+ * these formats too (OpenCV's COLOR_YUV2BGR_YUY2 uses the same constants and has never been run against this); JFIF inherits the
+ * Pillow pin of tests/test_yuv_cpu.py because the per-pixel function is shared.  A clip may mix NV12, I420, YUYV and UYVY frames
+ * of different sizes and matrices.  Not built: YVYU / VYUY, planar 4:2:2 / 4:4:4, interpolated chroma, packed destinations.
  *   whenet_yuv_to_bgr_host  the conversion as pure host arithmetic (no GPU needed): bgr = uint8 [h][w][3]; the text of an error is
  *                  whenet_last_error(NULL)'s, the frame's index in it is 0
  *   whenet_op_yuv_to_bgr    the kernel alone, host to host, on 1..16 frames of their own sizes, formats and matrices: bgr[f] = uint8
@@ -554,6 +565,8 @@ WHENET_API int whenet_letterbox_cache_stats(whenet_t* h, int32_t out[4]);
  * plane, a pitch below the plane's row bytes, an unknown format or matrix, a side outside 1..8192, a frame count outside 1..16. */
 #define WHENET_YUV_NV12 0
 #define WHENET_YUV_I420 1
+#define WHENET_YUV_YUYV 3       /* (2 is WHENET_SURF_PACKED of whenet_surface_t; 2 is an unknown format here) */
+#define WHENET_YUV_UYVY 4
 #define WHENET_YUV_BT601 0
 #define WHENET_YUV_BT709 1
 #define WHENET_YUV_JFIF 2
@@ -1168,7 +1181,20 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  *                  whenet_frame_begin / whenet_clip_begin[_mixed] of the oriented frames leaves; a clip is one-size by its ORIENTED sizes
  *   option "jpeg_orient"   0 (default) / 1, above.
  * Not built: oriented I420 / NV12 destinations, whenet_jpeg_decode_device (it sees no header), an orientation stored anywhere but IFD0
- * of the first Exif APP1, other EXIF tags. */
+ * of the first Exif APP1, other EXIF tags.
+ *
+ * JPEG DECODER, DEFAULT TABLES (one entry point, 131 in all, ABI still 6; csrc/jpeg_dec_host.h's jpeg_add_default_tables).  The MJPG
+ * frames of UVC cameras and of many AVI writers carry no DHT segment: their Huffman tables are T.81's Annex K ones, which every
+ * player installs (libjpeg's std_huff_tables).  Every call above refuses such a stream with "a missing Huffman table (DHT)", and
+ * keeps doing so; this pure host function completes the stream first:
+ *   whenet_jpeg_add_default_tables   walks the header to the first SOS.  For each of the four slots DC 0, AC 0, DC 1, AC 1 that no
+ *                  DHT in front of that SOS defines it adds the Annex K table of that slot (K.3 / K.5 for id 0, K.4 / K.6 for id
+ *                  1): the missing tables go into ONE DHT segment, in that order, directly in front of the first SOS marker, at
+ *                  most 420 bytes more.  out[0 .. *out_size) is the completed stream.  A stream that defines all four comes back
+ *                  byte for byte, and so does a header that cannot be followed to an SOS (no SOI, a truncated or malformed
+ *                  segment): this call never refuses a stream, the decoder then gives its own reason.  Ids 2 and 3 are never
+ *                  filled.  WHENET_EINVAL only for a NULL argument or capacity < size + 420.
+ * Not built: default tables for ids 2 / 3, default quantiser tables (no player installs any). */
 #define WHENET_JPEG_SEG_WINDOW 256
 #define WHENET_JPEG_PROG_MAX_SCANS 128
 #define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
@@ -1256,6 +1282,7 @@ WHENET_API int whenet_clip_begin_jpeg_progressive(whenet_t* h, const uint8_t* co
 WHENET_API int whenet_jpeg_clip_plan_progressive(const uint8_t* const* data, const int64_t* size, int num_frames, int entropy, int seg_bytes,
                                       int64_t* out);
 
+WHENET_API int whenet_jpeg_add_default_tables(const uint8_t* data, int64_t size, uint8_t* out, int64_t capacity, int64_t* out_size);
 WHENET_API int whenet_jpeg_orientation(const uint8_t* data, int64_t size);
 WHENET_API int whenet_jpeg_decode_oriented_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
                                      int progressive, int32_t status[2]);
