@@ -16,6 +16,7 @@
 
 #include "engine.h"
 #include "engine_internal.h"
+#include "../../include/whenet_hip_jpeg_accept.h"
 
 // A handle = one primary engine plus, with option "inflight" > 1, replica engines (own streams,
 // activation arena, hipGraphs and a copy of the 8.6-17 MB device weights).  A forward is a chain of
@@ -203,9 +204,9 @@ void require_seg_args(const std::string& what, int seg_bytes, int window) {
 // destination's checks, the padded planes by make_planes(info, planes), the pixel rule
 template <typename F>
 void decode_into_host_surface(const std::string& what, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule,
-                              whenet::JpegProgPlan* plan, F&& make_planes) {
+                              whenet::JpegProgPlan* plan, F&& make_planes, bool layouts = false, bool sof2 = true) {
     whenet_jpeg_info_t info;
-    jpeg_parse_or_refuse(what.c_str(), data, size, info, plan);
+    jpeg_parse_or_refuse(what.c_str(), data, size, info, plan, layouts, sof2);
     const char* bad = whenet::jpeg_dec_check_dst(info, dst, channel_order, rule);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, what + ": " + (bad ? bad : ""));
     WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, what + ": the surface must be host memory (on_device = 0)");
@@ -218,9 +219,9 @@ void decode_into_host_surface(const std::string& what, const uint8_t* data, int6
 // their rows out at the caller's pitch
 template <typename F>
 void decode_into_host_planes(const std::string& what, const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch,
-                             whenet::JpegProgPlan* plan, F&& make_planes) {
+                             whenet::JpegProgPlan* plan, F&& make_planes, bool layouts = false, bool sof2 = true) {
     whenet_jpeg_info_t info;
-    jpeg_parse_or_refuse(what.c_str(), data, size, info, plan);
+    jpeg_parse_or_refuse(what.c_str(), data, size, info, plan, layouts, sof2);
     const whenet::JpegDecGeom g = whenet::jpeg_dec_geom(info);
     for (int c = 0; c < g.comps; ++c) {
         const int cw = c == 0 ? g.w : (g.w + g.hs - 1) / g.hs;
@@ -1506,7 +1507,7 @@ int whenet_frame_begin_jpeg_oriented(whenet_t* h, const uint8_t* data, int64_t s
                                      int* ticket, int32_t* status, int32_t* orientation) {
     int applied = 1;
     const int rc = begin_on_next_engine(
-        h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status, rule, progressive, orient, &applied); });
+        h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status, rule, progressive == -1 ? -1 : int(progressive != 0), orient, &applied); });
     if (rc == WHENET_OK && orientation != nullptr) *orientation = applied;
     return rc;
 }
@@ -1515,10 +1516,193 @@ int whenet_clip_begin_jpeg_oriented(whenet_t* h, const uint8_t* const* data, con
                                     int progressive, int orient, int* ticket, int32_t* status, int32_t* orientation) {
     int applied[whenet::JPEG_CLIP_MAX_FRAMES];
     const int rc = begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
-        return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule, progressive, orient, applied);
+        return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule, int(progressive != 0), orient, applied);
     });
     if (rc == WHENET_OK && orientation != nullptr) std::copy(applied, applied + num_frames, orientation);
     return rc;
+}
+
+// ---- the accept bits (JPEG DECODER, LAYOUTS): the calls above with one `accept` bit set in the place of `progressive` ----
+static_assert(WHENET_JPEG_ACCEPT_PROGRESSIVE == whenet::detail::JPEG_ACCEPT_PROGRESSIVE && WHENET_JPEG_ACCEPT_LAYOUTS == whenet::detail::JPEG_ACCEPT_LAYOUTS,
+              "the header states the accept bits");
+namespace {
+void require_accept(const std::string& what, int accept, bool option_too) {
+    WHENET_REQUIRE((option_too && accept == -1) || whenet::detail::jpeg_accept_ok(accept), WHENET_EINVAL,
+                   what + (option_too ? ": accept must be -1 (the handle's options) or a set of WHENET_JPEG_ACCEPT_* bits (0..3)"
+                                      : ": accept must be a set of WHENET_JPEG_ACCEPT_* bits (0..3)"));
+}
+// the padded planes of a stream parsed with the accept bits (plan: filled where a bit is set)
+void planes_by_accept(const whenet_jpeg_info_t& info, const whenet::JpegProgPlan& plan, int accept, const uint8_t* data, int64_t size,
+                      whenet::JpegDecPlanes& pl, int32_t status[2], int rule) {
+    if (accept != 0) whenet::jpeg_prog_decode_planes_host(info, plan, data, size, pl, status, rule);
+    else whenet::jpeg_dec_planes_host(info, data + info.data_offset, int(size - info.data_offset), pl, status, rule);
+}
+}  // namespace
+
+int whenet_jpeg_parse_scans_accept(const uint8_t* data, int64_t size, int accept, whenet_jpeg_info_t* info, whenet_jpeg_scan_t* scans, int cap,
+                                   int* num_scans) {
+    return host_statement([&] {
+        const std::string what = "jpeg_parse_scans_accept";
+        WHENET_REQUIRE(info != nullptr && num_scans != nullptr && (scans != nullptr || cap == 0) && cap >= 0, WHENET_EINVAL, what + ": NULL argument");
+        require_accept(what, accept, false);
+        whenet::JpegProgPlan plan;      // (accept = 0: the baseline parser's refusals, and its one scan as the scan parser records it)
+        jpeg_parse_or_refuse(what.c_str(), data, size, *info, &plan, (accept & WHENET_JPEG_ACCEPT_LAYOUTS) != 0,
+                             (accept & WHENET_JPEG_ACCEPT_PROGRESSIVE) != 0);
+        *num_scans = int(plan.scans.size());
+        WHENET_REQUIRE(cap >= *num_scans, WHENET_EINVAL,
+                       what + ": the stream has " + std::to_string(*num_scans) + " scans, the capacity is " + std::to_string(cap));
+        for (size_t i = 0; i < plan.scans.size(); ++i) scans[i] = plan.scans[i];
+    });
+}
+
+int whenet_jpeg_decode_accept_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int rule, int accept, int orient,
+                                   int32_t status[2], int32_t* orientation) {
+    return host_statement([&] {
+        const std::string what = "jpeg_decode_accept_host";
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        require_accept(what, accept, false);
+        WHENET_REQUIRE(orient == 0 || orient == 1, WHENET_EINVAL, what + ": orient must be 0 (the orientation is ignored) or 1 (it is applied)");
+        whenet_jpeg_info_t info;
+        whenet::JpegProgPlan plan;
+        whenet::detail::jpeg_parse_accept_or_refuse(what.c_str(), data, size, info, plan, accept);
+        const int o = orient ? whenet::jpeg_exif_orientation(data, size) : 1;
+        WHENET_REQUIRE(o <= 1 || (dst->format != WHENET_YUV_I420 && dst->format != WHENET_YUV_NV12), WHENET_EINVAL,
+                       what + ": the stream's orientation is " + std::to_string(o) +
+                           ": an oriented decode writes packed surfaces only (WHENET_SURF_PACKED)");
+        const whenet_jpeg_info_t landed = whenet::jpeg_orient_info(info, o);
+        const char* bad = whenet::jpeg_dec_check_dst(landed, dst, channel_order, rule);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, what + ": " + (bad ? bad : ""));
+        WHENET_REQUIRE(dst->on_device == 0, WHENET_EINVAL, what + ": the surface must be host memory (on_device = 0)");
+        whenet::JpegDecPlanes planes;
+        planes_by_accept(info, plan, accept, data, size, planes, status, rule);
+        whenet::jpeg_dec_frame_oriented_host(whenet::jpeg_dec_geom(info), planes, *dst, channel_order, rule, o);
+        if (orientation != nullptr) *orientation = o;
+    });
+}
+
+int whenet_jpeg_decode_accept_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int rule, int accept,
+                                          int32_t status[2]) {
+    return host_statement([&] {
+        const std::string what = "jpeg_decode_accept_planes_host";
+        WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        WHENET_REQUIRE(whenet::jpeg_rule_ok(rule), WHENET_EINVAL, what + ": the rule must be 0 or 1");
+        require_accept(what, accept, false);
+        whenet::JpegProgPlan plan;
+        decode_into_host_planes(
+            what, data, size, planes, pitch, accept != 0 ? &plan : nullptr,
+            [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) { planes_by_accept(info, plan, accept, data, size, pl, status, rule); },
+            (accept & WHENET_JPEG_ACCEPT_LAYOUTS) != 0, (accept & WHENET_JPEG_ACCEPT_PROGRESSIVE) != 0);
+    });
+}
+
+int whenet_jpeg_decode_segmented_accept_host(const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int seg_bytes,
+                                             int window, int rule, int accept, int32_t status[2], int64_t stats[8]) {
+    return host_statement([&] {
+        const std::string what = "jpeg_decode_segmented_accept_host";
+        WHENET_REQUIRE(dst != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        require_seg_args(what, seg_bytes, window);
+        // (the segmented form is the baseline decoder's: the PROGRESSIVE bit has nothing to select here)
+        WHENET_REQUIRE(accept == 0 || accept == WHENET_JPEG_ACCEPT_LAYOUTS, WHENET_EINVAL, what + ": accept must be 0 or WHENET_JPEG_ACCEPT_LAYOUTS");
+        decode_into_host_surface(
+            what, data, size, dst, channel_order, rule, nullptr,
+            [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+                whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, pl, status, stats, rule);
+            },
+            accept != 0);
+    });
+}
+
+int whenet_jpeg_decode_segmented_accept_planes_host(const uint8_t* data, int64_t size, uint8_t* const* planes, const int* pitch, int seg_bytes,
+                                                    int window, int rule, int accept, int32_t status[2], int64_t stats[8]) {
+    return host_statement([&] {
+        const std::string what = "jpeg_decode_segmented_accept_planes_host";
+        WHENET_REQUIRE(planes != nullptr && pitch != nullptr && status != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        WHENET_REQUIRE(whenet::jpeg_rule_ok(rule), WHENET_EINVAL, what + ": the rule must be 0 or 1");
+        require_seg_args(what, seg_bytes, window);
+        WHENET_REQUIRE(accept == 0 || accept == WHENET_JPEG_ACCEPT_LAYOUTS, WHENET_EINVAL, what + ": accept must be 0 or WHENET_JPEG_ACCEPT_LAYOUTS");
+        decode_into_host_planes(
+            what, data, size, planes, pitch, nullptr,
+            [&](const whenet_jpeg_info_t& info, whenet::JpegDecPlanes& pl) {
+                whenet::jpeg_dec_planes_seg_host(info, data + info.data_offset, int(size - info.data_offset), seg_bytes, window, pl, status, stats, rule);
+            },
+            accept != 0);
+    });
+}
+
+int whenet_op_jpeg_decode_accept(whenet_t* h, const uint8_t* data, int64_t size, const whenet_surface_t* dst, int channel_order, int entropy,
+                                 int seg_bytes, int rule, int accept, int orient, int32_t status[2], int64_t stats[8], int32_t* orientation) {
+    return guarded(h, [&](whenet::Engine& e) {
+        const std::string what = "op_jpeg_decode_accept";
+        WHENET_REQUIRE(dst != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       what + ": entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL, what + ": seg_bytes must be a power of two in 4..4096");
+        require_accept(what, accept, true);
+        int applied = 1;
+        e.op_jpeg_decode(data, size, *dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, stats, rule, accept, orient, &applied);
+        if (orientation != nullptr) *orientation = applied;
+    });
+}
+
+int whenet_op_jpeg_decode_clip_accept(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, const whenet_surface_t* dst,
+                                      int channel_order, int32_t* status, int entropy, int seg_bytes, int rule, int accept, int orient,
+                                      int32_t* orientation) {
+    return guarded(h, [&](whenet::Engine& e) {
+        const std::string what = "op_jpeg_decode_clip_accept";
+        WHENET_REQUIRE(entropy >= -1 && entropy <= 1, WHENET_EINVAL,
+                       what + ": entropy must be -1 (the handle's options), 0 (an interval per lane) or 1 (segmented)");
+        WHENET_REQUIRE(entropy != 1 || whenet::jpeg_seg_bytes_ok(seg_bytes), WHENET_EINVAL, what + ": seg_bytes must be a power of two in 4..4096");
+        require_accept(what, accept, false);
+        int applied[whenet::JPEG_CLIP_MAX_FRAMES];
+        e.op_jpeg_decode_clip(data, size, num_frames, dst, channel_order, status, entropy, entropy == 1 ? seg_bytes : 0, rule, accept, orient, applied);
+        if (orientation != nullptr) std::copy(applied, applied + num_frames, orientation);
+    });
+}
+
+int whenet_frame_begin_jpeg_accept(whenet_t* h, const uint8_t* data, int64_t size, int channel_order, int rule, int accept, int orient, int* ticket,
+                                   int32_t* status, int32_t* orientation) {
+    int applied = 1;
+    const int rc = begin_on_next_engine(
+        h, ticket, [&](whenet::Engine& e) { return e.frame_begin_jpeg(data, size, channel_order, status, rule, accept, orient, &applied); });
+    if (rc == WHENET_OK && orientation != nullptr) *orientation = applied;
+    return rc;
+}
+
+int whenet_clip_begin_jpeg_accept(whenet_t* h, const uint8_t* const* data, const int64_t* size, int num_frames, int channel_order, int rule,
+                                  int accept, int orient, int* ticket, int32_t* status, int32_t* orientation) {
+    int applied[whenet::JPEG_CLIP_MAX_FRAMES];
+    const int rc = begin_on_next_engine(
+        h, ticket, [&](whenet::Engine& e) { return e.clip_begin_jpeg(data, size, num_frames, channel_order, status, rule, accept, orient, applied); });
+    if (rc == WHENET_OK && orientation != nullptr) std::copy(applied, applied + num_frames, orientation);
+    return rc;
+}
+
+int whenet_jpeg_clip_plan_accept(const uint8_t* const* data, const int64_t* size, int num_frames, int entropy, int seg_bytes, int accept,
+                                 int64_t* out) {
+    try {
+        const std::string what = "jpeg_clip_plan_accept";
+        WHENET_REQUIRE(num_frames >= 1 && num_frames <= whenet::JPEG_CLIP_MAX_FRAMES, WHENET_EINVAL, what + ": a clip holds 1..16 frames");
+        WHENET_REQUIRE(data != nullptr && size != nullptr && out != nullptr, WHENET_EINVAL, what + ": NULL argument");
+        require_accept(what, accept, false);
+        std::vector<whenet::JpegProgPlan> plans(static_cast<size_t>(num_frames));
+        const whenet::JpegProgPlan* ptr[whenet::JPEG_CLIP_MAX_FRAMES];
+        whenet::JpegDecGeom g[whenet::JPEG_CLIP_MAX_FRAMES];
+        int64_t nbytes[whenet::JPEG_CLIP_MAX_FRAMES];
+        for (int f = 0; f < num_frames; ++f) {
+            whenet_jpeg_info_t info;
+            const std::string who = what + ": frame " + std::to_string(f);
+            whenet::detail::jpeg_parse_or_refuse(who.c_str(), data[f], size[f], info, &plans[size_t(f)], (accept & WHENET_JPEG_ACCEPT_LAYOUTS) != 0,
+                                                 (accept & WHENET_JPEG_ACCEPT_PROGRESSIVE) != 0);
+            g[f] = whenet::jpeg_dec_geom(info), nbytes[f] = size[f] - info.data_offset, ptr[f] = &plans[size_t(f)];
+        }
+        whenet::JpegClipProgPlan plan;
+        const char* bad = whenet::jpeg_clip_plan_progressive(g, nbytes, ptr, num_frames, entropy, seg_bytes, plan);
+        WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, what + ": " + (bad ? bad : ""));
+        whenet::jpeg_clip_plan_progressive_words(plan, out);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);
+    }
 }
 
 int whenet_yolo_eval_mixed(whenet_t* h, const float* const* feats, int num_images, const int* grid_h, const int* grid_w, int num_layers,

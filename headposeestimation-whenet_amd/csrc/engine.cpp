@@ -289,6 +289,11 @@ void Engine::set_option(const std::string& key, long value) {
         WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL, "jpeg_progressive must be 0 (SOF2 streams are refused, default) or 1 (they are decoded)");
         jpeg_progressive_ = int(value);
         return;
+    } else if (key == "jpeg_layouts") {
+        WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL,
+                       "jpeg_layouts must be 0 (4:4:0 / 4:1:1 / 4:1:0 and SOF1 streams are refused, default) or 1 (they are decoded)");
+        jpeg_layouts_ = int(value);
+        return;
     } else if (key == "jpeg_orient") {
         WHENET_REQUIRE(value == 0 || value == 1, WHENET_EINVAL,
                        "jpeg_orient must be 0 (the EXIF orientation is ignored, default) or 1 (single streams are decoded upright)");

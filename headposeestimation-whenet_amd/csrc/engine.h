@@ -624,6 +624,8 @@ class Engine {
     int jpeg_entropy_ = 2, jpeg_seg_bytes_ = JPEG_SEG_DEFAULT_BYTES;      // options "jpeg_entropy", "jpeg_seg_bytes"
     int jpeg_rule_ = JPEG_RULE_OWN;                                       // option "jpeg_rule"
     int jpeg_progressive_ = 0, jpeg_prog_levels_ = 1;                     // options "jpeg_progressive", "jpeg_prog_levels"
+    int jpeg_layouts_ = 0;                                                // option "jpeg_layouts" (the header's JPEG DECODER, LAYOUTS)
+    int jpeg_accept_of(const char* what, int accept) const;               // the accept bits of a call: its argument, or (-1) the two options
     int jpeg_orient_ = 0;                                                 // option "jpeg_orient"
     // the orientation a single-stream call applies: the stream's tag where `orient` is 1, or -1 with the option set; else 1
     int jpeg_orient_of(const char* what, int orient, const uint8_t* data, int64_t size) const;

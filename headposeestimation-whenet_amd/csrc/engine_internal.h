@@ -37,10 +37,23 @@ struct TempBufs {     // hipMalloc'd scratch of the single-stage entry points
 // The header of a JPEG stream into `info`, for the engine and for the host statements of capi.cpp alike.  plan: nullptr (baseline
 // streams only), or where the scan plan goes (the parser that accepts progressive streams too).  WHENET_EINVAL, or WHENET_EFORMAT
 // with the parser's reason.
-inline void jpeg_parse_or_refuse(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info, JpegProgPlan* plan = nullptr) {
+// layouts, sof2: the parsers' arguments (the header's JPEG DECODER, LAYOUTS): with layouts a plan is needed whether or not SOF2
+// frames are accepted (a sequential frame of several scans has one), and sof2 says whether they are.
+inline void jpeg_parse_or_refuse(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info, JpegProgPlan* plan = nullptr,
+                                 bool layouts = false, bool sof2 = true) {
     WHENET_REQUIRE(data != nullptr && size >= 1, WHENET_EINVAL, std::string(what) + ": NULL argument or size < 1");
-    const char* bad = plan != nullptr ? jpeg_prog_parse(data, size, info, *plan) : jpeg_parse(data, size, info);
+    const char* bad = plan != nullptr ? jpeg_prog_parse(data, size, info, *plan, layouts, sof2) : jpeg_parse(data, size, info, layouts);
     WHENET_REQUIRE(bad == nullptr, WHENET_EFORMAT, std::string(what) + ": " + (bad ? bad : ""));
+}
+
+// The `progressive` argument of the engine's JPEG calls is a set of accept bits (include/whenet_hip_jpeg_accept.h: WHENET_JPEG_ACCEPT_*): 0 and 1
+// are what they were, 2 adds the layouts; -1 stands for the handle's options "jpeg_progressive" and "jpeg_layouts".
+constexpr int JPEG_ACCEPT_PROGRESSIVE = 1, JPEG_ACCEPT_LAYOUTS = 2;
+inline bool jpeg_accept_ok(int accept) { return accept >= 0 && accept <= (JPEG_ACCEPT_PROGRESSIVE | JPEG_ACCEPT_LAYOUTS); }
+// a stream parsed with these bits (jpeg_accept_ok) into info and, where either bit is set, its scan plan
+inline void jpeg_parse_accept_or_refuse(const char* what, const uint8_t* data, int64_t size, whenet_jpeg_info_t& info, JpegProgPlan& plan, int accept) {
+    jpeg_parse_or_refuse(what, data, size, info, accept != 0 ? &plan : nullptr, (accept & JPEG_ACCEPT_LAYOUTS) != 0,
+                         (accept & JPEG_ACCEPT_PROGRESSIVE) != 0);
 }
 
 struct FlagGuard {    // sets a flag for a scope

@@ -1499,6 +1499,13 @@ static void jpeg_orient_require_packed(const std::string& what, int orient, cons
                        ": an oriented decode writes packed surfaces only (WHENET_SURF_PACKED)");
 }
 
+// the accept bits of a single-stream call: the argument, or (-1) the handle's options "jpeg_progressive" and "jpeg_layouts"
+int Engine::jpeg_accept_of(const char* what, int accept) const {
+    WHENET_REQUIRE(accept == -1 || jpeg_accept_ok(accept), WHENET_EINVAL,
+                   std::string(what) + ": the accept bits must be -1 (the handle's options) or 0..3 (1: progressive streams, 2: layouts)");
+    return accept == -1 ? (jpeg_progressive_ != 0 ? JPEG_ACCEPT_PROGRESSIVE : 0) | (jpeg_layouts_ != 0 ? JPEG_ACCEPT_LAYOUTS : 0) : accept;
+}
+
 void Engine::add_jpeg_decode_counters(int64_t out[4]) const { out[0] += jpeg_dec_launched_[0], out[1] += jpeg_dec_launched_[1]; }
 void Engine::add_jpeg_progressive_counters(int64_t out[4]) const {
     for (int i = 0; i < 3; ++i) out[i] += jpeg_prog_counts_[i];
@@ -1560,8 +1567,9 @@ void Engine::op_jpeg_decode(const uint8_t* data, int64_t size, const whenet_surf
     rule = jpeg_rule_of("op_jpeg_decode", rule);
     whenet_jpeg_info_t info;
     JpegProgPlan plan;
-    const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
-    jpeg_parse_or_refuse("op_jpeg_decode", data, size, info, accept ? &plan : nullptr);
+    const int bits = jpeg_accept_of("op_jpeg_decode", progressive);
+    const bool accept = bits != 0;      // (the stream has a scan plan: `plan.baseline` where the baseline decoder takes it)
+    jpeg_parse_accept_or_refuse("op_jpeg_decode", data, size, info, plan, bits);
     const int o = jpeg_orient_of("op_jpeg_decode", orient, data, size);
     jpeg_orient_require_packed("op_jpeg_decode", o, dst);
     const whenet_jpeg_info_t landed = jpeg_orient_info(info, o);      // (the destination is the oriented frame)
@@ -1601,7 +1609,7 @@ void Engine::jpeg_decode_device(const whenet_jpeg_info_t& info, const uint8_t* d
     DeviceGuard guard(device_);
     WHENET_REQUIRE(d_entropy != nullptr && d_status != nullptr, WHENET_EINVAL, "jpeg_decode_device: NULL argument");
     WHENET_REQUIRE(nbytes >= 1 && nbytes <= JPEG_DEC_MAX_BYTES, WHENET_EINVAL, "jpeg_decode_device: nbytes must be 1..2^31 - 1");
-    const char* bad = jpeg_dec_check_info(info);
+    const char* bad = jpeg_dec_check_info(info, jpeg_layouts_ != 0);      // (no argument here: the handle's option "jpeg_layouts")
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_device: info: ") + (bad ? bad : ""));
     bad = jpeg_dec_check_dst(info, &dst, channel_order, jpeg_rule_);
     WHENET_REQUIRE(bad == nullptr, WHENET_EINVAL, std::string("jpeg_decode_device: ") + (bad ? bad : ""));
@@ -1687,8 +1695,9 @@ int Engine::frame_begin_jpeg(const uint8_t* data, int64_t size, int channel_orde
     WHENET_REQUIRE(channel_order == WHENET_RGB || channel_order == WHENET_BGR, WHENET_EINVAL, "frame_begin_jpeg: unknown channel order");
     whenet_jpeg_info_t info;
     JpegProgPlan plan;
-    const bool accept = progressive == -1 ? jpeg_progressive_ != 0 : progressive != 0;
-    jpeg_parse_or_refuse("frame_begin_jpeg", data, size, info, accept ? &plan : nullptr);      // (before a slot is taken)
+    const int bits = jpeg_accept_of("frame_begin_jpeg", progressive);
+    const bool accept = bits != 0;
+    jpeg_parse_accept_or_refuse("frame_begin_jpeg", data, size, info, plan, bits);      // (before a slot is taken)
     const int o = jpeg_orient_of("frame_begin_jpeg", orient, data, size);
     const whenet_jpeg_info_t landed = jpeg_orient_info(info, o);      // (the slot's frame is the oriented one: the same byte count)
     const JpegStreamJob job(*this, info, plan, accept, size, -1, 0);
@@ -1730,11 +1739,13 @@ void Engine::jpeg_clip_prepare(const char* what, const uint8_t* const* data, con
     job.frames = nframes;
     job.info.resize(size_t(nframes));
     job.landed.resize(size_t(nframes));
-    job.progressive = progressive != 0;
+    WHENET_REQUIRE(jpeg_accept_ok(progressive), WHENET_EINVAL, w + ": the accept bits must be 0..3 (1: progressive streams, 2: layouts)");
+    job.progressive = progressive != 0;      // (every frame has a scan plan: `baseline` where the baseline decoder takes it)
     if (job.progressive) job.prog.resize(size_t(nframes));
     for (int f = 0; f < nframes; ++f) {
         const std::string who = w + ": frame " + std::to_string(f);
-        jpeg_parse_or_refuse(who.c_str(), data[f], size[f], job.info[f], job.progressive ? &job.prog[size_t(f)] : nullptr);
+        JpegProgPlan none;
+        jpeg_parse_accept_or_refuse(who.c_str(), data[f], size[f], job.info[f], job.progressive ? job.prog[size_t(f)] : none, progressive);
         job.g[f] = jpeg_dec_geom(job.info[f]);
         job.nbytes[f] = size[f] - job.info[f].data_offset;
         job.orient[f] = orient != 0 ? jpeg_exif_orientation(data[f], size[f]) : 1;

@@ -17,7 +17,7 @@
 //                                   lane y runs the row pass of row y and stores its 8 samples as one 8-byte store.  The component
 //                                   planes are padded to whole MCUs, so every block lies inside its plane.  Writes the status words.
 //   whenet_jpeg_dec_frame_kernel    planes -> packed pixels, 4 pixels of a row per lane: one luma dword, the chroma samples of
-//                                   (x >> (hs - 1), y >> (vs - 1)), 12 bytes out with the head / funnel-shift / tail stores of yuv.hip.
+//                                   (x >> log2 hs, y >> log2 vs) (hs = 4: one byte for the group), 12 bytes out with the head / funnel-shift / tail stores of yuv.hip.
 //                                   A tight BGR destination of a 4:2:0 stream goes through yuv.hip's own plane kernel instead.
 //   whenet_jpeg_dec_yuv_kernel      4:2:0 planes -> an I420 or NV12 surface (a copy).
 //   whenet_jpeg_dec_frame_oriented_kernel   in the frame kernel's place where the record's EXIF orientation is 2..8 (the header's JPEG
@@ -231,11 +231,13 @@ template <>
 __device__ __forceinline__ void frame_group<JPEG_RULE_OWN>(const JpegDecArgs& a, int y, int x, uint32_t px[4]) {
     // (x is a multiple of 4 and the planes' pitches are multiples of 8: the loads are aligned and inside the padded planes)
     const uint32_t y4 = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
-    const int hsh = a.g.hs - 1, vsh = a.g.vs - 1;
+    const int hsh = jpeg_dec_shift(a.g.hs), vsh = jpeg_dec_shift(a.g.vs);
     uint32_t u4 = 0, v4 = 0;
     if (a.g.comps == 3) {
         const size_t ci = size_t(y >> vsh) * size_t(a.g.plane_pitch[1]) + size_t(x >> hsh);
-        if (hsh) {
+        if (hsh == 2) {      // hs = 4: the group's four pixels share ONE sample (j >> 2 = 0 below): a byte load, aligned wherever it lies
+            u4 = a.plane[1][ci], v4 = a.plane[2][ci];
+        } else if (hsh) {
             u4 = *reinterpret_cast<const uint16_t*>(a.plane[1] + ci), v4 = *reinterpret_cast<const uint16_t*>(a.plane[2] + ci);
         } else {
             u4 = *reinterpret_cast<const uint32_t*>(a.plane[1] + ci), v4 = *reinterpret_cast<const uint32_t*>(a.plane[2] + ci);
@@ -258,17 +260,33 @@ template <>
 __device__ __forceinline__ void frame_group<JPEG_RULE_LIBJPEG>(const JpegDecArgs& a, int y, int x, uint32_t px[4]) {
     const int h = a.g.h, w = a.g.w;
     const uint32_t y4 = *reinterpret_cast<const uint32_t*>(a.plane[0] + size_t(y) * size_t(a.g.plane_pitch[0]) + size_t(x));
-    const int hsh = a.g.hs - 1, vsh = a.g.vs - 1;
+    const int hsh = jpeg_dec_shift(a.g.hs), vsh = jpeg_dec_shift(a.g.vs);
     const int ch = (h + a.g.vs - 1) >> vsh, cw = (w + a.g.hs - 1) >> hsh;
     int uv[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // Cb, Cr of the 4 pixels
     if (a.g.comps == 3) {
         const int cr = y >> vsh;
-        if (hsh == 0) {                               // 4:4:4: the samples themselves (x + 3 lies inside the padded plane)
+        if (hsh == 0 && vsh == 0) {                   // 4:4:4: the samples themselves (x + 3 lies inside the padded plane)
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const uint32_t v = *reinterpret_cast<const uint32_t*>(a.plane[c + 1] + size_t(cr) * size_t(a.g.plane_pitch[c + 1]) + size_t(x));
 #pragma unroll
                 for (int j = 0; j < 4; ++j) uv[c][j] = int((v >> (8 * j)) & 255u);
+            }
+        } else if (hsh == 0) {                        // 4:4:0: the vertical filter alone, at every width (h1v2_fancy_upsample); the
+            // neighbour row is clamped to the real plane, the columns x .. x + 3 lie inside the padded one (a dword each, aligned)
+            const int cn = min(max(cr + ((y & 1) ? 1 : -1), 0), ch - 1);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint32_t own = *reinterpret_cast<const uint32_t*>(a.plane[c + 1] + size_t(cr) * size_t(a.g.plane_pitch[c + 1]) + size_t(x));
+                const uint32_t oth = *reinterpret_cast<const uint32_t*>(a.plane[c + 1] + size_t(cn) * size_t(a.g.plane_pitch[c + 1]) + size_t(x));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) uv[c][j] = jpeg_fancy_v(int((own >> (8 * j)) & 255u), int((oth >> (8 * j)) & 255u), (y & 1) != 0);
+            }
+        } else if (hsh == 2) {                        // 4:1:1, 4:1:0: replication in both directions (int_upsample): one byte per group
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int s = a.plane[c + 1][size_t(cr) * size_t(a.g.plane_pitch[c + 1]) + size_t(x >> 2)];
+                uv[c][0] = uv[c][1] = uv[c][2] = uv[c][3] = s;
             }
         } else if (cw <= 2) {                         // libjpeg's own switch: replication, no vertical filter either
 #pragma unroll
@@ -496,7 +514,7 @@ void check_jpeg_dec_args(const JpegDecArgs& a) {
     // (the destination is the ORIENTED frame: for 5..8 g.w rows of 3 g.h bytes)
     const int planes = overlay_surface_planes(a.format, jpeg_orient_h(a.orient, g.h, g.w), jpeg_orient_w(a.orient, g.h, g.w), rows, row_bytes);
     WHENET_REQUIRE(planes > 0 && g.h >= 1 && g.w >= 1 && g.h <= JPEG_MAX_SIDE && g.w <= JPEG_MAX_SIDE && (g.comps == 1 || g.comps == 3) &&
-                       (g.hs == 1 || g.hs == 2) && (g.vs == 1 || g.vs == 2) && g.bpm == (g.comps == 3 ? g.hs * g.vs + 2 : 1) &&
+                       (g.hs == 1 || g.hs == 2 || (g.hs == 4 && g.comps == 3)) && (g.vs == 1 || g.vs == 2) && g.bpm == (g.comps == 3 ? g.hs * g.vs + 2 : 1) &&
                        g.mcu_cols == (g.w + 8 * g.hs - 1) / (8 * g.hs) && g.mcu_rows == (g.h + 8 * g.vs - 1) / (8 * g.vs) && g.ri >= 1 &&
                        (long long)(g.intervals) == ((long long)(g.mcu_cols) * g.mcu_rows + g.ri - 1) / g.ri,
                    WHENET_EINVAL, "jpeg_decode: bad geometry");

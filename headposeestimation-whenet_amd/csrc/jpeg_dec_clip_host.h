@@ -67,7 +67,8 @@ struct JpegClipProgPlan {
     JpegClipPlan base;
     JpegClipProgFrame pf[JPEG_CLIP_MAX_FRAMES];
     int progressive;       // the progressive frames
-    int scan_launches;     // the largest level count among them: launch L of the scan kernel covers level L of every frame that has one
+    int scan_launches;     // the largest level count among the SOF2 frames: launch L of the scan kernel covers level L of every frame that
+                           // has one; + 1 where the clip holds sequential frames that go through the scan plan (plan.sequential)
 };
 
 inline bool jpeg_clip_is_progressive(const JpegProgPlan* plan) { return plan != nullptr && !plan->baseline; }
@@ -95,7 +96,7 @@ inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_
         if (!jpeg_clip_geom_ok(g[f])) return "bad geometry";
         if (is_prog(f)) {
             const JpegProgPlan& s = *prog[f];
-            if (s.dev.empty() || s.huff.size() != 3 * s.dev.size() || s.items.empty() || s.items.size() % JPEG_PROG_LANES != 0 || s.levels < 1 ||
+            if (s.dev.empty() || s.huff.size() != size_t(s.huff_per_scan()) * s.dev.size() || (s.sequential && s.levels != 1) || s.items.empty() || s.items.size() % JPEG_PROG_LANES != 0 || s.levels < 1 ||
                 s.level_off.size() != size_t(s.levels) || s.level_cnt.size() != size_t(s.levels) || s.data_bytes < 0 || s.data_bytes > JPEG_DEC_MAX_BYTES)
                 return "not the plan of a progressive stream";
         } else if (!jpeg_clip_nbytes_ok(nbytes[f])) {
@@ -110,6 +111,7 @@ inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_
     const auto take = [&](JpegClipRegion& r, size_t len) { r.off = at, r.len = len, at = up(at + len); };
     const auto none = [&](JpegClipRegion& r) { r = {at, 0}; };
     take(p.records, size_t(frames) * JPEG_CLIP_RECORD_BYTES);
+    int prog_launches = 0, seq_launch = 0;
     for (int f = 0; f < frames; ++f) {
         JpegClipFrame& q = p.f[f];
         JpegClipProgFrame& r = pp.pf[f];
@@ -118,7 +120,10 @@ inline const char* jpeg_clip_plan_progressive(const JpegDecGeom* g, const int64_
             q.form = JPEG_CLIP_FORM_PROGRESSIVE, q.seg_bytes = 0, q.seg_cap = 0;
             r.nscans = int(s.dev.size()), r.levels = s.levels, r.list = int(s.items.size());
             ++pp.progressive;
-            if (s.levels > pp.scan_launches) pp.scan_launches = s.levels;
+            // (the sequential frames of a clip -- one level each -- share ONE launch of their own scan kernel, the SOF2 frames a launch per level)
+            if (s.sequential) seq_launch = 1;
+            else if (s.levels > prog_launches) prog_launches = s.levels;
+            pp.scan_launches = prog_launches + seq_launch;
             none(q.tables);
             take(r.scans, s.dev.size() * sizeof(JpegProgScan));
             take(r.huff, s.huff.size() * sizeof(JpegDecHuff));

@@ -39,8 +39,8 @@ struct JpegDecTables {
 };
 // The geometry of a stream, from its whenet_jpeg_info_t
 struct JpegDecGeom {
-    int h, w, comps, hs, vs;          // hs, vs: the luma sampling factors, 1 or 2 (grey: 1, 1)
-    int mcu_cols, mcu_rows, bpm;      // blocks per MCU: hs vs + 2, or 1 for grey
+    int h, w, comps, hs, vs;          // hs, vs: the luma sampling factors, hs 1, 2 or 4 and vs 1 or 2 (grey: 1, 1)
+    int mcu_cols, mcu_rows, bpm;      // blocks per MCU: hs vs + 2 (up to 10, T.81's limit), or 1 for grey
     int ri, intervals;                // MCUs per interval (no DRI: all of them), ceil(MCUs / ri)
     int qt[3], dc[3], ac[3];          // per component: quantiser id, index of its DC / AC table in JpegDecTables::huff
     int plane_pitch[3], plane_rows[3];// the component planes padded to whole MCUs: every block lies inside its plane
@@ -60,6 +60,14 @@ inline JpegDecGeom jpeg_dec_geom(const whenet_jpeg_info_t& in) {
         g.plane_pitch[c] = g.mcu_cols * 8 * (c == 0 ? g.hs : 1), g.plane_rows[c] = g.mcu_rows * 8 * (c == 0 ? g.vs : 1);
     }
     return g;
+}
+
+// log2 of a sampling factor 1, 2 or 4: the shift that takes a pixel's coordinate to its chroma sample's (host and device)
+WHENET_HD inline int jpeg_dec_shift(int factor) { return factor >> 1; }
+// the luma factors the decoder has geometry for: the baseline set, and with `layouts` 1x2 (4:4:0), 4x1 (4:1:1) and 4x2 (4:1:0) too
+inline bool jpeg_dec_sampling_ok(int hs, int vs, bool layouts) {
+    if ((hs == 2 && vs == 2) || (hs == 2 && vs == 1) || (hs == 1 && vs == 1)) return true;
+    return layouts && ((hs == 1 && vs == 2) || (hs == 4 && vs == 1) || (hs == 4 && vs == 2));
 }
 
 // ---- the segment readers (pure host): one grammar for jpeg_parse below and jpeg_prog_parse (jpeg_prog_host.h) ----
@@ -88,7 +96,8 @@ inline const char* jpeg_next_segment(const uint8_t* d, int64_t size, bool scanne
 }
 
 // SOF0, or SOF2 (sof2: the name in the texts): the frame into `in`, its component ids into comp_id
-inline const char* jpeg_read_sof(const uint8_t* s, int n, bool sof2, whenet_jpeg_info_t& in, int comp_id[3]) {
+// (layouts: the samplings of the header's JPEG DECODER, LAYOUTS are frames too; the other factors are refused by name)
+inline const char* jpeg_read_sof(const uint8_t* s, int n, bool sof2, whenet_jpeg_info_t& in, int comp_id[3], bool layouts = false) {
     if (n < 6) return sof2 ? "a short SOF2" : "a short SOF0";
     if (s[0] == 12) return "12-bit samples: 8-bit streams only";
     if (s[0] != 8) return "the sample precision is not 8 bit";
@@ -105,10 +114,14 @@ inline const char* jpeg_read_sof(const uint8_t* s, int n, bool sof2, whenet_jpeg
         if (in.components == 1) {
             in.hs = in.vs = 1;      // one component: the MCU is one block whatever the factors say
         } else if (c == 0) {
-            if (hv != 0x22 && hv != 0x21 && hv != 0x11) return "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
+            if (!jpeg_dec_sampling_ok(hv >> 4, hv & 15, layouts))
+                return !layouts          ? "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)"
+                       : (hv & 15) == 4  ? "a luma sampling factor vs = 4: the luma factors must be hs 1, 2 or 4 by vs 1 or 2"
+                                         : "luma sampling factors other than hs 1, 2 or 4 by vs 1 or 2";
             in.hs = hv >> 4, in.vs = hv & 15;
         } else if (hv != 0x11) {
-            return "chroma sampling must be 1x1";
+            if (layouts && c == 2) return "Cb and Cr sampling factors that differ: chroma sampling must be 1x1";      // (Cb's were 1x1)
+            return layouts ? "chroma sampling factors other than 1x1: chroma sampling must be 1x1" : "chroma sampling must be 1x1";
         }
     }
     return nullptr;
@@ -171,7 +184,9 @@ inline const char* jpeg_read_dht(const uint8_t* s, int n, int max_id, uint8_t (*
 
 // ---- parse (pure host) ----
 // SOI .. SOS into `in`; returns nullptr, or the reason the stream is refused.
-inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in) {
+// layouts (the header's JPEG DECODER, LAYOUTS): the luma samplings 1x2, 4x1 and 4x2 are frames too, and so is a SOF1 frame that
+// is a baseline one but for its marker (8 bit, one interleaved scan, Huffman ids 0..1).  Without it every text is the one it was.
+inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in, bool layouts = false) {
     std::memset(&in, 0, sizeof(in));
     if (size > JPEG_DEC_MAX_BYTES) return "a stream above 2^31 - 1 bytes";
     if (size < 4 || d[0] != 0xFF || d[1] != 0xD8) return "no SOI marker at the start: not a JPEG stream";
@@ -184,13 +199,13 @@ inline const char* jpeg_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t
         const char* bad = jpeg_next_segment(d, size, false, p, m, s, n);
         if (bad != nullptr) return bad;
         if (m == 0xC2) return "progressive DCT (SOF2): baseline sequential streams only";
-        if (m == 0xC1) return "extended sequential DCT (SOF1): baseline sequential streams only";
+        if (m == 0xC1 && !layouts) return "extended sequential DCT (SOF1): baseline sequential streams only";
         if (m == 0xC3 || (m >= 0xC5 && m <= 0xC7)) return "a lossless, differential or hierarchical frame (SOF3, SOF5-7): baseline only";
         if (m == 0xCC || (m >= 0xC9 && m <= 0xCB) || (m >= 0xCD && m <= 0xCF)) return "arithmetic coding (SOF9-15, DAC): Huffman streams only";
         if (m == 0xC8) return "a reserved marker (JPG)";
-        if (m == 0xC0) {
+        if (m == 0xC0 || m == 0xC1) {
             if (sof) return "a second SOF0";
-            bad = jpeg_read_sof(s, n, false, in, comp_id);
+            bad = jpeg_read_sof(s, n, false, in, comp_id, layouts);
             sof = true;
         } else if (m == 0xDB) {
             bad = jpeg_read_dqt(s, n, in);
@@ -330,11 +345,11 @@ inline whenet_jpeg_info_t jpeg_orient_info(const whenet_jpeg_info_t& in, int o) 
 
 // What a whenet_jpeg_info_t must satisfy before anything is computed from it (the parser's own output does; a caller of
 // whenet_jpeg_decode_device may have filled one by hand): a text, or nullptr
-inline const char* jpeg_dec_check_info(const whenet_jpeg_info_t& in) {
+inline const char* jpeg_dec_check_info(const whenet_jpeg_info_t& in, bool layouts = false) {
     if (in.h < 1 || in.w < 1 || in.h > JPEG_MAX_SIDE || in.w > JPEG_MAX_SIDE) return "frame sides must be 1..8192";
     if (in.components != 1 && in.components != 3) return "the frame must have 1 or 3 components";
-    if (in.components == 3 && !((in.hs == 2 && in.vs == 2) || (in.hs == 2 && in.vs == 1) || (in.hs == 1 && in.vs == 1)))
-        return "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
+    if (in.components == 3 && !jpeg_dec_sampling_ok(in.hs, in.vs, layouts))
+        return layouts ? "luma sampling factors other than hs 1, 2 or 4 by vs 1 or 2" : "luma sampling must be 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)";
     if (in.restart_interval < 0 || in.restart_interval > 65535) return "a restart interval outside 0..65535";
     for (int c = 0; c < in.components; ++c) {
         if (in.qt[c] < 0 || in.qt[c] > 3 || in.dc[c] < 0 || in.dc[c] > 1 || in.ac[c] < 0 || in.ac[c] > 1) return "a table id out of range";
@@ -595,6 +610,9 @@ WHENET_HD inline int jpeg_fancy_col(int own_row, int other_row, bool v2) { retur
 WHENET_HD inline int jpeg_fancy_up(int own, int other, bool odd, bool v2) {
     return v2 ? (3 * own + other + (odd ? 7 : 8)) >> 4 : (3 * own + other + (odd ? 2 : 1)) >> 2;
 }
+// 4:4:0 (h1v2_fancy_upsample): a pixel takes 3 x its own chroma row + the vertical neighbour's, the row above for even y (bias 1),
+// the row below for odd y (bias 2); no horizontal filter and no narrow-width switch
+WHENET_HD inline int jpeg_fancy_v(int own_row, int other_row, bool odd) { return (3 * own_row + other_row + (odd ? 2 : 1)) >> 2; }
 // B, G, R of a pixel by jdcolor.c's tables: F(x) = int(x 65536 + 0.5)
 WHENET_HD inline void jpeg_ycc_pixel(int y, int u, int v, int& b, int& g, int& r) {
     const int d = u - 128, e = v - 128;
@@ -720,11 +738,13 @@ inline const char* jpeg_dec_check_dst(const whenet_jpeg_info_t& in, const whenet
 // (rule 1: a packed destination only, jpeg_dec_check_dst; the chroma planes' rows >= ch and columns >= cw are never read)
 inline void jpeg_dec_frame_host(const JpegDecGeom& g, const JpegDecPlanes& pl, const whenet_surface_t& dst, int channel_order,
                                 int rule = JPEG_RULE_OWN) {
-    const int hsh = g.hs - 1, vsh = g.vs - 1;
+    const int hsh = jpeg_dec_shift(g.hs), vsh = jpeg_dec_shift(g.vs);
     if (dst.format == WHENET_SURF_PACKED && rule == JPEG_RULE_LIBJPEG) {
         const int ri = channel_order == WHENET_BGR ? 2 : 0;
         const int ch = (g.h + g.vs - 1) / g.vs, cw = (g.w + g.hs - 1) / g.hs;
-        const bool fancy = g.comps == 3 && g.hs == 2 && cw > 2, v2 = g.vs == 2;
+        // hs = 2: the triangle filter (libjpeg's own switch to replication at cw <= 2); hs = 1, vs = 2 (4:4:0): the vertical filter
+        // alone, at every width; hs = 4 (4:1:1, 4:1:0): replication in both directions (int_upsample)
+        const bool fancy = g.comps == 3 && g.hs == 2 && cw > 2, v2 = g.vs == 2 && g.hs != 4, fancy_v = g.comps == 3 && g.hs == 1 && g.vs == 2;
         for (int y = 0; y < g.h; ++y) {
             uint8_t* o = static_cast<uint8_t*>(dst.plane[0]) + size_t(y) * size_t(dst.pitch[0]);
             const uint8_t* yr = pl.plane[0].data() + size_t(y) * size_t(g.plane_pitch[0]);
@@ -738,7 +758,9 @@ inline void jpeg_dec_frame_host(const JpegDecGeom& g, const JpegDecPlanes& pl, c
                     for (int c = 1; c < 3; ++c) {
                         const uint8_t* row = pl.plane[c].data() + size_t(cr) * size_t(g.plane_pitch[c]);
                         const uint8_t* other = pl.plane[c].data() + size_t(cn) * size_t(g.plane_pitch[c]);
-                        if (fancy) {
+                        if (fancy_v) {
+                            uv[c - 1] = jpeg_fancy_v(row[x], other[x], (y & 1) != 0);
+                        } else if (fancy) {
                             const int i = x >> 1, n = jpeg_dec_clamp(i + ((x & 1) ? 1 : -1), 0, cw - 1);
                             uv[c - 1] = jpeg_fancy_up(jpeg_fancy_col(row[i], other[i], v2), jpeg_fancy_col(row[n], other[n], v2), (x & 1) != 0, v2);
                         } else {

@@ -20,7 +20,7 @@ constexpr int JPEG_MAX_SIDE = 8192;
 constexpr int JPEG_HEADER_BYTES = WHENET_JPEG_HEADER_BYTES;
 constexpr int JPEG_BLOCK_MAX_BITS = 11 + 11 + 63 * (16 + 10);      // DC code + extra bits, 63 x (AC code + extra bits): no EOB then
 constexpr int JPEG_MCU_BLOCKS = 6;                                  // 4:2:0: Y00, Y01, Y10, Y11, Cb, Cr
-constexpr int JPEG_MAX_INTERVAL_BLOCKS = (JPEG_MAX_SIDE / 16) * JPEG_MCU_BLOCKS;      // 3,072: the most blocks of an interval, any sampling
+constexpr int JPEG_MAX_INTERVAL_BLOCKS = (JPEG_MAX_SIDE / 16) * JPEG_MCU_BLOCKS;      // 3,072: the most blocks of an interval of the ENCODER, at any of its three samplings (the decoder does not read it)
 constexpr int JPEG_HUFF_MAX_LEN = 257;                              // no code of 257 symbols is longer before the lengths are limited
 constexpr int JPEG_CODE_MAX_BITS = 26;                              // the longest code word with its extra bits
 

@@ -16,6 +16,14 @@
 //   whenet_jpeg_prog_finish_kernel  8 lanes per block: lane l loads the record's zigzag positions 8 l .. 8 l + 7 as 16 bytes,
 //                                   multiplies by the quantiser, clamps, scatters to natural order in LDS, and stores the natural
 //                                   positions 8 l .. 8 l + 7 as 16 bytes.
+//   whenet_jpeg_seq_scan_kernel     the scans of a SEQUENTIAL frame that goes through the scan plan (the header's JPEG DECODER, LAYOUTS:
+//                                   several scans, scans of two components, Huffman ids 2 / 3): the same item per lane and the same
+//                                   16 lanes, the scan's six tables (DC and AC of up to three components) in LDS.  The scans of such
+//                                   a frame hold different components, so an item owns whole records: a block is decoded in an LDS
+//                                   row and leaves as eight 16-byte stores, as in the baseline entropy kernel.  All scans are level 1:
+//                                   ONE launch per frame.  A kernel of its own, so that the progressive scan kernel keeps its 6,452
+//                                   bytes of LDS and its registers.  whenet_jpeg_seq_clip_scan_kernel: the clip form, one launch for
+//                                   all such frames of a clip.
 //   whenet_jpeg_prog_clip_scan_kernel, whenet_jpeg_prog_clip_finish_kernel
 //                                   the same bodies for a CLIP of up to 16 streams (jpeg_dec_clip_host.h: jpeg_clip_plan_progressive):
 //                                   launch L of the scan kernel covers level L of every progressive frame that has one, the finish
@@ -68,6 +76,31 @@ __device__ __forceinline__ void scan_body(const JpegProgArgs& a, long long group
         atomicMax(&a.meta[0], JPEG_DEC_NO_BAD - (s_sc.first_item + it.interval));
 }
 
+// a sequential frame's scans (jpeg_prog_host.h: jpeg_seq_item); group: as above
+__device__ __forceinline__ void seq_scan_body(const JpegProgArgs& a, long long group) {
+    __shared__ JpegDecHuff s_h[6];
+    __shared__ JpegProgScan s_sc;
+    __shared__ __attribute__((aligned(16))) int16_t s_block[JPEG_PROG_LANES][64 + 8];      // a lane's block in hand (144-byte rows)
+    const int tid = int(threadIdx.x);
+    const long long base = group * JPEG_PROG_LANES;
+    const int s = a.items[base].scan;      // (a scan's share begins with a real item: uniform over the workgroup)
+    if (s < 0) return;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.scans + s);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&s_sc);
+        for (int i = tid; i < int(sizeof(JpegProgScan) / 4); i += SCAN_THREADS) dst[i] = src[i];
+        src = reinterpret_cast<const uint32_t*>(a.huff + 6 * size_t(s));      // (six per scan: unused ones are zeroed tables)
+        dst = reinterpret_cast<uint32_t*>(s_h);
+        for (int i = tid; i < 6 * int(sizeof(JpegDecHuff) / 4); i += SCAN_THREADS) dst[i] = src[i];
+    }
+    __syncthreads();
+    if (tid >= JPEG_PROG_LANES || s_sc.kind != JPEG_PROG_SEQUENTIAL) return;
+    const JpegProgItem it = a.items[base + tid];
+    if (it.scan != s || it.interval < 0 || it.interval >= s_sc.intervals || it.start < 0 || it.end > a.nbytes || it.start > it.end) return;
+    if (!jpeg_seq_item(a.data, it.start, it.end, s_sc, s_h, a.g, it.interval, a.raw, s_block[tid]))
+        atomicMax(&a.meta[0], JPEG_DEC_NO_BAD - (s_sc.first_item + it.interval));
+}
+
 // bx: the workgroup's index among the stream's (32 blocks each)
 __device__ __forceinline__ void finish_body(const JpegProgArgs& a, int bx) {
     __shared__ __attribute__((aligned(16))) int16_t s_rec[FIN_BLOCKS][64 + 8];
@@ -102,6 +135,9 @@ __device__ __forceinline__ void finish_body(const JpegProgArgs& a, int bx) {
 __global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_prog_scan_kernel(JpegProgArgs a, int first_group) {
     scan_body(a, (long long)(first_group) + blockIdx.x);
 }
+__global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_seq_scan_kernel(JpegProgArgs a, int first_group) {
+    seq_scan_body(a, (long long)(first_group) + blockIdx.x);
+}
 __global__ __launch_bounds__(FIN_THREADS) void whenet_jpeg_prog_finish_kernel(JpegProgArgs a) { finish_body(a, int(blockIdx.x)); }
 
 // ---- the clip kernels: the frames' workgroups back to back in one grid (kernels.h, JpegClipGrid).  A workgroup finds its frame, reads
@@ -118,6 +154,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_prog_clip_scan_kerne
     const int f = jpeg_clip_frame_of(grid, b);
     scan_body(jpeg_clip_prog_record(recs, f), (long long)(level.first_group[f]) + (b - grid.first[f]));
 }
+__global__ __launch_bounds__(SCAN_THREADS) void whenet_jpeg_seq_clip_scan_kernel(const void* __restrict__ recs, JpegClipGrid grid,
+                                                                                 JpegProgClipLevel level) {
+    const int b = int(blockIdx.x);
+    if (b >= grid.total) return;
+    const int f = jpeg_clip_frame_of(grid, b);
+    seq_scan_body(jpeg_clip_prog_record(recs, f), (long long)(level.first_group[f]) + (b - grid.first[f]));
+}
 __global__ __launch_bounds__(FIN_THREADS) void whenet_jpeg_prog_clip_finish_kernel(const void* __restrict__ recs, JpegClipGrid grid) {
     const int b = int(blockIdx.x);
     if (b >= grid.total) return;
@@ -131,11 +174,17 @@ static_assert(sizeof(JpegDecArgs) <= JPEG_CLIP_PROG_RECORD_OFFSET && JPEG_CLIP_P
 
 // what a lane may index: every item inside its scan and the data, every scan's units inside the frame's records
 void check_jpeg_prog_plan(const JpegDecGeom& g, const JpegProgPlan& plan) {
-    WHENET_REQUIRE(!plan.baseline && !plan.dev.empty() && plan.huff.size() == 3 * plan.dev.size() && plan.items.size() % JPEG_PROG_LANES == 0 &&
+    WHENET_REQUIRE(!plan.baseline && !plan.dev.empty() && plan.huff.size() == size_t(plan.huff_per_scan()) * plan.dev.size() &&
+                       (!plan.sequential || plan.levels == 1) && plan.items.size() % JPEG_PROG_LANES == 0 &&
                        plan.data_bytes >= 0 && plan.data_bytes <= JPEG_DEC_MAX_BYTES,
                    WHENET_EINVAL, "jpeg_decode_progressive: not the plan of a progressive stream");
     for (const JpegProgScan& sc : plan.dev) {
         const long long frame_units = sc.ns > 1 || g.comps == 1 ? (long long)(g.mcu_cols) * g.mcu_rows : -1;
+        // (a sequential frame's scans are all of that kind, a progressive frame's never; the components a scan names are the frame's)
+        WHENET_REQUIRE((sc.kind == JPEG_PROG_SEQUENTIAL) == plan.sequential && sc.kind >= JPEG_PROG_DC_FIRST && sc.kind <= JPEG_PROG_SEQUENTIAL &&
+                           sc.ns >= 1 && sc.ns <= g.comps && sc.comp[0] >= 0 && sc.comp[0] < g.comps && (sc.ns < 2 || (sc.comp[1] > sc.comp[0] && sc.comp[1] < g.comps)) &&
+                           (sc.ns < 3 || (sc.comp[2] > sc.comp[1] && sc.comp[2] < g.comps)) && (sc.ns == 1 || g.comps == 3),
+                       WHENET_EINVAL, "jpeg_decode_progressive: a scan record outside the frame");
         WHENET_REQUIRE(sc.units >= 1 && sc.ri >= 1 && sc.intervals == (sc.units + sc.ri - 1) / sc.ri && sc.ss >= 0 && sc.ss <= sc.se && sc.se <= 63 &&
                            sc.al >= 0 && sc.al <= 13 && sc.ns >= 1 && sc.ns <= g.comps && sc.bw >= 1 && sc.units == sc.bw * sc.bh &&
                            (frame_units < 0 ? (sc.comp[0] >= 0 && sc.comp[0] < 3 && sc.bw <= g.mcu_cols * (sc.comp[0] == 0 ? g.hs : 1) &&
@@ -197,7 +246,7 @@ void launch_jpeg_decode_progressive(const JpegDecArgs& a, const JpegProgPlan& pl
     WHENET_HIP_CHECK(hipMemsetAsync(s + lay.meta, 0, lay.zero_bytes, stream));      // meta | raw
     const auto launch = [&](int off, int cnt) {
         if (cnt <= 0) return;
-        hipLaunchKernelGGL(whenet_jpeg_prog_scan_kernel, dim3(unsigned(cnt / JPEG_PROG_LANES)), dim3(SCAN_THREADS), 0, stream, p,
+        hipLaunchKernelGGL(plan.sequential ? whenet_jpeg_seq_scan_kernel : whenet_jpeg_prog_scan_kernel, dim3(unsigned(cnt / JPEG_PROG_LANES)), dim3(SCAN_THREADS), 0, stream, p,
                            off / JPEG_PROG_LANES);
         WHENET_HIP_CHECK(hipGetLastError());
         if (scan_launches != nullptr) ++*scan_launches;
@@ -220,6 +269,7 @@ void launch_jpeg_decode_clip_progressive(const JpegDecArgs* h_recs, const JpegPr
                    WHENET_EINVAL, "jpeg_decode_clip: NULL argument, or a frame count outside 1..16");
     uint8_t prog[MIXED_MAX_FRAMES] = {};
     int levels = 0;
+    bool any_sequential = false;
     for (int f = 0; f < frames; ++f) {
         if (!jpeg_clip_is_progressive(plans[f])) continue;
         const JpegProgPlan& plan = *plans[f];
@@ -246,7 +296,8 @@ void launch_jpeg_decode_clip_progressive(const JpegDecArgs* h_recs, const JpegPr
                            reinterpret_cast<uintptr_t>(p.raw) % 16 == 0 && p.coef == h_recs[f].coef && reinterpret_cast<uintptr_t>(p.coef) % 16 == 0 &&
                            p.meta == h_recs[f].meta && p.first_bad == plan.first_bad,
                        WHENET_EINVAL, who + ": the progressive record is not that of the frame's plan and buffers");
-        levels = std::max(levels, plan.levels);
+        if (plan.sequential) any_sequential = true;      // (one level, launched once for all such frames below)
+        else levels = std::max(levels, plan.levels);
     }
     launch_jpeg_decode_clip_entropy(h_recs, d_recs, frames, d_zero, zero_bytes, stream, enqueues, prog);      // checks, the one memset, the baseline frames
     int64_t n = 0;
@@ -255,7 +306,7 @@ void launch_jpeg_decode_clip_progressive(const JpegDecArgs* h_recs, const JpegPr
         JpegProgClipLevel level{};
         const auto count = [&](const JpegDecArgs& a) {
             const int f = int(&a - h_recs);
-            return prog[f] && l < plans[f]->levels ? plans[f]->level_cnt[size_t(l)] / JPEG_PROG_LANES : 0;
+            return prog[f] && !plans[f]->sequential && l < plans[f]->levels ? plans[f]->level_cnt[size_t(l)] / JPEG_PROG_LANES : 0;
         };
         for (int f = 0; f < frames; ++f)
             if (count(h_recs[f]) > 0) level.first_group[f] = plans[f]->level_off[size_t(l)] / JPEG_PROG_LANES;
@@ -264,6 +315,21 @@ void launch_jpeg_decode_clip_progressive(const JpegDecArgs* h_recs, const JpegPr
         WHENET_HIP_CHECK(hipGetLastError());
         ++n;
         if (scan_launches != nullptr) ++*scan_launches;
+    }
+    if (any_sequential) {      // the sequential frames' scans: level 1 of each, together
+        JpegProgClipLevel level{};
+        const auto count = [&](const JpegDecArgs& a) {
+            const int f = int(&a - h_recs);
+            return prog[f] && plans[f]->sequential ? plans[f]->level_cnt[0] / JPEG_PROG_LANES : 0;
+        };
+        for (int f = 0; f < frames; ++f)
+            if (count(h_recs[f]) > 0) level.first_group[f] = plans[f]->level_off[0] / JPEG_PROG_LANES;
+        if (jpeg_clip_grid(h_recs, frames, count, grid)) {
+            hipLaunchKernelGGL(whenet_jpeg_seq_clip_scan_kernel, dim3(unsigned(grid.total)), dim3(SCAN_THREADS), 0, stream, d_recs, grid, level);
+            WHENET_HIP_CHECK(hipGetLastError());
+            ++n;
+            if (scan_launches != nullptr) ++*scan_launches;
+        }
     }
     if (jpeg_clip_grid(h_recs, frames,
                        [&](const JpegDecArgs& a) {

@@ -19,7 +19,8 @@ namespace whenet {
 
 constexpr int JPEG_PROG_MAX_SCANS = WHENET_JPEG_PROG_MAX_SCANS;
 constexpr int JPEG_PROG_LANES = 16;      // items per workgroup of the scan kernel: the item lists are padded to it scan by scan
-enum { JPEG_PROG_DC_FIRST = 0, JPEG_PROG_DC_REFINE = 1, JPEG_PROG_AC_FIRST = 2, JPEG_PROG_AC_REFINE = 3 };
+// (JPEG_PROG_SEQUENTIAL: a scan of a sequential frame that goes through the scan plan -- include/whenet_hip.h, JPEG DECODER, LAYOUTS)
+enum { JPEG_PROG_DC_FIRST = 0, JPEG_PROG_DC_REFINE = 1, JPEG_PROG_AC_FIRST = 2, JPEG_PROG_AC_REFINE = 3, JPEG_PROG_SEQUENTIAL = 4 };
 // the counter block of whenet_jpeg_progressive_coefficients_host
 enum { JPEG_PROG_CNT_SCANS = 0, JPEG_PROG_CNT_ITEMS, JPEG_PROG_CNT_LEVELS, JPEG_PROG_CNT_EOBRUN, JPEG_PROG_CNT_REFINE_ZRL,
        JPEG_PROG_CNT_CORRECTION_BITS, JPEG_PROG_CNT_CORRECTIONS, JPEG_PROG_CNT_WORDS = 8 };
@@ -44,9 +45,12 @@ struct JpegProgItem {
 
 struct JpegProgPlan {
     bool baseline = false;                     // SOF0: one scan, decoded by the baseline decoder
+    bool sequential = false;                   // SOF0 / SOF1 through the scan plan: every scan is of the kind JPEG_PROG_SEQUENTIAL
     std::vector<whenet_jpeg_scan_t> scans;     // the public records
     std::vector<JpegProgScan> dev;
-    std::vector<JpegDecHuff> huff;             // 3 per scan: the table of the scan's i-th component (DC first), [0] for an AC scan
+    std::vector<JpegDecHuff> huff;             // 3 per scan: the table of the scan's i-th component (DC first), [0] for an AC scan;
+                                               // a sequential frame: 6 per scan, the DC tables of its components, then their AC tables
+    int huff_per_scan() const { return sequential ? 6 : 3; }
     int16_t qz[3][64] = {};                    // per component: its quantiser in ZIGZAG order
     std::vector<JpegProgItem> items;           // level by level, inside a level scan by scan, each scan's share padded
     std::vector<int32_t> level_off, level_cnt; // a level's share of `items`
@@ -61,7 +65,13 @@ struct JpegProgPlan {
 // (plan.baseline, one scan record).  For SOF2 `in` holds the frame, the quantisers and the first scan's data_offset and DRI; its
 // Huffman fields stay empty (the tables change between scans: they are the plan's).  The walk and the SOF / DQT / DHT readers are
 // jpeg_dec_host.h's, shared with jpeg_parse.
-inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in, JpegProgPlan& plan) {
+// layouts: jpeg_parse's argument, and the same samplings for a SOF2 frame (the scan geometry below is written in hs, vs and bpm);
+// a DC scan of a SOF2 frame may hold two components; and a sequential frame (SOF0 / SOF1) the baseline parser refuses for its scan
+// structure or its table ids -- any number of scans that hold every component once, Ns 1..3, Huffman ids 0..3 -- gets a scan plan of
+// JPEG_PROG_SEQUENTIAL scans, all of level 1 (plan.sequential).  A sequential frame of ONE interleaved scan and ids 0..1 stays the
+// baseline decoder's (plan.baseline).  sof2 = false: a SOF2 frame is refused with the baseline parser's text.
+inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_info_t& in, JpegProgPlan& plan, bool layouts = false,
+                                   bool sof2 = true) {
     plan = JpegProgPlan();
     std::memset(&in, 0, sizeof(in));
     if (size > JPEG_DEC_MAX_BYTES) return "a stream above 2^31 - 1 bytes";
@@ -82,10 +92,17 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             }
             p += 2 + ((d[p + 2] << 8) | d[p + 3]);
         }
+        if (sof == 0xC2 && !sof2) {
+            const char* bad = jpeg_parse(d, size, in, layouts);
+            return bad != nullptr ? bad : "progressive DCT (SOF2): baseline sequential streams only";
+        }
         if (sof != 0xC2) {
-            const char* bad = jpeg_parse(d, size, in);
-            if (bad != nullptr) return bad;
-            plan.baseline = true;
+            const char* bad = jpeg_parse(d, size, in, layouts);
+            if (bad == nullptr) plan.baseline = true;
+            else if (!(layouts && (sof == 0xC0 || sof == 0xC1))) return bad;
+            else plan.sequential = true, std::memset(&in, 0, sizeof(in));
+        }
+        if (plan.baseline) {
             whenet_jpeg_scan_t s{};
             s.ns = in.components;
             for (int c = 0; c < in.components; ++c) s.comp[c] = c, s.dc[c] = in.dc[c], s.ac[c] = in.ac[c];
@@ -97,6 +114,7 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             return nullptr;
         }
     }
+    const bool seq = plan.sequential;
     uint8_t hc[8][16], hv[8][256];            // the Huffman tables in force, at index 2 id + class
     uint8_t hp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int dht_seen = 0;
@@ -115,16 +133,18 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
         const char* refused = jpeg_next_segment(d, size, scanned, p, m, s, n);
         if (refused != nullptr) return refused;
         if (m == 0xD9) break;      // (behind the first scan: EOI, or the end of the bytes)
-        if (m == 0xC2) {
-            if (sof) return "a second SOF2";
-            refused = jpeg_read_sof(s, n, true, in, comp_id);
+        if (seq && m == 0xC2) return "a second frame header";
+        if (m == 0xC2 || (seq && (m == 0xC0 || m == 0xC1))) {
+            if (sof) return seq ? "a second SOF0" : "a second SOF2";
+            refused = jpeg_read_sof(s, n, !seq, in, comp_id, layouts);
             if (refused == nullptr && in.components == 3 && (comp_id[0] == comp_id[1] || comp_id[0] == comp_id[2] || comp_id[1] == comp_id[2]))
                 return "two components of the frame share an id";
             sof = true;
         } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4) {
+            if (seq) return jpeg_parse(d, size, in, layouts);      // (another frame type, arithmetic coding: the baseline parser's texts)
             return "a second frame header in a progressive stream";
         } else if (m == 0xDB) {
-            if (scanned) return "a quantiser table (DQT) behind the first scan of a progressive stream";
+            if (scanned) return seq ? "a quantiser table (DQT) behind the first scan" : "a quantiser table (DQT) behind the first scan of a progressive stream";
             refused = jpeg_read_dqt(s, n, in);
         } else if (m == 0xC4) {
             refused = jpeg_read_dht(s, n, 3, hc, hv, hp);
@@ -133,11 +153,12 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             if (n != 2) return "a DRI of the wrong length";
             dri = (s[0] << 8) | s[1];
         } else if (m == 0xDA) {
-            if (!sof) return "SOS before SOF2";
+            if (!sof) return seq ? "SOS before SOF0" : "SOS before SOF2";
             if (n < 1) return "a short SOS";
             const int ns = s[0];
-            if (ns == 2) return "a scan of two components: scans hold one component or all of them";
-            if (ns != 1 && ns != in.components) return "a scan must hold one component or all of the frame's";
+            if (ns == 2 && !layouts) return "a scan of two components: scans hold one component or all of them";
+            if (ns != 1 && ns != in.components && !(ns == 2 && in.components == 3))
+                return seq ? "a scan must hold one to three of the frame's components" : "a scan must hold one component or all of the frame's";
             if (n != 4 + 2 * ns) return "the length of SOS does not match its components";
             if (int(plan.dev.size()) >= JPEG_PROG_MAX_SCANS) return "more than 128 scans";
             JpegProgScan sc{};
@@ -147,14 +168,20 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
                 int c = -1;
                 for (int j = 0; j < in.components; ++j)
                     if (s[1 + 2 * i] == comp_id[j]) c = j;
-                if (c < 0 || (ns > 1 && c != i)) return "the scan's components are not the frame's, in order";
+                if (c < 0 || (ns > 1 && (ns == 2 ? (i > 0 && c <= sc.comp[0]) : c != i))) return "the scan's components are not the frame's, in order";
                 sc.comp[i] = c;
                 pub.comp[i] = c, pub.dc[i] = s[2 + 2 * i] >> 4, pub.ac[i] = s[2 + 2 * i] & 15;
                 if (pub.dc[i] > 3 || pub.ac[i] > 3) return "a Huffman table id above 3";
             }
             sc.ss = s[1 + 2 * ns], sc.se = s[2 + 2 * ns], sc.ah = s[3 + 2 * ns] >> 4, sc.al = s[3 + 2 * ns] & 15;
+            if (seq) {
+                if (sc.ss != 0 || sc.se != 63 || sc.ah != 0 || sc.al != 0)
+                    return "a spectral selection or successive approximation in a sequential frame (Ss = 0, Se = 63, Ah = Al = 0 only)";
+                for (int i = 0; i < ns; ++i)
+                    if (cur_al[sc.comp[i]][0] >= 0) return "a component in two scans of a sequential frame";
+            }
             if (sc.ss > sc.se || sc.se > 63) return "a spectral selection with Ss > Se or Se > 63";
-            if (sc.ss == 0 && sc.se != 0) return "a scan of DC and AC coefficients together (Ss = 0 with Se != 0)";
+            if (sc.ss == 0 && sc.se != 0 && !seq) return "a scan of DC and AC coefficients together (Ss = 0 with Se != 0)";
             if (sc.ss > 0 && ns > 1) return "an interleaved AC scan (Ss > 0 with several components)";
             if (sc.ah > 13 || sc.al > 13) return "a successive approximation bit position above 13";
             for (int i = 0; i < ns; ++i) {
@@ -175,9 +202,16 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             for (int c = 0; c < in.components; ++c)
                 if (!in.q_present[in.qt[c]]) return "a missing quantiser table (DQT)";
             sc.kind = sc.ss == 0 ? (sc.ah == 0 ? JPEG_PROG_DC_FIRST : JPEG_PROG_DC_REFINE) : (sc.ah == 0 ? JPEG_PROG_AC_FIRST : JPEG_PROG_AC_REFINE);
-            JpegDecHuff hu[3];
+            if (seq) sc.kind = JPEG_PROG_SEQUENTIAL;
+            JpegDecHuff hu[6];
             std::memset(hu, 0, sizeof(hu));
-            if (sc.kind == JPEG_PROG_DC_FIRST) {
+            if (seq) {
+                for (int i = 0; i < ns; ++i) {
+                    if (!hp[2 * pub.dc[i]] || !hp[2 * pub.ac[i] + 1]) return "a missing Huffman table (DHT)";
+                    jpeg_dec_build_huff(hc[2 * pub.dc[i]], hv[2 * pub.dc[i]], hu[i]);
+                    jpeg_dec_build_huff(hc[2 * pub.ac[i] + 1], hv[2 * pub.ac[i] + 1], hu[3 + i]);
+                }
+            } else if (sc.kind == JPEG_PROG_DC_FIRST) {
                 for (int i = 0; i < ns; ++i) {
                     if (!hp[2 * pub.dc[i]]) return "a missing Huffman table (DHT)";
                     jpeg_dec_build_huff(hc[2 * pub.dc[i]], hv[2 * pub.dc[i]], hu[i]);
@@ -256,10 +290,10 @@ inline const char* jpeg_prog_parse(const uint8_t* d, int64_t size, whenet_jpeg_i
             sc.items = int32_t(plan.items.size()) - sc.list_off;
             for (int i = 0; i < sc.items; ++i) plan.items[size_t(sc.list_off + i)].end = sc.data_end;
             pub.ns = ns, pub.ss = sc.ss, pub.se = sc.se, pub.ah = sc.ah, pub.al = sc.al, pub.tables = dht_seen;
-            pub.ri = sc.ri, pub.intervals = sc.intervals, pub.level = sc.level + 1, pub.first_item = sc.first_item, pub.progressive = 1;
+            pub.ri = sc.ri, pub.intervals = sc.intervals, pub.level = sc.level + 1, pub.first_item = sc.first_item, pub.progressive = seq ? 0 : 1;
             pub.data_offset = from, pub.data_bytes = q - from;
             plan.scans.push_back(pub), plan.dev.push_back(sc);
-            for (const JpegDecHuff& h : hu) plan.huff.push_back(h);
+            for (int i = 0; i < plan.huff_per_scan(); ++i) plan.huff.push_back(hu[i]);
             p = q;
             continue;
         } else if (!((m >= 0xE0 && m <= 0xEF) || m == 0xFE)) {      // (APPn, COM: skipped)
@@ -313,6 +347,15 @@ WHENET_HD inline long long jpeg_prog_record(const JpegDecGeom& g, const JpegProg
     return ((long long)(by) * g.mcu_cols + bx) * g.bpm + (g.bpm - 2) + (sc.comp[0] - 1);
 }
 
+// the blocks scan component i has in a unit of the scan (an interleaved scan: H_c V_c of them, T.81 A.2.3), and block j of them as its
+// index in the frame's MCU (what jpeg_prog_record takes)
+WHENET_HD inline int jpeg_prog_unit_blocks(const JpegDecGeom& g, const JpegProgScan& sc, int i) {
+    return sc.ns > 1 && sc.comp[i] == 0 ? g.bpm - 2 : 1;
+}
+WHENET_HD inline int jpeg_prog_unit_block(const JpegDecGeom& g, const JpegProgScan& sc, int i, int j) {
+    return sc.ns > 1 ? (sc.comp[i] == 0 ? j : g.bpm - 2 + sc.comp[i] - 1) : 0;
+}
+
 // one correction bit for a coefficient that is already non-zero; false: the data ends inside it
 WHENET_HD inline bool jpeg_prog_correct(JpegBitReader& br, int16_t& coef, int p1, long long* cnt) {
     int bit;
@@ -338,28 +381,27 @@ WHENET_HD inline bool jpeg_prog_item(const uint8_t* data, int start, int end, co
     const int p1 = 1 << sc.al;
     if (sc.kind == JPEG_PROG_DC_FIRST) {
         int pred0 = 0, pred1 = 0, pred2 = 0;
-        const int nb = sc.ns > 1 ? g.bpm : 1, ny = g.bpm - 2;
         for (int u = first; u < last; ++u)
-            for (int b = 0; b < nb; ++b) {
-                const int i = sc.ns > 1 && b >= ny ? b - ny + 1 : 0;      // the scan's i-th component
-                int v;
-                const int s = br.decode(huff[i]);
-                if (s < 0 || !br.receive(s & 15, v)) return false;
-                int& pred = i == 0 ? pred0 : (i == 1 ? pred1 : pred2);
-                pred = jpeg_dec_clamp(pred + v, -32768, 32767);
-                raw[jpeg_prog_record(g, sc, u, b) * 64] = jpeg_prog_i16(pred * p1);
-            }
+            for (int i = 0; i < sc.ns; ++i)      // the scan's i-th component
+                for (int j = 0, nb = jpeg_prog_unit_blocks(g, sc, i); j < nb; ++j) {
+                    int v;
+                    const int s = br.decode(huff[i]);
+                    if (s < 0 || !br.receive(s & 15, v)) return false;
+                    int& pred = i == 0 ? pred0 : (i == 1 ? pred1 : pred2);
+                    pred = jpeg_dec_clamp(pred + v, -32768, 32767);
+                    raw[jpeg_prog_record(g, sc, u, jpeg_prog_unit_block(g, sc, i, j)) * 64] = jpeg_prog_i16(pred * p1);
+                }
         return true;
     }
     if (sc.kind == JPEG_PROG_DC_REFINE) {
-        const int nb = sc.ns > 1 ? g.bpm : 1;
         for (int u = first; u < last; ++u)
-            for (int b = 0; b < nb; ++b) {
-                int bit;
-                if (!jpeg_prog_bits(br, 1, bit)) return false;
-                int16_t* const rec = raw + jpeg_prog_record(g, sc, u, b) * 64;
-                if (bit != 0) rec[0] = int16_t(rec[0] | p1);
-            }
+            for (int i = 0; i < sc.ns; ++i)
+                for (int j = 0, nb = jpeg_prog_unit_blocks(g, sc, i); j < nb; ++j) {
+                    int bit;
+                    if (!jpeg_prog_bits(br, 1, bit)) return false;
+                    int16_t* const rec = raw + jpeg_prog_record(g, sc, u, jpeg_prog_unit_block(g, sc, i, j)) * 64;
+                    if (bit != 0) rec[0] = int16_t(rec[0] | p1);
+                }
         return true;
     }
     int eobrun = 0;
@@ -466,6 +508,57 @@ WHENET_HD inline bool jpeg_prog_item(const uint8_t* data, int start, int end, co
     return true;
 }
 
+// ---- a scan of a sequential frame (JPEG_PROG_SEQUENTIAL; host and device) ----
+// One block as the baseline decoder reads it (jpeg_dec_block: DC symbol + EXTEND on the component's predictor, then AC symbols, no EOB
+// runs), but RAW: out[zigzag k] = the value itself (out is zero on entry).  The finish multiplies and clamps, which gives exactly
+// jpeg_dec_block's record.  false: damage; what was written stays.
+WHENET_HD inline bool jpeg_seq_block(JpegBitReader& br, const JpegDecHuff& dc, const JpegDecHuff& ac, int& pred, int16_t* out) {
+    int s = br.decode(dc), v;
+    if (s < 0 || !br.receive(s & 15, v)) return false;
+    pred = jpeg_dec_clamp(pred + v, -32768, 32767);
+    out[0] = int16_t(pred);
+    for (int k = 1; k < 64;) {
+        const int sym = br.decode(ac);
+        if (sym < 0) return false;
+        const int r = sym >> 4;
+        s = sym & 15;
+        if (s == 0) {
+            if (r != 15) break;      // EOB
+            k += 16;                 // ZRL
+            if (k > 64) return false;
+            continue;
+        }
+        k += r;
+        if (k > 63 || !br.receive(s, v)) return false;      // (|v| < 2^15: s <= 15)
+        out[k] = int16_t(v);
+        ++k;
+    }
+    return true;
+}
+
+// One (scan, interval) item of a sequential scan into raw.  huff: the scan's six tables (DC of its i-th component at [i], AC at
+// [3 + i]).  The scans of a sequential frame hold different components, so an item owns its records: a block is decoded in `stage`
+// (64 int16 of fast memory, 16-byte aligned like raw; nullptr: in place) and leaves as a whole record.  false: the interval is
+// damaged; the block in hand keeps what was decoded of it, the blocks behind it stay zero.
+WHENET_HD inline bool jpeg_seq_item(const uint8_t* data, int start, int end, const JpegProgScan& sc, const JpegDecHuff* huff, const JpegDecGeom& g,
+                                    int interval, int16_t* raw, int16_t* stage = nullptr) {
+    JpegBitReader br(data, start, end);
+    const int first = interval * sc.ri;
+    const int last = first + sc.ri < sc.units ? first + sc.ri : sc.units;
+    int pred0 = 0, pred1 = 0, pred2 = 0;
+    for (int u = first; u < last; ++u)
+        for (int i = 0; i < sc.ns; ++i)
+            for (int j = 0, nb = jpeg_prog_unit_blocks(g, sc, i); j < nb; ++j) {
+                int16_t* const rec = raw + jpeg_prog_record(g, sc, u, jpeg_prog_unit_block(g, sc, i, j)) * 64;
+                if (stage != nullptr) std::memset(__builtin_assume_aligned(stage, 16), 0, 128);
+                int& pred = i == 0 ? pred0 : (i == 1 ? pred1 : pred2);
+                const bool ok = jpeg_seq_block(br, huff[i], huff[3 + i], pred, stage != nullptr ? stage : rec);
+                if (stage != nullptr) std::memcpy(__builtin_assume_aligned(rec, 16), __builtin_assume_aligned(stage, 16), 128);
+                if (!ok) return false;
+            }
+    return true;
+}
+
 // the finish of one value: record[natural k] = clamp(raw[zigzag k] x Q[k], -2048, 2047)
 WHENET_HD inline int16_t jpeg_prog_finish_value(int raw, int q) { return int16_t(jpeg_dec_clamp(raw * q, -2048, 2047)); }
 
@@ -484,13 +577,15 @@ inline void jpeg_prog_coefficients_host(const whenet_jpeg_info_t& in, const Jpeg
     const size_t blocks = size_t(g.mcu_cols) * size_t(g.mcu_rows) * size_t(g.bpm);
     out.raw.assign(blocks * 64, 0), out.coef.assign(blocks * 64, 0);
     int bad = plan.first_bad;
-    int16_t stage[64];
+    alignas(16) int16_t stage[64];
     for (const JpegProgScan& sc : plan.dev)
         for (int i = 0; i < sc.items; ++i) {
             const JpegProgItem& it = plan.items[size_t(sc.list_off + i)];
             const size_t s = size_t(&sc - plan.dev.data());
-            if (!jpeg_prog_item(data, it.start, it.end, sc, plan.huff.data() + 3 * s, g, it.interval, out.raw.data(), stage, out.cnt))
-                bad = std::min(bad, sc.first_item + it.interval);
+            const JpegDecHuff* const hu = plan.huff.data() + size_t(plan.huff_per_scan()) * s;
+            const bool ok = sc.kind == JPEG_PROG_SEQUENTIAL ? jpeg_seq_item(data, it.start, it.end, sc, hu, g, it.interval, out.raw.data(), stage)
+                                                            : jpeg_prog_item(data, it.start, it.end, sc, hu, g, it.interval, out.raw.data(), stage, out.cnt);
+            if (!ok) bad = std::min(bad, sc.first_item + it.interval);
         }
     for (size_t b = 0; b < blocks; ++b) {
         const int bi = int(b % size_t(g.bpm)), c = g.comps == 1 || bi < g.bpm - 2 ? 0 : bi - (g.bpm - 2) + 1;

@@ -216,6 +216,22 @@ _PROTOS = {
     "whenet_memcpy_d2h": (C.c_int, [_P, _P, _P, C.c_size_t]),
 }
 EXPORTS = tuple(_PROTOS)
+# the entry points of include/whenet_hip_jpeg_accept.h (JPEG DECODER, LAYOUTS): a header and a table of their own, bound with the rest
+_PROTOS_ACCEPT = {
+    "whenet_jpeg_parse_scans_accept": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(JpegInfoC), C.POINTER(JpegScanC), C.c_int, C.POINTER(C.c_int)]),
+    "whenet_jpeg_decode_accept_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_jpeg_decode_accept_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, C.c_int, C.c_int, _P]),
+    "whenet_jpeg_decode_segmented_accept_host": (C.c_int, [_P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_jpeg_decode_segmented_accept_planes_host": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "whenet_op_jpeg_decode_accept": (C.c_int, [_P, _P, C.c_int64, C.POINTER(SurfaceC), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                               _P, _P]),
+    "whenet_op_jpeg_decode_clip_accept": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(SurfaceC), C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, _P]),
+    "whenet_frame_begin_jpeg_accept": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "whenet_clip_begin_jpeg_accept": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P]),
+    "whenet_jpeg_clip_plan_accept": (C.c_int, [C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+}
+EXPORTS_ACCEPT = tuple(_PROTOS_ACCEPT)
 
 _lib: Optional[C.CDLL] = None
 
@@ -230,7 +246,7 @@ def load() -> C.CDLL:
         raise OSError(f"{path} not found: build it with `python __graft_entry__.py` "
                       "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(os.path.abspath(path))
-    for name, (res, args) in _PROTOS.items():
+    for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_ACCEPT.items()):
         fn = getattr(lib, name)          # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args
@@ -867,6 +883,76 @@ def jpeg_decode_segmented_rule_host(data, surface: SurfaceC, bgr: bool, seg_byte
     return status, stats
 
 
+# ---- the accept bits (include/whenet_hip.h, JPEG DECODER, LAYOUTS): the calls named ..._accept ----
+JPEG_ACCEPT_PROGRESSIVE, JPEG_ACCEPT_LAYOUTS = 1, 2
+
+
+def jpeg_accept_bits(progressive=False, layouts=False) -> int:
+    """The `accept` argument of the ..._accept calls from the two flags."""
+    return (JPEG_ACCEPT_PROGRESSIVE if progressive else 0) | (JPEG_ACCEPT_LAYOUTS if layouts else 0)
+
+
+def jpeg_parse_scans_accept(data, accept: int):
+    """`whenet_jpeg_parse_scans_accept`: `jpeg_parse_scans` with the accept bits (without the PROGRESSIVE bit a SOF2 stream is refused)."""
+    lib = load()
+    a = _stream_array(data)
+    info, scans, n = JpegInfoC(), (JpegScanC * JPEG_PROG_MAX_SCANS)(), C.c_int(0)
+    _host_rc(lib, lib.whenet_jpeg_parse_scans_accept(_ptr(a) if a.size else None, int(a.size), int(accept), C.byref(info), scans,
+                                                     JPEG_PROG_MAX_SCANS, C.byref(n)))
+    return info, [scans[i] for i in range(n.value)]
+
+
+def jpeg_decode_accept_host(data, surface: SurfaceC, bgr: bool, rule: str = "own", accept: int = 0, orient: bool = False):
+    """`whenet_jpeg_decode_accept_host` into a packed host surface (of the ORIENTED size where orient): (the two status words, the
+    orientation applied)."""
+    lib = load()
+    a = _stream_array(data)
+    status, applied = np.zeros(2, np.int32), np.ones(1, np.int32)
+    _host_rc(lib, lib.whenet_jpeg_decode_accept_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB,
+                                                     jpeg_rule_code(rule), int(accept), int(bool(orient)), _ptr(status), _ptr(applied)))
+    return status, int(applied[0])
+
+
+def _plane_args(planes):
+    ptrs = (_P * 3)(*[p.ctypes.data for p in planes] + [None] * (3 - len(planes)))
+    pitch = np.array([int(p.strides[0]) if p.shape[0] > 1 else int(p.shape[1]) for p in planes] + [0] * (3 - len(planes)), np.int32)
+    return ptrs, pitch
+
+
+def jpeg_decode_accept_planes_host(data, planes, rule: str = "own", accept: int = 0) -> np.ndarray:
+    """`whenet_jpeg_decode_accept_planes_host` into uint8 2-D arrays (contiguous rows): the two status words."""
+    lib = load()
+    a = _stream_array(data)
+    status = np.zeros(2, np.int32)
+    ptrs, pitch = _plane_args(planes)
+    _host_rc(lib, lib.whenet_jpeg_decode_accept_planes_host(_ptr(a) if a.size else None, int(a.size), ptrs, _ptr(pitch), jpeg_rule_code(rule),
+                                                            int(accept), _ptr(status)))
+    return status
+
+
+def jpeg_decode_segmented_accept_host(data, surface: SurfaceC, bgr: bool, seg_bytes: int, window: int, rule: str = "own", accept: int = 0):
+    """`whenet_jpeg_decode_segmented_accept_host`: (status, statistics)."""
+    lib = load()
+    a = _stream_array(data)
+    status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+    _host_rc(lib, lib.whenet_jpeg_decode_segmented_accept_host(_ptr(a) if a.size else None, int(a.size), C.byref(surface), BGR if bgr else RGB,
+                                                               int(seg_bytes), int(window), jpeg_rule_code(rule), int(accept), _ptr(status),
+                                                               _ptr(stats)))
+    return status, stats
+
+
+def jpeg_decode_segmented_accept_planes_host(data, planes, seg_bytes: int, window: int, rule: str = "own", accept: int = 0):
+    """`whenet_jpeg_decode_segmented_accept_planes_host`: (status, statistics)."""
+    lib = load()
+    a = _stream_array(data)
+    status, stats = np.zeros(2, np.int32), np.zeros(8, np.int64)
+    ptrs, pitch = _plane_args(planes)
+    _host_rc(lib, lib.whenet_jpeg_decode_segmented_accept_planes_host(_ptr(a) if a.size else None, int(a.size), ptrs, _ptr(pitch),
+                                                                      int(seg_bytes), int(window), jpeg_rule_code(rule), int(accept),
+                                                                      _ptr(status), _ptr(stats)))
+    return status, stats
+
+
 JPEG_CLIP_PLAN_FRAME_WORDS, JPEG_CLIP_PLAN_TOTAL_WORDS = 32, 8
 JPEG_CLIP_REGIONS = ("tables", "data", "start", "meta", "seg_stats", "coef", "plane0", "plane1", "plane2", "first_seg", "seg_exit",
                      "seg_count", "seg_blk")
@@ -918,11 +1004,23 @@ def jpeg_clip_plan_progressive(datas, entropy: int = 2, seg_bytes: int = 128) ->
     regions of JPEG_CLIP_PROG_REGIONS (empty for a baseline frame) and the counts "nscans", "levels" and "list" (the entries of its
     item list); the totals add "progressive" (frames), "scan_launches", "record_stride" and "prog_record_offset".  ValueError that
     names the frame for a stream the scan parser refuses."""
+    return _clip_plan_progressive(datas, entropy, seg_bytes, None)
+
+
+def jpeg_clip_plan_accept(datas, entropy: int = 2, seg_bytes: int = 128, accept: int = 0) -> dict:
+    """`whenet_jpeg_clip_plan_accept` (pure host): `jpeg_clip_plan_progressive` with the accept bits."""
+    return _clip_plan_progressive(datas, entropy, seg_bytes, int(accept))
+
+
+def _clip_plan_progressive(datas, entropy, seg_bytes, accept):
     arrs, ptrs, sizes = _clip_streams(datas)
     n = len(arrs)
     out = np.zeros(max(n, 0) * JPEG_CLIP_PROG_PLAN_FRAME_WORDS + JPEG_CLIP_PROG_PLAN_TOTAL_WORDS, np.int64)
     lib = load()
-    rc = lib.whenet_jpeg_clip_plan_progressive(ptrs, _ptr(sizes) if sizes.size else None, n, int(entropy), int(seg_bytes), _ptr(out))
+    if accept is None:
+        rc = lib.whenet_jpeg_clip_plan_progressive(ptrs, _ptr(sizes) if sizes.size else None, n, int(entropy), int(seg_bytes), _ptr(out))
+    else:
+        rc = lib.whenet_jpeg_clip_plan_accept(ptrs, _ptr(sizes) if sizes.size else None, n, int(entropy), int(seg_bytes), accept, _ptr(out))
     if rc != OK:
         raise ValueError(lib.whenet_last_error(None).decode())
     frames = []
@@ -1776,6 +1874,52 @@ class Handle:
                                                               BGR if bgr else RGB, jpeg_rule_code(rule), int(bool(progressive)),
                                                               int(bool(orient)), C.byref(t), _ptr(status) if status.size else None,
                                                               _ptr(applied)))
+        return t.value, applied[:len(arrs)]
+
+    # ---- the accept bits (JPEG DECODER, LAYOUTS): `accept` None = the handle's options (single streams only) ----
+    def op_jpeg_decode_accept(self, data, surface: SurfaceC, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None, accept=None,
+                              orient=False):
+        """`whenet_op_jpeg_decode_accept`: `op_jpeg_decode_oriented` with the accept bits: (status, statistics, the orientation applied)."""
+        a = _stream_array(data)
+        status, stats, applied = np.zeros(2, np.int32), np.zeros(8, np.int64), np.ones(1, np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_accept(self._h, _ptr(a) if a.size else None, int(a.size), C.byref(surface),
+                                                           BGR if bgr else RGB, int(entropy), int(seg_bytes), jpeg_rule_code(rule),
+                                                           -1 if accept is None else int(accept), jpeg_tristate(orient), _ptr(status),
+                                                           _ptr(stats), _ptr(applied)))
+        return status, stats, int(applied[0])
+
+    def op_jpeg_decode_clip_accept(self, datas, surfaces, bgr: bool, entropy: int = -1, seg_bytes: int = 128, rule=None, accept: int = 0,
+                                   orient: bool = False):
+        """`whenet_op_jpeg_decode_clip_accept`: (the status words int32 [F,2], the orientation applied to each frame int32 [F])."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        surf = (SurfaceC * max(len(surfaces), 1))(*surfaces)
+        status, applied = np.zeros((len(arrs), 2), np.int32), np.ones(max(len(arrs), 1), np.int32)
+        self._check(self._lib.whenet_op_jpeg_decode_clip_accept(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs), surf,
+                                                                BGR if bgr else RGB, _ptr(status) if status.size else None, int(entropy),
+                                                                int(seg_bytes), jpeg_rule_code(rule), int(accept), int(bool(orient)),
+                                                                _ptr(applied)))
+        return status, applied[:len(arrs)]
+
+    def frame_begin_jpeg_accept(self, data, status: np.ndarray, bgr: bool = True, rule=None, accept=None, orient=False):
+        """`whenet_frame_begin_jpeg_accept`: `frame_begin_jpeg_oriented` with the accept bits: (ticket, the orientation applied)."""
+        a = _stream_array(data)
+        if status.dtype != np.int32 or status.size != 2 or not status.flags.c_contiguous:
+            raise ValueError("status must be a contiguous int32 [2] array")
+        t, applied = C.c_int(-1), np.ones(1, np.int32)
+        self._check(self._lib.whenet_frame_begin_jpeg_accept(self._h, _ptr(a) if a.size else None, int(a.size), BGR if bgr else RGB,
+                                                             jpeg_rule_code(rule), -1 if accept is None else int(accept),
+                                                             jpeg_tristate(orient), C.byref(t), _ptr(status), _ptr(applied)))
+        return t.value, int(applied[0])
+
+    def clip_begin_jpeg_accept(self, datas, status: np.ndarray, bgr: bool = True, rule=None, accept: int = 0, orient: bool = False):
+        """`whenet_clip_begin_jpeg_accept`: `clip_begin_jpeg_oriented` with the accept bits: (ticket, the orientations int32 [F])."""
+        arrs, ptrs, sizes = _clip_streams(datas)
+        if status.dtype != np.int32 or status.size != 2 * len(arrs) or not status.flags.c_contiguous:
+            raise ValueError("status must be a contiguous int32 [F,2] array")
+        t, applied = C.c_int(-1), np.ones(max(len(arrs), 1), np.int32)
+        self._check(self._lib.whenet_clip_begin_jpeg_accept(self._h, ptrs, _ptr(sizes) if sizes.size else None, len(arrs),
+                                                            BGR if bgr else RGB, jpeg_rule_code(rule), int(accept), int(bool(orient)),
+                                                            C.byref(t), _ptr(status) if status.size else None, _ptr(applied)))
         return t.value, applied[:len(arrs)]
 
     def jpeg_clip_counters(self) -> dict:

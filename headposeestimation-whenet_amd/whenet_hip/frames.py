@@ -290,7 +290,7 @@ class FramePipeline:
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
 
-    def begin_jpeg(self, data, rule=None, progressive=None, orient=None, default_tables: bool = False) -> "JpegStatus":
+    def begin_jpeg(self, data, rule=None, progressive=None, orient=None, default_tables: bool = False, layouts: bool = False) -> "JpegStatus":
         """`begin()` from the bytes of a baseline JPEG stream (a still, or one frame of an MJPG file: `whenet_hip.mjpeg.MJPGReader`):
         what stands for `cv2.imread` / `cap.read()`.  Only the compressed bytes cross the link; the frame is decoded on the device
         (`whenet_hip.jpeg`, csrc/jpeg_dec.hip) in the pipeline's channel order, and everything that follows is what it is after
@@ -307,11 +307,28 @@ class FramePipeline:
         kernel that writes it, and everything that follows (boxes included) is in the upright picture's coordinates; None (the
         default) follows the handle's option "jpeg_orient" (0: the tag is ignored, the default).  `JpegStatus.orientation` is
         the value applied.  default_tables=True: the stream is completed by `jpeg.add_default_tables` first -- the MJPG frame of a
-        UVC camera or of an AVI whose writer left the DHT segment out, which is refused otherwise."""
+        UVC camera or of an AVI whose writer left the DHT segment out, which is refused otherwise.  layouts=True
+        (`whenet_frame_begin_jpeg_accept`): 4:4:0, 4:1:1 and 4:1:0 streams and single-scan SOF1 streams are accepted too -- the
+        frame is `jpeg.decode_host(data, layouts=True, ...)`; a `progressive` of None counts as False then (the call states its
+        accept bits), `orient` keeps its meaning.  False, the default, is the call as it was and refuses these streams on EVERY handle: the header is
+        parsed here first, without the bit, so the handle's option "jpeg_layouts" (which the plain C calls read) does not reach
+        this method; say layouts=True."""
         self._check_can_begin()
         if default_tables:
             data = _lib.jpeg_add_default_tables(data)
         _lib.jpeg_rule_code(rule)
+        if layouts:
+            accept = _lib.jpeg_accept_bits(bool(progressive), True)
+            info = _lib.jpeg_parse_scans_accept(data, accept)[0]
+            st = JpegStatus()
+            ticket, st._orientation = self._h.frame_begin_jpeg_accept(data, st._status, bgr=self._bgr, rule=rule, accept=accept, orient=orient)
+            if self._jpeg is None:
+                self._jpeg = {}
+            self._jpeg.setdefault(ticket, []).append(st)
+            h, w = (info.w, info.h) if st._orientation >= 5 else (info.h, info.w)
+            self._begun = (ticket, h, w)
+            self._last_sizes = [(h, w)]
+            return st
         info = _lib.jpeg_parse(data) if progressive is False else _lib.jpeg_parse_scans(data)[0]
         st = JpegStatus()
         # (always the call that carries `orient`: False must switch the turn off on a handle whose option is on; and as in
@@ -326,7 +343,8 @@ class FramePipeline:
         self._last_sizes = [(h, w)]
         return st
 
-    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False, orient: bool = False, default_tables: bool = False) -> list:
+    def begin_clip_jpeg(self, datas, rule=None, progressive: bool = False, orient: bool = False, default_tables: bool = False,
+                        layouts: bool = False) -> list:
         """A clip from the bytes of 1..16 baseline JPEG streams (consecutive frames of an MJPG file: `MJPGReader.clips(16)`), each
         with its own size, sampling, tables and DRI: one upload of the compressed bytes, every decoder stage in one launch for all
         frames.  Frame f is what `begin_jpeg(datas[f])` makes; frames of one size make a clip as `begin_clip()` makes it, frames of
@@ -339,7 +357,8 @@ class FramePipeline:
         `JpegStatus.interval` of a progressive frame is its flat (scan, interval) item.  Clips do not read the handle's option
         "jpeg_progressive": only this argument accepts SOF2.  orient=True: every frame by its own EXIF orientation, as
         `begin_jpeg(datas[f], orient=True)`; a clip is one-size by the sizes of the turned frames.  Clips do not read the option
-        "jpeg_orient" either.  default_tables=True: every stream is completed by `jpeg.add_default_tables` first."""
+        "jpeg_orient" either.  default_tables=True: every stream is completed by `jpeg.add_default_tables` first.  layouts=True
+        (`whenet_clip_begin_jpeg_accept`): the streams `begin_jpeg(..., layouts=True)` accepts may be frames of the clip."""
         self._check_can_begin()
         _lib.jpeg_rule_code(rule)
         datas = [_lib.jpeg_add_default_tables(d) for d in datas] if default_tables else list(datas)
@@ -348,12 +367,18 @@ class FramePipeline:
         infos = []
         for i, d in enumerate(datas):
             try:
-                infos.append(_lib.jpeg_parse_scans(d)[0] if progressive else _lib.jpeg_parse(d))
+                if layouts:
+                    infos.append(_lib.jpeg_parse_scans_accept(d, _lib.jpeg_accept_bits(progressive, True))[0])
+                else:
+                    infos.append(_lib.jpeg_parse_scans(d)[0] if progressive else _lib.jpeg_parse(d))
             except ValueError as e:
                 raise ValueError(f"begin_clip_jpeg: frame {i}: {e}") from None
         block = np.zeros((len(datas), 2), np.int32)      # (one array for the library to write; every JpegStatus is a row of it)
         applied = np.ones(len(datas), np.int32)
-        if orient:
+        if layouts:
+            ticket, applied = self._h.clip_begin_jpeg_accept(datas, block, bgr=self._bgr, rule=rule,
+                                                             accept=_lib.jpeg_accept_bits(progressive, True), orient=bool(orient))
+        elif orient:
             ticket, applied = self._h.clip_begin_jpeg_oriented(datas, block, bgr=self._bgr, rule=rule, progressive=progressive, orient=True)
         else:
             ticket = self._h.clip_begin_jpeg(datas, block, bgr=self._bgr, rule=rule, progressive=progressive)

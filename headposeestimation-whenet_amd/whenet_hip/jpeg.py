@@ -131,17 +131,34 @@ def _completed(data, default_tables: bool):
     return _lib.jpeg_add_default_tables(data) if default_tables else data
 
 
-def info(data, progressive: bool = False, default_tables: bool = False) -> dict:
+def _parse(data, progressive, layouts):
+    """the header of a stream by the parser the flags select (layouts: the ..._accept call)"""
+    if layouts:
+        return _lib.jpeg_parse_scans_accept(data, _lib.jpeg_accept_bits(progressive, True))[0]
+    return _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
+
+
+def _auto_form(data, i, entropy, seg_bytes, decide: bool):
+    """(entropy argument, seg_bytes argument) of the op calls; decide: "auto" is resolved here by the library's rule"""
+    form, seg = _lib.JPEG_ENTROPY[entropy], 128 if seg_bytes is None else int(seg_bytes)
+    if form == 2 and decide:
+        form = 1 if (int(_lib._stream_array(data).size) - i.data_offset) // max(i.intervals, 1) >= _lib.JPEG_SEG_AUTO_BYTES else 0
+    return (-1 if form == 2 else form), seg
+
+
+def info(data, progressive: bool = False, default_tables: bool = False, layouts: bool = False) -> dict:
     """The header SOI..SOS of a stream (`whenet_jpeg_parse`): h, w, components, sampling (hs, vs), restart_interval, intervals,
     data_offset, the quantisers uint8 [4,64] in natural order and the table ids.  ValueError with the reason for anything but a
     baseline stream the decoder accepts (progressive, arithmetic, 12 bit, 4 components, several scans, ...).
     progressive=True (`whenet_jpeg_parse_scans`): a progressive (SOF2) stream is accepted too, and "scans" lists every scan as a
     dict: components, ss, se, ah, al, dc_ids, ac_ids, tables, ri, intervals, level, first_item, data_offset, data_bytes.
-    default_tables=True: the header of `add_default_tables(data)` (offsets are that stream's)."""
+    default_tables=True: the header of `add_default_tables(data)` (offsets are that stream's).
+    layouts=True (`whenet_jpeg_parse_scans_accept`): the samplings 4:4:0 (1, 2), 4:1:1 (4, 1) and 4:1:0 (4, 2) and a single-scan SOF1
+    stream are accepted too; "scans" is listed as with progressive=True (a sequential stream: its one scan)."""
     data = _completed(data, default_tables)
     scans = None
-    if progressive:
-        i, recs = _lib.jpeg_parse_scans(data)
+    if progressive or layouts:
+        i, recs = _lib.jpeg_parse_scans_accept(data, _lib.jpeg_accept_bits(progressive, True)) if layouts else _lib.jpeg_parse_scans(data)
         scans = [{"components": tuple(r.comp[:r.ns]), "ss": r.ss, "se": r.se, "ah": r.ah, "al": r.al, "dc_ids": tuple(r.dc[:r.ns]),
                   "ac_ids": tuple(r.ac[:r.ns]), "tables": r.tables, "ri": r.ri, "intervals": r.intervals, "level": r.level,
                   "first_item": r.first_item, "data_offset": r.data_offset, "data_bytes": r.data_bytes} for r in recs]
@@ -189,7 +206,7 @@ def _run_decode(handle, data, frame, bgr, entropy, seg_bytes, rule, progressive,
 
 
 def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: str = "auto", seg_bytes=None, stats: bool = False,
-           rule: str = "own", progressive: bool = False, orient: bool = False, default_tables: bool = False):
+           rule: str = "own", progressive: bool = False, orient: bool = False, default_tables: bool = False, layouts: bool = False):
     """uint8 [H,W,3] (B, G, R order unless bgr=False): the frame of a baseline JPEG stream, decoded by the kernels
     (`whenet_op_jpeg_decode`).  `handle`: a `WHENet` model or a `_lib.Handle`; None opens a postproc handle on device 0 for the call.
     Damaged data raises `DecodeError` (strict=False: returns the defined frame).  `entropy`: the form of the entropy stage --
@@ -206,11 +223,29 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
     itself, as `cv2.imread` applies it: the frame is `decode_host(data, orient=True, ...)`, its sides swapped for the values 5..8.
     orient=False is an upright decode on every handle: every path here goes through that call with `orient` stated, so the handle's
     option "jpeg_orient" (which the plain C calls read) never turns a frame this function sized upright.
-    default_tables=True: `add_default_tables(data)` is decoded in its place (an MJPG frame without DHT; refused otherwise)."""
+    default_tables=True: `add_default_tables(data)` is decoded in its place (an MJPG frame without DHT; refused otherwise).
+    layouts=True (`whenet_op_jpeg_decode_accept`): 4:4:0, 4:1:1 and 4:1:0 streams and single-scan SOF1 streams are accepted too
+    (include/whenet_hip.h, JPEG DECODER, LAYOUTS); the frame is `decode_host(data, layouts=True, ...)` in either entropy form.
+    With False, the default, the call is what it was and refuses them on every handle: the header is parsed here first, without the
+    bit, so the handle's option "jpeg_layouts" (which the plain C calls read) does not reach this function."""
     data = _completed(data, default_tables)
     if entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be 'auto', 'interval' or 'segmented'")
     _lib.jpeg_rule_code(rule)
+    if layouts:
+        i = _parse(data, progressive, True)
+        frame = np.empty((oriented_shape(i.h, i.w, orientation(data)) if orient else (i.h, i.w)) + (3,), np.uint8)
+        form, seg = _auto_form(data, i, entropy, seg_bytes, stats or seg_bytes is not None)
+        accept = _lib.jpeg_accept_bits(progressive, True)
+        def run(h):
+            return h.op_jpeg_decode_accept(data, packed_surface(frame), bgr, form, seg, rule, accept, bool(orient))[:2]
+        if handle is None:
+            with _lib.Handle.postproc(0) as own:
+                status, st = run(own)
+        else:
+            status, st = run(_handle_of(handle))
+        out = _result(frame, status, strict)
+        return (out, st) if stats else out
     if orient:
         i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
         frame = np.empty(oriented_shape(i.h, i.w, orientation(data)) + (3,), np.uint8)
@@ -240,7 +275,7 @@ def decode(data, handle=None, bgr: bool = True, strict: bool = True, entropy: st
 
 
 def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=None, strict: bool = True, rule: str = "own",
-                progressive: bool = False, orient: bool = False, default_tables: bool = False):
+                progressive: bool = False, orient: bool = False, default_tables: bool = False, layouts: bool = False):
     """(frames, statuses) of 1..16 baseline JPEG streams decoded as ONE clip by the kernels (`whenet_op_jpeg_decode_clip`): a list of
     uint8 [H_f,W_f,3] frames and the status words int32 [F,2].  Frame f is `decode(datas[f])`, bit for bit.  `entropy`: None or
     "auto" (the handle's options, stream by stream), "interval" or "segmented" (`seg_bytes`: None = 128).  A stream the decoder does
@@ -252,7 +287,9 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     the baseline frames.  The handle's option "jpeg_progressive" is not read by clips: only this argument accepts SOF2.
     orient=True (`whenet_op_jpeg_decode_clip_oriented`): every frame by its own EXIF orientation -- frame f is
     `decode_host(datas[f], orient=True, ...)` --, upright and turned frames in one clip, at most one launch more than without.
-    default_tables=True: every stream is completed by `add_default_tables` first."""
+    default_tables=True: every stream is completed by `add_default_tables` first.
+    layouts=True (`whenet_op_jpeg_decode_clip_accept`): the streams `decode(..., layouts=True)` accepts may be frames of the clip;
+    frame f is `decode_host(datas[f], layouts=True, ...)`.  Clips do not read the handle's option "jpeg_layouts"."""
     _lib.jpeg_rule_code(rule)
     if entropy is not None and entropy not in _lib.JPEG_ENTROPY:
         raise ValueError("entropy must be None, 'auto', 'interval' or 'segmented'")
@@ -262,7 +299,7 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     frames = []
     for f, d in enumerate(datas):
         try:
-            i = _lib.jpeg_parse_scans(d)[0] if progressive else _lib.jpeg_parse(d)
+            i = _parse(d, progressive, layouts)
         except ValueError as e:
             raise ValueError(f"decode_clip: frame {f}: {e}") from None
         frames.append(np.empty((oriented_shape(i.h, i.w, orientation(d)) if orient else (i.h, i.w)) + (3,), np.uint8))
@@ -270,6 +307,8 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
     seg = 128 if seg_bytes is None else int(seg_bytes)
     surfaces = [packed_surface(fr) for fr in frames]
     def run(h):
+        if layouts:
+            return h.op_jpeg_decode_clip_accept(datas, surfaces, bgr, form, seg, rule, _lib.jpeg_accept_bits(progressive, True), bool(orient))[0]
         if orient:
             return h.op_jpeg_decode_clip_oriented(datas, surfaces, bgr, form, seg, rule, bool(progressive), True)[0]
         if progressive:
@@ -294,14 +333,20 @@ def decode_clip(datas, bgr: bool = True, entropy=None, seg_bytes=None, handle=No
 
 
 def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", progressive: bool = False, orient: bool = False,
-                default_tables: bool = False) -> np.ndarray:
+                default_tables: bool = False, layouts: bool = False) -> np.ndarray:
     """The same frame by pure host arithmetic inside the library (`whenet_jpeg_decode_host`, no GPU): the statement the kernels are
     held to.  `rule`: "own" or "libjpeg", as `decode` (`whenet_jpeg_decode_rule_host`).  progressive=True: a progressive (SOF2)
     stream is accepted too (`whenet_jpeg_decode_progressive_host`).  orient=True (`whenet_jpeg_decode_oriented_host`): the EXIF
     orientation applied to that frame -- with u the upright frame and t = u.transpose(1, 0, 2): 1 u, 2 u[:, ::-1], 3 u[::-1, ::-1],
-    4 u[::-1], 5 t, 6 t[:, ::-1], 7 t[::-1, ::-1], 8 t[::-1].  default_tables=True: `add_default_tables(data)` is decoded in its place."""
+    4 u[::-1], 5 t, 6 t[:, ::-1], 7 t[::-1, ::-1], 8 t[::-1].  default_tables=True: `add_default_tables(data)` is decoded in its place.
+    layouts=True (`whenet_jpeg_decode_accept_host`): 4:4:0, 4:1:1, 4:1:0 and single-scan SOF1 streams are accepted too."""
     data = _completed(data, default_tables)
     _lib.jpeg_rule_code(rule)
+    if layouts:
+        i = _parse(data, progressive, True)
+        frame = np.empty((oriented_shape(i.h, i.w, orientation(data)) if orient else (i.h, i.w)) + (3,), np.uint8)
+        status = _lib.jpeg_decode_accept_host(data, packed_surface(frame), bgr, rule, _lib.jpeg_accept_bits(progressive, True), orient)[0]
+        return _result(frame, status, strict)
     if orient:
         i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
         frame = np.empty(oriented_shape(i.h, i.w, orientation(data)) + (3,), np.uint8)
@@ -318,14 +363,17 @@ def decode_host(data, bgr: bool = True, strict: bool = True, rule: str = "own", 
 
 
 def decode_segmented_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SEG_WINDOW, bgr: bool = True, strict: bool = True,
-                          stats: bool = False, rule: str = "own"):
+                          stats: bool = False, rule: str = "own", layouts: bool = False):
     """`decode_host` with the entropy stage run as the host emulation of the segmented form (`whenet_jpeg_decode_segmented_host`):
     segments of `seg_bytes`, sync windows of `window` segments, lanes in a plain loop.  The same frame, bit for bit.
-    stats=True: (frame, status int32 [2], statistics int64 [8]) and damaged data does not raise.  `rule`: as `decode_host`."""
+    stats=True: (frame, status int32 [2], statistics int64 [8]) and damaged data does not raise.  `rule`: as `decode_host`.
+    layouts=True (`whenet_jpeg_decode_segmented_accept_host`): as `decode_host`."""
     _lib.jpeg_rule_code(rule)
-    i = _lib.jpeg_parse(data)
+    i = _parse(data, False, layouts)
     frame = np.empty((i.h, i.w, 3), np.uint8)
-    if rule != "own":
+    if layouts:
+        status, st = _lib.jpeg_decode_segmented_accept_host(data, packed_surface(frame), bgr, seg_bytes, window, rule, _lib.JPEG_ACCEPT_LAYOUTS)
+    elif rule != "own":
         status, st = _lib.jpeg_decode_segmented_rule_host(data, packed_surface(frame), bgr, seg_bytes, window, rule)
     else:
         status, st = _lib.jpeg_decode_segmented_host(data, packed_surface(frame), bgr, seg_bytes, window)
@@ -334,22 +382,31 @@ def decode_segmented_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SE
     return _result(frame, status, strict)
 
 
-def decode_segmented_planes_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SEG_WINDOW):
-    """`decode_planes_host` by the segmented form's host emulation: (planes, status int32 [2], statistics int64 [8])."""
-    i = _lib.jpeg_parse(data)
+def decode_segmented_planes_host(data, seg_bytes: int = 128, window: int = _lib.JPEG_SEG_WINDOW, layouts: bool = False):
+    """`decode_planes_host` by the segmented form's host emulation: (planes, status int32 [2], statistics int64 [8]).  layouts=True
+    (`whenet_jpeg_decode_segmented_accept_planes_host`): as `decode_host`."""
+    i = _parse(data, False, layouts)
     shapes = [(i.h, i.w)] + [((i.h + i.vs - 1) // i.vs, (i.w + i.hs - 1) // i.hs)] * (i.components - 1)
     planes = [np.empty(s, np.uint8) for s in shapes]
+    if layouts:
+        status, st = _lib.jpeg_decode_segmented_accept_planes_host(data, planes, seg_bytes, window, "own", _lib.JPEG_ACCEPT_LAYOUTS)
+        return planes, status, st
     status, st = _lib.jpeg_decode_segmented_planes_host(data, planes, seg_bytes, window)
     return planes, status, st
 
 
-def decode_planes_host(data, progressive: bool = False, rule: str = "own", default_tables: bool = False):
+def decode_planes_host(data, progressive: bool = False, rule: str = "own", default_tables: bool = False, layouts: bool = False):
     """(the component planes [Y] or [Y, Cb, Cr] as uint8 arrays -- luma h x w, chroma ceil(h / vs) x ceil(w / hs) -- and the status
     int32 [2]) by the host statement: what the tests compare.  progressive=True: a progressive stream is accepted too, and `rule`
     chooses the inverse DCT (`whenet_jpeg_decode_progressive_planes_host`).  default_tables=True: `add_default_tables(data)` is
-    decoded in its place."""
+    decoded in its place.  layouts=True (`whenet_jpeg_decode_accept_planes_host`): as `decode_host`; `rule` applies either way."""
     data = _completed(data, default_tables)
     _lib.jpeg_rule_code(rule)
+    if layouts:
+        i = _parse(data, progressive, True)
+        shapes = [(i.h, i.w)] + [((i.h + i.vs - 1) // i.vs, (i.w + i.hs - 1) // i.hs)] * (i.components - 1)
+        planes = [np.empty(s, np.uint8) for s in shapes]
+        return planes, _lib.jpeg_decode_accept_planes_host(data, planes, rule, _lib.jpeg_accept_bits(progressive, True))
     i = _lib.jpeg_parse_scans(data)[0] if progressive else _lib.jpeg_parse(data)
     if rule != "own" and not progressive:
         raise ValueError("decode_planes_host: the planes of rule 'libjpeg' come from the progressive=True call (which takes baseline streams too)")

@@ -112,10 +112,15 @@ class MJPGReader:
 
     `MJPGReader(path, default_tables=True)`: UVC cameras and many AVI writers leave the DHT segment out of every frame (the tables
     are T.81's Annex K ones); indexing, iteration and `clips()` then return every frame completed by
-    `whenet_hip.jpeg.add_default_tables`.  The default returns the chunks' bytes as they are."""
+    `whenet_hip.jpeg.add_default_tables`.  The default returns the chunks' bytes as they are.
 
-    def __init__(self, path, default_tables: bool = False):
+    `MJPGReader(path, layouts=True)`: the file's frames may be 4:1:1 / 4:1:0 / 4:4:0 streams (DV-derived cameras, grabbers, old
+    webcams).  The bytes are returned as they are; `layouts` is what `info(i)` passes to `whenet_hip.jpeg.info` and what a caller
+    passes on to `jpeg.decode` / `FramePipeline.begin_jpeg` / `begin_clip_jpeg` (`reader.layouts`)."""
+
+    def __init__(self, path, default_tables: bool = False, layouts: bool = False):
         self._default_tables = bool(default_tables)
+        self.layouts = bool(layouts)
         self._f = open(path, "rb")
         try:
             self._f.seek(0, 2)
@@ -208,6 +213,11 @@ class MJPGReader:
             from . import _lib
             data = _lib.jpeg_add_default_tables(data)
         return data
+
+    def info(self, i: int) -> dict:
+        """`whenet_hip.jpeg.info` of frame i, with the reader's `layouts`."""
+        from . import jpeg
+        return jpeg.info(self[i], layouts=self.layouts)
 
     def __iter__(self):
         for i in range(len(self._frames)):

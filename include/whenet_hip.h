@@ -903,8 +903,8 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  * ACCEPTED.  Baseline sequential DCT (SOF0), 8 bit, one interleaved scan, Huffman coding.  Three components are Y, Cb, Cr (JFIF) with
  * luma sampling 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4) and chroma sampling 1x1; one component is grey.  8-bit DQT with ids 0..3 and
  * DHT with ids 0..1 per class, several tables per segment allowed; any DRI or none; APPn and COM are skipped; sides 1..8192; streams
- * below 2^31 bytes.  Everything else -- SOF1, SOF2 and later frame types, arithmetic coding, 12 bit, 4 components, a scan that does
- * not hold every component, 16-bit DQT, other sampling factors, a missing table, a header that ends early -- is WHENET_EFORMAT from
+ * below 2^31 bytes.  (SOF1, several scans and three more samplings: LAYOUTS below, opt-in.)  Everything else -- SOF1, SOF2 and later frame types, arithmetic coding, 12 bit, 4 components, a scan that does
+ * not hold every component, 16-bit DQT, other sampling factors (LAYOUTS below: opt-in), a missing table, a header that ends early -- is WHENET_EFORMAT from
  * the host parser with the reason in whenet_last_error (NULL handle for the pure-host calls), before anything is enqueued.
  * PARSE.  SOI .. SOS into a whenet_jpeg_info_t: size, components, the luma sampling factors hs, vs (1 or 2), per component the
  * quantiser id qt and the Huffman ids dc, ac; restart_interval Ri in MCUs (0: none); intervals = ceil(MCUs / Ri), 1 without DRI;
@@ -1083,7 +1083,7 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  * APPn and COM; a DQT behind the first SOS is refused.  A scan holds all components (interleaved: the frame's MCUs) or ONE; a scan
  * of one component of a 3-component frame has single blocks as its MCUs and covers ceil(cw / 8) x ceil(ch / 8) blocks of that
  * component in raster order, cw = ceil(w hs_c / hs_max) -- NOT the plane padded to whole frame MCUs; blocks of the padded plane
- * outside that grid receive DC only.  Refused with the reason (WHENET_EFORMAT, on the host, before anything is enqueued): Ns = 2;
+ * outside that grid receive DC only.  Refused with the reason (WHENET_EFORMAT, on the host, before anything is enqueued): Ns = 2 (LAYOUTS below: opt-in);
  * Ss > Se or Se > 63; Ss = 0 with Se != 0; Ss > 0 with Ns > 1; Ah or Al > 13; a first scan (Ah = 0) of a coefficient that already
  * had one; a refinement of a coefficient without a first scan, or with Ah != the coefficient's current Al or Al != Ah - 1; an AC
  * scan of a component whose DC has had no scan; more than WHENET_JPEG_PROG_MAX_SCANS scans; a missing table.
@@ -1145,8 +1145,7 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  *                  equal whenet_jpeg_clip_plan's.  entropy 0, 1 or 2 (auto), as there.
  * whenet_jpeg_clip_counters counts these clips as the others; whenet_jpeg_progressive_counters adds a decode per SOF2 frame, the
  * scan launches once per clip and the scans of all its frames.
- * Not built: a segmented (many lanes per interval) form for progressive scans -- a scan without DRI is ONE lane --, SOF0 / SOF1
- * streams of several scans, scans of two components, arithmetic, 12-bit and CMYK streams, block smoothing, a progressive
+ * Not built: a segmented (many lanes per interval) form for progressive scans -- a scan without DRI is ONE lane --, arithmetic, 12-bit and CMYK streams, block smoothing, a progressive
  * encoder, streams already in device memory.
  *
  * JPEG DECODER, ORIENTATION (six entry points, ABI still 6; the parser is csrc/jpeg_dec_host.h's jpeg_exif_orientation, the kernels
@@ -1194,7 +1193,81 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
  *                  byte for byte, and so does a header that cannot be followed to an SOS (no SOI, a truncated or malformed
  *                  segment): this call never refuses a stream, the decoder then gives its own reason.  Ids 2 and 3 are never
  *                  filled.  WHENET_EINVAL only for a NULL argument or capacity < size + 420.
- * Not built: default tables for ids 2 / 3, default quantiser tables (no player installs any). */
+ * Not built: default tables for ids 2 / 3, default quantiser tables (no player installs any).
+ *
+ * JPEG DECODER, LAYOUTS (ten entry points, declared in the companion header include/whenet_hip_jpeg_accept.h, which includes
+ * this one; this header keeps its 131; ABI still 6; the parsers of csrc/jpeg_dec_host.h and csrc/jpeg_prog_host.h
+ * with their `layouts` argument, frame_group of csrc/jpeg_dec.hip, the sequential scan kernel of csrc/jpeg_prog.hip).  Three kinds of
+ * ordinary 8-bit Huffman JPEG that cv2.imread opens without a word are refused by every call above: the chroma samplings 4:4:0 (luma
+ * 1x2: what a lossless quarter turn makes of a 4:2:2 camera file), 4:1:1 (luma 4x1: DV-derived cameras and grabbers) and 4:1:0 (luma
+ * 4x2: old webcams); sequential frames of several scans and scans of two components (jpegtran -scans, several camera firmwares);
+ * SOF1, which libjpeg writes as soon as a frame uses a Huffman table id above 1.  Decoding them is OPT-IN: every call above keeps
+ * refusing them with the text it has; the calls named ..._accept take one set of bits `accept` -- WHENET_JPEG_ACCEPT_PROGRESSIVE (1:
+ * what `progressive` = 1 is above) and WHENET_JPEG_ACCEPT_LAYOUTS (2) --, and whenet_frame_begin_jpeg[_rule|_progressive|_oriented] /
+ * whenet_op_jpeg_decode[_ex|_rule|_progressive|_oriented] with their defaults and whenet_jpeg_decode_device on a handle whose option
+ * "jpeg_layouts" is 1 (default 0) accept them too; clips take the argument only.  The `progressive` arguments above keep their 0 / 1
+ * range.  A stream every call accepts is the same bytes with the bit.
+ * ACCEPTED with the LAYOUTS bit, besides everything accepted without it.
+ *   Samplings: luma (hs, vs) in {1, 2, 4} x {1, 2} with chroma 1x1, in SOF0, SOF1 and (with the PROGRESSIVE bit) SOF2 frames: bpm =
+ *   hs vs + 2 blocks per MCU, up to 10 (T.81's limit); info.hs / info.vs simply take the new values.
+ *   Sequential frames (SOF0 / SOF1, 8 bit): any number of scans in which every component occurs exactly once, each with Ns 1..3 (its
+ *   components in the frame's order), Ss = 0, Se = 63, Ah = Al = 0 and Huffman ids 0..3; DHT, DRI, APPn and COM between scans (a scan
+ *   uses the tables and the DRI in force at its SOS).  A scan of one component of a 3-component frame covers that component's own
+ *   ceil(cw / 8) x ceil(ch / 8) blocks in raster order (the PROGRESSIVE section's rule; cw = ceil(w / hs) for chroma); a scan of two
+ *   or three components is interleaved over the FRAME's MCU grid, its MCU the H_c V_c blocks of each of its components in scan order
+ *   (T.81 A.2.3).
+ *   SOF2: a DC scan (first or refinement) of two components, interleaved the same way.
+ * REFUSED with the bit, on the host, before anything is written -- with a reason that names the factors: a chroma factor other than
+ * 1x1 ("chroma sampling factors other than 1x1 ..."), Cb and Cr that differ, vs = 4, any other luma pair; with the reasons they have
+ * above: 16-bit DQT, 12 bit, arithmetic coding, 4 components, lossless and hierarchical frames; with new reasons: "a component in two
+ * scans of a sequential frame", "a spectral selection or successive approximation in a sequential frame (...)", a DQT behind the
+ * first scan.
+ * ROUTING.  A sequential frame of ONE interleaved scan with Huffman ids 0..1 -- SOF0, or SOF1 that happens to qualify -- is the
+ * baseline decoder's: both entropy forms, the auto rule, clips and whenet_jpeg_decode_device, on the general geometry.  Every other
+ * sequential frame goes through the SCAN PLAN of the PROGRESSIVE section as a fifth scan kind, "sequential": an item is one (scan,
+ * interval); per block the baseline block decode (DC symbol + EXTEND on the component's predictor, 0 at every interval start, then AC
+ * symbols, no EOB runs) writes RAW values in zigzag order into records the memset zeroed; FINISH, inverse DCT and frame follow
+ * unchanged and give exactly the baseline decoder's records.  The scans of one frame hold different components, so all are level 1:
+ * ONE launch of the sequential scan kernel per frame, and ONE for all such frames of a clip (next to the launches per level of the
+ * clip's SOF2 frames).  The plan carries six tables per sequential scan (the DC tables of its components, then their AC tables).
+ * DAMAGE and the status pair follow the PROGRESSIVE section's ITEM rule (items numbered scan by scan, one per restart interval); a
+ * component without a scan at EOI or at the end of the bytes is the incomplete-progression status (status[1] = the item count) and
+ * its plane is decoded from zero coefficients.  Stated, not fixed: a multi-scan stream without DRI is one lane per scan.
+ * GEOMETRY.  An MCU is 8 hs x 8 vs luma samples: its luma blocks in vs rows of hs, then Cb, then Cr, as above.  Both entropy forms,
+ * the sync state of the segmented form (the block's index in its MCU, 0..9, in 8 bits), the component of a block in the count and
+ * write kernels, the clip plans and the scan plan are written in hs, vs and bpm and take the new values as they are: the output does
+ * not depend on the form, seg_bytes or "jpeg_seg_lanes".  Every work buffer, clip-plan word and segment bound is computed from the
+ * stream's own counts -- records: MCUs x bpm x 128 bytes; segments: ceil(nbytes / seg_bytes) + intervals --, never from a
+ * per-sampling constant: a full-width MCU row is 1024 x 4 = 4096 blocks at 4:4:0, 256 x 6 = 1536 at 4:1:1 and 256 x 10 = 2560 at
+ * 4:1:0, against (8192 / 16) x 6 = 3072 at 4:2:0 and 1024 x 3 = 3072 at 4:4:4.  (JPEG_MAX_INTERVAL_BLOCKS = 3072 of csrc/jpeg_host.h
+ * bounds the ENCODER's three samplings -- its per-interval bit budget -- and is not read by the decoder.)
+ * FRAME, RULE 0.  Pixel (x, y) takes the chroma sample (x >> log2 hs, y >> log2 vs); for hs = 4 a lane's four pixels share one
+ * sample, loaded as one byte (aligned wherever it lies, inside the padded plane: x / 4 < 8 mcu_cols).
+ * FRAME, RULE 1 (libjpeg-turbo's jdsample.c as Pillow 12.2.0 / libjpeg-turbo 3.1.4.1 executes it; tests/test_jpeg_layouts_cpu.py
+ * holds every stream of its table to the executed library, on noisy pictures).  4:4:0 is h1v2_fancy_upsample: with r = y >> 1 and the
+ * neighbour rows clamped to 0 .. ch - 1, an even row is (3 in[r] + in[r - 1] + 1) >> 2 and an odd row (3 in[r] + in[r + 1] + 2) >> 2;
+ * nothing is filtered along x and there is NO narrow-width switch (w = 2 is filtered, unlike 4:2:0 / 4:2:2).  4:1:1 and 4:1:0 are
+ * plain replication, in[y >> log2 vs][x >> 2] (int_upsample: no filter in either direction).  jdcolor's row and the SCOPE paragraph
+ * apply as written.  The oriented frame kernels compute their pixels through the same function and inherit both rules.  I420 / NV12
+ * destinations stay 4:2:0-only (WHENET_EINVAL otherwise) and stay refused under rule 1.
+ *   whenet_jpeg_parse_scans_accept      whenet_jpeg_parse_scans with the bits: a sequential frame of several scans lists them (level
+ *                  1 each, progressive = 0); without the PROGRESSIVE bit a SOF2 stream is refused with the baseline parser's text
+ *   whenet_jpeg_decode_accept_host      the host statement: rule 0 / 1, orient 0 / 1 (the EXIF orientation is applied),
+ *                  *orientation (may be NULL) = the value applied
+ *   whenet_jpeg_decode_accept_planes_host   the same up to the component planes
+ *   whenet_jpeg_decode_segmented_accept_host, ..._accept_planes_host   the emulation of the segmented form (the baseline decoder's
+ *                  streams only); accept 0 or 2
+ *   whenet_op_jpeg_decode_accept        whenet_op_jpeg_decode_oriented with `accept` (-1: the handle's two options) for `progressive`;
+ *                  stats of a frame that went through the scan plan: items, levels, scans, launches of the scan kernel
+ *   whenet_op_jpeg_decode_clip_accept, whenet_frame_begin_jpeg_accept, whenet_clip_begin_jpeg_accept   the twins of the ..._oriented
+ *                  calls, `accept` for `progressive` (a clip: 0..3, never -1)
+ *   whenet_jpeg_clip_plan_accept        whenet_jpeg_clip_plan_progressive with the bits; a sequential frame that goes through the
+ *                  scan plan is a form-2 frame of ONE level there, its `huff` region six tables per scan, and the totals' word 9
+ *                  is the SOF2 frames' largest level count + 1 where the clip holds such a frame
+ *   option "jpeg_layouts"   0 (default) / 1, above.
+ * whenet_jpeg_progressive_counters counts a frame that goes through the scan plan, its launch and its scans like a SOF2 frame's.
+ * Not built: a segmented (many lanes per interval) form for the scans of the scan plan, a component split over several sequential
+ * scans, default tables for ids 2 / 3, a DQT between scans. */
 #define WHENET_JPEG_SEG_WINDOW 256
 #define WHENET_JPEG_PROG_MAX_SCANS 128
 #define WHENET_JPEG_CLIP_PLAN_FRAME_WORDS 32
@@ -1203,7 +1276,7 @@ WHENET_API int whenet_frame_annotate_jpeg_ex(whenet_t* h, int ticket, int frame_
 #define WHENET_JPEG_CLIP_PROG_PLAN_TOTAL_WORDS 16
 typedef struct {
     int32_t h, w, components;
-    int32_t hs, vs;                  /* luma sampling factors (1 or 2); chroma is 1 x 1 */
+    int32_t hs, vs;                  /* luma sampling factors (1 or 2; LAYOUTS: hs 1, 2 or 4); chroma is 1 x 1 */
     int32_t qt[3], dc[3], ac[3];     /* per component: quantiser id, DC and AC Huffman table ids */
     int32_t restart_interval;        /* Ri in MCUs; 0: no DRI */
     int32_t intervals;               /* ceil(MCUs / Ri); 1 without DRI */

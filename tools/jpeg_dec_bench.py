@@ -62,7 +62,22 @@
                                 kernels' own times come from a kernel trace of this row (--rgb or --rule 1 puts the upright frame
                                 through the frame kernel too, so that the three can be read side by side).
 
-  python tools/jpeg_dec_bench.py [--progressive] [--orient 1 3 6] [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
+    (ix)  --layouts old | new   the LAYOUTS section (recorded, not gated), INSTEAD of (i)-(viii); ms per frame for begin -> release without
+                                heads -> collect through whenet_frame_begin_jpeg[_accept], every frame checked against the host
+                                statement first.  Each figure is the median of --repeats (>= 5) REPEATS, a repeat being the median of
+                                --clip-samples regions after 3 warm-up ones; "spread" is the repeats' own minimum and maximum.
+                                  old   what existed before the section, through calls that existed before it (so that the row runs
+                                        unchanged on the parent commit's library: WHENET_HIP_PKG): Pillow's 4:2:0, 4:2:2 and 4:4:4 streams
+                                        of the picture (quality 95, one interval per MCU row) with the entropy stage in form 0 and
+                                        form 1.  A commit does not regress where its medians lie inside the parent's spreads.
+                                  new   what the section adds: the 4:4:0, 4:1:1 and 4:1:0 twins of the picture (the layout writer of
+                                        tests/jpeg_layout_cases.py on the picture's own DCT blocks, one interval per MCU row) next to
+                                        its 4:2:2 twin from the same writer (Annex K Huffman tables); and a three-scan 4:2:0 twin against the interleaved one,
+                                        with one interval per MCU row and without DRI (a multi-scan stream without DRI is ONE lane
+                                        per scan: the known limit of the scan-plan path).
+                                The kernels' own times come from a kernel trace of this row.
+
+  python tools/jpeg_dec_bench.py [--progressive] [--layouts old] [--orient 1 3 6] [--sizes 1080x1920 480x640] [--rounds 7] [--iters 30] [--entropy 0 1] [--seg-bytes 64 128 256 512]
                                  [--lanes 0] [--rule 0] [--rgb] [--only-decode] [--clip 1 4 16] [--clip-samples 20]
                                  [--slow-seconds 5] [--slow-samples 20]
 
@@ -429,6 +444,93 @@ def orient_leg(m, h, w, args):
     return res
 
 
+def layouts_leg(m, h, w, args):
+    """row (ix): begin -> release without heads -> collect, per stream and entropy form; see the module's text"""
+    from PIL import Image
+    from whenet_hip import jpeg, synth
+    if m is not None:
+        import torch
+        hnd = m._handle
+        sync = torch.cuda.synchronize
+    no_heads = np.zeros((0, 4), np.int32)
+    status = np.zeros(2, np.int32)
+    frame = synth.video_frame(h, w)
+    res = {"frame": [h, w], "rule": args.rule, "layouts": args.layouts, "repeats": max(5, args.repeats), "streams": {}}
+
+    def timed(begin):
+        for _ in range(3):
+            begin()
+        reps = []
+        for _ in range(max(5, args.repeats)):
+            ms = []
+            for _ in range(max(5, args.clip_samples)):
+                sync()
+                t = time.perf_counter()
+                begin()
+                ms.append((time.perf_counter() - t) * 1e3)
+            reps.append(statistics.median(ms))
+        return {"ms": round(statistics.median(reps), 3), "spread": [round(min(reps), 3), round(max(reps), 3)]}
+
+    def collect(t):
+        hnd.frame_heads(t, no_heads)
+        hnd.collect(t, 0)
+
+    if args.layouts == "old":
+        im = Image.fromarray(np.ascontiguousarray(frame[..., ::-1]))
+        for name, sub in (("420", 2), ("422", 1), ("444", 0)):
+            buf = io.BytesIO()
+            im.save(buf, "JPEG", quality=95, subsampling=sub, restart_marker_rows=1)
+            data = buf.getvalue()
+            want = jpeg.decode_host(data, rule=RULES[args.rule])
+            r = {"bytes_jpeg": len(data), "equals_host": True}
+            for key, entropy in (("interval", 0), ("segmented", 1)):
+                hnd.set_option("jpeg_entropy", entropy)
+                r["equals_host"] = r["equals_host"] and bool(np.array_equal(jpeg.decode(data, handle=hnd, rule=RULES[args.rule], entropy=key), want))
+                r[key] = timed(lambda: collect(hnd.frame_begin_jpeg(data, status)))
+                print(f"{h}x{w} {name} {key}: {r[key]}", file=sys.stderr, flush=True)
+            hnd.set_option("jpeg_entropy", 2)
+            res["streams"][name] = r
+        return res
+    sys.path.insert(0, ROOT)
+    from tests import jpeg_layout_cases as LC
+    from whenet_hip import _lib
+    accept = _lib.JPEG_ACCEPT_LAYOUTS
+    table = [(n, hs, vs, [[0, 1, 2]], True) for n, (hs, vs) in (("422", (2, 1)), ("440", (1, 2)), ("411", (4, 1)), ("410", (4, 2)))]
+    table += [("420_interleaved_rows", 2, 2, [[0, 1, 2]], True), ("420_three_scans_rows", 2, 2, [[0], [1], [2]], True),
+              ("420_interleaved_nodri", 2, 2, [[0, 1, 2]], False), ("420_three_scans_nodri", 2, 2, [[0], [1], [2]], False)]
+    for name, hs, vs, groups, rows in table:
+        cached = os.path.join(args.stream_cache, f"layouts_{h}x{w}_{name}.jpg") if args.stream_cache else None
+        if cached and os.path.exists(cached):
+            with open(cached, "rb") as f:
+                data = f.read()
+        else:      # (the writer is plain Python: a 1080p stream takes it a minute)
+            blocks = LC.blocks_of(h, w, hs, vs, picture_of=lambda hh, ww, seed: frame[..., ::-1])
+            mcu_cols = -(-w // (8 * hs))
+            # one interval per MCU row of the SCAN: a one-component scan's rows are its own block rows
+            dris = [(mcu_cols if len(g) > 1 else -(-(w if g == [0] else -(-w // hs)) // 8)) if rows else None for g in groups]
+            data = LC.write(blocks, h, w, hs, vs, groups=groups, dris=dris, annexk=True)      # (T.81 Annex K codes: what cameras write)
+            if cached:
+                os.makedirs(args.stream_cache, exist_ok=True)
+                with open(cached, "wb") as f:
+                    f.write(data)
+        if args.write_only:
+            res["streams"][name] = {"bytes_jpeg": len(data)}
+            continue
+        want = jpeg.decode_host(data, rule=RULES[args.rule], layouts=True)
+        r = {"bytes_jpeg": len(data), "scans": len(groups), "equals_host": True}
+        forms = (("interval", 0), ("segmented", 1)) if len(groups) == 1 else (("scan_plan", -1),)
+        for key, entropy in forms:
+            ent = "auto" if entropy < 0 else key
+            r["equals_host"] = r["equals_host"] and bool(np.array_equal(jpeg.decode(data, handle=hnd, rule=RULES[args.rule], entropy=ent, layouts=True), want))
+            if entropy >= 0:
+                hnd.set_option("jpeg_entropy", entropy)
+            r[key] = timed(lambda: collect(hnd.frame_begin_jpeg_accept(data, status, accept=accept)[0]))
+            print(f"{h}x{w} {name} {key}: {r[key]}", file=sys.stderr, flush=True)
+        hnd.set_option("jpeg_entropy", 2)
+        res["streams"][name] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", nargs="+", default=["1080x1920", "480x640"], help="frame sizes, HxW")
@@ -444,9 +546,18 @@ def main():
     ap.add_argument("--clip-samples", type=int, default=20, help="regions per figure of row (v), at least 20")
     ap.add_argument("--progressive", action="store_true", help="row (vi) only: progressive streams against their baseline twins; with --clip: row (vii)")
     ap.add_argument("--orient", type=int, nargs="+", default=None, choices=range(1, 9), help="row (viii) only: EXIF orientation values to time")
+    ap.add_argument("--layouts", choices=["old", "new"], default=None, help="row (ix) only: the streams that existed before the LAYOUTS section, or its new ones")
+    ap.add_argument("--stream-cache", default=None, help="row (ix) new: a folder that keeps the written streams from run to run")
+    ap.add_argument("--write-only", action="store_true", help="row (ix) new: write the streams into --stream-cache and stop (needs no GPU)")
+    ap.add_argument("--repeats", type=int, default=5, help="row (ix): repeats per figure, at least 5")
     ap.add_argument("--slow-seconds", type=float, default=5.0, help="row (vii): a region longer than this counts as slow")
     ap.add_argument("--slow-samples", type=int, default=20, help="row (vii): regions per figure where one region is slow (after ONE warm-up region)")
     args = ap.parse_args()
+    if args.layouts == "new" and args.write_only:
+        for size in args.sizes:
+            h, w = (int(v) for v in size.split("x"))
+            print(json.dumps(layouts_leg(None, h, w, args)), flush=True)
+        return 0
     import torch  # noqa: F401  (first: one HIP runtime in the process, torch's)
     import whenet
     m = whenet.WHENet(dtype="f16")
@@ -458,6 +569,8 @@ def main():
             leg = (prog_clip_leg if args.clip else prog_leg) if args.progressive else (clip_leg if args.clip else size_leg)
             if args.orient:
                 leg = orient_leg
+            if args.layouts:
+                leg = layouts_leg
             print(json.dumps(leg(m, h, w, args)), flush=True)
     finally:
         m.close()
