@@ -928,6 +928,47 @@ int whenet_op_yuv_to_bgr_device(whenet_t* h, const whenet_yuv_frame_t* frames, i
     return guarded(h, [&](whenet::Engine& e) { e.op_yuv_to_bgr_device(frames, num_frames, static_cast<hipStream_t>(stream), bgr); });
 }
 
+// ---- extended YUV ingest (include/whenet_hip_yuv_ext.h; yuvx.hip, yuvx_host.h, engine_post.cpp) ----
+int whenet_yuvx_to_bgr_host(const whenet_yuvx_frame_t* frame, uint8_t* bgr) {
+    if (frame == nullptr || bgr == nullptr) return WHENET_EINVAL;
+    try {
+        whenet::check_yuvx_frames("yuvx_to_bgr_host", frame, 1);
+        whenet::yuvx_to_bgr_host(*frame, bgr);
+        return WHENET_OK;
+    } catch (...) {
+        return translate_exception(g_create_error);      // (no handle: the text is whenet_last_error(NULL)'s)
+    }
+}
+
+int whenet_op_yuvx_to_bgr(whenet_t* h, const whenet_yuvx_frame_t* frames, int num_frames, uint8_t* const* bgr) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_yuvx_to_bgr(frames, num_frames, bgr); });
+}
+
+// (begin_yuvx checks the arguments before it takes a slot, and a refusal throws before the round-robin moves)
+int whenet_frame_begin_yuvx(whenet_t* h, const whenet_yuvx_frame_t* frame, int* ticket) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.begin_yuvx("frame_begin_yuvx", frame, 1, false, false, nullptr); });
+}
+
+int whenet_clip_begin_yuvx(whenet_t* h, const whenet_yuvx_frame_t* frames, int num_frames, int* ticket) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) { return e.begin_yuvx("clip_begin_yuvx", frames, num_frames, true, false, nullptr); });
+}
+
+int whenet_frame_begin_yuvx_device(whenet_t* h, const whenet_yuvx_frame_t* frame, void* stream, int* ticket) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        return e.begin_yuvx("frame_begin_yuvx_device", frame, 1, false, true, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_clip_begin_yuvx_device(whenet_t* h, const whenet_yuvx_frame_t* frames, int num_frames, void* stream, int* ticket) {
+    return begin_on_next_engine(h, ticket, [&](whenet::Engine& e) {
+        return e.begin_yuvx("clip_begin_yuvx_device", frames, num_frames, true, true, static_cast<hipStream_t>(stream));
+    });
+}
+
+int whenet_op_yuvx_to_bgr_device(whenet_t* h, const whenet_yuvx_frame_t* frames, int num_frames, void* stream, uint8_t* const* bgr) {
+    return guarded(h, [&](whenet::Engine& e) { e.op_yuvx_to_bgr_device(frames, num_frames, static_cast<hipStream_t>(stream), bgr); });
+}
+
 // ---- pose overlay (overlay.hip, overlay_host.h, engine_post.cpp) ----
 int whenet_overlay_segments(const int32_t rect[4], float yaw, float pitch, float roll, int32_t segments[16], int32_t* flags) {
     if (rect == nullptr || segments == nullptr) return WHENET_EINVAL;

@@ -321,6 +321,14 @@ class Engine {
     void op_pack_device(const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw, hipStream_t stream,
                         uint8_t* const* out);
     void op_yuv_to_bgr_device(const whenet_yuv_frame_t* frames, int nframes, hipStream_t stream, uint8_t* const* bgr);
+    // EXTENDED YUV INGEST (yuvx.hip; include/whenet_hip_yuv_ext.h): the twins of the seven YUV calls above for whenet_yuvx_frame_t --
+    // 16-bit containers, planar 4:4:4, BT.2020, and the old formats through the same struct.  The slots, the stream order, the size
+    // rules of a clip and the device-pointer checks are those of the calls above; the planes of a host frame are staged by
+    // YuvxLayout (a 16-bit frame at an even offset).  begin_yuvx is the one body of the four begin calls: `clip` tells whether the
+    // slot is a clip's, `device` whether the planes are device memory ordered on `stream`.
+    int begin_yuvx(const char* what, const whenet_yuvx_frame_t* frames, int nframes, bool clip, bool device, hipStream_t stream);
+    void op_yuvx_to_bgr(const whenet_yuvx_frame_t* frames, int nframes, uint8_t* const* bgr);
+    void op_yuvx_to_bgr_device(const whenet_yuvx_frame_t* frames, int nframes, hipStream_t stream, uint8_t* const* bgr);
     // POSE OVERLAY (overlay.hip; the contract is in include/whenet_hip.h).  frame_annotate: between the call that enqueues a ticket's
     // heads and its collect -- the plan kernel (windows, valid flags and angles where the heads' launches leave them: the crop
     // plans of submit_frame / frame_heads, the DetRows of frame_detect_heads, the ClipRows + row map of clip_detect_heads) and the
@@ -583,6 +591,10 @@ class Engine {
     void check_device_plane(const std::string& who, const uint8_t* p, int rows, int pitch, int row_bytes) const;
     void check_device_frames(const char* what, const uint8_t* const* d_frames, const int* pitch, int nframes, const int* fh, const int* fw) const;
     void check_device_yuv_frames(const char* what, const whenet_yuv_frame_t* frames, int nframes) const;
+    void check_device_yuvx_frames(const char* what, const whenet_yuvx_frame_t* frames, int nframes) const;
+    // enqueue_yuv_ingest for whenet_yuvx_frame_t (one launch of yuvx.hip's upload form)
+    void enqueue_yuvx_ingest(const whenet_yuvx_frame_t* frames, int nframes, uint8_t* h_stage, uint8_t* d_planes, uint8_t* d_bgr,
+                             const size_t* off, hipStream_t s);
     void ingest_after_caller(Slot& slot, hipStream_t caller);      // caller's stream -> slot.source -> copy stream
     void ingest_done(Slot& slot, hipStream_t caller);              // copy stream -> slot.copied -> caller's stream
     // the argument checks of frame_annotate that concern the ticket; returns its slot, the head slots per frame and the frame's geometry

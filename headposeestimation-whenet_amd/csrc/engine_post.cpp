@@ -716,6 +716,108 @@ int Engine::clip_begin_yuv_device(const whenet_yuv_frame_t* frames, int nframes,
     return slot.frame_ticket;
 }
 
+// ---- extended YUV ingest (yuvx.hip; the contract is in include/whenet_hip_yuv_ext.h) ----
+void Engine::check_device_yuvx_frames(const char* what, const whenet_yuvx_frame_t* frames, int nframes) const {
+    check_yuvx_frames(what, frames, nframes);
+    for (int i = 0; i < nframes; ++i) {
+        const whenet_yuvx_frame_t& f = frames[i];
+        for (int p = 0; p < yuvx_plane_count(f.layout); ++p)
+            check_device_plane(std::string(what) + ": frame " + std::to_string(i) + ": plane " + std::to_string(p), f.plane[p],
+                               yuvx_plane_rows(f.layout, p, f.h), f.pitch[p], yuvx_plane_row_bytes(f.layout, p, f.w, f.container >> 3));
+    }
+}
+
+namespace {
+YuvxClip yuvx_clip(const whenet_yuvx_frame_t* frames, int nframes, const size_t* src, const size_t* dst) {
+    YuvxClip clip{};
+    clip.frames = nframes;
+    for (int f = 0; f < nframes; ++f) clip.f[f] = yuvx_frame(frames[f], src ? src[f] : 0, dst[f]);
+    return clip;
+}
+}  // namespace
+
+void Engine::enqueue_yuvx_ingest(const whenet_yuvx_frame_t* frames, int nframes, uint8_t* h_stage, uint8_t* d_planes, uint8_t* d_bgr,
+                                 const size_t* off, hipStream_t s) {
+    const YuvxLayout lay(frames, nframes);
+    for (int f = 0; f < nframes; ++f) {
+        if (f > 0) {                                   // (the padding byte in front of a 16-bit frame, if there is one)
+            const size_t prev_end = lay.src[f - 1] + yuvx_plane_bytes(frames[f - 1].h, frames[f - 1].w, frames[f - 1].layout, frames[f - 1].container);
+            if (lay.src[f] > prev_end) h_stage[prev_end] = 0;
+        }
+        yuvx_stage_planes(frames[f], h_stage + lay.src[f]);
+    }
+    WHENET_HIP_CHECK(hipMemcpyAsync(d_planes, h_stage, lay.end, hipMemcpyHostToDevice, s));
+    launch_yuvx_to_bgr(d_planes, d_bgr, yuvx_clip(frames, nframes, lay.src, off), s);
+}
+
+void Engine::op_yuvx_to_bgr(const whenet_yuvx_frame_t* frames, int nframes, uint8_t* const* bgr) {
+    DeviceGuard guard(device_);
+    check_yuvx_frames("op_yuvx_to_bgr", frames, nframes);
+    WHENET_REQUIRE(bgr != nullptr, WHENET_EINVAL, "op_yuvx_to_bgr: NULL argument");
+    for (int f = 0; f < nframes; ++f) WHENET_REQUIRE(bgr[f] != nullptr, WHENET_EINVAL, "op_yuvx_to_bgr: output " + std::to_string(f) + " is NULL");
+    const YuvxLayout lay(frames, nframes);
+    PinnedBuffer stage;
+    DeviceBuffer d_planes;
+    stage.reset(lay.end);
+    d_planes.reset(lay.end, "hipMalloc");
+    const GuardedOutput d_bgr(lay.dst[nframes], stream_);
+    enqueue_yuvx_ingest(frames, nframes, stage.as<uint8_t>(), d_planes.as<uint8_t>(), d_bgr.frames(), lay.dst, stream_);
+    d_bgr.to_host(stream_, lay.dst, nframes, bgr, "op_yuvx_to_bgr");
+}
+
+void Engine::op_yuvx_to_bgr_device(const whenet_yuvx_frame_t* frames, int nframes, hipStream_t stream, uint8_t* const* bgr) {
+    DeviceGuard guard(device_);
+    check_device_yuvx_frames("op_yuvx_to_bgr_device", frames, nframes);
+    WHENET_REQUIRE(bgr != nullptr, WHENET_EINVAL, "op_yuvx_to_bgr_device: NULL argument");
+    for (int f = 0; f < nframes; ++f)
+        WHENET_REQUIRE(bgr[f] != nullptr, WHENET_EINVAL, "op_yuvx_to_bgr_device: output " + std::to_string(f) + " is NULL");
+    const YuvxLayout lay(frames, nframes);
+    const GuardedOutput d_bgr(lay.dst[nframes], stream_);
+    Event after;
+    after.create();
+    WHENET_HIP_CHECK(hipEventRecord(after, stream));
+    WHENET_HIP_CHECK(hipStreamWaitEvent(stream_, after, 0));
+    launch_yuvx_planes_to_bgr(d_bgr.frames(), yuvx_clip(frames, nframes, nullptr, lay.dst), stream_);
+    d_bgr.to_host(stream_, lay.dst, nframes, bgr, "op_yuvx_to_bgr_device");
+}
+
+// frame_begin_yuv / clip_begin_yuv / frame_begin_yuv_device / clip_begin_yuv_device for whenet_yuvx_frame_t: the slot ends up
+// exactly as the call of that name leaves it
+int Engine::begin_yuvx(const char* what, const whenet_yuvx_frame_t* frames, int nframes, bool clip, bool device, hipStream_t stream) {
+    DeviceGuard guard(device_);
+    if (device) check_device_yuvx_frames(what, frames, nframes);      // (before a slot is taken)
+    else check_yuvx_frames(what, frames, nframes);
+    WHENET_REQUIRE(clip || nframes == 1, WHENET_EINVAL, std::string(what) + ": one frame");
+    bool one_size = true;
+    for (int f = 1; f < nframes; ++f) one_size = one_size && frames[f].h == frames[0].h && frames[f].w == frames[0].w;
+    WHENET_REQUIRE(one_size || nframes <= lb_cache_cap_, WHENET_EINVAL,
+                   std::string(what) + ": " + std::to_string(nframes) + " frames of their own sizes need option letterbox_cache >= " +
+                       std::to_string(nframes) + " (it is " + std::to_string(lb_cache_cap_) + ")");
+    Slot& slot = *free_slot();
+    ensure_slot(slot, 1);
+    const YuvxLayout lay(frames, nframes);
+    slot.frame.d.grow(lay.dst[nframes]);
+    if (device) {
+        ingest_after_caller(slot, stream);
+        launch_yuvx_planes_to_bgr(slot.frame.d.as<uint8_t>(), yuvx_clip(frames, nframes, nullptr, lay.dst), copy_stream());
+        ingest_done(slot, stream);
+    } else {
+        // (the size every other user of the staging grows it to; the planes of a 16-bit 4:4:4 frame are more bytes than the frame)
+        slot.frame.h.grow(std::max(lay.dst[nframes], lay.end));
+        slot.yuv.grow(lay.end);
+        enqueue_yuvx_ingest(frames, nframes, slot.frame.h.as<uint8_t>(), slot.yuv.as<uint8_t>(), slot.frame.d.as<uint8_t>(), lay.dst, copy_stream());
+        WHENET_HIP_CHECK(hipEventRecord(slot.copied, copy_stream()));
+    }
+    slot.fh = frames[0].h, slot.fw = frames[0].w, slot.swap_rb = 1;
+    if (clip && !one_size) {
+        for (int f = 0; f < nframes; ++f) slot.clip_fh[f] = frames[f].h, slot.clip_fw[f] = frames[f].w;
+        std::copy(lay.dst, lay.dst + nframes + 1, slot.clip_off);
+    }
+    slot.frame_ticket = finish_submission(slot, 0);
+    if (clip) slot.clip_f = nframes, slot.clip_mixed = !one_size;
+    return slot.frame_ticket;
+}
+
 Engine::Slot& Engine::resident_slot(int ticket, const char* what, int holds) {
     for (Slot& s : slots_)
         if (s.busy && s.ticket == ticket) {

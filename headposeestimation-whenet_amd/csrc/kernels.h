@@ -12,6 +12,7 @@
 #include "jpeg_dec_seg_host.h"
 #include "jpeg_dec_clip_host.h"
 #include "jpeg_prog_host.h"
+#include "yuvx_host.h"
 
 namespace whenet {
 
@@ -593,6 +594,32 @@ struct YuvPlanes {
     YuvPlanesFrame f[MIXED_MAX_FRAMES];
 };
 void launch_yuv_planes_to_bgr(uint8_t* d_bgr, YuvPlanes clip, hipStream_t stream);
+
+// ---- yuvx.hip ---------------------------------------------------------------------------
+// The extended ingest of include/whenet_hip_yuv_ext.h: every layout (NV12-like, I420-like, packed 4:2:2, planar 4:4:4) with 8-bit
+// or 16-bit samples -> the same packed BGR frame.  The geometry, the checks, the per-pixel function, the host statement and the
+// staging are yuvx_host.h (plain C++); these wrap its checks into WHENET_EINVAL.
+const YuvxCoeffs& yuvx_coeffs(int matrix);      // throws WHENET_EINVAL
+void check_yuvx_frames(const char* what, const whenet_yuvx_frame_t* frames, int nframes);
+// One frame of a launch, for both forms.  Upload form: the frame's planes lie TIGHT behind one another src_off bytes into
+// d_planes (YuvxLayout; plane[] / pitch[] unused).  Plane form: plane[] / pitch[] are the frame's own, in device memory (src_off
+// unused).  The output starts dst_off bytes into d_bgr (any alignment).
+struct YuvxFrame {
+    const uint8_t* plane[3];
+    int pitch[3];
+    int h, w, layout, container, shift;
+    YuvxCoeffs k;
+    unsigned long long src_off, dst_off;
+    int block0;                                 // the first workgroup of the frame
+};
+struct YuvxClip {
+    int frames, total_blocks;
+    YuvxFrame f[MIXED_MAX_FRAMES];
+};
+YuvxFrame yuvx_frame(const whenet_yuvx_frame_t& f, size_t src_off, size_t dst_off);
+// block0 / total_blocks are set by the launchers; the records travel by value in the argument block
+void launch_yuvx_to_bgr(const uint8_t* d_planes, uint8_t* d_bgr, YuvxClip clip, hipStream_t stream);
+void launch_yuvx_planes_to_bgr(uint8_t* d_bgr, YuvxClip clip, hipStream_t stream);
 
 // ---- ingest.hip -------------------------------------------------------------------------
 // Packed 3-byte pixels that are already in device memory -> the tight frame [h][w][3] the frame path reads: h rows of row_bytes =

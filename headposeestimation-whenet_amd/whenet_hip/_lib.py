@@ -43,6 +43,12 @@ class YuvFrameC(C.Structure):
     _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("format", C.c_int), ("matrix", C.c_int), ("h", C.c_int), ("w", C.c_int)]
 
 
+class YuvxFrameC(C.Structure):
+    """whenet_yuvx_frame_t (include/whenet_hip_yuv_ext.h): a frame as a layout times a sample container (8 or 16 bit, with a shift)."""
+    _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("layout", C.c_int), ("container", C.c_int), ("shift", C.c_int),
+                ("matrix", C.c_int), ("h", C.c_int), ("w", C.c_int)]
+
+
 class SurfaceC(C.Structure):
     """whenet_surface_t: a destination of the pose overlay (packed pixels, NV12 or I420; host or device memory)."""
     _fields_ = [("plane", _P * 3), ("pitch", C.c_int * 3), ("format", C.c_int), ("matrix", C.c_int), ("on_device", C.c_int)]
@@ -232,6 +238,17 @@ _PROTOS_ACCEPT = {
     "whenet_jpeg_clip_plan_accept": (C.c_int, [C.POINTER(_P), _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
 }
 EXPORTS_ACCEPT = tuple(_PROTOS_ACCEPT)
+# the entry points of include/whenet_hip_yuv_ext.h (16-bit containers, planar 4:4:4, BT.2020): the twins of the seven YUV calls above
+_PROTOS_YUVX = {
+    "whenet_yuvx_to_bgr_host": (C.c_int, [C.POINTER(YuvxFrameC), _P]),
+    "whenet_op_yuvx_to_bgr": (C.c_int, [_P, C.POINTER(YuvxFrameC), C.c_int, C.POINTER(_P)]),
+    "whenet_frame_begin_yuvx": (C.c_int, [_P, C.POINTER(YuvxFrameC), C.POINTER(C.c_int)]),
+    "whenet_clip_begin_yuvx": (C.c_int, [_P, C.POINTER(YuvxFrameC), C.c_int, C.POINTER(C.c_int)]),
+    "whenet_frame_begin_yuvx_device": (C.c_int, [_P, C.POINTER(YuvxFrameC), _P, C.POINTER(C.c_int)]),
+    "whenet_clip_begin_yuvx_device": (C.c_int, [_P, C.POINTER(YuvxFrameC), C.c_int, _P, C.POINTER(C.c_int)]),
+    "whenet_op_yuvx_to_bgr_device": (C.c_int, [_P, C.POINTER(YuvxFrameC), C.c_int, _P, C.POINTER(_P)]),
+}
+EXPORTS_YUVX = tuple(_PROTOS_YUVX)
 
 _lib: Optional[C.CDLL] = None
 
@@ -246,7 +263,7 @@ def load() -> C.CDLL:
         raise OSError(f"{path} not found: build it with `python __graft_entry__.py` "
                       "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(os.path.abspath(path))
-    for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_ACCEPT.items()):
+    for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_ACCEPT.items()) + list(_PROTOS_YUVX.items()):
         fn = getattr(lib, name)          # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args
@@ -503,6 +520,10 @@ YUV_BT601, YUV_BT709, YUV_JFIF = 0, 1, 2       # WHENET_YUV_BT601 / _BT709 / _JF
 def _yuv_descs(frames):
     """The whenet_yuv_frame_t array of a list of frames (`whenet_hip.yuv.YUVFrame`s, or YuvFrameC descriptors as they are)."""
     descs = [f if isinstance(f, YuvFrameC) else f.descriptor() for f in frames]
+    for i, d in enumerate(descs):
+        if not isinstance(d, YuvFrameC):
+            raise ValueError(f"frame {i} needs the extended calls (a 16-bit container, 4:4:4 or BT.2020): op_yuvx_to_bgr / frame_begin_yuvx / "
+                             "clip_begin_yuvx and their device twins take it")
     return (YuvFrameC * max(len(descs), 1))(*descs), descs
 
 
@@ -514,6 +535,41 @@ def yuv_to_bgr_host(desc: YuvFrameC) -> np.ndarray:
     rc = lib.whenet_yuv_to_bgr_host(C.byref(desc), _ptr(out) if out.size else None)
     if rc != OK:
         raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace") if out.size else "yuv_to_bgr_host: frame 0 is empty")
+    return out
+
+
+# ---- include/whenet_hip_yuv_ext.h ----
+YUVX_I444 = 16                                 # WHENET_YUVX_I444: the layout beside YUV_NV12 / _I420 / _YUYV / _UYVY
+YUVX_U8, YUVX_U16 = 8, 16                      # WHENET_YUVX_U8 / _U16: the container, bits per stored sample
+YUV_BT2020 = 3                                 # WHENET_YUV_BT2020: the fourth row of WHENET_YUVX_COEFFS
+
+
+def yuvx_desc(f) -> YuvxFrameC:
+    """The whenet_yuvx_frame_t of a frame: a YuvxFrameC as it is, a YuvFrameC (an old format: 8-bit container, shift 0), or a
+    `whenet_hip.yuv.YUVFrame` (its `descriptor_ext()`)."""
+    if isinstance(f, YuvxFrameC):
+        return f
+    if isinstance(f, YuvFrameC):
+        d = YuvxFrameC()
+        for i in range(3):
+            d.plane[i], d.pitch[i] = f.plane[i], f.pitch[i]
+        d.layout, d.container, d.shift, d.matrix, d.h, d.w = f.format, YUVX_U8, 0, f.matrix, f.h, f.w
+        return d
+    return f.descriptor_ext()
+
+
+def _yuvx_descs(frames):
+    descs = [yuvx_desc(f) for f in frames]
+    return (YuvxFrameC * max(len(descs), 1))(*descs), descs
+
+
+def yuvx_to_bgr_host(desc: YuvxFrameC) -> np.ndarray:
+    """`yuv_to_bgr_host` for a whenet_yuvx_frame_t: the host statement of include/whenet_hip_yuv_ext.h, inside the library."""
+    lib = load()
+    out = np.empty((max(int(desc.h), 0), max(int(desc.w), 0), 3), np.uint8)
+    rc = lib.whenet_yuvx_to_bgr_host(C.byref(desc), _ptr(out) if out.size else None)
+    if rc != OK:
+        raise_for(rc, (lib.whenet_last_error(None) or b"").decode(errors="replace") if out.size else "yuvx_to_bgr_host: frame 0 is empty")
     return out
 
 
@@ -1546,6 +1602,50 @@ class Handle:
         ptrs = (_P * max(len(outs), 1))(*[o.ctypes.data if o.size else None for o in outs])
         self._check(self._lib.whenet_op_yuv_to_bgr_device(self._h, arr, len(descs), _stream(stream), ptrs))
         return outs
+
+    # ---- extended YUV ingest (include/whenet_hip_yuv_ext.h): the same seven calls for whenet_yuvx_frame_t ---------------
+    def _op_yuvx(self, fn, frames, *stream):
+        arr, descs = _yuvx_descs(frames)
+        outs = [np.empty((max(int(d.h), 0), max(int(d.w), 0), 3), np.uint8) for d in descs]
+        ptrs = (_P * max(len(outs), 1))(*[o.ctypes.data if o.size else None for o in outs])
+        self._check(fn(self._h, arr, len(descs), *stream, ptrs))
+        return outs
+
+    def op_yuvx_to_bgr(self, frames: list) -> list:
+        """`op_yuv_to_bgr` through the extended call: frames of any layout, container and matrix (`YUVFrame`s, old formats included)."""
+        return self._op_yuvx(self._lib.whenet_op_yuvx_to_bgr, frames)
+
+    def op_yuvx_to_bgr_device(self, frames: list, stream=None) -> list:
+        """`op_yuv_to_bgr_device` through the extended call."""
+        return self._op_yuvx(self._lib.whenet_op_yuvx_to_bgr_device, frames, _stream(stream))
+
+    def frame_begin_yuvx(self, frame) -> int:
+        """`frame_begin_yuv` through the extended call."""
+        arr, _ = _yuvx_descs([frame])
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin_yuvx(self._h, arr, C.byref(t)))
+        return t.value
+
+    def clip_begin_yuvx(self, frames: list) -> int:
+        """`clip_begin_yuv` through the extended call: a clip may mix old and new formats."""
+        arr, descs = _yuvx_descs(frames)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_yuvx(self._h, arr, len(descs), C.byref(t)))
+        return t.value
+
+    def frame_begin_yuvx_device(self, frame, stream=None) -> int:
+        """`frame_begin_yuv_device` through the extended call."""
+        arr, _ = _yuvx_descs([frame])
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_frame_begin_yuvx_device(self._h, arr, _stream(stream), C.byref(t)))
+        return t.value
+
+    def clip_begin_yuvx_device(self, frames: list, stream=None) -> int:
+        """`clip_begin_yuv_device` through the extended call."""
+        arr, descs = _yuvx_descs(frames)
+        t = C.c_int(-1)
+        self._check(self._lib.whenet_clip_begin_yuvx_device(self._h, arr, len(descs), _stream(stream), C.byref(t)))
+        return t.value
 
     def op_letterbox_mixed(self, frames: list, size=(416, 416), bgr: bool = True, want_u8: bool = True, want_f32: bool = True):
         """`op_letterbox` of F frames of their own sizes in one call: (canvas uint8 [F,h,w,3], image float32 [F,h,w,3])."""

@@ -37,7 +37,8 @@ cv2.cvtColor (22), cv2.resize to 224x224 (23) and a batch-1 `get_angle` (27).  H
     and `begin_yuv` / `begin_clip_yuv` with a `YUVFrame` whose planes are device arrays.  One kernel (`csrc/ingest.hip`,
     `csrc/yuv.hip`) reads it where it is, with its row pitch, ordered on the caller's stream: no host copy, no PCIe, no host
     wait, and the same results bit for bit.  A device frame is never copied to make it fit: uint8 [H,W,3] with inner strides
-    (3, 1) or a ValueError.  Not built: BGRA / 4-channel, float or CHW tensors, 10-bit surfaces, memory of another GPU.
+    (3, 1) or a ValueError.  10-bit and 4:4:4 surfaces (P010 / P016, yuv420p10le,
+    I444; `whenet_hip.yuv`) go through the same two calls.  Not built: BGRA / 4-channel, float or CHW tensors, memory of another GPU.
 
 Only numpy and the C ABI are used (no torch, no cv2); there is no CPU fallback.
 """
@@ -286,7 +287,10 @@ class FramePipeline:
         self._check_can_begin()
         if not isinstance(frame, YUVFrame):
             raise ValueError(f"begin_yuv takes a whenet_hip.yuv.YUVFrame, got {type(frame).__name__}")
-        ticket = self._h.frame_begin_yuv_device(frame, stream=stream) if frame.on_device else self._h.frame_begin_yuv(frame)
+        if frame.needs_ext:                 # a 16-bit container, 4:4:4 or BT.2020: the calls of include/whenet_hip_yuv_ext.h
+            ticket = self._h.frame_begin_yuvx_device(frame, stream=stream) if frame.on_device else self._h.frame_begin_yuvx(frame)
+        else:
+            ticket = self._h.frame_begin_yuv_device(frame, stream=stream) if frame.on_device else self._h.frame_begin_yuv(frame)
         self._begun = (ticket, frame.h, frame.w)
         self._last_sizes = [(frame.h, frame.w)]
 
@@ -411,7 +415,10 @@ class FramePipeline:
         if len({f.on_device for f in frames}) > 1:
             raise ValueError("begin_clip_yuv: a clip's frames are all in device memory or all in host memory, not mixed: frames " +
                              str([i for i, f in enumerate(frames) if not f.on_device]) + " are host frames")
-        ticket = self._h.clip_begin_yuv_device(frames, stream=stream) if frames[0].on_device else self._h.clip_begin_yuv(frames)
+        if any(f.needs_ext for f in frames):      # (the extended calls take the old formats too: a clip may mix them)
+            ticket = self._h.clip_begin_yuvx_device(frames, stream=stream) if frames[0].on_device else self._h.clip_begin_yuvx(frames)
+        else:
+            ticket = self._h.clip_begin_yuv_device(frames, stream=stream) if frames[0].on_device else self._h.clip_begin_yuv(frames)
         self._begun_clip = (ticket, len(frames))
         self._last_sizes = [(f.h, f.w) for f in frames]
 

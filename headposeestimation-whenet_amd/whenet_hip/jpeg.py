@@ -52,6 +52,8 @@ def source_of(frame, what: str = "frame"):
     copy: another dtype or shape, pixels that are not packed, planes in device memory."""
     s = _lib.SurfaceC()
     if isinstance(frame, YUVFrame):
+        if frame.needs_ext:
+            raise ValueError(f"{what}: a 16-bit, 4:4:4 or BT.2020 frame as an encoder source is not built")
         if frame.on_device:
             raise ValueError(f"{what}: the planes are in device memory: Handle.jpeg_encode_device encodes those")
         for i, (a, p) in enumerate(zip(frame.planes, frame.pitches)):

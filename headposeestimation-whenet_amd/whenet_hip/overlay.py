@@ -49,6 +49,9 @@ def surface_of(out, h: int, w: int, what: str = "out"):
     would need a copy or a conversion: a read-only array, another shape or dtype, CHW, pixels that are not packed."""
     s = _lib.SurfaceC()
     if isinstance(out, YUVFrame):
+        if out.needs_ext:
+            raise ValueError(f"{what}: a 16-bit, 4:4:4 or BT.2020 frame as a destination is not built: destinations are packed "
+                             "BGR / RGB, or 8-bit NV12 / I420 under BT.601, BT.709 or JFIF")
         if out.format not in (_lib.YUV_NV12, _lib.YUV_I420):
             raise ValueError(f"{what}: a packed 4:2:2 frame (YUYV / UYVY) as a destination is not built: destinations are packed "
                              "BGR / RGB, NV12 or I420")

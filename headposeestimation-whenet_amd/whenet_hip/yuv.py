@@ -15,6 +15,21 @@ The planes may also lie in DEVICE memory -- a hardware decoder's surface, torch-
     surface = torch.empty(2048 * 1620, dtype=torch.uint8, device="cuda")          # filled by the decoder
     frame = YUVFrame.from_buffer(surface, 1080, 1920, "nv12", pitch=2048, matrix="bt709")
     fp.begin_yuv(frame, stream=torch.cuda.current_stream().cuda_stream)
+
+What a decoder makes of 10-bit video, and 4:4:4 surfaces (include/whenet_hip_yuv_ext.h, `csrc/yuvx.hip`): a frame is a LAYOUT (the
+four above, or planar 4:4:4) times a sample CONTAINER -- 8 bits, or 16 bits little endian with a `shift` (the sample at 16 bits is
+`(word << shift) & 0xFFFF`: 0 for P010 / P016 and a hardware decoder's 16-bit surfaces, 6 for yuv420p10le / I010, 4 for the 12-bit
+LSB-aligned forms) -- and a fourth matrix, "bt2020" (non-constant luminance, video range):
+
+    frame = YUVFrame.p010(y16, uv16, matrix="bt2020")                       # uint16 planes, or uint8 views with an even row
+    frame = YUVFrame.from_buffer(buf, 1080, 1920, "yuv420p10le", matrix="bt2020")
+    frame = YUVFrame.i444(y, u, v)                                          # uint8 or uint16 planes
+
+`begin_yuv` / `begin_clip_yuv` take such frames as they take the others (a clip may mix them).  The constructors `nv12`, `i420`,
+`yuyv`, `uyvy` keep the three matrices they had; and so do `from_buffer` with their names and the plain
+constructor; an 8-bit frame under BT.2020 is `YUVFrame(planes, "nv12", "bt2020", h, w, container=8)`: naming the container
+opens the extended tables.  Not built: Y210 / Y216 / v210, NV16 / NV24, big-endian samples, HDR transfer functions (PQ /
+HLG), full-range BT.709 / BT.2020, 10-bit destinations of `annotate`.
 """
 from __future__ import annotations
 
@@ -31,6 +46,19 @@ COEFFS = {"bt601": (16, 1220542, 1673527, 409993, 852492, 2116026),
           "bt709": (16, 1220945, 1879825, 223578, 558767, 2215014),
           "jfif": (0, 1048576, 1470104, 360853, 748826, 1858077)}
 MAX_SIDE = _lib.MAX_FRAME_SIDE
+# ---- include/whenet_hip_yuv_ext.h: layouts, containers, the fourth matrix ----
+I444 = _lib.YUVX_I444
+LAYOUTS = dict(FORMATS, i444=I444)
+_NAMES_EXT = dict(_NAMES)
+_NAMES_EXT[I444] = "I444"
+MATRICES_EXT = dict(MATRICES, bt2020=_lib.YUV_BT2020)
+COEFFS_EXT = dict(COEFFS, bt2020=(16, 1220945, 1760217, 196426, 682019, 2245811))      # WHENET_YUVX_COEFFS: a fourth row
+# names of `from_buffer` -> (layout, container bits, shift)
+FORMATS_EXT = {"p010": (_lib.YUV_NV12, 16, 0), "p012": (_lib.YUV_NV12, 16, 0), "p016": (_lib.YUV_NV12, 16, 0),
+               "i010": (_lib.YUV_I420, 16, 6), "yuv420p10le": (_lib.YUV_I420, 16, 6), "yuv420p12le": (_lib.YUV_I420, 16, 4),
+               "yuv420p16le": (_lib.YUV_I420, 16, 0),
+               "i444": (I444, 8, 0), "yuv444p": (I444, 8, 0), "yuv444p16": (I444, 16, 0), "yuv444p16le": (I444, 16, 0),
+               "yuv444p10le": (I444, 16, 6), "yuv444p12le": (I444, 16, 4)}
 
 
 def _code(table: dict, value, what: str) -> int:
@@ -43,12 +71,18 @@ def _code(table: dict, value, what: str) -> int:
     return int(value)
 
 
-def _plane(a, rows: int, row_bytes: int, name: str) -> np.ndarray:
+def _plane(a, rows: int, row_bytes: int, name: str, wide: bool = False) -> np.ndarray:
     """A plane as a uint8 array of `rows` rows of `row_bytes` contiguous bytes (an interleaved plane may be [rows, cw, 2]); the row
     stride is the pitch.  Nothing is copied: a plane whose bytes within a row are not contiguous is refused."""
     a = np.asarray(a)
+    if wide and a.dtype == np.dtype("<u2"):         # 16-bit samples: the same rows as bytes
+        if a.ndim == 3 and a.shape[2] == 2 and a.strides[1:] == (4, 2):
+            a = np.lib.stride_tricks.as_strided(a, (a.shape[0], a.shape[1] * 2), (a.strides[0], 2), writeable=False)
+        if a.ndim != 2 or (a.shape[1] > 1 and a.strides[1] != 2):
+            raise ValueError(f"{name} plane: the samples of a row must be contiguous (shape {a.shape}, strides {a.strides})")
+        a = np.lib.stride_tricks.as_strided(a, (a.shape[0], a.shape[1]), (a.strides[0], 2), writeable=False).view(np.uint8)
     if a.dtype != np.uint8:
-        raise ValueError(f"{name} plane must be uint8, got {a.dtype}")
+        raise ValueError(f"{name} plane must be {'uint16 (or uint8 bytes)' if wide else 'uint8'}, got {a.dtype}")
     if a.ndim == 3 and a.shape[2] == 2 and a.strides[1:] == (2, 1):
         a = np.lib.stride_tricks.as_strided(a, (a.shape[0], a.shape[1] * 2), (a.strides[0], 1), writeable=False)
     if a.ndim != 2 or a.shape != (rows, row_bytes):
@@ -60,12 +94,36 @@ def _plane(a, rows: int, row_bytes: int, name: str) -> np.ndarray:
     return a
 
 
-def _device_plane(a, rows: int, row_bytes: int, name: str) -> "_lib.DeviceView":
+def _device_bytes(a, what: str, wide: bool) -> "_lib.DeviceView":
+    """`_lib.device_view`, which takes uint8; for a 16-bit frame also a `<u2` device array, as the same rows of bytes."""
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if not (wide and isinstance(cai, dict) and cai.get("typestr") in ("<u2", "=u2") and "shape" in cai and "data" in cai):
+        return _lib.device_view(a, what)
+    shape = tuple(int(v) for v in cai["shape"])
+    strides = cai.get("strides")
+    if strides is None:
+        strides, acc = [], 2
+        for n in reversed(shape):
+            strides.append(acc)
+            acc *= n
+        strides = tuple(reversed(strides))
+    strides = tuple(int(v) for v in strides)
+    if len(shape) < 1 or len(strides) != len(shape) or any(v < 0 for v in strides) or (shape[-1] > 1 and strides[-1] != 2):
+        raise ValueError(f"{what}: the samples of a row must be contiguous (shape {shape}, strides {strides})")
+    ptr = cai["data"][0]
+    if not ptr and all(shape):
+        raise ValueError(f"{what}: NULL device pointer")
+    return _lib.DeviceView(int(ptr or 0), shape[:-1] + (shape[-1] * 2,), strides[:-1] + (1,), a)
+
+
+def _device_plane(a, rows: int, row_bytes: int, name: str, wide: bool = False) -> "_lib.DeviceView":
     """`_plane` for a plane in device memory: the same shapes and stride rules, read from `__cuda_array_interface__`."""
-    v = _lib.device_view(a, f"{name} plane")
+    v = _device_bytes(a, f"{name} plane", wide)
     shape, strides = v.shape, v.strides
     if len(shape) == 3 and shape[2] == 2 and strides[1:] == (2, 1):
         shape, strides = (shape[0], shape[1] * 2), (strides[0], 1)
+    if len(shape) == 3 and shape[2] == 4 and strides[1:] == (4, 1):      # (an interleaved plane of 16-bit samples as [ch, cw, 2])
+        shape, strides = (shape[0], shape[1] * 4), (strides[0], 1)
     if len(shape) != 2 or shape != (rows, row_bytes):
         raise ValueError(f"{name} plane must be uint8 [{rows},{row_bytes}], got shape {v.shape}")
     if row_bytes > 1 and strides[1] != 1:
@@ -95,22 +153,35 @@ class YUVFrame:
     4 * ((w + 1) // 2) bytes (Y0 U Y1 V, or U Y0 V Y1, per pixel pair; every row has its own chroma); for even w it may be handed
     in as [h, w, 2]."""
 
-    def __init__(self, planes, format, matrix, h: int, w: int, _writable=None):
-        self.format = _code(FORMATS, format, "format")
-        self.matrix = _code(MATRICES, matrix, "matrix")
+    def __init__(self, planes, format, matrix, h: int, w: int, _writable=None, container=None, shift: int = 0):
+        # without `container` the constructor takes what it always took: the four formats and three matrices of whenet_yuv_frame_t;
+        # with it (8 or 16) also planar 4:4:4 and BT.2020 (include/whenet_hip_yuv_ext.h)
+        ext = container is not None
+        self.format = _code(LAYOUTS if ext else FORMATS, format, "format")
+        self.matrix = _code(MATRICES_EXT if ext else MATRICES, matrix, "matrix")
+        self.container, self.shift = int(container) if ext else 8, int(shift)
+        if self.container not in (8, 16):
+            raise ValueError(f"unknown container {container!r}: 8 or 16 bits per stored sample")
+        if not 0 <= self.shift <= 8 or (self.shift and self.container == 8):
+            raise ValueError(f"shift {self.shift} with a container of {self.container} bits: 0..8 for 16-bit samples, 0 for 8-bit ones")
+        if self.format in PACKED and self.container != 8:
+            raise ValueError(f"{_NAMES_EXT[self.format]} has an 8-bit container (Y210 / Y216 are not built)")
+        wide, bs = self.container == 16, self.container // 8
         self.h, self.w = int(h), int(w)
         if not (1 <= self.h <= MAX_SIDE and 1 <= self.w <= MAX_SIDE):
             raise ValueError(f"frame is {self.h} x {self.w}: sides must be 1..{MAX_SIDE}")
         ch, cw = (self.h + 1) // 2, (self.w + 1) // 2
         if self.format in PACKED:
-            shapes = [(self.h, 4 * cw, _NAMES[self.format])]
+            shapes = [(self.h, 4 * cw, _NAMES_EXT[self.format])]
         elif self.format == _lib.YUV_NV12:
-            shapes = [(self.h, self.w, "Y"), (ch, 2 * cw, "UV")]
+            shapes = [(self.h, self.w * bs, "Y"), (ch, 2 * cw * bs, "UV")]
+        elif self.format == I444:
+            shapes = [(self.h, self.w * bs, "Y"), (self.h, self.w * bs, "U"), (self.h, self.w * bs, "V")]
         else:
-            shapes = [(self.h, self.w, "Y"), (ch, cw, "U"), (ch, cw, "V")]
+            shapes = [(self.h, self.w * bs, "Y"), (ch, cw * bs, "U"), (ch, cw * bs, "V")]
         planes = list(planes)
         if len(planes) != len(shapes):
-            raise ValueError(f"{_NAMES[self.format]} has {len(shapes)} plane{'s' if len(shapes) > 1 else ''}, got {len(planes)}")
+            raise ValueError(f"{_NAMES_EXT[self.format]} has {len(shapes)} plane{'s' if len(shapes) > 1 else ''}, got {len(planes)}")
         on_device = [_lib.is_device_array(a) for a in planes]
         if any(on_device) and not all(on_device):
             raise ValueError("the planes of a frame are all in device memory or all in host memory, got " +
@@ -120,11 +191,21 @@ class YUVFrame:
         # they were handed in -- the views kept in `planes` are read-only whatever their memory is
         self.writable = bool(_writable) if _writable is not None else all(_array_writable(a) for a in planes)
         if self.on_device:
-            self.planes = tuple(_device_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
+            self.planes = tuple(_device_plane(a, r, b, n, wide) for a, (r, b, n) in zip(planes, shapes))
         else:
-            self.planes = tuple(_plane(a, r, b, n) for a, (r, b, n) in zip(planes, shapes))
+            self.planes = tuple(_plane(a, r, b, n, wide) for a, (r, b, n) in zip(planes, shapes))
         # a plane of one row has no row stride of its own: its pitch is its row
         self.pitches = tuple(int(a.strides[0]) if a.shape[0] > 1 else int(a.shape[1]) for a in self.planes)
+        if wide:
+            for (_, _, n), a, p in zip(shapes, self.planes, self.pitches):
+                if (a.ptr if self.on_device else a.ctypes.data) & 1 or p & 1:
+                    raise ValueError(f"{n} plane: 16-bit samples lie at an even address with an even pitch (pitch {p})")
+
+    @property
+    def needs_ext(self) -> bool:
+        """Whether whenet_yuv_frame_t cannot describe this frame: a 16-bit container, planar 4:4:4 or BT.2020 (then the calls of
+        include/whenet_hip_yuv_ext.h take it, and `descriptor()` is their struct)."""
+        return self.container != 8 or self.format == I444 or self.matrix == _lib.YUV_BT2020
 
     @classmethod
     def nv12(cls, y, uv, matrix="bt601") -> "YUVFrame":
@@ -137,6 +218,33 @@ class YUVFrame:
         """Y uint8 [h,w], U and V uint8 [ch,cw]."""
         h, w = cls._luma_size(y)
         return cls((y, u, v), _lib.YUV_I420, matrix, h, w)
+
+    @classmethod
+    def p010(cls, y, uv, matrix="bt709") -> "YUVFrame":
+        """P010 (and P012): Y uint16 [h,w] and the interleaved chroma plane uint16 [ch, 2 cw] (or [ch, cw, 2]), the sample in the
+        HIGH bits of every word; or the same planes as uint8 bytes [h, 2 w] / [ch, 4 cw].  The low bits are used as they are."""
+        h, w = cls._luma_size(y, 16)
+        return cls((y, uv), _lib.YUV_NV12, matrix, h, w, container=16, shift=0)
+
+    p016 = p010      # one layout: all 16 bits are the sample
+
+    @classmethod
+    def i010(cls, y, u, v, depth=10, matrix="bt709") -> "YUVFrame":
+        """I010 / yuv420p10le (depth=10), yuv420p12le (12) or 16-bit planes (16): Y uint16 [h,w], U and V uint16 [ch,cw], the
+        sample in the LOW `depth` bits of every word (bits above them are masked off); or the planes as uint8 bytes."""
+        if depth not in range(8, 17):
+            raise ValueError(f"depth {depth!r}: 8..16 bits in a 16-bit word")
+        h, w = cls._luma_size(y, 16)
+        return cls((y, u, v), _lib.YUV_I420, matrix, h, w, container=16, shift=16 - int(depth))
+
+    @classmethod
+    def i444(cls, y, u, v, matrix="bt601", shift=0) -> "YUVFrame":
+        """Planar 4:4:4: Y, U, V all [h,w], uint8 (I444, a decoder's YUV444 surface) or uint16 (its 16-bit twin, `shift` as for
+        every 16-bit container: 0 for MSB-aligned samples, 6 for yuv444p10le)."""
+        first = y.__cuda_array_interface__["typestr"] if _lib.is_device_array(y) else np.asarray(y).dtype.str
+        bits = 16 if first in ("<u2", "=u2") else 8
+        h, w = cls._luma_size(y, bits)
+        return cls((y, u, v), I444, matrix, h, w, container=bits, shift=shift)
 
     @classmethod
     def yuyv(cls, buf, matrix="bt601", w=None) -> "YUVFrame":
@@ -164,11 +272,17 @@ class YUVFrame:
         return cls((buf,), fmt, matrix, int(shape[0]), w)
 
     @staticmethod
-    def _luma_size(y):
-        shape = tuple(y.__cuda_array_interface__["shape"]) if _lib.is_device_array(y) else np.asarray(y).shape
+    def _luma_size(y, bits=8):
+        dev = _lib.is_device_array(y)
+        shape = tuple(y.__cuda_array_interface__["shape"]) if dev else np.asarray(y).shape
         if len(shape) != 2:
-            raise ValueError(f"Y plane must be uint8 [h,w], got shape {shape}")
-        return int(shape[0]), int(shape[1])
+            raise ValueError(f"Y plane must be uint{bits} [h,w], got shape {shape}")
+        h, w = int(shape[0]), int(shape[1])
+        if bits == 16 and (y.__cuda_array_interface__["typestr"] if dev else np.asarray(y).dtype.str) in ("|u1", "<u1", "=u1"):
+            if w % 2:
+                raise ValueError(f"Y plane: a row of 16-bit samples handed in as bytes is even, got {w} bytes")
+            w //= 2
+        return h, w
 
     @classmethod
     def from_buffer(cls, buf, h: int, w: int, format="nv12", pitch=None, matrix="bt601") -> "YUVFrame":
@@ -178,6 +292,8 @@ class YUVFrame:
         tight: every row is followed by the next.  `buf` is anything with
         the buffer interface (bytes, a memoryview, a uint8 array), or a contiguous uint8 DEVICE array (the decoder's surface in
         device memory: the frame is then `on_device`); it is not copied."""
+        if isinstance(format, str) and format.lower() in FORMATS_EXT:
+            return cls._from_buffer_ext(buf, int(h), int(w), format.lower(), pitch, matrix)
         fmt = _code(FORMATS, format, "format")
         h, w = int(h), int(w)
         if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
@@ -233,8 +349,76 @@ class YUVFrame:
             planes.append(view(pitch * h + i * cpitch * ch, ch, crow, cpitch))
         return cls(planes, fmt, matrix, h, w, _writable=writable)
 
-    def descriptor(self) -> "_lib.YuvFrameC":
-        """The whenet_yuv_frame_t of this frame (it points into the planes: keep the frame alive while it is used)."""
+    @classmethod
+    def _from_buffer_ext(cls, buf, h, w, name, pitch, matrix):
+        """`from_buffer` for the names of FORMATS_EXT.  `pitch` is in BYTES: the luma rows' and, NV12-like, the interleaved rows';
+        I420-like chroma rows lie at the even pitch 2 * ceil(pitch / 4) (8-bit: (pitch + 1) // 2); every 4:4:4 plane at `pitch`."""
+        layout, bits, shift = FORMATS_EXT[name]
+        bs = bits // 8
+        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+            raise ValueError(f"frame is {h} x {w}: sides must be 1..{MAX_SIDE}")
+        writable = _array_writable(buf) if _lib.is_device_array(buf) or isinstance(buf, np.ndarray) else not memoryview(buf).readonly
+        dev = a = None
+        if _lib.is_device_array(buf):
+            dev = _device_bytes(buf, "buffer", bits == 16)
+            size, acc = int(np.prod(dev.shape, dtype=np.int64)), 1
+            for n, st in zip(reversed(dev.shape), reversed(dev.strides)):
+                if n > 1 and st != acc:
+                    raise ValueError("buffer must be contiguous")
+                acc *= n
+        else:
+            a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else buf
+            if not a.flags.c_contiguous:
+                raise ValueError("buffer must be contiguous")
+            if a.dtype == np.dtype("<u2") and bits == 16:
+                a = a.reshape(-1).view(np.uint8)
+            if a.dtype != np.uint8:
+                raise ValueError(f"buffer must hold uint8{' or uint16' if bits == 16 else ''}, got {a.dtype}")
+            a = a.reshape(-1)
+            size = a.size
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        row = w * bs
+        if layout == I444:
+            crow, crows, nchroma = row, h, 2
+        elif layout == _lib.YUV_NV12:
+            crow, crows, nchroma = 2 * cw * bs, ch, 1
+        else:
+            crow, crows, nchroma = cw * bs, ch, 2
+        if pitch is None:
+            pitch, cpitch = row, crow
+        else:
+            pitch = int(pitch)
+            cpitch = pitch if layout != _lib.YUV_I420 else ((pitch + 1) // 2 if bs == 1 else 2 * ((pitch + 3) // 4))
+        if pitch < row or cpitch < crow:
+            raise ValueError(f"pitch {pitch} is below a row of the {h} x {w} frame ({row} bytes)")
+        if bs == 2 and pitch % 2:
+            raise ValueError(f"pitch {pitch}: the rows of 16-bit samples lie an even number of bytes apart")
+        need = pitch * h + (nchroma * crows - 1) * cpitch + crow
+        if size < need:
+            raise ValueError(f"buffer holds {size} bytes, the frame needs {need} in format {name}")
+
+        def view(off, rows, row_bytes, p):
+            if dev is not None:
+                return _lib.DeviceView(dev.ptr + off, (rows, row_bytes), (p, 1), dev.owner)
+            return np.lib.stride_tricks.as_strided(a[off:], (rows, row_bytes), (p, 1), writeable=False)
+
+        planes = [view(0, h, row, pitch)] + [view(pitch * h + i * cpitch * crows, crows, crow, cpitch) for i in range(nchroma)]
+        return cls(planes, layout, matrix, h, w, _writable=writable, container=bits, shift=shift)
+
+    def descriptor_ext(self) -> "_lib.YuvxFrameC":
+        """The whenet_yuvx_frame_t of this frame, whatever its format (it points into the planes: keep the frame alive)."""
+        d = _lib.YuvxFrameC()
+        for i, (a, p) in enumerate(zip(self.planes, self.pitches)):
+            d.plane[i] = a.ptr if self.on_device else a.ctypes.data
+            d.pitch[i] = p
+        d.layout, d.container, d.shift, d.matrix, d.h, d.w = self.format, self.container, self.shift, self.matrix, self.h, self.w
+        return d
+
+    def descriptor(self):
+        """The whenet_yuv_frame_t of this frame (it points into the planes: keep the frame alive while it is used); the
+        whenet_yuvx_frame_t (`descriptor_ext()`) of a frame that `needs_ext`."""
+        if self.needs_ext:
+            return self.descriptor_ext()
         d = _lib.YuvFrameC()
         for i, (a, p) in enumerate(zip(self.planes, self.pitches)):
             d.plane[i] = a.ptr if self.on_device else a.ctypes.data
@@ -247,4 +431,6 @@ class YUVFrame:
         if self.on_device:
             raise ValueError("to_bgr() runs on the host and this frame's planes are in device memory: Handle.op_yuv_to_bgr_device([frame]) "
                              "converts them on the device")
+        if self.needs_ext:
+            return _lib.yuvx_to_bgr_host(self.descriptor_ext())
         return _lib.yuv_to_bgr_host(self.descriptor())
